@@ -26,6 +26,13 @@ What the timed window holds is reported, not assumed: `config.workload` is built
 inside it.  A window shorter than an epoch (the driver's --steps 20) is placed in the MIDDLE of the second
 epoch -- after one whole untimed epoch including its optimiser step, on trees of half-epoch size -- instead of
 on the freshly reset trees of call 0, and says so.
+
+A plain run sets up, warms up, times the --steps calls and prints the line (figures derived from the timed run's own
+counters included).  What takes work of its own -- the CPU baseline, the best-cost run, the launch-by-launch kernel timing of
+the per-call forms -- runs with --full only; without it those fields are null.  --dump-outputs DIR writes what the timed path
+computed in its last call (state vectors and predictions of the agents, the argmin, a sample of the trees, the model's
+parameters, the losses of the epoch boundaries inside the window) as DIR/<name>.npy; the inputs are seeded, so two builds can be
+compared array by array.
 """
 import argparse
 import json
@@ -194,6 +201,51 @@ def best_cost_run(az, wl, hidden, B, mlp_dtype, max_epochs, goal=5.2):
     return out
 
 
+# --dump-outputs stays under 64 MB: rows <= 16 MB, 8 trees' nodes <= 16 MB (65536 nodes each), predictions and parameters with
+# their indices <= 12 MB each
+DUMP_ROW_BYTES = 16 << 20    # state vectors + predictions of the agents, at most this many bytes of rows
+DUMP_TREES = 8               # agents whose trees are written
+DUMP_TREE_PREDS = 1 << 20    # prediction entries of those trees, at most
+DUMP_PARAMS = 1 << 20        # model parameters, at most
+
+
+def _seeded_subset(n, k):
+    """sorted indices of a fixed sample of k of range(n) (all of them when k >= n)"""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(out_dir, opt, model, global_argmin, losses):
+    """What the timed path computed in its last call, as the caller of that path receives it, written as float32 / float64 .npy
+    files (64 MB in all at most: larger outputs are a fixed, seeded sample, the indices beside them)."""
+    os.makedirs(out_dir, exist_ok=True)
+    sv, h = opt.state_vecs(), opt.predictions()
+    rows = _seeded_subset(opt.batch, max(1, DUMP_ROW_BYTES // (sv.shape[1] * 4 + h.shape[1] * 4)))
+    trees = [opt.get_tree(int(i)) for i in rows[_seeded_subset(rows.size, DUMP_TREES)]]
+    tree_preds = np.concatenate([t.p_g for t in trees]).astype(np.float32)
+    pred_idx = _seeded_subset(tree_preds.size, DUMP_TREE_PREDS)
+    params = model.get_params()
+    param_idx = _seeded_subset(params.size, DUMP_PARAMS)
+    arrays = {
+        "agent_rows": rows.astype(np.float64),
+        "state_vecs": sv[rows].astype(np.float32),
+        "predictions": h[rows].astype(np.float32),
+        "argmin_eval_cost": np.array(global_argmin, np.float64),
+        "epoch_losses": np.array(losses, np.float64),
+        # per node of the sampled trees, in the order the tree holds them: c, c_star, n_t, exhausted
+        "tree_nodes": np.concatenate([np.stack([t.c, t.c_star, t.n_t, t.exhausted], axis=1).astype(np.float64) for t in trees]),
+        "tree_sizes": np.array([[t.c.size, t.e_src.size, t.p_g.size] for t in trees], np.float64),
+        "tree_prediction_g": tree_preds[pred_idx],
+        "tree_prediction_index": pred_idx.astype(np.float64),
+        "model_params": params[param_idx].astype(np.float32),
+        "model_param_index": param_idx.astype(np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 # BASELINE.json configs[] are quoted at fixed GPU counts: which of them a run IS, and which it only shares the per-GPU shape with
 BASELINE_GPUS = {"A": (0, None), "B": (1, 1), "C": (2, 8), "D": (3, 4), "E": (4, 8), "E612": (4, 8)}
 
@@ -261,11 +313,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1600)
     ap.add_argument("--warmup", type=int, default=800)
-    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="CPU time budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes work of its own: the CPU baseline, the best-cost run, and the launch-by-launch kernel "
+                         "timing of the per-call step forms (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last call as DIR/<name>.npy (float32 / float64, seeded inputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="--full: CPU time budget of the cpu_baseline leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg and the best-cost run")
     ap.add_argument("--best-cost-epochs", type=int, default=120,
-                    help="c21 workloads at N = 1: after the timed region, run the reference driver's loop for at most this many epochs "
-                         "(until lambda_1 + mu < 5.2) and a frozen-model control beside it (0: skip)")
+                    help="--full, c21 workloads at N = 1: after the timed region, run the reference driver's loop for at most this many "
+                         "epochs (until lambda_1 + mu < 5.2) and a frozen-model control beside it (0: skip)")
     ap.add_argument("--chunk", type=int, default=800, help="calls per host round trip (<= one epoch)")
     ap.add_argument("--barrier-step", action="store_true", help="lock-step form (k_persist) instead of the default asynchronous step (k_async)")
     ap.add_argument("--step", choices=["async", "barrier", "pool"], default=None,
@@ -283,6 +340,8 @@ def main():
     ap.add_argument("--mlp-dtype", choices=["f32", "bf16"], default=None,
                     help="evaluator weight/activation storage for inference (bf16 = BASELINE configs[2]; f32 accumulate either way)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     wl_name, agents, dtype = CONFIGS[args.config or "B"]
     if args.workload:
         wl_name = args.workload
@@ -430,14 +489,20 @@ def main():
     c1 = opt.counters()
     n_bound = boundaries - b0
     form, form_why = opt.step_form()
+    if args.dump_outputs:  # before anything below runs a call of its own
+        best = sopt.global_argmin()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, opt, sopt.shard.model, best, losses[len(losses) - n_bound:])
     timing_note = None
-    if per_call:
+    if per_call and args.full:
         k = min(20, EPOCH_CALLS - calls_done % EPOCH_CALLS - 1)
         if k > 0:
             opt.set_timing(True)
             sopt.par_roll_out_episodes(TOL, n_calls=k)
             calls_done += k
             timing_note = "kernel durations from %d extra calls timed launch by launch after the timed region (which replays a hipGraph)" % k
+    elif per_call:
+        timing_note = "kernel durations not measured: the per-call forms time them in extra calls of their own, with --full"
     timing = opt.timing()
     opt.set_timing(False)
     if c1["FAILED"] != 0:
@@ -658,8 +723,9 @@ def main():
                                               "note": "a batch streams the model's weights once through its CU; measured with a vector-ALU consumer as well "
                                                       "(no MFMA issue at all): the same ~21-25 B per clock under this kernel's load"}
         out["best_cost_run"] = (best_cost_run(az, wl, HIDDEN, AGENTS_PER_GPU, mlp_dtype, args.best_cost_epochs)
-                                if (world == 1 and wl["kind"] == "c21" and mlp_dtype and args.best_cost_epochs > 0 and not args.no_cpu_baseline) else None)
-        if not args.no_cpu_baseline and world == 1:  # timed beside the GPU run at N = 1 only
+                                if (args.full and world == 1 and wl["kind"] == "c21" and mlp_dtype and args.best_cost_epochs > 0
+                                    and not args.no_cpu_baseline) else None)
+        if args.full and not args.no_cpu_baseline and world == 1:  # timed beside the GPU run at N = 1 only
             out["cpu_baseline"] = cpu_baseline(min(os.cpu_count() or 1, 64), wl, HIDDEN, space.default_permitted_range(), args.cpu_seconds)
         else:
             out["cpu_baseline"] = None

@@ -1,10 +1,12 @@
 """bench.py end to end on the GPU at reduced sizes: the contract line (metric, value, roofline, cpu_baseline, step form) of the
-default workload inside the driver's short window, and of BASELINE configs[4] on its CU-resident form."""
+default workload inside the driver's short window, and of BASELINE configs[4] on its CU-resident form; a plain run's line and
+the outputs it dumps."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +22,7 @@ def bench(*args):
 
 
 def test_bench_line_of_the_default_workload_in_the_drivers_window():
-    j = bench("--steps", "20", "--warmup", "5", "--agents", "512", "--cpu-seconds", "2")
+    j = bench("--steps", "20", "--warmup", "5", "--agents", "512", "--cpu-seconds", "2", "--full")
     assert j["metric"] == "node_expansions_per_s" and j["unit"] == "expansions/s" and j["n_gpus"] == 1 and j["steps"] == 20 and j["warmup"] == 5
     assert j["higher_is_better"] is True and j["scaling"] == "weak" and j["vs_baseline"] is None and j["data"] == "synthetic"
     assert j["value"] > 1e5 and abs(j["ms_per_step"] * 1e-3 * j["value"] - j["expansions"] / 20) < 1e-6 * j["expansions"]
@@ -70,3 +72,23 @@ def test_bench_gpus_2_launches_itself_on_a_one_gpu_box():
     assert j["replicas_identical"] is True and j["epoch_boundaries_in_timed_region"] >= 1 and j["epoch_exchange"]["count"] >= 1
     assert j["dtype"] == "bf16" and j["config"]["baseline_config"] == "C" and "quoted at 8 GPUs" in j["config"]["baseline_config_note"]
     assert j["value"] > 1e5 and j["cpu_baseline"] is None
+
+
+def test_plain_run_times_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run measures the headline only (no CPU baseline, no best-cost run); --dump-outputs writes the last timed call's
+    outputs as float .npy files under 64 MB, and the seeded inputs make a second run write the same arrays."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        j = bench("--steps", "20", "--warmup", "5", "--agents", "512", "--dump-outputs", str(d))
+        assert j["metric"] == "node_expansions_per_s" and j["steps"] == 20 and j["ms_per_step"] > 0
+        assert j["cpu_baseline"] is None and j["best_cost_run"] is None
+        files = sorted(p.name for p in d.iterdir())
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["state_vecs.npy"].shape[0] == 512 and arrays["tree_nodes.npy"].shape[0] > 0
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

@@ -16,14 +16,14 @@ for part in insts phases; do
   fi
 done
 if has bench; then
-  timeout -k 10 300 python bench.py > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log | cut -c1-140
+  timeout -k 10 300 python bench.py --full > $O/bench_default.log 2>&1; tail -1 $O/bench_default.log | cut -c1-140
   timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver20.log 2>&1
   timeout -k 10 200 python bench.py --no-cpu-baseline --step async > $O/bench_B_async.log 2>&1
   for cfg in A C D; do timeout -k 10 300 python bench.py --no-cpu-baseline --config $cfg > $O/bench_$cfg.log 2>&1; done
   AZD_POOL_EVAL_GROUP=0 timeout -k 10 300 python bench.py --no-cpu-baseline --config A > $O/bench_A_classic.log 2>&1
   timeout -k 10 300 python bench.py --no-cpu-baseline --agents 8192 > $O/bench_B8192.log 2>&1
-  timeout -k 10 400 python bench.py --config E --steps 400 --warmup 50 > $O/bench_E.log 2>&1
-  AZD_DENSE_NO_POOL=1 timeout -k 10 400 python bench.py --config E --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_E_per_call.log 2>&1
+  timeout -k 10 400 python bench.py --full --config E --steps 400 --warmup 50 > $O/bench_E.log 2>&1
+  AZD_DENSE_NO_POOL=1 timeout -k 10 400 python bench.py --full --config E --steps 400 --warmup 50 --no-cpu-baseline > $O/bench_E_per_call.log 2>&1
   timeout -k 10 400 python bench.py --config E --no-cpu-baseline > $O/bench_E_epochs.log 2>&1
   timeout -k 10 400 python bench.py --config E612 --steps 200 --warmup 50 --no-cpu-baseline > $O/bench_E612.log 2>&1
   timeout -k 10 400 python bench.py --config E612 --no-cpu-baseline > $O/bench_E612_epochs.log 2>&1
