@@ -621,6 +621,17 @@ int azd_evaluator_update_model_dev(azd_evaluator *ev, int batch, const float *d_
     AZD_HIP(hipSetDevice(ev->device));
     return ev->update_model_dev(batch, d_states, d_observations, d_action_weights, loss, (hipStream_t)stream);
 }
+int azd_debug_mlp_gradients(azd_evaluator *ev, int batch, const float *states, const float *observations, const float *action_weights,
+                            float *grads_out, float *loss) {
+    if (!ev || batch <= 0 || !states || !observations || !action_weights || !grads_out) return AZD_ERR_INVALID_ARGUMENT;
+    int st = ev->ensure_staging(batch);
+    if (st) return st;
+    size_t sb = (size_t)batch * ev->state_dim * 4, pb = (size_t)batch * ev->action_dim * 4;
+    AZD_HIP(hipMemcpyAsync(ev->d_states, states, sb, hipMemcpyHostToDevice, ev->own_stream));
+    AZD_HIP(hipMemcpyAsync(ev->d_obs, observations, pb, hipMemcpyHostToDevice, ev->own_stream));
+    AZD_HIP(hipMemcpyAsync(ev->d_w, action_weights, pb, hipMemcpyHostToDevice, ev->own_stream));
+    return ev->debug_gradients(batch, ev->d_states, ev->d_obs, ev->d_w, grads_out, loss, ev->own_stream);
+}
 int azd_debug_hash_stream_via_evaluators(azd_evaluator *ev, int on) { return ev ? ev->debug_serve_from_pool(on) : AZD_ERR_INVALID_ARGUMENT; }
 int azd_evaluator_set_weight_storage(azd_evaluator *ev, int dtype) { return ev ? ev->set_weight_storage(dtype) : AZD_ERR_INVALID_ARGUMENT; }
 int64_t azd_evaluator_num_params(azd_evaluator *ev) { return ev ? ev->num_params() : 0; }

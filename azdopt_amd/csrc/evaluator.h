@@ -72,6 +72,9 @@ struct azd_evaluator {
     virtual int set_params(const float *) { return AZD_ERR_UNSUPPORTED; }
     virtual int set_weight_storage(int) { return AZD_ERR_UNSUPPORTED; }
     virtual int debug_serve_from_pool(int) { return AZD_ERR_UNSUPPORTED; } // hash stream only (azd_debug_hash_stream_via_evaluators)
+    // the training step's gradient without the optimiser step (azd_debug_mlp_gradients): grads_out and *loss are host memory,
+    // valid on return; parameters and optimiser state stay as they are
+    virtual int debug_gradients(int, const float *, const float *, const float *, float *, float *, hipStream_t) { return AZD_ERR_UNSUPPORTED; }
     int ensure_staging(int batch);
 };
 

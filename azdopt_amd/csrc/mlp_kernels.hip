@@ -658,9 +658,16 @@ struct MlpEvaluator : azd_evaluator {
         return AZD_OK;
     }
 
-    // dfdx.rs:86-131
+    // dfdx.rs:86-131: the gradient of the weighted loss into d_grads (loss into d_scalars[1]), then the Adam step
     int update_model_dev(int batch, const float *d_s, const float *d_o, const float *d_w, float *loss, hipStream_t st) override {
         AZD_HIP(hipSetDevice(device));
+        int s = gradients(batch, d_s, d_o, d_w, st);
+        if (s) return s;
+        return adam_step(loss, st);
+    }
+    // forward on the f32 master weights, weight sum, loss and head delta, backward into d_grads (flat, get_params layout);
+    // the parameters, m, v and t are left as they are
+    int gradients(int batch, const float *d_s, const float *d_o, const float *d_w, hipStream_t st) {
         int s = ensure_batch(batch);
         if (s) return s;
         s = forward(batch, d_s, d_pred_train, st);
@@ -697,6 +704,11 @@ struct MlpEvaluator : azd_evaluator {
                 dx = tmp;
             }
         }
+        AZD_HIP(hipGetLastError());
+        return AZD_OK;
+    }
+    // Adam with L2 on d_grads; *loss (host) = the loss of the gradients() call before it
+    int adam_step(float *loss, hipStream_t st) {
         t += 1;
         float bc1 = 1.0f - std::pow(adam.beta1, (float)t), bc2 = 1.0f - std::pow(adam.beta2, (float)t);
         k_adam<<<(unsigned)((n_params + 255) / 256), 256, 0, st>>>(d_params, d_grads, d_m, d_v, (size_t)n_params, adam.lr, adam.beta1,
@@ -704,6 +716,16 @@ struct MlpEvaluator : azd_evaluator {
         if (bf16) requantize(st);
         repack(st);
         AZD_HIP(hipGetLastError());
+        AZD_HIP(hipMemcpyAsync(h_scalars, d_scalars, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+        AZD_HIP(hipStreamSynchronize(st));
+        if (loss) *loss = h_scalars[1];
+        return AZD_OK;
+    }
+    int debug_gradients(int batch, const float *d_s, const float *d_o, const float *d_w, float *grads_out, float *loss, hipStream_t st) override {
+        AZD_HIP(hipSetDevice(device));
+        int s = gradients(batch, d_s, d_o, d_w, st);
+        if (s) return s;
+        AZD_HIP(hipMemcpyAsync(grads_out, d_grads, (size_t)n_params * 4, hipMemcpyDeviceToHost, st));
         AZD_HIP(hipMemcpyAsync(h_scalars, d_scalars, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
         AZD_HIP(hipStreamSynchronize(st));
         if (loss) *loss = h_scalars[1];

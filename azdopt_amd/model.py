@@ -103,6 +103,19 @@ class ActionModel(NablaModel):
         _lib.check(_lib.lib().azd_evaluator_get_params(self._h, _lib.ptr(out)), "get_params")
         return out
 
+    def debug_gradients(self, states, observations, action_weights):
+        """(flat gradient in the get_params layout, loss) of update_model's step on these rows, without the Adam step:
+        parameters and optimiser state are left untouched"""
+        states = np.ascontiguousarray(states, np.float32).reshape(-1, self.state_dim)
+        obs = np.ascontiguousarray(observations, np.float32)
+        w = np.ascontiguousarray(action_weights, np.float32)
+        assert obs.size == w.size == states.shape[0] * self.action_dim
+        g = np.zeros(self.num_params(), np.float32)
+        loss = C.c_float()
+        _lib.check(_lib.lib().azd_debug_mlp_gradients(self._h, states.shape[0], _lib.ptr(states), _lib.ptr(obs), _lib.ptr(w),
+                                                      _lib.ptr(g), C.byref(loss)), "azd_debug_mlp_gradients")
+        return g, loss.value
+
     def set_params(self, p):
         p = np.ascontiguousarray(p, np.float32)
         assert p.size == self.num_params()

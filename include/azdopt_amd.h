@@ -476,6 +476,12 @@ int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks);
  * same harness: AZD_POOL_DEBUG_ABORT_CALL=k (agent 0 raises the launch's abort flag after its k-th call: the take-over by the
  * asynchronous step), AZD_POOL_MAX_RESIDENT=w (pretend the device holds w workgroups of the pool kernel at once). */
 int azd_debug_hash_stream_via_evaluators(azd_evaluator *ev, int on);
+/* The MLP evaluator's training gradient without the optimiser step (tests against a float64 reference): the same launches
+ * as azd_evaluator_update_model up to the Adam step, on host rows staged like that call's.  grads_out: num_params floats in
+ * the get_params layout; *loss as update_model reports it.  Parameters, Adam moments and the step count are left untouched.
+ * AZD_ERR_UNSUPPORTED for evaluators other than the MLP. */
+int azd_debug_mlp_gradients(azd_evaluator *ev, int batch, const float *states, const float *observations,
+                            const float *action_weights, float *grads_out, float *loss);
 
 /* Parity probe for the two f32 primitives the selection rule (tree/next_action.rs:70,81) depends
  * on bit-for-bit.  in: 2*n floats (pairs x, y); out: 4*n floats per pair:
