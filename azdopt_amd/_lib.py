@@ -24,6 +24,8 @@ ENGINE_POOL_STEP = 8
 SPACE_C21 = 1
 SPACE_RAMSEY = 2
 SPACE_DENSE = 3
+RAMSEY_MAX_N = 23       # AZD_RAMSEY_MAX_N
+RAMSEY_WIDE_MAX_N = 32  # AZD_RAMSEY_WIDE_MAX_N: a wide Ramsey engine (EngineConfig.max_slots > 0)
 PATH_SET, PATH_SEQUENCE = 0, 1
 
 
@@ -50,6 +52,11 @@ class EngineConfig(C.Structure):
 
 class RamseyArgmin(C.Structure):  # ArgminData<RamseyCountsNoRecolor, TotalCounts<C>>
     _fields_ = [("colors", C.c_uint8 * 256), ("permitted", C.c_uint64 * 4), ("totals", C.c_int32 * 4),
+                ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
+
+
+class RamseyWideArgmin(C.Structure):  # the same for any Ramsey engine, wide ones included (E <= 496)
+    _fields_ = [("colors", C.c_uint8 * 496), ("permitted", C.c_uint64 * 8), ("totals", C.c_int32 * 4),
                 ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
 
 
@@ -128,6 +135,7 @@ def lib():
     sig("azd_engine_pool_agent_finish", C.c_int, vp, vp)
     sig("azd_engine_pool_groups", C.c_int, vp, vp, vp, vp)
     sig("azd_engine_ramsey_argmin_data", C.c_int, vp, C.POINTER(RamseyArgmin))
+    sig("azd_engine_ramsey_wide_argmin_data", C.c_int, vp, C.POINTER(RamseyWideArgmin))
     sig("azd_engine_ramsey_agent_counts", C.c_int, vp, C.c_int, vp, vp)
     sig("azd_ramsey_state_dim", C.c_int, C.c_int, C.c_int)
     sig("azd_ramsey_action_dim", C.c_int, C.c_int, C.c_int)

@@ -182,11 +182,13 @@ struct azd_engine {
     int ext_depth = 2;
     hipEvent_t ext_done = nullptr, ext_fork = nullptr, ext_ring[EXT_STREAMS][EXT_IN_FLIGHT] = {};
     unsigned long long ext_iterations = 0; // evaluator graph replays of the last dense pool launch (diagnostics)
-    // dense-graph space: host-visible key width (action-id sets) and the packed roots as the device wants them
+    // dense-graph / Ramsey space: host-visible key width (action-id sets); a wide Ramsey engine's device keys are wider (zero-padded)
     int kw_host = 0;
+    int ramsey_slots = 0;             // Ramsey: the most permitted edges a root may bring (max_slots; else MAX_NODE_ACTIONS / (C - 1))
     int dense_slots = 0;              // 64 * a.KW: the most modifiable slots a root may bring
     uint64_t *d_stage_slots = nullptr; // device root policy: the slot masks it drew, [B][(E + 63) / 64]
     std::vector<uint64_t> dense_packed;
+    std::vector<uint64_t> ramsey_perm_pad; // a wide Ramsey engine's roots: permitted masks padded to the device's a.KW words
     // pool step (agents multiplexed over searcher waves, evaluator workgroups on CUs of their own)
     bool pool_step = false;
     azd::PoolArgs pool{};         // device pointers of the queues
@@ -226,6 +228,10 @@ struct azd_engine {
     uint32_t *h_win_flag = nullptr;          // pinned, host-coherent [log_calls]
     azd::ArgminRec *d_argmin_side = nullptr; // the argmin record as of a call inside the window (k_argmin_one)
     azd::RamseyArgminRec *d_argmin_r_side = nullptr;
+    // a wide Ramsey engine's kernels write azd::RamseyWideArgminRec where argmin_r points: records of the narrow type it spans
+    bool ramsey_wide() const { return a.space == azd::SPACE_RAMSEY && a.KW > azd::MAX_KW; }
+    size_t argmin_r_bytes() const { return ramsey_wide() ? sizeof(azd::RamseyWideArgminRec) : sizeof(azd::RamseyArgminRec); }
+    size_t argmin_r_recs() const { return (argmin_r_bytes() + sizeof(azd::RamseyArgminRec) - 1) / sizeof(azd::RamseyArgminRec); }
     float *d_pool = nullptr;      // pooled training triple of all ranks (azd_engine_par_update_model_sharded)
     size_t pool_rows = 0;
     int step_form = 0;            // AZD_STEP_* chosen by the last par_roll_out_episodes
@@ -405,7 +411,13 @@ int upload_roots(azd_engine *e, const uint8_t *parents, const uint64_t *permitte
     const Arenas &a = e->a;
     if (a.space == SPACE_DENSE) return upload_dense_roots(e, parents, permitted);
     if (a.space == SPACE_RAMSEY) {
-        // packed roots: colour of every edge in colex order (E bytes) + permitted edge positions
+        // packed roots: colour of every edge in colex order (E bytes) + permitted edge positions (kw_host words; a wide engine's
+        // device masks are a.KW words, zero-padded)
+        const int KWH = e->kw_host;
+        if (KWH != a.KW) {
+            e->ramsey_perm_pad.assign((size_t)a.B * a.KW, 0ull);
+            for (int i = 0; i < a.B; ++i) memcpy(&e->ramsey_perm_pad[(size_t)i * a.KW], permitted + (size_t)i * KWH, (size_t)KWH * 8);
+        }
         for (int i = 0; i < a.B; ++i) {
             const uint8_t *col = parents + (size_t)i * a.E;
             for (int x = 0; x < a.E; ++x)
@@ -414,8 +426,8 @@ int upload_roots(azd_engine *e, const uint8_t *parents, const uint64_t *permitte
                     return AZD_ERR_INVALID_ARGUMENT;
                 }
             int cnt = 0;
-            for (int w = 0; w < a.KW; ++w) {
-                uint64_t m = permitted[(size_t)i * a.KW + w];
+            for (int w = 0; w < KWH; ++w) {
+                uint64_t m = permitted[(size_t)i * KWH + w];
                 int hi = a.E - 64 * w;
                 if ((hi <= 0 && m != 0) || (hi > 0 && hi < 64 && (m >> hi) != 0)) {
                     g_last_error = "permitted mask has bits beyond the edge count";
@@ -423,13 +435,14 @@ int upload_roots(azd_engine *e, const uint8_t *parents, const uint64_t *permitte
                 }
                 cnt += __builtin_popcountll(m);
             }
-            if (cnt * (a.C - 1) > MAX_NODE_ACTIONS) {
-                g_last_error = "more permitted actions than a node can hold";
+            if (e->ramsey_wide() ? cnt > e->ramsey_slots : cnt * (a.C - 1) > MAX_NODE_ACTIONS) {
+                g_last_error = e->ramsey_wide() ? "more permitted edges than azd_engine_config::max_slots" : "more permitted actions than a node can hold";
                 return AZD_ERR_INVALID_ARGUMENT;
             }
         }
         AZD_HIP(hipMemcpyAsync(e->d_stage_parents, parents, (size_t)a.B * a.E, hipMemcpyHostToDevice, e->stream));
-        AZD_HIP(hipMemcpyAsync(e->d_stage_perm, permitted, (size_t)a.B * a.KW * 8, hipMemcpyHostToDevice, e->stream));
+        AZD_HIP(hipMemcpyAsync(e->d_stage_perm, KWH != a.KW ? e->ramsey_perm_pad.data() : permitted, (size_t)a.B * a.KW * 8, hipMemcpyHostToDevice, e->stream));
+        if (KWH != a.KW) AZD_HIP(hipStreamSynchronize(e->stream)); // the padded block is pageable host memory
         return AZD_OK;
     }
     // validate on the host what the kernels assume (parents[v] < v; at most MAX_NODE_ACTIONS permitted)
@@ -513,7 +526,7 @@ int azd_ramsey_action_dim(int n, int n_colors) { return azd::ramsey_action_dim(n
 int azd_ramsey_key_words(int n, int n_colors) { return azd::ramsey_key_words(n, n_colors); }
 int azd_ramsey_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int n_colors, int kmin,
                               int kmax, uint8_t *colors, uint64_t *permitted) {
-    if (!colors || !permitted || count < 0 || n < 3 || n > AZD_RAMSEY_MAX_N || n_colors < 2 || n_colors > 4) return AZD_ERR_INVALID_ARGUMENT;
+    if (!colors || !permitted || count < 0 || n < 3 || n > AZD_RAMSEY_WIDE_MAX_N || n_colors < 2 || n_colors > 4) return AZD_ERR_INVALID_ARGUMENT;
     if (kmin < 0 || kmax < kmin || kmax > azd::ramsey_edges(n)) return AZD_ERR_INVALID_ARGUMENT;
     azd::ramsey_generate_roots(seed, epoch, first_agent, count, n, n_colors, kmin, kmax, colors, permitted);
     return AZD_OK;
@@ -650,6 +663,24 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
             azd::g_last_error = "unsupported dense-graph space (need 4 <= n <= 64, no Layered wrapper, max_slots <= 1024, 0 <= dense_p <= 1)";
             return AZD_ERR_INVALID_ARGUMENT;
         }
+    } else if (ramsey && cfg->max_slots != 0) { // wide engine: max_slots = the most permitted edges a root may bring
+        bool ok = cfg->batch > 0 && cfg->n >= 3 && cfg->n <= AZD_RAMSEY_WIDE_MAX_N && cfg->n_colors >= 2 && cfg->n_colors <= 4;
+        if (ok) {
+            for (int c = 0; c < cfg->n_colors; ++c) ok = ok && cfg->clique_sizes[c] >= 2 && cfg->clique_sizes[c] <= 5;
+            ok = ok && azd::ramsey_action_dim(cfg->n, cfg->n_colors) <= 1024;
+        }
+        if (!ok) {
+            azd::g_last_error = "unsupported wide Ramsey space (max_slots > 0: need 3 <= n <= 32, 2..4 colours, clique sizes 2..5, E*C <= 1024)";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+        if (cfg->max_slots < 1 || cfg->max_slots > azd::ramsey_edges(cfg->n)) {
+            azd::g_last_error = "wide Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+        if (cfg->layers > 1 || cfg->path_kind != AZD_PATH_SET) { // (cur_seq holds MAX_NODE_ACTIONS actions; a wide path can be longer)
+            azd::g_last_error = "wide Ramsey space (max_slots > 0): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
     } else if (ramsey) {
         bool ok = cfg->batch > 0 && cfg->n >= 3 && cfg->n <= AZD_RAMSEY_MAX_N && cfg->n_colors >= 2 && cfg->n_colors <= 4;
         if (ok) {
@@ -704,6 +735,12 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         a.A = azd::ramsey_action_dim(cfg->n, a.C);
         a.S = azd::ramsey_state_dim(cfg->n, a.C);
         a.KW = azd::ramsey_key_words(cfg->n, a.C);
+        e->kw_host = a.KW;
+        e->ramsey_slots = azd::MAX_NODE_ACTIONS / (a.C - 1);
+        if (cfg->max_slots > 0) { // wide: the device keys padded to the widths ramsey_kernels.hip is built for (RamseyWideSpace<10 / 16>)
+            a.KW = a.A <= 640 ? 10 : 16;
+            e->ramsey_slots = cfg->max_slots;
+        }
         for (int c = 0; c < a.C; ++c) {
             a.sizes[c] = cfg->clique_sizes[c];
             a.cweights[c] = cfg->color_weights[c];
@@ -735,7 +772,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     {
         const char *bad = nullptr;
         static thread_local char msg[256];
-        const long per_node = dense ? (long)e->dense_slots : ramsey ? (long)a.E * (a.C - 1) : (long)a.A;
+        const long per_node = dense ? (long)e->dense_slots : ramsey ? (long)std::min(a.E, e->ramsey_slots) * (a.C - 1) : (long)a.A;
         if (a.node_cap > (uint32_t)AZD_MAX_NODE_CAPACITY) snprintf(msg, sizeof msg, "node_capacity %u is beyond the record format (<= %d)", a.node_cap, AZD_MAX_NODE_CAPACITY), bad = msg;
         else if (a.arc_cap > (uint32_t)AZD_MAX_ARC_CAPACITY) snprintf(msg, sizeof msg, "arc_capacity %u is beyond the record format (<= %d)", a.arc_cap, AZD_MAX_ARC_CAPACITY), bad = msg;
         else if (a.pred_cap > (uint32_t)AZD_MAX_PREDICTION_CAPACITY) snprintf(msg, sizeof msg, "prediction_capacity %u is beyond the record format (<= %d)", a.pred_cap, AZD_MAX_PREDICTION_CAPACITY), bad = msg;
@@ -821,7 +858,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         TRY(e->alloc(&a.cur_counts, B * (size_t)a.C * a.E));
         TRY(e->alloc(&a.root_tot, B * 4));
         TRY(e->alloc(&a.cur_tot, B * 4));
-        TRY(e->alloc(&a.argmin_r, 1));
+        TRY(e->alloc(&a.argmin_r, e->argmin_r_recs()));
     }
     e->persist_enabled = (cfg->flags & AZD_ENGINE_NO_PERSISTENT_STEP) == 0;
     e->barrier_step = (cfg->flags & AZD_ENGINE_BARRIER_STEP) != 0;
@@ -873,7 +910,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         TRY(e->alloc(&e->d_log_node, (size_t)e->log_calls * n_wg));
         TRY(e->alloc(&e->pool.win_count, (size_t)e->log_calls));
         TRY(e->alloc(&e->d_argmin_side, 1));
-        if (ramsey) TRY(e->alloc(&e->d_argmin_r_side, 1));
+        if (ramsey) TRY(e->alloc(&e->d_argmin_r_side, e->argmin_r_recs()));
         // what the kernel hands the host in the middle of a launch: fine-grained (host-coherent) pinned memory
         hipError_t he3 = hipHostMalloc((void **)&e->h_win_log, (size_t)e->log_calls * sizeof(unsigned long long), hipHostMallocCoherent);
         if (he3 == hipSuccess) he3 = hipHostMalloc((void **)&e->h_win_flag, (size_t)e->log_calls * sizeof(uint32_t), hipHostMallocCoherent);
@@ -1730,7 +1767,7 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
                 AZD_HIP(hipMemsetAsync(pool.win_count, 0, (size_t)e->log_calls * sizeof(uint32_t), e->stream));
                 AZD_HIP(hipMemcpyAsync(e->d_argmin_side, e->a.argmin, sizeof(azd::ArgminRec), hipMemcpyDeviceToDevice, e->stream));
                 if (e->d_argmin_r_side)
-                    AZD_HIP(hipMemcpyAsync(e->d_argmin_r_side, e->a.argmin_r, sizeof(azd::RamseyArgminRec), hipMemcpyDeviceToDevice, e->stream));
+                    AZD_HIP(hipMemcpyAsync(e->d_argmin_r_side, e->a.argmin_r, e->argmin_r_bytes(), hipMemcpyDeviceToDevice, e->stream));
                 AZD_HIP(hipMemcpyAsync(e->h_argmin, e->a.argmin, sizeof(azd::ArgminRec), hipMemcpyDeviceToHost, e->stream));
                 st = fetch_status(e); // (synchronises)
                 if (st) return st;
@@ -2250,8 +2287,11 @@ static int c21_policy_args_ok(azd_engine *e, int kmin, int kmax) {
         azd::g_last_error = "the device root policy handles sequence-keyed trees of at most 4096 nodes";
         return AZD_ERR_UNSUPPORTED;
     }
-    if (e->a.space == azd::SPACE_RAMSEY) {
-        if (kmin < 1 || kmax < kmin || kmax > e->a.E || kmax * (e->a.C - 1) > azd::MAX_NODE_ACTIONS) return AZD_ERR_INVALID_ARGUMENT;
+    if (e->a.space == azd::SPACE_RAMSEY) { // the node cap: max_slots edges on a wide engine, MAX_NODE_ACTIONS / (C - 1) otherwise
+        if (kmin < 1 || kmax < kmin || kmax > e->a.E || kmax > e->ramsey_slots) {
+            if (e->ramsey_wide()) azd::g_last_error = "Ramsey root policy: need 1 <= kmin <= kmax <= max_slots (azd_engine_config::max_slots)";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
         return AZD_OK;
     }
     if (kmin < 1 || kmax < kmin || kmax > e->a.A || kmax > azd::MAX_NODE_ACTIONS) return AZD_ERR_INVALID_ARGUMENT;
@@ -2295,7 +2335,12 @@ int azd_c21_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int k
     }
     azd::launch_c21_modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->stream);
     AZD_HIP(hipMemcpyAsync(parents_out, e->d_stage_parents, (size_t)a.B * (a.space == azd::SPACE_RAMSEY ? a.E : a.n), hipMemcpyDeviceToHost, e->stream));
-    AZD_HIP(hipMemcpyAsync(permitted_out, e->d_stage_perm, (size_t)a.B * a.KW * 8, hipMemcpyDeviceToHost, e->stream));
+    if (e->ramsey_wide()) { // device masks are a.KW words, the caller's kw_host
+        std::vector<uint64_t> pm((size_t)a.B * a.KW);
+        AZD_HIP(hipMemcpyAsync(pm.data(), e->d_stage_perm, pm.size() * 8, hipMemcpyDeviceToHost, e->stream));
+        AZD_HIP(hipStreamSynchronize(e->stream));
+        for (int i = 0; i < a.B; ++i) memcpy(permitted_out + (size_t)i * e->kw_host, &pm[(size_t)i * a.KW], (size_t)e->kw_host * 8);
+    } else AZD_HIP(hipMemcpyAsync(permitted_out, e->d_stage_perm, (size_t)a.B * a.KW * 8, hipMemcpyDeviceToHost, e->stream));
     AZD_HIP(hipStreamSynchronize(e->stream));
     AZD_HIP(hipGetLastError());
     return AZD_OK;
@@ -2313,6 +2358,10 @@ int azd_engine_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, in
 int azd_engine_ramsey_argmin_data(azd_engine *e, azd_ramsey_argmin *out) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (e->a.space != azd::SPACE_RAMSEY) return AZD_ERR_UNSUPPORTED;
+    if (e->a.E > 256) { // (colours of 256 edges: azd_ramsey_argmin)
+        azd::g_last_error = "E > 256 edges do not fit azd_ramsey_argmin: use azd_engine_ramsey_wide_argmin_data";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
     AZD_HIP(hipSetDevice(e->cfg.device));
     bool side = false; // inside a run-ahead window: the record as of the calls handed out so far
     {
@@ -2321,7 +2370,46 @@ int azd_engine_ramsey_argmin_data(azd_engine *e, azd_ramsey_argmin *out) {
     }
     static_assert(sizeof(azd_ramsey_argmin) == sizeof(azd::RamseyArgminRec), "ABI struct mismatch");
     AZD_HIP(hipStreamSynchronize(e->stream));
+    if (e->ramsey_wide()) { // the device holds the wide record; its E <= 256 edges fit this one
+        azd::RamseyWideArgminRec w;
+        AZD_HIP(hipMemcpy(&w, side ? e->d_argmin_r_side : e->a.argmin_r, sizeof(w), hipMemcpyDeviceToHost));
+        memset(out, 0, sizeof(*out));
+        memcpy(out->colors, w.colors, (size_t)e->a.E);
+        memcpy(out->permitted, w.permitted, sizeof(out->permitted));
+        memcpy(out->totals, w.totals, sizeof(out->totals));
+        out->eval = w.eval;
+        out->agent = w.agent;
+        out->node = w.node;
+        return AZD_OK;
+    }
     AZD_HIP(hipMemcpy(out, side ? e->d_argmin_r_side : e->a.argmin_r, sizeof(azd_ramsey_argmin), hipMemcpyDeviceToHost));
+    return AZD_OK;
+}
+int azd_engine_ramsey_wide_argmin_data(azd_engine *e, azd_ramsey_wide_argmin *out) {
+    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
+    if (e->a.space != azd::SPACE_RAMSEY) return AZD_ERR_UNSUPPORTED;
+    static_assert(sizeof(azd_ramsey_wide_argmin) == sizeof(azd::RamseyWideArgminRec), "ABI struct mismatch");
+    if (!e->ramsey_wide()) { // a narrow engine's record, widened
+        azd_ramsey_argmin n;
+        const int st = azd_engine_ramsey_argmin_data(e, &n);
+        if (st) return st;
+        memset(out, 0, sizeof(*out));
+        memcpy(out->colors, n.colors, sizeof(n.colors));
+        memcpy(out->permitted, n.permitted, sizeof(n.permitted));
+        memcpy(out->totals, n.totals, sizeof(n.totals));
+        out->eval = n.eval;
+        out->agent = n.agent;
+        out->node = n.node;
+        return AZD_OK;
+    }
+    AZD_HIP(hipSetDevice(e->cfg.device));
+    bool side = false;
+    {
+        const int st_w = window_argmin_side(e, &side);
+        if (st_w) return st_w;
+    }
+    AZD_HIP(hipStreamSynchronize(e->stream));
+    AZD_HIP(hipMemcpy(out, side ? e->d_argmin_r_side : e->a.argmin_r, sizeof(*out), hipMemcpyDeviceToHost));
     return AZD_OK;
 }
 int azd_engine_dense_argmin_data(azd_engine *e, azd_dense_argmin *out) {
@@ -2442,6 +2530,10 @@ int azd_engine_export_tree(azd_engine *e, int agent, float *c, float *c_star, ui
         for (int i = 0; i < nn; ++i)
             for (int r = 0; r < MAXS; ++r)
                 if ((rk[(size_t)i * KW + (r >> 6)] >> (r & 63)) & 1ull) keys[(size_t)i * e->kw_host + (tab[(size_t)r] >> 6)] |= 1ull << (tab[(size_t)r] & 63);
+    } else if (keys && e->ramsey_wide()) { // zero-padded device keys: the first kw_host words of each
+        std::vector<uint64_t> rk((size_t)nn * a.KW);
+        AZD_HIP(hipMemcpy(rk.data(), a.keys + (size_t)agent * a.node_cap * a.KW, rk.size() * 8, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nn; ++i) memcpy(keys + (size_t)i * e->kw_host, &rk[(size_t)i * a.KW], (size_t)e->kw_host * 8);
     } else if (keys) AZD_HIP(hipMemcpy(keys, a.keys + (size_t)agent * a.node_cap * a.KW, (size_t)nn * a.KW * 8, hipMemcpyDeviceToHost));
     for (int i = 0; i < nn; ++i) {
         if (c) c[i] = nodes[(size_t)i].c;
@@ -2511,8 +2603,9 @@ int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t 
                         if ((nbr[c * 32 + v] >> u) & 1u) parents[pos] = (uint8_t)c;
                 }
         }
-        if (permitted) AZD_HIP(hipMemcpy(permitted, a.cur_perm + (size_t)agent * a.KW, (size_t)a.KW * 8, hipMemcpyDeviceToHost));
-        if (path) AZD_HIP(hipMemcpy(path, a.cur_path + (size_t)agent * a.KW, (size_t)a.KW * 8, hipMemcpyDeviceToHost));
+        // (kw_host words: a wide engine's device masks are zero-padded beyond them)
+        if (permitted) AZD_HIP(hipMemcpy(permitted, a.cur_perm + (size_t)agent * a.KW, (size_t)e->kw_host * 8, hipMemcpyDeviceToHost));
+        if (path) AZD_HIP(hipMemcpy(path, a.cur_path + (size_t)agent * a.KW, (size_t)e->kw_host * 8, hipMemcpyDeviceToHost));
         if (state_pos) AZD_HIP(hipMemcpy(state_pos, a.state_pos + agent, 4, hipMemcpyDeviceToHost));
         if (lambda_1) *lambda_1 = 0.0;
         if (matching_size) *matching_size = 0;

@@ -122,6 +122,15 @@ struct RamseyArgminRec { // device copy of azd_ramsey_argmin
     uint32_t node;
 };
 
+struct RamseyWideArgminRec { // device copy of azd_ramsey_wide_argmin (wide Ramsey engines write this one)
+    uint8_t colors[496];
+    uint64_t permitted[8];
+    int32_t totals[4];
+    float eval;
+    int32_t agent;
+    uint32_t node;
+};
+
 struct DenseArgminRec { // device copy of azd_dense_argmin
     uint64_t adj[64];
     uint64_t permitted[40]; // modifiable slots (colex positions) still open

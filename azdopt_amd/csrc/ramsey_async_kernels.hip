@@ -14,6 +14,7 @@ namespace azd {
 #include "persistent_step.inc"
 #include "async_step.inc"
 
+// narrow engines: key widths 1..6; wide engines (max_slots > 0): 10 or 16 (space_ramsey.inc: ramsey_wide)
 #define DISPATCH_RKW(A, FN, ...)                                  \
     switch ((A).KW) {                                             \
     case 1: FN<RamseySpace<1>>(__VA_ARGS__); break;               \
@@ -21,6 +22,8 @@ namespace azd {
     case 3: FN<RamseySpace<3>>(__VA_ARGS__); break;               \
     case 4: FN<RamseySpace<4>>(__VA_ARGS__); break;               \
     case 5: FN<RamseySpace<5>>(__VA_ARGS__); break;               \
+    case 10: FN<RamseyWideSpace<10>>(__VA_ARGS__); break;         \
+    case 16: FN<RamseyWideSpace<16>>(__VA_ARGS__); break;         \
     default: FN<RamseySpace<6>>(__VA_ARGS__); break;              \
     }
 
@@ -48,7 +51,7 @@ bool ramsey_async_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_strid
         *why = "asynchronous step: more than 65536 agents or nodes per tree";
         return false;
     }
-    size_t stride = (RamseySpace<1>::dyn_bytes(a) + 15) & ~(size_t)15;
+    size_t stride = (ramsey_dyn_bytes(a) + 15) & ~(size_t)15;
     if (ev.kind == 3) {
         for (int l = 0; l < ev.n_layers; ++l)
             if (ev.dims[l] % (l == 0 ? 4 : 16) != 0) {
@@ -59,7 +62,7 @@ bool ramsey_async_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_strid
         if (rows > stride) stride = (rows + 15) & ~(size_t)15;
     }
     const size_t total = stride * PERSIST_WAVES;
-    const size_t static_lds = PERSIST_WAVES * (sizeof(RamseyLds) + 16) + sizeof(AsyncCtl) + 256;
+    const size_t static_lds = PERSIST_WAVES * (ramsey_lds_bytes(a) + 16) + sizeof(AsyncCtl) + 256;
     if (total + static_lds > 160 * 1024) {
         *why = "asynchronous step: 16 rows of activations do not fit the CU's 160 KB of LDS";
         return false;

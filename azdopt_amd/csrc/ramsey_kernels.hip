@@ -11,6 +11,7 @@ namespace azd {
 #include "tree_core.inc"
 #include "space_ramsey.inc"
 
+// narrow engines: key widths 1..6; wide engines (max_slots > 0): 10 or 16 (space_ramsey.inc: ramsey_wide)
 #define DISPATCH_RKW(A, FN, ...)                                  \
     switch ((A).KW) {                                             \
     case 1: FN<RamseySpace<1>>(__VA_ARGS__); break;               \
@@ -18,6 +19,8 @@ namespace azd {
     case 3: FN<RamseySpace<3>>(__VA_ARGS__); break;               \
     case 4: FN<RamseySpace<4>>(__VA_ARGS__); break;               \
     case 5: FN<RamseySpace<5>>(__VA_ARGS__); break;               \
+    case 10: FN<RamseyWideSpace<10>>(__VA_ARGS__); break;         \
+    case 16: FN<RamseyWideSpace<16>>(__VA_ARGS__); break;         \
     default: FN<RamseySpace<6>>(__VA_ARGS__); break;              \
     }
 
@@ -99,7 +102,7 @@ void ramsey_launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream) {
 bool ramsey_persist_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why) {
     const char *dummy;
     if (!why) why = &dummy;
-    size_t per = CORE_DYN_BYTES + (size_t)a.C * a.E * sizeof(int32_t);
+    size_t per = ramsey_dyn_bytes(a);
     size_t stride = (per + 15) & ~(size_t)15;
     size_t total = stride * PERSIST_WAVES;
     if (ev.kind == 3) {
@@ -115,7 +118,7 @@ bool ramsey_persist_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_str
         size_t mlp = (size_t)PERSIST_WAVES * ((size_t)(ev.dims[0] + 4) + (size_t)(ev.hid[0] + 4) + (size_t)(ev.hid[1] + 4)) * sizeof(float);
         if (mlp > total) total = mlp;
     }
-    const size_t static_lds = PERSIST_WAVES * (sizeof(RamseyLds) + 16) + 256;
+    const size_t static_lds = PERSIST_WAVES * (ramsey_lds_bytes(a) + 16) + 256;
     if (total + static_lds > 160 * 1024) {
         *why = "barrier step: 16 rows of activations do not fit the CU's 160 KB of LDS";
         return false;

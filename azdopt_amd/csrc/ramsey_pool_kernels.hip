@@ -14,6 +14,7 @@ namespace azd {
 #include "async_step.inc"
 #include "pool_step.inc"
 
+// narrow engines: key widths 1..6; wide engines (max_slots > 0): 10 or 16 (space_ramsey.inc: ramsey_wide)
 #define DISPATCH_RKW(A, FN, ...)                                  \
     switch ((A).KW) {                                             \
     case 1: FN<RamseySpace<1>>(__VA_ARGS__); break;               \
@@ -21,6 +22,8 @@ namespace azd {
     case 3: FN<RamseySpace<3>>(__VA_ARGS__); break;               \
     case 4: FN<RamseySpace<4>>(__VA_ARGS__); break;               \
     case 5: FN<RamseySpace<5>>(__VA_ARGS__); break;               \
+    case 10: FN<RamseyWideSpace<10>>(__VA_ARGS__); break;         \
+    case 16: FN<RamseyWideSpace<16>>(__VA_ARGS__); break;         \
     default: FN<RamseySpace<6>>(__VA_ARGS__); break;              \
     }
 
@@ -64,7 +67,7 @@ int ramsey_pool_max_resident(const Arenas &a, size_t dyn_bytes, int n_cus) {
 bool ramsey_pool_plan(const Arenas &a, const FusedEval &ev, PoolArgs *pool, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why) {
     const char *dummy;
     if (!why) why = &dummy;
-    return pool_plan_common(a, ev, pool, dyn_stride, dyn_bytes, why, RamseySpace<1>::pool_dyn_bytes(a), sizeof(RamseyLds));
+    return pool_plan_common(a, ev, pool, dyn_stride, dyn_bytes, why, ramsey_pool_dyn_bytes(a), ramsey_lds_bytes(a));
 }
 
 } // namespace azd

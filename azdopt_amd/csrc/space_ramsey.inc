@@ -14,17 +14,20 @@
 // need no atomics.  Integer work throughout; the only f32 arithmetic is evaluate / g / h_sa.
 
 constexpr int RAMSEY_MAX_E = 256;
+constexpr int RAMSEY_WIDE_MAX_E = 496; // N = 32 (wide engines: azd_engine_config::max_slots > 0)
 constexpr int RAMSEY_MAX_C = 4;
 
-struct RamseyLds {
+template <int ME>
+struct RamseyLdsT {
     uint32_t nbr[RAMSEY_MAX_C][32];
-    uint8_t ev[RAMSEY_MAX_E]; // edge position -> larger endpoint (edge.rs:55-65)
-    uint8_t eu[RAMSEY_MAX_E]; //               -> smaller endpoint
+    uint8_t ev[ME]; // edge position -> larger endpoint (edge.rs:55-65)
+    uint8_t eu[ME]; //               -> smaller endpoint
     unsigned long long ctr[NUM_COUNTERS];
     uint16_t seq[MAX_NODE_ACTIONS]; // actions of the current path in the order taken (Layered<L, _> only)
     uint32_t stack[PATH_STACK];     // nodes of the current path, root first (tree_core.inc: cascade)
 };
-__device__ __forceinline__ int32_t *lds_counts(uint32_t dyn) { return (int32_t *)(lds_base(dyn) + CORE_DYN_BYTES); }
+using RamseyLds = RamseyLdsT<RAMSEY_MAX_E>;
+using RamseyWideLds = RamseyLdsT<RAMSEY_WIDE_MAX_E>;
 
 __device__ __forceinline__ uint32_t u32_add(uint32_t a, uint32_t b) { return a + b; }
 // wave-wide sum: the same DPP ladder as wave_min_u32 is an inclusive scan, lane 63 holds the total
@@ -61,7 +64,8 @@ __device__ __forceinline__ int cliques_inside(const uint32_t *nb, uint32_t S, in
 }
 
 // ramsey_counts/mod.rs:101-164 reassign_color_count_adjustment (edge uv absent from `color`'s graph)
-__device__ __forceinline__ void ramsey_adjust(RamseyLds &s, int32_t *counts, const int E, const bool subtract, const int u,
+template <class LDS>
+__device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int E, const bool subtract, const int u,
                                               const int v, const int color, const int size) {
     if (size <= 2) return;
     const uint32_t *nb = s.nbr[color];
@@ -94,28 +98,34 @@ __device__ __forceinline__ void ramsey_adjust(RamseyLds &s, int32_t *counts, con
     }
 }
 
-struct RamseyArgminRec; // engine_types.h
-
-template <int KW_>
-struct RamseySpace {
+// The space over an edge capacity ME, ARG the argmin record it writes and CH_ chunks of 64 predictions per node.  RamseySpace<KW>
+// (below) is today's space: ME = 256, two chunks (MAX_NODE_ACTIONS).  RamseyWideSpace<KW> takes N <= 32 (ME = 496) and nodes of
+// up to 64 KW actions (select_big); the engine picks it when azd_engine_config::max_slots > 0.  The clique counts sit in the dynamic
+// LDS behind the search scratch, which is CORE_DYN_BYTES or select_big's two lists of 64 CH words, whichever is larger.
+template <int KW_, int ME, class ARG, int CH_>
+struct RamseySpaceBase {
     static constexpr int KW = KW_;
+    static constexpr int CH = CH_; // chunks of 64 predictions a node may hold (tree_core.inc: SpaceChunks)
     static constexpr int PW = (KW_ + 1) / 2; // permitted-edge words: E = A / C <= A / 2
     static constexpr bool FRONTIER_SPILL = true; // cascade levels wider than the LDS frontier go to memory (tree_core.inc: cascade)
-    using Lds = RamseyLds;
+    static constexpr size_t SCRATCH = (size_t)512 * CH_ > CORE_DYN_BYTES ? (size_t)512 * CH_ : CORE_DYN_BYTES;
+    static constexpr int APW = sizeof(ARG::permitted) / 8; // permitted words of the argmin record
+    using Lds = RamseyLdsT<ME>;
     struct St {
         uint64_t perm[PW];
         int32_t tot[RAMSEY_MAX_C];
     };
-    static size_t dyn_bytes(const Arenas &a) { return CORE_DYN_BYTES + (size_t)a.C * a.E * sizeof(int32_t); }
+    __device__ static __forceinline__ int32_t *lds_counts(uint32_t dyn) { return (int32_t *)(lds_base(dyn) + SCRATCH); }
+    static size_t dyn_bytes(const Arenas &a) { return SCRATCH + (size_t)a.C * a.E * sizeof(int32_t); }
     // pool step: write_vec reads the live clique counts (behind the search scratch), the scratch itself is dead by then:
     // the state-vector row is built over the scratch if it fits there, else behind the counts
     static size_t pool_dyn_bytes(const Arenas &a) {
         const size_t base = (dyn_bytes(a) + 15) & ~(size_t)15;
-        return (size_t)a.S * 4 <= CORE_DYN_BYTES ? base : base + (size_t)a.S * 4;
+        return (size_t)a.S * 4 <= SCRATCH ? base : base + (size_t)a.S * 4;
     }
     __device__ static __forceinline__ float *row_stage(const Arenas &a, const uint32_t dyn) {
-        if ((size_t)a.S * 4 <= CORE_DYN_BYTES) return reinterpret_cast<float *>(lds_base(dyn));
-        return reinterpret_cast<float *>(lds_base(dyn) + ((CORE_DYN_BYTES + (size_t)a.C * a.E * sizeof(int32_t) + 15) & ~(size_t)15));
+        if ((size_t)a.S * 4 <= SCRATCH) return reinterpret_cast<float *>(lds_base(dyn));
+        return reinterpret_cast<float *>(lds_base(dyn) + ((SCRATCH + (size_t)a.C * a.E * sizeof(int32_t) + 15) & ~(size_t)15));
     }
 
     // the ActionSet key is the bit mask of the action ids themselves
@@ -190,7 +200,8 @@ struct RamseySpace {
     }
 
     // space.rs:71-86 act = reassign_color (mod.rs:78-99) + permitted_edges.remove
-    __device__ static void act(const Arenas &a, Lds &s, const uint32_t dyn, St &st, const uint32_t aid) {
+    __device__ static void act(const Arenas &a, Lds &s, const uint32_t dyn, St &st, const uint32_t aid) { act_body(a, s, dyn, st, aid); }
+    __device__ static __forceinline__ void act_body(const Arenas &a, Lds &s, const uint32_t dyn, St &st, const uint32_t aid) {
         const int E = a.E, C = a.C;
         const int e = (int)(aid % (uint32_t)E), nc = (int)(aid / (uint32_t)E);
         const int v = s.ev[e], u = s.eu[e];
@@ -257,6 +268,37 @@ struct RamseySpace {
         return 1.0f - q;
     }
 
+    // the C - 1 actions of permitted edge e (larger endpoint v) from its colour classes nbv, counts cnv and prediction entries hv in
+    // every colour: predictions begin + rank (C - 1) + k
+    __device__ static __forceinline__ void edge_actions(const Arenas &a, const int e, const int v, const uint32_t (&nbv)[RAMSEY_MAX_C],
+                                                        const int32_t (&cnv)[RAMSEY_MAX_C], const float (&hv)[RAMSEY_MAX_C], const float c_s,
+                                                        PredRec *preds, const uint32_t begin, const uint32_t rank, FirstPick &fp) {
+        const int E = a.E, C = a.C;
+        int oc = 0;
+#pragma unroll
+        for (int c = 0; c < RAMSEY_MAX_C; ++c)
+            if (c < C && ((nbv[c] >> v) & 1u)) oc = c;
+        int32_t cnt_oc = cnv[0];
+#pragma unroll
+        for (int c = 1; c < RAMSEY_MAX_C; ++c) cnt_oc = oc == c ? cnv[c] : cnt_oc;
+        float cw_oc = a.cweights[0];
+#pragma unroll
+        for (int c = 1; c < RAMSEY_MAX_C; ++c) cw_oc = oc == c ? a.cweights[c] : cw_oc; // (a select over the four weights, not a per-lane load)
+        const float r_old = (float)cnt_oc * cw_oc;
+        uint32_t k = 0;
+#pragma unroll
+        for (int nc = 0; nc < RAMSEY_MAX_C; ++nc) {
+            if (nc >= C || nc == oc) continue;
+            const float r_sa = r_old - (float)cnv[nc] * a.cweights[nc];
+            const uint32_t a_id = (uint32_t)(e + nc * E);
+            const float hh = hv[nc];
+            const float g = c_s * hh + r_sa * (1.0f - hh);
+            const PredRec p = pred_new(a_id, c_s, g);
+            preds[begin + rank * (uint32_t)(C - 1) + k] = p;
+            pick_note(fp, __uint_as_float(p.w0), g, rank * (uint32_t)(C - 1) + k, a_id);
+            ++k;
+        }
+    }
     // graph_operations.rs:32-56 with space.rs:88-120 action_data (edges ascending, new colours
     // ascending, a_id = e + new_colour * E) and g = c_s h + r (1 - h), r = old_count w[old] -
     // new_count w[new] (:167-172).  Reads the state from HBM: in the persistent step the dynamic LDS
@@ -269,7 +311,7 @@ struct RamseySpace {
         for (int w = 0; w < PW; ++w) perm[w] = a.cur_perm[(size_t)t * KW + w];
         const uint32_t cnt = (uint32_t)mask_count<PW>(perm) * (uint32_t)(C - 1);
         const uint32_t begin = hint ? hint->n_preds : a.n_preds[t];
-        if (!add_actions_fits(a, t, begin, cnt)) return;
+        if (!add_actions_fits(a, t, begin, cnt, 64u * CH)) return;
         const uint32_t node = hint ? hint->pos : a.state_pos[t];
         PredRec *preds = a.preds + (size_t)t * a.pred_cap;
         const float c_s = hint ? hint->c : a.nodes[(size_t)t * a.node_cap + node].c;
@@ -282,6 +324,35 @@ struct RamseySpace {
         fp.key = 0ull;
         fp.aid = 0u;
         fp.g = 0.f;
+        if constexpr (CH > PRED_CHUNKS) {
+            // wide: a word of 64 edges at a time (every word's requests at once -- 8 words x 4 colours x 3 values -- do not fit the
+            // CU-resident forms' 128 registers)
+#pragma unroll 1
+            for (int w = 0; w < PW; ++w) {
+                const uint64_t pw = a.cur_perm[(size_t)t * KW + w];
+                const int e = w * 64 + LANE, ec = ((pw >> LANE) & 1ull) ? e : 0;
+                const int ev1 = s.ev[ec], eu1 = s.eu[ec];
+                uint32_t nbv[RAMSEY_MAX_C];
+                int32_t cnv[RAMSEY_MAX_C];
+                float hv[RAMSEY_MAX_C];
+#pragma unroll
+                for (int c = 0; c < RAMSEY_MAX_C; ++c) {
+                    nbv[c] = 0u;
+                    cnv[c] = 0;
+                    hv[c] = 0.f;
+                    if (c < C) {
+                        nbv[c] = nbr[c * 32 + eu1];
+                        cnv[c] = counts[c * E + ec];
+                        hv[c] = SC1 ? ld_sc1_f32(h + (ec + c * E)) : h[ec + c * E];
+                    }
+                }
+                if ((pw >> LANE) & 1ull) {
+                    const uint32_t rank = before + (uint32_t)__popcll(pw & ((1ull << LANE) - 1ull));
+                    edge_actions(a, e, ev1, nbv, cnv, hv, c_s, preds, begin, rank, fp);
+                }
+                before += (uint32_t)__popcll(pw);
+            }
+        } else {
         // Every request first (round 5): an edge's colour classes, its counts and its prediction-row entries in EVERY colour do not depend on
         // which colour it has -- requested edge by edge and colour by colour behind that question they were three dependent round trips per
         // 64 edges, nine at the head of every call of R(4,4).  A lane without a permitted edge in a chunk reads edge 0's (unused).
@@ -339,6 +410,7 @@ struct RamseySpace {
             }
             before += (uint32_t)__popcll(perm[w]);
         }
+        }
         add_actions_commit(a, t, node, begin, cnt, hint ? s.ctr : nullptr, link);
         if (pick) pick_finish(fp, begin, cnt, pick);
     }
@@ -387,8 +459,8 @@ struct RamseySpace {
     }
 
     // ---- hooks of the device root policy (root_policy.inc)
-    static constexpr int UNIVERSE_MAX = 256, SLOT_WORDS_MAX = MAX_KW;
-    static constexpr bool SEQ_POLICY = true;
+    static constexpr int UNIVERSE_MAX = ME, SLOT_WORDS_MAX = KW_ > MAX_KW ? KW_ : MAX_KW;
+    static constexpr bool SEQ_POLICY = ME == RAMSEY_MAX_E; // (wide engines take ActionSet keys only: the engine refuses the others)
     __device__ static __forceinline__ int slot_words(const Arenas &a) { return a.KW; }
     __device__ static __forceinline__ void finish_root(const Arenas &, Lds &, const int, const uint8_t *, const uint64_t *, uint64_t *) {}
     __device__ static __forceinline__ int policy_universe(const Arenas &a) { return a.E; }
@@ -412,7 +484,7 @@ struct RamseySpace {
     // ArgminData { state, cost: TotalCounts, eval } (log.rs:1-11)
     __device__ static void argmin_out(const Arenas &a, Lds &s, const uint32_t dyn, St &st, const int wt, const uint32_t win_node) {
         const int E = a.E, C = a.C;
-        RamseyArgminRec *out = a.argmin_r;
+        ARG *out = reinterpret_cast<ARG *>(a.argmin_r); // (a wide engine's record is the wide one: engine.hip sizes it)
         for (int e = LANE; e < E; e += 64) {
             const int v = s.ev[e], u = s.eu[e];
             int col = 0;
@@ -423,7 +495,7 @@ struct RamseySpace {
         const float ev = evaluate(a, s, dyn, st, 0);
         if (LANE == 0) {
 #pragma unroll
-            for (int w = 0; w < 4; ++w) out->permitted[w] = 0;
+            for (int w = 0; w < APW; ++w) out->permitted[w] = 0;
 #pragma unroll
             for (int w = 0; w < PW; ++w) out->permitted[w] = st.perm[w];
 #pragma unroll
@@ -437,3 +509,46 @@ struct RamseySpace {
         }
     }
 };
+
+template <int KW_>
+struct RamseySpace : RamseySpaceBase<KW_, RAMSEY_MAX_E, RamseyArgminRec, PRED_CHUNKS> {};
+template <int KW_>
+struct RamseyWideSpace : RamseySpaceBase<KW_, RAMSEY_WIDE_MAX_E, RamseyWideArgminRec, KW_> {
+    using Base = RamseySpaceBase<KW_, RAMSEY_WIDE_MAX_E, RamseyWideArgminRec, KW_>;
+    static constexpr bool REPLAY_BY_WORD = true; // (tree_core.inc: argmin_replay)
+    // Pool step: the state-vector row goes straight to memory (tree_core.inc: SpaceRowsDirect) instead of through an LDS stage behind
+    // the counts -- 5.5 KB per searcher wave at r45, 9.9 KB at N = 32, C = 2: sixteen of them are what kept the searcher side of the
+    // pool plan beyond 160 KB.  The entries are write_vec's, as 4-byte write-through stores (the request is posted after a drain).
+    static constexpr bool ROWS_DIRECT = true;
+    static size_t pool_dyn_bytes(const Arenas &a) { return (Base::dyn_bytes(a) + 15) & ~(size_t)15; }
+    __device__ static void write_rows_direct(const Arenas &a, typename Base::Lds &s, const uint32_t dyn, const typename Base::St &st, float *row,
+                                             uint16_t *) {
+        const int E = a.E, C = a.C, CE = a.C * a.E;
+        const int32_t *counts = Base::lds_counts(dyn);
+        for (int i = LANE; i < CE; i += 64) st_sc1_f32(row + i, (float)counts[i]);
+        for (int e = LANE; e < E; e += 64) {
+            const int v = s.ev[e], u = s.eu[e];
+            for (int c = 0; c < C; ++c) st_sc1_f32(row + CE + c * E + e, (float)((s.nbr[c][v] >> u) & 1u));
+        }
+#pragma unroll
+        for (int w = 0; w < Base::PW; ++w) {
+            const int e = w * 64 + LANE;
+            if (e < E) st_sc1_f32(row + 2 * CE + e, (float)((st.perm[w] >> LANE) & 1ull));
+        }
+    }
+    // (forced inline: left to its heuristics hipcc outlines it from the widest step kernels -- tools/check_kernels.py)
+    __device__ static __forceinline__ void act(const Arenas &a, typename Base::Lds &s, const uint32_t dyn, typename Base::St &st, const uint32_t aid) {
+        Base::act_body(a, s, dyn, st, aid);
+    }
+};
+
+// host side: what the instantiation an engine's key width selects needs of the LDS (the CU-resident forms' plans).  A wide engine's
+// keys are padded to 10 or 16 words (engine.hip), a width no narrow engine has (1..6): the key width names the engine's mode.
+static inline bool ramsey_wide(const Arenas &a) { return a.KW > MAX_KW; }
+static inline size_t ramsey_dyn_bytes(const Arenas &a) {
+    return a.KW == 16 ? RamseyWideSpace<16>::dyn_bytes(a) : a.KW == 10 ? RamseyWideSpace<10>::dyn_bytes(a) : RamseySpace<1>::dyn_bytes(a);
+}
+static inline size_t ramsey_pool_dyn_bytes(const Arenas &a) {
+    return a.KW == 16 ? RamseyWideSpace<16>::pool_dyn_bytes(a) : a.KW == 10 ? RamseyWideSpace<10>::pool_dyn_bytes(a) : RamseySpace<1>::pool_dyn_bytes(a);
+}
+static inline size_t ramsey_lds_bytes(const Arenas &a) { return ramsey_wide(a) ? sizeof(RamseyWideLds) : sizeof(RamseyLds); }

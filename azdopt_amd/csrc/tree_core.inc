@@ -652,6 +652,12 @@ template <class SP, class = void>
 struct SpaceTwoPhaseLoad { static constexpr bool value = false; };
 template <class SP>
 struct SpaceTwoPhaseLoad<SP, decltype((void)SP::TWO_PHASE_LOAD)> { static constexpr bool value = SP::TWO_PHASE_LOAD; };
+// Optional: SP::REPLAY_BY_WORD -- argmin_replay walks the key word by word in a loop (a wide key unrolled with act inlined per word is
+// more code than hipcc will inline: tools/check_kernels.py)
+template <class SP, class = void>
+struct SpaceReplayByWord { static constexpr bool value = false; };
+template <class SP>
+struct SpaceReplayByWord<SP, decltype((void)SP::REPLAY_BY_WORD)> { static constexpr bool value = SP::REPLAY_BY_WORD; };
 template <class SP, class = void>
 struct SpaceFrontierSpill { static constexpr bool value = false; };
 template <class SP>
@@ -1560,6 +1566,18 @@ __device__ void argmin_replay(const Arenas &a, typename SP::Lds &s, const uint32
     WAVE_SYNC();
     typename SP::St st;
     SP::load_root(a, wt, s, dyn, st);
+    if constexpr (SpaceReplayByWord<SP>::value) { // one copy of act in a loop over the key's words, read as they are used
+        WAVE_SYNC();
+#pragma unroll 1
+        for (int w = 0; w < KW; ++w) {
+            uint64_t bits = a.keys[((size_t)wt * a.node_cap + win_node) * KW + w];
+            while (bits) {
+                int b = __ffsll((unsigned long long)bits) - 1;
+                bits &= bits - 1;
+                SP::act(a, s, dyn, st, SP::bit_action(s, (uint32_t)(w * 64 + b)));
+            }
+        }
+    } else {
     uint64_t key[KW];
 #pragma unroll
     for (int w = 0; w < KW; ++w) key[w] = a.keys[((size_t)wt * a.node_cap + win_node) * KW + w];
@@ -1572,6 +1590,7 @@ __device__ void argmin_replay(const Arenas &a, typename SP::Lds &s, const uint32
             bits &= bits - 1;
             SP::act(a, s, dyn, st, SP::bit_action(s, (uint32_t)(w * 64 + b)));
         }
+    }
     }
     SP::argmin_out(a, s, dyn, st, wt, win_node);
     if (LANE == 0 && !init_mode) atomicAdd(&a.status->improved, 1ull);

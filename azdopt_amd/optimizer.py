@@ -98,6 +98,7 @@ class NablaOptimizer:
             cfg.max_slots = space.MAX_SLOTS
             cfg.dense_p = space.p
         if space.SPACE_ID == _lib.SPACE_RAMSEY:
+            cfg.max_slots = getattr(space, "MAX_SLOTS", 0)
             cfg.n_colors = space.C
             for i in range(space.C):
                 cfg.clique_sizes[i] = space.sizes[i]
@@ -196,8 +197,12 @@ class NablaOptimizer:
     def argmin_data(self):
         """optimizer/mod.rs:361"""
         if self.space.SPACE_ID == _lib.SPACE_RAMSEY:
-            rec = _lib.RamseyArgmin()
-            _lib.check(self._L.azd_engine_ramsey_argmin_data(self._h, C.byref(rec)), "ramsey_argmin_data")
+            if self.space.E > 256:  # (azd_ramsey_argmin holds 256 colours)
+                rec = _lib.RamseyWideArgmin()
+                _lib.check(self._L.azd_engine_ramsey_wide_argmin_data(self._h, C.byref(rec)), "ramsey_wide_argmin_data")
+            else:
+                rec = _lib.RamseyArgmin()
+                _lib.check(self._L.azd_engine_ramsey_argmin_data(self._h, C.byref(rec)), "ramsey_argmin_data")
             return RamseyArgminData(rec, self.space)
         if self.space.SPACE_ID == _lib.SPACE_DENSE:
             rec = _lib.DenseArgmin()

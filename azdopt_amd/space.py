@@ -111,7 +111,11 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
 
     SPACE_ID = _lib.SPACE_RAMSEY
 
-    def __init__(self, n, sizes, weights=None):
+    def __init__(self, n, sizes, weights=None, max_slots=None):
+        """`max_slots`: the most permitted edges a root may bring.  0 keeps the engine's narrow limits (E <= 256, E*C <= 384,
+        at most 128 / (C - 1) permitted edges); 1..E makes it a WIDE engine (N <= 32, E*C <= 1024; a node holds up to
+        max_slots * (C - 1) legal actions).  None: 0 where the narrow limits hold, else E -- every edge may be permitted,
+        as 05-r45.rs:83 allows."""
         self.n = int(n)
         self.sizes = [int(x) for x in sizes]
         self.weights = [1.0] * len(self.sizes) if weights is None else [float(x) for x in weights]
@@ -121,14 +125,23 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
         self.STATE_DIM = L.azd_ramsey_state_dim(self.n, self.C)    # space.rs:40
         self.ACTION_DIM = L.azd_ramsey_action_dim(self.n, self.C)  # space.rs:42
         self.KEY_WORDS = L.azd_ramsey_key_words(self.n, self.C)
+        if max_slots is None:
+            narrow = self.n <= _lib.RAMSEY_MAX_N and self.E <= 256 and self.KEY_WORDS <= 6
+            max_slots = 0 if narrow else self.E
+        self.MAX_SLOTS = int(max_slots)
 
     @property
     def ROOT_BYTES(self):
         return self.E
 
+    @property
+    def wide(self):
+        return self.MAX_SLOTS > 0
+
     def default_permitted_range(self):
-        """02-r44.rs:83: 12..=(E / 2), clamped to what one node can hold"""
-        hi = max(1, min(self.E // 2, 128 // (self.C - 1)))
+        """02-r44.rs:83: 12..=(E / 2), clamped to what one node can hold (max_slots edges on a wide engine)"""
+        cap = self.MAX_SLOTS if self.wide else 128 // (self.C - 1)
+        hi = max(1, min(self.E // 2, cap))
         return min(12, hi), hi
 
     def generate_roots(self, seed, count, first_agent=0, epoch=0, kmin=None, kmax=None):

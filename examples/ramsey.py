@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""The reference's Ramsey drivers (graph-state/examples/01-r333.rs, 02-r44.rs) over the MI355X engine.
+"""The reference's Ramsey drivers (graph-state/examples/01-r333.rs, 02-r44.rs, 05-r45.rs) over the MI355X engine.
 
-    python examples/ramsey.py r333|r44 [--epochs 250] [--episodes N] [--batch B]"""
+    python examples/ramsey.py r333|r44|r45 [--epochs 250] [--episodes N] [--batch B]"""
 import argparse
 import os
 import sys
@@ -16,6 +16,12 @@ DRIVERS = {  # N, SIZES, BATCH, episodes, n_as_tol, num_permitted_edges_range.st
                  tol=([200, 200, 200, 100, 100, 100, 50, 50, 50, 25, 25, 25], 10), tag="01-r333-grad"),   # 01-r333.rs:35-38,61,83,126-130
     "r44": dict(n=17, sizes=[4, 4], batch=512, episodes=3200, kmin=12,
                 tol=([200, 200, 100, 100, 50, 50, 25, 25], 10), tag="01-r333-grad"),                      # 02-r44.rs:35-38,61,83,126-130
+    # 05-r45.rs:35-46,61,83,101-103,129: N 24, [4, 5], every edge may be permitted (10..=E: a wide engine, max_slots = E),
+    # weights [1, P_RED / P_BLUE] with P_RED = 0.4685, lr 3e-4.  The seeded root generator draws colours uniformly: the driver's
+    # P_RED colouring probability (WeightedIndex, :84-90) is NOT reproduced -- it would change the generator's spec, which the
+    # oracle shares.  The driver's roll-out takes a decay (:134) this engine does not have: r44's tolerances stand in.
+    "r45": dict(n=24, sizes=[4, 5], batch=128, episodes=3200, kmin=10, kmax="E", weights=[1.0, 0.4685 / (1.0 - 0.4685)], lr=3e-4,
+                tol=([200, 200, 100, 100, 50, 50, 25, 25], 10), tag="01-r333-grad"),
 }
 
 
@@ -34,8 +40,8 @@ def main():
     batch = args.batch or d["batch"]
     episodes = args.episodes or d["episodes"]
 
-    space = az.RamseySpaceNoEdgeRecolor(d["n"], d["sizes"], [1.0] * len(d["sizes"]))
-    model = az.ActionModel(batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=1e-4, l2=1e-6, seed=args.seed)
+    space = az.RamseySpaceNoEdgeRecolor(d["n"], d["sizes"], d.get("weights", [1.0] * len(d["sizes"])))
+    model = az.ActionModel(batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=d.get("lr", 1e-4), l2=1e-6, seed=args.seed)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         writer = sinks.TensorboardWriter(open(os.path.join(args.out, "tfevents-losses"), "wb"))
@@ -43,6 +49,8 @@ def main():
     else:
         writer = sinks.TensorboardWriter.create(d["tag"])
     kmin, kmax = d["kmin"], space.default_permitted_range()[1]   # ..=(E / 2), capped by what a node holds
+    if d.get("kmax") == "E":
+        kmax = space.E
     C = len(d["sizes"])
     caps = az.tree_capacities(episodes, kmax * (C - 1))  # (limits of the packed records: 65536 nodes, 65535 arcs, 2^20 predictions)
     opt = az.NablaOptimizer.par_new(space, space.generate_roots(args.seed, batch, kmin=kmin, kmax=kmax), model, batch, **caps)

@@ -71,10 +71,13 @@ int azd_c21_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, 
 /*   graph-state/src/ramsey_counts/space.rs:10-176 (drivers 01-r333.rs,      */
 /*   02-r44.rs): E = N(N-1)/2 edges in colex order (simple_graph/edge.rs),   */
 /*   action id = edge + new_colour * E.  Built for E <= 256, 2..4 colours,   */
-/*   clique sizes 2..5, E*C <= 384 (r333: N=16, r44: N=17).                  */
+/*   clique sizes 2..5, E*C <= 384 (r333: N=16, r44: N=17).  A WIDE engine  */
+/*   (azd_engine_config::max_slots > 0) takes N <= 32, E*C <= 1024 and up to */
+/*   max_slots permitted edges per root (r45: N=24, 276 edges).              */
 /* ------------------------------------------------------------------------- */
 #define AZD_SPACE_RAMSEY 2
 #define AZD_RAMSEY_MAX_N 23
+#define AZD_RAMSEY_WIDE_MAX_N 32
 int azd_ramsey_state_dim(int n, int n_colors);  /* E(2C+1)  space.rs:40 */
 int azd_ramsey_action_dim(int n, int n_colors); /* EC       space.rs:42 */
 int azd_ramsey_key_words(int n, int n_colors);
@@ -181,7 +184,7 @@ typedef struct azd_engine azd_engine;
 
 typedef struct azd_engine_config {
     int space_id;      /* AZD_SPACE_C21 or AZD_SPACE_RAMSEY */
-    int n;             /* vertices N (c21: 4..AZD_C21_MAX_N; Ramsey: 3..AZD_RAMSEY_MAX_N) */
+    int n;             /* vertices N (c21: 4..AZD_C21_MAX_N; Ramsey: 3..AZD_RAMSEY_MAX_N, wide: ..AZD_RAMSEY_WIDE_MAX_N) */
     int batch;         /* BATCH: agents (trees) owned by this engine / GPU */
     int device;        /* HIP device ordinal */
     /* per-tree arena capacities; 0 = default sized for 800 calls per epoch (4096 / 8192 / 32768).  Upper limits, from what a
@@ -209,7 +212,11 @@ typedef struct azd_engine_config {
     /* AZD_SPACE_DENSE only: the most modifiable edge slots a root may bring (= legal actions a node can hold); 0 = 128.  The
      * engine keeps transposition keys over the ranks of a root's slots in 2, 4, 10 or 16 words: up to 128, 256, 640 or 1024
      * slots (E / 2 = 612 at N = 50).  dense_p: edge probability of the fresh roots the device root policy draws (the `p` of
-     * azd_dense_generate_roots; 0 = 0.2). */
+     * azd_dense_generate_roots; 0 = 0.2).
+     * AZD_SPACE_RAMSEY: 0 = today's limits (E <= 256, E*C <= 384, at most 128 / (C - 1) permitted edges per root).  1..E makes the
+     * engine WIDE: 3 <= n <= AZD_RAMSEY_WIDE_MAX_N, E*C <= 1024, a root may bring up to max_slots permitted edges (a node then
+     * holds up to max_slots * (C - 1) legal actions); ActionSet paths only, no Layered wrapper.  Its argmin is read with
+     * azd_engine_ramsey_wide_argmin_data. */
     int max_slots;
     float dense_p;
 } azd_engine_config;
@@ -263,6 +270,16 @@ typedef struct azd_ramsey_argmin {
     int32_t agent;
     uint32_t node;
 } azd_ramsey_argmin;
+
+/* The same for any Ramsey engine, wide ones included (N <= 32: E <= 496 edges) */
+typedef struct azd_ramsey_wide_argmin {
+    uint8_t colors[496];       /* colour per colex edge position (E of them) */
+    uint64_t permitted[8];     /* permitted edge positions */
+    int32_t totals[4];         /* TotalCounts: monochromatic cliques per colour */
+    float eval;
+    int32_t agent;
+    uint32_t node;
+} azd_ramsey_wide_argmin;
 
 /* ArgminData for the dense-graph space: the graph, its open slots, Conjecture2Dot1Cost */
 typedef struct azd_dense_argmin {
@@ -361,7 +378,8 @@ int azd_engine_par_update_model_sharded(azd_engine *e, uint32_t n_obs_tol, void 
 int azd_engine_par_reset_trees(azd_engine *e, const uint8_t *parents, const uint64_t *permitted);
 /* NablaOptimizer::argmin_data (optimizer/mod.rs:361) */
 int azd_engine_argmin_data(azd_engine *e, azd_argmin *out);
-int azd_engine_ramsey_argmin_data(azd_engine *e, azd_ramsey_argmin *out); /* AZD_SPACE_RAMSEY engines */
+int azd_engine_ramsey_argmin_data(azd_engine *e, azd_ramsey_argmin *out); /* AZD_SPACE_RAMSEY engines with E <= 256 */
+int azd_engine_ramsey_wide_argmin_data(azd_engine *e, azd_ramsey_wide_argmin *out); /* every AZD_SPACE_RAMSEY engine */
 int azd_engine_dense_argmin_data(azd_engine *e, azd_dense_argmin *out);   /* AZD_SPACE_DENSE engines */
 /* the agent's live per-edge clique counts [C][E] and totals [4] (RamseyCounts, mod.rs:12-17) */
 int azd_engine_ramsey_agent_counts(azd_engine *e, int agent, int32_t *counts, int32_t *totals);

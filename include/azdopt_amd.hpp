@@ -85,14 +85,18 @@ private:
     int n_;
 };
 
-// RamseySpaceNoEdgeRecolor<B32, N, E, C> (graph-state/src/ramsey_counts/space.rs:10-176)
+// RamseySpaceNoEdgeRecolor<B32, N, E, C> (graph-state/src/ramsey_counts/space.rs:10-176).  max_slots (azd_engine_config::max_slots):
+// 0 = the narrow limits (E <= 256, E*C <= 384); 1..E = a wide engine (N <= 32, E*C <= 1024, up to max_slots permitted edges per root);
+// -1 = 0 where the narrow limits hold, else E.
 class RamseySpaceNoEdgeRecolor {
 public:
-    RamseySpaceNoEdgeRecolor(int n, std::vector<int> sizes, std::vector<float> weights = {})
-        : n_(n), sizes_(std::move(sizes)), weights_(std::move(weights)) {
+    RamseySpaceNoEdgeRecolor(int n, std::vector<int> sizes, std::vector<float> weights = {}, int max_slots = -1)
+        : n_(n), sizes_(std::move(sizes)), weights_(std::move(weights)), max_slots_(max_slots) {
         if (weights_.empty()) weights_.assign(sizes_.size(), 1.0f);
         if (sizes_.size() < 2 || sizes_.size() > 4 || weights_.size() != sizes_.size()) throw Error(AZD_ERR_INVALID_ARGUMENT, "RamseySpaceNoEdgeRecolor");
+        if (max_slots_ < 0) max_slots_ = (n_ <= AZD_RAMSEY_MAX_N && E() <= 256 && KEY_WORDS() <= 6) ? 0 : E();
     }
+    int max_slots() const { return max_slots_; }
     int n() const { return n_; }
     int C() const { return (int)sizes_.size(); }
     int E() const { return n_ * (n_ - 1) / 2; }
@@ -109,6 +113,7 @@ public:
     void configure(azd_engine_config &cfg) const {
         cfg.space_id = AZD_SPACE_RAMSEY;
         cfg.n = n_;
+        cfg.max_slots = max_slots_;
         cfg.n_colors = C();
         for (int c = 0; c < C(); ++c) {
             cfg.clique_sizes[c] = sizes_[(size_t)c];
@@ -120,6 +125,7 @@ private:
     int n_;
     std::vector<int> sizes_;
     std::vector<float> weights_;
+    int max_slots_;
 };
 
 // Connected graphs on N <= 64 vertices, AddOrDeleteEdge actions, every edge slot modified at most once (BASELINE configs[4],
@@ -433,8 +439,8 @@ private:
         return r;
     }
     RamseyArgmin argmin_of(const RamseySpaceNoEdgeRecolor &sp) {
-        azd_ramsey_argmin a;
-        check(azd_engine_ramsey_argmin_data(h_, &a), "argmin_data");
+        azd_ramsey_wide_argmin a; // (every Ramsey engine; azd_ramsey_argmin holds 256 edges)
+        check(azd_engine_ramsey_wide_argmin_data(h_, &a), "argmin_data");
         RamseyArgmin r;
         r.colors.assign(a.colors, a.colors + sp.E());
         r.permitted.assign(a.permitted, a.permitted + (sp.E() + 63) / 64);

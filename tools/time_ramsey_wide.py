@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""Expansions/s of wide Ramsey engines (azd_engine_config::max_slots > 0) in every step form, at the reference's R(4,5) shape
+(05-r45.rs: N 24, [4, 5], 10..=E permitted edges, 512-1024-512 model; fp32 and bf16 weights) and at N = 32, C = 2.  Each form is
+asked for with the engine's flags; the line says which form ran and, when another one did, why (azd_engine_step_form).
+
+    python tools/time_ramsey_wide.py [--batch 256] [--calls 60] [--warmup 10]"""
+import argparse
+import os
+import re
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import azdopt_amd as az  # noqa: E402
+
+FORMS = {"pool": dict(pool_step=True), "async": dict(async_step=True, pool_step=False),
+         "barrier": dict(async_step=False, pool_step=False), "per_call": dict(persistent=False)}
+TOL = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
+SHAPES = [("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "f32"), ("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "bf16"),
+          ("n32c2", 32, [4, 4], [1.0, 1.0], "f32")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--calls", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--hidden", type=int, nargs="*", default=[512, 1024, 512])
+    args = ap.parse_args()
+    B, calls = args.batch, args.calls
+    print("# wide Ramsey engines (tools/time_ramsey_wide.py): batch %d, %d timed calls after %d, hidden %s; r45 = N 24, [4, 5], 10..=276 "
+          "permitted edges; n32c2 = N 32, [4, 4], 10..=496; 'ran' = azd_engine_step_form's form, 'why' its reasons (each once)"
+          % (B, calls, args.warmup, args.hidden))
+    print("# shape  dtype  asked     ran       expansions/s  s/call     why")
+    for tag, n, sizes, weights, dtype in SHAPES:
+        space = az.RamseySpaceNoEdgeRecolor(n, sizes, weights)
+        roots = space.generate_roots(0, B, kmin=10, kmax=space.E)
+        for form, kw in FORMS.items():
+            model = az.ActionModel(B, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, seed=1, dtype=dtype)
+            caps = az.tree_capacities(args.warmup + calls + 8, space.E * (space.C - 1))
+            opt = az.NablaOptimizer.par_new(space, roots, model, B, **kw, **caps)
+            opt.par_roll_out_episodes(TOL, n_calls=args.warmup)
+            e0 = opt.counters()["EXPANSIONS"]
+            t0 = time.perf_counter()
+            opt.par_roll_out_episodes(TOL, n_calls=calls)
+            dt = time.perf_counter() - t0
+            exp = opt.counters()["EXPANSIONS"] - e0
+            ran, why = opt.step_form()
+            # (the engine's reason string names a plan's refusal once per form it fell through, run together: each once, "; " between)
+            parts = [p.strip(" ;") for p in re.split(r"(?=(?:pool|asynchronous|barrier) step:|AZD_ENGINE_)", why) if p.strip(" ;")]
+            why = "; ".join(dict.fromkeys(parts))
+            print("%-7s %-6s %-9s %-9s %12.0f  %.2e   %s" % (tag, dtype, form, ran, exp / dt, dt / calls, why), flush=True)
+            del opt, model
+
+
+if __name__ == "__main__":
+    main()
