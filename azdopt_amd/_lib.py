@@ -21,11 +21,15 @@ ENGINE_NO_PERSISTENT_STEP = 1
 ENGINE_ASYNC_STEP = 2
 ENGINE_BARRIER_STEP = 4
 ENGINE_POOL_STEP = 8
+ENGINE_RAMSEY_U64 = 16  # AZD_ENGINE_RAMSEY_U64: the 64-bit Ramsey tier (n <= 64, E*C <= 2304), beside max_slots > 0
 SPACE_C21 = 1
 SPACE_RAMSEY = 2
 SPACE_DENSE = 3
 RAMSEY_MAX_N = 23       # AZD_RAMSEY_MAX_N
 RAMSEY_WIDE_MAX_N = 32  # AZD_RAMSEY_WIDE_MAX_N: a wide Ramsey engine (EngineConfig.max_slots > 0)
+RAMSEY_U64_MAX_N = 64   # AZD_RAMSEY_U64_MAX_N: the 64-bit tier (ENGINE_RAMSEY_U64)
+RAMSEY_U64_NODE_ACTIONS = 512  # AZD_RAMSEY_U64_NODE_ACTIONS: max_slots * (C - 1) of the 64-bit tier
+RAMSEY_U64_MAX_ACTIONS = 2304  # E*C of the 64-bit tier (keys of 36 words)
 PATH_SET, PATH_SEQUENCE = 0, 1
 
 
@@ -136,6 +140,7 @@ def lib():
     sig("azd_engine_pool_groups", C.c_int, vp, vp, vp, vp)
     sig("azd_engine_ramsey_argmin_data", C.c_int, vp, C.POINTER(RamseyArgmin))
     sig("azd_engine_ramsey_wide_argmin_data", C.c_int, vp, C.POINTER(RamseyWideArgmin))
+    sig("azd_engine_ramsey_argmin_any", C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, f32p, i32p, C.POINTER(C.c_uint32))
     sig("azd_engine_ramsey_agent_counts", C.c_int, vp, C.c_int, vp, vp)
     sig("azd_ramsey_state_dim", C.c_int, C.c_int, C.c_int)
     sig("azd_ramsey_action_dim", C.c_int, C.c_int, C.c_int)

@@ -230,7 +230,12 @@ struct azd_engine {
     azd::RamseyArgminRec *d_argmin_r_side = nullptr;
     // a wide Ramsey engine's kernels write azd::RamseyWideArgminRec where argmin_r points: records of the narrow type it spans
     bool ramsey_wide() const { return a.space == azd::SPACE_RAMSEY && a.KW > azd::MAX_KW; }
-    size_t argmin_r_bytes() const { return ramsey_wide() ? sizeof(azd::RamseyWideArgminRec) : sizeof(azd::RamseyArgminRec); }
+    // the 64-bit tier (AZD_ENGINE_RAMSEY_U64): uint64_t neighbourhood rows of 64 vertices, keys of RAMSEY_U64_KW words, its own record
+    bool ramsey_u64() const { return a.space == azd::SPACE_RAMSEY && a.KW == azd::RAMSEY_U64_KW; }
+    size_t ramsey_nbr_words() const { return ramsey_u64() ? 512 : 128; } // uint32_t words of an agent's [4][NV] rows
+    size_t argmin_r_bytes() const {
+        return ramsey_u64() ? sizeof(azd::RamseyU64ArgminRec) : ramsey_wide() ? sizeof(azd::RamseyWideArgminRec) : sizeof(azd::RamseyArgminRec);
+    }
     size_t argmin_r_recs() const { return (argmin_r_bytes() + sizeof(azd::RamseyArgminRec) - 1) / sizeof(azd::RamseyArgminRec); }
     float *d_pool = nullptr;      // pooled training triple of all ranks (azd_engine_par_update_model_sharded)
     size_t pool_rows = 0;
@@ -526,7 +531,7 @@ int azd_ramsey_action_dim(int n, int n_colors) { return azd::ramsey_action_dim(n
 int azd_ramsey_key_words(int n, int n_colors) { return azd::ramsey_key_words(n, n_colors); }
 int azd_ramsey_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int n_colors, int kmin,
                               int kmax, uint8_t *colors, uint64_t *permitted) {
-    if (!colors || !permitted || count < 0 || n < 3 || n > AZD_RAMSEY_WIDE_MAX_N || n_colors < 2 || n_colors > 4) return AZD_ERR_INVALID_ARGUMENT;
+    if (!colors || !permitted || count < 0 || n < 3 || n > AZD_RAMSEY_U64_MAX_N || n_colors < 2 || n_colors > 4) return AZD_ERR_INVALID_ARGUMENT;
     if (kmin < 0 || kmax < kmin || kmax > azd::ramsey_edges(n)) return AZD_ERR_INVALID_ARGUMENT;
     azd::ramsey_generate_roots(seed, epoch, first_agent, count, n, n_colors, kmin, kmax, colors, permitted);
     return AZD_OK;
@@ -663,6 +668,32 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
             azd::g_last_error = "unsupported dense-graph space (need 4 <= n <= 64, no Layered wrapper, max_slots <= 1024, 0 <= dense_p <= 1)";
             return AZD_ERR_INVALID_ARGUMENT;
         }
+    } else if (cfg->flags & AZD_ENGINE_RAMSEY_U64) { // the 64-bit tier: asked for by name, never chosen from the sizes
+        if (!ramsey || cfg->max_slots == 0) {
+            azd::g_last_error = "AZD_ENGINE_RAMSEY_U64 needs a Ramsey space (AZD_SPACE_RAMSEY) with max_slots > 0";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+        bool ok = cfg->batch > 0 && cfg->n >= 3 && cfg->n <= AZD_RAMSEY_U64_MAX_N && cfg->n_colors >= 2 && cfg->n_colors <= 4;
+        if (ok) {
+            for (int c = 0; c < cfg->n_colors; ++c) ok = ok && cfg->clique_sizes[c] >= 2 && cfg->clique_sizes[c] <= 5;
+            ok = ok && azd::ramsey_action_dim(cfg->n, cfg->n_colors) <= 64 * azd::RAMSEY_U64_KW;
+        }
+        if (!ok) {
+            azd::g_last_error = "unsupported 64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64: need 3 <= n <= 64, 2..4 colours, clique sizes 2..5, E*C <= 2304)";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+        if (cfg->max_slots < 1 || cfg->max_slots > azd::ramsey_edges(cfg->n)) {
+            azd::g_last_error = "64-bit Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+        if ((long)cfg->max_slots * (cfg->n_colors - 1) > AZD_RAMSEY_U64_NODE_ACTIONS) {
+            azd::g_last_error = "64-bit Ramsey space: a node holds 512 actions: need max_slots * (C - 1) <= 512 (azd_engine_config::max_slots)";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+        if (cfg->layers > 1 || cfg->path_kind != AZD_PATH_SET) {
+            azd::g_last_error = "64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
     } else if (ramsey && cfg->max_slots != 0) { // wide engine: max_slots = the most permitted edges a root may bring
         bool ok = cfg->batch > 0 && cfg->n >= 3 && cfg->n <= AZD_RAMSEY_WIDE_MAX_N && cfg->n_colors >= 2 && cfg->n_colors <= 4;
         if (ok) {
@@ -740,6 +771,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         if (cfg->max_slots > 0) { // wide: the device keys padded to the widths ramsey_kernels.hip is built for (RamseyWideSpace<10 / 16>)
             a.KW = a.A <= 640 ? 10 : 16;
             e->ramsey_slots = cfg->max_slots;
+            if (cfg->flags & AZD_ENGINE_RAMSEY_U64) a.KW = azd::RAMSEY_U64_KW; // one width for the tier (ramsey64_kernels.hip)
         }
         for (int c = 0; c < a.C; ++c) {
             a.sizes[c] = cfg->clique_sizes[c];
@@ -767,6 +799,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     // prediction 20, action id 12, actions per node 11, n_t 20 (one per arc at most), exhausted 12 (one per action at most).  The
     // reference's u32 indices (petgraph NodeIndex / EdgeIndex, tree/mod.rs:28-32) have no such limits: a configuration beyond them is
     // refused here, naming the argument, instead of corrupting a neighbouring bit field later.
+    static_assert(AZD_RAMSEY_U64_NODE_ACTIONS == 64 * azd::RAMSEY_U64_CH, "node capacity of the 64-bit Ramsey tier");
     static_assert(AZD_DENSE_MAX_SLOTS <= 2047 && azd::MAX_NODE_ACTIONS <= 2047, "actions per node must fit PredRec's 11-bit count");
     static_assert(AZD_MAX_NODE_CAPACITY == 65536 && AZD_MAX_ARC_CAPACITY == 65535 && AZD_MAX_PREDICTION_CAPACITY == (1 << 20), "limits of the packed records");
     {
@@ -852,8 +885,8 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         }
     }
     if (ramsey) {
-        TRY(e->alloc(&a.root_nbr, B * 128));
-        TRY(e->alloc(&a.cur_nbr, B * 128));
+        TRY(e->alloc(&a.root_nbr, B * e->ramsey_nbr_words()));
+        TRY(e->alloc(&a.cur_nbr, B * e->ramsey_nbr_words()));
         TRY(e->alloc(&a.root_counts, B * (size_t)a.C * a.E));
         TRY(e->alloc(&a.cur_counts, B * (size_t)a.C * a.E));
         TRY(e->alloc(&a.root_tot, B * 4));
@@ -2355,6 +2388,37 @@ int azd_engine_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, in
     return azd_c21_modify_roots_dev(e, seed, epoch, kmin, kmax, roots_out, permitted_out);
 }
 
+// the engine's Ramsey argmin record, whichever of the three the tier's kernels write, as the largest one
+static int ramsey_argmin_fetch(azd_engine *e, azd::RamseyU64ArgminRec *out) {
+    AZD_HIP(hipSetDevice(e->cfg.device));
+    bool side = false; // inside a run-ahead window: the record as of the calls handed out so far
+    {
+        const int st_w = window_argmin_side(e, &side);
+        if (st_w) return st_w;
+    }
+    AZD_HIP(hipStreamSynchronize(e->stream));
+    const void *src = side ? (const void *)e->d_argmin_r_side : (const void *)e->a.argmin_r;
+    memset(out, 0, sizeof(*out));
+    if (e->ramsey_u64()) {
+        AZD_HIP(hipMemcpy(out, src, sizeof(*out), hipMemcpyDeviceToHost));
+        return AZD_OK;
+    }
+#define AZD_WIDEN(REC)                                              \
+    {                                                               \
+        REC r;                                                      \
+        AZD_HIP(hipMemcpy(&r, src, sizeof(r), hipMemcpyDeviceToHost)); \
+        memcpy(out->colors, r.colors, sizeof(r.colors));            \
+        memcpy(out->permitted, r.permitted, sizeof(r.permitted));   \
+        memcpy(out->totals, r.totals, sizeof(r.totals));            \
+        out->eval = r.eval;                                         \
+        out->agent = r.agent;                                       \
+        out->node = r.node;                                         \
+    }
+    if (e->ramsey_wide()) AZD_WIDEN(azd::RamseyWideArgminRec)
+    else AZD_WIDEN(azd::RamseyArgminRec)
+#undef AZD_WIDEN
+    return AZD_OK;
+}
 int azd_engine_ramsey_argmin_data(azd_engine *e, azd_ramsey_argmin *out) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (e->a.space != azd::SPACE_RAMSEY) return AZD_ERR_UNSUPPORTED;
@@ -2362,54 +2426,63 @@ int azd_engine_ramsey_argmin_data(azd_engine *e, azd_ramsey_argmin *out) {
         azd::g_last_error = "E > 256 edges do not fit azd_ramsey_argmin: use azd_engine_ramsey_wide_argmin_data";
         return AZD_ERR_INVALID_ARGUMENT;
     }
-    AZD_HIP(hipSetDevice(e->cfg.device));
-    bool side = false; // inside a run-ahead window: the record as of the calls handed out so far
-    {
-        const int st_w = window_argmin_side(e, &side);
-        if (st_w) return st_w;
-    }
     static_assert(sizeof(azd_ramsey_argmin) == sizeof(azd::RamseyArgminRec), "ABI struct mismatch");
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    if (e->ramsey_wide()) { // the device holds the wide record; its E <= 256 edges fit this one
-        azd::RamseyWideArgminRec w;
-        AZD_HIP(hipMemcpy(&w, side ? e->d_argmin_r_side : e->a.argmin_r, sizeof(w), hipMemcpyDeviceToHost));
-        memset(out, 0, sizeof(*out));
-        memcpy(out->colors, w.colors, (size_t)e->a.E);
-        memcpy(out->permitted, w.permitted, sizeof(out->permitted));
-        memcpy(out->totals, w.totals, sizeof(out->totals));
-        out->eval = w.eval;
-        out->agent = w.agent;
-        out->node = w.node;
-        return AZD_OK;
-    }
-    AZD_HIP(hipMemcpy(out, side ? e->d_argmin_r_side : e->a.argmin_r, sizeof(azd_ramsey_argmin), hipMemcpyDeviceToHost));
+    azd::RamseyU64ArgminRec r;
+    const int st = ramsey_argmin_fetch(e, &r);
+    if (st) return st;
+    memset(out, 0, sizeof(*out));
+    memcpy(out->colors, r.colors, sizeof(out->colors));
+    memcpy(out->permitted, r.permitted, sizeof(out->permitted));
+    memcpy(out->totals, r.totals, sizeof(out->totals));
+    out->eval = r.eval;
+    out->agent = r.agent;
+    out->node = r.node;
     return AZD_OK;
 }
 int azd_engine_ramsey_wide_argmin_data(azd_engine *e, azd_ramsey_wide_argmin *out) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (e->a.space != azd::SPACE_RAMSEY) return AZD_ERR_UNSUPPORTED;
     static_assert(sizeof(azd_ramsey_wide_argmin) == sizeof(azd::RamseyWideArgminRec), "ABI struct mismatch");
-    if (!e->ramsey_wide()) { // a narrow engine's record, widened
-        azd_ramsey_argmin n;
-        const int st = azd_engine_ramsey_argmin_data(e, &n);
-        if (st) return st;
-        memset(out, 0, sizeof(*out));
-        memcpy(out->colors, n.colors, sizeof(n.colors));
-        memcpy(out->permitted, n.permitted, sizeof(n.permitted));
-        memcpy(out->totals, n.totals, sizeof(n.totals));
-        out->eval = n.eval;
-        out->agent = n.agent;
-        out->node = n.node;
-        return AZD_OK;
+    if (e->a.E > 496) { // (colours of 496 edges: azd_ramsey_wide_argmin)
+        azd::g_last_error = "E > 496 edges do not fit azd_ramsey_wide_argmin: use azd_engine_ramsey_argmin_any";
+        return AZD_ERR_INVALID_ARGUMENT;
     }
-    AZD_HIP(hipSetDevice(e->cfg.device));
-    bool side = false;
-    {
-        const int st_w = window_argmin_side(e, &side);
-        if (st_w) return st_w;
+    azd::RamseyU64ArgminRec r;
+    const int st = ramsey_argmin_fetch(e, &r);
+    if (st) return st;
+    memset(out, 0, sizeof(*out));
+    memcpy(out->colors, r.colors, sizeof(out->colors));
+    memcpy(out->permitted, r.permitted, sizeof(out->permitted));
+    memcpy(out->totals, r.totals, sizeof(out->totals));
+    out->eval = r.eval;
+    out->agent = r.agent;
+    out->node = r.node;
+    return AZD_OK;
+}
+int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap, uint64_t *permitted, int permitted_words_cap,
+                                 int32_t *totals, float *eval, int32_t *agent, uint32_t *node) {
+    if (!e || !e->initialised || colors_cap < 0 || permitted_words_cap < 0) return AZD_ERR_INVALID_ARGUMENT;
+    if (e->a.space != azd::SPACE_RAMSEY) return AZD_ERR_UNSUPPORTED;
+    const int PWH = (e->a.E + 63) / 64;
+    if ((colors && colors_cap < e->a.E) || (permitted && permitted_words_cap < PWH)) {
+        azd::g_last_error = "azd_engine_ramsey_argmin_any: need colors_cap >= E bytes and permitted_words_cap >= (E + 63) / 64 words";
+        return AZD_ERR_INVALID_ARGUMENT;
     }
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipMemcpy(out, side ? e->d_argmin_r_side : e->a.argmin_r, sizeof(*out), hipMemcpyDeviceToHost));
+    azd::RamseyU64ArgminRec r;
+    const int st = ramsey_argmin_fetch(e, &r);
+    if (st) return st;
+    if (colors) {
+        memset(colors, 0, (size_t)colors_cap);
+        memcpy(colors, r.colors, (size_t)e->a.E);
+    }
+    if (permitted) {
+        memset(permitted, 0, (size_t)permitted_words_cap * 8);
+        memcpy(permitted, r.permitted, (size_t)PWH * 8);
+    }
+    if (totals) memcpy(totals, r.totals, sizeof(r.totals));
+    if (eval) *eval = r.eval;
+    if (agent) *agent = r.agent;
+    if (node) *node = r.node;
     return AZD_OK;
 }
 int azd_engine_dense_argmin_data(azd_engine *e, azd_dense_argmin *out) {
@@ -2592,15 +2665,16 @@ int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t 
         return AZD_OK;
     }
     if (a.space == azd::SPACE_RAMSEY) { // `parents` receives the colour of every edge (E bytes)
-        uint32_t nbr[128];
-        AZD_HIP(hipMemcpy(nbr, a.cur_nbr + (size_t)agent * 128, sizeof(nbr), hipMemcpyDeviceToHost));
+        uint32_t nbr[512]; // [4][32] uint32_t rows, or the 64-bit tier's [4][64] uint64_t rows
+        const bool u64 = e->ramsey_u64();
+        AZD_HIP(hipMemcpy(nbr, a.cur_nbr + (size_t)agent * e->ramsey_nbr_words(), e->ramsey_nbr_words() * 4, hipMemcpyDeviceToHost));
         if (parents) {
             int pos = 0;
             for (int v = 0; v < a.n; ++v)
                 for (int u = 0; u < v; ++u, ++pos) {
                     parents[pos] = 0;
                     for (int c = 0; c < a.C; ++c)
-                        if ((nbr[c * 32 + v] >> u) & 1u) parents[pos] = (uint8_t)c;
+                        if (u64 ? (nbr[2 * (c * 64 + v) + (u >> 5)] >> (u & 31)) & 1u : (nbr[c * 32 + v] >> u) & 1u) parents[pos] = (uint8_t)c;
                 }
         }
         // (kw_host words: a wide engine's device masks are zero-padded beyond them)

@@ -24,6 +24,8 @@ constexpr int PATH_SET = 0, PATH_SEQUENCE = 1;   // = AZD_PATH_*
 constexpr int SPACE_C21 = 1, SPACE_RAMSEY = 2, SPACE_DENSE = 3; // = AZD_SPACE_* of include/azdopt_amd.h
 constexpr int PRED_CHUNKS = 2;               // a node holds at most 64*PRED_CHUNKS legal actions
 constexpr int MAX_NODE_ACTIONS = 64 * PRED_CHUNKS;
+constexpr int RAMSEY_U64_KW = 36;            // key words of the 64-bit Ramsey tier (AZD_ENGINE_RAMSEY_U64: E*C <= 2304), whatever the shape
+constexpr int RAMSEY_U64_CH = 8;             // ... and the chunks of 64 predictions one of its nodes may hold (= AZD_RAMSEY_U64_NODE_ACTIONS / 64)
 constexpr int FRONTIER_CAP = 256;            // LDS-staged cascade frontier per tree (a level's entries beyond it go to Arenas::fr_spill)
 constexpr int PATH_STACK = 32;               // nodes of the current path kept per agent, root first (deeper levels: not kept)
 constexpr int MAX_TOL = 32;
@@ -125,6 +127,15 @@ struct RamseyArgminRec { // device copy of azd_ramsey_argmin
 struct RamseyWideArgminRec { // device copy of azd_ramsey_wide_argmin (wide Ramsey engines write this one)
     uint8_t colors[496];
     uint64_t permitted[8];
+    int32_t totals[4];
+    float eval;
+    int32_t agent;
+    uint32_t node;
+};
+
+struct RamseyU64ArgminRec { // what the 64-bit tier's kernels write (E <= 1128); read through azd_engine_ramsey_argmin_any
+    uint8_t colors[1128];
+    uint64_t permitted[18];
     int32_t totals[4];
     float eval;
     int32_t agent;
@@ -427,6 +438,16 @@ void ramsey_launch_argmin_log(const Arenas &a, int n_calls, unsigned long long *
 void ramsey_launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream);
 void ramsey_launch_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax,
                                 uint8_t *d_colors, uint64_t *d_perm, void *stream);
+// the 64-bit tier's (ramsey64_kernels.hip: RamseyU64Space); the launchers above forward to them for engines of that tier
+void ramsey64_launch_init_roots(const Arenas &a, const uint8_t *d_colors, const uint64_t *d_permitted, void *stream);
+void ramsey64_launch_add_actions(const Arenas &a, int root_mode, void *stream);
+void ramsey64_launch_rollout(const Arenas &a, const TolTable &tol, void *stream);
+void ramsey64_launch_argmin(const Arenas &a, int init_mode, void *stream);
+void ramsey64_launch_argmin_one(const Arenas &a, int agent, uint32_t node, void *stream);
+void ramsey64_launch_argmin_log(const Arenas &a, int n_calls, unsigned long long *log_key, void *stream);
+void ramsey64_launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream);
+void ramsey64_launch_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax,
+                                  uint8_t *d_colors, uint64_t *d_perm, void *stream);
 bool ramsey_async_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why = nullptr);
 void ramsey_launch_async(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl,
                          const float *params, const void *wpk, uint32_t dyn_stride, size_t dyn_bytes, void *stream);

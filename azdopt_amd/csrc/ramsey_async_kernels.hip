@@ -47,6 +47,10 @@ void ramsey_launch_async(const Arenas &a, const PersistArgs *d_args, const StepL
 bool ramsey_async_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why) {
     const char *dummy;
     if (!why) why = &dummy;
+    if (ramsey_u64(a)) {
+        *why = RAMSEY_U64_NO_RESIDENT("asynchronous step");
+        return false;
+    }
     if (a.B > 65536 || a.node_cap > 65536) { // (agent, node) are packed 16 + 16 bits in the argmin log
         *why = "asynchronous step: more than 65536 agents or nodes per tree";
         return false;

@@ -11,7 +11,8 @@ namespace azd {
 #include "tree_core.inc"
 #include "space_ramsey.inc"
 
-// narrow engines: key widths 1..6; wide engines (max_slots > 0): 10 or 16 (space_ramsey.inc: ramsey_wide)
+// narrow engines: key widths 1..6; wide engines (max_slots > 0): 10 or 16 (space_ramsey.inc: ramsey_wide); the 64-bit tier's 36
+// never reach this switch: the launchers below forward them to ramsey64_kernels.hip, the plans refuse them
 #define DISPATCH_RKW(A, FN, ...)                                  \
     switch ((A).KW) {                                             \
     case 1: FN<RamseySpace<1>>(__VA_ARGS__); break;               \
@@ -66,15 +67,19 @@ static void l_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint6
 }
 void ramsey_launch_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax,
                                 uint8_t *d_colors, uint64_t *d_perm, void *stream) {
+    if (ramsey_u64(a)) return ramsey64_launch_modify_roots(a, seed, epoch, first_agent, kmin, kmax, d_colors, d_perm, stream);
     DISPATCH_RKW(a, l_modify_roots, a, seed, epoch, first_agent, kmin, kmax, d_colors, d_perm, (hipStream_t)stream);
 }
 void ramsey_launch_init_roots(const Arenas &a, const uint8_t *d_colors, const uint64_t *d_permitted, void *stream) {
+    if (ramsey_u64(a)) return ramsey64_launch_init_roots(a, d_colors, d_permitted, stream);
     DISPATCH_RKW(a, l_init_roots, a, d_colors, d_permitted, (hipStream_t)stream);
 }
 void ramsey_launch_add_actions(const Arenas &a, int root_mode, void *stream) {
+    if (ramsey_u64(a)) return ramsey64_launch_add_actions(a, root_mode, stream);
     DISPATCH_RKW(a, l_add_actions, a, root_mode, (hipStream_t)stream);
 }
 void ramsey_launch_rollout(const Arenas &a, const TolTable &tol, void *stream) {
+    if (ramsey_u64(a)) return ramsey64_launch_rollout(a, tol, stream);
     DISPATCH_RKW(a, l_rollout, a, tol, (hipStream_t)stream);
 }
 template <class SP>
@@ -86,15 +91,19 @@ static void l_argmin_one(const Arenas &a, int agent, uint32_t node, hipStream_t 
     k_argmin_one<SP><<<dim3(1), dim3(64), SP::dyn_bytes(a), st>>>(a, agent, node);
 }
 void ramsey_launch_argmin_one(const Arenas &a, int agent, uint32_t node, void *stream) {
+    if (ramsey_u64(a)) return ramsey64_launch_argmin_one(a, agent, node, stream);
     DISPATCH_RKW(a, l_argmin_one, a, agent, node, (hipStream_t)stream);
 }
 void ramsey_launch_argmin_log(const Arenas &a, int n_calls, unsigned long long *log_key, void *stream) {
+    if (ramsey_u64(a)) return ramsey64_launch_argmin_log(a, n_calls, log_key, stream);
     DISPATCH_RKW(a, l_argmin_log, a, n_calls, log_key, (hipStream_t)stream);
 }
 void ramsey_launch_argmin(const Arenas &a, int init_mode, void *stream) {
+    if (ramsey_u64(a)) return ramsey64_launch_argmin(a, init_mode, stream);
     DISPATCH_RKW(a, l_argmin, a, init_mode, (hipStream_t)stream);
 }
 void ramsey_launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream) {
+    if (ramsey_u64(a)) return ramsey64_launch_observe(a, n_obs_tol, stream);
     DISPATCH_RKW(a, l_observe, a, n_obs_tol, (hipStream_t)stream);
 }
 // LDS plan of the persistent step; false when the workgroup does not fit a CU or the in-kernel MLP
@@ -102,6 +111,10 @@ void ramsey_launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream) {
 bool ramsey_persist_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why) {
     const char *dummy;
     if (!why) why = &dummy;
+    if (ramsey_u64(a)) {
+        *why = RAMSEY_U64_NO_RESIDENT("barrier step");
+        return false;
+    }
     size_t per = ramsey_dyn_bytes(a);
     size_t stride = (per + 15) & ~(size_t)15;
     size_t total = stride * PERSIST_WAVES;

@@ -67,6 +67,10 @@ int ramsey_pool_max_resident(const Arenas &a, size_t dyn_bytes, int n_cus) {
 bool ramsey_pool_plan(const Arenas &a, const FusedEval &ev, PoolArgs *pool, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why) {
     const char *dummy;
     if (!why) why = &dummy;
+    if (ramsey_u64(a)) {
+        *why = RAMSEY_U64_NO_RESIDENT("pool step");
+        return false;
+    }
     return pool_plan_common(a, ev, pool, dyn_stride, dyn_bytes, why, ramsey_pool_dyn_bytes(a), ramsey_lds_bytes(a));
 }
 

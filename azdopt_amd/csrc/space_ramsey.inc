@@ -15,11 +15,15 @@
 
 constexpr int RAMSEY_MAX_E = 256;
 constexpr int RAMSEY_WIDE_MAX_E = 496; // N = 32 (wide engines: azd_engine_config::max_slots > 0)
+constexpr int RAMSEY_U64_MAX_E = 1128; // N = 48 (the 64-bit tier: AZD_ENGINE_RAMSEY_U64; E*C <= 2304 bounds E at two colours)
 constexpr int RAMSEY_MAX_C = 4;
 
-template <int ME>
+// W: the neighbourhood word (BitsetGraph<N, B32> / <N, B64>): uint32_t rows of 32 vertices, or uint64_t rows of 64 for the 64-bit tier
+template <int ME, class W = uint32_t>
 struct RamseyLdsT {
-    uint32_t nbr[RAMSEY_MAX_C][32];
+    using Word = W;
+    static constexpr int NV = (int)sizeof(W) * 8; // vertices a row can hold
+    W nbr[RAMSEY_MAX_C][NV];
     uint8_t ev[ME]; // edge position -> larger endpoint (edge.rs:55-65)
     uint8_t eu[ME]; //               -> smaller endpoint
     unsigned long long ctr[NUM_COUNTERS];
@@ -28,6 +32,12 @@ struct RamseyLdsT {
 };
 using RamseyLds = RamseyLdsT<RAMSEY_MAX_E>;
 using RamseyWideLds = RamseyLdsT<RAMSEY_WIDE_MAX_E>;
+using RamseyU64Lds = RamseyLdsT<RAMSEY_U64_MAX_E, uint64_t>;
+
+__device__ __forceinline__ int nb_popc(uint32_t x) { return __popc(x); }
+__device__ __forceinline__ int nb_popc(uint64_t x) { return __popcll(x); }
+__device__ __forceinline__ int nb_ffs(uint32_t x) { return __ffs((int)x); }
+__device__ __forceinline__ int nb_ffs(uint64_t x) { return __ffsll((unsigned long long)x); }
 
 __device__ __forceinline__ uint32_t u32_add(uint32_t a, uint32_t b) { return a + b; }
 // wave-wide sum: the same DPP ladder as wave_min_u32 is an inclusive scan, lane 63 holds the total
@@ -46,38 +56,62 @@ __device__ __forceinline__ int colex_pos(int mx, int mn) { return mx * (mx - 1) 
 
 // bitset_graph/mod.rs:164-185 count_cliques_inside for k <= 3 (clique sizes up to 5).  The
 // reference's `1 + |T| >= size` filter only skips terms that are zero.
-__device__ __forceinline__ int cliques_inside(const uint32_t *nb, uint32_t S, int k) {
+template <class W>
+__device__ __forceinline__ int cliques_inside(const W *nb, W S, int k) {
     if (k == 0) return 1;
-    if (k == 1) return __popc(S);
+    if (k == 1) return nb_popc(S);
     int sum = 0;
-    for (uint32_t r = S; r; r &= r - 1u) {
-        const int u = __ffs((int)r) - 1;
-        const uint32_t T = S & nb[u] & ((1u << u) - 1u);
-        if (k == 2) sum += __popc(T);
+    for (W r = S; r; r &= r - (W)1) {
+        const int u = nb_ffs(r) - 1;
+        const W T = S & nb[u] & (((W)1 << u) - (W)1);
+        if (k == 2) sum += nb_popc(T);
         else
-            for (uint32_t q = T; q; q &= q - 1u) {
-                const int x = __ffs((int)q) - 1;
-                sum += __popc(T & nb[x] & ((1u << x) - 1u));
+            for (W q = T; q; q &= q - (W)1) {
+                const int x = nb_ffs(q) - 1;
+                sum += nb_popc(T & nb[x] & (((W)1 << x) - (W)1));
             }
     }
     return sum;
 }
+
+// (atomicOr has no uint64_t overload: the 64-bit rows go through unsigned long long)
+__device__ __forceinline__ uint32_t *nbr_atomic(uint32_t *p) { return p; }
+__device__ __forceinline__ unsigned long long *nbr_atomic(uint64_t *p) { return reinterpret_cast<unsigned long long *>(p); }
+__device__ __forceinline__ uint32_t nbr_atomic_bit(int b, uint32_t) { return 1u << b; }
+__device__ __forceinline__ unsigned long long nbr_atomic_bit(int b, uint64_t) { return 1ull << b; }
 
 // ramsey_counts/mod.rs:101-164 reassign_color_count_adjustment (edge uv absent from `color`'s graph)
 template <class LDS>
 __device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int E, const bool subtract, const int u,
                                               const int v, const int color, const int size) {
     if (size <= 2) return;
-    const uint32_t *nb = s.nbr[color];
+    using W = typename LDS::Word;
+    const W *nb = s.nbr[color];
     int32_t *cnt = counts + color * E;
-    const uint32_t n_u = nb[u], n_v = nb[v], n_uv = n_u & n_v;
-    {
+    const W n_u = nb[u], n_v = nb[v], n_uv = n_u & n_v;
+    if constexpr (sizeof(W) == 8) {
+        // 64 vertices: one endpoint per pass, lanes over w.  Pass 0: edge {v, w} for w in n_u; pass 1: edge {u, w} for w in n_v.
+        // Within a pass the edges are distinct; the passes run one after the other.
+#pragma unroll 1
+        for (int pass = 0; pass < 2; ++pass) {
+            const int w = LANE;
+            const W mem = pass ? n_v : n_u;
+            const int other = pass ? u : v;
+            if ((mem >> w) & (W)1) {
+                const int change = cliques_inside(nb, n_uv & nb[w], size - 3);
+                if (change != 0) {
+                    const int pos = other > w ? colex_pos(other, w) : colex_pos(w, other);
+                    cnt[pos] += subtract ? -change : change;
+                }
+            }
+        }
+    } else {
         // lanes 0..31: edge {v, w} for w in n_u; lanes 32..63: edge {u, w} for w in n_v
         const int w = LANE & 31;
         const bool hi = LANE >= 32;
-        const uint32_t mem = hi ? n_v : n_u;
+        const W mem = hi ? n_v : n_u;
         const int other = hi ? u : v;
-        if ((mem >> w) & 1u) {
+        if ((mem >> w) & (W)1) {
             const int change = cliques_inside(nb, n_uv & nb[w], size - 3);
             if (change != 0) {
                 const int pos = other > w ? colex_pos(other, w) : colex_pos(w, other);
@@ -87,11 +121,11 @@ __device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int
     }
     if (size == 3) return;
     // edge {w, x} for w < x both in n_uv (tuple_combinations): scalar over w, lanes over x
-    for (uint32_t r = n_uv; r; r &= r - 1u) {
-        const int w = __ffs((int)r) - 1;
-        const uint32_t n_uvw = n_uv & nb[w];
+    for (W r = n_uv; r; r &= r - (W)1) {
+        const int w = nb_ffs(r) - 1;
+        const W n_uvw = n_uv & nb[w];
         const int x = LANE;
-        if (x < 32 && x > w && ((n_uv >> x) & 1u)) {
+        if (x < LDS::NV && x > w && ((n_uv >> x) & (W)1)) {
             const int change = cliques_inside(nb, n_uvw & nb[x], size - 4);
             if (change != 0) cnt[colex_pos(x, w)] += subtract ? -change : change;
         }
@@ -102,15 +136,19 @@ __device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int
 // (below) is today's space: ME = 256, two chunks (MAX_NODE_ACTIONS).  RamseyWideSpace<KW> takes N <= 32 (ME = 496) and nodes of
 // up to 64 KW actions (select_big); the engine picks it when azd_engine_config::max_slots > 0.  The clique counts sit in the dynamic
 // LDS behind the search scratch, which is CORE_DYN_BYTES or select_big's two lists of 64 CH words, whichever is larger.
-template <int KW_, int ME, class ARG, int CH_>
+template <int KW_, int ME, class ARG, int CH_, class W_ = uint32_t>
 struct RamseySpaceBase {
+    using W = W_;                                    // neighbourhood word
+    static constexpr int NV = (int)sizeof(W_) * 8;   // vertices per row: nbr is [RAMSEY_MAX_C][NV] words
+    static constexpr int NBL = RAMSEY_MAX_C * NV / 64; // words of nbr per lane: 2 or 4
+    static_assert(NBL == 2 || NBL == 4, "uint32_t or uint64_t neighbourhood words");
     static constexpr int KW = KW_;
     static constexpr int CH = CH_; // chunks of 64 predictions a node may hold (tree_core.inc: SpaceChunks)
     static constexpr int PW = (KW_ + 1) / 2; // permitted-edge words: E = A / C <= A / 2
     static constexpr bool FRONTIER_SPILL = true; // cascade levels wider than the LDS frontier go to memory (tree_core.inc: cascade)
     static constexpr size_t SCRATCH = (size_t)512 * CH_ > CORE_DYN_BYTES ? (size_t)512 * CH_ : CORE_DYN_BYTES;
     static constexpr int APW = sizeof(ARG::permitted) / 8; // permitted words of the argmin record
-    using Lds = RamseyLdsT<ME>;
+    using Lds = RamseyLdsT<ME, W_>;
     struct St {
         uint64_t perm[PW];
         int32_t tot[RAMSEY_MAX_C];
@@ -144,9 +182,15 @@ struct RamseySpaceBase {
                                                      const uint64_t *perm) {
         // every request first, by every lane, then the values where they go (round 5: the counts' loop -- a request and its LDS store per
         // trip, a runtime trip count -- was a round trip per 64 counts, at the head of every call AND at every return to the root; C E <= 64 KW)
-        uint32_t *dst = &s.nbr[0][0];
-        const uint32_t *src = nbr + (size_t)t * (RAMSEY_MAX_C * 32);
-        const uint32_t n0 = src[LANE], n1 = src[LANE + 64];
+        W *dst = &s.nbr[0][0];
+        const W *src = reinterpret_cast<const W *>(nbr) + (size_t)t * (RAMSEY_MAX_C * NV);
+        // (two named words per lane for the 32-bit rows, four for the 64-bit ones: as an array the two cost the narrow kernels registers)
+        const W n0 = src[LANE], n1 = src[LANE + 64];
+        W n2 = 0, n3 = 0;
+        if constexpr (NBL == 4) {
+            n2 = src[LANE + 128];
+            n3 = src[LANE + 192];
+        }
         const int CE = a.C * a.E;
         int32_t *lc = lds_counts(dyn);
         const int32_t *gc = counts + (size_t)t * CE;
@@ -163,6 +207,10 @@ struct RamseySpaceBase {
         __builtin_amdgcn_sched_barrier(0);
         dst[LANE] = n0;
         dst[LANE + 64] = n1;
+        if constexpr (NBL == 4) {
+            dst[LANE + 128] = n2;
+            dst[LANE + 192] = n3;
+        }
 #pragma unroll
         for (int k = 0; k < KW; ++k) {
             const int i = 64 * k + LANE;
@@ -180,10 +228,14 @@ struct RamseySpaceBase {
     __device__ static __forceinline__ void load_root_cached(const Arenas &a, const int t, Lds &s, const uint32_t dyn, St &st) { load_root(a, t, s, dyn, st); }
     __device__ static __forceinline__ void store_to(const Arenas &a, const int t, Lds &s, const uint32_t dyn, const St &st,
                                                     uint32_t *nbr, int32_t *counts, int32_t *tot, uint64_t *perm) {
-        const uint32_t *src = &s.nbr[0][0];
-        uint32_t *dst = nbr + (size_t)t * (RAMSEY_MAX_C * 32);
+        const W *src = &s.nbr[0][0];
+        W *dst = reinterpret_cast<W *>(nbr) + (size_t)t * (RAMSEY_MAX_C * NV);
         dst[LANE] = src[LANE];
         dst[LANE + 64] = src[LANE + 64];
+        if constexpr (NBL == 4) {
+            dst[LANE + 128] = src[LANE + 128];
+            dst[LANE + 192] = src[LANE + 192];
+        }
         const int CE = a.C * a.E;
         const int32_t *lc = lds_counts(dyn);
         int32_t *gc = counts + (size_t)t * CE;
@@ -207,21 +259,21 @@ struct RamseySpaceBase {
         const int v = s.ev[e], u = s.eu[e];
         int oc = 0;
         for (int c = 0; c < C; ++c)
-            if ((s.nbr[c][u] >> v) & 1u) oc = c; // ColoredCompleteBitsetGraph::color
+            if ((s.nbr[c][u] >> v) & (W)1) oc = c; // ColoredCompleteBitsetGraph::color
         oc = (int)uni((uint32_t)oc);
         int32_t *counts = lds_counts(dyn);
         WAVE_SYNC();
         if (LANE == 0) {
-            s.nbr[oc][v] ^= 1u << u;
-            s.nbr[oc][u] ^= 1u << v;
+            s.nbr[oc][v] ^= (W)1 << u;
+            s.nbr[oc][u] ^= (W)1 << v;
         }
         WAVE_SYNC();
         ramsey_adjust(s, counts, E, true, u, v, oc, a.sizes[oc]);
         ramsey_adjust(s, counts, E, false, u, v, nc, a.sizes[nc]);
         WAVE_SYNC();
         if (LANE == 0) {
-            s.nbr[nc][v] ^= 1u << u;
-            s.nbr[nc][u] ^= 1u << v;
+            s.nbr[nc][v] ^= (W)1 << u;
+            s.nbr[nc][u] ^= (W)1 << v;
         }
         const int32_t d_old = counts[oc * E + e], d_new = counts[nc * E + e];
 #pragma unroll
@@ -256,7 +308,7 @@ struct RamseySpaceBase {
                 const int v = s.ev[e], u = s.eu[e];
                 for (int c = 0; c < C; ++c) {
                     row[c * E + e] = (float)counts[c * E + e];
-                    row[C * E + c * E + e] = (float)((s.nbr[c][v] >> u) & 1u);
+                    row[C * E + c * E + e] = (float)((s.nbr[c][v] >> u) & (W)1);
                 }
                 row[2 * C * E + e] = (float)((st.perm[w] >> LANE) & 1ull);
             }
@@ -270,14 +322,14 @@ struct RamseySpaceBase {
 
     // the C - 1 actions of permitted edge e (larger endpoint v) from its colour classes nbv, counts cnv and prediction entries hv in
     // every colour: predictions begin + rank (C - 1) + k
-    __device__ static __forceinline__ void edge_actions(const Arenas &a, const int e, const int v, const uint32_t (&nbv)[RAMSEY_MAX_C],
+    __device__ static __forceinline__ void edge_actions(const Arenas &a, const int e, const int v, const W (&nbv)[RAMSEY_MAX_C],
                                                         const int32_t (&cnv)[RAMSEY_MAX_C], const float (&hv)[RAMSEY_MAX_C], const float c_s,
                                                         PredRec *preds, const uint32_t begin, const uint32_t rank, FirstPick &fp) {
         const int E = a.E, C = a.C;
         int oc = 0;
 #pragma unroll
         for (int c = 0; c < RAMSEY_MAX_C; ++c)
-            if (c < C && ((nbv[c] >> v) & 1u)) oc = c;
+            if (c < C && ((nbv[c] >> v) & (W)1)) oc = c;
         int32_t cnt_oc = cnv[0];
 #pragma unroll
         for (int c = 1; c < RAMSEY_MAX_C; ++c) cnt_oc = oc == c ? cnv[c] : cnt_oc;
@@ -317,7 +369,7 @@ struct RamseySpaceBase {
         const float c_s = hint ? hint->c : a.nodes[(size_t)t * a.node_cap + node].c;
         const uint2 link = node_link(a, t, node);
         const float *h = a.h_theta + (size_t)t * a.A;
-        const uint32_t *nbr = a.cur_nbr + (size_t)t * (RAMSEY_MAX_C * 32);
+        const W *nbr = reinterpret_cast<const W *>(a.cur_nbr) + (size_t)t * (RAMSEY_MAX_C * NV);
         const int32_t *counts = a.cur_counts + (size_t)t * C * E;
         uint32_t before = 0;
         FirstPick fp;
@@ -332,7 +384,7 @@ struct RamseySpaceBase {
                 const uint64_t pw = a.cur_perm[(size_t)t * KW + w];
                 const int e = w * 64 + LANE, ec = ((pw >> LANE) & 1ull) ? e : 0;
                 const int ev1 = s.ev[ec], eu1 = s.eu[ec];
-                uint32_t nbv[RAMSEY_MAX_C];
+                W nbv[RAMSEY_MAX_C];
                 int32_t cnv[RAMSEY_MAX_C];
                 float hv[RAMSEY_MAX_C];
 #pragma unroll
@@ -341,7 +393,7 @@ struct RamseySpaceBase {
                     cnv[c] = 0;
                     hv[c] = 0.f;
                     if (c < C) {
-                        nbv[c] = nbr[c * 32 + eu1];
+                        nbv[c] = nbr[c * NV + eu1];
                         cnv[c] = counts[c * E + ec];
                         hv[c] = SC1 ? ld_sc1_f32(h + (ec + c * E)) : h[ec + c * E];
                     }
@@ -356,7 +408,7 @@ struct RamseySpaceBase {
         // Every request first (round 5): an edge's colour classes, its counts and its prediction-row entries in EVERY colour do not depend on
         // which colour it has -- requested edge by edge and colour by colour behind that question they were three dependent round trips per
         // 64 edges, nine at the head of every call of R(4,4).  A lane without a permitted edge in a chunk reads edge 0's (unused).
-        uint32_t nbv[PW][RAMSEY_MAX_C];
+        W nbv[PW][RAMSEY_MAX_C];
         int32_t cnv[PW][RAMSEY_MAX_C];
         float hv[PW][RAMSEY_MAX_C];
         int ev_[PW], eu_[PW];
@@ -371,7 +423,7 @@ struct RamseySpaceBase {
                 cnv[w][c] = 0;
                 hv[w][c] = 0.f;
                 if (c < C) {
-                    nbv[w][c] = nbr[c * 32 + eu_[w]];
+                    nbv[w][c] = nbr[c * NV + eu_[w]];
                     cnv[w][c] = counts[c * E + ec];
                     hv[w][c] = SC1 ? ld_sc1_f32(h + (ec + c * E)) : h[ec + c * E];
                 }
@@ -386,7 +438,7 @@ struct RamseySpaceBase {
                 int oc = 0;
 #pragma unroll
                 for (int c = 0; c < RAMSEY_MAX_C; ++c)
-                    if (c < C && ((nbv[w][c] >> v) & 1u)) oc = c;
+                    if (c < C && ((nbv[w][c] >> v) & (W)1)) oc = c;
                 int32_t cnt_oc = cnv[w][0];
 #pragma unroll
                 for (int c = 1; c < RAMSEY_MAX_C; ++c) cnt_oc = oc == c ? cnv[w][c] : cnt_oc;
@@ -420,15 +472,19 @@ struct RamseySpaceBase {
     __device__ static float init_root(const Arenas &a, const int t, Lds &s, const uint32_t dyn, const uint8_t *__restrict__ colors,
                                       const uint64_t *__restrict__ permitted, St &st) {
         const int E = a.E, C = a.C;
-        uint32_t *nb = &s.nbr[0][0];
+        W *nb = &s.nbr[0][0];
         nb[LANE] = 0u;
         nb[LANE + 64] = 0u;
+        if constexpr (NBL == 4) {
+            nb[LANE + 128] = 0u;
+            nb[LANE + 192] = 0u;
+        }
         WAVE_SYNC();
         for (int e = LANE; e < E; e += 64) {
             const int c = colors[(size_t)t * E + e];
             const int v = s.ev[e], u = s.eu[e];
-            atomicOr(&s.nbr[c][v], 1u << u);
-            atomicOr(&s.nbr[c][u], 1u << v);
+            atomicOr(nbr_atomic(&s.nbr[c][v]), nbr_atomic_bit(u, (W)0));
+            atomicOr(nbr_atomic(&s.nbr[c][u]), nbr_atomic_bit(v, (W)0));
         }
         WAVE_SYNC();
         int32_t *counts = lds_counts(dyn);
@@ -438,10 +494,10 @@ struct RamseySpaceBase {
 #pragma unroll
             for (int c = 0; c < RAMSEY_MAX_C; ++c) {
                 if (c < C) {
-                    const uint32_t common = s.nbr[c][v] & s.nbr[c][u];
+                    const W common = s.nbr[c][v] & s.nbr[c][u];
                     const int cnt = cliques_inside(s.nbr[c], common, a.sizes[c] - 2);
                     counts[c * E + e] = cnt;
-                    if ((s.nbr[c][v] >> u) & 1u) part[c] += (uint32_t)cnt;
+                    if ((s.nbr[c][v] >> u) & (W)1) part[c] += (uint32_t)cnt;
                 }
             }
         }
@@ -476,7 +532,7 @@ struct RamseySpaceBase {
             const int v = s.ev[e], u = s.eu[e];
             int col = 0;
             for (int c = 0; c < a.C; ++c)
-                if ((s.nbr[c][v] >> u) & 1u) col = c;
+                if ((s.nbr[c][v] >> u) & (W)1) col = c;
             po[e] = (uint8_t)col;
         }
     }
@@ -489,7 +545,7 @@ struct RamseySpaceBase {
             const int v = s.ev[e], u = s.eu[e];
             int col = 0;
             for (int c = 0; c < C; ++c)
-                if ((s.nbr[c][v] >> u) & 1u) col = c;
+                if ((s.nbr[c][v] >> u) & (W)1) col = c;
             out->colors[e] = (uint8_t)col;
         }
         const float ev = evaluate(a, s, dyn, st, 0);
@@ -542,9 +598,44 @@ struct RamseyWideSpace : RamseySpaceBase<KW_, RAMSEY_WIDE_MAX_E, RamseyWideArgmi
     }
 };
 
+// The 64-bit tier (AZD_ENGINE_RAMSEY_U64): N <= 64 over uint64_t rows, E <= 1128, keys of RAMSEY_U64_KW words (E*C <= 2304) whatever
+// the shape.  A node holds up to 64 RAMSEY_U64_CH actions -- NOT tied to the key width as RamseyWideSpace does: at 36 words
+// select_big's two lists would be 18 KB per wave.
+// (RAMSEY_U64_KW, RAMSEY_U64_CH: engine_types.h)
+struct RamseyU64Space : RamseySpaceBase<RAMSEY_U64_KW, RAMSEY_U64_MAX_E, RamseyU64ArgminRec, RAMSEY_U64_CH, uint64_t> {
+    using Base = RamseySpaceBase<RAMSEY_U64_KW, RAMSEY_U64_MAX_E, RamseyU64ArgminRec, RAMSEY_U64_CH, uint64_t>;
+    static constexpr bool REPLAY_BY_WORD = true;
+    // (write_vec goes straight to the row in memory -- 20 KB at N = 34, four colours -- there is no LDS stage to avoid: the pool step,
+    // whose SP::row_stage ROWS_DIRECT replaces, is not built for this tier)
+    __device__ static __forceinline__ void act(const Arenas &a, typename Base::Lds &s, const uint32_t dyn, typename Base::St &st, const uint32_t aid) {
+        Base::act_body(a, s, dyn, st, aid);
+    }
+    // space.rs:122-153 write_vec, by entry rather than by permitted word (18 words unrolled over four colours are more code than hipcc
+    // inlines: tools/check_kernels.py)
+    __device__ static __forceinline__ void write_vec(const Arenas &a, typename Base::Lds &s, const uint32_t dyn, const typename Base::St &st, float *row) {
+        const int E = a.E, C = a.C, CE = a.C * a.E;
+        const int32_t *counts = Base::lds_counts(dyn);
+        for (int i = LANE; i < CE; i += 64) row[i] = (float)counts[i];
+        for (int e = LANE; e < E; e += 64) {
+            const int v = s.ev[e], u = s.eu[e];
+            for (int c = 0; c < C; ++c) row[CE + c * E + e] = (float)((s.nbr[c][v] >> u) & 1ull);
+        }
+#pragma unroll
+        for (int w = 0; w < Base::PW; ++w) {
+            const int e = w * 64 + LANE;
+            if (e < E) row[2 * CE + e] = (float)((st.perm[w] >> LANE) & 1ull);
+        }
+    }
+};
+
 // host side: what the instantiation an engine's key width selects needs of the LDS (the CU-resident forms' plans).  A wide engine's
-// keys are padded to 10 or 16 words (engine.hip), a width no narrow engine has (1..6): the key width names the engine's mode.
+// keys are padded to 10 or 16 words (engine.hip), a width no narrow engine has (1..6): the key width names the engine's mode;
+// 36 words are the 64-bit tier's.
 static inline bool ramsey_wide(const Arenas &a) { return a.KW > MAX_KW; }
+static inline bool ramsey_u64(const Arenas &a) { return a.KW == RAMSEY_U64_KW; }
+// The 64-bit tier runs the launch-per-phase form only: a workgroup of the CU-resident forms keeps 16 waves' clique counts in LDS,
+// 144 KB of the CU's 160 at the reference's R(3,3,3,3) shape before anything else.
+#define RAMSEY_U64_NO_RESIDENT(FORM) FORM ": not built for the 64-bit Ramsey tier (it runs one launch per phase)"
 static inline size_t ramsey_dyn_bytes(const Arenas &a) {
     return a.KW == 16 ? RamseyWideSpace<16>::dyn_bytes(a) : a.KW == 10 ? RamseyWideSpace<10>::dyn_bytes(a) : RamseySpace<1>::dyn_bytes(a);
 }

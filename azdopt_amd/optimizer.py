@@ -99,6 +99,8 @@ class NablaOptimizer:
             cfg.dense_p = space.p
         if space.SPACE_ID == _lib.SPACE_RAMSEY:
             cfg.max_slots = getattr(space, "MAX_SLOTS", 0)
+            if getattr(space, "U64", False):
+                cfg.flags |= _lib.ENGINE_RAMSEY_U64
             cfg.n_colors = space.C
             for i in range(space.C):
                 cfg.clique_sizes[i] = space.sizes[i]
@@ -197,6 +199,8 @@ class NablaOptimizer:
     def argmin_data(self):
         """optimizer/mod.rs:361"""
         if self.space.SPACE_ID == _lib.SPACE_RAMSEY:
+            if getattr(self.space, "U64", False) or self.space.E > 496:  # by capacities: every Ramsey engine, the 64-bit tier's E <= 1128 too
+                return RamseyArgminData(self.ramsey_argmin_any(), self.space)
             if self.space.E > 256:  # (azd_ramsey_argmin holds 256 colours)
                 rec = _lib.RamseyWideArgmin()
                 _lib.check(self._L.azd_engine_ramsey_wide_argmin_data(self._h, C.byref(rec)), "ramsey_wide_argmin_data")
@@ -304,6 +308,17 @@ class NablaOptimizer:
         _lib.check(self._L.azd_engine_agent_state(self._h, agent, _lib.ptr(parents), _lib.ptr(permitted), _lib.ptr(path),
                                                   C.byref(pos), C.byref(lam), C.byref(mu)), "agent_state")
         return dict(parents=parents, permitted=permitted, path=path, state_pos=pos.value, lambda1=lam.value, matching=mu.value)
+
+    def ramsey_argmin_any(self):
+        """azd_engine_ramsey_argmin_any: the argmin record of any Ramsey engine (colors [E], permitted [(E + 63) // 64 words],
+        totals [4], eval, agent, node) as a record with the fixed-size calls' field names"""
+        import types
+        E = self.space.E
+        colors, permitted, totals = np.zeros(E, np.uint8), np.zeros((E + 63) // 64, np.uint64), np.zeros(4, np.int32)
+        ev, agent, node = C.c_float(), C.c_int32(), C.c_uint32()
+        _lib.check(self._L.azd_engine_ramsey_argmin_any(self._h, _lib.ptr(colors), E, _lib.ptr(permitted), len(permitted), _lib.ptr(totals),
+                                                         C.byref(ev), C.byref(agent), C.byref(node)), "ramsey_argmin_any")
+        return types.SimpleNamespace(colors=colors, permitted=permitted, totals=totals, eval=ev.value, agent=agent.value, node=node.value)
 
     def ramsey_agent_counts(self, agent):
         """live (counts [C, E], totals [C]) of an agent's RamseyCounts state"""

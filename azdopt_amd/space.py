@@ -111,11 +111,14 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
 
     SPACE_ID = _lib.SPACE_RAMSEY
 
-    def __init__(self, n, sizes, weights=None, max_slots=None):
+    def __init__(self, n, sizes, weights=None, max_slots=None, u64=None):
         """`max_slots`: the most permitted edges a root may bring.  0 keeps the engine's narrow limits (E <= 256, E*C <= 384,
         at most 128 / (C - 1) permitted edges); 1..E makes it a WIDE engine (N <= 32, E*C <= 1024; a node holds up to
         max_slots * (C - 1) legal actions).  None: 0 where the narrow limits hold, else E -- every edge may be permitted,
-        as 05-r45.rs:83 allows."""
+        as 05-r45.rs:83 allows.
+        `u64`: the 64-bit tier (N <= 64, E*C <= 2304, max_slots * (C - 1) <= 512; 03-r3333.rs: N = 34, four colours).  None: only
+        where neither 32-bit tier takes the shape; True forces it (any shape it takes), False forbids it.  With it, max_slots = None
+        is as many edges as a node of 512 actions holds, at most E."""
         self.n = int(n)
         self.sizes = [int(x) for x in sizes]
         self.weights = [1.0] * len(self.sizes) if weights is None else [float(x) for x in weights]
@@ -125,9 +128,15 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
         self.STATE_DIM = L.azd_ramsey_state_dim(self.n, self.C)    # space.rs:40
         self.ACTION_DIM = L.azd_ramsey_action_dim(self.n, self.C)  # space.rs:42
         self.KEY_WORDS = L.azd_ramsey_key_words(self.n, self.C)
+        if u64 is None:
+            u64 = self.n > _lib.RAMSEY_WIDE_MAX_N or self.ACTION_DIM > 1024
+        self.U64 = bool(u64)
         if max_slots is None:
             narrow = self.n <= _lib.RAMSEY_MAX_N and self.E <= 256 and self.KEY_WORDS <= 6
-            max_slots = 0 if narrow else self.E
+            if self.U64:
+                max_slots = min(self.E, _lib.RAMSEY_U64_NODE_ACTIONS // (self.C - 1))
+            else:
+                max_slots = 0 if narrow else self.E
         self.MAX_SLOTS = int(max_slots)
 
     @property
@@ -137,6 +146,11 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
     @property
     def wide(self):
         return self.MAX_SLOTS > 0
+
+    @property
+    def tier(self):
+        """"narrow" (E <= 256, E*C <= 384), "wide" (N <= 32, E*C <= 1024) or "u64" (N <= 64, E*C <= 2304)"""
+        return "u64" if self.U64 else "wide" if self.wide else "narrow"
 
     def default_permitted_range(self):
         """02-r44.rs:83: 12..=(E / 2), clamped to what one node can hold (max_slots edges on a wide engine)"""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""The reference's Ramsey drivers (graph-state/examples/01-r333.rs, 02-r44.rs, 05-r45.rs) over the MI355X engine.
+"""The reference's Ramsey drivers (graph-state/examples/01-r333.rs, 02-r44.rs, 03-r3333.rs, 05-r45.rs) over the MI355X engine.
 
-    python examples/ramsey.py r333|r44|r45 [--epochs 250] [--episodes N] [--batch B]"""
+    python examples/ramsey.py r333|r44|r3333|r45 [--epochs 250] [--episodes N] [--batch B]"""
 import argparse
 import os
 import sys
@@ -22,6 +22,12 @@ DRIVERS = {  # N, SIZES, BATCH, episodes, n_as_tol, num_permitted_edges_range.st
     # oracle shares.  The driver's roll-out takes a decay (:134) this engine does not have: r44's tolerances stand in.
     "r45": dict(n=24, sizes=[4, 5], batch=128, episodes=3200, kmin=10, kmax="E", weights=[1.0, 0.4685 / (1.0 - 0.4685)], lr=3e-4,
                 tol=([200, 200, 100, 100, 50, 50, 25, 25], 10), tag="01-r333-grad"),
+    # 03-r3333.rs:34-63,83-84,98,121-124: N 34, [3,3,3,3], unit weights, uniform root colours, 10..=30 permitted edges, a ReLU head
+    # (:57), lr 3e-4, 800 episodes: the engine's 64-bit tier (64-bit neighbourhood words, as the driver's B64).  Its roll-out takes a
+    # decay (:124) this engine does not have: r44's tolerances stand in, as for r45.  The driver's modify_root keeps
+    # c == c_root_star; the engine's root policy is 02-r44's threshold rule.
+    "r3333": dict(n=34, sizes=[3, 3, 3, 3], batch=512, episodes=800, kmin=10, kmax=30, lr=3e-4, final_act=az._lib.ACT_RELU,
+                  tol=([200, 200, 100, 100, 50, 50, 25, 25], 10), tag="01-r333-grad"),
 }
 
 
@@ -41,7 +47,8 @@ def main():
     episodes = args.episodes or d["episodes"]
 
     space = az.RamseySpaceNoEdgeRecolor(d["n"], d["sizes"], d.get("weights", [1.0] * len(d["sizes"])))
-    model = az.ActionModel(batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=d.get("lr", 1e-4), l2=1e-6, seed=args.seed)
+    model = az.ActionModel(batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=d.get("lr", 1e-4), l2=1e-6, seed=args.seed,
+                           final_act=d.get("final_act", az._lib.ACT_SIGMOID))
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         writer = sinks.TensorboardWriter(open(os.path.join(args.out, "tfevents-losses"), "wb"))
@@ -51,6 +58,8 @@ def main():
     kmin, kmax = d["kmin"], space.default_permitted_range()[1]   # ..=(E / 2), capped by what a node holds
     if d.get("kmax") == "E":
         kmax = space.E
+    elif d.get("kmax"):
+        kmax = d["kmax"]
     C = len(d["sizes"])
     caps = az.tree_capacities(episodes, kmax * (C - 1))  # (limits of the packed records: 65536 nodes, 65535 arcs, 2^20 predictions)
     opt = az.NablaOptimizer.par_new(space, space.generate_roots(args.seed, batch, kmin=kmin, kmax=kmax), model, batch, **caps)

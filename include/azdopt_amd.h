@@ -73,11 +73,16 @@ int azd_c21_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, 
 /*   action id = edge + new_colour * E.  Built for E <= 256, 2..4 colours,   */
 /*   clique sizes 2..5, E*C <= 384 (r333: N=16, r44: N=17).  A WIDE engine  */
 /*   (azd_engine_config::max_slots > 0) takes N <= 32, E*C <= 1024 and up to */
-/*   max_slots permitted edges per root (r45: N=24, 276 edges).              */
+/*   max_slots permitted edges per root (r45: N=24, 276 edges).  With       */
+/*   AZD_ENGINE_RAMSEY_U64 beside max_slots > 0 the engine runs the 64-BIT   */
+/*   tier: N <= 64 over 64-bit neighbourhood words, E*C <= 2304, a node of   */
+/*   up to 512 actions (r3333: N=34, four colours, 561 edges).               */
 /* ------------------------------------------------------------------------- */
 #define AZD_SPACE_RAMSEY 2
 #define AZD_RAMSEY_MAX_N 23
 #define AZD_RAMSEY_WIDE_MAX_N 32
+#define AZD_RAMSEY_U64_MAX_N 64
+#define AZD_RAMSEY_U64_NODE_ACTIONS 512 /* 64-bit tier: max_slots * (C - 1) may not exceed it */
 int azd_ramsey_state_dim(int n, int n_colors);  /* E(2C+1)  space.rs:40 */
 int azd_ramsey_action_dim(int n, int n_colors); /* EC       space.rs:42 */
 int azd_ramsey_key_words(int n, int n_colors);
@@ -184,7 +189,7 @@ typedef struct azd_engine azd_engine;
 
 typedef struct azd_engine_config {
     int space_id;      /* AZD_SPACE_C21 or AZD_SPACE_RAMSEY */
-    int n;             /* vertices N (c21: 4..AZD_C21_MAX_N; Ramsey: 3..AZD_RAMSEY_MAX_N, wide: ..AZD_RAMSEY_WIDE_MAX_N) */
+    int n;             /* vertices N (c21: 4..AZD_C21_MAX_N; Ramsey: 3..AZD_RAMSEY_MAX_N, wide: ..AZD_RAMSEY_WIDE_MAX_N, 64-bit tier: ..AZD_RAMSEY_U64_MAX_N) */
     int batch;         /* BATCH: agents (trees) owned by this engine / GPU */
     int device;        /* HIP device ordinal */
     /* per-tree arena capacities; 0 = default sized for 800 calls per epoch (4096 / 8192 / 32768).  Upper limits, from what a
@@ -216,7 +221,7 @@ typedef struct azd_engine_config {
      * AZD_SPACE_RAMSEY: 0 = today's limits (E <= 256, E*C <= 384, at most 128 / (C - 1) permitted edges per root).  1..E makes the
      * engine WIDE: 3 <= n <= AZD_RAMSEY_WIDE_MAX_N, E*C <= 1024, a root may bring up to max_slots permitted edges (a node then
      * holds up to max_slots * (C - 1) legal actions); ActionSet paths only, no Layered wrapper.  Its argmin is read with
-     * azd_engine_ramsey_wide_argmin_data. */
+     * azd_engine_ramsey_wide_argmin_data.  With AZD_ENGINE_RAMSEY_U64 in `flags`: the 64-bit tier's limits (see the flag). */
     int max_slots;
     float dense_p;
 } azd_engine_config;
@@ -248,6 +253,13 @@ typedef struct azd_engine_config {
  * CUs of their own pull batches of up to 16 posted rows (full MFMA row tiles, an undisturbed weight stream).
  * Populations larger than the resident waves share them instead of running as serial rounds of workgroups. */
 #define AZD_ENGINE_POOL_STEP 8u
+/* AZD_SPACE_RAMSEY with max_slots > 0 only: the 64-bit tier.  3 <= n <= AZD_RAMSEY_U64_MAX_N (neighbourhoods are 64-bit words, the
+ * reference's B64), E*C <= 2304 (keys of 36 words: N = 34 at four colours, 39 at three, 48 at two), 2..4 colours, clique sizes
+ * 2..5, 1 <= max_slots <= E and max_slots * (C - 1) <= AZD_RAMSEY_U64_NODE_ACTIONS; ActionSet paths only, no Layered wrapper.
+ * Never chosen from the sizes: without the flag every limit, kernel and error text is the 32-bit tiers'.  Shapes a 32-bit wide
+ * engine takes are accepted too and give the same trees.  Runs the launch-per-phase step form (the CU-resident forms fall back,
+ * azd_engine_step_form gives the reason); its argmin is read with azd_engine_ramsey_argmin_any. */
+#define AZD_ENGINE_RAMSEY_U64 16u
 
 /* ArgminData<State, Cost> (az-discrete-opt/src/log.rs:1-11) for the c21 space */
 typedef struct azd_argmin {
@@ -379,7 +391,12 @@ int azd_engine_par_reset_trees(azd_engine *e, const uint8_t *parents, const uint
 /* NablaOptimizer::argmin_data (optimizer/mod.rs:361) */
 int azd_engine_argmin_data(azd_engine *e, azd_argmin *out);
 int azd_engine_ramsey_argmin_data(azd_engine *e, azd_ramsey_argmin *out); /* AZD_SPACE_RAMSEY engines with E <= 256 */
-int azd_engine_ramsey_wide_argmin_data(azd_engine *e, azd_ramsey_wide_argmin *out); /* every AZD_SPACE_RAMSEY engine */
+int azd_engine_ramsey_wide_argmin_data(azd_engine *e, azd_ramsey_wide_argmin *out); /* AZD_SPACE_RAMSEY engines with E <= 496 */
+/* The same for EVERY Ramsey engine, with the caller's capacities instead of a fixed-size record: `colors` receives E bytes
+ * (colors_cap >= E), `permitted` (E + 63) / 64 words (permitted_words_cap >= that); what lies beyond is zeroed.  totals[4].  Any
+ * output pointer may be NULL. */
+int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap, uint64_t *permitted, int permitted_words_cap,
+                                 int32_t *totals, float *eval, int32_t *agent, uint32_t *node);
 int azd_engine_dense_argmin_data(azd_engine *e, azd_dense_argmin *out);   /* AZD_SPACE_DENSE engines */
 /* the agent's live per-edge clique counts [C][E] and totals [4] (RamseyCounts, mod.rs:12-17) */
 int azd_engine_ramsey_agent_counts(azd_engine *e, int agent, int32_t *counts, int32_t *totals);

@@ -23,6 +23,7 @@
 // (04-c21-tree.rs:136-138).  Error behaviour: where the reference panics (unreachable!(), index out of bounds on an
 // over-full arena, a CUDA error), these throw azdopt::Error carrying the AZD_ERR_* status; nothing falls back to the CPU.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -87,16 +88,21 @@ private:
 
 // RamseySpaceNoEdgeRecolor<B32, N, E, C> (graph-state/src/ramsey_counts/space.rs:10-176).  max_slots (azd_engine_config::max_slots):
 // 0 = the narrow limits (E <= 256, E*C <= 384); 1..E = a wide engine (N <= 32, E*C <= 1024, up to max_slots permitted edges per root);
-// -1 = 0 where the narrow limits hold, else E.
+// -1 = 0 where the narrow limits hold, else E.  u64 (AZD_ENGINE_RAMSEY_U64): 1 = the 64-bit tier (N <= 64, E*C <= 2304, max_slots * (C - 1)
+// <= 512; 03-r3333.rs: N = 34, four colours), 0 = never, -1 = only where neither 32-bit tier takes the shape; with it max_slots = -1 is
+// as many edges as a node of 512 actions holds, at most E.
 class RamseySpaceNoEdgeRecolor {
 public:
-    RamseySpaceNoEdgeRecolor(int n, std::vector<int> sizes, std::vector<float> weights = {}, int max_slots = -1)
-        : n_(n), sizes_(std::move(sizes)), weights_(std::move(weights)), max_slots_(max_slots) {
+    RamseySpaceNoEdgeRecolor(int n, std::vector<int> sizes, std::vector<float> weights = {}, int max_slots = -1, int u64 = -1)
+        : n_(n), sizes_(std::move(sizes)), weights_(std::move(weights)), max_slots_(max_slots), u64_(u64) {
         if (weights_.empty()) weights_.assign(sizes_.size(), 1.0f);
         if (sizes_.size() < 2 || sizes_.size() > 4 || weights_.size() != sizes_.size()) throw Error(AZD_ERR_INVALID_ARGUMENT, "RamseySpaceNoEdgeRecolor");
+        if (u64_ < 0) u64_ = (n_ > AZD_RAMSEY_WIDE_MAX_N || ACTION_DIM() > 1024) ? 1 : 0;
+        if (max_slots_ < 0 && u64_) max_slots_ = std::min(E(), AZD_RAMSEY_U64_NODE_ACTIONS / (C() - 1));
         if (max_slots_ < 0) max_slots_ = (n_ <= AZD_RAMSEY_MAX_N && E() <= 256 && KEY_WORDS() <= 6) ? 0 : E();
     }
     int max_slots() const { return max_slots_; }
+    bool u64() const { return u64_ != 0; }
     int n() const { return n_; }
     int C() const { return (int)sizes_.size(); }
     int E() const { return n_ * (n_ - 1) / 2; }
@@ -114,6 +120,7 @@ public:
         cfg.space_id = AZD_SPACE_RAMSEY;
         cfg.n = n_;
         cfg.max_slots = max_slots_;
+        if (u64_) cfg.flags |= AZD_ENGINE_RAMSEY_U64;
         cfg.n_colors = C();
         for (int c = 0; c < C(); ++c) {
             cfg.clique_sizes[c] = sizes_[(size_t)c];
@@ -125,7 +132,7 @@ private:
     int n_;
     std::vector<int> sizes_;
     std::vector<float> weights_;
-    int max_slots_;
+    int max_slots_, u64_;
 };
 
 // Connected graphs on N <= 64 vertices, AddOrDeleteEdge actions, every edge slot modified at most once (BASELINE configs[4],
@@ -296,7 +303,7 @@ public:
         cfg.arc_capacity = arc_capacity;
         cfg.prediction_capacity = prediction_capacity;
         cfg.first_agent = first_agent;
-        cfg.flags = flags;
+        cfg.flags |= flags; // (beside what the space asked for: AZD_ENGINE_RAMSEY_U64)
         cfg.path_kind = path_kind;
         cfg.layers = layers;
         azd_engine *h = nullptr;
@@ -439,15 +446,13 @@ private:
         return r;
     }
     RamseyArgmin argmin_of(const RamseySpaceNoEdgeRecolor &sp) {
-        azd_ramsey_wide_argmin a; // (every Ramsey engine; azd_ramsey_argmin holds 256 edges)
-        check(azd_engine_ramsey_wide_argmin_data(h_, &a), "argmin_data");
-        RamseyArgmin r;
-        r.colors.assign(a.colors, a.colors + sp.E());
-        r.permitted.assign(a.permitted, a.permitted + (sp.E() + 63) / 64);
-        r.clique_counts.assign(a.totals, a.totals + sp.C());
-        r.eval = a.eval;
-        r.agent = a.agent;
-        r.node = a.node;
+        RamseyArgmin r; // (by capacities: every Ramsey engine, the 64-bit tier's E <= 1128 edges too)
+        r.colors.resize((size_t)sp.E());
+        r.permitted.resize((size_t)(sp.E() + 63) / 64);
+        int32_t totals[4];
+        check(azd_engine_ramsey_argmin_any(h_, r.colors.data(), (int)r.colors.size(), r.permitted.data(), (int)r.permitted.size(), totals,
+                                           &r.eval, &r.agent, &r.node), "argmin_data");
+        r.clique_counts.assign(totals, totals + sp.C());
         return r;
     }
     DenseArgmin argmin_of(const DenseGraphSpace &sp) {

@@ -2,8 +2,11 @@
 """Expansions/s of wide Ramsey engines (azd_engine_config::max_slots > 0) in every step form, at the reference's R(4,5) shape
 (05-r45.rs: N 24, [4, 5], 10..=E permitted edges, 512-1024-512 model; fp32 and bf16 weights) and at N = 32, C = 2.  Each form is
 asked for with the engine's flags; the line says which form ran and, when another one did, why (azd_engine_step_form).
+--preset u64: the 64-bit tier (AZD_ENGINE_RAMSEY_U64) at the reference's R(3,3,3,3) shape (03-r3333.rs: N 34, four colours, 10..=30
+permitted edges, 512-1024-512 model with a ReLU head, 512 agents) and r45 under the flag beside r45 on the 32-bit tier (what the
+wider word costs).
 
-    python tools/time_ramsey_wide.py [--batch 256] [--calls 60] [--warmup 10]"""
+    python tools/time_ramsey_wide.py [--preset wide|u64] [--batch 256] [--calls 60] [--warmup 10]"""
 import argparse
 import os
 import re
@@ -19,10 +22,18 @@ FORMS = {"pool": dict(pool_step=True), "async": dict(async_step=True, pool_step=
 TOL = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
 SHAPES = [("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "f32"), ("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "bf16"),
           ("n32c2", 32, [4, 4], [1.0, 1.0], "f32")]
+# (tag, n, sizes, weights, dtype, options: u64 = the tier, kmax, batch, relu head)
+U64_SHAPES = [("r3333", 34, [3, 3, 3, 3], [1.0] * 4, "f32", dict(u64=True, kmax=30, batch=512, relu=True)),
+              ("r3333", 34, [3, 3, 3, 3], [1.0] * 4, "bf16", dict(u64=True, kmax=30, batch=512, relu=True)),
+              ("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "bf16", dict(u64=False)),
+              ("r45u64", 24, [4, 5], [1.0, 0.4685 / 0.5315], "bf16", dict(u64=True)),
+              ("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "f32", dict(u64=False, forms=["per_call"])),
+              ("r45u64", 24, [4, 5], [1.0, 0.4685 / 0.5315], "f32", dict(u64=True, forms=["per_call"]))]
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--preset", choices=["wide", "u64"], default="wide")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--calls", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
@@ -32,13 +43,22 @@ def main():
     print("# wide Ramsey engines (tools/time_ramsey_wide.py): batch %d, %d timed calls after %d, hidden %s; r45 = N 24, [4, 5], 10..=276 "
           "permitted edges; n32c2 = N 32, [4, 4], 10..=496; 'ran' = azd_engine_step_form's form, 'why' its reasons (each once)"
           % (B, calls, args.warmup, args.hidden))
+    if args.preset == "u64":
+        print("# --preset u64: r3333 = N 34, [3,3,3,3], 10..=30 permitted edges, ReLU head, batch 512, the 64-bit tier; r45u64 = r45 on the 64-bit "
+              "tier (AZD_ENGINE_RAMSEY_U64) beside r45 on the 32-bit wide tier")
     print("# shape  dtype  asked     ran       expansions/s  s/call     why")
-    for tag, n, sizes, weights, dtype in SHAPES:
-        space = az.RamseySpaceNoEdgeRecolor(n, sizes, weights)
-        roots = space.generate_roots(0, B, kmin=10, kmax=space.E)
+    for tag, n, sizes, weights, dtype, *rest in (U64_SHAPES if args.preset == "u64" else SHAPES):
+        o = rest[0] if rest else {}
+        B = o.get("batch", args.batch)
+        space = az.RamseySpaceNoEdgeRecolor(n, sizes, weights, u64=o.get("u64"))
+        kmax = o.get("kmax", space.E)
+        roots = space.generate_roots(0, B, kmin=10, kmax=kmax)
         for form, kw in FORMS.items():
-            model = az.ActionModel(B, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, seed=1, dtype=dtype)
-            caps = az.tree_capacities(args.warmup + calls + 8, space.E * (space.C - 1))
+            if form not in o.get("forms", FORMS):
+                continue
+            model = az.ActionModel(B, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, seed=1, dtype=dtype,
+                                   **(dict(final_act=az._lib.ACT_RELU) if o.get("relu") else {}))
+            caps = az.tree_capacities(args.warmup + calls + 8, kmax * (space.C - 1))
             opt = az.NablaOptimizer.par_new(space, roots, model, B, **kw, **caps)
             opt.par_roll_out_episodes(TOL, n_calls=args.warmup)
             e0 = opt.counters()["EXPANSIONS"]
