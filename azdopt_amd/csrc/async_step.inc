@@ -1,4 +1,4 @@
-// async_step.inc -- included by tree_kernels.hip (inside namespace azd), after persistent_step.inc.
+// async_step.inc -- included by the asynchronous and pool units (inside namespace azd), after persistent_step.inc.
 //
 // Asynchronous CU-resident form of NablaOptimizer::par_roll_out_episodes.  As in k_persist one
 // workgroup = 16 wavefronts = 16 agents lives on one CU for `n_calls` calls, but the agents are
@@ -472,4 +472,35 @@ __global__ __launch_bounds__(PERSIST_WAVES * 64) void k_async(const PersistArgs 
             for (int k = 24; k < NUM_COUNTERS; ++k) ctr[k] += s.ctr[k];
         }
     }
+}
+
+// ---------------------------------------------------------------- host: LDS plan shared by the spaces
+// No evaluator buffers in LDS: a wave's region (wave_dyn_bytes: SP::dyn_bytes) holds its search scratch during a call and its
+// row's activations [x][h0][h1] while the agent waits.  wave_lds_bytes: a wave's static block (SP::Lds).
+static bool async_plan_common(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why,
+                              const size_t wave_dyn_bytes, const size_t wave_lds_bytes) {
+    if (a.B > 65536 || a.node_cap > 65536) { // (agent, node) are packed 16 + 16 bits in the argmin log
+        *why = "asynchronous step: more than 65536 agents or nodes per tree";
+        return false;
+    }
+    size_t stride = (wave_dyn_bytes + 15) & ~(size_t)15;
+    if (ev.kind == 3) {
+        for (int l = 0; l < ev.n_layers; ++l)
+            if (ev.dims[l] % (l == 0 ? 4 : 16) != 0) { // tile tasks walk K in steps of 16; x is zero-padded
+                *why = "asynchronous step: hidden widths must be multiples of 16 and the input width a multiple of 4";
+                return false;
+            }
+        // + the 16-B-per-wave skew
+        size_t rows = ((size_t)((ev.dims[0] + 15) & ~15) + (size_t)ev.hid[0] + (size_t)ev.hid[1]) * sizeof(float) + 16 * PERSIST_WAVES;
+        if (rows > stride) stride = (rows + 15) & ~(size_t)15;
+    }
+    const size_t total = stride * PERSIST_WAVES;
+    const size_t static_lds = PERSIST_WAVES * (wave_lds_bytes + 16) + sizeof(AsyncCtl) + 256;
+    if (total + static_lds > 160 * 1024) {
+        *why = "asynchronous step: 16 rows of activations do not fit the CU's 160 KB of LDS";
+        return false;
+    }
+    *dyn_stride = (uint32_t)stride;
+    *dyn_bytes = total;
+    return true;
 }

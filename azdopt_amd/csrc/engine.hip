@@ -16,6 +16,7 @@
 #include "c21_host.h"
 #include "engine_types.h"
 #include "evaluator.h"
+#include "space_ops.h"
 
 namespace azd {
 
@@ -40,6 +41,15 @@ static int device_ok(int device) {
         return AZD_ERR_INVALID_ARGUMENT;
     }
     return AZD_OK;
+}
+
+// the table of an engine's space and tier (space_ops.h): c21's and Ramsey's are put together from their three units' parts
+static const SpaceOps *space_ops(const Arenas &a) {
+    static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops()};
+    static const SpaceOps ramsey = {ramsey_phase_ops(), ramsey_async_ops(), ramsey_pool_ops()};
+    if (a.space == SPACE_DENSE) return &dense_ops();
+    if (a.space == SPACE_RAMSEY) return a.KW == RAMSEY_U64_KW ? &ramsey64_ops() : &ramsey;
+    return &c21;
 }
 
 // ------------------------------------------------------------------ simple evaluators
@@ -117,6 +127,7 @@ int azd_evaluator::ensure_staging(int batch) {
 struct azd_engine {
     azd_engine_config cfg;
     azd::Arenas a;
+    const azd::SpaceOps *ops = nullptr; // the launchers and LDS plans of the engine's space and tier (space_ops.h)
     azd_evaluator *ev = nullptr;
     hipStream_t stream = nullptr;
     std::vector<void *> allocs;
@@ -186,7 +197,7 @@ struct azd_engine {
     int kw_host = 0;
     int ramsey_slots = 0;             // Ramsey: the most permitted edges a root may bring (max_slots; else MAX_NODE_ACTIONS / (C - 1))
     int dense_slots = 0;              // 64 * a.KW: the most modifiable slots a root may bring
-    uint64_t *d_stage_slots = nullptr; // device root policy: the slot masks it drew, [B][(E + 63) / 64]
+    uint64_t *d_stage_slots = nullptr; // device root policy: the slot masks it drew, [B][(E + 63) / 64] (dense-graph space; else d_stage_perm)
     std::vector<uint64_t> dense_packed;
     std::vector<uint64_t> ramsey_perm_pad; // a wide Ramsey engine's roots: permitted masks padded to the device's a.KW words
     // pool step (agents multiplexed over searcher waves, evaluator workgroups on CUs of their own)
@@ -784,6 +795,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         a.eval_slope = azd::c21_eval_slope(cfg->n);
         azd::c21_lambda_bracket(cfg->n, &a.lam_lo, &a.lam_hi);
     }
+    e->ops = azd::space_ops(a);
     a.S_inner = a.S;
     a.S = a.S_inner * a.layers; // Layered<L, Space>::STATE_DIM (nabla/space/mod.rs:53)
     if (ev && (ev->state_dim != a.S || ev->action_dim != a.A)) {
@@ -957,6 +969,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     }
     TRY(e->alloc(&e->d_stage_parents, B * (size_t)(dense ? 8 * a.n : ramsey ? a.E : a.n)));
     TRY(e->alloc(&e->d_stage_perm, B * (size_t)(dense ? 17 * a.KW : a.KW)));
+    if (!dense) e->d_stage_slots = e->d_stage_perm; // (SpaceOps::modify_roots)
     {
         hipError_t he = hipHostMalloc((void **)&e->h_status, sizeof(azd::StatusRec));
         if (he == hipSuccess) he = hipHostMalloc((void **)&e->h_argmin, sizeof(azd::ArgminRec));
@@ -1033,14 +1046,14 @@ int azd_engine_par_new_begin(azd_engine *e, const uint8_t *parents, const uint64
     e->counters_by_wave = false;
     AZD_HIP(hipMemsetAsync(a.status, 0, sizeof(azd::StatusRec), e->stream));
     e->seen_improved = 0;
-    azd::launch_init_roots(a, e->d_stage_parents, e->d_stage_perm, e->stream);
+    e->ops->init_roots(a, e->d_stage_parents, e->d_stage_perm, e->stream);
     AZD_HIP(hipMemsetAsync(a.h_theta, 0, (size_t)a.B * a.A * 4, e->stream)); // vec![0.; ..] at :71
     AZD_HIP(hipGetLastError());
     return AZD_OK;
 }
 static int new_finish(azd_engine *e) {
-    azd::launch_add_actions(e->a, 1, e->stream);
-    azd::launch_argmin(e->a, 1, e->stream);
+    e->ops->add_actions(e->a, 1, e->stream);
+    e->ops->argmin(e->a, 1, e->stream);
     e->initialised = true;
     return sync_status(e);
 }
@@ -1069,7 +1082,7 @@ int azd_engine_roll_out_begin(azd_engine *e, const uint32_t *tol, int n_tol, uin
     int st = fill_tol(t, tol, n_tol, dflt);
     if (st) return st;
     e->time_begin(0);
-    azd::launch_rollout(e->a, t, e->stream);
+    e->ops->rollout(e->a, t, e->stream);
     e->time_end();
     return sync_status(e);
 }
@@ -1078,8 +1091,8 @@ int azd_engine_roll_out_end(azd_engine *e, const float *h_theta, int *improved) 
     if (!e || !h_theta || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ENTER(e);
     AZD_HIP(hipMemcpyAsync(e->a.h_theta, h_theta, (size_t)e->a.B * e->a.A * 4, hipMemcpyHostToDevice, e->stream));
-    azd::launch_add_actions(e->a, 0, e->stream);
-    azd::launch_argmin(e->a, 0, e->stream);
+    e->ops->add_actions(e->a, 0, e->stream);
+    e->ops->argmin(e->a, 0, e->stream);
     int st = sync_status(e);
     if (improved) *improved = (int)(e->h_status->improved - e->seen_improved);
     e->seen_improved = e->h_status->improved;
@@ -1191,7 +1204,7 @@ static int pool_finish_launch(azd_engine *e, const azd::FusedEval &fe, const azd
     uint32_t as = 0;
     size_t ab = 0;
     const char *why_t = "";
-    if (!azd::async_plan(e->a, fe, &as, &ab, &why_t)) {
+    if (!e->ops->async_plan(e->a, fe, &as, &ab, &why_t)) {
         e->time_collect();
         azd::g_last_error = std::string("pool step: a queue wait ran into its bound, and the asynchronous step cannot take over: ") + why_t;
         return AZD_ERR_UNREACHABLE;
@@ -1207,7 +1220,7 @@ static int pool_finish_launch(azd_engine *e, const azd::FusedEval &fe, const azd
     sl.hashed = fe.kind == 4;
     sl.window = 0;
     e->time_begin(0);
-    azd::launch_async(e->a, e->d_pargs, sl, fe.params, fe.wpk, as, ab, e->stream);
+    e->ops->launch_async(e->a, e->d_pargs, sl, fe.params, fe.wpk, as, ab, e->stream);
     e->time_end();
     e->log_clean = true; // k_argmin_log1 has replayed and cleared it
     e->step_form = AZD_STEP_ASYNC;
@@ -1471,18 +1484,18 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
                 azd::launch_park(a, e->d_resume, k, -1, 1, e->stream);
                 st = evaluate_rows();
                 if (st) return st;
-                azd::launch_add_actions(a, 0, e->stream);
+                e->ops->add_actions(a, 0, e->stream);
             }
             for (int r = 0; r < rounds; ++r) {
                 azd::launch_park(a, e->d_resume, k, r, 1, e->stream);
-                azd::launch_rollout(a, t, e->stream);
+                e->ops->rollout(a, t, e->stream);
                 st = evaluate_rows();
                 if (st) return st;
-                azd::launch_add_actions(a, 0, e->stream);
+                e->ops->add_actions(a, 0, e->stream);
                 azd::launch_log_candidates_resume(a, e->d_log_key, e->d_resume, k, r, e->stream);
             }
             azd::launch_park(a, e->d_resume, k, 0, 0, e->stream); // everyone back
-            azd::launch_argmin_log(a, k, e->d_log_key, e->stream);  // replays the k calls and leaves the log clean
+            e->ops->argmin_log(a, k, e->d_log_key, e->stream);  // replays the k calls and leaves the log clean
             e->log_clean = true;
             AZD_HIP(hipGetLastError());
             st = fetch_status(e);
@@ -1526,9 +1539,9 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
     const char *why_a = "", *why_b = "";
     const char *why_p = "";
     azd::PoolArgs pool = e->pool;
-    bool use_pool = fusable && e->pool_step && azd::pool_plan(e->a, fe, &pool, &dyn_stride, &dyn_bytes, &why_p);
-    bool use_async = fusable && !use_pool && !e->barrier_step && azd::async_plan(e->a, fe, &dyn_stride, &dyn_bytes, &why_a);
-    bool use_barrier = fusable && !use_pool && !use_async && azd::persist_plan(e->a, fe, &dyn_stride, &dyn_bytes, &why_b);
+    bool use_pool = fusable && e->pool_step && e->ops->pool_plan(e->a, fe, &pool, &dyn_stride, &dyn_bytes, &why_p);
+    bool use_async = fusable && !use_pool && !e->barrier_step && e->ops->async_plan(e->a, fe, &dyn_stride, &dyn_bytes, &why_a);
+    bool use_barrier = fusable && !use_pool && !use_async && e->ops->persist_plan(e->a, fe, &dyn_stride, &dyn_bytes, &why_b);
     // which form runs is part of the result a caller may want to check (azd_engine_step_form): the launch-per-phase
     // form is several times slower than the CU-resident ones
     e->step_form = use_pool ? AZD_STEP_POOL : use_async ? AZD_STEP_ASYNC : use_barrier ? AZD_STEP_BARRIER : AZD_STEP_PER_CALL;
@@ -1610,7 +1623,7 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
         // above ask for and whatever the device can hold (a CU mask, a partition, another kernel's LDS).  Clamp the grid to the
         // co-resident capacity the runtime reports, evaluators first (they are dispatched first: a grid of evaluators alone
         // would never let a searcher in); with no room for one of each the call takes the asynchronous step instead.
-        int capacity = azd::pool_max_resident(e->a, dyn_bytes, e->n_cus);
+        int capacity = e->ops->pool_max_resident(e->a, dyn_bytes, e->n_cus);
         if (const char *env = getenv("AZD_POOL_MAX_RESIDENT")) capacity = atoi(env); // tests: a device that holds fewer workgroups
         if (fe.kind < 3) n_eval = 0; // TrivialModel / in-wave hash stream: nothing to serve
         if (n_eval + n_search > capacity) {
@@ -1739,8 +1752,8 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
         e->pool_search_waves = (n_search - pool.n_express) * 16 + pool.n_express * (int)pool.express_waves;
     }
     if (e->pool_step && fusable && !use_pool) { // the pool step was wanted and cannot run: the next form down
-        use_async = !e->barrier_step && azd::async_plan(e->a, fe, &dyn_stride, &dyn_bytes, &why_a);
-        use_barrier = !use_async && azd::persist_plan(e->a, fe, &dyn_stride, &dyn_bytes, &why_b);
+        use_async = !e->barrier_step && e->ops->async_plan(e->a, fe, &dyn_stride, &dyn_bytes, &why_a);
+        use_barrier = !use_async && e->ops->persist_plan(e->a, fe, &dyn_stride, &dyn_bytes, &why_b);
         if (!use_async) e->step_reason += why_a;
         if (!use_async && !use_barrier && *why_b) e->step_reason += std::string("; ") + why_b;
     }
@@ -1817,13 +1830,13 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
             sl.groups = (use_pool && pool.grp_g > 0) ? 1 : 0;
             e->time_begin(0);
             if (use_pool) {
-                azd::launch_pool(e->a, e->d_pargs, sl, fe.params, fe.wpk, pool_blocks, dyn_stride, dyn_bytes, e->stream);
+                e->ops->launch_pool(e->a, e->d_pargs, sl, fe.params, fe.wpk, pool_blocks, dyn_stride, dyn_bytes, e->stream);
 #ifndef AZD_PHASE_PROFILE
                 e->counters_by_wave = true;
 #endif
-            } else if (use_async) azd::launch_async(e->a, e->d_pargs, sl, fe.params, fe.wpk, dyn_stride, dyn_bytes, e->stream);
+            } else if (use_async) e->ops->launch_async(e->a, e->d_pargs, sl, fe.params, fe.wpk, dyn_stride, dyn_bytes, e->stream);
             else {
-                azd::launch_persist(e->a, e->d_pargs, sl, e->d_log_node, dyn_stride, dyn_bytes, e->stream);
+                e->ops->launch_persist(e->a, e->d_pargs, sl, e->d_log_node, dyn_stride, dyn_bytes, e->stream);
                 e->log_clean = false;
             }
             e->time_end();
@@ -1912,9 +1925,9 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
                     if (as.tn <= 0) continue;
                     hipGraph_t g = nullptr;
                     AZD_HIP(hipStreamBeginCapture(e->sub_stream[i], hipStreamCaptureModeThreadLocal));
-                    azd::launch_rollout(as, t, e->sub_stream[i]);
+                    e->ops->rollout(as, t, e->sub_stream[i]);
                     st = e->ev->write_predictions_rows(as.t0, as.tn, e->a.state_vecs, e->a.state_vecs16, e->a.S16, e->a.h_theta, e->sub_stream[i]);
-                    azd::launch_add_actions(as, 0, e->sub_stream[i]);
+                    e->ops->add_actions(as, 0, e->sub_stream[i]);
                     azd::launch_log_candidates(as, e->d_log_key, e->d_call_ctr + i, e->sub_stream[i]);
                     hipError_t he = hipStreamEndCapture(e->sub_stream[i], &g);
                     if (st) {
@@ -1953,7 +1966,7 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
                         AZD_HIP(hipEventRecord(e->sub_join[i], e->sub_stream[i]));
                         AZD_HIP(hipStreamWaitEvent(e->stream, e->sub_join[i], 0));
                     }
-                azd::launch_argmin_log(e->a, k, e->d_log_key, e->stream); // replays the k calls and leaves the log clean
+                e->ops->argmin_log(e->a, k, e->d_log_key, e->stream); // replays the k calls and leaves the log clean
                 left -= k;
             }
             e->ev->calls += (uint64_t)n_calls;
@@ -1965,12 +1978,12 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
                 e->call_graph = nullptr;
                 hipGraph_t g = nullptr;
                 AZD_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-                azd::launch_rollout(e->a, t, e->stream);
+                e->ops->rollout(e->a, t, e->stream);
                 const uint64_t calls_before = e->ev->calls;
                 st = e->ev->write_predictions_dev16(e->a.B, e->a.state_vecs, e->a.state_vecs16, e->a.S16, e->a.h_theta, e->stream);
                 e->ev->calls = calls_before;
-                azd::launch_add_actions(e->a, 0, e->stream);
-                azd::launch_argmin(e->a, 0, e->stream);
+                e->ops->add_actions(e->a, 0, e->stream);
+                e->ops->argmin(e->a, 0, e->stream);
                 hipError_t he = hipStreamEndCapture(e->stream, &g);
                 if (st) {
                     if (g) (void)hipGraphDestroy(g);
@@ -1989,12 +2002,12 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
         } else
             for (int c = 0; c < n_calls; ++c) {
                 e->time_begin(0);
-                azd::launch_rollout(e->a, t, e->stream);
+                e->ops->rollout(e->a, t, e->stream);
                 e->time_end();
                 st = run_evaluator(e); // :175-176
                 if (st) return st;
-                azd::launch_add_actions(e->a, 0, e->stream);
-                azd::launch_argmin(e->a, 0, e->stream); // :190
+                e->ops->add_actions(e->a, 0, e->stream);
+                e->ops->argmin(e->a, 0, e->stream); // :190
             }
     }
     st = status_fresh ? check_status(e) : sync_status(e);
@@ -2100,7 +2113,7 @@ static int window_argmin_side(azd_engine *e, bool *side) {
         azd::Arenas a2 = e->a;
         a2.argmin = e->d_argmin_side;
         a2.argmin_r = e->d_argmin_r_side;
-        azd::launch_argmin_one(a2, (int)((w.best_key >> 16) & 0xFFFFull), (uint32_t)(w.best_key & 0xFFFFull), e->stream);
+        e->ops->argmin_one(a2, (int)((w.best_key >> 16) & 0xFFFFull), (uint32_t)(w.best_key & 0xFFFFull), e->stream);
         AZD_HIP(hipGetLastError());
         w.side_key = w.best_key;
     }
@@ -2154,7 +2167,7 @@ int azd_engine_observe_dev(azd_engine *e, uint32_t n_obs_tol, const float **d_st
                            const float **d_w) {
     if (!e || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ENTER(e);
-    azd::launch_observe(e->a, n_obs_tol, e->stream);
+    e->ops->observe(e->a, n_obs_tol, e->stream);
     AZD_HIP(hipStreamSynchronize(e->stream));
     AZD_HIP(hipGetLastError());
     if (d_state_vecs) *d_state_vecs = e->a.state_vecs;
@@ -2175,7 +2188,7 @@ int azd_engine_par_update_model(azd_engine *e, uint32_t n_obs_tol, float *loss) 
     if (!e || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (!e->ev) return AZD_ERR_NO_EVALUATOR;
     AZD_ENTER(e);
-    azd::launch_observe(e->a, n_obs_tol, e->stream);
+    e->ops->observe(e->a, n_obs_tol, e->stream);
     AZD_HIP(hipGetLastError());
     float l = 0.f;
     int st = e->ev->update_model_dev(e->a.B, e->a.state_vecs, e->a.obs, e->a.weights, &l, e->stream); // :279-280
@@ -2245,7 +2258,7 @@ int azd_engine_par_update_model_sharded(azd_engine *e, uint32_t n_obs_tol, void 
         return AZD_ERR_CAPACITY;
     }
     float *g_sv = e->d_pool, *g_obs = g_sv + ns, *g_w = g_obs + na;
-    azd::launch_observe(a, n_obs_tol, e->stream); // :262-278 on this rank's trees
+    e->ops->observe(a, n_obs_tol, e->stream); // :262-278 on this rank's trees
     AZD_HIP(hipGetLastError());
     // rank order = global agent order (shards are contiguous agent ranges); the collectives run on the engine's
     // stream, behind k_observe and ahead of the optimiser step
@@ -2276,13 +2289,13 @@ int azd_engine_reset_begin(azd_engine *e, const uint8_t *parents, const uint64_t
     if (st) return st;
     const azd::Arenas &a = e->a;
     AZD_HIP(hipMemsetAsync(&a.status->failed, 0, sizeof(unsigned long long), e->stream));
-    azd::launch_init_roots(a, e->d_stage_parents, e->d_stage_perm, e->stream);
+    e->ops->init_roots(a, e->d_stage_parents, e->d_stage_perm, e->stream);
     AZD_HIP(hipMemsetAsync(a.h_theta, 0, (size_t)a.B * a.A * 4, e->stream)); // h_theta_host.fill(0.) at :347
     AZD_HIP(hipGetLastError());
     return AZD_OK;
 }
 static int reset_finish(azd_engine *e) {
-    azd::launch_add_actions(e->a, 1, e->stream); // :350-358; num_inspected_nodes = 0 via cand_* in init_roots
+    e->ops->add_actions(e->a, 1, e->stream); // :350-358; num_inspected_nodes = 0 via cand_* in init_roots
     return sync_status(e);
 }
 int azd_engine_reset_end(azd_engine *e, const float *h_theta) {
@@ -2336,11 +2349,9 @@ int azd_engine_par_reset_trees_c21(azd_engine *e, uint64_t seed, uint64_t epoch,
     if (!e->ev) return AZD_ERR_NO_EVALUATOR;
     AZD_ENTER(e);
     const azd::Arenas &a = e->a;
-    if (a.space == azd::SPACE_DENSE)
-        azd::dense_launch_modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->stream);
-    else azd::launch_c21_modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->stream);
+    e->ops->modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->stream);
     AZD_HIP(hipMemsetAsync(&a.status->failed, 0, sizeof(unsigned long long), e->stream));
-    azd::launch_init_roots(a, e->d_stage_parents, e->d_stage_perm, e->stream);
+    e->ops->init_roots(a, e->d_stage_parents, e->d_stage_perm, e->stream);
     AZD_HIP(hipMemsetAsync(a.h_theta, 0, (size_t)a.B * a.A * 4, e->stream));
     AZD_HIP(hipGetLastError());
     st = run_evaluator(e);
@@ -2354,8 +2365,8 @@ int azd_c21_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int k
     if (!parents_out || !permitted_out) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ENTER(e);
     const azd::Arenas &a = e->a;
+    e->ops->modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->stream);
     if (a.space == azd::SPACE_DENSE) { // roots_out: neighbourhoods (8 n bytes per root); permitted_out: slot masks in kw_host words per root
-        azd::dense_launch_modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->stream);
         const int ow = (a.E + 63) / 64;
         std::vector<uint64_t> sl((size_t)a.B * ow);
         AZD_HIP(hipMemcpyAsync(parents_out, e->d_stage_parents, (size_t)a.B * a.n * 8, hipMemcpyDeviceToHost, e->stream));
@@ -2366,7 +2377,6 @@ int azd_c21_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int k
         for (int i = 0; i < a.B; ++i) memcpy(permitted_out + (size_t)i * e->kw_host, &sl[(size_t)i * ow], (size_t)ow * 8);
         return AZD_OK;
     }
-    azd::launch_c21_modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->stream);
     AZD_HIP(hipMemcpyAsync(parents_out, e->d_stage_parents, (size_t)a.B * (a.space == azd::SPACE_RAMSEY ? a.E : a.n), hipMemcpyDeviceToHost, e->stream));
     if (e->ramsey_wide()) { // device masks are a.KW words, the caller's kw_host
         std::vector<uint64_t> pm((size_t)a.B * a.KW);
@@ -2538,7 +2548,7 @@ int azd_engine_debug_tile_forward(azd_engine *e, const float *states, float *pre
     uint32_t dyn_stride = 0;
     size_t dyn_bytes = 0;
     const char *why = "";
-    if (e->a.space == azd::SPACE_DENSE || !e->ev->fused_desc(&fe) || fe.kind != 3 || !azd::pool_plan(e->a, fe, &pool, &dyn_stride, &dyn_bytes, &why)) {
+    if (e->a.space == azd::SPACE_DENSE || !e->ev->fused_desc(&fe) || fe.kind != 3 || !e->ops->pool_plan(e->a, fe, &pool, &dyn_stride, &dyn_bytes, &why)) {
         azd::g_last_error = "debug_tile_forward: needs the c21 or the Ramsey space with an MLP evaluator the pool step can serve";
         return AZD_ERR_INVALID_ARGUMENT;
     }

@@ -359,100 +359,4 @@ struct PersistArgs { // argument block of the persistent step, read from device 
     PoolArgs pool;
 };
 
-// kernel launchers (tree_kernels.hip); all asynchronous on `stream`.  The *_plan functions lay out the LDS of a
-// CU-resident step; when the model or the population does not fit they return false and say why in *why.
-void launch_init_roots(const Arenas &a, const uint8_t *d_parents, const uint64_t *d_permitted, void *stream);
-void launch_add_actions(const Arenas &a, int root_mode, void *stream);
-void launch_rollout(const Arenas &a, const TolTable &tol, void *stream);
-void launch_argmin(const Arenas &a, int init_mode, void *stream);
-// launch-per-phase form over sub-populations on streams of their own (engine.hip): the candidates of agents a.t0 .. a.t0 + a.tn - 1
-// since their last inspection go into log_key[*call_ctr] (atomic min), the counter is bumped; replayed by launch_argmin_log
-void launch_log_candidates(const Arenas &a, unsigned long long *log_key, uint32_t *call_ctr, void *stream);
-void launch_argmin_log(const Arenas &a, int n_calls, unsigned long long *log_key, void *stream);
-// one candidate (agent, node) replayed into the argmin records `a` points at; StatusRec untouched (run-ahead window, engine.hip)
-void launch_argmin_one(const Arenas &a, int agent, uint32_t node, void *stream);
-void ramsey_launch_argmin_one(const Arenas &a, int agent, uint32_t node, void *stream);
-void launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream);
-bool async_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why = nullptr);
-void launch_async(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl,
-                  const float *params, const void *wpk, uint32_t dyn_stride, size_t dyn_bytes, void *stream);
-bool persist_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why = nullptr);
-// pool step (pool_kernels.hip / ramsey_pool_kernels.hip): the plan also lays out an evaluator batch (pool->eval_*)
-bool pool_plan(const Arenas &a, const FusedEval &ev, PoolArgs *pool, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why = nullptr);
-void launch_pool(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, const float *params,
-                 const void *wpk, int n_blocks, uint32_t dyn_stride, size_t dyn_bytes, void *stream);
-// workgroups of k_pool the device can hold at once with this much dynamic LDS (occupancy query x CUs): the pool step's
-// searcher and evaluator workgroups spin-wait on each other, so all of them must be resident together
-int pool_max_resident(const Arenas &a, size_t dyn_bytes, int n_cus);
-int ramsey_pool_max_resident(const Arenas &a, size_t dyn_bytes, int n_cus);
-// after an aborted pool launch: resume[t] for k_async (StepLaunch::resume) from the trees and PoolArgs::pend
-void launch_pool_resume_scan(const Arenas &a, const PoolArgs &pool, int n_calls, uint32_t *resume, void *stream);
-// test entry: the in-kernel evaluator's forward (pool_eval's staging + mlp_tile_task) for rows given by the host
-hipError_t launch_tile_forward(const FusedEval &ev, const PoolArgs &pool, int n_rows, const float *states, float *out, void *stream);
-bool ramsey_pool_plan(const Arenas &a, const FusedEval &ev, PoolArgs *pool, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why = nullptr);
-void ramsey_launch_pool(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, const float *params,
-                        const void *wpk, int n_blocks, uint32_t dyn_stride, size_t dyn_bytes, void *stream);
-void launch_probe_xcc(uint32_t *d_out, int n_blocks, void *stream); // HW_REG_XCC_ID of every block of a launch (tests)
-
-// the launch-per-phase kernels for SPACE_DENSE (dense_kernels.hip); the c21 entry points forward to them.  The space's
-// state vector (3E + 1 floats) does not fit the CU-resident forms' LDS plans: it runs one launch per phase.
-void dense_launch_init_roots(const Arenas &a, const uint8_t *d_adj, const uint64_t *d_packed, void *stream);
-void dense_launch_add_actions(const Arenas &a, int root_mode, void *stream);
-void dense_launch_rollout(const Arenas &a, const TolTable &tol, void *stream);
-void dense_launch_argmin(const Arenas &a, int init_mode, void *stream);
-void dense_launch_argmin_log(const Arenas &a, int n_calls, unsigned long long *log_key, void *stream);
-void dense_launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream);
-// pool step of the dense-graph space: searcher workgroups only (k_pool_search); the evaluator is a stream of batched GEMM launches
-// over the rows the searchers have posted, collected by k_ext_take and handed back by k_ext_deliver (pool_step.inc)
-bool dense_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
-void dense_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
-                              size_t dyn_bytes, void *stream);
-int dense_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
-void launch_ext_take(const PoolArgs &pool, uint32_t *rows, uint32_t *home, uint32_t *n, unsigned long long *t0, void *stream);
-// recovery of an aborted dense pool launch (engine.hip): park (round >= 0: the agents whose calls are through by that round; -1: the
-// agents that are not waiting for a row) / unpark (mode 0), and the candidates of round r under the call each agent is really in
-void launch_park(const Arenas &a, const uint32_t *resume, int n_calls, int round, int park, void *stream);
-void launch_log_candidates_resume(const Arenas &a, unsigned long long *log_key, const uint32_t *resume, int n_calls, int round, void *stream);
-void launch_ext_hash_rows(const PersistArgs *d_args, const uint32_t *rows, const uint32_t *n, uint32_t cap, float *h_theta, void *stream);
-void launch_ext_deliver(const PoolArgs &pool, const Arenas &a, const uint32_t *rows, const uint32_t *home, const uint32_t *n, uint32_t cap,
-                        const unsigned long long *t0, void *stream);
-void launch_persist(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl,
-                    uint32_t *log_node, uint32_t dyn_stride, size_t dyn_bytes, void *stream);
-void launch_c21_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax,
-                             uint8_t *d_parents, uint64_t *d_perm, void *stream);
-// dense-graph space: d_packed = what k_init_roots takes (17 KW words per root), d_slots = the drawn slot masks ((E + 63) / 64 words per root)
-void dense_launch_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax,
-                               uint8_t *d_adj, uint64_t *d_packed, uint64_t *d_slots, void *stream);
-void launch_hash_predictions(float *d_out, int batch, int action_dim, uint64_t seed, uint64_t first_agent,
-                             uint64_t call, void *stream);
-void launch_probe_cost(const uint8_t *d_parents, int n, int count, int reps, int full, double *d_lam, int *d_mu,
-                       void *stream);
-void launch_probe_math(const float *d_in, float *d_out, int n, void *stream); // sqrtf / sub parity probe (tests)
-
-// the same launchers for SPACE_RAMSEY (ramsey_kernels.hip); the functions above forward to them
-void ramsey_launch_init_roots(const Arenas &a, const uint8_t *d_colors, const uint64_t *d_permitted, void *stream);
-void ramsey_launch_add_actions(const Arenas &a, int root_mode, void *stream);
-void ramsey_launch_rollout(const Arenas &a, const TolTable &tol, void *stream);
-void ramsey_launch_argmin(const Arenas &a, int init_mode, void *stream);
-void ramsey_launch_argmin_log(const Arenas &a, int n_calls, unsigned long long *log_key, void *stream);
-void ramsey_launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream);
-void ramsey_launch_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax,
-                                uint8_t *d_colors, uint64_t *d_perm, void *stream);
-// the 64-bit tier's (ramsey64_kernels.hip: RamseyU64Space); the launchers above forward to them for engines of that tier
-void ramsey64_launch_init_roots(const Arenas &a, const uint8_t *d_colors, const uint64_t *d_permitted, void *stream);
-void ramsey64_launch_add_actions(const Arenas &a, int root_mode, void *stream);
-void ramsey64_launch_rollout(const Arenas &a, const TolTable &tol, void *stream);
-void ramsey64_launch_argmin(const Arenas &a, int init_mode, void *stream);
-void ramsey64_launch_argmin_one(const Arenas &a, int agent, uint32_t node, void *stream);
-void ramsey64_launch_argmin_log(const Arenas &a, int n_calls, unsigned long long *log_key, void *stream);
-void ramsey64_launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream);
-void ramsey64_launch_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax,
-                                  uint8_t *d_colors, uint64_t *d_perm, void *stream);
-bool ramsey_async_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why = nullptr);
-void ramsey_launch_async(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl,
-                         const float *params, const void *wpk, uint32_t dyn_stride, size_t dyn_bytes, void *stream);
-bool ramsey_persist_plan(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why = nullptr);
-void ramsey_launch_persist(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl,
-                           uint32_t *log_node, uint32_t dyn_stride, size_t dyn_bytes, void *stream);
-
 } // namespace azd

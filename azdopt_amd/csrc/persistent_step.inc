@@ -217,4 +217,34 @@ __global__ __launch_bounds__(64) void k_argmin_log(Arenas a, int n_calls, int n_
     if (LANE == 0) atomicAdd(&a.status->improved, improved - 1); // argmin_replay adds the last one
     argmin_replay<SP>(a, s, dyn, wt, win_node, 0);
 }
+
+// ---------------------------------------------------------------- host: LDS plan shared by the spaces
+// wave_dyn_bytes: a wave's dynamic region (SP::dyn_bytes); wave_lds_bytes: its static block (SP::Lds).  False when the workgroup
+// does not fit a CU or the in-kernel MLP cannot take the layer widths.
+static bool persist_plan_common(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why,
+                                const size_t wave_dyn_bytes, const size_t wave_lds_bytes) {
+    const size_t stride = (wave_dyn_bytes + 15) & ~(size_t)15;
+    size_t total = stride * PERSIST_WAVES;
+    if (ev.kind == 3) {
+        if (ev.bf16) { // bf16 weight storage is built into the asynchronous step only
+            *why = "barrier step: bf16 weight storage is not built into it";
+            return false;
+        }
+        for (int l = 0; l < ev.n_layers; ++l)
+            if (ev.dims[l] % 4 != 0) { // the in-kernel MLP loads rows as float4
+                *why = "barrier step: layer widths must be multiples of 4";
+                return false;
+            }
+        size_t mlp = (size_t)PERSIST_WAVES * ((size_t)(ev.dims[0] + 4) + (size_t)(ev.hid[0] + 4) + (size_t)(ev.hid[1] + 4)) * sizeof(float);
+        if (mlp > total) total = mlp;
+    }
+    const size_t static_lds = PERSIST_WAVES * (wave_lds_bytes + 16) + 256;
+    if (total + static_lds > 160 * 1024) {
+        *why = "barrier step: 16 rows of activations do not fit the CU's 160 KB of LDS";
+        return false;
+    }
+    *dyn_stride = (uint32_t)stride;
+    *dyn_bytes = total;
+    return true;
+}
 #endif // !AZD_TU_ASYNC

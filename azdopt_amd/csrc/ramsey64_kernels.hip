@@ -1,11 +1,11 @@
 // ramsey64_kernels.hip -- the 64-bit tier of the Ramsey space (AZD_ENGINE_RAMSEY_U64: N <= 64 over uint64_t neighbourhood rows,
 // E*C <= 2304, keys of 36 words): tree_core.inc instantiated with RamseyU64Space (space_ramsey.inc) in a translation unit of its
 // own, so that its kernels' register allocation and build time stay apart from the 32-bit tiers'.  Launch-per-phase kernels and the
-// device root policy; ramsey_kernels.hip forwards to these launchers for engines with ramsey_u64(a).
+// device root policy, and the tier's table (space_ops.h).
 // Built with -ffp-contract=off like the other search units.
 #include <hip/hip_runtime.h>
 
-#include "engine_types.h"
+#include "space_ops.h"
 
 namespace azd {
 
@@ -13,33 +13,30 @@ namespace azd {
 #include "space_ramsey.inc"
 #include "persistent_step.inc"
 #include "root_policy.inc"
+#include "launchers.inc"
 
-using SP64 = RamseyU64Space;
-
-void ramsey64_launch_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax,
-                                  uint8_t *d_colors, uint64_t *d_perm, void *stream) {
-    k_modify_roots<SP64><<<dim3(a.B), dim3(64), SP64::dyn_bytes(a), (hipStream_t)stream>>>(a, seed, epoch, first_agent, kmin, kmax, d_colors, d_perm, d_perm);
+AZD_PHASE_ENTRIES(DISPATCH_RU64)
+static void e_argmin_one(const Arenas &a, int agent, uint32_t node, void *stream) {
+    DISPATCH_RU64(a, l_argmin_one, a, agent, node, (hipStream_t)stream);
 }
-void ramsey64_launch_init_roots(const Arenas &a, const uint8_t *d_colors, const uint64_t *d_permitted, void *stream) {
-    k_init_roots<SP64><<<dim3(a.B), dim3(64), SP64::dyn_bytes(a), (hipStream_t)stream>>>(a, d_colors, d_permitted);
+// The tier runs the launch-per-phase form only: a workgroup of the CU-resident forms keeps 16 waves' clique counts in LDS,
+// 144 KB of the CU's 160 at the reference's R(3,3,3,3) shape before anything else.
+#define RAMSEY_U64_NO_RESIDENT(FORM) FORM ": not built for the 64-bit Ramsey tier (it runs one launch per phase)"
+static bool no_persist(const Arenas &, const FusedEval &, uint32_t *, size_t *, const char **why) {
+    *why = RAMSEY_U64_NO_RESIDENT("barrier step");
+    return false;
 }
-void ramsey64_launch_add_actions(const Arenas &a, int root_mode, void *stream) {
-    k_add_actions<SP64><<<dim3(a.tn ? a.tn : a.B), dim3(64), SP64::dyn_bytes(a), (hipStream_t)stream>>>(a, root_mode);
+static bool no_async(const Arenas &, const FusedEval &, uint32_t *, size_t *, const char **why) {
+    *why = RAMSEY_U64_NO_RESIDENT("asynchronous step");
+    return false;
 }
-void ramsey64_launch_rollout(const Arenas &a, const TolTable &tol, void *stream) {
-    k_rollout<SP64><<<dim3(a.tn ? a.tn : a.B), dim3(64), SP64::dyn_bytes(a), (hipStream_t)stream>>>(a, tol);
+static bool no_pool(const Arenas &, const FusedEval &, PoolArgs *, uint32_t *, size_t *, const char **why) {
+    *why = RAMSEY_U64_NO_RESIDENT("pool step");
+    return false;
 }
-void ramsey64_launch_argmin_one(const Arenas &a, int agent, uint32_t node, void *stream) {
-    k_argmin_one<SP64><<<dim3(1), dim3(64), SP64::dyn_bytes(a), (hipStream_t)stream>>>(a, agent, node);
-}
-void ramsey64_launch_argmin_log(const Arenas &a, int n_calls, unsigned long long *log_key, void *stream) {
-    k_argmin_log1<SP64><<<dim3(1), dim3(64), SP64::dyn_bytes(a), (hipStream_t)stream>>>(a, n_calls, log_key, nullptr);
-}
-void ramsey64_launch_argmin(const Arenas &a, int init_mode, void *stream) {
-    k_argmin<SP64><<<dim3(1), dim3(1024), SP64::dyn_bytes(a), (hipStream_t)stream>>>(a, init_mode);
-}
-void ramsey64_launch_observe(const Arenas &a, uint32_t n_obs_tol, void *stream) {
-    k_observe<SP64><<<dim3(a.B), dim3(64), SP64::dyn_bytes(a), (hipStream_t)stream>>>(a, n_obs_tol);
+const SpaceOps &ramsey64_ops() {
+    static const SpaceOps ops = {{AZD_PHASE_OPS, e_argmin_one, no_persist, nullptr}, {no_async, nullptr}, {no_pool, nullptr, nullptr}};
+    return ops;
 }
 
 } // namespace azd

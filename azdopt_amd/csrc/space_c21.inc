@@ -282,6 +282,7 @@ struct C21Space {
     static size_t dyn_bytes(const Arenas &a) { return dyn_lds_bytes(a.n); }
     // pool step: the state-vector row is built over the wave's search scratch, which is dead by then
     static size_t pool_dyn_bytes(const Arenas &a) { return dyn_lds_bytes(a.n) > (size_t)a.S * 4 ? dyn_lds_bytes(a.n) : (size_t)a.S * 4; }
+    static constexpr bool POOL_EVAL_GROUPS = true; // k_pool is built with evaluator groups too (launchers.inc: l_pool)
     __device__ static __forceinline__ float *row_stage(const Arenas &, const uint32_t dyn) { return reinterpret_cast<float *>(lds_base(dyn)); }
 
     // the ActionSet key is the bit mask of the action ids themselves
@@ -529,3 +530,13 @@ struct C21Space {
         }
     }
 };
+
+// host side: the instantiation an engine's key width selects
+// BIG is a spare specialisation flag (n > 19); the kernels no longer depend on it
+#define DISPATCH_KW(A, FN, ...)                                   \
+    switch ((A).KW) {                                             \
+    case 1: FN<C21Space<1>>(__VA_ARGS__); break;                  \
+    case 2: FN<C21Space<2>>(__VA_ARGS__); break;                  \
+    case 3: FN<C21Space<3>>(__VA_ARGS__); break;                  \
+    default: FN<C21Space<4>>(__VA_ARGS__); break;                 \
+    }

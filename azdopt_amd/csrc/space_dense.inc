@@ -735,3 +735,12 @@ struct DenseSpace {
         if (LANE == 0) a.argmin->eval = ev;
     }
 };
+
+// host side: the key width (words of a rank set) follows the engine's max_slots: 2, 4, 10 or 16 (engine.hip)
+#define DISPATCH_DKW(A, FN, ...)                                  \
+    switch ((A).KW) {                                             \
+    case 2: FN<DenseSpace<2>>(__VA_ARGS__); break;                \
+    case 4: FN<DenseSpace<4>>(__VA_ARGS__); break;                \
+    case 10: FN<DenseSpace<10>>(__VA_ARGS__); break;              \
+    default: FN<DenseSpace<16>>(__VA_ARGS__); break;              \
+    }

@@ -629,13 +629,9 @@ struct RamseyU64Space : RamseySpaceBase<RAMSEY_U64_KW, RAMSEY_U64_MAX_E, RamseyU
 };
 
 // host side: what the instantiation an engine's key width selects needs of the LDS (the CU-resident forms' plans).  A wide engine's
-// keys are padded to 10 or 16 words (engine.hip), a width no narrow engine has (1..6): the key width names the engine's mode;
-// 36 words are the 64-bit tier's.
+// keys are padded to 10 or 16 words (engine.hip), a width no narrow engine has (1..6): the key width names the engine's mode.
+// (The 64-bit tier's 36 words never come here: its table refuses the CU-resident forms, ramsey64_kernels.hip.)
 static inline bool ramsey_wide(const Arenas &a) { return a.KW > MAX_KW; }
-static inline bool ramsey_u64(const Arenas &a) { return a.KW == RAMSEY_U64_KW; }
-// The 64-bit tier runs the launch-per-phase form only: a workgroup of the CU-resident forms keeps 16 waves' clique counts in LDS,
-// 144 KB of the CU's 160 at the reference's R(3,3,3,3) shape before anything else.
-#define RAMSEY_U64_NO_RESIDENT(FORM) FORM ": not built for the 64-bit Ramsey tier (it runs one launch per phase)"
 static inline size_t ramsey_dyn_bytes(const Arenas &a) {
     return a.KW == 16 ? RamseyWideSpace<16>::dyn_bytes(a) : a.KW == 10 ? RamseyWideSpace<10>::dyn_bytes(a) : RamseySpace<1>::dyn_bytes(a);
 }
@@ -643,3 +639,18 @@ static inline size_t ramsey_pool_dyn_bytes(const Arenas &a) {
     return a.KW == 16 ? RamseyWideSpace<16>::pool_dyn_bytes(a) : a.KW == 10 ? RamseyWideSpace<10>::pool_dyn_bytes(a) : RamseySpace<1>::pool_dyn_bytes(a);
 }
 static inline size_t ramsey_lds_bytes(const Arenas &a) { return ramsey_wide(a) ? sizeof(RamseyWideLds) : sizeof(RamseyLds); }
+
+// narrow engines: key widths 1..6; wide engines (max_slots > 0): 10 or 16.  The 64-bit tier's 36 never reach this switch: its engines
+// have a table of their own (ramsey64_kernels.hip)
+#define DISPATCH_RKW(A, FN, ...)                                  \
+    switch ((A).KW) {                                             \
+    case 1: FN<RamseySpace<1>>(__VA_ARGS__); break;               \
+    case 2: FN<RamseySpace<2>>(__VA_ARGS__); break;               \
+    case 3: FN<RamseySpace<3>>(__VA_ARGS__); break;               \
+    case 4: FN<RamseySpace<4>>(__VA_ARGS__); break;               \
+    case 5: FN<RamseySpace<5>>(__VA_ARGS__); break;               \
+    case 10: FN<RamseyWideSpace<10>>(__VA_ARGS__); break;         \
+    case 16: FN<RamseyWideSpace<16>>(__VA_ARGS__); break;         \
+    default: FN<RamseySpace<6>>(__VA_ARGS__); break;              \
+    }
+#define DISPATCH_RU64(A, FN, ...) FN<RamseyU64Space>(__VA_ARGS__)

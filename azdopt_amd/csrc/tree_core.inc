@@ -1,5 +1,5 @@
 // tree_core.inc -- the space-independent part of the data-parallel tree-search step on gfx950
-// (included inside namespace azd by tree_kernels.hip, async_kernels.hip and ramsey_kernels.hip).
+// (included inside namespace azd by every search translation unit: tree_kernels.hip and its like).
 //
 // One 64-lane wavefront owns one agent (= one SearchTree + its state).  Control
 // flow is wave-uniform; lanes parallelise the per-node work:
