@@ -21,6 +21,7 @@ ENGINE_NO_PERSISTENT_STEP = 1
 ENGINE_ASYNC_STEP = 2
 ENGINE_BARRIER_STEP = 4
 ENGINE_POOL_STEP = 8
+ENGINE_DENSE_AH = 32    # AZD_ENGINE_DENSE_AH: the dense-graph space with the Aouchiche-Hansen cost (n <= 32)
 ENGINE_RAMSEY_U64 = 16  # AZD_ENGINE_RAMSEY_U64: the 64-bit Ramsey tier (n <= 64, E*C <= 2304), beside max_slots > 0
 SPACE_C21 = 1
 SPACE_RAMSEY = 2
@@ -30,6 +31,7 @@ RAMSEY_WIDE_MAX_N = 32  # AZD_RAMSEY_WIDE_MAX_N: a wide Ramsey engine (EngineCon
 RAMSEY_U64_MAX_N = 64   # AZD_RAMSEY_U64_MAX_N: the 64-bit tier (ENGINE_RAMSEY_U64)
 RAMSEY_U64_NODE_ACTIONS = 512  # AZD_RAMSEY_U64_NODE_ACTIONS: max_slots * (C - 1) of the 64-bit tier
 RAMSEY_U64_MAX_ACTIONS = 2304  # E*C of the 64-bit tier (keys of 36 words)
+DENSE_AH_MAX_N = 32     # AZD_DENSE_AH_MAX_N: the Aouchiche-Hansen cost (azd_dense_ah_cost)
 PATH_SET, PATH_SEQUENCE = 0, 1
 
 
@@ -67,6 +69,17 @@ class RamseyWideArgmin(C.Structure):  # the same for any Ramsey engine, wide one
 class DenseArgmin(C.Structure):  # ArgminData of the dense-graph space
     _fields_ = [("adj", C.c_uint64 * 64), ("permitted", C.c_uint64 * 40), ("lambda_1", C.c_double),
                 ("matching_size", C.c_int32), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
+
+
+class DenseAhCost(C.Structure):  # azd_dense_ah_cost_t: the Aouchiche-Hansen cost of one connected graph
+    _fields_ = [("proximity", C.c_double), ("eigenvalue", C.c_double), ("diameter", C.c_int32), ("k", C.c_int32),
+                ("cost", C.c_float), ("eval", C.c_float)]
+
+
+class DenseAhArgmin(C.Structure):  # azd_dense_ah_argmin: ArgminData of a dense engine with the Aouchiche-Hansen cost
+    _fields_ = [("adj", C.c_uint64 * 32), ("permitted", C.c_uint64 * 8), ("proximity", C.c_double), ("eigenvalue", C.c_double),
+                ("diameter", C.c_int32), ("k", C.c_int32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32),
+                ("node", C.c_uint32)]
 
 
 class Argmin(C.Structure):  # ArgminData<State, Cost>, az-discrete-opt/src/log.rs:1-11
@@ -184,6 +197,11 @@ def lib():
     sig("azd_debug_probe_math", C.c_int, C.c_int, vp, vp, C.c_int)
     sig("azd_debug_gemm_bf16", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p)
     sig("azd_debug_probe_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, f32p)
+    sig("azd_dense_ah_cost", C.c_int, vp, C.c_int, C.POINTER(DenseAhCost))
+    sig("azd_engine_dense_ah_argmin_data", C.c_int, vp, C.POINTER(DenseAhArgmin))
+    sig("azd_engine_dense_ah_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseAhCost))
+    sig("azd_debug_probe_ah_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, f32p)
+    sig("azd_debug_probe_math_f64", C.c_int, C.c_int, vp, vp, C.c_int)
     _LIB = L
     return L
 

@@ -158,4 +158,134 @@ void dense_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, i
     }
 }
 
+// ---- Aouchiche-Hansen cost (the dense space's second objective).  connected_bitset_graph/mod.rs:156-198 restated: BFS from every
+// vertex over the bitsets (distance matrix, transmissions, diameter), proximity = min transmission / (n - 1), k = 2D/3 - 1 (n - 1
+// when 2D/3 = 0), cost = (f32)(proximity + entry k of the distance matrix's eigenvalues sorted descending).  The eigenvalue comes
+// from a Householder reduction to tridiagonal form and a Sturm-count multisection, written as the 64-lane wave of
+// dense_ah_cost.inc runs it: `lane` loops stand for the lanes, tree64 for the xor-butterfly.  One IEEE operation at a time
+// (this file is built with -ffp-contract=off); tests/dense_ah_ref.py is the same sequence in Python.
+float dense_ah_eval_slope(int n) { return 1.0f / (float)(2 * n + 2); }
+const char *dense_ah_check_graph(const uint64_t *adj, int n) {
+    if (!adj) return "adj: null";
+    if (n < 4 || n > DENSE_AH_MAX_N) return "n: the Aouchiche-Hansen cost needs 4 <= n <= 32 (AZD_DENSE_AH_MAX_N)";
+    const uint64_t all = (1ull << n) - 1ull;
+    for (int v = 0; v < n; ++v) {
+        if (adj[v] & ~all) return "adj: a neighbour beyond n";
+        if ((adj[v] >> v) & 1ull) return "adj: a loop";
+        for (int u = 0; u < n; ++u)
+            if (((adj[v] >> u) & 1ull) != ((adj[u] >> v) & 1ull)) return "adj: not symmetric";
+    }
+    if (!dense_connected(adj, n)) return "adj: the graph is not connected";
+    return nullptr;
+}
+static double ah_tree64(const double *v) { // balanced binary tree over 64 slots, adjacent pairs first
+    double t[64];
+    for (int i = 0; i < 64; ++i) t[i] = v[i];
+    for (int w = 64; w > 1; w >>= 1)
+        for (int i = 0; i < w / 2; ++i) t[i] = t[2 * i] + t[2 * i + 1];
+    return t[0];
+}
+static int ah_sturm(const double *diag, const double *sub2, int n, double x) {
+    double q = diag[0] - x;
+    if (std::fabs(q) < DENSE_AH_TINY) q = -DENSE_AH_TINY;
+    int c = q < 0.0 ? 1 : 0;
+    for (int i = 1; i < n; ++i) {
+        const double r = sub2[i - 1] / q;
+        q = (diag[i] - x) - r;
+        if (std::fabs(q) < DENSE_AH_TINY) q = -DENSE_AH_TINY;
+        c += q < 0.0 ? 1 : 0;
+    }
+    return c;
+}
+void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
+    constexpr int P = DENSE_AH_STRIDE;
+    std::vector<double> Am((size_t)DENSE_AH_MAX_N * P, 0.0);
+    double *A = Am.data();
+    int min_t = 0x7FFFFFFF, diam = 0;
+    for (int u = 0; u < n; ++u) { // BFS from u
+        uint64_t seen = 1ull << u, frontier = seen;
+        int d = 0, t = 0;
+        for (;;) {
+            uint64_t next = 0;
+            for (uint64_t f = frontier; f; f &= f - 1ull) next |= adj[__builtin_ctzll(f)];
+            next &= ~seen;
+            if (!next) break;
+            ++d;
+            for (uint64_t m = next; m; m &= m - 1ull) A[u * P + __builtin_ctzll(m)] = (double)d;
+            t += d * __builtin_popcountll(next);
+            seen |= next;
+            frontier = next;
+        }
+        if (t < min_t) min_t = t;
+        if (d > diam) diam = d;
+    }
+    const double prox = (double)min_t / (double)(n - 1);
+    const int q23 = (2 * diam) / 3, k = q23 >= 1 ? q23 - 1 : n - 1;
+    // Householder reduction: step i clears column i below row i + 1
+    double diag[DENSE_AH_MAX_N], sub[DENSE_AH_MAX_N], v[64], p[64], q[64], tmp[64];
+    for (int i = 0; i < DENSE_AH_MAX_N; ++i) diag[i] = sub[i] = 0.0;
+    for (int i = 0; i + 2 < n; ++i) {
+        for (int lane = 0; lane < 64; ++lane) {
+            v[lane] = lane > i && lane < n ? A[lane * P + i] : 0.0;
+            tmp[lane] = lane > i + 1 ? v[lane] * v[lane] : 0.0;
+        }
+        const double tail = ah_tree64(tmp), x1 = v[i + 1];
+        diag[i] = A[i * P + i];
+        if (tail == 0.0) {
+            sub[i] = x1;
+            continue;
+        }
+        const double sigma = tail + x1 * x1;
+        const double s = std::sqrt(sigma);
+        const double alpha = x1 >= 0.0 ? -s : s;
+        const double v1 = x1 - alpha;
+        v[i + 1] = v1;
+        const double beta = 2.0 / (tail + v1 * v1);
+        for (int lane = 0; lane < 64; ++lane) {
+            double acc = 0.0;
+            if (lane > i && lane < n)
+                for (int c = i + 1; c < n; ++c) acc = acc + A[lane * P + c] * v[c];
+            p[lane] = lane > i && lane < n ? beta * acc : 0.0;
+            tmp[lane] = v[lane] * p[lane];
+        }
+        const double vp = ah_tree64(tmp);
+        const double K = (0.5 * beta) * vp;
+        for (int lane = 0; lane < 64; ++lane) q[lane] = lane > i && lane < n ? p[lane] - K * v[lane] : 0.0;
+        for (int lane = i + 1; lane < n; ++lane)
+            for (int c = i + 1; c < n; ++c) A[lane * P + c] = A[lane * P + c] - (v[lane] * q[c] + q[lane] * v[c]);
+        sub[i] = alpha;
+    }
+    diag[n - 2] = A[(n - 2) * P + (n - 2)];
+    sub[n - 2] = A[(n - 1) * P + (n - 2)];
+    diag[n - 1] = A[(n - 1) * P + (n - 1)];
+    // multisection for ascending index j = n - 1 - k
+    const int j = n - 1 - k;
+    double sub2[DENSE_AH_MAX_N], R = 0.0;
+    for (int i = 0; i < n; ++i) {
+        sub2[i] = sub[i] * sub[i];
+        const double g = (std::fabs(diag[i]) + (i > 0 ? std::fabs(sub[i - 1]) : 0.0)) + std::fabs(sub[i]);
+        if (g > R) R = g;
+    }
+    double hi = R + 1.0, lo = -hi;
+    for (int round = 0; round < DENSE_AH_ROUNDS; ++round) {
+        const double w = hi - lo;
+        double xs[64];
+        int m = 0;
+        for (int lane = 0; lane < 64; ++lane) {
+            xs[lane] = lo + (w * (double)(lane + 1)) / 65.0;
+            m += ah_sturm(diag, sub2, n, xs[lane]) <= j ? 1 : 0;
+        }
+        const double nlo = m > 0 ? xs[m - 1] : lo, nhi = m < 64 ? xs[m] : hi;
+        lo = nlo;
+        hi = nhi;
+    }
+    const double eig = (lo + hi) * 0.5;
+    out->proximity = prox;
+    out->eigenvalue = eig;
+    out->diameter = diam;
+    out->k = k;
+    out->cost = (float)(prox + eig);
+    out->eval = dense_ah_eval_slope(n) * (out->cost + 2.0f);
+}
+
 } // namespace azd

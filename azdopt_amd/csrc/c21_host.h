@@ -45,4 +45,21 @@ bool dense_connected(const uint64_t *adj, int n);
 void dense_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int kmin, int kmax,
                           uint32_t p24, uint64_t *adj, uint64_t *slots);
 
+// Aouchiche-Hansen cost of a connected graph on 4 <= n <= DENSE_AH_MAX_N vertices (connected_bitset_graph/mod.rs:156-198,
+// restated; DESIGN.md "The AH cost"): the host form of dense_ah_cost_wave (dense_ah_cost.inc), the same IEEE f64 operations in
+// the same order.  The constants below are shared by both.
+constexpr int DENSE_AH_MAX_N = 32;
+constexpr int DENSE_AH_STRIDE = 33;        // row pitch of the working matrix in doubles (odd: a lane per row meets no bank twice)
+constexpr int DENSE_AH_ROUNDS = 11;        // multisection rounds of 64 shifts: the bracket shrinks by 65 a round
+constexpr double DENSE_AH_TINY = 0x1p-512; // a Sturm pivot smaller than this in magnitude becomes -DENSE_AH_TINY
+struct DenseAhCost {
+    double proximity, eigenvalue; // pi = min transmission / (n - 1); entry k of the distance spectrum, descending
+    int diameter, k;
+    float cost, eval;             // (f32)(pi + eigenvalue); slope (cost + 2) with slope = 1 / (2 n + 2) (build-defined)
+};
+float dense_ah_eval_slope(int n);
+// nullptr when the graph is acceptable, else what is wrong with it (an argument name leads the text)
+const char *dense_ah_check_graph(const uint64_t *adj, int n);
+void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out);
+
 } // namespace azd

@@ -1,0 +1,139 @@
+// dense_ah_kernels.hip -- translation unit of the dense-graph space's second objective, the Aouchiche-Hansen cost
+// (dense_ah_cost.inc: all-sources BFS, Householder tridiagonalisation in LDS, Sturm-count multisection; one wave per graph):
+// tree_core.inc instantiated with DenseSpace<KW, DenseCostAH> for key widths 2 / 4 / 10 (AZD_ENGINE_DENSE_AH engines: n <= 32, so
+// max_slots <= E <= 496) -- launch-per-phase kernels, the device root policy, the pool step's searchers -- built like
+// dense_kernels.hip, whose evaluator side (k_ext_*) and recovery kernels serve these engines too; and the probes that run the cost
+// and its f64 primitives outside any engine.
+// Built with -ffp-contract=off like the other tree units: the cost is bit-identical to azd_dense_ah_cost on the host.
+#include <hip/hip_runtime.h>
+
+#include "bf16.h"
+#include "c21_host.h"
+#include "space_ops.h"
+
+namespace azd {
+
+#include "tree_core.inc"
+#include "space_dense.inc"
+#include "dense_ah_cost.inc"
+
+#include "root_policy.inc"
+
+#include "persistent_step.inc"
+#include "async_step.inc"
+#include "pool_step.inc"
+
+#include "launchers.inc"
+
+#define DISPATCH_DAHKW(A, FN, ...)                                         \
+    switch ((A).KW) {                                                      \
+    case 2: FN<DenseSpace<2, DenseCostAH>>(__VA_ARGS__); break;            \
+    case 4: FN<DenseSpace<4, DenseCostAH>>(__VA_ARGS__); break;            \
+    default: FN<DenseSpace<10, DenseCostAH>>(__VA_ARGS__); break;          \
+    }
+AZD_PHASE_ENTRIES(DISPATCH_DAHKW)
+static void no_argmin_one(const Arenas &, int, uint32_t, void *) {}
+#define DENSE_AH_NO_RESIDENT "dense-graph space: its CU-resident form is the pool searchers with the evaluator outside the kernel (engine.hip: dense_pool_run)"
+static bool no_resident(const Arenas &, const FusedEval &, uint32_t *, size_t *, const char **why) {
+    *why = DENSE_AH_NO_RESIDENT;
+    return false;
+}
+static bool no_pool(const Arenas &, const FusedEval &, PoolArgs *, uint32_t *, size_t *, const char **why) {
+    *why = DENSE_AH_NO_RESIDENT;
+    return false;
+}
+const SpaceOps &dense_ah_ops() {
+    static const SpaceOps ops = {{AZD_PHASE_OPS, no_argmin_one, no_resident, nullptr}, {no_resident, nullptr}, {no_pool, nullptr, nullptr}};
+    return ops;
+}
+
+// ---------------------------------------------------------------- pool step, searchers only (dense_kernels.hip has the default cost's)
+template <class SP>
+static void q_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes) {
+    const size_t stride = (SP::dyn_bytes(a) + 15) & ~(size_t)15;
+    const size_t sw_bytes = (PERSIST_WAVES * sizeof(typename SP::Lds) + 15) & ~(size_t)15; // (k_pool_search's SW_BYTES: the layout of 16 waves' blocks)
+    *dyn_stride = (uint32_t)stride;
+    *dyn_bytes = sw_bytes + stride * (size_t)waves;
+}
+// A wave's block carries the cost's working set (4.1 KB of matrix): sixteen blocks and sixteen scratch regions are beyond a CU's
+// LDS, so the engine plans fewer waves per workgroup (dense_pool_run counts down from 16): 10 at key width 2, 9 at 4, 7 at 10.
+bool dense_ah_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why) {
+    if (a.B > 65536 || a.node_cap > 65536) {
+        *why = "pool step: more than 65536 agents or nodes per tree";
+        return false;
+    }
+    DISPATCH_DAHKW(a, q_pool_plan, a, waves, dyn_stride, dyn_bytes);
+    if (*dyn_bytes + sizeof(PoolIdle) + 256 > 160 * 1024) {
+        *why = "pool step (Aouchiche-Hansen cost): the searcher waves' blocks and scratch do not fit the CU's 160 KB of LDS";
+        return false;
+    }
+    return true;
+}
+template <class SP>
+static void l_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
+                          size_t dyn_bytes, hipStream_t st) {
+    if (sl.hashed) { // the test harness' evaluator (FusedEval kind 4): the searchers note the call of every row they post
+        if (hipFuncSetAttribute((const void *)k_pool_search<SP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess) return;
+        k_pool_search<SP, 1><<<dim3(n_blocks), dim3(waves * 64), dyn_bytes, st>>>(d_args, sl.n_calls, sl.log_key, dyn_stride);
+    } else {
+        if (hipFuncSetAttribute((const void *)k_pool_search<SP, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess) return;
+        k_pool_search<SP, 0><<<dim3(n_blocks), dim3(waves * 64), dyn_bytes, st>>>(d_args, sl.n_calls, sl.log_key, dyn_stride);
+    }
+    k_argmin_log1<SP><<<dim3(1), dim3(64), SP::dyn_bytes(a), st>>>(a, sl.n_calls, sl.log_key, sl.ctl);
+}
+void dense_ah_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
+                                 size_t dyn_bytes, void *stream) {
+    DISPATCH_DAHKW(a, l_pool_search, a, d_args, sl, n_blocks, waves, dyn_stride, dyn_bytes, (hipStream_t)stream);
+}
+template <class SP>
+static void q_pool_search_resident(int *out, int waves, size_t dyn_bytes) {
+    int nb = 0;
+    if (hipFuncSetAttribute((const void *)k_pool_search<SP, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_pool_search<SP, 0>, waves * 64, dyn_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        nb = 0;
+    }
+    *out = nb;
+}
+int dense_ah_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes) {
+    int nb = 0;
+    DISPATCH_DAHKW(a, q_pool_search_resident, &nb, waves, dyn_bytes);
+    return nb;
+}
+
+// one wave per graph, `reps` repetitions (timing), the result of the last one
+__global__ __launch_bounds__(64) void k_probe_ah_cost(const uint64_t *__restrict__ adj, const int n, const int count, const int reps,
+                                                      const float slope, DenseAhCost *__restrict__ out) {
+    __shared__ uint64_t s_adj[DENSE_AH_MAX_N];
+    __shared__ DenseAhLds w;
+    const int g = blockIdx.x;
+    if (g >= count) return;
+    if (LANE < DENSE_AH_MAX_N) s_adj[LANE] = LANE < n ? adj[(size_t)g * n + LANE] : 0ull;
+    LDS_SYNC();
+    DenseAhCost c;
+    for (int r = 0; r < reps; ++r) {
+        dense_ah_cost_wave(s_adj, w, n, slope, DenseNoHook{}, c);
+        LDS_SYNC();
+    }
+    if (LANE == 0) out[g] = c;
+}
+void launch_probe_ah_cost(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream) {
+    k_probe_ah_cost<<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, reps, dense_ah_eval_slope(n), d_out);
+}
+
+// parity probe of the f64 primitives the cost depends on bit for bit: out[3 i] = x / y, [3 i + 1] = sqrt(|x|), [3 i + 2] = x - x / y * y
+__global__ void k_probe_math_f64(const double *__restrict__ in, double *__restrict__ out, const int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double x = in[2 * i], y = in[2 * i + 1];
+    const double q = x / y;
+    out[3 * i] = q;
+    out[3 * i + 1] = sqrt(fabs(x));
+    const double m = q * y;
+    out[3 * i + 2] = x - m;
+}
+void launch_probe_math_f64(const double *d_in, double *d_out, int n, void *stream) {
+    k_probe_math_f64<<<dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(d_in, d_out, n);
+}
+
+} // namespace azd

@@ -47,7 +47,7 @@ static int device_ok(int device) {
 static const SpaceOps *space_ops(const Arenas &a) {
     static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops()};
     static const SpaceOps ramsey = {ramsey_phase_ops(), ramsey_async_ops(), ramsey_pool_ops()};
-    if (a.space == SPACE_DENSE) return &dense_ops();
+    if (a.space == SPACE_DENSE) return a.lam_lo != 0.0 ? &dense_ah_ops() : &dense_ops(); // (Arenas::lam_lo: c21's bracket; 1.0 marks an AH dense engine)
     if (a.space == SPACE_RAMSEY) return a.KW == RAMSEY_U64_KW ? &ramsey64_ops() : &ramsey;
     return &c21;
 }
@@ -242,6 +242,7 @@ struct azd_engine {
     // a wide Ramsey engine's kernels write azd::RamseyWideArgminRec where argmin_r points: records of the narrow type it spans
     bool ramsey_wide() const { return a.space == azd::SPACE_RAMSEY && a.KW > azd::MAX_KW; }
     // the 64-bit tier (AZD_ENGINE_RAMSEY_U64): uint64_t neighbourhood rows of 64 vertices, keys of RAMSEY_U64_KW words, its own record
+    bool dense_ah() const { return a.space == azd::SPACE_DENSE && a.lam_lo != 0.0; } // AZD_ENGINE_DENSE_AH
     bool ramsey_u64() const { return a.space == azd::SPACE_RAMSEY && a.KW == azd::RAMSEY_U64_KW; }
     size_t ramsey_nbr_words() const { return ramsey_u64() ? 512 : 128; } // uint32_t words of an agent's [4][NV] rows
     size_t argmin_r_bytes() const {
@@ -673,6 +674,19 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     if (!out || !cfg) return AZD_ERR_INVALID_ARGUMENT;
     const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
     const bool dense = cfg->space_id == AZD_SPACE_DENSE;
+    const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
+    if (dense_ah) {
+        const char *bad = !dense                                                  ? "space_id: AZD_ENGINE_DENSE_AH needs the dense-graph space (AZD_SPACE_DENSE)"
+                          : cfg->n < 4 || cfg->n > AZD_DENSE_AH_MAX_N             ? "n: the Aouchiche-Hansen cost needs 4 <= n <= 32 (AZD_DENSE_AH_MAX_N)"
+                          : cfg->layers > 1                                       ? "layers: AZD_ENGINE_DENSE_AH engines take no Layered wrapper (layers <= 1)"
+                          : cfg->max_slots > azd::dense_edges(cfg->n)             ? "max_slots: AZD_ENGINE_DENSE_AH needs max_slots <= E = n (n - 1) / 2"
+                          : cfg->path_kind != AZD_PATH_SET                        ? "path_kind: AZD_ENGINE_DENSE_AH engines keep ActionSet paths (AZD_PATH_SET)"
+                                                                                  : nullptr;
+        if (bad) {
+            azd::g_last_error = bad;
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+    }
     if (dense) {
         if (cfg->n < 4 || cfg->n > AZD_DENSE_MAX_N || cfg->batch <= 0 || cfg->layers > 1 || cfg->max_slots < 0 || cfg->max_slots > AZD_DENSE_MAX_SLOTS ||
             !(cfg->dense_p >= 0.f && cfg->dense_p <= 1.f)) {
@@ -770,6 +784,10 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         }
         a.dense_p24 = (uint32_t)((cfg->dense_p > 0.f ? (double)cfg->dense_p : 0.2) * 16777216.0 + 0.5);
         a.eval_slope = azd::c21_eval_slope(cfg->n);
+        if (dense_ah) { // (key widths 2, 4 and 10 only: max_slots <= E <= 496)
+            a.eval_slope = azd::dense_ah_eval_slope(cfg->n);
+            a.lam_lo = 1.0; // marks the engine for space_ops() and dense_ah(); no dense kernel reads the c21 bracket
+        }
         e->kw_host = azd::dense_key_words(cfg->n);
     } else if (ramsey) {
         a.C = cfg->n_colors;
@@ -858,8 +876,9 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     TRY(e->alloc(&a.root_perm, B * a.KW));
     TRY(e->alloc(&a.cur_perm, B * a.KW));
     TRY(e->alloc(&a.cur_path, B * a.KW));
-    TRY(e->alloc(&a.cur_lambda, B));
-    TRY(e->alloc(&a.cur_mu, B));
+    // (an AH dense engine keeps two doubles and two ints per agent there: dense_ah_cost.inc, DenseCostAH)
+    TRY(e->alloc(&a.cur_lambda, dense_ah ? 2 * B : B));
+    TRY(e->alloc(&a.cur_mu, dense_ah ? 2 * B : B));
     TRY(e->alloc(&a.state_pos, B));
     TRY(e->alloc(&a.n_nodes, B));
     TRY(e->alloc(&a.n_arcs, B));
@@ -888,7 +907,8 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         TRY(e->alloc(&a.root_aid, B * (size_t)e->dense_slots));
         TRY(e->alloc(&e->d_stage_slots, B * (size_t)((a.E + 63) / 64)));
         TRY(e->alloc(&a.argmin_d, 1));
-        TRY(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64));
+        static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec), "an AH engine's argmin record lives in argmin_d's allocation");
+        if (!dense_ah) TRY(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH cost keeps nothing per node)
         // a bf16 evaluator takes the state vectors as bf16 rows: this space's kernels write them beside the f32 rows (write_vec16)
         if (ev && ev->input16_pitch() >= a.S) {
             a.S16 = ev->input16_pitch();
@@ -1255,11 +1275,13 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
             return AZD_ERR_INVALID_ARGUMENT;
         }
     }
-    while (waves > 4 && !azd::dense_pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) waves -= 1;
+    const bool ah = e->dense_ah();
+    auto pool_plan = ah ? azd::dense_ah_pool_plan : azd::dense_pool_plan;
+    while (waves > 4 && !pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) waves -= 1;
     azd::FusedEval fe;
     const bool hashed = e->ev->fused_desc(&fe) && fe.kind == 4; // the test harness' fixed prediction stream, served like a model's rows
     if (!e->pool_step || !e->persist_enabled || e->pool_failed || e->ext_unsupported || (!a.state_vecs16 && !hashed) ||
-        n_calls < 1 || !azd::dense_pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) {
+        n_calls < 1 || !pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) {
         e->step_reason = !e->pool_step || !e->persist_enabled ? "dense-graph space: the pool step is not configured for this engine"
                          : e->pool_failed                      ? "an earlier pool launch of this engine aborted: launch-per-phase form"
                          : ((!a.state_vecs16 && !hashed) || e->ext_unsupported)
@@ -1267,7 +1289,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
                              : why;
         return AZD_OK;
     }
-    const int per_cu = azd::dense_pool_search_resident(a, waves, dyn_bytes);
+    const int per_cu = (ah ? azd::dense_ah_pool_search_resident : azd::dense_pool_search_resident)(a, waves, dyn_bytes);
     // searcher workgroups: no more waves than twice the agents, and no more than half the chip's wave slots -- the GEMM launches
     // need the rest
     int n_search = (2 * a.B + waves - 1) / waves;
@@ -1408,7 +1430,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
         sl.hashed = hashed ? 1 : 0;
         sl.window = 0;
         e->time_begin(0);
-        azd::dense_launch_pool_search(a, e->d_pargs, sl, n_search, waves, dyn_stride, dyn_bytes, e->stream);
+        (ah ? azd::dense_ah_launch_pool_search : azd::dense_launch_pool_search)(a, e->d_pargs, sl, n_search, waves, dyn_stride, dyn_bytes, e->stream);
 #ifndef AZD_PHASE_PROFILE
         e->counters_by_wave = true;
 #endif
@@ -2498,10 +2520,37 @@ int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap,
 int azd_engine_dense_argmin_data(azd_engine *e, azd_dense_argmin *out) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (e->a.space != azd::SPACE_DENSE) return AZD_ERR_UNSUPPORTED;
+    if (e->dense_ah()) {
+        azd::g_last_error = "azd_engine_dense_argmin_data: an AZD_ENGINE_DENSE_AH engine's record is read with azd_engine_dense_ah_argmin_data";
+        return AZD_ERR_UNSUPPORTED;
+    }
     AZD_ENTER(e);
     static_assert(sizeof(azd_dense_argmin) == sizeof(azd::DenseArgminRec), "ABI struct mismatch");
     AZD_HIP(hipStreamSynchronize(e->stream));
     AZD_HIP(hipMemcpy(out, e->a.argmin_d, sizeof(azd_dense_argmin), hipMemcpyDeviceToHost));
+    return AZD_OK;
+}
+int azd_engine_dense_ah_argmin_data(azd_engine *e, azd_dense_ah_argmin *out) {
+    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
+    if (!e->dense_ah()) return AZD_ERR_UNSUPPORTED;
+    AZD_ENTER(e);
+    static_assert(sizeof(azd_dense_ah_argmin) == sizeof(azd::DenseAhArgminRec), "ABI struct mismatch");
+    AZD_HIP(hipStreamSynchronize(e->stream));
+    AZD_HIP(hipMemcpy(out, e->a.argmin_d, sizeof(azd_dense_ah_argmin), hipMemcpyDeviceToHost));
+    return AZD_OK;
+}
+int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out) {
+    if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
+    if (!e->dense_ah()) return AZD_ERR_UNSUPPORTED;
+    AZD_ENTER(e);
+    AZD_HIP(hipStreamSynchronize(e->stream));
+    const azd::Arenas &a = e->a;
+    AZD_HIP(hipMemcpy(&out->proximity, a.cur_lambda + agent, 8, hipMemcpyDeviceToHost));
+    AZD_HIP(hipMemcpy(&out->eigenvalue, a.cur_lambda + a.B + agent, 8, hipMemcpyDeviceToHost));
+    AZD_HIP(hipMemcpy(&out->diameter, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
+    AZD_HIP(hipMemcpy(&out->k, a.cur_mu + a.B + agent, 4, hipMemcpyDeviceToHost));
+    out->cost = (float)(out->proximity + out->eigenvalue);
+    out->eval = a.eval_slope * (out->cost + 2.0f);
     return AZD_OK;
 }
 int azd_engine_ramsey_agent_counts(azd_engine *e, int agent, int32_t *counts, int32_t *totals) {
@@ -2653,6 +2702,10 @@ int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t 
     AZD_HIP(hipStreamSynchronize(e->stream));
     const azd::Arenas &a = e->a;
     if (a.space == azd::SPACE_DENSE) { // `parents` receives the neighbourhoods (8 n bytes); masks are kw_host words
+        if (e->dense_ah() && (lambda_1 || matching_size)) {
+            azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_AH engine keeps neither (azd_engine_dense_ah_agent_cost)";
+            return AZD_ERR_UNSUPPORTED;
+        }
         const int KW = a.KW, MAXS = e->dense_slots;
         std::vector<uint16_t> tab((size_t)MAXS);
         uint64_t rem[16], pth[16];
@@ -2862,6 +2915,77 @@ int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, i
     (void)hipEventDestroy(e1);
     if (he != hipSuccess) return azd::hip_fail(he, "probe_cost");
     if (ms) *ms = t;
+    return AZD_OK;
+}
+
+// ------------------------------------------------------------------ Aouchiche-Hansen cost of the dense-graph space
+static_assert(sizeof(azd_dense_ah_cost_t) == sizeof(azd::DenseAhCost) && offsetof(azd_dense_ah_cost_t, eval) == offsetof(azd::DenseAhCost, eval),
+              "azd_dense_ah_cost_t mirrors azd::DenseAhCost");
+static_assert(AZD_DENSE_AH_MAX_N == azd::DENSE_AH_MAX_N, "AZD_DENSE_AH_MAX_N");
+int azd_dense_ah_cost(const uint64_t *adj, int n, azd_dense_ah_cost_t *out) {
+    if (!out) {
+        azd::g_last_error = "azd_dense_ah_cost: out: null";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (const char *why = azd::dense_ah_check_graph(adj, n)) {
+        azd::g_last_error = std::string("azd_dense_ah_cost: ") + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    azd::dense_ah_cost_host(adj, n, reinterpret_cast<azd::DenseAhCost *>(out));
+    return AZD_OK;
+}
+int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
+    if (!out || count <= 0 || reps <= 0) {
+        azd::g_last_error = "azd_debug_probe_ah_cost: out / count / reps";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
+        if (const char *why = azd::dense_ah_check_graph(adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n)) {
+            azd::g_last_error = std::string("azd_debug_probe_ah_cost: graph ") + std::to_string(i) + ": " + why;
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+    int st = azd::device_ok(device);
+    if (st) return st;
+    AZD_HIP(hipSetDevice(device));
+    uint64_t *d_adj = nullptr;
+    azd::DenseAhCost *d_out = nullptr;
+    hipEvent_t e0, e1;
+    AZD_HIP(hipMalloc(&d_adj, (size_t)count * n * 8));
+    AZD_HIP(hipMalloc(&d_out, (size_t)count * sizeof(azd::DenseAhCost)));
+    AZD_HIP(hipEventCreate(&e0));
+    AZD_HIP(hipEventCreate(&e1));
+    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
+    azd::launch_probe_ah_cost(d_adj, n, count, 1, d_out, nullptr); // warm-up
+    AZD_HIP(hipEventRecord(e0, nullptr));
+    azd::launch_probe_ah_cost(d_adj, n, count, reps, d_out, nullptr);
+    AZD_HIP(hipEventRecord(e1, nullptr));
+    hipError_t he = hipDeviceSynchronize();
+    float t = 0.f;
+    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
+    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseAhCost), hipMemcpyDeviceToHost);
+    (void)hipFree(d_adj);
+    (void)hipFree(d_out);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_ah_cost");
+    if (ms) *ms = t;
+    return AZD_OK;
+}
+int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
+    if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;
+    int st = azd::device_ok(device);
+    if (st) return st;
+    AZD_HIP(hipSetDevice(device));
+    double *d_in = nullptr, *d_out = nullptr;
+    AZD_HIP(hipMalloc(&d_in, (size_t)n * 16));
+    AZD_HIP(hipMalloc(&d_out, (size_t)n * 24));
+    AZD_HIP(hipMemcpy(d_in, in, (size_t)n * 16, hipMemcpyHostToDevice));
+    azd::launch_probe_math_f64(d_in, d_out, n, nullptr);
+    hipError_t he = hipDeviceSynchronize();
+    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)n * 24, hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_math_f64");
     return AZD_OK;
 }
 

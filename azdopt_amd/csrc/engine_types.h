@@ -152,6 +152,16 @@ struct DenseArgminRec { // device copy of azd_dense_argmin
     uint32_t node;
 };
 
+struct DenseAhArgminRec { // device copy of azd_dense_ah_argmin (AZD_ENGINE_DENSE_AH engines: n <= 32, E <= 496); written where Arenas::argmin_d points
+    uint64_t adj[32];
+    uint64_t permitted[8]; // modifiable slots (colex positions) still open
+    double proximity, eigenvalue;
+    int32_t diameter, k;
+    float cost, eval;
+    int32_t agent;
+    uint32_t node;
+};
+
 struct StatusRec { // small device block copied back after every host-visible call
     unsigned long long improved;   // k_argmin calls that improved the argmin
     unsigned long long expansions; // sum over agents and calls (metric numerator)
@@ -174,8 +184,8 @@ struct Arenas {
     uint8_t *cur_parents;
     uint64_t *cur_perm;
     uint64_t *cur_path;
-    double *cur_lambda;
-    int32_t *cur_mu;
+    double *cur_lambda;     // [B]; an AH dense engine: [2 B] = proximity, then eigenvalue (dense_ah_cost.inc: DenseCostAH)
+    int32_t *cur_mu;        // [B]; an AH dense engine: [2 B] = diameter, then k
     uint32_t *state_pos;
     uint32_t *n_nodes, *n_arcs, *n_preds;
     uint32_t *flags;
@@ -195,7 +205,8 @@ struct Arenas {
     int n, A, S, KW, B;
     int t0, tn;             // launch-per-phase kernels over a SUB-population: agents t0 .. t0 + tn - 1 (tn = 0: all B); see engine.hip
     float eval_slope;       // squish slope 1/(C_UPPER - C_LOWER), 04-c21-tree.rs:58-74
-    double lam_lo, lam_hi;  // c21: initial bracket of the lambda_1 multisection (c21_host.cpp:c21_lambda_bracket)
+    double lam_lo, lam_hi;  // c21: initial bracket of the lambda_1 multisection (c21_host.cpp:c21_lambda_bracket).  Dense-graph space (no
+                            // kernel of it reads them): lam_lo = 1.0 marks an AZD_ENGINE_DENSE_AH engine for the host's dispatch, else 0
     // ---- Ramsey space (space_ramsey.inc); unused (null / 0) for c21
     int space;              // SPACE_C21 / SPACE_RAMSEY
     int C, E;               // colours, edges N(N-1)/2;  A = E*C, S = E*(2C+1)

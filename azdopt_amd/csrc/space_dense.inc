@@ -7,7 +7,9 @@
 // over general graphs.  The space is BUILD-DEFINED from those pieces in the image of the c21 space; its definition and
 // the procedures that stand in for faer's eigenvalues and the exponential matching search are spelled out in
 // oracle/dense_graph.inc, which this file mirrors operation for operation (integer work exactly; the f64 power iteration
-// one IEEE operation at a time, -ffp-contract=off).
+// one IEEE operation at a time, -ffp-contract=off).  The COST is a policy of the space (DenseCostC21 below: lambda_1 + matching
+// number, the default and what every comment up to the policy speaks of; DenseCostAH, dense_ah_cost.inc: the objective 05-ah.rs
+// searches with).
 //
 // State of one agent:
 //   adj[v]   u64   neighbourhood bitsets of the connected graph, N <= 64                         static LDS
@@ -288,12 +290,20 @@ __device__ __forceinline__ int dense_matching_update(L &s, const int n, const in
     return __popcll(__ballot(i < n && mate_i != DM_NONE)) >> 1;
 }
 
-template <int KW_>
-struct DenseSpace {
-    static constexpr int KW = KW_; // words of a rank set: the root's modifiable slots, at most 64 KW
-    static constexpr int CH = KW_; // chunks of 64 predictions a node may hold (tree_core.inc: SpaceChunks)
-    static constexpr int MAX_SLOTS = 64 * KW_;
+__device__ __forceinline__ float c21_eval_dense(float slope, double lambda1, int mu) {
+    const float c = (float)mu + (float)lambda1;
+    const float x = c - 2.0f;
+    return slope * x;
+}
+// ---------------------------------------------------------------- the cost of a DenseSpace: a policy
+// What a dense engine minimises enters the space as a class: its part of the wave's LDS block and of the register state, what a
+// new node computes (and keeps per node), what an agent keeps between launches, and the argmin record.  DenseCostC21 is
+// conjecture_2_1_cost (mod.rs:319-338: lambda_1 + matching number) through the procedures above, the default; DenseCostAH
+// (dense_ah_cost.inc, built in dense_ah_kernels.hip) is the Aouchiche-Hansen cost.
+struct DenseCostC21 {
+    template <int KW_>
     using Lds = DenseLds<KW_>;
+    template <int KW_>
     struct St {
         uint64_t rem[KW_];
         double lambda;
@@ -301,19 +311,103 @@ struct DenseSpace {
         uint32_t last_aid; // the action that leads to the node being created (new_node_begin): its edge is what the matching repairs
         uint32_t mate_of;  // ... and the node whose matching is repaired (the parent)
     };
+    struct Replay { // the argmin's recomputed cost
+        double lam;
+        int mu;
+        float ev;
+    };
+    // tree_core.inc, new node: the parent's maximum matching (one 64-byte row of an arena of gigabytes) is requested by
+    // evaluate() -- after the state row has left (a load ahead of the row's stores would be waited for with them: the counter is
+    // in order) -- and stays in flight while lambda_1 iterates; the new node's goes out once the node has its index.
+    template <class S>
+    __device__ static __forceinline__ void new_node_begin(S &st, const uint32_t parent, const uint32_t aid) {
+        st.last_aid = aid;
+        st.mate_of = parent;
+    }
+    template <class L>
+    __device__ static __forceinline__ void new_node_end(const Arenas &a, const int t, L &s, const uint32_t node) {
+        a.node_mate[((size_t)t * a.node_cap + node) * DENSE_MAX_N + LANE] = s.mate[LANE];
+    }
+    template <class S>
+    __device__ static __forceinline__ void load_cost(const Arenas &a, const int t, S &st) {
+        st.lambda = a.cur_lambda[t];
+        st.mu = a.cur_mu[t];
+    }
+    template <class S>
+    __device__ static __forceinline__ void store_cost(const Arenas &a, const int t, const S &st) { // (one lane)
+        a.cur_lambda[t] = st.lambda;
+        a.cur_mu[t] = st.mu;
+    }
+    template <class L, class S, class Hook>
+    __device__ static __forceinline__ float evaluate(const Arenas &a, L &s, S &st, const int t, Hook &&hook) {
+        const unsigned long long ph_l0 = PH_NOW();
+        const uint8_t parent_mate = a.node_mate[((size_t)t * a.node_cap + st.mate_of) * DENSE_MAX_N + LANE];
+        st.lambda = dense_lambda1_wave(s, a.n, hook);
+        const unsigned long long ph_l1 = PH_NOW();
+        {   // the parent's matching (new_node_begin) after the toggle of this action's edge
+            int mx, mn;
+            dense_from_colex((int)(st.last_aid % (uint32_t)a.E), mx, mn);
+            s.mate[LANE] = parent_mate;
+            LDS_SYNC();
+            st.mu = dense_matching_update(s, a.n, mx, mn);
+        }
+        CTR_ADD(22, ph_l1 - ph_l0);
+        CTR_ADD(23, PH_NOW() - ph_l1);
+        return c21_eval_dense(a.eval_slope, st.lambda, st.mu);
+    }
+    // the cost of a root from nothing (the graph is in s.adj): the agent's record, the root node's matching
+    template <class L, class S>
+    __device__ static __forceinline__ float root_cost(const Arenas &a, const int t, L &s, S &st) {
+        const int n = a.n;
+        st.lambda = dense_lambda1_wave(s, n, DenseNoHook{});
+        st.mu = dense_matching_scratch(s, n);
+        st.last_aid = 0;
+        a.node_mate[((size_t)t * a.node_cap) * DENSE_MAX_N + LANE] = s.mate[LANE]; // the root node's matching
+        if (LANE == 0) {
+            a.cur_lambda[t] = st.lambda;
+            a.cur_mu[t] = st.mu;
+        }
+        return c21_eval_dense(a.eval_slope, st.lambda, st.mu);
+    }
+    template <class L>
+    __device__ static __forceinline__ void argmin_cost(const Arenas &a, L &s, Replay &r) {
+        r.lam = dense_lambda1_wave(s, a.n, DenseNoHook{});
+        r.mu = dense_matching_scratch(s, a.n);
+        r.ev = c21_eval_dense(a.eval_slope, r.lam, r.mu);
+    }
+    // ArgminData { state, cost, eval } (log.rs:1-11); s.slotmask holds the open slots
+    template <class L>
+    __device__ static __forceinline__ void argmin_write(const Arenas &a, L &s, const Replay &r, const int wt, const uint32_t win_node) {
+        DenseArgminRec *out = a.argmin_d;
+        out->adj[LANE] = LANE < a.n ? s.adj[LANE] : 0ull;
+        if (LANE < 40) out->permitted[LANE] = LANE < 32 ? s.slotmask[LANE] : 0ull;
+        if (LANE == 0) {
+            out->lambda_1 = r.lam;
+            out->matching_size = r.mu;
+            out->eval = r.ev;
+            out->agent = wt;
+            out->node = win_node;
+        }
+    }
+};
+
+template <int KW_, class Cost = DenseCostC21>
+struct DenseSpace {
+    static constexpr int KW = KW_; // words of a rank set: the root's modifiable slots, at most 64 KW
+    static constexpr int CH = KW_; // chunks of 64 predictions a node may hold (tree_core.inc: SpaceChunks)
+    static constexpr int MAX_SLOTS = 64 * KW_;
+    using Lds = typename Cost::template Lds<KW_>;
+    using St = typename Cost::template St<KW_>;
     static size_t dyn_bytes(const Arenas &) {
         const size_t t = (size_t)512 * KW_; // select_big's two lists of 64 KW words
         return t > CORE_DYN_BYTES ? t : CORE_DYN_BYTES;
     }
-    // tree_core.inc, new node: the parent's maximum matching (one 64-byte row of an arena of gigabytes) is requested by
-    // evaluate() -- after the state row has left (a load ahead of the row's stores would be waited for with them: the counter is
-    // in order) -- and stays in flight while lambda_1 iterates; the new node's goes out once the node has its index.
+    // tree_core.inc, new node: what the cost keeps per node (DenseCostC21: the parent's maximum matching)
     __device__ static __forceinline__ void new_node_begin(const Arenas &, const int, Lds &, St &st, const uint32_t parent, const uint32_t aid) {
-        st.last_aid = aid;
-        st.mate_of = parent;
+        Cost::new_node_begin(st, parent, aid);
     }
     __device__ static __forceinline__ void new_node_end(const Arenas &a, const int t, Lds &s, const St &, const uint32_t node) {
-        a.node_mate[((size_t)t * a.node_cap + node) * DENSE_MAX_N + LANE] = s.mate[LANE];
+        Cost::new_node_end(a, t, s, node);
     }
     __device__ static __forceinline__ void prepare(const Arenas &, Lds &) {}
     __device__ static __forceinline__ float *row_stage(const Arenas &, const uint32_t) { return nullptr; } // pool step: not built for this space
@@ -326,8 +420,7 @@ struct DenseSpace {
         load_tables(a, t, s);
 #pragma unroll
         for (int w = 0; w < KW; ++w) st.rem[w] = a.cur_perm[(size_t)t * KW + w];
-        st.lambda = a.cur_lambda[t];
-        st.mu = a.cur_mu[t];
+        Cost::load_cost(a, t, st);
     }
     __device__ static __forceinline__ void load_root(const Arenas &a, const int t, Lds &s, const uint32_t, St &st) {
         s.adj[LANE] = a.root_adj[(size_t)t * DENSE_MAX_N + LANE];
@@ -343,8 +436,7 @@ struct DenseSpace {
         if (LANE == 0) {
 #pragma unroll
             for (int w = 0; w < KW; ++w) a.cur_perm[(size_t)t * KW + w] = st.rem[w];
-            a.cur_lambda[t] = st.lambda;
-            a.cur_mu[t] = st.mu;
+            Cost::store_cost(a, t, st);
         }
     }
     // the ActionSet key of a path is kept over the RANKS of the root's modifiable slots
@@ -372,32 +464,15 @@ struct DenseSpace {
             if ((int)(r >> 6) == w) st.rem[w] &= ~(1ull << (r & 63u));
         WAVE_SYNC();
     }
-    // conjecture_2_1_cost (mod.rs:319-338) through the procedures above; squish of 04-c21-tree.rs:58-74 with N's bounds
+    // the policy's cost of the state just acted into, squished (DenseCostC21: conjecture_2_1_cost, mod.rs:319-338, and the squish of
+    // 04-c21-tree.rs:58-74 with N's bounds)
     static constexpr bool EVALUATE_TAKES_HOOK = true; // tree_core.inc SpaceEvaluate: hook() = the row's drain and the request's post
     __device__ static __forceinline__ float evaluate(const Arenas &a, Lds &s, const uint32_t dyn, St &st, const int t) {
         return evaluate_hooked(a, s, dyn, st, t, DenseNoHook{});
     }
     template <class Hook>
     __device__ static __forceinline__ float evaluate_hooked(const Arenas &a, Lds &s, const uint32_t dyn, St &st, const int t, Hook &&hook) {
-        const unsigned long long ph_l0 = PH_NOW();
-        const uint8_t parent_mate = a.node_mate[((size_t)t * a.node_cap + st.mate_of) * DENSE_MAX_N + LANE];
-        st.lambda = dense_lambda1_wave(s, a.n, hook);
-        const unsigned long long ph_l1 = PH_NOW();
-        {   // the parent's matching (new_node_begin) after the toggle of this action's edge
-            int mx, mn;
-            dense_from_colex((int)(st.last_aid % (uint32_t)a.E), mx, mn);
-            s.mate[LANE] = parent_mate;
-            LDS_SYNC();
-            st.mu = dense_matching_update(s, a.n, mx, mn);
-        }
-        CTR_ADD(22, ph_l1 - ph_l0);
-        CTR_ADD(23, PH_NOW() - ph_l1);
-        return c21_eval_dense(a.eval_slope, st.lambda, st.mu);
-    }
-    __device__ static __forceinline__ float c21_eval_dense(float slope, double lambda1, int mu) {
-        const float c = (float)mu + (float)lambda1;
-        const float x = c - 2.0f;
-        return slope * x;
+        return Cost::evaluate(a, s, st, t, hook);
     }
     // action_kinds (mod.rs:139-158) over the remaining ranks: bit r of legal[r >> 6]
     __device__ static __forceinline__ void legal_ranks(const Arenas &a, const Lds &s, const St &st, uint64_t (&legal)[KW]) {
@@ -651,15 +726,7 @@ struct DenseSpace {
             }
         }
         WAVE_SYNC();
-        st.lambda = dense_lambda1_wave(s, n, DenseNoHook{});
-        st.mu = dense_matching_scratch(s, n);
-        st.last_aid = 0;
-        a.node_mate[((size_t)t * a.node_cap) * DENSE_MAX_N + LANE] = s.mate[LANE]; // the root node's matching
-        if (LANE == 0) {
-            a.cur_lambda[t] = st.lambda;
-            a.cur_mu[t] = st.mu;
-        }
-        return c21_eval_dense(a.eval_slope, st.lambda, st.mu);
+        return Cost::root_cost(a, t, s, st);
     }
 
     // ---- hooks of the device root policy (root_policy.inc): the drivers' modify_root (04-c21-tree.rs:172-206) over this space --
@@ -717,26 +784,17 @@ struct DenseSpace {
 
     // ArgminData { state, cost, eval } (log.rs:1-11)
     __device__ static void argmin_out(const Arenas &a, Lds &s, const uint32_t dyn, St &st, const int wt, const uint32_t win_node) {
-        DenseArgminRec *out = a.argmin_d;
-        const double lam = dense_lambda1_wave(s, a.n, DenseNoHook{});
-        const int mu = dense_matching_scratch(s, a.n);
-        const float ev = c21_eval_dense(a.eval_slope, lam, mu);
+        typename Cost::Replay r;
+        Cost::argmin_cost(a, s, r);
         open_slots(a, s, st);
-        out->adj[LANE] = LANE < a.n ? s.adj[LANE] : 0ull;
-        if (LANE < 40) out->permitted[LANE] = LANE < 32 ? s.slotmask[LANE] : 0ull;
-        if (LANE == 0) {
-            out->lambda_1 = lam;
-            out->matching_size = mu;
-            out->eval = ev;
-            out->agent = wt;
-            out->node = win_node;
-        }
+        Cost::argmin_write(a, s, r, wt, win_node);
         // a.argmin->eval is what k_argmin / k_argmin_log1 compare against
-        if (LANE == 0) a.argmin->eval = ev;
+        if (LANE == 0) a.argmin->eval = r.ev;
     }
 };
 
 // host side: the key width (words of a rank set) follows the engine's max_slots: 2, 4, 10 or 16 (engine.hip)
+// (DenseSpace<KW> = DenseSpace<KW, DenseCostC21>; the AH engines' switch is dense_ah_kernels.hip's)
 #define DISPATCH_DKW(A, FN, ...)                                  \
     switch ((A).KW) {                                             \
     case 2: FN<DenseSpace<2>>(__VA_ARGS__); break;                \

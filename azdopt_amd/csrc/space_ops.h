@@ -48,7 +48,7 @@ struct SpaceOps : PhaseOps, AsyncOps, PoolOps {};
 const PhaseOps &c21_phase_ops(), &ramsey_phase_ops();
 const AsyncOps &c21_async_ops(), &ramsey_async_ops();
 const PoolOps &c21_pool_ops(), &ramsey_pool_ops();
-const SpaceOps &ramsey64_ops(), &dense_ops();
+const SpaceOps &ramsey64_ops(), &dense_ops(), &dense_ah_ops(); // dense_ah_ops: DenseSpace with the Aouchiche-Hansen cost (dense_ah_kernels.hip)
 
 // ---- the same for every space
 // launch-per-phase form over sub-populations on streams of their own (engine.hip): the candidates of agents a.t0 .. a.t0 + a.tn - 1
@@ -64,6 +64,11 @@ void launch_hash_predictions(float *d_out, int batch, int action_dim, uint64_t s
 void launch_probe_cost(const uint8_t *d_parents, int n, int count, int reps, int full, double *d_lam, int *d_mu,
                        void *stream);
 void launch_probe_math(const float *d_in, float *d_out, int n, void *stream); // sqrtf / sub parity probe (tests)
+// dense_ah_kernels.hip: the Aouchiche-Hansen cost of `count` graphs on n vertices, one wave each (c21_host.h: DenseAhCost), and the
+// f64 division / sqrt parity probe (tests)
+struct DenseAhCost;
+void launch_probe_ah_cost(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream);
+void launch_probe_math_f64(const double *d_in, double *d_out, int n, void *stream);
 
 // ---- pool step of the dense-graph space (dense_kernels.hip): searcher workgroups only (k_pool_search); the evaluator is a stream of
 // batched GEMM launches over the rows the searchers have posted, collected by k_ext_take and handed back by k_ext_deliver (pool_step.inc)
@@ -71,6 +76,11 @@ bool dense_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *d
 void dense_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
                               size_t dyn_bytes, void *stream);
 int dense_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
+// the same three for an AH dense engine (dense_ah_kernels.hip); the evaluator side and the recovery below serve both
+bool dense_ah_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
+void dense_ah_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
+                                 size_t dyn_bytes, void *stream);
+int dense_ah_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
 void launch_ext_take(const PoolArgs &pool, uint32_t *rows, uint32_t *home, uint32_t *n, unsigned long long *t0, void *stream);
 // recovery of an aborted dense pool launch (engine.hip): park (round >= 0: the agents whose calls are through by that round; -1: the
 // agents that are not waiting for a row) / unpark (mode 0), and the candidates of round r under the call each agent is really in

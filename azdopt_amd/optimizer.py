@@ -43,6 +43,20 @@ class DenseArgminData:
         self.agent, self.node = rec.agent, rec.node
 
 
+class DenseAhArgminData:
+    """az-discrete-opt/src/log.rs:1-11 for the dense-graph space with the Aouchiche-Hansen cost: state = neighbourhoods + open
+    slots, cost = {proximity, eigenvalue, diameter, k, cost}"""
+
+    def __init__(self, rec, space):
+        slots = np.zeros(space.KEY_WORDS, np.uint64)
+        ow = (space.E + 63) // 64
+        slots[:ow] = rec.permitted[:ow]
+        self.state = dict(adj=np.array(rec.adj[:space.n], np.uint64), permitted=slots)
+        self.cost = dict(proximity=rec.proximity, eigenvalue=rec.eigenvalue, diameter=rec.diameter, k=rec.k, cost=np.float32(rec.cost))
+        self.eval = np.float32(rec.eval)
+        self.agent, self.node = rec.agent, rec.node
+
+
 class TreeView:
     """Raw arrays of one SearchTree (tree/mod.rs:28-32): nodes, arcs, predictions, keys."""
     FIELDS = ("c", "c_star", "n_t", "exhausted", "act_begin", "act_end", "keys", "e_src", "e_dst", "e_pp",
@@ -97,6 +111,8 @@ class NablaOptimizer:
         if space.SPACE_ID == _lib.SPACE_DENSE:
             cfg.max_slots = space.MAX_SLOTS
             cfg.dense_p = space.p
+            if getattr(space, "COST", "c21") == "ah":
+                cfg.flags |= _lib.ENGINE_DENSE_AH
         if space.SPACE_ID == _lib.SPACE_RAMSEY:
             cfg.max_slots = getattr(space, "MAX_SLOTS", 0)
             if getattr(space, "U64", False):
@@ -208,6 +224,10 @@ class NablaOptimizer:
                 rec = _lib.RamseyArgmin()
                 _lib.check(self._L.azd_engine_ramsey_argmin_data(self._h, C.byref(rec)), "ramsey_argmin_data")
             return RamseyArgminData(rec, self.space)
+        if self.space.SPACE_ID == _lib.SPACE_DENSE and getattr(self.space, "COST", "c21") == "ah":
+            rec = _lib.DenseAhArgmin()
+            _lib.check(self._L.azd_engine_dense_ah_argmin_data(self._h, C.byref(rec)), "dense_ah_argmin_data")
+            return DenseAhArgminData(rec, self.space)
         if self.space.SPACE_ID == _lib.SPACE_DENSE:
             rec = _lib.DenseArgmin()
             _lib.check(self._L.azd_engine_dense_argmin_data(self._h, C.byref(rec)), "dense_argmin_data")
@@ -305,6 +325,13 @@ class NablaOptimizer:
         permitted = np.zeros(self.space.KEY_WORDS, np.uint64)
         path = np.zeros(self.space.KEY_WORDS, np.uint64)
         pos, lam, mu = C.c_uint32(), C.c_double(), C.c_int32()
+        if self.space.SPACE_ID == _lib.SPACE_DENSE and getattr(self.space, "COST", "c21") == "ah":
+            _lib.check(self._L.azd_engine_agent_state(self._h, agent, _lib.ptr(parents), _lib.ptr(permitted), _lib.ptr(path),
+                                                      C.byref(pos), None, None), "agent_state")
+            c = _lib.DenseAhCost()
+            _lib.check(self._L.azd_engine_dense_ah_agent_cost(self._h, agent, C.byref(c)), "dense_ah_agent_cost")
+            return dict(parents=parents, permitted=permitted, path=path, state_pos=pos.value, proximity=c.proximity,
+                        eigenvalue=c.eigenvalue, diameter=c.diameter, k=c.k, cost=np.float32(c.cost))
         _lib.check(self._L.azd_engine_agent_state(self._h, agent, _lib.ptr(parents), _lib.ptr(permitted), _lib.ptr(path),
                                                   C.byref(pos), C.byref(lam), C.byref(mu)), "agent_state")
         return dict(parents=parents, permitted=permitted, path=path, state_pos=pos.value, lambda1=lam.value, matching=mu.value)

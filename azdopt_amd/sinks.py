@@ -117,6 +117,12 @@ def c21_cost_summary(lambda_1, matching_size):
     return Summary().scalar("cost/cost", cost).scalar("cost/lambda_1", lambda_1).scalar("cost/mu", matching_size)
 
 
+def ah_cost_summary(cost):
+    """scalars of the Aouchiche-Hansen cost (DenseAhArgminData.cost): the cost and its parts"""
+    return (Summary().scalar("cost/cost", cost["cost"]).scalar("cost/proximity", cost["proximity"])
+            .scalar("cost/eigenvalue", cost["eigenvalue"]).scalar("cost/diameter", cost["diameter"]))
+
+
 def clique_counts_summary(counts):
     s = Summary()
     for c, n in enumerate(counts):

@@ -3,6 +3,8 @@
 `NablaStateActionSpace` (az-discrete-opt/src/nabla/space/mod.rs:5-39) methods are arbitrary Rust
 in the reference; a device engine needs built-in device implementations, selected by id.  The
 classes here carry the constants and the host-side closures (`init_states`), nothing more."""
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
@@ -183,14 +185,22 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     graphs; the definition is in oracle/dense_graph.inc.  cost = Conjecture2Dot1Cost {lambda_1, matching number};
     evaluate = squish(mu + lambda_1) with the bounds of 04-c21-tree.rs:58-74.  `max_slots`: the most modifiable slots a root
     may bring (= legal actions a node can hold; the engine sizes its keys from it: 128 / 256 / 640 / 1024); the drivers'
-    image is E // 2 (04-c21-tree.rs:85 permits up to half of ACTION_DIM), 128 keeps the keys at two words."""
+    image is E // 2 (04-c21-tree.rs:85 permits up to half of ACTION_DIM), 128 keeps the keys at two words.
+    `cost`: "c21" (the default, above) or "ah" -- the Aouchiche-Hansen cost, the objective of the reference's 05-ah.rs
+    (ConnectedBitsetGraph::ah_cost, mod.rs:156-198): proximity + the distance matrix's eigenvalue of index floor(2D/3) - 1;
+    BUILD-DEFINED evaluate = (cost + 2) / (2N + 2).  N <= 32 there (AZD_ENGINE_DENSE_AH); states, actions, keys and roots are the
+    same space's."""
 
     SPACE_ID = _lib.SPACE_DENSE
 
-    def __init__(self, n, p=0.2, max_slots=128):
+    def __init__(self, n, p=0.2, max_slots=128, cost="c21"):
+        if cost not in ("c21", "ah"):
+            raise ValueError('cost must be "c21" or "ah"')
+        self.COST = cost
         self.n, self.p = int(n), float(p)
-        self.MAX_SLOTS = int(max_slots)
         self.E = self.n * (self.n - 1) // 2
+        # (an AZD_ENGINE_DENSE_AH engine refuses max_slots > E; a root cannot bring more than E slots anyway)
+        self.MAX_SLOTS = min(int(max_slots), self.E) if cost == "ah" else int(max_slots)
         L = _lib.lib()
         self.STATE_DIM = L.azd_dense_state_dim(self.n)
         self.ACTION_DIM = L.azd_dense_action_dim(self.n)
@@ -218,6 +228,15 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     def action(self, index):
         """("add" | "delete", edge slot) of action `index` (AddOrDeleteEdge::from_action_index, action.rs:20-27)"""
         return ("add", index) if index < self.E else ("delete", index - self.E)
+
+    def ah_cost(self, adj):
+        """The Aouchiche-Hansen cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_ah_cost, the same
+        procedure as the device's, bit for bit.  -> dict(proximity, eigenvalue, diameter, k, cost, eval)"""
+        a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
+        out = _lib.DenseAhCost()
+        _lib.check(_lib.lib().azd_dense_ah_cost(_lib.ptr(a), self.n, C.byref(out)), "azd_dense_ah_cost")
+        return dict(proximity=out.proximity, eigenvalue=out.eigenvalue, diameter=out.diameter, k=out.k,
+                    cost=np.float32(out.cost), eval=np.float32(out.eval))
 
 
 class Layered:

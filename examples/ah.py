@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""What the reference's graph-state/examples/05-ah.rs set out to be (its driver is a todo!() stub; its objective,
+ConnectedBitsetGraph::ah_cost, is live code), written as the live drivers' loop over the MI355X engine: a search for counterexamples
+to the Aouchiche-Hansen conjecture on connected graphs with N = 31 vertices.
+
+    python examples/ah.py [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
+
+Roots are G(31, 0.4) redrawn until connected (05-ah.rs:93); the model is 1396-256-128-930 (the stub's widths under the live
+ActionModel head).  The loop is par_roll_out_episodes x episodes, par_update_model, par_reset_trees with the device root policy.
+A cost below 0 would be a counterexample: the run stops there.  (The complete graph's cost is 0 up to the eigen-solve's rounding,
+a few 1e-16 either way, so "below 0" is taken as below -1e-4.)  With --dtype bf16 and 256 agents or more the engine runs its pool
+step; an fp32 model runs one launch per phase."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import azdopt_amd as az  # noqa: E402
+from azdopt_amd import sinks  # noqa: E402
+
+N, P = 31, 0.4                  # 05-ah.rs:30,93
+TOL = ([200, 50, 50], 25)       # the live drivers' n_as_tol (04-c21-tree.rs:136-138)
+COUNTEREXAMPLE_BELOW = -1e-4
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--epochs", type=int, default=250)
+    ap.add_argument("--episodes", type=int, default=800)
+    ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--hidden", type=int, nargs="*", default=[256, 128])
+    ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
+    ap.add_argument("--max-slots", type=int, default=128)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    space = az.DenseGraphSpace(N, P, max_slots=args.max_slots, cost="ah")
+    model = az.ActionModel(args.batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=1e-4, l2=1e-6, seed=args.seed,
+                           dtype=args.dtype)
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        writer = sinks.TensorboardWriter(open(os.path.join(args.out, "tfevents-losses"), "wb"))
+        writer.write_file_version()
+    else:
+        writer = sinks.TensorboardWriter.create("05-ah")
+    kmin, kmax = space.default_permitted_range()
+    caps = az.tree_capacities(args.episodes, kmax)
+    opt = az.NablaOptimizer.par_new(space, space.generate_roots(args.seed, args.batch, kmin=kmin, kmax=kmax), model, args.batch, **caps)
+
+    def process_argmin(argmin, step):
+        c = argmin.cost
+        print("%s\tAhCost { cost: %s, proximity: %s, eigenvalue: %s, diameter: %d, k: %d }"
+              % (argmin.eval, c["cost"], c["proximity"], c["eigenvalue"], c["diameter"], c["k"]))
+        writer.write_summary(None, step, sinks.ah_cost_summary(c))
+        writer.flush()
+        if c["cost"] < COUNTEREXAMPLE_BELOW:
+            raise SystemExit("counterexample to the Aouchiche-Hansen conjecture (cost %s):\n%s" % (c["cost"], argmin.state["adj"]))
+
+    process_argmin(opt.argmin_data(), 0)
+    for epoch in range(1, args.epochs + 1):
+        print("==== EPOCH: %d ====" % epoch)
+        for done in range(1, args.episodes + 1):
+            if opt.par_roll_out_episodes(TOL, n_calls=1):
+                process_argmin(opt.argmin_data(), args.episodes * (epoch - 1) + done)
+        print("==== EPISODE: %d ====" % args.episodes)
+        print("sizes:", sinks.sizes(opt.get_tree(0)))
+        loss = opt.par_update_model(200)
+        writer.write_summary(None, args.episodes * epoch, sinks.loss_summary(loss))
+        writer.write_summary(None, args.episodes * epoch, sinks.ah_cost_summary(opt.argmin_data().cost))
+        writer.flush()
+        opt.par_reset_trees_policy(args.seed, epoch, kmin, kmax)
+
+
+if __name__ == "__main__":
+    main()

@@ -102,6 +102,12 @@ int azd_ramsey_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agen
 /*   139-158, 226-338), AddOrDeleteEdge (bitset_graph/space/action.rs:4-27)   */
 /*   and the STATE = E + ACTION + 1 hint (05-ah.rs:39-40); definition in      */
 /*   oracle/dense_graph.inc.  BASELINE.json configs[4]: N = 50.               */
+/*   The objective is a choice: Conjecture2Dot1Cost (lambda_1 + matching      */
+/*   number; mod.rs:319-338), the default, or -- with the engine flag         */
+/*   AZD_ENGINE_DENSE_AH, N <= AZD_DENSE_AH_MAX_N = 32 -- the Aouchiche-      */
+/*   Hansen cost that 05-ah.rs searches with (ah_cost, mod.rs:156-198;        */
+/*   azd_dense_ah_cost below).  States, actions, vectors and roots are the    */
+/*   same for both.                                                           */
 /* ------------------------------------------------------------------------- */
 #define AZD_SPACE_DENSE 3
 #define AZD_DENSE_MAX_N 64
@@ -260,6 +266,15 @@ typedef struct azd_engine_config {
  * engine takes are accepted too and give the same trees.  Runs the launch-per-phase step form (the CU-resident forms fall back,
  * azd_engine_step_form gives the reason); its argmin is read with azd_engine_ramsey_argmin_any. */
 #define AZD_ENGINE_RAMSEY_U64 16u
+/* The dense-graph space with the Aouchiche-Hansen cost (azd_dense_ah_cost below; the objective of the reference's
+ * examples/05-ah.rs) where a dense engine minimises lambda_1 + matching number by default.  Valid only with AZD_SPACE_DENSE,
+ * never inferred from sizes; without it every limit, kernel and error text is the default's.  Limits, refused by
+ * azd_engine_create with AZD_ERR_INVALID_ARGUMENT and an azd_last_error() naming the argument: 4 <= n <= AZD_DENSE_AH_MAX_N,
+ * layers <= 1, max_slots <= E, ActionSet paths.  State vector, actions, keys, roots and root policy are the dense space's.
+ * Such an engine keeps (proximity, eigenvalue, diameter, k) per agent where the default keeps (lambda_1, matching size), and no
+ * per-node matching arena; read them with azd_engine_dense_ah_agent_cost and azd_engine_dense_ah_argmin_data
+ * (azd_engine_dense_argmin_data, and azd_engine_agent_state's lambda_1 / matching_size, are AZD_ERR_UNSUPPORTED on it). */
+#define AZD_ENGINE_DENSE_AH 32u
 
 /* ArgminData<State, Cost> (az-discrete-opt/src/log.rs:1-11) for the c21 space */
 typedef struct azd_argmin {
@@ -527,6 +542,50 @@ int azd_debug_probe_math(int device, const float *in, float *out, int n);
  * `count` trees, one wavefront each, repeated `reps` times; *ms = GPU time of the timed launch. */
 int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, int reps, int full,
                          double *lambda_1, int *matching_size, float *ms);
+
+/* ---- Aouchiche-Hansen cost: the dense-graph space's second objective (AZD_ENGINE_DENSE_AH engines minimise it; every other dense
+ * engine minimises Conjecture2Dot1Cost = lambda_1 + matching number, as before). (the objective of the reference's examples/05-ah.rs,
+ * ConnectedBitsetGraph::ah_cost, connected_bitset_graph/mod.rs:156-198).  For a CONNECTED graph on n vertices, from a BFS out of
+ * every vertex: proximity pi = min_u sum_v d(u, v) / (n - 1); diameter D; k = floor(2D/3) - 1, or n - 1 when floor(2D/3) = 0
+ * (complete graphs); eigenvalue = entry k (0-based) of the distance matrix's eigenvalues sorted descending;
+ * cost = (float)(pi + eigenvalue).  A graph with cost < 0 would be a counterexample to the Aouchiche-Hansen conjecture.
+ * BUILD-DEFINED (the reference's driver is a stub): eval = slope * (cost + 2.0f), slope = 1.0f / (2n + 2), in the image of the
+ * dense space's squish; and the eigenvalue procedure that stands in for faer -- Householder tridiagonalisation, then a Sturm-count
+ * multisection for the one eigenvalue -- one IEEE f64 operation at a time in a fixed order, so that this host function, the
+ * device kernel (azd_debug_probe_ah_cost) and the tests' Python reference agree bit for bit (DESIGN.md "The AH cost").
+ * 4 <= n <= AZD_DENSE_AH_MAX_N: at 32 vertices a wave's working matrix (a packed triangle) is 4 KB of LDS, at 64 it would be 16 KB. */
+#define AZD_DENSE_AH_MAX_N 32
+typedef struct azd_dense_ah_cost_t {
+    double proximity;  /* pi */
+    double eigenvalue; /* entry k of the distance spectrum, descending */
+    int32_t diameter;  /* D */
+    int32_t k;
+    float cost;        /* (float)(proximity + eigenvalue) */
+    float eval;        /* slope * (cost + 2.0f) */
+} azd_dense_ah_cost_t;
+/* The cost on the host; needs no GPU.  adj: n neighbourhood bitsets (bit u of adj[v] = edge {u, v}).  AZD_ERR_INVALID_ARGUMENT
+ * with an azd_last_error() that names the argument for n out of range or a graph that is not simple, symmetric and connected. */
+int azd_dense_ah_cost(const uint64_t *adj, int n, azd_dense_ah_cost_t *out);
+/* The device kernel in isolation: the cost of `count` graphs on n vertices (adj[count][n]), one wavefront each, repeated `reps`
+ * times; *ms = GPU time of the timed launch.  The graphs are checked like azd_dense_ah_cost's, before the device is looked for. */
+int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms);
+/* ArgminData of an AZD_ENGINE_DENSE_AH engine: the graph, the slots still open, the cost's parts */
+typedef struct azd_dense_ah_argmin {
+    uint64_t adj[32];
+    uint64_t permitted[8]; /* modifiable slots (colex positions) still open; E <= 496 */
+    double proximity, eigenvalue;
+    int32_t diameter, k;
+    float cost, eval;
+    int32_t agent;
+    uint32_t node;
+} azd_dense_ah_argmin;
+int azd_engine_dense_ah_argmin_data(azd_engine *e, azd_dense_ah_argmin *out);
+/* the cost of agent `agent`'s current state as the engine keeps it (the AH counterpart of azd_engine_agent_state's lambda_1 /
+ * matching_size) */
+int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out);
+/* Parity probe for the f64 primitives the AH cost depends on bit for bit.  in: 2*n doubles (pairs x, y); out: 3*n doubles per
+ * pair: [0] x / y, [1] sqrt(|x|), [2] x - (x / y) * y (two roundings: a contracted form would differ). */
+int azd_debug_probe_math_f64(int device, const double *in, double *out, int n);
 
 /* The evaluator's bf16 forward GEMM in isolation (timing, tests): Y[M, N] = act(A[M, K] . W[N, K]^T + bias) on device
  * pointers; A and W are bf16 rows of pitch Kp (a multiple of 64, zero beyond K), Y f32 or bf16 with pitch ldy;

@@ -172,6 +172,23 @@ private:
     int max_slots_;
 };
 
+// The same space with the Aouchiche-Hansen cost as the objective (AZD_ENGINE_DENSE_AH; the objective of the reference's 05-ah.rs,
+// ConnectedBitsetGraph::ah_cost, mod.rs:156-198): n <= AZD_DENSE_AH_MAX_N, max_slots <= E.  argmin_data() gives a DenseAhArgmin.
+class DenseGraphAhSpace : public DenseGraphSpace {
+public:
+    explicit DenseGraphAhSpace(int n, double p = 0.4, int max_slots = 128) : DenseGraphSpace(n, p, max_slots) {}
+    void configure(azd_engine_config &cfg) const {
+        DenseGraphSpace::configure(cfg);
+        cfg.flags |= AZD_ENGINE_DENSE_AH;
+    }
+    // the cost of one connected graph on the host (adj: n neighbourhood bitsets): the device's procedure, bit for bit
+    azd_dense_ah_cost_t cost(const uint64_t *adj) const {
+        azd_dense_ah_cost_t c;
+        check(azd_dense_ah_cost(adj, n(), &c), "azd_dense_ah_cost");
+        return c;
+    }
+};
+
 // ---------------------------------------------------------------- models (NablaModel, nabla/model/mod.rs:4-8)
 class NablaModel {
 public:
@@ -271,6 +288,17 @@ struct DenseArgmin {
     std::vector<uint64_t> permitted; // ... and the edge slots still modifiable
     double lambda_1;                 // cost: Conjecture2Dot1Cost { lambda_1, matching number }
     int matching_number;
+    float eval;
+    int agent;
+    uint32_t node;
+};
+
+struct DenseAhArgmin {
+    std::vector<uint64_t> adj;       // state: neighbourhood bitsets
+    std::vector<uint64_t> permitted; // ... and the edge slots still modifiable
+    double proximity, eigenvalue;    // cost: the Aouchiche-Hansen cost's parts
+    int diameter, k;
+    float cost;                      // (float)(proximity + eigenvalue)
     float eval;
     int agent;
     uint32_t node;
@@ -467,6 +495,22 @@ private:
         r.permitted.assign(a.permitted, a.permitted + slot_words);
         r.lambda_1 = a.lambda_1;
         r.matching_number = a.matching_size;
+        r.eval = a.eval;
+        r.agent = a.agent;
+        r.node = a.node;
+        return r;
+    }
+    DenseAhArgmin argmin_of(const DenseGraphAhSpace &sp) {
+        azd_dense_ah_argmin a;
+        check(azd_engine_dense_ah_argmin_data(h_, &a), "argmin_data");
+        DenseAhArgmin r;
+        r.adj.assign(a.adj, a.adj + sp.n());
+        r.permitted.assign(a.permitted, a.permitted + (sp.E() + 63) / 64);
+        r.proximity = a.proximity;
+        r.eigenvalue = a.eigenvalue;
+        r.diameter = a.diameter;
+        r.k = a.k;
+        r.cost = a.cost;
         r.eval = a.eval;
         r.agent = a.agent;
         r.node = a.node;
