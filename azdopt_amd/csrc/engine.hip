@@ -124,6 +124,64 @@ int azd_evaluator::ensure_staging(int batch) {
 }
 
 // ------------------------------------------------------------------ engine
+// The searcher-only pool step (ext_pool_run) of one kind of engine: the plan, launch and residency entries of its searcher kernel
+// (space_ops.h), how many wavefronts a workgroup of it may have, and the knobs and reason strings it goes by.  The evaluator's side
+// and the recovery of an aborted launch are the same for all of them.
+struct ExtPoolForm {
+    bool (*plan)(const azd::Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
+    void (*launch)(const azd::Arenas &a, const azd::PersistArgs *d_args, const azd::StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
+                   size_t dyn_bytes, void *stream);
+    int (*resident)(const azd::Arenas &a, int waves, size_t dyn_bytes);
+    int waves_max, waves_min;  // wavefronts per searcher workgroup: the default (as many as the LDS holds, down to waves_min) and the knob's range
+    bool needs_pool_step;      // runs only where the engine's configured form is the pool step (dense); else the flag alone asks for it
+    bool keep_quarter_free;    // also without a knob: at most CUs - CUs / 4 searcher workgroups
+    int early_post;            // PoolArgs::early_post without AZD_POOL_EARLY_POST
+    int streams;               // evaluator streams without the knob (<= azd_engine::EXT_STREAMS)
+    const char *env_off, *env_waves, *env_wgs, *env_streams, *env_rounds, *env_depth, *env_debug, *debug_tag;
+    const char *e_waves_range, *r_not_configured, *r_failed_before, *r_needs_bf16, *r_no_wg, *r_aborted, *e_abort_hashed;
+};
+#define AZD_DENSE_EXT_FORM(PLAN, LAUNCH, RESIDENT)                                                                                         \
+    {PLAN, LAUNCH, RESIDENT, 16, 4, true, false, 1, 1, /* the request leaves with the row: the GEMMs run while the wave computes lambda_1 and the matching */ \
+     "AZD_DENSE_NO_POOL", "AZD_DENSE_POOL_WAVES", "AZD_DENSE_POOL_SEARCH_WGS", "AZD_DENSE_POOL_STREAMS", "AZD_DENSE_POOL_ROUNDS", "AZD_DENSE_POOL_DEPTH", \
+     "AZD_DENSE_POOL_DEBUG", "dense pool",                                                                                                 \
+     "AZD_DENSE_POOL_WAVES must be 4..16 (wavefronts per searcher workgroup of the dense-graph pool step)",                                \
+     "dense-graph space: the pool step is not configured for this engine",                                                                 \
+     "an earlier pool launch of this engine aborted: launch-per-phase form",                                                               \
+     "dense-graph space: the pool step needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",                 \
+     "dense-graph space: the device holds no searcher workgroup of the pool step",                                                         \
+     "dense pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "                        \
+     "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",                                    \
+     "dense pool step aborted with the test harness' prediction stream: no recovery"}
+// Ramsey tiers with max_slots > 0 under AZD_ENGINE_EXT_POOL_STEP.  Eight wavefronts per workgroup.  The request
+// leaves with the row (early post): there is no cost to compute behind it, but the tree's write-back and the wave's drain still
+// overlap with the evaluator's round (r3333 1.54 against 1.46 M expansions/s, r45 on the 64-bit tier 0.94 against 0.90).  Two
+// evaluator streams: the evaluator's rounds, not the searchers, bound these engines (its stream is busy 0.8-0.9 of a launch, a
+// searcher wave 0.1-0.2), and a second stream collects and runs its first layer while the first is in its later ones -- r45 on
+// the wide tier 1.26 -> 1.38 M, r3333 and r45 on the 64-bit tier +1..3 % (profiles/r09_ramsey_ext_pool.txt); the dense-graph
+// space, with a population ten times as large, measured the opposite.
+#define AZD_RAMSEY_EXT_FORM(PLAN, LAUNCH, RESIDENT, WAVES)                                                                                 \
+    {PLAN, LAUNCH, RESIDENT, WAVES, 1, false, true, 1, 2, nullptr, "AZD_RAMSEY_EXT_POOL_WAVES", "AZD_RAMSEY_EXT_POOL_SEARCH_WGS",              \
+     "AZD_RAMSEY_EXT_POOL_STREAMS", "AZD_RAMSEY_EXT_POOL_ROUNDS", "AZD_RAMSEY_EXT_POOL_DEPTH", "AZD_RAMSEY_EXT_POOL_DEBUG", "ramsey external pool", \
+     "AZD_RAMSEY_EXT_POOL_WAVES must be 1..8 (wavefronts per searcher workgroup of the external pool step)",                               \
+     "external pool step: not configured for this engine",                                                                                 \
+     "external pool step: an earlier launch of this engine aborted: launch-per-phase form",                                                \
+     "external pool step: needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",                              \
+     "external pool step: the device holds no searcher workgroup",                                                                         \
+     "external pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "                     \
+     "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",                                    \
+     "external pool step aborted with the test harness' prediction stream: no recovery"}
+static const ExtPoolForm *ext_pool_form(int space, bool dense_ah, bool ramsey_u64) {
+    static const ExtPoolForm dense = AZD_DENSE_EXT_FORM(azd::dense_pool_plan, azd::dense_launch_pool_search, azd::dense_pool_search_resident);
+    static const ExtPoolForm ah = AZD_DENSE_EXT_FORM(azd::dense_ah_pool_plan, azd::dense_ah_launch_pool_search, azd::dense_ah_pool_search_resident);
+    static const ExtPoolForm wide = AZD_RAMSEY_EXT_FORM(azd::ramsey_ext_pool_plan, azd::ramsey_ext_launch_pool_search,
+                                                        azd::ramsey_ext_pool_search_resident, azd::RAMSEY_EXT_WAVES);
+    static const ExtPoolForm u64 = AZD_RAMSEY_EXT_FORM(azd::ramsey64_ext_pool_plan, azd::ramsey64_ext_launch_pool_search,
+                                                       azd::ramsey64_ext_pool_search_resident, azd::RAMSEY64_EXT_WAVES);
+    static_assert(azd::RAMSEY_EXT_WAVES == 8 && azd::RAMSEY64_EXT_WAVES == 8, "AZD_RAMSEY_EXT_POOL_WAVES' range is spelled out in its error text");
+    if (space == azd::SPACE_DENSE) return dense_ah ? &ah : &dense;
+    return ramsey_u64 ? &u64 : &wide;
+}
+
 struct azd_engine {
     azd_engine_config cfg;
     azd::Arenas a;
@@ -193,6 +251,14 @@ struct azd_engine {
     int ext_depth = 2;
     hipEvent_t ext_done = nullptr, ext_fork = nullptr, ext_ring[EXT_STREAMS][EXT_IN_FLIGHT] = {};
     unsigned long long ext_iterations = 0; // evaluator graph replays of the last dense pool launch (diagnostics)
+    // which searcher-only pool step this engine has (ExtPoolForm above): the dense-graph space's, or -- under
+    // AZD_ENGINE_EXT_POOL_STEP -- a Ramsey tier's; null: none.  A flagged Ramsey engine keeps the bf16 rows of the form HERE and
+    // not in Arenas::state_vecs16: only the form's own searchers write them (ramsey_ext.inc), so every evaluator call outside the
+    // replayed graph -- the first rows after par_new and a reset, the fallback forms, the completion of an aborted launch -- sees
+    // a null pointer and converts the f32 rows itself, as it does on an engine without the flag.
+    const struct ExtPoolForm *ext = nullptr;
+    uint16_t *ext_s16 = nullptr;
+    int ext_s16_pitch = 0;
     // dense-graph / Ramsey space: host-visible key width (action-id sets); a wide Ramsey engine's device keys are wider (zero-padded)
     int kw_host = 0;
     int ramsey_slots = 0;             // Ramsey: the most permitted edges a root may bring (max_slots; else MAX_NODE_ACTIONS / (C - 1))
@@ -670,8 +736,8 @@ int azd_evaluator_set_params(azd_evaluator *ev, const float *in) { return ev && 
 uint64_t azd_evaluator_calls(azd_evaluator *ev) { return ev ? ev->calls : 0; }
 
 // ------------------------------------------------------------------ engine ABI
-int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evaluator *ev) {
-    if (!out || !cfg) return AZD_ERR_INVALID_ARGUMENT;
+// The argument checks of azd_engine_create, before the device is touched (azd_debug_ext_pool_plan runs them too)
+static int check_engine_config(const azd_engine_config *cfg) {
     const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
     const bool dense = cfg->space_id == AZD_SPACE_DENSE;
     const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
@@ -759,7 +825,39 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         azd::g_last_error = "unknown path encoding";
         return AZD_ERR_INVALID_ARGUMENT;
     }
-    int st = azd::device_ok(cfg->device);
+    // the searcher-only pool step of the Ramsey tiers with max_slots > 0: asked for by name, never chosen from the sizes
+    if (cfg->flags & AZD_ENGINE_EXT_POOL_STEP) {
+        const char *bad = !ramsey || cfg->max_slots <= 0 ? "AZD_ENGINE_EXT_POOL_STEP needs a Ramsey space (AZD_SPACE_RAMSEY) with max_slots > 0 (the wide or the 64-bit tier)"
+                          : (cfg->flags & AZD_ENGINE_NO_PERSISTENT_STEP)
+                              ? "AZD_ENGINE_EXT_POOL_STEP is a CU-resident step form: it cannot be combined with AZD_ENGINE_NO_PERSISTENT_STEP"
+                              : nullptr;
+        if (bad) {
+            azd::g_last_error = bad;
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+    }
+    return AZD_OK;
+}
+// what the LDS plans read of an engine's arenas, for a Ramsey configuration that check_engine_config has accepted
+static void ramsey_shape(const azd_engine_config *cfg, azd::Arenas *a) {
+    a->C = cfg->n_colors;
+    a->E = azd::ramsey_edges(cfg->n);
+    a->A = azd::ramsey_action_dim(cfg->n, a->C);
+    a->S = azd::ramsey_state_dim(cfg->n, a->C);
+    a->KW = azd::ramsey_key_words(cfg->n, a->C);
+    if (cfg->max_slots > 0) { // wide: the device keys padded to the widths ramsey_kernels.hip is built for (RamseyWideSpace<10 / 16>)
+        a->KW = a->A <= 640 ? 10 : 16;
+        if (cfg->flags & AZD_ENGINE_RAMSEY_U64) a->KW = azd::RAMSEY_U64_KW; // one width for the tier (ramsey64_kernels.hip)
+    }
+}
+int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evaluator *ev) {
+    if (!out || !cfg) return AZD_ERR_INVALID_ARGUMENT;
+    int st = check_engine_config(cfg);
+    if (st) return st;
+    const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
+    const bool dense = cfg->space_id == AZD_SPACE_DENSE;
+    const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0;
+    st = azd::device_ok(cfg->device);
     if (st) return st;
     AZD_HIP(hipSetDevice(cfg->device));
     azd_engine *e = new (std::nothrow) azd_engine();
@@ -790,18 +888,9 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         }
         e->kw_host = azd::dense_key_words(cfg->n);
     } else if (ramsey) {
-        a.C = cfg->n_colors;
-        a.E = azd::ramsey_edges(cfg->n);
-        a.A = azd::ramsey_action_dim(cfg->n, a.C);
-        a.S = azd::ramsey_state_dim(cfg->n, a.C);
-        a.KW = azd::ramsey_key_words(cfg->n, a.C);
-        e->kw_host = a.KW;
-        e->ramsey_slots = azd::MAX_NODE_ACTIONS / (a.C - 1);
-        if (cfg->max_slots > 0) { // wide: the device keys padded to the widths ramsey_kernels.hip is built for (RamseyWideSpace<10 / 16>)
-            a.KW = a.A <= 640 ? 10 : 16;
-            e->ramsey_slots = cfg->max_slots;
-            if (cfg->flags & AZD_ENGINE_RAMSEY_U64) a.KW = azd::RAMSEY_U64_KW; // one width for the tier (ramsey64_kernels.hip)
-        }
+        ramsey_shape(cfg, &a);
+        e->kw_host = azd::ramsey_key_words(cfg->n, a.C);
+        e->ramsey_slots = cfg->max_slots > 0 ? cfg->max_slots : azd::MAX_NODE_ACTIONS / (a.C - 1);
         for (int c = 0; c < a.C; ++c) {
             a.sizes[c] = cfg->clique_sizes[c];
             a.cweights[c] = cfg->color_weights[c];
@@ -814,6 +903,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         azd::c21_lambda_bracket(cfg->n, &a.lam_lo, &a.lam_hi);
     }
     e->ops = azd::space_ops(a);
+    if (dense || (cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) e->ext = ext_pool_form(a.space, dense_ah, e->ramsey_u64());
     a.S_inner = a.S;
     a.S = a.S_inner * a.layers; // Layered<L, Space>::STATE_DIM (nabla/space/mod.rs:53)
     if (ev && (ev->state_dim != a.S || ev->action_dim != a.A)) {
@@ -924,6 +1014,16 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         TRY(e->alloc(&a.root_tot, B * 4));
         TRY(e->alloc(&a.cur_tot, B * 4));
         TRY(e->alloc(&a.argmin_r, e->argmin_r_recs()));
+        // AZD_ENGINE_EXT_POOL_STEP with a bf16 evaluator: the rows its searchers write beside the f32 rows (azd_engine::ext_s16; the
+        // padding between S and the pitch is zeroed here and never written)
+        if (e->ext && ev && ev->input16_pitch() >= a.S && ev->input16_pitch() % 8 == 0) {
+            e->ext_s16_pitch = ev->input16_pitch();
+            TRY(e->alloc(&e->ext_s16, B * (size_t)e->ext_s16_pitch));
+            if (hipMemset(e->ext_s16, 0, B * (size_t)e->ext_s16_pitch * 2) != hipSuccess) {
+                azd_engine_destroy(e);
+                return AZD_ERR_HIP;
+            }
+        }
     }
     e->persist_enabled = (cfg->flags & AZD_ENGINE_NO_PERSISTENT_STEP) == 0;
     e->barrier_step = (cfg->flags & AZD_ENGINE_BARRIER_STEP) != 0;
@@ -954,7 +1054,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         TRY(e->alloc(&e->pool.post_call, B));
         TRY(e->alloc(&e->d_resume, B));
         TRY(e->alloc(&e->d_call_ctr, (size_t)azd_engine::MAX_SUBS));
-        if (dense) {
+        if (e->ext) {
             TRY(e->alloc(&e->d_ext_rows, B * azd_engine::EXT_STREAMS));
             TRY(e->alloc(&e->d_ext_home, B * azd_engine::EXT_STREAMS));
             TRY(e->alloc(&e->d_ext_n, (size_t)azd_engine::EXT_STREAMS));
@@ -1006,6 +1106,9 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     if (he == hipSuccess) he = hipMemsetAsync(a.h_theta, 0, B * a.A * 4, e->stream);
     if (he == hipSuccess) he = hipMemsetAsync(a.state_vecs, 0, B * a.S * 4, e->stream); // vec![0.; ..] (optimizer/mod.rs:65)
     if (he == hipSuccess) he = hipMemsetAsync(a.weights, 0, B * a.A * 4, e->stream);
+    // (the argmin kernels write E colours of the record: the entries beyond them are read back as zeros, whatever the memory held before)
+    if (he == hipSuccess && ramsey) he = hipMemsetAsync(a.argmin_r, 0, e->argmin_r_recs() * sizeof(azd::RamseyArgminRec), e->stream);
+    if (he == hipSuccess && ramsey) he = hipMemsetAsync(e->d_argmin_r_side, 0, e->argmin_r_recs() * sizeof(azd::RamseyArgminRec), e->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
     if (he != hipSuccess) {
         st = azd::hip_fail(he, "engine init memset");
@@ -1258,67 +1361,78 @@ static int pool_finish_launch(azd_engine *e, const azd::FusedEval &fe, const azd
 // lasts as long as its slowest agent per call (launch-per-phase form: a roll-out launch took 1.2 ms where the mean agent needed 0.06).
 // *ran = false: the form cannot run here (why in e->step_reason) and the caller takes the launch-per-phase form.
 // *left_out: calls still to run when an aborted launch had to be completed by the launch-per-phase kernels (the caller runs them).
-static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bool *ran, int *left_out) {
+// The Ramsey tiers with max_slots > 0 run the same form under AZD_ENGINE_EXT_POOL_STEP: what differs between the engines that have
+// it -- the searcher kernel's entries, its wavefronts per workgroup, knobs and reason strings -- comes from e->ext (ExtPoolForm).
+static int ext_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bool *ran, int *left_out) {
     *ran = false;
     *left_out = 0;
-    const azd::Arenas &a = e->a;
+    const ExtPoolForm &xf = *e->ext;
+    // what the searchers and the evaluator's graph see: a flagged Ramsey engine's bf16 rows exist for this form only (azd_engine::ext_s16)
+    azd::Arenas ax = e->a;
+    if (e->ext_s16) {
+        ax.state_vecs16 = e->ext_s16;
+        ax.S16 = e->ext_s16_pitch;
+    }
+    const azd::Arenas &a = ax;
     const char *why = "";
     uint32_t dyn_stride = 0;
     size_t dyn_bytes = 0;
     // wavefronts per searcher workgroup: 16, or as many as the LDS holds (roots of more than 640 slots: 12 -- a wave's block and its
     // selection scratch are 12 KB there)
-    int waves = 16;
-    if (const char *env = getenv("AZD_DENSE_POOL_WAVES")) {
+    // (the Ramsey tiers: 8, the bound their kernels are built for -- every shape the tiers accept fits)
+    int waves = xf.waves_max;
+    if (const char *env = getenv(xf.env_waves)) {
         waves = atoi(env);
-        if (waves < 4 || waves > 16) { // (round-4 verdict, 7c: a knob out of range is refused, not silently bent)
-            azd::g_last_error = "AZD_DENSE_POOL_WAVES must be 4..16 (wavefronts per searcher workgroup of the dense-graph pool step)";
+        if (waves < xf.waves_min || waves > xf.waves_max) { // (round-4 verdict, 7c: a knob out of range is refused, not silently bent)
+            azd::g_last_error = xf.e_waves_range;
             return AZD_ERR_INVALID_ARGUMENT;
         }
     }
-    const bool ah = e->dense_ah();
-    auto pool_plan = ah ? azd::dense_ah_pool_plan : azd::dense_pool_plan;
-    while (waves > 4 && !pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) waves -= 1;
+    const bool knobs = getenv(xf.env_wgs) || getenv(xf.env_waves);
+    auto pool_plan = xf.plan;
+    while (waves > xf.waves_min && !pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) waves -= 1;
     azd::FusedEval fe;
     const bool hashed = e->ev->fused_desc(&fe) && fe.kind == 4; // the test harness' fixed prediction stream, served like a model's rows
-    if (!e->pool_step || !e->persist_enabled || e->pool_failed || e->ext_unsupported || (!a.state_vecs16 && !hashed) ||
+    const bool configured = (e->pool_step || !xf.needs_pool_step) && e->persist_enabled;
+    if (!configured || e->pool_failed || e->ext_unsupported || (!a.state_vecs16 && !hashed) ||
         n_calls < 1 || !pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) {
-        e->step_reason = !e->pool_step || !e->persist_enabled ? "dense-graph space: the pool step is not configured for this engine"
-                         : e->pool_failed                      ? "an earlier pool launch of this engine aborted: launch-per-phase form"
-                         : ((!a.state_vecs16 && !hashed) || e->ext_unsupported)
-                             ? "dense-graph space: the pool step needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)"
-                             : why;
+        e->step_reason = !configured       ? xf.r_not_configured
+                         : e->pool_failed ? xf.r_failed_before
+                         : ((!a.state_vecs16 && !hashed) || e->ext_unsupported) ? xf.r_needs_bf16
+                                                                                 : why;
         return AZD_OK;
     }
-    const int per_cu = (ah ? azd::dense_ah_pool_search_resident : azd::dense_pool_search_resident)(a, waves, dyn_bytes);
+    const int per_cu = xf.resident(a, waves, dyn_bytes);
     // searcher workgroups: no more waves than twice the agents, and no more than half the chip's wave slots -- the GEMM launches
     // need the rest
     int n_search = (2 * a.B + waves - 1) / waves;
     if (n_search > e->n_cus * 8 / waves) n_search = e->n_cus * 8 / waves;
-    if (const char *env = getenv("AZD_DENSE_POOL_SEARCH_WGS")) n_search = atoi(env) > 0 ? atoi(env) : n_search;
+    if (xf.keep_quarter_free && n_search > e->n_cus - e->n_cus / 4) n_search = e->n_cus - e->n_cus / 4;
+    if (const char *env = getenv(xf.env_wgs)) n_search = atoi(env) > 0 ? atoi(env) : n_search;
     // The evaluator of this form is a stream of GEMM LAUNCHES beside the searchers' persistent kernel: they run only where a CU has
     // LDS and registers left, and a searcher workgroup (1024 threads' worth of LDS blocks) leaves none.  A setting of the two knobs
     // that lets the searchers cover more than three quarters of the CUs used to be accepted and then cost a 4-s wait bound, an
     // abort and the engine's demotion to the launch-per-phase form (gpurun_out/ew.txt, round 4): refused up front instead.
     // (workgroups, not wave slots: the dispatcher deals one workgroup to every CU before it doubles up, so 256 workgroups of 8 waves
     // sit on 256 CUs although two would fit one)
-    if (per_cu >= 1 && (getenv("AZD_DENSE_POOL_SEARCH_WGS") || getenv("AZD_DENSE_POOL_WAVES")) && n_search > e->n_cus - e->n_cus / 4) {
+    if (per_cu >= 1 && knobs && n_search > e->n_cus - e->n_cus / 4) {
         static thread_local char msg[256];
-        snprintf(msg, sizeof msg, "AZD_DENSE_POOL_SEARCH_WGS / AZD_DENSE_POOL_WAVES: %d searcher workgroups of %d waves would sit on %d of %d CUs; "
-                 "the evaluator's GEMM launches need at least a quarter of the chip free (at most %d workgroups)", n_search, waves,
+        snprintf(msg, sizeof msg, "%s / %s: %d searcher workgroups of %d waves would sit on %d of %d CUs; "
+                 "the evaluator's GEMM launches need at least a quarter of the chip free (at most %d workgroups)", xf.env_wgs, xf.env_waves, n_search, waves,
                  n_search < e->n_cus ? n_search : e->n_cus, e->n_cus, e->n_cus - e->n_cus / 4);
         azd::g_last_error = msg;
         return AZD_ERR_INVALID_ARGUMENT;
     }
     if (per_cu < 1 || n_search > e->n_cus * per_cu * 7 / 8) n_search = per_cu < 1 ? 0 : e->n_cus * per_cu * 7 / 8;
     if (n_search < 1) {
-        e->step_reason = "dense-graph space: the device holds no searcher workgroup of the pool step";
+        e->step_reason = xf.r_no_wg;
         return AZD_OK;
     }
     // (one stream by default: with two, each batch is half as large and takes as long -- the GEMMs' k loops are latency-bound at these
     // batch sizes and the streams share the same CUs -- so an agent's cycle, which sets the rate, gets no shorter: 18.8 M expansions/s
     // with one stream against 17.8 with two at config E)
-    int n_ext = 1;
-    if (const char *env = getenv("AZD_DENSE_POOL_STREAMS")) n_ext = atoi(env);
+    int n_ext = xf.streams;
+    if (const char *env = getenv(xf.env_streams)) n_ext = atoi(env);
     n_ext = n_ext < 1 ? 1 : n_ext > azd_engine::EXT_STREAMS ? azd_engine::EXT_STREAMS : n_ext;
     if (!e->ext_done) AZD_HIP(hipEventCreateWithFlags(&e->ext_done, hipEventDisableTiming));
     if (!e->ext_fork) AZD_HIP(hipEventCreateWithFlags(&e->ext_fork, hipEventDisableTiming));
@@ -1333,7 +1447,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
     pool.n_express = 0;
     pool.express_waves = 0;
     pool.express_shift = 0;
-    pool.early_post = 1; // the request leaves with the row: the GEMMs run while the wave computes lambda_1 and the matching
+    pool.early_post = xf.early_post;
     if (const char *env = getenv("AZD_POOL_EARLY_POST")) pool.early_post = atoi(env);
     pool.eval_stride = pool.eval_out_off = 0;
     pool.eval_rows = 0;
@@ -1346,7 +1460,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
         if (st_r) return st_r;
     }
     int rounds = 4; // collect / layers / hand-back rounds per replay of the evaluator's graph
-    if (const char *env = getenv("AZD_DENSE_POOL_ROUNDS")) rounds = atoi(env);
+    if (const char *env = getenv(xf.env_rounds)) rounds = atoi(env);
     rounds = rounds < 1 ? 1 : rounds > 16 ? 16 : rounds;
     const uint64_t layout = e->ev->layout_version + (hashed ? 1ull << 63 : 0ull) + ((uint64_t)rounds << 56);
     if (e->ext_graph_n != n_ext || e->ext_graph_layout != layout) {
@@ -1373,7 +1487,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
                 if (g) (void)hipGraphDestroy(g);
                 if (st_g != AZD_ERR_UNSUPPORTED) return st_g;
                 e->ext_unsupported = true;
-                e->step_reason = "dense-graph space: the pool step needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)";
+                e->step_reason = xf.r_needs_bf16;
                 return AZD_OK;
             }
             if (he != hipSuccess) return azd::hip_fail(he, "hipStreamEndCapture");
@@ -1430,7 +1544,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
         sl.hashed = hashed ? 1 : 0;
         sl.window = 0;
         e->time_begin(0);
-        (ah ? azd::dense_ah_launch_pool_search : azd::dense_launch_pool_search)(a, e->d_pargs, sl, n_search, waves, dyn_stride, dyn_bytes, e->stream);
+        xf.launch(a, e->d_pargs, sl, n_search, waves, dyn_stride, dyn_bytes, e->stream);
 #ifndef AZD_PHASE_PROFILE
         e->counters_by_wave = true;
 #endif
@@ -1442,7 +1556,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
         // replays queued per stream at a time -- a replay that finds nothing posted costs a few microseconds
         unsigned long long it = 0;
         int depth = e->ext_depth;
-        if (const char *env = getenv("AZD_DENSE_POOL_DEPTH")) depth = atoi(env);
+        if (const char *env = getenv(xf.env_depth)) depth = atoi(env);
         depth = depth < 1 ? 1 : depth > azd_engine::EXT_IN_FLIGHT ? azd_engine::EXT_IN_FLIGHT : depth;
         for (;;) {
             const hipError_t q = hipEventQuery(e->ext_done);
@@ -1458,7 +1572,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
         }
         for (int x = 0; x < n_ext; ++x) AZD_HIP(hipStreamSynchronize(e->ext_stream[x]));
         e->ext_iterations += it;
-        if (getenv("AZD_DENSE_POOL_DEBUG")) fprintf(stderr, "dense pool: %d calls, %d searcher workgroups, %llu evaluator replays\n", k, n_search, it);
+        if (getenv(xf.env_debug)) fprintf(stderr, "%s: %d calls, %d searcher workgroups, %llu evaluator replays\n", xf.debug_tag, k, n_search, it);
         left -= k;
         e->ev->calls += (uint64_t)k;
         st = fetch_status(e);
@@ -1477,6 +1591,9 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
             // agent from where each one stands (k_pool_resume_scan), the ones that are through sitting out (FLAG_PARKED), every
             // candidate logged under the call it really belongs to, one replay of the log at the end -- the results of an
             // undisturbed launch.  This engine stays with the launch-per-phase form.
+            // (the engine's own arenas from here on: a flagged Ramsey engine's launch-per-phase kernels write no bf16 rows, so the
+            // evaluator is handed none and converts the f32 rows -- ext_s16 above)
+            const azd::Arenas &a = e->a;
             e->pool_failed = true;
             e->log_clean = false;
             azd::launch_pool_resume_scan(a, pool, k, e->d_resume, e->stream);
@@ -1494,7 +1611,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
             }
             auto evaluate_rows = [&]() -> int {
                 if (hashed) { // the fixed stream's rows depend on the call: not reproducible outside the launch that posted them
-                    azd::g_last_error = "dense pool step aborted with the test harness' prediction stream: no recovery";
+                    azd::g_last_error = xf.e_abort_hashed;
                     return AZD_ERR_UNREACHABLE;
                 }
                 const uint64_t calls_before = e->ev->calls;
@@ -1523,8 +1640,7 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
             st = fetch_status(e);
             if (st) return st;
             e->step_form = AZD_STEP_PER_CALL;
-            e->step_reason = "dense pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "
-                             "progress); the launch-per-phase kernels completed the launch and serve this engine from here on";
+            e->step_reason = xf.r_aborted;
             *ran = true;
             *left_out = left;
             return AZD_OK;
@@ -1539,11 +1655,11 @@ static int dense_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bo
 static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int *improved, bool ahead, int *accepted) {
     int st = AZD_OK;
     if (accepted) *accepted = 0;
-    if (e->a.space == azd::SPACE_DENSE && !getenv("AZD_DENSE_NO_POOL")) {
-        if (ahead) return AZD_OK; // (the evaluator's launches need this thread: nothing can run ahead of the host)
+    if (e->ext && !(e->ext->env_off && getenv(e->ext->env_off))) {
+        if (ahead) return AZD_OK; // (the evaluator's launches need this thread: nothing can run ahead of the host; a hint, declined)
         bool ran = false;
         int left_after = 0;
-        st = dense_pool_run(e, t, n_calls, &ran, &left_after);
+        st = ext_pool_run(e, t, n_calls, &ran, &left_after);
         if (st) return st;
         if (ran && left_after == 0) {
             st = check_status(e);
@@ -1554,10 +1670,16 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
         if (ran) n_calls = left_after; // (an aborted launch was completed call by call: what is left runs the same way, below)
     }
     const std::string dense_reason = e->a.space == azd::SPACE_DENSE ? e->step_reason : std::string();
+    // a Ramsey engine under AZD_ENGINE_EXT_POOL_STEP whose form did not run takes what it would have taken without the flag; the
+    // reason opens with why the form did not run.  After an aborted launch of the form it stays with the launch-per-phase kernels
+    // that completed it.
+    const bool ext_ramsey = e->ext && e->a.space == azd::SPACE_RAMSEY;
+    const std::string ext_reason = ext_ramsey ? e->step_reason : std::string();
+    const bool ext_demoted = ext_ramsey && e->pool_failed;
     azd::FusedEval fe;
     uint32_t dyn_stride = 0;
     size_t dyn_bytes = 0;
-    const bool fusable = e->persist_enabled && e->ev->fused_desc(&fe);
+    const bool fusable = e->persist_enabled && !ext_demoted && e->ev->fused_desc(&fe);
     const char *why_a = "", *why_b = "";
     const char *why_p = "";
     azd::PoolArgs pool = e->pool;
@@ -1782,6 +1904,7 @@ static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int
     e->step_form = use_pool ? AZD_STEP_POOL : use_async ? AZD_STEP_ASYNC : use_barrier ? AZD_STEP_BARRIER : AZD_STEP_PER_CALL;
     if (e->a.space == azd::SPACE_DENSE) // why the space's pool step did not run: the launch-per-phase form follows
         e->step_reason = dense_reason.empty() ? "AZD_DENSE_NO_POOL: the dense-graph space's pool step was switched off" : dense_reason;
+    if (ext_ramsey) e->step_reason = ext_demoted || e->step_reason.empty() ? ext_reason : ext_reason + "; " + e->step_reason;
     if (ahead) { // only the pool step publishes its calls while it runs, one launch's worth of them
         const bool ok = use_pool && fe.kind >= 3 && n_calls >= 1 && n_calls <= e->log_calls && !e->timing;
         if (!ok) return AZD_OK; // a hint: the calls run when they are asked for
@@ -2849,6 +2972,37 @@ int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks) {
     if (he == hipSuccess) he = hipMemcpy(out, d, (size_t)n_blocks * 4, hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (he != hipSuccess) return azd::hip_fail(he, "probe_xcc");
+    return AZD_OK;
+}
+// The LDS plan of the searcher-only pool step for a configuration (AZD_ENGINE_EXT_POOL_STEP): wavefronts per searcher workgroup
+// and bytes of LDS a workgroup takes, its static blocks included.  Arithmetic only: no device is touched.
+int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes) {
+    if (!cfg || !waves || !lds_bytes) return AZD_ERR_INVALID_ARGUMENT;
+    const int st = check_engine_config(cfg);
+    if (st) return st;
+    if (!(cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) {
+        azd::g_last_error = "azd_debug_ext_pool_plan: the configuration does not set AZD_ENGINE_EXT_POOL_STEP";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    azd::Arenas a;
+    memset(&a, 0, sizeof(a));
+    a.space = azd::SPACE_RAMSEY;
+    a.n = cfg->n;
+    a.B = cfg->batch;
+    a.node_cap = cfg->node_capacity > 0 ? (uint32_t)cfg->node_capacity : 4096u;
+    ramsey_shape(cfg, &a);
+    const ExtPoolForm *xf = ext_pool_form(a.space, false, a.KW == azd::RAMSEY_U64_KW);
+    const char *why = "";
+    uint32_t dyn_stride = 0;
+    size_t dyn_bytes = 0;
+    int w = xf->waves_max;
+    while (w > xf->waves_min && !xf->plan(a, w, &dyn_stride, &dyn_bytes, &why)) w -= 1;
+    if (!xf->plan(a, w, &dyn_stride, &dyn_bytes, &why)) {
+        azd::g_last_error = why;
+        return AZD_ERR_UNSUPPORTED;
+    }
+    *waves = w;
+    *lds_bytes = dyn_bytes + azd::POOL_SEARCH_STATIC_LDS;
     return AZD_OK;
 }
 int azd_engine_step_form(azd_engine *e, int *form, const char **reason) {

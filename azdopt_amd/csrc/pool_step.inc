@@ -1171,6 +1171,29 @@ __global__ __launch_bounds__(PERSIST_WAVES * 64) void k_pool_search(const Persis
     __syncthreads();
     pool_search<SP, MODE>(pa, n_calls, log_key, s, SW_BYTES + (uint32_t)wave * dyn_stride, xcc, idle, false);
 }
+// The same searchers for a space whose waves are too large for the layout above (the Ramsey tiers with max_slots > 0,
+// ramsey_ext.inc): WAVES wavefronts per workgroup at the most, WAVES static blocks -- sixteen RamseyU64Lds blocks are 79 KB before
+// any wave's clique counts -- and a launch bound of WAVES * 64 threads, so that eight waves may keep 256 registers each.
+template <class SP, int MODE, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void k_pool_search_w(const PersistArgs *__restrict__ pa, int n_calls,
+                                                              unsigned long long *__restrict__ log_key, uint32_t dyn_stride) {
+    constexpr uint32_t SW_BYTES = (uint32_t)((WAVES * sizeof(typename SP::Lds) + 15) & ~(size_t)15);
+    typename SP::Lds *const sw = reinterpret_cast<typename SP::Lds *>(lds_base(0u));
+    __shared__ PoolIdle idle;
+    const uint32_t xcc = pool_xcc_id();
+    if (threadIdx.x == 0) atomicCAS(&pa->pool.ctl->t_first, 0ull, (unsigned long long)wall_clock64());
+    const int wave = threadIdx.x >> 6;
+    typename SP::Lds &s = sw[wave];
+    if (threadIdx.x == 0) {
+        idle.leave = 0u;
+        idle.claims_done = 0u;
+        idle.mean_calls = 0u;
+    }
+    SP::prepare(pa->a, s);
+    if (LANE < NUM_COUNTERS) s.ctr[LANE] = 0;
+    __syncthreads();
+    pool_search<SP, MODE>(pa, n_calls, log_key, s, SW_BYTES + (uint32_t)wave * dyn_stride, xcc, idle, false);
+}
 
 #ifdef AZD_TU_POOL_EXT
 // What the searchers have posted, XCD by XCD (wave x of the block takes queue x): the tickets whose slot is filled, in order, up

@@ -81,6 +81,19 @@ bool dense_ah_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t
 void dense_ah_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
                                  size_t dyn_bytes, void *stream);
 int dense_ah_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
+// the same three for the Ramsey tiers with max_slots > 0 under AZD_ENGINE_EXT_POOL_STEP (ramsey_ext_kernels.hip: the 32-bit wide tier;
+// ramsey64_ext_kernels.hip: the 64-bit tier).  waves <= *_EXT_WAVES, the wavefronts per workgroup their kernels are built and
+// launch-bounded for (k_pool_search_w; DESIGN.md section 3 says why eight).  The plans are arithmetic: they touch no device.
+constexpr int RAMSEY_EXT_WAVES = 8, RAMSEY64_EXT_WAVES = 8;
+constexpr size_t POOL_SEARCH_STATIC_LDS = 16; // k_pool_search_w's static LDS (PoolIdle) beside the dynamic region the plans lay out
+bool ramsey_ext_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
+void ramsey_ext_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
+                                   size_t dyn_bytes, void *stream);
+int ramsey_ext_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
+bool ramsey64_ext_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
+void ramsey64_ext_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
+                                     size_t dyn_bytes, void *stream);
+int ramsey64_ext_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
 void launch_ext_take(const PoolArgs &pool, uint32_t *rows, uint32_t *home, uint32_t *n, unsigned long long *t0, void *stream);
 // recovery of an aborted dense pool launch (engine.hip): park (round >= 0: the agents whose calls are through by that round; -1: the
 // agents that are not waiting for a row) / unpark (mode 0), and the candidates of round r under the call each agent is really in

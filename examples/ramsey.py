@@ -41,6 +41,9 @@ def main():
     ap.add_argument("--stride", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ext-pool-step", action="store_true",
+                    help="r45 / r3333 with bf16 weight storage: the searcher-only pool step with the model's batched GEMMs beside it "
+                         "(NablaOptimizer.par_new(..., ext_pool_step=True)); the default stays the engine's own choice of form")
     args = ap.parse_args()
     d = DRIVERS[args.driver]
     batch = args.batch or d["batch"]
@@ -48,7 +51,7 @@ def main():
 
     space = az.RamseySpaceNoEdgeRecolor(d["n"], d["sizes"], d.get("weights", [1.0] * len(d["sizes"])))
     model = az.ActionModel(batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=d.get("lr", 1e-4), l2=1e-6, seed=args.seed,
-                           final_act=d.get("final_act", az._lib.ACT_SIGMOID))
+                           final_act=d.get("final_act", az._lib.ACT_SIGMOID), **(dict(dtype="bf16") if args.ext_pool_step else {}))
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         writer = sinks.TensorboardWriter(open(os.path.join(args.out, "tfevents-losses"), "wb"))
@@ -62,7 +65,8 @@ def main():
         kmax = d["kmax"]
     C = len(d["sizes"])
     caps = az.tree_capacities(episodes, kmax * (C - 1))  # (limits of the packed records: 65536 nodes, 65535 arcs, 2^20 predictions)
-    opt = az.NablaOptimizer.par_new(space, space.generate_roots(args.seed, batch, kmin=kmin, kmax=kmax), model, batch, **caps)
+    opt = az.NablaOptimizer.par_new(space, space.generate_roots(args.seed, batch, kmin=kmin, kmax=kmax), model, batch, **caps,
+                                    **(dict(ext_pool_step=True) if args.ext_pool_step else {}))
 
     def process_argmin(argmin, step):
         print("%s\tTotalCounts(%s)" % (argmin.eval, argmin.cost["clique_counts"]))

@@ -263,8 +263,10 @@ typedef struct azd_engine_config {
  * reference's B64), E*C <= 2304 (keys of 36 words: N = 34 at four colours, 39 at three, 48 at two), 2..4 colours, clique sizes
  * 2..5, 1 <= max_slots <= E and max_slots * (C - 1) <= AZD_RAMSEY_U64_NODE_ACTIONS; ActionSet paths only, no Layered wrapper.
  * Never chosen from the sizes: without the flag every limit, kernel and error text is the 32-bit tiers'.  Shapes a 32-bit wide
- * engine takes are accepted too and give the same trees.  Runs the launch-per-phase step form (the CU-resident forms fall back,
- * azd_engine_step_form gives the reason); its argmin is read with azd_engine_ramsey_argmin_any. */
+ * engine takes are accepted too and give the same trees.  Runs the launch-per-phase step form (the other CU-resident forms fall
+ * back, azd_engine_step_form gives the reason) or, with AZD_ENGINE_EXT_POOL_STEP beside it and a bf16 model, the searcher-only pool
+ * step (r3333 at 512 agents 1.53 M expansions/s against 1.00 M, r45 at 256 agents 0.97 M against 0.29 M); its argmin is read with
+ * azd_engine_ramsey_argmin_any. */
 #define AZD_ENGINE_RAMSEY_U64 16u
 /* The dense-graph space with the Aouchiche-Hansen cost (azd_dense_ah_cost below; the objective of the reference's
  * examples/05-ah.rs) where a dense engine minimises lambda_1 + matching number by default.  Valid only with AZD_SPACE_DENSE,
@@ -275,6 +277,24 @@ typedef struct azd_engine_config {
  * per-node matching arena; read them with azd_engine_dense_ah_agent_cost and azd_engine_dense_ah_argmin_data
  * (azd_engine_dense_argmin_data, and azd_engine_agent_state's lambda_1 / matching_size, are AZD_ERR_UNSUPPORTED on it). */
 #define AZD_ENGINE_DENSE_AH 32u
+/* AZD_SPACE_RAMSEY with max_slots > 0 only (the 32-bit wide tier, or the 64-bit tier beside AZD_ENGINE_RAMSEY_U64): the
+ * searcher-only pool step, the CU-resident form of these engines for a model that does not fit an evaluator workgroup's LDS.
+ * Persistent searcher workgroups of eight wavefronts pull agents from the per-XCD ready queues, write each new node's state row
+ * to memory (f32, and bf16 beside it) and post a request; on a second stream the host replays a graph of [collect the requests,
+ * the model's bf16 GEMMs over the gathered rows, hand the agents back] for as long as the searchers run -- the dense-graph
+ * space's form.  Results are bit for bit those of the launch-per-phase form.  Never chosen from the sizes: without the flag every
+ * engine, limit, kernel, fallback chain and reason string is what it is without it.  On any other engine (c21, dense-graph,
+ * Ramsey with max_slots == 0) and together with AZD_ENGINE_NO_PERSISTENT_STEP azd_engine_create returns
+ * AZD_ERR_INVALID_ARGUMENT.  Needs an evaluator that serves gathered bf16 rows: an MLP with AZD_STORAGE_BF16 (or the tests' hash
+ * stream); with any other the engine runs what it would have run without the flag and azd_engine_step_form's reason opens with
+ * "external pool step:".  When the form runs azd_engine_step_form reports AZD_STEP_POOL with an empty reason and
+ * azd_engine_pool_split 0 evaluator workgroups beside the searcher workgroups.
+ * Which form where (profiles/r09_ramsey_ext_pool.txt, bf16 storage): on the 64-bit tier this one -- 1.5 times the launch-per-phase
+ * form at r3333, 3.3 times at r45.  On the 32-bit wide tier prefer the in-kernel pool step (AZD_ENGINE_POOL_STEP, the default from
+ * 256 agents) wherever its plan takes the model: at r45 with 512-1024-512 the two run level (1.39 against 1.40 M expansions/s, 256
+ * agents) and the in-kernel form needs no second stream and no host thread; take this one for a model whose 16 bf16 rows of
+ * activations do not fit an evaluator workgroup's LDS, where the in-kernel form falls back to one launch per phase (0.39 M). */
+#define AZD_ENGINE_EXT_POOL_STEP 64u
 
 /* ArgminData<State, Cost> (az-discrete-opt/src/log.rs:1-11) for the c21 space */
 typedef struct azd_argmin {
@@ -526,6 +546,10 @@ int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks);
  * same harness: AZD_POOL_DEBUG_ABORT_CALL=k (agent 0 raises the launch's abort flag after its k-th call: the take-over by the
  * asynchronous step), AZD_POOL_MAX_RESIDENT=w (pretend the device holds w workgroups of the pool kernel at once). */
 int azd_debug_hash_stream_via_evaluators(azd_evaluator *ev, int on);
+/* The LDS plan of the searcher-only pool step (AZD_ENGINE_EXT_POOL_STEP) for a configuration: wavefronts per searcher workgroup and
+ * the bytes of LDS one workgroup takes (of the CU's 160 KB).  Arithmetic on the configuration: no device is touched.
+ * AZD_ERR_INVALID_ARGUMENT for a configuration azd_engine_create refuses, or one without the flag. */
+int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes);
 /* The MLP evaluator's training gradient without the optimiser step (tests against a float64 reference): the same launches
  * as azd_evaluator_update_model up to the Adam step, on host rows staged like that call's.  grads_out: num_params floats in
  * the get_params layout; *loss as update_model reports it.  Parameters, Adam moments and the step count are left untouched.

@@ -5,8 +5,11 @@ asked for with the engine's flags; the line says which form ran and, when anothe
 --preset u64: the 64-bit tier (AZD_ENGINE_RAMSEY_U64) at the reference's R(3,3,3,3) shape (03-r3333.rs: N 34, four colours, 10..=30
 permitted edges, 512-1024-512 model with a ReLU head, 512 agents) and r45 under the flag beside r45 on the 32-bit tier (what the
 wider word costs).
+The form 'ext' is the searcher-only pool step (par_new(..., ext_pool_step=True): bf16 storage only; with fp32 the line shows what ran
+instead); its line ends with the busy shares of the evaluator's stream and of the searching waves (azd_engine_pool_utilisation).
+--forms picks the forms to time (a library built before 'ext' existed, chosen with AZD_LIB, is timed with --forms per_call pool).
 
-    python tools/time_ramsey_wide.py [--preset wide|u64] [--batch 256] [--calls 60] [--warmup 10]"""
+    python tools/time_ramsey_wide.py [--preset wide|u64] [--batch 256] [--calls 60] [--warmup 10] [--forms ext per_call] [--shapes r45]"""
 import argparse
 import os
 import re
@@ -18,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import azdopt_amd as az  # noqa: E402
 
 FORMS = {"pool": dict(pool_step=True), "async": dict(async_step=True, pool_step=False),
-         "barrier": dict(async_step=False, pool_step=False), "per_call": dict(persistent=False)}
+         "barrier": dict(async_step=False, pool_step=False), "per_call": dict(persistent=False), "ext": dict(ext_pool_step=True)}
 TOL = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
 SHAPES = [("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "f32"), ("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "bf16"),
           ("n32c2", 32, [4, 4], [1.0, 1.0], "f32")]
@@ -38,6 +41,9 @@ def main():
     ap.add_argument("--calls", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--hidden", type=int, nargs="*", default=[512, 1024, 512])
+    ap.add_argument("--forms", nargs="*", default=list(FORMS), choices=list(FORMS))
+    ap.add_argument("--shapes", nargs="*", default=None, help="tags of the preset's shapes to run (default: all)")
+    ap.add_argument("--dtypes", nargs="*", default=["f32", "bf16"])
     args = ap.parse_args()
     B, calls = args.batch, args.calls
     print("# wide Ramsey engines (tools/time_ramsey_wide.py): batch %d, %d timed calls after %d, hidden %s; r45 = N 24, [4, 5], 10..=276 "
@@ -49,12 +55,14 @@ def main():
     print("# shape  dtype  asked     ran       expansions/s  s/call     why")
     for tag, n, sizes, weights, dtype, *rest in (U64_SHAPES if args.preset == "u64" else SHAPES):
         o = rest[0] if rest else {}
+        if (args.shapes and tag not in args.shapes) or dtype not in args.dtypes:
+            continue
         B = o.get("batch", args.batch)
         space = az.RamseySpaceNoEdgeRecolor(n, sizes, weights, u64=o.get("u64"))
         kmax = o.get("kmax", space.E)
         roots = space.generate_roots(0, B, kmin=10, kmax=kmax)
         for form, kw in FORMS.items():
-            if form not in o.get("forms", FORMS):
+            if form not in list(o.get("forms", FORMS)) + ["ext"] or form not in args.forms:
                 continue
             model = az.ActionModel(B, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, seed=1, dtype=dtype,
                                    **(dict(final_act=az._lib.ACT_RELU) if o.get("relu") else {}))
@@ -70,6 +78,8 @@ def main():
             # (the engine's reason string names a plan's refusal once per form it fell through, run together: each once, "; " between)
             parts = [p.strip(" ;") for p in re.split(r"(?=(?:pool|asynchronous|barrier) step:|AZD_ENGINE_)", why) if p.strip(" ;")]
             why = "; ".join(dict.fromkeys(parts))
+            if form == "ext" and ran == "pool":
+                why = "evaluator stream busy %.2f, searcher waves busy %.2f; workgroups (evaluator, searcher) %s" % (*opt.pool_utilisation(), opt.pool_split())
             print("%-7s %-6s %-9s %-9s %12.0f  %.2e   %s" % (tag, dtype, form, ran, exp / dt, dt / calls, why), flush=True)
             del opt, model
 
