@@ -34,6 +34,8 @@ RAMSEY_U64_NODE_ACTIONS = 512  # AZD_RAMSEY_U64_NODE_ACTIONS: max_slots * (C - 1
 RAMSEY_U64_MAX_ACTIONS = 2304  # E*C of the 64-bit tier (keys of 36 words)
 DENSE_AH_MAX_N = 32     # AZD_DENSE_AH_MAX_N: the Aouchiche-Hansen cost (azd_dense_ah_cost)
 PATH_SET, PATH_SEQUENCE = 0, 1
+ROOT_RULE_THRESHOLD, ROOT_RULE_BEST = 0, 1  # AZD_ROOT_RULE_*
+ROOT_RULES = {"threshold": ROOT_RULE_THRESHOLD, "best": ROOT_RULE_BEST}
 
 
 class AzdError(RuntimeError):
@@ -55,6 +57,10 @@ class EngineConfig(C.Structure):
                 ("first_agent", C.c_uint64), ("flags", C.c_uint32),
                 ("n_colors", C.c_int), ("clique_sizes", C.c_int * 4), ("color_weights", C.c_float * 4),
                 ("path_kind", C.c_int), ("layers", C.c_int), ("max_slots", C.c_int), ("dense_p", C.c_float)]
+
+
+class RootPolicy(C.Structure):  # azd_root_policy
+    _fields_ = [("rule", C.c_int), ("n_color_weights", C.c_int), ("color_weights", C.c_double * 4)]
 
 
 class RamseyArgmin(C.Structure):  # ArgminData<RamseyCountsNoRecolor, TotalCounts<C>>
@@ -161,6 +167,12 @@ def lib():
     sig("azd_ramsey_key_words", C.c_int, C.c_int, C.c_int)
     sig("azd_ramsey_generate_roots", C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
         C.c_int, vp, vp)
+    sig("azd_ramsey_generate_roots_weighted", C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
+        C.c_int, vp, vp, vp)
+    sig("azd_engine_set_root_policy", C.c_int, vp, C.POINTER(RootPolicy))
+    sig("azd_engine_get_root_policy", C.c_int, vp, C.POINTER(RootPolicy))
+    sig("azd_root_policy_check", C.c_int, C.c_int, C.c_int, C.POINTER(RootPolicy))
+    sig("azd_engine_root_policy_report", C.c_int, vp, vp, vp, vp)
     sig("azd_dense_state_dim", C.c_int, C.c_int)
     sig("azd_dense_action_dim", C.c_int, C.c_int)
     sig("azd_dense_key_words", C.c_int, C.c_int)

@@ -74,8 +74,9 @@ void c21_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int
 
 // ---- Ramsey space: seeded stand-in for the drivers' init_state closure (01-r333.rs:84-90,
 // 02-r44.rs:84-90: ColoredCompleteBitsetGraph::generate with uniform colour weights +
-// RamseyCountsNoRecolor::generate).  colour[e] = below(draw 1024 + e, C); permitted edges = first k of
-// the Fisher-Yates shuffle of 0..E-1 (draws 64 + j).
+// RamseyCountsNoRecolor::generate).  colour[e] = below(draw 1024 + e, C), or with colour weights (05-r45.rs:84-90) the
+// number of thresholds the draw's high word reaches (c21_host.h); permitted edges = first k of the Fisher-Yates shuffle
+// of 0..E-1 (draws 64 + j).
 int ramsey_edges(int n) { return n * (n - 1) / 2; }
 int ramsey_state_dim(int n, int c) { return ramsey_edges(n) * (2 * c + 1); }
 int ramsey_action_dim(int n, int c) { return ramsey_edges(n) * c; }
@@ -93,21 +94,60 @@ void shuffle_mask(uint64_t seed, uint64_t domain, uint64_t agent, int universe, 
         mask[perm[(size_t)j] >> 6] |= 1ull << (perm[(size_t)j] & 63);
     }
 }
-void ramsey_fresh_root(uint64_t seed, uint64_t domain, uint64_t agent, int n, int c, int k, uint8_t *colors,
-                       uint64_t *permitted) {
+const char *ramsey_check_color_weights(const double *w, int c) {
+    if (!w) return "color_weights: null";
+    for (int i = 0; i < c; ++i)
+        if (!std::isfinite(w[i]) || !(w[i] > 0.0)) return "color_weights: every weight must be finite and positive";
+    return nullptr;
+}
+void ramsey_color_thresholds(const double *w, int c, uint64_t *thr) {
+    double cum[4] = {0.0, 0.0, 0.0, 0.0}, run = 0.0;
+    for (int i = 0; i < c; ++i) {
+        run = run + w[i];
+        cum[i] = run;
+    }
+    const double W = cum[c - 1];
+    for (int i = 0; i < RAMSEY_COLOR_THRESHOLDS; ++i) {
+        thr[i] = 1ull << 32;
+        if (i < c - 1) {
+            const double t = std::ceil((cum[i] / W) * 4294967296.0);
+            thr[i] = t >= 4294967296.0 ? (1ull << 32) : (uint64_t)t;
+        }
+    }
+}
+uint32_t ramsey_weighted_color(uint64_t r, int c, const uint64_t *thr) {
+    const uint64_t hi = r >> 32;
+    uint32_t col = 0;
+    for (int i = 0; i < c - 1; ++i) col += hi >= thr[i] ? 1u : 0u;
+    return col;
+}
+// thr: the colour thresholds (ramsey_color_thresholds), or nullptr for uniform colours
+static void ramsey_fresh_root_thr(uint64_t seed, uint64_t domain, uint64_t agent, int n, int c, int k, const uint64_t *thr,
+                                  uint8_t *colors, uint64_t *permitted) {
     const int E = ramsey_edges(n);
-    for (int e = 0; e < E; ++e) colors[e] = (uint8_t)draw_below(stream_key(seed, domain, agent, 1024 + (uint64_t)e), (uint32_t)c);
+    for (int e = 0; e < E; ++e) {
+        const uint64_t r = stream_key(seed, domain, agent, 1024 + (uint64_t)e);
+        colors[e] = (uint8_t)(thr ? ramsey_weighted_color(r, c, thr) : draw_below(r, (uint32_t)c));
+    }
     shuffle_mask(seed, domain, agent, E, ramsey_key_words(n, c), k, permitted);
 }
-void ramsey_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int c, int kmin,
-                           int kmax, uint8_t *colors, uint64_t *permitted) {
+void ramsey_fresh_root(uint64_t seed, uint64_t domain, uint64_t agent, int n, int c, int k, uint8_t *colors,
+                       uint64_t *permitted) {
+    ramsey_fresh_root_thr(seed, domain, agent, n, c, k, nullptr, colors, permitted);
+}
+void ramsey_generate_roots_weighted(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int c, int kmin,
+                                    int kmax, const uint64_t *thr, uint8_t *colors, uint64_t *permitted) {
     const int E = ramsey_edges(n), KW = ramsey_key_words(n, c);
     const uint64_t domain = DOMAIN_ROOT ^ (epoch << 32);
     for (int i = 0; i < count; ++i) {
         uint64_t agent = first_agent + (uint64_t)i;
         int k = kmin + (int)draw_below(stream_key(seed, domain, agent, 0), (uint32_t)(kmax - kmin + 1));
-        ramsey_fresh_root(seed, domain, agent, n, c, k, colors + (size_t)i * E, permitted + (size_t)i * KW);
+        ramsey_fresh_root_thr(seed, domain, agent, n, c, k, thr, colors + (size_t)i * E, permitted + (size_t)i * KW);
     }
+}
+void ramsey_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int c, int kmin,
+                           int kmax, uint8_t *colors, uint64_t *permitted) {
+    ramsey_generate_roots_weighted(seed, epoch, first_agent, count, n, c, kmin, kmax, nullptr, colors, permitted);
 }
 
 // ---- dense-graph space: seeded stand-in for ConnectedBitsetGraph::generate(p) (connected_bitset_graph/mod.rs:84-97:

@@ -34,6 +34,17 @@ void ramsey_fresh_root(uint64_t seed, uint64_t domain, uint64_t agent, int n, in
                        uint64_t *permitted);
 void ramsey_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int c, int kmin,
                            int kmax, uint8_t *colors, uint64_t *permitted);
+// Weighted edge colours (05-r45.rs:84-90: WeightedIndex over the colour probabilities), integer-only once the thresholds exist:
+//   cum_c = cum_{c-1} + w_c (f64, in colour order), W = cum_{C-1}, T_c = min(2^32, ceil((cum_c / W) * 2^32)) for c < C - 1;
+//   colour of a draw r = #{ c < C - 1 : (r >> 32) >= T_c }.  Equal weights give draw_below(r, C) for C = 2, 3, 4.
+// nullptr when the weights are acceptable (finite and positive), else what is wrong with them.
+constexpr int RAMSEY_COLOR_THRESHOLDS = 3; // C - 1 at most
+const char *ramsey_check_color_weights(const double *w, int c);
+void ramsey_color_thresholds(const double *w, int c, uint64_t *thr /* [RAMSEY_COLOR_THRESHOLDS], 2^32 beyond C - 1 */);
+uint32_t ramsey_weighted_color(uint64_t r, int c, const uint64_t *thr);
+// thr = nullptr: ramsey_generate_roots
+void ramsey_generate_roots_weighted(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int c, int kmin,
+                                    int kmax, const uint64_t *thr, uint8_t *colors, uint64_t *permitted);
 
 // dense-graph space (space_dense.inc; oracle/dense_graph.inc): E = N(N-1)/2 slots, ACTION = 2E (AddOrDeleteEdge,
 // bitset_graph/space/action.rs:10-27), STATE = 3E + 1 (= E + ACTION + 1, 05-ah.rs:39-40)

@@ -264,6 +264,13 @@ struct azd_engine {
     int ramsey_slots = 0;             // Ramsey: the most permitted edges a root may bring (max_slots; else MAX_NODE_ACTIONS / (C - 1))
     int dense_slots = 0;              // 64 * a.KW: the most modifiable slots a root may bring
     uint64_t *d_stage_slots = nullptr; // device root policy: the slot masks it drew, [B][(E + 63) / 64] (dense-graph space; else d_stage_perm)
+    // device root policy (azd_engine_set_root_policy): the policy as set, as k_modify_roots takes it, and what its last launch
+    // reported per tree ([B][3] on the device; read back by the calls that launch it)
+    azd_root_policy root_policy{AZD_ROOT_RULE_THRESHOLD, 0, {0.0, 0.0, 0.0, 0.0}};
+    azd::RootPolicyArgs root_args{};
+    uint32_t *d_root_report = nullptr;
+    uint32_t *root_report = nullptr; // pinned [B][3]
+    bool root_report_valid = false;
     std::vector<uint64_t> dense_packed;
     std::vector<uint64_t> ramsey_perm_pad; // a wide Ramsey engine's roots: permitted masks padded to the device's a.KW words
     // pool step (agents multiplexed over searcher waves, evaluator workgroups on CUs of their own)
@@ -607,12 +614,25 @@ int azd_device_count(void) {
 int azd_ramsey_state_dim(int n, int n_colors) { return azd::ramsey_state_dim(n, n_colors); }
 int azd_ramsey_action_dim(int n, int n_colors) { return azd::ramsey_action_dim(n, n_colors); }
 int azd_ramsey_key_words(int n, int n_colors) { return azd::ramsey_key_words(n, n_colors); }
-int azd_ramsey_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int n_colors, int kmin,
-                              int kmax, uint8_t *colors, uint64_t *permitted) {
+int azd_ramsey_generate_roots_weighted(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int n_colors, int kmin,
+                                       int kmax, const double *color_weights, uint8_t *colors, uint64_t *permitted) {
     if (!colors || !permitted || count < 0 || n < 3 || n > AZD_RAMSEY_U64_MAX_N || n_colors < 2 || n_colors > 4) return AZD_ERR_INVALID_ARGUMENT;
     if (kmin < 0 || kmax < kmin || kmax > azd::ramsey_edges(n)) return AZD_ERR_INVALID_ARGUMENT;
-    azd::ramsey_generate_roots(seed, epoch, first_agent, count, n, n_colors, kmin, kmax, colors, permitted);
+    uint64_t thr[azd::RAMSEY_COLOR_THRESHOLDS];
+    if (color_weights) {
+        if (const char *why = azd::ramsey_check_color_weights(color_weights, n_colors)) {
+            azd::g_last_error = why;
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+        azd::ramsey_color_thresholds(color_weights, n_colors, thr);
+    }
+    azd::ramsey_generate_roots_weighted(seed, epoch, first_agent, count, n, n_colors, kmin, kmax, color_weights ? thr : nullptr, colors,
+                                        permitted);
     return AZD_OK;
+}
+int azd_ramsey_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int n_colors, int kmin,
+                              int kmax, uint8_t *colors, uint64_t *permitted) {
+    return azd_ramsey_generate_roots_weighted(seed, epoch, first_agent, count, n, n_colors, kmin, kmax, nullptr, colors, permitted);
 }
 int azd_dense_state_dim(int n) { return azd::dense_state_dim(n); }
 int azd_dense_action_dim(int n) { return azd::dense_action_dim(n); }
@@ -1090,8 +1110,11 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     TRY(e->alloc(&e->d_stage_parents, B * (size_t)(dense ? 8 * a.n : ramsey ? a.E : a.n)));
     TRY(e->alloc(&e->d_stage_perm, B * (size_t)(dense ? 17 * a.KW : a.KW)));
     if (!dense) e->d_stage_slots = e->d_stage_perm; // (SpaceOps::modify_roots)
+    TRY(e->alloc(&e->d_root_report, B * 3));
+    e->root_args.report = e->d_root_report;
     {
         hipError_t he = hipHostMalloc((void **)&e->h_status, sizeof(azd::StatusRec));
+        if (he == hipSuccess) he = hipHostMalloc((void **)&e->root_report, B * 3 * sizeof(uint32_t));
         if (he == hipSuccess) he = hipHostMalloc((void **)&e->h_argmin, sizeof(azd::ArgminRec));
         if (he != hipSuccess) {
             st = azd::hip_fail(he, "hipHostMalloc");
@@ -1126,6 +1149,7 @@ int azd_engine_destroy(azd_engine *e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (void *p : e->allocs) (void)hipFree(p);
     if (e->h_status) (void)hipHostFree(e->h_status);
+    if (e->root_report) (void)hipHostFree(e->root_report);
     if (e->h_argmin) (void)hipHostFree(e->h_argmin);
     if (e->h_pargs) (void)hipHostFree(e->h_pargs);
     if (e->h_win_log) (void)hipHostFree(e->h_win_log);
@@ -2459,6 +2483,19 @@ int azd_engine_par_reset_trees(azd_engine *e, const uint8_t *parents, const uint
     return reset_finish(e);
 }
 
+// the report of the policy launch the stream has completed: an empty kept set (k_modify_roots left that tree's root where it was)
+static int root_report_check(azd_engine *e) {
+    e->root_report_valid = true;
+    for (int t = 0; t < e->a.B; ++t)
+        if (e->root_report[(size_t)t * 3] != (uint32_t)azd::ROOT_BRANCH_FRESH && e->root_report[(size_t)t * 3 + 2] == 0) {
+            char buf[128];
+            snprintf(buf, sizeof(buf), "root policy: tree %d keeps no node (the reference's unwrap() on None)", t);
+            azd::g_last_error = buf;
+            return AZD_ERR_UNREACHABLE;
+        }
+    return AZD_OK;
+}
+
 // par_reset_trees with the c21 driver's modify_root policy (04-c21-tree.rs:172-206) evaluated on the
 // device: no host round trip at the epoch boundary.
 static int c21_policy_args_ok(azd_engine *e, int kmin, int kmax) {
@@ -2494,14 +2531,20 @@ int azd_engine_par_reset_trees_c21(azd_engine *e, uint64_t seed, uint64_t epoch,
     if (!e->ev) return AZD_ERR_NO_EVALUATOR;
     AZD_ENTER(e);
     const azd::Arenas &a = e->a;
-    e->ops->modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->stream);
+    e->root_report_valid = false;
+    e->ops->modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->root_args,
+                         e->stream);
     AZD_HIP(hipMemsetAsync(&a.status->failed, 0, sizeof(unsigned long long), e->stream));
     e->ops->init_roots(a, e->d_stage_parents, e->d_stage_perm, e->stream);
     AZD_HIP(hipMemsetAsync(a.h_theta, 0, (size_t)a.B * a.A * 4, e->stream));
     AZD_HIP(hipGetLastError());
     st = run_evaluator(e);
     if (st) return st;
-    return reset_finish(e);
+    e->ops->add_actions(e->a, 1, e->stream); // reset_finish, with the policy's report read back under the same synchronisation
+    AZD_HIP(hipMemcpyAsync(e->root_report, e->d_root_report, (size_t)e->a.B * 3 * 4, hipMemcpyDeviceToHost, e->stream));
+    st = sync_status(e);
+    if (st) return st;
+    return root_report_check(e);
 }
 int azd_c21_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int kmin, int kmax, uint8_t *parents_out,
                              uint64_t *permitted_out) {
@@ -2510,7 +2553,10 @@ int azd_c21_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int k
     if (!parents_out || !permitted_out) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ENTER(e);
     const azd::Arenas &a = e->a;
-    e->ops->modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->stream);
+    e->root_report_valid = false;
+    e->ops->modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->root_args,
+                         e->stream);
+    AZD_HIP(hipMemcpyAsync(e->root_report, e->d_root_report, (size_t)e->a.B * 3 * 4, hipMemcpyDeviceToHost, e->stream));
     if (a.space == azd::SPACE_DENSE) { // roots_out: neighbourhoods (8 n bytes per root); permitted_out: slot masks in kw_host words per root
         const int ow = (a.E + 63) / 64;
         std::vector<uint64_t> sl((size_t)a.B * ow);
@@ -2520,7 +2566,7 @@ int azd_c21_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int k
         AZD_HIP(hipGetLastError());
         memset(permitted_out, 0, (size_t)a.B * e->kw_host * 8);
         for (int i = 0; i < a.B; ++i) memcpy(permitted_out + (size_t)i * e->kw_host, &sl[(size_t)i * ow], (size_t)ow * 8);
-        return AZD_OK;
+        return root_report_check(e);
     }
     AZD_HIP(hipMemcpyAsync(parents_out, e->d_stage_parents, (size_t)a.B * (a.space == azd::SPACE_RAMSEY ? a.E : a.n), hipMemcpyDeviceToHost, e->stream));
     if (e->ramsey_wide()) { // device masks are a.KW words, the caller's kw_host
@@ -2531,6 +2577,61 @@ int azd_c21_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int k
     } else AZD_HIP(hipMemcpyAsync(permitted_out, e->d_stage_perm, (size_t)a.B * a.KW * 8, hipMemcpyDeviceToHost, e->stream));
     AZD_HIP(hipStreamSynchronize(e->stream));
     AZD_HIP(hipGetLastError());
+    return root_report_check(e);
+}
+
+// ---- the policy's description (include/azdopt_amd.h: azd_root_policy)
+int azd_root_policy_check(int space_id, int n_colors, const azd_root_policy *p) {
+    if (!p) return AZD_OK; // the defaults
+    if (p->rule != AZD_ROOT_RULE_THRESHOLD && p->rule != AZD_ROOT_RULE_BEST) {
+        azd::g_last_error = "rule: AZD_ROOT_RULE_THRESHOLD or AZD_ROOT_RULE_BEST";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (p->n_color_weights == 0) return AZD_OK;
+    if (space_id != AZD_SPACE_RAMSEY) {
+        azd::g_last_error = "color_weights: only an AZD_SPACE_RAMSEY engine colours its fresh roots";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (p->n_color_weights != n_colors) {
+        azd::g_last_error = "n_color_weights: 0 or the engine's n_colors";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (const char *why = azd::ramsey_check_color_weights(p->color_weights, n_colors)) {
+        azd::g_last_error = why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    return AZD_OK;
+}
+int azd_engine_set_root_policy(azd_engine *e, const azd_root_policy *p) {
+    if (!e) return AZD_ERR_INVALID_ARGUMENT;
+    const int st = azd_root_policy_check(e->a.space, e->a.C, p);
+    if (st) return st;
+    const azd_root_policy defaults{AZD_ROOT_RULE_THRESHOLD, 0, {0.0, 0.0, 0.0, 0.0}};
+    e->root_policy = p ? *p : defaults;
+    for (int c = e->root_policy.n_color_weights; c < 4; ++c) e->root_policy.color_weights[c] = 0.0;
+    e->root_args.rule = e->root_policy.rule;
+    e->root_args.weighted = e->root_policy.n_color_weights != 0;
+    for (int c = 0; c < azd::RAMSEY_COLOR_THRESHOLDS; ++c) e->root_args.color_thr[c] = 1ull << 32;
+    if (e->root_args.weighted) azd::ramsey_color_thresholds(e->root_policy.color_weights, e->a.C, e->root_args.color_thr);
+    return AZD_OK;
+}
+int azd_engine_get_root_policy(const azd_engine *e, azd_root_policy *p) {
+    if (!p) return AZD_ERR_INVALID_ARGUMENT;
+    const azd_root_policy defaults{AZD_ROOT_RULE_THRESHOLD, 0, {0.0, 0.0, 0.0, 0.0}};
+    *p = e ? e->root_policy : defaults;
+    return AZD_OK;
+}
+int azd_engine_root_policy_report(azd_engine *e, uint8_t *branch, uint32_t *node, uint32_t *kept) {
+    if (!e) return AZD_ERR_INVALID_ARGUMENT;
+    if (!e->root_report_valid) {
+        azd::g_last_error = "root policy report: no policy call has completed on this engine";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    for (int t = 0; t < e->a.B; ++t) {
+        if (branch) branch[t] = (uint8_t)e->root_report[(size_t)t * 3];
+        if (node) node[t] = e->root_report[(size_t)t * 3 + 1];
+        if (kept) kept[t] = e->root_report[(size_t)t * 3 + 2];
+    }
     return AZD_OK;
 }
 

@@ -236,6 +236,17 @@ struct Arenas {
     uint32_t *cur_stack; // [B][PATH_STACK]
 };
 
+// What the device root policy (root_policy.inc: k_modify_roots) is told beside the trees: azd_root_policy as the kernel takes it.
+// A kernel argument of that kernel alone -- no field of Arenas, which every search kernel receives.
+constexpr int ROOT_RULE_THRESHOLD = 0, ROOT_RULE_BEST = 1; // = AZD_ROOT_RULE_*
+constexpr int ROOT_BRANCH_FRESH = 0, ROOT_BRANCH_STAGNANT = 1, ROOT_BRANCH_IMPROVED = 2;
+struct RootPolicyArgs {
+    int rule;              // which nodes an improved tree keeps: c <= (c_root + 3 c_root*) / 4, or c == c_root*
+    int weighted;          // Ramsey: a fresh root's colours come from color_thr, not from below(r, C)
+    uint64_t color_thr[3]; // T_c of c21_host.h: ramsey_color_thresholds
+    uint32_t *report;      // [B][3]: branch, chosen node (NONE for a fresh root), size of the kept set
+};
+
 // what the persistent step needs to run the evaluator inside the kernel
 struct FusedEval {
     int kind;                // 0 not fusable (external), 1 TrivialModel, 2 hash stream, 3 MLP,

@@ -86,8 +86,8 @@ static void l_observe(const Arenas &a, uint32_t tol, hipStream_t st) {
 }
 template <class SP>
 static void l_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax, uint8_t *d_roots,
-                           uint64_t *d_perm, uint64_t *d_slots, hipStream_t st) {
-    k_modify_roots<SP><<<dim3(a.B), dim3(64), SP::dyn_bytes(a), st>>>(a, seed, epoch, first_agent, kmin, kmax, d_roots, d_perm, d_slots);
+                           uint64_t *d_perm, uint64_t *d_slots, const RootPolicyArgs &rp, hipStream_t st) {
+    k_modify_roots<SP><<<dim3(a.B), dim3(64), SP::dyn_bytes(a), st>>>(a, seed, epoch, first_agent, kmin, kmax, d_roots, d_perm, d_slots, rp);
 }
 template <class SP>
 static void l_argmin_one(const Arenas &a, int agent, uint32_t node, hipStream_t st) {
@@ -107,8 +107,8 @@ static void l_persist(const Arenas &a, const PersistArgs *d_args, const StepLaun
 // Ramsey policies' k_modify_roots comes out a few instructions different.  It stays where the Ramsey units had it: first.)
 #define AZD_PHASE_ENTRIES(D)                                                                                                          \
     static void e_modify_roots(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax,              \
-                               uint8_t *d_roots, uint64_t *d_perm, uint64_t *d_slots, void *stream) {                                 \
-        D(a, l_modify_roots, a, seed, epoch, first_agent, kmin, kmax, d_roots, d_perm, d_slots, (hipStream_t)stream);                 \
+                               uint8_t *d_roots, uint64_t *d_perm, uint64_t *d_slots, const RootPolicyArgs &rp, void *stream) {       \
+        D(a, l_modify_roots, a, seed, epoch, first_agent, kmin, kmax, d_roots, d_perm, d_slots, rp, (hipStream_t)stream);             \
     }                                                                                                                                 \
     static void e_init_roots(const Arenas &a, const uint8_t *d_roots, const uint64_t *d_permitted, void *stream) {                    \
         D(a, l_init_roots, a, d_roots, d_permitted, (hipStream_t)stream);                                                             \

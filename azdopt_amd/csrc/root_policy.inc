@@ -10,6 +10,8 @@
 //                                   path onto the root, k' in k..=kmax
 //   else:               keep nodes with c <= (c_root + 3 c_root*)/4, pick one uniformly, replay,
 //                       k' in kmin..=kmax
+//                       (RootPolicyArgs::rule = ROOT_RULE_BEST: keep nodes with c == c_root* instead -- 05-r45.rs:201,
+//                       03-r3333.rs:191; c_root* is the cost of some node, carried up by a cascade, so the kept set is never empty)
 //   then re-randomise the permitted set (k' of ACTION_DIM for c21, k' of the E edges for Ramsey).
 // "Pick uniformly" = index r = below(draw 0, #kept) into the kept nodes IN KEY ORDER (that is what
 // `n.choose` sees); the r-th key in that order is found by an MSB-first radix select over the
@@ -61,10 +63,28 @@ constexpr int POLICY_SEQ_MAX_NODES = 4096;
 // ([B][slot_words]: the host's `permitted` argument of par_new / par_reset_trees).  `out_perm` is what k_init_roots takes
 // as its `permitted` argument: the same mask for c21 / Ramsey (out_slots == out_perm), the packed rank table for the
 // dense-graph space (SP::finish_root builds it from the new root's graph and slots).
+// A space whose fresh roots depend on the policy (SP::WEIGHTED_ROOTS: the Ramsey colour weights) takes it as a last argument.
+template <class SP, class = void>
+struct SpaceWeightedRoots { static constexpr bool value = false; };
+template <class SP>
+struct SpaceWeightedRoots<SP, decltype((void)SP::WEIGHTED_ROOTS)> { static constexpr bool value = SP::WEIGHTED_ROOTS; };
+
+// what the policy did with tree t (azd_engine_root_policy_report): three words, plain stores of the wave's first lane
+__device__ __forceinline__ void policy_report(const RootPolicyArgs &rp, const int t, const uint32_t branch, const uint32_t node,
+                                              const uint32_t kept) {
+    if (LANE == 0) {
+        uint32_t *o = rp.report + (size_t)t * 3;
+        o[0] = branch;
+        o[1] = node;
+        o[2] = kept;
+    }
+}
+
 template <class SP>
 __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin,
                                                      int kmax, uint8_t *__restrict__ out_parents,
-                                                     uint64_t *__restrict__ out_perm, uint64_t *__restrict__ out_slots) {
+                                                     uint64_t *__restrict__ out_perm, uint64_t *__restrict__ out_slots,
+                                                     const RootPolicyArgs rp) {
     constexpr int KW = SP::KW;
     constexpr int CH = SpaceChunks<SP>::value;
     constexpr int HQ = KW + 1;       // histogram buckets per lane: digits 0 .. 64 KW
@@ -97,24 +117,37 @@ __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, ui
     const int kcur = SP::permitted_count(st);
     if (same && kcur == kmax) { // *state = a freshly generated root with k permitted
         const int k = kmin + (int)below_dev(r1, (uint32_t)(kmax - kmin + 1));
-        SP::fresh_root(a, s, seed, domain, agent, po);
+        if constexpr (SpaceWeightedRoots<SP>::value) SP::fresh_root(a, s, seed, domain, agent, po, rp);
+        else SP::fresh_root(a, s, seed, domain, agent, po);
         shuffle_permitted(seed, domain, agent, U, k, perm_arr, draws, bm, ow, mo);
         SP::finish_root(a, s, t, po, mo, out_perm);
+        policy_report(rp, t, ROOT_BRANCH_FRESH, NONE, 0u);
         return;
     }
     const float three_cs = 3.0f * c_root_star;
     const float thr = (c_root + three_cs) / 4.0f;
+    // the nodes the tree keeps: stagnant c == c_root; improved c <= thr, or under ROOT_RULE_BEST c == c_root*
+    const bool exact = same || rp.rule == ROOT_RULE_BEST;
+    const float c_keep = same ? c_root : c_root_star;
+    auto kept = [&](const float c) { return exact ? (c == c_keep) : (c <= thr); };
     const int k_new = same ? kcur + (int)below_dev(r1, (uint32_t)(kmax - kcur + 1)) : kmin + (int)below_dev(r1, (uint32_t)(kmax - kmin + 1));
     // ---- count the kept nodes
     uint32_t m_local = 0;
     for (uint32_t v = LANE; v < nn; v += 64) {
         const float c = nodes[v].c;
-        m_local += (same ? (c == c_root) : (c <= thr)) ? 1u : 0u;
+        m_local += kept(c) ? 1u : 0u;
     }
     uint32_t m = m_local;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) m += __shfl_xor(m, off, 64);
-    uint32_t r = below_dev(r0, m);
+    // (m == 0 is the reference's unwrap() on None.  It cannot happen -- the root itself has c == c_root, some node c == c_root* --
+    // but no index is drawn from an empty set: the agent is flagged, the root stays where it is, the host call reports it.)
+    if (m == 0 && LANE == 0) {
+        a.flags[t] |= FLAG_UNREACHABLE;
+        atomicAdd(&a.status->failed, 1ull);
+    }
+    uint32_t r = m ? below_dev(r0, m) : 0u;
+    uint32_t chosen = 0; // node id of the chosen key
     // ---- radix select of the r-th kept key in BTreeMap order
     uint64_t prefix[KW], le[KW];
 #pragma unroll
@@ -122,12 +155,13 @@ __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, ui
         prefix[w] = 0;
         le[w] = 0; // elements <= last chosen element (none yet)
     }
-    if (SP::SEQ_POLICY && a.path_kind == PATH_SEQUENCE) {
+    if (m == 0) { // nothing to choose from: the key stays the root's
+    } else if (SP::SEQ_POLICY && a.path_kind == PATH_SEQUENCE) {
         const ArcRec *arcs = a.arcs + (size_t)t * a.arc_cap;
         const PredRec *preds = a.preds + (size_t)t * a.pred_cap;
         for (uint32_t v = LANE; v < nn; v += 64) {
             const float c = nodes[v].c;
-            sub[v] = (same ? (c == c_root) : (c <= thr)) ? 1u : 0u;
+            sub[v] = kept(c) ? 1u : 0u;
         }
         WAVE_SYNC();
         // children have larger indices than their parents: one backward pass accumulates the subtrees
@@ -147,7 +181,7 @@ __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, ui
         uint32_t u = 0, rr = r;
         for (uint32_t guard = 0; guard <= nn; ++guard) {
             const NodeRec ru = nodes[u];
-            if ((same ? (ru.c == c_root) : (ru.c <= thr))) {
+            if (kept(ru.c)) {
                 if (rr == 0) break; // u is the chosen node
                 rr -= 1;
             }
@@ -177,7 +211,8 @@ __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, ui
         }
 #pragma unroll
         for (int w = 0; w < KW; ++w) prefix[w] = keys[(size_t)u * KW + w];
-    } else
+        chosen = u;
+    } else {
     for (int j = 0; j <= 64 * CH + 1; ++j) { // a key holds at most one action per permitted item
         for (int i = LANE; i < HD; i += 64) hist[i] = 0;
         WAVE_SYNC();
@@ -185,7 +220,7 @@ __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, ui
             const uint32_t v = base + (uint32_t)LANE;
             if (v < nn) {
                 const float c = nodes[v].c;
-                bool cand = same ? (c == c_root) : (c <= thr);
+                bool cand = kept(c);
                 uint64_t k[KW];
                 int d = 0;
                 bool found = false;
@@ -240,6 +275,19 @@ __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, ui
         prefix[e >> 6] |= 1ull << (e & 63);
         mask_le<KW>(e, le);
     }
+    // the node that holds the chosen key (keys are unique within a tree), for the report
+    uint32_t found = NONE;
+    for (uint32_t base = 0; base < nn; base += 64) {
+        const uint32_t v = base + (uint32_t)LANE;
+        bool eq = v < nn;
+        if (eq) {
+#pragma unroll
+            for (int w = 0; w < KW; ++w) eq = eq && keys[(size_t)v * KW + w] == prefix[w];
+        }
+        if (eq && v < found) found = v;
+    }
+    chosen = wave_min_u32(found);
+    }
     // ---- p.actions_taken().for_each(|a| space.act(state, &a))   (ascending)
 #pragma unroll
     for (int w = 0; w < KW; ++w) {
@@ -253,4 +301,5 @@ __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, ui
     SP::pack_root(a, s, po);
     shuffle_permitted(seed, domain, agent, U, k_new, perm_arr, draws, bm, ow, mo); // randomize_permitted_actions / _edges
     SP::finish_root(a, s, t, po, mo, out_perm);
+    policy_report(rp, t, same ? ROOT_BRANCH_STAGNANT : ROOT_BRANCH_IMPROVED, chosen, m);
 }

@@ -17,9 +17,9 @@ struct PhaseOps { // a space's phase unit (tree_kernels.hip, ramsey_kernels.hip,
     void (*argmin_log)(const Arenas &a, int n_calls, unsigned long long *log_key, void *stream);
     void (*observe)(const Arenas &a, uint32_t n_obs_tol, void *stream);
     // device root policy.  d_perm: what k_init_roots takes; d_slots: the drawn slot masks of the dense-graph space ((E + 63) / 64
-    // words per root), d_perm again for the other spaces
+    // words per root), d_perm again for the other spaces; rp: the engine's root policy (azd_engine_set_root_policy) and its report
     void (*modify_roots)(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax, uint8_t *d_roots,
-                         uint64_t *d_perm, uint64_t *d_slots, void *stream);
+                         uint64_t *d_perm, uint64_t *d_slots, const RootPolicyArgs &rp, void *stream);
     // one candidate (agent, node) replayed into the argmin records `a` points at; StatusRec untouched (run-ahead window, engine.hip)
     void (*argmin_one)(const Arenas &a, int agent, uint32_t node, void *stream);
     bool (*persist_plan)(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);

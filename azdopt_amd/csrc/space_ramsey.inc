@@ -522,10 +522,22 @@ struct RamseySpaceBase {
     __device__ static __forceinline__ int policy_universe(const Arenas &a) { return a.E; }
     __device__ static __forceinline__ int root_bytes(const Arenas &a) { return a.E; }
     __device__ static __forceinline__ int permitted_count(const St &st) { return mask_count<PW>(st.perm); }
-    // ColoredCompleteBitsetGraph::generate with uniform weights, seeded: colour[e] = below(draw 1024 + e, C)
-    __device__ static __forceinline__ void fresh_root(const Arenas &a, Lds &, uint64_t seed, uint64_t domain, uint64_t agent, uint8_t *po) {
-        for (int e = LANE; e < a.E; e += 64)
-            po[e] = (uint8_t)below_dev(stream_key_dev(seed, domain, agent, 1024 + (uint64_t)e), (uint32_t)a.C);
+    // ColoredCompleteBitsetGraph::generate, seeded: colour[e] = below(draw 1024 + e, C) with uniform weights; with colour weights
+    // (05-r45.rs:84-90; azd_root_policy::color_weights) the number of thresholds the draw's high word reaches (c21_host.h)
+    static constexpr bool WEIGHTED_ROOTS = true; // (root_policy.inc: fresh_root takes the policy)
+    __device__ static __forceinline__ void fresh_root(const Arenas &a, Lds &, uint64_t seed, uint64_t domain, uint64_t agent, uint8_t *po,
+                                                      const RootPolicyArgs &rp) {
+        for (int e = LANE; e < a.E; e += 64) {
+            const uint64_t r = stream_key_dev(seed, domain, agent, 1024 + (uint64_t)e);
+            uint32_t col = below_dev(r, (uint32_t)a.C);
+            if (rp.weighted) {
+                const uint64_t hi = r >> 32;
+                col = 0;
+#pragma unroll
+                for (int c = 0; c < RAMSEY_MAX_C - 1; ++c) col += (c < a.C - 1 && hi >= rp.color_thr[c]) ? 1u : 0u;
+            }
+            po[e] = (uint8_t)col;
+        }
     }
     __device__ static __forceinline__ void pack_root(const Arenas &a, Lds &s, uint8_t *po) {
         for (int e = LANE; e < a.E; e += 64) {

@@ -215,6 +215,39 @@ class NablaOptimizer:
     par_reset_trees_c21 = par_reset_trees_policy
     modify_roots = c21_modify_roots
 
+    def set_root_policy(self, rule="threshold", color_weights=None):
+        """What the device policy (modify_roots, par_reset_trees_policy) does from now on (azd_root_policy).
+        rule: which nodes an improved tree keeps before one is picked -- "threshold", c <= (c_root + 3 c_root*) / 4
+        (02-r44.rs:194-196, 04-c21-tree.rs:196-198: the default), or "best", c == c_root* (05-r45.rs:201, 03-r3333.rs:191).
+        color_weights (Ramsey spaces): the colour probabilities of a fresh root (05-r45.rs:84-90), one per colour; None: uniform."""
+        if rule not in _lib.ROOT_RULES:
+            raise ValueError('rule must be "threshold" or "best"')
+        p = _lib.RootPolicy(_lib.ROOT_RULES[rule], 0)
+        if color_weights is not None:
+            w = [float(x) for x in color_weights]
+            if len(w) > 4:
+                raise ValueError("color_weights: at most four colours")
+            p.n_color_weights = len(w)
+            for i, x in enumerate(w):
+                p.color_weights[i] = x
+        _lib.check(self._L.azd_engine_set_root_policy(self._h, C.byref(p)), "set_root_policy")
+
+    def root_policy(self):
+        """the policy in force: dict(rule="threshold" | "best", color_weights=None | [w_0, ..])"""
+        p = _lib.RootPolicy()
+        _lib.check(self._L.azd_engine_get_root_policy(self._h, C.byref(p)), "root_policy")
+        rule = next(k for k, v in _lib.ROOT_RULES.items() if v == p.rule)
+        return dict(rule=rule, color_weights=list(p.color_weights[:p.n_color_weights]) if p.n_color_weights else None)
+
+    def root_policy_report(self):
+        """What the last policy call did with each tree: dict of numpy arrays [batch] -- branch (0 a fresh root, 1 stagnant: the
+        permitted set grows, 2 improved: jump to a kept node), node (the chosen node's index, 0xFFFFFFFF for a fresh root), kept
+        (the size of the set it was chosen from)."""
+        branch = np.zeros(self.batch, np.uint8)
+        node, kept = np.zeros(self.batch, np.uint32), np.zeros(self.batch, np.uint32)
+        _lib.check(self._L.azd_engine_root_policy_report(self._h, _lib.ptr(branch), _lib.ptr(node), _lib.ptr(kept)), "root_policy_report")
+        return dict(branch=branch, node=node, kept=kept)
+
     def argmin_data(self):
         """optimizer/mod.rs:361"""
         if self.space.SPACE_ID == _lib.SPACE_RAMSEY:

@@ -110,6 +110,15 @@ class EngineShard:
     def reset(self, roots):
         self.opt.par_reset_trees(roots)
 
+    def set_root_policy(self, rule="threshold", color_weights=None):
+        self.opt.set_root_policy(rule, color_weights)
+
+    def root_policy(self):
+        return self.opt.root_policy()
+
+    def root_policy_report(self):
+        return self.opt.root_policy_report()
+
     def argmin(self):
         am = self.opt.argmin_data()
         cost = float(sum(am.cost["clique_counts"])) if "clique_counts" in am.cost else am.cost["lambda_1"] + len(am.cost["matching"])
@@ -206,6 +215,17 @@ class ShardedOptimizer:
 
     def par_reset_trees(self, roots):
         self.shard.reset(roots)
+
+    def set_root_policy(self, rule="threshold", color_weights=None):
+        """NablaOptimizer.set_root_policy on this rank's engine: every rank sets the same policy (no collective)"""
+        self.shard.set_root_policy(rule, color_weights)
+
+    def root_policy(self):
+        return self.shard.root_policy()
+
+    def root_policy_report(self):
+        """this rank's trees (local agent order)"""
+        return self.shard.root_policy_report()
 
     def argmin_data(self):
         """this rank's ArgminData (optimizer/mod.rs:361)"""

@@ -160,16 +160,23 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
         hi = max(1, min(self.E // 2, cap))
         return min(12, hi), hi
 
-    def generate_roots(self, seed, count, first_agent=0, epoch=0, kmin=None, kmax=None):
+    def generate_roots(self, seed, count, first_agent=0, epoch=0, kmin=None, kmax=None, color_weights=None):
         """`init_state` of the drivers with a seeded generator.  Returns packed roots:
-        colors u8 [count, E], permitted edges u64 [count, KEY_WORDS]."""
+        colors u8 [count, E], permitted edges u64 [count, KEY_WORDS].
+        color_weights: the colour probabilities of 05-r45.rs:84-90 (WeightedIndex), one per colour; None: uniform colours."""
         lo, hi = self.default_permitted_range()
         kmin = lo if kmin is None else kmin
         kmax = hi if kmax is None else kmax
         colors = np.zeros((count, self.E), np.uint8)
         permitted = np.zeros((count, self.KEY_WORDS), np.uint64)
-        _lib.check(_lib.lib().azd_ramsey_generate_roots(seed, epoch, first_agent, count, self.n, self.C, kmin, kmax,
-                                                        _lib.ptr(colors), _lib.ptr(permitted)), "azd_ramsey_generate_roots")
+        w = None
+        if color_weights is not None:
+            w = np.ascontiguousarray(color_weights, np.float64)
+            if w.shape != (self.C,):
+                raise ValueError("color_weights: one weight per colour")
+        _lib.check(_lib.lib().azd_ramsey_generate_roots_weighted(seed, epoch, first_agent, count, self.n, self.C, kmin, kmax,
+                                                                 None if w is None else _lib.ptr(w), _lib.ptr(colors),
+                                                                 _lib.ptr(permitted)), "azd_ramsey_generate_roots_weighted")
         return colors, permitted
 
     def action(self, index):

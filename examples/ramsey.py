@@ -16,19 +16,42 @@ DRIVERS = {  # N, SIZES, BATCH, episodes, n_as_tol, num_permitted_edges_range.st
                  tol=([200, 200, 200, 100, 100, 100, 50, 50, 50, 25, 25, 25], 10), tag="01-r333-grad"),   # 01-r333.rs:35-38,61,83,126-130
     "r44": dict(n=17, sizes=[4, 4], batch=512, episodes=3200, kmin=12,
                 tol=([200, 200, 100, 100, 50, 50, 25, 25], 10), tag="01-r333-grad"),                      # 02-r44.rs:35-38,61,83,126-130
-    # 05-r45.rs:35-46,61,83,101-103,129: N 24, [4, 5], every edge may be permitted (10..=E: a wide engine, max_slots = E),
-    # weights [1, P_RED / P_BLUE] with P_RED = 0.4685, lr 3e-4.  The seeded root generator draws colours uniformly: the driver's
-    # P_RED colouring probability (WeightedIndex, :84-90) is NOT reproduced -- it would change the generator's spec, which the
-    # oracle shares.  The driver's roll-out takes a decay (:134) this engine does not have: r44's tolerances stand in.
+    # 05-r45.rs:35-46,58,61,83,101-103,129: N 24, [4, 5], every edge may be permitted (10..=E: a wide engine, max_slots = E),
+    # weights [1, P_RED / P_BLUE] with P_RED = 0.4685, a ReLU head (:58), lr 3e-4.  Roots are coloured by
+    # WeightedIndex([P_RED, P_BLUE]) (:84-90): generate_roots(color_weights=...) at the start, the root policy's color_weights for
+    # the fresh roots of an epoch boundary.  modify_root keeps c == c_root_star (:201): rule="best".  The driver's roll-out takes a
+    # decay (:134) this engine does not have: r44's tolerances stand in.
     "r45": dict(n=24, sizes=[4, 5], batch=128, episodes=3200, kmin=10, kmax="E", weights=[1.0, 0.4685 / (1.0 - 0.4685)], lr=3e-4,
+                final_act=az._lib.ACT_RELU, rule="best", color_weights=[0.4685, 1.0 - 0.4685],
                 tol=([200, 200, 100, 100, 50, 50, 25, 25], 10), tag="01-r333-grad"),
     # 03-r3333.rs:34-63,83-84,98,121-124: N 34, [3,3,3,3], unit weights, uniform root colours, 10..=30 permitted edges, a ReLU head
     # (:57), lr 3e-4, 800 episodes: the engine's 64-bit tier (64-bit neighbourhood words, as the driver's B64).  Its roll-out takes a
-    # decay (:124) this engine does not have: r44's tolerances stand in, as for r45.  The driver's modify_root keeps
-    # c == c_root_star; the engine's root policy is 02-r44's threshold rule.
-    "r3333": dict(n=34, sizes=[3, 3, 3, 3], batch=512, episodes=800, kmin=10, kmax=30, lr=3e-4, final_act=az._lib.ACT_RELU,
+    # decay (:124) this engine does not have: r44's tolerances stand in, as for r45.  modify_root keeps c == c_root_star (:191):
+    # rule="best".
+    "r3333": dict(n=34, sizes=[3, 3, 3, 3], batch=512, episodes=800, kmin=10, kmax=30, lr=3e-4, final_act=az._lib.ACT_RELU, rule="best",
                   tol=([200, 200, 100, 100, 50, 50, 25, 25], 10), tag="01-r333-grad"),
 }
+
+
+def build_optimizer(driver, batch=0, episodes=0, hidden=(512, 1024, 512), seed=0, ext_pool_step=False):
+    """the space, model and optimizer of a driver as its reference sets them up: (opt, model, kmin, kmax, episodes)"""
+    d = DRIVERS[driver]
+    batch = batch or d["batch"]
+    episodes = episodes or d["episodes"]
+    space = az.RamseySpaceNoEdgeRecolor(d["n"], d["sizes"], d.get("weights", [1.0] * len(d["sizes"])))
+    model = az.ActionModel(batch, space.STATE_DIM, space.ACTION_DIM, hidden=list(hidden), lr=d.get("lr", 1e-4), l2=1e-6, seed=seed,
+                           final_act=d.get("final_act", az._lib.ACT_SIGMOID), **(dict(dtype="bf16") if ext_pool_step else {}))
+    kmin, kmax = d["kmin"], space.default_permitted_range()[1]   # ..=(E / 2), capped by what a node holds
+    if d.get("kmax") == "E":
+        kmax = space.E
+    elif d.get("kmax"):
+        kmax = d["kmax"]
+    C = len(d["sizes"])
+    caps = az.tree_capacities(episodes, kmax * (C - 1))  # (limits of the packed records: 65536 nodes, 65535 arcs, 2^20 predictions)
+    roots = space.generate_roots(seed, batch, kmin=kmin, kmax=kmax, color_weights=d.get("color_weights"))
+    opt = az.NablaOptimizer.par_new(space, roots, model, batch, **caps, **(dict(ext_pool_step=True) if ext_pool_step else {}))
+    opt.set_root_policy(rule=d.get("rule", "threshold"), color_weights=d.get("color_weights"))  # r333 / r44: the engine's defaults
+    return opt, model, kmin, kmax, episodes
 
 
 def main():
@@ -46,27 +69,13 @@ def main():
                          "(NablaOptimizer.par_new(..., ext_pool_step=True)); the default stays the engine's own choice of form")
     args = ap.parse_args()
     d = DRIVERS[args.driver]
-    batch = args.batch or d["batch"]
-    episodes = args.episodes or d["episodes"]
-
-    space = az.RamseySpaceNoEdgeRecolor(d["n"], d["sizes"], d.get("weights", [1.0] * len(d["sizes"])))
-    model = az.ActionModel(batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=d.get("lr", 1e-4), l2=1e-6, seed=args.seed,
-                           final_act=d.get("final_act", az._lib.ACT_SIGMOID), **(dict(dtype="bf16") if args.ext_pool_step else {}))
+    opt, model, kmin, kmax, episodes = build_optimizer(args.driver, args.batch, args.episodes, args.hidden, args.seed, args.ext_pool_step)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         writer = sinks.TensorboardWriter(open(os.path.join(args.out, "tfevents-losses"), "wb"))
         writer.write_file_version()
     else:
         writer = sinks.TensorboardWriter.create(d["tag"])
-    kmin, kmax = d["kmin"], space.default_permitted_range()[1]   # ..=(E / 2), capped by what a node holds
-    if d.get("kmax") == "E":
-        kmax = space.E
-    elif d.get("kmax"):
-        kmax = d["kmax"]
-    C = len(d["sizes"])
-    caps = az.tree_capacities(episodes, kmax * (C - 1))  # (limits of the packed records: 65536 nodes, 65535 arcs, 2^20 predictions)
-    opt = az.NablaOptimizer.par_new(space, space.generate_roots(args.seed, batch, kmin=kmin, kmax=kmax), model, batch, **caps,
-                                    **(dict(ext_pool_step=True) if args.ext_pool_step else {}))
 
     def process_argmin(argmin, step):
         print("%s\tTotalCounts(%s)" % (argmin.eval, argmin.cost["clique_counts"]))

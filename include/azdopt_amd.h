@@ -94,6 +94,16 @@ int azd_ramsey_key_words(int n, int n_colors);
  *   permitted [count][KW] u64  bit e set <=> edge position e may still be recoloured */
 int azd_ramsey_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n,
                               int n_colors, int kmin, int kmax, uint8_t *colors, uint64_t *permitted);
+/* The same with colour weights (05-r45.rs:84-90: WeightedIndex([P_RED, P_BLUE])): color_weights[n_colors], finite and
+ * positive; NULL is azd_ramsey_generate_roots.  k and the shuffle take the same draws; only the colour of an edge differs.
+ * Integer-only once the thresholds exist, so host, device and any restatement agree bit for bit:
+ *   cum_c = cum_{c-1} + w_c in f64, in colour order;  W = cum_{C-1};
+ *   T_c = min(2^32, ceil((cum_c / W) * 4294967296.0)) for c < C - 1, a 64-bit integer;
+ *   colour of edge e = #{ c < C - 1 : (r >> 32) >= T_c } with r the edge's draw 1024 + e.
+ * Equal weights give the uniform draw for C = 2, 3, 4. */
+int azd_ramsey_generate_roots_weighted(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n,
+                                       int n_colors, int kmin, int kmax, const double *color_weights, uint8_t *colors,
+                                       uint64_t *permitted);
 
 /* ------------------------------------------------------------------------- */
 /* Space seam: dense graphs (BUILD-DEFINED: the reference has no live         */
@@ -453,6 +463,34 @@ int azd_engine_par_reset_trees_c21(azd_engine *e, uint64_t seed, uint64_t epoch,
 int azd_engine_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int kmin, int kmax,
                                 uint8_t *roots_out, uint64_t *permitted_out);
 int azd_engine_par_reset_trees_policy(azd_engine *e, uint64_t seed, uint64_t epoch, int kmin, int kmax);
+
+/* What the device policy of the four calls above does at the epoch boundary: engine state, set between any two engine calls.
+ *   rule           which nodes an IMPROVED tree (c_root != c_root_star) keeps before one is picked uniformly:
+ *                  THRESHOLD c <= (c_root + 3 c_root_star) / 4, or BEST c == c_root_star.  The stagnant branch, the draws and
+ *                  the shuffle are the same under both.
+ *   color_weights  AZD_SPACE_RAMSEY: the colours of a FRESH root (azd_ramsey_generate_roots_weighted's thresholds over the
+ *                  policy's own draws); n_color_weights = 0: uniform, else = the engine's n_colors.
+ * Refused with AZD_ERR_INVALID_ARGUMENT and an azd_last_error() that names the field: an unknown rule; colour weights on an
+ * engine of another space; n_color_weights other than 0 and n_colors; a weight that is not finite and positive.
+ * p = NULL sets the defaults {THRESHOLD, no weights}, with which every root is what it was before this call existed.
+ * azd_engine_get_root_policy(NULL, p) writes those defaults.  azd_root_policy_check is the check alone, without an engine. */
+#define AZD_ROOT_RULE_THRESHOLD 0 /* 02-r44.rs:194-196, 04-c21-tree.rs:196-198: the default */
+#define AZD_ROOT_RULE_BEST 1      /* 05-r45.rs:201, 03-r3333.rs:191: keep c == c_root_star */
+typedef struct {
+    int rule;
+    int n_color_weights;
+    double color_weights[4];
+} azd_root_policy;
+int azd_engine_set_root_policy(azd_engine *e, const azd_root_policy *p);
+int azd_engine_get_root_policy(const azd_engine *e, azd_root_policy *p);
+int azd_root_policy_check(int space_id, int n_colors, const azd_root_policy *p);
+/* What the last policy evaluation (any of the four calls) did with each tree; [batch] each, any pointer may be NULL:
+ *   branch  0 a fresh root, 1 stagnant (c_root == c_root_star: grow the permitted set), 2 improved (jump to a kept node)
+ *   node    the chosen node's index in the tree it was chosen from (0xFFFFFFFF for a fresh root)
+ *   kept    the size of the set it was chosen from (0 for a fresh root)
+ * AZD_ERR_INVALID_ARGUMENT before any evaluation.  An empty kept set -- the reference's unwrap() on None; it cannot happen,
+ * c_root_star is some node's cost -- makes the policy call itself return AZD_ERR_UNREACHABLE. */
+int azd_engine_root_policy_report(azd_engine *e, uint8_t *branch, uint32_t *node, uint32_t *kept);
 
 /* Split-phase forms of the three calls above, cut at the model call
  * (optimizer/mod.rs:72, :175-176, :348), for an external NablaModel:

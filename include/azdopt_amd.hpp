@@ -109,11 +109,16 @@ public:
     int STATE_DIM() const { return azd_ramsey_state_dim(n_, C()); }   // space.rs:40
     int ACTION_DIM() const { return azd_ramsey_action_dim(n_, C()); } // space.rs:42
     int KEY_WORDS() const { return azd_ramsey_key_words(n_, C()); }
-    Roots generate_roots(uint64_t seed, int count, int kmin, int kmax, uint64_t first_agent = 0, uint64_t epoch = 0) const {
+    // color_weights: the colour probabilities of 05-r45.rs:84-90 (one per colour, any positive scale); empty: uniform colours
+    Roots generate_roots(uint64_t seed, int count, int kmin, int kmax, uint64_t first_agent = 0, uint64_t epoch = 0,
+                         const std::vector<double> &color_weights = {}) const {
+        if (!color_weights.empty() && (int)color_weights.size() != C()) throw Error(AZD_ERR_INVALID_ARGUMENT, "generate_roots: color_weights");
         Roots r;
         r.state.resize((size_t)count * E());
         r.permitted.resize((size_t)count * KEY_WORDS());
-        check(azd_ramsey_generate_roots(seed, epoch, first_agent, count, n_, C(), kmin, kmax, r.state.data(), r.permitted.data()), "generate_roots");
+        check(azd_ramsey_generate_roots_weighted(seed, epoch, first_agent, count, n_, C(), kmin, kmax,
+                                                 color_weights.empty() ? nullptr : color_weights.data(), r.state.data(), r.permitted.data()),
+              "generate_roots");
         return r;
     }
     void configure(azd_engine_config &cfg) const {
@@ -434,6 +439,34 @@ public:
         r.permitted.resize((size_t)batch_ * space_.KEY_WORDS());
         check(azd_engine_modify_roots_dev(h_, seed, epoch, kmin, kmax, r.state.data(), r.permitted.data()), "modify_roots");
         par_reset_trees(r);
+    }
+    // what the device policy does at the epoch boundary (azd_root_policy): the rule an improved tree keeps nodes by
+    // (AZD_ROOT_RULE_THRESHOLD, the default, or AZD_ROOT_RULE_BEST) and, for a Ramsey space, the colour weights of a fresh root
+    void set_root_policy(int rule, const std::vector<double> &color_weights = {}) {
+        azd_root_policy p{};
+        p.rule = rule;
+        if (color_weights.size() > 4) throw Error(AZD_ERR_INVALID_ARGUMENT, "set_root_policy: color_weights");
+        p.n_color_weights = (int)color_weights.size();
+        for (size_t c = 0; c < color_weights.size(); ++c) p.color_weights[c] = color_weights[c];
+        check(azd_engine_set_root_policy(h_, &p), "set_root_policy");
+    }
+    azd_root_policy root_policy() const {
+        azd_root_policy p{};
+        check(azd_engine_get_root_policy(h_, &p), "root_policy");
+        return p;
+    }
+    // per tree, of the last policy call: branch (0 fresh root, 1 stagnant, 2 improved), chosen node, size of the kept set
+    struct RootPolicyReport {
+        std::vector<uint8_t> branch;
+        std::vector<uint32_t> node, kept;
+    };
+    RootPolicyReport root_policy_report() {
+        RootPolicyReport r;
+        r.branch.resize((size_t)batch_);
+        r.node.resize((size_t)batch_);
+        r.kept.resize((size_t)batch_);
+        check(azd_engine_root_policy_report(h_, r.branch.data(), r.node.data(), r.kept.data()), "root_policy_report");
+        return r;
     }
     // optimizer/mod.rs:361
     auto argmin_data() { return argmin_of(space_); }
