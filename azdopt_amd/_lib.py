@@ -24,6 +24,7 @@ ENGINE_POOL_STEP = 8
 ENGINE_DENSE_AH = 32    # AZD_ENGINE_DENSE_AH: the dense-graph space with the Aouchiche-Hansen cost (n <= 32)
 ENGINE_RAMSEY_U64 = 16  # AZD_ENGINE_RAMSEY_U64: the 64-bit Ramsey tier (n <= 64, E*C <= 2304), beside max_slots > 0
 ENGINE_EXT_POOL_STEP = 64  # AZD_ENGINE_EXT_POOL_STEP: Ramsey engines with max_slots > 0: searcher-only pool step, batched GEMMs beside it
+ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STEP only: that form with an fp32 model (gathered fp32 GEMMs)
 SPACE_C21 = 1
 SPACE_RAMSEY = 2
 SPACE_DENSE = 3
@@ -208,6 +209,7 @@ def lib():
     sig("azd_debug_hash_stream_via_evaluators", C.c_int, vp, C.c_int)
     sig("azd_debug_ext_pool_plan", C.c_int, C.POINTER(EngineConfig), i32p, C.POINTER(C.c_size_t))
     sig("azd_debug_mlp_gradients", C.c_int, vp, C.c_int, vp, vp, vp, vp, f32p)
+    sig("azd_debug_write_predictions_gathered", C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp)
     sig("azd_debug_probe_math", C.c_int, C.c_int, vp, vp, C.c_int)
     sig("azd_debug_gemm_bf16", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p)
     sig("azd_debug_probe_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, f32p)

@@ -246,6 +246,8 @@ struct azd_engine {
     uint64_t ext_graph_layout = 0;
     int ext_graph_n = 0;
     bool ext_unsupported = false;     // the evaluator cannot serve gathered rows from device-side lists (asked once)
+    bool ext_f32 = false;             // AZD_ENGINE_EXT_POOL_F32: an fp32-storage evaluator serves the form's rows (write_predictions_gathered_f32)
+    uint64_t ext_unsupported_layout = 0; // ... under that flag: once per evaluator layout (a storage switch is asked again)
     uint32_t *d_ext_rows = nullptr, *d_ext_home = nullptr, *d_ext_n = nullptr; // [EXT_STREAMS][B], [EXT_STREAMS][B], [EXT_STREAMS]
     unsigned long long *d_ext_t0 = nullptr; // [EXT_STREAMS] when the batch in hand was collected (PoolCtl::eval_busy)
     int ext_depth = 2;
@@ -748,6 +750,17 @@ int azd_debug_mlp_gradients(azd_evaluator *ev, int batch, const float *states, c
     AZD_HIP(hipMemcpyAsync(ev->d_w, action_weights, pb, hipMemcpyHostToDevice, ev->own_stream));
     return ev->debug_gradients(batch, ev->d_states, ev->d_obs, ev->d_w, grads_out, loss, ev->own_stream);
 }
+int azd_debug_write_predictions_gathered(azd_evaluator *ev, int max_rows, const uint32_t *rows, int n_rows, const float *states, int n_state_rows,
+                                         float *predictions) {
+    if (!ev || max_rows < 1 || n_rows < 0 || n_rows > max_rows || (n_rows > 0 && !rows) || !states || n_state_rows < 1 || !predictions)
+        return AZD_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n_rows; ++i)
+        if (rows[i] >= (uint32_t)n_state_rows) {
+            azd::g_last_error = "azd_debug_write_predictions_gathered: a row index is not below n_state_rows";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+    return ev->debug_write_predictions_gathered(max_rows, rows, n_rows, states, n_state_rows, predictions);
+}
 int azd_debug_hash_stream_via_evaluators(azd_evaluator *ev, int on) { return ev ? ev->debug_serve_from_pool(on) : AZD_ERR_INVALID_ARGUMENT; }
 int azd_evaluator_set_weight_storage(azd_evaluator *ev, int dtype) { return ev ? ev->set_weight_storage(dtype) : AZD_ERR_INVALID_ARGUMENT; }
 int64_t azd_evaluator_num_params(azd_evaluator *ev) { return ev ? ev->num_params() : 0; }
@@ -856,6 +869,11 @@ static int check_engine_config(const azd_engine_config *cfg) {
             return AZD_ERR_INVALID_ARGUMENT;
         }
     }
+    // ... and its fp32 evaluator: a second flag beside the first, never a form of its own
+    if ((cfg->flags & AZD_ENGINE_EXT_POOL_F32) && !(cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) {
+        azd::g_last_error = "AZD_ENGINE_EXT_POOL_F32 is valid only beside AZD_ENGINE_EXT_POOL_STEP (the searcher-only pool step whose fp32 evaluator it asks for)";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
     return AZD_OK;
 }
 // what the LDS plans read of an engine's arenas, for a Ramsey configuration that check_engine_config has accepted
@@ -924,6 +942,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     }
     e->ops = azd::space_ops(a);
     if (dense || (cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) e->ext = ext_pool_form(a.space, dense_ah, e->ramsey_u64());
+    e->ext_f32 = (cfg->flags & AZD_ENGINE_EXT_POOL_F32) != 0;
     a.S_inner = a.S;
     a.S = a.S_inner * a.layers; // Layered<L, Space>::STATE_DIM (nabla/space/mod.rs:53)
     if (ev && (ev->state_dim != a.S || ev->action_dim != a.A)) {
@@ -1398,6 +1417,13 @@ static int ext_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bool
         ax.S16 = e->ext_s16_pitch;
     }
     const azd::Arenas &a = ax;
+    // AZD_ENGINE_EXT_POOL_F32: the evaluator's graph may read the f32 rows, which the searchers always write (write_rows_direct), so
+    // the form runs without bf16 rows; which of the two gathered forwards is captured is the evaluator's answer (its storage type)
+    const bool f32_rows = e->ext_f32;
+    const char *const r_needs_rows = f32_rows ? "external pool step: needs an evaluator that serves gathered rows (ActionModel: bf16 storage, or fp32 "
+                                                "storage under AZD_ENGINE_EXT_POOL_F32)"
+                                              : xf.r_needs_bf16;
+    if (f32_rows && e->ext_unsupported && e->ext_unsupported_layout != e->ev->layout_version) e->ext_unsupported = false;
     const char *why = "";
     uint32_t dyn_stride = 0;
     size_t dyn_bytes = 0;
@@ -1418,11 +1444,11 @@ static int ext_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bool
     azd::FusedEval fe;
     const bool hashed = e->ev->fused_desc(&fe) && fe.kind == 4; // the test harness' fixed prediction stream, served like a model's rows
     const bool configured = (e->pool_step || !xf.needs_pool_step) && e->persist_enabled;
-    if (!configured || e->pool_failed || e->ext_unsupported || (!a.state_vecs16 && !hashed) ||
+    if (!configured || e->pool_failed || e->ext_unsupported || (!a.state_vecs16 && !hashed && !f32_rows) ||
         n_calls < 1 || !pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) {
         e->step_reason = !configured       ? xf.r_not_configured
                          : e->pool_failed ? xf.r_failed_before
-                         : ((!a.state_vecs16 && !hashed) || e->ext_unsupported) ? xf.r_needs_bf16
+                         : ((!a.state_vecs16 && !hashed && !f32_rows) || e->ext_unsupported) ? r_needs_rows
                                                                                  : why;
         return AZD_OK;
     }
@@ -1503,7 +1529,12 @@ static int ext_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bool
             for (int r = 0; r < rounds && st_g == AZD_OK; ++r) {
                 azd::launch_ext_take(pool, rows, home, cnt, e->d_ext_t0 + x, e->ext_stream[x]);
                 if (hashed) azd::launch_ext_hash_rows(e->d_pargs, rows, cnt, (uint32_t)a.B, a.h_theta, e->ext_stream[x]);
-                else st_g = e->ev->write_predictions_gathered(rows, cnt, a.B, a.state_vecs16, a.S16, a.h_theta, e->ext_stream[x], x * a.B);
+                else {
+                    st_g = a.state_vecs16 ? e->ev->write_predictions_gathered(rows, cnt, a.B, a.state_vecs16, a.S16, a.h_theta, e->ext_stream[x], x * a.B)
+                                          : AZD_ERR_UNSUPPORTED;
+                    if (st_g == AZD_ERR_UNSUPPORTED && f32_rows) // (asked before anything is launched: a refusal leaves the capture empty)
+                        st_g = e->ev->write_predictions_gathered_f32(rows, cnt, a.B, a.state_vecs, a.S, a.h_theta, e->ext_stream[x], x * a.B);
+                }
                 azd::launch_ext_deliver(pool, a, rows, home, cnt, (uint32_t)a.B, e->d_ext_t0 + x, e->ext_stream[x]);
             }
             const hipError_t he = hipStreamEndCapture(e->ext_stream[x], &g);
@@ -1511,7 +1542,8 @@ static int ext_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bool
                 if (g) (void)hipGraphDestroy(g);
                 if (st_g != AZD_ERR_UNSUPPORTED) return st_g;
                 e->ext_unsupported = true;
-                e->step_reason = xf.r_needs_bf16;
+                e->ext_unsupported_layout = e->ev->layout_version;
+                e->step_reason = r_needs_rows;
                 return AZD_OK;
             }
             if (he != hipSuccess) return azd::hip_fail(he, "hipStreamEndCapture");

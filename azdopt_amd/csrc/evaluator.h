@@ -62,6 +62,17 @@ struct azd_evaluator {
                                            int /*pitch16*/, float * /*d_p*/, hipStream_t /*st*/, int /*act_row0*/ = 0) {
         return AZD_ERR_UNSUPPORTED;
     }
+    // The same for an evaluator with fp32 storage: inputs d_s[row], f32 rows of pitch `pitch` elements (the engine's state_vecs).
+    // AZD_ERR_UNSUPPORTED: this evaluator cannot, or its storage is bf16 (write_predictions_gathered serves it then).
+    virtual int write_predictions_gathered_f32(const uint32_t * /*d_rows*/, const uint32_t * /*d_count*/, int /*max_rows*/, const float * /*d_s*/,
+                                               int /*pitch*/, float * /*d_p*/, hipStream_t /*st*/, int /*act_row0*/ = 0) {
+        return AZD_ERR_UNSUPPORTED;
+    }
+    // azd_debug_write_predictions_gathered: the gathered forward of whichever storage the model has, on host arrays
+    virtual int debug_write_predictions_gathered(int /*max_rows*/, const uint32_t * /*rows*/, int /*n_rows*/, const float * /*states*/,
+                                                 int /*n_state_rows*/, float * /*predictions*/) {
+        return AZD_ERR_UNSUPPORTED;
+    }
     // description for the persistent step (evaluator inside the kernel); false = not fusable
     virtual bool fused_desc(azd::FusedEval *) { return false; }
     // write_predictions_dev(batch) launches the same kernels with the same arguments on every call and allocates nothing

@@ -277,6 +277,7 @@ __global__ __launch_bounds__(256, MI == 1 ? 4 : 2) void k_gemm_bf16(const float 
 
 #include "gemm_bf16_glds.inc"
 #include "gemm_bf16_hidden2.inc"
+#include "gemm_f32_gathered.inc"
 
 // ---- bf16 weight storage: w16 = RNE(params) in 16-bit words, params_q = the same values widened back
 // to f32 (what the f32 GEMM path multiplies with, so that it computes what the bf16 MFMA path computes)
@@ -656,6 +657,72 @@ struct MlpEvaluator : azd_evaluator {
         }
         AZD_HIP(hipGetLastError());
         return AZD_OK;
+    }
+
+    // The same for fp32 storage (the searcher-only pool step under AZD_ENGINE_EXT_POOL_F32): inputs d_s[row] (f32, pitch `pitch`),
+    // every layer on k_gemm_f32_gathered through the f32 activation buffers from row act_row0 on -- the sums of forward(quant = false),
+    // bit for bit.  No allocation, no synchronisation: the call is captured into a graph.
+    int write_predictions_gathered_f32(const uint32_t *d_rows, const uint32_t *d_count, int max_rows, const float *d_s, int pitch, float *d_p,
+                                       hipStream_t st, int act_row0) override {
+        if (bf16) return AZD_ERR_UNSUPPORTED; // (the caller takes write_predictions_gathered then)
+        if (!d_s || !d_p || max_rows < 1 || act_row0 < 0 || pitch < dims[0]) return AZD_ERR_INVALID_ARGUMENT;
+        if (act_row0 + max_rows > cap_batch) return AZD_ERR_CAPACITY; // (the engine sizes the evaluator first: ensure_rows)
+        AZD_HIP(hipSetDevice(device));
+        const float *x = d_s;
+        int ldx = pitch;
+        for (int l = 0; l < L; ++l) {
+            const bool last = l == L - 1;
+            const int N = dims[(size_t)l + 1];
+            float *y = last ? d_p : d_act[(size_t)l + 1] + (size_t)act_row0 * N;
+            launch_gemm_f32_gathered(st, x, ldx, d_params + w_off[(size_t)l], dims[(size_t)l], y, N, max_rows, N, dims[(size_t)l], last ? final_act : AZD_ACT_RELU,
+                                     d_params + b_off[(size_t)l], d_count, l == 0 ? d_rows : nullptr, last ? d_rows : nullptr);
+            x = y;
+            ldx = N;
+        }
+        AZD_HIP(hipGetLastError());
+        return AZD_OK;
+    }
+    // azd_debug_write_predictions_gathered: host arrays in, the gathered forward of the storage type in force, predictions back
+    int debug_write_predictions_gathered(int max_rows, const uint32_t *rows, int n_rows, const float *states, int n_state_rows, float *predictions) override {
+        AZD_HIP(hipSetDevice(device));
+        int s = ensure_batch(max_rows);
+        if (s) return s;
+        const size_t sb = (size_t)n_state_rows * dims[0] * 4, pb = (size_t)n_state_rows * dims[(size_t)L] * 4;
+        float *d_s = nullptr, *d_p = nullptr;
+        uint32_t *d_r = nullptr; // [max_rows] the list, then the count
+        uint16_t *d_s16 = nullptr;
+        auto release = [&]() {
+            for (void *p : {(void *)d_s, (void *)d_p, (void *)d_r, (void *)d_s16})
+                if (p) (void)hipFree(p);
+        };
+        const uint32_t count = (uint32_t)n_rows;
+        hipError_t he = hipMalloc(&d_s, sb);
+        if (he == hipSuccess) he = hipMalloc(&d_p, pb);
+        if (he == hipSuccess) he = hipMalloc(&d_r, ((size_t)max_rows + 1) * 4);
+        if (he == hipSuccess) he = hipMemcpy(d_s, states, sb, hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipMemcpy(d_p, predictions, pb, hipMemcpyHostToDevice);
+        if (he == hipSuccess && n_rows > 0) he = hipMemcpy(d_r, rows, (size_t)n_rows * 4, hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipMemcpy(d_r + max_rows, &count, 4, hipMemcpyHostToDevice);
+        if (he == hipSuccess && bf16) { // the rows as the searchers would have written them: RNE, pitch kp[0], zero beyond the state
+            he = hipMalloc(&d_s16, (size_t)n_state_rows * kp[0] * 2);
+            if (he == hipSuccess) {
+                const size_t n = (size_t)n_state_rows * (kp[0] / 4);
+                k_rows_to_bf16<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(d_s, dims[0], n_state_rows, dims[0], d_s16, kp[0]);
+            }
+        }
+        if (he != hipSuccess) {
+            release();
+            return hip_fail(he, "azd_debug_write_predictions_gathered: staging");
+        }
+        s = bf16 ? write_predictions_gathered(d_r, d_r + max_rows, max_rows, d_s16, kp[0], d_p, nullptr, 0)
+                 : write_predictions_gathered_f32(d_r, d_r + max_rows, max_rows, d_s, dims[0], d_p, nullptr, 0);
+        if (s == AZD_OK) {
+            he = hipDeviceSynchronize();
+            if (he == hipSuccess) he = hipMemcpy(predictions, d_p, pb, hipMemcpyDeviceToHost);
+            if (he != hipSuccess) s = hip_fail(he, "azd_debug_write_predictions_gathered");
+        }
+        release();
+        return s;
     }
 
     // dfdx.rs:86-131: the gradient of the weighted loss into d_grads (loss into d_scalars[1]), then the Adam step

@@ -116,6 +116,19 @@ class ActionModel(NablaModel):
                                                       _lib.ptr(g), C.byref(loss)), "azd_debug_mlp_gradients")
         return g, loss.value
 
+    def debug_write_predictions_gathered(self, rows, states, predictions, max_rows=None):
+        """the evaluator of the searcher-only pool step in isolation (azd_debug_write_predictions_gathered): the gathered forward
+        of the model's storage type over the state rows `rows` names; predictions (rows x ACTION, float32, in and out) receives
+        those rows and keeps every other"""
+        states = np.ascontiguousarray(states, np.float32).reshape(-1, self.state_dim)
+        rows = np.ascontiguousarray(rows, np.uint32)
+        assert predictions.dtype == np.float32 and predictions.flags.c_contiguous
+        assert predictions.size == states.shape[0] * self.action_dim
+        _lib.check(_lib.lib().azd_debug_write_predictions_gathered(self._h, states.shape[0] if max_rows is None else max_rows,
+                                                                   _lib.ptr(rows) if rows.size else None, rows.size, _lib.ptr(states),
+                                                                   states.shape[0], _lib.ptr(predictions)),
+                   "azd_debug_write_predictions_gathered")
+
     def set_params(self, p):
         p = np.ascontiguousarray(p, np.float32)
         assert p.size == self.num_params()

@@ -94,11 +94,12 @@ class NablaOptimizer:
 
     def __init__(self, space, model, batch, device=0, first_agent=0, node_capacity=0, arc_capacity=0,
                  prediction_capacity=0, path=ActionSet, persistent=True, async_step=True, pool_step=None,
-                 ext_pool_step=False):
+                 ext_pool_step=False, ext_pool_f32=False):
         """step form: pool_step=None lets the engine choose (pool step from 256 agents, else the asynchronous one),
         True / False force the pool / asynchronous step, async_step=False the lock-step one, persistent=False one
         launch per phase.  ext_pool_step=True (Ramsey spaces with MAX_SLOTS > 0 only, a bf16 ActionModel): the searcher-only pool
-        step with the model's batched GEMMs beside it (ENGINE_EXT_POOL_STEP); step_form() says whether it ran."""
+        step with the model's batched GEMMs beside it (ENGINE_EXT_POOL_STEP); step_form() says whether it ran.  ext_pool_f32=True
+        beside it (ENGINE_EXT_POOL_F32; alone the engine refuses it): that form also with an fp32 ActionModel."""
         if not hasattr(path, "PATH_KIND") or not path.licensed_for(space):
             raise TypeError("path encoding %r is not licensed for this space (space/axioms.rs:12-19)" % (path,))
         self.space, self.model, self.batch, self.first_agent = space, model, batch, first_agent
@@ -108,7 +109,8 @@ class NablaOptimizer:
                                 (0 if persistent else _lib.ENGINE_NO_PERSISTENT_STEP) | (0 if async_step else _lib.ENGINE_BARRIER_STEP)
                                 | (_lib.ENGINE_POOL_STEP if pool_step else 0)
                                 | (_lib.ENGINE_ASYNC_STEP if (pool_step is False and async_step) else 0)
-                                | (_lib.ENGINE_EXT_POOL_STEP if ext_pool_step else 0))
+                                | (_lib.ENGINE_EXT_POOL_STEP if ext_pool_step else 0)
+                                | (_lib.ENGINE_EXT_POOL_F32 if ext_pool_f32 else 0))
         cfg.path_kind = path.PATH_KIND
         cfg.layers = getattr(space, "layers", 1)
         if space.SPACE_ID == _lib.SPACE_DENSE:

@@ -290,13 +290,13 @@ typedef struct azd_engine_config {
 /* AZD_SPACE_RAMSEY with max_slots > 0 only (the 32-bit wide tier, or the 64-bit tier beside AZD_ENGINE_RAMSEY_U64): the
  * searcher-only pool step, the CU-resident form of these engines for a model that does not fit an evaluator workgroup's LDS.
  * Persistent searcher workgroups of eight wavefronts pull agents from the per-XCD ready queues, write each new node's state row
- * to memory (f32, and bf16 beside it) and post a request; on a second stream the host replays a graph of [collect the requests,
- * the model's bf16 GEMMs over the gathered rows, hand the agents back] for as long as the searchers run -- the dense-graph
+ * to memory (f32, and bf16 beside it for a bf16 model) and post a request; on a second stream the host replays a graph of [collect
+ * the requests, the model's GEMMs over the gathered rows, hand the agents back] for as long as the searchers run -- the dense-graph
  * space's form.  Results are bit for bit those of the launch-per-phase form.  Never chosen from the sizes: without the flag every
  * engine, limit, kernel, fallback chain and reason string is what it is without it.  On any other engine (c21, dense-graph,
  * Ramsey with max_slots == 0) and together with AZD_ENGINE_NO_PERSISTENT_STEP azd_engine_create returns
  * AZD_ERR_INVALID_ARGUMENT.  Needs an evaluator that serves gathered bf16 rows: an MLP with AZD_STORAGE_BF16 (or the tests' hash
- * stream); with any other the engine runs what it would have run without the flag and azd_engine_step_form's reason opens with
+ * stream) -- or, beside AZD_ENGINE_EXT_POOL_F32 below, an MLP with AZD_STORAGE_F32; with any other the engine runs what it would have run without the flag and azd_engine_step_form's reason opens with
  * "external pool step:".  When the form runs azd_engine_step_form reports AZD_STEP_POOL with an empty reason and
  * azd_engine_pool_split 0 evaluator workgroups beside the searcher workgroups.
  * Which form where (profiles/r09_ramsey_ext_pool.txt, bf16 storage): on the 64-bit tier this one -- 1.5 times the launch-per-phase
@@ -305,6 +305,17 @@ typedef struct azd_engine_config {
  * agents) and the in-kernel form needs no second stream and no host thread; take this one for a model whose 16 bf16 rows of
  * activations do not fit an evaluator workgroup's LDS, where the in-kernel form falls back to one launch per phase (0.39 M). */
 #define AZD_ENGINE_EXT_POOL_STEP 64u
+/* Beside AZD_ENGINE_EXT_POOL_STEP only (alone: AZD_ERR_INVALID_ARGUMENT from azd_engine_create and azd_debug_ext_pool_plan): the
+ * form also takes an MLP with fp32 storage (AZD_STORAGE_F32, the reference's own models).  The searchers are the same -- they
+ * write the f32 row whatever the model -- and the evaluator's graph runs the layers as gathered fp32 GEMMs on
+ * v_mfma_f32_32x32x2_f32 over those rows: every prediction is the sum azd_evaluator_write_predictions gives the row, bit for bit,
+ * so results are those of the launch-per-phase form.  The LDS plan is that of AZD_ENGINE_EXT_POOL_STEP alone.  With a bf16 model
+ * nothing differs from AZD_ENGINE_EXT_POOL_STEP alone; without this flag an fp32 model under AZD_ENGINE_EXT_POOL_STEP keeps
+ * falling back with the "external pool step: ... bf16" reason.  A storage switch (azd_evaluator_set_weight_storage) re-captures
+ * the evaluator's graph.  Measured (profiles/r10_ramsey_ext_f32.txt, fp32, against the launch-per-phase form on the same box): r3333 at
+ * 512 agents 0.99 against 0.52 M expansions/s, r45 at 256 agents 1.03 against 0.31 M on the wide tier and 0.79 against 0.25 M on the
+ * 64-bit tier. */
+#define AZD_ENGINE_EXT_POOL_F32 128u
 
 /* ArgminData<State, Cost> (az-discrete-opt/src/log.rs:1-11) for the c21 space */
 typedef struct azd_argmin {
@@ -588,6 +599,13 @@ int azd_debug_hash_stream_via_evaluators(azd_evaluator *ev, int on);
  * the bytes of LDS one workgroup takes (of the CU's 160 KB).  Arithmetic on the configuration: no device is touched.
  * AZD_ERR_INVALID_ARGUMENT for a configuration azd_engine_create refuses, or one without the flag. */
 int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes);
+/* The evaluator of the searcher-only pool step in isolation (tests): the MLP's gathered forward of whichever storage type it has
+ * -- fp32: the gathered fp32 GEMMs of AZD_ENGINE_EXT_POOL_F32; bf16: the gathered bf16 GEMMs -- on host arrays.  states:
+ * n_state_rows rows of state_dim floats; rows: n_rows (<= max_rows, the size the launches are made for) indices into them;
+ * predictions: n_state_rows rows of action_dim floats, in and out: row rows[i] receives the prediction of state row rows[i],
+ * every other row is left as it was.  AZD_ERR_UNSUPPORTED for evaluators other than the MLP. */
+int azd_debug_write_predictions_gathered(azd_evaluator *ev, int max_rows, const uint32_t *rows, int n_rows, const float *states,
+                                         int n_state_rows, float *predictions);
 /* The MLP evaluator's training gradient without the optimiser step (tests against a float64 reference): the same launches
  * as azd_evaluator_update_model up to the Adam step, on host rows staged like that call's.  grads_out: num_params floats in
  * the get_params layout; *loss as update_model reports it.  Parameters, Adam moments and the step count are left untouched.

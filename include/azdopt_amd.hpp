@@ -327,7 +327,8 @@ public:
     // optimizer (the reference moves it in; here the engine borrows the evaluator).  Capacities 0 = sized for 800 calls per epoch.
     // `flags`: the step-form options (AZD_ENGINE_POOL_STEP, AZD_ENGINE_ASYNC_STEP, AZD_ENGINE_BARRIER_STEP,
     // AZD_ENGINE_NO_PERSISTENT_STEP, and -- Ramsey spaces with max_slots > 0 and a bf16 model -- AZD_ENGINE_EXT_POOL_STEP, the
-    // searcher-only pool step with the model's batched GEMMs beside it); step_form() says which form ran and why.
+    // searcher-only pool step with the model's batched GEMMs beside it; AZD_ENGINE_EXT_POOL_F32 beside it takes an fp32 model too);
+    // step_form() says which form ran and why.
     static NablaOptimizer par_new(const Space &space, const Roots &roots, NablaModel &model, int batch, int device = 0, uint64_t first_agent = 0,
                                   uint32_t flags = 0, int node_capacity = 0, int arc_capacity = 0, int prediction_capacity = 0, int layers = 0,
                                   int path_kind = AZD_PATH_SET) {

@@ -6,7 +6,7 @@ asked for with the engine's flags; the line says which form ran and, when anothe
 permitted edges, 512-1024-512 model with a ReLU head, 512 agents) and r45 under the flag beside r45 on the 32-bit tier (what the
 wider word costs).
 The form 'ext' is the searcher-only pool step (par_new(..., ext_pool_step=True): bf16 storage only; with fp32 the line shows what ran
-instead); its line ends with the busy shares of the evaluator's stream and of the searching waves (azd_engine_pool_utilisation).
+instead; 'ext_f32' is the same form with its fp32 evaluator, ext_pool_f32=True beside it: run it with --dtypes f32); its line ends with the busy shares of the evaluator's stream and of the searching waves (azd_engine_pool_utilisation).
 --forms picks the forms to time (a library built before 'ext' existed, chosen with AZD_LIB, is timed with --forms per_call pool).
 
     python tools/time_ramsey_wide.py [--preset wide|u64] [--batch 256] [--calls 60] [--warmup 10] [--forms ext per_call] [--shapes r45]"""
@@ -21,7 +21,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import azdopt_amd as az  # noqa: E402
 
 FORMS = {"pool": dict(pool_step=True), "async": dict(async_step=True, pool_step=False),
-         "barrier": dict(async_step=False, pool_step=False), "per_call": dict(persistent=False), "ext": dict(ext_pool_step=True)}
+         "barrier": dict(async_step=False, pool_step=False), "per_call": dict(persistent=False), "ext": dict(ext_pool_step=True),
+         "ext_f32": dict(ext_pool_step=True, ext_pool_f32=True)}
 TOL = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
 SHAPES = [("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "f32"), ("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "bf16"),
           ("n32c2", 32, [4, 4], [1.0, 1.0], "f32")]
@@ -62,7 +63,7 @@ def main():
         kmax = o.get("kmax", space.E)
         roots = space.generate_roots(0, B, kmin=10, kmax=kmax)
         for form, kw in FORMS.items():
-            if form not in list(o.get("forms", FORMS)) + ["ext"] or form not in args.forms:
+            if form not in list(o.get("forms", FORMS)) + ["ext", "ext_f32"] or form not in args.forms:
                 continue
             model = az.ActionModel(B, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, seed=1, dtype=dtype,
                                    **(dict(final_act=az._lib.ACT_RELU) if o.get("relu") else {}))
@@ -78,7 +79,7 @@ def main():
             # (the engine's reason string names a plan's refusal once per form it fell through, run together: each once, "; " between)
             parts = [p.strip(" ;") for p in re.split(r"(?=(?:pool|asynchronous|barrier) step:|AZD_ENGINE_)", why) if p.strip(" ;")]
             why = "; ".join(dict.fromkeys(parts))
-            if form == "ext" and ran == "pool":
+            if form in ("ext", "ext_f32") and ran == "pool":
                 why = "evaluator stream busy %.2f, searcher waves busy %.2f; workgroups (evaluator, searcher) %s" % (*opt.pool_utilisation(), opt.pool_split())
             print("%-7s %-6s %-9s %-9s %12.0f  %.2e   %s" % (tag, dtype, form, ran, exp / dt, dt / calls, why), flush=True)
             del opt, model
