@@ -575,7 +575,7 @@ int azd_engine_step_form(azd_engine *e, int *form, const char **reason);
  * column tiles of every layer in LDS for the whole launch (no weight stream per batch; the batch's activations travel between the
  * layers through device memory), `groups` of them, a workgroup's waves in slots of `waves_per_slot`.  0 members: the classic form
  * (one workgroup per batch, weights streamed from L2).  The engine forms groups where a classic batch is long (fp32 weights beyond
- * 2.5 MB, at most 2048 agents: BASELINE configs[0], the reference's 304-512-1024-512-152); AZD_POOL_EVAL_GROUP = 0 / g overrides.
+ * 2.5 MB, at most 1536 agents: BASELINE configs[0], the reference's 304-512-1024-512-152); AZD_POOL_EVAL_GROUP = 0 / g overrides.
  * Same rows to the bit either way. */
 int azd_engine_pool_groups(azd_engine *e, int *members, int *groups, int *waves_per_slot);
 /* Pool step (product build): for every agent, when it was through with the calls of the LAST pool launch, in 100 MHz ticks from the
