@@ -24,6 +24,7 @@ ENGINE_POOL_STEP = 8
 ENGINE_DENSE_AH = 32    # AZD_ENGINE_DENSE_AH: the dense-graph space with the Aouchiche-Hansen cost (n <= 32)
 ENGINE_RAMSEY_U64 = 16  # AZD_ENGINE_RAMSEY_U64: the 64-bit Ramsey tier (n <= 64, E*C <= 2304), beside max_slots > 0
 ENGINE_EXT_POOL_STEP = 64  # AZD_ENGINE_EXT_POOL_STEP: Ramsey engines with max_slots > 0: searcher-only pool step, batched GEMMs beside it
+ENGINE_DENSE_AH_WIDE = 256  # AZD_ENGINE_DENSE_AH_WIDE: beside ENGINE_DENSE_AH only: the Aouchiche-Hansen cost up to n = 64 (64-row kernels)
 ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STEP only: that form with an fp32 model (gathered fp32 GEMMs)
 SPACE_C21 = 1
 SPACE_RAMSEY = 2
@@ -34,6 +35,7 @@ RAMSEY_U64_MAX_N = 64   # AZD_RAMSEY_U64_MAX_N: the 64-bit tier (ENGINE_RAMSEY_U
 RAMSEY_U64_NODE_ACTIONS = 512  # AZD_RAMSEY_U64_NODE_ACTIONS: max_slots * (C - 1) of the 64-bit tier
 RAMSEY_U64_MAX_ACTIONS = 2304  # E*C of the 64-bit tier (keys of 36 words)
 DENSE_AH_MAX_N = 32     # AZD_DENSE_AH_MAX_N: the Aouchiche-Hansen cost (azd_dense_ah_cost)
+DENSE_AH_WIDE_MAX_N = 64  # AZD_DENSE_AH_WIDE_MAX_N: its 64-row form (azd_dense_ah_cost_wide, ENGINE_DENSE_AH_WIDE)
 PATH_SET, PATH_SEQUENCE = 0, 1
 ROOT_RULE_THRESHOLD, ROOT_RULE_BEST = 0, 1  # AZD_ROOT_RULE_*
 ROOT_RULES = {"threshold": ROOT_RULE_THRESHOLD, "best": ROOT_RULE_BEST}
@@ -86,6 +88,12 @@ class DenseAhCost(C.Structure):  # azd_dense_ah_cost_t: the Aouchiche-Hansen cos
 
 class DenseAhArgmin(C.Structure):  # azd_dense_ah_argmin: ArgminData of a dense engine with the Aouchiche-Hansen cost
     _fields_ = [("adj", C.c_uint64 * 32), ("permitted", C.c_uint64 * 8), ("proximity", C.c_double), ("eigenvalue", C.c_double),
+                ("diameter", C.c_int32), ("k", C.c_int32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32),
+                ("node", C.c_uint32)]
+
+
+class DenseAhWideArgmin(C.Structure):  # azd_dense_ah_wide_argmin: the same of an engine with ENGINE_DENSE_AH_WIDE (n <= 64, E <= 2016)
+    _fields_ = [("adj", C.c_uint64 * 64), ("permitted", C.c_uint64 * 32), ("proximity", C.c_double), ("eigenvalue", C.c_double),
                 ("diameter", C.c_int32), ("k", C.c_int32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32),
                 ("node", C.c_uint32)]
 
@@ -217,6 +225,9 @@ def lib():
     sig("azd_engine_dense_ah_argmin_data", C.c_int, vp, C.POINTER(DenseAhArgmin))
     sig("azd_engine_dense_ah_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseAhCost))
     sig("azd_debug_probe_ah_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, f32p)
+    sig("azd_dense_ah_cost_wide", C.c_int, vp, C.c_int, C.POINTER(DenseAhCost))
+    sig("azd_engine_dense_ah_wide_argmin_data", C.c_int, vp, C.POINTER(DenseAhWideArgmin))
+    sig("azd_debug_probe_ah_cost_wide", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, f32p)
     sig("azd_debug_probe_math_f64", C.c_int, C.c_int, vp, vp, C.c_int)
     _LIB = L
     return L

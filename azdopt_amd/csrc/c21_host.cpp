@@ -205,10 +205,10 @@ void dense_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, i
 // dense_ah_cost.inc runs it: `lane` loops stand for the lanes, tree64 for the xor-butterfly.  One IEEE operation at a time
 // (this file is built with -ffp-contract=off); tests/dense_ah_ref.py is the same sequence in Python.
 float dense_ah_eval_slope(int n) { return 1.0f / (float)(2 * n + 2); }
-const char *dense_ah_check_graph(const uint64_t *adj, int n) {
+static const char *ah_check_graph(const uint64_t *adj, int n, int max_n, const char *bad_n) {
     if (!adj) return "adj: null";
-    if (n < 4 || n > DENSE_AH_MAX_N) return "n: the Aouchiche-Hansen cost needs 4 <= n <= 32 (AZD_DENSE_AH_MAX_N)";
-    const uint64_t all = (1ull << n) - 1ull;
+    if (n < 4 || n > max_n) return bad_n;
+    const uint64_t all = ~0ull >> (64 - n); // (no shift by 64 at n = 64)
     for (int v = 0; v < n; ++v) {
         if (adj[v] & ~all) return "adj: a neighbour beyond n";
         if ((adj[v] >> v) & 1ull) return "adj: a loop";
@@ -217,6 +217,12 @@ const char *dense_ah_check_graph(const uint64_t *adj, int n) {
     }
     if (!dense_connected(adj, n)) return "adj: the graph is not connected";
     return nullptr;
+}
+const char *dense_ah_check_graph(const uint64_t *adj, int n) {
+    return ah_check_graph(adj, n, DENSE_AH_MAX_N, "n: the Aouchiche-Hansen cost needs 4 <= n <= 32 (AZD_DENSE_AH_MAX_N)");
+}
+const char *dense_ah_check_graph_wide(const uint64_t *adj, int n) {
+    return ah_check_graph(adj, n, DENSE_AH_WIDE_MAX_N, "n: the wide Aouchiche-Hansen cost needs 4 <= n <= 64 (AZD_DENSE_AH_WIDE_MAX_N)");
 }
 static double ah_tree64(const double *v) { // balanced binary tree over 64 slots, adjacent pairs first
     double t[64];
@@ -239,7 +245,8 @@ static int ah_sturm(const double *diag, const double *sub2, int n, double x) {
 }
 void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
     constexpr int P = DENSE_AH_STRIDE;
-    std::vector<double> Am((size_t)DENSE_AH_MAX_N * P, 0.0);
+    constexpr int MAX_N = DENSE_AH_WIDE_MAX_N; // (the values do not depend on the pitch or on the rows beyond n)
+    std::vector<double> Am((size_t)MAX_N * P, 0.0);
     double *A = Am.data();
     int min_t = 0x7FFFFFFF, diam = 0;
     for (int u = 0; u < n; ++u) { // BFS from u
@@ -262,8 +269,8 @@ void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
     const double prox = (double)min_t / (double)(n - 1);
     const int q23 = (2 * diam) / 3, k = q23 >= 1 ? q23 - 1 : n - 1;
     // Householder reduction: step i clears column i below row i + 1
-    double diag[DENSE_AH_MAX_N], sub[DENSE_AH_MAX_N], v[64], p[64], q[64], tmp[64];
-    for (int i = 0; i < DENSE_AH_MAX_N; ++i) diag[i] = sub[i] = 0.0;
+    double diag[MAX_N], sub[MAX_N], v[64], p[64], q[64], tmp[64];
+    for (int i = 0; i < MAX_N; ++i) diag[i] = sub[i] = 0.0;
     for (int i = 0; i + 2 < n; ++i) {
         for (int lane = 0; lane < 64; ++lane) {
             v[lane] = lane > i && lane < n ? A[lane * P + i] : 0.0;
@@ -300,7 +307,7 @@ void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
     diag[n - 1] = A[(n - 1) * P + (n - 1)];
     // multisection for ascending index j = n - 1 - k
     const int j = n - 1 - k;
-    double sub2[DENSE_AH_MAX_N], R = 0.0;
+    double sub2[MAX_N], R = 0.0;
     for (int i = 0; i < n; ++i) {
         sub2[i] = sub[i] * sub[i];
         const double g = (std::fabs(diag[i]) + (i > 0 ? std::fabs(sub[i - 1]) : 0.0)) + std::fabs(sub[i]);

@@ -60,7 +60,8 @@ void dense_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, i
 // restated; DESIGN.md "The AH cost"): the host form of dense_ah_cost_wave (dense_ah_cost.inc), the same IEEE f64 operations in
 // the same order.  The constants below are shared by both.
 constexpr int DENSE_AH_MAX_N = 32;
-constexpr int DENSE_AH_STRIDE = 33;        // row pitch of the working matrix in doubles (odd: a lane per row meets no bank twice)
+constexpr int DENSE_AH_WIDE_MAX_N = 64;    // AZD_ENGINE_DENSE_AH_WIDE engines, azd_dense_ah_cost_wide: the same procedure with 64 rows
+constexpr int DENSE_AH_STRIDE = 65;        // row pitch of the host's working matrix in doubles (either limit)
 constexpr int DENSE_AH_ROUNDS = 11;        // multisection rounds of 64 shifts: the bracket shrinks by 65 a round
 constexpr double DENSE_AH_TINY = 0x1p-512; // a Sturm pivot smaller than this in magnitude becomes -DENSE_AH_TINY
 struct DenseAhCost {
@@ -71,6 +72,8 @@ struct DenseAhCost {
 float dense_ah_eval_slope(int n);
 // nullptr when the graph is acceptable, else what is wrong with it (an argument name leads the text)
 const char *dense_ah_check_graph(const uint64_t *adj, int n);
+const char *dense_ah_check_graph_wide(const uint64_t *adj, int n); // 4 <= n <= DENSE_AH_WIDE_MAX_N
+// n <= DENSE_AH_WIDE_MAX_N (one function behind azd_dense_ah_cost and azd_dense_ah_cost_wide: the limit is the callers' check)
 void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out);
 
 } // namespace azd

@@ -20,22 +20,35 @@
 // sixteen waves' blocks of the pool step's searchers have to share a CU's 160 KB).  The host form keeps the square; the values are
 // the same to the bit, because the rank-two update A_rc - (v_r q_c + q_r v_c) is symmetric in (r, c) operation by operation
 // (products and the sum commute), so the square's two triangles never differ.
-constexpr int DENSE_AH_TRI = DENSE_AH_MAX_N * (DENSE_AH_MAX_N + 1) / 2;
+//
+// The row limit is the including unit's: DENSE_AH_ROWS = 32 where nothing is defined (dense_ah_kernels.hip, AZD_ENGINE_DENSE_AH) or
+// 64 (dense_ah_wide_kernels.hip, AZD_ENGINE_DENSE_AH_WIDE: a triangle of 2080 doubles, 16.6 KB a wave), and with it the names of
+// what this file declares and the engine's argmin record -- two units of one library cannot both define azd::DenseCostAH.  Order
+// of operations, lane roles and reductions do not depend on it: at n <= 32 the two units compute the same bits.
+#ifndef DENSE_AH_ROWS
+#define DENSE_AH_ROWS DENSE_AH_MAX_N
+#define DenseAhLdsR DenseAhLds
+#define DenseAhSpaceLdsR DenseAhSpaceLds
+#define DenseCostAhR DenseCostAH
+#define DenseAhArgminRecR DenseAhArgminRec
+#endif
+static_assert(DENSE_AH_ROWS == 32 || DENSE_AH_ROWS == 64, "the lanes of one wave own the rows");
+constexpr int DENSE_AH_TRI = DENSE_AH_ROWS * (DENSE_AH_ROWS + 1) / 2;
 __device__ __forceinline__ int dense_ah_at(const int r, const int c) { return r >= c ? r * (r + 1) / 2 + c : c * (c + 1) / 2 + r; }
-struct DenseAhLds {
+struct DenseAhLdsR {
     double A[DENSE_AH_TRI]; // distance matrix (lower triangle, packed), reduced in place
-    double v[DENSE_AH_MAX_N], q[DENSE_AH_MAX_N]; // Householder vector and its companion, by row
-    double diag[DENSE_AH_MAX_N], sub2[DENSE_AH_MAX_N]; // the tridiagonal form: diagonal, squared subdiagonal
+    double v[DENSE_AH_ROWS], q[DENSE_AH_ROWS]; // Householder vector and its companion, by row
+    double diag[DENSE_AH_ROWS], sub2[DENSE_AH_ROWS]; // the tridiagonal form: diagonal, squared subdiagonal
 };
 
-// adj: the graph's neighbourhood bitsets in LDS (n <= DENSE_AH_MAX_N words are read).  hook: called once, after the BFS (the pool
+// adj: the graph's neighbourhood bitsets in LDS (n <= DENSE_AH_ROWS words are read).  hook: called once, after the BFS (the pool
 // step's deferred post, as in dense_lambda1_wave).  Wave-uniform result in `out`.
 template <class Hook>
-__device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhLds &w, const int n, const float slope, Hook &&hook, DenseAhCost &out) {
+__device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhLdsR &w, const int n, const float slope, Hook &&hook, DenseAhCost &out) {
     const int lane = LANE;
     const int row = lane * (lane + 1) / 2; // this lane's row of the packed triangle (lanes < n only)
     const bool in = lane < n;
-    const uint64_t all = (1ull << n) - 1ull; // (n <= 32)
+    const uint64_t all = DENSE_AH_ROWS < 64 ? (1ull << n) - 1ull : ~0ull >> (64 - n); // (64 rows: n = 64 must not shift by 64; n >= 4)
     // ---- BFS from every vertex at once
     int t = 0, d = 0;
     if (in) {
@@ -78,7 +91,7 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
         const double v1 = x1 - alpha;
         const double v = lane == i + 1 ? v1 : x;
         const double beta = 2.0 / (tail + v1 * v1);
-        if (lane < DENSE_AH_MAX_N) w.v[lane] = v;
+        if (lane < DENSE_AH_ROWS) w.v[lane] = v;
         LDS_SYNC();
         double acc = 0.0;
         if (act)
@@ -87,7 +100,7 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
         const double vp = dense_tree_sum(v * p);
         const double K = (0.5 * beta) * vp;
         const double q = act ? p - K * v : 0.0;
-        if (lane < DENSE_AH_MAX_N) w.q[lane] = q;
+        if (lane < DENSE_AH_ROWS) w.q[lane] = q;
         LDS_SYNC();
         if (act)
             for (int c = i + 1; c <= lane; ++c) w.A[row + c] = w.A[row + c] - (v * w.q[c] + q * w.v[c]);
@@ -104,7 +117,7 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
     const double sb_below = __shfl(sb, lane > 0 ? lane - 1 : 0, 64);
     const double g = (fabs(dg) + (lane > 0 ? fabs(sb_below) : 0.0)) + fabs(sb); // Gershgorin; >= 0: the bit patterns order like the numbers
     const double R = __longlong_as_double((long long)wave_max_u64(in ? (uint64_t)__double_as_longlong(g) : 0ull));
-    if (lane < DENSE_AH_MAX_N) {
+    if (lane < DENSE_AH_ROWS) {
         w.diag[lane] = dg;
         w.sub2[lane] = sb * sb;
     }
@@ -138,23 +151,23 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
 }
 
 // ---------------------------------------------------------------- the AH cost as a DenseSpace's cost policy (space_dense.inc)
-// A wave's block: DenseLds without the matching, with the cost's working set.  4 <= n <= DENSE_AH_MAX_N, so E <= 496.
+// A wave's block: DenseLds without the matching, with the cost's working set.  4 <= n <= DENSE_AH_ROWS, so E <= 496 or 2016.
 template <int KW_>
-struct DenseAhSpaceLds {
+struct DenseAhSpaceLdsR {
     uint64_t adj[DENSE_MAX_N];
-    double x[32];                    // write_rows_direct's scratch (the present edges as a bitmap: 8 words, read one past)
+    double x[32];                    // write_rows_direct's scratch (the present edges as a bitmap: 8 words at 32 rows, 32 at 64, read one past)
     uint64_t slotmask[32];
     uint16_t aid[64 * KW_];
     unsigned long long ctr[NUM_COUNTERS];
     uint16_t seq[4];
     uint32_t stack[PATH_STACK];
-    DenseAhLds ah;
+    DenseAhLdsR ah;
 };
 // An agent's record between launches lives in the arrays the default cost uses, twice as long (engine.hip allocates 2 B entries):
 // cur_lambda[t] = pi, cur_lambda[B + t] = eigenvalue, cur_mu[t] = D, cur_mu[B + t] = k.  No per-node arena: node_mate is null.
-struct DenseCostAH {
+struct DenseCostAhR {
     template <int KW_>
-    using Lds = DenseAhSpaceLds<KW_>;
+    using Lds = DenseAhSpaceLdsR<KW_>;
     template <int KW_>
     struct St {
         uint64_t rem[KW_];
@@ -214,9 +227,9 @@ struct DenseCostAH {
     }
     template <class L>
     __device__ static __forceinline__ void argmin_write(const Arenas &a, L &s, const Replay &r, const int wt, const uint32_t win_node) {
-        DenseAhArgminRec *out = reinterpret_cast<DenseAhArgminRec *>(a.argmin_d);
-        if (LANE < DENSE_AH_MAX_N) out->adj[LANE] = LANE < a.n ? s.adj[LANE] : 0ull;
-        if (LANE < 8) out->permitted[LANE] = s.slotmask[LANE];
+        DenseAhArgminRecR *out = reinterpret_cast<DenseAhArgminRecR *>(a.argmin_d);
+        if (LANE < DENSE_AH_ROWS) out->adj[LANE] = LANE < a.n ? s.adj[LANE] : 0ull;
+        if (LANE < (int)(sizeof(out->permitted) / sizeof(uint64_t))) out->permitted[LANE] = s.slotmask[LANE];
         if (LANE == 0) {
             out->proximity = r.c.proximity;
             out->eigenvalue = r.c.eigenvalue;

@@ -49,7 +49,8 @@ static int device_ok(int device) {
 static const SpaceOps *space_ops(const Arenas &a) {
     static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops()};
     static const SpaceOps ramsey = {ramsey_phase_ops(), ramsey_async_ops(), ramsey_pool_ops()};
-    if (a.space == SPACE_DENSE) return a.lam_lo != 0.0 ? &dense_ah_ops() : &dense_ops(); // (Arenas::lam_lo: c21's bracket; 1.0 marks an AH dense engine)
+    // (Arenas::lam_lo: c21's bracket; 1.0 marks an AH dense engine, 2.0 one with AZD_ENGINE_DENSE_AH_WIDE)
+    if (a.space == SPACE_DENSE) return a.lam_lo == 2.0 ? &dense_ah_wide_ops() : a.lam_lo != 0.0 ? &dense_ah_ops() : &dense_ops();
     if (a.space == SPACE_RAMSEY) return a.KW == RAMSEY_U64_KW ? &ramsey64_ops() : &ramsey;
     return &c21;
 }
@@ -179,15 +180,19 @@ struct ExtPoolForm {
      "external pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "                     \
      "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",                                    \
      "external pool step aborted with the test harness' prediction stream: no recovery"}
-static const ExtPoolForm *ext_pool_form(int space, bool dense_ah, bool ramsey_u64) {
+// dense_ah: 0 the default cost, 1 AZD_ENGINE_DENSE_AH, 2 with AZD_ENGINE_DENSE_AH_WIDE beside it
+static const ExtPoolForm *ext_pool_form(int space, int dense_ah, bool ramsey_u64) {
     static const ExtPoolForm dense = AZD_DENSE_EXT_FORM(azd::dense_pool_plan, azd::dense_launch_pool_search, azd::dense_pool_search_resident);
     static const ExtPoolForm ah = AZD_DENSE_EXT_FORM(azd::dense_ah_pool_plan, azd::dense_ah_launch_pool_search, azd::dense_ah_pool_search_resident);
+    // (the same knobs and bounds: its plan takes at most the 6 wavefronts whose blocks a CU's LDS holds, dense_ah_wide_kernels.hip)
+    static const ExtPoolForm ah_wide = AZD_DENSE_EXT_FORM(azd::dense_ah_wide_pool_plan, azd::dense_ah_wide_launch_pool_search,
+                                                          azd::dense_ah_wide_pool_search_resident);
     static const ExtPoolForm wide = AZD_RAMSEY_EXT_FORM(azd::ramsey_ext_pool_plan, azd::ramsey_ext_launch_pool_search,
                                                         azd::ramsey_ext_pool_search_resident, azd::RAMSEY_EXT_WAVES);
     static const ExtPoolForm u64 = AZD_RAMSEY_EXT_FORM(azd::ramsey64_ext_pool_plan, azd::ramsey64_ext_launch_pool_search,
                                                        azd::ramsey64_ext_pool_search_resident, azd::RAMSEY64_EXT_WAVES);
     static_assert(azd::RAMSEY_EXT_WAVES == 8 && azd::RAMSEY64_EXT_WAVES == 8, "AZD_RAMSEY_EXT_POOL_WAVES' range is spelled out in its error text");
-    if (space == azd::SPACE_DENSE) return dense_ah ? &ah : &dense;
+    if (space == azd::SPACE_DENSE) return dense_ah == 2 ? &ah_wide : dense_ah ? &ah : &dense;
     return ramsey_u64 ? &u64 : &wide;
 }
 
@@ -327,6 +332,7 @@ struct azd_engine {
     bool ramsey_wide() const { return a.space == azd::SPACE_RAMSEY && a.KW > azd::MAX_KW; }
     // the 64-bit tier (AZD_ENGINE_RAMSEY_U64): uint64_t neighbourhood rows of 64 vertices, keys of RAMSEY_U64_KW words, its own record
     bool dense_ah() const { return a.space == azd::SPACE_DENSE && a.lam_lo != 0.0; } // AZD_ENGINE_DENSE_AH
+    bool dense_ah_wide() const { return a.space == azd::SPACE_DENSE && a.lam_lo == 2.0; } // ... with AZD_ENGINE_DENSE_AH_WIDE: 64 rows, its own record
     bool ramsey_u64() const { return a.space == azd::SPACE_RAMSEY && a.KW == azd::RAMSEY_U64_KW; }
     size_t ramsey_nbr_words() const { return ramsey_u64() ? 512 : 128; } // uint32_t words of an agent's [4][NV] rows
     size_t argmin_r_bytes() const {
@@ -790,7 +796,21 @@ static int check_engine_config(const azd_engine_config *cfg) {
     const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
     const bool dense = cfg->space_id == AZD_SPACE_DENSE;
     const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
-    if (dense_ah) {
+    const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
+    if (dense_ah_wide) {
+        const char *bad = !dense_ah ? "flags: AZD_ENGINE_DENSE_AH_WIDE is valid only beside AZD_ENGINE_DENSE_AH (the Aouchiche-Hansen cost whose 64-row form it asks for)"
+                          : !dense  ? "space_id: AZD_ENGINE_DENSE_AH_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
+                          : cfg->n < 4 || cfg->n > AZD_DENSE_AH_WIDE_MAX_N ? "n: the wide Aouchiche-Hansen cost needs 4 <= n <= 64 (AZD_DENSE_AH_WIDE_MAX_N)"
+                          : cfg->layers > 1 ? "layers: AZD_ENGINE_DENSE_AH_WIDE engines take no Layered wrapper (layers <= 1)"
+                          : cfg->path_kind != AZD_PATH_SET ? "path_kind: AZD_ENGINE_DENSE_AH_WIDE engines keep ActionSet paths (AZD_PATH_SET)"
+                          : cfg->max_slots > std::min(azd::dense_edges(cfg->n), 640)
+                              ? "max_slots: AZD_ENGINE_DENSE_AH_WIDE needs max_slots <= min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)"
+                              : nullptr;
+        if (bad) {
+            azd::g_last_error = bad;
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+    } else if (dense_ah) {
         const char *bad = !dense                                                  ? "space_id: AZD_ENGINE_DENSE_AH needs the dense-graph space (AZD_SPACE_DENSE)"
                           : cfg->n < 4 || cfg->n > AZD_DENSE_AH_MAX_N             ? "n: the Aouchiche-Hansen cost needs 4 <= n <= 32 (AZD_DENSE_AH_MAX_N)"
                           : cfg->layers > 1                                       ? "layers: AZD_ENGINE_DENSE_AH engines take no Layered wrapper (layers <= 1)"
@@ -892,6 +912,11 @@ static int check_engine_config(const azd_engine_config *cfg) {
     }
     return AZD_OK;
 }
+// dense-graph space, device keys: ranks of the root's modifiable slots, in 2 / 4 / 10 / 16 words (the widths dense_kernels.hip is built for)
+static int dense_device_key_words(int max_slots) {
+    const int ms = max_slots > 0 ? max_slots : 128;
+    return ms <= 128 ? 2 : ms <= 256 ? 4 : ms <= 640 ? 10 : 16;
+}
 // what the LDS plans read of an engine's arenas, for a Ramsey configuration that check_engine_config has accepted
 static void ramsey_shape(const azd_engine_config *cfg, azd::Arenas *a) {
     a->C = cfg->n_colors;
@@ -911,6 +936,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
     const bool dense = cfg->space_id == AZD_SPACE_DENSE;
     const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0;
+    const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0;
     AZD_ST(azd::device_ok(cfg->device));
     AZD_HIP(hipSetDevice(cfg->device));
     azd_engine *e = new (std::nothrow) azd_engine();
@@ -928,16 +954,13 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         a.E = azd::dense_edges(cfg->n);
         a.A = azd::dense_action_dim(cfg->n);
         a.S = azd::dense_state_dim(cfg->n);
-        {   // device keys: ranks of the root's modifiable slots, in 2 / 4 / 10 / 16 words (the widths dense_kernels.hip is built for)
-            const int ms = cfg->max_slots > 0 ? cfg->max_slots : 128;
-            a.KW = ms <= 128 ? 2 : ms <= 256 ? 4 : ms <= 640 ? 10 : 16;
-            e->dense_slots = 64 * a.KW;
-        }
+        a.KW = dense_device_key_words(cfg->max_slots);
+        e->dense_slots = 64 * a.KW;
         a.dense_p24 = (uint32_t)((cfg->dense_p > 0.f ? (double)cfg->dense_p : 0.2) * 16777216.0 + 0.5);
         a.eval_slope = azd::c21_eval_slope(cfg->n);
         if (dense_ah) { // (key widths 2, 4 and 10 only: max_slots <= E <= 496)
             a.eval_slope = azd::dense_ah_eval_slope(cfg->n);
-            a.lam_lo = 1.0; // marks the engine for space_ops() and dense_ah(); no dense kernel reads the c21 bracket
+            a.lam_lo = dense_ah_wide ? 2.0 : 1.0; // marks the engine for space_ops() and dense_ah(); no dense kernel reads the c21 bracket
         }
         e->kw_host = azd::dense_key_words(cfg->n);
     } else if (ramsey) {
@@ -956,7 +979,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         azd::c21_lambda_bracket(cfg->n, &a.lam_lo, &a.lam_hi);
     }
     e->ops = azd::space_ops(a);
-    if (dense || (cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) e->ext = ext_pool_form(a.space, dense_ah, e->ramsey_u64());
+    if (dense || (cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) e->ext = ext_pool_form(a.space, dense_ah_wide ? 2 : dense_ah ? 1 : 0, e->ramsey_u64());
     e->ext_f32 = (cfg->flags & AZD_ENGINE_EXT_POOL_F32) != 0;
     a.S_inner = a.S;
     a.S = a.S_inner * a.layers; // Layered<L, Space>::STATE_DIM (nabla/space/mod.rs:53)
@@ -1051,7 +1074,8 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         TRY(e->alloc(&a.root_aid, B * (size_t)e->dense_slots));
         TRY(e->alloc(&e->d_stage_slots, B * (size_t)((a.E + 63) / 64)));
         TRY(e->alloc(&a.argmin_d, 1));
-        static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec), "an AH engine's argmin record lives in argmin_d's allocation");
+        static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseAhWideArgminRec) <= sizeof(azd::DenseArgminRec),
+                      "an AH engine's argmin record lives in argmin_d's allocation");
         if (!dense_ah) TRY(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH cost keeps nothing per node)
         // a bf16 evaluator takes the state vectors as bf16 rows: this space's kernels write them beside the f32 rows (write_vec16)
         if (ev && ev->input16_pitch() >= a.S) {
@@ -2794,10 +2818,28 @@ int azd_engine_dense_argmin_data(azd_engine *e, azd_dense_argmin *out) {
 int azd_engine_dense_ah_argmin_data(azd_engine *e, azd_dense_ah_argmin *out) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (!e->dense_ah()) return AZD_ERR_UNSUPPORTED;
+    if (e->dense_ah_wide()) {
+        azd::g_last_error = "azd_engine_dense_ah_argmin_data: an AZD_ENGINE_DENSE_AH_WIDE engine's record is read with azd_engine_dense_ah_wide_argmin_data";
+        return AZD_ERR_UNSUPPORTED;
+    }
     AZD_ENTER(e);
     static_assert(sizeof(azd_dense_ah_argmin) == sizeof(azd::DenseAhArgminRec), "ABI struct mismatch");
     AZD_HIP(hipStreamSynchronize(e->stream));
     AZD_HIP(hipMemcpy(out, e->a.argmin_d, sizeof(azd_dense_ah_argmin), hipMemcpyDeviceToHost));
+    return AZD_OK;
+}
+int azd_engine_dense_ah_wide_argmin_data(azd_engine *e, azd_dense_ah_wide_argmin *out) {
+    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
+    if (!e->dense_ah_wide()) {
+        azd::g_last_error = "azd_engine_dense_ah_wide_argmin_data: not an AZD_ENGINE_DENSE_AH_WIDE engine";
+        return AZD_ERR_UNSUPPORTED;
+    }
+    AZD_ENTER(e);
+    static_assert(sizeof(azd_dense_ah_wide_argmin) == sizeof(azd::DenseAhWideArgminRec) &&
+                      offsetof(azd_dense_ah_wide_argmin, node) == offsetof(azd::DenseAhWideArgminRec, node),
+                  "ABI struct mismatch");
+    AZD_HIP(hipStreamSynchronize(e->stream));
+    AZD_HIP(hipMemcpy(out, e->a.argmin_d, sizeof(azd_dense_ah_wide_argmin), hipMemcpyDeviceToHost));
     return AZD_OK;
 }
 int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out) {
@@ -3110,23 +3152,26 @@ int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks) {
     if (he != hipSuccess) return azd::hip_fail(he, "probe_xcc");
     return AZD_OK;
 }
-// The LDS plan of the searcher-only pool step for a configuration (AZD_ENGINE_EXT_POOL_STEP): wavefronts per searcher workgroup
-// and bytes of LDS a workgroup takes, its static blocks included.  Arithmetic only: no device is touched.
+// The LDS plan of the searcher-only pool step for a configuration (AZD_ENGINE_EXT_POOL_STEP, or a dense-graph engine with
+// AZD_ENGINE_DENSE_AH_WIDE, whose pool step is planned by what the LDS holds too): wavefronts per searcher workgroup and bytes of
+// LDS a workgroup takes, its static blocks included.  Arithmetic only: no device is touched.
 int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes) {
     if (!cfg || !waves || !lds_bytes) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ST(check_engine_config(cfg));
-    if (!(cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) {
+    const bool ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0;
+    if (!(cfg->flags & AZD_ENGINE_EXT_POOL_STEP) && !ah_wide) {
         azd::g_last_error = "azd_debug_ext_pool_plan: the configuration does not set AZD_ENGINE_EXT_POOL_STEP";
         return AZD_ERR_INVALID_ARGUMENT;
     }
     azd::Arenas a;
     memset(&a, 0, sizeof(a));
-    a.space = azd::SPACE_RAMSEY;
+    a.space = ah_wide ? azd::SPACE_DENSE : azd::SPACE_RAMSEY;
     a.n = cfg->n;
     a.B = cfg->batch;
     a.node_cap = cfg->node_capacity > 0 ? (uint32_t)cfg->node_capacity : 4096u;
-    ramsey_shape(cfg, &a);
-    const ExtPoolForm *xf = ext_pool_form(a.space, false, a.KW == azd::RAMSEY_U64_KW);
+    if (ah_wide) a.KW = dense_device_key_words(cfg->max_slots);
+    else ramsey_shape(cfg, &a);
+    const ExtPoolForm *xf = ext_pool_form(a.space, ah_wide ? 2 : 0, a.KW == azd::RAMSEY_U64_KW);
     const char *why = "";
     uint32_t dyn_stride = 0;
     size_t dyn_bytes = 0;
@@ -3208,7 +3253,7 @@ int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, i
 // ------------------------------------------------------------------ Aouchiche-Hansen cost of the dense-graph space
 static_assert(sizeof(azd_dense_ah_cost_t) == sizeof(azd::DenseAhCost) && offsetof(azd_dense_ah_cost_t, eval) == offsetof(azd::DenseAhCost, eval),
               "azd_dense_ah_cost_t mirrors azd::DenseAhCost");
-static_assert(AZD_DENSE_AH_MAX_N == azd::DENSE_AH_MAX_N, "AZD_DENSE_AH_MAX_N");
+static_assert(AZD_DENSE_AH_MAX_N == azd::DENSE_AH_MAX_N && AZD_DENSE_AH_WIDE_MAX_N == azd::DENSE_AH_WIDE_MAX_N, "AZD_DENSE_AH_MAX_N, AZD_DENSE_AH_WIDE_MAX_N");
 int azd_dense_ah_cost(const uint64_t *adj, int n, azd_dense_ah_cost_t *out) {
     if (!out) {
         azd::g_last_error = "azd_dense_ah_cost: out: null";
@@ -3221,14 +3266,29 @@ int azd_dense_ah_cost(const uint64_t *adj, int n, azd_dense_ah_cost_t *out) {
     azd::dense_ah_cost_host(adj, n, reinterpret_cast<azd::DenseAhCost *>(out));
     return AZD_OK;
 }
-int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
-    if (!out || count <= 0 || reps <= 0) {
-        azd::g_last_error = "azd_debug_probe_ah_cost: out / count / reps";
+int azd_dense_ah_cost_wide(const uint64_t *adj, int n, azd_dense_ah_cost_t *out) {
+    if (!out) {
+        azd::g_last_error = "azd_dense_ah_cost_wide: out: null";
         return AZD_ERR_INVALID_ARGUMENT;
     }
+    if (const char *why = azd::dense_ah_check_graph_wide(adj, n)) {
+        azd::g_last_error = std::string("azd_dense_ah_cost_wide: ") + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    azd::dense_ah_cost_host(adj, n, reinterpret_cast<azd::DenseAhCost *>(out));
+    return AZD_OK;
+}
+// the two probes: the same host side around the 32-row and the 64-row kernel
+static int probe_ah_cost(const char *name, bool wide, int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
+    if (!out || count <= 0 || reps <= 0) {
+        azd::g_last_error = std::string(name) + ": out / count / reps";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    const auto check = wide ? azd::dense_ah_check_graph_wide : azd::dense_ah_check_graph;
+    const auto launch = wide ? azd::launch_probe_ah_cost_wide : azd::launch_probe_ah_cost;
     for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
-        if (const char *why = azd::dense_ah_check_graph(adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n)) {
-            azd::g_last_error = std::string("azd_debug_probe_ah_cost: graph ") + std::to_string(i) + ": " + why;
+        if (const char *why = check(adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n)) {
+            azd::g_last_error = std::string(name) + ": graph " + std::to_string(i) + ": " + why;
             return AZD_ERR_INVALID_ARGUMENT;
         }
     AZD_ST(azd::device_ok(device));
@@ -3241,9 +3301,9 @@ int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, i
     AZD_HIP(hipEventCreate(&e0));
     AZD_HIP(hipEventCreate(&e1));
     AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
-    azd::launch_probe_ah_cost(d_adj, n, count, 1, d_out, nullptr); // warm-up
+    launch(d_adj, n, count, 1, d_out, nullptr); // warm-up
     AZD_HIP(hipEventRecord(e0, nullptr));
-    azd::launch_probe_ah_cost(d_adj, n, count, reps, d_out, nullptr);
+    launch(d_adj, n, count, reps, d_out, nullptr);
     AZD_HIP(hipEventRecord(e1, nullptr));
     hipError_t he = hipDeviceSynchronize();
     float t = 0.f;
@@ -3256,6 +3316,12 @@ int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, i
     if (he != hipSuccess) return azd::hip_fail(he, "probe_ah_cost");
     if (ms) *ms = t;
     return AZD_OK;
+}
+int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
+    return probe_ah_cost("azd_debug_probe_ah_cost", false, device, adj, n, count, reps, out, ms);
+}
+int azd_debug_probe_ah_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
+    return probe_ah_cost("azd_debug_probe_ah_cost_wide", true, device, adj, n, count, reps, out, ms);
 }
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
     if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;

@@ -162,6 +162,16 @@ struct DenseAhArgminRec { // device copy of azd_dense_ah_argmin (AZD_ENGINE_DENS
     uint32_t node;
 };
 
+struct DenseAhWideArgminRec { // device copy of azd_dense_ah_wide_argmin (AZD_ENGINE_DENSE_AH_WIDE engines: n <= 64, E <= 2016); in argmin_d's place too
+    uint64_t adj[64];
+    uint64_t permitted[32]; // modifiable slots (colex positions) still open
+    double proximity, eigenvalue;
+    int32_t diameter, k;
+    float cost, eval;
+    int32_t agent;
+    uint32_t node;
+};
+
 struct StatusRec { // small device block copied back after every host-visible call
     unsigned long long improved;   // k_argmin calls that improved the argmin
     unsigned long long expansions; // sum over agents and calls (metric numerator)
@@ -206,7 +216,7 @@ struct Arenas {
     int t0, tn;             // launch-per-phase kernels over a SUB-population: agents t0 .. t0 + tn - 1 (tn = 0: all B); see engine.hip
     float eval_slope;       // squish slope 1/(C_UPPER - C_LOWER), 04-c21-tree.rs:58-74
     double lam_lo, lam_hi;  // c21: initial bracket of the lambda_1 multisection (c21_host.cpp:c21_lambda_bracket).  Dense-graph space (no
-                            // kernel of it reads them): lam_lo = 1.0 marks an AZD_ENGINE_DENSE_AH engine for the host's dispatch, else 0
+                            // kernel of it reads them): lam_lo = 1.0 marks an AZD_ENGINE_DENSE_AH engine for the host's dispatch (2.0: with AZD_ENGINE_DENSE_AH_WIDE), else 0
     // ---- Ramsey space (space_ramsey.inc); unused (null / 0) for c21
     int space;              // SPACE_C21 / SPACE_RAMSEY
     int C, E;               // colours, edges N(N-1)/2;  A = E*C, S = E*(2C+1)

@@ -49,6 +49,7 @@ const PhaseOps &c21_phase_ops(), &ramsey_phase_ops();
 const AsyncOps &c21_async_ops(), &ramsey_async_ops();
 const PoolOps &c21_pool_ops(), &ramsey_pool_ops();
 const SpaceOps &ramsey64_ops(), &dense_ops(), &dense_ah_ops(); // dense_ah_ops: DenseSpace with the Aouchiche-Hansen cost (dense_ah_kernels.hip)
+const SpaceOps &dense_ah_wide_ops();                            // ... with its 64-row form (dense_ah_wide_kernels.hip: AZD_ENGINE_DENSE_AH_WIDE)
 
 // ---- the same for every space
 // launch-per-phase form over sub-populations on streams of their own (engine.hip): the candidates of agents a.t0 .. a.t0 + a.tn - 1
@@ -69,6 +70,7 @@ void launch_probe_math(const float *d_in, float *d_out, int n, void *stream); //
 struct DenseAhCost;
 void launch_probe_ah_cost(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream);
 void launch_probe_math_f64(const double *d_in, double *d_out, int n, void *stream);
+void launch_probe_ah_cost_wide(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream); // n <= 64 (dense_ah_wide_kernels.hip)
 
 // ---- pool step of the dense-graph space (dense_kernels.hip): searcher workgroups only (k_pool_search); the evaluator is a stream of
 // batched GEMM launches over the rows the searchers have posted, collected by k_ext_take and handed back by k_ext_deliver (pool_step.inc)
@@ -81,6 +83,12 @@ bool dense_ah_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t
 void dense_ah_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
                                  size_t dyn_bytes, void *stream);
 int dense_ah_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
+// ... and for an AZD_ENGINE_DENSE_AH_WIDE engine (dense_ah_wide_kernels.hip): k_pool_search_w with as many wavefronts as the LDS holds
+// of its 20-KB blocks (6); the plan refuses more, and touches no device
+bool dense_ah_wide_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
+void dense_ah_wide_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
+                                      size_t dyn_bytes, void *stream);
+int dense_ah_wide_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
 // the same three for the Ramsey tiers with max_slots > 0 under AZD_ENGINE_EXT_POOL_STEP (ramsey_ext_kernels.hip: the 32-bit wide tier;
 // ramsey64_ext_kernels.hip: the 64-bit tier).  waves <= *_EXT_WAVES, the wavefronts per workgroup their kernels are built and
 // launch-bounded for (k_pool_search_w; DESIGN.md section 3 says why eight).  The plans are arithmetic: they touch no device.

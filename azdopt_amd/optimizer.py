@@ -118,6 +118,8 @@ class NablaOptimizer:
             cfg.dense_p = space.p
             if getattr(space, "COST", "c21") == "ah":
                 cfg.flags |= _lib.ENGINE_DENSE_AH
+                if getattr(space, "AH_WIDE", False):
+                    cfg.flags |= _lib.ENGINE_DENSE_AH_WIDE
         if space.SPACE_ID == _lib.SPACE_RAMSEY:
             cfg.max_slots = getattr(space, "MAX_SLOTS", 0)
             if getattr(space, "U64", False):
@@ -263,8 +265,12 @@ class NablaOptimizer:
                 _lib.check(self._L.azd_engine_ramsey_argmin_data(self._h, C.byref(rec)), "ramsey_argmin_data")
             return RamseyArgminData(rec, self.space)
         if self.space.SPACE_ID == _lib.SPACE_DENSE and getattr(self.space, "COST", "c21") == "ah":
-            rec = _lib.DenseAhArgmin()
-            _lib.check(self._L.azd_engine_dense_ah_argmin_data(self._h, C.byref(rec)), "dense_ah_argmin_data")
+            if getattr(self.space, "AH_WIDE", False):  # (the 64-row form's record: 64 neighbourhoods, 32 words of open slots)
+                rec = _lib.DenseAhWideArgmin()
+                _lib.check(self._L.azd_engine_dense_ah_wide_argmin_data(self._h, C.byref(rec)), "dense_ah_wide_argmin_data")
+            else:
+                rec = _lib.DenseAhArgmin()
+                _lib.check(self._L.azd_engine_dense_ah_argmin_data(self._h, C.byref(rec)), "dense_ah_argmin_data")
             return DenseAhArgminData(rec, self.space)
         if self.space.SPACE_ID == _lib.SPACE_DENSE:
             rec = _lib.DenseArgmin()

@@ -196,18 +196,23 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     `cost`: "c21" (the default, above) or "ah" -- the Aouchiche-Hansen cost, the objective of the reference's 05-ah.rs
     (ConnectedBitsetGraph::ah_cost, mod.rs:156-198): proximity + the distance matrix's eigenvalue of index floor(2D/3) - 1;
     BUILD-DEFINED evaluate = (cost + 2) / (2N + 2).  N <= 32 there (AZD_ENGINE_DENSE_AH); states, actions, keys and roots are the
-    same space's."""
+    same space's.  `ah_wide=True` (with cost="ah" only): the cost's 64-row form, N <= 64 (AZD_ENGINE_DENSE_AH_WIDE beside the
+    first flag; never chosen from N), roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives."""
 
     SPACE_ID = _lib.SPACE_DENSE
 
-    def __init__(self, n, p=0.2, max_slots=128, cost="c21"):
+    def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False):
         if cost not in ("c21", "ah"):
             raise ValueError('cost must be "c21" or "ah"')
+        if ah_wide and cost != "ah":
+            raise ValueError('ah_wide=True needs cost="ah" (it is the Aouchiche-Hansen cost\'s 64-row form)')
         self.COST = cost
+        self.AH_WIDE = bool(ah_wide)
         self.n, self.p = int(n), float(p)
         self.E = self.n * (self.n - 1) // 2
         # (an AZD_ENGINE_DENSE_AH engine refuses max_slots > E; a root cannot bring more than E slots anyway)
-        self.MAX_SLOTS = min(int(max_slots), self.E) if cost == "ah" else int(max_slots)
+        # (... and an AZD_ENGINE_DENSE_AH_WIDE engine max_slots > min(E, 640): its keys are 2, 4 or 10 words)
+        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide else min(int(max_slots), self.E) if cost == "ah" else int(max_slots)
         L = _lib.lib()
         self.STATE_DIM = L.azd_dense_state_dim(self.n)
         self.ACTION_DIM = L.azd_dense_action_dim(self.n)
@@ -237,11 +242,15 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
         return ("add", index) if index < self.E else ("delete", index - self.E)
 
     def ah_cost(self, adj):
-        """The Aouchiche-Hansen cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_ah_cost, the same
-        procedure as the device's, bit for bit.  -> dict(proximity, eigenvalue, diameter, k, cost, eval)"""
+        """The Aouchiche-Hansen cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_ah_cost
+        (azd_dense_ah_cost_wide for an ah_wide space), the same procedure as the device's, bit for bit.
+        -> dict(proximity, eigenvalue, diameter, k, cost, eval)"""
         a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
         out = _lib.DenseAhCost()
-        _lib.check(_lib.lib().azd_dense_ah_cost(_lib.ptr(a), self.n, C.byref(out)), "azd_dense_ah_cost")
+        if getattr(self, "AH_WIDE", False):
+            _lib.check(_lib.lib().azd_dense_ah_cost_wide(_lib.ptr(a), self.n, C.byref(out)), "azd_dense_ah_cost_wide")
+        else:
+            _lib.check(_lib.lib().azd_dense_ah_cost(_lib.ptr(a), self.n, C.byref(out)), "azd_dense_ah_cost")
         return dict(proximity=out.proximity, eigenvalue=out.eigenvalue, diameter=out.diameter, k=out.k,
                     cost=np.float32(out.cost), eval=np.float32(out.eval))
 

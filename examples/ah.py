@@ -3,13 +3,14 @@
 ConnectedBitsetGraph::ah_cost, is live code), written as the live drivers' loop over the MI355X engine: a search for counterexamples
 to the Aouchiche-Hansen conjecture on connected graphs with N = 31 vertices.
 
-    python examples/ah.py [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
+    python examples/ah.py [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16] [--n N --wide]
 
 Roots are G(31, 0.4) redrawn until connected (05-ah.rs:93); the model is 1396-256-128-930 (the stub's widths under the live
 ActionModel head).  The loop is par_roll_out_episodes x episodes, par_update_model, par_reset_trees with the device root policy.
 A cost below 0 would be a counterexample: the run stops there.  (The complete graph's cost is 0 up to the eigen-solve's rounding,
 a few 1e-16 either way, so "below 0" is taken as below -1e-4.)  With --dtype bf16 and 256 agents or more the engine runs its pool
-step; an fp32 model runs one launch per phase."""
+step; an fp32 model runs one launch per phase.  --n N sets another number of vertices; beyond 32 it needs --wide, the cost's 64-row
+form (AZD_ENGINE_DENSE_AH_WIDE, N <= 64), which is asked for by name and never chosen from N."""
 import argparse
 import os
 import sys
@@ -34,9 +35,11 @@ def main():
     ap.add_argument("--max-slots", type=int, default=128)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--n", type=int, default=N, help="vertices (default 31, the reference's; more than 32 needs --wide)")
+    ap.add_argument("--wide", action="store_true", help="the cost's 64-row form: n <= 64")
     args = ap.parse_args()
 
-    space = az.DenseGraphSpace(N, P, max_slots=args.max_slots, cost="ah")
+    space = az.DenseGraphSpace(args.n, P, max_slots=args.max_slots, cost="ah", ah_wide=args.wide)
     model = az.ActionModel(args.batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=1e-4, l2=1e-6, seed=args.seed,
                            dtype=args.dtype)
     if args.out:

@@ -116,8 +116,9 @@ int azd_ramsey_generate_roots_weighted(uint64_t seed, uint64_t epoch, uint64_t f
 /*   number; mod.rs:319-338), the default, or -- with the engine flag         */
 /*   AZD_ENGINE_DENSE_AH, N <= AZD_DENSE_AH_MAX_N = 32 -- the Aouchiche-      */
 /*   Hansen cost that 05-ah.rs searches with (ah_cost, mod.rs:156-198;        */
-/*   azd_dense_ah_cost below).  States, actions, vectors and roots are the    */
-/*   same for both.                                                           */
+/*   azd_dense_ah_cost below), or up to N = 64 with                           */
+/*   AZD_ENGINE_DENSE_AH_WIDE beside it.  States, actions, vectors and roots  */
+/*   are the same for all of them.                                            */
 /* ------------------------------------------------------------------------- */
 #define AZD_SPACE_DENSE 3
 #define AZD_DENSE_MAX_N 64
@@ -287,6 +288,18 @@ typedef struct azd_engine_config {
  * per-node matching arena; read them with azd_engine_dense_ah_agent_cost and azd_engine_dense_ah_argmin_data
  * (azd_engine_dense_argmin_data, and azd_engine_agent_state's lambda_1 / matching_size, are AZD_ERR_UNSUPPORTED on it). */
 #define AZD_ENGINE_DENSE_AH 32u
+/* Beside AZD_ENGINE_DENSE_AH only (alone, or on another space: AZD_ERR_INVALID_ARGUMENT naming the argument): the same cost up to
+ * 64 vertices, the dense-graph space's own limit -- the device procedure with 64 rows (a wave's packed triangle is 2080 doubles,
+ * 16.6 KB of LDS, where the 32-row form's is 4.1 KB), in kernels of their own; the 32-row kernels and every engine without the flag
+ * are what they are without it.  Never chosen from the sizes.  Limits: 4 <= n <= AZD_DENSE_AH_WIDE_MAX_N, layers <= 1, ActionSet
+ * paths, max_slots <= min(E, 640) (key widths 2, 4 and 10; roots of more than 640 slots are out of scope).  A wide engine on
+ * n <= 32 is accepted and gives the trees the narrow engine gives.  eval = slope * (cost + 2.0f), slope = 1.0f / (2n + 2), as
+ * there.  Its argmin record is azd_dense_ah_wide_argmin, read with azd_engine_dense_ah_wide_argmin_data
+ * (azd_engine_dense_ah_argmin_data is AZD_ERR_UNSUPPORTED on it and names that call); azd_engine_dense_ah_agent_cost serves both.
+ * Pool step: a searcher wave's LDS block is 20 KB, so a searcher workgroup has as many wavefronts as a CU's 160 KB hold -- 6 --
+ * where the narrow engine's has 7..10 and the default cost's 16 (azd_debug_ext_pool_plan reports the plan for such a
+ * configuration too); AZD_DENSE_POOL_WAVES keeps its range 4..16, a setting above what fits runs what fits. */
+#define AZD_ENGINE_DENSE_AH_WIDE 256u
 /* AZD_SPACE_RAMSEY with max_slots > 0 only (the 32-bit wide tier, or the 64-bit tier beside AZD_ENGINE_RAMSEY_U64): the
  * searcher-only pool step, the CU-resident form of these engines for a model that does not fit an evaluator workgroup's LDS.
  * Persistent searcher workgroups of eight wavefronts pull agents from the per-XCD ready queues, write each new node's state row
@@ -595,9 +608,10 @@ int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks);
  * same harness: AZD_POOL_DEBUG_ABORT_CALL=k (agent 0 raises the launch's abort flag after its k-th call: the take-over by the
  * asynchronous step), AZD_POOL_MAX_RESIDENT=w (pretend the device holds w workgroups of the pool kernel at once). */
 int azd_debug_hash_stream_via_evaluators(azd_evaluator *ev, int on);
-/* The LDS plan of the searcher-only pool step (AZD_ENGINE_EXT_POOL_STEP) for a configuration: wavefronts per searcher workgroup and
- * the bytes of LDS one workgroup takes (of the CU's 160 KB).  Arithmetic on the configuration: no device is touched.
- * AZD_ERR_INVALID_ARGUMENT for a configuration azd_engine_create refuses, or one without the flag. */
+/* The LDS plan of the searcher-only pool step (AZD_ENGINE_EXT_POOL_STEP; also a dense-graph configuration with
+ * AZD_ENGINE_DENSE_AH_WIDE, whose pool step takes as many wavefronts as the LDS holds) for a configuration: wavefronts per
+ * searcher workgroup and the bytes of LDS one workgroup takes (of the CU's 160 KB).  Arithmetic on the configuration: no device is
+ * touched.  AZD_ERR_INVALID_ARGUMENT for a configuration azd_engine_create refuses, or one with neither flag. */
 int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes);
 /* The evaluator of the searcher-only pool step in isolation (tests): the MLP's gathered forward of whichever storage type it has
  * -- fp32: the gathered fp32 GEMMs of AZD_ENGINE_EXT_POOL_F32; bf16: the gathered bf16 GEMMs -- on host arrays.  states:
@@ -633,8 +647,10 @@ int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, i
  * dense space's squish; and the eigenvalue procedure that stands in for faer -- Householder tridiagonalisation, then a Sturm-count
  * multisection for the one eigenvalue -- one IEEE f64 operation at a time in a fixed order, so that this host function, the
  * device kernel (azd_debug_probe_ah_cost) and the tests' Python reference agree bit for bit (DESIGN.md "The AH cost").
- * 4 <= n <= AZD_DENSE_AH_MAX_N: at 32 vertices a wave's working matrix (a packed triangle) is 4 KB of LDS, at 64 it would be 16 KB. */
+ * 4 <= n <= AZD_DENSE_AH_MAX_N: at 32 vertices a wave's working matrix (a packed triangle) is 4 KB of LDS; at 64 it is 16.6 KB,
+ * and that form has names of its own: AZD_DENSE_AH_WIDE_MAX_N, azd_dense_ah_cost_wide, AZD_ENGINE_DENSE_AH_WIDE. */
 #define AZD_DENSE_AH_MAX_N 32
+#define AZD_DENSE_AH_WIDE_MAX_N 64
 typedef struct azd_dense_ah_cost_t {
     double proximity;  /* pi */
     double eigenvalue; /* entry k of the distance spectrum, descending */
@@ -646,9 +662,14 @@ typedef struct azd_dense_ah_cost_t {
 /* The cost on the host; needs no GPU.  adj: n neighbourhood bitsets (bit u of adj[v] = edge {u, v}).  AZD_ERR_INVALID_ARGUMENT
  * with an azd_last_error() that names the argument for n out of range or a graph that is not simple, symmetric and connected. */
 int azd_dense_ah_cost(const uint64_t *adj, int n, azd_dense_ah_cost_t *out);
+/* The same host function for 4 <= n <= AZD_DENSE_AH_WIDE_MAX_N: the same sequence of IEEE f64 operations and the same graph
+ * checks; for n <= 32 bit for bit azd_dense_ah_cost. */
+int azd_dense_ah_cost_wide(const uint64_t *adj, int n, azd_dense_ah_cost_t *out);
 /* The device kernel in isolation: the cost of `count` graphs on n vertices (adj[count][n]), one wavefront each, repeated `reps`
  * times; *ms = GPU time of the timed launch.  The graphs are checked like azd_dense_ah_cost's, before the device is looked for. */
 int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms);
+/* ... and the 64-row kernel (AZD_ENGINE_DENSE_AH_WIDE engines' cost), 4 <= n <= AZD_DENSE_AH_WIDE_MAX_N; checked the same way */
+int azd_debug_probe_ah_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms);
 /* ArgminData of an AZD_ENGINE_DENSE_AH engine: the graph, the slots still open, the cost's parts */
 typedef struct azd_dense_ah_argmin {
     uint64_t adj[32];
@@ -660,6 +681,17 @@ typedef struct azd_dense_ah_argmin {
     uint32_t node;
 } azd_dense_ah_argmin;
 int azd_engine_dense_ah_argmin_data(azd_engine *e, azd_dense_ah_argmin *out);
+/* ArgminData of an engine with AZD_ENGINE_DENSE_AH_WIDE beside AZD_ENGINE_DENSE_AH (on any other engine: AZD_ERR_UNSUPPORTED) */
+typedef struct azd_dense_ah_wide_argmin {
+    uint64_t adj[64];
+    uint64_t permitted[32]; /* modifiable slots (colex positions) still open; E <= 2016 */
+    double proximity, eigenvalue;
+    int32_t diameter, k;
+    float cost, eval;
+    int32_t agent;
+    uint32_t node;
+} azd_dense_ah_wide_argmin;
+int azd_engine_dense_ah_wide_argmin_data(azd_engine *e, azd_dense_ah_wide_argmin *out);
 /* the cost of agent `agent`'s current state as the engine keeps it (the AH counterpart of azd_engine_agent_state's lambda_1 /
  * matching_size) */
 int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out);

@@ -179,19 +179,26 @@ private:
 
 // The same space with the Aouchiche-Hansen cost as the objective (AZD_ENGINE_DENSE_AH; the objective of the reference's 05-ah.rs,
 // ConnectedBitsetGraph::ah_cost, mod.rs:156-198): n <= AZD_DENSE_AH_MAX_N, max_slots <= E.  argmin_data() gives a DenseAhArgmin.
+// wide = true: the cost's 64-row form (AZD_ENGINE_DENSE_AH_WIDE beside the first flag; asked for by name, never chosen from n):
+// n <= AZD_DENSE_AH_WIDE_MAX_N, max_slots <= min(E, 640); at n <= 32 it gives what the narrow form gives.
 class DenseGraphAhSpace : public DenseGraphSpace {
 public:
-    explicit DenseGraphAhSpace(int n, double p = 0.4, int max_slots = 128) : DenseGraphSpace(n, p, max_slots) {}
+    explicit DenseGraphAhSpace(int n, double p = 0.4, int max_slots = 128, bool wide = false) : DenseGraphSpace(n, p, max_slots), wide_(wide) {}
+    bool wide() const { return wide_; }
     void configure(azd_engine_config &cfg) const {
         DenseGraphSpace::configure(cfg);
-        cfg.flags |= AZD_ENGINE_DENSE_AH;
+        cfg.flags |= AZD_ENGINE_DENSE_AH | (wide_ ? AZD_ENGINE_DENSE_AH_WIDE : 0u);
     }
     // the cost of one connected graph on the host (adj: n neighbourhood bitsets): the device's procedure, bit for bit
     azd_dense_ah_cost_t cost(const uint64_t *adj) const {
         azd_dense_ah_cost_t c;
-        check(azd_dense_ah_cost(adj, n(), &c), "azd_dense_ah_cost");
+        if (wide_) check(azd_dense_ah_cost_wide(adj, n(), &c), "azd_dense_ah_cost_wide");
+        else check(azd_dense_ah_cost(adj, n(), &c), "azd_dense_ah_cost");
         return c;
     }
+
+private:
+    bool wide_;
 };
 
 // ---------------------------------------------------------------- models (NablaModel, nabla/model/mod.rs:4-8)
@@ -538,8 +545,17 @@ private:
         return r;
     }
     DenseAhArgmin argmin_of(const DenseGraphAhSpace &sp) {
+        if (sp.wide()) { // (the 64-row form's record: 64 neighbourhoods, 32 words of open slots)
+            azd_dense_ah_wide_argmin a;
+            check(azd_engine_dense_ah_wide_argmin_data(h_, &a), "argmin_data");
+            return dense_ah_argmin_from(a, sp);
+        }
         azd_dense_ah_argmin a;
         check(azd_engine_dense_ah_argmin_data(h_, &a), "argmin_data");
+        return dense_ah_argmin_from(a, sp);
+    }
+    template <class Rec>
+    static DenseAhArgmin dense_ah_argmin_from(const Rec &a, const DenseGraphAhSpace &sp) {
         DenseAhArgmin r;
         r.adj.assign(a.adj, a.adj + sp.n());
         r.permitted.assign(a.permitted, a.permitted + (sp.E() + 63) / 64);

@@ -18,7 +18,7 @@ import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
 SCRATCH_BUDGET = 512  # bytes per lane; the largest today is 368 (k_pool_search<DenseSpace<16>>)
-TREE_TUS = ("tree_kernels", "async_kernels", "pool_kernels", "ramsey_kernels", "ramsey_async_kernels", "ramsey_pool_kernels", "ramsey64_kernels", "dense_kernels", "dense_ah_kernels",
+TREE_TUS = ("tree_kernels", "async_kernels", "pool_kernels", "ramsey_kernels", "ramsey_async_kernels", "ramsey_pool_kernels", "ramsey64_kernels", "dense_kernels", "dense_ah_kernels", "dense_ah_wide_kernels",
             "ramsey_ext_kernels", "ramsey64_ext_kernels")
 
 
