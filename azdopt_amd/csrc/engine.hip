@@ -45,13 +45,15 @@ static int device_ok(int device) {
     return AZD_OK;
 }
 
-// the table of an engine's space and tier (space_ops.h): c21's and Ramsey's are put together from their three units' parts
+// the table of an engine's space and tier (space_ops.h): c21's and Ramsey's are put together from their units' parts (c21 has no
+// searcher-only pool step; the 64-bit Ramsey tier's is joined to the three parts of its phase unit's table)
 static const SpaceOps *space_ops(const Arenas &a) {
-    static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops()};
-    static const SpaceOps ramsey = {ramsey_phase_ops(), ramsey_async_ops(), ramsey_pool_ops()};
+    static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops(), PoolSearchOps{}};
+    static const SpaceOps ramsey = {ramsey_phase_ops(), ramsey_async_ops(), ramsey_pool_ops(), ramsey_pool_search_ops()};
+    static const SpaceOps ramsey64 = {ramsey64_ops(), ramsey64_ops(), ramsey64_ops(), ramsey64_pool_search_ops()};
     // (Arenas::lam_lo: c21's bracket; 1.0 marks an AH dense engine, 2.0 one with AZD_ENGINE_DENSE_AH_WIDE)
     if (a.space == SPACE_DENSE) return a.lam_lo == 2.0 ? &dense_ah_wide_ops() : a.lam_lo != 0.0 ? &dense_ah_ops() : &dense_ops();
-    if (a.space == SPACE_RAMSEY) return a.KW == RAMSEY_U64_KW ? &ramsey64_ops() : &ramsey;
+    if (a.space == SPACE_RAMSEY) return a.KW == RAMSEY_U64_KW ? &ramsey64 : &ramsey;
     return &c21;
 }
 
@@ -134,15 +136,11 @@ int azd_evaluator::ensure_staging(int batch) {
 }
 
 // ------------------------------------------------------------------ engine
-// The searcher-only pool step (ext_pool_run) of one kind of engine: the plan, launch and residency entries of its searcher kernel
-// (space_ops.h), how many wavefronts a workgroup of it may have, and the knobs and reason strings it goes by.  The evaluator's side
-// and the recovery of an aborted launch are the same for all of them.
+// The searcher-only pool step (ext_pool_run) of one kind of engine: the knobs, defaults and reason strings it goes by.  The searcher
+// kernel's plan, launch and residency entries and the wavefronts it is built for are the space's (SpaceOps: PoolSearchOps); the
+// evaluator's side and the recovery of an aborted launch are the same for all of them.
 struct ExtPoolForm {
-    bool (*plan)(const azd::Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
-    void (*launch)(const azd::Arenas &a, const azd::PersistArgs *d_args, const azd::StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
-                   size_t dyn_bytes, void *stream);
-    int (*resident)(const azd::Arenas &a, int waves, size_t dyn_bytes);
-    int waves_max, waves_min;  // wavefronts per searcher workgroup: the default (as many as the LDS holds, down to waves_min) and the knob's range
+    int waves_min, waves_knob_max; // the knob's range; without it a workgroup has PoolSearchOps::waves_max wavefronts, or as many as the LDS holds
     bool needs_pool_step;      // runs only where the engine's configured form is the pool step (dense); else the flag alone asks for it
     bool keep_quarter_free;    // also without a knob: at most CUs - CUs / 4 searcher workgroups
     int early_post;            // PoolArgs::early_post without AZD_POOL_EARLY_POST
@@ -150,50 +148,40 @@ struct ExtPoolForm {
     const char *env_off, *env_waves, *env_wgs, *env_streams, *env_rounds, *env_depth, *env_debug, *debug_tag;
     const char *e_waves_range, *r_not_configured, *r_failed_before, *r_needs_bf16, *r_no_wg, *r_aborted, *e_abort_hashed;
 };
-#define AZD_DENSE_EXT_FORM(PLAN, LAUNCH, RESIDENT)                                                                                         \
-    {PLAN, LAUNCH, RESIDENT, 16, 4, true, false, 1, 1, /* the request leaves with the row: the GEMMs run while the wave computes lambda_1 and the matching */ \
-     "AZD_DENSE_NO_POOL", "AZD_DENSE_POOL_WAVES", "AZD_DENSE_POOL_SEARCH_WGS", "AZD_DENSE_POOL_STREAMS", "AZD_DENSE_POOL_ROUNDS", "AZD_DENSE_POOL_DEPTH", \
-     "AZD_DENSE_POOL_DEBUG", "dense pool",                                                                                                 \
-     "AZD_DENSE_POOL_WAVES must be 4..16 (wavefronts per searcher workgroup of the dense-graph pool step)",                                \
-     "dense-graph space: the pool step is not configured for this engine",                                                                 \
-     "an earlier pool launch of this engine aborted: launch-per-phase form",                                                               \
-     "dense-graph space: the pool step needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",                 \
-     "dense-graph space: the device holds no searcher workgroup of the pool step",                                                         \
-     "dense pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "                        \
-     "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",                                    \
-     "dense pool step aborted with the test harness' prediction stream: no recovery"}
-// Ramsey tiers with max_slots > 0 under AZD_ENGINE_EXT_POOL_STEP.  Eight wavefronts per workgroup.  The request
-// leaves with the row (early post): there is no cost to compute behind it, but the tree's write-back and the wave's drain still
-// overlap with the evaluator's round (r3333 1.54 against 1.46 M expansions/s, r45 on the 64-bit tier 0.94 against 0.90).  Two
-// evaluator streams: the evaluator's rounds, not the searchers, bound these engines (its stream is busy 0.8-0.9 of a launch, a
-// searcher wave 0.1-0.2), and a second stream collects and runs its first layer while the first is in its later ones -- r45 on
-// the wide tier 1.26 -> 1.38 M, r3333 and r45 on the 64-bit tier +1..3 % (profiles/r09_ramsey_ext_pool.txt); the dense-graph
-// space, with a population ten times as large, measured the opposite.
-#define AZD_RAMSEY_EXT_FORM(PLAN, LAUNCH, RESIDENT, WAVES)                                                                                 \
-    {PLAN, LAUNCH, RESIDENT, WAVES, 1, false, true, 1, 2, nullptr, "AZD_RAMSEY_EXT_POOL_WAVES", "AZD_RAMSEY_EXT_POOL_SEARCH_WGS",              \
-     "AZD_RAMSEY_EXT_POOL_STREAMS", "AZD_RAMSEY_EXT_POOL_ROUNDS", "AZD_RAMSEY_EXT_POOL_DEPTH", "AZD_RAMSEY_EXT_POOL_DEBUG", "ramsey external pool", \
-     "AZD_RAMSEY_EXT_POOL_WAVES must be 1..8 (wavefronts per searcher workgroup of the external pool step)",                               \
-     "external pool step: not configured for this engine",                                                                                 \
-     "external pool step: an earlier launch of this engine aborted: launch-per-phase form",                                                \
-     "external pool step: needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",                              \
-     "external pool step: the device holds no searcher workgroup",                                                                         \
-     "external pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "                     \
-     "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",                                    \
-     "external pool step aborted with the test harness' prediction stream: no recovery"}
-// dense_ah: 0 the default cost, 1 AZD_ENGINE_DENSE_AH, 2 with AZD_ENGINE_DENSE_AH_WIDE beside it
-static const ExtPoolForm *ext_pool_form(int space, int dense_ah, bool ramsey_u64) {
-    static const ExtPoolForm dense = AZD_DENSE_EXT_FORM(azd::dense_pool_plan, azd::dense_launch_pool_search, azd::dense_pool_search_resident);
-    static const ExtPoolForm ah = AZD_DENSE_EXT_FORM(azd::dense_ah_pool_plan, azd::dense_ah_launch_pool_search, azd::dense_ah_pool_search_resident);
-    // (the same knobs and bounds: its plan takes at most the 6 wavefronts whose blocks a CU's LDS holds, dense_ah_wide_kernels.hip)
-    static const ExtPoolForm ah_wide = AZD_DENSE_EXT_FORM(azd::dense_ah_wide_pool_plan, azd::dense_ah_wide_launch_pool_search,
-                                                          azd::dense_ah_wide_pool_search_resident);
-    static const ExtPoolForm wide = AZD_RAMSEY_EXT_FORM(azd::ramsey_ext_pool_plan, azd::ramsey_ext_launch_pool_search,
-                                                        azd::ramsey_ext_pool_search_resident, azd::RAMSEY_EXT_WAVES);
-    static const ExtPoolForm u64 = AZD_RAMSEY_EXT_FORM(azd::ramsey64_ext_pool_plan, azd::ramsey64_ext_launch_pool_search,
-                                                       azd::ramsey64_ext_pool_search_resident, azd::RAMSEY64_EXT_WAVES);
-    static_assert(azd::RAMSEY_EXT_WAVES == 8 && azd::RAMSEY64_EXT_WAVES == 8, "AZD_RAMSEY_EXT_POOL_WAVES' range is spelled out in its error text");
-    if (space == azd::SPACE_DENSE) return dense_ah == 2 ? &ah_wide : dense_ah ? &ah : &dense;
-    return ramsey_u64 ? &u64 : &wide;
+static const ExtPoolForm *ext_pool_form(bool dense_space) {
+    // the dense-graph space, whatever its cost (the 64-row Aouchiche-Hansen cost has the same knobs and bounds: a setting above the 6
+    // wavefronts its kernels are built for runs what fits)
+    static const ExtPoolForm dense =
+        {4, 16, true, false, 1, 1, /* the request leaves with the row: the GEMMs run while the wave computes lambda_1 and the matching */
+         "AZD_DENSE_NO_POOL", "AZD_DENSE_POOL_WAVES", "AZD_DENSE_POOL_SEARCH_WGS", "AZD_DENSE_POOL_STREAMS", "AZD_DENSE_POOL_ROUNDS", "AZD_DENSE_POOL_DEPTH",
+         "AZD_DENSE_POOL_DEBUG", "dense pool",
+         "AZD_DENSE_POOL_WAVES must be 4..16 (wavefronts per searcher workgroup of the dense-graph pool step)",
+         "dense-graph space: the pool step is not configured for this engine",
+         "an earlier pool launch of this engine aborted: launch-per-phase form",
+         "dense-graph space: the pool step needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",
+         "dense-graph space: the device holds no searcher workgroup of the pool step",
+         "dense pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "
+         "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",
+         "dense pool step aborted with the test harness' prediction stream: no recovery"};
+    // Ramsey tiers with max_slots > 0 under AZD_ENGINE_EXT_POOL_STEP.  Eight wavefronts per workgroup.  The request
+    // leaves with the row (early post): there is no cost to compute behind it, but the tree's write-back and the wave's drain still
+    // overlap with the evaluator's round (r3333 1.54 against 1.46 M expansions/s, r45 on the 64-bit tier 0.94 against 0.90).  Two
+    // evaluator streams: the evaluator's rounds, not the searchers, bound these engines (its stream is busy 0.8-0.9 of a launch, a
+    // searcher wave 0.1-0.2), and a second stream collects and runs its first layer while the first is in its later ones -- r45 on
+    // the wide tier 1.26 -> 1.38 M, r3333 and r45 on the 64-bit tier +1..3 % (profiles/r09_ramsey_ext_pool.txt); the dense-graph
+    // space, with a population ten times as large, measured the opposite.
+    static const ExtPoolForm ramsey =
+        {1, 8, false, true, 1, 2, nullptr, "AZD_RAMSEY_EXT_POOL_WAVES", "AZD_RAMSEY_EXT_POOL_SEARCH_WGS",
+         "AZD_RAMSEY_EXT_POOL_STREAMS", "AZD_RAMSEY_EXT_POOL_ROUNDS", "AZD_RAMSEY_EXT_POOL_DEPTH", "AZD_RAMSEY_EXT_POOL_DEBUG", "ramsey external pool",
+         "AZD_RAMSEY_EXT_POOL_WAVES must be 1..8 (wavefronts per searcher workgroup of the external pool step)",
+         "external pool step: not configured for this engine",
+         "external pool step: an earlier launch of this engine aborted: launch-per-phase form",
+         "external pool step: needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",
+         "external pool step: the device holds no searcher workgroup",
+         "external pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "
+         "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",
+         "external pool step aborted with the test harness' prediction stream: no recovery"};
+    return dense_space ? &dense : &ramsey;
 }
 
 struct azd_engine {
@@ -979,7 +967,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         azd::c21_lambda_bracket(cfg->n, &a.lam_lo, &a.lam_hi);
     }
     e->ops = azd::space_ops(a);
-    if (dense || (cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) e->ext = ext_pool_form(a.space, dense_ah_wide ? 2 : dense_ah ? 1 : 0, e->ramsey_u64());
+    if (dense || (cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) e->ext = ext_pool_form(dense);
     e->ext_f32 = (cfg->flags & AZD_ENGINE_EXT_POOL_F32) != 0;
     a.S_inner = a.S;
     a.S = a.S_inner * a.layers; // Layered<L, Space>::STATE_DIM (nabla/space/mod.rs:53)
@@ -1483,7 +1471,7 @@ static int pool_finish_launch(azd_engine *e, const azd::FusedEval &fe, const azd
 // replayed from a graph on a second stream for as long as the searchers run.  Agents advance independently, so a launch no longer
 // lasts as long as its slowest agent per call (launch-per-phase form: a roll-out launch took 1.2 ms where the mean agent needed 0.06).
 // The Ramsey tiers with max_slots > 0 run the same form under AZD_ENGINE_EXT_POOL_STEP: what differs between the engines that have
-// it -- the searcher kernel's entries, its wavefronts per workgroup, knobs and reason strings -- comes from e->ext (ExtPoolForm).
+// it comes from e->ops (PoolSearchOps: the searcher kernel's entries and its wavefronts per workgroup) and e->ext (ExtPoolForm: knobs and reason strings).
 struct ExtPlan { // one roll-out of the form, as ext_plan decided it
     azd::Arenas a;     // what the searchers and the evaluator's graph see
     azd::FusedEval fe; // what the searchers look at
@@ -1518,13 +1506,13 @@ static int ext_plan(azd_engine *e, int n_calls, ExtPlan *out, bool *runs) {
     // wavefronts per searcher workgroup: 16, or as many as the LDS holds (roots of more than 640 slots: 12 -- a wave's block and its
     // selection scratch are 12 KB there)
     // (the Ramsey tiers: 8, the bound their kernels are built for -- every shape the tiers accept fits)
-    int waves = knob_int(xf.env_waves, xf.waves_max);
-    if (waves < xf.waves_min || waves > xf.waves_max) { // (round-4 verdict, 7c: a knob out of range is refused, not silently bent)
+    int waves = knob_int(xf.env_waves, e->ops->waves_max);
+    if (waves < xf.waves_min || waves > xf.waves_knob_max) { // (round-4 verdict, 7c: a knob out of range is refused, not silently bent)
         azd::g_last_error = xf.e_waves_range;
         return AZD_ERR_INVALID_ARGUMENT;
     }
     const bool knobs = getenv(xf.env_wgs) || getenv(xf.env_waves);
-    auto pool_plan = xf.plan;
+    auto pool_plan = e->ops->pool_search_plan;
     while (waves > xf.waves_min && !pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) waves -= 1;
     azd::FusedEval fe;
     const bool hashed = e->ev->fused_desc(&fe) && fe.kind == 4; // the test harness' fixed prediction stream, served like a model's rows
@@ -1537,7 +1525,7 @@ static int ext_plan(azd_engine *e, int n_calls, ExtPlan *out, bool *runs) {
                                                                                  : why;
         return AZD_OK;
     }
-    const int per_cu = xf.resident(a, waves, dyn_bytes);
+    const int per_cu = e->ops->pool_search_resident(a, waves, dyn_bytes);
     // searcher workgroups: no more waves than twice the agents, and no more than half the chip's wave slots -- the GEMM launches
     // need the rest
     int n_search = (2 * a.B + waves - 1) / waves;
@@ -1705,7 +1693,7 @@ static int ext_run_launches(azd_engine *e, const azd::TolTable &t, int n_calls, 
         for (int x = 0; x < xp.n_ext; ++x) AZD_HIP(hipStreamWaitEvent(e->ext_stream[x], e->ext_fork, 0)); // the first collect sees the cleared queues
         const azd::StepLaunch sl = step_launch(e, k, xp.pool.ctl, nullptr, xp.hashed);
         e->time_begin(0);
-        xf.launch(xp.a, e->d_pargs, sl, xp.n_search, xp.waves, xp.dyn_stride, xp.dyn_bytes, e->stream);
+        e->ops->launch_pool_search(xp.a, e->d_pargs, sl, xp.n_search, xp.waves, xp.dyn_stride, xp.dyn_bytes, e->stream);
 #ifndef AZD_PHASE_PROFILE
         e->counters_by_wave = true;
 #endif
@@ -3166,18 +3154,20 @@ int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *ld
     azd::Arenas a;
     memset(&a, 0, sizeof(a));
     a.space = ah_wide ? azd::SPACE_DENSE : azd::SPACE_RAMSEY;
+    if (ah_wide) a.lam_lo = 2.0; // (as azd_engine_create marks the engine for space_ops())
     a.n = cfg->n;
     a.B = cfg->batch;
     a.node_cap = cfg->node_capacity > 0 ? (uint32_t)cfg->node_capacity : 4096u;
     if (ah_wide) a.KW = dense_device_key_words(cfg->max_slots);
     else ramsey_shape(cfg, &a);
-    const ExtPoolForm *xf = ext_pool_form(a.space, ah_wide ? 2 : 0, a.KW == azd::RAMSEY_U64_KW);
+    const azd::SpaceOps *ops = azd::space_ops(a);
+    const ExtPoolForm *xf = ext_pool_form(ah_wide);
     const char *why = "";
     uint32_t dyn_stride = 0;
     size_t dyn_bytes = 0;
-    int w = xf->waves_max;
-    while (w > xf->waves_min && !xf->plan(a, w, &dyn_stride, &dyn_bytes, &why)) w -= 1;
-    if (!xf->plan(a, w, &dyn_stride, &dyn_bytes, &why)) {
+    int w = ops->waves_max;
+    while (w > xf->waves_min && !ops->pool_search_plan(a, w, &dyn_stride, &dyn_bytes, &why)) w -= 1;
+    if (!ops->pool_search_plan(a, w, &dyn_stride, &dyn_bytes, &why)) {
         azd::g_last_error = why;
         return AZD_ERR_UNSUPPORTED;
     }

@@ -1,7 +1,8 @@
 // launchers.inc -- host side of a search translation unit: the launcher templates, once for every space.  Included (inside
 // namespace azd) after tree_core.inc, the space policy and the step includes; a unit sees the launchers of the kernels it is built
 // with -- the phase units those of the launch-per-phase kernels, the root policy and the barrier step, the AZD_TU_ASYNC units
-// l_async, the AZD_TU_POOL units l_pool -- and builds the instantiations that its table entries (space_ops.h) name, no others.
+// l_async, the AZD_TU_POOL units l_pool, and beside any of these the AZD_TU_POOL_SEARCH units the searcher-only pool step's plan,
+// launch and residency query -- and builds the instantiations that its table entries (space_ops.h) name, no others.
 //
 // Dynamic LDS beyond the default 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize, which is per DEVICE (the current one): the
 // CU-resident launchers set it on every launch -- a host-side call, once per <= 1024 search calls -- so that engines on several
@@ -121,4 +122,88 @@ static void l_persist(const Arenas &a, const PersistArgs *d_args, const StepLaun
     }                                                                                                                                 \
     static void e_observe(const Arenas &a, uint32_t n_obs_tol, void *stream) { D(a, l_observe, a, n_obs_tol, (hipStream_t)stream); }
 #define AZD_PHASE_OPS e_init_roots, e_add_actions, e_rollout, e_argmin, e_argmin_log, e_observe, e_modify_roots
+// What the dense-graph units put in their tables for the forms they do not build: the space's state vector (3E + 1 floats) does not
+// fit the CU-resident forms' LDS plans, so it runs one launch per phase, or its searcher-only pool step (hence no run-ahead window)
+#define DENSE_NO_RESIDENT "dense-graph space: its CU-resident form is the pool searchers with the evaluator outside the kernel (engine.hip: dense_pool_run)"
+#define AZD_DENSE_NO_RESIDENT_ENTRIES                                                                                                 \
+    static void no_argmin_one(const Arenas &, int, uint32_t, void *) {}                                                               \
+    static bool no_resident(const Arenas &, const FusedEval &, uint32_t *, size_t *, const char **why) {                              \
+        *why = DENSE_NO_RESIDENT;                                                                                                     \
+        return false;                                                                                                                 \
+    }                                                                                                                                 \
+    static bool no_pool(const Arenas &, const FusedEval &, PoolArgs *, uint32_t *, size_t *, const char **why) {                      \
+        *why = DENSE_NO_RESIDENT;                                                                                                     \
+        return false;                                                                                                                 \
+    }
+#endif
+
+#if defined(AZD_TU_POOL_SEARCH)
+// ---------------------------------------------------------------- pool step, searchers only (pool_step.inc: k_pool_search<SP, MODE, WAVES>)
+// WAVES: the wavefronts per workgroup the unit's kernels are built and launch-bounded for.  The Ramsey tiers' (ramsey_ext_kernels.hip,
+// ramsey64_ext_kernels.hip; DESIGN.md section 3 says why eight):
+constexpr int RAMSEY_EXT_WAVES = 8, RAMSEY64_EXT_WAVES = 8;
+static_assert(RAMSEY_EXT_WAVES == 8 && RAMSEY64_EXT_WAVES == 8, "AZD_RAMSEY_EXT_POOL_WAVES' range is spelled out in its error text (engine.hip)");
+static_assert(sizeof(PoolIdle) <= POOL_SEARCH_STATIC_LDS, "space_ops.h: POOL_SEARCH_STATIC_LDS");
+template <int WAVES>
+struct PoolSearch { // (a class over WAVES, so that a unit's key-width switch can name its members as templates over SP alone)
+    // LDS of a searcher workgroup: WAVES blocks (the kernel's SW_BYTES), then a scratch region per wave that runs (no row is staged:
+    // SP::write_rows_direct).  Arithmetic only.  *bad: one of the unit's three refusals, or left as it was.
+    template <class SP>
+    static void plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **bad, const char *r_agents,
+                     const char *r_waves, const char *r_lds) {
+        if (a.B > 65536 || a.node_cap > 65536) { // (agent, node) are packed 16 + 16 bits in the argmin log
+            *bad = r_agents;
+            return;
+        }
+        const size_t stride = (SP::dyn_bytes(a) + 15) & ~(size_t)15;
+        const size_t sw_bytes = (WAVES * sizeof(typename SP::Lds) + 15) & ~(size_t)15;
+        *dyn_stride = (uint32_t)stride;
+        *dyn_bytes = sw_bytes + stride * (size_t)waves;
+        if (waves < 1 || waves > WAVES) *bad = r_waves;
+        else if (*dyn_bytes + sizeof(PoolIdle) + 256 > 160 * 1024) *bad = r_lds;
+    }
+    template <class SP>
+    static void launch(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
+                       size_t dyn_bytes, hipStream_t st) {
+        if (waves < 1 || waves > WAVES) return; // (the plan refuses it)
+        if (sl.hashed) { // the test harness' evaluator (FusedEval kind 4): the searchers note the call of every row they post
+            if (hipFuncSetAttribute((const void *)k_pool_search<SP, 1, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess) return;
+            k_pool_search<SP, 1, WAVES><<<dim3(n_blocks), dim3(waves * 64), dyn_bytes, st>>>(d_args, sl.n_calls, sl.log_key, dyn_stride);
+        } else {
+            if (hipFuncSetAttribute((const void *)k_pool_search<SP, 0, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess) return;
+            k_pool_search<SP, 0, WAVES><<<dim3(n_blocks), dim3(waves * 64), dyn_bytes, st>>>(d_args, sl.n_calls, sl.log_key, dyn_stride);
+        }
+        k_argmin_log1<SP><<<dim3(1), dim3(64), SP::dyn_bytes(a), st>>>(a, sl.n_calls, sl.log_key, sl.ctl);
+    }
+    template <class SP>
+    static void resident(int *out, int waves, size_t dyn_bytes) { // workgroups of the kernel one CU holds
+        int nb = 0;
+        if (waves < 1 || waves > WAVES ||
+            hipFuncSetAttribute((const void *)k_pool_search<SP, 0, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_pool_search<SP, 0, WAVES>, waves * 64, dyn_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            nb = 0;
+        }
+        *out = nb;
+    }
+};
+// A unit's PoolSearchOps (space_ops.h) for its key-width switch D, and its refusals: more than 65536 agents or nodes, more wavefronts
+// than WAVES, more LDS than a CU has.
+#define AZD_POOL_SEARCH_ENTRIES(D, WAVES, R_AGENTS, R_WAVES, R_LDS)                                                                   \
+    static bool e_pool_search_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why) {           \
+        const char *bad = nullptr;                                                                                                    \
+        D(a, PoolSearch<WAVES>::plan, a, waves, dyn_stride, dyn_bytes, &bad, R_AGENTS, R_WAVES, R_LDS);                               \
+        if (bad) *why = bad;                                                                                                          \
+        return bad == nullptr;                                                                                                        \
+    }                                                                                                                                 \
+    static void e_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves,       \
+                                     uint32_t dyn_stride, size_t dyn_bytes, void *stream) {                                           \
+        D(a, PoolSearch<WAVES>::launch, a, d_args, sl, n_blocks, waves, dyn_stride, dyn_bytes, (hipStream_t)stream);                  \
+    }                                                                                                                                 \
+    static int e_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes) {                                                 \
+        int nb = 0;                                                                                                                   \
+        D(a, PoolSearch<WAVES>::resident, &nb, waves, dyn_bytes);                                                                     \
+        return nb;                                                                                                                    \
+    }
+#define AZD_POOL_SEARCH_OPS(WAVES) e_pool_search_plan, e_launch_pool_search, e_pool_search_resident, WAVES
 #endif

@@ -1151,32 +1151,14 @@ __global__ __launch_bounds__(PERSIST_WAVES * 64) void k_pool(const PersistArgs *
 // (gemm_bf16_glds.inc: k_gemm16 with row lists) and k_ext_deliver (the agents go back on their ready queues).  The searchers'
 // grid leaves CUs free for those launches.  Rows and requests are written through (sc1) and a kernel's launch acquires, its end
 // releases: the same hand-off as inside k_pool, with a kernel boundary in place of the evaluator's polls.
-template <class SP, int MODE>
-__global__ __launch_bounds__(PERSIST_WAVES * 64) void k_pool_search(const PersistArgs *__restrict__ pa, int n_calls,
-                                                                    unsigned long long *__restrict__ log_key, uint32_t dyn_stride) {
-    constexpr uint32_t SW_BYTES = (uint32_t)((PERSIST_WAVES * sizeof(typename SP::Lds) + 15) & ~(size_t)15);
-    typename SP::Lds *const sw = reinterpret_cast<typename SP::Lds *>(lds_base(0u));
-    __shared__ PoolIdle idle;
-    const uint32_t xcc = pool_xcc_id();
-    if (threadIdx.x == 0) atomicCAS(&pa->pool.ctl->t_first, 0ull, (unsigned long long)wall_clock64());
-    const int wave = threadIdx.x >> 6;
-    typename SP::Lds &s = sw[wave];
-    if (threadIdx.x == 0) {
-        idle.leave = 0u;
-        idle.claims_done = 0u;
-        idle.mean_calls = 0u;
-    }
-    SP::prepare(pa->a, s);
-    if (LANE < NUM_COUNTERS) s.ctr[LANE] = 0;
-    __syncthreads();
-    pool_search<SP, MODE>(pa, n_calls, log_key, s, SW_BYTES + (uint32_t)wave * dyn_stride, xcc, idle, false);
-}
-// The same searchers for a space whose waves are too large for the layout above (the Ramsey tiers with max_slots > 0,
-// ramsey_ext.inc): WAVES wavefronts per workgroup at the most, WAVES static blocks -- sixteen RamseyU64Lds blocks are 79 KB before
-// any wave's clique counts -- and a launch bound of WAVES * 64 threads, so that eight waves may keep 256 registers each.
+// WAVES bounds a workgroup three ways: it lays out WAVES static blocks ahead of the waves' scratch regions (SW_BYTES, which the
+// host's plan repeats: launchers.inc), it is launch-bounded for WAVES * 64 threads, and hence sets the registers a wave may keep.
+// The dense-graph space launches it with PERSIST_WAVES, and fewer where a wave's block is large: six for the 64-row
+// Aouchiche-Hansen cost (20-KB blocks), eight for the Ramsey tiers with max_slots > 0 (ramsey_ext.inc) -- sixteen RamseyU64Lds
+// blocks are 79 KB before any wave's clique counts, and eight waves may keep 256 registers each.
 template <class SP, int MODE, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void k_pool_search_w(const PersistArgs *__restrict__ pa, int n_calls,
-                                                              unsigned long long *__restrict__ log_key, uint32_t dyn_stride) {
+__global__ __launch_bounds__(WAVES * 64) void k_pool_search(const PersistArgs *__restrict__ pa, int n_calls,
+                                                            unsigned long long *__restrict__ log_key, uint32_t dyn_stride) {
     constexpr uint32_t SW_BYTES = (uint32_t)((WAVES * sizeof(typename SP::Lds) + 15) & ~(size_t)15);
     typename SP::Lds *const sw = reinterpret_cast<typename SP::Lds *>(lds_base(0u));
     __shared__ PoolIdle idle;

@@ -34,7 +34,7 @@ static bool no_pool(const Arenas &, const FusedEval &, PoolArgs *, uint32_t *, s
     *why = RAMSEY_U64_NO_RESIDENT("pool step");
     return false;
 }
-const SpaceOps &ramsey64_ops() {
+const SpaceOps &ramsey64_ops() { // (the searcher-only part stays null here: ramsey64_ext_kernels.hip exports it, engine.hip joins the two)
     static const SpaceOps ops = {{AZD_PHASE_OPS, e_argmin_one, no_persist, nullptr}, {no_async, nullptr}, {no_pool, nullptr, nullptr}};
     return ops;
 }

@@ -1,6 +1,6 @@
-// ramsey_ext.inc -- the Ramsey side of the searcher-only pool step (AZD_ENGINE_EXT_POOL_STEP; pool_step.inc: k_pool_search_w, with
+// ramsey_ext.inc -- the Ramsey side of the searcher-only pool step (AZD_ENGINE_EXT_POOL_STEP; pool_step.inc: k_pool_search, with
 // the evaluator's batched GEMM launches outside the kernel, engine.hip: ext_pool_run): the space policies of the form and the
-// launchers of a unit that builds it.  Included inside namespace azd after space_ramsey.inc and pool_step.inc by
+// refusals of its plan.  Included inside namespace azd after space_ramsey.inc and pool_step.inc, ahead of launchers.inc, by
 // ramsey_ext_kernels.hip (32-bit wide tier) and ramsey64_ext_kernels.hip (64-bit tier), which say which policies they build.
 
 typedef float azd_f32x2 __attribute__((ext_vector_type(2)));
@@ -17,7 +17,6 @@ struct RamseyExtSpace : BASE {
     using St = typename BASE::St;
     using W = typename BASE::W;
     static constexpr bool ROWS_DIRECT = true;
-    static size_t pool_dyn_bytes(const Arenas &a) { return (BASE::dyn_bytes(a) + 15) & ~(size_t)15; }
     // the permitted edges as a bitmap the lanes can index: Lds::seq, which only the Layered wrapper uses (the tiers take none)
     static_assert(sizeof(Lds::seq) >= (size_t)BASE::PW * 8, "the permitted-edge bitmap must fit RamseyLdsT::seq");
 
@@ -106,49 +105,8 @@ struct RamseyExtSpace : BASE {
     }
 };
 
-// ---------------------------------------------------------------- host: plan, launch, residency of one policy
-static_assert(sizeof(PoolIdle) <= POOL_SEARCH_STATIC_LDS, "space_ops.h: POOL_SEARCH_STATIC_LDS");
-// LDS of a searcher workgroup: WAVES blocks (k_pool_search_w's SW_BYTES) and a region of scratch and clique counts per wave
-template <class SP, int WAVES>
-static bool rx_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why) {
-    if (a.B > 65536 || a.node_cap > 65536) {
-        *why = "external pool step: more than 65536 agents or nodes per tree";
-        return false;
-    }
-    if (waves < 1 || waves > WAVES) {
-        *why = "external pool step: more wavefronts per searcher workgroup than the kernel is built for";
-        return false;
-    }
-    const size_t stride = SP::pool_dyn_bytes(a);
-    const size_t sw_bytes = (WAVES * sizeof(typename SP::Lds) + 15) & ~(size_t)15;
-    *dyn_stride = (uint32_t)stride;
-    *dyn_bytes = sw_bytes + stride * (size_t)waves;
-    if (*dyn_bytes + sizeof(PoolIdle) + 256 > 160 * 1024) {
-        *why = "external pool step: the searcher waves' blocks, scratch and clique counts do not fit the CU's 160 KB of LDS";
-        return false;
-    }
-    return true;
-}
-template <class SP, int WAVES>
-static void rx_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
-                           size_t dyn_bytes, hipStream_t st) {
-    if (waves < 1 || waves > WAVES) return; // (the plan refuses it)
-    if (sl.hashed) { // the test harness' evaluator (FusedEval kind 4): the searchers note the call of every row they post
-        if (hipFuncSetAttribute((const void *)k_pool_search_w<SP, 1, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess) return;
-        k_pool_search_w<SP, 1, WAVES><<<dim3(n_blocks), dim3(waves * 64), dyn_bytes, st>>>(d_args, sl.n_calls, sl.log_key, dyn_stride);
-    } else {
-        if (hipFuncSetAttribute((const void *)k_pool_search_w<SP, 0, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess) return;
-        k_pool_search_w<SP, 0, WAVES><<<dim3(n_blocks), dim3(waves * 64), dyn_bytes, st>>>(d_args, sl.n_calls, sl.log_key, dyn_stride);
-    }
-    k_argmin_log1<SP><<<dim3(1), dim3(64), SP::dyn_bytes(a), st>>>(a, sl.n_calls, sl.log_key, sl.ctl);
-}
-template <class SP, int WAVES>
-static void rx_pool_search_resident(int *out, int waves, size_t dyn_bytes) {
-    int nb = 0;
-    if (hipFuncSetAttribute((const void *)k_pool_search_w<SP, 0, WAVES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_pool_search_w<SP, 0, WAVES>, waves * 64, dyn_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        nb = 0;
-    }
-    *out = nb;
-}
+// ---------------------------------------------------------------- host: the refusals of the tiers' plans (launchers.inc: PoolSearch)
+#define RAMSEY_EXT_POOL_SEARCH_ENTRIES(D, WAVES)                                                                                       \
+    AZD_POOL_SEARCH_ENTRIES(D, WAVES, "external pool step: more than 65536 agents or nodes per tree",                                  \
+                            "external pool step: more wavefronts per searcher workgroup than the kernel is built for",                 \
+                            "external pool step: the searcher waves' blocks, scratch and clique counts do not fit the CU's 160 KB of LDS")

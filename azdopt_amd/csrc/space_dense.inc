@@ -794,11 +794,18 @@ struct DenseSpace {
 };
 
 // host side: the key width (words of a rank set) follows the engine's max_slots: 2, 4, 10 or 16 (engine.hip)
-// (DenseSpace<KW> = DenseSpace<KW, DenseCostC21>; the AH engines' switch is dense_ah_kernels.hip's)
+// (DenseSpace<KW> = DenseSpace<KW, DenseCostC21>)
 #define DISPATCH_DKW(A, FN, ...)                                  \
     switch ((A).KW) {                                             \
     case 2: FN<DenseSpace<2>>(__VA_ARGS__); break;                \
     case 4: FN<DenseSpace<4>>(__VA_ARGS__); break;                \
     case 10: FN<DenseSpace<10>>(__VA_ARGS__); break;              \
     default: FN<DenseSpace<16>>(__VA_ARGS__); break;              \
+    }
+// ... and of an engine with another cost policy (key widths 2 / 4 / 10: dense_ah_kernels.hip, dense_ah_wide_kernels.hip)
+#define DISPATCH_DKW_COST(COST, A, FN, ...)                       \
+    switch ((A).KW) {                                             \
+    case 2: FN<DenseSpace<2, COST>>(__VA_ARGS__); break;          \
+    case 4: FN<DenseSpace<4, COST>>(__VA_ARGS__); break;          \
+    default: FN<DenseSpace<10, COST>>(__VA_ARGS__); break;        \
     }

@@ -1,14 +1,15 @@
 // space_ops.h -- what the host engine calls in the search translation units: one table of launchers and LDS plans per space
-// (SpaceOps; azd_engine_create picks it once), and the helpers that are the same for every space.  Everything is asynchronous
-// on `stream`.
+// and tier (SpaceOps, in four parts: launch-per-phase and barrier step, asynchronous step, pool step, searcher-only pool step;
+// azd_engine_create picks it once), and the helpers that are the same for every space.  Everything is asynchronous on `stream`.
 #pragma once
 #include "engine_types.h"
 
 namespace azd {
 
 // A *_plan lays out the LDS of a CU-resident step; when the model or the population does not fit, or the space does not build
-// the form, it returns false and says why in *why.  The launch entries of a form whose plan always refuses are null.
-struct PhaseOps { // a space's phase unit (tree_kernels.hip, ramsey_kernels.hip, ramsey64_kernels.hip, dense_kernels.hip)
+// the form, it returns false and says why in *why.  The launch entries of a form whose plan always refuses are null; a space
+// without the searcher-only pool step (c21) has that whole part null.
+struct PhaseOps { // a space's phase unit (tree_kernels.hip, ramsey_kernels.hip, ramsey64_kernels.hip, dense_kernels.hip and its AH siblings)
     void (*init_roots)(const Arenas &a, const uint8_t *d_roots, const uint64_t *d_permitted, void *stream);
     void (*add_actions)(const Arenas &a, int root_mode, void *stream);
     void (*rollout)(const Arenas &a, const TolTable &tol, void *stream);
@@ -40,16 +41,32 @@ struct PoolOps { // pool_kernels.hip, ramsey_pool_kernels.hip
     // searcher and evaluator workgroups spin-wait on each other, so all of them must be resident together
     int (*pool_max_resident)(const Arenas &a, size_t dyn_bytes, int n_cus);
 };
-struct SpaceOps : PhaseOps, AsyncOps, PoolOps {};
+struct PoolSearchOps { // the pool step with searcher workgroups only (pool_step.inc: k_pool_search; launchers.inc): the evaluator is a stream
+                       // of batched GEMM launches over the rows the searchers have posted (launch_ext_* below).  Null where a space has none.
+    // waves: wavefronts per searcher workgroup; the plan is arithmetic and touches no device
+    bool (*pool_search_plan)(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
+    void (*launch_pool_search)(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
+                               size_t dyn_bytes, void *stream);
+    int (*pool_search_resident)(const Arenas &a, int waves, size_t dyn_bytes); // workgroups of the kernel one CU holds
+    // the wavefronts the unit's kernels lay out blocks and are launch-bounded for; the plan refuses more, and more than the LDS holds
+    // (the engine counts down from here: 16 for the dense-graph space -- 10, 9 or 7 fit with the Aouchiche-Hansen cost --, 6 for that
+    // cost's 64-row form, 8 for the Ramsey tiers)
+    int waves_max;
+};
+struct SpaceOps : PhaseOps, AsyncOps, PoolOps, PoolSearchOps {};
 
 // what the units export: c21 and Ramsey (narrow and wide) build each form in a unit of its own, the 64-bit Ramsey tier and the
-// dense-graph space run one launch per phase and refuse the CU-resident forms in their tables
+// dense-graph space run one launch per phase and refuse the CU-resident forms in their tables; the dense-graph units build their
+// searcher-only pool step themselves, the Ramsey tiers with max_slots > 0 have it in units of their own (AZD_ENGINE_EXT_POOL_STEP:
+// ramsey_ext_kernels.hip the 32-bit wide tier, ramsey64_ext_kernels.hip the 64-bit tier)
 // (functions, not objects: a const object of a .hip file is compiled for the device too, where its entries do not exist)
 const PhaseOps &c21_phase_ops(), &ramsey_phase_ops();
 const AsyncOps &c21_async_ops(), &ramsey_async_ops();
 const PoolOps &c21_pool_ops(), &ramsey_pool_ops();
+const PoolSearchOps &ramsey_pool_search_ops(), &ramsey64_pool_search_ops();
 const SpaceOps &ramsey64_ops(), &dense_ops(), &dense_ah_ops(); // dense_ah_ops: DenseSpace with the Aouchiche-Hansen cost (dense_ah_kernels.hip)
 const SpaceOps &dense_ah_wide_ops();                            // ... with its 64-row form (dense_ah_wide_kernels.hip: AZD_ENGINE_DENSE_AH_WIDE)
+constexpr size_t POOL_SEARCH_STATIC_LDS = 16; // k_pool_search's static LDS (PoolIdle) beside the dynamic region the plans lay out
 
 // ---- the same for every space
 // launch-per-phase form over sub-populations on streams of their own (engine.hip): the candidates of agents a.t0 .. a.t0 + a.tn - 1
@@ -72,38 +89,9 @@ void launch_probe_ah_cost(const uint64_t *d_adj, int n, int count, int reps, Den
 void launch_probe_math_f64(const double *d_in, double *d_out, int n, void *stream);
 void launch_probe_ah_cost_wide(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream); // n <= 64 (dense_ah_wide_kernels.hip)
 
-// ---- pool step of the dense-graph space (dense_kernels.hip): searcher workgroups only (k_pool_search); the evaluator is a stream of
-// batched GEMM launches over the rows the searchers have posted, collected by k_ext_take and handed back by k_ext_deliver (pool_step.inc)
-bool dense_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
-void dense_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
-                              size_t dyn_bytes, void *stream);
-int dense_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
-// the same three for an AH dense engine (dense_ah_kernels.hip); the evaluator side and the recovery below serve both
-bool dense_ah_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
-void dense_ah_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
-                                 size_t dyn_bytes, void *stream);
-int dense_ah_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
-// ... and for an AZD_ENGINE_DENSE_AH_WIDE engine (dense_ah_wide_kernels.hip): k_pool_search_w with as many wavefronts as the LDS holds
-// of its 20-KB blocks (6); the plan refuses more, and touches no device
-bool dense_ah_wide_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
-void dense_ah_wide_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
-                                      size_t dyn_bytes, void *stream);
-int dense_ah_wide_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
-// the same three for the Ramsey tiers with max_slots > 0 under AZD_ENGINE_EXT_POOL_STEP (ramsey_ext_kernels.hip: the 32-bit wide tier;
-// ramsey64_ext_kernels.hip: the 64-bit tier).  waves <= *_EXT_WAVES, the wavefronts per workgroup their kernels are built and
-// launch-bounded for (k_pool_search_w; DESIGN.md section 3 says why eight).  The plans are arithmetic: they touch no device.
-constexpr int RAMSEY_EXT_WAVES = 8, RAMSEY64_EXT_WAVES = 8;
-constexpr size_t POOL_SEARCH_STATIC_LDS = 16; // k_pool_search_w's static LDS (PoolIdle) beside the dynamic region the plans lay out
-bool ramsey_ext_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
-void ramsey_ext_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
-                                   size_t dyn_bytes, void *stream);
-int ramsey_ext_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
-bool ramsey64_ext_pool_plan(const Arenas &a, int waves, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
-void ramsey64_ext_launch_pool_search(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, int n_blocks, int waves, uint32_t dyn_stride,
-                                     size_t dyn_bytes, void *stream);
-int ramsey64_ext_pool_search_resident(const Arenas &a, int waves, size_t dyn_bytes);
+// ---- the evaluator's side of the searcher-only pool step and the recovery of an aborted launch (dense_kernels.hip; for every space that has the form)
 void launch_ext_take(const PoolArgs &pool, uint32_t *rows, uint32_t *home, uint32_t *n, unsigned long long *t0, void *stream);
-// recovery of an aborted dense pool launch (engine.hip): park (round >= 0: the agents whose calls are through by that round; -1: the
+// recovery of an aborted launch (engine.hip): park (round >= 0: the agents whose calls are through by that round; -1: the
 // agents that are not waiting for a row) / unpark (mode 0), and the candidates of round r under the call each agent is really in
 void launch_park(const Arenas &a, const uint32_t *resume, int n_calls, int round, int park, void *stream);
 void launch_log_candidates_resume(const Arenas &a, unsigned long long *log_key, const uint32_t *resume, int n_calls, int round, void *stream);

@@ -8,7 +8,7 @@ the GPU.
     shape) with roots of up to 612 slots (key width 10).  Sizes are set by the Python side (an eigenproblem per node: 5 ms at
     n = 33, 25 ms at n = 64);
   * a wide engine at n = 20 and n = 31 against the narrow engine: trees, argmin, root-policy report, bit for bit;
-  * the pool step (k_pool_search_w, as many wavefronts as the LDS holds) against the launch-per-phase form at 256 agents for key
+  * the pool step (k_pool_search built for as many wavefronts as the LDS holds) against the launch-per-phase form at 256 agents for key
     widths 2, 4 and 10 at n = 40; with a bf16 model at n = 33; an fp32 model falls back with the dense pool step's reason;
   * the argmin record's reads and refusals; the example driver with --wide.
 Run with -m gpu on an MI355X."""

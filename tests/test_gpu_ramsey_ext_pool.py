@@ -1,5 +1,5 @@
 """GPU tests of the searcher-only pool step of the Ramsey tiers with max_slots > 0 (AZD_ENGINE_EXT_POOL_STEP; par_new(...,
-ext_pool_step=True)): persistent searcher workgroups of eight waves (k_pool_search_w over RamseyExtSpace), the evaluator a replayed
+ext_pool_step=True)): persistent searcher workgroups of eight waves (k_pool_search over RamseyExtSpace), the evaluator a replayed
 graph of take -> gathered bf16 GEMMs -> deliver beside them.  Its results are those of the launch-per-phase form bit for bit:
   * with the hash stream against the C++ oracle (r45 on both tiers) and against tests/ramsey64_ref.py (past 32 vertices: N = 33 with
     one searcher workgroup for twelve agents, and the reference's R(3,3,3,3) shape), what tests/test_gpu_ramsey64.py's run_parity
