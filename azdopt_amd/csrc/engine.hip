@@ -1,27 +1,9 @@
 // engine.hip -- host side of the C ABI (include/azdopt_amd.h): owns the device arenas,
 // sequences the kernels of one NablaOptimizer call on a HIP stream, copies results out.
 // No CPU fallback: every compute entry point needs a gfx950 device.
-#include <hip/hip_runtime.h>
-
-#include <dlfcn.h>
-
-#include <algorithm>
-#include <climits>
-#include <cstdio>
-#include <cstring>
-#include <functional>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "../../include/azdopt_amd.h"
-#include "c21_host.h"
-#include "engine_types.h"
-#include "evaluator.h"
-#include "space_ops.h"
+#include "engine_impl.h"
 
 namespace azd {
-
 thread_local std::string g_last_error;
 
 int hip_fail(hipError_t e, const char *what) {
@@ -31,7 +13,7 @@ int hip_fail(hipError_t e, const char *what) {
     return AZD_ERR_HIP;
 }
 
-static int device_ok(int device) {
+int device_ok(int device) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0) {
@@ -45,24 +27,81 @@ static int device_ok(int device) {
     return AZD_OK;
 }
 
-// the table of an engine's space and tier (space_ops.h): c21's and Ramsey's are put together from their units' parts (c21 has no
-// searcher-only pool step; the 64-bit Ramsey tier's is joined to the three parts of its phase unit's table)
-static const SpaceOps *space_ops(const Arenas &a) {
+// The searcher-only pool step's two forms (ExtPoolForm, engine_impl.h)
+static const ExtPoolForm *ext_pool_form(bool dense_space) {
+    // the dense-graph space, whatever its cost (the 64-row Aouchiche-Hansen cost has the same knobs and bounds: a setting above the 6
+    // wavefronts its kernels are built for runs what fits)
+    static const ExtPoolForm dense =
+        {4, 16, true, false, 1, 1, /* the request leaves with the row: the GEMMs run while the wave computes lambda_1 and the matching */
+         "AZD_DENSE_NO_POOL", "AZD_DENSE_POOL_WAVES", "AZD_DENSE_POOL_SEARCH_WGS", "AZD_DENSE_POOL_STREAMS", "AZD_DENSE_POOL_ROUNDS", "AZD_DENSE_POOL_DEPTH",
+         "AZD_DENSE_POOL_DEBUG", "dense pool",
+         "AZD_DENSE_POOL_WAVES must be 4..16 (wavefronts per searcher workgroup of the dense-graph pool step)",
+         "dense-graph space: the pool step is not configured for this engine",
+         "an earlier pool launch of this engine aborted: launch-per-phase form",
+         "dense-graph space: the pool step needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",
+         "dense-graph space: the device holds no searcher workgroup of the pool step",
+         "dense pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "
+         "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",
+         "dense pool step aborted with the test harness' prediction stream: no recovery"};
+    // Ramsey tiers with max_slots > 0 under AZD_ENGINE_EXT_POOL_STEP.  Eight wavefronts per workgroup (DESIGN.md section 3).  The request
+    // leaves with the row (early post): there is no cost to compute behind it, but the tree's write-back and the wave's drain still
+    // overlap with the evaluator's round (r3333 1.54 against 1.46 M expansions/s, r45 on the 64-bit tier 0.94 against 0.90).  Two
+    // evaluator streams: the evaluator's rounds, not the searchers, bound these engines (its stream is busy 0.8-0.9 of a launch, a
+    // searcher wave 0.1-0.2), and a second stream collects and runs its first layer while the first is in its later ones -- r45 on
+    // the wide tier 1.26 -> 1.38 M, r3333 and r45 on the 64-bit tier +1..3 % (profiles/r09_ramsey_ext_pool.txt); the dense-graph
+    // space, with a population ten times as large, measured the opposite.
+    static const ExtPoolForm ramsey =
+        {1, 8, false, true, 1, 2, nullptr, "AZD_RAMSEY_EXT_POOL_WAVES", "AZD_RAMSEY_EXT_POOL_SEARCH_WGS",
+         "AZD_RAMSEY_EXT_POOL_STREAMS", "AZD_RAMSEY_EXT_POOL_ROUNDS", "AZD_RAMSEY_EXT_POOL_DEPTH", "AZD_RAMSEY_EXT_POOL_DEBUG", "ramsey external pool",
+         "AZD_RAMSEY_EXT_POOL_WAVES must be 1..8 (wavefronts per searcher workgroup of the external pool step)",
+         "external pool step: not configured for this engine",
+         "external pool step: an earlier launch of this engine aborted: launch-per-phase form",
+         "external pool step: needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",
+         "external pool step: the device holds no searcher workgroup",
+         "external pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "
+         "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",
+         "external pool step aborted with the test harness' prediction stream: no recovery"};
+    return dense_space ? &dense : &ramsey;
+}
+
+// The seven kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
+// parts: c21 has no searcher-only pool step; the 64-bit Ramsey tier's is joined to the three parts of its phase unit's table.
+static const TierDesc *tier_desc(Tier t) {
     static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops(), PoolSearchOps{}};
     static const SpaceOps ramsey = {ramsey_phase_ops(), ramsey_async_ops(), ramsey_pool_ops(), ramsey_pool_search_ops()};
     static const SpaceOps ramsey64 = {ramsey64_ops(), ramsey64_ops(), ramsey64_ops(), ramsey64_pool_search_ops()};
-    // (Arenas::lam_lo: c21's bracket; 1.0 marks an AH dense engine, 2.0 one with AZD_ENGINE_DENSE_AH_WIDE)
-    if (a.space == SPACE_DENSE) return a.lam_lo == 2.0 ? &dense_ah_wide_ops() : a.lam_lo != 0.0 ? &dense_ah_ops() : &dense_ops();
-    if (a.space == SPACE_RAMSEY) return a.KW == RAMSEY_U64_KW ? &ramsey64 : &ramsey;
-    return &c21;
+    const ExtPoolForm *const xd = ext_pool_form(true), *const xr = ext_pool_form(false);
+    static const TierDesc tiers[TIER_COUNT] = {
+        {TIER_C21, SPACE_C21, &c21, nullptr, 0, 0, false, false, false, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr},
+        {TIER_RAMSEY, SPACE_RAMSEY, &ramsey, nullptr, sizeof(RamseyArgminRec), 128, false, false, false, AZD_RAMSEY_MAX_N, 256, 64 * MAX_KW, 0,
+         "unsupported Ramsey space (need 3 <= n, E <= 256, 2..4 colours, clique sizes 2..5, E*C <= 384)", nullptr, nullptr, nullptr},
+        // max_slots > 0: the most permitted edges a root may bring; device keys padded to the widths ramsey_kernels.hip is built for
+        {TIER_RAMSEY_WIDE, SPACE_RAMSEY, &ramsey, xr, sizeof(RamseyWideArgminRec), 128, true, true, false, AZD_RAMSEY_WIDE_MAX_N, 496, 1024, 0,
+         "unsupported wide Ramsey space (max_slots > 0: need 3 <= n <= 32, 2..4 colours, clique sizes 2..5, E*C <= 1024)",
+         "wide Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)", nullptr,
+         // (cur_seq holds MAX_NODE_ACTIONS actions; a wide path can be longer)
+         "wide Ramsey space (max_slots > 0): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)"},
+        // AZD_ENGINE_RAMSEY_U64: uint64_t neighbourhood rows of 64 vertices, keys of RAMSEY_U64_KW words, its own record
+        {TIER_RAMSEY_U64, SPACE_RAMSEY, &ramsey64, xr, sizeof(RamseyU64ArgminRec), 512, true, true, false, AZD_RAMSEY_U64_MAX_N, 2016,
+         64 * RAMSEY_U64_KW, AZD_RAMSEY_U64_NODE_ACTIONS,
+         "unsupported 64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64: need 3 <= n <= 64, 2..4 colours, clique sizes 2..5, E*C <= 2304)",
+         "64-bit Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)",
+         "64-bit Ramsey space: a node holds 512 actions: need max_slots * (C - 1) <= 512 (azd_engine_config::max_slots)",
+         "64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)"},
+        {TIER_DENSE, SPACE_DENSE, &dense_ops(), xd, sizeof(DenseArgminRec), 0, false, true, false, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr},
+        {TIER_DENSE_AH, SPACE_DENSE, &dense_ah_ops(), xd, sizeof(DenseAhArgminRec), 0, false, true, true, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr},
+        {TIER_DENSE_AH_WIDE, SPACE_DENSE, &dense_ah_wide_ops(), xd, sizeof(DenseAhWideArgminRec), 0, false, true, true, 0, 0, 0, 0, nullptr, nullptr,
+         nullptr, nullptr},
+    };
+    return &tiers[t];
 }
-
-// a status that is not AZD_OK ends the calling function (as AZD_HIP does for a HIP call)
-#define AZD_ST(call)            \
-    do {                        \
-        const int st_ = (call); \
-        if (st_) return st_;    \
-    } while (0)
+// the tier of a configuration that check_engine_config has accepted: the flags name it, never the sizes
+const TierDesc *engine_tier(const azd_engine_config *cfg) {
+    if (cfg->space_id == AZD_SPACE_DENSE)
+        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_AH_WIDE ? TIER_DENSE_AH_WIDE : cfg->flags & AZD_ENGINE_DENSE_AH ? TIER_DENSE_AH : TIER_DENSE);
+    if (cfg->space_id != AZD_SPACE_RAMSEY) return tier_desc(TIER_C21);
+    return tier_desc(cfg->flags & AZD_ENGINE_RAMSEY_U64 ? TIER_RAMSEY_U64 : cfg->max_slots != 0 ? TIER_RAMSEY_WIDE : TIER_RAMSEY);
+}
 
 // ------------------------------------------------------------------ simple evaluators
 struct TrivialEvaluator : azd_evaluator { // TrivialModel, model/mod.rs:10-23
@@ -135,283 +174,9 @@ int azd_evaluator::ensure_staging(int batch) {
     return AZD_OK;
 }
 
-// ------------------------------------------------------------------ engine
-// The searcher-only pool step (ext_pool_run) of one kind of engine: the knobs, defaults and reason strings it goes by.  The searcher
-// kernel's plan, launch and residency entries and the wavefronts it is built for are the space's (SpaceOps: PoolSearchOps); the
-// evaluator's side and the recovery of an aborted launch are the same for all of them.
-struct ExtPoolForm {
-    int waves_min, waves_knob_max; // the knob's range; without it a workgroup has PoolSearchOps::waves_max wavefronts, or as many as the LDS holds
-    bool needs_pool_step;      // runs only where the engine's configured form is the pool step (dense); else the flag alone asks for it
-    bool keep_quarter_free;    // also without a knob: at most CUs - CUs / 4 searcher workgroups
-    int early_post;            // PoolArgs::early_post without AZD_POOL_EARLY_POST
-    int streams;               // evaluator streams without the knob (<= azd_engine::EXT_STREAMS)
-    const char *env_off, *env_waves, *env_wgs, *env_streams, *env_rounds, *env_depth, *env_debug, *debug_tag;
-    const char *e_waves_range, *r_not_configured, *r_failed_before, *r_needs_bf16, *r_no_wg, *r_aborted, *e_abort_hashed;
-};
-static const ExtPoolForm *ext_pool_form(bool dense_space) {
-    // the dense-graph space, whatever its cost (the 64-row Aouchiche-Hansen cost has the same knobs and bounds: a setting above the 6
-    // wavefronts its kernels are built for runs what fits)
-    static const ExtPoolForm dense =
-        {4, 16, true, false, 1, 1, /* the request leaves with the row: the GEMMs run while the wave computes lambda_1 and the matching */
-         "AZD_DENSE_NO_POOL", "AZD_DENSE_POOL_WAVES", "AZD_DENSE_POOL_SEARCH_WGS", "AZD_DENSE_POOL_STREAMS", "AZD_DENSE_POOL_ROUNDS", "AZD_DENSE_POOL_DEPTH",
-         "AZD_DENSE_POOL_DEBUG", "dense pool",
-         "AZD_DENSE_POOL_WAVES must be 4..16 (wavefronts per searcher workgroup of the dense-graph pool step)",
-         "dense-graph space: the pool step is not configured for this engine",
-         "an earlier pool launch of this engine aborted: launch-per-phase form",
-         "dense-graph space: the pool step needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",
-         "dense-graph space: the device holds no searcher workgroup of the pool step",
-         "dense pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "
-         "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",
-         "dense pool step aborted with the test harness' prediction stream: no recovery"};
-    // Ramsey tiers with max_slots > 0 under AZD_ENGINE_EXT_POOL_STEP.  Eight wavefronts per workgroup (DESIGN.md section 3).  The request
-    // leaves with the row (early post): there is no cost to compute behind it, but the tree's write-back and the wave's drain still
-    // overlap with the evaluator's round (r3333 1.54 against 1.46 M expansions/s, r45 on the 64-bit tier 0.94 against 0.90).  Two
-    // evaluator streams: the evaluator's rounds, not the searchers, bound these engines (its stream is busy 0.8-0.9 of a launch, a
-    // searcher wave 0.1-0.2), and a second stream collects and runs its first layer while the first is in its later ones -- r45 on
-    // the wide tier 1.26 -> 1.38 M, r3333 and r45 on the 64-bit tier +1..3 % (profiles/r09_ramsey_ext_pool.txt); the dense-graph
-    // space, with a population ten times as large, measured the opposite.
-    static const ExtPoolForm ramsey =
-        {1, 8, false, true, 1, 2, nullptr, "AZD_RAMSEY_EXT_POOL_WAVES", "AZD_RAMSEY_EXT_POOL_SEARCH_WGS",
-         "AZD_RAMSEY_EXT_POOL_STREAMS", "AZD_RAMSEY_EXT_POOL_ROUNDS", "AZD_RAMSEY_EXT_POOL_DEPTH", "AZD_RAMSEY_EXT_POOL_DEBUG", "ramsey external pool",
-         "AZD_RAMSEY_EXT_POOL_WAVES must be 1..8 (wavefronts per searcher workgroup of the external pool step)",
-         "external pool step: not configured for this engine",
-         "external pool step: an earlier launch of this engine aborted: launch-per-phase form",
-         "external pool step: needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",
-         "external pool step: the device holds no searcher workgroup",
-         "external pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "
-         "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",
-         "external pool step aborted with the test harness' prediction stream: no recovery"};
-    return dense_space ? &dense : &ramsey;
-}
+namespace azd {
 
-struct azd_engine {
-    azd_engine_config cfg;
-    azd::Arenas a;
-    const azd::SpaceOps *ops = nullptr; // the launchers and LDS plans of the engine's space and tier (space_ops.h)
-    azd_evaluator *ev = nullptr;
-    hipStream_t stream = nullptr;
-    std::vector<void *> allocs;
-    uint8_t *d_stage_parents = nullptr;
-    uint64_t *d_stage_perm = nullptr;
-    azd::StatusRec *h_status = nullptr; // pinned
-    azd::ArgminRec *h_argmin = nullptr; // pinned
-    unsigned long long seen_improved = 0;
-    bool timing = false;
-    double rollout_ms = 0, evaluator_ms = 0;
-    uint64_t rollout_launches = 0;
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev_inflight; // kind 0 rollout, 1 evaluator
-    bool initialised = false;
-    // persistent (CU-resident) step
-    bool persist_enabled = true;
-    bool barrier_step = false;
-    azd::PersistArgs *d_pargs = nullptr;
-    azd::PersistArgs *h_pargs = nullptr; // pinned
-    azd::PersistArgs pargs_sent{};       // what d_pargs holds: the block is re-sent only when it changed
-    bool pargs_valid = false;
-    bool log_clean = false;              // d_log_key is all ones (k_argmin_log1 leaves it so; the barrier step and an abort do not)
-    bool pool_clean = false;             // PoolCtl, the queue slots and the join counters are zero (a completed pool launch leaves them so)
-    bool pool_failed = false;            // a pool launch aborted: this engine takes the asynchronous step from then on
-    bool counters_by_wave = false;       // a pool launch of the product build has run since the counters were cleared: the blocks of
-                                         // azd_engine_agent_counters then hold what searcher WAVES counted, not what agents did
-    uint32_t *d_resume = nullptr;        // [B] take-over of an aborted pool launch by k_async (StepLaunch::resume)
-    // evaluator groups of the pool step (PoolArgs::grp_*): device tables and per-slot exchange state, (re)built when the plan changes
-    int16_t *d_grp_tile = nullptr;
-    uint32_t *d_grp_lds = nullptr, *d_grp_desc = nullptr, *d_grp_cnt = nullptr, *d_grp_flag = nullptr;
-    size_t grp_flag_words = 0;
-    float *d_grp_x = nullptr;
-    size_t grp_x_floats = 0, grp_slots_alloc = 0;
-    std::vector<int16_t> grp_tile_host;  // what d_grp_tile holds (the plan is re-sent only when it changes)
-    std::vector<uint32_t> grp_lds_host;
-    unsigned long long *d_log_key = nullptr;
-    uint32_t *d_log_node = nullptr;
-    int log_calls = 0;
-    // launch-per-phase form: the five launches of a call captured once in a hipGraph and replayed per call
-    hipGraphExec_t call_graph = nullptr;
-    azd::TolTable call_graph_tol{};
-    uint64_t call_graph_layout = 0;
-    bool graph_enabled = true;
-    // launch-per-phase form over sub-populations, each on a stream of its own with its call captured in a graph: the kernels of
-    // one sub-population's call overlap the slowest agents of another's (a roll-out launch lasts as long as its slowest agent)
-    static constexpr int MAX_SUBS = 8;
-    hipStream_t sub_stream[MAX_SUBS] = {};
-    hipEvent_t sub_fork = nullptr, sub_join[MAX_SUBS] = {};
-    hipGraphExec_t sub_graph[MAX_SUBS] = {};
-    int sub_graph_n = 0;
-    uint32_t *d_call_ctr = nullptr; // [MAX_SUBS] calls a sub-population has logged in the current run
-    // pool step with the evaluator outside the kernel (dense-graph space): the searchers run on `stream`, the host replays a graph of
-    // [collect the posted rows, the model's GEMMs over them, hand the agents back] on ext_stream until the searchers are through
-    static constexpr int EXT_STREAMS = 2;    // evaluator streams: one collects and runs its first layer while the other is in its later ones
-    static constexpr int EXT_IN_FLIGHT = 4;  // ring size per stream; replays queued at a time per stream: ext_depth
-    hipStream_t ext_stream[EXT_STREAMS] = {};
-    hipGraphExec_t ext_graph[EXT_STREAMS] = {};
-    uint64_t ext_graph_layout = 0;
-    int ext_graph_n = 0;
-    bool ext_unsupported = false;     // the evaluator cannot serve gathered rows from device-side lists (asked once)
-    bool ext_f32 = false;             // AZD_ENGINE_EXT_POOL_F32: an fp32-storage evaluator serves the form's rows (write_predictions_gathered_f32)
-    uint64_t ext_unsupported_layout = 0; // ... under that flag: once per evaluator layout (a storage switch is asked again)
-    uint32_t *d_ext_rows = nullptr, *d_ext_home = nullptr, *d_ext_n = nullptr; // [EXT_STREAMS][B], [EXT_STREAMS][B], [EXT_STREAMS]
-    unsigned long long *d_ext_t0 = nullptr; // [EXT_STREAMS] when the batch in hand was collected (PoolCtl::eval_busy)
-    int ext_depth = 2;
-    hipEvent_t ext_done = nullptr, ext_fork = nullptr, ext_ring[EXT_STREAMS][EXT_IN_FLIGHT] = {};
-    unsigned long long ext_iterations = 0; // evaluator graph replays of the last dense pool launch (diagnostics)
-    // which searcher-only pool step this engine has (ExtPoolForm above): the dense-graph space's, or -- under
-    // AZD_ENGINE_EXT_POOL_STEP -- a Ramsey tier's; null: none.  A flagged Ramsey engine keeps the bf16 rows of the form HERE and
-    // not in Arenas::state_vecs16: only the form's own searchers write them (ramsey_ext.inc), so every evaluator call outside the
-    // replayed graph -- the first rows after par_new and a reset, the fallback forms, the completion of an aborted launch -- sees
-    // a null pointer and converts the f32 rows itself, as it does on an engine without the flag.
-    const struct ExtPoolForm *ext = nullptr;
-    uint16_t *ext_s16 = nullptr;
-    int ext_s16_pitch = 0;
-    // dense-graph / Ramsey space: host-visible key width (action-id sets); a wide Ramsey engine's device keys are wider (zero-padded)
-    int kw_host = 0;
-    int ramsey_slots = 0;             // Ramsey: the most permitted edges a root may bring (max_slots; else MAX_NODE_ACTIONS / (C - 1))
-    int dense_slots = 0;              // 64 * a.KW: the most modifiable slots a root may bring
-    uint64_t *d_stage_slots = nullptr; // device root policy: the slot masks it drew, [B][(E + 63) / 64] (dense-graph space; else d_stage_perm)
-    // device root policy (azd_engine_set_root_policy): the policy as set, as k_modify_roots takes it, and what its last launch
-    // reported per tree ([B][3] on the device; read back by the calls that launch it)
-    azd_root_policy root_policy{AZD_ROOT_RULE_THRESHOLD, 0, {0.0, 0.0, 0.0, 0.0}};
-    azd::RootPolicyArgs root_args{};
-    uint32_t *d_root_report = nullptr;
-    uint32_t *root_report = nullptr; // pinned [B][3]
-    bool root_report_valid = false;
-    std::vector<uint64_t> dense_packed;
-    std::vector<uint64_t> ramsey_perm_pad; // a wide Ramsey engine's roots: permitted masks padded to the device's a.KW words
-    // pool step (agents multiplexed over searcher waves, evaluator workgroups on CUs of their own)
-    bool pool_step = false;
-    azd::PoolArgs pool{};         // device pointers of the queues
-    size_t pool_slot_words = 0;
-    int n_cus = 0;
-    int pool_eval_wgs = 0, pool_search_wgs = 0; // of the last launch (diagnostics)
-    int pool_grp_g = 0, pool_grp_groups = 0, pool_grp_w = 0; // evaluator groups of the last pool launch (0: none)
-    int pool_search_waves = 0;                  // searching waves of the last launch
-    double pool_util_eval = 0, pool_util_search = 0; // busy share of the two sides in the last completed pool launch
-    // Measured feedback on the split (the fitted constants give the first guess only).  Every pool launch reports how busy its two
-    // sides were (PoolCtl::eval_busy / search_busy over the launch's span): the share of its time an evaluator workgroup spent
-    // on batches, u_e, and the share a searcher wave spent with an agent in hand, u_s.  Across splits u_e falls and u_s rises
-    // with the evaluators' share, and the best split of every workload measured sits where u_e - u_s is +0.00 .. +0.09
-    // (profiles/r03_pool_split.txt: configs A-D, 8192 agents fp32, a 384 x 384 model no sweep had seen), so the next launch
-    // moves the evaluators' share by 100 workgroups per unit of (u_e - u_s - target), target 0 .. 0.06 by how crowded the waves are.
-    struct {
-        int n_eval = 0; // what the next launch takes (0: the first guess)
-        int updates = 0; // launches the controller has acted on
-    } pool_fb;
-    // Run-ahead window (azd_engine_run_ahead): one pool launch of n calls is under way, or over, and par_roll_out_episodes hands
-    // its calls out one by one from what the kernel publishes (PoolArgs::win_*) instead of launching anything.
-    struct Window {
-        bool open = false;    // calls run ahead of the host are still to be handed out
-        bool drained = false; // the launch behind them is over and its status is in
-        bool lumped = false;  // the launch aborted: the calls the take-over completed were reported together
-        int n = 0, consumed = 0;
-        azd::TolTable tol{};
-        uint32_t best_ord = 0;                // order key of the best cost as of `consumed` calls
-        unsigned long long best_key = ~0ull;  // its log entry (all ones: still the record from before the window)
-        unsigned long long side_key = ~0ull;  // what the side argmin record holds
-        unsigned long long base_improved = 0; // StatusRec::improved when the window opened
-        unsigned long long reported = 0;      // improvements handed out from this window
-        azd::FusedEval fe{};
-        azd::PoolArgs pool{};
-    } win;
-    unsigned long long *h_win_log = nullptr; // pinned, host-coherent [log_calls]
-    uint32_t *h_win_flag = nullptr;          // pinned, host-coherent [log_calls]
-    azd::ArgminRec *d_argmin_side = nullptr; // the argmin record as of a call inside the window (k_argmin_one)
-    azd::RamseyArgminRec *d_argmin_r_side = nullptr;
-    // a wide Ramsey engine's kernels write azd::RamseyWideArgminRec where argmin_r points: records of the narrow type it spans
-    bool ramsey_wide() const { return a.space == azd::SPACE_RAMSEY && a.KW > azd::MAX_KW; }
-    // the 64-bit tier (AZD_ENGINE_RAMSEY_U64): uint64_t neighbourhood rows of 64 vertices, keys of RAMSEY_U64_KW words, its own record
-    bool dense_ah() const { return a.space == azd::SPACE_DENSE && a.lam_lo != 0.0; } // AZD_ENGINE_DENSE_AH
-    bool dense_ah_wide() const { return a.space == azd::SPACE_DENSE && a.lam_lo == 2.0; } // ... with AZD_ENGINE_DENSE_AH_WIDE: 64 rows, its own record
-    bool ramsey_u64() const { return a.space == azd::SPACE_RAMSEY && a.KW == azd::RAMSEY_U64_KW; }
-    size_t ramsey_nbr_words() const { return ramsey_u64() ? 512 : 128; } // uint32_t words of an agent's [4][NV] rows
-    size_t argmin_r_bytes() const {
-        return ramsey_u64() ? sizeof(azd::RamseyU64ArgminRec) : ramsey_wide() ? sizeof(azd::RamseyWideArgminRec) : sizeof(azd::RamseyArgminRec);
-    }
-    size_t argmin_r_recs() const { return (argmin_r_bytes() + sizeof(azd::RamseyArgminRec) - 1) / sizeof(azd::RamseyArgminRec); }
-    float *d_pool = nullptr;      // pooled training triple of all ranks (azd_engine_par_update_model_sharded)
-    size_t pool_rows = 0;
-    int step_form = 0;            // AZD_STEP_* chosen by the last par_roll_out_episodes
-    std::string step_reason;      // why the faster forms were not taken ("" if the asynchronous step ran)
-
-    template <typename T>
-    int alloc(T **p, size_t count) {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, count * sizeof(T));
-        if (e != hipSuccess) return azd::hip_fail(e, "hipMalloc");
-        allocs.push_back(q);
-        *p = (T *)q;
-        return AZD_OK;
-    }
-    hipEvent_t get_event() {
-        if (!ev_pool.empty()) {
-            hipEvent_t e = ev_pool.back();
-            ev_pool.pop_back();
-            return e;
-        }
-        hipEvent_t e;
-        (void)hipEventCreate(&e);
-        return e;
-    }
-    void time_begin(int kind) {
-        if (!timing) return;
-        hipEvent_t b = get_event(), en = get_event();
-        (void)hipEventRecord(b, stream);
-        ev_inflight.push_back({kind, {b, en}});
-    }
-    void time_end() {
-        if (!timing) return;
-        (void)hipEventRecord(ev_inflight.back().second.second, stream);
-    }
-    void time_collect() { // after a stream sync
-        for (auto &it : ev_inflight) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, it.second.first, it.second.second);
-            if (it.first == 0) {
-                rollout_ms += ms;
-                rollout_launches += 1;
-            } else evaluator_ms += ms;
-            ev_pool.push_back(it.second.first);
-            ev_pool.push_back(it.second.second);
-        }
-        ev_inflight.clear();
-    }
-};
-
-static int window_close(azd_engine *e);
-// Entry of every call that changes or reads what a running launch works on: the device is selected and a run-ahead window, if
-// one is open, is closed first (its launch is waited for; calls not yet handed out have run and stay run).
-#define AZD_ENTER(e)                                \
-    do {                                            \
-        AZD_HIP(hipSetDevice((e)->cfg.device));     \
-        if ((e)->win.open) {                        \
-            const int st_w_ = window_close(e);      \
-            if (st_w_) return st_w_;                \
-        }                                           \
-    } while (0)
-
-namespace {
-
-using namespace azd;
-
-uint32_t host_ordf(float f) { // tree_core.inc ordf
-    f = f + 0.0f;
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// Environment knobs: a positive integer overrides the default (knob_pos), or any integer does (knob_int).
-static constexpr int KNOB_UNSET = INT_MIN; // as a default: "the knob is not set", where the default is worked out later
-static int knob_pos(const char *name, int dflt) {
-    const char *env = getenv(name);
-    return env && atoi(env) > 0 ? atoi(env) : dflt;
-}
-static int knob_int(const char *name, int dflt) {
-    const char *env = getenv(name);
-    return env ? atoi(env) : dflt;
-}
-bool pool_feedback_on() { return knob_int("AZD_POOL_FEEDBACK", 1) != 0; }
-
-int next_pow2(int v) {
+static int next_pow2(int v) {
     int p = 128;
     while (p < v) p <<= 1;
     return p;
@@ -452,7 +217,7 @@ int report_improved(azd_engine *e, int st, int *improved) {
 // dense-graph space: check the roots and hand the device what it works with -- the modifiable slots ranked by ACTION ID
 // (Add(e) = e for an absent edge, Delete(e) = E + e for a present one: adds first, each group ascending), as a
 // rank -> action id table, and the mask of ranks still open (all k of them)
-int upload_dense_roots(azd_engine *e, const uint8_t *adj_bytes, const uint64_t *slots) {
+static int upload_dense_roots(azd_engine *e, const uint8_t *adj_bytes, const uint64_t *slots) {
     const Arenas &a = e->a;
     const int n = a.n, E = a.E, KWH = e->kw_host, KW = a.KW, MAXS = e->dense_slots;
     const size_t per = (size_t)17 * KW; // [rank mask: KW words][rank -> action id: 64 KW x u16]
@@ -515,7 +280,7 @@ int upload_dense_roots(azd_engine *e, const uint8_t *adj_bytes, const uint64_t *
     return AZD_OK;
 }
 
-int upload_roots(azd_engine *e, const uint8_t *parents, const uint64_t *permitted) {
+static int upload_roots(azd_engine *e, const uint8_t *parents, const uint64_t *permitted) {
     const Arenas &a = e->a;
     if (a.space == SPACE_DENSE) return upload_dense_roots(e, parents, permitted);
     if (a.space == SPACE_RAMSEY) {
@@ -543,8 +308,8 @@ int upload_roots(azd_engine *e, const uint8_t *parents, const uint64_t *permitte
                 }
                 cnt += __builtin_popcountll(m);
             }
-            if (e->ramsey_wide() ? cnt > e->ramsey_slots : cnt * (a.C - 1) > MAX_NODE_ACTIONS) {
-                g_last_error = e->ramsey_wide() ? "more permitted edges than azd_engine_config::max_slots" : "more permitted actions than a node can hold";
+            if (e->tier->cap_from_slots ? cnt > e->ramsey_slots : cnt * (a.C - 1) > MAX_NODE_ACTIONS) {
+                g_last_error = e->tier->cap_from_slots ? "more permitted edges than azd_engine_config::max_slots" : "more permitted actions than a node can hold";
                 return AZD_ERR_INVALID_ARGUMENT;
             }
         }
@@ -595,15 +360,125 @@ int run_evaluator(azd_engine *e) {
     return st;
 }
 
-int fill_tol(TolTable &t, const uint32_t *tol, int n_tol, uint32_t dflt) {
-    if (n_tol < 0 || n_tol > MAX_TOL || (n_tol > 0 && !tol)) return AZD_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < MAX_TOL; ++i) t.tol[i] = i < n_tol ? tol[i] : dflt;
-    t.n_tol = n_tol;
-    t.tol_default = dflt;
+// The argument checks of azd_engine_create, before the device is touched (azd_debug_ext_pool_plan runs them too)
+static int refuse(const char *why) {
+    g_last_error = why;
+    return AZD_ERR_INVALID_ARGUMENT;
+}
+// ... of a Ramsey configuration, against its tier's limits
+static int check_ramsey_config(const azd_engine_config *cfg, const TierDesc &t) {
+    bool ok = cfg->batch > 0 && cfg->n >= 3 && cfg->n <= t.max_n && cfg->n_colors >= 2 && cfg->n_colors <= 4;
+    if (ok) {
+        for (int c = 0; c < cfg->n_colors; ++c) ok = ok && cfg->clique_sizes[c] >= 2 && cfg->clique_sizes[c] <= 5;
+        ok = ok && ramsey_edges(cfg->n) <= t.max_edges && ramsey_action_dim(cfg->n, cfg->n_colors) <= t.max_actions;
+    }
+    if (!ok) return refuse(t.e_range);
+    if (!t.cap_from_slots) return AZD_OK;
+    if (cfg->max_slots < 1 || cfg->max_slots > ramsey_edges(cfg->n)) return refuse(t.e_slots);
+    if (t.node_actions && (long)cfg->max_slots * (cfg->n_colors - 1) > t.node_actions) return refuse(t.e_node_actions);
+    if (cfg->layers > 1 || cfg->path_kind != AZD_PATH_SET) return refuse(t.e_paths);
     return AZD_OK;
 }
+int check_engine_config(const azd_engine_config *cfg) {
+    const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
+    const bool dense = cfg->space_id == AZD_SPACE_DENSE;
+    const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
+    const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
+    if (dense_ah_wide) {
+        const char *bad = !dense_ah ? "flags: AZD_ENGINE_DENSE_AH_WIDE is valid only beside AZD_ENGINE_DENSE_AH (the Aouchiche-Hansen cost whose 64-row form it asks for)"
+                          : !dense  ? "space_id: AZD_ENGINE_DENSE_AH_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
+                          : cfg->n < 4 || cfg->n > AZD_DENSE_AH_WIDE_MAX_N ? "n: the wide Aouchiche-Hansen cost needs 4 <= n <= 64 (AZD_DENSE_AH_WIDE_MAX_N)"
+                          : cfg->layers > 1 ? "layers: AZD_ENGINE_DENSE_AH_WIDE engines take no Layered wrapper (layers <= 1)"
+                          : cfg->path_kind != AZD_PATH_SET ? "path_kind: AZD_ENGINE_DENSE_AH_WIDE engines keep ActionSet paths (AZD_PATH_SET)"
+                          : cfg->max_slots > std::min(dense_edges(cfg->n), 640)
+                              ? "max_slots: AZD_ENGINE_DENSE_AH_WIDE needs max_slots <= min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)"
+                              : nullptr;
+        if (bad) return refuse(bad);
+    } else if (dense_ah) {
+        const char *bad = !dense                                                  ? "space_id: AZD_ENGINE_DENSE_AH needs the dense-graph space (AZD_SPACE_DENSE)"
+                          : cfg->n < 4 || cfg->n > AZD_DENSE_AH_MAX_N             ? "n: the Aouchiche-Hansen cost needs 4 <= n <= 32 (AZD_DENSE_AH_MAX_N)"
+                          : cfg->layers > 1                                       ? "layers: AZD_ENGINE_DENSE_AH engines take no Layered wrapper (layers <= 1)"
+                          : cfg->max_slots > dense_edges(cfg->n)                  ? "max_slots: AZD_ENGINE_DENSE_AH needs max_slots <= E = n (n - 1) / 2"
+                          : cfg->path_kind != AZD_PATH_SET                        ? "path_kind: AZD_ENGINE_DENSE_AH engines keep ActionSet paths (AZD_PATH_SET)"
+                                                                                  : nullptr;
+        if (bad) return refuse(bad);
+    }
+    if (dense) {
+        if (cfg->n < 4 || cfg->n > AZD_DENSE_MAX_N || cfg->batch <= 0 || cfg->layers > 1 || cfg->max_slots < 0 || cfg->max_slots > AZD_DENSE_MAX_SLOTS ||
+            !(cfg->dense_p >= 0.f && cfg->dense_p <= 1.f))
+            return refuse("unsupported dense-graph space (need 4 <= n <= 64, no Layered wrapper, max_slots <= 1024, 0 <= dense_p <= 1)");
+    } else if (cfg->flags & AZD_ENGINE_RAMSEY_U64) { // the 64-bit tier: asked for by name, never chosen from the sizes
+        if (!ramsey || cfg->max_slots == 0) return refuse("AZD_ENGINE_RAMSEY_U64 needs a Ramsey space (AZD_SPACE_RAMSEY) with max_slots > 0");
+        AZD_ST(check_ramsey_config(cfg, *tier_desc(TIER_RAMSEY_U64)));
+    } else if (ramsey) { // (max_slots != 0: wide)
+        AZD_ST(check_ramsey_config(cfg, *tier_desc(cfg->max_slots != 0 ? TIER_RAMSEY_WIDE : TIER_RAMSEY)));
+    } else if (cfg->space_id != AZD_SPACE_C21 || cfg->n < 4 || cfg->n > AZD_C21_MAX_N || cfg->batch <= 0) {
+        return refuse("unsupported space / n / batch");
+    }
+    if (cfg->layers < 0 || cfg->layers > 8) return refuse("layers must be 0/1 (plain space) or 2..8");
+    if (cfg->path_kind != AZD_PATH_SET && cfg->path_kind != AZD_PATH_SEQUENCE) return refuse("unknown path encoding");
+    // the searcher-only pool step of the Ramsey tiers with max_slots > 0: asked for by name, never chosen from the sizes
+    if (cfg->flags & AZD_ENGINE_EXT_POOL_STEP) {
+        const char *bad = !ramsey || cfg->max_slots <= 0 ? "AZD_ENGINE_EXT_POOL_STEP needs a Ramsey space (AZD_SPACE_RAMSEY) with max_slots > 0 (the wide or the 64-bit tier)"
+                          : (cfg->flags & AZD_ENGINE_NO_PERSISTENT_STEP)
+                              ? "AZD_ENGINE_EXT_POOL_STEP is a CU-resident step form: it cannot be combined with AZD_ENGINE_NO_PERSISTENT_STEP"
+                              : nullptr;
+        if (bad) return refuse(bad);
+    }
+    // ... and its fp32 evaluator: a second flag beside the first, never a form of its own
+    if ((cfg->flags & AZD_ENGINE_EXT_POOL_F32) && !(cfg->flags & AZD_ENGINE_EXT_POOL_STEP))
+        return refuse("AZD_ENGINE_EXT_POOL_F32 is valid only beside AZD_ENGINE_EXT_POOL_STEP (the searcher-only pool step whose fp32 evaluator it asks for)");
+    return AZD_OK;
+}
+// dense-graph space, device keys: ranks of the root's modifiable slots, in 2 / 4 / 10 / 16 words (the widths dense_kernels.hip is built for)
+static int dense_device_key_words(int max_slots) {
+    const int ms = max_slots > 0 ? max_slots : 128;
+    return ms <= 128 ? 2 : ms <= 256 ? 4 : ms <= 640 ? 10 : 16;
+}
+// The shape part of an engine's arenas -- what the LDS plans and the allocations read -- for a configuration that check_engine_config
+// has accepted.  Everything else in *a is zeroed.
+void engine_shape(const azd_engine_config *cfg, const TierDesc *t, Arenas *ap) {
+    Arenas &a = *ap;
+    memset(&a, 0, sizeof(a));
+    a.n = cfg->n;
+    a.B = cfg->batch;
+    a.space = t->space;
+    a.path_kind = cfg->path_kind;
+    a.layers = cfg->layers > 1 ? cfg->layers : 1;
+    if (t->space == SPACE_DENSE) {
+        a.E = dense_edges(cfg->n);
+        a.A = dense_action_dim(cfg->n);
+        a.S = dense_state_dim(cfg->n);
+        a.KW = dense_device_key_words(cfg->max_slots); // (an AH engine: key widths 2, 4 and 10 only: max_slots <= E <= 496)
+        a.dense_p24 = (uint32_t)((cfg->dense_p > 0.f ? (double)cfg->dense_p : 0.2) * 16777216.0 + 0.5);
+        a.eval_slope = t->ah ? dense_ah_eval_slope(cfg->n) : c21_eval_slope(cfg->n);
+    } else if (t->space == SPACE_RAMSEY) {
+        a.C = cfg->n_colors;
+        a.E = ramsey_edges(cfg->n);
+        a.A = ramsey_action_dim(cfg->n, a.C);
+        a.S = ramsey_state_dim(cfg->n, a.C);
+        a.KW = ramsey_key_words(cfg->n, a.C);
+        if (t->padded_keys) a.KW = t->id == TIER_RAMSEY_U64 ? RAMSEY_U64_KW : a.A <= 640 ? 10 : 16; // RamseyWideSpace<10 / 16>; one width for the 64-bit tier
+        for (int c = 0; c < a.C; ++c) {
+            a.sizes[c] = cfg->clique_sizes[c];
+            a.cweights[c] = cfg->color_weights[c];
+        }
+    } else {
+        a.A = c21_action_dim(cfg->n);
+        a.S = c21_state_dim(cfg->n);
+        a.KW = c21_key_words(cfg->n);
+        a.eval_slope = c21_eval_slope(cfg->n);
+        c21_lambda_bracket(cfg->n, &a.lam_lo, &a.lam_hi);
+    }
+    a.S_inner = a.S;
+    a.S = a.S_inner * a.layers; // Layered<L, Space>::STATE_DIM (nabla/space/mod.rs:53)
+    a.node_cap = cfg->node_capacity > 0 ? (uint32_t)cfg->node_capacity : 4096u;
+    a.arc_cap = cfg->arc_capacity > 0 ? (uint32_t)cfg->arc_capacity : 8192u;
+    a.pred_cap = cfg->prediction_capacity > 0 ? (uint32_t)cfg->prediction_capacity : 32768u;
+    a.ht_cap = (uint32_t)next_pow2((int)(2 * a.node_cap));
+}
 
-} // namespace
+} // namespace azd
 
 extern "C" {
 
@@ -750,28 +625,6 @@ int azd_evaluator_update_model_dev(azd_evaluator *ev, int batch, const float *d_
     AZD_HIP(hipSetDevice(ev->device));
     return ev->update_model_dev(batch, d_states, d_observations, d_action_weights, loss, (hipStream_t)stream);
 }
-int azd_debug_mlp_gradients(azd_evaluator *ev, int batch, const float *states, const float *observations, const float *action_weights,
-                            float *grads_out, float *loss) {
-    if (!ev || batch <= 0 || !states || !observations || !action_weights || !grads_out) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ST(ev->ensure_staging(batch));
-    size_t sb = (size_t)batch * ev->state_dim * 4, pb = (size_t)batch * ev->action_dim * 4;
-    AZD_HIP(hipMemcpyAsync(ev->d_states, states, sb, hipMemcpyHostToDevice, ev->own_stream));
-    AZD_HIP(hipMemcpyAsync(ev->d_obs, observations, pb, hipMemcpyHostToDevice, ev->own_stream));
-    AZD_HIP(hipMemcpyAsync(ev->d_w, action_weights, pb, hipMemcpyHostToDevice, ev->own_stream));
-    return ev->debug_gradients(batch, ev->d_states, ev->d_obs, ev->d_w, grads_out, loss, ev->own_stream);
-}
-int azd_debug_write_predictions_gathered(azd_evaluator *ev, int max_rows, const uint32_t *rows, int n_rows, const float *states, int n_state_rows,
-                                         float *predictions) {
-    if (!ev || max_rows < 1 || n_rows < 0 || n_rows > max_rows || (n_rows > 0 && !rows) || !states || n_state_rows < 1 || !predictions)
-        return AZD_ERR_INVALID_ARGUMENT;
-    for (int i = 0; i < n_rows; ++i)
-        if (rows[i] >= (uint32_t)n_state_rows) {
-            azd::g_last_error = "azd_debug_write_predictions_gathered: a row index is not below n_state_rows";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    return ev->debug_write_predictions_gathered(max_rows, rows, n_rows, states, n_state_rows, predictions);
-}
-int azd_debug_hash_stream_via_evaluators(azd_evaluator *ev, int on) { return ev ? ev->debug_serve_from_pool(on) : AZD_ERR_INVALID_ARGUMENT; }
 int azd_evaluator_set_weight_storage(azd_evaluator *ev, int dtype) { return ev ? ev->set_weight_storage(dtype) : AZD_ERR_INVALID_ARGUMENT; }
 int64_t azd_evaluator_num_params(azd_evaluator *ev) { return ev ? ev->num_params() : 0; }
 int azd_evaluator_get_params(azd_evaluator *ev, float *out) { return ev && out ? ev->get_params(out) : AZD_ERR_INVALID_ARGUMENT; }
@@ -779,207 +632,37 @@ int azd_evaluator_set_params(azd_evaluator *ev, const float *in) { return ev && 
 uint64_t azd_evaluator_calls(azd_evaluator *ev) { return ev ? ev->calls : 0; }
 
 // ------------------------------------------------------------------ engine ABI
-// The argument checks of azd_engine_create, before the device is touched (azd_debug_ext_pool_plan runs them too)
-static int check_engine_config(const azd_engine_config *cfg) {
-    const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
-    const bool dense = cfg->space_id == AZD_SPACE_DENSE;
-    const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
-    const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
-    if (dense_ah_wide) {
-        const char *bad = !dense_ah ? "flags: AZD_ENGINE_DENSE_AH_WIDE is valid only beside AZD_ENGINE_DENSE_AH (the Aouchiche-Hansen cost whose 64-row form it asks for)"
-                          : !dense  ? "space_id: AZD_ENGINE_DENSE_AH_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_AH_WIDE_MAX_N ? "n: the wide Aouchiche-Hansen cost needs 4 <= n <= 64 (AZD_DENSE_AH_WIDE_MAX_N)"
-                          : cfg->layers > 1 ? "layers: AZD_ENGINE_DENSE_AH_WIDE engines take no Layered wrapper (layers <= 1)"
-                          : cfg->path_kind != AZD_PATH_SET ? "path_kind: AZD_ENGINE_DENSE_AH_WIDE engines keep ActionSet paths (AZD_PATH_SET)"
-                          : cfg->max_slots > std::min(azd::dense_edges(cfg->n), 640)
-                              ? "max_slots: AZD_ENGINE_DENSE_AH_WIDE needs max_slots <= min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)"
-                              : nullptr;
-        if (bad) {
-            azd::g_last_error = bad;
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    } else if (dense_ah) {
-        const char *bad = !dense                                                  ? "space_id: AZD_ENGINE_DENSE_AH needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_AH_MAX_N             ? "n: the Aouchiche-Hansen cost needs 4 <= n <= 32 (AZD_DENSE_AH_MAX_N)"
-                          : cfg->layers > 1                                       ? "layers: AZD_ENGINE_DENSE_AH engines take no Layered wrapper (layers <= 1)"
-                          : cfg->max_slots > azd::dense_edges(cfg->n)             ? "max_slots: AZD_ENGINE_DENSE_AH needs max_slots <= E = n (n - 1) / 2"
-                          : cfg->path_kind != AZD_PATH_SET                        ? "path_kind: AZD_ENGINE_DENSE_AH engines keep ActionSet paths (AZD_PATH_SET)"
-                                                                                  : nullptr;
-        if (bad) {
-            azd::g_last_error = bad;
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    }
-    if (dense) {
-        if (cfg->n < 4 || cfg->n > AZD_DENSE_MAX_N || cfg->batch <= 0 || cfg->layers > 1 || cfg->max_slots < 0 || cfg->max_slots > AZD_DENSE_MAX_SLOTS ||
-            !(cfg->dense_p >= 0.f && cfg->dense_p <= 1.f)) {
-            azd::g_last_error = "unsupported dense-graph space (need 4 <= n <= 64, no Layered wrapper, max_slots <= 1024, 0 <= dense_p <= 1)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    } else if (cfg->flags & AZD_ENGINE_RAMSEY_U64) { // the 64-bit tier: asked for by name, never chosen from the sizes
-        if (!ramsey || cfg->max_slots == 0) {
-            azd::g_last_error = "AZD_ENGINE_RAMSEY_U64 needs a Ramsey space (AZD_SPACE_RAMSEY) with max_slots > 0";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-        bool ok = cfg->batch > 0 && cfg->n >= 3 && cfg->n <= AZD_RAMSEY_U64_MAX_N && cfg->n_colors >= 2 && cfg->n_colors <= 4;
-        if (ok) {
-            for (int c = 0; c < cfg->n_colors; ++c) ok = ok && cfg->clique_sizes[c] >= 2 && cfg->clique_sizes[c] <= 5;
-            ok = ok && azd::ramsey_action_dim(cfg->n, cfg->n_colors) <= 64 * azd::RAMSEY_U64_KW;
-        }
-        if (!ok) {
-            azd::g_last_error = "unsupported 64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64: need 3 <= n <= 64, 2..4 colours, clique sizes 2..5, E*C <= 2304)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-        if (cfg->max_slots < 1 || cfg->max_slots > azd::ramsey_edges(cfg->n)) {
-            azd::g_last_error = "64-bit Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-        if ((long)cfg->max_slots * (cfg->n_colors - 1) > AZD_RAMSEY_U64_NODE_ACTIONS) {
-            azd::g_last_error = "64-bit Ramsey space: a node holds 512 actions: need max_slots * (C - 1) <= 512 (azd_engine_config::max_slots)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-        if (cfg->layers > 1 || cfg->path_kind != AZD_PATH_SET) {
-            azd::g_last_error = "64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    } else if (ramsey && cfg->max_slots != 0) { // wide engine: max_slots = the most permitted edges a root may bring
-        bool ok = cfg->batch > 0 && cfg->n >= 3 && cfg->n <= AZD_RAMSEY_WIDE_MAX_N && cfg->n_colors >= 2 && cfg->n_colors <= 4;
-        if (ok) {
-            for (int c = 0; c < cfg->n_colors; ++c) ok = ok && cfg->clique_sizes[c] >= 2 && cfg->clique_sizes[c] <= 5;
-            ok = ok && azd::ramsey_action_dim(cfg->n, cfg->n_colors) <= 1024;
-        }
-        if (!ok) {
-            azd::g_last_error = "unsupported wide Ramsey space (max_slots > 0: need 3 <= n <= 32, 2..4 colours, clique sizes 2..5, E*C <= 1024)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-        if (cfg->max_slots < 1 || cfg->max_slots > azd::ramsey_edges(cfg->n)) {
-            azd::g_last_error = "wide Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-        if (cfg->layers > 1 || cfg->path_kind != AZD_PATH_SET) { // (cur_seq holds MAX_NODE_ACTIONS actions; a wide path can be longer)
-            azd::g_last_error = "wide Ramsey space (max_slots > 0): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    } else if (ramsey) {
-        bool ok = cfg->batch > 0 && cfg->n >= 3 && cfg->n <= AZD_RAMSEY_MAX_N && cfg->n_colors >= 2 && cfg->n_colors <= 4;
-        if (ok) {
-            for (int c = 0; c < cfg->n_colors; ++c) ok = ok && cfg->clique_sizes[c] >= 2 && cfg->clique_sizes[c] <= 5;
-            ok = ok && azd::ramsey_edges(cfg->n) <= 256 && azd::ramsey_key_words(cfg->n, cfg->n_colors) <= azd::MAX_KW;
-        }
-        if (!ok) {
-            azd::g_last_error = "unsupported Ramsey space (need 3 <= n, E <= 256, 2..4 colours, clique sizes 2..5, E*C <= 384)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    } else if (cfg->space_id != AZD_SPACE_C21 || cfg->n < 4 || cfg->n > AZD_C21_MAX_N || cfg->batch <= 0) {
-        azd::g_last_error = "unsupported space / n / batch";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (cfg->layers < 0 || cfg->layers > 8) {
-        azd::g_last_error = "layers must be 0/1 (plain space) or 2..8";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (cfg->path_kind != AZD_PATH_SET && cfg->path_kind != AZD_PATH_SEQUENCE) {
-        azd::g_last_error = "unknown path encoding";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    // the searcher-only pool step of the Ramsey tiers with max_slots > 0: asked for by name, never chosen from the sizes
-    if (cfg->flags & AZD_ENGINE_EXT_POOL_STEP) {
-        const char *bad = !ramsey || cfg->max_slots <= 0 ? "AZD_ENGINE_EXT_POOL_STEP needs a Ramsey space (AZD_SPACE_RAMSEY) with max_slots > 0 (the wide or the 64-bit tier)"
-                          : (cfg->flags & AZD_ENGINE_NO_PERSISTENT_STEP)
-                              ? "AZD_ENGINE_EXT_POOL_STEP is a CU-resident step form: it cannot be combined with AZD_ENGINE_NO_PERSISTENT_STEP"
-                              : nullptr;
-        if (bad) {
-            azd::g_last_error = bad;
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    }
-    // ... and its fp32 evaluator: a second flag beside the first, never a form of its own
-    if ((cfg->flags & AZD_ENGINE_EXT_POOL_F32) && !(cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) {
-        azd::g_last_error = "AZD_ENGINE_EXT_POOL_F32 is valid only beside AZD_ENGINE_EXT_POOL_STEP (the searcher-only pool step whose fp32 evaluator it asks for)";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    return AZD_OK;
-}
-// dense-graph space, device keys: ranks of the root's modifiable slots, in 2 / 4 / 10 / 16 words (the widths dense_kernels.hip is built for)
-static int dense_device_key_words(int max_slots) {
-    const int ms = max_slots > 0 ? max_slots : 128;
-    return ms <= 128 ? 2 : ms <= 256 ? 4 : ms <= 640 ? 10 : 16;
-}
-// what the LDS plans read of an engine's arenas, for a Ramsey configuration that check_engine_config has accepted
-static void ramsey_shape(const azd_engine_config *cfg, azd::Arenas *a) {
-    a->C = cfg->n_colors;
-    a->E = azd::ramsey_edges(cfg->n);
-    a->A = azd::ramsey_action_dim(cfg->n, a->C);
-    a->S = azd::ramsey_state_dim(cfg->n, a->C);
-    a->KW = azd::ramsey_key_words(cfg->n, a->C);
-    if (cfg->max_slots > 0) { // wide: the device keys padded to the widths ramsey_kernels.hip is built for (RamseyWideSpace<10 / 16>)
-        a->KW = a->A <= 640 ? 10 : 16;
-        if (cfg->flags & AZD_ENGINE_RAMSEY_U64) a->KW = azd::RAMSEY_U64_KW; // one width for the tier (ramsey64_kernels.hip)
-    }
-}
 int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evaluator *ev) {
     if (!out || !cfg) return AZD_ERR_INVALID_ARGUMENT;
     int st = check_engine_config(cfg);
     if (st) return st;
-    const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
-    const bool dense = cfg->space_id == AZD_SPACE_DENSE;
-    const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0;
-    const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0;
+    const TierDesc *const tier = engine_tier(cfg);
+    const bool ramsey = tier->space == azd::SPACE_RAMSEY, dense = tier->space == azd::SPACE_DENSE;
     AZD_ST(azd::device_ok(cfg->device));
     AZD_HIP(hipSetDevice(cfg->device));
     azd_engine *e = new (std::nothrow) azd_engine();
     if (!e) return AZD_ERR_OUT_OF_MEMORY;
     e->cfg = *cfg;
     e->ev = ev;
+    e->tier = tier;
+    e->ops = tier->ops;
     azd::Arenas &a = e->a;
-    memset(&a, 0, sizeof(a));
-    a.n = cfg->n;
-    a.B = cfg->batch;
-    a.space = dense ? azd::SPACE_DENSE : ramsey ? azd::SPACE_RAMSEY : azd::SPACE_C21;
-    a.path_kind = cfg->path_kind;
-    a.layers = cfg->layers > 1 ? cfg->layers : 1;
+    engine_shape(cfg, tier, &a);
     if (dense) {
-        a.E = azd::dense_edges(cfg->n);
-        a.A = azd::dense_action_dim(cfg->n);
-        a.S = azd::dense_state_dim(cfg->n);
-        a.KW = dense_device_key_words(cfg->max_slots);
         e->dense_slots = 64 * a.KW;
-        a.dense_p24 = (uint32_t)((cfg->dense_p > 0.f ? (double)cfg->dense_p : 0.2) * 16777216.0 + 0.5);
-        a.eval_slope = azd::c21_eval_slope(cfg->n);
-        if (dense_ah) { // (key widths 2, 4 and 10 only: max_slots <= E <= 496)
-            a.eval_slope = azd::dense_ah_eval_slope(cfg->n);
-            a.lam_lo = dense_ah_wide ? 2.0 : 1.0; // marks the engine for space_ops() and dense_ah(); no dense kernel reads the c21 bracket
-        }
         e->kw_host = azd::dense_key_words(cfg->n);
     } else if (ramsey) {
-        ramsey_shape(cfg, &a);
         e->kw_host = azd::ramsey_key_words(cfg->n, a.C);
-        e->ramsey_slots = cfg->max_slots > 0 ? cfg->max_slots : azd::MAX_NODE_ACTIONS / (a.C - 1);
-        for (int c = 0; c < a.C; ++c) {
-            a.sizes[c] = cfg->clique_sizes[c];
-            a.cweights[c] = cfg->color_weights[c];
-        }
-    } else {
-        a.A = azd::c21_action_dim(cfg->n);
-        a.S = azd::c21_state_dim(cfg->n);
-        a.KW = azd::c21_key_words(cfg->n);
-        a.eval_slope = azd::c21_eval_slope(cfg->n);
-        azd::c21_lambda_bracket(cfg->n, &a.lam_lo, &a.lam_hi);
+        e->ramsey_slots = tier->cap_from_slots ? cfg->max_slots : azd::MAX_NODE_ACTIONS / (a.C - 1);
     }
-    e->ops = azd::space_ops(a);
-    if (dense || (cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) e->ext = ext_pool_form(dense);
+    // (the flag decides whether a Ramsey tier has its searcher-only pool step; the dense-graph space always has)
+    if (dense || (cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) e->ext = tier->ext;
     e->ext_f32 = (cfg->flags & AZD_ENGINE_EXT_POOL_F32) != 0;
-    a.S_inner = a.S;
-    a.S = a.S_inner * a.layers; // Layered<L, Space>::STATE_DIM (nabla/space/mod.rs:53)
     if (ev && (ev->state_dim != a.S || ev->action_dim != a.A)) {
         delete e;
         azd::g_last_error = "evaluator dimensions do not match the space";
         return AZD_ERR_INVALID_ARGUMENT;
     }
-    a.node_cap = cfg->node_capacity > 0 ? (uint32_t)cfg->node_capacity : 4096u;
-    a.arc_cap = cfg->arc_capacity > 0 ? (uint32_t)cfg->arc_capacity : 8192u;
-    a.pred_cap = cfg->prediction_capacity > 0 ? (uint32_t)cfg->prediction_capacity : 32768u;
-    a.ht_cap = (uint32_t)next_pow2((int)(2 * a.node_cap));
     // what the packed records hold (engine_types.h: PredRec / node_pack): child node 16 bits, arc id 16 (0xFFFF = none), a child's first
     // prediction 20, action id 12, actions per node 11, n_t 20 (one per arc at most), exhausted 12 (one per action at most).  The
     // reference's u32 indices (petgraph NodeIndex / EdgeIndex, tree/mod.rs:28-32) have no such limits: a configuration beyond them is
@@ -1032,8 +715,8 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     TRY(e->alloc(&a.cur_perm, B * a.KW));
     TRY(e->alloc(&a.cur_path, B * a.KW));
     // (an AH dense engine keeps two doubles and two ints per agent there: dense_ah_cost.inc, DenseCostAH)
-    TRY(e->alloc(&a.cur_lambda, dense_ah ? 2 * B : B));
-    TRY(e->alloc(&a.cur_mu, dense_ah ? 2 * B : B));
+    TRY(e->alloc(&a.cur_lambda, tier->ah ? 2 * B : B));
+    TRY(e->alloc(&a.cur_mu, tier->ah ? 2 * B : B));
     TRY(e->alloc(&a.state_pos, B));
     TRY(e->alloc(&a.n_nodes, B));
     TRY(e->alloc(&a.n_arcs, B));
@@ -1064,7 +747,7 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         TRY(e->alloc(&a.argmin_d, 1));
         static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseAhWideArgminRec) <= sizeof(azd::DenseArgminRec),
                       "an AH engine's argmin record lives in argmin_d's allocation");
-        if (!dense_ah) TRY(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH cost keeps nothing per node)
+        if (!tier->ah) TRY(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH cost keeps nothing per node)
         // a bf16 evaluator takes the state vectors as bf16 rows: this space's kernels write them beside the f32 rows (write_vec16)
         if (ev && ev->input16_pitch() >= a.S) {
             a.S16 = ev->input16_pitch();
@@ -1076,8 +759,8 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         }
     }
     if (ramsey) {
-        TRY(e->alloc(&a.root_nbr, B * e->ramsey_nbr_words()));
-        TRY(e->alloc(&a.cur_nbr, B * e->ramsey_nbr_words()));
+        TRY(e->alloc(&a.root_nbr, B * tier->nbr_words));
+        TRY(e->alloc(&a.cur_nbr, B * tier->nbr_words));
         TRY(e->alloc(&a.root_counts, B * (size_t)a.C * a.E));
         TRY(e->alloc(&a.cur_counts, B * (size_t)a.C * a.E));
         TRY(e->alloc(&a.root_tot, B * 4));
@@ -1267,1134 +950,6 @@ int azd_engine_par_new(azd_engine *e, const uint8_t *parents, const uint64_t *pe
     return new_finish(e);
 }
 
-// optimizer/mod.rs:159-174
-int azd_engine_roll_out_begin(azd_engine *e, const uint32_t *tol, int n_tol, uint32_t dflt) {
-    if (!e || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    azd::TolTable t;
-    AZD_ST(fill_tol(t, tol, n_tol, dflt));
-    e->time_begin(0);
-    e->ops->rollout(e->a, t, e->stream);
-    e->time_end();
-    return sync_status(e);
-}
-// optimizer/mod.rs:177-190
-int azd_engine_roll_out_end(azd_engine *e, const float *h_theta, int *improved) {
-    if (!e || !h_theta || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    AZD_HIP(hipMemcpyAsync(e->a.h_theta, h_theta, (size_t)e->a.B * e->a.A * 4, hipMemcpyHostToDevice, e->stream));
-    e->ops->add_actions(e->a, 0, e->stream);
-    e->ops->argmin(e->a, 0, e->stream);
-    return report_improved(e, sync_status(e), improved);
-}
-// Evaluator groups (pool_step.inc: pool_eval_group): which member keeps which column tile of which layer in its LDS.
-// Greedy by size: the largest tiles first, each to the member that holds the fewest bytes so far and fewer than W tiles of that
-// layer.  The smallest group (a multiple of 8 workgroups) and the fewest waves per slot that fit the LDS are taken: a batch's
-// latency does not depend on g (a layer is one tile's MFMA chain per wave either way), the number of groups the CUs make does.
-struct GroupPlan {
-    int g = 0, W = 0;
-    size_t lds_bytes = 0;      // the fullest member's
-    uint32_t xstride = 0;      // floats per exchange buffer
-    std::vector<int16_t> tile; // [L][g][W]
-    std::vector<uint32_t> lds; // [L][g][W]
-};
-static bool plan_groups(const azd::FusedEval &fe, size_t lds_budget, int avail_wgs, int force_g, GroupPlan *out) {
-    const int L = fe.n_layers;
-    if (L < 1 || L > 7 || fe.bf16) return false;
-    std::vector<int> tiles(L), steps(L);
-    int max_tiles = 0;
-    uint32_t xs = 0;
-    for (int l = 0; l < L; ++l) {
-        steps[l] = (fe.dims[l] + 15) / 16;
-        tiles[l] = (fe.dims[l + 1] + 15) / 16;
-        max_tiles = std::max(max_tiles, tiles[l]);
-        if (l < L - 1) xs = std::max<uint32_t>(xs, (uint32_t)tiles[l] * 256u);
-        if (l < L - 1 && fe.dims[l + 1] % 16 != 0) return false; // a hidden layer's output is the next layer's whole k-steps
-    }
-    // the fewest waves per slot first (W = 1: sixteen batch slots per group), then the smallest group that fits the LDS and leaves
-    // room for two groups (config A: W = 1 needs g = 64 of the 192 CUs the searchers leave: 5.7 M expansions/s against 5.2 at g = 40, W = 2)
-    for (int W : {1, 2, 4})
-    for (int g = force_g > 0 ? force_g : 8; g <= avail_wgs && g <= 128; g += 8) {
-        {
-            if (force_g <= 0 && W < 4 && 2 * g > avail_wgs) break; // (a lone group only as the last resort)
-            if ((max_tiles + g - 1) / g > W) {
-                if (force_g > 0) break; // (a forced size is tried with every W, never enlarged)
-                continue;
-            }
-            struct Item { int l, t; size_t bytes; };
-            std::vector<Item> items;
-            for (int l = 0; l < L; ++l)
-                for (int t = 0; t < tiles[l]; ++t) items.push_back({l, t, (size_t)steps[l] * 1024});
-            std::stable_sort(items.begin(), items.end(), [](const Item &x, const Item &y) { return x.bytes > y.bytes; });
-            std::vector<size_t> load((size_t)g, 0);
-            std::vector<int> cnt((size_t)L * g, 0);
-            std::vector<int16_t> tile((size_t)L * g * W, (int16_t)-1);
-            std::vector<uint32_t> lds((size_t)L * g * W, 0u);
-            bool ok = true;
-            for (const Item &it : items) {
-                int best = -1;
-                for (int m = 0; m < g; ++m)
-                    if (cnt[(size_t)it.l * g + m] < W && (best < 0 || load[(size_t)m] < load[(size_t)best])) best = m;
-                if (best < 0 || load[(size_t)best] + it.bytes > lds_budget) {
-                    ok = false;
-                    break;
-                }
-                const int w = cnt[(size_t)it.l * g + best]++;
-                tile[((size_t)it.l * g + best) * W + w] = (int16_t)it.t;
-                lds[((size_t)it.l * g + best) * W + w] = (uint32_t)load[(size_t)best];
-                load[(size_t)best] += it.bytes;
-            }
-            if (!ok) {
-                if (force_g > 0) break;
-                continue;
-            }
-            out->g = g;
-            out->W = W;
-            out->lds_bytes = *std::max_element(load.begin(), load.end());
-            out->xstride = xs ? xs : 256u;
-            out->tile = tile;
-            out->lds = lds;
-            return true;
-        }
-        if (force_g > 0) break;
-    }
-    return false;
-}
-
-// ---- launch steps the roll-out forms share
-// The argument block of the CU-resident forms, re-sent only when it changed (per-launch values are kernel arguments).
-static int send_pargs(azd_engine *e, const azd::Arenas &arenas, const azd::TolTable &tol, const azd::FusedEval &fe, const azd::PoolArgs &pool) {
-    azd::PersistArgs now;
-    memset(&now, 0, sizeof(now)); // (padding bytes compare equal)
-    now.a = arenas;
-    now.tol = tol;
-    now.ev = fe;
-    now.ev.call_base = (fe.kind == 2 || fe.kind == 4) ? e->ev->calls : 0; // hash stream: index of the launch's first call
-    now.pool = pool;
-    if (e->pargs_valid && memcmp(&e->pargs_sent, &now, sizeof(now)) == 0) return AZD_OK;
-    AZD_HIP(hipStreamSynchronize(e->stream)); // the pinned block may still be in flight from the copy before
-    memcpy(e->h_pargs, &now, sizeof(now));
-    AZD_HIP(hipMemcpyAsync(e->d_pargs, e->h_pargs, sizeof(azd::PersistArgs), hipMemcpyHostToDevice, e->stream));
-    memcpy(&e->pargs_sent, &now, sizeof(now));
-    e->pargs_valid = true;
-    return AZD_OK;
-}
-// The per-call log starts a launch with all ones; the launches that replay it (k_argmin_log1, argmin_log) leave it so.
-static int ensure_log_clean(azd_engine *e) {
-    if (e->log_clean) return AZD_OK;
-    AZD_HIP(hipMemsetAsync(e->d_log_key, 0xFF, (size_t)e->log_calls * sizeof(unsigned long long), e->stream));
-    e->log_clean = true;
-    return AZD_OK;
-}
-static azd::StepLaunch step_launch(const azd_engine *e, int k, azd::PoolCtl *ctl, const uint32_t *resume, bool hashed, bool window = false, bool groups = false) {
-    azd::StepLaunch sl;
-    sl.n_calls = k;
-    sl.log_key = e->d_log_key;
-    sl.resume = resume;
-    sl.ctl = ctl;
-    sl.hashed = hashed ? 1 : 0;
-    sl.window = window ? 1 : 0;
-    sl.groups = groups ? 1 : 0;
-    return sl;
-}
-// What `body` launches on `stream`, captured and instantiated as *exec; body's own status comes first, the template graph always goes.
-static int capture_graph(hipStream_t stream, const std::function<int()> &body, hipGraphExec_t *exec) {
-    hipGraph_t g = nullptr;
-    AZD_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    const int st = body();
-    const hipError_t he = hipStreamEndCapture(stream, &g);
-    if (st) {
-        if (g) (void)hipGraphDestroy(g);
-        return st;
-    }
-    if (he != hipSuccess) return azd::hip_fail(he, "hipStreamEndCapture");
-    const hipError_t hi = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (hi != hipSuccess) return azd::hip_fail(hi, "hipGraphInstantiate");
-    return AZD_OK;
-}
-
-static int pool_clear(azd_engine *e, const azd::PoolArgs &pool) { // empty queues, nobody claimed, no call done
-    AZD_HIP(hipMemsetAsync(pool.ctl, 0, sizeof(azd::PoolCtl), e->stream));
-    AZD_HIP(hipMemsetAsync(pool.ready_slots, 0, e->pool_slot_words * sizeof(uint32_t), e->stream));
-    AZD_HIP(hipMemsetAsync(pool.join, 0, (size_t)e->a.B * sizeof(uint32_t), e->stream));
-    e->pool_clean = true;
-    return AZD_OK;
-}
-
-// What follows a pool launch of k calls on the host: its status block (the two sides' busy shares, for the split feedback) and
-// -- when a wait ran into its bound -- the take-over.
-// A wait that ran into its bound ends a pool launch instead of hanging it (PoolCtl::abort; k_argmin_log1 has put the flag into
-// the status block and left the log alone).  The trees are consistent -- a wave never leaves an agent inside a call -- so the
-// asynchronous step, whose workgroups need no company, takes the launch over where every agent stands, and this engine stays
-// with it (*took_over; the asynchronous step's LDS plan in *as_out / *ab_out).
-static int pool_finish_launch(azd_engine *e, const azd::FusedEval &fe, const azd::PoolArgs &pool, int k, bool *took_over,
-                              uint32_t *as_out, size_t *ab_out) {
-    *took_over = false;
-    AZD_ST(fetch_status(e));
-    if (e->h_status->pool_ticks > 0 && !e->h_status->pool_abort) {
-        const double T = (double)e->h_status->pool_ticks;
-        e->pool_util_eval = e->pool_eval_wgs > 0 ? (double)e->h_status->pool_eval_busy / (T * e->pool_eval_wgs) : 0.0;
-        e->pool_util_search = e->pool_search_waves > 0 ? (double)e->h_status->pool_search_busy / (T * e->pool_search_waves) : 0.0;
-    }
-    if (!e->h_status->pool_abort) return AZD_OK;
-    e->pool_clean = false;
-    e->log_clean = false; // (it holds the aborted launch's candidates, which the take-over's replay needs: not cleared here)
-    e->pool_failed = true;
-    e->pool_step = false;
-    uint32_t as = 0;
-    size_t ab = 0;
-    const char *why_t = "";
-    if (!e->ops->async_plan(e->a, fe, &as, &ab, &why_t)) {
-        e->time_collect();
-        azd::g_last_error = std::string("pool step: a queue wait ran into its bound, and the asynchronous step cannot take over: ") + why_t;
-        return AZD_ERR_UNREACHABLE;
-    }
-    azd::launch_pool_resume_scan(e->a, pool, k, e->d_resume, e->stream);
-    AZD_ST(pool_clear(e, pool));
-    const azd::StepLaunch sl = step_launch(e, k, nullptr, e->d_resume, fe.kind == 4);
-    e->time_begin(0);
-    e->ops->launch_async(e->a, e->d_pargs, sl, fe.params, fe.wpk, as, ab, e->stream);
-    e->time_end();
-    e->log_clean = true; // k_argmin_log1 has replayed and cleared it
-    e->step_form = AZD_STEP_ASYNC;
-    e->step_reason = "pool step aborted (a queue wait ran into its bound: no evaluator or searcher workgroup made progress); "
-                     "the asynchronous step took the launch over and serves this engine from here on";
-    *took_over = true;
-    *as_out = as;
-    *ab_out = ab;
-    return AZD_OK;
-}
-
-// The pool step of the dense-graph space (BASELINE configs[4]): searcher workgroups only (k_pool_search) on part of the chip; the
-// model -- too large for an evaluator workgroup's LDS -- is served by batched GEMM launches over the rows the searchers have posted,
-// replayed from a graph on a second stream for as long as the searchers run.  Agents advance independently, so a launch no longer
-// lasts as long as its slowest agent per call (launch-per-phase form: a roll-out launch took 1.2 ms where the mean agent needed 0.06).
-// The Ramsey tiers with max_slots > 0 run the same form under AZD_ENGINE_EXT_POOL_STEP: what differs between the engines that have
-// it comes from e->ops (PoolSearchOps: the searcher kernel's entries and its wavefronts per workgroup) and e->ext (ExtPoolForm: knobs and reason strings).
-struct ExtPlan { // one roll-out of the form, as ext_plan decided it
-    azd::Arenas a;     // what the searchers and the evaluator's graph see
-    azd::FusedEval fe; // what the searchers look at
-    azd::PoolArgs pool;
-    bool hashed, f32_rows;
-    const char *r_needs_rows;
-    int waves, n_search, n_ext;
-    uint32_t dyn_stride;
-    size_t dyn_bytes;
-};
-// *runs = false: the form cannot run here (why in e->step_reason).  A knob that asks for what cannot run is an error.
-static int ext_plan(azd_engine *e, int n_calls, ExtPlan *out, bool *runs) {
-    *runs = false;
-    const ExtPoolForm &xf = *e->ext;
-    // what the searchers and the evaluator's graph see: a flagged Ramsey engine's bf16 rows exist for this form only (azd_engine::ext_s16)
-    azd::Arenas ax = e->a;
-    if (e->ext_s16) {
-        ax.state_vecs16 = e->ext_s16;
-        ax.S16 = e->ext_s16_pitch;
-    }
-    const azd::Arenas &a = ax;
-    // AZD_ENGINE_EXT_POOL_F32: the evaluator's graph may read the f32 rows, which the searchers always write (write_rows_direct), so
-    // the form runs without bf16 rows; which of the two gathered forwards is captured is the evaluator's answer (its storage type)
-    const bool f32_rows = e->ext_f32;
-    const char *const r_needs_rows = f32_rows ? "external pool step: needs an evaluator that serves gathered rows (ActionModel: bf16 storage, or fp32 "
-                                                "storage under AZD_ENGINE_EXT_POOL_F32)"
-                                              : xf.r_needs_bf16;
-    if (f32_rows && e->ext_unsupported && e->ext_unsupported_layout != e->ev->layout_version) e->ext_unsupported = false;
-    const char *why = "";
-    uint32_t dyn_stride = 0;
-    size_t dyn_bytes = 0;
-    // wavefronts per searcher workgroup: 16, or as many as the LDS holds (roots of more than 640 slots: 12 -- a wave's block and its
-    // selection scratch are 12 KB there)
-    // (the Ramsey tiers: 8, the bound their kernels are built for -- every shape the tiers accept fits)
-    int waves = knob_int(xf.env_waves, e->ops->waves_max);
-    if (waves < xf.waves_min || waves > xf.waves_knob_max) { // (round-4 verdict, 7c: a knob out of range is refused, not silently bent)
-        azd::g_last_error = xf.e_waves_range;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    const bool knobs = getenv(xf.env_wgs) || getenv(xf.env_waves);
-    auto pool_plan = e->ops->pool_search_plan;
-    while (waves > xf.waves_min && !pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) waves -= 1;
-    azd::FusedEval fe;
-    const bool hashed = e->ev->fused_desc(&fe) && fe.kind == 4; // the test harness' fixed prediction stream, served like a model's rows
-    const bool configured = (e->pool_step || !xf.needs_pool_step) && e->persist_enabled;
-    if (!configured || e->pool_failed || e->ext_unsupported || (!a.state_vecs16 && !hashed && !f32_rows) ||
-        n_calls < 1 || !pool_plan(a, waves, &dyn_stride, &dyn_bytes, &why)) {
-        e->step_reason = !configured       ? xf.r_not_configured
-                         : e->pool_failed ? xf.r_failed_before
-                         : ((!a.state_vecs16 && !hashed && !f32_rows) || e->ext_unsupported) ? r_needs_rows
-                                                                                 : why;
-        return AZD_OK;
-    }
-    const int per_cu = e->ops->pool_search_resident(a, waves, dyn_bytes);
-    // searcher workgroups: no more waves than twice the agents, and no more than half the chip's wave slots -- the GEMM launches
-    // need the rest
-    int n_search = (2 * a.B + waves - 1) / waves;
-    if (n_search > e->n_cus * 8 / waves) n_search = e->n_cus * 8 / waves;
-    if (xf.keep_quarter_free && n_search > e->n_cus - e->n_cus / 4) n_search = e->n_cus - e->n_cus / 4;
-    n_search = knob_pos(xf.env_wgs, n_search);
-    // The evaluator of this form is a stream of GEMM LAUNCHES beside the searchers' persistent kernel: they run only where a CU has
-    // LDS and registers left, and a searcher workgroup (1024 threads' worth of LDS blocks) leaves none.  A setting of the two knobs
-    // that lets the searchers cover more than three quarters of the CUs used to be accepted and then cost a 4-s wait bound, an
-    // abort and the engine's demotion to the launch-per-phase form (gpurun_out/ew.txt, round 4): refused up front instead.
-    // (workgroups, not wave slots: the dispatcher deals one workgroup to every CU before it doubles up, so 256 workgroups of 8 waves
-    // sit on 256 CUs although two would fit one)
-    if (per_cu >= 1 && knobs && n_search > e->n_cus - e->n_cus / 4) {
-        static thread_local char msg[256];
-        snprintf(msg, sizeof msg, "%s / %s: %d searcher workgroups of %d waves would sit on %d of %d CUs; "
-                 "the evaluator's GEMM launches need at least a quarter of the chip free (at most %d workgroups)", xf.env_wgs, xf.env_waves, n_search, waves,
-                 n_search < e->n_cus ? n_search : e->n_cus, e->n_cus, e->n_cus - e->n_cus / 4);
-        azd::g_last_error = msg;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (per_cu < 1 || n_search > e->n_cus * per_cu * 7 / 8) n_search = per_cu < 1 ? 0 : e->n_cus * per_cu * 7 / 8;
-    if (n_search < 1) {
-        e->step_reason = xf.r_no_wg;
-        return AZD_OK;
-    }
-    // (one stream by default: with two, each batch is half as large and takes as long -- the GEMMs' k loops are latency-bound at these
-    // batch sizes and the streams share the same CUs -- so an agent's cycle, which sets the rate, gets no shorter: 18.8 M expansions/s
-    // with one stream against 17.8 with two at config E)
-    int n_ext = knob_int(xf.env_streams, xf.streams);
-    n_ext = n_ext < 1 ? 1 : n_ext > azd_engine::EXT_STREAMS ? azd_engine::EXT_STREAMS : n_ext;
-    azd::PoolArgs pool = e->pool;
-    pool.n_eval = 0;
-    pool.ready_lanes = 0;
-    pool.n_express = 0;
-    pool.express_waves = 0;
-    pool.express_shift = 0;
-    pool.early_post = knob_int("AZD_POOL_EARLY_POST", xf.early_post);
-    pool.eval_stride = pool.eval_out_off = 0;
-    pool.eval_rows = 0;
-    pool.debug_abort_call = (uint32_t)knob_int("AZD_POOL_DEBUG_ABORT_CALL", 0); // test hook: k_ext_deliver
-    if (!hashed) {
-        memset(&fe, 0, sizeof(fe));
-        fe.kind = 3; // what the searchers look at: requests are posted for an evaluator
-    }
-    *out = ExtPlan{ax, fe, pool, hashed, f32_rows, r_needs_rows, waves, n_search, n_ext, dyn_stride, dyn_bytes};
-    *runs = true;
-    return AZD_OK;
-}
-// the evaluator's graphs, one per stream: collect, the layers over the collected rows, hand back.  Every stream may find the
-// whole population posted, so each has row lists and activation rows of its own.
-// *served = false: the evaluator cannot serve gathered rows (why in e->step_reason; asked once per layout).
-static int ext_graphs(azd_engine *e, const ExtPlan &xp, bool *served) {
-    *served = true;
-    if (!xp.hashed) AZD_ST(e->ev->ensure_rows(xp.n_ext * xp.a.B));
-    int rounds = knob_int(e->ext->env_rounds, 4); // collect / layers / hand-back rounds per replay of the evaluator's graph
-    rounds = rounds < 1 ? 1 : rounds > 16 ? 16 : rounds;
-    const uint64_t layout = e->ev->layout_version + (xp.hashed ? 1ull << 63 : 0ull) + ((uint64_t)rounds << 56);
-    if (e->ext_graph_n != xp.n_ext || e->ext_graph_layout != layout) {
-        for (int x = 0; x < azd_engine::EXT_STREAMS; ++x)
-            if (e->ext_graph[x]) {
-                (void)hipGraphExecDestroy(e->ext_graph[x]);
-                e->ext_graph[x] = nullptr;
-            }
-        e->ext_graph_n = 0;
-        for (int x = 0; x < xp.n_ext; ++x) {
-            uint32_t *rows = e->d_ext_rows + (size_t)x * xp.a.B, *home = e->d_ext_home + (size_t)x * xp.a.B, *cnt = e->d_ext_n + x;
-            const int st_x = capture_graph(e->ext_stream[x], [&]() -> int {
-                int st_g = AZD_OK;
-                // several rounds per graph: between two graphs on a stream the GPU idles ~18 us, between two kernels of one graph not at all
-                for (int r = 0; r < rounds && st_g == AZD_OK; ++r) {
-                    azd::launch_ext_take(xp.pool, rows, home, cnt, e->d_ext_t0 + x, e->ext_stream[x]);
-                    if (xp.hashed) azd::launch_ext_hash_rows(e->d_pargs, rows, cnt, (uint32_t)xp.a.B, xp.a.h_theta, e->ext_stream[x]);
-                    else {
-                        st_g = xp.a.state_vecs16 ? e->ev->write_predictions_gathered(rows, cnt, xp.a.B, xp.a.state_vecs16, xp.a.S16, xp.a.h_theta, e->ext_stream[x], x * xp.a.B)
-                                              : AZD_ERR_UNSUPPORTED;
-                        if (st_g == AZD_ERR_UNSUPPORTED && xp.f32_rows) // (asked before anything is launched: a refusal leaves the capture empty)
-                            st_g = e->ev->write_predictions_gathered_f32(rows, cnt, xp.a.B, xp.a.state_vecs, xp.a.S, xp.a.h_theta, e->ext_stream[x], x * xp.a.B);
-                    }
-                    azd::launch_ext_deliver(xp.pool, xp.a, rows, home, cnt, (uint32_t)xp.a.B, e->d_ext_t0 + x, e->ext_stream[x]);
-                }
-                return st_g;
-            }, &e->ext_graph[x]);
-            if (st_x == AZD_ERR_UNSUPPORTED) {
-                e->ext_unsupported = true;
-                e->ext_unsupported_layout = e->ev->layout_version;
-                e->step_reason = xp.r_needs_rows;
-                *served = false;
-                return AZD_OK;
-            }
-            if (st_x) return st_x;
-        }
-        e->ext_graph_n = xp.n_ext;
-        e->ext_graph_layout = layout;
-    }
-    return AZD_OK;
-}
-// A wait ran into its bound (nothing made progress for 4 s: the GEMM launches never got CUs, say).  The trees are
-// consistent -- a wave never leaves an agent inside a call -- but the agents stand at different calls.  No other
-// CU-resident form of this space exists to take the launch over, so the launch-per-phase kernels complete it: agent by
-// agent from where each one stands (k_pool_resume_scan), the ones that are through sitting out (FLAG_PARKED), every
-// candidate logged under the call it really belongs to, one replay of the log at the end -- the results of an
-// undisturbed launch.  This engine stays with the launch-per-phase form.
-// (the engine's own arenas from here on: a flagged Ramsey engine's launch-per-phase kernels write no bf16 rows, so the
-// evaluator is handed none and converts the f32 rows -- ext_s16 above)
-static int ext_recover(azd_engine *e, const azd::TolTable &t, const ExtPlan &xp, int k) {
-    const azd::Arenas &a = e->a;
-    e->pool_failed = true;
-    e->log_clean = false;
-    azd::launch_pool_resume_scan(a, xp.pool, k, e->d_resume, e->stream);
-    std::vector<uint32_t> res((size_t)a.B);
-    AZD_HIP(hipMemcpyAsync(res.data(), e->d_resume, res.size() * 4, hipMemcpyDeviceToHost, e->stream));
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_ST(pool_clear(e, xp.pool));
-    int rounds = 0;
-    bool any_pending = false;
-    for (uint32_t r : res) {
-        const int rem = k - (int)(r & 0x7FFFFFFFu);
-        rounds = rem > rounds ? rem : rounds;
-        any_pending = any_pending || (r >> 31) != 0u;
-    }
-    auto evaluate_rows = [&]() -> int {
-        if (xp.hashed) { // the fixed stream's rows depend on the call: not reproducible outside the launch that posted them
-            azd::g_last_error = e->ext->e_abort_hashed;
-            return AZD_ERR_UNREACHABLE;
-        }
-        const uint64_t calls_before = e->ev->calls;
-        const int s2 = e->ev->write_predictions_dev16(a.B, a.state_vecs, a.state_vecs16, a.S16, a.h_theta, e->stream);
-        e->ev->calls = calls_before;
-        return s2;
-    };
-    if (any_pending) { // the rows that were still due, and add_actions for the nodes waiting for them
-        azd::launch_park(a, e->d_resume, k, -1, 1, e->stream);
-        AZD_ST(evaluate_rows());
-        e->ops->add_actions(a, 0, e->stream);
-    }
-    for (int r = 0; r < rounds; ++r) {
-        azd::launch_park(a, e->d_resume, k, r, 1, e->stream);
-        e->ops->rollout(a, t, e->stream);
-        AZD_ST(evaluate_rows());
-        e->ops->add_actions(a, 0, e->stream);
-        azd::launch_log_candidates_resume(a, e->d_log_key, e->d_resume, k, r, e->stream);
-    }
-    azd::launch_park(a, e->d_resume, k, 0, 0, e->stream); // everyone back
-    e->ops->argmin_log(a, k, e->d_log_key, e->stream);  // replays the k calls and leaves the log clean
-    e->log_clean = true;
-    AZD_HIP(hipGetLastError());
-    AZD_ST(fetch_status(e));
-    e->step_form = AZD_STEP_PER_CALL;
-    e->step_reason = e->ext->r_aborted;
-    return AZD_OK;
-}
-// The launches of one roll-out and, beside each, the replays of the evaluator's graphs.  *left_out: see ext_pool_run.
-static int ext_run_launches(azd_engine *e, const azd::TolTable &t, int n_calls, const ExtPlan &xp, int *left_out) {
-    const ExtPoolForm &xf = *e->ext;
-    int depth = knob_int(xf.env_depth, e->ext_depth);
-    depth = depth < 1 ? 1 : depth > azd_engine::EXT_IN_FLIGHT ? azd_engine::EXT_IN_FLIGHT : depth;
-    int left = n_calls;
-    while (left > 0) {
-        const int k = left < e->log_calls ? left : e->log_calls;
-        AZD_ST(send_pargs(e, xp.a, t, xp.fe, xp.pool));
-        AZD_ST(pool_clear(e, xp.pool)); // (always: a collect that ran past the end of the last launch may have touched the control block)
-        AZD_ST(ensure_log_clean(e));
-        AZD_HIP(hipMemsetAsync(e->d_ext_n, 0, sizeof(uint32_t) * azd_engine::EXT_STREAMS, e->stream));
-        AZD_HIP(hipEventRecord(e->ext_fork, e->stream));
-        for (int x = 0; x < xp.n_ext; ++x) AZD_HIP(hipStreamWaitEvent(e->ext_stream[x], e->ext_fork, 0)); // the first collect sees the cleared queues
-        const azd::StepLaunch sl = step_launch(e, k, xp.pool.ctl, nullptr, xp.hashed);
-        e->time_begin(0);
-        e->ops->launch_pool_search(xp.a, e->d_pargs, sl, xp.n_search, xp.waves, xp.dyn_stride, xp.dyn_bytes, e->stream);
-#ifndef AZD_PHASE_PROFILE
-        e->counters_by_wave = true;
-#endif
-        e->time_end();
-        AZD_HIP(hipGetLastError());
-        AZD_HIP(hipEventRecord(e->ext_done, e->stream));
-        e->pool_clean = false;
-        // the evaluator: replayed, stream after stream, until the searchers (and the argmin replay behind them) are through; ext_depth
-        // replays queued per stream at a time -- a replay that finds nothing posted costs a few microseconds
-        unsigned long long it = 0;
-        for (;;) {
-            const hipError_t q = hipEventQuery(e->ext_done);
-            if (q == hipSuccess) break;
-            if (q != hipErrorNotReady) return azd::hip_fail(q, "hipEventQuery");
-            const int x = (int)(it % (unsigned long long)xp.n_ext);
-            const unsigned long long round = it / (unsigned long long)xp.n_ext;
-            hipEvent_t slot = e->ext_ring[x][round % (unsigned long long)depth];
-            if (round >= (unsigned long long)depth) AZD_HIP(hipEventSynchronize(slot));
-            AZD_HIP(hipGraphLaunch(e->ext_graph[x], e->ext_stream[x]));
-            AZD_HIP(hipEventRecord(slot, e->ext_stream[x]));
-            it += 1;
-        }
-        for (int x = 0; x < xp.n_ext; ++x) AZD_HIP(hipStreamSynchronize(e->ext_stream[x]));
-        e->ext_iterations += it;
-        if (getenv(xf.env_debug)) fprintf(stderr, "%s: %d calls, %d searcher workgroups, %llu evaluator replays\n", xf.debug_tag, k, xp.n_search, it);
-        left -= k;
-        e->ev->calls += (uint64_t)k;
-        AZD_ST(fetch_status(e));
-        if (e->h_status->pool_ticks > 0) {
-            const double T = (double)e->h_status->pool_ticks;
-            e->pool_util_eval = (double)e->h_status->pool_eval_busy / (T * xp.n_ext); // the share of the launch an evaluator stream held a batch
-            e->pool_util_search = (double)e->h_status->pool_search_busy / (T * e->pool_search_waves);
-            // (A controller on these two shares, as for the in-kernel evaluator, was measured and not kept: over whole epochs the rate is flat
-            // between 112 and 160 searcher workgroups -- config E 19.7-20.0 M expansions/s, 612-slot roots 10.2-10.3 M.)
-        }
-        if (e->h_status->pool_abort) {
-            *left_out = left;
-            return ext_recover(e, t, xp, k);
-        }
-    }
-    return AZD_OK;
-}
-// *ran = false: the form cannot run here (why in e->step_reason) and the caller takes the launch-per-phase form.
-// *left_out: calls still to run when an aborted launch had to be completed by the launch-per-phase kernels (the caller runs them).
-static int ext_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bool *ran, int *left_out) {
-    *ran = false;
-    *left_out = 0;
-    ExtPlan xp;
-    bool go = false; // (the plan runs / the evaluator serves its rows)
-    int st = ext_plan(e, n_calls, &xp, &go);
-    if (st || !go) return st;
-    if (!e->ext_done) AZD_HIP(hipEventCreateWithFlags(&e->ext_done, hipEventDisableTiming));
-    if (!e->ext_fork) AZD_HIP(hipEventCreateWithFlags(&e->ext_fork, hipEventDisableTiming));
-    for (int x = 0; x < xp.n_ext; ++x) {
-        if (!e->ext_stream[x]) AZD_HIP(hipStreamCreateWithFlags(&e->ext_stream[x], hipStreamNonBlocking));
-        for (int i = 0; i < azd_engine::EXT_IN_FLIGHT; ++i)
-            if (!e->ext_ring[x][i]) AZD_HIP(hipEventCreateWithFlags(&e->ext_ring[x][i], hipEventDisableTiming));
-    }
-    st = ext_graphs(e, xp, &go);
-    if (st || !go) return st;
-    e->step_form = AZD_STEP_POOL;
-    e->step_reason.clear();
-    e->pool_eval_wgs = 0;
-    e->pool_search_wgs = xp.n_search;
-    e->pool_search_waves = xp.n_search * xp.waves;
-    e->ext_iterations = 0;
-    AZD_ST(ext_run_launches(e, t, n_calls, xp, left_out));
-    *ran = true;
-    return AZD_OK;
-}
-// The AZD_POOL_* knobs of the split (read in plan_step).  0: not set, where a positive value overrides; KNOB_UNSET where any integer does.
-struct PoolKnobs { int eval_wgs, search_wgs, ready_lanes, express_wgs, express_waves, express_shift, early_post; };
-// Split of the CUs between the two roles, in proportion to the CU time a row costs an evaluator and a call costs
-// the searchers.  AZD_POOL_EVAL_WGS / AZD_POOL_SEARCH_WGS override (experiments).
-// A function of its arguments alone (tests/test_gpu_pool_split.py pins what it gives on an MI355X): capacity = the workgroups the device holds at once,
-// fb_n_eval = the feedback controller's wish (0: none).  Returns the searcher workgroups (none: no room for one of each); everything else goes into *pool.
-static int pool_split(int n_cus, const azd::Arenas &a, const azd::FusedEval &fe, int n_calls, int capacity, int fb_n_eval, const PoolKnobs &k, azd::PoolArgs *pool) {
-    const int B = a.B;
-    int cap = 0; // (set below, with the measurement behind it)
-    auto clamp_eval = [&](int v) { // at most `cap`; at most half the chip, or whatever the searchers of a small population leave; one at least
-        const int want_search = (B + 7) / 8;
-        const int most = want_search < n_cus / 2 ? n_cus - want_search : n_cus / 2;
-        v = v > cap ? cap : v;
-        v = v > most ? most : v;
-        return v < 1 ? 1 : v;
-    };
-    int n_eval = 0;
-    if (fe.kind >= 3) {
-        double flop = 0;
-        if (fe.kind == 3)
-            for (int l = 0; l < fe.n_layers; ++l) flop += 2.0 * fe.dims[l] * fe.dims[l + 1];
-        else flop = 2.0 * 256.0 * (a.S + 512.0 + a.A); // hashed rows (test harness): the split a 3 x 256 model would get
-        // measured (profiles/r02_pool_probe.txt): a 16-row fp32 batch of the 3 x 256 MLP takes 25 us of an evaluator
-        // CU, bf16 storage 16 us; pure search 4.65 us of a CU per call on young trees.  Whole epochs (older, larger
-        // trees) want a few more evaluators than that ratio says: best 88-100 of 256 at 4096 agents fp32, 80 at 8192,
-        // 56 at 8192 bf16 (gpurun sweeps r2c/sw_*), which the constants below reproduce
-        const double eval_us_per_row = flop / (256.0 * 2400.0) / (fe.bf16 ? 1.85 : 1.0) / 0.33;
-        // (a Ramsey call costs the searchers less: no lambda_1, five selections per expansion against eleven; best 126 of 256
-        // for config D, 113 cost 10 %, 134 5 % -- gpurun sweep r2m/D_*)
-        // (round 4: a c21 call costs the searchers a quarter less -- one round trip per selection level, 3.6 rounds of lambda_1 -- and the
-        // measured-feedback split settles at 100-105 of 256 where it used to settle at 89-96; a first guess of 88 cost a process that
-        // makes few launches -- the bench's 20-call window -- 8 %: 27.0 against 29.4 M expansions/s at 88 / 104 evaluator workgroups)
-        const double search_us_per_call = a.space == azd::SPACE_RAMSEY ? 3.6 : 3.65;
-        n_eval = (int)(n_cus * eval_us_per_row / (eval_us_per_row + search_us_per_call) + 0.5);
-        // populations well beyond the searching waves keep the evaluator queues deep enough for 32-row batches (two row
-        // tiles per weight fragment, where they fit the LDS), which cost an evaluator 1.2 us per row instead of 1.6:
-        // best 76-84 of 256 at 8192 agents fp32 (88-92 at 4096), 50-58 at 8192 bf16 (gpurun sweeps r2m/B8_*, C_*)
-        if (pool->eval_rows > 16 && B >= 6144) n_eval = (int)(n_eval * 0.91 + 0.5);
-        // small populations leave CUs free (the searchers need no more waves than twice the agents): evaluators may take
-        // them down to ~4 rows per batch -- rows then rarely queue behind a running batch (config A, 512 agents and a
-        // 2.5 MFLOP model: 33 / 64 / 128 evaluator workgroups -> 2.70 / 2.92 / 3.09 M expansions/s; gpurun r2t/A_*)
-        cap = (B + 3) / 4 + 1;
-        n_eval = clamp_eval(n_eval);
-        if (fb_n_eval > 0) n_eval = clamp_eval(fb_n_eval); // the split the last launches' busy shares ask for, under the same caps
-        // a SHORT launch is fill and drain (its length is its slowest agents' few calls, each with an evaluator round trip in it): a seventh
-        // more evaluator workgroups than the busy shares of whole epochs ask for -- bench.py --steps 20, 4096 agents, same box, four
-        // alternating runs each: 104 workgroups 27.7 / 28.6 / 30.1 / 29.4 M expansions/s, 116: 29.9 / 29.2 / 29.3 / 29.8, 124: 29.5 / 29.8 /
-        // 29.6 / 29.6 (round 5; the launch over its median agent 1.50 -> 1.44 -> 1.37)
-        if (n_calls <= 64 && fe.kind == 3) n_eval = clamp_eval(n_eval + n_eval / 7);
-        if (k.eval_wgs > 0) n_eval = k.eval_wgs;
-    }
-    int n_search = n_cus - n_eval;
-    const int want = (B + 7) / 8; // no more waves than twice the agents: a wave without an agent only polls
-    n_search = n_search > want ? want : n_search;
-    n_search = n_search < 1 ? 1 : n_search;
-    if (k.search_wgs > 0) n_search = k.search_wgs;
-    // Searcher and evaluator workgroups spin-wait on each other: every one of them must be RESIDENT, whatever the overrides
-    // above ask for and whatever the device can hold (a CU mask, a partition, another kernel's LDS).  Clamp the grid to the
-    // co-resident capacity the runtime reports, evaluators first (they are dispatched first: a grid of evaluators alone
-    // would never let a searcher in); with no room for one of each the call takes the asynchronous step instead.
-    if (fe.kind < 3) n_eval = 0; // TrivialModel / in-wave hash stream: nothing to serve
-    if (n_eval + n_search > capacity) {
-        if (n_eval > capacity / 2) n_eval = capacity / 2;
-        if (fe.kind >= 3 && n_eval < 1) n_eval = 1;
-        n_search = capacity - n_eval;
-    }
-    pool->n_eval = n_eval;
-    // With more agents than searching waves an agent's cycle is mostly waiting for a wave (92 of 179 us at 8192 agents);
-    // in lane mode the agents behind the mean progress are taken first, so that the slow chains do not also queue.
-    // (lane mode: measured +4 % at 8192 agents fp32, -4 % at config C, +-0 at config D -- within run-to-run noise: those
-    // populations are bound by the searchers' capacity, not by the order they are served in.  Off unless asked for.)
-    pool->ready_lanes = k.ready_lanes;
-    // Express mode (default with a model evaluator and a chip-sized grid): one searcher workgroup per XCD serves only the
-    // agents that lag behind the progress of their XCD's unfinished agents (by more than 1/16 of it), and every other wave
-    // takes one of those first when more of them wait than express waves stand by.  A launch lasts as long as its slowest
-    // agent's chain of calls; in that chain ~10 us per call were the agent waiting for a wave.  4096 agents fp32: 32.7-33.3
-    // -> 34.1-34.6 M expansions/s over whole epochs, 25.4-25.7 -> 26.0 in a 20-call launch (gpurun r3 sweeps: 8 / 16 / 24
-    // express workgroups, thresholds 1/4 .. 1/64, 4 / 8 / 16 waves each: 8-16 workgroups and 1/16-1/32 are the flat optimum,
-    // the waves per workgroup do not matter -- what helps is the place in the queue, not the emptier CU).
-    pool->n_express = (fe.kind >= 3 && n_search >= 64) ? 8 : 0;
-    if (k.express_wgs != KNOB_UNSET) pool->n_express = k.express_wgs;
-    int express_waves = k.express_waves;
-    pool->express_shift = (uint32_t)k.express_shift;
-    if (pool->n_express > n_search / 2) pool->n_express = n_search / 2;
-    if (pool->n_express < 0) pool->n_express = 0;
-    if (pool->ready_lanes != 1) pool->ready_lanes = (pool->n_express > 0 && fe.kind >= 3) ? 2 : 0;
-    if (pool->ready_lanes != 2) pool->n_express = 0;
-    if (express_waves < 1 || express_waves > 16) express_waves = 4;
-    pool->express_waves = (uint32_t)express_waves;
-    // Early post: the row leaves, and the evaluator is asked, before the wave computes the new node's cost and writes the
-    // tree back (the agent is queued again by whoever is later, PoolArgs::join).  That takes ~15 us off an agent's cycle
-    // and costs the wave a second drain of its stores (~1.5 us): +10 % where agents rarely wait for a wave (512..2048
-    // agents, gpurun r2k/e_*), -3 % where the searchers' capacity is the bound (4096 agents and beyond).
-    // Larger populations: only by a wave that had to wait for its agent (mode 2), which is the state of the last fifth of a
-    // launch, when the slowest chains are all that is left.
-    pool->early_post = (double)B <= 1.25 * n_search * 16 ? 1 : 2; // 16 waves per searcher workgroup
-    // (a SHORT launch is fill and drain: its length is its slowest agent's few calls, not the searchers' capacity -- always early
-    // there: 28.4 -> 29.05 M expansions/s in the driver's 20-call window, same-box A/B of two runs each, round 5)
-    if (n_calls <= 64) pool->early_post = 1;
-    if (k.early_post != KNOB_UNSET) pool->early_post = k.early_post;
-    return n_search;
-}
-
-// ---- evaluator groups (pool_eval_group): where a classic batch is long -- a model whose weights one CU streams in tens of
-// microseconds -- and the population small enough that a few groups carry its rows.  AZD_POOL_EVAL_GROUP = 0: never;
-// = g: groups of g workgroups whatever the model (tests, experiments).  f32 weight storage only.
-// `avail`: what the searchers leave of the resident capacity (>= n_eval: idle CUs of a small population included); with groups, pool->n_eval and *dyn_bytes are theirs.
-static int ensure_eval_groups(azd_engine *e, const azd::FusedEval &fe, bool enabled, int avail, int force_knob, azd::PoolArgs *pool, size_t *dyn_bytes) {
-    const int B = e->a.B;
-    pool->grp_g = pool->grp_w = pool->grp_groups = 0;
-    pool->grp_tile = nullptr;
-    pool->grp_lds = nullptr;
-    pool->grp_desc = pool->grp_cnt = nullptr;
-    pool->grp_x = nullptr;
-    pool->grp_flag = nullptr;
-    pool->grp_xstride = 0;
-    if (!enabled || fe.kind != 3 || fe.bf16 || e->a.space != azd::SPACE_C21 || (size_t)B * (size_t)e->a.S * 4 >= (1ull << 31)) return AZD_OK;
-    double wbytes = 0;
-    for (int l = 0; l < fe.n_layers; ++l) wbytes += 4.0 * fe.dims[l] * fe.dims[l + 1];
-    int force_g = 0;
-    bool want = wbytes > 2.5e6 && B <= 1536; // (measured with config A's model: groups 5.7 / 9.8 / 11.0 M expansions/s at 512 / 1024 / 2048 agents, the classic form 3.5 / 6.8 / 13.2)
-    if (force_knob != KNOB_UNSET) {
-        force_g = force_knob;
-        want = force_g > 0;
-    }
-    GroupPlan gpl;
-    if (!want || !plan_groups(fe, (size_t)160 * 1024 - 2048, avail, force_g, &gpl)) return AZD_OK;
-    const int n_groups = std::max(1, avail / gpl.g);
-    const int NS = 16 / gpl.W;
-    const size_t slots = (size_t)n_groups * NS;
-    {   // the groups' device memory and the two tables of the plan
-        if (!e->d_grp_tile) {
-            AZD_HIP(hipMalloc(&e->d_grp_tile, (size_t)8 * 128 * 4 * sizeof(int16_t)));
-            AZD_HIP(hipMalloc(&e->d_grp_lds, (size_t)8 * 128 * 4 * sizeof(uint32_t)));
-        }
-        if (slots > e->grp_slots_alloc || slots * 2 * gpl.xstride > e->grp_x_floats || slots * gpl.g * 16 > e->grp_flag_words) {
-            AZD_HIP(hipStreamSynchronize(e->stream));
-            (void)hipFree(e->d_grp_desc);
-            (void)hipFree(e->d_grp_cnt);
-            (void)hipFree(e->d_grp_x);
-            (void)hipFree(e->d_grp_flag);
-            e->d_grp_flag = nullptr;
-            e->d_grp_desc = e->d_grp_cnt = nullptr;
-            e->d_grp_x = nullptr;
-            AZD_HIP(hipMalloc(&e->d_grp_desc, slots * 64 * 4));
-            AZD_HIP(hipMalloc(&e->d_grp_cnt, slots * 8 * 32 * 4));
-            AZD_HIP(hipMalloc(&e->d_grp_x, slots * 2 * gpl.xstride * 4));
-            AZD_HIP(hipMalloc(&e->d_grp_flag, slots * gpl.g * 16 * 4));
-            e->grp_flag_words = slots * gpl.g * 16;
-            e->grp_slots_alloc = slots;
-            e->grp_x_floats = slots * 2 * gpl.xstride;
-        }
-        if (gpl.tile != e->grp_tile_host || gpl.lds != e->grp_lds_host) {
-            AZD_HIP(hipStreamSynchronize(e->stream));
-            AZD_HIP(hipMemcpy(e->d_grp_tile, gpl.tile.data(), gpl.tile.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-            AZD_HIP(hipMemcpy(e->d_grp_lds, gpl.lds.data(), gpl.lds.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            e->grp_tile_host = gpl.tile;
-            e->grp_lds_host = gpl.lds;
-        }
-    }
-    pool->grp_g = gpl.g;
-    pool->grp_w = gpl.W;
-    pool->grp_groups = n_groups;
-    pool->grp_tile = e->d_grp_tile;
-    pool->grp_lds = e->d_grp_lds;
-    pool->grp_desc = e->d_grp_desc;
-    pool->grp_cnt = e->d_grp_cnt;
-    pool->grp_x = e->d_grp_x;
-    pool->grp_flag = e->d_grp_flag;
-    pool->grp_xstride = gpl.xstride;
-    pool->n_eval = n_groups * gpl.g; // every evaluator workgroup is a group member
-    if (gpl.lds_bytes > *dyn_bytes) *dyn_bytes = gpl.lds_bytes;
-    return AZD_OK;
-}
-
-// What a runner needs of plan_step's decision, beside e->step_form.  Which form runs is part of the result a caller may want to check
-// (azd_engine_step_form): the launch-per-phase form is several times slower than the CU-resident ones
-struct StepPlan {
-    azd::FusedEval fe;
-    uint32_t dyn_stride;
-    size_t dyn_bytes;
-    azd::PoolArgs pool;
-    int pool_blocks;
-    bool feedback; // the pool step's controller acts on this engine's launches (pool_feedback_update)
-};
-
-// Pool, asynchronous, lock-step or launch-per-phase form, with the step down from a pool step that cannot be resident: writes
-// e->step_form and e->step_reason and fills *out, which comes zeroed.
-static int plan_step(azd_engine *e, int n_calls, StepPlan *out) {
-    StepPlan &p = *out;
-    const std::string dense_reason = e->a.space == azd::SPACE_DENSE ? e->step_reason : std::string();
-    // a Ramsey engine under AZD_ENGINE_EXT_POOL_STEP whose form did not run takes what it would have taken without the flag; the
-    // reason opens with why the form did not run.  After an aborted launch of the form it stays with the launch-per-phase kernels
-    // that completed it.
-    const bool ext_ramsey = e->ext && e->a.space == azd::SPACE_RAMSEY;
-    const std::string ext_reason = ext_ramsey ? e->step_reason : std::string();
-    const bool ext_demoted = ext_ramsey && e->pool_failed;
-    p.pool = e->pool;
-    const bool fusable = e->persist_enabled && !ext_demoted && e->ev->fused_desc(&p.fe);
-    const bool pool_wanted = fusable && e->pool_step;
-    const char *why_a = "", *why_b = "", *why_p = "";
-    const bool pool_planned = pool_wanted && e->ops->pool_plan(e->a, p.fe, &p.pool, &p.dyn_stride, &p.dyn_bytes, &why_p);
-    bool use_pool = pool_planned, use_async = false, use_barrier = false;
-    e->step_reason.clear();
-    if (pool_planned) { // the launch: the split, the evaluator groups, and what azd_engine_pool_split / azd_engine_pool_groups report
-        const int capacity = knob_int("AZD_POOL_MAX_RESIDENT", e->ops->pool_max_resident(e->a, p.dyn_bytes, e->n_cus)); // (the knob: tests -- a device that holds fewer workgroups)
-        PoolKnobs k;
-        k.eval_wgs = knob_pos("AZD_POOL_EVAL_WGS", 0);
-        k.search_wgs = knob_pos("AZD_POOL_SEARCH_WGS", 0);
-        k.ready_lanes = knob_int("AZD_POOL_READY_LANES", 0);
-        k.express_wgs = knob_int("AZD_POOL_EXPRESS_WGS", KNOB_UNSET);
-        k.express_waves = knob_int("AZD_POOL_EXPRESS_WAVES", 8);
-        k.express_shift = knob_int("AZD_POOL_EXPRESS_SHIFT", 4);
-        k.early_post = knob_int("AZD_POOL_EARLY_POST", KNOB_UNSET);
-        const int n_search = pool_split(e->n_cus, e->a, p.fe, n_calls, capacity, pool_feedback_on() ? e->pool_fb.n_eval : 0, k, &p.pool);
-        if (n_search < 1 || capacity < 1) {
-            use_pool = false;
-            char buf[160];
-            snprintf(buf, sizeof(buf), "pool step: the device holds %d of its workgroups at once; it needs an evaluator and a searcher resident together; ", capacity);
-            e->step_reason = buf;
-        }
-        p.pool.debug_abort_call = (uint32_t)knob_int("AZD_POOL_DEBUG_ABORT_CALL", 0);
-        AZD_ST(ensure_eval_groups(e, p.fe, use_pool, capacity - n_search, knob_int("AZD_POOL_EVAL_GROUP", KNOB_UNSET), &p.pool, &p.dyn_bytes));
-        p.pool_blocks = p.pool.n_eval + n_search;
-        e->pool_grp_g = p.pool.grp_g;
-        e->pool_grp_groups = p.pool.grp_groups;
-        e->pool_grp_w = p.pool.grp_w;
-        e->pool_eval_wgs = p.pool.n_eval;
-        e->pool_search_wgs = n_search;
-        e->pool_search_waves = (n_search - p.pool.n_express) * 16 + p.pool.n_express * (int)p.pool.express_waves;
-    }
-    auto step_down = [&]() { // the forms below the pool step, in order; what each of them says goes behind the reason so far
-        use_async = !e->barrier_step && e->ops->async_plan(e->a, p.fe, &p.dyn_stride, &p.dyn_bytes, &why_a);
-        use_barrier = !use_async && e->ops->persist_plan(e->a, p.fe, &p.dyn_stride, &p.dyn_bytes, &why_b);
-        if (!use_async) e->step_reason += why_a;
-        if (!use_async && !use_barrier && *why_b) e->step_reason += std::string("; ") + why_b;
-    };
-    if (!e->persist_enabled) e->step_reason = "AZD_ENGINE_NO_PERSISTENT_STEP";
-    else if (!fusable) e->step_reason = "the evaluator cannot run inside the kernel (external model, more than 7 layers, or a layer width that is not a multiple of 4)";
-    else if (pool_planned && !use_pool) step_down(); // the pool step was wanted and cannot be resident: the next form down
-    else if (!use_pool) {
-        if (pool_wanted) e->step_reason = std::string(why_p) + "; ";
-        if (e->barrier_step) e->step_reason = "AZD_ENGINE_BARRIER_STEP";
-        step_down();
-        if (e->pool_failed && use_async)
-            e->step_reason = "an earlier pool launch of this engine aborted (a queue wait ran into its bound): asynchronous step";
-        // (a pool step that was wanted and could not be planned has always asked the forms below it twice: where the asynchronous
-        // step cannot run either, the reason names what was said about it and the lock-step form a second time.  Kept as it is.)
-        if (pool_wanted) step_down();
-    }
-    e->step_form = use_pool ? AZD_STEP_POOL : use_async ? AZD_STEP_ASYNC : use_barrier ? AZD_STEP_BARRIER : AZD_STEP_PER_CALL;
-    p.feedback = use_pool && p.fe.kind == 3 && pool_feedback_on() && !getenv("AZD_POOL_EVAL_WGS");
-    if (e->a.space == azd::SPACE_DENSE) // why the space's pool step did not run: the launch-per-phase form follows
-        e->step_reason = dense_reason.empty() ? "AZD_DENSE_NO_POOL: the dense-graph space's pool step was switched off" : dense_reason;
-    if (ext_ramsey) e->step_reason = ext_demoted || e->step_reason.empty() ? ext_reason : ext_reason + "; " + e->step_reason;
-    return AZD_OK;
-}
-// From the busy shares of a launch that is over: the evaluator workgroups the next launch's pool_split is given (fb_n_eval).
-static void pool_feedback_update(azd_engine *e) {
-    // where the best split sits: at equal shares when the agents hardly outnumber the searching waves (their cycle, not the
-    // chip, sets the pace: configs A, B, the 384 x 384 model), at u_e - u_s = +0.06 when they queue for waves (8192 agents:
-    // a slightly starved evaluator side fills 32-row batches, which cost it a quarter less per row)
-    const double crowd = e->pool_search_waves > 0 ? (double)e->a.B / e->pool_search_waves - 1.5 : 0.0;
-    const double d = e->pool_util_eval - e->pool_util_search - 0.06 * (crowd < 0 ? 0.0 : crowd > 1 ? 1.0 : crowd);
-    // (large steps while the first guess is being corrected; afterwards at most 6 workgroups per launch, so that one disturbed
-    // launch -- another tenant's burst on the box, a first dispatch under a profiler -- cannot carry the split far: a run whose
-    // warm-up launch moved it from 89 to 102 evaluators stayed 7 % low for the two launches it had left to walk back)
-    const int cur = e->pool_eval_wgs, lim = e->pool_fb.updates < 2 ? (cur / 4 > 4 ? cur / 4 : 4) : 6;
-    e->pool_fb.updates += 1;
-    int mv = (int)(100.0 * d + (d >= 0 ? 0.5 : -0.5));
-    mv = mv > lim ? lim : mv < -lim ? -lim : mv;
-    int next = cur + mv;
-    next = next > e->n_cus / 2 ? e->n_cus / 2 : next < 1 ? 1 : next;
-    e->pool_fb.n_eval = next;
-}
-// CU-resident forms: the whole call chain, n_calls times, in one launch per <= log_calls calls.  What a launch costs
-// the host: the argument block is re-sent only when it changed (per-launch values are kernel arguments), the log and
-// the pool's control block are left clean by k_argmin_log1, the abort flag comes back with the status block.
-// ahead: one launch, left running behind an open window.  *fresh: h_status already holds the status behind the last launch.
-static int run_resident(azd_engine *e, const azd::TolTable &t, int n_calls, StepPlan p, bool ahead, bool *fresh) {
-    int left = n_calls;
-    while (left > 0) {
-        const int k = left < e->log_calls ? left : e->log_calls;
-        const bool use_pool = e->step_form == AZD_STEP_POOL, use_async = e->step_form == AZD_STEP_ASYNC, use_barrier = e->step_form == AZD_STEP_BARRIER;
-        *fresh = false;
-        AZD_ST(send_pargs(e, e->a, t, p.fe, p.pool));
-        if (use_pool && !e->pool_clean) AZD_ST(pool_clear(e, p.pool));
-        if (use_pool && p.pool.grp_g > 0) { // batch numbers and arrival counts of the groups' slots start from zero in every launch
-            const size_t slots = (size_t)p.pool.grp_groups * (16 / p.pool.grp_w);
-            AZD_HIP(hipMemsetAsync(p.pool.grp_desc, 0, slots * 64 * 4, e->stream));
-            AZD_HIP(hipMemsetAsync(p.pool.grp_cnt, 0, slots * 8 * 32 * 4, e->stream));
-            AZD_HIP(hipMemsetAsync(p.pool.grp_flag, 0, slots * p.pool.grp_g * 16 * 4, e->stream));
-        }
-        if (!use_barrier) AZD_ST(ensure_log_clean(e));
-        if (ahead) {
-            // the window's hand-over words (no launch that writes them is in flight: a window is drained before the next opens),
-            // and the argmin record the window starts from: its cost for the host's per-call compare, a copy for argmin_data
-            AZD_HIP(hipMemsetAsync(p.pool.win_count, 0, (size_t)e->log_calls * sizeof(uint32_t), e->stream));
-            AZD_HIP(hipMemcpyAsync(e->d_argmin_side, e->a.argmin, sizeof(azd::ArgminRec), hipMemcpyDeviceToDevice, e->stream));
-            if (e->d_argmin_r_side)
-                AZD_HIP(hipMemcpyAsync(e->d_argmin_r_side, e->a.argmin_r, e->argmin_r_bytes(), hipMemcpyDeviceToDevice, e->stream));
-            AZD_HIP(hipMemcpyAsync(e->h_argmin, e->a.argmin, sizeof(azd::ArgminRec), hipMemcpyDeviceToHost, e->stream));
-            AZD_ST(fetch_status(e)); // (synchronises)
-            memset(e->h_win_flag, 0, (size_t)e->log_calls * sizeof(uint32_t));
-            __atomic_thread_fence(__ATOMIC_SEQ_CST);
-        }
-        const azd::StepLaunch sl = step_launch(e, k, use_pool ? p.pool.ctl : nullptr, nullptr, p.fe.kind == 4, ahead, use_pool && p.pool.grp_g > 0);
-        e->time_begin(0);
-        if (use_pool) {
-            e->ops->launch_pool(e->a, e->d_pargs, sl, p.fe.params, p.fe.wpk, p.pool_blocks, p.dyn_stride, p.dyn_bytes, e->stream);
-#ifndef AZD_PHASE_PROFILE
-            e->counters_by_wave = true;
-#endif
-        } else if (use_async) e->ops->launch_async(e->a, e->d_pargs, sl, p.fe.params, p.fe.wpk, p.dyn_stride, p.dyn_bytes, e->stream);
-        else {
-            e->ops->launch_persist(e->a, e->d_pargs, sl, e->d_log_node, p.dyn_stride, p.dyn_bytes, e->stream);
-            e->log_clean = false;
-        }
-        e->time_end();
-        left -= k;
-        if (ahead) { // the launch is on its way; window_serve / window_drain do the rest
-            AZD_HIP(hipGetLastError());
-            e->ev->calls += (uint64_t)k;
-            azd_engine::Window &w = e->win;
-            w = azd_engine::Window();
-            w.open = true;
-            w.n = k;
-            w.tol = t;
-            w.best_ord = host_ordf(e->h_argmin->eval);
-            w.base_improved = e->h_status->improved;
-            w.fe = p.fe;
-            w.pool = p.pool;
-            return AZD_OK;
-        }
-        if (use_pool) {
-            bool took_over = false;
-            AZD_ST(pool_finish_launch(e, p.fe, p.pool, k, &took_over, &p.dyn_stride, &p.dyn_bytes));
-            *fresh = left == 0 && !took_over; // the last launch's status is in, and nothing ran behind it
-        }
-        e->ev->calls += (uint64_t)k;
-    }
-    AZD_HIP(hipGetLastError());
-    if (p.feedback && n_calls >= 100 && e->step_form == AZD_STEP_POOL && *fresh && e->h_status->pool_ticks > 0) pool_feedback_update(e); // the launch is over and its busy shares are in
-    return AZD_OK;
-}
-// One launch-per-phase call per sub-population, captured in a graph each and replayed on streams of their own.
-static int run_per_call_subs(azd_engine *e, const azd::TolTable &t, int n_calls, int n_subs) {
-    const int per = (e->a.B + n_subs - 1) / n_subs;
-    if (!e->sub_fork) AZD_HIP(hipEventCreateWithFlags(&e->sub_fork, hipEventDisableTiming));
-    for (int i = 0; i < n_subs; ++i) {
-        if (!e->sub_stream[i]) AZD_HIP(hipStreamCreateWithFlags(&e->sub_stream[i], hipStreamNonBlocking));
-        if (!e->sub_join[i]) AZD_HIP(hipEventCreateWithFlags(&e->sub_join[i], hipEventDisableTiming));
-    }
-    int st = AZD_OK;
-    if (e->sub_graph_n != n_subs || memcmp(&e->call_graph_tol, &t, sizeof(t)) != 0 || e->call_graph_layout != e->ev->layout_version) {
-        for (int i = 0; i < azd_engine::MAX_SUBS; ++i)
-            if (e->sub_graph[i]) {
-                (void)hipGraphExecDestroy(e->sub_graph[i]);
-                e->sub_graph[i] = nullptr;
-            }
-        e->sub_graph_n = 0;
-        for (int i = 0; i < n_subs; ++i) {
-            azd::Arenas as = e->a;
-            as.t0 = i * per;
-            as.tn = e->a.B - as.t0 < per ? e->a.B - as.t0 : per;
-            if (as.tn <= 0) continue;
-            st = capture_graph(e->sub_stream[i], [&]() -> int {
-                e->ops->rollout(as, t, e->sub_stream[i]);
-                const int st_w = e->ev->write_predictions_rows(as.t0, as.tn, e->a.state_vecs, e->a.state_vecs16, e->a.S16, e->a.h_theta, e->sub_stream[i]);
-                e->ops->add_actions(as, 0, e->sub_stream[i]);
-                azd::launch_log_candidates(as, e->d_log_key, e->d_call_ctr + i, e->sub_stream[i]);
-                return st_w;
-            }, &e->sub_graph[i]);
-            if (st) return st;
-        }
-        e->sub_graph_n = n_subs;
-        e->call_graph_tol = t;
-        e->call_graph_layout = e->ev->layout_version;
-        if (e->call_graph) { // (the single-stream graph was captured for another tol table or layout)
-            (void)hipGraphExecDestroy(e->call_graph);
-            e->call_graph = nullptr;
-        }
-    }
-    int left = n_calls;
-    while (left > 0) {
-        const int k = left < e->log_calls ? left : e->log_calls;
-        AZD_ST(ensure_log_clean(e));
-        AZD_HIP(hipMemsetAsync(e->d_call_ctr, 0, sizeof(uint32_t) * azd_engine::MAX_SUBS, e->stream));
-        AZD_HIP(hipEventRecord(e->sub_fork, e->stream));
-        for (int i = 0; i < n_subs; ++i)
-            if (e->sub_graph[i]) AZD_HIP(hipStreamWaitEvent(e->sub_stream[i], e->sub_fork, 0));
-        for (int c = 0; c < k; ++c)
-            for (int i = 0; i < n_subs; ++i)
-                if (e->sub_graph[i]) AZD_HIP(hipGraphLaunch(e->sub_graph[i], e->sub_stream[i]));
-        for (int i = 0; i < n_subs; ++i)
-            if (e->sub_graph[i]) {
-                AZD_HIP(hipEventRecord(e->sub_join[i], e->sub_stream[i]));
-                AZD_HIP(hipStreamWaitEvent(e->stream, e->sub_join[i], 0));
-            }
-        e->ops->argmin_log(e->a, k, e->d_log_key, e->stream); // replays the k calls and leaves the log clean
-        left -= k;
-    }
-    e->ev->calls += (uint64_t)n_calls;
-    e->step_form = AZD_STEP_PER_CALL_GRAPH;
-    return AZD_OK;
-}
-// One call captured once into a hipGraph and replayed per call.
-static int run_per_call_graph(azd_engine *e, const azd::TolTable &t, int n_calls) {
-    if (!e->call_graph || e->sub_graph_n != 0 || memcmp(&e->call_graph_tol, &t, sizeof(t)) != 0 || e->call_graph_layout != e->ev->layout_version) {
-        e->sub_graph_n = 0; // (the sub-population graphs, if any, belong to another tol table or layout from here on)
-        if (e->call_graph) (void)hipGraphExecDestroy(e->call_graph);
-        e->call_graph = nullptr;
-        const int st = capture_graph(e->stream, [&]() -> int {
-            e->ops->rollout(e->a, t, e->stream);
-            const uint64_t calls_before = e->ev->calls;
-            const int st_w = e->ev->write_predictions_dev16(e->a.B, e->a.state_vecs, e->a.state_vecs16, e->a.S16, e->a.h_theta, e->stream);
-            e->ev->calls = calls_before;
-            e->ops->add_actions(e->a, 0, e->stream);
-            e->ops->argmin(e->a, 0, e->stream);
-            return st_w;
-        }, &e->call_graph);
-        if (st) return st;
-        e->call_graph_tol = t;
-        e->call_graph_layout = e->ev->layout_version;
-    }
-    for (int c = 0; c < n_calls; ++c) AZD_HIP(hipGraphLaunch(e->call_graph, e->stream));
-    e->ev->calls += (uint64_t)n_calls;
-    e->step_form = AZD_STEP_PER_CALL_GRAPH;
-    return AZD_OK;
-}
-
-// optimizer/mod.rs:159-190, n_calls times.  ahead: azd_engine_run_ahead -- the launch is left running and its calls are handed
-// out by window_serve; *accepted = 0 when this engine's step form cannot do that (nothing is launched then).
-static int roll_out_impl(azd_engine *e, const azd::TolTable &t, int n_calls, int *improved, bool ahead, int *accepted) {
-    if (accepted) *accepted = 0;
-    if (e->ext && !(e->ext->env_off && getenv(e->ext->env_off))) {
-        if (ahead) return AZD_OK; // (the evaluator's launches need this thread: nothing can run ahead of the host; a hint, declined)
-        bool ran = false;
-        int left_after = 0;
-        AZD_ST(ext_pool_run(e, t, n_calls, &ran, &left_after));
-        if (ran && left_after == 0) return report_improved(e, check_status(e), improved);
-        if (ran) n_calls = left_after; // (an aborted launch was completed call by call: what is left runs the same way, below)
-    }
-    StepPlan p{};
-    AZD_ST(plan_step(e, n_calls, &p));
-    if (ahead) { // only the pool step publishes its calls while it runs, one launch's worth of them
-        const bool ok = e->step_form == AZD_STEP_POOL && p.fe.kind >= 3 && n_calls >= 1 && n_calls <= e->log_calls && !e->timing;
-        if (!ok) return AZD_OK; // a hint: the calls run when they are asked for
-        *accepted = 1;
-    }
-    bool status_fresh = false; // h_status already holds the status behind the last launch
-    if (e->step_form != AZD_STEP_PER_CALL) {
-        AZD_ST(run_resident(e, t, n_calls, p, ahead, &status_fresh));
-        if (ahead) { // the launch is on its way; window_serve / window_drain do the rest
-            if (improved) *improved = 0;
-            return AZD_OK;
-        }
-    } else {
-        // One call = roll-out, model call, add_actions, argmin: four to eight launches.  With the MLP evaluator (whose
-        // launches take no per-call arguments) the sequence is captured once into a hipGraph and replayed per call, so
-        // a call costs one graph launch instead of a launch per phase (BASELINE configs[4]: "hipGraph-captured episode
-        // step").  Not while per-launch timing is on (the events would be captured too), nor for evaluators whose
-        // kernels take the call index.
-        const bool graphable = e->graph_enabled && !e->timing && n_calls >= 2 && e->ev->replayable(e->a.B);
-        // Sub-populations: a roll-out launch lasts as long as its slowest agent (config E: 1.2 ms against a mean agent's 0.06), so
-        // the population is cut into S parts, each with a stream and a graph of its own (roll-out, model rows, add_actions,
-        // candidates into the per-call log); the parts run n_calls calls independently -- trees never exchange data and the
-        // model is constant -- and one part's kernels fill the CUs another part's stragglers leave idle.  The per-call argmin
-        // is replayed from the log afterwards, as in the CU-resident forms.  Needs an evaluator whose rows may run concurrently.
-        // (Config E, 8192 agents: 1 / 2 / 4 / 8 parts -> 11.7 / 12.4 / 8.0 / 6.0 M expansions/s: every part adds seven graph nodes per
-        // call for the host to enqueue, and beyond two parts the host, not the GPU, sets the pace.)
-        int n_subs = (e->a.B >= 2048 && e->ev->rows_concurrent()) ? 2 : 1;
-        n_subs = knob_int("AZD_PER_CALL_STREAMS", n_subs);
-        if (n_subs > azd_engine::MAX_SUBS) n_subs = azd_engine::MAX_SUBS;
-        if (n_subs > 1 && (!e->ev->rows_concurrent() || e->a.B > 65536 || e->a.node_cap > 65536)) n_subs = 1;
-        if (graphable && n_subs > 1) AZD_ST(run_per_call_subs(e, t, n_calls, n_subs));
-        else if (graphable) AZD_ST(run_per_call_graph(e, t, n_calls));
-        else
-            for (int c = 0; c < n_calls; ++c) {
-                e->time_begin(0);
-                e->ops->rollout(e->a, t, e->stream);
-                e->time_end();
-                AZD_ST(run_evaluator(e)); // :175-176
-                e->ops->add_actions(e->a, 0, e->stream);
-                e->ops->argmin(e->a, 0, e->stream); // :190
-            }
-    }
-    return report_improved(e, status_fresh ? check_status(e) : sync_status(e), improved);
-}
-
-// ---------------------------------------------------------------- run-ahead window
-// The launch behind the window is over (or is waited for here): status in, busy shares noted, an aborted launch taken over.
-static int window_drain(azd_engine *e) {
-    azd_engine::Window &w = e->win;
-    if (w.drained) return AZD_OK;
-    bool took_over = false;
-    uint32_t as = 0;
-    size_t ab = 0;
-    AZD_ST(pool_finish_launch(e, w.fe, w.pool, w.n, &took_over, &as, &ab));
-    if (took_over) AZD_ST(fetch_status(e));
-    w.drained = true;
-    return check_status(e);
-}
-// The window ends: every call it ran is accounted for, whether handed out or not.
-static int window_close(azd_engine *e) {
-    azd_engine::Window &w = e->win;
-    if (!w.open) return AZD_OK;
-    const int st = window_drain(e);
-    w.open = false;
-    if (st) return st;
-    // every improvement the host was told of, call by call, is one the device's replay of the same log counted
-    const unsigned long long total = e->h_status->improved - w.base_improved;
-    if (w.consumed == w.n && !w.lumped && w.reported != total) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "run-ahead window: %llu improvements handed out call by call, %llu in the device's replay", w.reported, total);
-        azd::g_last_error = buf;
-        e->seen_improved = e->h_status->improved;
-        return AZD_ERR_UNREACHABLE;
-    }
-    e->seen_improved = e->h_status->improved;
-    return AZD_OK;
-}
-// k calls of the window, in order: each is waited for (the kernel publishes a call once its last agent is through it) and
-// compared with the best cost so far exactly as k_argmin_log1 will compare it (strict, optimizer/mod.rs:211).
-static int window_serve(azd_engine *e, int k, int *improved) {
-    azd_engine::Window &w = e->win;
-    int imp = 0;
-    for (int i = w.consumed; i < w.consumed + k; ++i) {
-        uint32_t spins = 0;
-        while (!w.drained && __atomic_load_n(&e->h_win_flag[i], __ATOMIC_ACQUIRE) == 0u) {
-            if ((++spins & 255u) == 0u) {
-                const hipError_t q = hipStreamQuery(e->stream);
-                if (q == hipSuccess) { // the launch is over: whatever it has not published it will not (an abort)
-                    const int st = window_drain(e);
-                    if (st) {
-                        w.open = false;
-                        e->seen_improved = e->h_status->improved;
-                        return st;
-                    }
-                } else if (q != hipErrorNotReady) return azd::hip_fail(q, "hipStreamQuery");
-            }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-        if (__atomic_load_n(&e->h_win_flag[i], __ATOMIC_ACQUIRE) != 0u) {
-            const unsigned long long key = e->h_win_log[i];
-            if (key != ~0ull && (uint32_t)(key >> 32) < w.best_ord) {
-                w.best_ord = (uint32_t)(key >> 32);
-                w.best_key = key;
-                imp += 1;
-            }
-        } else if (!w.lumped) {
-            // an aborted launch: the take-over completed the calls from here on and does not publish them one by one -- what they
-            // improved is reported with this call, and the argmin record is the one the launch ended with
-            const unsigned long long total = e->h_status->improved - w.base_improved;
-            imp += (int)(total - w.reported - (unsigned long long)imp);
-            w.lumped = true;
-        }
-    }
-    w.consumed += k;
-    w.reported += (unsigned long long)imp;
-    if (improved) *improved = imp;
-    if (w.consumed == w.n) return window_close(e);
-    return AZD_OK;
-}
-// argmin_data inside a window: the record as of the calls handed out.  The winner's replay reads its tree, so the launch is
-// waited for; the calls not yet handed out stay in the window.
-static int window_argmin_side(azd_engine *e, bool *side) {
-    azd_engine::Window &w = e->win;
-    *side = false;
-    if (!w.open) return AZD_OK;
-    const int st = window_drain(e);
-    if (st) {
-        w.open = false;
-        e->seen_improved = e->h_status->improved;
-        return st;
-    }
-    if (w.lumped) return AZD_OK; // (the device's record is all there is)
-    if (w.best_key != w.side_key) {
-        azd::Arenas a2 = e->a;
-        a2.argmin = e->d_argmin_side;
-        a2.argmin_r = e->d_argmin_r_side;
-        e->ops->argmin_one(a2, (int)((w.best_key >> 16) & 0xFFFFull), (uint32_t)(w.best_key & 0xFFFFull), e->stream);
-        AZD_HIP(hipGetLastError());
-        w.side_key = w.best_key;
-    }
-    *side = true;
-    return AZD_OK;
-}
-
-int azd_engine_par_roll_out_episodes(azd_engine *e, const uint32_t *tol, int n_tol, uint32_t dflt, int n_calls,
-                                     int *improved) {
-    if (!e || n_calls < 0 || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (!e->ev) return AZD_ERR_NO_EVALUATOR;
-    AZD_HIP(hipSetDevice(e->cfg.device));
-    azd::TolTable t;
-    AZD_ST(fill_tol(t, tol, n_tol, dflt));
-    if (e->win.open) {
-        // calls that were run ahead: handed out without a launch.  Other calls (another tolerance table, more calls than the
-        // window has left) close the window and run as usual.
-        if (memcmp(&e->win.tol, &t, sizeof(t)) == 0 && n_calls <= e->win.n - e->win.consumed) {
-            if (n_calls == 0) {
-                if (improved) *improved = 0;
-                return AZD_OK;
-            }
-            return window_serve(e, n_calls, improved);
-        }
-        AZD_ST(window_close(e));
-    }
-    return roll_out_impl(e, t, n_calls, improved, false, nullptr);
-}
-
-// Run-ahead window: the next n_calls calls of par_roll_out_episodes(tol, ...) are started now, in one launch, and the calls
-// that ask for them -- one by one, or in any chunks -- are answered from what the kernel publishes as it goes.
-int azd_engine_run_ahead(azd_engine *e, const uint32_t *tol, int n_tol, uint32_t dflt, int n_calls, int *accepted) {
-    if (accepted) *accepted = 0;
-    if (!e || n_calls < 0 || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (!e->ev) return AZD_ERR_NO_EVALUATOR;
-    AZD_ENTER(e);
-    azd::TolTable t;
-    int st = fill_tol(t, tol, n_tol, dflt);
-    if (st) return st;
-    if (n_calls == 0) return AZD_OK;
-    int ok = 0;
-    st = roll_out_impl(e, t, n_calls, nullptr, true, &ok);
-    if (accepted) *accepted = ok;
-    return st;
-}
-
-// optimizer/mod.rs:262-278
 int azd_engine_observe_dev(azd_engine *e, uint32_t n_obs_tol, const float **d_state_vecs, const float **d_obs,
                            const float **d_w) {
     if (!e || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
@@ -2538,897 +1093,6 @@ int azd_engine_par_reset_trees(azd_engine *e, const uint8_t *parents, const uint
     AZD_ST(azd_engine_reset_begin(e, parents, permitted));
     AZD_ST(run_evaluator(e)); // :348
     return reset_finish(e);
-}
-
-// the report of the policy launch the stream has completed: an empty kept set (k_modify_roots left that tree's root where it was)
-static int root_report_check(azd_engine *e) {
-    e->root_report_valid = true;
-    for (int t = 0; t < e->a.B; ++t)
-        if (e->root_report[(size_t)t * 3] != (uint32_t)azd::ROOT_BRANCH_FRESH && e->root_report[(size_t)t * 3 + 2] == 0) {
-            char buf[128];
-            snprintf(buf, sizeof(buf), "root policy: tree %d keeps no node (the reference's unwrap() on None)", t);
-            azd::g_last_error = buf;
-            return AZD_ERR_UNREACHABLE;
-        }
-    return AZD_OK;
-}
-
-// par_reset_trees with the c21 driver's modify_root policy (04-c21-tree.rs:172-206) evaluated on the
-// device: no host round trip at the epoch boundary.
-static int c21_policy_args_ok(azd_engine *e, int kmin, int kmax) {
-    if (!e || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->a.space == azd::SPACE_DENSE) {
-        if (e->a.path_kind == azd::PATH_SEQUENCE) {
-            azd::g_last_error = "the device root policy of the dense-graph space handles ActionSet keys only";
-            return AZD_ERR_UNSUPPORTED;
-        }
-        if (kmin < 1 || kmax < kmin || kmax > e->a.E || kmax > e->dense_slots) {
-            azd::g_last_error = "dense root policy: need 1 <= kmin <= kmax <= min(E, 64 * key words) (azd_engine_config::max_slots)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-        return AZD_OK;
-    }
-    if (e->a.path_kind == azd::PATH_SEQUENCE && e->a.node_cap > 4096) {
-        azd::g_last_error = "the device root policy handles sequence-keyed trees of at most 4096 nodes";
-        return AZD_ERR_UNSUPPORTED;
-    }
-    if (e->a.space == azd::SPACE_RAMSEY) { // the node cap: max_slots edges on a wide engine, MAX_NODE_ACTIONS / (C - 1) otherwise
-        if (kmin < 1 || kmax < kmin || kmax > e->a.E || kmax > e->ramsey_slots) {
-            if (e->ramsey_wide()) azd::g_last_error = "Ramsey root policy: need 1 <= kmin <= kmax <= max_slots (azd_engine_config::max_slots)";
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-        return AZD_OK;
-    }
-    if (kmin < 1 || kmax < kmin || kmax > e->a.A || kmax > azd::MAX_NODE_ACTIONS) return AZD_ERR_INVALID_ARGUMENT;
-    return AZD_OK;
-}
-int azd_engine_par_reset_trees_c21(azd_engine *e, uint64_t seed, uint64_t epoch, int kmin, int kmax) {
-    AZD_ST(c21_policy_args_ok(e, kmin, kmax));
-    if (!e->ev) return AZD_ERR_NO_EVALUATOR;
-    AZD_ENTER(e);
-    const azd::Arenas &a = e->a;
-    e->root_report_valid = false;
-    e->ops->modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->root_args,
-                         e->stream);
-    AZD_HIP(hipMemsetAsync(&a.status->failed, 0, sizeof(unsigned long long), e->stream));
-    e->ops->init_roots(a, e->d_stage_parents, e->d_stage_perm, e->stream);
-    AZD_HIP(hipMemsetAsync(a.h_theta, 0, (size_t)a.B * a.A * 4, e->stream));
-    AZD_HIP(hipGetLastError());
-    AZD_ST(run_evaluator(e));
-    e->ops->add_actions(e->a, 1, e->stream); // reset_finish, with the policy's report read back under the same synchronisation
-    AZD_HIP(hipMemcpyAsync(e->root_report, e->d_root_report, (size_t)e->a.B * 3 * 4, hipMemcpyDeviceToHost, e->stream));
-    AZD_ST(sync_status(e));
-    return root_report_check(e);
-}
-int azd_c21_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int kmin, int kmax, uint8_t *parents_out,
-                             uint64_t *permitted_out) {
-    AZD_ST(c21_policy_args_ok(e, kmin, kmax));
-    if (!parents_out || !permitted_out) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    const azd::Arenas &a = e->a;
-    e->root_report_valid = false;
-    e->ops->modify_roots(a, seed, epoch, e->cfg.first_agent, kmin, kmax, e->d_stage_parents, e->d_stage_perm, e->d_stage_slots, e->root_args,
-                         e->stream);
-    AZD_HIP(hipMemcpyAsync(e->root_report, e->d_root_report, (size_t)e->a.B * 3 * 4, hipMemcpyDeviceToHost, e->stream));
-    if (a.space == azd::SPACE_DENSE) { // roots_out: neighbourhoods (8 n bytes per root); permitted_out: slot masks in kw_host words per root
-        const int ow = (a.E + 63) / 64;
-        std::vector<uint64_t> sl((size_t)a.B * ow);
-        AZD_HIP(hipMemcpyAsync(parents_out, e->d_stage_parents, (size_t)a.B * a.n * 8, hipMemcpyDeviceToHost, e->stream));
-        AZD_HIP(hipMemcpyAsync(sl.data(), e->d_stage_slots, sl.size() * 8, hipMemcpyDeviceToHost, e->stream));
-        AZD_HIP(hipStreamSynchronize(e->stream));
-        AZD_HIP(hipGetLastError());
-        memset(permitted_out, 0, (size_t)a.B * e->kw_host * 8);
-        for (int i = 0; i < a.B; ++i) memcpy(permitted_out + (size_t)i * e->kw_host, &sl[(size_t)i * ow], (size_t)ow * 8);
-        return root_report_check(e);
-    }
-    AZD_HIP(hipMemcpyAsync(parents_out, e->d_stage_parents, (size_t)a.B * (a.space == azd::SPACE_RAMSEY ? a.E : a.n), hipMemcpyDeviceToHost, e->stream));
-    if (e->ramsey_wide()) { // device masks are a.KW words, the caller's kw_host
-        std::vector<uint64_t> pm((size_t)a.B * a.KW);
-        AZD_HIP(hipMemcpyAsync(pm.data(), e->d_stage_perm, pm.size() * 8, hipMemcpyDeviceToHost, e->stream));
-        AZD_HIP(hipStreamSynchronize(e->stream));
-        for (int i = 0; i < a.B; ++i) memcpy(permitted_out + (size_t)i * e->kw_host, &pm[(size_t)i * a.KW], (size_t)e->kw_host * 8);
-    } else AZD_HIP(hipMemcpyAsync(permitted_out, e->d_stage_perm, (size_t)a.B * a.KW * 8, hipMemcpyDeviceToHost, e->stream));
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipGetLastError());
-    return root_report_check(e);
-}
-
-// ---- the policy's description (include/azdopt_amd.h: azd_root_policy)
-int azd_root_policy_check(int space_id, int n_colors, const azd_root_policy *p) {
-    if (!p) return AZD_OK; // the defaults
-    if (p->rule != AZD_ROOT_RULE_THRESHOLD && p->rule != AZD_ROOT_RULE_BEST) {
-        azd::g_last_error = "rule: AZD_ROOT_RULE_THRESHOLD or AZD_ROOT_RULE_BEST";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (p->n_color_weights == 0) return AZD_OK;
-    if (space_id != AZD_SPACE_RAMSEY) {
-        azd::g_last_error = "color_weights: only an AZD_SPACE_RAMSEY engine colours its fresh roots";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (p->n_color_weights != n_colors) {
-        azd::g_last_error = "n_color_weights: 0 or the engine's n_colors";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (const char *why = azd::ramsey_check_color_weights(p->color_weights, n_colors)) {
-        azd::g_last_error = why;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    return AZD_OK;
-}
-int azd_engine_set_root_policy(azd_engine *e, const azd_root_policy *p) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ST(azd_root_policy_check(e->a.space, e->a.C, p));
-    const azd_root_policy defaults{AZD_ROOT_RULE_THRESHOLD, 0, {0.0, 0.0, 0.0, 0.0}};
-    e->root_policy = p ? *p : defaults;
-    for (int c = e->root_policy.n_color_weights; c < 4; ++c) e->root_policy.color_weights[c] = 0.0;
-    e->root_args.rule = e->root_policy.rule;
-    e->root_args.weighted = e->root_policy.n_color_weights != 0;
-    for (int c = 0; c < azd::RAMSEY_COLOR_THRESHOLDS; ++c) e->root_args.color_thr[c] = 1ull << 32;
-    if (e->root_args.weighted) azd::ramsey_color_thresholds(e->root_policy.color_weights, e->a.C, e->root_args.color_thr);
-    return AZD_OK;
-}
-int azd_engine_get_root_policy(const azd_engine *e, azd_root_policy *p) {
-    if (!p) return AZD_ERR_INVALID_ARGUMENT;
-    const azd_root_policy defaults{AZD_ROOT_RULE_THRESHOLD, 0, {0.0, 0.0, 0.0, 0.0}};
-    *p = e ? e->root_policy : defaults;
-    return AZD_OK;
-}
-int azd_engine_root_policy_report(azd_engine *e, uint8_t *branch, uint32_t *node, uint32_t *kept) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (!e->root_report_valid) {
-        azd::g_last_error = "root policy report: no policy call has completed on this engine";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    for (int t = 0; t < e->a.B; ++t) {
-        if (branch) branch[t] = (uint8_t)e->root_report[(size_t)t * 3];
-        if (node) node[t] = e->root_report[(size_t)t * 3 + 1];
-        if (kept) kept[t] = e->root_report[(size_t)t * 3 + 2];
-    }
-    return AZD_OK;
-}
-
-// space-neutral names of the two entry points above (the policy is the same for both spaces)
-int azd_engine_par_reset_trees_policy(azd_engine *e, uint64_t seed, uint64_t epoch, int kmin, int kmax) {
-    return azd_engine_par_reset_trees_c21(e, seed, epoch, kmin, kmax);
-}
-int azd_engine_modify_roots_dev(azd_engine *e, uint64_t seed, uint64_t epoch, int kmin, int kmax, uint8_t *roots_out,
-                                uint64_t *permitted_out) {
-    return azd_c21_modify_roots_dev(e, seed, epoch, kmin, kmax, roots_out, permitted_out);
-}
-
-// the engine's Ramsey argmin record, whichever of the three the tier's kernels write, as the largest one
-static int ramsey_argmin_fetch(azd_engine *e, azd::RamseyU64ArgminRec *out) {
-    AZD_HIP(hipSetDevice(e->cfg.device));
-    bool side = false; // inside a run-ahead window: the record as of the calls handed out so far
-    {
-        const int st_w = window_argmin_side(e, &side);
-        if (st_w) return st_w;
-    }
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    const void *src = side ? (const void *)e->d_argmin_r_side : (const void *)e->a.argmin_r;
-    memset(out, 0, sizeof(*out));
-    if (e->ramsey_u64()) {
-        AZD_HIP(hipMemcpy(out, src, sizeof(*out), hipMemcpyDeviceToHost));
-        return AZD_OK;
-    }
-#define AZD_WIDEN(REC)                                              \
-    {                                                               \
-        REC r;                                                      \
-        AZD_HIP(hipMemcpy(&r, src, sizeof(r), hipMemcpyDeviceToHost)); \
-        memcpy(out->colors, r.colors, sizeof(r.colors));            \
-        memcpy(out->permitted, r.permitted, sizeof(r.permitted));   \
-        memcpy(out->totals, r.totals, sizeof(r.totals));            \
-        out->eval = r.eval;                                         \
-        out->agent = r.agent;                                       \
-        out->node = r.node;                                         \
-    }
-    if (e->ramsey_wide()) AZD_WIDEN(azd::RamseyWideArgminRec)
-    else AZD_WIDEN(azd::RamseyArgminRec)
-#undef AZD_WIDEN
-    return AZD_OK;
-}
-int azd_engine_ramsey_argmin_data(azd_engine *e, azd_ramsey_argmin *out) {
-    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->a.space != azd::SPACE_RAMSEY) return AZD_ERR_UNSUPPORTED;
-    if (e->a.E > 256) { // (colours of 256 edges: azd_ramsey_argmin)
-        azd::g_last_error = "E > 256 edges do not fit azd_ramsey_argmin: use azd_engine_ramsey_wide_argmin_data";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    static_assert(sizeof(azd_ramsey_argmin) == sizeof(azd::RamseyArgminRec), "ABI struct mismatch");
-    azd::RamseyU64ArgminRec r;
-    AZD_ST(ramsey_argmin_fetch(e, &r));
-    memset(out, 0, sizeof(*out));
-    memcpy(out->colors, r.colors, sizeof(out->colors));
-    memcpy(out->permitted, r.permitted, sizeof(out->permitted));
-    memcpy(out->totals, r.totals, sizeof(out->totals));
-    out->eval = r.eval;
-    out->agent = r.agent;
-    out->node = r.node;
-    return AZD_OK;
-}
-int azd_engine_ramsey_wide_argmin_data(azd_engine *e, azd_ramsey_wide_argmin *out) {
-    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->a.space != azd::SPACE_RAMSEY) return AZD_ERR_UNSUPPORTED;
-    static_assert(sizeof(azd_ramsey_wide_argmin) == sizeof(azd::RamseyWideArgminRec), "ABI struct mismatch");
-    if (e->a.E > 496) { // (colours of 496 edges: azd_ramsey_wide_argmin)
-        azd::g_last_error = "E > 496 edges do not fit azd_ramsey_wide_argmin: use azd_engine_ramsey_argmin_any";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    azd::RamseyU64ArgminRec r;
-    AZD_ST(ramsey_argmin_fetch(e, &r));
-    memset(out, 0, sizeof(*out));
-    memcpy(out->colors, r.colors, sizeof(out->colors));
-    memcpy(out->permitted, r.permitted, sizeof(out->permitted));
-    memcpy(out->totals, r.totals, sizeof(out->totals));
-    out->eval = r.eval;
-    out->agent = r.agent;
-    out->node = r.node;
-    return AZD_OK;
-}
-int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap, uint64_t *permitted, int permitted_words_cap,
-                                 int32_t *totals, float *eval, int32_t *agent, uint32_t *node) {
-    if (!e || !e->initialised || colors_cap < 0 || permitted_words_cap < 0) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->a.space != azd::SPACE_RAMSEY) return AZD_ERR_UNSUPPORTED;
-    const int PWH = (e->a.E + 63) / 64;
-    if ((colors && colors_cap < e->a.E) || (permitted && permitted_words_cap < PWH)) {
-        azd::g_last_error = "azd_engine_ramsey_argmin_any: need colors_cap >= E bytes and permitted_words_cap >= (E + 63) / 64 words";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    azd::RamseyU64ArgminRec r;
-    AZD_ST(ramsey_argmin_fetch(e, &r));
-    if (colors) {
-        memset(colors, 0, (size_t)colors_cap);
-        memcpy(colors, r.colors, (size_t)e->a.E);
-    }
-    if (permitted) {
-        memset(permitted, 0, (size_t)permitted_words_cap * 8);
-        memcpy(permitted, r.permitted, (size_t)PWH * 8);
-    }
-    if (totals) memcpy(totals, r.totals, sizeof(r.totals));
-    if (eval) *eval = r.eval;
-    if (agent) *agent = r.agent;
-    if (node) *node = r.node;
-    return AZD_OK;
-}
-int azd_engine_dense_argmin_data(azd_engine *e, azd_dense_argmin *out) {
-    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->a.space != azd::SPACE_DENSE) return AZD_ERR_UNSUPPORTED;
-    if (e->dense_ah()) {
-        azd::g_last_error = "azd_engine_dense_argmin_data: an AZD_ENGINE_DENSE_AH engine's record is read with azd_engine_dense_ah_argmin_data";
-        return AZD_ERR_UNSUPPORTED;
-    }
-    AZD_ENTER(e);
-    static_assert(sizeof(azd_dense_argmin) == sizeof(azd::DenseArgminRec), "ABI struct mismatch");
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipMemcpy(out, e->a.argmin_d, sizeof(azd_dense_argmin), hipMemcpyDeviceToHost));
-    return AZD_OK;
-}
-int azd_engine_dense_ah_argmin_data(azd_engine *e, azd_dense_ah_argmin *out) {
-    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (!e->dense_ah()) return AZD_ERR_UNSUPPORTED;
-    if (e->dense_ah_wide()) {
-        azd::g_last_error = "azd_engine_dense_ah_argmin_data: an AZD_ENGINE_DENSE_AH_WIDE engine's record is read with azd_engine_dense_ah_wide_argmin_data";
-        return AZD_ERR_UNSUPPORTED;
-    }
-    AZD_ENTER(e);
-    static_assert(sizeof(azd_dense_ah_argmin) == sizeof(azd::DenseAhArgminRec), "ABI struct mismatch");
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipMemcpy(out, e->a.argmin_d, sizeof(azd_dense_ah_argmin), hipMemcpyDeviceToHost));
-    return AZD_OK;
-}
-int azd_engine_dense_ah_wide_argmin_data(azd_engine *e, azd_dense_ah_wide_argmin *out) {
-    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (!e->dense_ah_wide()) {
-        azd::g_last_error = "azd_engine_dense_ah_wide_argmin_data: not an AZD_ENGINE_DENSE_AH_WIDE engine";
-        return AZD_ERR_UNSUPPORTED;
-    }
-    AZD_ENTER(e);
-    static_assert(sizeof(azd_dense_ah_wide_argmin) == sizeof(azd::DenseAhWideArgminRec) &&
-                      offsetof(azd_dense_ah_wide_argmin, node) == offsetof(azd::DenseAhWideArgminRec, node),
-                  "ABI struct mismatch");
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipMemcpy(out, e->a.argmin_d, sizeof(azd_dense_ah_wide_argmin), hipMemcpyDeviceToHost));
-    return AZD_OK;
-}
-int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out) {
-    if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (!e->dense_ah()) return AZD_ERR_UNSUPPORTED;
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    const azd::Arenas &a = e->a;
-    AZD_HIP(hipMemcpy(&out->proximity, a.cur_lambda + agent, 8, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&out->eigenvalue, a.cur_lambda + a.B + agent, 8, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&out->diameter, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&out->k, a.cur_mu + a.B + agent, 4, hipMemcpyDeviceToHost));
-    out->cost = (float)(out->proximity + out->eigenvalue);
-    out->eval = a.eval_slope * (out->cost + 2.0f);
-    return AZD_OK;
-}
-int azd_engine_ramsey_agent_counts(azd_engine *e, int agent, int32_t *counts, int32_t *totals) {
-    if (!e || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->a.space != azd::SPACE_RAMSEY) return AZD_ERR_UNSUPPORTED;
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    const azd::Arenas &a = e->a;
-    if (counts) AZD_HIP(hipMemcpy(counts, a.cur_counts + (size_t)agent * a.C * a.E, (size_t)a.C * a.E * 4, hipMemcpyDeviceToHost));
-    if (totals) AZD_HIP(hipMemcpy(totals, a.cur_tot + (size_t)agent * 4, 16, hipMemcpyDeviceToHost));
-    return AZD_OK;
-}
-
-int azd_engine_argmin_data(azd_engine *e, azd_argmin *out) {
-    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->a.space != azd::SPACE_C21) return AZD_ERR_UNSUPPORTED;
-    AZD_HIP(hipSetDevice(e->cfg.device));
-    bool side = false; // inside a run-ahead window: the record as of the calls handed out so far
-    {
-        const int st_w = window_argmin_side(e, &side);
-        if (st_w) return st_w;
-    }
-    static_assert(sizeof(azd_argmin) == sizeof(azd::ArgminRec), "ABI struct mismatch");
-    AZD_HIP(hipMemcpyAsync(e->h_argmin, side ? e->d_argmin_side : e->a.argmin, sizeof(azd::ArgminRec), hipMemcpyDeviceToHost, e->stream));
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    memcpy(out, e->h_argmin, sizeof(azd_argmin));
-    return AZD_OK;
-}
-
-int azd_engine_read_state_vecs(azd_engine *e, float *out) {
-    if (!e || !out) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipMemcpy(out, e->a.state_vecs, (size_t)e->a.B * e->a.S * 4, hipMemcpyDeviceToHost));
-    return AZD_OK;
-}
-// Test entry: rows of the evaluator as the CU-resident step forms compute them (mlp_tile_task; k_tile_forward), for `rows` state
-// vectors given by the host.  Needs an MLP evaluator the pool step can serve (the plan lays the rows out in LDS).
-int azd_engine_debug_tile_forward(azd_engine *e, const float *states, float *predictions, int rows) {
-    if (!e || !states || !predictions || rows < 1) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    azd::FusedEval fe;
-    azd::PoolArgs pool = e->pool;
-    uint32_t dyn_stride = 0;
-    size_t dyn_bytes = 0;
-    const char *why = "";
-    if (e->a.space == azd::SPACE_DENSE || !e->ev->fused_desc(&fe) || fe.kind != 3 || !e->ops->pool_plan(e->a, fe, &pool, &dyn_stride, &dyn_bytes, &why)) {
-        azd::g_last_error = "debug_tile_forward: needs the c21 or the Ramsey space with an MLP evaluator the pool step can serve";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    float *d_in = nullptr, *d_out = nullptr;
-    hipError_t he = hipMalloc(&d_in, (size_t)rows * e->a.S * 4);
-    const char *what = "hipMalloc";
-    if (he == hipSuccess) he = hipMalloc(&d_out, (size_t)rows * e->a.A * 4);
-    if (he == hipSuccess) what = "hipMemcpyAsync", he = hipMemcpyAsync(d_in, states, (size_t)rows * e->a.S * 4, hipMemcpyHostToDevice, e->stream);
-    if (he == hipSuccess) what = "k_tile_forward", he = azd::launch_tile_forward(fe, pool, rows, d_in, d_out, e->stream);
-    if (he == hipSuccess) what = "hipMemcpyAsync", he = hipMemcpyAsync(predictions, d_out, (size_t)rows * e->a.A * 4, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) what = "hipStreamSynchronize", he = hipStreamSynchronize(e->stream);
-    else (void)hipStreamSynchronize(e->stream); // nothing of this call may still be running on the buffers freed below
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return he == hipSuccess ? AZD_OK : azd::hip_fail(he, what);
-}
-int azd_engine_read_predictions(azd_engine *e, float *out) {
-    if (!e || !out) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipMemcpy(out, e->a.h_theta, (size_t)e->a.B * e->a.A * 4, hipMemcpyDeviceToHost));
-    return AZD_OK;
-}
-
-int azd_engine_tree_sizes(azd_engine *e, int agent, int *n_nodes, int *n_arcs, int *n_preds) {
-    if (!e || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    uint32_t v[3];
-    AZD_HIP(hipMemcpy(&v[0], e->a.n_nodes + agent, 4, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&v[1], e->a.n_arcs + agent, 4, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&v[2], e->a.n_preds + agent, 4, hipMemcpyDeviceToHost));
-    if (n_nodes) *n_nodes = (int)v[0];
-    if (n_arcs) *n_arcs = (int)v[1];
-    if (n_preds) *n_preds = (int)v[2];
-    return AZD_OK;
-}
-
-int azd_engine_export_tree(azd_engine *e, int agent, float *c, float *c_star, uint32_t *n_t, uint32_t *exhausted,
-                           uint32_t *act_begin, uint32_t *act_end, uint64_t *keys, uint32_t *arc_src,
-                           uint32_t *arc_dst, uint32_t *arc_pp, uint32_t *pred_a_id, float *pred_g,
-                           int32_t *pred_arc) {
-    int nn, na, np;
-    AZD_ST(azd_engine_tree_sizes(e, agent, &nn, &na, &np));
-    const azd::Arenas &a = e->a;
-    std::vector<azd::NodeRec> nodes((size_t)nn);
-    std::vector<azd::ArcRec> arcs((size_t)na);
-    std::vector<azd::PredRec> preds((size_t)np);
-    AZD_HIP(hipMemcpy(nodes.data(), a.nodes + (size_t)agent * a.node_cap, nodes.size() * sizeof(azd::NodeRec), hipMemcpyDeviceToHost));
-    if (na) AZD_HIP(hipMemcpy(arcs.data(), a.arcs + (size_t)agent * a.arc_cap, arcs.size() * sizeof(azd::ArcRec), hipMemcpyDeviceToHost));
-    if (np) AZD_HIP(hipMemcpy(preds.data(), a.preds + (size_t)agent * a.pred_cap, preds.size() * sizeof(azd::PredRec), hipMemcpyDeviceToHost));
-    std::vector<float> g_exp((size_t)np); // g of the expanded predictions (the record holds the child's summary in its place)
-    if (np) AZD_HIP(hipMemcpy(g_exp.data(), a.pred_g + (size_t)agent * a.pred_cap, g_exp.size() * 4, hipMemcpyDeviceToHost));
-    if (keys && a.space == azd::SPACE_DENSE) { // device keys are sets of RANKS: back to action-id sets (kw_host words per node)
-        const int KW = a.KW, MAXS = e->dense_slots;
-        std::vector<uint64_t> rk((size_t)nn * KW);
-        std::vector<uint16_t> tab((size_t)MAXS);
-        AZD_HIP(hipMemcpy(rk.data(), a.keys + (size_t)agent * a.node_cap * KW, rk.size() * 8, hipMemcpyDeviceToHost));
-        AZD_HIP(hipMemcpy(tab.data(), a.root_aid + (size_t)agent * MAXS, tab.size() * 2, hipMemcpyDeviceToHost));
-        memset(keys, 0, (size_t)nn * e->kw_host * 8);
-        for (int i = 0; i < nn; ++i)
-            for (int r = 0; r < MAXS; ++r)
-                if ((rk[(size_t)i * KW + (r >> 6)] >> (r & 63)) & 1ull) keys[(size_t)i * e->kw_host + (tab[(size_t)r] >> 6)] |= 1ull << (tab[(size_t)r] & 63);
-    } else if (keys && e->ramsey_wide()) { // zero-padded device keys: the first kw_host words of each
-        std::vector<uint64_t> rk((size_t)nn * a.KW);
-        AZD_HIP(hipMemcpy(rk.data(), a.keys + (size_t)agent * a.node_cap * a.KW, rk.size() * 8, hipMemcpyDeviceToHost));
-        for (int i = 0; i < nn; ++i) memcpy(keys + (size_t)i * e->kw_host, &rk[(size_t)i * a.KW], (size_t)e->kw_host * 8);
-    } else if (keys) AZD_HIP(hipMemcpy(keys, a.keys + (size_t)agent * a.node_cap * a.KW, (size_t)nn * a.KW * 8, hipMemcpyDeviceToHost));
-    for (int i = 0; i < nn; ++i) {
-        if (c) c[i] = nodes[(size_t)i].c;
-        if (c_star) c_star[i] = nodes[(size_t)i].c_star;
-        if (n_t) n_t[i] = azd::node_nt(nodes[(size_t)i]);
-        if (exhausted) exhausted[i] = azd::node_exhausted(nodes[(size_t)i]);
-        if (act_begin) act_begin[i] = nodes[(size_t)i].act_begin;
-        if (act_end) act_end[i] = nodes[(size_t)i].act_end;
-    }
-    for (int i = 0; i < na; ++i) {
-        if (arc_src) arc_src[i] = arcs[(size_t)i].src;
-        if (arc_dst) arc_dst[i] = arcs[(size_t)i].dst;
-        if (arc_pp) arc_pp[i] = arcs[(size_t)i].pp;
-    }
-    for (int i = 0; i < np; ++i) {
-        const azd::PredRec &pr = preds[(size_t)i];
-        const bool ex = azd::pred_expanded(pr);
-        if (pred_a_id) pred_a_id[i] = azd::pred_aid(pr);
-        if (pred_g) {
-            const uint32_t gb = pr.w1;
-            float gv;
-            memcpy(&gv, &gb, 4);
-            pred_g[i] = ex ? g_exp[(size_t)i] : gv;
-        }
-        if (pred_arc) pred_arc[i] = ex ? (int32_t)azd::pred_arc(pr) : -1;
-    }
-    return AZD_OK;
-}
-
-int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t *permitted, uint64_t *path,
-                           uint32_t *state_pos, double *lambda_1, int *matching_size) {
-    if (!e || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    const azd::Arenas &a = e->a;
-    if (a.space == azd::SPACE_DENSE) { // `parents` receives the neighbourhoods (8 n bytes); masks are kw_host words
-        if (e->dense_ah() && (lambda_1 || matching_size)) {
-            azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_AH engine keeps neither (azd_engine_dense_ah_agent_cost)";
-            return AZD_ERR_UNSUPPORTED;
-        }
-        const int KW = a.KW, MAXS = e->dense_slots;
-        std::vector<uint16_t> tab((size_t)MAXS);
-        uint64_t rem[16], pth[16];
-        AZD_HIP(hipMemcpy(tab.data(), a.root_aid + (size_t)agent * MAXS, tab.size() * 2, hipMemcpyDeviceToHost));
-        AZD_HIP(hipMemcpy(rem, a.cur_perm + (size_t)agent * KW, (size_t)KW * 8, hipMemcpyDeviceToHost));
-        AZD_HIP(hipMemcpy(pth, a.cur_path + (size_t)agent * KW, (size_t)KW * 8, hipMemcpyDeviceToHost));
-        if (parents) AZD_HIP(hipMemcpy(parents, a.cur_adj + (size_t)agent * 64, (size_t)a.n * 8, hipMemcpyDeviceToHost));
-        if (permitted) memset(permitted, 0, (size_t)e->kw_host * 8);
-        if (path) memset(path, 0, (size_t)e->kw_host * 8);
-        for (int r = 0; r < MAXS; ++r) {
-            if (permitted && ((rem[r >> 6] >> (r & 63)) & 1ull)) { // open SLOTS, as in the packed root
-                const int slot = tab[(size_t)r] % a.E;
-                permitted[slot >> 6] |= 1ull << (slot & 63);
-            }
-            if (path && ((pth[r >> 6] >> (r & 63)) & 1ull)) path[tab[(size_t)r] >> 6] |= 1ull << (tab[(size_t)r] & 63);
-        }
-        if (state_pos) AZD_HIP(hipMemcpy(state_pos, a.state_pos + agent, 4, hipMemcpyDeviceToHost));
-        if (lambda_1) AZD_HIP(hipMemcpy(lambda_1, a.cur_lambda + agent, 8, hipMemcpyDeviceToHost));
-        if (matching_size) AZD_HIP(hipMemcpy(matching_size, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
-        return AZD_OK;
-    }
-    if (a.space == azd::SPACE_RAMSEY) { // `parents` receives the colour of every edge (E bytes)
-        uint32_t nbr[512]; // [4][32] uint32_t rows, or the 64-bit tier's [4][64] uint64_t rows
-        const bool u64 = e->ramsey_u64();
-        AZD_HIP(hipMemcpy(nbr, a.cur_nbr + (size_t)agent * e->ramsey_nbr_words(), e->ramsey_nbr_words() * 4, hipMemcpyDeviceToHost));
-        if (parents) {
-            int pos = 0;
-            for (int v = 0; v < a.n; ++v)
-                for (int u = 0; u < v; ++u, ++pos) {
-                    parents[pos] = 0;
-                    for (int c = 0; c < a.C; ++c)
-                        if (u64 ? (nbr[2 * (c * 64 + v) + (u >> 5)] >> (u & 31)) & 1u : (nbr[c * 32 + v] >> u) & 1u) parents[pos] = (uint8_t)c;
-                }
-        }
-        // (kw_host words: a wide engine's device masks are zero-padded beyond them)
-        if (permitted) AZD_HIP(hipMemcpy(permitted, a.cur_perm + (size_t)agent * a.KW, (size_t)e->kw_host * 8, hipMemcpyDeviceToHost));
-        if (path) AZD_HIP(hipMemcpy(path, a.cur_path + (size_t)agent * a.KW, (size_t)e->kw_host * 8, hipMemcpyDeviceToHost));
-        if (state_pos) AZD_HIP(hipMemcpy(state_pos, a.state_pos + agent, 4, hipMemcpyDeviceToHost));
-        if (lambda_1) *lambda_1 = 0.0;
-        if (matching_size) *matching_size = 0;
-        return AZD_OK;
-    }
-    uint8_t par[azd::PARENTS_STRIDE];
-    AZD_HIP(hipMemcpy(par, a.cur_parents + (size_t)agent * azd::PARENTS_STRIDE, azd::PARENTS_STRIDE, hipMemcpyDeviceToHost));
-    if (parents) memcpy(parents, par, (size_t)a.n);
-    if (permitted) AZD_HIP(hipMemcpy(permitted, a.cur_perm + (size_t)agent * a.KW, (size_t)a.KW * 8, hipMemcpyDeviceToHost));
-    if (path) AZD_HIP(hipMemcpy(path, a.cur_path + (size_t)agent * a.KW, (size_t)a.KW * 8, hipMemcpyDeviceToHost));
-    if (state_pos) AZD_HIP(hipMemcpy(state_pos, a.state_pos + agent, 4, hipMemcpyDeviceToHost));
-    if (lambda_1) AZD_HIP(hipMemcpy(lambda_1, a.cur_lambda + agent, 8, hipMemcpyDeviceToHost));
-    if (matching_size) AZD_HIP(hipMemcpy(matching_size, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
-    return AZD_OK;
-}
-
-int azd_engine_counters(azd_engine *e, uint64_t *out) {
-    if (!e || !out) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    const azd::Arenas &a = e->a;
-    std::vector<unsigned long long> h((size_t)a.B * azd::NUM_COUNTERS);
-    std::vector<uint32_t> fl((size_t)a.B);
-    AZD_HIP(hipMemcpy(h.data(), a.counters, h.size() * 8, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(fl.data(), a.flags, fl.size() * 4, hipMemcpyDeviceToHost));
-    for (int k = 0; k < AZD_CTR_COUNT; ++k) out[k] = 0;
-    for (int i = 0; i < a.B; ++i) {
-        for (int k = 0; k < azd::NUM_COUNTERS; ++k) {
-            unsigned long long v = h[(size_t)i * azd::NUM_COUNTERS + k];
-            if (k >= AZD_CTR_COUNT) continue;
-            if (k == AZD_CTR_MAX_FRONTIER || k == AZD_CTR_MAX_DEPTH || k == AZD_CTR_TICKS_MAX_CALL) out[k] = std::max<uint64_t>(out[k], v);
-            else out[k] += v;
-        }
-    }
-    uint64_t failed = 0;
-    for (uint32_t f : fl) failed += f != 0;
-    out[AZD_CTR_FAILED_AGENTS] = failed;
-    return AZD_OK;
-}
-
-int azd_engine_agent_counters(azd_engine *e, uint64_t *out) {
-    if (!e || !out) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipMemcpy(out, e->a.counters, (size_t)e->a.B * azd::NUM_COUNTERS * 8, hipMemcpyDeviceToHost));
-    return AZD_OK;
-}
-int azd_engine_agent_counters_per_agent(azd_engine *e) { return e ? (e->counters_by_wave ? 0 : 1) : AZD_ERR_INVALID_ARGUMENT; }
-
-int azd_engine_set_timing(azd_engine *e, int enabled) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    e->timing = enabled != 0;
-    e->rollout_ms = e->evaluator_ms = 0;
-    e->rollout_launches = 0;
-    return AZD_OK;
-}
-int azd_engine_timing(azd_engine *e, double *tree_ms, double *evaluator_ms, uint64_t *tree_launches) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (tree_ms) *tree_ms = e->rollout_ms;
-    if (evaluator_ms) *evaluator_ms = e->evaluator_ms;
-    if (tree_launches) *tree_launches = e->rollout_launches;
-    return AZD_OK;
-}
-void *azd_engine_stream(azd_engine *e) { return e ? (void *)e->stream : nullptr; }
-int azd_engine_pool_utilisation(azd_engine *e, double *eval_busy, double *search_busy) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (eval_busy) *eval_busy = e->pool_util_eval;
-    if (search_busy) *search_busy = e->pool_util_search;
-    return AZD_OK;
-}
-int azd_engine_pool_groups(azd_engine *e, int *members, int *groups, int *waves_per_slot) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (members) *members = e->pool_grp_g;
-    if (groups) *groups = e->pool_grp_groups;
-    if (waves_per_slot) *waves_per_slot = e->pool_grp_w;
-    return AZD_OK;
-}
-int azd_engine_pool_agent_finish(azd_engine *e, uint64_t *ticks_out) {
-    if (!e || !ticks_out) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ENTER(e);
-    if (!e->pool.stamp) {
-        azd::g_last_error = "pool_agent_finish: this engine has run no pool step";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipMemcpy(ticks_out, e->pool.stamp, (size_t)e->a.B * 8, hipMemcpyDeviceToHost));
-    return AZD_OK;
-}
-int azd_engine_pool_split(azd_engine *e, int *eval_wgs, int *search_wgs) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (eval_wgs) *eval_wgs = e->pool_eval_wgs;
-    if (search_wgs) *search_wgs = e->pool_search_wgs;
-    return AZD_OK;
-}
-int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks) {
-    if (!out || n_blocks <= 0) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ST(azd::device_ok(device));
-    AZD_HIP(hipSetDevice(device));
-    uint32_t *d = nullptr;
-    AZD_HIP(hipMalloc(&d, (size_t)n_blocks * 4));
-    azd::launch_probe_xcc(d, n_blocks, nullptr);
-    hipError_t he = hipDeviceSynchronize();
-    if (he == hipSuccess) he = hipMemcpy(out, d, (size_t)n_blocks * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (he != hipSuccess) return azd::hip_fail(he, "probe_xcc");
-    return AZD_OK;
-}
-// The LDS plan of the searcher-only pool step for a configuration (AZD_ENGINE_EXT_POOL_STEP, or a dense-graph engine with
-// AZD_ENGINE_DENSE_AH_WIDE, whose pool step is planned by what the LDS holds too): wavefronts per searcher workgroup and bytes of
-// LDS a workgroup takes, its static blocks included.  Arithmetic only: no device is touched.
-int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes) {
-    if (!cfg || !waves || !lds_bytes) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ST(check_engine_config(cfg));
-    const bool ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0;
-    if (!(cfg->flags & AZD_ENGINE_EXT_POOL_STEP) && !ah_wide) {
-        azd::g_last_error = "azd_debug_ext_pool_plan: the configuration does not set AZD_ENGINE_EXT_POOL_STEP";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    azd::Arenas a;
-    memset(&a, 0, sizeof(a));
-    a.space = ah_wide ? azd::SPACE_DENSE : azd::SPACE_RAMSEY;
-    if (ah_wide) a.lam_lo = 2.0; // (as azd_engine_create marks the engine for space_ops())
-    a.n = cfg->n;
-    a.B = cfg->batch;
-    a.node_cap = cfg->node_capacity > 0 ? (uint32_t)cfg->node_capacity : 4096u;
-    if (ah_wide) a.KW = dense_device_key_words(cfg->max_slots);
-    else ramsey_shape(cfg, &a);
-    const azd::SpaceOps *ops = azd::space_ops(a);
-    const ExtPoolForm *xf = ext_pool_form(ah_wide);
-    const char *why = "";
-    uint32_t dyn_stride = 0;
-    size_t dyn_bytes = 0;
-    int w = ops->waves_max;
-    while (w > xf->waves_min && !ops->pool_search_plan(a, w, &dyn_stride, &dyn_bytes, &why)) w -= 1;
-    if (!ops->pool_search_plan(a, w, &dyn_stride, &dyn_bytes, &why)) {
-        azd::g_last_error = why;
-        return AZD_ERR_UNSUPPORTED;
-    }
-    *waves = w;
-    *lds_bytes = dyn_bytes + azd::POOL_SEARCH_STATIC_LDS;
-    return AZD_OK;
-}
-int azd_engine_step_form(azd_engine *e, int *form, const char **reason) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (form) *form = e->step_form;
-    if (reason) *reason = e->step_reason.c_str();
-    return AZD_OK;
-}
-
-int azd_debug_probe_math(int device, const float *in, float *out, int n) {
-    if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ST(azd::device_ok(device));
-    AZD_HIP(hipSetDevice(device));
-    float *d_in = nullptr, *d_out = nullptr;
-    AZD_HIP(hipMalloc(&d_in, (size_t)n * 8));
-    AZD_HIP(hipMalloc(&d_out, (size_t)n * 16));
-    AZD_HIP(hipMemcpy(d_in, in, (size_t)n * 8, hipMemcpyHostToDevice));
-    azd::launch_probe_math(d_in, d_out, n, nullptr);
-    hipError_t he = hipDeviceSynchronize();
-    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (he != hipSuccess) return azd::hip_fail(he, "probe_math");
-    return AZD_OK;
-}
-
-int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, int reps, int full, double *lambda_1,
-                         int *matching_size, float *ms) {
-    if (!parents || !lambda_1 || !matching_size || n < 4 || n > AZD_C21_MAX_N || count <= 0 || reps <= 0)
-        return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ST(azd::device_ok(device));
-    AZD_HIP(hipSetDevice(device));
-    for (int i = 0; i < count; ++i) {
-        const uint8_t *p = parents + (size_t)i * n;
-        if (p[0] != 0 || p[n - 1] != 0) return AZD_ERR_INVALID_ARGUMENT;
-        for (int v = 1; v < n; ++v)
-            if (p[v] >= v) return AZD_ERR_INVALID_ARGUMENT;
-    }
-    uint8_t *d_p = nullptr;
-    double *d_l = nullptr;
-    int *d_m = nullptr;
-    hipEvent_t e0, e1;
-    AZD_HIP(hipMalloc(&d_p, (size_t)count * n));
-    AZD_HIP(hipMalloc(&d_l, (size_t)count * 8));
-    AZD_HIP(hipMalloc(&d_m, (size_t)count * 4));
-    AZD_HIP(hipEventCreate(&e0));
-    AZD_HIP(hipEventCreate(&e1));
-    AZD_HIP(hipMemcpy(d_p, parents, (size_t)count * n, hipMemcpyHostToDevice));
-    azd::launch_probe_cost(d_p, n, count, 1, full, d_l, d_m, nullptr); // warm-up
-    AZD_HIP(hipEventRecord(e0, nullptr));
-    azd::launch_probe_cost(d_p, n, count, reps, full, d_l, d_m, nullptr);
-    AZD_HIP(hipEventRecord(e1, nullptr));
-    hipError_t he = hipDeviceSynchronize();
-    float t = 0.f;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    if (he == hipSuccess) he = hipMemcpy(lambda_1, d_l, (size_t)count * 8, hipMemcpyDeviceToHost);
-    if (he == hipSuccess) he = hipMemcpy(matching_size, d_m, (size_t)count * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_p);
-    (void)hipFree(d_l);
-    (void)hipFree(d_m);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (he != hipSuccess) return azd::hip_fail(he, "probe_cost");
-    if (ms) *ms = t;
-    return AZD_OK;
-}
-
-// ------------------------------------------------------------------ Aouchiche-Hansen cost of the dense-graph space
-static_assert(sizeof(azd_dense_ah_cost_t) == sizeof(azd::DenseAhCost) && offsetof(azd_dense_ah_cost_t, eval) == offsetof(azd::DenseAhCost, eval),
-              "azd_dense_ah_cost_t mirrors azd::DenseAhCost");
-static_assert(AZD_DENSE_AH_MAX_N == azd::DENSE_AH_MAX_N && AZD_DENSE_AH_WIDE_MAX_N == azd::DENSE_AH_WIDE_MAX_N, "AZD_DENSE_AH_MAX_N, AZD_DENSE_AH_WIDE_MAX_N");
-int azd_dense_ah_cost(const uint64_t *adj, int n, azd_dense_ah_cost_t *out) {
-    if (!out) {
-        azd::g_last_error = "azd_dense_ah_cost: out: null";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (const char *why = azd::dense_ah_check_graph(adj, n)) {
-        azd::g_last_error = std::string("azd_dense_ah_cost: ") + why;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    azd::dense_ah_cost_host(adj, n, reinterpret_cast<azd::DenseAhCost *>(out));
-    return AZD_OK;
-}
-int azd_dense_ah_cost_wide(const uint64_t *adj, int n, azd_dense_ah_cost_t *out) {
-    if (!out) {
-        azd::g_last_error = "azd_dense_ah_cost_wide: out: null";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (const char *why = azd::dense_ah_check_graph_wide(adj, n)) {
-        azd::g_last_error = std::string("azd_dense_ah_cost_wide: ") + why;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    azd::dense_ah_cost_host(adj, n, reinterpret_cast<azd::DenseAhCost *>(out));
-    return AZD_OK;
-}
-// the two probes: the same host side around the 32-row and the 64-row kernel
-static int probe_ah_cost(const char *name, bool wide, int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
-    if (!out || count <= 0 || reps <= 0) {
-        azd::g_last_error = std::string(name) + ": out / count / reps";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    const auto check = wide ? azd::dense_ah_check_graph_wide : azd::dense_ah_check_graph;
-    const auto launch = wide ? azd::launch_probe_ah_cost_wide : azd::launch_probe_ah_cost;
-    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
-        if (const char *why = check(adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n)) {
-            azd::g_last_error = std::string(name) + ": graph " + std::to_string(i) + ": " + why;
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    AZD_ST(azd::device_ok(device));
-    AZD_HIP(hipSetDevice(device));
-    uint64_t *d_adj = nullptr;
-    azd::DenseAhCost *d_out = nullptr;
-    hipEvent_t e0, e1;
-    AZD_HIP(hipMalloc(&d_adj, (size_t)count * n * 8));
-    AZD_HIP(hipMalloc(&d_out, (size_t)count * sizeof(azd::DenseAhCost)));
-    AZD_HIP(hipEventCreate(&e0));
-    AZD_HIP(hipEventCreate(&e1));
-    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
-    launch(d_adj, n, count, 1, d_out, nullptr); // warm-up
-    AZD_HIP(hipEventRecord(e0, nullptr));
-    launch(d_adj, n, count, reps, d_out, nullptr);
-    AZD_HIP(hipEventRecord(e1, nullptr));
-    hipError_t he = hipDeviceSynchronize();
-    float t = 0.f;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseAhCost), hipMemcpyDeviceToHost);
-    (void)hipFree(d_adj);
-    (void)hipFree(d_out);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (he != hipSuccess) return azd::hip_fail(he, "probe_ah_cost");
-    if (ms) *ms = t;
-    return AZD_OK;
-}
-int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
-    return probe_ah_cost("azd_debug_probe_ah_cost", false, device, adj, n, count, reps, out, ms);
-}
-int azd_debug_probe_ah_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
-    return probe_ah_cost("azd_debug_probe_ah_cost_wide", true, device, adj, n, count, reps, out, ms);
-}
-int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
-    if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;
-    AZD_ST(azd::device_ok(device));
-    AZD_HIP(hipSetDevice(device));
-    double *d_in = nullptr, *d_out = nullptr;
-    AZD_HIP(hipMalloc(&d_in, (size_t)n * 16));
-    AZD_HIP(hipMalloc(&d_out, (size_t)n * 24));
-    AZD_HIP(hipMemcpy(d_in, in, (size_t)n * 16, hipMemcpyHostToDevice));
-    azd::launch_probe_math_f64(d_in, d_out, n, nullptr);
-    hipError_t he = hipDeviceSynchronize();
-    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)n * 24, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (he != hipSuccess) return azd::hip_fail(he, "probe_math_f64");
-    return AZD_OK;
-}
-
-// ------------------------------------------------------------------ c21 root policy (host)
-// 04-c21-tree.rs:172-206 applied to node_data() (tree/mod.rs:302-307: BTreeMap order, i.e. keys
-// compared lexicographically over their ascending elements; n[0] is the root).
-static bool key_less(const uint64_t *x, const uint64_t *y, int KW) {
-    // d = lowest differing action id; the set holding d is smaller iff the other has an element > d
-    for (int w = 0; w < KW; ++w) {
-        uint64_t diff = x[w] ^ y[w];
-        if (!diff) continue;
-        int b = __builtin_ctzll(diff);
-        bool x_has = (x[w] >> b) & 1ull;
-        const uint64_t *other = x_has ? y : x;
-        bool other_has_more = (b < 63 ? (other[w] >> (b + 1)) != 0 : false);
-        for (int w2 = w + 1; w2 < KW && !other_has_more; ++w2) other_has_more = other[w2] != 0;
-        // x_has: x < y iff y continues; else y has d: x < y iff x does NOT continue (x is a proper prefix)
-        return x_has ? other_has_more : !other_has_more;
-    }
-    return false;
-}
-
-int azd_c21_modify_roots(azd_engine *e, uint64_t seed, uint64_t epoch, int kmin, int kmax, uint8_t *parents_out,
-                         uint64_t *permitted_out) {
-    if (!e || !parents_out || !permitted_out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->a.space != azd::SPACE_C21 || e->a.path_kind != azd::PATH_SET) return AZD_ERR_UNSUPPORTED;
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    const azd::Arenas &a = e->a;
-    const int B = a.B, KW = a.KW, n = a.n;
-    std::vector<uint32_t> n_nodes((size_t)B);
-    AZD_HIP(hipMemcpy(n_nodes.data(), a.n_nodes, (size_t)B * 4, hipMemcpyDeviceToHost));
-    std::vector<uint8_t> rp((size_t)B * azd::PARENTS_STRIDE);
-    std::vector<uint64_t> rm((size_t)B * KW);
-    AZD_HIP(hipMemcpy(rp.data(), a.root_parents, rp.size(), hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(rm.data(), a.root_perm, rm.size() * 8, hipMemcpyDeviceToHost));
-    uint32_t max_nodes = 0;
-    for (uint32_t v : n_nodes) max_nodes = std::max(max_nodes, v);
-    std::vector<azd::NodeRec> nodes((size_t)max_nodes);
-    std::vector<uint64_t> keys((size_t)max_nodes * KW);
-    const uint64_t domain = azd::DOMAIN_RESET ^ (epoch << 32);
-    // (parent, child) of an action id
-    auto act = [&](uint8_t *par, uint64_t *perm, int aid) {
-        int c = 2;
-        while (c * (c + 1) / 2 - 1 <= aid) ++c;
-        int p = aid - (c * (c - 1) / 2 - 1);
-        par[c] = (uint8_t)p;
-        for (int u = 0; u < c; ++u) {
-            int id = c * (c - 1) / 2 + u - 1;
-            perm[id >> 6] &= ~(1ull << (id & 63));
-        }
-    };
-    std::vector<uint32_t> keep;
-    for (int i = 0; i < B; ++i) {
-        const uint64_t agent = e->cfg.first_agent + (uint64_t)i;
-        const uint32_t nn = n_nodes[(size_t)i];
-        AZD_HIP(hipMemcpy(nodes.data(), a.nodes + (size_t)i * a.node_cap, (size_t)nn * sizeof(azd::NodeRec), hipMemcpyDeviceToHost));
-        AZD_HIP(hipMemcpy(keys.data(), a.keys + (size_t)i * a.node_cap * KW, (size_t)nn * KW * 8, hipMemcpyDeviceToHost));
-        uint8_t par[azd::PARENTS_STRIDE];
-        uint64_t perm[azd::MAX_KW] = {0, 0, 0, 0};
-        memcpy(par, &rp[(size_t)i * azd::PARENTS_STRIDE], azd::PARENTS_STRIDE);
-        for (int w = 0; w < KW; ++w) perm[w] = rm[(size_t)i * KW + w];
-        uint8_t *po = parents_out + (size_t)i * n;
-        uint64_t *mo = permitted_out + (size_t)i * KW;
-        const float c_root = nodes[0].c, c_root_star = nodes[0].c_star;
-        const uint64_t r0 = azd::stream_key(seed, domain, agent, 0), r1 = azd::stream_key(seed, domain, agent, 1);
-        int k_new;
-        keep.clear();
-        if (c_root == c_root_star) {
-            int kcur = 0;
-            for (int w = 0; w < KW; ++w) kcur += __builtin_popcountll(perm[w]);
-            if (kcur == kmax) {
-                int k = kmin + (int)azd::draw_below(r1, (uint32_t)(kmax - kmin + 1));
-                azd::c21_fresh_root(seed, domain, agent, n, k, po, mo);
-                continue;
-            }
-            for (uint32_t v = 0; v < nn; ++v)
-                if (nodes[v].c == c_root) keep.push_back(v);
-            k_new = kcur + (int)azd::draw_below(r1, (uint32_t)(kmax - kcur + 1));
-        } else {
-            const float thr = (c_root + 3.0f * c_root_star) / 4.0f;
-            for (uint32_t v = 0; v < nn; ++v)
-                if (nodes[v].c <= thr) keep.push_back(v);
-            k_new = kmin + (int)azd::draw_below(r1, (uint32_t)(kmax - kmin + 1));
-        }
-        const uint32_t r = azd::draw_below(r0, (uint32_t)keep.size());
-        std::nth_element(keep.begin(), keep.begin() + r, keep.end(), [&](uint32_t x, uint32_t y) {
-            return key_less(&keys[(size_t)x * KW], &keys[(size_t)y * KW], KW);
-        });
-        const uint64_t *key = &keys[(size_t)keep[r] * KW];
-        for (int w = 0; w < KW; ++w) {
-            uint64_t bits = key[w];
-            while (bits) {
-                int b = __builtin_ctzll(bits);
-                bits &= bits - 1;
-                act(par, perm, w * 64 + b);
-            }
-        }
-        memcpy(po, par, (size_t)n);
-        azd::c21_shuffle_permitted(seed, domain, agent, n, k_new, mo);
-    }
-    return AZD_OK;
 }
 
 } // extern "C"

@@ -1,0 +1,244 @@
+// engine_probes.hip -- the azd_debug_* entries (probes and test hooks) and the host entries of the Aouchiche-Hansen cost.
+#include "engine_impl.h"
+
+extern "C" {
+
+int azd_debug_mlp_gradients(azd_evaluator *ev, int batch, const float *states, const float *observations, const float *action_weights,
+                            float *grads_out, float *loss) {
+    if (!ev || batch <= 0 || !states || !observations || !action_weights || !grads_out) return AZD_ERR_INVALID_ARGUMENT;
+    AZD_ST(ev->ensure_staging(batch));
+    size_t sb = (size_t)batch * ev->state_dim * 4, pb = (size_t)batch * ev->action_dim * 4;
+    AZD_HIP(hipMemcpyAsync(ev->d_states, states, sb, hipMemcpyHostToDevice, ev->own_stream));
+    AZD_HIP(hipMemcpyAsync(ev->d_obs, observations, pb, hipMemcpyHostToDevice, ev->own_stream));
+    AZD_HIP(hipMemcpyAsync(ev->d_w, action_weights, pb, hipMemcpyHostToDevice, ev->own_stream));
+    return ev->debug_gradients(batch, ev->d_states, ev->d_obs, ev->d_w, grads_out, loss, ev->own_stream);
+}
+int azd_debug_write_predictions_gathered(azd_evaluator *ev, int max_rows, const uint32_t *rows, int n_rows, const float *states, int n_state_rows,
+                                         float *predictions) {
+    if (!ev || max_rows < 1 || n_rows < 0 || n_rows > max_rows || (n_rows > 0 && !rows) || !states || n_state_rows < 1 || !predictions)
+        return AZD_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < n_rows; ++i)
+        if (rows[i] >= (uint32_t)n_state_rows) {
+            azd::g_last_error = "azd_debug_write_predictions_gathered: a row index is not below n_state_rows";
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+    return ev->debug_write_predictions_gathered(max_rows, rows, n_rows, states, n_state_rows, predictions);
+}
+int azd_debug_hash_stream_via_evaluators(azd_evaluator *ev, int on) { return ev ? ev->debug_serve_from_pool(on) : AZD_ERR_INVALID_ARGUMENT; }
+// Test entry: rows of the evaluator as the CU-resident step forms compute them (mlp_tile_task; k_tile_forward), for `rows` state
+// vectors given by the host.  Needs an MLP evaluator the pool step can serve (the plan lays the rows out in LDS).
+int azd_engine_debug_tile_forward(azd_engine *e, const float *states, float *predictions, int rows) {
+    if (!e || !states || !predictions || rows < 1) return AZD_ERR_INVALID_ARGUMENT;
+    AZD_ENTER(e);
+    azd::FusedEval fe;
+    azd::PoolArgs pool = e->pool;
+    uint32_t dyn_stride = 0;
+    size_t dyn_bytes = 0;
+    const char *why = "";
+    if (e->a.space == azd::SPACE_DENSE || !e->ev->fused_desc(&fe) || fe.kind != 3 || !e->ops->pool_plan(e->a, fe, &pool, &dyn_stride, &dyn_bytes, &why)) {
+        azd::g_last_error = "debug_tile_forward: needs the c21 or the Ramsey space with an MLP evaluator the pool step can serve";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    float *d_in = nullptr, *d_out = nullptr;
+    hipError_t he = hipMalloc(&d_in, (size_t)rows * e->a.S * 4);
+    const char *what = "hipMalloc";
+    if (he == hipSuccess) he = hipMalloc(&d_out, (size_t)rows * e->a.A * 4);
+    if (he == hipSuccess) what = "hipMemcpyAsync", he = hipMemcpyAsync(d_in, states, (size_t)rows * e->a.S * 4, hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) what = "k_tile_forward", he = azd::launch_tile_forward(fe, pool, rows, d_in, d_out, e->stream);
+    if (he == hipSuccess) what = "hipMemcpyAsync", he = hipMemcpyAsync(predictions, d_out, (size_t)rows * e->a.A * 4, hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) what = "hipStreamSynchronize", he = hipStreamSynchronize(e->stream);
+    else (void)hipStreamSynchronize(e->stream); // nothing of this call may still be running on the buffers freed below
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return he == hipSuccess ? AZD_OK : azd::hip_fail(he, what);
+}
+int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks) {
+    if (!out || n_blocks <= 0) return AZD_ERR_INVALID_ARGUMENT;
+    AZD_ST(azd::device_ok(device));
+    AZD_HIP(hipSetDevice(device));
+    uint32_t *d = nullptr;
+    AZD_HIP(hipMalloc(&d, (size_t)n_blocks * 4));
+    azd::launch_probe_xcc(d, n_blocks, nullptr);
+    hipError_t he = hipDeviceSynchronize();
+    if (he == hipSuccess) he = hipMemcpy(out, d, (size_t)n_blocks * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_xcc");
+    return AZD_OK;
+}
+// The LDS plan of the searcher-only pool step for a configuration (AZD_ENGINE_EXT_POOL_STEP, or a dense-graph engine with
+// AZD_ENGINE_DENSE_AH_WIDE, whose pool step is planned by what the LDS holds too): wavefronts per searcher workgroup and bytes of
+// LDS a workgroup takes, its static blocks included.  Arithmetic only: no device is touched.
+int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes) {
+    if (!cfg || !waves || !lds_bytes) return AZD_ERR_INVALID_ARGUMENT;
+    AZD_ST(check_engine_config(cfg));
+    const bool ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0;
+    if (!(cfg->flags & AZD_ENGINE_EXT_POOL_STEP) && !ah_wide) {
+        azd::g_last_error = "azd_debug_ext_pool_plan: the configuration does not set AZD_ENGINE_EXT_POOL_STEP";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    const TierDesc *const tier = engine_tier(cfg);
+    azd::Arenas a;
+    engine_shape(cfg, tier, &a);
+    const azd::SpaceOps *ops = tier->ops;
+    const ExtPoolForm *xf = tier->ext;
+    const char *why = "";
+    uint32_t dyn_stride = 0;
+    size_t dyn_bytes = 0;
+    int w = ops->waves_max;
+    while (w > xf->waves_min && !ops->pool_search_plan(a, w, &dyn_stride, &dyn_bytes, &why)) w -= 1;
+    if (!ops->pool_search_plan(a, w, &dyn_stride, &dyn_bytes, &why)) {
+        azd::g_last_error = why;
+        return AZD_ERR_UNSUPPORTED;
+    }
+    *waves = w;
+    *lds_bytes = dyn_bytes + azd::POOL_SEARCH_STATIC_LDS;
+    return AZD_OK;
+}
+int azd_debug_probe_math(int device, const float *in, float *out, int n) {
+    if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;
+    AZD_ST(azd::device_ok(device));
+    AZD_HIP(hipSetDevice(device));
+    float *d_in = nullptr, *d_out = nullptr;
+    AZD_HIP(hipMalloc(&d_in, (size_t)n * 8));
+    AZD_HIP(hipMalloc(&d_out, (size_t)n * 16));
+    AZD_HIP(hipMemcpy(d_in, in, (size_t)n * 8, hipMemcpyHostToDevice));
+    azd::launch_probe_math(d_in, d_out, n, nullptr);
+    hipError_t he = hipDeviceSynchronize();
+    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_math");
+    return AZD_OK;
+}
+
+int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, int reps, int full, double *lambda_1,
+                         int *matching_size, float *ms) {
+    if (!parents || !lambda_1 || !matching_size || n < 4 || n > AZD_C21_MAX_N || count <= 0 || reps <= 0)
+        return AZD_ERR_INVALID_ARGUMENT;
+    AZD_ST(azd::device_ok(device));
+    AZD_HIP(hipSetDevice(device));
+    for (int i = 0; i < count; ++i) {
+        const uint8_t *p = parents + (size_t)i * n;
+        if (p[0] != 0 || p[n - 1] != 0) return AZD_ERR_INVALID_ARGUMENT;
+        for (int v = 1; v < n; ++v)
+            if (p[v] >= v) return AZD_ERR_INVALID_ARGUMENT;
+    }
+    uint8_t *d_p = nullptr;
+    double *d_l = nullptr;
+    int *d_m = nullptr;
+    hipEvent_t e0, e1;
+    AZD_HIP(hipMalloc(&d_p, (size_t)count * n));
+    AZD_HIP(hipMalloc(&d_l, (size_t)count * 8));
+    AZD_HIP(hipMalloc(&d_m, (size_t)count * 4));
+    AZD_HIP(hipEventCreate(&e0));
+    AZD_HIP(hipEventCreate(&e1));
+    AZD_HIP(hipMemcpy(d_p, parents, (size_t)count * n, hipMemcpyHostToDevice));
+    azd::launch_probe_cost(d_p, n, count, 1, full, d_l, d_m, nullptr); // warm-up
+    AZD_HIP(hipEventRecord(e0, nullptr));
+    azd::launch_probe_cost(d_p, n, count, reps, full, d_l, d_m, nullptr);
+    AZD_HIP(hipEventRecord(e1, nullptr));
+    hipError_t he = hipDeviceSynchronize();
+    float t = 0.f;
+    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
+    if (he == hipSuccess) he = hipMemcpy(lambda_1, d_l, (size_t)count * 8, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(matching_size, d_m, (size_t)count * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d_p);
+    (void)hipFree(d_l);
+    (void)hipFree(d_m);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_cost");
+    if (ms) *ms = t;
+    return AZD_OK;
+}
+
+// ------------------------------------------------------------------ Aouchiche-Hansen cost of the dense-graph space
+static_assert(sizeof(azd_dense_ah_cost_t) == sizeof(azd::DenseAhCost) && offsetof(azd_dense_ah_cost_t, eval) == offsetof(azd::DenseAhCost, eval),
+              "azd_dense_ah_cost_t mirrors azd::DenseAhCost");
+static_assert(AZD_DENSE_AH_MAX_N == azd::DENSE_AH_MAX_N && AZD_DENSE_AH_WIDE_MAX_N == azd::DENSE_AH_WIDE_MAX_N, "AZD_DENSE_AH_MAX_N, AZD_DENSE_AH_WIDE_MAX_N");
+int azd_dense_ah_cost(const uint64_t *adj, int n, azd_dense_ah_cost_t *out) {
+    if (!out) {
+        azd::g_last_error = "azd_dense_ah_cost: out: null";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (const char *why = azd::dense_ah_check_graph(adj, n)) {
+        azd::g_last_error = std::string("azd_dense_ah_cost: ") + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    azd::dense_ah_cost_host(adj, n, reinterpret_cast<azd::DenseAhCost *>(out));
+    return AZD_OK;
+}
+int azd_dense_ah_cost_wide(const uint64_t *adj, int n, azd_dense_ah_cost_t *out) {
+    if (!out) {
+        azd::g_last_error = "azd_dense_ah_cost_wide: out: null";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (const char *why = azd::dense_ah_check_graph_wide(adj, n)) {
+        azd::g_last_error = std::string("azd_dense_ah_cost_wide: ") + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    azd::dense_ah_cost_host(adj, n, reinterpret_cast<azd::DenseAhCost *>(out));
+    return AZD_OK;
+}
+// the two probes: the same host side around the 32-row and the 64-row kernel
+static int probe_ah_cost(const char *name, bool wide, int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
+    if (!out || count <= 0 || reps <= 0) {
+        azd::g_last_error = std::string(name) + ": out / count / reps";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    const auto check = wide ? azd::dense_ah_check_graph_wide : azd::dense_ah_check_graph;
+    const auto launch = wide ? azd::launch_probe_ah_cost_wide : azd::launch_probe_ah_cost;
+    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
+        if (const char *why = check(adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n)) {
+            azd::g_last_error = std::string(name) + ": graph " + std::to_string(i) + ": " + why;
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+    AZD_ST(azd::device_ok(device));
+    AZD_HIP(hipSetDevice(device));
+    uint64_t *d_adj = nullptr;
+    azd::DenseAhCost *d_out = nullptr;
+    hipEvent_t e0, e1;
+    AZD_HIP(hipMalloc(&d_adj, (size_t)count * n * 8));
+    AZD_HIP(hipMalloc(&d_out, (size_t)count * sizeof(azd::DenseAhCost)));
+    AZD_HIP(hipEventCreate(&e0));
+    AZD_HIP(hipEventCreate(&e1));
+    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
+    launch(d_adj, n, count, 1, d_out, nullptr); // warm-up
+    AZD_HIP(hipEventRecord(e0, nullptr));
+    launch(d_adj, n, count, reps, d_out, nullptr);
+    AZD_HIP(hipEventRecord(e1, nullptr));
+    hipError_t he = hipDeviceSynchronize();
+    float t = 0.f;
+    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
+    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseAhCost), hipMemcpyDeviceToHost);
+    (void)hipFree(d_adj);
+    (void)hipFree(d_out);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_ah_cost");
+    if (ms) *ms = t;
+    return AZD_OK;
+}
+int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
+    return probe_ah_cost("azd_debug_probe_ah_cost", false, device, adj, n, count, reps, out, ms);
+}
+int azd_debug_probe_ah_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
+    return probe_ah_cost("azd_debug_probe_ah_cost_wide", true, device, adj, n, count, reps, out, ms);
+}
+int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
+    if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;
+    AZD_ST(azd::device_ok(device));
+    AZD_HIP(hipSetDevice(device));
+    double *d_in = nullptr, *d_out = nullptr;
+    AZD_HIP(hipMalloc(&d_in, (size_t)n * 16));
+    AZD_HIP(hipMalloc(&d_out, (size_t)n * 24));
+    AZD_HIP(hipMemcpy(d_in, in, (size_t)n * 16, hipMemcpyHostToDevice));
+    azd::launch_probe_math_f64(d_in, d_out, n, nullptr);
+    hipError_t he = hipDeviceSynchronize();
+    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)n * 24, hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_math_f64");
+    return AZD_OK;
+}
+} // extern "C"

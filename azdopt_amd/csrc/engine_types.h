@@ -99,7 +99,7 @@ enum : uint32_t {
     FLAG_UNREACHABLE = 1u << 5,
     FLAG_NODE_ACTIONS = 1u << 6,
     FLAG_LOOP_GUARD = 1u << 7,
-    // not a failure: the agent sits out the launches of a recovery round (engine.hip: an aborted dense pool launch is completed by
+    // not a failure: the agent sits out the launches of a recovery round (engine_rollout.hip: an aborted dense pool launch is completed by
     // the launch-per-phase kernels, agent by agent from where each one stands); set and cleared by k_park
     FLAG_PARKED = 1u << 30,
 };
@@ -213,10 +213,10 @@ struct Arenas {
     ArgminRec *argmin;
     StatusRec *status;
     int n, A, S, KW, B;
-    int t0, tn;             // launch-per-phase kernels over a SUB-population: agents t0 .. t0 + tn - 1 (tn = 0: all B); see engine.hip
+    int t0, tn;             // launch-per-phase kernels over a SUB-population: agents t0 .. t0 + tn - 1 (tn = 0: all B); see engine_rollout.hip
     float eval_slope;       // squish slope 1/(C_UPPER - C_LOWER), 04-c21-tree.rs:58-74
-    double lam_lo, lam_hi;  // c21: initial bracket of the lambda_1 multisection (c21_host.cpp:c21_lambda_bracket).  Dense-graph space (no
-                            // kernel of it reads them): lam_lo = 1.0 marks an AZD_ENGINE_DENSE_AH engine for the host's dispatch (2.0: with AZD_ENGINE_DENSE_AH_WIDE), else 0
+    double lam_lo, lam_hi;  // c21: initial bracket of the lambda_1 multisection (c21_host.cpp:c21_lambda_bracket); 0 in every other space (no
+                            // kernel of them reads it; the host knows an engine's tier from its descriptor, engine_impl.h: TierDesc)
     // ---- Ramsey space (space_ramsey.inc); unused (null / 0) for c21
     int space;              // SPACE_C21 / SPACE_RAMSEY
     int C, E;               // colours, edges N(N-1)/2;  A = E*C, S = E*(2C+1)
@@ -375,7 +375,7 @@ struct PoolArgs {
 struct StepLaunch {
     int n_calls;
     unsigned long long *log_key;   // [>= n_calls] per-call argmin candidates, all ones when the launch starts (k_argmin_log1 leaves them so)
-    // k_async taking over from an aborted pool launch (engine.hip): [B] calls the agent has completed | 1u << 31 if its last
+    // k_async taking over from an aborted pool launch (engine_rollout.hip): [B] calls the agent has completed | 1u << 31 if its last
     // call ended on a new node whose prediction row / add_actions are still due.  Null: every agent starts at call 0.
     const uint32_t *resume;
     PoolCtl *ctl;                  // pool step: the control block k_argmin_log1 reports the abort flag from and clears; else null

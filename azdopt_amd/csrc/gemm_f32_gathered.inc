@@ -1,6 +1,6 @@
 // gemm_f32_gathered.inc -- included by mlp_kernels.hip (inside namespace azd).
 //
-// The fp32 evaluator of the searcher-only pool step (engine.hip: ext_pool_run under AZD_ENGINE_EXT_POOL_F32): one layer
+// The fp32 evaluator of the searcher-only pool step (engine_rollout.hip: ext_pool_run under AZD_ENGINE_EXT_POOL_F32): one layer
 // Y = act(A . W^T + b) over a row list whose length lives in device memory, on v_mfma_f32_32x32x2_f32.  The EXT conventions of
 // k_gemm16<BN, true> (gemm_bf16_glds.inc): the row count is *m_dev clamped to max_rows, the grid is sized for max_rows and the
 // blocks beyond the tiles of *m_dev rows leave at once (a count of 0: nothing happens), row i of A is row rows_in[i] of the array

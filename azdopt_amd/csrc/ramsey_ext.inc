@@ -1,5 +1,5 @@
 // ramsey_ext.inc -- the Ramsey side of the searcher-only pool step (AZD_ENGINE_EXT_POOL_STEP; pool_step.inc: k_pool_search, with
-// the evaluator's batched GEMM launches outside the kernel, engine.hip: ext_pool_run): the space policies of the form and the
+// the evaluator's batched GEMM launches outside the kernel, engine_rollout.hip: ext_pool_run): the space policies of the form and the
 // refusals of its plan.  Included inside namespace azd after space_ramsey.inc and pool_step.inc, ahead of launchers.inc, by
 // ramsey_ext_kernels.hip (32-bit wide tier) and ramsey64_ext_kernels.hip (64-bit tier), which say which policies they build.
 

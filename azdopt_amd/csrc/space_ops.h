@@ -21,7 +21,7 @@ struct PhaseOps { // a space's phase unit (tree_kernels.hip, ramsey_kernels.hip,
     // words per root), d_perm again for the other spaces; rp: the engine's root policy (azd_engine_set_root_policy) and its report
     void (*modify_roots)(const Arenas &a, uint64_t seed, uint64_t epoch, uint64_t first_agent, int kmin, int kmax, uint8_t *d_roots,
                          uint64_t *d_perm, uint64_t *d_slots, const RootPolicyArgs &rp, void *stream);
-    // one candidate (agent, node) replayed into the argmin records `a` points at; StatusRec untouched (run-ahead window, engine.hip)
+    // one candidate (agent, node) replayed into the argmin records `a` points at; StatusRec untouched (run-ahead window, engine_rollout.hip)
     void (*argmin_one)(const Arenas &a, int agent, uint32_t node, void *stream);
     bool (*persist_plan)(const Arenas &a, const FusedEval &ev, uint32_t *dyn_stride, size_t *dyn_bytes, const char **why);
     void (*launch_persist)(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, uint32_t *log_node, uint32_t dyn_stride,
@@ -69,7 +69,7 @@ const SpaceOps &dense_ah_wide_ops();                            // ... with its 
 constexpr size_t POOL_SEARCH_STATIC_LDS = 16; // k_pool_search's static LDS (PoolIdle) beside the dynamic region the plans lay out
 
 // ---- the same for every space
-// launch-per-phase form over sub-populations on streams of their own (engine.hip): the candidates of agents a.t0 .. a.t0 + a.tn - 1
+// launch-per-phase form over sub-populations on streams of their own (engine_rollout.hip): the candidates of agents a.t0 .. a.t0 + a.tn - 1
 // since their last inspection go into log_key[*call_ctr] (atomic min), the counter is bumped; replayed by SpaceOps::argmin_log
 void launch_log_candidates(const Arenas &a, unsigned long long *log_key, uint32_t *call_ctr, void *stream);
 // after an aborted pool launch: resume[t] for k_async (StepLaunch::resume) from the trees and PoolArgs::pend
@@ -91,7 +91,7 @@ void launch_probe_ah_cost_wide(const uint64_t *d_adj, int n, int count, int reps
 
 // ---- the evaluator's side of the searcher-only pool step and the recovery of an aborted launch (dense_kernels.hip; for every space that has the form)
 void launch_ext_take(const PoolArgs &pool, uint32_t *rows, uint32_t *home, uint32_t *n, unsigned long long *t0, void *stream);
-// recovery of an aborted launch (engine.hip): park (round >= 0: the agents whose calls are through by that round; -1: the
+// recovery of an aborted launch (engine_rollout.hip): park (round >= 0: the agents whose calls are through by that round; -1: the
 // agents that are not waiting for a row) / unpark (mode 0), and the candidates of round r under the call each agent is really in
 void launch_park(const Arenas &a, const uint32_t *resume, int n_calls, int round, int park, void *stream);
 void launch_log_candidates_resume(const Arenas &a, unsigned long long *log_key, const uint32_t *resume, int n_calls, int round, void *stream);

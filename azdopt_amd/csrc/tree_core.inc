@@ -1726,7 +1726,7 @@ __global__ __launch_bounds__(64) void k_argmin_log1(Arenas a, int n_calls, unsig
     argmin_replay<SP>(a, s, dyn, wt, win_node, 0);
 }
 
-// Run-ahead window (engine.hip): the argmin record as of a call in the middle of a launch -- one candidate replayed into the
+// Run-ahead window (engine_rollout.hip): the argmin record as of a call in the middle of a launch -- one candidate replayed into the
 // records `a` points at (the engine passes a copy of the arenas whose argmin pointers lead to a side buffer); the status
 // block is left alone.
 template <class SP>

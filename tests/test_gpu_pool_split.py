@@ -2,7 +2,7 @@
 
 tests/golden/pool_split_mi355x.json holds, per case, the evaluator / searcher workgroups and the evaluator groups that the FIRST
 roll-out of a fresh engine launched (azd_engine_pool_split, azd_engine_pool_groups), recorded once on an MI355X from the library
-as it stood before the split arithmetic became a function of its own (engine.hip: pool_split).  Trees do not depend on the
+as it stood before the split arithmetic became a function of its own (engine_rollout.hip: pool_split).  Trees do not depend on the
 split, so no parity test sees a slip in that arithmetic; this module does.  Every case sets AZD_POOL_MAX_RESIDENT, so that the
 co-resident capacity is an input and not what the runtime of the day reports; the first roll-out of an engine runs before the
 feedback controller has acted.

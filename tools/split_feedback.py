@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The pool step's split between evaluator and searcher workgroups under the engine's measured feedback (engine.hip: pool_fb:
+"""The pool step's split between evaluator and searcher workgroups under the engine's measured feedback (engine_rollout.hip: pool_fb:
 the busy shares of the two sides are balanced from launch to launch): the trajectory of the split and the rate per epoch, beside
 fixed splits given on the command line.   python tools/split_feedback.py CONFIG [epochs 14] [fixed ev ...]
 CONFIG: A B C D (BASELINE), B8 (8192 agents fp32), X (4096 agents, 384 x 384 model: a shape no sweep was fitted to)"""
