@@ -26,6 +26,7 @@ ENGINE_RAMSEY_U64 = 16  # AZD_ENGINE_RAMSEY_U64: the 64-bit Ramsey tier (n <= 64
 ENGINE_EXT_POOL_STEP = 64  # AZD_ENGINE_EXT_POOL_STEP: Ramsey engines with max_slots > 0: searcher-only pool step, batched GEMMs beside it
 ENGINE_DENSE_AH_WIDE = 256  # AZD_ENGINE_DENSE_AH_WIDE: beside ENGINE_DENSE_AH only: the Aouchiche-Hansen cost up to n = 64 (64-row kernels)
 ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STEP only: that form with an fp32 model (gathered fp32 GEMMs)
+ENGINE_RAMSEY_BIG_CLIQUES = 512  # AZD_ENGINE_RAMSEY_BIG_CLIQUES: beside ENGINE_RAMSEY_U64 only: clique sizes up to 8 (kernels of their own)
 SPACE_C21 = 1
 SPACE_RAMSEY = 2
 SPACE_DENSE = 3
@@ -33,6 +34,7 @@ RAMSEY_MAX_N = 23       # AZD_RAMSEY_MAX_N
 RAMSEY_WIDE_MAX_N = 32  # AZD_RAMSEY_WIDE_MAX_N: a wide Ramsey engine (EngineConfig.max_slots > 0)
 RAMSEY_U64_MAX_N = 64   # AZD_RAMSEY_U64_MAX_N: the 64-bit tier (ENGINE_RAMSEY_U64)
 RAMSEY_U64_NODE_ACTIONS = 512  # AZD_RAMSEY_U64_NODE_ACTIONS: max_slots * (C - 1) of the 64-bit tier
+RAMSEY_BIG_CLIQUE_MAX = 8  # AZD_RAMSEY_BIG_CLIQUE_MAX: the largest forbidden clique under ENGINE_RAMSEY_BIG_CLIQUES (else 5)
 RAMSEY_U64_MAX_ACTIONS = 2304  # E*C of the 64-bit tier (keys of 36 words)
 DENSE_AH_MAX_N = 32     # AZD_DENSE_AH_MAX_N: the Aouchiche-Hansen cost (azd_dense_ah_cost)
 DENSE_AH_WIDE_MAX_N = 64  # AZD_DENSE_AH_WIDE_MAX_N: its 64-row form (azd_dense_ah_cost_wide, ENGINE_DENSE_AH_WIDE)

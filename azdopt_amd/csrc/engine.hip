@@ -64,33 +64,44 @@ static const ExtPoolForm *ext_pool_form(bool dense_space) {
     return dense_space ? &dense : &ramsey;
 }
 
-// The seven kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
+// The eight kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
 // parts: c21 has no searcher-only pool step; the 64-bit Ramsey tier's is joined to the three parts of its phase unit's table.
 static const TierDesc *tier_desc(Tier t) {
     static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops(), PoolSearchOps{}};
     static const SpaceOps ramsey = {ramsey_phase_ops(), ramsey_async_ops(), ramsey_pool_ops(), ramsey_pool_search_ops()};
     static const SpaceOps ramsey64 = {ramsey64_ops(), ramsey64_ops(), ramsey64_ops(), ramsey64_pool_search_ops()};
+    static const SpaceOps ramsey64_big = {ramsey64_big_ops(), ramsey64_big_ops(), ramsey64_big_ops(), ramsey64_big_pool_search_ops()};
     const ExtPoolForm *const xd = ext_pool_form(true), *const xr = ext_pool_form(false);
     static const TierDesc tiers[TIER_COUNT] = {
-        {TIER_C21, SPACE_C21, &c21, nullptr, 0, 0, false, false, false, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr},
-        {TIER_RAMSEY, SPACE_RAMSEY, &ramsey, nullptr, sizeof(RamseyArgminRec), 128, false, false, false, AZD_RAMSEY_MAX_N, 256, 64 * MAX_KW, 0,
+        {TIER_C21, SPACE_C21, &c21, nullptr, 0, 0, false, false, false, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        {TIER_RAMSEY, SPACE_RAMSEY, &ramsey, nullptr, sizeof(RamseyArgminRec), 128, false, false, false, AZD_RAMSEY_MAX_N, 256, 64 * MAX_KW, 0, 5, false,
          "unsupported Ramsey space (need 3 <= n, E <= 256, 2..4 colours, clique sizes 2..5, E*C <= 384)", nullptr, nullptr, nullptr},
         // max_slots > 0: the most permitted edges a root may bring; device keys padded to the widths ramsey_kernels.hip is built for
-        {TIER_RAMSEY_WIDE, SPACE_RAMSEY, &ramsey, xr, sizeof(RamseyWideArgminRec), 128, true, true, false, AZD_RAMSEY_WIDE_MAX_N, 496, 1024, 0,
+        {TIER_RAMSEY_WIDE, SPACE_RAMSEY, &ramsey, xr, sizeof(RamseyWideArgminRec), 128, true, true, false, AZD_RAMSEY_WIDE_MAX_N, 496, 1024, 0, 5, false,
          "unsupported wide Ramsey space (max_slots > 0: need 3 <= n <= 32, 2..4 colours, clique sizes 2..5, E*C <= 1024)",
          "wide Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)", nullptr,
          // (cur_seq holds MAX_NODE_ACTIONS actions; a wide path can be longer)
          "wide Ramsey space (max_slots > 0): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)"},
         // AZD_ENGINE_RAMSEY_U64: uint64_t neighbourhood rows of 64 vertices, keys of RAMSEY_U64_KW words, its own record
         {TIER_RAMSEY_U64, SPACE_RAMSEY, &ramsey64, xr, sizeof(RamseyU64ArgminRec), 512, true, true, false, AZD_RAMSEY_U64_MAX_N, 2016,
-         64 * RAMSEY_U64_KW, AZD_RAMSEY_U64_NODE_ACTIONS,
+         64 * RAMSEY_U64_KW, AZD_RAMSEY_U64_NODE_ACTIONS, 5, false,
          "unsupported 64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64: need 3 <= n <= 64, 2..4 colours, clique sizes 2..5, E*C <= 2304)",
          "64-bit Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)",
          "64-bit Ramsey space: a node holds 512 actions: need max_slots * (C - 1) <= 512 (azd_engine_config::max_slots)",
          "64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)"},
-        {TIER_DENSE, SPACE_DENSE, &dense_ops(), xd, sizeof(DenseArgminRec), 0, false, true, false, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr},
-        {TIER_DENSE_AH, SPACE_DENSE, &dense_ah_ops(), xd, sizeof(DenseAhArgminRec), 0, false, true, true, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr},
-        {TIER_DENSE_AH_WIDE, SPACE_DENSE, &dense_ah_wide_ops(), xd, sizeof(DenseAhWideArgminRec), 0, false, true, true, 0, 0, 0, 0, nullptr, nullptr,
+        // AZD_ENGINE_RAMSEY_BIG_CLIQUES beside AZD_ENGINE_RAMSEY_U64: the same tier over kernels that count cliques up to K8
+        // (ramsey64_big_kernels.hip); the record, the limits and the pool step's form are the 64-bit tier's
+        {TIER_RAMSEY_U64_BIG, SPACE_RAMSEY, &ramsey64_big, xr, sizeof(RamseyU64ArgminRec), 512, true, true, false, AZD_RAMSEY_U64_MAX_N, 2016,
+         64 * RAMSEY_U64_KW, AZD_RAMSEY_U64_NODE_ACTIONS, AZD_RAMSEY_BIG_CLIQUE_MAX, true,
+         "unsupported 64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64 with AZD_ENGINE_RAMSEY_BIG_CLIQUES: need 3 <= n <= 64, 2..4 colours, clique "
+         "sizes 2..8, E*C <= 2304)",
+         "64-bit Ramsey space (AZD_ENGINE_RAMSEY_BIG_CLIQUES): need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)",
+         "64-bit Ramsey space (AZD_ENGINE_RAMSEY_BIG_CLIQUES): a node holds 512 actions: need max_slots * (C - 1) <= 512 (azd_engine_config::max_slots)",
+         "64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64 with AZD_ENGINE_RAMSEY_BIG_CLIQUES): ActionSet paths only (path_kind = AZD_PATH_SET), no "
+         "Layered wrapper (layers <= 1)"},
+        {TIER_DENSE, SPACE_DENSE, &dense_ops(), xd, sizeof(DenseArgminRec), 0, false, true, false, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        {TIER_DENSE_AH, SPACE_DENSE, &dense_ah_ops(), xd, sizeof(DenseAhArgminRec), 0, false, true, true, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        {TIER_DENSE_AH_WIDE, SPACE_DENSE, &dense_ah_wide_ops(), xd, sizeof(DenseAhWideArgminRec), 0, false, true, true, 0, 0, 0, 0, 0, false, nullptr, nullptr,
          nullptr, nullptr},
     };
     return &tiers[t];
@@ -100,7 +111,8 @@ const TierDesc *engine_tier(const azd_engine_config *cfg) {
     if (cfg->space_id == AZD_SPACE_DENSE)
         return tier_desc(cfg->flags & AZD_ENGINE_DENSE_AH_WIDE ? TIER_DENSE_AH_WIDE : cfg->flags & AZD_ENGINE_DENSE_AH ? TIER_DENSE_AH : TIER_DENSE);
     if (cfg->space_id != AZD_SPACE_RAMSEY) return tier_desc(TIER_C21);
-    return tier_desc(cfg->flags & AZD_ENGINE_RAMSEY_U64 ? TIER_RAMSEY_U64 : cfg->max_slots != 0 ? TIER_RAMSEY_WIDE : TIER_RAMSEY);
+    if (cfg->flags & AZD_ENGINE_RAMSEY_U64) return tier_desc(cfg->flags & AZD_ENGINE_RAMSEY_BIG_CLIQUES ? TIER_RAMSEY_U64_BIG : TIER_RAMSEY_U64);
+    return tier_desc(cfg->max_slots != 0 ? TIER_RAMSEY_WIDE : TIER_RAMSEY);
 }
 
 // ------------------------------------------------------------------ simple evaluators
@@ -369,9 +381,26 @@ static int refuse(const char *why) {
 static int check_ramsey_config(const azd_engine_config *cfg, const TierDesc &t) {
     bool ok = cfg->batch > 0 && cfg->n >= 3 && cfg->n <= t.max_n && cfg->n_colors >= 2 && cfg->n_colors <= 4;
     if (ok) {
-        for (int c = 0; c < cfg->n_colors; ++c) ok = ok && cfg->clique_sizes[c] >= 2 && cfg->clique_sizes[c] <= 5;
-        ok = ok && ramsey_edges(cfg->n) <= t.max_edges && ramsey_action_dim(cfg->n, cfg->n_colors) <= t.max_actions;
+        for (int c = 0; c < cfg->n_colors; ++c) ok = ok && cfg->clique_sizes[c] >= 2 && cfg->clique_sizes[c] <= t.max_clique;
     }
+    if (ok && t.clique_overflow_rule) {
+        // RamseyCounts::new (ramsey_counts/mod.rs:47-62) adds the per-edge counts of a colour's adjacent pairs into an i32 BEFORE it
+        // divides by C(s,2): a root monochromatic in colour c brings C(s,2) * C(n,s)
+        for (int c = 0; c < cfg->n_colors; ++c) {
+            const int64_t s = cfg->clique_sizes[c];
+            int64_t binom = 1; // C(n, s), exact at every step (C(n, k) * (n - k) is divisible by k + 1); <= C(64, 8) = 4.4e9
+            for (int64_t k = 0; k < s; ++k) binom = binom * (cfg->n - k) / (k + 1);
+            if (s * (s - 1) / 2 * binom > (int64_t)INT32_MAX) {
+                char why[256];
+                snprintf(why, sizeof(why),
+                         "AZD_ENGINE_RAMSEY_BIG_CLIQUES: colour %d (clique size %d at n = %d) is beyond the reference's i32 bound: need "
+                         "C(s,2) * C(n,s) <= 2^31 - 1 for every colour (size 7: n <= 50, size 8: n <= 39)",
+                         c, (int)s, cfg->n);
+                return refuse(why);
+            }
+        }
+    }
+    if (ok) ok = ramsey_edges(cfg->n) <= t.max_edges && ramsey_action_dim(cfg->n, cfg->n_colors) <= t.max_actions;
     if (!ok) return refuse(t.e_range);
     if (!t.cap_from_slots) return AZD_OK;
     if (cfg->max_slots < 1 || cfg->max_slots > ramsey_edges(cfg->n)) return refuse(t.e_slots);
@@ -382,6 +411,10 @@ static int check_ramsey_config(const azd_engine_config *cfg, const TierDesc &t) 
 int check_engine_config(const azd_engine_config *cfg) {
     const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
     const bool dense = cfg->space_id == AZD_SPACE_DENSE;
+    // clique sizes up to 8: a second flag beside the 64-bit tier's, never a tier chosen from the sizes
+    if ((cfg->flags & AZD_ENGINE_RAMSEY_BIG_CLIQUES) && (!ramsey || !(cfg->flags & AZD_ENGINE_RAMSEY_U64)))
+        return refuse("flags: AZD_ENGINE_RAMSEY_BIG_CLIQUES is valid only beside AZD_ENGINE_RAMSEY_U64 (the 64-bit tier of the Ramsey space, "
+                      "AZD_SPACE_RAMSEY with max_slots > 0, whose kernels for clique sizes up to 8 it asks for)");
     const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
     const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
     if (dense_ah_wide) {
@@ -409,7 +442,7 @@ int check_engine_config(const azd_engine_config *cfg) {
             return refuse("unsupported dense-graph space (need 4 <= n <= 64, no Layered wrapper, max_slots <= 1024, 0 <= dense_p <= 1)");
     } else if (cfg->flags & AZD_ENGINE_RAMSEY_U64) { // the 64-bit tier: asked for by name, never chosen from the sizes
         if (!ramsey || cfg->max_slots == 0) return refuse("AZD_ENGINE_RAMSEY_U64 needs a Ramsey space (AZD_SPACE_RAMSEY) with max_slots > 0");
-        AZD_ST(check_ramsey_config(cfg, *tier_desc(TIER_RAMSEY_U64)));
+        AZD_ST(check_ramsey_config(cfg, *engine_tier(cfg))); // (... and its big-clique kernels by a second flag beside the first)
     } else if (ramsey) { // (max_slots != 0: wide)
         AZD_ST(check_ramsey_config(cfg, *tier_desc(cfg->max_slots != 0 ? TIER_RAMSEY_WIDE : TIER_RAMSEY)));
     } else if (cfg->space_id != AZD_SPACE_C21 || cfg->n < 4 || cfg->n > AZD_C21_MAX_N || cfg->batch <= 0) {
@@ -458,7 +491,7 @@ void engine_shape(const azd_engine_config *cfg, const TierDesc *t, Arenas *ap) {
         a.A = ramsey_action_dim(cfg->n, a.C);
         a.S = ramsey_state_dim(cfg->n, a.C);
         a.KW = ramsey_key_words(cfg->n, a.C);
-        if (t->padded_keys) a.KW = t->id == TIER_RAMSEY_U64 ? RAMSEY_U64_KW : a.A <= 640 ? 10 : 16; // RamseyWideSpace<10 / 16>; one width for the 64-bit tier
+        if (t->padded_keys) a.KW = t->id == TIER_RAMSEY_U64 || t->id == TIER_RAMSEY_U64_BIG ? RAMSEY_U64_KW : a.A <= 640 ? 10 : 16; // RamseyWideSpace<10 / 16>; one width for the 64-bit tier
         for (int c = 0; c < a.C; ++c) {
             a.sizes[c] = cfg->clique_sizes[c];
             a.cweights[c] = cfg->color_weights[c];

@@ -42,7 +42,7 @@ struct ExtPoolForm {
 
 // The kind of engine a configuration asks for, and what the host code goes by for it: chosen once (engine_tier, after
 // check_engine_config has accepted the configuration), never re-derived from how the arenas were filled.
-enum Tier { TIER_C21, TIER_RAMSEY, TIER_RAMSEY_WIDE, TIER_RAMSEY_U64, TIER_DENSE, TIER_DENSE_AH, TIER_DENSE_AH_WIDE, TIER_COUNT };
+enum Tier { TIER_C21, TIER_RAMSEY, TIER_RAMSEY_WIDE, TIER_RAMSEY_U64, TIER_RAMSEY_U64_BIG, TIER_DENSE, TIER_DENSE_AH, TIER_DENSE_AH_WIDE, TIER_COUNT };
 struct TierDesc {
     Tier id;
     int space;                  // azd::SPACE_*
@@ -56,6 +56,8 @@ struct TierDesc {
     bool ah;                    // Aouchiche-Hansen cost: cur_lambda and cur_mu hold two values per agent, there is no node_mate
     // Ramsey: what check_engine_config tests, and says
     int max_n, max_edges, max_actions, node_actions; // the most n, E, E*C and max_slots * (C - 1) (0: no bound of its own)
+    int max_clique;             // the largest forbidden clique its kernels count
+    bool clique_overflow_rule;  // sizes above 5: every colour must pass RamseyCounts::new's i32 bound, C(s,2) * C(n,s) <= 2^31 - 1
     const char *e_range, *e_slots, *e_node_actions, *e_paths;
 };
 
@@ -63,7 +65,7 @@ struct azd_engine {
     azd_engine_config cfg;
     azd::Arenas a;
     const azd::SpaceOps *ops = nullptr; // the launchers and LDS plans of the engine's space and tier (space_ops.h)
-    const TierDesc *tier = nullptr;     // which of the seven kinds of engine this is (engine_tier)
+    const TierDesc *tier = nullptr;     // which of the eight kinds of engine this is (engine_tier)
     azd_evaluator *ev = nullptr;
     hipStream_t stream = nullptr;
     std::vector<void *> allocs;

@@ -28,7 +28,8 @@ static int ramsey_argmin_fetch(azd_engine *e, azd::RamseyU64ArgminRec *out) {
     AZD_HIP(hipStreamSynchronize(e->stream));
     const void *src = side ? (const void *)e->d_argmin_r_side : (const void *)e->a.argmin_r;
     switch (e->tier->id) {
-    case TIER_RAMSEY_U64: return ramsey_rec_fetch<azd::RamseyU64ArgminRec>(src, out);
+    case TIER_RAMSEY_U64:
+    case TIER_RAMSEY_U64_BIG: return ramsey_rec_fetch<azd::RamseyU64ArgminRec>(src, out);
     case TIER_RAMSEY_WIDE: return ramsey_rec_fetch<azd::RamseyWideArgminRec>(src, out);
     default: return ramsey_rec_fetch<azd::RamseyArgminRec>(src, out);
     }
@@ -271,7 +272,7 @@ int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t 
     }
     if (a.space == azd::SPACE_RAMSEY) { // `parents` receives the colour of every edge (E bytes)
         uint32_t nbr[512]; // [4][32] uint32_t rows, or the 64-bit tier's [4][64] uint64_t rows
-        const bool u64 = e->tier->id == TIER_RAMSEY_U64;
+        const bool u64 = e->tier->id == TIER_RAMSEY_U64 || e->tier->id == TIER_RAMSEY_U64_BIG;
         AZD_HIP(hipMemcpy(nbr, a.cur_nbr + (size_t)agent * e->tier->nbr_words, e->tier->nbr_words * 4, hipMemcpyDeviceToHost));
         if (parents) {
             int pos = 0;

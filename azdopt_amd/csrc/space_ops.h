@@ -64,6 +64,9 @@ const PhaseOps &c21_phase_ops(), &ramsey_phase_ops();
 const AsyncOps &c21_async_ops(), &ramsey_async_ops();
 const PoolOps &c21_pool_ops(), &ramsey_pool_ops();
 const PoolSearchOps &ramsey_pool_search_ops(), &ramsey64_pool_search_ops();
+// the 64-bit tier with forbidden cliques up to K8 (AZD_ENGINE_RAMSEY_BIG_CLIQUES: ramsey64_big_kernels.hip, ramsey64_big_ext_kernels.hip)
+const SpaceOps &ramsey64_big_ops();
+const PoolSearchOps &ramsey64_big_pool_search_ops();
 const SpaceOps &ramsey64_ops(), &dense_ops(), &dense_ah_ops(); // dense_ah_ops: DenseSpace with the Aouchiche-Hansen cost (dense_ah_kernels.hip)
 const SpaceOps &dense_ah_wide_ops();                            // ... with its 64-row form (dense_ah_wide_kernels.hip: AZD_ENGINE_DENSE_AH_WIDE)
 constexpr size_t POOL_SEARCH_STATIC_LDS = 16; // k_pool_search's static LDS (PoolIdle) beside the dynamic region the plans lay out

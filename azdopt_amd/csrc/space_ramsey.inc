@@ -54,6 +54,12 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 // edge.rs:48-53 colex_position for mx > mn
 __device__ __forceinline__ int colex_pos(int mx, int mn) { return mx * (mx - 1) / 2 + mn; }
 
+// The deepest count_cliques_inside an including unit asks for: 3 (clique sizes up to 5) unless the unit says otherwise before it
+// includes this file (ramsey64_big_kernels.hip: 6, sizes up to AZD_RAMSEY_BIG_CLIQUE_MAX, under names of its own).
+#ifndef RAMSEY_CLIQUE_DEPTH
+#define RAMSEY_CLIQUE_DEPTH 3
+#endif
+#if RAMSEY_CLIQUE_DEPTH == 3
 // bitset_graph/mod.rs:164-185 count_cliques_inside for k <= 3 (clique sizes up to 5).  The
 // reference's `1 + |T| >= size` filter only skips terms that are zero.
 template <class W>
@@ -73,6 +79,42 @@ __device__ __forceinline__ int cliques_inside(const W *nb, W S, int k) {
     }
     return sum;
 }
+#else
+// bitset_graph/mod.rs:164-185 count_cliques_inside for k <= RAMSEY_CLIQUE_DEPTH: a nest of fixed depth K, written as a compile-time
+// recursion that is inlined whole (no stack: the K sets of a lane are registers), the run-time depth picks the nest in one
+// wave-uniform switch.  Each level takes the largest vertex u of the clique and goes on in the part of the set below u.  The
+// reference's `1 + |T| >= size` filter only skips terms that are zero: from K = 4 a set with fewer than K - 1 vertices is left at once.
+template <int K, class W>
+__device__ __forceinline__ int cliques_nest(const W *nb, const W S) {
+    if constexpr (K == 0) return 1;
+    else if constexpr (K == 1) return nb_popc(S);
+    else {
+        int sum = 0;
+        for (W r = S; r; r &= r - (W)1) {
+            const int u = nb_ffs(r) - 1;
+            const W T = S & nb[u] & (((W)1 << u) - (W)1);
+            if constexpr (K >= 4) {
+                if (nb_popc(T) < K - 1) continue;
+            }
+            sum += cliques_nest<K - 1>(nb, T);
+        }
+        return sum;
+    }
+}
+template <class W>
+__device__ __forceinline__ int cliques_inside(const W *nb, W S, int k) {
+    static_assert(RAMSEY_CLIQUE_DEPTH == 6, "the switch below is written out for depths 0..6");
+    switch (k) {
+    case 0: return 1;
+    case 1: return cliques_nest<1>(nb, S);
+    case 2: return cliques_nest<2>(nb, S);
+    case 3: return cliques_nest<3>(nb, S);
+    case 4: return cliques_nest<4>(nb, S);
+    case 5: return cliques_nest<5>(nb, S);
+    default: return cliques_nest<6>(nb, S);
+    }
+}
+#endif
 
 // (atomicOr has no uint64_t overload: the 64-bit rows go through unsigned long long)
 __device__ __forceinline__ uint32_t *nbr_atomic(uint32_t *p) { return p; }

@@ -124,6 +124,8 @@ class NablaOptimizer:
             cfg.max_slots = getattr(space, "MAX_SLOTS", 0)
             if getattr(space, "U64", False):
                 cfg.flags |= _lib.ENGINE_RAMSEY_U64
+            if getattr(space, "BIG_CLIQUES", False):
+                cfg.flags |= _lib.ENGINE_RAMSEY_BIG_CLIQUES
             cfg.n_colors = space.C
             for i in range(space.C):
                 cfg.clique_sizes[i] = space.sizes[i]

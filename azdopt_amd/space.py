@@ -4,6 +4,7 @@
 in the reference; a device engine needs built-in device implementations, selected by id.  The
 classes here carry the constants and the host-side closures (`init_states`), nothing more."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -113,14 +114,18 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
 
     SPACE_ID = _lib.SPACE_RAMSEY
 
-    def __init__(self, n, sizes, weights=None, max_slots=None, u64=None):
+    def __init__(self, n, sizes, weights=None, max_slots=None, u64=None, big_cliques=None):
         """`max_slots`: the most permitted edges a root may bring.  0 keeps the engine's narrow limits (E <= 256, E*C <= 384,
         at most 128 / (C - 1) permitted edges); 1..E makes it a WIDE engine (N <= 32, E*C <= 1024; a node holds up to
         max_slots * (C - 1) legal actions).  None: 0 where the narrow limits hold, else E -- every edge may be permitted,
         as 05-r45.rs:83 allows.
         `u64`: the 64-bit tier (N <= 64, E*C <= 2304, max_slots * (C - 1) <= 512; 03-r3333.rs: N = 34, four colours).  None: only
         where neither 32-bit tier takes the shape; True forces it (any shape it takes), False forbids it.  With it, max_slots = None
-        is as many edges as a node of 512 actions holds, at most E."""
+        is as many edges as a node of 512 actions holds, at most E.
+        `big_cliques`: clique sizes up to 8 on the 64-bit tier (ENGINE_RAMSEY_BIG_CLIQUES: kernels of their own).  None: exactly when
+        a size exceeds 5, and the 64-bit tier is then forced; True forces it (any shape the tier takes, the same trees); a size
+        above 5 with u64=False or big_cliques=False raises ValueError.  With it every colour must pass the reference's i32 bound
+        (RamseyCounts::new, ramsey_counts/mod.rs:47-62, sums before it divides): C(s,2) * C(n,s) <= 2^31 - 1."""
         self.n = int(n)
         self.sizes = [int(x) for x in sizes]
         self.weights = [1.0] * len(self.sizes) if weights is None else [float(x) for x in weights]
@@ -130,6 +135,19 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
         self.STATE_DIM = L.azd_ramsey_state_dim(self.n, self.C)    # space.rs:40
         self.ACTION_DIM = L.azd_ramsey_action_dim(self.n, self.C)  # space.rs:42
         self.KEY_WORDS = L.azd_ramsey_key_words(self.n, self.C)
+        if max(self.sizes) > 5 and (u64 is False or big_cliques is False):
+            raise ValueError("clique sizes above 5 need the 64-bit tier with big_cliques (u64=%r, big_cliques=%r)" % (u64, big_cliques))
+        if big_cliques is None:
+            big_cliques = max(self.sizes) > 5
+        if big_cliques and u64 is False:
+            raise ValueError("big_cliques needs the 64-bit tier (u64=False)")
+        self.BIG_CLIQUES = bool(big_cliques)
+        if self.BIG_CLIQUES:
+            u64 = True
+            for c, s_ in enumerate(self.sizes):
+                if 2 <= s_ <= _lib.RAMSEY_BIG_CLIQUE_MAX and math.comb(s_, 2) * math.comb(self.n, s_) > 2 ** 31 - 1:
+                    raise ValueError("colour %d (clique size %d at n = %d) is beyond the reference's i32 bound: C(s,2) * C(n,s) <= 2^31 - 1"
+                                     % (c, s_, self.n))
         if u64 is None:
             u64 = self.n > _lib.RAMSEY_WIDE_MAX_N or self.ACTION_DIM > 1024
         self.U64 = bool(u64)
@@ -151,7 +169,7 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
 
     @property
     def tier(self):
-        """"narrow" (E <= 256, E*C <= 384), "wide" (N <= 32, E*C <= 1024) or "u64" (N <= 64, E*C <= 2304)"""
+        """"narrow" (E <= 256, E*C <= 384), "wide" (N <= 32, E*C <= 1024) or "u64" (N <= 64, E*C <= 2304; with BIG_CLIQUES sizes up to 8)"""
         return "u64" if self.U64 else "wide" if self.wide else "narrow"
 
     def default_permitted_range(self):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's Ramsey drivers (graph-state/examples/01-r333.rs, 02-r44.rs, 03-r3333.rs, 05-r45.rs) over the MI355X engine.
 
-    python examples/ramsey.py r333|r44|r3333|r45 [--epochs 250] [--episodes N] [--batch B]"""
+    python examples/ramsey.py r333|r44|r3333|r45|r46 [--epochs 250] [--episodes N] [--batch B]"""
 import argparse
 import os
 import sys
@@ -30,6 +30,12 @@ DRIVERS = {  # N, SIZES, BATCH, episodes, n_as_tol, num_permitted_edges_range.st
     # rule="best".
     "r3333": dict(n=34, sizes=[3, 3, 3, 3], batch=512, episodes=800, kmin=10, kmax=30, lr=3e-4, final_act=az._lib.ACT_RELU, rule="best",
                   tol=([200, 200, 100, 100, 50, 50, 25, 25], 10), tag="01-r333-grad"),
+    # BUILD-DEFINED: the reference has no R(4,6) driver (its space takes any clique sizes, its examples stop at K5).  N 35 -- the
+    # open R(4,6) is in [36, 40] -- with [4, 6] on the 64-bit tier with big cliques (the size asks for it), and every
+    # hyper-parameter of the r45 entry above; "every edge may be permitted" ends at what a node of that tier holds (512 actions).
+    "r46": dict(n=35, sizes=[4, 6], batch=128, episodes=3200, kmin=10, kmax="E", weights=[1.0, 0.4685 / (1.0 - 0.4685)], lr=3e-4,
+                final_act=az._lib.ACT_RELU, rule="best", color_weights=[0.4685, 1.0 - 0.4685],
+                tol=([200, 200, 100, 100, 50, 50, 25, 25], 10), tag="01-r333-grad"),
 }
 
 
@@ -43,7 +49,7 @@ def build_optimizer(driver, batch=0, episodes=0, hidden=(512, 1024, 512), seed=0
                            final_act=d.get("final_act", az._lib.ACT_SIGMOID), **(dict(dtype="bf16") if ext_pool_step else {}))
     kmin, kmax = d["kmin"], space.default_permitted_range()[1]   # ..=(E / 2), capped by what a node holds
     if d.get("kmax") == "E":
-        kmax = space.E
+        kmax = min(space.E, space.MAX_SLOTS) if space.wide else space.E
     elif d.get("kmax"):
         kmax = d["kmax"]
     C = len(d["sizes"])
@@ -65,7 +71,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--ext-pool-step", action="store_true",
-                    help="r45 / r3333 with bf16 weight storage: the searcher-only pool step with the model's batched GEMMs beside it "
+                    help="r45 / r3333 / r46 with bf16 weight storage: the searcher-only pool step with the model's batched GEMMs beside it "
                          "(NablaOptimizer.par_new(..., ext_pool_step=True)); the default stays the engine's own choice of form")
     args = ap.parse_args()
     d = DRIVERS[args.driver]

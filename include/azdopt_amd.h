@@ -76,13 +76,16 @@ int azd_c21_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, 
 /*   max_slots permitted edges per root (r45: N=24, 276 edges).  With       */
 /*   AZD_ENGINE_RAMSEY_U64 beside max_slots > 0 the engine runs the 64-BIT   */
 /*   tier: N <= 64 over 64-bit neighbourhood words, E*C <= 2304, a node of   */
-/*   up to 512 actions (r3333: N=34, four colours, 561 edges).               */
+/*   up to 512 actions (r3333: N=34, four colours, 561 edges).  With         */
+/*   AZD_ENGINE_RAMSEY_BIG_CLIQUES beside that flag: clique sizes 2..8       */
+/*   (R(4,6): N=35), within the reference's i32 bound (see the flag).        */
 /* ------------------------------------------------------------------------- */
 #define AZD_SPACE_RAMSEY 2
 #define AZD_RAMSEY_MAX_N 23
 #define AZD_RAMSEY_WIDE_MAX_N 32
 #define AZD_RAMSEY_U64_MAX_N 64
 #define AZD_RAMSEY_U64_NODE_ACTIONS 512 /* 64-bit tier: max_slots * (C - 1) may not exceed it */
+#define AZD_RAMSEY_BIG_CLIQUE_MAX 8     /* 64-bit tier with AZD_ENGINE_RAMSEY_BIG_CLIQUES: the largest forbidden clique */
 int azd_ramsey_state_dim(int n, int n_colors);  /* E(2C+1)  space.rs:40 */
 int azd_ramsey_action_dim(int n, int n_colors); /* EC       space.rs:42 */
 int azd_ramsey_key_words(int n, int n_colors);
@@ -272,7 +275,8 @@ typedef struct azd_engine_config {
 #define AZD_ENGINE_POOL_STEP 8u
 /* AZD_SPACE_RAMSEY with max_slots > 0 only: the 64-bit tier.  3 <= n <= AZD_RAMSEY_U64_MAX_N (neighbourhoods are 64-bit words, the
  * reference's B64), E*C <= 2304 (keys of 36 words: N = 34 at four colours, 39 at three, 48 at two), 2..4 colours, clique sizes
- * 2..5, 1 <= max_slots <= E and max_slots * (C - 1) <= AZD_RAMSEY_U64_NODE_ACTIONS; ActionSet paths only, no Layered wrapper.
+ * 2..5 (2..AZD_RAMSEY_BIG_CLIQUE_MAX with AZD_ENGINE_RAMSEY_BIG_CLIQUES beside this flag), 1 <= max_slots <= E and
+ * max_slots * (C - 1) <= AZD_RAMSEY_U64_NODE_ACTIONS; ActionSet paths only, no Layered wrapper.
  * Never chosen from the sizes: without the flag every limit, kernel and error text is the 32-bit tiers'.  Shapes a 32-bit wide
  * engine takes are accepted too and give the same trees.  Runs the launch-per-phase step form (the other CU-resident forms fall
  * back, azd_engine_step_form gives the reason) or, with AZD_ENGINE_EXT_POOL_STEP beside it and a bf16 model, the searcher-only pool
@@ -300,6 +304,17 @@ typedef struct azd_engine_config {
  * where the narrow engine's has 7..10 and the default cost's 16 (azd_debug_ext_pool_plan reports the plan for such a
  * configuration too); AZD_DENSE_POOL_WAVES keeps its range 4..16, a setting above what fits runs what fits. */
 #define AZD_ENGINE_DENSE_AH_WIDE 256u
+/* Beside AZD_ENGINE_RAMSEY_U64 only (alone, on another space or on a 32-bit tier: AZD_ERR_INVALID_ARGUMENT naming both flags): the
+ * 64-bit tier with forbidden cliques up to K8 -- clique sizes 2..AZD_RAMSEY_BIG_CLIQUE_MAX, the reference's count_cliques_inside
+ * (bitset_graph/mod.rs:164-185) to depth 6 in kernels of their own; the 64-bit tier's kernels and every engine without the flag are
+ * what they are without it, a size 6 included ("clique sizes 2..5").  Never chosen from the sizes.  Every other limit is the
+ * 64-bit tier's (3 <= n <= 64, 2..4 colours, E*C <= 2304, the max_slots rules, ActionSet paths, no Layered wrapper), and so are the
+ * step forms (launch per phase, or the searcher-only pool step beside AZD_ENGINE_EXT_POOL_STEP / AZD_ENGINE_EXT_POOL_F32), the root
+ * policy and the read-back entries (azd_engine_ramsey_argmin_any).  One limit more, the reference's own: RamseyCounts::new
+ * (ramsey_counts/mod.rs:47-62) adds a colour's per-edge counts into an i32 before it divides by C(s,2), so every colour needs
+ * C(s,2) * C(n,s) <= 2^31 - 1 -- size 6 at every n <= 64, size 7 at n <= 50, size 8 at n <= 39; azd_last_error() names the colour.
+ * Shapes the 64-bit tier takes without the flag give the same trees with it. */
+#define AZD_ENGINE_RAMSEY_BIG_CLIQUES 512u
 /* AZD_SPACE_RAMSEY with max_slots > 0 only (the 32-bit wide tier, or the 64-bit tier beside AZD_ENGINE_RAMSEY_U64): the
  * searcher-only pool step, the CU-resident form of these engines for a model that does not fit an evaluator workgroup's LDS.
  * Persistent searcher workgroups of eight wavefronts pull agents from the per-XCD ready queues, write each new node's state row

@@ -90,19 +90,37 @@ private:
 // 0 = the narrow limits (E <= 256, E*C <= 384); 1..E = a wide engine (N <= 32, E*C <= 1024, up to max_slots permitted edges per root);
 // -1 = 0 where the narrow limits hold, else E.  u64 (AZD_ENGINE_RAMSEY_U64): 1 = the 64-bit tier (N <= 64, E*C <= 2304, max_slots * (C - 1)
 // <= 512; 03-r3333.rs: N = 34, four colours), 0 = never, -1 = only where neither 32-bit tier takes the shape; with it max_slots = -1 is
-// as many edges as a node of 512 actions holds, at most E.
+// as many edges as a node of 512 actions holds, at most E.  big_cliques (AZD_ENGINE_RAMSEY_BIG_CLIQUES beside the 64-bit tier's flag): 1 =
+// clique sizes up to AZD_RAMSEY_BIG_CLIQUE_MAX, 0 = never, -1 = exactly when a size exceeds 5, which then forces the 64-bit tier; a size above
+// 5 with u64 = 0 or big_cliques = 0, and a colour beyond the reference's i32 bound C(s,2) * C(n,s) <= 2^31 - 1, throw.
 class RamseySpaceNoEdgeRecolor {
 public:
-    RamseySpaceNoEdgeRecolor(int n, std::vector<int> sizes, std::vector<float> weights = {}, int max_slots = -1, int u64 = -1)
-        : n_(n), sizes_(std::move(sizes)), weights_(std::move(weights)), max_slots_(max_slots), u64_(u64) {
+    RamseySpaceNoEdgeRecolor(int n, std::vector<int> sizes, std::vector<float> weights = {}, int max_slots = -1, int u64 = -1, int big_cliques = -1)
+        : n_(n), sizes_(std::move(sizes)), weights_(std::move(weights)), max_slots_(max_slots), u64_(u64), big_(big_cliques) {
         if (weights_.empty()) weights_.assign(sizes_.size(), 1.0f);
         if (sizes_.size() < 2 || sizes_.size() > 4 || weights_.size() != sizes_.size()) throw Error(AZD_ERR_INVALID_ARGUMENT, "RamseySpaceNoEdgeRecolor");
+        const int largest = *std::max_element(sizes_.begin(), sizes_.end());
+        if (largest > 5 && (u64_ == 0 || big_ == 0))
+            throw Error(AZD_ERR_INVALID_ARGUMENT, "RamseySpaceNoEdgeRecolor: a clique size above 5 needs the 64-bit tier with big cliques (u64, big_cliques)");
+        if (big_ < 0) big_ = largest > 5 ? 1 : 0;
+        if (big_) {
+            if (u64_ == 0) throw Error(AZD_ERR_INVALID_ARGUMENT, "RamseySpaceNoEdgeRecolor: big_cliques needs the 64-bit tier (u64)");
+            u64_ = 1;
+            for (size_t c = 0; c < sizes_.size(); ++c) { // RamseyCounts::new sums in i32 before it divides by C(s,2)
+                const long long s = sizes_[c];
+                long long binom = 1;
+                for (long long k = 0; k < s; ++k) binom = binom * (n_ - k) / (k + 1);
+                if (s >= 2 && s <= AZD_RAMSEY_BIG_CLIQUE_MAX && n_ >= s && n_ <= AZD_RAMSEY_U64_MAX_N && s * (s - 1) / 2 * binom > 2147483647LL)
+                    throw Error(AZD_ERR_INVALID_ARGUMENT, "RamseySpaceNoEdgeRecolor: colour " + std::to_string(c) + " is beyond the reference's i32 bound C(s,2) * C(n,s) <= 2^31 - 1");
+            }
+        }
         if (u64_ < 0) u64_ = (n_ > AZD_RAMSEY_WIDE_MAX_N || ACTION_DIM() > 1024) ? 1 : 0;
         if (max_slots_ < 0 && u64_) max_slots_ = std::min(E(), AZD_RAMSEY_U64_NODE_ACTIONS / (C() - 1));
         if (max_slots_ < 0) max_slots_ = (n_ <= AZD_RAMSEY_MAX_N && E() <= 256 && KEY_WORDS() <= 6) ? 0 : E();
     }
     int max_slots() const { return max_slots_; }
     bool u64() const { return u64_ != 0; }
+    bool big_cliques() const { return big_ != 0; }
     int n() const { return n_; }
     int C() const { return (int)sizes_.size(); }
     int E() const { return n_ * (n_ - 1) / 2; }
@@ -126,6 +144,7 @@ public:
         cfg.n = n_;
         cfg.max_slots = max_slots_;
         if (u64_) cfg.flags |= AZD_ENGINE_RAMSEY_U64;
+        if (big_) cfg.flags |= AZD_ENGINE_RAMSEY_BIG_CLIQUES;
         cfg.n_colors = C();
         for (int c = 0; c < C(); ++c) {
             cfg.clique_sizes[c] = sizes_[(size_t)c];
@@ -137,7 +156,7 @@ private:
     int n_;
     std::vector<int> sizes_;
     std::vector<float> weights_;
-    int max_slots_, u64_;
+    int max_slots_, u64_, big_;
 };
 
 // Connected graphs on N <= 64 vertices, AddOrDeleteEdge actions, every edge slot modified at most once (BASELINE configs[4],

@@ -4,7 +4,8 @@
 asked for with the engine's flags; the line says which form ran and, when another one did, why (azd_engine_step_form).
 --preset u64: the 64-bit tier (AZD_ENGINE_RAMSEY_U64) at the reference's R(3,3,3,3) shape (03-r3333.rs: N 34, four colours, 10..=30
 permitted edges, 512-1024-512 model with a ReLU head, 512 agents) and r45 under the flag beside r45 on the 32-bit tier (what the
-wider word costs).
+wider word costs); and, by tag (--shapes r46 r37), the tier with clique sizes above 5 (AZD_ENGINE_RAMSEY_BIG_CLIQUES): r46 (N 35, [4, 6]) and
+r37 (N 22, [3, 7]) at 512 agents.
 The form 'ext' is the searcher-only pool step (par_new(..., ext_pool_step=True): bf16 storage only; with fp32 the line shows what ran
 instead; 'ext_f32' is the same form with its fp32 evaluator, ext_pool_f32=True beside it: run it with --dtypes f32); its line ends with the busy shares of the evaluator's stream and of the searching waves (azd_engine_pool_utilisation).
 --forms picks the forms to time (a library built before 'ext' existed, chosen with AZD_LIB, is timed with --forms per_call pool).
@@ -33,6 +34,10 @@ U64_SHAPES = [("r3333", 34, [3, 3, 3, 3], [1.0] * 4, "f32", dict(u64=True, kmax=
               ("r45u64", 24, [4, 5], [1.0, 0.4685 / 0.5315], "bf16", dict(u64=True)),
               ("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "f32", dict(u64=False, forms=["per_call"])),
               ("r45u64", 24, [4, 5], [1.0, 0.4685 / 0.5315], "f32", dict(u64=True, forms=["per_call"]))]
+# the 64-bit tier with clique sizes above 5 (AZD_ENGINE_RAMSEY_BIG_CLIQUES): r46 = examples/ramsey.py's entry (N 35, [4, 6], r45's weights, as many
+# permitted edges as a node of 512 actions holds), r37 = N 22, [3, 7]; 512 agents.  Run them by tag: --preset u64 --shapes r46 r37 r45u64 --batch 512
+U64_SHAPES += [(tag, n, sizes, w, dtype, dict(batch=512, forms=["per_call"]))
+               for tag, n, sizes, w in (("r46", 35, [4, 6], [1.0, 0.4685 / 0.5315]), ("r37", 22, [3, 7], [1.0, 1.0])) for dtype in ("f32", "bf16")]
 
 
 def main():
@@ -52,7 +57,8 @@ def main():
           % (B, calls, args.warmup, args.hidden))
     if args.preset == "u64":
         print("# --preset u64: r3333 = N 34, [3,3,3,3], 10..=30 permitted edges, ReLU head, batch 512, the 64-bit tier; r45u64 = r45 on the 64-bit "
-              "tier (AZD_ENGINE_RAMSEY_U64) beside r45 on the 32-bit wide tier")
+              "tier (AZD_ENGINE_RAMSEY_U64) beside r45 on the 32-bit wide tier; r46 = N 35, [4, 6], 10..=512 permitted edges, r37 = N 22, [3, 7], "
+              "10..=231, both with AZD_ENGINE_RAMSEY_BIG_CLIQUES (the size asks for it), batch 512")
     print("# shape  dtype  asked     ran       expansions/s  s/call     why")
     for tag, n, sizes, weights, dtype, *rest in (U64_SHAPES if args.preset == "u64" else SHAPES):
         o = rest[0] if rest else {}
@@ -60,7 +66,7 @@ def main():
             continue
         B = o.get("batch", args.batch)
         space = az.RamseySpaceNoEdgeRecolor(n, sizes, weights, u64=o.get("u64"))
-        kmax = o.get("kmax", space.E)
+        kmax = o.get("kmax", min(space.E, space.MAX_SLOTS))  # (every edge, or as many as a node of the 64-bit tier holds)
         roots = space.generate_roots(0, B, kmin=10, kmax=kmax)
         for form, kw in FORMS.items():
             if form not in list(o.get("forms", FORMS)) + ["ext", "ext_f32"] or form not in args.forms:
