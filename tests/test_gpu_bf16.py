@@ -5,7 +5,7 @@ against the oracle when the oracle is fed the device's predictions."""
 import numpy as np
 import pytest
 
-from test_gpu_ramsey import assert_tree_equal, az  # noqa: F401
+from gpu_parity import assert_tree_equal, az  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 F = np.float32

@@ -4,31 +4,13 @@ argmin, bit for bit; N = 50 with the 512-wide bf16 model on the launch-per-phase
 import numpy as np
 import pytest
 
-from test_gpu_parity import MAIN_CTRS, assert_tree_equal
+from gpu_parity import C21_CTRS, OracleRef, assert_tree_equal, az, compare_c21, run_lockstep  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    assert azdopt_amd.device_count() > 0, "no MI355X visible"
-    return azdopt_amd
-
-
-def compare(opt, oe, agents, tag):
-    assert np.array_equal(opt.state_vecs(), oe.state_vecs()), tag
-    for i in agents:
-        assert_tree_equal(opt.get_tree(i), oe.export_tree(i), f"{tag} agent {i}")
-        sg, so = opt.agent_state(i), oe.agent_state(i)
-        for k in so:
-            assert np.array_equal(sg[k], so[k]), (tag, i, k, sg[k], so[k])  # lambda_1 compared as an f64: bit-identical procedure
-    cg, co = opt.counters(), oe.counters()
-    for k in MAIN_CTRS:
-        assert cg[k] == co[k], (tag, k, cg[k], co[k])
-    ag, ao = opt.argmin_data(), oe.argmin()
-    assert ag.eval == ao["eval"] and ag.cost["lambda_1"] == ao["lambda1"] and len(ag.cost["matching"]) == ao["matching"], tag
-    assert np.array_equal(ag.state["adj"].view(np.uint8), ao["parents"]) and np.array_equal(ag.state["permitted"], ao["permitted"]), tag
+def compare(opt, ref, agents, tag):
+    compare_c21(opt, ref, agents, tag, counters=C21_CTRS)
 
 
 def run_dense_parity(az, orc, n, B, p, kmin, kmax, tol, steps, epochs, seed, check_every, max_slots=128, policy=False, pool=False, **caps):
@@ -43,45 +25,9 @@ def run_dense_parity(az, orc, n, B, p, kmin, kmax, tol, steps, epochs, seed, che
         caps = dict(caps, pool_step=True)
     roots = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
     opt = az.NablaOptimizer.par_new(space, roots, model, B, **caps)
-    oe = orc.Engine(n, B, threads=8, dense=True, dense_p=p)
-    oe.new_begin(*roots)
-    call = 0
-    oe.new_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-    compare(opt, oe, range(B), "par_new")
-    for epoch in range(epochs):
-        s = 0
-        while s < steps:
-            k = min(check_every, steps - s)
-            ig = opt.par_roll_out_episodes(tol, n_calls=k)
-            io = 0
-            for _ in range(k):
-                oe.rollout_begin(*tol)
-                call += 1
-                io += oe.rollout_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-            assert ig == io
-            s += k
-            compare(opt, oe, range(B), f"epoch {epoch} step {s}")
-        if pool:
-            assert opt.step_form() == ("pool", "")
-            c = opt.counters()
-            assert c["EVAL_ROWS"] == c["EXPANSIONS"] > 0  # every row went through the evaluator's launches
-        else:
-            assert opt.step_form()[0] == "per_call" and "dense-graph space" in opt.step_form()[1]
-        sv, obs, w = opt.observe(2)
-        oo, ow = oe.observe(2)
-        assert np.array_equal(obs.view(np.uint32), oo.view(np.uint32)) and np.array_equal(w, ow) and np.array_equal(sv, oe.state_vecs())
-        if policy:
-            roots = oe.modify_roots(seed, epoch, 0, kmin, kmax)
-            got = opt.modify_roots(seed, epoch, kmin, kmax)  # the policy alone: the new roots in the host's format
-            assert np.array_equal(got[0], roots[0]) and np.array_equal(got[1], roots[1]), epoch
-            opt.par_reset_trees_policy(seed, epoch, kmin, kmax)  # policy + reset without a host round trip
-        else:
-            roots = space.generate_roots(seed, B, epoch=epoch + 1, kmin=kmin, kmax=kmax)  # `modify_root`: fresh seeded roots from the host
-            opt.par_reset_trees(roots)
-        oe.reset_begin(*roots)
-        call += 1
-        oe.reset_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-        compare(opt, oe, range(B), f"epoch {epoch} reset")
+    run_lockstep(opt, OracleRef.dense(orc, n, B, p), roots, orc, compare, seed=seed, tol=tol, steps=steps, epochs=epochs, kmin=kmin,
+                 kmax=kmax, n_obs_tol=2, check_every=check_every, boundary="policy" if policy else "fresh",
+                 form="dense_pool" if pool else "dense_per_call", nan_payloads=True)
     return opt.counters()
 
 
@@ -147,7 +93,7 @@ def test_dense_pool_step_at_config_e_population_against_the_oracle(az, orc):
             io += oe.rollout_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
         assert ig == io
         assert opt.pool_split()[1] * 16 < B  # fewer searching waves than agents
-        compare(opt, oe, range(0, B, 97), f"epoch {epoch}")
+        compare(opt, OracleRef(oe), range(0, B, 97), f"epoch {epoch}")
         new_roots = oe.modify_roots(seed, epoch, 0, kmin, kmax)
         got = opt.modify_roots(seed, epoch, kmin, kmax)
         assert np.array_equal(got[0], new_roots[0]) and np.array_equal(got[1], new_roots[1]), epoch
@@ -182,7 +128,7 @@ def test_dense_pool_step_with_the_bf16_model_equals_the_launch_per_phase_form(az
     (o0, i0, j0, l0), (o1, i1, j1, l1) = runs
     assert (i0, j0) == (i1, j1) and l0 == l1
     c0, c1 = o0.counters(), o1.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c0[k] == c1[k], k
     assert c0["EVAL_ROWS"] == c0["EXPANSIONS"]
     for i in range(0, B, 5):
@@ -222,7 +168,7 @@ def test_dense_pool_abort_is_completed_by_the_launch_per_phase_kernels(az, monke
     monkeypatch.delenv("AZD_POOL_DEBUG_ABORT_CALL")
     assert imp == imp_ref
     c0, c1 = opt.counters(), ref.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c0[k] == c1[k], k
     for i in range(B):
         assert_tree_equal(opt.get_tree(i), ref.get_tree(i), f"agent {i}")
@@ -330,7 +276,7 @@ def test_hipgraph_replay_of_the_per_call_form_equals_launch_by_launch(az, monkey
     (o2, i2) = runs.pop()
     assert i2 == runs[0][1]
     c0, c2 = runs[0][0].counters(), o2.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c0[k] == c2[k], k
     for i in range(B):
         assert_tree_equal(runs[0][0].get_tree(i), o2.get_tree(i), f"sub-populations, agent {i}")
@@ -340,7 +286,7 @@ def test_hipgraph_replay_of_the_per_call_form_equals_launch_by_launch(az, monkey
     (o0, i0), (o1, i1) = runs
     assert i0 == i1
     c0, c1 = o0.counters(), o1.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c0[k] == c1[k], k
     for i in range(B):
         assert_tree_equal(o0.get_tree(i), o1.get_tree(i), f"agent {i}")

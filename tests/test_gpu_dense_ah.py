@@ -19,15 +19,10 @@ import numpy as np
 import pytest
 
 import dense_ah_ref as R
+from gpu_parity import C21_CTRS, TOL_REF, PyDenseRef, assert_tree_equal, az, compare_ah, run_lockstep  # noqa: F401
+from gpu_parity import f64_bits as bits
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    assert azdopt_amd.device_count() > 0, "no MI355X visible"
-    return azdopt_amd
 
 
 def test_f64_primitives_bit_exact(az):
@@ -90,41 +85,6 @@ def test_device_cost_equals_the_python_reference_at_the_reference_shape(az):
 
 
 # ---------------------------------------------------------------- engines against the Python reference
-from test_gpu_parity import MAIN_CTRS, assert_tree_equal  # noqa: E402
-
-TOL_REF = ([200, 50, 50], 25)  # 04-c21-tree.rs:136-138, the live drivers' tolerances
-
-
-def bits(x):
-    return np.float64(x).view(np.uint64)
-
-
-def compare(opt, pe, agents, tag):
-    assert np.array_equal(opt.state_vecs().view(np.uint32), pe.state_vecs().view(np.uint32)), tag
-    for i in agents:
-        assert_tree_equal(opt.get_tree(i), pe.export_tree(i), f"{tag} agent {i}")
-        sg, sp = opt.agent_state(i), pe.agent_state(i)
-        for k in sp:  # (the cost fields are absent while the reference's agent stands on its root)
-            if k in ("proximity", "eigenvalue"):
-                assert bits(sg[k]) == bits(sp[k]), (tag, i, k, sg[k], sp[k])
-            elif k == "cost":
-                assert np.float32(sg[k]).view(np.uint32) == np.float32(sp[k]).view(np.uint32), (tag, i, k)
-            else:
-                assert np.array_equal(sg[k], sp[k]), (tag, i, k, sg[k], sp[k])
-    cg, cp = opt.counters(), pe.counters()
-    for k in cp:
-        assert cg[k] == cp[k], (tag, k, cg[k], cp[k])
-    ag, ap = opt.argmin_data(), pe.argmin
-    assert ag.eval.view(np.uint32) == np.float32(ap["eval"]).view(np.uint32), tag
-    assert bits(ag.cost["proximity"]) == bits(ap["proximity"]) and bits(ag.cost["eigenvalue"]) == bits(ap["eigenvalue"]), tag
-    assert (ag.cost["diameter"], ag.cost["k"]) == (ap["diameter"], ap["k"]) and ag.cost["cost"] == ap["cost"], tag
-    assert np.array_equal(ag.state["adj"], np.array(ap["state"].adj, np.uint64)), tag
-    assert np.array_equal(ag.state["permitted"], np.array(pe.mask(ap["state"].slots), np.uint64)), tag
-    # the argmin's graph re-evaluates, through the host function, to the argmin's cost
-    again = opt.space.ah_cost(ag.state["adj"])
-    assert again["cost"] == ag.cost["cost"] and again["eval"] == ag.eval and bits(again["eigenvalue"]) == bits(ag.cost["eigenvalue"]), tag
-
-
 def run_ah_parity(az, orc, n, B, p, kmin, kmax, tol, steps, epochs, seed, check_every, max_slots=128, policy=True, pool=False, **caps):
     space = az.DenseGraphSpace(n, p, max_slots=max_slots, cost="ah")
     model = az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed)
@@ -133,45 +93,9 @@ def run_ah_parity(az, orc, n, B, p, kmin, kmax, tol, steps, epochs, seed, check_
         caps = dict(caps, pool_step=True)
     roots = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
     opt = az.NablaOptimizer.par_new(space, roots, model, B, **caps)
-    pe = R.PyDenseEngine(n, B, cost="ah", p=p)
-    pe.new_begin(*roots)
-    call = 0
-    pe.new_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-    compare(opt, pe, range(B), "par_new")
-    for epoch in range(epochs):
-        s = 0
-        while s < steps:
-            k = min(check_every, steps - s)
-            ig = opt.par_roll_out_episodes(tol, n_calls=k)
-            ip = 0
-            for _ in range(k):
-                pe.rollout_begin(*tol)
-                call += 1
-                ip += pe.rollout_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-            assert ig == ip, (epoch, s)
-            s += k
-            compare(opt, pe, range(B), f"epoch {epoch} step {s}")
-        if pool:
-            assert opt.step_form() == ("pool", ""), opt.step_form()
-            c = opt.counters()
-            assert c["EVAL_ROWS"] == c["EXPANSIONS"] > 0
-        else:
-            assert opt.step_form()[0] == "per_call" and "dense-graph space" in opt.step_form()[1]
-        sv, obs, w = opt.observe(2)
-        po_, pw = pe.observe(2)
-        assert np.array_equal(obs.view(np.uint32), po_.view(np.uint32)) and np.array_equal(w, pw) and np.array_equal(sv, pe.state_vecs())
-        if policy:
-            roots = pe.modify_roots(seed, epoch, 0, kmin, kmax)
-            got = opt.modify_roots(seed, epoch, kmin, kmax)
-            assert np.array_equal(got[0], roots[0]) and np.array_equal(got[1], roots[1]), epoch
-            opt.par_reset_trees_policy(seed, epoch, kmin, kmax)
-        else:
-            roots = space.generate_roots(seed, B, epoch=epoch + 1, kmin=kmin, kmax=kmax)
-            opt.par_reset_trees(roots)
-        pe.reset_begin(*roots)
-        call += 1
-        pe.reset_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-        compare(opt, pe, range(B), f"epoch {epoch} reset")
+    run_lockstep(opt, PyDenseRef(R.PyDenseEngine(n, B, cost="ah", p=p)), roots, orc, compare_ah, seed=seed, tol=tol, steps=steps,
+                 epochs=epochs, kmin=kmin, kmax=kmax, n_obs_tol=2, check_every=check_every, boundary="policy" if policy else "fresh",
+                 form="dense_pool" if pool else "dense_per_call", nan_payloads=True)
     return opt.counters()
 
 
@@ -223,7 +147,7 @@ def test_ah_pool_step_equals_the_launch_per_phase_form_at_640_agents(az, max_slo
     (o0, i0, j0), (o1, i1, j1) = runs
     assert (i0, j0) == (i1, j1)
     c0, c1 = o0.counters(), o1.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c0[k] == c1[k], k
     for i in range(0, B, 7):
         assert_tree_equal(o0.get_tree(i), o1.get_tree(i), f"agent {i}")
@@ -349,7 +273,7 @@ def test_ah_pool_step_with_a_bf16_model_and_its_abort_recovery(az, monkeypatch):
     assert imp == imp_ref == imp_pool
     for o in (pool, opt):
         c0, c1 = o.counters(), ref.counters()
-        for k in MAIN_CTRS:
+        for k in C21_CTRS:
             assert c0[k] == c1[k], k
         for i in range(0, B, 3):
             assert_tree_equal(o.get_tree(i), ref.get_tree(i), f"agent {i}")

@@ -22,15 +22,9 @@ import pytest
 
 import dense_ah_ref as R
 import dense_ah_wide_ref as W
+from gpu_parity import C21_CTRS, TOL_REF, PyDenseRef, assert_same_run, assert_tree_equal, az, compare_ah, run_lockstep  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    assert azdopt_amd.device_count() > 0, "no MI355X visible"
-    return azdopt_amd
 
 
 # ---------------------------------------------------------------- the cost kernel alone
@@ -69,50 +63,22 @@ def test_wide_kernel_equals_the_narrow_kernel_up_to_32_vertices(az):
 
 
 # ---------------------------------------------------------------- engines against the Python reference
-from test_gpu_dense_ah import TOL_REF, bits, compare  # noqa: E402
-from test_gpu_parity import MAIN_CTRS, assert_tree_equal  # noqa: E402
-
-
 def run_wide_parity(az, orc, n, B, p, kmin, kmax, tol, steps, epochs, seed, max_slots=128, **caps):
     """a wide engine, one launch per phase, against PyDenseWideEngine after every call; the device root policy between epochs"""
     space = az.DenseGraphSpace(n, p, max_slots=max_slots, cost="ah", ah_wide=True)
     model = az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed)
     roots = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
     opt = az.NablaOptimizer.par_new(space, roots, model, B, **caps)
-    pe = W.PyDenseWideEngine(n, B, cost="ah", p=p)
-    pe.new_begin(*roots)
-    call = 0
-    pe.new_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-    compare(opt, pe, range(B), "par_new")
-    for epoch in range(epochs):
-        for s in range(1, steps + 1):
-            ig = opt.par_roll_out_episodes(tol, n_calls=1)
-            pe.rollout_begin(*tol)
-            call += 1
-            ip = pe.rollout_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-            assert ig == ip, (epoch, s)
-            compare(opt, pe, range(B), f"epoch {epoch} step {s}")
-        assert opt.step_form()[0] == "per_call" and "dense-graph space" in opt.step_form()[1]
-        if epoch + 1 == epochs:
-            break
-        sv, obs, w = opt.observe(2)
-        po_, pw = pe.observe(2)
-        assert np.array_equal(obs.view(np.uint32), po_.view(np.uint32)) and np.array_equal(w, pw) and np.array_equal(sv, pe.state_vecs())
-        roots = pe.modify_roots(seed, epoch, 0, kmin, kmax)
-        got = opt.modify_roots(seed, epoch, kmin, kmax)
-        assert np.array_equal(got[0], roots[0]) and np.array_equal(got[1], roots[1]), epoch
-        opt.par_reset_trees_policy(seed, epoch, kmin, kmax)
-        pe.reset_begin(*roots)
-        call += 1
-        pe.reset_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-        compare(opt, pe, range(B), f"epoch {epoch} reset")
+    run_lockstep(opt, PyDenseRef(W.PyDenseWideEngine(n, B, cost="ah", p=p)), roots, orc, compare_ah, seed=seed, tol=tol, steps=steps,
+                 epochs=epochs, kmin=kmin, kmax=kmax, n_obs_tol=2, boundary="policy", last_boundary=False, form="dense_per_call",
+                 nan_payloads=True)
     return opt
 
 
 def test_wide_parity_n33_two_epochs_with_the_device_root_policy(az, orc):
     opt = run_wide_parity(az, orc, 33, 12, 0.2, 5, 100, ([50, 20, 10], 5), steps=40, epochs=2, seed=3)
     c = opt.counters()
-    print("n = 33:", {k: c[k] for k in MAIN_CTRS})
+    print("n = 33:", {k: c[k] for k in C21_CTRS})
     assert c["EXPANSIONS"] > 0
 
 
@@ -157,7 +123,7 @@ def test_wide_engine_gives_the_narrow_engines_trees(az, n, p, kmax):
     (o0, i0, j0, r0), (o1, i1, j1, r1) = runs
     assert (i0, j0) == (i1, j1) and all(np.array_equal(r0[k], r1[k]) for k in ("branch", "node", "kept"))
     c0, c1 = o0.counters(), o1.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c0[k] == c1[k], k
     for i in range(B):
         assert_tree_equal(o0.get_tree(i), o1.get_tree(i), f"agent {i}")
@@ -170,20 +136,6 @@ def test_wide_engine_gives_the_narrow_engines_trees(az, n, p, kmax):
 
 
 # ---------------------------------------------------------------- pool step
-def assert_same_run(o0, o1, B, every):
-    c0, c1 = o0.counters(), o1.counters()
-    for k in MAIN_CTRS:
-        assert c0[k] == c1[k], k
-    for i in range(0, B, every):
-        assert_tree_equal(o0.get_tree(i), o1.get_tree(i), f"agent {i}")
-        s0, s1 = o0.agent_state(i), o1.agent_state(i)
-        assert all(np.array_equal(s0[k], s1[k]) for k in s0), i
-    a0, a1 = o0.argmin_data(), o1.argmin_data()
-    assert a0.eval == a1.eval and a0.agent == a1.agent and a0.node == a1.node and a0.cost == a1.cost
-    assert np.array_equal(o0.state_vecs(), o1.state_vecs())
-    assert o0.space.ah_cost(a0.state["adj"])["cost"] == a0.cost["cost"]
-
-
 @pytest.mark.parametrize("max_slots,kmin,kmax", [(128, 5, 128), (256, 129, 256), (640, 300, 640)])
 def test_wide_pool_step_equals_the_launch_per_phase_form_at_256_agents(az, max_slots, kmin, kmax):
     """key widths 2, 4 and 10 at n = 40 (E = 780): the pool step's searchers == one launch per phase -- trees, counters, argmin,
@@ -210,7 +162,7 @@ def test_wide_pool_step_equals_the_launch_per_phase_form_at_256_agents(az, max_s
         runs.append((o, imp, imp2))
     (o0, i0, j0), (o1, i1, j1) = runs
     assert (i0, j0) == (i1, j1)
-    assert_same_run(o0, o1, B, 5)
+    assert_same_run(o0, o1, B, every=5)
 
 
 def test_wide_pool_step_with_a_bf16_model_and_the_fp32_fallback(az, monkeypatch):
@@ -234,7 +186,7 @@ def test_wide_pool_step_with_a_bf16_model_and_the_fp32_fallback(az, monkeypatch)
     imp_pool = pool.par_roll_out_episodes(tol, n_calls=calls)
     assert pool.step_form() == ("pool", ""), pool.step_form()
     assert imp_pool == imp_ref
-    assert_same_run(pool, ref, B, 3)
+    assert_same_run(pool, ref, B, every=3)
     assert pool.counters()["EVAL_ROWS"] == pool.counters()["EXPANSIONS"] > 0
     f32 = mk("f32")
     f32.par_roll_out_episodes(tol, n_calls=5)

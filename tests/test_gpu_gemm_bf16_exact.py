@@ -17,20 +17,13 @@ import pytest
 import torch  # (before the package loads its library: one HIP runtime in the process, torch's)
 
 import bf16_exact as X
+from gpu_parity import az  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 SENT32 = np.uint32(0x7FC0ABCD)  # a quiet NaN with a payload: an untouched f32 word
 SENT16 = np.uint16(0x7FC1)      # ... an untouched bf16 word
 TOL = ([200, 50, 50], 25)
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    if azdopt_amd.device_count() < 1:
-        pytest.fail("no gfx950 device: the GPU tests need the HIP path")
-    return azdopt_amd
 
 
 def diff_report(got, want, what):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import mlp_f64 as M
+from gpu_parity import az  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,14 +23,6 @@ def row_lists():
     return {"empty": np.zeros(0, np.uint32), "one": np.array([57], np.uint32), "31": np.arange(31, dtype=np.uint32) + 3,
             "32": np.arange(32, dtype=np.uint32) + 40, "33": perm[:33].copy(), "80 permuted": perm,
             "20 with gaps": np.arange(79, -1, -4, dtype=np.uint32)}
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    if azdopt_amd.device_count() < 1:
-        pytest.fail("no gfx950 device: the GPU tests need the HIP path")
-    return azdopt_amd
 
 
 @pytest.fixture(scope="module")

@@ -10,6 +10,7 @@ import pytest
 
 import mlp_f64 as R
 from test_gpu_bf16 import bf16_round
+from gpu_parity import az  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,13 +23,6 @@ HEADS = {"none": R.ACT_NONE, "relu": R.ACT_RELU, "sigmoid": R.ACT_SIGMOID}
 VISIBLE = dict(lr=1e-2, betas=(0.8, 0.99), eps=1e-3, l2=1e-1)
 REFERENCE = dict(lr=1e-4, betas=(0.9, 0.999), eps=1e-8, l2=1e-6)  # 04-c21-tree.rs:87-92
 TOL_REF = ([200, 50, 50], 25)
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    assert azdopt_amd.device_count() > 0, "no MI355X visible"
-    return azdopt_amd
 
 
 def report(tag, ref, rep):

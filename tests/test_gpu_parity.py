@@ -3,37 +3,14 @@
 Bit-exact for everything integer / index / f32-selection related (tree topology, counters,
 visit counts n_t, state vectors, observations, argmin, root policy); stated tolerances for the
 MLP.  Run with -m gpu on an MI355X."""
+import functools
+
 import numpy as np
 import pytest
 
+from gpu_parity import C21_CTRS, TOL_REF, OracleRef, assert_tree_equal, az, compare_c21, run_lockstep  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-TOL_REF = ([200, 50, 50], 25)  # 04-c21-tree.rs:136-138
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    assert azdopt_amd.device_count() > 0, "no MI355X visible"
-    return azdopt_amd
-
-
-def assert_tree_equal(tg, to, tag=""):
-    for f in to.FIELDS:
-        a, b = getattr(tg, f), getattr(to, f)
-        assert a.shape == b.shape, (tag, f, a.shape, b.shape)
-        if a.dtype.kind == "f":
-            same = np.array_equal(a.view(np.uint32), b.view(np.uint32))
-        else:
-            same = np.array_equal(a.astype(np.int64), b.astype(np.int64))
-        if not same:
-            idx = np.argwhere(a != b)
-            raise AssertionError(f"{tag} field {f}: first mismatch at {idx[:3].tolist()} gpu={a[tuple(idx[0])]} oracle={b[tuple(idx[0])]}")
-
-
-MAIN_CTRS = ("EXPANSIONS", "TERMINALS", "TRANSPOSITIONS", "VISITED_STEPS", "SELECT_CALLS", "SUM_DEG", "SUM_ACTIONS",
-             "CASCADE_NODES", "NEW_PREDS", "ROOT_EXHAUSTED", "MAX_DEPTH", "CURIOSITY_PAIRS", "FAILED")
-
 
 def test_f32_primitives_bit_exact(az):
     """sqrt(|x - y|) and x - (x - y) on the GPU equal numpy f32 bit for bit: uniform values, subnormal
@@ -70,6 +47,9 @@ def test_hash_stream_matches_oracle(az, orc):
         assert np.array_equal(buf, orc.hash_predictions(5, 10, 7, 152, call))
 
 
+compare = functools.partial(compare_c21, counters=C21_CTRS)
+
+
 def run_parity(az, orc, n, B, kmin, kmax, tol, steps, epochs, seed, n_obs_tol, check_every=1, sample=None,
                first_agent=0, threads=8):
     space = az.ROTModifyParentsOnce(n)
@@ -78,56 +58,10 @@ def run_parity(az, orc, n, B, kmin, kmax, tol, steps, epochs, seed, n_obs_tol, c
     po, mo = orc.gen_roots(seed, 0, first_agent, B, n, kmin, kmax)
     assert np.array_equal(parents, po) and np.array_equal(permitted, mo)
     opt = az.NablaOptimizer.par_new(space, (parents, permitted), model, B, first_agent=first_agent)
-    oe = orc.Engine(n, B, threads=threads)
-    oe.new_begin(parents, permitted)
-    call = 0
-    oe.new_end(orc.hash_predictions(seed, first_agent, B, space.ACTION_DIM, call))
-    agents = range(B) if sample is None else sample
-
-    def compare(tag):
-        assert np.array_equal(opt.state_vecs(), oe.state_vecs()), tag
-        for i in agents:
-            assert_tree_equal(opt.get_tree(i), oe.export_tree(i), f"{tag} agent {i}")
-            sg, so = opt.agent_state(i), oe.agent_state(i)
-            for k in so:
-                assert np.array_equal(sg[k], so[k]), (tag, i, k, sg[k], so[k])
-        ag, ao = opt.argmin_data(), oe.argmin()
-        assert np.array_equal(ag.state["parents"], ao["parents"]) and np.array_equal(ag.state["permitted"], ao["permitted"])
-        assert ag.eval == ao["eval"] and ag.cost["lambda_1"] == ao["lambda1"] and len(ag.cost["matching"]) == ao["matching"]
-        cg, co = opt.counters(), oe.counters()
-        for k in MAIN_CTRS:
-            assert cg[k] == co[k], (tag, k, cg[k], co[k])
-
-    compare("par_new")
-    for epoch in range(epochs):
-        s = 0
-        while s < steps:
-            k = min(check_every, steps - s)
-            improved_g = opt.par_roll_out_episodes(tol, n_calls=k)
-            improved_o = 0
-            for _ in range(k):
-                oe.rollout_begin(*tol)
-                call += 1
-                improved_o += oe.rollout_end(orc.hash_predictions(seed, first_agent, B, space.ACTION_DIM, call))
-            assert improved_g == improved_o
-            s += k
-            compare(f"epoch {epoch} step {s}")
-        sv, obs, w = opt.observe(n_obs_tol)
-        oo, ow = oe.observe(n_obs_tol)
-        assert np.array_equal(obs.view(np.uint32), oo.view(np.uint32)) and np.array_equal(w, ow)
-        assert np.array_equal(sv, oe.state_vecs())
-        ro = oe.modify_roots(seed, epoch, first_agent, kmin, kmax)
-        for device in (True, False):  # device kernel and host C++ restatement of the root policy
-            rg = opt.c21_modify_roots(seed, epoch, kmin, kmax, device=device)
-            assert np.array_equal(rg[0], ro[0]) and np.array_equal(rg[1], ro[1]), (epoch, device)
-        if epoch % 2 == 0:
-            opt.par_reset_trees_c21(seed, epoch, kmin, kmax)  # policy + reset without a host round trip
-        else:
-            opt.par_reset_trees(rg)
-        oe.reset_begin(*ro)
-        call += 1
-        oe.reset_end(orc.hash_predictions(seed, first_agent, B, space.ACTION_DIM, call))
-        compare(f"epoch {epoch} reset")
+    # the boundary checks the device kernel and the host C++ restatement of the root policy
+    run_lockstep(opt, OracleRef.c21(orc, n, B, threads), (parents, permitted), orc, compare, seed=seed, tol=tol, steps=steps,
+                 epochs=epochs, kmin=kmin, kmax=kmax, n_obs_tol=n_obs_tol, first_agent=first_agent, check_every=check_every,
+                 sample=sample, host_policy=True, nan_payloads=True)
     return opt.counters()
 
 
@@ -336,7 +270,7 @@ def test_persistent_step_equals_launch_per_phase(az, orc):
     def same_engines(o1, i1, o2, i2):
         assert i1 == i2
         c1, c2 = o1.counters(), o2.counters()
-        for k in MAIN_CTRS:
+        for k in C21_CTRS:
             assert c1[k] == c2[k], k
         for i in range(B):
             t1, t2 = o1.get_tree(i), o2.get_tree(i)
@@ -395,7 +329,7 @@ def test_async_epoch_is_reproducible_at_full_size(az):
     for o, imp in runs[1:]:
         c, am = o.counters(), o.argmin_data()
         assert imp == i0
-        for k in MAIN_CTRS:
+        for k in C21_CTRS:
             assert c[k] == c0[k], k
         assert (am.eval, am.agent, am.node) == (a0.eval, a0.agent, a0.node)
         assert np.array_equal(o.state_vecs(), o0.state_vecs())

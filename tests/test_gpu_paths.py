@@ -4,55 +4,27 @@ ActionMultiset (coincides with ActionSet on ActionsNeverRepeat spaces) against t
 import numpy as np
 import pytest
 
-from test_gpu_ramsey import MAIN_CTRS, assert_tree_equal, az  # noqa: F401
+from gpu_parity import OracleRef, assert_tree_equal, az, run_lockstep, same_array, same_counters  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
+def compare(opt, ref, agents, tag):
+    same_array(opt.state_vecs(), ref.state_vecs(), f"{tag} state_vecs")
+    for i in agents:
+        assert_tree_equal(opt.get_tree(i), ref.tree(i), f"{tag} agent {i}")
+    same_counters(opt.counters(), ref.counters(), tag)
+    assert opt.argmin_data().eval.tobytes() == ref.e.argmin()["eval"].tobytes(), tag
+
+
 def run(az, orc, space, ramsey, path, kmin, kmax, B, tol, steps, epochs, seed, n_obs_tol, check_every):
-    kind = path.PATH_KIND
     model = az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed, 0)
     roots = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
     opt = az.NablaOptimizer.par_new(space, roots, model, B, path=path)
-    oe = orc.Engine(space.n, B, threads=8, ramsey=ramsey, path_kind=kind)
-    oe.new_begin(*roots)
-    call = 0
-    oe.new_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-
-    def compare(tag):
-        assert np.array_equal(opt.state_vecs(), oe.state_vecs()), tag
-        for i in range(B):
-            assert_tree_equal(opt.get_tree(i), oe.export_tree(i), f"{tag} agent {i}")
-        cg, co = opt.counters(), oe.counters()
-        for k in MAIN_CTRS:
-            assert cg[k] == co[k], (tag, k, cg[k], co[k])
-        assert opt.argmin_data().eval.tobytes() == oe.argmin()["eval"].tobytes(), tag
-
-    compare("par_new")
-    for epoch in range(epochs):
-        for s in range(0, steps, check_every):
-            k = min(check_every, steps - s)
-            ig = opt.par_roll_out_episodes(tol, n_calls=k)
-            io = 0
-            for _ in range(k):
-                oe.rollout_begin(*tol)
-                call += 1
-                io += oe.rollout_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-            assert ig == io
-            compare(f"epoch {epoch} step {s + k}")
-        sv, obs, w = opt.observe(n_obs_tol)
-        oo, ow = oe.observe(n_obs_tol)
-        nan = np.isnan(oo)
-        assert np.array_equal(np.isnan(obs), nan) and np.array_equal(w, ow)
-        assert np.array_equal(obs[~nan].view(np.uint32), oo[~nan].view(np.uint32))
-        ro = oe.modify_roots(seed, epoch, 0, kmin, kmax)
-        rg = opt.modify_roots(seed, epoch, kmin, kmax)  # device policy, key order of this encoding
-        assert np.array_equal(rg[0], ro[0]) and np.array_equal(rg[1], ro[1]), epoch
-        opt.par_reset_trees_policy(seed, epoch, kmin, kmax)
-        oe.reset_begin(*ro)
-        call += 1
-        oe.reset_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call))
-        compare(f"epoch {epoch} reset")
+    ref = OracleRef(orc.Engine(space.n, B, threads=8, ramsey=ramsey, path_kind=path.PATH_KIND))
+    # (the boundary: the device policy, key order of this encoding)
+    run_lockstep(opt, ref, roots, orc, compare, seed=seed, tol=tol, steps=steps, epochs=epochs, kmin=kmin, kmax=kmax, n_obs_tol=n_obs_tol,
+                 check_every=check_every, boundary="policy")
     return opt.counters()
 
 

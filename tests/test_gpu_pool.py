@@ -4,22 +4,15 @@ the oracle, whatever wave ran which call and whichever batch carried which row."
 import numpy as np
 import pytest
 
-from test_gpu_parity import MAIN_CTRS, TOL_REF, assert_tree_equal
+from gpu_parity import C21_CTRS, TOL_REF, assert_tree_equal, az  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    assert azdopt_amd.device_count() > 0, "no MI355X visible"
-    return azdopt_amd
 
 
 def same_engines(o1, i1, o2, i2, agents):
     assert i1 == i2
     c1, c2 = o1.counters(), o2.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c1[k] == c2[k], k
     for i in agents:
         assert_tree_equal(o1.get_tree(i), o2.get_tree(i), f"agent {i}")
@@ -155,7 +148,7 @@ def test_pool_step_reference_shape_and_ramsey(az):
     assert runs[0][0].step_form() == ("pool", "")
     assert runs[0][1] == runs[1][1]
     c1, c2 = runs[0][0].counters(), runs[1][0].counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c1[k] == c2[k], k
     for i in range(0, B, 17):
         assert_tree_equal(runs[0][0].get_tree(i), runs[1][0].get_tree(i), f"ramsey agent {i}")
@@ -260,7 +253,7 @@ def _oracle_two_epochs(orc, n, B, seed, calls, n_obs_tol, kmin, kmax):
 def _check_against_snapshot(opt, imp, snap, tag):
     assert imp == snap["improved"], tag
     c = opt.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c[k] == snap["counters"][k], (tag, k, c[k], snap["counters"][k])
     assert np.array_equal(opt.state_vecs(), snap["state_vecs"]), tag
     for i, to in snap["trees"].items():
@@ -328,7 +321,7 @@ def test_product_pool_kernel_with_the_real_model_over_whole_epochs_against_the_o
         assert opt.step_form() == ("pool", "")
         assert ig == io, epoch
         cg, co = opt.counters(), oe.counters()
-        for k in MAIN_CTRS:
+        for k in C21_CTRS:
             assert cg[k] == co[k], (epoch, k, cg[k], co[k])
         assert cg["EVAL_ROWS"] == cg["EXPANSIONS"] > 100 * B
         assert np.array_equal(opt.state_vecs(), oe.state_vecs()), epoch
@@ -356,7 +349,7 @@ def _follow_with_the_oracle(opt, oe, tol, calls):
     ig = opt.par_roll_out_episodes(tol, n_calls=calls)
     assert ig == io
     cg, co = opt.counters(), oe.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert cg[k] == co[k], (k, cg[k], co[k])
     assert np.array_equal(opt.state_vecs(), oe.state_vecs())
 
@@ -625,7 +618,7 @@ def test_agent_counters_say_when_they_are_not_per_agent(az):
             pool.agent_counters()
     blocks = pool.agent_counters(allow_wave_blocks=True)
     cp, ca = pool.counters(), asy.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert cp[k] == ca[k], k
         if k not in ("MAX_FRONTIER", "MAX_DEPTH"):
             assert int(blocks[k].sum()) == cp[k], k

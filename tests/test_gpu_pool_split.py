@@ -14,6 +14,8 @@ import os
 
 import pytest
 
+from gpu_parity import az  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pool_split_mi355x.json")
@@ -37,13 +39,6 @@ def _replayed(rows):
             big.add(kind)
             out.append(r)
     return out
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    assert azdopt_amd.device_count() > 0, "no MI355X visible"
-    return azdopt_amd
 
 
 def make_space(az, s):

@@ -4,98 +4,23 @@ bit-for-bit (integer / index work; the three f32 formulas evaluate, g and h_sa a
 import numpy as np
 import pytest
 
+from gpu_parity import MAIN_CTRS, CppRef, assert_tree_equal, az, compare_ramsey, run_lockstep  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-MAIN_CTRS = ["EXPANSIONS", "TERMINALS", "TRANSPOSITIONS", "VISITED_STEPS", "SELECT_CALLS", "SUM_DEG", "SUM_ACTIONS",
-             "CASCADE_NODES", "NEW_PREDS", "ROOT_EXHAUSTED", "MAX_FRONTIER", "MAX_DEPTH", "CURIOSITY_PAIRS"]
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    if azdopt_amd.device_count() < 1:
-        pytest.fail("no gfx950 device: the GPU tests need the HIP path")
-    return azdopt_amd
-
-
-def assert_tree_equal(tg, to, tag=""):
-    for f in to.FIELDS:
-        a, b = getattr(tg, f), getattr(to, f)
-        assert a.shape == b.shape, (tag, f, a.shape, b.shape)
-        if a.dtype.kind == "f":
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (tag, f)
-        else:
-            assert np.array_equal(a.astype(np.int64), b.astype(np.int64)), (tag, f)
-
 
 def run_ramsey_parity(az, orc, n, sizes, weights, B, kmin, kmax, tol, steps, epochs, seed, n_obs_tol, check_every=1,
                       sample=None, first_agent=0, threads=8, persistent=True):
     space = az.RamseySpaceNoEdgeRecolor(n, sizes, weights)
-    C = len(sizes)
     model = az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed, first_agent)
     colors, permitted = space.generate_roots(seed, B, first_agent=first_agent, kmin=kmin, kmax=kmax)
-    co, mo = orc.gen_ramsey_roots(seed, 0, first_agent, B, n, C, kmin, kmax)
+    co, mo = orc.gen_ramsey_roots(seed, 0, first_agent, B, n, len(sizes), kmin, kmax)
     assert np.array_equal(colors, co) and np.array_equal(permitted, mo)
     opt = az.NablaOptimizer.par_new(space, (colors, permitted), model, B, first_agent=first_agent, persistent=persistent)
-    oe = orc.Engine(n, B, threads=threads, ramsey=(sizes, weights))
-    assert (oe.S, oe.A, oe.KW) == (space.STATE_DIM, space.ACTION_DIM, space.KEY_WORDS)
-    oe.new_begin(colors, permitted)
-    call = 0
-    oe.new_end(orc.hash_predictions(seed, first_agent, B, space.ACTION_DIM, call))
-    agents = range(B) if sample is None else sample
-
-    def compare(tag):
-        assert np.array_equal(opt.state_vecs(), oe.state_vecs()), tag
-        for i in agents:
-            assert_tree_equal(opt.get_tree(i), oe.export_tree(i), f"{tag} agent {i}")
-            sg, so = opt.agent_state(i), oe.agent_state(i)
-            for k in ("parents", "permitted", "path", "state_pos"):
-                assert np.array_equal(sg[k], so[k]), (tag, i, k, sg[k], so[k])
-            cg, tg = opt.ramsey_agent_counts(i)
-            assert np.array_equal(cg, oe.agent_counts(i)), (tag, i)
-        ag, ao = opt.argmin_data(), oe.argmin()
-        assert np.array_equal(ag.state["colors"], ao["parents"]), tag
-        pw = min(4, space.KEY_WORDS)  # permitted EDGES: E <= 256 bits
-        assert np.array_equal(ag.state["permitted"][:pw], ao["permitted"][:pw]) and not ao["permitted"][pw:].any(), tag
-        assert ag.eval.tobytes() == ao["eval"].tobytes(), (tag, ag.eval, ao["eval"])
-        assert ag.cost["clique_counts"] == oe.argmin_totals()[:C].tolist(), tag
-        cg, co_ = opt.counters(), oe.counters()
-        for k in MAIN_CTRS:
-            assert cg[k] == co_[k], (tag, k, cg[k], co_[k])
-
-    compare("par_new")
-    for epoch in range(epochs):
-        s = 0
-        while s < steps:
-            k = min(check_every, steps - s)
-            improved_g = opt.par_roll_out_episodes(tol, n_calls=k)
-            improved_o = 0
-            for _ in range(k):
-                oe.rollout_begin(*tol)
-                call += 1
-                improved_o += oe.rollout_end(orc.hash_predictions(seed, first_agent, B, space.ACTION_DIM, call))
-            assert improved_g == improved_o, (epoch, s, improved_g, improved_o)
-            s += k
-            compare(f"epoch {epoch} step {s}")
-        sv, obs, w = opt.observe(n_obs_tol)
-        oo, ow = oe.observe(n_obs_tol)
-        # h_sa = 1 - c*/c is NaN for a child with c = c* = 0 (a monochromatic-clique-free colouring: the
-        # drivers stop there); NaN payloads are not part of the contract, everything else is bit-exact
-        nan = np.isnan(oo)
-        assert np.array_equal(np.isnan(obs), nan) and np.array_equal(w, ow)
-        assert np.array_equal(obs[~nan].view(np.uint32), oo[~nan].view(np.uint32))
-        assert np.array_equal(sv, oe.state_vecs())
-        ro = oe.modify_roots(seed, epoch, first_agent, kmin, kmax)  # the drivers' modify_root policy (02-r44.rs:196-228)
-        rg = opt.modify_roots(seed, epoch, kmin, kmax)               # the same policy on the device
-        assert np.array_equal(rg[0], ro[0]) and np.array_equal(rg[1], ro[1]), epoch
-        if epoch % 2 == 0:
-            opt.par_reset_trees_policy(seed, epoch, kmin, kmax)      # policy + reset without a host round trip
-        else:
-            opt.par_reset_trees(ro)
-        oe.reset_begin(*ro)
-        call += 1
-        oe.reset_end(orc.hash_predictions(seed, first_agent, B, space.ACTION_DIM, call))
-        compare(f"epoch {epoch} reset")
+    ref = CppRef(orc, n, sizes, weights, B, threads=threads)
+    assert (ref.e.S, ref.e.A, ref.KW) == (space.STATE_DIM, space.ACTION_DIM, space.KEY_WORDS)
+    # (h_sa = 1 - c*/c is NaN for a child with c = c* = 0 -- a monochromatic-clique-free colouring: the drivers stop there)
+    run_lockstep(opt, ref, (colors, permitted), orc, compare_ramsey(space), seed=seed, tol=tol, steps=steps, epochs=epochs, kmin=kmin,
+                 kmax=kmax, n_obs_tol=n_obs_tol, first_agent=first_agent, check_every=check_every, sample=sample)
     return opt.counters()
 
 

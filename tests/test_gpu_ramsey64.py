@@ -16,199 +16,28 @@ import numpy as np
 import pytest
 
 import mlp_f64 as M
-import ramsey64_ref as R
+from gpu_parity import (MAIN_CTRS, R3333, R3333_DIMS, R45_W, TOL, CppRef, PyRef, assert_tree_equal, az, caps,  # noqa: F401
+                        compare_ramsey, run_lockstep, same_array)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAIN_CTRS = ["EXPANSIONS", "TERMINALS", "TRANSPOSITIONS", "VISITED_STEPS", "SELECT_CALLS", "SUM_DEG", "SUM_ACTIONS",
-             "CASCADE_NODES", "NEW_PREDS", "ROOT_EXHAUSTED", "MAX_FRONTIER", "MAX_DEPTH", "CURIOSITY_PAIRS"]
-R45_W = [1.0, 0.4685 / (1.0 - 0.4685)]
-TOL = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
-R3333 = (34, [3, 3, 3, 3], [1.0] * 4)
-R3333_DIMS = (5049, 512, 1024, 512, 2244)
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    if azdopt_amd.device_count() < 1:
-        pytest.fail("no gfx950 device: the GPU tests need the HIP path")
-    return azdopt_amd
-
-
-def same_array(a, b, tag):
-    assert a.shape == b.shape, (tag, a.shape, b.shape)
-    if a.dtype.kind == "f":
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), tag
-    else:
-        assert np.array_equal(a.astype(np.int64), b.astype(np.int64)), tag
-
-
-def assert_tree_equal(tg, to, tag=""):
-    for f in tg.FIELDS:
-        same_array(getattr(tg, f), to[f] if isinstance(to, dict) else getattr(to, f), (tag, f))
-
-
-def caps(calls, space, kmax):
-    return dict(node_capacity=2 * calls + 256, arc_capacity=min(65535, 8 * calls + 256),
-                prediction_capacity=(calls + 2) * kmax * (space.C - 1) + 256)
-
-
-def words(bits, kw):
-    out = np.zeros(kw, np.uint64)
-    for b in bits:
-        out[b >> 6] |= np.uint64(1 << (b & 63))
-    return out
-
-
-class CppRef:
-    """the C++ oracle engine (N <= 32) behind the interface run_parity compares against"""
-
-    def __init__(self, orc, n, sizes, weights, B):
-        self.e = orc.Engine(n, B, threads=16, ramsey=(sizes, weights))
-        self.KW, self.C = self.e.KW, len(sizes)
-
-    def new(self, colors, permitted, h):
-        self.e.new_begin(colors, permitted)
-        self.e.new_end(h)
-
-    def step(self, h_of_call):
-        self.e.rollout_begin(*TOL)
-        return self.e.rollout_end(h_of_call())
-
-    state_vecs = lambda self: self.e.state_vecs()
-    tree = lambda self, i: self.e.export_tree(i)
-    counts = lambda self, i: self.e.agent_counts(i)
-    observe = lambda self, t: self.e.observe(t)
-    counters = lambda self: self.e.counters()
-
-    def agent_state(self, i):
-        return self.e.agent_state(i)
-
-    def argmin(self):
-        a = self.e.argmin()
-        return a["parents"], a["permitted"], a["eval"], self.e.argmin_totals()[:self.C].tolist()
-
-    def modify_roots(self, seed, epoch, kmin, kmax):
-        return self.e.modify_roots(seed, epoch, 0, kmin, kmax)
-
-    def reset(self, roots, h):
-        self.e.reset_begin(*roots)
-        self.e.reset_end(h)
-
-
-class PyRef:
-    """tests/ramsey64_ref.py's engine (any N) behind the same interface; it keeps no counters"""
-
-    def __init__(self, n, sizes, weights, B):
-        self.e = R.Ramsey64RefEngine(n, sizes, weights, B)
-        self.E, self.C = self.e.E, len(sizes)
-        self.KW = (self.e.A + 63) // 64
-
-    def new(self, colors, permitted, h):
-        self.e.new_begin(R.unpack_roots(colors, permitted, self.E))
-        self.e.new_end(h)
-
-    def step(self, h_of_call):
-        self.e.rollout_begin(*TOL)
-        return self.e.rollout_end(h_of_call())
-
-    state_vecs = lambda self: self.e.vecs
-    tree = lambda self, i: self.e.export_tree(i, self.KW)
-    counts = lambda self, i: np.array(self.e.states[i].counts, np.int32)
-    observe = lambda self, t: self.e.observe(t)
-    counters = lambda self: None
-
-    def agent_state(self, i):
-        st = self.e.states[i]
-        return dict(parents=np.array(st.colors, np.uint8), permitted=words(st.permitted, self.KW), path=words(self.e.paths[i], self.KW),
-                    state_pos=self.e.posn[i])
-
-    def argmin(self):
-        st = self.e.argmin["state"]
-        return np.array(st.colors, np.uint8), words(st.permitted, self.KW), np.float32(self.e.argmin["eval"]), list(st.totals)
-
-    def modify_roots(self, seed, epoch, kmin, kmax):
-        return R.pack_roots(self.e.modify_roots(seed, epoch, 0, kmin, kmax), self.E, self.KW)
-
-    def reset(self, roots, h):
-        self.e.reset_begin(R.unpack_roots(roots[0], roots[1], self.E))
-        self.e.reset_end(h)
 
 
 def run_parity(az, orc, ref, n, sizes, weights, B, kmin, kmax, steps, epochs, seed, n_obs_tol=4, check_every=10, sample=None, **kw):
     """run_wide_parity of tests/test_gpu_ramsey_wide.py for an engine of the 64-bit tier against `ref` (CppRef or PyRef)"""
     space = az.RamseySpaceNoEdgeRecolor(n, sizes, weights, u64=True)
     assert space.tier == "u64"
-    Cn = len(sizes)
     model = az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed)
     colors, permitted = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
-    co, mo = orc.gen_ramsey_roots(seed, 0, 0, B, n, Cn, kmin, kmax)
+    co, mo = orc.gen_ramsey_roots(seed, 0, 0, B, n, len(sizes), kmin, kmax)
     assert np.array_equal(colors, co) and np.array_equal(permitted, mo)
     opt = az.NablaOptimizer.par_new(space, (colors, permitted), model, B, **kw, **caps(steps + 8, space, kmax))
     assert ref.KW == space.KEY_WORDS
-    call = [0]
-
-    def h_next():
-        call[0] += 1
-        return orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call[0])
-
-    ref.new(colors, permitted, orc.hash_predictions(seed, 0, B, space.ACTION_DIM, 0))
-    agents = range(B) if sample is None else sample
-    pw = (space.E + 63) // 64
-    taken = opt.taken = set()  # action ids on the agents' paths at the compared moments
-
-    def compare(tag):
-        same_array(opt.state_vecs(), ref.state_vecs(), (tag, "state_vecs"))
-        for i in agents:
-            assert_tree_equal(opt.get_tree(i), ref.tree(i), f"{tag} agent {i}")
-            sg, so = opt.agent_state(i), ref.agent_state(i)
-            for k in ("parents", "permitted", "path", "state_pos"):
-                assert np.array_equal(sg[k], so[k]), (tag, i, k)
-            taken.update(64 * w + b for w, x in enumerate(sg["path"]) for b in range(64) if (int(x) >> b) & 1)
-            cg, tg = opt.ramsey_agent_counts(i)
-            assert np.array_equal(cg, ref.counts(i)), (tag, i)
-        ag = opt.argmin_data()  # (through azd_engine_ramsey_argmin_any)
-        colors_o, perm_o, eval_o, totals_o = ref.argmin()
-        assert np.array_equal(ag.state["colors"], colors_o), tag
-        assert np.array_equal(ag.state["permitted"][:pw], perm_o[:pw]) and len(ag.state["permitted"]) == pw, tag
-        assert ag.eval.tobytes() == np.float32(eval_o).tobytes(), (tag, ag.eval, eval_o)
-        assert ag.cost["clique_counts"] == totals_o, tag
-        co_ = ref.counters()
-        if co_ is not None:
-            cg = opt.counters()
-            for k in MAIN_CTRS:
-                assert cg[k] == co_[k], (tag, k, cg[k], co_[k])
-
-    compare("par_new")
-    for epoch in range(epochs):
-        s = 0
-        while s < steps:
-            k = min(check_every, steps - s)
-            improved_g = opt.par_roll_out_episodes(TOL, n_calls=k)
-            improved_o = sum(ref.step(h_next) for _ in range(k))
-            assert improved_g == improved_o, (epoch, s, improved_g, improved_o)
-            s += k
-            compare(f"epoch {epoch} step {s}")
-        sv, obs, w = opt.observe(n_obs_tol)
-        oo, ow = ref.observe(n_obs_tol)
-        nan = np.isnan(oo)
-        assert np.array_equal(np.isnan(obs), nan) and np.array_equal(w, ow)
-        assert np.array_equal(obs[~nan].view(np.uint32), oo[~nan].view(np.uint32))
-        same_array(sv, ref.state_vecs(), "observe rows")
-        ro = ref.modify_roots(seed, epoch, kmin, kmax)
-        rg = opt.modify_roots(seed, epoch, kmin, kmax)  # the drivers' modify_root policy on the device
-        assert np.array_equal(rg[0], ro[0]) and np.array_equal(rg[1], ro[1]), epoch
-        if epoch % 2 == 0:
-            opt.par_reset_trees_policy(seed, epoch, kmin, kmax)
-        else:
-            opt.par_reset_trees(ro)
-        ref.reset(ro, h_next())
-        compare(f"epoch {epoch} reset")
-    c = opt.counters()
-    assert c["FAILED"] == 0 and c["EXPANSIONS"] > 0
-    assert opt.step_form()[0].startswith("per_call"), opt.step_form()
+    opt.taken = set()  # action ids on the agents' paths at the compared moments
+    run_lockstep(opt, ref, (colors, permitted), orc, compare_ramsey(space, taken=opt.taken, argmin_any=True), seed=seed, tol=TOL,
+                 steps=steps, epochs=epochs, kmin=kmin, kmax=kmax, n_obs_tol=n_obs_tol, check_every=check_every, sample=sample,
+                 form="per_call")
     return opt, ref
 
 

@@ -19,21 +19,14 @@ import pytest
 
 import ramsey64_ref as R
 import ramsey_big_cases as K
-from test_gpu_ramsey64 import MAIN_CTRS, R45_W, TOL, CppRef, PyRef, assert_tree_equal, caps, same_array
-from test_gpu_ramsey_ext_pool import SMALL, assert_same_run, run_model
+from gpu_parity import (MAIN_CTRS, R45_W, TOL, CppRef, PyRef, assert_same_run, assert_tree_equal, az, caps, compare_ramsey,  # noqa: F401
+                        run_lockstep, same_array)
+from test_gpu_ramsey_ext_pool import SMALL, run_model
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KMIN, KMAX = 10, 30
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    if azdopt_amd.device_count() < 1:
-        pytest.fail("no gfx950 device: the GPU tests need the HIP path")
-    return azdopt_amd
 
 
 def big_space(az, n, sizes, weights=None):
@@ -87,68 +80,15 @@ def run_big_parity(az, orc, make_ref, case, B, steps, seed=1, ext=False, sample=
         model = model.serve_from_pool_evaluators()
     opt = az.NablaOptimizer.par_new(space, (colors, permitted), model, B, **(dict(ext_pool_step=True) if ext else {}),
                                     **caps(steps + after + 8, space, KMAX))
-    call = [0]
 
-    def h_next():
-        call[0] += 1
-        return orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call[0])
+    def compare(opt, ref, agents, tag, ramsey=compare_ramsey(space, argmin_any=True)):
+        if tag == "par_new":  # the roots as the reference counts them, before anything rests on them
+            lo, hi, share = K.assert_not_vacuous(sizes, [RootView(sizes, colors[i], ref.counts(i)) for i in range(B)], case)
+            print("%s: big colour's totals %d..%d over %d roots, %.2f of its per-edge counts nonzero (reference)" % (case, lo, hi, B, share))
+        ramsey(opt, ref, agents, tag)
 
-    ref.new(colors, permitted, orc.hash_predictions(seed, 0, B, space.ACTION_DIM, 0))
-    lo, hi, share = K.assert_not_vacuous(sizes, [RootView(sizes, colors[i], ref.counts(i)) for i in range(B)], case)
-    print("%s: big colour's totals %d..%d over %d roots, %.2f of its per-edge counts nonzero (reference)" % (case, lo, hi, B, share))
-    agents = range(B) if sample is None else sample
-    pw = (space.E + 63) // 64
-
-    def compare(tag):
-        same_array(opt.state_vecs(), ref.state_vecs(), (tag, "state_vecs"))
-        for i in agents:
-            assert_tree_equal(opt.get_tree(i), ref.tree(i), f"{tag} agent {i}")
-            sg, so = opt.agent_state(i), ref.agent_state(i)
-            for k in ("parents", "permitted", "path", "state_pos"):
-                assert np.array_equal(sg[k], so[k]), (tag, i, k)
-            cg, tg = opt.ramsey_agent_counts(i)
-            assert np.array_equal(cg, ref.counts(i)), (tag, i)
-        ag = opt.argmin_data()  # (through azd_engine_ramsey_argmin_any)
-        colors_o, perm_o, eval_o, totals_o = ref.argmin()
-        assert np.array_equal(ag.state["colors"], colors_o), tag
-        assert np.array_equal(ag.state["permitted"][:pw], perm_o[:pw]), tag
-        assert ag.eval.tobytes() == np.float32(eval_o).tobytes(), (tag, ag.eval, eval_o)
-        assert ag.cost["clique_counts"] == totals_o, tag
-        co_ = ref.counters()
-        if co_ is not None:
-            cg = opt.counters()
-            for k in MAIN_CTRS:
-                assert cg[k] == co_[k], (tag, k, cg[k], co_[k])
-
-    def roll(count, tag):
-        s = 0
-        while s < count:
-            k = min(check_every, count - s)
-            improved_g = opt.par_roll_out_episodes(TOL, n_calls=k)
-            form = opt.step_form()
-            assert (form == ("pool", "")) if ext else form[0].startswith("per_call"), form
-            improved_o = sum(ref.step(h_next) for _ in range(k))
-            assert improved_g == improved_o, (tag, s, improved_g, improved_o)
-            s += k
-            compare(f"{tag} step {s}")
-
-    compare("par_new")
-    roll(steps, "epoch 0")
-    sv, obs, w = opt.observe(n_obs_tol)
-    oo, ow = ref.observe(n_obs_tol)
-    nan = np.isnan(oo)
-    assert np.array_equal(np.isnan(obs), nan) and np.array_equal(w, ow)
-    assert np.array_equal(obs[~nan].view(np.uint32), oo[~nan].view(np.uint32))
-    same_array(sv, ref.state_vecs(), "observe rows")
-    ro = ref.modify_roots(seed, 0, KMIN, KMAX)
-    rg = opt.modify_roots(seed, 0, KMIN, KMAX)  # the drivers' modify_root policy on the device
-    assert np.array_equal(rg[0], ro[0]) and np.array_equal(rg[1], ro[1])
-    opt.par_reset_trees_policy(seed, 0, KMIN, KMAX)
-    ref.reset(ro, h_next())
-    compare("reset")
-    roll(after, "epoch 1")
-    c = opt.counters()
-    assert c["FAILED"] == 0 and c["EXPANSIONS"] > 0
+    run_lockstep(opt, ref, (colors, permitted), orc, compare, seed=seed, tol=TOL, steps=[steps, after], kmin=KMIN, kmax=KMAX,
+                 n_obs_tol=n_obs_tol, check_every=check_every, sample=sample, last_boundary=False, form="pool" if ext else "per_call")
     if ext:
         ev_wgs, search_wgs = opt.pool_split()
         assert ev_wgs == 0 and search_wgs >= 1, (ev_wgs, search_wgs)

@@ -9,20 +9,12 @@ back with its bf16 reason."""
 import numpy as np
 import pytest
 
-from test_gpu_ramsey64 import R3333, R45_W, TOL
-from test_gpu_ramsey_ext_pool import SMALL, assert_same_run, run_model
+from gpu_parity import R3333, R45_W, TOL, assert_same_run, az  # noqa: F401
+from test_gpu_ramsey_ext_pool import SMALL, run_model
 
 pytestmark = pytest.mark.gpu
 
 F32 = dict(ext_pool_step=True, ext_pool_f32=True)
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    if azdopt_amd.device_count() < 1:
-        pytest.fail("no gfx950 device: the GPU tests need the HIP path")
-    return azdopt_amd
 
 
 def shape_space(az, shape, u64):

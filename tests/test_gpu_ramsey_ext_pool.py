@@ -10,92 +10,27 @@ import numpy as np
 import pytest
 
 import mlp_f64 as M
-from test_gpu_ramsey64 import MAIN_CTRS, R3333, R3333_DIMS, R45_W, TOL, CppRef, PyRef, assert_tree_equal, caps, same_array
+from gpu_parity import (R3333, R3333_DIMS, R45_W, TOL, CppRef, PyRef, assert_same_run, assert_tree_equal, az, caps,  # noqa: F401
+                        compare_ramsey, run_lockstep)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    if azdopt_amd.device_count() < 1:
-        pytest.fail("no gfx950 device: the GPU tests need the HIP path")
-    return azdopt_amd
 
 
 def run_ext_parity(az, orc, ref, n, sizes, weights, u64, B, kmin, kmax, steps, epochs, seed, n_obs_tol=4, check_every=10, sample=None):
     """run_parity of tests/test_gpu_ramsey64.py with the flag set, on either tier, and the form asserted to be the pool step"""
     space = az.RamseySpaceNoEdgeRecolor(n, sizes, weights, u64=u64)
     assert space.tier == ("u64" if u64 else "wide")
-    Cn = len(sizes)
     # (the stream served like a model's rows: posted by the searchers, written by k_ext_hash_rows in the evaluator's graph)
     model = az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed).serve_from_pool_evaluators()
     colors, permitted = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
-    co, mo = orc.gen_ramsey_roots(seed, 0, 0, B, n, Cn, kmin, kmax)
+    co, mo = orc.gen_ramsey_roots(seed, 0, 0, B, n, len(sizes), kmin, kmax)
     assert np.array_equal(colors, co) and np.array_equal(permitted, mo)
     opt = az.NablaOptimizer.par_new(space, (colors, permitted), model, B, ext_pool_step=True, **caps(steps + 8, space, kmax))
     assert ref.KW == space.KEY_WORDS
-    call = [0]
-
-    def h_next():
-        call[0] += 1
-        return orc.hash_predictions(seed, 0, B, space.ACTION_DIM, call[0])
-
-    ref.new(colors, permitted, orc.hash_predictions(seed, 0, B, space.ACTION_DIM, 0))
-    agents = range(B) if sample is None else sample
-    pw = (space.E + 63) // 64
-    taken = opt.taken = set()  # action ids on the agents' paths at the compared moments
-
-    def compare(tag):
-        same_array(opt.state_vecs(), ref.state_vecs(), (tag, "state_vecs"))
-        for i in agents:
-            assert_tree_equal(opt.get_tree(i), ref.tree(i), f"{tag} agent {i}")
-            sg, so = opt.agent_state(i), ref.agent_state(i)
-            for k in ("parents", "permitted", "path", "state_pos"):
-                assert np.array_equal(sg[k], so[k]), (tag, i, k)
-            taken.update(64 * w + b for w, x in enumerate(sg["path"]) for b in range(64) if (int(x) >> b) & 1)
-            cg, tg = opt.ramsey_agent_counts(i)
-            assert np.array_equal(cg, ref.counts(i)), (tag, i)
-        ag = opt.argmin_data()
-        colors_o, perm_o, eval_o, totals_o = ref.argmin()
-        assert np.array_equal(ag.state["colors"], colors_o), tag
-        assert np.array_equal(ag.state["permitted"][:pw], perm_o[:pw]) and not ag.state["permitted"][pw:].any(), tag
-        assert ag.eval.tobytes() == np.float32(eval_o).tobytes(), (tag, ag.eval, eval_o)
-        assert ag.cost["clique_counts"] == totals_o, tag
-        co_ = ref.counters()
-        if co_ is not None:
-            cg = opt.counters()
-            for k in MAIN_CTRS:
-                assert cg[k] == co_[k], (tag, k, cg[k], co_[k])
-
-    compare("par_new")
-    for epoch in range(epochs):
-        s = 0
-        while s < steps:
-            k = min(check_every, steps - s)
-            improved_g = opt.par_roll_out_episodes(TOL, n_calls=k)
-            assert opt.step_form() == ("pool", ""), opt.step_form()
-            improved_o = sum(ref.step(h_next) for _ in range(k))
-            assert improved_g == improved_o, (epoch, s, improved_g, improved_o)
-            s += k
-            compare(f"epoch {epoch} step {s}")
-        sv, obs, w = opt.observe(n_obs_tol)
-        oo, ow = ref.observe(n_obs_tol)
-        nan = np.isnan(oo)
-        assert np.array_equal(np.isnan(obs), nan) and np.array_equal(w, ow)
-        assert np.array_equal(obs[~nan].view(np.uint32), oo[~nan].view(np.uint32))
-        same_array(sv, ref.state_vecs(), "observe rows")
-        ro = ref.modify_roots(seed, epoch, kmin, kmax)
-        rg = opt.modify_roots(seed, epoch, kmin, kmax)  # the drivers' modify_root policy on the device
-        assert np.array_equal(rg[0], ro[0]) and np.array_equal(rg[1], ro[1]), epoch
-        if epoch % 2 == 0:
-            opt.par_reset_trees_policy(seed, epoch, kmin, kmax)
-        else:
-            opt.par_reset_trees(ro)
-        ref.reset(ro, h_next())
-        compare(f"epoch {epoch} reset")
-    c = opt.counters()
-    assert c["FAILED"] == 0 and c["EXPANSIONS"] > 0
+    opt.taken = set()  # action ids on the agents' paths at the compared moments
+    run_lockstep(opt, ref, (colors, permitted), orc, compare_ramsey(space, taken=opt.taken, argmin_any=u64), seed=seed, tol=TOL,
+                 steps=steps, epochs=epochs, kmin=kmin, kmax=kmax, n_obs_tol=n_obs_tol, check_every=check_every, sample=sample,
+                 form="pool")
     ev_wgs, search_wgs = opt.pool_split()
     assert ev_wgs == 0 and search_wgs >= 1, (ev_wgs, search_wgs)  # searchers only, as for a dense engine
     return opt, ref
@@ -135,18 +70,6 @@ def run_model(az, space, roots, B, calls, kmax, seed, hidden, relu, dtype, **kw)
     o = az.NablaOptimizer.par_new(space, roots, model, B, **kw, **caps(calls + 12, space, kmax))
     imp = o.par_roll_out_episodes(TOL, n_calls=calls)
     return o, imp
-
-
-def assert_same_run(o0, o1, B, tag):
-    c0, c1 = o0.counters(), o1.counters()
-    for k in MAIN_CTRS:
-        assert c0[k] == c1[k], (tag, k, c0[k], c1[k])
-    for i in range(B):
-        assert_tree_equal(o0.get_tree(i), o1.get_tree(i), f"{tag} agent {i}")
-    same_array(o0.state_vecs(), o1.state_vecs(), (tag, "state_vecs"))
-    assert np.array_equal(o0.predictions().view(np.uint32), o1.predictions().view(np.uint32)), (tag, "prediction bits")
-    a0, a1 = o0.argmin_data(), o1.argmin_data()
-    assert a0.eval.tobytes() == a1.eval.tobytes() and (a0.agent, a0.node) == (a1.agent, a1.node), tag
 
 
 SMALL, REFERENCE = (64, 64), R3333_DIMS[1:-1]

@@ -4,18 +4,11 @@ of the error a full prediction arena must raise in every step form."""
 import numpy as np
 import pytest
 
-from test_gpu_parity import MAIN_CTRS, TOL_REF, assert_tree_equal
+from gpu_parity import C21_CTRS, TOL_REF, assert_tree_equal, az  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 REF_HIDDEN = (512, 1024, 512)  # 04-c21-tree.rs:46-52
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    assert azdopt_amd.device_count() > 0, "no MI355X visible"
-    return azdopt_amd
 
 
 def test_reference_shape_runs_on_the_async_step_with_oracle_parity(az, orc):
@@ -40,7 +33,7 @@ def test_reference_shape_runs_on_the_async_step_with_oracle_parity(az, orc):
     c = opt.counters()
     assert c["EXPANSIONS"] > 0 and c["EVAL_ROWS"] == c["EXPANSIONS"]
     co = oe.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c[k] == co[k], k
     for i in range(0, B, 7):
         assert_tree_equal(opt.get_tree(i), oe.export_tree(i), f"agent {i}")
@@ -74,7 +67,7 @@ def test_reference_shape_many_calls_per_launch_all_forms_agree(az):
     (o0, i0), (o1, i1) = runs
     assert i0 == i1
     c0, c1 = o0.counters(), o1.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c0[k] == c1[k], k
     assert c0["EVAL_ROWS"] == c0["EXPANSIONS"] and c0["FAILED"] == 0
     a0, a1 = o0.argmin_data(), o1.argmin_data()

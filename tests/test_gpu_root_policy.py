@@ -13,37 +13,15 @@ import pytest
 
 import ramsey64_ref as R64
 import root_policy_ref as RP
+from gpu_parity import R45_W, TOL, assert_tree_equal, az, same_array  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
 R45_P = [0.4685, 0.5315]
-R45_W = [1.0, 0.4685 / (1.0 - 0.4685)]
 
 
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    if azdopt_amd.device_count() < 1:
-        pytest.fail("no gfx950 device: the GPU tests need the HIP path")
-    return azdopt_amd
-
-
-def same_array(a, b, tag):
-    assert a.shape == b.shape, (tag, a.shape, b.shape)
-    if a.dtype.kind == "f":
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), tag
-    else:
-        assert np.array_equal(a.astype(np.int64), b.astype(np.int64)), tag
-
-
-def assert_tree_equal(tg, to, tag=""):
-    for f in tg.FIELDS:
-        same_array(getattr(tg, f), to[f], (tag, f))
-
-
-def caps(calls, per_node):
+def caps_per_node(calls, per_node):
     return dict(node_capacity=2 * calls + 256, arc_capacity=min(65535, 8 * calls + 256), prediction_capacity=(calls + 2) * per_node + 256)
 
 
@@ -60,7 +38,7 @@ class RamseyCase:
         sp = self.space
         colors, permitted = sp.generate_roots(seed, B, kmin=kmin, kmax=kmax)
         self.opt = az.NablaOptimizer.par_new(sp, (colors, permitted), az.HashStreamModel(sp.STATE_DIM, sp.ACTION_DIM, seed), B,
-                                             **caps(40, kmax * (sp.C - 1)))
+                                             **caps_per_node(40, kmax * (sp.C - 1)))
         self.ref = RP.Ramsey64PolicyEngine(n, sizes, weights, B)
         self.call = 0
         self.ref.new_begin(R64.unpack_roots(colors, permitted, sp.E))
@@ -269,7 +247,7 @@ def test_defaults_equal_the_cpp_oracle(az, orc):
     n, sizes, B, kmin, kmax, seed = 10, [3, 3, 3], 32, 5, 12, 3
     space = az.RamseySpaceNoEdgeRecolor(n, sizes)
     roots = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
-    opt = az.NablaOptimizer.par_new(space, roots, az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed), B, **caps(40, kmax * 2))
+    opt = az.NablaOptimizer.par_new(space, roots, az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed), B, **caps_per_node(40, kmax * 2))
     oe = orc.Engine(n, B, threads=8, ramsey=(sizes, [1.0] * 3))
     oe.new_begin(*roots)
     oe.new_end(orc.hash_predictions(seed, 0, B, space.ACTION_DIM, 0))

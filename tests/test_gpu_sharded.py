@@ -7,16 +7,9 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_parity import MAIN_CTRS, TOL_REF
+from gpu_parity import C21_CTRS, TOL_REF, az  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def az():
-    import azdopt_amd
-    assert azdopt_amd.device_count() > 0, "no MI355X visible"
-    return azdopt_amd
 
 
 def _load_rccl():
@@ -82,7 +75,7 @@ def test_sharded_optimizer_world_size_one_equals_plain_optimizer(az):
     for o in (sopt, opt):
         o.par_roll_out_episodes(TOL_REF, n_calls=20)
     c0, c1 = sopt.shard.opt.counters(), opt.counters()
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert c0[k] == c1[k], k
     assert sopt.global_argmin()[0] == float(opt.argmin_data().eval)
     assert sopt.total_expansions() == c1["EXPANSIONS"]
@@ -103,5 +96,5 @@ def test_engines_on_two_devices_in_one_process(az):
         o.par_roll_out_episodes(TOL_REF, n_calls=30)
         assert o.step_form()[0] == "async"  # 64 agents: below the pool step's threshold
         res.append(o.counters())
-    for k in MAIN_CTRS:
+    for k in C21_CTRS:
         assert res[0][k] == res[1][k], k

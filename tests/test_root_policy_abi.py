@@ -15,8 +15,8 @@ WEIGHTS = {2: R45_P, 3: [3, 1, 2], 4: [1e-9, 1, 1, 1e9]}
 TOL = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
 
 
-@pytest.fixture(scope="module")
-def az():
+@pytest.fixture(scope="module", name="az")
+def package():  # (no device needed here: tests/gpu_parity.py's `az` is the GPU tests')
     import azdopt_amd
     return azdopt_amd
 

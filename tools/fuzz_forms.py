@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import azdopt_amd as az  # noqa: E402
-from test_gpu_parity import MAIN_CTRS, assert_tree_equal  # noqa: E402
+from gpu_parity import C21_CTRS, assert_tree_equal  # noqa: E402
 
 
 KNOBS = {"AZD_POOL_EARLY_POST": ["0", "1", "2"], "AZD_POOL_EXPRESS_WGS": ["0", "8", "16"], "AZD_POOL_EVAL_WGS": ["24", "64", "100"],
@@ -40,7 +40,7 @@ def _run(cases, seed):
     def same(o1, i1, o2, i2, B, tag):
         assert i1 == i2, (tag, i1, i2)
         c1, c2 = o1.counters(), o2.counters()
-        for k in MAIN_CTRS:
+        for k in C21_CTRS:
             assert c1[k] == c2[k], (tag, k, c1[k], c2[k])
         for t in rng.sample(range(B), min(B, 24)):
             assert_tree_equal(o1.get_tree(t), o2.get_tree(t), f"{tag} agent {t}")

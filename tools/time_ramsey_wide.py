@@ -17,14 +17,16 @@ import re
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import azdopt_amd as az  # noqa: E402
+from gpu_parity import TOL  # noqa: E402
 
 FORMS = {"pool": dict(pool_step=True), "async": dict(async_step=True, pool_step=False),
          "barrier": dict(async_step=False, pool_step=False), "per_call": dict(persistent=False), "ext": dict(ext_pool_step=True),
          "ext_f32": dict(ext_pool_step=True, ext_pool_f32=True)}
-TOL = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
 SHAPES = [("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "f32"), ("r45", 24, [4, 5], [1.0, 0.4685 / 0.5315], "bf16"),
           ("n32c2", 32, [4, 4], [1.0, 1.0], "f32")]
 # (tag, n, sizes, weights, dtype, options: u64 = the tier, kmax, batch, relu head)
