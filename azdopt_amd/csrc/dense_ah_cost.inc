@@ -21,34 +21,30 @@
 // the same to the bit, because the rank-two update A_rc - (v_r q_c + q_r v_c) is symmetric in (r, c) operation by operation
 // (products and the sum commute), so the square's two triangles never differ.
 //
-// The row limit is the including unit's: DENSE_AH_ROWS = 32 where nothing is defined (dense_ah_kernels.hip, AZD_ENGINE_DENSE_AH) or
-// 64 (dense_ah_wide_kernels.hip, AZD_ENGINE_DENSE_AH_WIDE: a triangle of 2080 doubles, 16.6 KB a wave), and with it the names of
-// what this file declares and the engine's argmin record -- two units of one library cannot both define azd::DenseCostAH.  Order
-// of operations, lane roles and reductions do not depend on it: at n <= 32 the two units compute the same bits.
-#ifndef DENSE_AH_ROWS
-#define DENSE_AH_ROWS DENSE_AH_MAX_N
-#define DenseAhLdsR DenseAhLds
-#define DenseAhSpaceLdsR DenseAhSpaceLds
-#define DenseCostAhR DenseCostAH
-#define DenseAhArgminRecR DenseAhArgminRec
-#endif
-static_assert(DENSE_AH_ROWS == 32 || DENSE_AH_ROWS == 64, "the lanes of one wave own the rows");
-constexpr int DENSE_AH_TRI = DENSE_AH_ROWS * (DENSE_AH_ROWS + 1) / 2;
+// The row limit ROWS is a template parameter of everything here that depends on it: 32 (DenseCostAH: dense_ah_kernels.hip,
+// AZD_ENGINE_DENSE_AH) or 64 (DenseCostAhWide: dense_ah_wide_kernels.hip, AZD_ENGINE_DENSE_AH_WIDE: a triangle of 2080 doubles,
+// 16.6 KB a wave), and the engine's argmin record follows from it -- one library may instantiate both.  Order of operations, lane
+// roles and reductions do not depend on it: at n <= 32 the two compute the same bits.
 __device__ __forceinline__ int dense_ah_at(const int r, const int c) { return r >= c ? r * (r + 1) / 2 + c : c * (c + 1) / 2 + r; }
-struct DenseAhLdsR {
-    double A[DENSE_AH_TRI]; // distance matrix (lower triangle, packed), reduced in place
-    double v[DENSE_AH_ROWS], q[DENSE_AH_ROWS]; // Householder vector and its companion, by row
-    double diag[DENSE_AH_ROWS], sub2[DENSE_AH_ROWS]; // the tridiagonal form: diagonal, squared subdiagonal
+template <int ROWS>
+struct DenseAhLdsT {
+    static_assert(ROWS == 32 || ROWS == 64, "the lanes of one wave own the rows");
+    static constexpr int TRI = ROWS * (ROWS + 1) / 2;
+    double A[TRI]; // distance matrix (lower triangle, packed), reduced in place
+    double v[ROWS], q[ROWS]; // Householder vector and its companion, by row
+    double diag[ROWS], sub2[ROWS]; // the tridiagonal form: diagonal, squared subdiagonal
 };
+using DenseAhLds = DenseAhLdsT<DENSE_AH_MAX_N>;
+using DenseAhWideLds = DenseAhLdsT<DENSE_AH_WIDE_MAX_N>;
 
-// adj: the graph's neighbourhood bitsets in LDS (n <= DENSE_AH_ROWS words are read).  hook: called once, after the BFS (the pool
+// adj: the graph's neighbourhood bitsets in LDS (n <= ROWS words are read).  hook: called once, after the BFS (the pool
 // step's deferred post, as in dense_lambda1_wave).  Wave-uniform result in `out`.
-template <class Hook>
-__device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhLdsR &w, const int n, const float slope, Hook &&hook, DenseAhCost &out) {
+template <int ROWS, class Hook>
+__device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhLdsT<ROWS> &w, const int n, const float slope, Hook &&hook, DenseAhCost &out) {
     const int lane = LANE;
     const int row = lane * (lane + 1) / 2; // this lane's row of the packed triangle (lanes < n only)
     const bool in = lane < n;
-    const uint64_t all = DENSE_AH_ROWS < 64 ? (1ull << n) - 1ull : ~0ull >> (64 - n); // (64 rows: n = 64 must not shift by 64; n >= 4)
+    const uint64_t all = ROWS < 64 ? (1ull << n) - 1ull : ~0ull >> (64 - n); // (64 rows: n = 64 must not shift by 64; n >= 4)
     // ---- BFS from every vertex at once
     int t = 0, d = 0;
     if (in) {
@@ -91,7 +87,7 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
         const double v1 = x1 - alpha;
         const double v = lane == i + 1 ? v1 : x;
         const double beta = 2.0 / (tail + v1 * v1);
-        if (lane < DENSE_AH_ROWS) w.v[lane] = v;
+        if (lane < ROWS) w.v[lane] = v;
         LDS_SYNC();
         double acc = 0.0;
         if (act)
@@ -100,7 +96,7 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
         const double vp = dense_tree_sum(v * p);
         const double K = (0.5 * beta) * vp;
         const double q = act ? p - K * v : 0.0;
-        if (lane < DENSE_AH_ROWS) w.q[lane] = q;
+        if (lane < ROWS) w.q[lane] = q;
         LDS_SYNC();
         if (act)
             for (int c = i + 1; c <= lane; ++c) w.A[row + c] = w.A[row + c] - (v * w.q[c] + q * w.v[c]);
@@ -117,7 +113,7 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
     const double sb_below = __shfl(sb, lane > 0 ? lane - 1 : 0, 64);
     const double g = (fabs(dg) + (lane > 0 ? fabs(sb_below) : 0.0)) + fabs(sb); // Gershgorin; >= 0: the bit patterns order like the numbers
     const double R = __longlong_as_double((long long)wave_max_u64(in ? (uint64_t)__double_as_longlong(g) : 0ull));
-    if (lane < DENSE_AH_ROWS) {
+    if (lane < ROWS) {
         w.diag[lane] = dg;
         w.sub2[lane] = sb * sb;
     }
@@ -151,9 +147,9 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
 }
 
 // ---------------------------------------------------------------- the AH cost as a DenseSpace's cost policy (space_dense.inc)
-// A wave's block: DenseLds without the matching, with the cost's working set.  4 <= n <= DENSE_AH_ROWS, so E <= 496 or 2016.
-template <int KW_>
-struct DenseAhSpaceLdsR {
+// A wave's block: DenseLds without the matching, with the cost's working set.  4 <= n <= ROWS, so E <= 496 or 2016.
+template <int KW_, int ROWS>
+struct DenseAhSpaceLdsT {
     uint64_t adj[DENSE_MAX_N];
     double x[32];                    // write_rows_direct's scratch (the present edges as a bitmap: 8 words at 32 rows, 32 at 64, read one past)
     uint64_t slotmask[32];
@@ -161,13 +157,15 @@ struct DenseAhSpaceLdsR {
     unsigned long long ctr[NUM_COUNTERS];
     uint16_t seq[4];
     uint32_t stack[PATH_STACK];
-    DenseAhLdsR ah;
+    DenseAhLdsT<ROWS> ah;
 };
 // An agent's record between launches lives in the arrays the default cost uses, twice as long (engine.hip allocates 2 B entries):
 // cur_lambda[t] = pi, cur_lambda[B + t] = eigenvalue, cur_mu[t] = D, cur_mu[B + t] = k.  No per-node arena: node_mate is null.
-struct DenseCostAhR {
+template <int ROWS>
+struct DenseCostAhT {
+    using ArgminRec = std::conditional_t<ROWS == DENSE_AH_MAX_N, DenseAhArgminRec, DenseAhWideArgminRec>; // (what engine.hip sizes argmin_d for)
     template <int KW_>
-    using Lds = DenseAhSpaceLdsR<KW_>;
+    using Lds = DenseAhSpaceLdsT<KW_, ROWS>;
     template <int KW_>
     struct St {
         uint64_t rem[KW_];
@@ -227,8 +225,8 @@ struct DenseCostAhR {
     }
     template <class L>
     __device__ static __forceinline__ void argmin_write(const Arenas &a, L &s, const Replay &r, const int wt, const uint32_t win_node) {
-        DenseAhArgminRecR *out = reinterpret_cast<DenseAhArgminRecR *>(a.argmin_d);
-        if (LANE < DENSE_AH_ROWS) out->adj[LANE] = LANE < a.n ? s.adj[LANE] : 0ull;
+        ArgminRec *out = reinterpret_cast<ArgminRec *>(a.argmin_d);
+        if (LANE < ROWS) out->adj[LANE] = LANE < a.n ? s.adj[LANE] : 0ull;
         if (LANE < (int)(sizeof(out->permitted) / sizeof(uint64_t))) out->permitted[LANE] = s.slotmask[LANE];
         if (LANE == 0) {
             out->proximity = r.c.proximity;
@@ -242,3 +240,25 @@ struct DenseCostAhR {
         }
     }
 };
+// Named structs, not aliases: the kernels' names carry them (k_rollout<DenseSpace<2, DenseCostAH>>)
+struct DenseCostAH : DenseCostAhT<DENSE_AH_MAX_N> {};
+struct DenseCostAhWide : DenseCostAhT<DENSE_AH_WIDE_MAX_N> {};
+
+// The cost outside any engine (space_ops.h: launch_probe_ah_cost, launch_probe_ah_cost_wide): one wave per graph, `reps` repetitions
+// (timing), the result of the last one.  Each AH unit launches the instantiation of its own row limit.
+template <int ROWS>
+__global__ __launch_bounds__(64) void k_probe_ah_cost(const uint64_t *__restrict__ adj, const int n, const int count, const int reps,
+                                                      const float slope, DenseAhCost *__restrict__ out) {
+    __shared__ uint64_t s_adj[ROWS];
+    __shared__ DenseAhLdsT<ROWS> w;
+    const int g = blockIdx.x;
+    if (g >= count) return;
+    if (LANE < ROWS) s_adj[LANE] = LANE < n ? adj[(size_t)g * n + LANE] : 0ull;
+    LDS_SYNC();
+    DenseAhCost c;
+    for (int r = 0; r < reps; ++r) {
+        dense_ah_cost_wave(s_adj, w, n, slope, DenseNoHook{}, c);
+        LDS_SYNC();
+    }
+    if (LANE == 0) out[g] = c;
+}

@@ -40,24 +40,8 @@ const SpaceOps &dense_ah_ops() {
     return ops;
 }
 
-// one wave per graph, `reps` repetitions (timing), the result of the last one
-__global__ __launch_bounds__(64) void k_probe_ah_cost(const uint64_t *__restrict__ adj, const int n, const int count, const int reps,
-                                                      const float slope, DenseAhCost *__restrict__ out) {
-    __shared__ uint64_t s_adj[DENSE_AH_MAX_N];
-    __shared__ DenseAhLds w;
-    const int g = blockIdx.x;
-    if (g >= count) return;
-    if (LANE < DENSE_AH_MAX_N) s_adj[LANE] = LANE < n ? adj[(size_t)g * n + LANE] : 0ull;
-    LDS_SYNC();
-    DenseAhCost c;
-    for (int r = 0; r < reps; ++r) {
-        dense_ah_cost_wave(s_adj, w, n, slope, DenseNoHook{}, c);
-        LDS_SYNC();
-    }
-    if (LANE == 0) out[g] = c;
-}
 void launch_probe_ah_cost(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream) {
-    k_probe_ah_cost<<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, reps, dense_ah_eval_slope(n), d_out);
+    k_probe_ah_cost<DENSE_AH_MAX_N><<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, reps, dense_ah_eval_slope(n), d_out);
 }
 
 // parity probe of the f64 primitives the cost depends on bit for bit: out[3 i] = x / y, [3 i + 1] = sqrt(|x|), [3 i + 2] = x - x / y * y

@@ -1,6 +1,6 @@
 // dense_ah_wide_kernels.hip -- the Aouchiche-Hansen cost of the dense-graph space up to 64 vertices (AZD_ENGINE_DENSE_AH_WIDE beside
-// AZD_ENGINE_DENSE_AH): dense_ah_cost.inc with a row limit of 64 -- the packed triangle is 2080 doubles, 16.6 KB a wave --
-// under names of its own, and tree_core.inc instantiated with DenseSpace<KW, DenseCostAhWide> for key widths 2 / 4 / 10
+// AZD_ENGINE_DENSE_AH): dense_ah_cost.inc's DenseCostAhWide, the cost at a row limit of 64 -- the packed triangle is 2080 doubles,
+// 16.6 KB a wave -- and tree_core.inc instantiated with DenseSpace<KW, DenseCostAhWide> for key widths 2 / 4 / 10
 // (max_slots <= min(E, 640)): launch-per-phase kernels, the device root policy, the pool step's searchers and the cost probe, as
 // dense_ah_kernels.hip has them for 32 rows.  That unit and dense_kernels.hip are not touched by this one; the evaluator side of the
 // pool step (k_ext_*) and the recovery kernels are dense_kernels.hip's.
@@ -17,12 +17,6 @@ namespace azd {
 
 #include "tree_core.inc"
 #include "space_dense.inc"
-
-#define DENSE_AH_ROWS DENSE_AH_WIDE_MAX_N
-#define DenseAhLdsR DenseAhWideLds
-#define DenseAhSpaceLdsR DenseAhWideSpaceLds
-#define DenseCostAhR DenseCostAhWide
-#define DenseAhArgminRecR DenseAhWideArgminRec
 #include "dense_ah_cost.inc"
 
 #include "root_policy.inc"
@@ -65,24 +59,8 @@ const SpaceOps &dense_ah_wide_ops() {
     return ops;
 }
 
-// one wave per graph, `reps` repetitions (timing), the result of the last one
-__global__ __launch_bounds__(64) void k_probe_ah_cost_wide(const uint64_t *__restrict__ adj, const int n, const int count, const int reps,
-                                                           const float slope, DenseAhCost *__restrict__ out) {
-    __shared__ uint64_t s_adj[DENSE_AH_WIDE_MAX_N];
-    __shared__ DenseAhWideLds w;
-    const int g = blockIdx.x;
-    if (g >= count) return;
-    s_adj[LANE] = LANE < n ? adj[(size_t)g * n + LANE] : 0ull;
-    LDS_SYNC();
-    DenseAhCost c;
-    for (int r = 0; r < reps; ++r) {
-        dense_ah_cost_wave(s_adj, w, n, slope, DenseNoHook{}, c);
-        LDS_SYNC();
-    }
-    if (LANE == 0) out[g] = c;
-}
 void launch_probe_ah_cost_wide(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream) {
-    k_probe_ah_cost_wide<<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, reps, dense_ah_eval_slope(n), d_out);
+    k_probe_ah_cost<DENSE_AH_WIDE_MAX_N><<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, reps, dense_ah_eval_slope(n), d_out);
 }
 
 } // namespace azd

@@ -3,8 +3,6 @@
 // (ramsey_ext.inc) in a translation unit of its own, apart from ramsey64_kernels.hip's launch-per-phase kernels.  The evaluator's
 // side (k_ext_take, the gathered GEMMs, k_ext_deliver) is the dense-graph space's: dense_kernels.hip, mlp_kernels.hip.
 // Built with -ffp-contract=off like the other search units.
-#define AZD_TU_ASYNC 1 // (no launch-per-phase kernel is built here)
-#define AZD_TU_POOL_SEARCH 1
 #include <hip/hip_runtime.h>
 
 #include "bf16.h"
@@ -12,19 +10,9 @@
 
 namespace azd {
 
-#include "tree_core.inc"
-#include "space_ramsey.inc"
-#include "persistent_step.inc"
-#include "async_step.inc"
-#include "pool_step.inc"
 #include "ramsey_ext.inc"
-#include "launchers.inc"
 
 #define DISPATCH_RX64(A, FN, ...) FN<RamseyExtSpace<RamseyU64Space>>(__VA_ARGS__)
-RAMSEY_EXT_POOL_SEARCH_ENTRIES(DISPATCH_RX64, RAMSEY64_EXT_WAVES)
-const PoolSearchOps &ramsey64_pool_search_ops() {
-    static const PoolSearchOps ops = {AZD_POOL_SEARCH_OPS(RAMSEY64_EXT_WAVES)};
-    return ops;
-}
+RAMSEY_EXT_POOL_SEARCH_UNIT(DISPATCH_RX64, RAMSEY64_EXT_WAVES, ramsey64_pool_search_ops)
 
 } // namespace azd

@@ -1,14 +1,22 @@
 // ramsey_ext.inc -- the Ramsey side of the searcher-only pool step (AZD_ENGINE_EXT_POOL_STEP; pool_step.inc: k_pool_search, with
 // the evaluator's batched GEMM launches outside the kernel, engine_rollout.hip: ext_pool_run): the space policies of the form and the
-// refusals of its plan.  Included inside namespace azd after space_ramsey.inc and pool_step.inc, ahead of launchers.inc, by
-// ramsey_ext_kernels.hip (32-bit wide tier) and ramsey64_ext_kernels.hip (64-bit tier), which say which policies they build.
+// refusals of its plan, between the search core and the launchers they need: a searcher-only unit of a Ramsey tier, but for the
+// policies it builds and the name it exports.  Included inside namespace azd after bf16.h and space_ops.h by ramsey_ext_kernels.hip
+// (32-bit wide tier), ramsey64_ext_kernels.hip (64-bit tier) and ramsey64_big_ext_kernels.hip (64-bit tier, cliques up to K8).
+#define AZD_TU_ASYNC 1 // (no launch-per-phase kernel is built in these units)
+#define AZD_TU_POOL_SEARCH 1
+#include "tree_core.inc"
+#include "space_ramsey.inc"
+#include "persistent_step.inc"
+#include "async_step.inc"
+#include "pool_step.inc"
 
 typedef float azd_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void st_sc1_x2(float *p, azd_f32x2 v) { asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
 __device__ __forceinline__ void st_sc1_u16(uint16_t *p, uint32_t v) { asm volatile("global_store_short %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
 
-// BASE: RamseyWideSpace<10 / 16> or RamseyU64Space, untouched (their own write_rows_direct / write_vec are compiled into the
-// existing kernels).  What the form adds is the row hand-over: the f32 row (training, observe and the tests read it) and, for a bf16
+// BASE: RamseyWideSpace<10 / 16>, RamseyU64Space or RamseyU64BigSpace, untouched (their own write_rows_direct / write_vec are
+// compiled into the existing kernels).  What the form adds is the row hand-over: the f32 row (training, observe and the tests read it) and, for a bf16
 // evaluator, the same entries as bf16 (bf16.h: round to nearest even -- a clique count can pass 256, where bf16 is no longer
 // exact) at pitch Arenas::S16, both as write-through stores: the gathered GEMM that reads them is another kernel on another stream.
 template <class BASE>
@@ -105,8 +113,15 @@ struct RamseyExtSpace : BASE {
     }
 };
 
-// ---------------------------------------------------------------- host: the refusals of the tiers' plans (launchers.inc: PoolSearch)
-#define RAMSEY_EXT_POOL_SEARCH_ENTRIES(D, WAVES)                                                                                       \
+#include "launchers.inc"
+
+// ---------------------------------------------------------------- host: a unit's PoolSearchOps (space_ops.h), exported as NAME, for its
+// key-width switch D over the policies above, with the refusals of the tiers' plans (launchers.inc: PoolSearch)
+#define RAMSEY_EXT_POOL_SEARCH_UNIT(D, WAVES, NAME)                                                                                    \
     AZD_POOL_SEARCH_ENTRIES(D, WAVES, "external pool step: more than 65536 agents or nodes per tree",                                  \
                             "external pool step: more wavefronts per searcher workgroup than the kernel is built for",                 \
-                            "external pool step: the searcher waves' blocks, scratch and clique counts do not fit the CU's 160 KB of LDS")
+                            "external pool step: the searcher waves' blocks, scratch and clique counts do not fit the CU's 160 KB of LDS") \
+    const PoolSearchOps &NAME() {                                                                                                      \
+        static const PoolSearchOps ops = {AZD_POOL_SEARCH_OPS(WAVES)};                                                                 \
+        return ops;                                                                                                                    \
+    }

@@ -3,8 +3,6 @@
 // in a translation unit of its own, so that the register allocation of the existing Ramsey units stays as it is.  The evaluator's
 // side (k_ext_take, the gathered GEMMs, k_ext_deliver) is the dense-graph space's: dense_kernels.hip, mlp_kernels.hip.
 // Built with -ffp-contract=off like the other search units.
-#define AZD_TU_ASYNC 1 // (no launch-per-phase kernel is built here)
-#define AZD_TU_POOL_SEARCH 1
 #include <hip/hip_runtime.h>
 
 #include "bf16.h"
@@ -12,13 +10,7 @@
 
 namespace azd {
 
-#include "tree_core.inc"
-#include "space_ramsey.inc"
-#include "persistent_step.inc"
-#include "async_step.inc"
-#include "pool_step.inc"
 #include "ramsey_ext.inc"
-#include "launchers.inc"
 
 // key widths of a wide engine: 10 (E*C <= 640) or 16
 #define DISPATCH_RXW(A, FN, ...)                                                \
@@ -26,10 +18,6 @@ namespace azd {
         if ((A).KW == 10) FN<RamseyExtSpace<RamseyWideSpace<10>>>(__VA_ARGS__); \
         else FN<RamseyExtSpace<RamseyWideSpace<16>>>(__VA_ARGS__);              \
     } while (0)
-RAMSEY_EXT_POOL_SEARCH_ENTRIES(DISPATCH_RXW, RAMSEY_EXT_WAVES)
-const PoolSearchOps &ramsey_pool_search_ops() {
-    static const PoolSearchOps ops = {AZD_POOL_SEARCH_OPS(RAMSEY_EXT_WAVES)};
-    return ops;
-}
+RAMSEY_EXT_POOL_SEARCH_UNIT(DISPATCH_RXW, RAMSEY_EXT_WAVES, ramsey_pool_search_ops)
 
 } // namespace azd

@@ -54,35 +54,8 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 // edge.rs:48-53 colex_position for mx > mn
 __device__ __forceinline__ int colex_pos(int mx, int mn) { return mx * (mx - 1) / 2 + mn; }
 
-// The deepest count_cliques_inside an including unit asks for: 3 (clique sizes up to 5) unless the unit says otherwise before it
-// includes this file (ramsey64_big_kernels.hip: 6, sizes up to AZD_RAMSEY_BIG_CLIQUE_MAX, under names of its own).
-#ifndef RAMSEY_CLIQUE_DEPTH
-#define RAMSEY_CLIQUE_DEPTH 3
-#endif
-#if RAMSEY_CLIQUE_DEPTH == 3
-// bitset_graph/mod.rs:164-185 count_cliques_inside for k <= 3 (clique sizes up to 5).  The
-// reference's `1 + |T| >= size` filter only skips terms that are zero.
-template <class W>
-__device__ __forceinline__ int cliques_inside(const W *nb, W S, int k) {
-    if (k == 0) return 1;
-    if (k == 1) return nb_popc(S);
-    int sum = 0;
-    for (W r = S; r; r &= r - (W)1) {
-        const int u = nb_ffs(r) - 1;
-        const W T = S & nb[u] & (((W)1 << u) - (W)1);
-        if (k == 2) sum += nb_popc(T);
-        else
-            for (W q = T; q; q &= q - (W)1) {
-                const int x = nb_ffs(q) - 1;
-                sum += nb_popc(T & nb[x] & (((W)1 << x) - (W)1));
-            }
-    }
-    return sum;
-}
-#else
-// bitset_graph/mod.rs:164-185 count_cliques_inside for k <= RAMSEY_CLIQUE_DEPTH: a nest of fixed depth K, written as a compile-time
-// recursion that is inlined whole (no stack: the K sets of a lane are registers), the run-time depth picks the nest in one
-// wave-uniform switch.  Each level takes the largest vertex u of the clique and goes on in the part of the set below u.  The
+// bitset_graph/mod.rs:164-185 count_cliques_inside at a fixed depth K: a compile-time recursion that is inlined whole (no stack: the K
+// sets of a lane are registers).  Each level takes the largest vertex u of the clique and goes on in the part of the set below u.  The
 // reference's `1 + |T| >= size` filter only skips terms that are zero: from K = 4 a set with fewer than K - 1 vertices is left at once.
 template <int K, class W>
 __device__ __forceinline__ int cliques_nest(const W *nb, const W S) {
@@ -101,20 +74,39 @@ __device__ __forceinline__ int cliques_nest(const W *nb, const W S) {
         return sum;
     }
 }
-template <class W>
+// count_cliques_inside for k <= DEPTH, the deepest count a space asks for: 3 (clique sizes up to 5; RamseySpaceBase's default) as
+// written-out loops, 6 (RamseyU64BigSpace: sizes up to AZD_RAMSEY_BIG_CLIQUE_MAX) as the nest the run-time depth picks in one
+// wave-uniform switch.
+template <int DEPTH, class W>
 __device__ __forceinline__ int cliques_inside(const W *nb, W S, int k) {
-    static_assert(RAMSEY_CLIQUE_DEPTH == 6, "the switch below is written out for depths 0..6");
-    switch (k) {
-    case 0: return 1;
-    case 1: return cliques_nest<1>(nb, S);
-    case 2: return cliques_nest<2>(nb, S);
-    case 3: return cliques_nest<3>(nb, S);
-    case 4: return cliques_nest<4>(nb, S);
-    case 5: return cliques_nest<5>(nb, S);
-    default: return cliques_nest<6>(nb, S);
+    static_assert(DEPTH == 3 || DEPTH == 6, "written out for depths 0..3 and 0..6");
+    if constexpr (DEPTH == 3) {
+        if (k == 0) return 1;
+        if (k == 1) return nb_popc(S);
+        int sum = 0;
+        for (W r = S; r; r &= r - (W)1) {
+            const int u = nb_ffs(r) - 1;
+            const W T = S & nb[u] & (((W)1 << u) - (W)1);
+            if (k == 2) sum += nb_popc(T);
+            else
+                for (W q = T; q; q &= q - (W)1) {
+                    const int x = nb_ffs(q) - 1;
+                    sum += nb_popc(T & nb[x] & (((W)1 << x) - (W)1));
+                }
+        }
+        return sum;
+    } else {
+        switch (k) {
+        case 0: return 1;
+        case 1: return cliques_nest<1>(nb, S);
+        case 2: return cliques_nest<2>(nb, S);
+        case 3: return cliques_nest<3>(nb, S);
+        case 4: return cliques_nest<4>(nb, S);
+        case 5: return cliques_nest<5>(nb, S);
+        default: return cliques_nest<6>(nb, S);
+        }
     }
 }
-#endif
 
 // (atomicOr has no uint64_t overload: the 64-bit rows go through unsigned long long)
 __device__ __forceinline__ uint32_t *nbr_atomic(uint32_t *p) { return p; }
@@ -123,7 +115,7 @@ __device__ __forceinline__ uint32_t nbr_atomic_bit(int b, uint32_t) { return 1u 
 __device__ __forceinline__ unsigned long long nbr_atomic_bit(int b, uint64_t) { return 1ull << b; }
 
 // ramsey_counts/mod.rs:101-164 reassign_color_count_adjustment (edge uv absent from `color`'s graph)
-template <class LDS>
+template <int DEPTH, class LDS>
 __device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int E, const bool subtract, const int u,
                                               const int v, const int color, const int size) {
     if (size <= 2) return;
@@ -140,7 +132,7 @@ __device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int
             const W mem = pass ? n_v : n_u;
             const int other = pass ? u : v;
             if ((mem >> w) & (W)1) {
-                const int change = cliques_inside(nb, n_uv & nb[w], size - 3);
+                const int change = cliques_inside<DEPTH>(nb, n_uv & nb[w], size - 3);
                 if (change != 0) {
                     const int pos = other > w ? colex_pos(other, w) : colex_pos(w, other);
                     cnt[pos] += subtract ? -change : change;
@@ -154,7 +146,7 @@ __device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int
         const W mem = hi ? n_v : n_u;
         const int other = hi ? u : v;
         if ((mem >> w) & (W)1) {
-            const int change = cliques_inside(nb, n_uv & nb[w], size - 3);
+            const int change = cliques_inside<DEPTH>(nb, n_uv & nb[w], size - 3);
             if (change != 0) {
                 const int pos = other > w ? colex_pos(other, w) : colex_pos(w, other);
                 cnt[pos] += subtract ? -change : change;
@@ -168,7 +160,7 @@ __device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int
         const W n_uvw = n_uv & nb[w];
         const int x = LANE;
         if (x < LDS::NV && x > w && ((n_uv >> x) & (W)1)) {
-            const int change = cliques_inside(nb, n_uvw & nb[x], size - 4);
+            const int change = cliques_inside<DEPTH>(nb, n_uvw & nb[x], size - 4);
             if (change != 0) cnt[colex_pos(x, w)] += subtract ? -change : change;
         }
     }
@@ -178,7 +170,7 @@ __device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int
 // (below) is today's space: ME = 256, two chunks (MAX_NODE_ACTIONS).  RamseyWideSpace<KW> takes N <= 32 (ME = 496) and nodes of
 // up to 64 KW actions (select_big); the engine picks it when azd_engine_config::max_slots > 0.  The clique counts sit in the dynamic
 // LDS behind the search scratch, which is CORE_DYN_BYTES or select_big's two lists of 64 CH words, whichever is larger.
-template <int KW_, int ME, class ARG, int CH_, class W_ = uint32_t>
+template <int KW_, int ME, class ARG, int CH_, class W_ = uint32_t, int DEPTH = 3>
 struct RamseySpaceBase {
     using W = W_;                                    // neighbourhood word
     static constexpr int NV = (int)sizeof(W_) * 8;   // vertices per row: nbr is [RAMSEY_MAX_C][NV] words
@@ -310,8 +302,8 @@ struct RamseySpaceBase {
             s.nbr[oc][u] ^= (W)1 << v;
         }
         WAVE_SYNC();
-        ramsey_adjust(s, counts, E, true, u, v, oc, a.sizes[oc]);
-        ramsey_adjust(s, counts, E, false, u, v, nc, a.sizes[nc]);
+        ramsey_adjust<DEPTH>(s, counts, E, true, u, v, oc, a.sizes[oc]);
+        ramsey_adjust<DEPTH>(s, counts, E, false, u, v, nc, a.sizes[nc]);
         WAVE_SYNC();
         if (LANE == 0) {
             s.nbr[nc][v] ^= (W)1 << u;
@@ -537,7 +529,7 @@ struct RamseySpaceBase {
             for (int c = 0; c < RAMSEY_MAX_C; ++c) {
                 if (c < C) {
                     const W common = s.nbr[c][v] & s.nbr[c][u];
-                    const int cnt = cliques_inside(s.nbr[c], common, a.sizes[c] - 2);
+                    const int cnt = cliques_inside<DEPTH>(s.nbr[c], common, a.sizes[c] - 2);
                     counts[c * E + e] = cnt;
                     if ((s.nbr[c][v] >> u) & (W)1) part[c] += (uint32_t)cnt;
                 }
@@ -656,8 +648,9 @@ struct RamseyWideSpace : RamseySpaceBase<KW_, RAMSEY_WIDE_MAX_E, RamseyWideArgmi
 // the shape.  A node holds up to 64 RAMSEY_U64_CH actions -- NOT tied to the key width as RamseyWideSpace does: at 36 words
 // select_big's two lists would be 18 KB per wave.
 // (RAMSEY_U64_KW, RAMSEY_U64_CH: engine_types.h)
-struct RamseyU64Space : RamseySpaceBase<RAMSEY_U64_KW, RAMSEY_U64_MAX_E, RamseyU64ArgminRec, RAMSEY_U64_CH, uint64_t> {
-    using Base = RamseySpaceBase<RAMSEY_U64_KW, RAMSEY_U64_MAX_E, RamseyU64ArgminRec, RAMSEY_U64_CH, uint64_t>;
+template <int DEPTH>
+struct RamseyU64SpaceT : RamseySpaceBase<RAMSEY_U64_KW, RAMSEY_U64_MAX_E, RamseyU64ArgminRec, RAMSEY_U64_CH, uint64_t, DEPTH> {
+    using Base = RamseySpaceBase<RAMSEY_U64_KW, RAMSEY_U64_MAX_E, RamseyU64ArgminRec, RAMSEY_U64_CH, uint64_t, DEPTH>;
     static constexpr bool REPLAY_BY_WORD = true;
     // (write_vec goes straight to the row in memory -- 20 KB at N = 34, four colours -- there is no LDS stage to avoid: the pool step,
     // whose SP::row_stage ROWS_DIRECT replaces, is not built for this tier)
@@ -681,6 +674,10 @@ struct RamseyU64Space : RamseySpaceBase<RAMSEY_U64_KW, RAMSEY_U64_MAX_E, RamseyU
         }
     }
 };
+// Named structs, not aliases: the kernels' names carry them (k_rollout<RamseyU64Space>).  Forbidden cliques up to K5, and up to
+// AZD_RAMSEY_BIG_CLIQUE_MAX (AZD_ENGINE_RAMSEY_BIG_CLIQUES: ramsey64_big_kernels.hip, ramsey64_big_ext_kernels.hip).
+struct RamseyU64Space : RamseyU64SpaceT<3> {};
+struct RamseyU64BigSpace : RamseyU64SpaceT<6> {};
 
 // host side: what the instantiation an engine's key width selects needs of the LDS (the CU-resident forms' plans).  A wide engine's
 // keys are padded to 10 or 16 words (engine.hip), a width no narrow engine has (1..6): the key width names the engine's mode.
@@ -707,4 +704,3 @@ static inline size_t ramsey_lds_bytes(const Arenas &a) { return ramsey_wide(a) ?
     case 16: FN<RamseyWideSpace<16>>(__VA_ARGS__); break;         \
     default: FN<RamseySpace<6>>(__VA_ARGS__); break;              \
     }
-#define DISPATCH_RU64(A, FN, ...) FN<RamseyU64Space>(__VA_ARGS__)

@@ -25,7 +25,8 @@ TREE_TUS = ("tree_kernels", "async_kernels", "pool_kernels", "ramsey_kernels", "
 
 def code_object(path, tmp):
     fat, co = os.path.join(tmp, os.path.basename(path) + ".fat"), os.path.join(tmp, os.path.basename(path) + ".co")
-    if subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, path], capture_output=True).returncode != 0:
+    # (with an output file of its own: without one llvm-objcopy rewrites `path` in place, and the next make relinks the library)
+    if subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, path, co + ".unused"], capture_output=True).returncode != 0:
         return None
     r = subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
                         "--input=" + fat, "--output=" + co], capture_output=True)
