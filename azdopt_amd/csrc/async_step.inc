@@ -424,7 +424,6 @@ __global__ __launch_bounds__(PERSIST_WAVES * 64) void k_async(const PersistArgs 
         for (; call < n_calls; ++call) {
             if (LANE == 0) LDS_STORE(&ctl.prog[wave], (uint32_t)call);
             if (!due) {
-#ifdef AZD_ASYNC_LAG_PRIO
                 {   // the agents furthest behind win issue arbitration against their neighbours
                     uint32_t mn = 0xFFFFFFFFu;
                     for (int w = 0; w < n_live; ++w) {
@@ -434,13 +433,10 @@ __global__ __launch_bounds__(PERSIST_WAVES * 64) void k_async(const PersistArgs 
                     if ((uint32_t)call <= mn + (uint32_t)AZD_ASYNC_LAG_PRIO) __builtin_amdgcn_s_setprio(3);
                     else __builtin_amdgcn_s_setprio(AZD_ASYNC_BASE_PRIO);
                 }
-#endif
                 // the agent stays on this wave: its counters accumulate in LDS until the launch ends, and what the
                 // call leaves in registers (candidate, node, cost) is not read back from HBM
                 const bool expanded = rollout_agent<SP, true>(a, tol, s, dyn, t, &ro);
-#ifdef AZD_ASYNC_LAG_PRIO
                 __builtin_amdgcn_s_setprio(0);
-#endif
                 // candidate of this call for the argmin replay (first-min over this tree's new nodes)
                 if (LANE == 0 && ro.flags == 0) {
                     const uint32_t node = ro.cand_node;

@@ -309,7 +309,7 @@ struct PoolCtl {
     // ready[0] takes the agents behind the mean progress; a wave looking for work takes a ticket of ready[0] while that
     // queue holds agents or has fewer than a handful of waves standing by, so a lagging agent never waits for a wave.
     PoolQ ready[2][POOL_XCDS];
-    PoolQ evalq[2][POOL_XCDS];      // agents waiting for a prediction row, by home XCD; [0] = agents that lag behind, served first
+    PoolQ evalq[2][POOL_XCDS];      // agents waiting for a prediction row, by home XCD: all in [1]; nothing posts to [0] (it was the lagging agents' lane)
     struct {
         uint32_t v, pad[31];
     } sum_calls[POOL_XCDS], claimed[POOL_XCDS], // calls completed by / agents living on each XCD: their ratio is the mean progress
@@ -330,7 +330,7 @@ struct PendRec { // what a call that ended on a new node leaves for the add_acti
 struct PoolArgs {
     PoolCtl *ctl;
     uint32_t *ready_slots; // [2][POOL_XCDS][qcap]  agent + 1, 0 = empty
-    uint32_t *eval_slots;  // [2][POOL_XCDS][qcap]  (agent + 1) | home XCD << 24
+    uint32_t *eval_slots;  // [2][POOL_XCDS][qcap]  (agent + 1) | home XCD << 24; [0] unused, as evalq[0]
     int ready_lanes;       // 1: lane mode; 2: express mode -- the last n_express searcher workgroups run express_waves waves each (a wave
                            // searches faster with its SIMD to itself: 39 us per call against 50 with 16 waves per CU) and serve ready[0]
                            // only, which takes the agents that lag behind their XCD's progress: the launch lasts as long as the

@@ -104,6 +104,19 @@ __device__ void mlp_forward_wg(const Arenas &a, const FusedEval &ev, const int t
     }
 }
 
+// PROFILE=1: agent t's ticks of a k_persist call behind its search -- barrier wait (slot 24), evaluator (28), add_actions (29) --
+// from the stamps at the end of the roll-out, behind the barrier and behind the evaluator
+__device__ __forceinline__ void diag_persist_agent_ticks(const Arenas &a, const int t, const unsigned long long ph_r1, const unsigned long long ph_b1,
+                                                         const unsigned long long ph_m1) {
+    if constexpr (DIAG_PROFILE)
+        if (LANE == 0) {
+            unsigned long long *ctr = a.counters + (size_t)t * NUM_COUNTERS;
+            ctr[24] += ph_b1 - ph_r1;
+            ctr[28] += ph_m1 - ph_b1;
+            ctr[29] += PH_NOW() - ph_m1;
+        }
+}
+
 // The argument block lives in device memory (not in kernel arguments): ~140 dwords of pointers
 // and tables kept in SGPRs for the whole launch cost the kernel 100 spilled scalars; from memory
 // they are scalar loads at the point of use.
@@ -127,7 +140,7 @@ __global__ __launch_bounds__(PERSIST_WAVES * 64) void k_persist(const PersistArg
     WAVE_SYNC();
     for (int call = 0; call < n_calls; ++call) {
         if (active) rollout_agent<SP>(a, tol, s, dyn, t);
-        [[maybe_unused]] const unsigned long long ph_r1 = PH_NOW();
+        const unsigned long long ph_r1 = PH_NOW();
         // this call's candidate for par_update_argmmim_data: first-min over the nodes this tree
         // created since its last inspection (num_inspected_nodes = nodes.len() afterwards)
         if (LANE == 0) {
@@ -142,7 +155,7 @@ __global__ __launch_bounds__(PERSIST_WAVES * 64) void k_persist(const PersistArg
             s_cnode[wave] = node;
         }
         __syncthreads();
-        [[maybe_unused]] const unsigned long long ph_b1 = PH_NOW();
+        const unsigned long long ph_b1 = PH_NOW();
         if (wave == 0) {
             unsigned long long k = LANE < PERSIST_WAVES ? s_cand[LANE] : ~0ull;
             const unsigned long long m = wave_min_u64(k);
@@ -167,16 +180,9 @@ __global__ __launch_bounds__(PERSIST_WAVES * 64) void k_persist(const PersistArg
             }
         } // kind 1 (TrivialModel): h_theta untouched
         __syncthreads();
-        [[maybe_unused]] const unsigned long long ph_m1 = PH_NOW();
+        const unsigned long long ph_m1 = PH_NOW();
         if (active) add_actions_agent<SP>(a, s, t, 0);
-#ifdef AZD_PHASE_PROFILE
-        if (active && LANE == 0) { // diagnostic build: barrier wait / evaluator / add_actions ticks of this agent
-            unsigned long long *ctr = a.counters + (size_t)t * NUM_COUNTERS;
-            ctr[24] += ph_b1 - ph_r1;
-            ctr[28] += ph_m1 - ph_b1;
-            ctr[29] += PH_NOW() - ph_m1;
-        }
-#endif
+        if (active) diag_persist_agent_ticks(a, t, ph_r1, ph_b1, ph_m1);
     }
 }
 

@@ -66,17 +66,6 @@ __device__ __forceinline__ uint32_t pool_xcc_id() {
 #ifndef AZD_POOL_FILL_SLEEP
 #define AZD_POOL_FILL_SLEEP 32
 #endif
-// Agents that lag behind the mean progress of their XCD go through a lane of their own in front of the evaluators: the
-// launch ends with the slowest agent's chain of calls, and ~30 us of an agent's ~135 us cycle is queueing for a free
-// evaluator.  Lagging = more than max(2, mean / 32) calls behind the XCD's mean (about the slowest tenth).
-// Measured: 0 ... +2 % (28.4 -> 27.8 M at 4096 agents, 32.8 -> 33.5 at 8192, 35.9 -> 36.7 at config C; run-to-run noise is
-// +-2 %): what makes an agent slow is its own search (more re-descents, more new nodes), not the queue.  Off.
-#ifndef AZD_POOL_PRIORITY
-#define AZD_POOL_PRIORITY 0
-#endif
-#ifndef AZD_POOL_READY_SLACK
-#define AZD_POOL_READY_SLACK 0
-#endif
 #ifndef AZD_POOL_POLL_SLEEP
 // x 64 clocks between two looks of a waiting searcher wave at its ticket's slot: 127 = 3.4 us.  Shorter naps find the agent
 // sooner but cost the running waves more than that gains: 16 / 32 / 64 / 96 / 127 / 190 / 254 -> 31.9 / 32.2 / 32.6 / 33.0 / 33.0 /
@@ -95,19 +84,8 @@ __device__ __forceinline__ uint32_t pool_xcc_id() {
 #ifndef AZD_POOL_TWO_TILES
 #define AZD_POOL_TWO_TILES 1
 #endif
-#ifndef AZD_POOL_ASM_TILE
-#define AZD_POOL_ASM_TILE 0 // 1: the classic evaluator workgroups' tile task with the software-pipelined asm k loop (pool_tile1) instead of
-                            // mlp_tile_task.  Bit-identical; measured on one box (profiles/r05_group_exchange.txt): fp32 config B unchanged, config A's
-                            // classic batch 91 -> 86 us, but bf16 (config C) 15.3 -> 20.8 us of layers per batch (its per-step guards and waits cost
-                            // more than a bf16 k-step's one MFMA) and 45 spilled registers in k_pool against 22: off.  The evaluator GROUPS' k loop
-                            // (rows' quads from memory, weights from LDS) is the asm form regardless.
-#endif
 #include "tile_task_asm.inc"
-#ifdef AZD_PHASE_PROFILE
-#define POOL_FLUSH_PER_AGENT(A, S, T) flush_counters(A, S, T)
-#else
-#define POOL_FLUSH_PER_AGENT(A, S, T) ((void)0)
-#endif
+#include "pool_diag.inc"
 #ifndef AZD_POOL_EXPRESS_SLACK
 #define AZD_POOL_EXPRESS_SLACK 2 // an agent lags when its calls + SLACK + (ref >> express_shift) < ref (1 / 0 measured: no better, also in 20-call launches)
 #endif
@@ -218,59 +196,6 @@ __device__ void pool_tile2(const FusedEval &ev, const PoolRows &rows, const Eval
     }
 }
 
-// ---------------------------------------------------------------- a tile task over ONE row tile, software-pipelined (round 5)
-// mlp_tile_task's arithmetic (same MFMA sequence per output element: k-steps ascending, per step the quads' x, y, z, w) with the
-// k loop as one asm block (tile_task_asm.inc, generated by tools/gen_tile_asm.py): the weight quads of the NEXT group of 8
-// k-steps are requested before the MFMAs of the current group.  hipcc cannot be talked into the counted wait for a loop with a
-// runtime trip count (it drains to vmcnt(0) at every merge), hence asm with registers of its own.  What it buys
-// (profiles/r05_group_exchange.txt, r05_bench_lines.txt): 23.2 -> 19.6 us per 16-row batch of the 3 x 256 fp32 model in the probe
-// (tools/probes/group_exchange.hip); in the pool step itself config A's batch 91 -> 86 us, config B's unchanged (23.4 us of
-// layers against 13.2 us of MFMA issue at the 2.37 GHz the evaluator CUs hold: AZD_CTR_EVAL_LAYER_CLOCKS).
-// (the lane id is read through volatile asm on both sides of the k loop: nothing per-lane is then hoisted out of the layer / tile loops
-// or kept alive across the asm block, whose 72 registers would otherwise push the evaluator path's values into scratch)
-__device__ __forceinline__ int opaque_lane() {
-    int v;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(v));
-    return v;
-}
-__device__ __forceinline__ void pool_tile1(const FusedEval &ev, const PoolRows &rows, const EvalPtrs &gp, const int l, const int tile) {
-    const int L = ev.n_layers;
-    const int K = ev.dims[l], N = ev.dims[l + 1];
-    const int S4 = (ev.dims[0] + 15) & ~15, H = ev.hid[0];
-    const int nrows = rows.count();
-    const int n0 = tile * 16;
-    const int steps = (K + 15) >> 4;
-    const size_t tile0 = (size_t)ev.p_off[l] + (size_t)tile * steps * 256; // elements: a k-step is 64 lanes x 4
-    azd_tile_acc acc = {0.f, 0.f, 0.f, 0.f};
-    {
-        const int lane = opaque_lane();
-        const int r = lane & 15;
-        float *const rbase = rows.row(r < nrows ? r : 0);
-        const int in_off = (l == 0 ? 0 : S4 + ((l - 1) & 1) * H) + 4 * (lane >> 4);
-        if (ev.bf16)
-            tile_k_loop_bf16(acc, reinterpret_cast<const uint16_t *>(gp.wpk) + tile0, (uint32_t)lane * 8u,
-                             (uint32_t)(uintptr_t)(reinterpret_cast<const uint16_t *>(rbase) + in_off), steps);
-        else
-            tile_k_loop_f32(acc, reinterpret_cast<const float *>(gp.wpk) + tile0, (uint32_t)lane * 16u, (uint32_t)(uintptr_t)(rbase + in_off), steps);
-    }
-    const int lane = opaque_lane();
-    const int col = n0 + (lane & 15);
-    if (col < N) {
-        const float bj = gp.params[ev.b_off[l] + col];
-        const int act = (l == L - 1) ? ev.final_act : 1;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = 4 * (lane >> 4) + i;
-            if (row < nrows) {
-                const float v = act_apply(acc[i] + bj, act);
-                if (l == L - 1) rows.out(row)[col] = v;
-                else if (ev.bf16) reinterpret_cast<uint16_t *>(rows.row(row))[S4 + (l & 1) * H + col] = (uint16_t)bf16_bits(v);
-                else rows.row(row)[S4 + (l & 1) * H + col] = v;
-            }
-        }
-    }
-}
-
 // FusedEval kind 4 (test harness): h(agent, call, a) of the call each agent posted (PoolArgs::post_call, stored sc1 ahead of the
 // request) instead of the MLP.  Only in the harness' instantiation of the kernel (k_pool<SP, true>): the product kernel is
 // compiled without a trace of it.
@@ -308,8 +233,7 @@ __device__ __forceinline__ void pool_eval(const PersistArgs *pa, const EvalPtrs 
             for (;;) {
                 for (uint32_t k = 0; k < (uint32_t)POOL_XCDS && n == 0u; ++k) {
                     const uint32_t x = (xcc + k) & (uint32_t)(POOL_XCDS - 1);
-                    // (lane 0, the lagging agents' queue, is only ever filled with AZD_POOL_PRIORITY: not looked at otherwise)
-                    const uint32_t h0 = AZD_POOL_PRIORITY ? ld_sc1(&ctl->evalq[0][x].head) : 0u, t0 = AZD_POOL_PRIORITY ? ld_sc1(&ctl->evalq[0][x].tail) : 0u;
+                    const uint32_t h0 = 0u, t0 = 0u; // (lane 0, once the lagging agents' queue: nothing posts to it, so it is not looked at)
                     const uint32_t h1 = ld_sc1(&ctl->evalq[1][x].head), t1 = ld_sc1(&ctl->evalq[1][x].tail);
                     const int a0 = (int)(t0 - h0) > 0 ? (int)(t0 - h0) : 0, a1 = (int)(t1 - h1) > 0 ? (int)(t1 - h1) : 0;
                     if (a0 + a1 == 0) continue;
@@ -384,12 +308,7 @@ __device__ __forceinline__ void pool_eval(const PersistArgs *pa, const EvalPtrs 
             st_sc1(slot, 0u);
             bt.agent[tid] = v ? (v & 0xFFFFFFu) - 1u : 0u;
             bt.home[tid] = v >> 24; // bits 0-2: home XCD, bit 6: posted early (join), bit 7: the agent is behind the mean progress
-#ifdef AZD_PHASE_PROFILE
-            if (v) { // diagnostic build: how long the row waited for an evaluator (slot 24, ticks of 10 ns)
-                unsigned long long *st = pl.stamp + bt.agent[tid];
-                atomicAdd(&a.counters[(size_t)bt.agent[tid] * NUM_COUNTERS + 24], (unsigned long long)wall_clock64() - __hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            }
-#endif
+            if (v) diag_row_waited_for_evaluator(a, pl, bt.agent[tid]);
         }
         __syncthreads();
         if (bt.leave) break;
@@ -425,12 +344,8 @@ __device__ __forceinline__ void pool_eval(const PersistArgs *pa, const EvalPtrs 
                     if (ev.bf16) pool_tile2<true>(ev, rows, gp, l, tile);
                     else pool_tile2<false>(ev, rows, gp, l, tile);
                 } else {
-#if AZD_POOL_ASM_TILE
-                    pool_tile1(ev, rows, gp, l, tile);
-#else
                     unsigned long long ph[3];
                     mlp_tile_task<PoolRows, true>(ev, rows, gp, l, tile, ph);
-#endif
                 }
             }
             __syncthreads();
@@ -454,9 +369,7 @@ __device__ __forceinline__ void pool_eval(const PersistArgs *pa, const EvalPtrs 
         // computes the new node's cost): whoever comes second queues it
         // (bit 6 of the request: posted early.  A request posted after the call needs no join: its wave was through first.)
         if (tid < n && ((bt.home[tid] & 0x40u) == 0u || (atomicAdd(&pl.join[bt.agent[tid]], 1u) & 1u))) {
-#ifdef AZD_PHASE_PROFILE
-            __hip_atomic_store(pl.stamp + bt.agent[tid], (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
+            diag_stamp_handed_over(pl.stamp + bt.agent[tid]);
             const uint32_t x = bt.home[tid] & (uint32_t)(POOL_XCDS - 1);
             const uint32_t rl = (pl.ready_lanes && (bt.home[tid] & 0x80u)) ? 0u : 1u;
             const uint32_t i = atomicAdd(&ctl->ready[rl][x].tail, 1u);
@@ -477,10 +390,7 @@ __device__ __forceinline__ void pool_eval(const PersistArgs *pa, const EvalPtrs 
         atomicAdd(&ctr[26], n_rows);
         atomicAdd(&ctr[27], n_tiles);
         atomicAdd(&ctr[29], busy); // 100 MHz ticks from batch taken to batch released (AZD_CTR_TICKS_BATCH)
-#ifndef AZD_PHASE_PROFILE // (the diagnostic build keeps per-agent first / last stamps in 30 / 31)
-        atomicAdd(&ctr[30], t_stage);  // ... of which: slots + state-vector rows in
-        atomicAdd(&ctr[31], t_layers); // ... of which: the layers
-#endif
+        pool_eval_stage_ticks(ctr, t_stage, t_layers); // ... of which: slots + state-vector rows in, the layers
         atomicAdd(&ctr[13], c_layers);     // the layers in SHADER clocks (AZD_CTR_EVAL_LAYER_CLOCKS): / ticks of 10 ns = the clock the evaluator CUs held
     }
 }
@@ -817,9 +727,7 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
     uint32_t *eslots[2] = {pl.eval_slots + (size_t)xcc * pl.qcap, pl.eval_slots + ((size_t)POOL_XCDS + xcc) * pl.qcap};
     for (;;) {
         // ---- take an agent: one whose prediction row has arrived, else one nobody has touched in this launch
-#ifdef AZD_WAVE_PHASES
-        const unsigned long long wp_take0 = PH_NOW();
-#endif
+        const unsigned long long wp_take0 = WAVE_NOW();
         uint32_t t = NONE, pending = 0, waited = 0;
         if (LANE == 0) {
             // 1) an agent nobody has touched in this launch, while there is one (first come, first served: an XCD gets
@@ -829,9 +737,7 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
                 if (c < B) {
                     t = c;
                     atomicAdd(&ctl->claimed[xcc].v, 1u);
-#ifdef AZD_PHASE_PROFILE
-                    a.counters[(size_t)c * NUM_COUNTERS + 31] = (unsigned long long)wall_clock64(); // diagnostic: first touched (absolute)
-#endif
+                    diag_first_touch(a, c);
                 } else LDS_STORE(&idle.claims_done, 1u);
             }
             // 2) else the next agent to come back from the evaluator on this XCD: take a ticket (fetch-add: a CAS on
@@ -861,9 +767,6 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
                         }
                     }
                     __builtin_amdgcn_s_sleep(AZD_POOL_POLL_SLEEP);
-#ifdef AZD_POOL_POLL_SLEEP2
-                    __builtin_amdgcn_s_sleep(AZD_POOL_POLL_SLEEP2);
-#endif
                     if (wt.expired()) {
                         // A ticket can legitimately wait this long: in a launch of seconds the agents of this XCD may all be
                         // through while others still run.  Only a population that has made no call since the last look is stuck.
@@ -900,23 +803,16 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
         if (t == NONE) break;
         // another CU of this XCD may have run this agent since this CU last held lines of it
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#ifdef AZD_PHASE_PROFILE
-        if (LANE < 24) s.ctr[LANE] = 0; // (diagnostic build: counters per agent, flushed with every call; else per wave, flushed once: below)
-#endif
+        diag_per_agent_counters_reset(s);
         if (LANE == 0) s.ctr[31] = (unsigned long long)wall_clock64(); // the wave has an agent in hand from here (slots 30 / 31: busy ticks, stamp)
-#ifdef AZD_WAVE_PHASES
-        CTR_ADD(24, PH_NOW() - wp_take0); // ticket + wait for its slot (slot 24)
-        const unsigned long long wp_add0 = PH_NOW();
-#endif
+        diag_wave_take(s, wp_take0); // ticket + wait for its slot
+        const unsigned long long wp_add0 = WAVE_NOW();
         WAVE_SYNC();
         uint32_t call = 0u;   // calls of this launch the agent has completed (travels with the agent in PendRec)
         RolloutOut first;     // next_action's choice on the node add_actions fills below, if it does
         first.first_nact = 0u;
         if (pending) { // graph_operations.rs:32-56 for the node the previous call ended on; its row came from an evaluator CU
-#ifdef AZD_PHASE_PROFILE
-            // diagnostic build: how long the agent waited for a wave after its row was stored (slot 28)
-            CTR_ADD(28, (unsigned long long)wall_clock64() - __hip_atomic_load(pl.stamp + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-#endif
+            diag_agent_waited_for_wave(s, pl, t);
             const PendRec pr = pl.pend[t];
             RolloutOut ro;
             ro.flags = 0;
@@ -927,9 +823,7 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
             ro.n_preds = pr.n_preds;
             call = pr.call;
             add_actions_agent<SP, true>(a, s, (int)t, 0, &ro, &first);
-#ifdef AZD_WAVE_PHASES
-            CTR_ADD(14, PH_NOW() - wp_add0); // acquire fence + PendRec + add_actions with the arrived row (slot 14)
-#endif
+            diag_wave_add(s, wp_add0); // acquire fence + PendRec + add_actions with the arrived row
         }
         bool posted = false;
         for (;; ++call) {
@@ -937,14 +831,7 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
                 if (LANE == 0) {
                     atomicAdd(&ctl->done_agents, 1u);
                     if (pl.ready_lanes == 2) atomicAdd(&ctl->done_x[xcc].v, 1u);
-#ifdef AZD_PHASE_PROFILE
-                    a.counters[(size_t)t * NUM_COUNTERS + 30] = (unsigned long long)wall_clock64(); // diagnostic: last call done (absolute)
-#else
-                    // when this agent was through with the launch's calls, in 100 MHz ticks from the launch's first workgroup: the
-                    // launch lasts as long as its slowest agent's chain, and the bench line says how far behind the median that is
-                    // (azd_engine_pool_agent_finish; one store per agent and launch)
-                    pl.stamp[t] = (unsigned long long)wall_clock64() - __hip_atomic_load(&ctl->t_first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
+                    pool_last_call_done(a, pl, ctl, t);
                 }
                 break;
             }
@@ -960,21 +847,13 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
             first.first_nact = 0u;
             uint32_t behind = 0u, lane_q = 1u;
             if (HASHED || ev.kind == 3) { // where rollout_agent posts the request the moment the row is out
-#if AZD_POOL_PRIORITY
-                {   // does this agent lag behind the mean progress of the agents living on this XCD?
-                    const uint32_t cl = ld_sc1(&ctl->claimed[xcc].v);
-                    const uint32_t mean = ld_sc1(&ctl->sum_calls[xcc].v) / (cl ? cl : 1u);
-                    const uint32_t slack = (mean >> 5) > 2u ? (mean >> 5) : 2u;
-                    if (call + 1u + slack < mean) lane_q = 0u;
-                }
-#endif
                 if (pl.ready_lanes == 2) { // express mode: does this agent lag behind the unfinished agents of its XCD?
                     const uint32_t ref = LDS_LOAD(&idle.mean_calls);
                     if (call + (uint32_t)AZD_POOL_EXPRESS_SLACK + (ref >> pl.express_shift) < ref) behind = 0x80u;
                 } else if (pl.ready_lanes) { // is this agent behind the mean progress of the agents living on this XCD?
                     const uint32_t cl = ld_sc1(&ctl->claimed[xcc].v);
                     const uint32_t mean = ld_sc1(&ctl->sum_calls[xcc].v) / (cl ? cl : 1u);
-                    behind = call + 1u + (uint32_t)AZD_POOL_READY_SLACK < mean ? 0x80u : 0u;
+                    behind = call + 1u < mean ? 0x80u : 0u;
                 }
                 // early (PoolArgs::early_post): always, or -- mode 2 -- while waves stand idle waiting for agents (the end of a launch, when
                 // the slow chains are all that is left: their latency is the launch's, and a wave's time costs nothing)
@@ -993,13 +872,9 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
                 // hashed rows (test harness): the call whose row this will be, out before the request can be (both posts drain first)
                 if (HASHED && LANE == 0) st_sc1(pl.post_call + t, call);
             }
-#ifdef AZD_WAVE_PHASES
-            const unsigned long long wp_roll0 = PH_NOW();
-#endif
+            const unsigned long long wp_roll0 = WAVE_NOW();
             const bool expanded = rollout_agent<SP, true, true>(a, tol, s, dyn, (int)t, &ro);
-#ifdef AZD_WAVE_PHASES
-            CTR_ADD(28, PH_NOW() - wp_roll0); // the whole of rollout_agent, its loading of the agent and its write-back included (slot 28 of these builds)
-#endif
+            diag_wave_rollout(s, wp_roll0); // the whole of rollout_agent, its loading of the agent and its write-back included
             // candidate of this call for the argmin replay (first-min over this tree's new nodes)
             if (LANE == 0 && ro.flags == 0) {
                 const uint32_t node = ro.cand_node;
@@ -1028,21 +903,17 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
                     pl.pend[t] = pr;
                 }
                 WAVE_SYNC();
-                POOL_FLUSH_PER_AGENT(a, s, (int)t);
+                diag_per_agent_counters_flush(a, s, (int)t);
                 VM_DRAIN(); // the tree's stores are in this XCD's L2 (and the row's in memory) before the agent can move on
                 if (LANE == 0) {
                     if (!ro.posted) { // (rollout_agent posts every row it writes; kept for a caller that passes no queue)
-#ifdef AZD_PHASE_PROFILE
-                        __hip_atomic_store(pl.stamp + t, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
+                        diag_stamp_handed_over(pl.stamp + t);
                         const uint32_t i = atomicAdd(&ctl->evalq[lane_q][xcc].tail, 1u);
                         st_sc1(eslots[lane_q] + (i & qmask), (t + 1u) | ((xcc | behind) << 24));
                     }
                     // posted early: this wave is through with the agent now; if the prediction row is out already, queue the agent here
                     else if (atomicAdd(&pl.join[t], 1u) & 1u) {
-#ifdef AZD_PHASE_PROFILE
-                        __hip_atomic_store(pl.stamp + t, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
+                        diag_stamp_handed_over(pl.stamp + t);
                         const uint32_t rl = (pl.ready_lanes && behind) ? 0u : 1u;
                         const uint32_t i = atomicAdd(&ctl->ready[rl][xcc].tail, 1u);
                         st_sc1(rslots[rl] + (i & qmask), t + 1u);
@@ -1065,7 +936,7 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
         }
         if (!posted) {
             WAVE_SYNC();
-            POOL_FLUSH_PER_AGENT(a, s, (int)t);
+            diag_per_agent_counters_flush(a, s, (int)t);
         }
         if (LANE == 0) s.ctr[30] += (unsigned long long)wall_clock64() - s.ctr[31];
     }
@@ -1073,25 +944,7 @@ __device__ __forceinline__ void pool_search(const PersistArgs *pa, const int n_c
         atomicAdd(&ctl->search_busy, s.ctr[30]);
         atomicMax(&ctl->t_last, (unsigned long long)wall_clock64());
     }
-#ifndef AZD_PHASE_PROFILE
-    // The search counters of everything this wave has run, once (round 4): a read-modify-write of the agent's block behind every
-    // call was a dependent round trip (load, then store, then the drain that waits for both) at the end of each call, on the wave's
-    // time.  The host sums (or, for the three maxima, maximises) the blocks over the agents, so which block takes them does not
-    // matter; per-agent attribution is the diagnostic build's (tools/slow_agents.py and friends run on it).
-    WAVE_SYNC();
-#ifdef AZD_WAVE_PHASES
-    if ((LANE == 24 || LANE == 28) && s.ctr[LANE]) atomicAdd(&a.counters[(size_t)((blockIdx.x * PERSIST_WAVES + (threadIdx.x >> 6)) % B) * NUM_COUNTERS + LANE], s.ctr[LANE]);
-#endif
-    if (LANE < 24) {
-        const unsigned long long v = s.ctr[LANE];
-        unsigned long long *ctr = a.counters + (size_t)((blockIdx.x * PERSIST_WAVES + (threadIdx.x >> 6)) % B) * NUM_COUNTERS;
-        if (LANE == 10 || LANE == 11 || LANE == 21) atomicMax(&ctr[LANE], v);
-        else if (v) atomicAdd(&ctr[LANE], v);
-    }
-#endif
-#ifdef AZD_PHASE_PROFILE
-    if (LANE == 0 && s.ctr[28]) atomicAdd(&a.counters[(size_t)((blockIdx.x * PERSIST_WAVES + (threadIdx.x >> 6)) % B) * NUM_COUNTERS + 28], s.ctr[28]);
-#endif
+    POOL_SEARCH_FLUSH(a, s, B);
 }
 
 // MODE: see pool_search (1: the test harness' hashed rows, FusedEval kind 4 / pool_hash_rows; 2: run-ahead window)
@@ -1135,9 +988,6 @@ __global__ __launch_bounds__(PERSIST_WAVES * 64) void k_pool(const PersistArgs *
     SP::prepare(pa->a, s);
     if (LANE < NUM_COUNTERS) s.ctr[LANE] = 0;
     __syncthreads();
-#ifdef AZD_POOL_ACTIVE_WAVES // experiment: how much do the waves of a CU slow each other down?
-    if (wave >= AZD_POOL_ACTIVE_WAVES) return;
-#endif
     // express mode: the last n_express searcher workgroups keep express_waves waves (one per SIMD) and serve the lagging agents
     const bool express = pa->pool.ready_lanes == 2 && (int)blockIdx.x >= (int)gridDim.x - pa->pool.n_express;
     if (express && (uint32_t)wave >= pa->pool.express_waves) return;

@@ -42,17 +42,40 @@
 // slots 16..22.  In the product build PH_NOW() folds to 0 and the adds vanish.
 // AZD_WAVE_PHASES (make VARIANT=phases EXTRA=-DAZD_WAVE_PHASES=1; tools/wave_phases.py): the same stamps summed per WAVE and flushed once
 // at the end of the launch -- none of the diagnostic build's per-agent, per-call counter traffic, so the shares are the product build's.
-#if defined(AZD_PHASE_PROFILE) || defined(AZD_WAVE_PHASES)
-#define PH_NOW() ((unsigned long long)wall_clock64())
+// Which build this is, for the diagnostic hooks (here, persistent_step.inc and pool_diag.inc, whose table says what each build
+// keeps in which counter slot): they test these constants, so no function body needs an #if.
+#ifdef AZD_PHASE_PROFILE
+constexpr bool DIAG_PROFILE = true;
 #else
-#define PH_NOW() (0ull)
+constexpr bool DIAG_PROFILE = false;
 #endif
+#ifdef AZD_WAVE_PHASES
+constexpr bool DIAG_WAVE = true;
+#else
+constexpr bool DIAG_WAVE = false;
+#endif
+#define PH_NOW() ((DIAG_PROFILE || DIAG_WAVE) ? (unsigned long long)wall_clock64() : 0ull)
+#define PROF_NOW() (DIAG_PROFILE ? (unsigned long long)wall_clock64() : 0ull) // stamps only PROFILE=1 takes ...
+#define WAVE_NOW() (DIAG_WAVE ? (unsigned long long)wall_clock64() : 0ull)    // ... and only the AZD_WAVE_PHASES builds
 
 // per-call counters live in the wave's LDS block `s` (lane 0 updates; values are wave-uniform)
 #define CTR_ADD(K, V)                                            \
     do {                                                         \
         if (LANE == 0) s.ctr[K] += (unsigned long long)(V);      \
     } while (0)
+#define PROF_CTR_ADD(K, V)                                                   \
+    do {                                                                     \
+        if (DIAG_PROFILE && LANE == 0) s.ctr[K] += (unsigned long long)(V);  \
+    } while (0)
+#define WAVE_CTR_ADD(K, V)                                                   \
+    do {                                                                     \
+        if (DIAG_WAVE && LANE == 0) s.ctr[K] += (unsigned long long)(V);     \
+    } while (0)
+// PROFILE=1 keeps in PoolArgs::stamp[agent] the moment the agent was last handed over: its row posted to an evaluator queue, or the
+// agent put on a ready queue (pool_diag.inc)
+__device__ __forceinline__ void diag_stamp_handed_over(unsigned long long *stamp) {
+    if constexpr (DIAG_PROFILE) __hip_atomic_store(stamp, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 #define CTR_MAX(K, V)                                                                        \
     do {                                                                                     \
         if (LANE == 0 && (unsigned long long)(V) > s.ctr[K]) s.ctr[K] = (unsigned long long)(V); \
@@ -1054,19 +1077,15 @@ __device__ __forceinline__ void select_small(Agent<KW> &ag, LDS &s, SelCtr &sc, 
         n_exp += (uint32_t)__popcll(exp_mask[ch]);
     }
     sc.deg += n_exp;
-#ifdef AZD_PHASE_PROFILE
-    const unsigned long long ph_sel1 = PH_NOW(); // the node's predictions have arrived (slot 13)
-    CTR_ADD(13, ph_sel1 - ph_sel0);
-#endif
+    const unsigned long long ph_sel1 = PROF_NOW(); // the node's predictions have arrived (slot 13)
+    PROF_CTR_ADD(13, ph_sel1 - ph_sel0);
     // ---- revisit_choice (next_action.rs:28-53): first-min of (n_t, c_t_star) over ACTIVE
     // children in newest-arc-first order  ==  min key, ties -> largest arc id
     uint64_t kmin = rkey[0];
 #pragma unroll
     for (int ch = 1; ch < NCH; ++ch) kmin = rkey[ch] < kmin ? rkey[ch] : kmin;
     kmin = wave_min_u64(kmin);
-#ifdef AZD_PHASE_PROFILE
-    CTR_ADD(14, PH_NOW() - ph_sel1); // ... reduced (slot 14)
-#endif
+    PROF_CTR_ADD(14, PROF_NOW() - ph_sel1); // ... reduced (slot 14)
     bool have_r = kmin != ~0ull;
     uint32_t r_arc = 0, r_nt = (uint32_t)(kmin >> 32);
     if (have_r) {
@@ -1437,9 +1456,7 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
                 if (POOL && post_pending) {
                     VM_DRAIN(); // the row is in memory before anyone can see the request
                     if (LANE == 0) {
-#ifdef AZD_PHASE_PROFILE
-                        __hip_atomic_store(out->post_stamp, (unsigned long long)wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
+                        diag_stamp_handed_over(out->post_stamp);
                         const uint32_t i = atomicAdd(out->post_tail, 1u);
                         st_sc1(out->post_slots + (i & out->post_mask), out->post_word);
                     }

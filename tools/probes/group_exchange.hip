@@ -442,9 +442,10 @@ __global__ __launch_bounds__(1024) void k_classic2(Args a) {
     if (threadIdx.x == 0) a.stat[(size_t)blockIdx.x * 8] = t_total;
 }
 
-// classic form with the generated asm k loop (tools/gen_tile_asm.py -> azdopt_amd/csrc/tile_task_asm.inc): within a tile task
-// the next group of 8 k-steps is requested before the current group's MFMAs
+// classic form with the generated asm k loop (tools/gen_tile_asm.py -> tile_task_asm_probe.inc; the product's file for the
+// accumulator type): within a tile task the next group of 8 k-steps is requested before the current group's MFMAs
 #include "../../azdopt_amd/csrc/tile_task_asm.inc"
+#include "tile_task_asm_probe.inc"
 template <int XPF> // XPF = 1: the k loop only (every layer begins with one exposed request)
 __global__ __launch_bounds__(1024) void k_classic3(Args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
