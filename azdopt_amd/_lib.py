@@ -25,7 +25,7 @@ ENGINE_DENSE_AH = 32    # AZD_ENGINE_DENSE_AH: the dense-graph space with the Ao
 ENGINE_RAMSEY_U64 = 16  # AZD_ENGINE_RAMSEY_U64: the 64-bit Ramsey tier (n <= 64, E*C <= 2304), beside max_slots > 0
 ENGINE_EXT_POOL_STEP = 64  # AZD_ENGINE_EXT_POOL_STEP: Ramsey engines with max_slots > 0: searcher-only pool step, batched GEMMs beside it
 ENGINE_DENSE_AH_WIDE = 256  # AZD_ENGINE_DENSE_AH_WIDE: beside ENGINE_DENSE_AH only: the Aouchiche-Hansen cost up to n = 64 (64-row kernels)
-ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STEP only: that form with an fp32 model (gathered fp32 GEMMs)
+ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STEP (Ramsey), alone on SPACE_DENSE: that form with an fp32 model (gathered fp32 GEMMs)
 ENGINE_RAMSEY_BIG_CLIQUES = 512  # AZD_ENGINE_RAMSEY_BIG_CLIQUES: beside ENGINE_RAMSEY_U64 only: clique sizes up to 8 (kernels of their own)
 SPACE_C21 = 1
 SPACE_RAMSEY = 2

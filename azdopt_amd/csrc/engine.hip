@@ -30,7 +30,10 @@ int device_ok(int device) {
 // The searcher-only pool step's two forms (ExtPoolForm, engine_impl.h)
 static const ExtPoolForm *ext_pool_form(bool dense_space) {
     // the dense-graph space, whatever its cost (the 64-row Aouchiche-Hansen cost has the same knobs and bounds: a setting above the 6
-    // wavefronts its kernels are built for runs what fits)
+    // wavefronts its kernels are built for runs what fits).  One evaluator stream, for fp32 rows (AZD_ENGINE_EXT_POOL_F32) as for
+    // bf16: with the gathered fp32 GEMMs a second stream gave +2..4 % at 512 agents (AH N = 31, AH-wide N = 50) and at config E's
+    // shape, and -9 % at AH N = 31 with 4096 agents (5.03 against 5.51 M expansions/s) -- no win across the shapes, so no default
+    // of its own (profiles/r16_dense_ext_f32.txt; AZD_DENSE_POOL_STREAMS=2 where it helps)
     static const ExtPoolForm dense =
         {4, 16, true, false, 1, 1, /* the request leaves with the row: the GEMMs run while the wave computes lambda_1 and the matching */
          "AZD_DENSE_NO_POOL", "AZD_DENSE_POOL_WAVES", "AZD_DENSE_POOL_SEARCH_WGS", "AZD_DENSE_POOL_STREAMS", "AZD_DENSE_POOL_ROUNDS", "AZD_DENSE_POOL_DEPTH",
@@ -39,6 +42,8 @@ static const ExtPoolForm *ext_pool_form(bool dense_space) {
          "dense-graph space: the pool step is not configured for this engine",
          "an earlier pool launch of this engine aborted: launch-per-phase form",
          "dense-graph space: the pool step needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",
+         "dense-graph space: the pool step needs an evaluator that serves gathered rows (ActionModel: bf16 storage, or fp32 storage under "
+         "AZD_ENGINE_EXT_POOL_F32)",
          "dense-graph space: the device holds no searcher workgroup of the pool step",
          "dense pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "
          "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",
@@ -57,6 +62,7 @@ static const ExtPoolForm *ext_pool_form(bool dense_space) {
          "external pool step: not configured for this engine",
          "external pool step: an earlier launch of this engine aborted: launch-per-phase form",
          "external pool step: needs an evaluator that serves gathered bf16 rows (ActionModel with bf16 storage)",
+         "external pool step: needs an evaluator that serves gathered rows (ActionModel: bf16 storage, or fp32 storage under AZD_ENGINE_EXT_POOL_F32)",
          "external pool step: the device holds no searcher workgroup",
          "external pool step aborted (a queue wait ran into its bound: the searchers or the evaluator's launches made no "
          "progress); the launch-per-phase kernels completed the launch and serve this engine from here on",
@@ -458,9 +464,16 @@ int check_engine_config(const azd_engine_config *cfg) {
                               : nullptr;
         if (bad) return refuse(bad);
     }
-    // ... and its fp32 evaluator: a second flag beside the first, never a form of its own
-    if ((cfg->flags & AZD_ENGINE_EXT_POOL_F32) && !(cfg->flags & AZD_ENGINE_EXT_POOL_STEP))
-        return refuse("AZD_ENGINE_EXT_POOL_F32 is valid only beside AZD_ENGINE_EXT_POOL_STEP (the searcher-only pool step whose fp32 evaluator it asks for)");
+    // ... and its fp32 evaluator: a second flag beside the first, never a form of its own.  The dense-graph space's searcher-only
+    // form needs no flag (it is the space's pool step, on all three tiers), so there the flag stands alone: a request to the
+    // configured pool step, refused beside the flag that rules every CU-resident form out
+    if ((cfg->flags & AZD_ENGINE_EXT_POOL_F32) && dense) {
+        if (cfg->flags & AZD_ENGINE_NO_PERSISTENT_STEP)
+            return refuse("AZD_ENGINE_EXT_POOL_F32 asks the dense-graph space's pool step, a CU-resident step form, for its fp32 evaluator: it cannot be "
+                          "combined with AZD_ENGINE_NO_PERSISTENT_STEP");
+    } else if ((cfg->flags & AZD_ENGINE_EXT_POOL_F32) && !(cfg->flags & AZD_ENGINE_EXT_POOL_STEP))
+        return refuse("AZD_ENGINE_EXT_POOL_F32 is valid only beside AZD_ENGINE_EXT_POOL_STEP (the searcher-only pool step whose fp32 evaluator it asks for), "
+                      "or alone on the dense-graph space (AZD_SPACE_DENSE), whose pool step is that form");
     return AZD_OK;
 }
 // dense-graph space, device keys: ranks of the root's modifiable slots, in 2 / 4 / 10 / 16 words (the widths dense_kernels.hip is built for)

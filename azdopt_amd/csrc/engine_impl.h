@@ -36,8 +36,9 @@ struct ExtPoolForm {
     bool keep_quarter_free;    // also without a knob: at most CUs - CUs / 4 searcher workgroups
     int early_post;            // PoolArgs::early_post without AZD_POOL_EARLY_POST
     int streams;               // evaluator streams without the knob (<= azd_engine::EXT_STREAMS)
+    // r_needs_rows: r_needs_bf16 under AZD_ENGINE_EXT_POOL_F32, where an fp32-storage evaluator serves the rows too
     const char *env_off, *env_waves, *env_wgs, *env_streams, *env_rounds, *env_depth, *env_debug, *debug_tag;
-    const char *e_waves_range, *r_not_configured, *r_failed_before, *r_needs_bf16, *r_no_wg, *r_aborted, *e_abort_hashed;
+    const char *e_waves_range, *r_not_configured, *r_failed_before, *r_needs_bf16, *r_needs_rows, *r_no_wg, *r_aborted, *e_abort_hashed;
 };
 
 // The kind of engine a configuration asks for, and what the host code goes by for it: chosen once (engine_tier, after
@@ -126,7 +127,7 @@ struct azd_engine {
     uint64_t ext_graph_layout = 0;
     int ext_graph_n = 0;
     bool ext_unsupported = false;     // the evaluator cannot serve gathered rows from device-side lists (asked once)
-    bool ext_f32 = false;             // AZD_ENGINE_EXT_POOL_F32: an fp32-storage evaluator serves the form's rows (write_predictions_gathered_f32)
+    bool ext_f32 = false;             // AZD_ENGINE_EXT_POOL_F32 (Ramsey: beside AZD_ENGINE_EXT_POOL_STEP; dense-graph space: alone): an fp32-storage evaluator serves the form's rows (write_predictions_gathered_f32)
     uint64_t ext_unsupported_layout = 0; // ... under that flag: once per evaluator layout (a storage switch is asked again)
     uint32_t *d_ext_rows = nullptr, *d_ext_home = nullptr, *d_ext_n = nullptr; // [EXT_STREAMS][B], [EXT_STREAMS][B], [EXT_STREAMS]
     unsigned long long *d_ext_t0 = nullptr; // [EXT_STREAMS] when the batch in hand was collected (PoolCtl::eval_busy)

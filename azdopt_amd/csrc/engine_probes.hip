@@ -72,7 +72,10 @@ int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *ld
     if (!cfg || !waves || !lds_bytes) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ST(check_engine_config(cfg));
     const bool ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0;
-    if (!(cfg->flags & AZD_ENGINE_EXT_POOL_STEP) && !ah_wide) {
+    // (a dense-graph configuration that sets AZD_ENGINE_EXT_POOL_F32 alone asks its pool step for the fp32 evaluator: the plan is
+    // that step's, whatever the cost -- the searchers do not know which evaluator serves them)
+    const bool dense_f32 = cfg->space_id == AZD_SPACE_DENSE && (cfg->flags & AZD_ENGINE_EXT_POOL_F32) != 0;
+    if (!(cfg->flags & AZD_ENGINE_EXT_POOL_STEP) && !ah_wide && !dense_f32) {
         azd::g_last_error = "azd_debug_ext_pool_plan: the configuration does not set AZD_ENGINE_EXT_POOL_STEP";
         return AZD_ERR_INVALID_ARGUMENT;
     }

@@ -246,11 +246,12 @@ static int ext_plan(azd_engine *e, int n_calls, ExtPlan *out, bool *runs) {
     }
     const azd::Arenas &a = ax;
     // AZD_ENGINE_EXT_POOL_F32: the evaluator's graph may read the f32 rows, which the searchers always write (write_rows_direct), so
-    // the form runs without bf16 rows; which of the two gathered forwards is captured is the evaluator's answer (its storage type)
+    // the form runs without bf16 rows; which of the two gathered forwards is captured is the evaluator's answer (its storage type).
+    // On the dense-graph space the flag stands alone and is a request to the configured pool step: the plan below is the one a
+    // bf16 model gets (the searchers do not know which evaluator serves them), and where the pool step is not configured
+    // (`configured` below) nothing changes.
     const bool f32_rows = e->ext_f32;
-    const char *const r_needs_rows = f32_rows ? "external pool step: needs an evaluator that serves gathered rows (ActionModel: bf16 storage, or fp32 "
-                                                "storage under AZD_ENGINE_EXT_POOL_F32)"
-                                              : xf.r_needs_bf16;
+    const char *const r_needs_rows = f32_rows ? xf.r_needs_rows : xf.r_needs_bf16;
     if (f32_rows && e->ext_unsupported && e->ext_unsupported_layout != e->ev->layout_version) e->ext_unsupported = false;
     const char *why = "";
     uint32_t dyn_stride = 0;

@@ -14,6 +14,11 @@
 // lane -> k mapping (step s multiplies k = 2 s and 2 s + 1), no split of K, and as many zero-padded steps behind K as k_gemm runs
 // (it pads K to a multiple of 16: a step of zeros turns an accumulator of -0.0f into +0.0f).
 //
+// The dense-graph space's pool step asks for the same evaluator (the flag alone on AZD_SPACE_DENSE): S = 3 E + 1 is a multiple of 4
+// only when E = 1 (mod 4) -- N = 31 and N = 50 take VEC, N = 8, 20, 33 and 64 the one-float path -- rows are 0/1-valued but for the
+// last entry, heads run from 56 to 4032 columns; nothing in the kernel or its launcher had to change for them
+// (tests/test_gpu_gemm_f32_gathered_dense.py).
+//
 // Shape: a batch is tens to a few hundred rows against K of 1380 .. 5049, and the chain above is K / 2 dependent MFMAs of 16
 // passes whatever the tile -- a wave alone nearly fills its SIMD's matrix pipe, so the grid is many small tiles: a block is 256
 // threads = 4 waves, one per SIMD, over 32 rows x 128 columns; the 32-row A panel is staged once and shared by the four waves,

@@ -99,7 +99,13 @@ class NablaOptimizer:
         True / False force the pool / asynchronous step, async_step=False the lock-step one, persistent=False one
         launch per phase.  ext_pool_step=True (Ramsey spaces with MAX_SLOTS > 0 only, a bf16 ActionModel): the searcher-only pool
         step with the model's batched GEMMs beside it (ENGINE_EXT_POOL_STEP); step_form() says whether it ran.  ext_pool_f32=True
-        beside it (ENGINE_EXT_POOL_F32; alone the engine refuses it): that form also with an fp32 ActionModel."""
+        beside it (ENGINE_EXT_POOL_F32; alone the engine refuses it on c21 and the Ramsey spaces): that form also with an fp32
+        ActionModel.  On a DenseGraphSpace, whose pool step IS that form, ext_pool_f32=True stands alone (all three tiers: default
+        cost, cost="ah", ah_wide=True): where the engine's configured form is the pool step (256 agents or more, or pool_step=True)
+        an fp32 ActionModel is served by the gathered fp32 GEMMs instead of falling back to one launch per phase -- same
+        predictions bit for bit; with persistent=False beside it the engine refuses it.  On an MI355X with a whole epoch per launch:
+        AH N = 31 2.6 against 0.82 M expansions/s at 512 agents, 5.5 against 4.7 M at 4096; config E's shape (8192 agents,
+        512-512-512) is SLOWER with it, 4.0 against 6.8 M (profiles/r16_dense_ext_f32.txt) -- a request, not a default."""
         if not hasattr(path, "PATH_KIND") or not path.licensed_for(space):
             raise TypeError("path encoding %r is not licensed for this space (space/axioms.rs:12-19)" % (path,))
         self.space, self.model, self.batch, self.first_agent = space, model, batch, first_agent

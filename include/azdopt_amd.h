@@ -333,7 +333,8 @@ typedef struct azd_engine_config {
  * agents) and the in-kernel form needs no second stream and no host thread; take this one for a model whose 16 bf16 rows of
  * activations do not fit an evaluator workgroup's LDS, where the in-kernel form falls back to one launch per phase (0.39 M). */
 #define AZD_ENGINE_EXT_POOL_STEP 64u
-/* Beside AZD_ENGINE_EXT_POOL_STEP only (alone: AZD_ERR_INVALID_ARGUMENT from azd_engine_create and azd_debug_ext_pool_plan): the
+/* Beside AZD_ENGINE_EXT_POOL_STEP on the Ramsey tiers (alone there, and on c21: AZD_ERR_INVALID_ARGUMENT from azd_engine_create and
+ * azd_debug_ext_pool_plan, naming both flags), ALONE on AZD_SPACE_DENSE (below): the
  * form also takes an MLP with fp32 storage (AZD_STORAGE_F32, the reference's own models).  The searchers are the same -- they
  * write the f32 row whatever the model -- and the evaluator's graph runs the layers as gathered fp32 GEMMs on
  * v_mfma_f32_32x32x2_f32 over those rows: every prediction is the sum azd_evaluator_write_predictions gives the row, bit for bit,
@@ -342,7 +343,22 @@ typedef struct azd_engine_config {
  * falling back with the "external pool step: ... bf16" reason.  A storage switch (azd_evaluator_set_weight_storage) re-captures
  * the evaluator's graph.  Measured (profiles/r10_ramsey_ext_f32.txt, fp32, against the launch-per-phase form on the same box): r3333 at
  * 512 agents 0.99 against 0.52 M expansions/s, r45 at 256 agents 1.03 against 0.31 M on the wide tier and 0.79 against 0.25 M on the
- * 64-bit tier. */
+ * 64-bit tier.
+ * AZD_SPACE_DENSE: the space's pool step is the searcher-only form and needs no flag of its own, so there this flag stands alone, on
+ * all three tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
+ * this flag beside AZD_ENGINE_NO_PERSISTENT_STEP is AZD_ERR_INVALID_ARGUMENT naming both.  It is a request to the configured pool
+ * step, not a form: where the engine's form is not the pool step (fewer than 256 agents without AZD_ENGINE_POOL_STEP) nothing
+ * changes and azd_engine_step_form gives the reason it gave.  With it an fp32 MLP is served by the same gathered fp32 GEMMs over the
+ * engine's f32 state rows, on the plan a bf16 model gets (same wavefronts per workgroup, LDS bytes and workgroups;
+ * azd_debug_ext_pool_plan takes a dense configuration with the flag); without it an fp32 MLP keeps falling back with "dense-graph
+ * space: the pool step needs an evaluator that serves gathered bf16 rows"; with it and an evaluator that serves no rows at all the
+ * reason opens with "dense-graph space:" too.  Measured on one MI355X (profiles/r16_dense_ext_f32.txt; fp32, whole epochs of 200
+ * calls in one launch, against the launch-per-phase form): AH N = 31 (1396-256-128-930) 2.62 against 0.82 M expansions/s at 512
+ * agents and 5.51 against 4.69 M at 4096; AH-wide N = 50 at 512 agents 1.51 against 0.55 M.  NOT everywhere a gain: at BASELINE
+ * configs[4]'s shape (N = 50, 512-512-512, 8192 agents) the evaluator's stream is busy 0.99 of the launch and the form runs 4.04
+ * against 6.80 M (roots of at most 612 slots: 4.03 against 5.55 M) -- at that population one whole-batch fp32 GEMM per call beats
+ * gathered batches; and with ONE call per launch (examples/ah.py's loop) 0.49 against 0.57 M.  One evaluator stream, as for bf16
+ * (AZD_DENSE_POOL_STREAMS=2: +2..4 % at 512 agents, -9 % at 4096). */
 #define AZD_ENGINE_EXT_POOL_F32 128u
 
 /* ArgminData<State, Cost> (az-discrete-opt/src/log.rs:1-11) for the c21 space */
@@ -624,9 +640,10 @@ int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks);
  * asynchronous step), AZD_POOL_MAX_RESIDENT=w (pretend the device holds w workgroups of the pool kernel at once). */
 int azd_debug_hash_stream_via_evaluators(azd_evaluator *ev, int on);
 /* The LDS plan of the searcher-only pool step (AZD_ENGINE_EXT_POOL_STEP; also a dense-graph configuration with
- * AZD_ENGINE_DENSE_AH_WIDE, whose pool step takes as many wavefronts as the LDS holds) for a configuration: wavefronts per
+ * AZD_ENGINE_DENSE_AH_WIDE, whose pool step takes as many wavefronts as the LDS holds, and any dense-graph configuration with
+ * AZD_ENGINE_EXT_POOL_F32, whose plan is the one a bf16 model gets: the flag is not read) for a configuration: wavefronts per
  * searcher workgroup and the bytes of LDS one workgroup takes (of the CU's 160 KB).  Arithmetic on the configuration: no device is
- * touched.  AZD_ERR_INVALID_ARGUMENT for a configuration azd_engine_create refuses, or one with neither flag. */
+ * touched.  AZD_ERR_INVALID_ARGUMENT for a configuration azd_engine_create refuses, or one with none of these flags. */
 int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes);
 /* The evaluator of the searcher-only pool step in isolation (tests): the MLP's gathered forward of whichever storage type it has
  * -- fp32: the gathered fp32 GEMMs of AZD_ENGINE_EXT_POOL_F32; bf16: the gathered bf16 GEMMs -- on host arrays.  states:

@@ -162,6 +162,8 @@ private:
 // Connected graphs on N <= 64 vertices, AddOrDeleteEdge actions, every edge slot modified at most once (BASELINE configs[4],
 // N = 50).  BUILD-DEFINED: the reference has the pieces (connected_bitset_graph/mod.rs, bitset_graph/space/action.rs:4-27,
 // STATE = E + ACTION + 1 at 05-ah.rs:39-40) but no live NablaStateActionSpace over general graphs; see azdopt_amd.h.
+// Step forms: from 256 agents (or under AZD_ENGINE_POOL_STEP) the pool step with a bf16 model; an fp32 model runs one launch per
+// phase, or -- par_new(..., flags = AZD_ENGINE_EXT_POOL_F32), alone on this space -- the pool step with gathered fp32 GEMMs.
 class DenseGraphSpace {
 public:
     // max_slots: the most modifiable edge slots a root may bring (azd_engine_config::max_slots; up to E / 2 in the drivers' image)
@@ -200,6 +202,8 @@ private:
 // ConnectedBitsetGraph::ah_cost, mod.rs:156-198): n <= AZD_DENSE_AH_MAX_N, max_slots <= E.  argmin_data() gives a DenseAhArgmin.
 // wide = true: the cost's 64-row form (AZD_ENGINE_DENSE_AH_WIDE beside the first flag; asked for by name, never chosen from n):
 // n <= AZD_DENSE_AH_WIDE_MAX_N, max_slots <= min(E, 640); at n <= 32 it gives what the narrow form gives.
+// AZD_ENGINE_EXT_POOL_F32 (alone) serves an fp32 model in the pool step on both forms, as on DenseGraphSpace: at N = 31 with
+// 1396-256-128-930 and 512 agents 2.6 against 0.82 M expansions/s over whole-epoch launches (profiles/r16_dense_ext_f32.txt).
 class DenseGraphAhSpace : public DenseGraphSpace {
 public:
     explicit DenseGraphAhSpace(int n, double p = 0.4, int max_slots = 128, bool wide = false) : DenseGraphSpace(n, p, max_slots), wide_(wide) {}
@@ -353,7 +357,10 @@ public:
     // optimizer (the reference moves it in; here the engine borrows the evaluator).  Capacities 0 = sized for 800 calls per epoch.
     // `flags`: the step-form options (AZD_ENGINE_POOL_STEP, AZD_ENGINE_ASYNC_STEP, AZD_ENGINE_BARRIER_STEP,
     // AZD_ENGINE_NO_PERSISTENT_STEP, and -- Ramsey spaces with max_slots > 0 and a bf16 model -- AZD_ENGINE_EXT_POOL_STEP, the
-    // searcher-only pool step with the model's batched GEMMs beside it; AZD_ENGINE_EXT_POOL_F32 beside it takes an fp32 model too);
+    // searcher-only pool step with the model's batched GEMMs beside it; AZD_ENGINE_EXT_POOL_F32 beside it takes an fp32 model too;
+    // on a DenseGraphSpace / DenseGraphAhSpace, whose pool step is that form, AZD_ENGINE_EXT_POOL_F32 stands ALONE and asks the
+    // configured pool step to serve an fp32 model instead of falling back to one launch per phase: a gain at a few hundred to a
+    // few thousand agents with whole epochs per launch, a loss at 8192 agents with 512-512-512 -- azdopt_amd.h has the numbers);
     // step_form() says which form ran and why.
     static NablaOptimizer par_new(const Space &space, const Roots &roots, NablaModel &model, int batch, int device = 0, uint64_t first_agent = 0,
                                   uint32_t flags = 0, int node_capacity = 0, int arc_capacity = 0, int prediction_capacity = 0, int layers = 0,

@@ -3,7 +3,10 @@
 models, call counts and pool-step knobs; every case runs the same seeded search in two forms -- pool step (in one launch, in
 random chunks, or call by call through a run-ahead window) against the asynchronous step for c21 / Ramsey, pool searchers
 against the launch-per-phase form for the dense-graph space -- and compares trees, counters, argmin, improvement counts and state vectors.
-    python tools/fuzz_forms.py [cases 40] [seed 0]"""
+    python tools/fuzz_forms.py [cases 40] [seed 0] [dense_f32]
+dense_f32 (run(..., dense_f32=True); tests/test_gpu_fuzz_dense_f32.py runs a 12-case slice): dense-graph cases only, on all three
+tiers, with an fp32 model in the pool step (ext_pool_f32=True: the evaluator's gathered fp32 GEMMs) against the launch-per-phase
+form; prediction bits are compared too, and a case whose pool step did not run fails.  Without it the cases drawn are what they were."""
 import os
 import random
 import sys
@@ -22,10 +25,10 @@ KNOBS = {"AZD_POOL_EARLY_POST": ["0", "1", "2"], "AZD_POOL_EXPRESS_WGS": ["0", "
          "AZD_DENSE_POOL_STREAMS": ["1", "2"]}
 
 
-def run(cases=40, seed=0):
+def run(cases=40, seed=0, dense_f32=False):
     saved = {k: os.environ.get(k) for k in list(KNOBS) + ["AZD_DENSE_NO_POOL"]}
     try:
-        _run(cases, seed)
+        _run(cases, seed, dense_f32)
     finally:  # whatever happens, the process's environment is what it was
         for k, v in saved.items():
             if v is None:
@@ -34,7 +37,7 @@ def run(cases=40, seed=0):
                 os.environ[k] = v
 
 
-def _run(cases, seed):
+def _run(cases, seed, dense_f32=False):
     rng = random.Random(seed)
 
     def same(o1, i1, o2, i2, B, tag):
@@ -47,10 +50,11 @@ def _run(cases, seed):
         a1, a2 = o1.argmin_data(), o2.argmin_data()
         assert a1.eval == a2.eval and a1.agent == a2.agent and a1.node == a2.node, tag
         assert np.array_equal(o1.state_vecs(), o2.state_vecs()), tag
-
+        if dense_f32:  # the gathered fp32 GEMMs' sums are forward's: every agent's current row, bit for bit
+            assert np.array_equal(o1.predictions().view(np.uint32), o2.predictions().view(np.uint32)), tag
 
     for case in range(cases):
-        kind = rng.choice(["c21", "c21", "ramsey", "dense", "dense"])
+        kind = "dense" if dense_f32 else rng.choice(["c21", "c21", "ramsey", "dense", "dense"])
         seed = rng.randrange(1 << 30)
         env = {k: rng.choice(v) for k, v in KNOBS.items() if rng.random() < 0.4}
         calls = rng.choice([20, 60, 150, 400])
@@ -70,6 +74,19 @@ def _run(cases, seed):
             tol = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
             kw = dict(prediction_capacity=131072)
             calls = min(calls, 150)
+        elif dense_f32:
+            cost, wide = rng.choice([("c21", False), ("c21", False), ("ah", False), ("ah", True)])
+            n = rng.choice([33, 40] if wide else [12, 20, 31] if cost == "ah" else [12, 20, 50])
+            slots = rng.choice([128, 128, 256, 612])
+            if cost == "ah":
+                slots = min(slots, n * (n - 1) // 2)
+            B = rng.choice([256, 300, 512])
+            space = az.DenseGraphSpace(n, rng.choice([0.2, 0.4]), max_slots=slots, cost=cost, ah_wide=wide)
+            hidden = rng.choice([(64,), (256, 128), (512, 512, 512)])
+            dtype = "f32"
+            tol = ([200, 50, 50], 25)
+            kw = dict(prediction_capacity=262144)
+            calls = rng.choice([20, 60, 100])
         else:
             n = rng.choice([12, 20, 50])
             slots = rng.choice([128, 128, 256, 612])
@@ -84,7 +101,7 @@ def _run(cases, seed):
         kmin = rng.randint(lo, max(lo, hi // 2))
         roots = space.generate_roots(seed, B, kmin=kmin, kmax=hi)
         mode = rng.choice(["one", "chunks", "window"]) if kind != "dense" else rng.choice(["one", "chunks"])
-        tag = f"case {case}: {kind} B={B} calls={calls} hidden={hidden} {dtype} mode={mode} env={env} seed={seed}"
+        tag = f"case {case}: {kind}{' ' + space.COST + (' wide' if space.AH_WIDE else '') + f' n={n} slots={slots}' if dense_f32 else ''} B={B} calls={calls} hidden={hidden} {dtype} mode={mode} env={env} seed={seed}"
         print(tag, flush=True)
         for k in KNOBS:
             os.environ.pop(k, None)
@@ -94,7 +111,7 @@ def _run(cases, seed):
             m = az.ActionModel(B, space.STATE_DIM, space.ACTION_DIM, hidden=hidden, seed=seed, dtype=dtype)
             return az.NablaOptimizer.par_new(space, roots, m, B, **kw, **more)
 
-        o1 = mk(pool_step=True)
+        o1 = mk(pool_step=True, **(dict(ext_pool_f32=True) if dense_f32 else {}))
         if mode == "one":
             i1 = o1.par_roll_out_episodes(tol, n_calls=calls)
         elif mode == "chunks":
@@ -113,6 +130,7 @@ def _run(cases, seed):
                 if rng.random() < 0.1:
                     o1.argmin_data()
                 left -= k
+        assert not dense_f32 or o1.step_form() == ("pool", ""), (tag, o1.step_form())
         if o1.step_form()[0] != "pool":  # (a width the in-kernel evaluator does not take: nothing to compare)
             print("   skipped:", o1.step_form())
             for k in KNOBS:  # (the case's knobs must not outlive it: they once leaked into the rest of the test session)
@@ -151,4 +169,4 @@ def _run(cases, seed):
 
 
 if __name__ == "__main__":
-    run(int(sys.argv[1]) if len(sys.argv) > 1 else 40, int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+    run(int(sys.argv[1]) if len(sys.argv) > 1 else 40, int(sys.argv[2]) if len(sys.argv) > 2 else 0, "dense_f32" in sys.argv[3:])
