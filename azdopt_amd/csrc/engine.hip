@@ -166,28 +166,13 @@ struct HashStreamEvaluator : azd_evaluator {
 
 } // namespace azd
 
-azd_evaluator::~azd_evaluator() {
-    if (d_states) (void)hipFree(d_states);
-    if (d_preds) (void)hipFree(d_preds);
-    if (d_obs) (void)hipFree(d_obs);
-    if (d_w) (void)hipFree(d_w);
-    if (own_stream) (void)hipStreamDestroy(own_stream);
-}
-
 int azd_evaluator::ensure_staging(int batch) {
     AZD_HIP(hipSetDevice(device));
-    if (!own_stream) AZD_HIP(hipStreamCreate(&own_stream));
+    if (!own_stream) AZD_ST(own_stream.create());
     if (batch <= staged_batch) return AZD_OK;
-    if (d_states) (void)hipFree(d_states);
-    if (d_preds) (void)hipFree(d_preds);
-    if (d_obs) (void)hipFree(d_obs);
-    if (d_w) (void)hipFree(d_w);
-    d_states = d_preds = d_obs = d_w = nullptr;
     staged_batch = 0;
-    AZD_HIP(hipMalloc(&d_states, (size_t)batch * state_dim * sizeof(float)));
-    AZD_HIP(hipMalloc(&d_preds, (size_t)batch * action_dim * sizeof(float)));
-    AZD_HIP(hipMalloc(&d_obs, (size_t)batch * action_dim * sizeof(float)));
-    AZD_HIP(hipMalloc(&d_w, (size_t)batch * action_dim * sizeof(float)));
+    const size_t ns = (size_t)batch * state_dim, na = (size_t)batch * action_dim;
+    AZD_ST(alloc_set(d_states, ns, d_preds, na, d_obs, na, d_w, na));
     staged_batch = batch;
     return AZD_OK;
 }
@@ -680,13 +665,12 @@ uint64_t azd_evaluator_calls(azd_evaluator *ev) { return ev ? ev->calls : 0; }
 // ------------------------------------------------------------------ engine ABI
 int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evaluator *ev) {
     if (!out || !cfg) return AZD_ERR_INVALID_ARGUMENT;
-    int st = check_engine_config(cfg);
-    if (st) return st;
+    AZD_ST(check_engine_config(cfg));
     const TierDesc *const tier = engine_tier(cfg);
     const bool ramsey = tier->space == azd::SPACE_RAMSEY, dense = tier->space == azd::SPACE_DENSE;
     AZD_ST(azd::device_ok(cfg->device));
     AZD_HIP(hipSetDevice(cfg->device));
-    azd_engine *e = new (std::nothrow) azd_engine();
+    std::unique_ptr<azd_engine> e(new (std::nothrow) azd_engine()); // whatever it holds by then goes with it on every early return
     if (!e) return AZD_ERR_OUT_OF_MEMORY;
     e->cfg = *cfg;
     e->ev = ev;
@@ -705,7 +689,6 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     if (dense || (cfg->flags & AZD_ENGINE_EXT_POOL_STEP)) e->ext = tier->ext;
     e->ext_f32 = (cfg->flags & AZD_ENGINE_EXT_POOL_F32) != 0;
     if (ev && (ev->state_dim != a.S || ev->action_dim != a.A)) {
-        delete e;
         azd::g_last_error = "evaluator dimensions do not match the space";
         return AZD_ERR_INVALID_ARGUMENT;
     }
@@ -728,99 +711,77 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         else if (per_node > 2047) snprintf(msg, sizeof msg, "%ld legal actions per node are beyond the record format (<= 2047)", per_node), bad = msg;
         if (bad) {
             azd::g_last_error = bad;
-            delete e;
             return AZD_ERR_INVALID_ARGUMENT;
         }
     }
     const size_t B = (size_t)a.B;
-#define TRY(x)              \
-    do {                    \
-        st = (x);           \
-        if (st) {           \
-            azd_engine_destroy(e); \
-            return st;      \
-        }                   \
-    } while (0)
-    {
-        hipError_t he = hipStreamCreate(&e->stream);
-        if (he != hipSuccess) {
-            st = azd::hip_fail(he, "hipStreamCreate");
-            delete e;
-            return st;
-        }
-    }
-    TRY(e->alloc(&a.nodes, B * a.node_cap));
-    TRY(e->alloc(&a.keys, B * a.node_cap * a.KW));
-    TRY(e->alloc(&a.arcs, B * a.arc_cap));
-    TRY(e->alloc(&a.preds, B * a.pred_cap));
-    TRY(e->alloc(&a.pred_g, B * a.pred_cap));
-    TRY(e->alloc(&a.ht, B * a.ht_cap));
-    TRY(e->alloc(&a.root_parents, B * azd::PARENTS_STRIDE));
-    TRY(e->alloc(&a.cur_parents, B * azd::PARENTS_STRIDE));
-    TRY(e->alloc(&a.root_perm, B * a.KW));
-    TRY(e->alloc(&a.cur_perm, B * a.KW));
-    TRY(e->alloc(&a.cur_path, B * a.KW));
+    AZD_ST(e->stream.create());
+    AZD_ST(e->alloc(&a.nodes, B * a.node_cap));
+    AZD_ST(e->alloc(&a.keys, B * a.node_cap * a.KW));
+    AZD_ST(e->alloc(&a.arcs, B * a.arc_cap));
+    AZD_ST(e->alloc(&a.preds, B * a.pred_cap));
+    AZD_ST(e->alloc(&a.pred_g, B * a.pred_cap));
+    AZD_ST(e->alloc(&a.ht, B * a.ht_cap));
+    AZD_ST(e->alloc(&a.root_parents, B * azd::PARENTS_STRIDE));
+    AZD_ST(e->alloc(&a.cur_parents, B * azd::PARENTS_STRIDE));
+    AZD_ST(e->alloc(&a.root_perm, B * a.KW));
+    AZD_ST(e->alloc(&a.cur_perm, B * a.KW));
+    AZD_ST(e->alloc(&a.cur_path, B * a.KW));
     // (an AH dense engine keeps two doubles and two ints per agent there: dense_ah_cost.inc, DenseCostAH)
-    TRY(e->alloc(&a.cur_lambda, tier->ah ? 2 * B : B));
-    TRY(e->alloc(&a.cur_mu, tier->ah ? 2 * B : B));
-    TRY(e->alloc(&a.state_pos, B));
-    TRY(e->alloc(&a.n_nodes, B));
-    TRY(e->alloc(&a.n_arcs, B));
-    TRY(e->alloc(&a.n_preds, B));
-    TRY(e->alloc(&a.flags, B));
+    AZD_ST(e->alloc(&a.cur_lambda, tier->ah ? 2 * B : B));
+    AZD_ST(e->alloc(&a.cur_mu, tier->ah ? 2 * B : B));
+    AZD_ST(e->alloc(&a.state_pos, B));
+    AZD_ST(e->alloc(&a.n_nodes, B));
+    AZD_ST(e->alloc(&a.n_arcs, B));
+    AZD_ST(e->alloc(&a.n_preds, B));
+    AZD_ST(e->alloc(&a.flags, B));
     a.fr_lds = (uint32_t)azd::FRONTIER_CAP;
     if (const char *v = getenv("AZD_DEBUG_FRONTIER_LDS")) { // test hook: a smaller LDS share, so that small trees reach the spill arena
         const int k = atoi(v);
         if (k >= 64 && k <= azd::FRONTIER_CAP && k % 64 == 0) a.fr_lds = (uint32_t)k;
     }
-    if (ramsey) TRY(e->alloc(&a.fr_spill, B * 4 * a.node_cap)); // cascade frontier levels beyond the LDS's FRONTIER_CAP entries: (node, x) x node_cap x 2 levels (RamseySpace::FRONTIER_SPILL)
-    TRY(e->alloc(&a.cand_c, B));
-    TRY(e->alloc(&a.cand_node, B));
-    TRY(e->alloc(&a.counters, B * azd::NUM_COUNTERS));
-    TRY(e->alloc(&a.state_vecs, B * a.S));
-    TRY(e->alloc(&a.h_theta, B * a.A));
+    if (ramsey) AZD_ST(e->alloc(&a.fr_spill, B * 4 * a.node_cap)); // cascade frontier levels beyond the LDS's FRONTIER_CAP entries: (node, x) x node_cap x 2 levels (RamseySpace::FRONTIER_SPILL)
+    AZD_ST(e->alloc(&a.cand_c, B));
+    AZD_ST(e->alloc(&a.cand_node, B));
+    AZD_ST(e->alloc(&a.counters, B * azd::NUM_COUNTERS));
+    AZD_ST(e->alloc(&a.state_vecs, B * a.S));
+    AZD_ST(e->alloc(&a.h_theta, B * a.A));
     a.obs = a.h_theta; // the reference reuses h_theta_host as the observation buffer (optimizer/mod.rs:270-277)
-    TRY(e->alloc(&a.weights, B * a.A));
-    TRY(e->alloc(&a.argmin, 1));
-    TRY(e->alloc(&a.status, 1));
-    if (a.layers > 1) TRY(e->alloc(&a.cur_seq, B * azd::MAX_NODE_ACTIONS));
-    TRY(e->alloc(&a.cur_stack, B * azd::PATH_STACK));
+    AZD_ST(e->alloc(&a.weights, B * a.A));
+    AZD_ST(e->alloc(&a.argmin, 1));
+    AZD_ST(e->alloc(&a.status, 1));
+    if (a.layers > 1) AZD_ST(e->alloc(&a.cur_seq, B * azd::MAX_NODE_ACTIONS));
+    AZD_ST(e->alloc(&a.cur_stack, B * azd::PATH_STACK));
     if (dense) {
-        TRY(e->alloc(&a.root_adj, B * 64));
-        TRY(e->alloc(&a.cur_adj, B * 64));
-        TRY(e->alloc(&a.root_aid, B * (size_t)e->dense_slots));
-        TRY(e->alloc(&e->d_stage_slots, B * (size_t)((a.E + 63) / 64)));
-        TRY(e->alloc(&a.argmin_d, 1));
+        AZD_ST(e->alloc(&a.root_adj, B * 64));
+        AZD_ST(e->alloc(&a.cur_adj, B * 64));
+        AZD_ST(e->alloc(&a.root_aid, B * (size_t)e->dense_slots));
+        AZD_ST(e->alloc(&e->d_stage_slots, B * (size_t)((a.E + 63) / 64)));
+        AZD_ST(e->alloc(&a.argmin_d, 1));
         static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseAhWideArgminRec) <= sizeof(azd::DenseArgminRec),
                       "an AH engine's argmin record lives in argmin_d's allocation");
-        if (!tier->ah) TRY(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH cost keeps nothing per node)
+        if (!tier->ah) AZD_ST(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH cost keeps nothing per node)
         // a bf16 evaluator takes the state vectors as bf16 rows: this space's kernels write them beside the f32 rows (write_vec16)
         if (ev && ev->input16_pitch() >= a.S) {
             a.S16 = ev->input16_pitch();
-            TRY(e->alloc(&a.state_vecs16, B * (size_t)a.S16));
-            if (hipMemset(a.state_vecs16, 0, B * (size_t)a.S16 * 2) != hipSuccess) {
-                azd_engine_destroy(e);
-                return AZD_ERR_HIP;
-            }
+            AZD_ST(e->alloc(&a.state_vecs16, B * (size_t)a.S16));
+            if (hipMemset(a.state_vecs16, 0, B * (size_t)a.S16 * 2) != hipSuccess) return AZD_ERR_HIP;
         }
     }
     if (ramsey) {
-        TRY(e->alloc(&a.root_nbr, B * tier->nbr_words));
-        TRY(e->alloc(&a.cur_nbr, B * tier->nbr_words));
-        TRY(e->alloc(&a.root_counts, B * (size_t)a.C * a.E));
-        TRY(e->alloc(&a.cur_counts, B * (size_t)a.C * a.E));
-        TRY(e->alloc(&a.root_tot, B * 4));
-        TRY(e->alloc(&a.cur_tot, B * 4));
-        TRY(e->alloc(&a.argmin_r, e->argmin_r_recs()));
+        AZD_ST(e->alloc(&a.root_nbr, B * tier->nbr_words));
+        AZD_ST(e->alloc(&a.cur_nbr, B * tier->nbr_words));
+        AZD_ST(e->alloc(&a.root_counts, B * (size_t)a.C * a.E));
+        AZD_ST(e->alloc(&a.cur_counts, B * (size_t)a.C * a.E));
+        AZD_ST(e->alloc(&a.root_tot, B * 4));
+        AZD_ST(e->alloc(&a.cur_tot, B * 4));
+        AZD_ST(e->alloc(&a.argmin_r, e->argmin_r_recs()));
         // AZD_ENGINE_EXT_POOL_STEP with a bf16 evaluator: the rows its searchers write beside the f32 rows (azd_engine::ext_s16; the
         // padding between S and the pitch is zeroed here and never written)
         if (e->ext && ev && ev->input16_pitch() >= a.S && ev->input16_pitch() % 8 == 0) {
             e->ext_s16_pitch = ev->input16_pitch();
-            TRY(e->alloc(&e->ext_s16, B * (size_t)e->ext_s16_pitch));
-            if (hipMemset(e->ext_s16, 0, B * (size_t)e->ext_s16_pitch * 2) != hipSuccess) {
-                azd_engine_destroy(e);
-                return AZD_ERR_HIP;
-            }
+            AZD_ST(e->alloc(&e->ext_s16, B * (size_t)e->ext_s16_pitch));
+            if (hipMemset(e->ext_s16, 0, B * (size_t)e->ext_s16_pitch * 2) != hipSuccess) return AZD_ERR_HIP;
         }
     }
     e->persist_enabled = (cfg->flags & AZD_ENGINE_NO_PERSISTENT_STEP) == 0;
@@ -843,63 +804,46 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         while (qcap < 2u * (uint32_t)a.B) qcap <<= 1;
         e->pool.qcap = qcap;
         e->pool_slot_words = (size_t)4 * azd::POOL_XCDS * qcap; // two ready lanes + two evaluator lanes
-        TRY(e->alloc(&e->pool.ctl, 1));
-        TRY(e->alloc(&e->pool.ready_slots, e->pool_slot_words));
+        AZD_ST(e->alloc(&e->pool.ctl, 1));
+        AZD_ST(e->alloc(&e->pool.ready_slots, e->pool_slot_words));
         e->pool.eval_slots = e->pool.ready_slots + (size_t)2 * azd::POOL_XCDS * qcap;
-        TRY(e->alloc(&e->pool.join, B));
-        TRY(e->alloc(&e->pool.pend, B));
-        TRY(e->alloc(&e->pool.stamp, B));
-        TRY(e->alloc(&e->pool.post_call, B));
-        TRY(e->alloc(&e->d_resume, B));
-        TRY(e->alloc(&e->d_call_ctr, (size_t)azd_engine::MAX_SUBS));
+        AZD_ST(e->alloc(&e->pool.join, B));
+        AZD_ST(e->alloc(&e->pool.pend, B));
+        AZD_ST(e->alloc(&e->pool.stamp, B));
+        AZD_ST(e->alloc(&e->pool.post_call, B));
+        AZD_ST(e->alloc(&e->d_resume, B));
+        AZD_ST(e->alloc(&e->d_call_ctr, (size_t)azd_engine::MAX_SUBS));
         if (e->ext) {
-            TRY(e->alloc(&e->d_ext_rows, B * azd_engine::EXT_STREAMS));
-            TRY(e->alloc(&e->d_ext_home, B * azd_engine::EXT_STREAMS));
-            TRY(e->alloc(&e->d_ext_n, (size_t)azd_engine::EXT_STREAMS));
-            TRY(e->alloc(&e->d_ext_t0, (size_t)azd_engine::EXT_STREAMS));
+            AZD_ST(e->alloc(&e->d_ext_rows, B * azd_engine::EXT_STREAMS));
+            AZD_ST(e->alloc(&e->d_ext_home, B * azd_engine::EXT_STREAMS));
+            AZD_ST(e->alloc(&e->d_ext_n, (size_t)azd_engine::EXT_STREAMS));
+            AZD_ST(e->alloc(&e->d_ext_t0, (size_t)azd_engine::EXT_STREAMS));
         }
     }
     e->log_calls = 1024;
     {
         const size_t n_wg = (B + 15) / 16;
-        TRY(e->alloc(&e->d_pargs, 1));
-        hipError_t he2 = hipHostMalloc((void **)&e->h_pargs, sizeof(azd::PersistArgs));
-        if (he2 != hipSuccess) {
-            st = azd::hip_fail(he2, "hipHostMalloc");
-            azd_engine_destroy(e);
-            return st;
-        }
-        TRY(e->alloc(&e->d_log_key, (size_t)e->log_calls * n_wg));
-        TRY(e->alloc(&e->d_log_node, (size_t)e->log_calls * n_wg));
-        TRY(e->alloc(&e->pool.win_count, (size_t)e->log_calls));
-        TRY(e->alloc(&e->d_argmin_side, 1));
-        if (ramsey) TRY(e->alloc(&e->d_argmin_r_side, e->argmin_r_recs()));
+        AZD_ST(e->alloc(&e->d_pargs, 1));
+        AZD_ST(e->h_pargs.alloc(1));
+        AZD_ST(e->alloc(&e->d_log_key, (size_t)e->log_calls * n_wg));
+        AZD_ST(e->alloc(&e->d_log_node, (size_t)e->log_calls * n_wg));
+        AZD_ST(e->alloc(&e->pool.win_count, (size_t)e->log_calls));
+        AZD_ST(e->alloc(&e->d_argmin_side, 1));
+        if (ramsey) AZD_ST(e->alloc(&e->d_argmin_r_side, e->argmin_r_recs()));
         // what the kernel hands the host in the middle of a launch: fine-grained (host-coherent) pinned memory
-        hipError_t he3 = hipHostMalloc((void **)&e->h_win_log, (size_t)e->log_calls * sizeof(unsigned long long), hipHostMallocCoherent);
-        if (he3 == hipSuccess) he3 = hipHostMalloc((void **)&e->h_win_flag, (size_t)e->log_calls * sizeof(uint32_t), hipHostMallocCoherent);
-        if (he3 != hipSuccess) {
-            st = azd::hip_fail(he3, "hipHostMalloc");
-            azd_engine_destroy(e);
-            return st;
-        }
+        AZD_ST(e->h_win_log.alloc((size_t)e->log_calls, hipHostMallocCoherent));
+        AZD_ST(e->h_win_flag.alloc((size_t)e->log_calls, hipHostMallocCoherent));
         e->pool.win_log = e->h_win_log;
         e->pool.win_flag = e->h_win_flag;
     }
-    TRY(e->alloc(&e->d_stage_parents, B * (size_t)(dense ? 8 * a.n : ramsey ? a.E : a.n)));
-    TRY(e->alloc(&e->d_stage_perm, B * (size_t)(dense ? 17 * a.KW : a.KW)));
+    AZD_ST(e->alloc(&e->d_stage_parents, B * (size_t)(dense ? 8 * a.n : ramsey ? a.E : a.n)));
+    AZD_ST(e->alloc(&e->d_stage_perm, B * (size_t)(dense ? 17 * a.KW : a.KW)));
     if (!dense) e->d_stage_slots = e->d_stage_perm; // (SpaceOps::modify_roots)
-    TRY(e->alloc(&e->d_root_report, B * 3));
+    AZD_ST(e->alloc(&e->d_root_report, B * 3));
     e->root_args.report = e->d_root_report;
-    {
-        hipError_t he = hipHostMalloc((void **)&e->h_status, sizeof(azd::StatusRec));
-        if (he == hipSuccess) he = hipHostMalloc((void **)&e->root_report, B * 3 * sizeof(uint32_t));
-        if (he == hipSuccess) he = hipHostMalloc((void **)&e->h_argmin, sizeof(azd::ArgminRec));
-        if (he != hipSuccess) {
-            st = azd::hip_fail(he, "hipHostMalloc");
-            azd_engine_destroy(e);
-            return st;
-        }
-    }
+    AZD_ST(e->h_status.alloc(1));
+    AZD_ST(e->root_report.alloc(B * 3));
+    AZD_ST(e->h_argmin.alloc(1));
     hipError_t he = hipMemsetAsync(a.counters, 0, B * azd::NUM_COUNTERS * 8, e->stream);
     if (he == hipSuccess) he = hipMemsetAsync(a.status, 0, sizeof(azd::StatusRec), e->stream);
     if (he == hipSuccess) he = hipMemsetAsync(a.argmin, 0, sizeof(azd::ArgminRec), e->stream);
@@ -911,52 +855,13 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     if (he == hipSuccess && ramsey) he = hipMemsetAsync(a.argmin_r, 0, e->argmin_r_recs() * sizeof(azd::RamseyArgminRec), e->stream);
     if (he == hipSuccess && ramsey) he = hipMemsetAsync(e->d_argmin_r_side, 0, e->argmin_r_recs() * sizeof(azd::RamseyArgminRec), e->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he != hipSuccess) {
-        st = azd::hip_fail(he, "engine init memset");
-        azd_engine_destroy(e);
-        return st;
-    }
-#undef TRY
-    *out = e;
+    if (he != hipSuccess) return azd::hip_fail(he, "engine init memset");
+    *out = e.release();
     return AZD_OK;
 }
 
 int azd_engine_destroy(azd_engine *e) {
-    if (!e) return AZD_OK;
-    (void)hipSetDevice(e->cfg.device);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (void *p : e->allocs) (void)hipFree(p);
-    if (e->h_status) (void)hipHostFree(e->h_status);
-    if (e->root_report) (void)hipHostFree(e->root_report);
-    if (e->h_argmin) (void)hipHostFree(e->h_argmin);
-    if (e->h_pargs) (void)hipHostFree(e->h_pargs);
-    if (e->h_win_log) (void)hipHostFree(e->h_win_log);
-    if (e->h_win_flag) (void)hipHostFree(e->h_win_flag);
-    if (e->d_pool) (void)hipFree(e->d_pool);
-    for (void *p : {(void *)e->d_grp_tile, (void *)e->d_grp_lds, (void *)e->d_grp_desc, (void *)e->d_grp_cnt, (void *)e->d_grp_x, (void *)e->d_grp_flag})
-        if (p) (void)hipFree(p);
-    if (e->call_graph) (void)hipGraphExecDestroy(e->call_graph);
-    for (int i = 0; i < azd_engine::MAX_SUBS; ++i) {
-        if (e->sub_graph[i]) (void)hipGraphExecDestroy(e->sub_graph[i]);
-        if (e->sub_join[i]) (void)hipEventDestroy(e->sub_join[i]);
-        if (e->sub_stream[i]) (void)hipStreamDestroy(e->sub_stream[i]);
-    }
-    if (e->sub_fork) (void)hipEventDestroy(e->sub_fork);
-    if (e->ext_done) (void)hipEventDestroy(e->ext_done);
-    if (e->ext_fork) (void)hipEventDestroy(e->ext_fork);
-    for (int x = 0; x < azd_engine::EXT_STREAMS; ++x) {
-        if (e->ext_graph[x]) (void)hipGraphExecDestroy(e->ext_graph[x]);
-        for (int i = 0; i < azd_engine::EXT_IN_FLIGHT; ++i)
-            if (e->ext_ring[x][i]) (void)hipEventDestroy(e->ext_ring[x][i]);
-        if (e->ext_stream[x]) (void)hipStreamDestroy(e->ext_stream[x]);
-    }
-    for (auto &it : e->ev_inflight) {
-        (void)hipEventDestroy(it.second.first);
-        (void)hipEventDestroy(it.second.second);
-    }
-    for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    if (e) delete e; // (~azd_engine, engine_impl.h: waits for the streams; then the members release what they own)
     return AZD_OK;
 }
 
@@ -1078,10 +983,8 @@ int azd_engine_par_update_model_sharded(azd_engine *e, uint32_t n_obs_tol, void 
     const size_t B = (size_t)a.B, rows = B * (size_t)world;
     const size_t ns = rows * a.S, na = rows * a.A;
     if (rows > e->pool_rows) {
-        if (e->d_pool) (void)hipFree(e->d_pool);
-        e->d_pool = nullptr;
         e->pool_rows = 0;
-        AZD_HIP(hipMalloc(&e->d_pool, (ns + 2 * na) * sizeof(float)));
+        AZD_ST(e->d_pool.alloc(ns + 2 * na));
         e->pool_rows = rows;
     }
     if (rows > e->pool_rows || rows > (size_t)INT32_MAX) { // (the pooled buffers hold `pool_rows` rows: sized just above)

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -19,13 +20,6 @@
 #include "engine_types.h"
 #include "evaluator.h"
 #include "space_ops.h"
-
-// a status that is not AZD_OK ends the calling function (as AZD_HIP does for a HIP call)
-#define AZD_ST(call)            \
-    do {                        \
-        const int st_ = (call); \
-        if (st_) return st_;    \
-    } while (0)
 
 // The searcher-only pool step (engine_rollout.hip: ext_pool_run) of one kind of engine: the knobs, defaults and reason strings it goes by.  The searcher
 // kernel's plan, launch and residency entries and the wavefronts it is built for are the space's (SpaceOps: PoolSearchOps); the
@@ -62,30 +56,58 @@ struct TierDesc {
     const char *e_range, *e_slots, *e_node_actions, *e_paths;
 };
 
+// The evaluator groups' device memory (PoolArgs::grp_*): the two tables of the plan, and the per-slot exchange state, regrown as a
+// whole when the plan needs more of any of it.
+struct EvalGroupMem {
+    azd::DevBuf<int16_t> tile;
+    azd::DevBuf<uint32_t> lds, desc, cnt, flag;
+    azd::DevBuf<float> x;
+    size_t slots = 0, x_floats = 0, flag_words = 0; // what desc / cnt, x and flag hold (all 0: none of them is allocated)
+    std::vector<int16_t> tile_host;                 // what `tile` holds (the plan is re-sent only when it changes)
+    std::vector<uint32_t> lds_host;
+    // after a failure the set that failed is empty and its sizes are 0: the next call allocates it again
+    int ensure(hipStream_t stream, size_t want_slots, size_t want_x_floats, size_t want_flag_words) {
+        if (!tile || !lds) {
+            tile_host.clear(), lds_host.clear();
+            AZD_ST(azd::alloc_set(tile, (size_t)8 * 128 * 4, lds, (size_t)8 * 128 * 4));
+        }
+        if (want_slots > slots || want_x_floats > x_floats || want_flag_words > flag_words) {
+            AZD_HIP(hipStreamSynchronize(stream));
+            slots = x_floats = flag_words = 0;
+            AZD_ST(azd::alloc_set(desc, want_slots * 64, cnt, want_slots * 8 * 32, x, want_x_floats, flag, want_flag_words));
+            slots = want_slots, x_floats = want_x_floats, flag_words = want_flag_words;
+        }
+        return AZD_OK;
+    }
+};
+
+// The members own what they hold and release it in reverse order of declaration, after ~azd_engine has waited for the streams.
+// So the order below matters where one resource works on another: the main stream stands before everything that is queued on it
+// or lives in the arena (it goes last), and every graph executable stands behind the stream it is replayed on (it goes first).
 struct azd_engine {
     azd_engine_config cfg;
     azd::Arenas a;
     const azd::SpaceOps *ops = nullptr; // the launchers and LDS plans of the engine's space and tier (space_ops.h)
     const TierDesc *tier = nullptr;     // which of the eight kinds of engine this is (engine_tier)
     azd_evaluator *ev = nullptr;
-    hipStream_t stream = nullptr;
-    std::vector<void *> allocs;
+    azd::Stream stream;
+    azd::DevArena allocs;
     uint8_t *d_stage_parents = nullptr;
     uint64_t *d_stage_perm = nullptr;
-    azd::StatusRec *h_status = nullptr; // pinned
-    azd::ArgminRec *h_argmin = nullptr; // pinned
+    azd::Pinned<azd::StatusRec> h_status;
+    azd::Pinned<azd::ArgminRec> h_argmin;
     unsigned long long seen_improved = 0;
     bool timing = false;
     double rollout_ms = 0, evaluator_ms = 0;
     uint64_t rollout_launches = 0;
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev_inflight; // kind 0 rollout, 1 evaluator
+    std::vector<azd::Event> ev_pool;
+    std::vector<std::pair<int, std::pair<azd::Event, azd::Event>>> ev_inflight; // kind 0 rollout, 1 evaluator
     bool initialised = false;
     // persistent (CU-resident) step
     bool persist_enabled = true;
     bool barrier_step = false;
     azd::PersistArgs *d_pargs = nullptr;
-    azd::PersistArgs *h_pargs = nullptr; // pinned
+    azd::Pinned<azd::PersistArgs> h_pargs;
     azd::PersistArgs pargs_sent{};       // what d_pargs holds: the block is re-sent only when it changed
     bool pargs_valid = false;
     bool log_clean = false;              // d_log_key is all ones (k_argmin_log1 leaves it so; the barrier step and an abort do not)
@@ -94,36 +116,29 @@ struct azd_engine {
     bool counters_by_wave = false;       // a pool launch of the product build has run since the counters were cleared: the blocks of
                                          // azd_engine_agent_counters then hold what searcher WAVES counted, not what agents did
     uint32_t *d_resume = nullptr;        // [B] take-over of an aborted pool launch by k_async (StepLaunch::resume)
-    // evaluator groups of the pool step (PoolArgs::grp_*): device tables and per-slot exchange state, (re)built when the plan changes
-    int16_t *d_grp_tile = nullptr;
-    uint32_t *d_grp_lds = nullptr, *d_grp_desc = nullptr, *d_grp_cnt = nullptr, *d_grp_flag = nullptr;
-    size_t grp_flag_words = 0;
-    float *d_grp_x = nullptr;
-    size_t grp_x_floats = 0, grp_slots_alloc = 0;
-    std::vector<int16_t> grp_tile_host;  // what d_grp_tile holds (the plan is re-sent only when it changes)
-    std::vector<uint32_t> grp_lds_host;
+    EvalGroupMem grp;                    // evaluator groups of the pool step: device tables and per-slot exchange state, (re)built when the plan changes
     unsigned long long *d_log_key = nullptr;
     uint32_t *d_log_node = nullptr;
     int log_calls = 0;
     // launch-per-phase form: the five launches of a call captured once in a hipGraph and replayed per call
-    hipGraphExec_t call_graph = nullptr;
+    azd::GraphExec call_graph;
     azd::TolTable call_graph_tol{};
     uint64_t call_graph_layout = 0;
     bool graph_enabled = true;
     // launch-per-phase form over sub-populations, each on a stream of its own with its call captured in a graph: the kernels of
     // one sub-population's call overlap the slowest agents of another's (a roll-out launch lasts as long as its slowest agent)
     static constexpr int MAX_SUBS = 8;
-    hipStream_t sub_stream[MAX_SUBS] = {};
-    hipEvent_t sub_fork = nullptr, sub_join[MAX_SUBS] = {};
-    hipGraphExec_t sub_graph[MAX_SUBS] = {};
+    azd::Stream sub_stream[MAX_SUBS];
+    azd::Event sub_fork, sub_join[MAX_SUBS];
+    azd::GraphExec sub_graph[MAX_SUBS];
     int sub_graph_n = 0;
     uint32_t *d_call_ctr = nullptr; // [MAX_SUBS] calls a sub-population has logged in the current run
     // pool step with the evaluator outside the kernel (dense-graph space): the searchers run on `stream`, the host replays a graph of
     // [collect the posted rows, the model's GEMMs over them, hand the agents back] on ext_stream until the searchers are through
     static constexpr int EXT_STREAMS = 2;    // evaluator streams: one collects and runs its first layer while the other is in its later ones
     static constexpr int EXT_IN_FLIGHT = 4;  // ring size per stream; replays queued at a time per stream: ext_depth
-    hipStream_t ext_stream[EXT_STREAMS] = {};
-    hipGraphExec_t ext_graph[EXT_STREAMS] = {};
+    azd::Stream ext_stream[EXT_STREAMS];
+    azd::GraphExec ext_graph[EXT_STREAMS];
     uint64_t ext_graph_layout = 0;
     int ext_graph_n = 0;
     bool ext_unsupported = false;     // the evaluator cannot serve gathered rows from device-side lists (asked once)
@@ -132,7 +147,7 @@ struct azd_engine {
     uint32_t *d_ext_rows = nullptr, *d_ext_home = nullptr, *d_ext_n = nullptr; // [EXT_STREAMS][B], [EXT_STREAMS][B], [EXT_STREAMS]
     unsigned long long *d_ext_t0 = nullptr; // [EXT_STREAMS] when the batch in hand was collected (PoolCtl::eval_busy)
     int ext_depth = 2;
-    hipEvent_t ext_done = nullptr, ext_fork = nullptr, ext_ring[EXT_STREAMS][EXT_IN_FLIGHT] = {};
+    azd::Event ext_done, ext_fork, ext_ring[EXT_STREAMS][EXT_IN_FLIGHT];
     unsigned long long ext_iterations = 0; // evaluator graph replays of the last dense pool launch (diagnostics)
     // which searcher-only pool step this engine has (ExtPoolForm above): the dense-graph space's, or -- under
     // AZD_ENGINE_EXT_POOL_STEP -- a Ramsey tier's; null: none.  A flagged Ramsey engine keeps the bf16 rows of the form HERE and
@@ -152,7 +167,7 @@ struct azd_engine {
     azd_root_policy root_policy{AZD_ROOT_RULE_THRESHOLD, 0, {0.0, 0.0, 0.0, 0.0}};
     azd::RootPolicyArgs root_args{};
     uint32_t *d_root_report = nullptr;
-    uint32_t *root_report = nullptr; // pinned [B][3]
+    azd::Pinned<uint32_t> root_report; // [B][3]
     bool root_report_valid = false;
     std::vector<uint64_t> dense_packed;
     std::vector<uint64_t> ramsey_perm_pad; // a wide Ramsey engine's roots: permitted masks padded to the device's a.KW words
@@ -191,41 +206,42 @@ struct azd_engine {
         azd::FusedEval fe{};
         azd::PoolArgs pool{};
     } win;
-    unsigned long long *h_win_log = nullptr; // pinned, host-coherent [log_calls]
-    uint32_t *h_win_flag = nullptr;          // pinned, host-coherent [log_calls]
+    azd::Pinned<unsigned long long> h_win_log; // host-coherent [log_calls]
+    azd::Pinned<uint32_t> h_win_flag;          // host-coherent [log_calls]
     azd::ArgminRec *d_argmin_side = nullptr; // the argmin record as of a call inside the window (k_argmin_one)
     azd::RamseyArgminRec *d_argmin_r_side = nullptr;
     // (a tier's kernels write its own record where argmin_r points, TierDesc::argmin_bytes of it: so many records of the narrow type)
     size_t argmin_r_recs() const { return (tier->argmin_bytes + sizeof(azd::RamseyArgminRec) - 1) / sizeof(azd::RamseyArgminRec); }
-    float *d_pool = nullptr;      // pooled training triple of all ranks (azd_engine_par_update_model_sharded)
+    azd::DevBuf<float> d_pool;    // pooled training triple of all ranks (azd_engine_par_update_model_sharded)
     size_t pool_rows = 0;
     int step_form = 0;            // AZD_STEP_* chosen by the last par_roll_out_episodes
     std::string step_reason;      // why the faster forms were not taken ("" if the asynchronous step ran)
 
+    ~azd_engine() { // nothing the members release may still be in use
+        (void)hipSetDevice(cfg.device);
+        for (const azd::Stream &s : sub_stream)
+            if (s) (void)hipStreamSynchronize(s);
+        for (const azd::Stream &s : ext_stream)
+            if (s) (void)hipStreamSynchronize(s);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
     template <typename T>
     int alloc(T **p, size_t count) {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, count * sizeof(T));
-        if (e != hipSuccess) return azd::hip_fail(e, "hipMalloc");
-        allocs.push_back(q);
-        *p = (T *)q;
-        return AZD_OK;
+        return allocs.alloc(p, count);
     }
-    hipEvent_t get_event() {
+    azd::Event get_event() {
+        azd::Event e;
         if (!ev_pool.empty()) {
-            hipEvent_t e = ev_pool.back();
+            e = std::move(ev_pool.back());
             ev_pool.pop_back();
-            return e;
-        }
-        hipEvent_t e;
-        (void)hipEventCreate(&e);
+        } else (void)e.create();
         return e;
     }
     void time_begin(int kind) {
         if (!timing) return;
-        hipEvent_t b = get_event(), en = get_event();
+        azd::Event b = get_event(), en = get_event();
         (void)hipEventRecord(b, stream);
-        ev_inflight.push_back({kind, {b, en}});
+        ev_inflight.emplace_back(kind, std::make_pair(std::move(b), std::move(en)));
     }
     void time_end() {
         if (!timing) return;
@@ -239,8 +255,8 @@ struct azd_engine {
                 rollout_ms += ms;
                 rollout_launches += 1;
             } else evaluator_ms += ms;
-            ev_pool.push_back(it.second.first);
-            ev_pool.push_back(it.second.second);
+            ev_pool.push_back(std::move(it.second.first));
+            ev_pool.push_back(std::move(it.second.second));
         }
         ev_inflight.clear();
     }

@@ -39,29 +39,25 @@ int azd_engine_debug_tile_forward(azd_engine *e, const float *states, float *pre
         azd::g_last_error = "debug_tile_forward: needs the c21 or the Ramsey space with an MLP evaluator the pool step can serve";
         return AZD_ERR_INVALID_ARGUMENT;
     }
-    float *d_in = nullptr, *d_out = nullptr;
-    hipError_t he = hipMalloc(&d_in, (size_t)rows * e->a.S * 4);
-    const char *what = "hipMalloc";
-    if (he == hipSuccess) he = hipMalloc(&d_out, (size_t)rows * e->a.A * 4);
-    if (he == hipSuccess) what = "hipMemcpyAsync", he = hipMemcpyAsync(d_in, states, (size_t)rows * e->a.S * 4, hipMemcpyHostToDevice, e->stream);
+    azd::DevBuf<float> d_in, d_out;
+    AZD_ST(azd::alloc_set(d_in, (size_t)rows * e->a.S, d_out, (size_t)rows * e->a.A));
+    const char *what = "hipMemcpyAsync";
+    hipError_t he = hipMemcpyAsync(d_in, states, (size_t)rows * e->a.S * 4, hipMemcpyHostToDevice, e->stream);
     if (he == hipSuccess) what = "k_tile_forward", he = azd::launch_tile_forward(fe, pool, rows, d_in, d_out, e->stream);
     if (he == hipSuccess) what = "hipMemcpyAsync", he = hipMemcpyAsync(predictions, d_out, (size_t)rows * e->a.A * 4, hipMemcpyDeviceToHost, e->stream);
     if (he == hipSuccess) what = "hipStreamSynchronize", he = hipStreamSynchronize(e->stream);
-    else (void)hipStreamSynchronize(e->stream); // nothing of this call may still be running on the buffers freed below
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
+    else (void)hipStreamSynchronize(e->stream); // nothing of this call may still be running on the buffers when they go
     return he == hipSuccess ? AZD_OK : azd::hip_fail(he, what);
 }
 int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks) {
     if (!out || n_blocks <= 0) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ST(azd::device_ok(device));
     AZD_HIP(hipSetDevice(device));
-    uint32_t *d = nullptr;
-    AZD_HIP(hipMalloc(&d, (size_t)n_blocks * 4));
+    azd::DevBuf<uint32_t> d;
+    AZD_ST(d.alloc((size_t)n_blocks));
     azd::launch_probe_xcc(d, n_blocks, nullptr);
     hipError_t he = hipDeviceSynchronize();
     if (he == hipSuccess) he = hipMemcpy(out, d, (size_t)n_blocks * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (he != hipSuccess) return azd::hip_fail(he, "probe_xcc");
     return AZD_OK;
 }
@@ -101,15 +97,12 @@ int azd_debug_probe_math(int device, const float *in, float *out, int n) {
     if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ST(azd::device_ok(device));
     AZD_HIP(hipSetDevice(device));
-    float *d_in = nullptr, *d_out = nullptr;
-    AZD_HIP(hipMalloc(&d_in, (size_t)n * 8));
-    AZD_HIP(hipMalloc(&d_out, (size_t)n * 16));
+    azd::DevBuf<float> d_in, d_out;
+    AZD_ST(azd::alloc_set(d_in, (size_t)n * 2, d_out, (size_t)n * 4));
     AZD_HIP(hipMemcpy(d_in, in, (size_t)n * 8, hipMemcpyHostToDevice));
     azd::launch_probe_math(d_in, d_out, n, nullptr);
     hipError_t he = hipDeviceSynchronize();
     if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     if (he != hipSuccess) return azd::hip_fail(he, "probe_math");
     return AZD_OK;
 }
@@ -126,15 +119,13 @@ int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, i
         for (int v = 1; v < n; ++v)
             if (p[v] >= v) return AZD_ERR_INVALID_ARGUMENT;
     }
-    uint8_t *d_p = nullptr;
-    double *d_l = nullptr;
-    int *d_m = nullptr;
-    hipEvent_t e0, e1;
-    AZD_HIP(hipMalloc(&d_p, (size_t)count * n));
-    AZD_HIP(hipMalloc(&d_l, (size_t)count * 8));
-    AZD_HIP(hipMalloc(&d_m, (size_t)count * 4));
-    AZD_HIP(hipEventCreate(&e0));
-    AZD_HIP(hipEventCreate(&e1));
+    azd::DevBuf<uint8_t> d_p;
+    azd::DevBuf<double> d_l;
+    azd::DevBuf<int> d_m;
+    azd::Event e0, e1;
+    AZD_ST(azd::alloc_set(d_p, (size_t)count * n, d_l, (size_t)count, d_m, (size_t)count));
+    AZD_ST(e0.create());
+    AZD_ST(e1.create());
     AZD_HIP(hipMemcpy(d_p, parents, (size_t)count * n, hipMemcpyHostToDevice));
     azd::launch_probe_cost(d_p, n, count, 1, full, d_l, d_m, nullptr); // warm-up
     AZD_HIP(hipEventRecord(e0, nullptr));
@@ -145,11 +136,6 @@ int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, i
     if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
     if (he == hipSuccess) he = hipMemcpy(lambda_1, d_l, (size_t)count * 8, hipMemcpyDeviceToHost);
     if (he == hipSuccess) he = hipMemcpy(matching_size, d_m, (size_t)count * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_p);
-    (void)hipFree(d_l);
-    (void)hipFree(d_m);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (he != hipSuccess) return azd::hip_fail(he, "probe_cost");
     if (ms) *ms = t;
     return AZD_OK;
@@ -198,13 +184,12 @@ static int probe_ah_cost(const char *name, bool wide, int device, const uint64_t
         }
     AZD_ST(azd::device_ok(device));
     AZD_HIP(hipSetDevice(device));
-    uint64_t *d_adj = nullptr;
-    azd::DenseAhCost *d_out = nullptr;
-    hipEvent_t e0, e1;
-    AZD_HIP(hipMalloc(&d_adj, (size_t)count * n * 8));
-    AZD_HIP(hipMalloc(&d_out, (size_t)count * sizeof(azd::DenseAhCost)));
-    AZD_HIP(hipEventCreate(&e0));
-    AZD_HIP(hipEventCreate(&e1));
+    azd::DevBuf<uint64_t> d_adj;
+    azd::DevBuf<azd::DenseAhCost> d_out;
+    azd::Event e0, e1;
+    AZD_ST(azd::alloc_set(d_adj, (size_t)count * n, d_out, (size_t)count));
+    AZD_ST(e0.create());
+    AZD_ST(e1.create());
     AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
     launch(d_adj, n, count, 1, d_out, nullptr); // warm-up
     AZD_HIP(hipEventRecord(e0, nullptr));
@@ -214,10 +199,6 @@ static int probe_ah_cost(const char *name, bool wide, int device, const uint64_t
     float t = 0.f;
     if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
     if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseAhCost), hipMemcpyDeviceToHost);
-    (void)hipFree(d_adj);
-    (void)hipFree(d_out);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (he != hipSuccess) return azd::hip_fail(he, "probe_ah_cost");
     if (ms) *ms = t;
     return AZD_OK;
@@ -232,15 +213,12 @@ int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
     if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ST(azd::device_ok(device));
     AZD_HIP(hipSetDevice(device));
-    double *d_in = nullptr, *d_out = nullptr;
-    AZD_HIP(hipMalloc(&d_in, (size_t)n * 16));
-    AZD_HIP(hipMalloc(&d_out, (size_t)n * 24));
+    azd::DevBuf<double> d_in, d_out;
+    AZD_ST(azd::alloc_set(d_in, (size_t)n * 2, d_out, (size_t)n * 3));
     AZD_HIP(hipMemcpy(d_in, in, (size_t)n * 16, hipMemcpyHostToDevice));
     azd::launch_probe_math_f64(d_in, d_out, n, nullptr);
     hipError_t he = hipDeviceSynchronize();
     if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)n * 24, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     if (he != hipSuccess) return azd::hip_fail(he, "probe_math_f64");
     return AZD_OK;
 }

@@ -150,8 +150,9 @@ static azd::StepLaunch step_launch(const azd_engine *e, int k, azd::PoolCtl *ctl
     return sl;
 }
 // What `body` launches on `stream`, captured and instantiated as *exec; body's own status comes first, the template graph always goes.
-static int capture_graph(hipStream_t stream, const std::function<int()> &body, hipGraphExec_t *exec) {
+static int capture_graph(hipStream_t stream, const std::function<int()> &body, azd::GraphExec *exec) {
     hipGraph_t g = nullptr;
+    hipGraphExec_t x = nullptr;
     AZD_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
     const int st = body();
     const hipError_t he = hipStreamEndCapture(stream, &g);
@@ -160,9 +161,10 @@ static int capture_graph(hipStream_t stream, const std::function<int()> &body, h
         return st;
     }
     if (he != hipSuccess) return azd::hip_fail(he, "hipStreamEndCapture");
-    const hipError_t hi = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
+    const hipError_t hi = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     if (hi != hipSuccess) return azd::hip_fail(hi, "hipGraphInstantiate");
+    exec->adopt(x);
     return AZD_OK;
 }
 
@@ -337,11 +339,7 @@ static int ext_graphs(azd_engine *e, const ExtPlan &xp, bool *served) {
     rounds = rounds < 1 ? 1 : rounds > 16 ? 16 : rounds;
     const uint64_t layout = e->ev->layout_version + (xp.hashed ? 1ull << 63 : 0ull) + ((uint64_t)rounds << 56);
     if (e->ext_graph_n != xp.n_ext || e->ext_graph_layout != layout) {
-        for (int x = 0; x < azd_engine::EXT_STREAMS; ++x)
-            if (e->ext_graph[x]) {
-                (void)hipGraphExecDestroy(e->ext_graph[x]);
-                e->ext_graph[x] = nullptr;
-            }
+        for (azd::GraphExec &g : e->ext_graph) g.reset();
         e->ext_graph_n = 0;
         for (int x = 0; x < xp.n_ext; ++x) {
             uint32_t *rows = e->d_ext_rows + (size_t)x * xp.a.B, *home = e->d_ext_home + (size_t)x * xp.a.B, *cnt = e->d_ext_n + x;
@@ -498,12 +496,12 @@ static int ext_pool_run(azd_engine *e, const azd::TolTable &t, int n_calls, bool
     bool go = false; // (the plan runs / the evaluator serves its rows)
     int st = ext_plan(e, n_calls, &xp, &go);
     if (st || !go) return st;
-    if (!e->ext_done) AZD_HIP(hipEventCreateWithFlags(&e->ext_done, hipEventDisableTiming));
-    if (!e->ext_fork) AZD_HIP(hipEventCreateWithFlags(&e->ext_fork, hipEventDisableTiming));
+    if (!e->ext_done) AZD_ST(e->ext_done.create(hipEventDisableTiming));
+    if (!e->ext_fork) AZD_ST(e->ext_fork.create(hipEventDisableTiming));
     for (int x = 0; x < xp.n_ext; ++x) {
-        if (!e->ext_stream[x]) AZD_HIP(hipStreamCreateWithFlags(&e->ext_stream[x], hipStreamNonBlocking));
+        if (!e->ext_stream[x]) AZD_ST(e->ext_stream[x].create(hipStreamNonBlocking));
         for (int i = 0; i < azd_engine::EXT_IN_FLIGHT; ++i)
-            if (!e->ext_ring[x][i]) AZD_HIP(hipEventCreateWithFlags(&e->ext_ring[x][i], hipEventDisableTiming));
+            if (!e->ext_ring[x][i]) AZD_ST(e->ext_ring[x][i].create(hipEventDisableTiming));
     }
     st = ext_graphs(e, xp, &go);
     if (st || !go) return st;
@@ -647,45 +645,25 @@ static int ensure_eval_groups(azd_engine *e, const azd::FusedEval &fe, bool enab
     const int n_groups = std::max(1, avail / gpl.g);
     const int NS = 16 / gpl.W;
     const size_t slots = (size_t)n_groups * NS;
-    {   // the groups' device memory and the two tables of the plan
-        if (!e->d_grp_tile) {
-            AZD_HIP(hipMalloc(&e->d_grp_tile, (size_t)8 * 128 * 4 * sizeof(int16_t)));
-            AZD_HIP(hipMalloc(&e->d_grp_lds, (size_t)8 * 128 * 4 * sizeof(uint32_t)));
-        }
-        if (slots > e->grp_slots_alloc || slots * 2 * gpl.xstride > e->grp_x_floats || slots * gpl.g * 16 > e->grp_flag_words) {
-            AZD_HIP(hipStreamSynchronize(e->stream));
-            (void)hipFree(e->d_grp_desc);
-            (void)hipFree(e->d_grp_cnt);
-            (void)hipFree(e->d_grp_x);
-            (void)hipFree(e->d_grp_flag);
-            e->d_grp_flag = nullptr;
-            e->d_grp_desc = e->d_grp_cnt = nullptr;
-            e->d_grp_x = nullptr;
-            AZD_HIP(hipMalloc(&e->d_grp_desc, slots * 64 * 4));
-            AZD_HIP(hipMalloc(&e->d_grp_cnt, slots * 8 * 32 * 4));
-            AZD_HIP(hipMalloc(&e->d_grp_x, slots * 2 * gpl.xstride * 4));
-            AZD_HIP(hipMalloc(&e->d_grp_flag, slots * gpl.g * 16 * 4));
-            e->grp_flag_words = slots * gpl.g * 16;
-            e->grp_slots_alloc = slots;
-            e->grp_x_floats = slots * 2 * gpl.xstride;
-        }
-        if (gpl.tile != e->grp_tile_host || gpl.lds != e->grp_lds_host) {
-            AZD_HIP(hipStreamSynchronize(e->stream));
-            AZD_HIP(hipMemcpy(e->d_grp_tile, gpl.tile.data(), gpl.tile.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-            AZD_HIP(hipMemcpy(e->d_grp_lds, gpl.lds.data(), gpl.lds.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            e->grp_tile_host = gpl.tile;
-            e->grp_lds_host = gpl.lds;
-        }
+    EvalGroupMem &m = e->grp;
+    // the groups' device memory and the two tables of the plan
+    AZD_ST(m.ensure(e->stream, slots, slots * 2 * gpl.xstride, slots * gpl.g * 16));
+    if (gpl.tile != m.tile_host || gpl.lds != m.lds_host) {
+        AZD_HIP(hipStreamSynchronize(e->stream));
+        AZD_HIP(hipMemcpy(m.tile, gpl.tile.data(), gpl.tile.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+        AZD_HIP(hipMemcpy(m.lds, gpl.lds.data(), gpl.lds.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        m.tile_host = gpl.tile;
+        m.lds_host = gpl.lds;
     }
     pool->grp_g = gpl.g;
     pool->grp_w = gpl.W;
     pool->grp_groups = n_groups;
-    pool->grp_tile = e->d_grp_tile;
-    pool->grp_lds = e->d_grp_lds;
-    pool->grp_desc = e->d_grp_desc;
-    pool->grp_cnt = e->d_grp_cnt;
-    pool->grp_x = e->d_grp_x;
-    pool->grp_flag = e->d_grp_flag;
+    pool->grp_tile = m.tile;
+    pool->grp_lds = m.lds;
+    pool->grp_desc = m.desc;
+    pool->grp_cnt = m.cnt;
+    pool->grp_x = m.x;
+    pool->grp_flag = m.flag;
     pool->grp_xstride = gpl.xstride;
     pool->n_eval = n_groups * gpl.g; // every evaluator workgroup is a group member
     if (gpl.lds_bytes > *dyn_bytes) *dyn_bytes = gpl.lds_bytes;
@@ -865,18 +843,14 @@ static int run_resident(azd_engine *e, const azd::TolTable &t, int n_calls, Step
 // One launch-per-phase call per sub-population, captured in a graph each and replayed on streams of their own.
 static int run_per_call_subs(azd_engine *e, const azd::TolTable &t, int n_calls, int n_subs) {
     const int per = (e->a.B + n_subs - 1) / n_subs;
-    if (!e->sub_fork) AZD_HIP(hipEventCreateWithFlags(&e->sub_fork, hipEventDisableTiming));
+    if (!e->sub_fork) AZD_ST(e->sub_fork.create(hipEventDisableTiming));
     for (int i = 0; i < n_subs; ++i) {
-        if (!e->sub_stream[i]) AZD_HIP(hipStreamCreateWithFlags(&e->sub_stream[i], hipStreamNonBlocking));
-        if (!e->sub_join[i]) AZD_HIP(hipEventCreateWithFlags(&e->sub_join[i], hipEventDisableTiming));
+        if (!e->sub_stream[i]) AZD_ST(e->sub_stream[i].create(hipStreamNonBlocking));
+        if (!e->sub_join[i]) AZD_ST(e->sub_join[i].create(hipEventDisableTiming));
     }
     int st = AZD_OK;
     if (e->sub_graph_n != n_subs || memcmp(&e->call_graph_tol, &t, sizeof(t)) != 0 || e->call_graph_layout != e->ev->layout_version) {
-        for (int i = 0; i < azd_engine::MAX_SUBS; ++i)
-            if (e->sub_graph[i]) {
-                (void)hipGraphExecDestroy(e->sub_graph[i]);
-                e->sub_graph[i] = nullptr;
-            }
+        for (azd::GraphExec &g : e->sub_graph) g.reset();
         e->sub_graph_n = 0;
         for (int i = 0; i < n_subs; ++i) {
             azd::Arenas as = e->a;
@@ -895,10 +869,7 @@ static int run_per_call_subs(azd_engine *e, const azd::TolTable &t, int n_calls,
         e->sub_graph_n = n_subs;
         e->call_graph_tol = t;
         e->call_graph_layout = e->ev->layout_version;
-        if (e->call_graph) { // (the single-stream graph was captured for another tol table or layout)
-            (void)hipGraphExecDestroy(e->call_graph);
-            e->call_graph = nullptr;
-        }
+        e->call_graph.reset(); // (the single-stream graph was captured for another tol table or layout)
     }
     int left = n_calls;
     while (left > 0) {
@@ -927,8 +898,7 @@ static int run_per_call_subs(azd_engine *e, const azd::TolTable &t, int n_calls,
 static int run_per_call_graph(azd_engine *e, const azd::TolTable &t, int n_calls) {
     if (!e->call_graph || e->sub_graph_n != 0 || memcmp(&e->call_graph_tol, &t, sizeof(t)) != 0 || e->call_graph_layout != e->ev->layout_version) {
         e->sub_graph_n = 0; // (the sub-population graphs, if any, belong to another tol table or layout from here on)
-        if (e->call_graph) (void)hipGraphExecDestroy(e->call_graph);
-        e->call_graph = nullptr;
+        e->call_graph.reset();
         const int st = capture_graph(e->stream, [&]() -> int {
             e->ops->rollout(e->a, t, e->stream);
             const uint64_t calls_before = e->ev->calls;

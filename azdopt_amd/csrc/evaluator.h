@@ -7,19 +7,7 @@
 
 #include "../../include/azdopt_amd.h"
 #include "engine_types.h"
-
-namespace azd {
-
-extern thread_local std::string g_last_error;
-int hip_fail(hipError_t e, const char *what);
-
-#define AZD_HIP(call)                                        \
-    do {                                                     \
-        hipError_t _e = (call);                              \
-        if (_e != hipSuccess) return azd::hip_fail(_e, #call); \
-    } while (0)
-
-} // namespace azd
+#include "hip_own.h"
 
 struct azd_evaluator {
     int device = 0;
@@ -28,11 +16,11 @@ struct azd_evaluator {
     uint64_t calls = 0;
     uint64_t layout_version = 0; // bumped whenever buffers are reallocated or the storage type changes: a captured graph of write_predictions_dev is stale then
     // staging for the host-pointer entry points
-    float *d_states = nullptr, *d_preds = nullptr, *d_obs = nullptr, *d_w = nullptr;
+    azd::DevBuf<float> d_states, d_preds, d_obs, d_w; // whole for staged_batch rows, or empty with staged_batch = 0
     int staged_batch = 0;
-    hipStream_t own_stream = nullptr;
+    azd::Stream own_stream;
 
-    virtual ~azd_evaluator();
+    virtual ~azd_evaluator() = default;
     // NablaModel::write_predictions on device pointers
     virtual int write_predictions_dev(int batch, const float *d_s, float *d_p, hipStream_t st) = 0;
     // NablaModel::update_model on device pointers; *loss is a host float, valid on return

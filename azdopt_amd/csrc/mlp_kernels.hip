@@ -437,91 +437,80 @@ struct MlpEvaluator : azd_evaluator {
     int t = 0;
     int64_t n_params = 0;
     std::vector<int64_t> w_off, b_off;
-    float *d_params = nullptr, *d_grads = nullptr, *d_m = nullptr, *d_v = nullptr;
-    std::vector<float *> d_act; // d_act[l], l = 1..L-1 hidden outputs (max_batch x dims[l]); [0] and [L] are caller buffers
-    float *d_pred_train = nullptr;
-    float *d_delta_a = nullptr, *d_delta_b = nullptr; // ping-pong deltas (max_batch x max_dim)
-    float *d_partial = nullptr, *d_scalars = nullptr; // [0] wsum [1] loss
-    float *h_scalars = nullptr;
+    // Three sets of buffers, each whole or empty.  Of the model (mlp_init; a failure there ends the evaluator): d_params .. d_scalars,
+    // h_scalars, d_wpk, d_split.  Of the batch (ensure_batch; whole for cap_batch rows, empty with cap_batch = 0): d_act, d_pred_train,
+    // d_delta_a / _b, d_xq, and with bf16 weights d_part and d_act16.  Of bf16 storage (set_weight_storage, at the first switch;
+    // has_bf16()): d_w16, d_params_q, d_w16p.
+    DevBuf<float> d_params, d_grads, d_m, d_v;
+    std::vector<DevBuf<float>> d_act; // d_act[l], l = 1..L-1 hidden outputs (max_batch x dims[l]); [0] and [L] are caller buffers
+    DevBuf<float> d_pred_train;
+    DevBuf<float> d_delta_a, d_delta_b; // ping-pong deltas (max_batch x max_dim)
+    DevBuf<float> d_partial, d_scalars; // [0] wsum [1] loss
+    Pinned<float> h_scalars;
     int cap_batch = 0;
     bool bf16 = false;             // AZD_STORAGE_BF16
-    uint16_t *d_w16 = nullptr;     // bf16 copy of d_params (same offsets)
+    DevBuf<uint16_t> d_w16;        // bf16 copy of d_params (same offsets)
     // the bf16 forward GEMM's operands (gemm_bf16_glds.inc): rows of pitch kp[l] = dims[l] rounded up to 64, zero beyond dims[l]
-    uint16_t *d_w16p = nullptr;    // weights, layer l at wp_off[l]: [dims[l + 1]][kp[l]]
+    DevBuf<uint16_t> d_w16p;       // weights, layer l at wp_off[l]: [dims[l + 1]][kp[l]]
     std::vector<int64_t> wp_off;
     std::vector<int> kp;
-    std::vector<uint16_t *> d_act16; // d_act16[l], l = 0 .. L-1: the input rows of layer l, [cap_batch][kp[l]] ([0]: the converted state vectors)
+    std::vector<DevBuf<uint16_t>> d_act16; // d_act16[l], l = 0 .. L-1: the input rows of layer l, [cap_batch][kp[l]] ([0]: the converted state vectors)
     int n_cus = 256;
-    float *d_params_q = nullptr;   // the bf16 values widened to f32 (GEMM path)
-    float *d_xq = nullptr;         // input rows rounded to bf16 precision (GEMM path)
-    float *d_split = nullptr;      // split-K parts of the largest weight gradient (gemm_dw)
+    DevBuf<float> d_params_q;      // the bf16 values widened to f32 (GEMM path)
+    DevBuf<float> d_xq;            // input rows rounded to bf16 precision (GEMM path)
+    DevBuf<float> d_split;         // split-K parts of the largest weight gradient (gemm_dw)
     static constexpr int MAX_SPLITS = 64;
-    float *d_wpk = nullptr;        // fragment-major weights for the asynchronous step (f32 words / bf16 halves)
-    float *d_part = nullptr;       // split-k partial sums of the bf16 forward (gemm_bf16_glds.inc)
+    DevBuf<float> d_wpk;           // fragment-major weights for the asynchronous step (f32 words / bf16 halves)
+    DevBuf<float> d_part;          // split-k partial sums of the bf16 forward (gemm_bf16_glds.inc)
     size_t part_stride = 0;        // elements per slice
     std::vector<int64_t> p_off;
     int64_t n_packed = 0;
     bool fuse_hidden2 = true; // two consecutive 512-wide hidden layers in one launch (gemm_bf16_hidden2.inc; AZD_MLP_FUSE_HIDDEN=0: layer by layer)
     int gemm_small_below = 1024; // bf16 GEMM: grids of fewer 128 x 128 tiles than this use 64 x 128 tiles (AZD_GEMM_SMALL_BELOW overrides: experiments)
 
-    ~MlpEvaluator() override {
-        (void)hipSetDevice(device);
-        if (d_w16) (void)hipFree(d_w16);
-        if (d_w16p) (void)hipFree(d_w16p);
-        for (uint16_t *p : d_act16)
-            if (p) (void)hipFree(p);
-        for (float *p : {d_params, d_grads, d_m, d_v, d_pred_train, d_delta_a, d_delta_b, d_partial, d_scalars, d_params_q, d_xq, d_wpk, d_split, d_part})
-            if (p) (void)hipFree(p);
-        for (float *p : d_act)
-            if (p) (void)hipFree(p);
-        if (h_scalars) (void)hipHostFree(h_scalars);
-    }
+    ~MlpEvaluator() override { (void)hipSetDevice(device); } // (the members release what they own)
 
+    bool has_bf16() const { return d_w16 && d_params_q && d_w16p; }
+    // A regrow that fails leaves the batch's set empty and cap_batch = 0: the next call, whatever its batch, allocates again.
     int ensure_batch(int batch) {
         if (batch <= cap_batch) return AZD_OK;
         layout_version += 1;
-        for (float *&p : d_act) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-        }
-        for (float **pp : {&d_pred_train, &d_delta_a, &d_delta_b}) {
-            if (*pp) (void)hipFree(*pp);
-            *pp = nullptr;
-        }
+        const int st = alloc_batch(batch);
+        if (st) release_batch();
+        return st;
+    }
+    void release_batch() {
+        cap_batch = 0;
+        part_stride = 0;
+        d_act.clear();
+        d_act16.clear();
+        for (DevBuf<float> *b : {&d_pred_train, &d_delta_a, &d_delta_b, &d_xq, &d_part}) b->reset();
+    }
+    int alloc_batch(int batch) {
+        release_batch();
         int maxd = 0;
         for (int d : dims) maxd = d > maxd ? d : maxd;
-        d_act.assign((size_t)L + 1, nullptr);
-        for (int l = 1; l < L; ++l) AZD_HIP(hipMalloc(&d_act[(size_t)l], (size_t)batch * dims[(size_t)l] * 4));
-        AZD_HIP(hipMalloc(&d_pred_train, (size_t)batch * dims[(size_t)L] * 4));
-        AZD_HIP(hipMalloc(&d_delta_a, (size_t)batch * maxd * 4));
-        AZD_HIP(hipMalloc(&d_delta_b, (size_t)batch * maxd * 4));
-        if (d_xq) {
-            (void)hipFree(d_xq);
-            d_xq = nullptr;
-        }
-        if (bf16 || d_w16) AZD_HIP(hipMalloc(&d_xq, (size_t)batch * dims[0] * 4));
+        d_act.resize((size_t)L + 1);
+        for (int l = 1; l < L; ++l) AZD_ST(d_act[(size_t)l].alloc((size_t)batch * dims[(size_t)l]));
+        AZD_ST(d_pred_train.alloc((size_t)batch * dims[(size_t)L]));
+        AZD_ST(d_delta_a.alloc((size_t)batch * maxd));
+        AZD_ST(d_delta_b.alloc((size_t)batch * maxd));
+        if (has_bf16()) AZD_ST(d_xq.alloc((size_t)batch * dims[0]));
         cap_batch = batch;
-        if (d_w16p) {
-            int st16 = alloc_act16();
-            if (st16) return st16;
-        }
-        return AZD_OK;
+        return has_bf16() ? alloc_act16() : AZD_OK;
     }
 
+    // the batch's buffers of the bf16 forward, for cap_batch rows (the caller releases the batch's set if this fails)
     int alloc_act16() { // zeroed once: the kernels write columns < dims[l] only, the padding stays zero
-        if (d_part) (void)hipFree(d_part);
-        d_part = nullptr;
         part_stride = 0;
+        d_act16.clear();
+        if (cap_batch == 0) return d_part.alloc(0); // (a regrow failed before: ensure_batch allocates these with the next batch)
         for (int l = 0; l + 1 < L; ++l) // split-k layers (by shape: gemm16_ksplit): f32 partial sums, 8 slices at most, in batch row order
             if (gemm16_ksplit(dims[(size_t)l + 1], kp[(size_t)l]) > 1 || getenv("AZD_GEMM16_KSPLIT")) part_stride = std::max(part_stride, (size_t)cap_batch * kp[(size_t)l + 1]);
-        if (part_stride) AZD_HIP(hipMalloc(&d_part, part_stride * 8 * sizeof(float)));
-        for (uint16_t *&p : d_act16) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-        }
-        d_act16.assign((size_t)L, nullptr);
+        AZD_ST(d_part.alloc(part_stride * 8));
+        d_act16.resize((size_t)L);
         for (int l = 0; l < L; ++l) {
-            AZD_HIP(hipMalloc(&d_act16[(size_t)l], (size_t)cap_batch * kp[(size_t)l] * 2));
+            AZD_ST(d_act16[(size_t)l].alloc((size_t)cap_batch * kp[(size_t)l]));
             AZD_HIP(hipMemset(d_act16[(size_t)l], 0, (size_t)cap_batch * kp[(size_t)l] * 2));
         }
         return AZD_OK;
@@ -688,31 +677,20 @@ struct MlpEvaluator : azd_evaluator {
         int s = ensure_batch(max_rows);
         if (s) return s;
         const size_t sb = (size_t)n_state_rows * dims[0] * 4, pb = (size_t)n_state_rows * dims[(size_t)L] * 4;
-        float *d_s = nullptr, *d_p = nullptr;
-        uint32_t *d_r = nullptr; // [max_rows] the list, then the count
-        uint16_t *d_s16 = nullptr;
-        auto release = [&]() {
-            for (void *p : {(void *)d_s, (void *)d_p, (void *)d_r, (void *)d_s16})
-                if (p) (void)hipFree(p);
-        };
+        DevBuf<float> d_s, d_p;
+        DevBuf<uint32_t> d_r; // [max_rows] the list, then the count
+        DevBuf<uint16_t> d_s16;
         const uint32_t count = (uint32_t)n_rows;
-        hipError_t he = hipMalloc(&d_s, sb);
-        if (he == hipSuccess) he = hipMalloc(&d_p, pb);
-        if (he == hipSuccess) he = hipMalloc(&d_r, ((size_t)max_rows + 1) * 4);
-        if (he == hipSuccess) he = hipMemcpy(d_s, states, sb, hipMemcpyHostToDevice);
+        AZD_ST(alloc_set(d_s, sb / 4, d_p, pb / 4, d_r, (size_t)max_rows + 1));
+        hipError_t he = hipMemcpy(d_s, states, sb, hipMemcpyHostToDevice);
         if (he == hipSuccess) he = hipMemcpy(d_p, predictions, pb, hipMemcpyHostToDevice);
         if (he == hipSuccess && n_rows > 0) he = hipMemcpy(d_r, rows, (size_t)n_rows * 4, hipMemcpyHostToDevice);
         if (he == hipSuccess) he = hipMemcpy(d_r + max_rows, &count, 4, hipMemcpyHostToDevice);
-        if (he == hipSuccess && bf16) { // the rows as the searchers would have written them: RNE, pitch kp[0], zero beyond the state
-            he = hipMalloc(&d_s16, (size_t)n_state_rows * kp[0] * 2);
-            if (he == hipSuccess) {
-                const size_t n = (size_t)n_state_rows * (kp[0] / 4);
-                k_rows_to_bf16<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(d_s, dims[0], n_state_rows, dims[0], d_s16, kp[0]);
-            }
-        }
-        if (he != hipSuccess) {
-            release();
-            return hip_fail(he, "azd_debug_write_predictions_gathered: staging");
+        if (he != hipSuccess) return hip_fail(he, "azd_debug_write_predictions_gathered: staging");
+        if (bf16) { // the rows as the searchers would have written them: RNE, pitch kp[0], zero beyond the state
+            AZD_ST(d_s16.alloc((size_t)n_state_rows * kp[0]));
+            const size_t n = (size_t)n_state_rows * (kp[0] / 4);
+            k_rows_to_bf16<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(d_s, dims[0], n_state_rows, dims[0], d_s16, kp[0]);
         }
         s = bf16 ? write_predictions_gathered(d_r, d_r + max_rows, max_rows, d_s16, kp[0], d_p, nullptr, 0)
                  : write_predictions_gathered_f32(d_r, d_r + max_rows, max_rows, d_s, dims[0], d_p, nullptr, 0);
@@ -721,7 +699,6 @@ struct MlpEvaluator : azd_evaluator {
             if (he == hipSuccess) he = hipMemcpy(predictions, d_p, pb, hipMemcpyDeviceToHost);
             if (he != hipSuccess) s = hip_fail(he, "azd_debug_write_predictions_gathered");
         }
-        release();
         return s;
     }
 
@@ -833,7 +810,7 @@ struct MlpEvaluator : azd_evaluator {
             const int K = dims[(size_t)l], N = dims[(size_t)l + 1];
             const size_t n = (size_t)((N + 15) >> 4) * ((K + 15) >> 4) * 256;
             float *d32 = bf16 ? nullptr : d_wpk + p_off[(size_t)l];
-            uint16_t *d16 = bf16 ? reinterpret_cast<uint16_t *>(d_wpk) + p_off[(size_t)l] : nullptr;
+            uint16_t *d16 = bf16 ? reinterpret_cast<uint16_t *>(d_wpk.get()) + p_off[(size_t)l] : nullptr;
             k_pack_weights<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(d_params + w_off[(size_t)l], K, N, d32, d16);
         }
     }
@@ -845,6 +822,22 @@ struct MlpEvaluator : azd_evaluator {
                                                                          d_w16p + wp_off[(size_t)l], kp[(size_t)l]);
         }
     }
+    // what bf16 storage needs beside the fp32 buffers, at the first switch to it: the weights' copies, and the batch's bf16 buffers
+    int alloc_bf16() {
+        kp.clear();
+        wp_off.clear();
+        int64_t off = 0;
+        for (int l = 0; l < L; ++l) {
+            kp.push_back((dims[(size_t)l] + 63) / 64 * 64);
+            wp_off.push_back(off);
+            off += (int64_t)dims[(size_t)l + 1] * kp[(size_t)l];
+        }
+        AZD_ST(alloc_set(d_w16, (size_t)n_params, d_params_q, (size_t)n_params, d_w16p, (size_t)off));
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess) n_cus = prop.multiProcessorCount;
+        AZD_ST(alloc_act16());
+        return d_xq.alloc((size_t)cap_batch * dims[0]);
+    }
     // AZD_STORAGE_BF16: inference reads bf16 copies of the weights (refreshed after every optimiser step),
     // the optimiser keeps f32 master weights
     int set_weight_storage(int dtype) override {
@@ -852,25 +845,14 @@ struct MlpEvaluator : azd_evaluator {
         if (dtype != AZD_STORAGE_F32 && dtype != AZD_STORAGE_BF16) return AZD_ERR_INVALID_ARGUMENT;
         layout_version += 1;
         AZD_HIP(hipDeviceSynchronize());
-        if (dtype == AZD_STORAGE_BF16 && !d_w16) {
-            AZD_HIP(hipMalloc(&d_w16, (size_t)n_params * 2));
-            AZD_HIP(hipMalloc(&d_params_q, (size_t)n_params * 4));
-            {
-                kp.clear();
-                wp_off.clear();
-                int64_t off = 0;
-                for (int l = 0; l < L; ++l) {
-                    kp.push_back((dims[(size_t)l] + 63) / 64 * 64);
-                    wp_off.push_back(off);
-                    off += (int64_t)dims[(size_t)l + 1] * kp[(size_t)l];
-                }
-                AZD_HIP(hipMalloc(&d_w16p, (size_t)off * 2));
-                hipDeviceProp_t prop;
-                if (hipGetDeviceProperties(&prop, device) == hipSuccess) n_cus = prop.multiProcessorCount;
-                int st16 = alloc_act16();
-                if (st16) return st16;
+        if (dtype == AZD_STORAGE_BF16 && !has_bf16()) {
+            const int st16 = alloc_bf16();
+            if (st16) { // neither half a bf16 set nor a batch's set without its bf16 part: the model stays in fp32 storage, the next call allocates again
+                for (DevBuf<uint16_t> *b : {&d_w16, &d_w16p}) b->reset();
+                d_params_q.reset();
+                release_batch();
+                return st16;
             }
-            AZD_HIP(hipMalloc(&d_xq, (size_t)cap_batch * dims[0] * 4));
         }
         bf16 = dtype == AZD_STORAGE_BF16;
         if (bf16) requantize(nullptr);
@@ -898,13 +880,8 @@ struct MlpEvaluator : azd_evaluator {
 
 static int mlp_init(MlpEvaluator *m, uint64_t seed) {
     AZD_HIP(hipSetDevice(m->device));
-    AZD_HIP(hipMalloc(&m->d_params, (size_t)m->n_params * 4));
-    AZD_HIP(hipMalloc(&m->d_grads, (size_t)m->n_params * 4));
-    AZD_HIP(hipMalloc(&m->d_m, (size_t)m->n_params * 4));
-    AZD_HIP(hipMalloc(&m->d_v, (size_t)m->n_params * 4));
-    AZD_HIP(hipMalloc(&m->d_partial, 256 * 4));
-    AZD_HIP(hipMalloc(&m->d_scalars, 4 * 4));
-    AZD_HIP(hipHostMalloc((void **)&m->h_scalars, 4 * 4));
+    const size_t np = (size_t)m->n_params;
+    AZD_ST(alloc_set(m->d_params, np, m->d_grads, np, m->d_m, np, m->d_v, np, m->d_partial, 256, m->d_scalars, 4, m->h_scalars, 4));
     AZD_HIP(hipMemset(m->d_grads, 0, (size_t)m->n_params * 4));
     AZD_HIP(hipMemset(m->d_m, 0, (size_t)m->n_params * 4));
     AZD_HIP(hipMemset(m->d_v, 0, (size_t)m->n_params * 4));
@@ -933,7 +910,7 @@ static int mlp_init(MlpEvaluator *m, uint64_t seed) {
     }
     // + 8 KB of zeros behind the last fragment: nothing reads them (the k loop that requested up to 7 k-steps past its tile is gone:
     // profiles/HISTORY.md); the allocation keeps its size
-    AZD_HIP(hipMalloc(&m->d_wpk, (size_t)m->n_packed * 4 + 8192));
+    AZD_ST(m->d_wpk.alloc((size_t)m->n_packed + 2048));
     AZD_HIP(hipMemset(m->d_wpk, 0, (size_t)m->n_packed * 4 + 8192));
     {
         size_t big = 0;
@@ -941,7 +918,7 @@ static int mlp_init(MlpEvaluator *m, uint64_t seed) {
             const size_t n = (size_t)m->dims[(size_t)l] * m->dims[(size_t)l + 1];
             big = n > big ? n : big;
         }
-        AZD_HIP(hipMalloc(&m->d_split, big * MlpEvaluator::MAX_SPLITS * 4));
+        AZD_ST(m->d_split.alloc(big * MlpEvaluator::MAX_SPLITS));
     }
     m->repack(nullptr);
     AZD_HIP(hipDeviceSynchronize());
@@ -995,11 +972,11 @@ extern "C" int azd_debug_gemm_bf16(int device, int M, int N, int Kp, const void 
     AZD_HIP(hipSetDevice(device));
     hipDeviceProp_t prop;
     AZD_HIP(hipGetDeviceProperties(&prop, device));
-    hipStream_t st;
-    AZD_HIP(hipStreamCreate(&st));
-    hipEvent_t e0, e1;
-    AZD_HIP(hipEventCreate(&e0));
-    AZD_HIP(hipEventCreate(&e1));
+    azd::Stream st;
+    AZD_ST(st.create());
+    azd::Event e0, e1;
+    AZD_ST(e0.create());
+    AZD_ST(e1.create());
     const int force_bn = getenv("AZD_GEMM16_BN") ? atoi(getenv("AZD_GEMM16_BN")) : 0; // (this entry only: tile experiments)
     azd::launch_gemm16(st, (const uint16_t *)d_a, Kp, (const uint16_t *)d_w, Kp, d_y, ldy, M, N, Kp, act, out_bf16, d_bias, prop.multiProcessorCount, force_bn);
     AZD_HIP(hipEventRecord(e0, st));
@@ -1011,8 +988,5 @@ extern "C" int azd_debug_gemm_bf16(int device, int M, int N, int Kp, const void 
     float t = 0.f;
     AZD_HIP(hipEventElapsedTime(&t, e0, e1));
     if (ms) *ms = t / (float)reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipStreamDestroy(st);
     return AZD_OK;
 }
