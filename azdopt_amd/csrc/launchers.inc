@@ -10,15 +10,10 @@
 // failure is sticky: the caller's hipGetLastError reports it.
 
 #if defined(AZD_TU_POOL)
-template <class SP, class = void>
-struct SpacePoolEvalGroups { static constexpr bool value = false; };
-template <class SP>
-struct SpacePoolEvalGroups<SP, decltype((void)SP::POOL_EVAL_GROUPS)> { static constexpr bool value = SP::POOL_EVAL_GROUPS; };
-
 template <class SP>
 static void l_pool(const Arenas &a, const PersistArgs *d_args, const StepLaunch &sl, const float *params,
                    const void *wpk, int n_blocks, uint32_t dyn_stride, size_t dyn_bytes, hipStream_t st) {
-    constexpr bool GROUPS = SpacePoolEvalGroups<SP>::value; // (the instantiations with evaluator groups are built for such a space only)
+    constexpr bool GROUPS = SP::POOL_EVAL_GROUPS; // (the instantiations with evaluator groups are built for such a space only)
     const int mode = (sl.hashed ? 1 : 0) | (sl.window ? 2 : 0) | ((GROUPS && sl.groups && !sl.hashed) ? 4 : 0);
 #define AZD_LAUNCH_POOL(M)                                                                                                          \
     case M:                                                                                                                         \

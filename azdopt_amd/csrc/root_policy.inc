@@ -58,16 +58,12 @@ __device__ void shuffle_permitted(uint64_t seed, uint64_t domain, uint64_t agent
 // The r-th kept node in that order is found by descending with per-subtree counts of kept nodes.
 constexpr int POLICY_SEQ_MAX_NODES = 4096;
 
-// Sizes the policy needs from a space (defaults: the two-chunk spaces): SP::UNIVERSE_MAX items the permitted set is drawn
-// from, SP::SLOT_WORDS_MAX words of that set's bit mask; SP::slot_words(a) of them are written per root to `out_slots`
-// ([B][slot_words]: the host's `permitted` argument of par_new / par_reset_trees).  `out_perm` is what k_init_roots takes
-// as its `permitted` argument: the same mask for c21 / Ramsey (out_slots == out_perm), the packed rank table for the
-// dense-graph space (SP::finish_root builds it from the new root's graph and slots).
+// What the policy needs from a space is the root-policy set of the space contract (tree_core.inc, SpaceDefaults): SP::UNIVERSE_MAX
+// items the permitted set is drawn from, SP::SLOT_WORDS_MAX words of that set's bit mask; SP::slot_words(a) of them are written per
+// root to `out_slots` ([B][slot_words]: the host's `permitted` argument of par_new / par_reset_trees).  `out_perm` is what
+// k_init_roots takes as its `permitted` argument: the same mask for c21 / Ramsey (out_slots == out_perm), the packed rank table for
+// the dense-graph space (SP::finish_root builds it from the new root's graph and slots).
 // A space whose fresh roots depend on the policy (SP::WEIGHTED_ROOTS: the Ramsey colour weights) takes it as a last argument.
-template <class SP, class = void>
-struct SpaceWeightedRoots { static constexpr bool value = false; };
-template <class SP>
-struct SpaceWeightedRoots<SP, decltype((void)SP::WEIGHTED_ROOTS)> { static constexpr bool value = SP::WEIGHTED_ROOTS; };
 
 // what the policy did with tree t (azd_engine_root_policy_report): three words, plain stores of the wave's first lane
 __device__ __forceinline__ void policy_report(const RootPolicyArgs &rp, const int t, const uint32_t branch, const uint32_t node,
@@ -86,7 +82,7 @@ __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, ui
                                                      uint64_t *__restrict__ out_perm, uint64_t *__restrict__ out_slots,
                                                      const RootPolicyArgs rp) {
     constexpr int KW = SP::KW;
-    constexpr int CH = SpaceChunks<SP>::value;
+    constexpr int CH = SP::CH;
     constexpr int HQ = KW + 1;       // histogram buckets per lane: digits 0 .. 64 KW
     constexpr int HD = 64 * HQ;
     __shared__ typename SP::Lds s;
@@ -117,7 +113,7 @@ __global__ __launch_bounds__(64) void k_modify_roots(Arenas a, uint64_t seed, ui
     const int kcur = SP::permitted_count(st);
     if (same && kcur == kmax) { // *state = a freshly generated root with k permitted
         const int k = kmin + (int)below_dev(r1, (uint32_t)(kmax - kmin + 1));
-        if constexpr (SpaceWeightedRoots<SP>::value) SP::fresh_root(a, s, seed, domain, agent, po, rp);
+        if constexpr (SP::WEIGHTED_ROOTS) SP::fresh_root(a, s, seed, domain, agent, po, rp);
         else SP::fresh_root(a, s, seed, domain, agent, po);
         shuffle_permitted(seed, domain, agent, U, k, perm_arr, draws, bm, ow, mo);
         SP::finish_root(a, s, t, po, mo, out_perm);

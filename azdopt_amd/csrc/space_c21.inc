@@ -269,9 +269,10 @@ __device__ __forceinline__ void write_state_vec(const WaveLds &s, const uint64_t
     }
 }
 
-// ---------------------------------------------------------------- the policy tree_core.inc drives
+// ---------------------------------------------------------------- the policy tree_core.inc drives (the contract: tree_core.inc, SpaceDefaults)
+// Its ActionSet key is the bit mask of the action ids themselves, and its observation map h_sa = c_as* (04-c21-tree.rs:104): the defaults.
 template <int KW_>
-struct C21Space {
+struct C21Space : SpaceDefaults {
     static constexpr int KW = KW_;
     using Lds = WaveLds;
     struct St {
@@ -285,9 +286,6 @@ struct C21Space {
     static constexpr bool POOL_EVAL_GROUPS = true; // k_pool is built with evaluator groups too (launchers.inc: l_pool)
     __device__ static __forceinline__ float *row_stage(const Arenas &, const uint32_t dyn) { return reinterpret_cast<float *>(lds_base(dyn)); }
 
-    // the ActionSet key is the bit mask of the action ids themselves
-    __device__ static __forceinline__ uint32_t key_bit(const Lds &, const uint32_t aid) { return aid; }
-    __device__ static __forceinline__ uint32_t bit_action(const Lds &, const uint32_t bit) { return bit; }
     __device__ static __forceinline__ void prepare(const Arenas &a, Lds &s) { build_action_table(s, a.A); }
     __device__ static __forceinline__ void load_cur(const Arenas &a, const int t, Lds &s, const uint32_t, St &st) {
         if (LANE < PARENTS_STRIDE) s.par[LANE] = a.cur_parents[(size_t)t * PARENTS_STRIDE + LANE];
@@ -401,8 +399,6 @@ struct C21Space {
     __device__ static __forceinline__ void write_vec(const Arenas &a, Lds &s, const uint32_t, const St &st, float *row) {
         write_state_vec<KW>(s, st.perm, a.A, row);
     }
-    // 04-c21-tree.rs:104
-    __device__ static __forceinline__ float h_sa(float, float, float c_as_star) { return c_as_star; }
 
     // graph_operations.rs:32-56 with space.rs:75-89 action_data and g = c_s - h (04-c21-tree.rs:103)
     template <bool SC1 = false>
@@ -491,8 +487,6 @@ struct C21Space {
     // ---- hooks of the device root policy (root_policy.inc)
     static constexpr int UNIVERSE_MAX = 256, SLOT_WORDS_MAX = 4;
     static constexpr bool SEQ_POLICY = true;
-    __device__ static __forceinline__ int slot_words(const Arenas &a) { return a.KW; }
-    __device__ static __forceinline__ void finish_root(const Arenas &, Lds &, const int, const uint8_t *, const uint64_t *, uint64_t *) {}
     __device__ static __forceinline__ int policy_universe(const Arenas &a) { return a.A; }
     __device__ static __forceinline__ int root_bytes(const Arenas &a) { return a.n; }
     __device__ static __forceinline__ int permitted_count(const St &st) { return mask_count<KW>(st.perm); }

@@ -391,10 +391,12 @@ struct DenseCostC21 {
     }
 };
 
+// (the contract: tree_core.inc, SpaceDefaults.  No tables to prepare, no LDS copy of the root -- it is as large as the live state --
+// and the observation map h_sa = c_as*, 04-c21-tree.rs:104: the defaults)
 template <int KW_, class Cost = DenseCostC21>
-struct DenseSpace {
+struct DenseSpace : SpaceDefaults {
     static constexpr int KW = KW_; // words of a rank set: the root's modifiable slots, at most 64 KW
-    static constexpr int CH = KW_; // chunks of 64 predictions a node may hold (tree_core.inc: SpaceChunks)
+    static constexpr int CH = KW_; // chunks of 64 predictions a node may hold
     static constexpr int MAX_SLOTS = 64 * KW_;
     using Lds = typename Cost::template Lds<KW_>;
     using St = typename Cost::template St<KW_>;
@@ -409,7 +411,6 @@ struct DenseSpace {
     __device__ static __forceinline__ void new_node_end(const Arenas &a, const int t, Lds &s, const St &, const uint32_t node) {
         Cost::new_node_end(a, t, s, node);
     }
-    __device__ static __forceinline__ void prepare(const Arenas &, Lds &) {}
     __device__ static __forceinline__ float *row_stage(const Arenas &, const uint32_t) { return nullptr; } // pool step: not built for this space
     __device__ static __forceinline__ void load_tables(const Arenas &a, const int t, Lds &s) {
 #pragma unroll
@@ -428,8 +429,6 @@ struct DenseSpace {
 #pragma unroll
         for (int w = 0; w < KW; ++w) st.rem[w] = a.root_perm[(size_t)t * KW + w];
     }
-    // (no LDS copy of the root for this space: its root state is as large as the live one)
-    __device__ static __forceinline__ void cache_root(const Arenas &, const int, Lds &) {}
     __device__ static __forceinline__ void load_root_cached(const Arenas &a, const int t, Lds &s, const uint32_t dyn, St &st) { load_root(a, t, s, dyn, st); }
     __device__ static __forceinline__ void store_cur(const Arenas &a, const int t, Lds &s, const uint32_t, const St &st) {
         a.cur_adj[(size_t)t * DENSE_MAX_N + LANE] = s.adj[LANE];
@@ -466,7 +465,7 @@ struct DenseSpace {
     }
     // the policy's cost of the state just acted into, squished (DenseCostC21: conjecture_2_1_cost, mod.rs:319-338, and the squish of
     // 04-c21-tree.rs:58-74 with N's bounds)
-    static constexpr bool EVALUATE_TAKES_HOOK = true; // tree_core.inc SpaceEvaluate: hook() = the row's drain and the request's post
+    static constexpr bool EVALUATE_TAKES_HOOK = true; // hook() = the row's drain and the request's post
     __device__ static __forceinline__ float evaluate(const Arenas &a, Lds &s, const uint32_t dyn, St &st, const int t) {
         return evaluate_hooked(a, s, dyn, st, t, DenseNoHook{});
     }
@@ -621,7 +620,6 @@ struct DenseSpace {
         }
         LDS_SYNC();
     }
-    __device__ static __forceinline__ float h_sa(float, float, float c_as_star) { return c_as_star; } // 04-c21-tree.rs:104
 
     // graph_operations.rs:32-56 with the legal actions above and g = c_s - h (04-c21-tree.rs:103)
     template <bool SC1 = false>

@@ -170,14 +170,16 @@ __device__ __forceinline__ void ramsey_adjust(LDS &s, int32_t *counts, const int
 // (below) is today's space: ME = 256, two chunks (MAX_NODE_ACTIONS).  RamseyWideSpace<KW> takes N <= 32 (ME = 496) and nodes of
 // up to 64 KW actions (select_big); the engine picks it when azd_engine_config::max_slots > 0.  The clique counts sit in the dynamic
 // LDS behind the search scratch, which is CORE_DYN_BYTES or select_big's two lists of 64 CH words, whichever is larger.
+// (The contract: tree_core.inc, SpaceDefaults.  The ActionSet key is the bit mask of the action ids themselves, and there is no LDS
+// copy of the root -- it is as large as the live state: the defaults.)
 template <int KW_, int ME, class ARG, int CH_, class W_ = uint32_t, int DEPTH = 3>
-struct RamseySpaceBase {
+struct RamseySpaceBase : SpaceDefaults {
     using W = W_;                                    // neighbourhood word
     static constexpr int NV = (int)sizeof(W_) * 8;   // vertices per row: nbr is [RAMSEY_MAX_C][NV] words
     static constexpr int NBL = RAMSEY_MAX_C * NV / 64; // words of nbr per lane: 2 or 4
     static_assert(NBL == 2 || NBL == 4, "uint32_t or uint64_t neighbourhood words");
     static constexpr int KW = KW_;
-    static constexpr int CH = CH_; // chunks of 64 predictions a node may hold (tree_core.inc: SpaceChunks)
+    static constexpr int CH = CH_; // chunks of 64 predictions a node may hold
     static constexpr int PW = (KW_ + 1) / 2; // permitted-edge words: E = A / C <= A / 2
     static constexpr bool FRONTIER_SPILL = true; // cascade levels wider than the LDS frontier go to memory (tree_core.inc: cascade)
     static constexpr size_t SCRATCH = (size_t)512 * CH_ > CORE_DYN_BYTES ? (size_t)512 * CH_ : CORE_DYN_BYTES;
@@ -200,9 +202,6 @@ struct RamseySpaceBase {
         return reinterpret_cast<float *>(lds_base(dyn) + ((SCRATCH + (size_t)a.C * a.E * sizeof(int32_t) + 15) & ~(size_t)15));
     }
 
-    // the ActionSet key is the bit mask of the action ids themselves
-    __device__ static __forceinline__ uint32_t key_bit(const Lds &, const uint32_t aid) { return aid; }
-    __device__ static __forceinline__ uint32_t bit_action(const Lds &, const uint32_t bit) { return bit; }
     __device__ static __forceinline__ void prepare(const Arenas &a, Lds &s) {
         for (int e = LANE; e < a.E; e += 64) {
             int v = 1;
@@ -257,8 +256,6 @@ struct RamseySpaceBase {
     __device__ static __forceinline__ void load_root(const Arenas &a, const int t, Lds &s, const uint32_t dyn, St &st) {
         load_from(a, t, s, dyn, st, a.root_nbr, a.root_counts, a.root_tot, a.root_perm);
     }
-    // (no LDS copy of the root for this space: its root state is as large as the live one)
-    __device__ static __forceinline__ void cache_root(const Arenas &, const int, Lds &) {}
     __device__ static __forceinline__ void load_root_cached(const Arenas &a, const int t, Lds &s, const uint32_t dyn, St &st) { load_root(a, t, s, dyn, st); }
     __device__ static __forceinline__ void store_to(const Arenas &a, const int t, Lds &s, const uint32_t dyn, const St &st,
                                                     uint32_t *nbr, int32_t *counts, int32_t *tot, uint64_t *perm) {
@@ -551,14 +548,12 @@ struct RamseySpaceBase {
     // ---- hooks of the device root policy (root_policy.inc)
     static constexpr int UNIVERSE_MAX = ME, SLOT_WORDS_MAX = KW_ > MAX_KW ? KW_ : MAX_KW;
     static constexpr bool SEQ_POLICY = ME == RAMSEY_MAX_E; // (wide engines take ActionSet keys only: the engine refuses the others)
-    __device__ static __forceinline__ int slot_words(const Arenas &a) { return a.KW; }
-    __device__ static __forceinline__ void finish_root(const Arenas &, Lds &, const int, const uint8_t *, const uint64_t *, uint64_t *) {}
     __device__ static __forceinline__ int policy_universe(const Arenas &a) { return a.E; }
     __device__ static __forceinline__ int root_bytes(const Arenas &a) { return a.E; }
     __device__ static __forceinline__ int permitted_count(const St &st) { return mask_count<PW>(st.perm); }
     // ColoredCompleteBitsetGraph::generate, seeded: colour[e] = below(draw 1024 + e, C) with uniform weights; with colour weights
     // (05-r45.rs:84-90; azd_root_policy::color_weights) the number of thresholds the draw's high word reaches (c21_host.h)
-    static constexpr bool WEIGHTED_ROOTS = true; // (root_policy.inc: fresh_root takes the policy)
+    static constexpr bool WEIGHTED_ROOTS = true; // (fresh_root takes the policy)
     __device__ static __forceinline__ void fresh_root(const Arenas &a, Lds &, uint64_t seed, uint64_t domain, uint64_t agent, uint8_t *po,
                                                       const RootPolicyArgs &rp) {
         for (int e = LANE; e < a.E; e += 64) {
@@ -618,7 +613,7 @@ template <int KW_>
 struct RamseyWideSpace : RamseySpaceBase<KW_, RAMSEY_WIDE_MAX_E, RamseyWideArgminRec, KW_> {
     using Base = RamseySpaceBase<KW_, RAMSEY_WIDE_MAX_E, RamseyWideArgminRec, KW_>;
     static constexpr bool REPLAY_BY_WORD = true; // (tree_core.inc: argmin_replay)
-    // Pool step: the state-vector row goes straight to memory (tree_core.inc: SpaceRowsDirect) instead of through an LDS stage behind
+    // Pool step: the state-vector row goes straight to memory (tree_core.inc: ROWS_DIRECT) instead of through an LDS stage behind
     // the counts -- 5.5 KB per searcher wave at r45, 9.9 KB at N = 32, C = 2: sixteen of them are what kept the searcher side of the
     // pool plan beyond 160 KB.  The entries are write_vec's, as 4-byte write-through stores (the request is posted after a drain).
     static constexpr bool ROWS_DIRECT = true;

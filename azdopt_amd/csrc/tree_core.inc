@@ -12,20 +12,10 @@
 // Built with -ffp-contract=off: every f32/f64 operation below is a single IEEE
 // operation so results are bit-identical to the CPU oracle.
 //
-// The state/action space enters through a policy class SP (space_c21.inc, space_ramsey.inc), the
-// device-side counterpart of the reference's NablaStateActionSpace trait (nabla/space/mod.rs:5-39):
-//   SP::KW, SP::Lds (static per-wave LDS block with .ctr[]), SP::St (register part of a state)
-//   prepare      once per wave: action tables
-//   load_cur / load_root / store_cur      state <-> HBM      (state.clone_from(root), mod.rs:186)
-//   act          space.act (mod.rs:150, :181)
-//   evaluate     space.evaluate(space.cost(state)) of the state just acted into (mod.rs:182-183)
-//   terminal     space.is_terminal (nabla/space/mod.rs:23-25)
-//   write_vec    space.write_vec (optimizer/mod.rs:171-173)
-//   add_actions  space.action_data + g_theta_star_sa (graph_operations.rs:32-56)
-//   init_root    roots[i] from the packed upload, cost, state vector (optimizer/mod.rs:61-70)
-//   argmin_out   ArgminData for a replayed winner (optimizer/mod.rs:226-241)
-//   h_sa         the observation map (tree/mod.rs:255)
-// Reference semantics (file:line relative to the reference root) are cited at each device function.
+// The state/action space enters through a policy class SP (space_c21.inc, space_dense.inc, space_ramsey.inc), the
+// device-side counterpart of the reference's NablaStateActionSpace trait (nabla/space/mod.rs:5-39).  What a policy
+// must define and what it may leave to a default is written down once, at SpaceDefaults below ("the space policy
+// contract").  Reference semantics (file:line relative to the reference root) are cited at each device function.
 
 #define LANE ((int)(threadIdx.x & 63))
 // Intra-wave LDS hand-off: a wave's LDS operations complete in issue order, so lanes only need
@@ -648,43 +638,100 @@ __device__ __forceinline__ uint32_t add_arc(Agent<KW> &ag, uint32_t src, uint32_
     return e;
 }
 
-// Optional: SP::write_vec16(a, s, dyn, st, row16) writes the state vector as bf16 beside the f32 row (Arenas::state_vecs16).
-template <class SP, class = void>
-struct SpaceVec16 {
-    template <class... A> __device__ static __forceinline__ void write(A &&...) {}
+// ---------------------------------------------------------------- the space policy contract
+// Everything below this point (and root_policy.inc, launchers.inc, the step includes) is templated on a space policy SP: a struct
+// of statics that derives from SpaceDefaults -- C21Space (space_c21.inc), DenseSpace (space_dense.inc), RamseySpaceBase and the tiers
+// under it (space_ramsey.inc, ramsey_ext.inc).  A policy defines the REQUIRED members and those OPTIONAL ones that differ from
+// SpaceDefaults; the core names every one of them as SP::member, with no detection.  (a: const Arenas &, s: Lds &, dyn: the wave's
+// offset into the dynamic LDS, st: St &, t: the agent.)
+//
+// REQUIRED
+//   KW                     words of an ActionSet key
+//   Lds                    the wave's static LDS block; the core names .ctr[NUM_COUNTERS], .stack[PATH_STACK], .seq[]
+//   St                     the register part of a state
+//   static size_t dyn_bytes(a)                      host: dynamic LDS of a wave (the search scratch, CORE_DYN_BYTES, and what the space keeps behind it)
+//   void  load_cur(a, t, s, dyn, st)                the agent's state from HBM
+//   void  load_root(a, t, s, dyn, st)               its root                            (state.clone_from(root), optimizer/mod.rs:186)
+//   void  load_root_cached(a, t, s, dyn, st)        the same inside a call, after cache_root: every return to the root (tree/mod.rs:172-179,
+//                                                   :220-229); a space without an LDS copy forwards to load_root
+//   void  store_cur(a, t, s, dyn, const st)         the agent's state back to HBM
+//   void  act(a, s, dyn, st, aid)                   space.act                           (tree/mod.rs:150, :181)
+//   float evaluate(a, s, dyn, st, t)                space.evaluate(space.cost(state)) of the state just acted into (tree/mod.rs:182-183)
+//   bool  terminal(a, s, dyn, const st)             space.is_terminal                   (nabla/space/mod.rs:23-25)
+//   void  write_vec(a, s, dyn, const st, float *row)  space.write_vec                   (optimizer/mod.rs:171-173)
+//   template <bool SC1> void add_actions(a, s, t, const RolloutOut *hint, RolloutOut *pick)
+//                                                   space.action_data + g_theta_star_sa (graph_operations.rs:32-56); add_actions_agent
+//                                                   above says what SC1, hint and pick are
+//   float init_root(a, t, s, dyn, const uint8_t *root_bytes, const uint64_t *permitted, st)
+//                                                   roots[t] from the packed upload into the root and current arenas; returns its cost
+//                                                   (optimizer/mod.rs:61-70)
+//   void  argmin_out(a, s, dyn, st, agent, node)    ArgminData of a replayed winner, cost at full precision (optimizer/mod.rs:226-241, log.rs:1-11)
+//   float *row_stage(a, dyn)                        pool step: where the wave builds its state-vector row in LDS (nullptr: the pool step
+//                                                   is not built for the space, or it sets ROWS_DIRECT)
+//  the device root policy (root_policy.inc: k_modify_roots)
+//   UNIVERSE_MAX, SLOT_WORDS_MAX                    items the permitted set is drawn from at most, and words of that set's bit mask
+//   SEQ_POLICY                                      the policy is built for sequence-keyed paths too
+//   int   policy_universe(a)                        items the permitted set is drawn from
+//   int   root_bytes(a)                             bytes of a packed root
+//   int   permitted_count(const st)                 k of the state
+//   void  fresh_root(a, s, seed, domain, agent, uint8_t *po)   a freshly generated root, packed (the space's generate, seeded: DESIGN.md
+//                                                   "Seeded generator")
+//   void  pack_root(a, s, uint8_t *po)              the state in `s`, packed
+//
+// OPTIONAL (SpaceDefaults holds the default; a space that sets a flag owes the members after =>)
+//   CH = PRED_CHUNKS       chunks of 64 predictions a node may hold; above PRED_CHUNKS the selection is select_big's
+//   ROWS_DIRECT = false    => write_rows_direct(a, s, dyn, const st, float *row, uint16_t *row16).  In the pool step the space writes
+//                          its state-vector row itself, straight to memory, f32 and (row16 non-null) bf16, instead of building it in
+//                          the wave's LDS (row_stage)
+//   DEFER_ACT = false      => act_set(a, s, dyn, st, const uint64_t (&todo)[KW]).  The space's actions commute, and a set of them can be
+//                          applied at once: rollout_agent then skips act() on the steps of a descent through existing nodes and builds
+//                          the state (load_root_cached + act_set) when a new node needs it
+//   TWO_PHASE_LOAD = false => Raw, load_issue(a, t, Raw &), load_finish(s, st, const Raw &) = load_cur + cache_root: the agent's state
+//                          requested with everything else at the head of a call, stored where it goes afterwards
+//   REPLAY_BY_WORD = false argmin_replay walks the key word by word in a loop (a wide key unrolled with act inlined per word is more
+//                          code than hipcc will inline: tools/check_kernels.py)
+//   FRONTIER_SPILL = false cascade levels wider than the LDS frontier go to the agent's slice of Arenas::fr_spill (cascade above: SPILL)
+//   EVALUATE_TAKES_HOOK = false  => template <class Hook> float evaluate_hooked(a, s, dyn, st, t, Hook &&).  The space calls hook() once
+//                          from inside its work: the new-node path's deferred post -- the row's drain and the request -- so that the
+//                          row's stores travel under the cost's computation
+//   WEIGHTED_ROOTS = false => fresh_root takes the policy as a last argument (const RootPolicyArgs &: the Ramsey colour weights)
+//   POOL_EVAL_GROUPS = false     launchers.inc: k_pool is built with evaluator groups too (l_pool)
+//   write_vec16(a, s, dyn, const st, uint16_t *row16)   nothing.  The state vector as bf16 beside the f32 row (Arenas::state_vecs16)
+//   new_node_begin(a, t, s, st, parent, aid), new_node_end(a, t, s, const st, node)   nothing.  Around the creation of a node: before the
+//                          action is applied, and once the node has its index (the dense-graph space keeps a maximum matching per node)
+//   cache_root(a, t, s)    nothing.  roll_out_episodes: the root fetched into LDS when the call starts, for load_root_cached
+//   finish_root(a, s, t, const uint8_t *po, const uint64_t *slots, uint64_t *out_packed)   nothing.  Root policy: what k_init_roots
+//                          takes as `permitted` where that is not the slot mask itself (the dense-graph space's packed rank table)
+//   key_bit(s, aid) = aid, bit_action(s, bit) = bit   the action's bit in the ActionSet key and back: the id itself, or its rank
+//   slot_words(a) = a.KW   root policy: words of the permitted set's mask written per root
+//   h_sa(c_s, c_as, c_as_star) = c_as_star   the observation map (tree/mod.rs:255; 04-c21-tree.rs:104)
+//   prepare(a, s)          nothing.  Once per wave: the space's tables in LDS
+struct SpaceDefaults {
+    static constexpr int CH = PRED_CHUNKS;
+    static constexpr bool ROWS_DIRECT = false, DEFER_ACT = false, TWO_PHASE_LOAD = false, REPLAY_BY_WORD = false, FRONTIER_SPILL = false,
+                          EVALUATE_TAKES_HOOK = false, WEIGHTED_ROOTS = false, POOL_EVAL_GROUPS = false;
+    template <class... A> __device__ static __forceinline__ void write_vec16(A &&...) {}
+    template <class... A> __device__ static __forceinline__ void new_node_begin(A &&...) {}
+    template <class... A> __device__ static __forceinline__ void new_node_end(A &&...) {}
+    template <class... A> __device__ static __forceinline__ void cache_root(A &&...) {}
+    template <class... A> __device__ static __forceinline__ void finish_root(A &&...) {}
+    template <class LDS> __device__ static __forceinline__ uint32_t key_bit(const LDS &, const uint32_t aid) { return aid; }
+    template <class LDS> __device__ static __forceinline__ uint32_t bit_action(const LDS &, const uint32_t bit) { return bit; }
+    __device__ static __forceinline__ int slot_words(const Arenas &a) { return a.KW; }
+    __device__ static __forceinline__ float h_sa(float, float, float c_as_star) { return c_as_star; }
+    template <class LDS> __device__ static __forceinline__ void prepare(const Arenas &, LDS &) {}
 };
-template <class SP>
-struct SpaceVec16<SP, decltype((void)&SP::write_vec16)> {
-    template <class... A> __device__ static __forceinline__ void write(A &&...x) { SP::write_vec16(x...); }
-};
-
-// Optional: SP::ROWS_DIRECT -- in the pool step the space writes its state-vector row itself, straight to memory
-// (SP::write_rows_direct), instead of building it in the wave's LDS (SP::row_stage).
-template <class SP, class = void>
-struct SpaceRowsDirect { static constexpr bool value = false; };
-template <class SP>
-struct SpaceRowsDirect<SP, decltype((void)SP::ROWS_DIRECT)> { static constexpr bool value = SP::ROWS_DIRECT; };
-// Optional: SP::DEFER_ACT + SP::act_set -- the space's actions commute, and a set of them can be applied at once (rollout_agent then
-// skips act() on the steps of a descent through existing nodes and builds the state when a new node needs it)
-template <class SP, class = void>
-struct SpaceDeferAct { static constexpr bool value = false; };
-template <class SP>
-struct SpaceDeferAct<SP, decltype((void)SP::DEFER_ACT)> { static constexpr bool value = SP::DEFER_ACT; };
-// Optional: SP::TWO_PHASE_LOAD + SP::Raw / load_issue / load_finish -- the agent's state requested with everything else at the head of a call
-template <class SP, class = void>
-struct SpaceTwoPhaseLoad { static constexpr bool value = false; };
-template <class SP>
-struct SpaceTwoPhaseLoad<SP, decltype((void)SP::TWO_PHASE_LOAD)> { static constexpr bool value = SP::TWO_PHASE_LOAD; };
-// Optional: SP::REPLAY_BY_WORD -- argmin_replay walks the key word by word in a loop (a wide key unrolled with act inlined per word is
-// more code than hipcc will inline: tools/check_kernels.py)
-template <class SP, class = void>
-struct SpaceReplayByWord { static constexpr bool value = false; };
-template <class SP>
-struct SpaceReplayByWord<SP, decltype((void)SP::REPLAY_BY_WORD)> { static constexpr bool value = SP::REPLAY_BY_WORD; };
-template <class SP, class = void>
-struct SpaceFrontierSpill { static constexpr bool value = false; };
-template <class SP>
-struct SpaceFrontierSpill<SP, decltype((void)SP::FRONTIER_SPILL)> { static constexpr bool value = SP::FRONTIER_SPILL; };
+// Three calls of rollout_agent's new-node path go through forwarding helpers in place of the plain SP::member: they keep the
+// kernels' machine code what it was under the detector structs they replace (profiles/r18_space_contract.txt).  With evaluate as a
+// plain `if constexpr` in rollout_agent the 36 C21Space kernels with a roll-out in them moved (k_rollout, k_persist, k_async, k_pool);
+// with the new-node hooks called as SP::new_node_begin / _end, the 30 kernels k_rollout and k_pool_search of the ten DenseSpace instantiations.
+template <class SP, class Hook>
+__device__ __forceinline__ float space_evaluate(const Arenas &a, typename SP::Lds &s, const uint32_t dyn, typename SP::St &st, const int t, Hook &hook) {
+    if constexpr (SP::EVALUATE_TAKES_HOOK) return SP::evaluate_hooked(a, s, dyn, st, t, hook);
+    else return SP::evaluate(a, s, dyn, st, t);
+}
+template <class SP, class... A> __device__ __forceinline__ void space_new_node_begin(A &&...x) { SP::new_node_begin(x...); }
+template <class SP, class... A> __device__ __forceinline__ void space_new_node_end(A &&...x) { SP::new_node_end(x...); }
 
 // ---------------------------------------------------------------- kernels
 #ifndef AZD_TU_ASYNC
@@ -727,7 +774,7 @@ __global__ __launch_bounds__(64) void k_init_roots(Arenas a, const uint8_t *__re
         a.cand_node[t] = 0;
     }
     SP::write_vec(a, s, dyn, st, a.state_vecs + (size_t)t * a.S);
-    if (a.state_vecs16) SpaceVec16<SP>::write(a, s, dyn, st, a.state_vecs16 + (size_t)t * a.S16);
+    if (a.state_vecs16) SP::write_vec16(a, s, dyn, st, a.state_vecs16 + (size_t)t * a.S16);
 }
 
 #endif // !AZD_TU_ASYNC
@@ -857,42 +904,6 @@ __global__ __launch_bounds__(64) void k_add_actions(Arenas a, int root_mode) {
 }
 
 #endif // !AZD_TU_ASYNC
-// Chunks of 64 predictions a node of the space may hold: 2 (PRED_CHUNKS) unless the policy says otherwise (SP::CH).
-template <class SP, class = void>
-struct SpaceChunks { static constexpr int value = PRED_CHUNKS; };
-template <class SP>
-struct SpaceChunks<SP, decltype((void)SP::CH)> { static constexpr int value = SP::CH; };
-
-// evaluate() with a hook the space calls once from inside its work (the new-node path's deferred post), where the space has one
-// (SP::EVALUATE_TAKES_HOOK, SP::evaluate_hooked)
-template <class SP, class = void>
-struct SpaceEvaluate {
-    template <class Hook>
-    __device__ static __forceinline__ float run(const Arenas &a, typename SP::Lds &s, const uint32_t dyn, typename SP::St &st, const int t, Hook &) {
-        return SP::evaluate(a, s, dyn, st, t);
-    }
-};
-template <class SP>
-struct SpaceEvaluate<SP, decltype((void)SP::EVALUATE_TAKES_HOOK)> {
-    template <class Hook>
-    __device__ static __forceinline__ float run(const Arenas &a, typename SP::Lds &s, const uint32_t dyn, typename SP::St &st, const int t, Hook &hook) {
-        return SP::evaluate_hooked(a, s, dyn, st, t, hook);
-    }
-};
-// Optional hooks of a space around the creation of a node (the dense-graph space keeps a maximum matching per node):
-// SP::new_node_begin(a, t, s, st, parent, action) before the action is applied, SP::new_node_end(a, t, s, st, node) once the
-// node has its index.  Spaces without them compile to nothing.
-template <class SP, class = void>
-struct SpaceNewNode {
-    template <class... A> __device__ static __forceinline__ void begin(A &&...) {}
-    template <class... A> __device__ static __forceinline__ void end(A &&...) {}
-};
-template <class SP>
-struct SpaceNewNode<SP, decltype((void)&SP::new_node_end)> {
-    template <class... A> __device__ static __forceinline__ void begin(A &&...x) { SP::new_node_begin(x...); }
-    template <class... A> __device__ static __forceinline__ void end(A &&...x) { SP::new_node_end(x...); }
-};
-
 // next_action (next_action.rs:11-88) on a node that may hold more than two chunks of predictions (the dense-graph space: up to
 // 64 * SP::CH modifiable edge slots): the same rule as the two-chunk code in rollout_agent, chunk by chunk.
 //   pass 1   the predictions and, behind them, the children's records: revisit_choice's first minimum of (n_t, c_t_star) over the
@@ -911,7 +922,7 @@ struct SelCtr {
 template <class SP, int KW, class LDS>
 __device__ __forceinline__ void select_big(Agent<KW> &ag, LDS &s, SelCtr &sc, const uint32_t dyn, const uint32_t act_begin, const uint32_t nact, const uint32_t tl, int &kind,
                            uint32_t &sel_pp, uint32_t &sel_aid, float &sel_g, uint32_t &sel_child, uint32_t &next_begin, uint32_t &next_cnt) {
-    constexpr int CH = SpaceChunks<SP>::value;
+    constexpr int CH = SP::CH;
     float *const kid_cs = lds_kids(dyn);                                  // [64 * CH]
     uint32_t *const kid_arc = reinterpret_cast<uint32_t *>(lds_base(dyn)) + 64 * CH; // [64 * CH]
     const uint32_t nch = (nact + 63u) >> 6;
@@ -1221,7 +1232,7 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
     const uint32_t pos_v = a.state_pos[t];
     const uint32_t stack_v = a.cur_stack[(size_t)t * PATH_STACK + (LANE & (PATH_STACK - 1))];
     typename SP::St st;
-    if constexpr (SpaceTwoPhaseLoad<SP>::value) {
+    if constexpr (SP::TWO_PHASE_LOAD) {
         typename SP::Raw raw;
         SP::load_issue(a, t, raw);
         __builtin_amdgcn_sched_barrier(0);
@@ -1257,7 +1268,7 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
     // optimizer/mod.rs:171-173 write_vec for the node the call ends on
     bool row_out = false;
     auto emit_row = [&]() __attribute__((always_inline)) {
-        if constexpr (POOL && SpaceRowsDirect<SP>::value) {
+        if constexpr (POOL && SP::ROWS_DIRECT) {
             // pool step of a space whose row does not fit the wave's LDS: written straight to memory, in whole 16-byte
             // write-through stores, as f32 and -- for a bf16 evaluator -- as bf16
             SP::write_rows_direct(a, s, dyn, st, a.state_vecs + (size_t)t * a.S, a.state_vecs16 ? a.state_vecs16 + (size_t)t * a.S16 : nullptr);
@@ -1266,7 +1277,7 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
         float *row = POOL ? SP::row_stage(a, dyn) : a.state_vecs + (size_t)t * a.S;
         if (!layered) {
             SP::write_vec(a, s, dyn, st, row);
-            if (!POOL && a.state_vecs16) SpaceVec16<SP>::write(a, s, dyn, st, a.state_vecs16 + (size_t)t * a.S16);
+            if (!POOL && a.state_vecs16) SP::write_vec16(a, s, dyn, st, a.state_vecs16 + (size_t)t * a.S16);
         } else {
             // Layered::write_vec (nabla/space/mod.rs:80-96): the ring holds the states at depths
             // d - len + 1 .. d of the path (len = min(L, d + 1)), oldest first, one chunk each; chunks past
@@ -1298,10 +1309,10 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
     // descent is ONE dependent load, the node's predictions.
     uint32_t next_begin = 0, next_cnt = 0;
     bool have_next = false;
-    // deferred act (SpaceDeferAct; not under the Layered wrapper, whose row replays the path step by step anyway): `stale` = the state in
+    // deferred act (SP::DEFER_ACT; not under the Layered wrapper, whose row replays the path step by step anyway): `stale` = the state in
     // LDS / st is not the path's (steps were taken, or the path went back to the root, without touching it); whoever needs the state
     // rebuilds it from the cached root and the path's action set
-    constexpr bool DEFER_ACT = SpaceDeferAct<SP>::value;
+    constexpr bool DEFER_ACT = SP::DEFER_ACT;
     const bool defer_act = DEFER_ACT && !layered;
     bool stale = false;
     auto state_now = [&]() __attribute__((always_inline)) {
@@ -1353,7 +1364,7 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
             sel_aid = out->first_aid;
             sel_g = out->first_g;
         } else if (r_active) {
-          if constexpr (SpaceChunks<SP>::value > PRED_CHUNKS) {
+          if constexpr (SP::CH > PRED_CHUNKS) {
             select_big<SP, KW>(ag, s, sc, dyn, r_begin, nact, tl, kind, sel_pp, sel_aid, sel_g, sel_child, next_begin, next_cnt);
             have_next = kind == 1;
           } else {
@@ -1417,7 +1428,7 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
             const NodeRec met = uni_rec(ag.nodes[hit]);
             add_arc<KW>(ag, pos, hit, sel_pp, sel_aid, sel_g, false, met, met.act_begin);
             LDS_SYNC();
-            cascade<KW, SpaceFrontierSpill<SP>::value>(a, ag, s, dyn, pos, met, true, depth, mine);
+            cascade<KW, SP::FRONTIER_SPILL>(a, ag, s, dyn, pos, met, true, depth, mine);
             CTR_ADD(20, PH_NOW() - ph_c0);
             CTR_ADD(2, 1);
             reset_to_root = true;
@@ -1433,7 +1444,7 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
             }
 
             const unsigned long long ph_n0 = PH_NOW();
-            SpaceNewNode<SP>::begin(a, t, s, st, pos, sel_aid);
+            space_new_node_begin<SP>(a, t, s, st, pos, sel_aid);
             if (defer_act && stale) state_now(); // (the path holds the new action's bit already)
             else SP::act(a, s, dyn, st, sel_aid);
             bool term = false, term_known = false, post_pending = false;
@@ -1464,8 +1475,8 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
                     post_pending = false;
                 }
             };
-            if constexpr (!SpaceRowsDirect<SP>::value) post();
-            const float c_as = SpaceEvaluate<SP>::run(a, s, dyn, st, t, post);
+            if constexpr (!SP::ROWS_DIRECT) post();
+            const float c_as = space_evaluate<SP>(a, s, dyn, st, t, post);
             post(); // (an evaluate() that does not take the hook)
             CTR_ADD(19, PH_NOW() - ph_n0);
             const uint32_t v = ag.n_nodes;
@@ -1478,7 +1489,7 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
                 if (set_keys) ag.ht[ins_slot] = ht_entry<KW>(path, v);
             }
             ag.n_nodes = v + 1;
-            SpaceNewNode<SP>::end(a, t, s, st, v);
+            space_new_node_end<SP>(a, t, s, st, v);
             if (c_as < ag.cand_c || ag.cand_node == NONE) { // first-min over nodes since last inspection
                 ag.cand_c = c_as;
                 ag.cand_node = v;
@@ -1488,7 +1499,7 @@ __device__ __forceinline__ bool rollout_agent(const Arenas &a, const TolTable &t
             LDS_SYNC();
             if (term_known ? term : SP::terminal(a, s, dyn, st)) { // is_terminal, nabla/space/mod.rs:23-25
                 const unsigned long long ph_c0 = PH_NOW();
-                cascade<KW, SpaceFrontierSpill<SP>::value>(a, ag, s, dyn, pos, fresh, false, depth, cascade_fetch<KW>(ag, s, depth));
+                cascade<KW, SP::FRONTIER_SPILL>(a, ag, s, dyn, pos, fresh, false, depth, cascade_fetch<KW>(ag, s, depth));
                 CTR_ADD(20, PH_NOW() - ph_c0);
                 CTR_ADD(1, 1);
                 reset_to_root = true;
@@ -1583,7 +1594,7 @@ __device__ void argmin_replay(const Arenas &a, typename SP::Lds &s, const uint32
     WAVE_SYNC();
     typename SP::St st;
     SP::load_root(a, wt, s, dyn, st);
-    if constexpr (SpaceReplayByWord<SP>::value) { // one copy of act in a loop over the key's words, read as they are used
+    if constexpr (SP::REPLAY_BY_WORD) { // one copy of act in a loop over the key's words, read as they are used
         WAVE_SYNC();
 #pragma unroll 1
         for (int w = 0; w < KW; ++w) {
