@@ -223,6 +223,7 @@ def lib():
     sig("azd_debug_probe_math", C.c_int, C.c_int, vp, vp, C.c_int)
     sig("azd_debug_gemm_bf16", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p)
     sig("azd_debug_probe_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, f32p)
+    sig("azd_debug_probe_dense_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp)
     sig("azd_dense_ah_cost", C.c_int, vp, C.c_int, C.POINTER(DenseAhCost))
     sig("azd_engine_dense_ah_argmin_data", C.c_int, vp, C.POINTER(DenseAhArgmin))
     sig("azd_engine_dense_ah_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseAhCost))

@@ -80,5 +80,10 @@ void launch_ext_deliver(const PoolArgs &pool, const Arenas &a, const uint32_t *r
                         const unsigned long long *t0, void *stream) {
     k_ext_deliver<<<dim3((cap + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(pool, a, rows, home, n, t0);
 }
+// ---------------------------------------------------------------- the default cost outside any engine (tests)
+void launch_probe_dense_cost(const uint64_t *d_adj, int n, int count, const uint16_t *d_toggles, int n_toggles, double *d_lam, int *d_mu,
+                             uint8_t *d_mate, int *d_hooks, void *stream) {
+    k_probe_dense_cost<2><<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, d_toggles, n_toggles, d_lam, d_mu, d_mate, d_hooks);
+}
 
 } // namespace azd

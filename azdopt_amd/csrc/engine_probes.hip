@@ -141,6 +141,64 @@ int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, i
     return AZD_OK;
 }
 
+// The dense-graph space's default cost outside any engine (space_dense.inc: k_probe_dense_cost).  Everything the kernel indexes
+// by -- the bits of adj, the slots -- is checked before the device is looked for.
+int azd_debug_probe_dense_cost(int device, const uint64_t *adj, int n, int count, const uint16_t *toggles, int n_toggles, double *lambda_1,
+                               int *matching_size, uint8_t *mate, int *hook_calls) {
+    const std::string name = "azd_debug_probe_dense_cost: ";
+    if (!adj || !lambda_1 || !matching_size || !mate || !hook_calls || count <= 0 || n_toggles < 0 || n_toggles > 64 || (n_toggles > 0 && !toggles)) {
+        azd::g_last_error = name + "adj / outputs / count / toggles / n_toggles (0 .. 64)";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (n < 4 || n > 64) {
+        azd::g_last_error = name + "n: 4 <= n <= 64";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    const int E = n * (n - 1) / 2;
+    const uint64_t beyond = n >= 64 ? 0ull : ~((1ull << n) - 1ull);
+    for (int g = 0; g < count; ++g) {
+        const uint64_t *a = adj + (size_t)g * n;
+        const char *why = nullptr;
+        for (int v = 0; v < n && !why; ++v) {
+            if ((a[v] >> v) & 1ull) why = "adj: a loop";
+            else if (a[v] & beyond) why = "adj: a neighbour at or above n";
+            else
+                for (int u = 0; u < v && !why; ++u)
+                    if (((a[v] >> u) & 1ull) != ((a[u] >> v) & 1ull)) why = "adj: not symmetric";
+        }
+        uint64_t seen[32] = {};
+        for (int j = 0; j < n_toggles && !why; ++j) {
+            const int slot = toggles[(size_t)g * n_toggles + j];
+            if (slot >= E) why = "toggles: a slot at or above E = n (n - 1) / 2";
+            else if ((seen[slot >> 6] >> (slot & 63)) & 1ull) why = "toggles: a slot twice";
+            else seen[slot >> 6] |= 1ull << (slot & 63);
+        }
+        if (why) {
+            azd::g_last_error = name + "graph " + std::to_string(g) + ": " + why;
+            return AZD_ERR_INVALID_ARGUMENT;
+        }
+    }
+    AZD_ST(azd::device_ok(device));
+    AZD_HIP(hipSetDevice(device));
+    const size_t rows = (size_t)count * (size_t)(n_toggles + 1);
+    azd::DevBuf<uint64_t> d_adj;
+    azd::DevBuf<uint16_t> d_tog;
+    azd::DevBuf<double> d_l;
+    azd::DevBuf<int> d_m, d_h;
+    azd::DevBuf<uint8_t> d_mate;
+    AZD_ST(azd::alloc_set(d_adj, (size_t)count * n, d_tog, (size_t)count * n_toggles + 1, d_l, rows, d_m, rows, d_h, rows, d_mate, rows * 64));
+    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
+    if (n_toggles > 0) AZD_HIP(hipMemcpy(d_tog, toggles, (size_t)count * n_toggles * 2, hipMemcpyHostToDevice));
+    azd::launch_probe_dense_cost(d_adj, n, count, d_tog, n_toggles, d_l, d_m, d_mate, d_h, nullptr);
+    hipError_t he = hipDeviceSynchronize();
+    if (he == hipSuccess) he = hipMemcpy(lambda_1, d_l, rows * 8, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(matching_size, d_m, rows * 4, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(hook_calls, d_h, rows * 4, hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(mate, d_mate, rows * 64, hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_dense_cost");
+    return AZD_OK;
+}
+
 // ------------------------------------------------------------------ Aouchiche-Hansen cost of the dense-graph space
 static_assert(sizeof(azd_dense_ah_cost_t) == sizeof(azd::DenseAhCost) && offsetof(azd_dense_ah_cost_t, eval) == offsetof(azd::DenseAhCost, eval),
               "azd_dense_ah_cost_t mirrors azd::DenseAhCost");

@@ -68,7 +68,9 @@ __device__ __forceinline__ bool dense_is_cut_edge(const L &s, const int v, const
 // plain steps x <- B x, then one whose Collatz-Wielandt ratios (B x)_v / x_v bracket lambda_1 + 1 and decide whether to stop
 // (bracket <= 1e-4, or the step cap), x scaled back to maximum 1 otherwise.  The value is the Rayleigh quotient of the last
 // pair, (x . y) / (x . x) - 1: its error is of the order of the bracket squared over the spectral gap, so the iteration stops
-// after half the steps the bracket itself would need to reach 1e-7.  The dot products are xor-butterflies over the wave = the
+// after half the steps the bracket itself would need to reach 1e-7.  That figure holds only where the bracket closed: a run the
+// step cap ends (near-trees at N = 64 whose two largest eigenvalues are within a few 1e-3) has no such bound -- 3.2e-5 measured
+// (DESIGN.md "The dense cost at the step cap"; tests/test_dense_cost_cases.py).  The dot products are xor-butterflies over the wave = the
 // oracle's balanced binary tree over 64 slots, operand order included (a + b == b + a bit for bit).
 constexpr int DENSE_LAMBDA_ITERS = 2000;
 constexpr double DENSE_LAMBDA_BRACKET = 1e-4;
@@ -807,3 +809,42 @@ struct DenseSpace : SpaceDefaults {
     case 4: FN<DenseSpace<4, COST>>(__VA_ARGS__); break;          \
     default: FN<DenseSpace<10, COST>>(__VA_ARGS__); break;        \
     }
+
+// The default cost outside any engine (space_ops.h: launch_probe_dense_cost; a template, so that only the unit that launches it
+// holds it): one wave per graph.  Step 0 is a root's cost -- lambda_1 and a maximum matching from nothing -- and step j = 1 ..
+// n_toggles a new node's: the edge at colex slot toggles[g][j - 1] flipped, the previous step's matching repaired, lambda_1 with
+// a hook that counts its calls (evaluate() above, without the arenas).  Outputs are [count][n_toggles + 1], mate [..][64] bytes.
+// The host has checked the graphs and the slots (engine_probes.hip): LDS is indexed by the bits of adj.
+template <int KW_>
+__global__ __launch_bounds__(64) void k_probe_dense_cost(const uint64_t *__restrict__ adj, const int n, const int count,
+                                                         const uint16_t *__restrict__ toggles, const int n_toggles, double *__restrict__ lambda_1,
+                                                         int *__restrict__ matching_size, uint8_t *__restrict__ mate, int *__restrict__ hook_calls) {
+    __shared__ DenseLds<KW_> s;
+    const int g = blockIdx.x;
+    if (g >= count) return;
+    s.adj[LANE] = LANE < n ? adj[(size_t)g * n + LANE] : 0ull;
+    LDS_SYNC();
+    const size_t row = (size_t)g * (size_t)(n_toggles + 1);
+    for (int j = 0; j <= n_toggles; ++j) {
+        int mu, calls = 0;
+        if (j == 0) mu = dense_matching_scratch(s, n);
+        else {
+            int mx, mn;
+            dense_from_colex((int)toggles[(size_t)g * n_toggles + j - 1], mx, mn);
+            if (LANE == 0) {
+                s.adj[mx] ^= 1ull << mn;
+                s.adj[mn] ^= 1ull << mx;
+            }
+            LDS_SYNC();
+            mu = dense_matching_update(s, n, mx, mn);
+        }
+        const double lam = dense_lambda1_wave(s, n, [&]() { calls += 1; });
+        mate[(row + j) * DENSE_MAX_N + LANE] = s.mate[LANE];
+        if (LANE == 0) {
+            lambda_1[row + j] = lam;
+            matching_size[row + j] = mu;
+            hook_calls[row + j] = calls;
+        }
+        LDS_SYNC();
+    }
+}

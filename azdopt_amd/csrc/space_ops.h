@@ -85,6 +85,10 @@ void launch_hash_predictions(float *d_out, int batch, int action_dim, uint64_t s
 void launch_probe_cost(const uint8_t *d_parents, int n, int count, int reps, int full, double *d_lam, int *d_mu,
                        void *stream);
 void launch_probe_math(const float *d_in, float *d_out, int n, void *stream); // sqrtf / sub parity probe (tests)
+// dense_kernels.hip: the dense-graph space's default cost (lambda_1 + matching number) of `count` graphs on n vertices, one wave
+// each: from nothing, then after each of n_toggles edge toggles with the matching repaired (outputs [count][n_toggles + 1])
+void launch_probe_dense_cost(const uint64_t *d_adj, int n, int count, const uint16_t *d_toggles, int n_toggles, double *d_lam, int *d_mu,
+                             uint8_t *d_mate, int *d_hooks, void *stream);
 // dense_ah_kernels.hip: the Aouchiche-Hansen cost of `count` graphs on n vertices, one wave each (c21_host.h: DenseAhCost), and the
 // f64 division / sqrt parity probe (tests)
 struct DenseAhCost;

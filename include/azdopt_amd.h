@@ -668,6 +668,18 @@ int azd_debug_probe_math(int device, const float *in, float *out, int n);
  * `count` trees, one wavefront each, repeated `reps` times; *ms = GPU time of the timed launch. */
 int azd_debug_probe_cost(int device, const uint8_t *parents, int n, int count, int reps, int full,
                          double *lambda_1, int *matching_size, float *ms);
+/* The dense-graph space's default cost (Conjecture2Dot1Cost over general graphs: lambda_1 + matching number) in isolation, as the
+ * search computes it: `count` graphs on n vertices (adj[count][n] neighbourhood bitsets), one wavefront each.  Step 0 is a root's
+ * cost: lambda_1 and a maximum matching from nothing.  Step j = 1 .. n_toggles is a new node's: the edge at colex slot
+ * toggles[g * n_toggles + j - 1] (slot of {v, u}, u < v: v (v - 1) / 2 + u) is added if absent and deleted if present, the
+ * previous step's matching is repaired, lambda_1 is computed with a hook that counts its calls.  Outputs are
+ * [count][n_toggles + 1]: lambda_1, matching_size, hook_calls (1 whenever the iteration keeps its contract), and mate as
+ * [count][n_toggles + 1][64] bytes (the vertex's partner; 0xFF: unmatched, and at and above n).  Checked before the device is
+ * looked for, with an azd_last_error() that names the graph: 4 <= n <= 64, count > 0, 0 <= n_toggles <= 64; every graph without
+ * loops, symmetric, no bit at or above n; every slot below E = n (n - 1) / 2 and at most once per graph.  Connectivity is the
+ * caller's business (a deletion may disconnect the graph: both procedures are defined there, the search never goes there). */
+int azd_debug_probe_dense_cost(int device, const uint64_t *adj, int n, int count, const uint16_t *toggles, int n_toggles,
+                               double *lambda_1, int *matching_size, uint8_t *mate, int *hook_calls);
 
 /* ---- Aouchiche-Hansen cost: the dense-graph space's second objective (AZD_ENGINE_DENSE_AH engines minimise it; every other dense
  * engine minimises Conjecture2Dot1Cost = lambda_1 + matching number, as before). (the objective of the reference's examples/05-ah.rs,

@@ -1114,6 +1114,11 @@ int orc_dense_matching_exact(const uint64_t *adj, int n) { return dense_matching
 int orc_dense_matching_reference(const uint64_t *adj, int n) { return dense_matching_reference(adj, n); }
 int orc_dense_is_cut_edge(const uint64_t *adj, int v, int u) { return dense_is_cut_edge(adj, v, u) ? 1 : 0; }
 double orc_dense_lambda1(const uint64_t *adj, int n) { return dense_lambda1(adj, n); }
+int orc_dense_lambda1_steps(const uint64_t *adj, int n) {
+    int steps = 0;
+    dense_lambda1(adj, n, &steps);
+    return steps;
+}
 void orc_gen_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, int count, int n, int kmin, int kmax,
                    uint8_t *parents, uint64_t *permitted) {
     int KW = key_words(n);

@@ -148,6 +148,7 @@ int orc_dense_matching_exact(const uint64_t *adj, int n); /* Edmonds: the matchi
 int orc_dense_matching_reference(const uint64_t *adj, int n); /* connected_bitset_graph/mod.rs:235-317, literally */
 int orc_dense_is_cut_edge(const uint64_t *adj, int v, int u); /* :47-71 */
 double orc_dense_lambda1(const uint64_t *adj, int n);
+int orc_dense_lambda1_steps(const uint64_t *adj, int n); /* steps the power iteration took; 2000: it ended at the cap */
 orc_mlp *orc_mlp_create(int n_layers, const int *dims, int final_act, float lr, float beta1,
                         float beta2, float eps, float l2, uint64_t seed, int threads);
 void orc_mlp_destroy(orc_mlp *m);

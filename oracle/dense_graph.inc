@@ -28,7 +28,8 @@
  *             whether to stop -- bracket <= 1e-4, or 2000 steps -- and x is scaled back to maximum 1.  The VALUE is the
  *             Rayleigh quotient of the last pair, (x . y) / (x . x) - 1, whose error is of the order of the bracket
  *             SQUARED over the spectral gap (B is symmetric): half the steps of waiting for the bracket itself to close
- *             to 1e-7.  The two dot products are balanced binary trees over the 64 vertex slots (0 beyond n) -- the order
+ *             to 1e-7 -- where the bracket closed: a run that the 2000-step cap ends has no such bound (3.2e-5 measured on a
+ *             64-vertex near-tree with a gap of 3.6e-3: DESIGN.md "The dense cost at the step cap").  The two dot products are balanced binary trees over the 64 vertex slots (0 beyond n) -- the order
  *             a wave's xor-butterfly adds in -- so oracle and GPU agree bit for bit
  *   mu        the matching number, EXACTLY (as the reference's maximum_matching().len(), mod.rs:235-317, whose search is
  *             exponential): Edmonds' blossom algorithm here; the GPU keeps a maximum matching per tree node and repairs it
@@ -278,7 +279,8 @@ inline double dense_tree_sum64(const double *v) { /* balanced binary tree over 6
         for (int i = 0; i < 64; i += 2 * w) t[i] = t[i] + t[i + w];
     return t[0];
 }
-double dense_lambda1(const uint64_t *adj, int n) {
+/* steps: where given, the number of steps x <- B x the iteration took (a multiple of 4; DENSE_LAMBDA_ITERS: the cap ended it) */
+double dense_lambda1(const uint64_t *adj, int n, int *steps = nullptr) {
     double x[DMAXN], y[DMAXN];
     for (int v = 0; v < n; ++v) x[v] = 1.0;
     auto step = [&]() { /* y = (A + I) x, neighbours in ascending order */
@@ -307,7 +309,10 @@ double dense_lambda1(const uint64_t *adj, int n) {
             if (v == 0 || r > mx) mx = r;
             if (v == 0 || y[v] > ymax) ymax = y[v];
         }
-        if (mx - mn <= DENSE_LAMBDA_BRACKET || it + 4 >= DENSE_LAMBDA_ITERS) break;
+        if (mx - mn <= DENSE_LAMBDA_BRACKET || it + 4 >= DENSE_LAMBDA_ITERS) {
+            if (steps) *steps = it + 4;
+            break;
+        }
         for (int v = 0; v < n; ++v) x[v] = y[v] / ymax;
     }
     double xy[64], xx[64];

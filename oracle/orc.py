@@ -93,6 +93,7 @@ def lib():
     sig("orc_dense_matching_reference", C.c_int, vp, C.c_int)
     sig("orc_dense_is_cut_edge", C.c_int, vp, C.c_int, C.c_int)
     sig("orc_dense_lambda1", C.c_double, vp, C.c_int)
+    sig("orc_dense_lambda1_steps", C.c_int, vp, C.c_int)
     sig("orc_mlp_create", vp, C.c_int, vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
         C.c_uint64, C.c_int)
     sig("orc_mlp_destroy", None, vp)
@@ -170,6 +171,12 @@ def dense_is_cut_edge(adj, v, u):
 def dense_lambda1(adj):
     adj = np.ascontiguousarray(adj, np.uint64)
     return lib().orc_dense_lambda1(_p(adj), len(adj))
+
+
+def dense_lambda1_steps(adj):
+    """steps x <- B x that dense_lambda1 takes on this graph (a multiple of 4); 2000 = the cap ended the iteration"""
+    adj = np.ascontiguousarray(adj, np.uint64)
+    return lib().orc_dense_lambda1_steps(_p(adj), len(adj))
 
 
 def ramsey_counts_new(n, sizes, colors):

@@ -62,6 +62,21 @@ def test_dense_pool_step_against_the_oracle(az, orc, n, B, p, kmin, kmax, tol, s
     assert c["EXPANSIONS"] > 100
 
 
+@pytest.mark.parametrize("pool", [False, True], ids=["per_call", "pool"])
+def test_dense_parity_n64_default_cost(az, orc, pool):
+    """N = 64 = DENSE_MAX_N with the default cost: every lane of the wave is a vertex (lane 63, which an unmatched vertex's
+    `mate & 63` names, is a real one; the greedy start's free mask is all ones), E = 2016"""
+    c = run_dense_parity(az, orc, 64, 8, 0.06, 5, 128, ([50, 20, 10], 5), steps=40, epochs=2, seed=13, check_every=20, policy=True, pool=pool)
+    assert c["EXPANSIONS"] > 100
+
+
+def test_dense_parity_n64_default_cost_with_1024_slots(az, orc):
+    """... and with the widest keys (16 words): 700 .. 1000 of the 2016 slots open per root"""
+    c = run_dense_parity(az, orc, 64, 8, 0.06, 700, 1000, ([50, 20, 10], 5), steps=40, epochs=2, seed=13, check_every=20, max_slots=1024, policy=True,
+                         prediction_capacity=131072)
+    assert c["EXPANSIONS"] > 100
+
+
 def test_dense_pool_step_with_more_agents_than_waves_against_the_oracle(az, orc, monkeypatch):
     """four searcher workgroups (64 waves) for 300 agents: every agent queues for a wave and changes waves and CUs many times --
     the product regime of config E (8192 agents on 2048 waves) -- against the oracle, with the device root policy and a second epoch"""
