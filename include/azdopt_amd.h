@@ -81,6 +81,8 @@ int azd_c21_generate_roots(uint64_t seed, uint64_t epoch, uint64_t first_agent, 
 /*   (R(4,6): N=35), within the reference's i32 bound (see the flag).        */
 /* ------------------------------------------------------------------------- */
 #define AZD_SPACE_RAMSEY 2
+/* (narrow tier: E <= 256 alone would allow N = 23, but E*C <= 384 with C >= 2 bounds it at N = 20 -- E = 190, E*C = 380; with
+ * three colours at N = 16, with four at N = 14.  No narrow engine of N = 21..23 is accepted; the constant stays as it is: ABI) */
 #define AZD_RAMSEY_MAX_N 23
 #define AZD_RAMSEY_WIDE_MAX_N 32
 #define AZD_RAMSEY_U64_MAX_N 64

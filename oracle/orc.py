@@ -239,6 +239,7 @@ class Engine:
         path_kind: 0 ActionSet / ActionMultiset, 1 ActionSequence / OrderedActionSet"""
         self.L = lib()
         self.n, self.B = n, batch
+        self.dense = bool(dense)
         if dense:
             self.h = self.L.orc_create_dense(n, batch, threads)
             self.L.orc_set_dense_p(self.h, int(round(dense_p * (1 << 24))))  # fresh roots of the root policy
@@ -267,9 +268,23 @@ class Engine:
         ptr = self.L.orc_state_vecs(self.h)
         return np.ctypeslib.as_array(ptr, shape=(self.B, self.S)).copy()
 
-    def new_begin(self, parents, permitted):
+    def _roots(self, parents, permitted):
+        """the root block as the library reads it: B x root_bytes bytes, B x KW words.  A dense engine's neighbourhood rows are
+        taken as bytes whether they come as gen_dense_roots' u64 [B, n] or as the engine's u8 [B, 8 n]; a block of any other size
+        is refused here (the library checks no root: cast to u8 by value, u64 rows once gave it a quarter of the bytes it read,
+        and graphs with neighbours beyond n on which its search never returned)"""
+        parents = np.ascontiguousarray(parents)
+        if self.dense and parents.dtype == np.uint64:
+            parents = parents.view(np.uint8)
         parents = np.ascontiguousarray(parents, np.uint8)
         permitted = np.ascontiguousarray(permitted, np.uint64)
+        if parents.size != self.B * self.RB or permitted.size != self.B * self.KW:
+            raise ValueError("roots: expected %d x %d bytes and %d x %d words, got %d and %d" % (self.B, self.RB, self.B, self.KW, parents.size,
+                                                                                              permitted.size))
+        return parents, permitted
+
+    def new_begin(self, parents, permitted):
+        parents, permitted = self._roots(parents, permitted)
         self.L.orc_new_begin(self.h, _p(parents), _p(permitted))
 
     def new_end(self, h):
@@ -291,8 +306,7 @@ class Engine:
         return obs, w
 
     def reset_begin(self, parents, permitted):
-        parents = np.ascontiguousarray(parents, np.uint8)
-        permitted = np.ascontiguousarray(permitted, np.uint64)
+        parents, permitted = self._roots(parents, permitted)
         self.L.orc_reset_begin(self.h, _p(parents), _p(permitted))
 
     def reset_end(self, h):

@@ -3,6 +3,9 @@
 models, call counts and pool-step knobs; every case runs the same seeded search in two forms -- pool step (in one launch, in
 random chunks, or call by call through a run-ahead window) against the asynchronous step for c21 / Ramsey, pool searchers
 against the launch-per-phase form for the dense-graph space -- and compares trees, counters, argmin, improvement counts and state vectors.
+Ramsey shapes whose STATE_DIM is no multiple of 4 (12 [3,4,3]: key width 4 at three colours; 14 [3,3,3,3]: four colours, E*C = 364;
+20 [4,4]: the narrow tier's ceiling) take neither the pool step nor a model in the kernel: there the two forms are the asynchronous
+step and the launch-per-phase form, both on the hash-stream model.
     python tools/fuzz_forms.py [cases 40] [seed 0] [dense_f32]
 dense_f32 (run(..., dense_f32=True); tests/test_gpu_fuzz_dense_f32.py runs a 12-case slice): dense-graph cases only, on all three
 tiers, with an fp32 model in the pool step (ext_pool_f32=True: the evaluator's gathered fp32 GEMMs) against the launch-per-phase
@@ -23,6 +26,7 @@ from gpu_parity import C21_CTRS, assert_tree_equal  # noqa: E402
 KNOBS = {"AZD_POOL_EARLY_POST": ["0", "1", "2"], "AZD_POOL_EXPRESS_WGS": ["0", "8", "16"], "AZD_POOL_EVAL_WGS": ["24", "64", "100"],
          "AZD_POOL_READY_LANES": ["0", "1"], "AZD_DENSE_POOL_SEARCH_WGS": ["32", "96", "128"], "AZD_DENSE_POOL_ROUNDS": ["1", "4"],
          "AZD_DENSE_POOL_STREAMS": ["1", "2"]}
+RAMSEY_SHAPES = [(16, [4, 4]), (17, [4, 4]), (16, [3, 3, 3]), (16, [3, 3, 3]), (12, [3, 4, 3]), (14, [3, 3, 3, 3]), (20, [4, 4])]
 
 
 def run(cases=40, seed=0, dense_f32=False):
@@ -58,6 +62,7 @@ def _run(cases, seed, dense_f32=False):
         seed = rng.randrange(1 << 30)
         env = {k: rng.choice(v) for k, v in KNOBS.items() if rng.random() < 0.4}
         calls = rng.choice([20, 60, 150, 400])
+        hashed = False
         if kind == "c21":
             n = rng.choice([8, 13, 19, 22])
             B = rng.choice([256, 300, 1024, 3000])
@@ -68,7 +73,9 @@ def _run(cases, seed, dense_f32=False):
             kw = {}
         elif kind == "ramsey":
             B = rng.choice([256, 512, 2048])
-            space = az.RamseySpaceNoEdgeRecolor(rng.choice([16, 17]), [4, 4], [1.0, 1.0]) if rng.random() < 0.5 else az.RamseySpaceNoEdgeRecolor(16, [3, 3, 3], [1.0, 1.0, 1.0])
+            n, sizes = rng.choice(RAMSEY_SHAPES)
+            space = az.RamseySpaceNoEdgeRecolor(n, sizes, [1.0] * len(sizes))
+            hashed = space.STATE_DIM % 4 != 0  # (rows travel as 16-byte stores: no pool step, no model in the kernel)
             hidden = rng.choice([(64, 64), (256, 256)])
             dtype = rng.choice(["f32", "bf16"])
             tol = ([200, 200, 100, 100, 50, 50, 25, 25], 10)
@@ -100,18 +107,19 @@ def _run(cases, seed, dense_f32=False):
         lo, hi = space.default_permitted_range()
         kmin = rng.randint(lo, max(lo, hi // 2))
         roots = space.generate_roots(seed, B, kmin=kmin, kmax=hi)
-        mode = rng.choice(["one", "chunks", "window"]) if kind != "dense" else rng.choice(["one", "chunks"])
-        tag = f"case {case}: {kind}{' ' + space.COST + (' wide' if space.AH_WIDE else '') + f' n={n} slots={slots}' if dense_f32 else ''} B={B} calls={calls} hidden={hidden} {dtype} mode={mode} env={env} seed={seed}"
+        mode = rng.choice(["one", "chunks", "window"]) if kind != "dense" and not hashed else rng.choice(["one", "chunks"])
+        tag = f"case {case}: {kind}{f' n={space.n} {space.sizes}' if kind == 'ramsey' else ''}{' ' + space.COST + (' wide' if space.AH_WIDE else '') + f' n={n} slots={slots}' if dense_f32 else ''} B={B} calls={calls} hidden={hidden} {dtype} mode={mode} env={env} seed={seed}"
         print(tag, flush=True)
         for k in KNOBS:
             os.environ.pop(k, None)
         os.environ.update(env)
 
         def mk(**more):
-            m = az.ActionModel(B, space.STATE_DIM, space.ACTION_DIM, hidden=hidden, seed=seed, dtype=dtype)
+            m = (az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed) if hashed else
+                 az.ActionModel(B, space.STATE_DIM, space.ACTION_DIM, hidden=hidden, seed=seed, dtype=dtype))
             return az.NablaOptimizer.par_new(space, roots, m, B, **kw, **more)
 
-        o1 = mk(pool_step=True, **(dict(ext_pool_f32=True) if dense_f32 else {}))
+        o1 = mk(pool_step=False) if hashed else mk(pool_step=True, **(dict(ext_pool_f32=True) if dense_f32 else {}))
         if mode == "one":
             i1 = o1.par_roll_out_episodes(tol, n_calls=calls)
         elif mode == "chunks":
@@ -131,7 +139,8 @@ def _run(cases, seed, dense_f32=False):
                     o1.argmin_data()
                 left -= k
         assert not dense_f32 or o1.step_form() == ("pool", ""), (tag, o1.step_form())
-        if o1.step_form()[0] != "pool":  # (a width the in-kernel evaluator does not take: nothing to compare)
+        assert not hashed or o1.step_form() == ("async", ""), (tag, o1.step_form())
+        if o1.step_form()[0] != "pool" and not hashed:  # (a width the in-kernel evaluator does not take: nothing to compare)
             print("   skipped:", o1.step_form())
             for k in KNOBS:  # (the case's knobs must not outlive it: they once leaked into the rest of the test session)
                 os.environ.pop(k, None)
@@ -143,6 +152,10 @@ def _run(cases, seed, dense_f32=False):
             o2 = mk()
             i2 = o2.par_roll_out_episodes(tol, n_calls=calls)
             os.environ.pop("AZD_DENSE_NO_POOL")
+            assert o2.step_form()[0].startswith("per_call"), o2.step_form()
+        elif hashed:
+            o2 = mk(persistent=False)
+            i2 = o2.par_roll_out_episodes(tol, n_calls=calls)
             assert o2.step_form()[0].startswith("per_call"), o2.step_form()
         else:
             o2 = mk(pool_step=False)
