@@ -243,13 +243,11 @@ static int ah_sturm(const double *diag, const double *sub2, int n, double x) {
     }
     return c;
 }
-void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
+// The three stages of the procedure, shared by the Aouchiche-Hansen cost and the weighted-invariant cost below.
+// BFS from every vertex: row u of A (pitch DENSE_AH_STRIDE) receives d(u, .), trans[u] the transmission, ecc[u] the eccentricity
+static void ah_bfs(const uint64_t *adj, int n, double *A, int *trans, int *ecc) {
     constexpr int P = DENSE_AH_STRIDE;
-    constexpr int MAX_N = DENSE_AH_WIDE_MAX_N; // (the values do not depend on the pitch or on the rows beyond n)
-    std::vector<double> Am((size_t)MAX_N * P, 0.0);
-    double *A = Am.data();
-    int min_t = 0x7FFFFFFF, diam = 0;
-    for (int u = 0; u < n; ++u) { // BFS from u
+    for (int u = 0; u < n; ++u) {
         uint64_t seen = 1ull << u, frontier = seen;
         int d = 0, t = 0;
         for (;;) {
@@ -258,18 +256,21 @@ void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
             next &= ~seen;
             if (!next) break;
             ++d;
-            for (uint64_t m = next; m; m &= m - 1ull) A[u * P + __builtin_ctzll(m)] = (double)d;
+            if (A)
+                for (uint64_t m = next; m; m &= m - 1ull) A[u * P + __builtin_ctzll(m)] = (double)d;
             t += d * __builtin_popcountll(next);
             seen |= next;
             frontier = next;
         }
-        if (t < min_t) min_t = t;
-        if (d > diam) diam = d;
+        trans[u] = t;
+        ecc[u] = d;
     }
-    const double prox = (double)min_t / (double)(n - 1);
-    const int q23 = (2 * diam) / 3, k = q23 >= 1 ? q23 - 1 : n - 1;
-    // Householder reduction: step i clears column i below row i + 1
-    double diag[MAX_N], sub[MAX_N], v[64], p[64], q[64], tmp[64];
+}
+// Householder reduction of the symmetric matrix A (pitch DENSE_AH_STRIDE, reduced in place): step i clears column i below row i + 1
+static void ah_householder(double *A, int n, double *diag, double *sub) {
+    constexpr int P = DENSE_AH_STRIDE;
+    constexpr int MAX_N = DENSE_AH_WIDE_MAX_N;
+    double v[64], p[64], q[64], tmp[64];
     for (int i = 0; i < MAX_N; ++i) diag[i] = sub[i] = 0.0;
     for (int i = 0; i + 2 < n; ++i) {
         for (int lane = 0; lane < 64; ++lane) {
@@ -305,7 +306,10 @@ void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
     diag[n - 2] = A[(n - 2) * P + (n - 2)];
     sub[n - 2] = A[(n - 1) * P + (n - 2)];
     diag[n - 1] = A[(n - 1) * P + (n - 1)];
-    // multisection for ascending index j = n - 1 - k
+}
+// multisection for entry k of the tridiagonal matrix's eigenvalues sorted descending = ascending index j = n - 1 - k
+static double ah_multisection(const double *diag, const double *sub, int n, int k) {
+    constexpr int MAX_N = DENSE_AH_WIDE_MAX_N;
     const int j = n - 1 - k;
     double sub2[MAX_N], R = 0.0;
     for (int i = 0; i < n; ++i) {
@@ -326,13 +330,109 @@ void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
         lo = nlo;
         hi = nhi;
     }
-    const double eig = (lo + hi) * 0.5;
+    return (lo + hi) * 0.5;
+}
+void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
+    constexpr int P = DENSE_AH_STRIDE;
+    constexpr int MAX_N = DENSE_AH_WIDE_MAX_N; // (the values do not depend on the pitch or on the rows beyond n)
+    std::vector<double> Am((size_t)MAX_N * P, 0.0);
+    int trans[MAX_N], ecc[MAX_N];
+    ah_bfs(adj, n, Am.data(), trans, ecc);
+    int min_t = 0x7FFFFFFF, diam = 0;
+    for (int u = 0; u < n; ++u) {
+        if (trans[u] < min_t) min_t = trans[u];
+        if (ecc[u] > diam) diam = ecc[u];
+    }
+    const double prox = (double)min_t / (double)(n - 1);
+    const int q23 = (2 * diam) / 3, k = q23 >= 1 ? q23 - 1 : n - 1;
+    double diag[MAX_N], sub[MAX_N];
+    ah_householder(Am.data(), n, diag, sub);
+    const double eig = ah_multisection(diag, sub, n, k);
     out->proximity = prox;
     out->eigenvalue = eig;
     out->diameter = diam;
     out->k = k;
     out->cost = (float)(prox + eig);
     out->eval = dense_ah_eval_slope(n) * (out->cost + 2.0f);
+}
+
+// ---- weighted-invariant cost (c21_host.h: DenseInvRecipe; the dense space's third objective): the host form of
+// dense_inv_cost_wave (dense_inv_cost.inc), the same IEEE operations in the same order, over the three stages above.
+const char *dense_inv_check_graph(const uint64_t *adj, int n) {
+    return ah_check_graph(adj, n, DENSE_INV_MAX_N, "n: the weighted-invariant cost needs 4 <= n <= 32 (AZD_DENSE_INV_MAX_N)");
+}
+const char *dense_inv_check_recipe(const DenseInvRecipe *r, int n) {
+    if (!r) return "recipe: null";
+    bool any = false;
+    for (int i = 0; i < DENSE_INV_COUNT; ++i) {
+        if (!std::isfinite(r->weight[i])) return "weight: every weight must be finite";
+        any = any || r->weight[i] != 0.0;
+    }
+    if (!any) return "weight: all ten weights are zero";
+    if (!std::isfinite(r->bias)) return "bias: must be finite";
+    if (!std::isfinite(r->eval_offset)) return "eval_offset: must be finite";
+    if (!std::isfinite(r->eval_scale) || r->eval_scale == 0.0f) return "eval_scale: must be finite and not zero";
+    if (r->adj_index < 0 || r->adj_index > n - 1) return "adj_index: must be in 0 .. n - 1 (descending index into the adjacency spectrum)";
+    if (r->dist_index != DENSE_INV_INDEX_AH && (r->dist_index < 0 || r->dist_index > n - 1))
+        return "dist_index: must be in 0 .. n - 1 (descending index into the distance spectrum) or AZD_DENSE_INV_INDEX_AH";
+    return nullptr;
+}
+void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, DenseInvCost *out) {
+    constexpr int P = DENSE_AH_STRIDE;
+    constexpr int MAX_N = DENSE_AH_WIDE_MAX_N;
+    const bool need_adj = r.weight[DENSE_INV_ADJ_EIG] != 0.0, need_dist = r.weight[DENSE_INV_DIST_EIG] != 0.0;
+    std::vector<double> Am((size_t)MAX_N * P, 0.0);
+    double *A = Am.data();
+    int trans[MAX_N], ecc[MAX_N];
+    ah_bfs(adj, n, need_dist ? A : nullptr, trans, ecc);
+    int m2 = 0, max_deg = 0, min_deg = 0x7FFFFFFF, diam = 0, rad = 0x7FFFFFFF, min_t = 0x7FFFFFFF, max_t = 0, sum_t = 0;
+    for (int u = 0; u < n; ++u) {
+        const int deg = __builtin_popcountll(adj[u]);
+        m2 += deg;
+        max_deg = deg > max_deg ? deg : max_deg;
+        min_deg = deg < min_deg ? deg : min_deg;
+        diam = ecc[u] > diam ? ecc[u] : diam;
+        rad = ecc[u] < rad ? ecc[u] : rad;
+        min_t = trans[u] < min_t ? trans[u] : min_t;
+        max_t = trans[u] > max_t ? trans[u] : max_t;
+        sum_t += trans[u];
+    }
+    const int q23 = (2 * diam) / 3;
+    const int dist_k = r.dist_index != DENSE_INV_INDEX_AH ? r.dist_index : q23 >= 1 ? q23 - 1 : n - 1;
+    double I[DENSE_INV_COUNT];
+    I[0] = (double)(m2 / 2);
+    I[1] = (double)max_deg;
+    I[2] = (double)min_deg;
+    I[3] = (double)diam;
+    I[4] = (double)rad;
+    I[5] = (double)min_t / (double)(n - 1);
+    I[6] = (double)max_t / (double)(n - 1);
+    I[7] = (double)sum_t / (double)(n * (n - 1));
+    I[8] = I[9] = 0.0;
+    double diag[MAX_N], sub[MAX_N];
+    // the distance pass runs first, on the rows the BFS left; the adjacency pass refills the matrix from the bitsets
+    if (need_dist) {
+        ah_householder(A, n, diag, sub);
+        I[DENSE_INV_DIST_EIG] = ah_multisection(diag, sub, n, dist_k);
+    }
+    if (need_adj) {
+        for (int u = 0; u < n; ++u)
+            for (int v = 0; v < n; ++v) A[u * P + v] = (adj[u] >> v) & 1ull ? 1.0 : 0.0;
+        ah_householder(A, n, diag, sub);
+        I[DENSE_INV_ADJ_EIG] = ah_multisection(diag, sub, n, r.adj_index);
+    }
+    double c = r.bias;
+    for (int i = 0; i < DENSE_INV_COUNT; ++i) {
+        out->inv[i] = I[i];
+        if (r.weight[i] != 0.0) {
+            const double term = r.weight[i] * I[i];
+            c = c + term;
+        }
+    }
+    out->dist_k = dist_k;
+    out->computed = DENSE_INV_ALWAYS | (need_adj ? 1u << DENSE_INV_ADJ_EIG : 0u) | (need_dist ? 1u << DENSE_INV_DIST_EIG : 0u);
+    out->cost = (float)c;
+    out->eval = r.eval_scale * (out->cost + r.eval_offset);
 }
 
 } // namespace azd

@@ -76,4 +76,39 @@ const char *dense_ah_check_graph_wide(const uint64_t *adj, int n); // 4 <= n <= 
 // n <= DENSE_AH_WIDE_MAX_N (one function behind azd_dense_ah_cost and azd_dense_ah_cost_wide: the limit is the callers' check)
 void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out);
 
+// Weighted-invariant cost of a connected graph on 4 <= n <= DENSE_INV_MAX_N vertices (BUILD-DEFINED; DESIGN.md "The invariant
+// cost"): ten invariants in a fixed order -- index and name are ABI -- combined with weights the caller gives at run time:
+//   0 edges m   1 max_degree   2 min_degree   3 diameter   4 radius   5 proximity = min_u t(u) / (n - 1)
+//   6 remoteness = max_u t(u) / (n - 1)   7 avg_distance = sum_u t(u) / (n (n - 1))
+//   8 adj_eig = eigenvalue of the adjacency matrix at descending index adj_index
+//   9 dist_eig = eigenvalue of the distance matrix at descending index dist_index, or (DENSE_INV_INDEX_AH) k = 2D/3 - 1, n - 1 when 2D/3 = 0
+//   c = bias; for i = 0 .. 9 in order, if weight[i] != 0: c = c + weight[i] * I_i (two IEEE f64 operations, never fused)
+//   cost = (float)c;  eval = eval_scale * (cost + eval_offset)  (f32, this order)
+// A spectral invariant whose weight is zero is not computed: its value is 0.0 and its bit of `computed` is clear.  The matching
+// number is not in the list: it needs the default cost's per-node matching arena and repair (space_dense.inc), and lambda_1 + mu
+// stays that tier's objective.  The spectral procedure and its constants are the Aouchiche-Hansen cost's (DENSE_AH_ROUNDS,
+// DENSE_AH_TINY); with weight[5] = weight[9] = 1, dist_index = DENSE_INV_INDEX_AH, offset 2 and scale 1.0f / (2 n + 2) the cost
+// and eval are that cost's, bit for bit.
+constexpr int DENSE_INV_MAX_N = 32;
+constexpr int DENSE_INV_COUNT = 10;
+constexpr int DENSE_INV_ADJ_EIG = 8, DENSE_INV_DIST_EIG = 9;
+constexpr int DENSE_INV_INDEX_AH = -1;
+constexpr uint32_t DENSE_INV_ALWAYS = 0xFFu; // bits of `computed` that are always set: the eight integer invariants
+struct DenseInvRecipe {
+    double weight[DENSE_INV_COUNT];
+    double bias;
+    int adj_index, dist_index;
+    float eval_offset, eval_scale;
+};
+struct DenseInvCost {
+    double inv[DENSE_INV_COUNT];
+    int dist_k;        // the distance index the recipe resolves to on this graph (reported whether or not dist_eig is computed)
+    uint32_t computed; // bit i: inv[i] was computed
+    float cost, eval;
+};
+// nullptr when the recipe is acceptable for graphs on n vertices, else what is wrong with it (a field name leads the text)
+const char *dense_inv_check_recipe(const DenseInvRecipe *r, int n);
+const char *dense_inv_check_graph(const uint64_t *adj, int n); // as dense_ah_check_graph, in this cost's words
+void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, DenseInvCost *out);
+
 } // namespace azd

@@ -70,7 +70,7 @@ static const ExtPoolForm *ext_pool_form(bool dense_space) {
     return dense_space ? &dense : &ramsey;
 }
 
-// The eight kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
+// The nine kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
 // parts: c21 has no searcher-only pool step; the 64-bit Ramsey tier's is joined to the three parts of its phase unit's table.
 static const TierDesc *tier_desc(Tier t) {
     static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops(), PoolSearchOps{}};
@@ -79,17 +79,17 @@ static const TierDesc *tier_desc(Tier t) {
     static const SpaceOps ramsey64_big = {ramsey64_big_ops(), ramsey64_big_ops(), ramsey64_big_ops(), ramsey64_big_pool_search_ops()};
     const ExtPoolForm *const xd = ext_pool_form(true), *const xr = ext_pool_form(false);
     static const TierDesc tiers[TIER_COUNT] = {
-        {TIER_C21, SPACE_C21, &c21, nullptr, 0, 0, false, false, false, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
-        {TIER_RAMSEY, SPACE_RAMSEY, &ramsey, nullptr, sizeof(RamseyArgminRec), 128, false, false, false, AZD_RAMSEY_MAX_N, 256, 64 * MAX_KW, 0, 5, false,
+        {TIER_C21, SPACE_C21, &c21, nullptr, 0, 0, false, false, false, 1, 1, 0, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        {TIER_RAMSEY, SPACE_RAMSEY, &ramsey, nullptr, sizeof(RamseyArgminRec), 128, false, false, false, 1, 1, 0, AZD_RAMSEY_MAX_N, 256, 64 * MAX_KW, 0, 5, false,
          "unsupported Ramsey space (need 3 <= n, E <= 256, 2..4 colours, clique sizes 2..5, E*C <= 384)", nullptr, nullptr, nullptr},
         // max_slots > 0: the most permitted edges a root may bring; device keys padded to the widths ramsey_kernels.hip is built for
-        {TIER_RAMSEY_WIDE, SPACE_RAMSEY, &ramsey, xr, sizeof(RamseyWideArgminRec), 128, true, true, false, AZD_RAMSEY_WIDE_MAX_N, 496, 1024, 0, 5, false,
+        {TIER_RAMSEY_WIDE, SPACE_RAMSEY, &ramsey, xr, sizeof(RamseyWideArgminRec), 128, true, true, false, 1, 1, 0, AZD_RAMSEY_WIDE_MAX_N, 496, 1024, 0, 5, false,
          "unsupported wide Ramsey space (max_slots > 0: need 3 <= n <= 32, 2..4 colours, clique sizes 2..5, E*C <= 1024)",
          "wide Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)", nullptr,
          // (cur_seq holds MAX_NODE_ACTIONS actions; a wide path can be longer)
          "wide Ramsey space (max_slots > 0): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)"},
         // AZD_ENGINE_RAMSEY_U64: uint64_t neighbourhood rows of 64 vertices, keys of RAMSEY_U64_KW words, its own record
-        {TIER_RAMSEY_U64, SPACE_RAMSEY, &ramsey64, xr, sizeof(RamseyU64ArgminRec), 512, true, true, false, AZD_RAMSEY_U64_MAX_N, 2016,
+        {TIER_RAMSEY_U64, SPACE_RAMSEY, &ramsey64, xr, sizeof(RamseyU64ArgminRec), 512, true, true, false, 1, 1, 0, AZD_RAMSEY_U64_MAX_N, 2016,
          64 * RAMSEY_U64_KW, AZD_RAMSEY_U64_NODE_ACTIONS, 5, false,
          "unsupported 64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64: need 3 <= n <= 64, 2..4 colours, clique sizes 2..5, E*C <= 2304)",
          "64-bit Ramsey space: need 1 <= max_slots <= E (azd_engine_config::max_slots: permitted edges per root)",
@@ -97,7 +97,7 @@ static const TierDesc *tier_desc(Tier t) {
          "64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64): ActionSet paths only (path_kind = AZD_PATH_SET), no Layered wrapper (layers <= 1)"},
         // AZD_ENGINE_RAMSEY_BIG_CLIQUES beside AZD_ENGINE_RAMSEY_U64: the same tier over kernels that count cliques up to K8
         // (ramsey64_big_kernels.hip); the record, the limits and the pool step's form are the 64-bit tier's
-        {TIER_RAMSEY_U64_BIG, SPACE_RAMSEY, &ramsey64_big, xr, sizeof(RamseyU64ArgminRec), 512, true, true, false, AZD_RAMSEY_U64_MAX_N, 2016,
+        {TIER_RAMSEY_U64_BIG, SPACE_RAMSEY, &ramsey64_big, xr, sizeof(RamseyU64ArgminRec), 512, true, true, false, 1, 1, 0, AZD_RAMSEY_U64_MAX_N, 2016,
          64 * RAMSEY_U64_KW, AZD_RAMSEY_U64_NODE_ACTIONS, AZD_RAMSEY_BIG_CLIQUE_MAX, true,
          "unsupported 64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64 with AZD_ENGINE_RAMSEY_BIG_CLIQUES: need 3 <= n <= 64, 2..4 colours, clique "
          "sizes 2..8, E*C <= 2304)",
@@ -105,17 +105,23 @@ static const TierDesc *tier_desc(Tier t) {
          "64-bit Ramsey space (AZD_ENGINE_RAMSEY_BIG_CLIQUES): a node holds 512 actions: need max_slots * (C - 1) <= 512 (azd_engine_config::max_slots)",
          "64-bit Ramsey space (AZD_ENGINE_RAMSEY_U64 with AZD_ENGINE_RAMSEY_BIG_CLIQUES): ActionSet paths only (path_kind = AZD_PATH_SET), no "
          "Layered wrapper (layers <= 1)"},
-        {TIER_DENSE, SPACE_DENSE, &dense_ops(), xd, sizeof(DenseArgminRec), 0, false, true, false, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
-        {TIER_DENSE_AH, SPACE_DENSE, &dense_ah_ops(), xd, sizeof(DenseAhArgminRec), 0, false, true, true, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
-        {TIER_DENSE_AH_WIDE, SPACE_DENSE, &dense_ah_wide_ops(), xd, sizeof(DenseAhWideArgminRec), 0, false, true, true, 0, 0, 0, 0, 0, false, nullptr, nullptr,
+        {TIER_DENSE, SPACE_DENSE, &dense_ops(), xd, sizeof(DenseArgminRec), 0, false, true, false, 1, 1, 0, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        {TIER_DENSE_AH, SPACE_DENSE, &dense_ah_ops(), xd, sizeof(DenseAhArgminRec), 0, false, true, true, 2, 2, 0, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        {TIER_DENSE_AH_WIDE, SPACE_DENSE, &dense_ah_wide_ops(), xd, sizeof(DenseAhWideArgminRec), 0, false, true, true, 2, 2, 0, 0, 0, 0, 0, 0, false, nullptr, nullptr,
          nullptr, nullptr},
+        // AZD_ENGINE_DENSE_INV: the weighted-invariant cost (dense_inv_kernels.hip): ten doubles and two ints per agent, the recipe behind the doubles
+        {TIER_DENSE_INV, SPACE_DENSE, &dense_inv_ops(), xd, sizeof(DenseInvArgminRec), 0, false, true, false, DENSE_INV_COUNT, 2,
+         (int)((sizeof(DenseInvRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
     };
     return &tiers[t];
 }
 // the tier of a configuration that check_engine_config has accepted: the flags name it, never the sizes
 const TierDesc *engine_tier(const azd_engine_config *cfg) {
     if (cfg->space_id == AZD_SPACE_DENSE)
-        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_AH_WIDE ? TIER_DENSE_AH_WIDE : cfg->flags & AZD_ENGINE_DENSE_AH ? TIER_DENSE_AH : TIER_DENSE);
+        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_INV       ? TIER_DENSE_INV
+                         : cfg->flags & AZD_ENGINE_DENSE_AH_WIDE ? TIER_DENSE_AH_WIDE
+                         : cfg->flags & AZD_ENGINE_DENSE_AH      ? TIER_DENSE_AH
+                                                                 : TIER_DENSE);
     if (cfg->space_id != AZD_SPACE_RAMSEY) return tier_desc(TIER_C21);
     if (cfg->flags & AZD_ENGINE_RAMSEY_U64) return tier_desc(cfg->flags & AZD_ENGINE_RAMSEY_BIG_CLIQUES ? TIER_RAMSEY_U64_BIG : TIER_RAMSEY_U64);
     return tier_desc(cfg->max_slots != 0 ? TIER_RAMSEY_WIDE : TIER_RAMSEY);
@@ -408,7 +414,17 @@ int check_engine_config(const azd_engine_config *cfg) {
                       "AZD_SPACE_RAMSEY with max_slots > 0, whose kernels for clique sizes up to 8 it asks for)");
     const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
     const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
-    if (dense_ah_wide) {
+    if (cfg->flags & AZD_ENGINE_DENSE_INV) { // the weighted-invariant cost: a tier of its own, asked for by name; the AH tier's limits
+        const char *bad = dense_ah || dense_ah_wide ? "flags: AZD_ENGINE_DENSE_INV is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH or AZD_ENGINE_DENSE_AH_WIDE "
+                                                      "(the Aouchiche-Hansen cost is one of its recipes)"
+                          : !dense                                       ? "space_id: AZD_ENGINE_DENSE_INV needs the dense-graph space (AZD_SPACE_DENSE)"
+                          : cfg->n < 4 || cfg->n > AZD_DENSE_INV_MAX_N   ? "n: the weighted-invariant cost needs 4 <= n <= 32 (AZD_DENSE_INV_MAX_N)"
+                          : cfg->layers > 1                              ? "layers: AZD_ENGINE_DENSE_INV engines take no Layered wrapper (layers <= 1)"
+                          : cfg->max_slots > dense_edges(cfg->n)         ? "max_slots: AZD_ENGINE_DENSE_INV needs max_slots <= E = n (n - 1) / 2"
+                          : cfg->path_kind != AZD_PATH_SET               ? "path_kind: AZD_ENGINE_DENSE_INV engines keep ActionSet paths (AZD_PATH_SET)"
+                                                                         : nullptr;
+        if (bad) return refuse(bad);
+    } else if (dense_ah_wide) {
         const char *bad = !dense_ah ? "flags: AZD_ENGINE_DENSE_AH_WIDE is valid only beside AZD_ENGINE_DENSE_AH (the Aouchiche-Hansen cost whose 64-row form it asks for)"
                           : !dense  ? "space_id: AZD_ENGINE_DENSE_AH_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
                           : cfg->n < 4 || cfg->n > AZD_DENSE_AH_WIDE_MAX_N ? "n: the wide Aouchiche-Hansen cost needs 4 <= n <= 64 (AZD_DENSE_AH_WIDE_MAX_N)"
@@ -482,7 +498,7 @@ void engine_shape(const azd_engine_config *cfg, const TierDesc *t, Arenas *ap) {
         a.S = dense_state_dim(cfg->n);
         a.KW = dense_device_key_words(cfg->max_slots); // (an AH engine: key widths 2, 4 and 10 only: max_slots <= E <= 496)
         a.dense_p24 = (uint32_t)((cfg->dense_p > 0.f ? (double)cfg->dense_p : 0.2) * 16777216.0 + 0.5);
-        a.eval_slope = t->ah ? dense_ah_eval_slope(cfg->n) : c21_eval_slope(cfg->n);
+        a.eval_slope = t->ah ? dense_ah_eval_slope(cfg->n) : c21_eval_slope(cfg->n); // (the weighted-invariant cost reads its recipe's scale, not this)
     } else if (t->space == SPACE_RAMSEY) {
         a.C = cfg->n_colors;
         a.E = ramsey_edges(cfg->n);
@@ -727,9 +743,10 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
     AZD_ST(e->alloc(&a.root_perm, B * a.KW));
     AZD_ST(e->alloc(&a.cur_perm, B * a.KW));
     AZD_ST(e->alloc(&a.cur_path, B * a.KW));
-    // (an AH dense engine keeps two doubles and two ints per agent there: dense_ah_cost.inc, DenseCostAH)
-    AZD_ST(e->alloc(&a.cur_lambda, tier->ah ? 2 * B : B));
-    AZD_ST(e->alloc(&a.cur_mu, tier->ah ? 2 * B : B));
+    // (an AH dense engine keeps two doubles and two ints per agent there: dense_ah_cost.inc, DenseCostAH; an INV dense engine ten and
+    // two, and its recipe behind the doubles: dense_inv_cost.inc, DenseCostInv -- the tier's row says how many)
+    AZD_ST(e->alloc(&a.cur_lambda, (size_t)tier->cost_f64 * B + (size_t)tier->cost_tail_f64));
+    AZD_ST(e->alloc(&a.cur_mu, (size_t)tier->cost_i32 * B));
     AZD_ST(e->alloc(&a.state_pos, B));
     AZD_ST(e->alloc(&a.n_nodes, B));
     AZD_ST(e->alloc(&a.n_arcs, B));
@@ -758,9 +775,10 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         AZD_ST(e->alloc(&a.root_aid, B * (size_t)e->dense_slots));
         AZD_ST(e->alloc(&e->d_stage_slots, B * (size_t)((a.E + 63) / 64)));
         AZD_ST(e->alloc(&a.argmin_d, 1));
-        static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseAhWideArgminRec) <= sizeof(azd::DenseArgminRec),
-                      "an AH engine's argmin record lives in argmin_d's allocation");
-        if (!tier->ah) AZD_ST(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH cost keeps nothing per node)
+        static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseAhWideArgminRec) <= sizeof(azd::DenseArgminRec) &&
+                          sizeof(azd::DenseInvArgminRec) <= sizeof(azd::DenseArgminRec),
+                      "an AH or INV engine's argmin record lives in argmin_d's allocation");
+        if (tier->id == TIER_DENSE) AZD_ST(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH and the weighted-invariant cost keep nothing per node)
         // a bf16 evaluator takes the state vectors as bf16 rows: this space's kernels write them beside the f32 rows (write_vec16)
         if (ev && ev->input16_pitch() >= a.S) {
             a.S16 = ev->input16_pitch();
@@ -868,8 +886,13 @@ int azd_engine_destroy(azd_engine *e) {
 // optimizer/mod.rs:61-70
 int azd_engine_par_new_begin(azd_engine *e, const uint8_t *parents, const uint64_t *permitted) {
     if (!e || !parents || !permitted) return AZD_ERR_INVALID_ARGUMENT;
+    if (e->tier->id == TIER_DENSE_INV && !e->inv_recipe_set) {
+        azd::g_last_error = "par_new: an AZD_ENGINE_DENSE_INV engine has no cost before azd_engine_set_dense_inv_recipe has given it its recipe";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
     AZD_ENTER(e);
     AZD_ST(upload_roots(e, parents, permitted));
+    e->inv_recipe_locked = true;
     const azd::Arenas &a = e->a;
     AZD_HIP(hipMemsetAsync(a.counters, 0, (size_t)a.B * azd::NUM_COUNTERS * 8, e->stream));
     e->counters_by_wave = false;

@@ -267,6 +267,62 @@ int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, i
 int azd_debug_probe_ah_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
     return probe_ah_cost("azd_debug_probe_ah_cost_wide", true, device, adj, n, count, reps, out, ms);
 }
+// ------------------------------------------------------------------ weighted-invariant cost of the dense-graph space
+static_assert(AZD_DENSE_INV_MAX_N == azd::DENSE_INV_MAX_N && AZD_DENSE_INV_COUNT == azd::DENSE_INV_COUNT && AZD_DENSE_INV_INDEX_AH == azd::DENSE_INV_INDEX_AH,
+              "AZD_DENSE_INV_*");
+// graph `i` (or the only one) and the recipe, checked in this order; the text names `fn` and the argument
+static int inv_check(const char *fn, const uint64_t *adj, int n, int i, const azd_dense_inv_recipe *recipe) {
+    const char *why = azd::dense_inv_check_graph(adj, n);
+    if (!why) why = azd::dense_inv_check_recipe(reinterpret_cast<const azd::DenseInvRecipe *>(recipe), n);
+    else if (i >= 0) {
+        azd::g_last_error = std::string(fn) + ": graph " + std::to_string(i) + ": " + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (!why) return AZD_OK;
+    azd::g_last_error = std::string(fn) + ": " + why;
+    return AZD_ERR_INVALID_ARGUMENT;
+}
+int azd_dense_inv_cost(const uint64_t *adj, int n, const azd_dense_inv_recipe *recipe, azd_dense_inv_cost_t *out) {
+    if (!out) {
+        azd::g_last_error = "azd_dense_inv_cost: out: null";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    AZD_ST(inv_check("azd_dense_inv_cost", adj, n, -1, recipe));
+    azd::dense_inv_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvRecipe *>(recipe), reinterpret_cast<azd::DenseInvCost *>(out));
+    return AZD_OK;
+}
+int azd_debug_probe_inv_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_inv_recipe *recipe,
+                             azd_dense_inv_cost_t *out, float *ms) {
+    const char *name = "azd_debug_probe_inv_cost";
+    if (!out || count <= 0 || reps <= 0) {
+        azd::g_last_error = std::string(name) + ": out / count / reps";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
+        AZD_ST(inv_check(name, adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n, i, recipe));
+    AZD_ST(azd::device_ok(device));
+    AZD_HIP(hipSetDevice(device));
+    azd::DevBuf<uint64_t> d_adj;
+    azd::DevBuf<azd::DenseInvCost> d_out;
+    azd::DevBuf<azd::DenseInvRecipe> d_recipe;
+    azd::Event e0, e1;
+    AZD_ST(azd::alloc_set(d_adj, (size_t)count * n, d_out, (size_t)count, d_recipe, (size_t)1));
+    AZD_ST(e0.create());
+    AZD_ST(e1.create());
+    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
+    AZD_HIP(hipMemcpy(d_recipe, recipe, sizeof(azd::DenseInvRecipe), hipMemcpyHostToDevice));
+    azd::launch_probe_inv_cost(d_adj, n, count, 1, d_recipe, d_out, nullptr); // warm-up
+    AZD_HIP(hipEventRecord(e0, nullptr));
+    azd::launch_probe_inv_cost(d_adj, n, count, reps, d_recipe, d_out, nullptr);
+    AZD_HIP(hipEventRecord(e1, nullptr));
+    hipError_t he = hipDeviceSynchronize();
+    float t = 0.f;
+    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
+    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseInvCost), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_inv_cost");
+    if (ms) *ms = t;
+    return AZD_OK;
+}
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
     if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ST(azd::device_ok(device));

@@ -90,7 +90,9 @@ int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap,
 static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes, const char *refusal) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (e->tier->id != reads) {
-        if (e->tier->ah || reads == TIER_DENSE_AH_WIDE) azd::g_last_error = refusal;
+        if (e->tier->id == TIER_DENSE_INV)
+            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_argmin_data";
+        else if (e->tier->ah || reads == TIER_DENSE_AH_WIDE || reads == TIER_DENSE_INV) azd::g_last_error = refusal;
         return AZD_ERR_UNSUPPORTED;
     }
     AZD_ENTER(e);
@@ -100,7 +102,11 @@ static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes,
 }
 static_assert(sizeof(azd_dense_argmin) == sizeof(azd::DenseArgminRec) && sizeof(azd_dense_ah_argmin) == sizeof(azd::DenseAhArgminRec) &&
                   sizeof(azd_dense_ah_wide_argmin) == sizeof(azd::DenseAhWideArgminRec) &&
-                  offsetof(azd_dense_ah_wide_argmin, node) == offsetof(azd::DenseAhWideArgminRec, node),
+                  offsetof(azd_dense_ah_wide_argmin, node) == offsetof(azd::DenseAhWideArgminRec, node) &&
+                  sizeof(azd_dense_inv_argmin) == sizeof(azd::DenseInvArgminRec) && offsetof(azd_dense_inv_argmin, node) == offsetof(azd::DenseInvArgminRec, node) &&
+                  offsetof(azd_dense_inv_argmin, inv) == offsetof(azd::DenseInvArgminRec, inv) &&
+                  sizeof(azd_dense_inv_recipe) == sizeof(azd::DenseInvRecipe) && offsetof(azd_dense_inv_recipe, eval_scale) == offsetof(azd::DenseInvRecipe, eval_scale) &&
+                  sizeof(azd_dense_inv_cost_t) == sizeof(azd::DenseInvCost) && offsetof(azd_dense_inv_cost_t, eval) == offsetof(azd::DenseInvCost, eval),
               "ABI struct mismatch");
 int azd_engine_dense_argmin_data(azd_engine *e, azd_dense_argmin *out) {
     return dense_argmin_read(e, out, TIER_DENSE, sizeof(*out),
@@ -113,8 +119,59 @@ int azd_engine_dense_ah_argmin_data(azd_engine *e, azd_dense_ah_argmin *out) {
 int azd_engine_dense_ah_wide_argmin_data(azd_engine *e, azd_dense_ah_wide_argmin *out) {
     return dense_argmin_read(e, out, TIER_DENSE_AH_WIDE, sizeof(*out), "azd_engine_dense_ah_wide_argmin_data: not an AZD_ENGINE_DENSE_AH_WIDE engine");
 }
+int azd_engine_dense_inv_argmin_data(azd_engine *e, azd_dense_inv_argmin *out) {
+    return dense_argmin_read(e, out, TIER_DENSE_INV, sizeof(*out), "azd_engine_dense_inv_argmin_data: not an AZD_ENGINE_DENSE_INV engine");
+}
+// The recipe of an AZD_ENGINE_DENSE_INV engine: checked, then copied behind the per-agent doubles of cur_lambda, where the tier's
+// kernels read it (dense_inv_cost.inc: dense_inv_recipe)
+int azd_engine_set_dense_inv_recipe(azd_engine *e, const azd_dense_inv_recipe *recipe) {
+    if (!e) return AZD_ERR_INVALID_ARGUMENT;
+    if (e->tier->id != TIER_DENSE_INV) {
+        azd::g_last_error = "azd_engine_set_dense_inv_recipe: not an AZD_ENGINE_DENSE_INV engine";
+        return AZD_ERR_UNSUPPORTED;
+    }
+    if (e->inv_recipe_locked) {
+        azd::g_last_error = "azd_engine_set_dense_inv_recipe: par_new has run: the trees' evals were computed with the recipe in force, which stays";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    const azd::DenseInvRecipe *r = reinterpret_cast<const azd::DenseInvRecipe *>(recipe);
+    if (const char *why = azd::dense_inv_check_recipe(r, e->a.n)) {
+        azd::g_last_error = std::string("azd_engine_set_dense_inv_recipe: ") + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    AZD_HIP(hipSetDevice(e->cfg.device));
+    AZD_HIP(hipMemcpy(e->a.cur_lambda + (size_t)azd::DENSE_INV_COUNT * e->a.B, r, sizeof(*r), hipMemcpyHostToDevice));
+    e->inv_recipe = *r;
+    e->inv_recipe_set = true;
+    return AZD_OK;
+}
+int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost_t *out) {
+    if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
+    if (e->tier->id != TIER_DENSE_INV) {
+        azd::g_last_error = "azd_engine_dense_inv_agent_cost: not an AZD_ENGINE_DENSE_INV engine";
+        return AZD_ERR_UNSUPPORTED;
+    }
+    AZD_ENTER(e);
+    AZD_HIP(hipStreamSynchronize(e->stream));
+    const azd::Arenas &a = e->a;
+    for (int i = 0; i < azd::DENSE_INV_COUNT; ++i) AZD_HIP(hipMemcpy(&out->inv[i], a.cur_lambda + (size_t)i * a.B + agent, 8, hipMemcpyDeviceToHost));
+    AZD_HIP(hipMemcpy(&out->dist_k, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
+    AZD_HIP(hipMemcpy(&out->computed, a.cur_mu + a.B + agent, 4, hipMemcpyDeviceToHost));
+    // cost and eval from the kept invariants: the device's combination, operation for operation (this unit is built with -ffp-contract=off)
+    const azd::DenseInvRecipe &r = e->inv_recipe;
+    double c = r.bias;
+    for (int i = 0; i < azd::DENSE_INV_COUNT; ++i)
+        if (r.weight[i] != 0.0) {
+            const double term = r.weight[i] * out->inv[i];
+            c = c + term;
+        }
+    out->cost = (float)c;
+    out->eval = r.eval_scale * (out->cost + r.eval_offset);
+    return AZD_OK;
+}
 int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
+    if (e->tier->id == TIER_DENSE_INV) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost";
     if (!e->tier->ah) return AZD_ERR_UNSUPPORTED;
     AZD_ENTER(e);
     AZD_HIP(hipStreamSynchronize(e->stream));
@@ -245,6 +302,10 @@ int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t 
     AZD_HIP(hipStreamSynchronize(e->stream));
     const azd::Arenas &a = e->a;
     if (a.space == azd::SPACE_DENSE) { // `parents` receives the neighbourhoods (8 n bytes); masks are kw_host words
+        if (e->tier->id == TIER_DENSE_INV && (lambda_1 || matching_size)) {
+            azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_INV engine keeps neither (azd_engine_dense_inv_agent_cost)";
+            return AZD_ERR_UNSUPPORTED;
+        }
         if (e->tier->ah && (lambda_1 || matching_size)) {
             azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_AH engine keeps neither (azd_engine_dense_ah_agent_cost)";
             return AZD_ERR_UNSUPPORTED;

@@ -172,6 +172,17 @@ struct DenseAhWideArgminRec { // device copy of azd_dense_ah_wide_argmin (AZD_EN
     uint32_t node;
 };
 
+struct DenseInvArgminRec { // device copy of azd_dense_inv_argmin (AZD_ENGINE_DENSE_INV engines: n <= 32, E <= 496); in argmin_d's place too
+    uint64_t adj[32];
+    uint64_t permitted[8]; // modifiable slots (colex positions) still open
+    double inv[10];        // the ten invariants (c21_host.h: DenseInvCost), 0.0 where not computed
+    int32_t dist_k;
+    uint32_t computed;
+    float cost, eval;
+    int32_t agent;
+    uint32_t node;
+};
+
 struct StatusRec { // small device block copied back after every host-visible call
     unsigned long long improved;   // k_argmin calls that improved the argmin
     unsigned long long expansions; // sum over agents and calls (metric numerator)
@@ -194,8 +205,9 @@ struct Arenas {
     uint8_t *cur_parents;
     uint64_t *cur_perm;
     uint64_t *cur_path;
-    double *cur_lambda;     // [B]; an AH dense engine: [2 B] = proximity, then eigenvalue (dense_ah_cost.inc: DenseCostAH)
-    int32_t *cur_mu;        // [B]; an AH dense engine: [2 B] = diameter, then k
+    double *cur_lambda;     // [B]; an AH dense engine: [2 B] = proximity, then eigenvalue (dense_ah_cost.inc: DenseCostAH); an INV dense
+                            // engine: [10 B] = the ten invariants, then the engine's recipe (dense_inv_cost.inc: DenseCostInv)
+    int32_t *cur_mu;        // [B]; an AH dense engine: [2 B] = diameter, then k; an INV dense engine: [2 B] = distance index, then `computed`
     uint32_t *state_pos;
     uint32_t *n_nodes, *n_arcs, *n_preds;
     uint32_t *flags;

@@ -69,6 +69,7 @@ const SpaceOps &ramsey64_big_ops();
 const PoolSearchOps &ramsey64_big_pool_search_ops();
 const SpaceOps &ramsey64_ops(), &dense_ops(), &dense_ah_ops(); // dense_ah_ops: DenseSpace with the Aouchiche-Hansen cost (dense_ah_kernels.hip)
 const SpaceOps &dense_ah_wide_ops();                            // ... with its 64-row form (dense_ah_wide_kernels.hip: AZD_ENGINE_DENSE_AH_WIDE)
+const SpaceOps &dense_inv_ops();                                // ... with the weighted-invariant cost (dense_inv_kernels.hip: AZD_ENGINE_DENSE_INV)
 constexpr size_t POOL_SEARCH_STATIC_LDS = 16; // k_pool_search's static LDS (PoolIdle) beside the dynamic region the plans lay out
 
 // ---- the same for every space
@@ -95,6 +96,11 @@ struct DenseAhCost;
 void launch_probe_ah_cost(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream);
 void launch_probe_math_f64(const double *d_in, double *d_out, int n, void *stream);
 void launch_probe_ah_cost_wide(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream); // n <= 64 (dense_ah_wide_kernels.hip)
+// dense_inv_kernels.hip: the weighted-invariant cost of `count` graphs on n vertices under the recipe at d_recipe (device memory), one
+// wave each (c21_host.h: DenseInvRecipe, DenseInvCost)
+struct DenseInvRecipe;
+struct DenseInvCost;
+void launch_probe_inv_cost(const uint64_t *d_adj, int n, int count, int reps, const DenseInvRecipe *d_recipe, DenseInvCost *d_out, void *stream);
 
 // ---- the evaluator's side of the searcher-only pool step and the recovery of an aborted launch (dense_kernels.hip; for every space that has the form)
 void launch_ext_take(const PoolArgs &pool, uint32_t *rows, uint32_t *home, uint32_t *n, unsigned long long *t0, void *stream);

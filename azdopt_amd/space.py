@@ -202,6 +202,52 @@ class RamseySpaceNoEdgeRecolor(ActionsNeverRepeat, ActionOrderIndependent):
         return index % self.E, index // self.E
 
 
+class InvariantCost:
+    """A recipe of the dense-graph space's weighted-invariant cost (AZD_ENGINE_DENSE_INV; azd_dense_inv_recipe): a linear
+    combination of ten invariants of a connected graph, chosen at run time --
+        edges, max_degree, min_degree, diameter, radius, proximity, remoteness, avg_distance,
+        adj_eig (adjacency eigenvalue at descending index adj_index), dist_eig (distance-matrix eigenvalue at descending index
+        dist_index, or "ah": floor(2D/3) - 1, n - 1 when floor(2D/3) = 0)
+    cost = (f32)(bias + sum of weight * invariant, in that order, over the non-zero weights); eval = eval_scale * (cost + eval_offset).
+    A spectral invariant with weight 0 is not computed.  `weights`: dict name -> weight (names not given weigh 0)."""
+
+    NAMES = _lib.DENSE_INV_NAMES
+
+    def __init__(self, weights, bias=0.0, adj_index=0, dist_index="ah", eval_offset=0.0, eval_scale=1.0):
+        unknown = sorted(set(weights) - set(self.NAMES))
+        if unknown:
+            raise ValueError("unknown invariant(s) %s: the names are %s" % (", ".join(unknown), ", ".join(self.NAMES)))
+        self.weights = {k: float(v) for k, v in weights.items()}
+        self.bias, self.adj_index = float(bias), int(adj_index)
+        self.dist_index = _lib.DENSE_INV_INDEX_AH if dist_index in ("ah", None) else int(dist_index)
+        self.eval_offset, self.eval_scale = np.float32(eval_offset), np.float32(eval_scale)
+
+    @classmethod
+    def aouchiche_hansen(cls, n):
+        """the recipe whose cost and eval are the Aouchiche-Hansen cost's (cost="ah") bit for bit"""
+        return cls({"proximity": 1.0, "dist_eig": 1.0}, dist_index="ah", eval_offset=2.0, eval_scale=np.float32(1.0) / np.float32(2 * n + 2))
+
+    @classmethod
+    def from_dict(cls, d):
+        """from a JSON object: {"weights": {...}, "bias": .., "adj_index": .., "dist_index": .. | "ah", "eval_offset": .., "eval_scale": ..}"""
+        return cls(d["weights"], **{k: d[k] for k in ("bias", "adj_index", "dist_index", "eval_offset", "eval_scale") if k in d})
+
+    def recipe(self):
+        r = _lib.DenseInvRecipe()
+        for i, name in enumerate(self.NAMES):
+            r.weight[i] = self.weights.get(name, 0.0)
+        r.bias, r.adj_index, r.dist_index = self.bias, self.adj_index, self.dist_index
+        r.eval_offset, r.eval_scale = float(self.eval_offset), float(self.eval_scale)
+        return r
+
+    @classmethod
+    def record(cls, rec):
+        """an azd_dense_inv_cost_t (or the cost part of an argmin record) as a dict: the invariants by name, dist_k, computed, cost"""
+        out = {name: rec.inv[i] for i, name in enumerate(cls.NAMES)}
+        out.update(dist_k=rec.dist_k, computed=rec.computed, cost=np.float32(rec.cost))
+        return out
+
+
 class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     """Connected graphs on N <= 64 vertices; an action adds an absent edge or deletes a present non-cut edge, every edge
     slot at most once (BASELINE configs[4], N = 50).  BUILD-DEFINED: the reference has the pieces
@@ -215,13 +261,19 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     (ConnectedBitsetGraph::ah_cost, mod.rs:156-198): proximity + the distance matrix's eigenvalue of index floor(2D/3) - 1;
     BUILD-DEFINED evaluate = (cost + 2) / (2N + 2).  N <= 32 there (AZD_ENGINE_DENSE_AH); states, actions, keys and roots are the
     same space's.  `ah_wide=True` (with cost="ah" only): the cost's 64-row form, N <= 64 (AZD_ENGINE_DENSE_AH_WIDE beside the
-    first flag; never chosen from N), roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives."""
+    first flag; never chosen from N), roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives.
+    `cost=InvariantCost(...)`: the weighted-invariant cost (AZD_ENGINE_DENSE_INV, N <= 32, the AH tier's limits): a linear
+    combination of ten graph invariants whose weights are given here, at run time; NablaOptimizer.par_new hands the recipe to
+    the engine.  InvariantCost.aouchiche_hansen(n) is the recipe that gives cost="ah"'s trees."""
 
     SPACE_ID = _lib.SPACE_DENSE
 
     def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False):
-        if cost not in ("c21", "ah"):
-            raise ValueError('cost must be "c21" or "ah"')
+        self.INV = cost if isinstance(cost, InvariantCost) else None
+        if self.INV is not None:
+            cost = "inv"
+        elif cost not in ("c21", "ah"):
+            raise ValueError('cost must be "c21", "ah" or an InvariantCost')
         if ah_wide and cost != "ah":
             raise ValueError('ah_wide=True needs cost="ah" (it is the Aouchiche-Hansen cost\'s 64-row form)')
         self.COST = cost
@@ -230,7 +282,7 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
         self.E = self.n * (self.n - 1) // 2
         # (an AZD_ENGINE_DENSE_AH engine refuses max_slots > E; a root cannot bring more than E slots anyway)
         # (... and an AZD_ENGINE_DENSE_AH_WIDE engine max_slots > min(E, 640): its keys are 2, 4 or 10 words)
-        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide else min(int(max_slots), self.E) if cost == "ah" else int(max_slots)
+        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide else min(int(max_slots), self.E) if cost in ("ah", "inv") else int(max_slots)
         L = _lib.lib()
         self.STATE_DIM = L.azd_dense_state_dim(self.n)
         self.ACTION_DIM = L.azd_dense_action_dim(self.n)
@@ -271,6 +323,18 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
             _lib.check(_lib.lib().azd_dense_ah_cost(_lib.ptr(a), self.n, C.byref(out)), "azd_dense_ah_cost")
         return dict(proximity=out.proximity, eigenvalue=out.eigenvalue, diameter=out.diameter, k=out.k,
                     cost=np.float32(out.cost), eval=np.float32(out.eval))
+
+    def inv_cost(self, adj, cost=None):
+        """The weighted-invariant cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_inv_cost under this
+        space's recipe (or `cost`, another InvariantCost), the same procedure as the device's, bit for bit.
+        -> dict(the ten invariants by name, dist_k, computed, cost, eval)"""
+        cost = self.INV if cost is None else cost
+        if cost is None:
+            raise ValueError("inv_cost: the space has no InvariantCost; pass one")
+        a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
+        out, r = _lib.DenseInvCost(), cost.recipe()
+        _lib.check(_lib.lib().azd_dense_inv_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_inv_cost")
+        return dict(InvariantCost.record(out), eval=np.float32(out.eval))
 
 
 class Layered:

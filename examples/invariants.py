@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""examples/ah.py's loop with the objective taken from the command line: a search over connected graphs on N vertices for a graph
+that minimises a linear combination of graph invariants -- the shape of an AutoGraphiX conjecture, "a combination of invariants is
+bounded below by ..." -- on the MI355X engine's weighted-invariant cost (AZD_ENGINE_DENSE_INV, N <= 32).
+
+    python examples/invariants.py --recipe '{"weights": {"remoteness": 1, "proximity": -1}, "eval_offset": 2, "eval_scale": 0.02}'
+                                  [--n 31] [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
+
+--recipe is a JSON object: "weights" (name -> weight over edges, max_degree, min_degree, diameter, radius, proximity, remoteness,
+avg_distance, adj_eig, dist_eig), and optionally "bias", "adj_index", "dist_index" (a descending index or "ah"), "eval_offset",
+"eval_scale" (the evaluator is trained on eval = eval_scale * (cost + eval_offset): choose them so that evals lie in (0, 1)).
+--recipe ah is the Aouchiche-Hansen cost as a recipe: the trees examples/ah.py grows, bit for bit.  A spectral invariant whose
+weight is zero is not computed, so a recipe over the integer invariants and the transmissions alone runs no eigen-solve.
+The loop is par_roll_out_episodes x episodes, par_update_model, par_reset_trees with the device root policy; every improvement of
+the argmin and every epoch print the argmin's invariants."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import azdopt_amd as az  # noqa: E402
+from azdopt_amd import sinks  # noqa: E402
+
+P = 0.4
+TOL = ([200, 50, 50], 25)       # the live drivers' n_as_tol (04-c21-tree.rs:136-138)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--recipe", required=True, help='a JSON object (see above), or "ah"')
+    ap.add_argument("--n", type=int, default=31)
+    ap.add_argument("--epochs", type=int, default=250)
+    ap.add_argument("--episodes", type=int, default=800)
+    ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--hidden", type=int, nargs="*", default=[256, 128])
+    ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
+    ap.add_argument("--max-slots", type=int, default=128)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+
+    cost = az.InvariantCost.aouchiche_hansen(args.n) if args.recipe == "ah" else az.InvariantCost.from_dict(json.loads(args.recipe))
+    space = az.DenseGraphSpace(args.n, P, max_slots=args.max_slots, cost=cost)
+    model = az.ActionModel(args.batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=1e-4, l2=1e-6, seed=args.seed,
+                           dtype=args.dtype)
+    kmin, kmax = space.default_permitted_range()
+    caps = az.tree_capacities(args.episodes, kmax)
+    opt = az.NablaOptimizer.par_new(space, space.generate_roots(args.seed, args.batch, kmin=kmin, kmax=kmax), model, args.batch, **caps)
+
+    def show(argmin, tag):
+        c = argmin.cost
+        parts = ", ".join("%s: %s" % (name, c[name]) for i, name in enumerate(az.InvariantCost.NAMES) if (c["computed"] >> i) & 1)
+        print("%s\t%s\tInvariantCost { cost: %s, %s, dist_k: %d }" % (tag, argmin.eval, c["cost"], parts, c["dist_k"]))
+
+    show(opt.argmin_data(), "argmin")
+    for epoch in range(1, args.epochs + 1):
+        print("==== EPOCH: %d ====" % epoch)
+        for _ in range(args.episodes):
+            if opt.par_roll_out_episodes(TOL, n_calls=1):
+                show(opt.argmin_data(), "argmin")
+        print("sizes:", sinks.sizes(opt.get_tree(0)))
+        loss = opt.par_update_model(200)
+        print("loss:", loss)
+        show(opt.argmin_data(), "epoch %d" % epoch)
+        opt.par_reset_trees_policy(args.seed, epoch, kmin, kmax)
+
+
+if __name__ == "__main__":
+    main()

@@ -123,7 +123,9 @@ int azd_ramsey_generate_roots_weighted(uint64_t seed, uint64_t epoch, uint64_t f
 /*   Hansen cost that 05-ah.rs searches with (ah_cost, mod.rs:156-198;        */
 /*   azd_dense_ah_cost below), or up to N = 64 with                           */
 /*   AZD_ENGINE_DENSE_AH_WIDE beside it.  States, actions, vectors and roots  */
-/*   are the same for all of them.                                            */
+/*   are the same for all of them.  A third choice, AZD_ENGINE_DENSE_INV      */
+/*   (N <= 32), is a weighted combination of ten graph invariants whose      */
+/*   weights are given at run time (azd_dense_inv_cost below).                */
 /* ------------------------------------------------------------------------- */
 #define AZD_SPACE_DENSE 3
 #define AZD_DENSE_MAX_N 64
@@ -306,6 +308,17 @@ typedef struct azd_engine_config {
  * where the narrow engine's has 7..10 and the default cost's 16 (azd_debug_ext_pool_plan reports the plan for such a
  * configuration too); AZD_DENSE_POOL_WAVES keeps its range 4..16, a setting above what fits runs what fits. */
 #define AZD_ENGINE_DENSE_AH_WIDE 256u
+/* The dense-graph space with the weighted-invariant cost (azd_dense_inv_cost below): ten graph invariants combined with weights
+ * given at RUN time by azd_engine_set_dense_inv_recipe, so that one build serves a family of objectives.  A tier of its own, in
+ * kernels of their own (dense_inv_kernels.hip); asked for by name, never inferred.  In every respect but its cost it behaves as an
+ * AZD_ENGINE_DENSE_AH engine: 4 <= n <= AZD_DENSE_INV_MAX_N = 32, layers <= 1, max_slots <= E, ActionSet paths (refused by
+ * azd_engine_create with AZD_ERR_INVALID_ARGUMENT and an azd_last_error() naming the argument, as is this flag beside
+ * AZD_ENGINE_DENSE_AH or AZD_ENGINE_DENSE_AH_WIDE or on another space); the same step forms, the pool step's wave counts (10 / 9 / 7
+ * at key widths 2 / 4 / 10), AZD_ENGINE_EXT_POOL_F32 accepted beside it.  Such an engine keeps the ten invariants, the distance
+ * index used and the `computed` mask per agent; read them with azd_engine_dense_inv_agent_cost and
+ * azd_engine_dense_inv_argmin_data (the default and the AH argmin reads, and azd_engine_agent_state's lambda_1 / matching_size, are
+ * AZD_ERR_UNSUPPORTED on it and name the right call). */
+#define AZD_ENGINE_DENSE_INV 1024u
 /* Beside AZD_ENGINE_RAMSEY_U64 only (alone, on another space or on a 32-bit tier: AZD_ERR_INVALID_ARGUMENT naming both flags): the
  * 64-bit tier with forbidden cliques up to K8 -- clique sizes 2..AZD_RAMSEY_BIG_CLIQUE_MAX, the reference's count_cliques_inside
  * (bitset_graph/mod.rs:164-185) to depth 6 in kernels of their own; the 64-bit tier's kernels and every engine without the flag are
@@ -347,7 +360,7 @@ typedef struct azd_engine_config {
  * 512 agents 0.99 against 0.52 M expansions/s, r45 at 256 agents 1.03 against 0.31 M on the wide tier and 0.79 against 0.25 M on the
  * 64-bit tier.
  * AZD_SPACE_DENSE: the space's pool step is the searcher-only form and needs no flag of its own, so there this flag stands alone, on
- * all three tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
+ * all four tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
  * this flag beside AZD_ENGINE_NO_PERSISTENT_STEP is AZD_ERR_INVALID_ARGUMENT naming both.  It is a request to the configured pool
  * step, not a form: where the engine's form is not the pool step (fewer than 256 agents without AZD_ENGINE_POOL_STEP) nothing
  * changes and azd_engine_step_form gives the reason it gave.  With it an fp32 MLP is served by the same gathered fp32 GEMMs over the
@@ -741,6 +754,71 @@ int azd_engine_dense_ah_wide_argmin_data(azd_engine *e, azd_dense_ah_wide_argmin
 /* the cost of agent `agent`'s current state as the engine keeps it (the AH counterpart of azd_engine_agent_state's lambda_1 /
  * matching_size) */
 int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out);
+
+/* ---- Weighted-invariant cost: the dense-graph space's third objective (AZD_ENGINE_DENSE_INV engines minimise it), BUILD-DEFINED
+ * (DESIGN.md "The invariant cost").  Ten invariants of a CONNECTED graph on n vertices, in this order -- index and name are ABI:
+ *   0 edges         m                                   5 proximity     min_u t(u) / (n - 1)       (one f64 division)
+ *   1 max_degree                                        6 remoteness    max_u t(u) / (n - 1)       (one f64 division)
+ *   2 min_degree                                        7 avg_distance  sum_u t(u) / (n (n - 1))   (integer sum, one f64 division)
+ *   3 diameter      D = largest eccentricity            8 adj_eig       adjacency eigenvalue at descending index adj_index
+ *   4 radius        smallest eccentricity               9 dist_eig      distance-matrix eigenvalue at descending index dist_index,
+ *                                                                       or (AZD_DENSE_INV_INDEX_AH) k = 2D/3 - 1, n - 1 when 2D/3 = 0
+ * (t(u) = sum_v d(u, v), the transmission), combined by a recipe the caller gives at run time:
+ *   c = bias;  for i = 0 .. 9 in order, if weight[i] != 0:  c = c + weight[i] * I_i   (two IEEE f64 operations, never fused)
+ *   cost = (float)c;  eval = eval_scale * (cost + eval_offset)                         (f32, this order)
+ * A spectral invariant (8, 9) whose weight is zero is not computed: it is reported as 0.0 and its bit of `computed` is clear; the
+ * eight others are always computed and reported.  The eigenvalues come from the Aouchiche-Hansen cost's procedure (Householder
+ * reduction, Sturm-count multisection), so host function, device kernel and the tests' Python reference agree bit for bit; with
+ * weight[5] = weight[9] = 1, bias 0, dist_index = AZD_DENSE_INV_INDEX_AH, eval_offset 2.0f and eval_scale 1.0f / (2n + 2) cost
+ * and eval are azd_dense_ah_cost's.  The matching number is not in the list: it needs the default cost's per-node matching arena
+ * and repair; lambda_1 + matching number stays the default tier's objective. */
+#define AZD_DENSE_INV_MAX_N 32
+#define AZD_DENSE_INV_COUNT 10
+#define AZD_DENSE_INV_INDEX_AH (-1)
+#define AZD_DENSE_INV_NAMES "edges", "max_degree", "min_degree", "diameter", "radius", "proximity", "remoteness", "avg_distance", "adj_eig", "dist_eig"
+typedef struct azd_dense_inv_recipe {
+    double weight[AZD_DENSE_INV_COUNT];
+    double bias;
+    int adj_index;     /* 0 .. n - 1 */
+    int dist_index;    /* 0 .. n - 1, or AZD_DENSE_INV_INDEX_AH */
+    float eval_offset;
+    float eval_scale;  /* not zero */
+} azd_dense_inv_recipe;
+typedef struct azd_dense_inv_cost_t {
+    double inv[AZD_DENSE_INV_COUNT];
+    int dist_k;        /* the distance index the recipe resolves to on this graph */
+    uint32_t computed; /* bit i: inv[i] was computed (0xFF always; bits 8, 9 by the weights) */
+    float cost;
+    float eval;
+} azd_dense_inv_cost_t;
+/* The cost on the host; needs no GPU.  The graph is checked like azd_dense_ah_cost's (4 <= n <= AZD_DENSE_INV_MAX_N, simple,
+ * symmetric, connected), the recipe like azd_engine_set_dense_inv_recipe's: AZD_ERR_INVALID_ARGUMENT naming the argument or field. */
+int azd_dense_inv_cost(const uint64_t *adj, int n, const azd_dense_inv_recipe *recipe, azd_dense_inv_cost_t *out);
+/* The device kernel in isolation: the cost of `count` graphs on n vertices (adj[count][n]) under one recipe, one wavefront each,
+ * repeated `reps` times; *ms = GPU time of the timed launch.  Graphs and recipe are checked before the device is looked for. */
+int azd_debug_probe_inv_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_inv_recipe *recipe,
+                             azd_dense_inv_cost_t *out, float *ms);
+/* The recipe of an AZD_ENGINE_DENSE_INV engine: set once, between azd_engine_create and the first par_new (par_new on such an engine
+ * without a recipe is refused and names this call; once par_new has run the recipe is fixed -- a tree's evals must mean one thing --
+ * and this call is AZD_ERR_INVALID_ARGUMENT).  AZD_ERR_INVALID_ARGUMENT naming the field: a weight, the bias, eval_offset or
+ * eval_scale not finite; eval_scale 0; all ten weights zero; an index outside its range.  AZD_ERR_UNSUPPORTED on an engine of
+ * another tier. */
+int azd_engine_set_dense_inv_recipe(azd_engine *e, const azd_dense_inv_recipe *recipe);
+/* ArgminData of an AZD_ENGINE_DENSE_INV engine: the graph, the slots still open, the cost record */
+typedef struct azd_dense_inv_argmin {
+    uint64_t adj[32];
+    uint64_t permitted[8]; /* modifiable slots (colex positions) still open; E <= 496 */
+    double inv[AZD_DENSE_INV_COUNT];
+    int32_t dist_k;
+    uint32_t computed;
+    float cost;
+    float eval;
+    int32_t agent;
+    uint32_t node;
+} azd_dense_inv_argmin;
+int azd_engine_dense_inv_argmin_data(azd_engine *e, azd_dense_inv_argmin *out);
+/* the cost record of agent `agent`'s current state as the engine keeps it (cost and eval recomputed from the kept invariants) */
+int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost_t *out);
 /* Parity probe for the f64 primitives the AH cost depends on bit for bit.  in: 2*n doubles (pairs x, y); out: 3*n doubles per
  * pair: [0] x / y, [1] sqrt(|x|), [2] x - (x / y) * y (two roundings: a contracted form would differ). */
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n);

@@ -224,6 +224,61 @@ private:
     bool wide_;
 };
 
+// A recipe of the weighted-invariant cost (azd_dense_inv_recipe): a linear combination of ten invariants of a connected graph --
+// edges, max_degree, min_degree, diameter, radius, proximity, remoteness, avg_distance, adj_eig, dist_eig (azdopt_amd.h has the
+// definitions) -- chosen at run time.  cost = (float)(bias + sum of weight * invariant); eval = scale * (cost + offset).
+class InvariantCost {
+public:
+    InvariantCost() : r_{} {
+        r_.dist_index = AZD_DENSE_INV_INDEX_AH;
+        r_.eval_scale = 1.0f;
+    }
+    // the recipe whose cost and eval are the Aouchiche-Hansen cost's (DenseGraphAhSpace), bit for bit
+    static InvariantCost aouchiche_hansen(int n) {
+        InvariantCost c;
+        return c.weight("proximity", 1.0).weight("dist_eig", 1.0).offset(2.0f).scale(1.0f / (float)(2 * n + 2));
+    }
+    InvariantCost &weight(const std::string &name, double w) {
+        static const char *const names[AZD_DENSE_INV_COUNT] = {AZD_DENSE_INV_NAMES};
+        for (int i = 0; i < AZD_DENSE_INV_COUNT; ++i)
+            if (name == names[i]) {
+                r_.weight[i] = w;
+                return *this;
+            }
+        throw Error(AZD_ERR_INVALID_ARGUMENT, "InvariantCost: unknown invariant " + name);
+    }
+    InvariantCost &bias(double b) { r_.bias = b; return *this; }
+    InvariantCost &adj_index(int k) { r_.adj_index = k; return *this; }
+    InvariantCost &dist_index(int k) { r_.dist_index = k; return *this; } // a descending index, or AZD_DENSE_INV_INDEX_AH (the default)
+    InvariantCost &offset(float o) { r_.eval_offset = o; return *this; }
+    InvariantCost &scale(float s) { r_.eval_scale = s; return *this; }
+    const azd_dense_inv_recipe &recipe() const { return r_; }
+
+private:
+    azd_dense_inv_recipe r_;
+};
+
+// The same space with the weighted-invariant cost as the objective (AZD_ENGINE_DENSE_INV): n <= AZD_DENSE_INV_MAX_N,
+// max_slots <= E; par_new hands the recipe to the engine.  argmin_data() gives a DenseInvArgmin.
+class DenseGraphInvSpace : public DenseGraphSpace {
+public:
+    DenseGraphInvSpace(int n, double p, int max_slots, const InvariantCost &cost) : DenseGraphSpace(n, p, max_slots), cost_(cost) {}
+    const InvariantCost &invariant_cost() const { return cost_; }
+    void configure(azd_engine_config &cfg) const {
+        DenseGraphSpace::configure(cfg);
+        cfg.flags |= AZD_ENGINE_DENSE_INV;
+    }
+    // the cost of one connected graph on the host (adj: n neighbourhood bitsets): the device's procedure, bit for bit
+    azd_dense_inv_cost_t cost(const uint64_t *adj) const {
+        azd_dense_inv_cost_t c;
+        check(azd_dense_inv_cost(adj, n(), &cost_.recipe(), &c), "azd_dense_inv_cost");
+        return c;
+    }
+
+private:
+    InvariantCost cost_;
+};
+
 // ---------------------------------------------------------------- models (NablaModel, nabla/model/mod.rs:4-8)
 class NablaModel {
 public:
@@ -339,6 +394,15 @@ struct DenseAhArgmin {
     uint32_t node;
 };
 
+struct DenseInvArgmin {
+    std::vector<uint64_t> adj;       // state: neighbourhood bitsets
+    std::vector<uint64_t> permitted; // ... and the edge slots still modifiable
+    azd_dense_inv_cost_t cost;       // the ten invariants (AZD_DENSE_INV_NAMES order), dist_k, computed, cost, eval
+    float eval;
+    int agent;
+    uint32_t node;
+};
+
 // ---------------------------------------------------------------- NablaOptimizer<Space, M, P> (nabla/optimizer/mod.rs)
 template <class Space>
 class NablaOptimizer {
@@ -379,6 +443,7 @@ public:
         azd_engine *h = nullptr;
         check(azd_engine_create(&h, &cfg, model.handle()), "NablaOptimizer::par_new (engine)");
         NablaOptimizer opt(space, model, h, batch);
+        set_recipe(space, h);
         check(azd_engine_par_new(h, roots.state.data(), roots.permitted.data()), "NablaOptimizer::par_new");
         return opt;
     }
@@ -399,6 +464,7 @@ public:
         check(azd_engine_create(&h, &cfg, nullptr), "NablaOptimizer::par_new (engine)");
         NablaOptimizer opt(space, h, batch);
         opt.host_ = &model;
+        set_recipe(space, h);
         opt.sv_.assign((size_t)batch * space.STATE_DIM(), 0.f);
         opt.pred_.assign((size_t)batch * space.ACTION_DIM(), 0.f);
         check(azd_engine_par_new_begin(h, roots.state.data(), roots.permitted.data()), "par_new_begin");
@@ -526,6 +592,12 @@ private:
     static int root_bytes(const ROTModifyParentsOnce &sp) { return sp.n(); }
     static int root_bytes(const RamseySpaceNoEdgeRecolor &sp) { return sp.E(); }
     static int root_bytes(const DenseGraphSpace &sp) { return 8 * sp.n(); }
+    // an AZD_ENGINE_DENSE_INV engine gets its recipe between create and par_new; every other space has none
+    template <class S>
+    static void set_recipe(const S &, azd_engine *) {}
+    static void set_recipe(const DenseGraphInvSpace &sp, azd_engine *h) {
+        check(azd_engine_set_dense_inv_recipe(h, &sp.invariant_cost().recipe()), "NablaOptimizer::par_new (recipe)");
+    }
     void host_predictions() { // the model call of optimizer/mod.rs:72 / :175-176 / :348 on the host side
         check(azd_engine_read_state_vecs(h_, sv_.data()), "read_state_vecs");
         host_->write_predictions(batch_, sv_.data(), pred_.data());
@@ -579,6 +651,22 @@ private:
         azd_dense_ah_argmin a;
         check(azd_engine_dense_ah_argmin_data(h_, &a), "argmin_data");
         return dense_ah_argmin_from(a, sp);
+    }
+    DenseInvArgmin argmin_of(const DenseGraphInvSpace &sp) {
+        azd_dense_inv_argmin a;
+        check(azd_engine_dense_inv_argmin_data(h_, &a), "argmin_data");
+        DenseInvArgmin r;
+        r.adj.assign(a.adj, a.adj + sp.n());
+        r.permitted.assign(a.permitted, a.permitted + (sp.E() + 63) / 64);
+        std::memcpy(r.cost.inv, a.inv, sizeof(a.inv));
+        r.cost.dist_k = a.dist_k;
+        r.cost.computed = a.computed;
+        r.cost.cost = a.cost;
+        r.cost.eval = a.eval;
+        r.eval = a.eval;
+        r.agent = a.agent;
+        r.node = a.node;
+        return r;
     }
     template <class Rec>
     static DenseAhArgmin dense_ah_argmin_from(const Rec &a, const DenseGraphAhSpace &sp) {
