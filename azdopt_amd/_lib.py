@@ -27,6 +27,7 @@ ENGINE_EXT_POOL_STEP = 64  # AZD_ENGINE_EXT_POOL_STEP: Ramsey engines with max_s
 ENGINE_DENSE_AH_WIDE = 256  # AZD_ENGINE_DENSE_AH_WIDE: beside ENGINE_DENSE_AH only: the Aouchiche-Hansen cost up to n = 64 (64-row kernels)
 ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STEP (Ramsey), alone on SPACE_DENSE: that form with an fp32 model (gathered fp32 GEMMs)
 ENGINE_DENSE_INV = 1024  # AZD_ENGINE_DENSE_INV: the dense-graph space with the weighted-invariant cost (n <= 32; recipe set at run time)
+ENGINE_DENSE_INV_WIDE = 2048  # AZD_ENGINE_DENSE_INV_WIDE: beside ENGINE_DENSE_INV only: the weighted-invariant cost up to n = 64 (64-row kernels)
 ENGINE_RAMSEY_BIG_CLIQUES = 512  # AZD_ENGINE_RAMSEY_BIG_CLIQUES: beside ENGINE_RAMSEY_U64 only: clique sizes up to 8 (kernels of their own)
 SPACE_C21 = 1
 SPACE_RAMSEY = 2
@@ -40,6 +41,7 @@ RAMSEY_U64_MAX_ACTIONS = 2304  # E*C of the 64-bit tier (keys of 36 words)
 DENSE_AH_MAX_N = 32     # AZD_DENSE_AH_MAX_N: the Aouchiche-Hansen cost (azd_dense_ah_cost)
 DENSE_AH_WIDE_MAX_N = 64  # AZD_DENSE_AH_WIDE_MAX_N: its 64-row form (azd_dense_ah_cost_wide, ENGINE_DENSE_AH_WIDE)
 DENSE_INV_MAX_N = 32    # AZD_DENSE_INV_MAX_N: the weighted-invariant cost (azd_dense_inv_cost)
+DENSE_INV_WIDE_MAX_N = 64  # AZD_DENSE_INV_WIDE_MAX_N: its 64-row form (azd_dense_inv_cost_wide, ENGINE_DENSE_INV_WIDE)
 DENSE_INV_COUNT = 10    # AZD_DENSE_INV_COUNT
 DENSE_INV_INDEX_AH = -1  # AZD_DENSE_INV_INDEX_AH: dist_index by the Aouchiche-Hansen rule, k = 2D/3 - 1 (n - 1 when 2D/3 = 0)
 # AZD_DENSE_INV_NAMES: index and name are ABI
@@ -111,6 +113,11 @@ class DenseInvCost(C.Structure):  # azd_dense_inv_cost_t
 
 class DenseInvArgmin(C.Structure):  # azd_dense_inv_argmin: ArgminData of a dense engine with the weighted-invariant cost
     _fields_ = [("adj", C.c_uint64 * 32), ("permitted", C.c_uint64 * 8), ("inv", C.c_double * 10), ("dist_k", C.c_int32),
+                ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
+
+
+class DenseInvWideArgmin(C.Structure):  # azd_dense_inv_wide_argmin: the same of an engine with ENGINE_DENSE_INV_WIDE (n <= 64, E <= 2016)
+    _fields_ = [("adj", C.c_uint64 * 64), ("permitted", C.c_uint64 * 32), ("inv", C.c_double * 10), ("dist_k", C.c_int32),
                 ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
 
 
@@ -253,6 +260,9 @@ def lib():
     sig("azd_debug_probe_ah_cost_wide", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, f32p)
     sig("azd_dense_inv_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvRecipe), C.POINTER(DenseInvCost))
     sig("azd_debug_probe_inv_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DenseInvRecipe), vp, f32p)
+    sig("azd_dense_inv_cost_wide", C.c_int, vp, C.c_int, C.POINTER(DenseInvRecipe), C.POINTER(DenseInvCost))
+    sig("azd_debug_probe_inv_cost_wide", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DenseInvRecipe), vp, f32p)
+    sig("azd_engine_dense_inv_wide_argmin_data", C.c_int, vp, C.POINTER(DenseInvWideArgmin))
     sig("azd_engine_set_dense_inv_recipe", C.c_int, vp, C.POINTER(DenseInvRecipe))
     sig("azd_engine_dense_inv_argmin_data", C.c_int, vp, C.POINTER(DenseInvArgmin))
     sig("azd_engine_dense_inv_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvCost))

@@ -266,8 +266,10 @@ static void ah_bfs(const uint64_t *adj, int n, double *A, int *trans, int *ecc) 
         ecc[u] = d;
     }
 }
-// Householder reduction of the symmetric matrix A (pitch DENSE_AH_STRIDE, reduced in place): step i clears column i below row i + 1
-static void ah_householder(double *A, int n, double *diag, double *sub) {
+// Householder reduction of the symmetric matrix A (pitch DENSE_AH_STRIDE, reduced in place): step i clears column i below row i + 1.
+// deflate: a column whose tail is below it is left as it is, like one whose tail is zero (0.0: none -- the Aouchiche-Hansen cost and
+// the weighted-invariant cost up to 32 vertices; c21_host.h: DENSE_INV_DEFLATE)
+static void ah_householder(double *A, int n, double *diag, double *sub, double deflate = 0.0) {
     constexpr int P = DENSE_AH_STRIDE;
     constexpr int MAX_N = DENSE_AH_WIDE_MAX_N;
     double v[64], p[64], q[64], tmp[64];
@@ -279,7 +281,7 @@ static void ah_householder(double *A, int n, double *diag, double *sub) {
         }
         const double tail = ah_tree64(tmp), x1 = v[i + 1];
         diag[i] = A[i * P + i];
-        if (tail == 0.0) {
+        if (tail == 0.0 || tail < deflate) {
             sub[i] = x1;
             continue;
         }
@@ -361,6 +363,9 @@ void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out) {
 const char *dense_inv_check_graph(const uint64_t *adj, int n) {
     return ah_check_graph(adj, n, DENSE_INV_MAX_N, "n: the weighted-invariant cost needs 4 <= n <= 32 (AZD_DENSE_INV_MAX_N)");
 }
+const char *dense_inv_check_graph_wide(const uint64_t *adj, int n) {
+    return ah_check_graph(adj, n, DENSE_INV_WIDE_MAX_N, "n: the wide weighted-invariant cost needs 4 <= n <= 64 (AZD_DENSE_INV_WIDE_MAX_N)");
+}
 const char *dense_inv_check_recipe(const DenseInvRecipe *r, int n) {
     if (!r) return "recipe: null";
     bool any = false;
@@ -410,15 +415,16 @@ void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, De
     I[7] = (double)sum_t / (double)(n * (n - 1));
     I[8] = I[9] = 0.0;
     double diag[MAX_N], sub[MAX_N];
+    const double deflate = n > DENSE_INV_MAX_N ? DENSE_INV_DEFLATE : 0.0;
     // the distance pass runs first, on the rows the BFS left; the adjacency pass refills the matrix from the bitsets
     if (need_dist) {
-        ah_householder(A, n, diag, sub);
+        ah_householder(A, n, diag, sub, deflate);
         I[DENSE_INV_DIST_EIG] = ah_multisection(diag, sub, n, dist_k);
     }
     if (need_adj) {
         for (int u = 0; u < n; ++u)
             for (int v = 0; v < n; ++v) A[u * P + v] = (adj[u] >> v) & 1ull ? 1.0 : 0.0;
-        ah_householder(A, n, diag, sub);
+        ah_householder(A, n, diag, sub, deflate);
         I[DENSE_INV_ADJ_EIG] = ah_multisection(diag, sub, n, r.adj_index);
     }
     double c = r.bias;

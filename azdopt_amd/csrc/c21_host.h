@@ -90,6 +90,15 @@ void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out);
 // DENSE_AH_TINY); with weight[5] = weight[9] = 1, dist_index = DENSE_INV_INDEX_AH, offset 2 and scale 1.0f / (2 n + 2) the cost
 // and eval are that cost's, bit for bit.
 constexpr int DENSE_INV_MAX_N = 32;
+constexpr int DENSE_INV_WIDE_MAX_N = 64; // AZD_ENGINE_DENSE_INV_WIDE engines, azd_dense_inv_cost_wide: the same procedure with 64 rows
+// Beyond 32 vertices only (n > DENSE_INV_MAX_N; at n <= 32 the procedure is the narrow tier's, bit for bit): a Householder step whose
+// column tail -- the sum of squares below the subdiagonal -- is below this is skipped like one whose tail is exactly zero.  A
+// rank-deficient matrix (the adjacency matrix of a double broom: rank 20 at n = 50) leaves a trailing block of rounding noise that
+// shrinks by about 2^-53 every other step; past step 35 its squares are subnormal, beta = 2 / (tail + v1 v1) overflows and the
+// reduction ends in NaN.  32 rows have too few steps to get there (smallest tail on the narrow graph set: 3e-224).  Both matrices
+// have integer entries, so ||M||_F >= 1: the entries dropped are below 2^-100 each, far inside the cost's own backward error
+// 64 n 2^-53 ||M||_F, and every tail that is reduced keeps beta <= 2^201.
+constexpr double DENSE_INV_DEFLATE = 0x1p-200;
 constexpr int DENSE_INV_COUNT = 10;
 constexpr int DENSE_INV_ADJ_EIG = 8, DENSE_INV_DIST_EIG = 9;
 constexpr int DENSE_INV_INDEX_AH = -1;
@@ -109,6 +118,8 @@ struct DenseInvCost {
 // nullptr when the recipe is acceptable for graphs on n vertices, else what is wrong with it (a field name leads the text)
 const char *dense_inv_check_recipe(const DenseInvRecipe *r, int n);
 const char *dense_inv_check_graph(const uint64_t *adj, int n); // as dense_ah_check_graph, in this cost's words
+const char *dense_inv_check_graph_wide(const uint64_t *adj, int n); // 4 <= n <= DENSE_INV_WIDE_MAX_N
+// n <= DENSE_INV_WIDE_MAX_N (one function behind azd_dense_inv_cost and azd_dense_inv_cost_wide: the limit is the callers' check)
 void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, DenseInvCost *out);
 
 } // namespace azd

@@ -16,25 +16,32 @@
 // to the code they compiled to before.
 // One triangle serves both spectral invariants, one after the other.  The BFS leaves the distances in it, so the DISTANCE pass
 // runs first, on those rows; the ADJACENCY pass then refills the triangle with 0 / 1 from the bitsets, which are still in LDS.
-// So the BFS neither runs again nor keeps its rows anywhere else, and the wave's LDS block is the 32-row AH block's size.  The
+// So the BFS neither runs again nor keeps its rows anywhere else, and the wave's LDS block is the AH block's size at either row limit.  The
 // two values do not depend on the order they are computed in; the cost takes them in index order (adj_eig, then dist_eig).
 // A spectral invariant whose weight is zero is not computed (a wave-uniform branch: the recipe is the same for all lanes): its
 // value is 0.0 and its bit of `computed` is clear.
+//
+// The row limit ROWS is a template parameter of everything here that depends on it, as in dense_ah_cost.inc: 32 (DenseCostInv:
+// dense_inv_kernels.hip, AZD_ENGINE_DENSE_INV) or 64 (DenseCostInvWide: dense_inv_wide_kernels.hip, AZD_ENGINE_DENSE_INV_WIDE beside
+// the first flag: a triangle of 2080 doubles), and the engine's argmin record follows from it.  Order of operations, lane roles
+// and reductions do not depend on it: at n <= 32 the two compute the same bits.  Beyond 32 vertices, which only the 64-row form
+// reaches, a Householder step whose column tail is below DENSE_INV_DEFLATE is skipped like one whose tail is zero (c21_host.h: a
+// rank-deficient adjacency matrix otherwise runs the reduction into subnormal squares and NaN after some 36 steps).
 __device__ __forceinline__ uint32_t dense_inv_sum_u32(uint32_t v) {
 #pragma unroll
     for (int w = 1; w < 64; w <<= 1) v += (uint32_t)__shfl_xor((int)v, w, 64);
     return uni(v);
 }
 
-// adj: the graph's neighbourhood bitsets in LDS (n <= 32 words are read).  rc: the recipe in device memory, the same address in
+// adj: the graph's neighbourhood bitsets in LDS (n <= ROWS words are read).  rc: the recipe in device memory, the same address in
 // every lane.  hook: called once, after the BFS (the pool step's deferred post).  Wave-uniform result in `out`.
-template <class Hook>
-__device__ __forceinline__ void dense_inv_cost_wave(const uint64_t *adj, DenseAhLdsT<DENSE_INV_MAX_N> &w, const int n, const DenseInvRecipe *rc,
+template <int ROWS, class Hook>
+__device__ __forceinline__ void dense_inv_cost_wave(const uint64_t *adj, DenseAhLdsT<ROWS> &w, const int n, const DenseInvRecipe *rc,
                                                     Hook &&hook, DenseInvCost &out) {
     const int lane = LANE;
     const int row = lane * (lane + 1) / 2; // this lane's row of the packed triangle (lanes < n only)
     const bool in = lane < n;
-    const uint64_t all = (1ull << n) - 1ull; // (n <= 32)
+    const uint64_t all = ROWS < 64 ? (1ull << n) - 1ull : ~0ull >> (64 - n); // (64 rows: n = 64 must not shift by 64; n >= 4)
     const bool need_adj = uni(rc->weight[DENSE_INV_ADJ_EIG] != 0.0 ? 1u : 0u) != 0u;
     const bool need_dist = uni(rc->weight[DENSE_INV_DIST_EIG] != 0.0 ? 1u : 0u) != 0u;
     const int adj_index = (int)uni((uint32_t)rc->adj_index), dist_index = (int)uni((uint32_t)rc->dist_index);
@@ -87,7 +94,9 @@ __device__ __forceinline__ void dense_inv_cost_wave(const uint64_t *adj, DenseAh
             const double tail = dense_tree_sum(lane > i + 1 ? x * x : 0.0);
             const double x1 = __shfl(x, i + 1, 64);
             if (lane == i) dg = w.A[row + i];
-            if (tail == 0.0) { // the column is tridiagonal already (adjacency matrices: often)
+            // (the column is tridiagonal already -- adjacency matrices: often -- or, beyond 32 vertices, is rounding noise of a matrix
+            // whose rank is used up: c21_host.h, DENSE_INV_DEFLATE.  At 32 rows the second condition is constant false)
+            if (tail == 0.0 || (ROWS > DENSE_INV_MAX_N && n > DENSE_INV_MAX_N && tail < DENSE_INV_DEFLATE)) {
                 if (lane == i) sb = x1;
                 continue;
             }
@@ -97,7 +106,7 @@ __device__ __forceinline__ void dense_inv_cost_wave(const uint64_t *adj, DenseAh
             const double v1 = x1 - alpha;
             const double v = lane == i + 1 ? v1 : x;
             const double beta = 2.0 / (tail + v1 * v1);
-            if (lane < DENSE_INV_MAX_N) w.v[lane] = v;
+            if (lane < ROWS) w.v[lane] = v;
             LDS_SYNC();
             double acc = 0.0;
             if (act)
@@ -106,7 +115,7 @@ __device__ __forceinline__ void dense_inv_cost_wave(const uint64_t *adj, DenseAh
             const double vp = dense_tree_sum(v * p);
             const double K = (0.5 * beta) * vp;
             const double q = act ? p - K * v : 0.0;
-            if (lane < DENSE_INV_MAX_N) w.q[lane] = q;
+            if (lane < ROWS) w.q[lane] = q;
             LDS_SYNC();
             if (act)
                 for (int c = i + 1; c <= lane; ++c) w.A[row + c] = w.A[row + c] - (v * w.q[c] + q * w.v[c]);
@@ -124,7 +133,7 @@ __device__ __forceinline__ void dense_inv_cost_wave(const uint64_t *adj, DenseAh
         const double sb_below = __shfl(sb, lane > 0 ? lane - 1 : 0, 64);
         const double g = (fabs(dg) + (lane > 0 ? fabs(sb_below) : 0.0)) + fabs(sb); // Gershgorin; >= 0: the bit patterns order like the numbers
         const double R = __longlong_as_double((long long)wave_max_u64(in ? (uint64_t)__double_as_longlong(g) : 0ull));
-        if (lane < DENSE_INV_MAX_N) {
+        if (lane < ROWS) {
             w.diag[lane] = dg;
             w.sub2[lane] = sb * sb;
         }
@@ -176,8 +185,8 @@ __device__ __forceinline__ void dense_inv_cost_wave(const uint64_t *adj, DenseAh
 }
 
 // ---------------------------------------------------------------- the weighted-invariant cost as a DenseSpace's cost policy (space_dense.inc)
-// A wave's block is the 32-row AH block (DenseAhSpaceLdsT<KW, 32>: the pool step plans 10 / 9 / 7 waves at key widths 2 / 4 / 10, as
-// there).  4 <= n <= 32, so E <= 496.
+// A wave's block is the AH block of the same row limit (DenseAhSpaceLdsT<KW, ROWS>: at 32 rows the pool step plans 10 / 9 / 7 waves at
+// key widths 2 / 4 / 10, at 64 rows what the LDS holds, as there).  4 <= n <= ROWS, so E <= 496 or 2016.
 // The recipe reaches the kernels without a field of Arenas (every search kernel receives that block): it lies in device memory
 // behind the per-agent cost arrays.  An agent's record between launches:
 //   cur_lambda[i B + t] = I_i, i = 0 .. 9;  cur_lambda + 10 B: the engine's DenseInvRecipe (azd_engine_set_dense_inv_recipe)
@@ -189,10 +198,11 @@ __device__ __forceinline__ void dense_inv_cost_wave(const uint64_t *adj, DenseAh
 __device__ __forceinline__ const DenseInvRecipe *dense_inv_recipe(const Arenas &a) {
     return reinterpret_cast<const DenseInvRecipe *>(a.cur_lambda + (size_t)DENSE_INV_COUNT * (size_t)a.B);
 }
-struct DenseCostInv {
-    using ArgminRec = DenseInvArgminRec;
+template <int ROWS>
+struct DenseCostInvT {
+    using ArgminRec = std::conditional_t<ROWS == DENSE_INV_MAX_N, DenseInvArgminRec, DenseInvWideArgminRec>; // (what engine.hip sizes argmin_d for)
     template <int KW_>
-    using Lds = DenseAhSpaceLdsT<KW_, DENSE_INV_MAX_N>;
+    using Lds = DenseAhSpaceLdsT<KW_, ROWS>;
     template <int KW_>
     struct St {
         uint64_t rem[KW_];
@@ -239,7 +249,7 @@ struct DenseCostInv {
     template <class L>
     __device__ static __forceinline__ void argmin_write(const Arenas &a, L &s, const Replay &r, const int wt, const uint32_t win_node) {
         ArgminRec *out = reinterpret_cast<ArgminRec *>(a.argmin_d);
-        if (LANE < DENSE_INV_MAX_N) out->adj[LANE] = LANE < a.n ? s.adj[LANE] : 0ull;
+        if (LANE < ROWS) out->adj[LANE] = LANE < a.n ? s.adj[LANE] : 0ull;
         if (LANE < (int)(sizeof(out->permitted) / sizeof(uint64_t))) out->permitted[LANE] = s.slotmask[LANE];
         if (LANE == 0) {
 #pragma unroll
@@ -253,16 +263,21 @@ struct DenseCostInv {
         }
     }
 };
+// Named structs, not aliases: the kernels' names carry them (k_rollout<DenseSpace<2, DenseCostInv>>)
+struct DenseCostInv : DenseCostInvT<DENSE_INV_MAX_N> {};
+struct DenseCostInvWide : DenseCostInvT<DENSE_INV_WIDE_MAX_N> {};
 
-// The cost outside any engine (space_ops.h: launch_probe_inv_cost): one wave per graph, `reps` repetitions (timing), the result
-// of the last one.  The host has checked the graphs and the recipe (engine_probes.hip): LDS is indexed by the bits of adj.
+// The cost outside any engine (space_ops.h: launch_probe_inv_cost, launch_probe_inv_cost_wide): one wave per graph, `reps`
+// repetitions (timing), the result of the last one.  Each unit launches the instantiation of its own row limit.  The host has
+// checked the graphs and the recipe (engine_probes.hip): LDS is indexed by the bits of adj.
+template <int ROWS>
 __global__ __launch_bounds__(64) void k_probe_inv_cost(const uint64_t *__restrict__ adj, const int n, const int count, const int reps,
                                                        const DenseInvRecipe *__restrict__ recipe, DenseInvCost *__restrict__ out) {
-    __shared__ uint64_t s_adj[DENSE_INV_MAX_N];
-    __shared__ DenseAhLdsT<DENSE_INV_MAX_N> w;
+    __shared__ uint64_t s_adj[ROWS];
+    __shared__ DenseAhLdsT<ROWS> w;
     const int g = blockIdx.x;
     if (g >= count) return;
-    if (LANE < DENSE_INV_MAX_N) s_adj[LANE] = LANE < n ? adj[(size_t)g * n + LANE] : 0ull;
+    if (LANE < ROWS) s_adj[LANE] = LANE < n ? adj[(size_t)g * n + LANE] : 0ull;
     LDS_SYNC();
     DenseInvCost c;
     for (int r = 0; r < reps; ++r) {

@@ -42,7 +42,7 @@ const SpaceOps &dense_inv_ops() {
 }
 
 void launch_probe_inv_cost(const uint64_t *d_adj, int n, int count, int reps, const DenseInvRecipe *d_recipe, DenseInvCost *d_out, void *stream) {
-    k_probe_inv_cost<<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, reps, d_recipe, d_out);
+    k_probe_inv_cost<DENSE_INV_MAX_N><<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, reps, d_recipe, d_out);
 }
 
 } // namespace azd

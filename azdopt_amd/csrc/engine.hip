@@ -70,7 +70,7 @@ static const ExtPoolForm *ext_pool_form(bool dense_space) {
     return dense_space ? &dense : &ramsey;
 }
 
-// The nine kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
+// The ten kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
 // parts: c21 has no searcher-only pool step; the 64-bit Ramsey tier's is joined to the three parts of its phase unit's table.
 static const TierDesc *tier_desc(Tier t) {
     static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops(), PoolSearchOps{}};
@@ -112,13 +112,17 @@ static const TierDesc *tier_desc(Tier t) {
         // AZD_ENGINE_DENSE_INV: the weighted-invariant cost (dense_inv_kernels.hip): ten doubles and two ints per agent, the recipe behind the doubles
         {TIER_DENSE_INV, SPACE_DENSE, &dense_inv_ops(), xd, sizeof(DenseInvArgminRec), 0, false, true, false, DENSE_INV_COUNT, 2,
          (int)((sizeof(DenseInvRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        // AZD_ENGINE_DENSE_INV_WIDE beside it: the same record per agent over the 64-row kernels (dense_inv_wide_kernels.hip)
+        {TIER_DENSE_INV_WIDE, SPACE_DENSE, &dense_inv_wide_ops(), xd, sizeof(DenseInvWideArgminRec), 0, false, true, false, DENSE_INV_COUNT, 2,
+         (int)((sizeof(DenseInvRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
     };
     return &tiers[t];
 }
 // the tier of a configuration that check_engine_config has accepted: the flags name it, never the sizes
 const TierDesc *engine_tier(const azd_engine_config *cfg) {
     if (cfg->space_id == AZD_SPACE_DENSE)
-        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_INV       ? TIER_DENSE_INV
+        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_INV_WIDE  ? TIER_DENSE_INV_WIDE
+                         : cfg->flags & AZD_ENGINE_DENSE_INV     ? TIER_DENSE_INV
                          : cfg->flags & AZD_ENGINE_DENSE_AH_WIDE ? TIER_DENSE_AH_WIDE
                          : cfg->flags & AZD_ENGINE_DENSE_AH      ? TIER_DENSE_AH
                                                                  : TIER_DENSE);
@@ -414,7 +418,21 @@ int check_engine_config(const azd_engine_config *cfg) {
                       "AZD_SPACE_RAMSEY with max_slots > 0, whose kernels for clique sizes up to 8 it asks for)");
     const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
     const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
-    if (cfg->flags & AZD_ENGINE_DENSE_INV) { // the weighted-invariant cost: a tier of its own, asked for by name; the AH tier's limits
+    if (cfg->flags & AZD_ENGINE_DENSE_INV_WIDE) { // the weighted-invariant cost's 64-row form: a second flag beside the first, never a cost of its own
+        const char *bad = !(cfg->flags & AZD_ENGINE_DENSE_INV)
+                              ? "flags: AZD_ENGINE_DENSE_INV_WIDE is valid only beside AZD_ENGINE_DENSE_INV (the weighted-invariant cost whose 64-row form it asks for)"
+                          : dense_ah || dense_ah_wide
+                              ? "flags: AZD_ENGINE_DENSE_INV_WIDE belongs to a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH or AZD_ENGINE_DENSE_AH_WIDE "
+                                "(the Aouchiche-Hansen cost is one of its recipes)"
+                          : !dense ? "space_id: AZD_ENGINE_DENSE_INV_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
+                          : cfg->n < 4 || cfg->n > AZD_DENSE_INV_WIDE_MAX_N ? "n: the wide weighted-invariant cost needs 4 <= n <= 64 (AZD_DENSE_INV_WIDE_MAX_N)"
+                          : cfg->layers > 1 ? "layers: AZD_ENGINE_DENSE_INV_WIDE engines take no Layered wrapper (layers <= 1)"
+                          : cfg->path_kind != AZD_PATH_SET ? "path_kind: AZD_ENGINE_DENSE_INV_WIDE engines keep ActionSet paths (AZD_PATH_SET)"
+                          : cfg->max_slots < 1 || cfg->max_slots > std::min(dense_edges(cfg->n), 640)
+                              ? "max_slots: AZD_ENGINE_DENSE_INV_WIDE needs 1 <= max_slots <= min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)"
+                              : nullptr;
+        if (bad) return refuse(bad);
+    } else if (cfg->flags & AZD_ENGINE_DENSE_INV) { // the weighted-invariant cost: a tier of its own, asked for by name; the AH tier's limits
         const char *bad = dense_ah || dense_ah_wide ? "flags: AZD_ENGINE_DENSE_INV is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH or AZD_ENGINE_DENSE_AH_WIDE "
                                                       "(the Aouchiche-Hansen cost is one of its recipes)"
                           : !dense                                       ? "space_id: AZD_ENGINE_DENSE_INV needs the dense-graph space (AZD_SPACE_DENSE)"
@@ -774,10 +792,13 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         AZD_ST(e->alloc(&a.cur_adj, B * 64));
         AZD_ST(e->alloc(&a.root_aid, B * (size_t)e->dense_slots));
         AZD_ST(e->alloc(&e->d_stage_slots, B * (size_t)((a.E + 63) / 64)));
-        AZD_ST(e->alloc(&a.argmin_d, 1));
+        // (a tier's kernels write its own record where argmin_d points, TierDesc::argmin_bytes of it: so many records of the default
+        // cost's type, as argmin_r_recs counts them for the Ramsey tiers -- one for every tier but the 64-row weighted-invariant
+        // one, whose 64 rows, 32 slot words and ten invariants come to 872 bytes where the default cost's record has 856)
         static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseAhWideArgminRec) <= sizeof(azd::DenseArgminRec) &&
-                          sizeof(azd::DenseInvArgminRec) <= sizeof(azd::DenseArgminRec),
+                          sizeof(azd::DenseInvArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseInvWideArgminRec) <= 2 * sizeof(azd::DenseArgminRec),
                       "an AH or INV engine's argmin record lives in argmin_d's allocation");
+        AZD_ST(e->alloc(&a.argmin_d, (tier->argmin_bytes + sizeof(azd::DenseArgminRec) - 1) / sizeof(azd::DenseArgminRec)));
         if (tier->id == TIER_DENSE) AZD_ST(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH and the weighted-invariant cost keep nothing per node)
         // a bf16 evaluator takes the state vectors as bf16 rows: this space's kernels write them beside the f32 rows (write_vec16)
         if (ev && ev->input16_pitch() >= a.S) {
@@ -886,7 +907,7 @@ int azd_engine_destroy(azd_engine *e) {
 // optimizer/mod.rs:61-70
 int azd_engine_par_new_begin(azd_engine *e, const uint8_t *parents, const uint64_t *permitted) {
     if (!e || !parents || !permitted) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->tier->id == TIER_DENSE_INV && !e->inv_recipe_set) {
+    if (tier_inv(e->tier) && !e->inv_recipe_set) {
         azd::g_last_error = "par_new: an AZD_ENGINE_DENSE_INV engine has no cost before azd_engine_set_dense_inv_recipe has given it its recipe";
         return AZD_ERR_INVALID_ARGUMENT;
     }

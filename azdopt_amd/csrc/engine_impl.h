@@ -37,7 +37,7 @@ struct ExtPoolForm {
 
 // The kind of engine a configuration asks for, and what the host code goes by for it: chosen once (engine_tier, after
 // check_engine_config has accepted the configuration), never re-derived from how the arenas were filled.
-enum Tier { TIER_C21, TIER_RAMSEY, TIER_RAMSEY_WIDE, TIER_RAMSEY_U64, TIER_RAMSEY_U64_BIG, TIER_DENSE, TIER_DENSE_AH, TIER_DENSE_AH_WIDE, TIER_DENSE_INV, TIER_COUNT };
+enum Tier { TIER_C21, TIER_RAMSEY, TIER_RAMSEY_WIDE, TIER_RAMSEY_U64, TIER_RAMSEY_U64_BIG, TIER_DENSE, TIER_DENSE_AH, TIER_DENSE_AH_WIDE, TIER_DENSE_INV, TIER_DENSE_INV_WIDE, TIER_COUNT };
 struct TierDesc {
     Tier id;
     int space;                  // azd::SPACE_*
@@ -57,6 +57,9 @@ struct TierDesc {
     bool clique_overflow_rule;  // sizes above 5: every colour must pass RamseyCounts::new's i32 bound, C(s,2) * C(n,s) <= 2^31 - 1
     const char *e_range, *e_slots, *e_node_actions, *e_paths;
 };
+
+// the weighted-invariant cost at either row limit: the recipe, its setter and the per-agent record are the same on both tiers
+inline bool tier_inv(const TierDesc *t) { return t->id == TIER_DENSE_INV || t->id == TIER_DENSE_INV_WIDE; }
 
 // The evaluator groups' device memory (PoolArgs::grp_*): the two tables of the plan, and the per-slot exchange state, regrown as a
 // whole when the plan needs more of any of it.
@@ -90,7 +93,7 @@ struct azd_engine {
     azd_engine_config cfg;
     azd::Arenas a;
     const azd::SpaceOps *ops = nullptr; // the launchers and LDS plans of the engine's space and tier (space_ops.h)
-    const TierDesc *tier = nullptr;     // which of the nine kinds of engine this is (engine_tier)
+    const TierDesc *tier = nullptr;     // which of the ten kinds of engine this is (engine_tier)
     bool inv_recipe_set = false;        // AZD_ENGINE_DENSE_INV: azd_engine_set_dense_inv_recipe has run (par_new refuses before it) ...
     azd::DenseInvRecipe inv_recipe{};   // ... the recipe as set (the device's copy lies behind cur_lambda's per-agent part)
     bool inv_recipe_locked = false;     // ... and par_new has computed the roots' evals with it (the setter refuses from then on)

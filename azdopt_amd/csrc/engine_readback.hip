@@ -85,14 +85,17 @@ int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap,
     if (node) *node = r.node;
     return AZD_OK;
 }
-// The three dense argmin entries: `reads` is the tier whose record the entry copies out, `refusal` its text for an engine of another
-// tier -- said to an engine with the Aouchiche-Hansen cost (an engine without it is refused without a text), by the wide entry to all
+// The dense argmin entries: `reads` is the tier whose record the entry copies out, `refusal` its text for an engine of another
+// tier -- said to an engine with the Aouchiche-Hansen cost (an engine without it is refused without a text), by the wide entry to all.
+// The two weighted-invariant tiers name each other's reader, as the two Aouchiche-Hansen tiers do.
 static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes, const char *refusal) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (e->tier->id != reads) {
-        if (e->tier->id == TIER_DENSE_INV)
+        if (e->tier->id == TIER_DENSE_INV_WIDE)
+            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INV_WIDE engine's record is read with azd_engine_dense_inv_wide_argmin_data";
+        else if (e->tier->id == TIER_DENSE_INV)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_argmin_data";
-        else if (e->tier->ah || reads == TIER_DENSE_AH_WIDE || reads == TIER_DENSE_INV) azd::g_last_error = refusal;
+        else if (e->tier->ah || reads == TIER_DENSE_AH_WIDE || reads == TIER_DENSE_INV || reads == TIER_DENSE_INV_WIDE) azd::g_last_error = refusal;
         return AZD_ERR_UNSUPPORTED;
     }
     AZD_ENTER(e);
@@ -105,6 +108,9 @@ static_assert(sizeof(azd_dense_argmin) == sizeof(azd::DenseArgminRec) && sizeof(
                   offsetof(azd_dense_ah_wide_argmin, node) == offsetof(azd::DenseAhWideArgminRec, node) &&
                   sizeof(azd_dense_inv_argmin) == sizeof(azd::DenseInvArgminRec) && offsetof(azd_dense_inv_argmin, node) == offsetof(azd::DenseInvArgminRec, node) &&
                   offsetof(azd_dense_inv_argmin, inv) == offsetof(azd::DenseInvArgminRec, inv) &&
+                  sizeof(azd_dense_inv_wide_argmin) == sizeof(azd::DenseInvWideArgminRec) &&
+                  offsetof(azd_dense_inv_wide_argmin, node) == offsetof(azd::DenseInvWideArgminRec, node) &&
+                  offsetof(azd_dense_inv_wide_argmin, inv) == offsetof(azd::DenseInvWideArgminRec, inv) &&
                   sizeof(azd_dense_inv_recipe) == sizeof(azd::DenseInvRecipe) && offsetof(azd_dense_inv_recipe, eval_scale) == offsetof(azd::DenseInvRecipe, eval_scale) &&
                   sizeof(azd_dense_inv_cost_t) == sizeof(azd::DenseInvCost) && offsetof(azd_dense_inv_cost_t, eval) == offsetof(azd::DenseInvCost, eval),
               "ABI struct mismatch");
@@ -122,11 +128,14 @@ int azd_engine_dense_ah_wide_argmin_data(azd_engine *e, azd_dense_ah_wide_argmin
 int azd_engine_dense_inv_argmin_data(azd_engine *e, azd_dense_inv_argmin *out) {
     return dense_argmin_read(e, out, TIER_DENSE_INV, sizeof(*out), "azd_engine_dense_inv_argmin_data: not an AZD_ENGINE_DENSE_INV engine");
 }
-// The recipe of an AZD_ENGINE_DENSE_INV engine: checked, then copied behind the per-agent doubles of cur_lambda, where the tier's
-// kernels read it (dense_inv_cost.inc: dense_inv_recipe)
+int azd_engine_dense_inv_wide_argmin_data(azd_engine *e, azd_dense_inv_wide_argmin *out) {
+    return dense_argmin_read(e, out, TIER_DENSE_INV_WIDE, sizeof(*out), "azd_engine_dense_inv_wide_argmin_data: not an AZD_ENGINE_DENSE_INV_WIDE engine");
+}
+// The recipe of an AZD_ENGINE_DENSE_INV engine (either row limit: the indices are checked at the engine's n): checked, then copied
+// behind the per-agent doubles of cur_lambda, where the tier's kernels read it (dense_inv_cost.inc: dense_inv_recipe)
 int azd_engine_set_dense_inv_recipe(azd_engine *e, const azd_dense_inv_recipe *recipe) {
     if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->tier->id != TIER_DENSE_INV) {
+    if (!tier_inv(e->tier)) {
         azd::g_last_error = "azd_engine_set_dense_inv_recipe: not an AZD_ENGINE_DENSE_INV engine";
         return AZD_ERR_UNSUPPORTED;
     }
@@ -147,7 +156,7 @@ int azd_engine_set_dense_inv_recipe(azd_engine *e, const azd_dense_inv_recipe *r
 }
 int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->tier->id != TIER_DENSE_INV) {
+    if (!tier_inv(e->tier)) {
         azd::g_last_error = "azd_engine_dense_inv_agent_cost: not an AZD_ENGINE_DENSE_INV engine";
         return AZD_ERR_UNSUPPORTED;
     }
@@ -171,7 +180,7 @@ int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost
 }
 int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->tier->id == TIER_DENSE_INV) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost";
+    if (tier_inv(e->tier)) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost";
     if (!e->tier->ah) return AZD_ERR_UNSUPPORTED;
     AZD_ENTER(e);
     AZD_HIP(hipStreamSynchronize(e->stream));
@@ -302,7 +311,7 @@ int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t 
     AZD_HIP(hipStreamSynchronize(e->stream));
     const azd::Arenas &a = e->a;
     if (a.space == azd::SPACE_DENSE) { // `parents` receives the neighbourhoods (8 n bytes); masks are kw_host words
-        if (e->tier->id == TIER_DENSE_INV && (lambda_1 || matching_size)) {
+        if (tier_inv(e->tier) && (lambda_1 || matching_size)) {
             azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_INV engine keeps neither (azd_engine_dense_inv_agent_cost)";
             return AZD_ERR_UNSUPPORTED;
         }

@@ -183,6 +183,17 @@ struct DenseInvArgminRec { // device copy of azd_dense_inv_argmin (AZD_ENGINE_DE
     uint32_t node;
 };
 
+struct DenseInvWideArgminRec { // device copy of azd_dense_inv_wide_argmin (AZD_ENGINE_DENSE_INV_WIDE engines: n <= 64, E <= 2016); in argmin_d's place too
+    uint64_t adj[64];
+    uint64_t permitted[32]; // modifiable slots (colex positions) still open
+    double inv[10];
+    int32_t dist_k;
+    uint32_t computed;
+    float cost, eval;
+    int32_t agent;
+    uint32_t node;
+};
+
 struct StatusRec { // small device block copied back after every host-visible call
     unsigned long long improved;   // k_argmin calls that improved the argmin
     unsigned long long expansions; // sum over agents and calls (metric numerator)

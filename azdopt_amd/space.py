@@ -264,11 +264,13 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     first flag; never chosen from N), roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives.
     `cost=InvariantCost(...)`: the weighted-invariant cost (AZD_ENGINE_DENSE_INV, N <= 32, the AH tier's limits): a linear
     combination of ten graph invariants whose weights are given here, at run time; NablaOptimizer.par_new hands the recipe to
-    the engine.  InvariantCost.aouchiche_hansen(n) is the recipe that gives cost="ah"'s trees."""
+    the engine.  InvariantCost.aouchiche_hansen(n) is the recipe that gives cost="ah"'s trees.  `inv_wide=True` (with an
+    InvariantCost only): that cost's 64-row form, N <= 64 (AZD_ENGINE_DENSE_INV_WIDE beside the first flag; never chosen from N),
+    roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives."""
 
     SPACE_ID = _lib.SPACE_DENSE
 
-    def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False):
+    def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False, inv_wide=False):
         self.INV = cost if isinstance(cost, InvariantCost) else None
         if self.INV is not None:
             cost = "inv"
@@ -276,13 +278,16 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
             raise ValueError('cost must be "c21", "ah" or an InvariantCost')
         if ah_wide and cost != "ah":
             raise ValueError('ah_wide=True needs cost="ah" (it is the Aouchiche-Hansen cost\'s 64-row form)')
+        if inv_wide and cost != "inv":
+            raise ValueError("inv_wide=True needs cost=InvariantCost(...) (it is the weighted-invariant cost's 64-row form)")
         self.COST = cost
         self.AH_WIDE = bool(ah_wide)
+        self.INV_WIDE = bool(inv_wide)
         self.n, self.p = int(n), float(p)
         self.E = self.n * (self.n - 1) // 2
         # (an AZD_ENGINE_DENSE_AH engine refuses max_slots > E; a root cannot bring more than E slots anyway)
-        # (... and an AZD_ENGINE_DENSE_AH_WIDE engine max_slots > min(E, 640): its keys are 2, 4 or 10 words)
-        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide else min(int(max_slots), self.E) if cost in ("ah", "inv") else int(max_slots)
+        # (... and an AZD_ENGINE_DENSE_AH_WIDE or AZD_ENGINE_DENSE_INV_WIDE engine max_slots > min(E, 640): its keys are 2, 4 or 10 words)
+        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide or inv_wide else min(int(max_slots), self.E) if cost in ("ah", "inv") else int(max_slots)
         L = _lib.lib()
         self.STATE_DIM = L.azd_dense_state_dim(self.n)
         self.ACTION_DIM = L.azd_dense_action_dim(self.n)
@@ -325,15 +330,19 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
                     cost=np.float32(out.cost), eval=np.float32(out.eval))
 
     def inv_cost(self, adj, cost=None):
-        """The weighted-invariant cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_inv_cost under this
-        space's recipe (or `cost`, another InvariantCost), the same procedure as the device's, bit for bit.
+        """The weighted-invariant cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_inv_cost
+        (azd_dense_inv_cost_wide for an inv_wide space) under this space's recipe (or `cost`, another InvariantCost), the same
+        procedure as the device's, bit for bit.
         -> dict(the ten invariants by name, dist_k, computed, cost, eval)"""
         cost = self.INV if cost is None else cost
         if cost is None:
             raise ValueError("inv_cost: the space has no InvariantCost; pass one")
         a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
         out, r = _lib.DenseInvCost(), cost.recipe()
-        _lib.check(_lib.lib().azd_dense_inv_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_inv_cost")
+        if getattr(self, "INV_WIDE", False):
+            _lib.check(_lib.lib().azd_dense_inv_cost_wide(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_inv_cost_wide")
+        else:
+            _lib.check(_lib.lib().azd_dense_inv_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_inv_cost")
         return dict(InvariantCost.record(out), eval=np.float32(out.eval))
 
 

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """examples/ah.py's loop with the objective taken from the command line: a search over connected graphs on N vertices for a graph
 that minimises a linear combination of graph invariants -- the shape of an AutoGraphiX conjecture, "a combination of invariants is
-bounded below by ..." -- on the MI355X engine's weighted-invariant cost (AZD_ENGINE_DENSE_INV, N <= 32).
+bounded below by ..." -- on the MI355X engine's weighted-invariant cost (AZD_ENGINE_DENSE_INV, N <= 32; with --wide its 64-row
+form, AZD_ENGINE_DENSE_INV_WIDE, N <= 64, which is asked for by name and never chosen from N).
 
     python examples/invariants.py --recipe '{"weights": {"remoteness": 1, "proximity": -1}, "eval_offset": 2, "eval_scale": 0.02}'
-                                  [--n 31] [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
+                                  [--n 31] [--wide] [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
 
 --recipe is a JSON object: "weights" (name -> weight over edges, max_degree, min_degree, diameter, radius, proximity, remoteness,
 avg_distance, adj_eig, dist_eig), and optionally "bias", "adj_index", "dist_index" (a descending index or "ah"), "eval_offset",
@@ -31,6 +32,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--recipe", required=True, help='a JSON object (see above), or "ah"')
     ap.add_argument("--n", type=int, default=31)
+    ap.add_argument("--wide", action="store_true", help="the cost's 64-row form (N <= 64)")
     ap.add_argument("--epochs", type=int, default=250)
     ap.add_argument("--episodes", type=int, default=800)
     ap.add_argument("--batch", type=int, default=512)
@@ -41,7 +43,7 @@ def main():
     args = ap.parse_args()
 
     cost = az.InvariantCost.aouchiche_hansen(args.n) if args.recipe == "ah" else az.InvariantCost.from_dict(json.loads(args.recipe))
-    space = az.DenseGraphSpace(args.n, P, max_slots=args.max_slots, cost=cost)
+    space = az.DenseGraphSpace(args.n, P, max_slots=args.max_slots, cost=cost, inv_wide=args.wide)
     model = az.ActionModel(args.batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=1e-4, l2=1e-6, seed=args.seed,
                            dtype=args.dtype)
     kmin, kmax = space.default_permitted_range()

@@ -319,6 +319,19 @@ typedef struct azd_engine_config {
  * azd_engine_dense_inv_argmin_data (the default and the AH argmin reads, and azd_engine_agent_state's lambda_1 / matching_size, are
  * AZD_ERR_UNSUPPORTED on it and name the right call). */
 #define AZD_ENGINE_DENSE_INV 1024u
+/* Beside AZD_ENGINE_DENSE_INV only (alone, beside AZD_ENGINE_DENSE_AH or AZD_ENGINE_DENSE_AH_WIDE, or on another space:
+ * AZD_ERR_INVALID_ARGUMENT naming the argument): the weighted-invariant cost up to 64 vertices, the dense-graph space's own limit
+ * -- the device procedure with 64 rows (one packed triangle of 2080 doubles serves both spectral passes), in kernels of their own
+ * (dense_inv_wide_kernels.hip); the 32-row kernels and every engine without the flag are what they are without it.  Never chosen
+ * from the sizes.  Limits: 4 <= n <= AZD_DENSE_INV_WIDE_MAX_N, layers <= 1, ActionSet paths, 1 <= max_slots <= min(E, 640) (key
+ * widths 2, 4 and 10; roots of more than 640 slots are out of scope); AZD_ENGINE_EXT_POOL_F32 is accepted beside it.  A wide
+ * engine on n <= 32 is accepted and gives the trees the narrow engine gives; under the Aouchiche-Hansen recipe it gives the trees
+ * of an AZD_ENGINE_DENSE_AH_WIDE engine.  azd_engine_set_dense_inv_recipe (indices checked against 0 .. n - 1 at the engine's n) and
+ * azd_engine_dense_inv_agent_cost serve both tiers.  Its argmin record is azd_dense_inv_wide_argmin, read with
+ * azd_engine_dense_inv_wide_argmin_data (azd_engine_dense_inv_argmin_data is AZD_ERR_UNSUPPORTED on it and names that call, and
+ * the reverse).  Pool step: a searcher wave's LDS block is the AZD_ENGINE_DENSE_AH_WIDE tier's, so a searcher workgroup has the 6
+ * wavefronts it has there (azd_debug_ext_pool_plan reports the plan for such a configuration too). */
+#define AZD_ENGINE_DENSE_INV_WIDE 2048u
 /* Beside AZD_ENGINE_RAMSEY_U64 only (alone, on another space or on a 32-bit tier: AZD_ERR_INVALID_ARGUMENT naming both flags): the
  * 64-bit tier with forbidden cliques up to K8 -- clique sizes 2..AZD_RAMSEY_BIG_CLIQUE_MAX, the reference's count_cliques_inside
  * (bitset_graph/mod.rs:164-185) to depth 6 in kernels of their own; the 64-bit tier's kernels and every engine without the flag are
@@ -360,7 +373,7 @@ typedef struct azd_engine_config {
  * 512 agents 0.99 against 0.52 M expansions/s, r45 at 256 agents 1.03 against 0.31 M on the wide tier and 0.79 against 0.25 M on the
  * 64-bit tier.
  * AZD_SPACE_DENSE: the space's pool step is the searcher-only form and needs no flag of its own, so there this flag stands alone, on
- * all four tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
+ * all five tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
  * this flag beside AZD_ENGINE_NO_PERSISTENT_STEP is AZD_ERR_INVALID_ARGUMENT naming both.  It is a request to the configured pool
  * step, not a form: where the engine's form is not the pool step (fewer than 256 agents without AZD_ENGINE_POOL_STEP) nothing
  * changes and azd_engine_step_form gives the reason it gave.  With it an fp32 MLP is served by the same gathered fp32 GEMMs over the
@@ -773,6 +786,8 @@ int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t
  * and eval are azd_dense_ah_cost's.  The matching number is not in the list: it needs the default cost's per-node matching arena
  * and repair; lambda_1 + matching number stays the default tier's objective. */
 #define AZD_DENSE_INV_MAX_N 32
+/* ... of the 64-row form, which has names of its own: azd_dense_inv_cost_wide, AZD_ENGINE_DENSE_INV_WIDE */
+#define AZD_DENSE_INV_WIDE_MAX_N 64
 #define AZD_DENSE_INV_COUNT 10
 #define AZD_DENSE_INV_INDEX_AH (-1)
 #define AZD_DENSE_INV_NAMES "edges", "max_degree", "min_degree", "diameter", "radius", "proximity", "remoteness", "avg_distance", "adj_eig", "dist_eig"
@@ -794,10 +809,20 @@ typedef struct azd_dense_inv_cost_t {
 /* The cost on the host; needs no GPU.  The graph is checked like azd_dense_ah_cost's (4 <= n <= AZD_DENSE_INV_MAX_N, simple,
  * symmetric, connected), the recipe like azd_engine_set_dense_inv_recipe's: AZD_ERR_INVALID_ARGUMENT naming the argument or field. */
 int azd_dense_inv_cost(const uint64_t *adj, int n, const azd_dense_inv_recipe *recipe, azd_dense_inv_cost_t *out);
+/* The same host function for 4 <= n <= AZD_DENSE_INV_WIDE_MAX_N: the same sequence of IEEE f64 operations, the same graph and
+ * recipe checks (the indices against 0 .. n - 1); at n <= 32 the same bytes as azd_dense_inv_cost.  Beyond 32 vertices one
+ * condition more, on the host and on the device alike: a Householder step whose column has less than 2^-200 below the subdiagonal
+ * (sum of squares) is skipped like one that has nothing there -- the trailing block of a rank-deficient matrix (the adjacency
+ * matrix of a double broom on 50 vertices) is rounding noise that otherwise shrinks into subnormal squares and ends in NaN.  The
+ * entries dropped are below 2^-100, far inside the procedure's backward error. */
+int azd_dense_inv_cost_wide(const uint64_t *adj, int n, const azd_dense_inv_recipe *recipe, azd_dense_inv_cost_t *out);
 /* The device kernel in isolation: the cost of `count` graphs on n vertices (adj[count][n]) under one recipe, one wavefront each,
  * repeated `reps` times; *ms = GPU time of the timed launch.  Graphs and recipe are checked before the device is looked for. */
 int azd_debug_probe_inv_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_inv_recipe *recipe,
                              azd_dense_inv_cost_t *out, float *ms);
+/* ... and the 64-row kernel (AZD_ENGINE_DENSE_INV_WIDE engines' cost), 4 <= n <= AZD_DENSE_INV_WIDE_MAX_N; checked the same way */
+int azd_debug_probe_inv_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_inv_recipe *recipe,
+                                  azd_dense_inv_cost_t *out, float *ms);
 /* The recipe of an AZD_ENGINE_DENSE_INV engine: set once, between azd_engine_create and the first par_new (par_new on such an engine
  * without a recipe is refused and names this call; once par_new has run the recipe is fixed -- a tree's evals must mean one thing --
  * and this call is AZD_ERR_INVALID_ARGUMENT).  AZD_ERR_INVALID_ARGUMENT naming the field: a weight, the bias, eval_offset or
@@ -817,6 +842,19 @@ typedef struct azd_dense_inv_argmin {
     uint32_t node;
 } azd_dense_inv_argmin;
 int azd_engine_dense_inv_argmin_data(azd_engine *e, azd_dense_inv_argmin *out);
+/* ArgminData of an engine with AZD_ENGINE_DENSE_INV_WIDE beside AZD_ENGINE_DENSE_INV (on any other engine: AZD_ERR_UNSUPPORTED) */
+typedef struct azd_dense_inv_wide_argmin {
+    uint64_t adj[64];
+    uint64_t permitted[32]; /* modifiable slots (colex positions) still open; E <= 2016 */
+    double inv[AZD_DENSE_INV_COUNT];
+    int32_t dist_k;
+    uint32_t computed;
+    float cost;
+    float eval;
+    int32_t agent;
+    uint32_t node;
+} azd_dense_inv_wide_argmin;
+int azd_engine_dense_inv_wide_argmin_data(azd_engine *e, azd_dense_inv_wide_argmin *out);
 /* the cost record of agent `agent`'s current state as the engine keeps it (cost and eval recomputed from the kept invariants) */
 int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost_t *out);
 /* Parity probe for the f64 primitives the AH cost depends on bit for bit.  in: 2*n doubles (pairs x, y); out: 3*n doubles per

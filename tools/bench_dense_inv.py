@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measurements of the dense-graph space with the weighted-invariant cost (profiles/r17_dense_inv.txt) on one MI355X.
 
-    python tools/bench_dense_inv.py [--reps 100] [--graphs 512] [--epochs 2] [--episodes 200] [--agents 512]
+    python tools/bench_dense_inv.py [--reps 100] [--graphs 512] [--epochs 2] [--episodes 200] [--agents 512] [--wide]
 
   * microseconds per cost from the probe (azd_debug_probe_inv_cost, `reps` repetitions per wave) at n = 31 on G(31, 0.4) graphs under
     the recipes AH, INT, ADJ and BOTH of tests/dense_inv_ref.py, beside azd_debug_probe_ah_cost on the same graphs in the same
@@ -10,6 +10,10 @@
     1396-256-128-930, par_update_model and the device root policy at the epoch boundary; the first epoch is warm-up and not counted
     -- at N = 31 for an AZD_ENGINE_DENSE_AH engine, an AZD_ENGINE_DENSE_INV engine under the AH recipe, and one under INT (which
     runs no eigen-solve).
+--wide (profiles/r18_dense_inv_wide.txt): the cost's 64-row form -- the wide probe (azd_debug_probe_inv_cost_wide) at n = 50 and
+n = 64 on G(n, 0.4) graphs under AH, INT and BOTH beside azd_debug_probe_ah_cost_wide on the same graphs, which is run twice (the
+difference of the two is the box's run-to-run spread); at n = 32 the wide probe beside the narrow one; and the examples' loop at
+N = 50 for an ah_wide=True engine, an inv_wide=True engine under the AH recipe, and one under INT.
 One line per figure; nothing here asserts."""
 import argparse
 import ctypes as C
@@ -54,8 +58,36 @@ def probes(graphs, reps):
                       % (N, len(graphs), reps, name, ms.value, 1e3 * ms.value / reps, ms.value / ah))
 
 
-def loop_rate(cost, agents, epochs, episodes, seed=0):
-    space = az.DenseGraphSpace(N, P, max_slots=128, cost=cost)
+def probes_wide(n, count, reps):
+    L = az.lib()
+    rng = np.random.default_rng(n)
+    a = np.array([A.gnp_connected(rng, n, P) for _ in range(count)], dtype=np.uint64)
+    ms = C.c_float(0)
+    tag = "probe n=%d graphs=%d reps=%d " % (n, count, reps)
+    for rnd in range(2):  # the second round's figures are printed (the first loads the code objects)
+        ah = []
+        for _ in range(2):
+            out = (_lib.DenseAhCost * count)()
+            _lib.check(L.azd_debug_probe_ah_cost_wide(0, _lib.ptr(a), n, count, reps, out, C.byref(ms)), "probe_ah_cost_wide")
+            ah.append(ms.value)
+        if rnd:
+            print(tag + " azd_debug_probe_ah_cost_wide        %9.3f ms  %8.3f us/cost/wave; again %9.3f ms  %8.3f us/cost/wave  (spread %.3f %%)"
+                  % (ah[0], 1e3 * ah[0] / reps, ah[1], 1e3 * ah[1] / reps, 100.0 * abs(ah[0] - ah[1]) / min(ah)))
+        for name in ("AH", "INT", "BOTH"):
+            rc = cost_of(R.RECIPES[name](n)).recipe()
+            dev = (_lib.DenseInvCost * count)()
+            _lib.check(L.azd_debug_probe_inv_cost_wide(0, _lib.ptr(a), n, count, reps, C.byref(rc), dev, C.byref(ms)), "probe_inv_cost_wide")
+            if rnd:
+                print(tag + " azd_debug_probe_inv_cost_wide %-4s  %9.3f ms  %8.3f us/cost/wave  %.3f x the AH-wide probe (its smaller run)"
+                      % (name, ms.value, 1e3 * ms.value / reps, ms.value / min(ah)))
+            if n <= 32:
+                _lib.check(L.azd_debug_probe_inv_cost(0, _lib.ptr(a), n, count, reps, C.byref(rc), dev, C.byref(ms)), "probe_inv_cost")
+                if rnd:
+                    print(tag + " azd_debug_probe_inv_cost      %-4s  %9.3f ms  %8.3f us/cost/wave  (the 32-row kernel)" % (name, ms.value, 1e3 * ms.value / reps))
+
+
+def loop_rate(cost, agents, epochs, episodes, seed=0, n=N, **wide):
+    space = az.DenseGraphSpace(n, P, max_slots=128, cost=cost, **wide)
     model = az.ActionModel(agents, space.STATE_DIM, space.ACTION_DIM, hidden=(256, 128), lr=1e-4, l2=1e-6, seed=seed)
     kmin, kmax = space.default_permitted_range()
     opt = az.NablaOptimizer.par_new(space, space.generate_roots(seed, agents, kmin=kmin, kmax=kmax), model, agents, **az.tree_capacities(episodes, kmax))
@@ -81,7 +113,18 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--episodes", type=int, default=200)
     ap.add_argument("--agents", type=int, default=512)
+    ap.add_argument("--wide", action="store_true")
     args = ap.parse_args()
+    if args.wide:
+        for n in (50, 64, 32):
+            probes_wide(n, args.graphs, args.reps)
+        for tag, cost, kw in (("cost=\"ah\", ah_wide=True (AZD_ENGINE_DENSE_AH_WIDE)", "ah", dict(ah_wide=True)),
+                              ("InvariantCost AH recipe, inv_wide=True", cost_of(R.recipe_ah(50)), dict(inv_wide=True)),
+                              ("InvariantCost INT recipe, inv_wide=True", cost_of(R.recipe_int(50)), dict(inv_wide=True))):
+            rate, form = loop_rate(cost, args.agents, args.epochs, args.episodes, n=50, **kw)
+            print("loop  n=50 agents=%d episodes=%d fp32 256-128, one call per launch  %-48s %8.3f M expansions/s  form %s"
+                  % (args.agents, args.episodes, tag, rate / 1e6, form[0]), flush=True)
+        return
     rng = np.random.default_rng(31)
     probes([A.gnp_connected(rng, N, P) for _ in range(args.graphs)], args.reps)
     for tag, cost in (("cost=\"ah\" (AZD_ENGINE_DENSE_AH)", "ah"), ("InvariantCost AH recipe", cost_of(R.recipe_ah(N))),
