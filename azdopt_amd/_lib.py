@@ -28,6 +28,7 @@ ENGINE_DENSE_AH_WIDE = 256  # AZD_ENGINE_DENSE_AH_WIDE: beside ENGINE_DENSE_AH o
 ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STEP (Ramsey), alone on SPACE_DENSE: that form with an fp32 model (gathered fp32 GEMMs)
 ENGINE_DENSE_INV = 1024  # AZD_ENGINE_DENSE_INV: the dense-graph space with the weighted-invariant cost (n <= 32; recipe set at run time)
 ENGINE_DENSE_INV_WIDE = 2048  # AZD_ENGINE_DENSE_INV_WIDE: beside ENGINE_DENSE_INV only: the weighted-invariant cost up to n = 64 (64-row kernels)
+ENGINE_DENSE_INVX = 4096  # AZD_ENGINE_DENSE_INVX: the dense-graph space with the extended invariant cost (n <= 32; sixteen invariants, pair terms)
 ENGINE_RAMSEY_BIG_CLIQUES = 512  # AZD_ENGINE_RAMSEY_BIG_CLIQUES: beside ENGINE_RAMSEY_U64 only: clique sizes up to 8 (kernels of their own)
 SPACE_C21 = 1
 SPACE_RAMSEY = 2
@@ -46,6 +47,12 @@ DENSE_INV_COUNT = 10    # AZD_DENSE_INV_COUNT
 DENSE_INV_INDEX_AH = -1  # AZD_DENSE_INV_INDEX_AH: dist_index by the Aouchiche-Hansen rule, k = 2D/3 - 1 (n - 1 when 2D/3 = 0)
 # AZD_DENSE_INV_NAMES: index and name are ABI
 DENSE_INV_NAMES = ("edges", "max_degree", "min_degree", "diameter", "radius", "proximity", "remoteness", "avg_distance", "adj_eig", "dist_eig")
+DENSE_INVX_MAX_N = 32   # AZD_DENSE_INVX_MAX_N: the extended invariant cost (azd_dense_invx_cost)
+DENSE_INVX_COUNT = 16   # AZD_DENSE_INVX_COUNT
+DENSE_INVX_MAX_TERMS = 4  # AZD_DENSE_INVX_MAX_TERMS: pair terms of a recipe
+DENSE_INVX_MUL, DENSE_INVX_DIV = 0, 1  # AZD_DENSE_INVX_MUL / _DIV: a pair term's op
+# AZD_DENSE_INVX_NAMES: index and name are ABI; the first ten are DENSE_INV_NAMES
+DENSE_INVX_NAMES = DENSE_INV_NAMES + ("lap_eig", "slap_eig", "randic", "zagreb1", "zagreb2", "triangles")
 PATH_SET, PATH_SEQUENCE = 0, 1
 ROOT_RULE_THRESHOLD, ROOT_RULE_BEST = 0, 1  # AZD_ROOT_RULE_*
 ROOT_RULES = {"threshold": ROOT_RULE_THRESHOLD, "best": ROOT_RULE_BEST}
@@ -118,6 +125,24 @@ class DenseInvArgmin(C.Structure):  # azd_dense_inv_argmin: ArgminData of a dens
 
 class DenseInvWideArgmin(C.Structure):  # azd_dense_inv_wide_argmin: the same of an engine with ENGINE_DENSE_INV_WIDE (n <= 64, E <= 2016)
     _fields_ = [("adj", C.c_uint64 * 64), ("permitted", C.c_uint64 * 32), ("inv", C.c_double * 10), ("dist_k", C.c_int32),
+                ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
+
+
+class DenseInvxTerm(C.Structure):  # azd_dense_invx_term: coef * (I_a * I_b) or coef * (I_a / I_b)
+    _fields_ = [("coef", C.c_double), ("a", C.c_int), ("b", C.c_int), ("op", C.c_int)]
+
+
+class DenseInvxRecipe(C.Structure):  # azd_dense_invx_recipe: sixteen weights, bias, four spectral indices, the eval's offset and scale, pair terms
+    _fields_ = [("weight", C.c_double * 16), ("bias", C.c_double), ("adj_index", C.c_int), ("dist_index", C.c_int), ("lap_index", C.c_int),
+                ("slap_index", C.c_int), ("eval_offset", C.c_float), ("eval_scale", C.c_float), ("term", DenseInvxTerm * 4), ("n_terms", C.c_int)]
+
+
+class DenseInvxCost(C.Structure):  # azd_dense_invx_cost_t
+    _fields_ = [("inv", C.c_double * 16), ("dist_k", C.c_int), ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float)]
+
+
+class DenseInvxArgmin(C.Structure):  # azd_dense_invx_argmin: ArgminData of a dense engine with the extended invariant cost
+    _fields_ = [("adj", C.c_uint64 * 32), ("permitted", C.c_uint64 * 8), ("inv", C.c_double * 16), ("dist_k", C.c_int32),
                 ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
 
 
@@ -263,6 +288,11 @@ def lib():
     sig("azd_dense_inv_cost_wide", C.c_int, vp, C.c_int, C.POINTER(DenseInvRecipe), C.POINTER(DenseInvCost))
     sig("azd_debug_probe_inv_cost_wide", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DenseInvRecipe), vp, f32p)
     sig("azd_engine_dense_inv_wide_argmin_data", C.c_int, vp, C.POINTER(DenseInvWideArgmin))
+    sig("azd_dense_invx_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvxRecipe), C.POINTER(DenseInvxCost))
+    sig("azd_debug_probe_invx_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DenseInvxRecipe), vp, f32p)
+    sig("azd_engine_set_dense_invx_recipe", C.c_int, vp, C.POINTER(DenseInvxRecipe))
+    sig("azd_engine_dense_invx_argmin_data", C.c_int, vp, C.POINTER(DenseInvxArgmin))
+    sig("azd_engine_dense_invx_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvxCost))
     sig("azd_engine_set_dense_inv_recipe", C.c_int, vp, C.POINTER(DenseInvRecipe))
     sig("azd_engine_dense_inv_argmin_data", C.c_int, vp, C.POINTER(DenseInvArgmin))
     sig("azd_engine_dense_inv_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvCost))

@@ -441,4 +441,138 @@ void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, De
     out->eval = r.eval_scale * (out->cost + r.eval_offset);
 }
 
+// ---- extended invariant cost (c21_host.h: DenseInvxRecipe; AZD_ENGINE_DENSE_INVX): the host form of dense_invx_cost_wave
+// (dense_invx_cost.inc), the same IEEE operations in the same order, over the stages above.
+const char *dense_invx_check_graph(const uint64_t *adj, int n) {
+    return ah_check_graph(adj, n, DENSE_INVX_MAX_N, "n: the extended invariant cost needs 4 <= n <= 32 (AZD_DENSE_INVX_MAX_N)");
+}
+const char *dense_invx_check_recipe(const DenseInvxRecipe *r, int n) {
+    if (!r) return "recipe: null";
+    bool any = false;
+    for (int i = 0; i < DENSE_INVX_COUNT; ++i) {
+        if (!std::isfinite(r->weight[i])) return "weight: every weight must be finite";
+        any = any || r->weight[i] != 0.0;
+    }
+    if (r->n_terms < 0 || r->n_terms > DENSE_INVX_MAX_TERMS) return "n_terms: must be in 0 .. 4 (AZD_DENSE_INVX_MAX_TERMS)";
+    for (int t = 0; t < r->n_terms; ++t) {
+        const DenseInvxTerm &p = r->term[t];
+        if (!std::isfinite(p.coef)) return "term.coef: every coefficient must be finite";
+        if (p.a < 0 || p.a >= DENSE_INVX_COUNT) return "term.a: must be in 0 .. 15 (an invariant's index)";
+        if (p.b < 0 || p.b >= DENSE_INVX_COUNT) return "term.b: must be in 0 .. 15 (an invariant's index)";
+        if (p.op != DENSE_INVX_MUL && p.op != DENSE_INVX_DIV) return "term.op: must be AZD_DENSE_INVX_MUL or AZD_DENSE_INVX_DIV";
+        if (p.op == DENSE_INVX_DIV && !((DENSE_INVX_DIVISORS >> p.b) & 1u))
+            return "term.b: a divisor must be positive on every connected graph: indices 0 .. 7, 12 (randic), 13 (zagreb1), 14 (zagreb2)";
+        any = any || p.coef != 0.0;
+    }
+    if (!any) return "weight: all sixteen weights and all coefficients are zero";
+    if (!std::isfinite(r->bias)) return "bias: must be finite";
+    if (!std::isfinite(r->eval_offset)) return "eval_offset: must be finite";
+    if (!std::isfinite(r->eval_scale) || r->eval_scale == 0.0f) return "eval_scale: must be finite and not zero";
+    if (r->adj_index < 0 || r->adj_index > n - 1) return "adj_index: must be in 0 .. n - 1 (descending index into the adjacency spectrum)";
+    if (r->dist_index != DENSE_INV_INDEX_AH && (r->dist_index < 0 || r->dist_index > n - 1))
+        return "dist_index: must be in 0 .. n - 1 (descending index into the distance spectrum) or AZD_DENSE_INV_INDEX_AH";
+    if (r->lap_index < 0 || r->lap_index > n - 1) return "lap_index: must be in 0 .. n - 1 (descending index into the Laplacian spectrum)";
+    if (r->slap_index < 0 || r->slap_index > n - 1) return "slap_index: must be in 0 .. n - 1 (descending index into the signless-Laplacian spectrum)";
+    return nullptr;
+}
+void dense_invx_cost_host(const uint64_t *adj, int n, const DenseInvxRecipe &r, DenseInvxCost *out) {
+    constexpr int P = DENSE_AH_STRIDE;
+    constexpr int MAX_N = DENSE_AH_WIDE_MAX_N;
+    const uint32_t need = dense_invx_needed(r);
+    const auto needs = [need](int i) { return ((need >> i) & 1u) != 0u; };
+    const bool need_dist = needs(DENSE_INV_DIST_EIG);
+    std::vector<double> Am((size_t)MAX_N * P, 0.0);
+    double *A = Am.data();
+    int trans[MAX_N], ecc[MAX_N], deg[MAX_N];
+    ah_bfs(adj, n, need_dist ? A : nullptr, trans, ecc);
+    int m2 = 0, max_deg = 0, min_deg = 0x7FFFFFFF, diam = 0, rad = 0x7FFFFFFF, min_t = 0x7FFFFFFF, max_t = 0, sum_t = 0;
+    for (int u = 0; u < n; ++u) {
+        deg[u] = __builtin_popcountll(adj[u]);
+        m2 += deg[u];
+        max_deg = deg[u] > max_deg ? deg[u] : max_deg;
+        min_deg = deg[u] < min_deg ? deg[u] : min_deg;
+        diam = ecc[u] > diam ? ecc[u] : diam;
+        rad = ecc[u] < rad ? ecc[u] : rad;
+        min_t = trans[u] < min_t ? trans[u] : min_t;
+        max_t = trans[u] > max_t ? trans[u] : max_t;
+        sum_t += trans[u];
+    }
+    const int q23 = (2 * diam) / 3;
+    const int dist_k = r.dist_index != DENSE_INV_INDEX_AH ? r.dist_index : q23 >= 1 ? q23 - 1 : n - 1;
+    double I[DENSE_INVX_COUNT];
+    I[0] = (double)(m2 / 2);
+    I[1] = (double)max_deg;
+    I[2] = (double)min_deg;
+    I[3] = (double)diam;
+    I[4] = (double)rad;
+    I[5] = (double)min_t / (double)(n - 1);
+    I[6] = (double)max_t / (double)(n - 1);
+    I[7] = (double)sum_t / (double)(n * (n - 1));
+    for (int i = DENSE_INV_ADJ_EIG; i < DENSE_INVX_COUNT; ++i) I[i] = 0.0;
+    // the degree-based invariants: vertex u over its neighbours v < u, ascending (every edge once)
+    if (need >> DENSE_INVX_RANDIC) {
+        double part[64];
+        int z1 = 0, z2 = 0, tri = 0;
+        for (int u = 0; u < 64; ++u) part[u] = 0.0;
+        for (int u = 0; u < n; ++u) {
+            z1 += deg[u] * deg[u];
+            double rr = 0.0, cc = 0.0;
+            for (int v = 0; v < u; ++v)
+                if ((adj[u] >> v) & 1ull) {
+                    const double s = std::sqrt((double)(deg[u] * deg[v]));
+                    const double term = 1.0 / s;
+                    // TwoSum (Knuth): t + e == rr + term exactly; the rounding errors are summed beside the sum
+                    const double t = rr + term;
+                    const double bp = t - rr;
+                    const double ap = t - bp;
+                    const double e = (rr - ap) + (term - bp);
+                    cc = cc + e;
+                    rr = t;
+                    z2 += deg[u] * deg[v];
+                    tri += __builtin_popcountll(adj[u] & adj[v]);
+                }
+            part[u] = rr + cc;
+        }
+        if (needs(DENSE_INVX_RANDIC)) I[DENSE_INVX_RANDIC] = ah_tree64(part);
+        if (needs(DENSE_INVX_ZAGREB1)) I[DENSE_INVX_ZAGREB1] = (double)z1;
+        if (needs(DENSE_INVX_ZAGREB2)) I[DENSE_INVX_ZAGREB2] = (double)z2;
+        if (needs(DENSE_INVX_TRIANGLES)) I[DENSE_INVX_TRIANGLES] = (double)(tri / 3);
+    }
+    double diag[MAX_N], sub[MAX_N];
+    // one matrix, up to four passes: the distance pass on the rows the BFS left, then the adjacency, Laplacian and signless-Laplacian
+    // refills from the bitsets and the degrees
+    if (need_dist) {
+        ah_householder(A, n, diag, sub);
+        I[DENSE_INV_DIST_EIG] = ah_multisection(diag, sub, n, dist_k);
+    }
+    for (int pass = 1; pass < 4; ++pass) {
+        const int which = pass == 1 ? DENSE_INV_ADJ_EIG : pass == 2 ? DENSE_INVX_LAP_EIG : DENSE_INVX_SLAP_EIG;
+        if (!needs(which)) continue;
+        const double off = pass == 2 ? -1.0 : 1.0;
+        for (int u = 0; u < n; ++u)
+            for (int v = 0; v < n; ++v) A[u * P + v] = pass > 1 && u == v ? (double)deg[u] : (adj[u] >> v) & 1ull ? off : 0.0;
+        ah_householder(A, n, diag, sub);
+        I[which] = ah_multisection(diag, sub, n, pass == 1 ? r.adj_index : pass == 2 ? r.lap_index : r.slap_index);
+    }
+    double c = r.bias;
+    for (int i = 0; i < DENSE_INVX_COUNT; ++i) {
+        out->inv[i] = I[i];
+        if (r.weight[i] != 0.0) {
+            const double term = r.weight[i] * I[i];
+            c = c + term;
+        }
+    }
+    for (int t = 0; t < r.n_terms; ++t) {
+        const DenseInvxTerm &p = r.term[t];
+        if (p.coef == 0.0) continue;
+        const double v = p.op == DENSE_INVX_DIV ? I[p.a] / I[p.b] : I[p.a] * I[p.b];
+        const double term = p.coef * v;
+        c = c + term;
+    }
+    out->dist_k = dist_k;
+    out->computed = DENSE_INV_ALWAYS | need;
+    out->cost = (float)c;
+    out->eval = r.eval_scale * (out->cost + r.eval_offset);
+}
+
 } // namespace azd

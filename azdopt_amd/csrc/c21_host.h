@@ -122,4 +122,56 @@ const char *dense_inv_check_graph_wide(const uint64_t *adj, int n); // 4 <= n <=
 // n <= DENSE_INV_WIDE_MAX_N (one function behind azd_dense_inv_cost and azd_dense_inv_cost_wide: the limit is the callers' check)
 void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, DenseInvCost *out);
 
+// Extended invariant cost of a connected graph on 4 <= n <= DENSE_INVX_MAX_N vertices (BUILD-DEFINED; DESIGN.md "The extended
+// invariant cost"; AZD_ENGINE_DENSE_INVX): sixteen invariants -- index and name are ABI.  0 .. 9 are the weighted-invariant cost's;
+//   10 lap_eig = eigenvalue of L = D - A at descending index lap_index   11 slap_eig = eigenvalue of Q = D + A at slap_index
+//   12 randic = sum_{uv in E} 1 / sqrt(d_u d_v): per vertex u, over its neighbours v < u ascending, x = 1.0 / sqrt((double)(d_u d_v)),
+//      (r, e) = TwoSum(r, x), c = c + e, one IEEE operation at a time (a compensated sum: the vertex's part r + c is right to an ulp;
+//      plain r = r + x is off by four ulps of the sum on K_27, whose 351 equal terms round the same way, and misses the
+//      n 2^-52 of math.fsum that the invariant is held to); then the balanced tree over the 64 lanes' parts (vertices >= n hold 0)
+//   13 zagreb1 = sum_u d_u^2   14 zagreb2 = sum_{uv in E} d_u d_v   15 triangles = (sum_{uv in E} popcount(N(u) & N(v))) / 3   (integers)
+//   c = bias; the sixteen weights as above; then for t = 0 .. n_terms - 1 in order, if coef_t != 0: v = I_a * I_b or I_a / I_b,
+//   c = c + coef_t * v (three IEEE f64 operations); cost = (float)c; eval = eval_scale * (cost + eval_offset)
+// 0 .. 7 are always computed; each of 8 .. 15 only when its weight is not zero or a pair term with a non-zero coefficient names it
+// (else 0.0, bit clear).  A divisor is one of DENSE_INVX_DIVISORS: positive on every connected graph with n >= 4, so the cost is
+// finite.  With weights 10 .. 15 zero and no term the sequence of operations is dense_inv_cost_host's.
+constexpr int DENSE_INVX_MAX_N = 32;
+constexpr int DENSE_INVX_COUNT = 16;
+constexpr int DENSE_INVX_LAP_EIG = 10, DENSE_INVX_SLAP_EIG = 11, DENSE_INVX_RANDIC = 12, DENSE_INVX_ZAGREB1 = 13, DENSE_INVX_ZAGREB2 = 14,
+              DENSE_INVX_TRIANGLES = 15;
+constexpr int DENSE_INVX_MAX_TERMS = 4;
+constexpr int DENSE_INVX_MUL = 0, DENSE_INVX_DIV = 1;
+constexpr uint32_t DENSE_INVX_DIVISORS = 0xFFu | 1u << DENSE_INVX_RANDIC | 1u << DENSE_INVX_ZAGREB1 | 1u << DENSE_INVX_ZAGREB2;
+struct DenseInvxTerm {
+    double coef;
+    int a, b, op;
+};
+struct DenseInvxRecipe {
+    double weight[DENSE_INVX_COUNT];
+    double bias;
+    int adj_index, dist_index, lap_index, slap_index;
+    float eval_offset, eval_scale;
+    DenseInvxTerm term[DENSE_INVX_MAX_TERMS];
+    int n_terms;
+};
+struct DenseInvxCost {
+    double inv[DENSE_INVX_COUNT];
+    int dist_k;
+    uint32_t computed;
+    float cost, eval;
+};
+// bits 8 .. 15 of `computed` under a checked recipe: the invariants its weights and its pair terms ask for (constexpr: the device
+// code calls it too)
+constexpr uint32_t dense_invx_needed(const DenseInvxRecipe &r) {
+    uint32_t m = 0;
+    for (int i = DENSE_INV_ADJ_EIG; i < DENSE_INVX_COUNT; ++i) m |= r.weight[i] != 0.0 ? 1u << i : 0u;
+    for (int t = 0; t < r.n_terms; ++t)
+        if (r.term[t].coef != 0.0) m |= (1u << r.term[t].a | 1u << r.term[t].b) & ~DENSE_INV_ALWAYS;
+    return m;
+}
+// nullptr when the recipe is acceptable for graphs on n vertices, else what is wrong with it (a field name leads the text)
+const char *dense_invx_check_recipe(const DenseInvxRecipe *r, int n);
+const char *dense_invx_check_graph(const uint64_t *adj, int n); // 4 <= n <= DENSE_INVX_MAX_N, in this cost's words
+void dense_invx_cost_host(const uint64_t *adj, int n, const DenseInvxRecipe &r, DenseInvxCost *out);
+
 } // namespace azd

@@ -70,7 +70,7 @@ static const ExtPoolForm *ext_pool_form(bool dense_space) {
     return dense_space ? &dense : &ramsey;
 }
 
-// The ten kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
+// The eleven kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
 // parts: c21 has no searcher-only pool step; the 64-bit Ramsey tier's is joined to the three parts of its phase unit's table.
 static const TierDesc *tier_desc(Tier t) {
     static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops(), PoolSearchOps{}};
@@ -115,13 +115,17 @@ static const TierDesc *tier_desc(Tier t) {
         // AZD_ENGINE_DENSE_INV_WIDE beside it: the same record per agent over the 64-row kernels (dense_inv_wide_kernels.hip)
         {TIER_DENSE_INV_WIDE, SPACE_DENSE, &dense_inv_wide_ops(), xd, sizeof(DenseInvWideArgminRec), 0, false, true, false, DENSE_INV_COUNT, 2,
          (int)((sizeof(DenseInvRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        // AZD_ENGINE_DENSE_INVX: the extended invariant cost (dense_invx_kernels.hip): sixteen doubles and two ints per agent, the recipe behind the doubles
+        {TIER_DENSE_INVX, SPACE_DENSE, &dense_invx_ops(), xd, sizeof(DenseInvxArgminRec), 0, false, true, false, DENSE_INVX_COUNT, 2,
+         (int)((sizeof(DenseInvxRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
     };
     return &tiers[t];
 }
 // the tier of a configuration that check_engine_config has accepted: the flags name it, never the sizes
 const TierDesc *engine_tier(const azd_engine_config *cfg) {
     if (cfg->space_id == AZD_SPACE_DENSE)
-        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_INV_WIDE  ? TIER_DENSE_INV_WIDE
+        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_INVX      ? TIER_DENSE_INVX
+                         : cfg->flags & AZD_ENGINE_DENSE_INV_WIDE ? TIER_DENSE_INV_WIDE
                          : cfg->flags & AZD_ENGINE_DENSE_INV     ? TIER_DENSE_INV
                          : cfg->flags & AZD_ENGINE_DENSE_AH_WIDE ? TIER_DENSE_AH_WIDE
                          : cfg->flags & AZD_ENGINE_DENSE_AH      ? TIER_DENSE_AH
@@ -418,7 +422,18 @@ int check_engine_config(const azd_engine_config *cfg) {
                       "AZD_SPACE_RAMSEY with max_slots > 0, whose kernels for clique sizes up to 8 it asks for)");
     const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
     const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
-    if (cfg->flags & AZD_ENGINE_DENSE_INV_WIDE) { // the weighted-invariant cost's 64-row form: a second flag beside the first, never a cost of its own
+    if (cfg->flags & AZD_ENGINE_DENSE_INVX) { // the extended invariant cost: a tier of its own, asked for by name; the INV tier's limits
+        const char *bad = dense_ah || dense_ah_wide || (cfg->flags & (AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE))
+                              ? "flags: AZD_ENGINE_DENSE_INVX is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
+                                "AZD_ENGINE_DENSE_INV or AZD_ENGINE_DENSE_INV_WIDE (the Aouchiche-Hansen cost and the weighted-invariant cost are among its recipes)"
+                          : !dense                                       ? "space_id: AZD_ENGINE_DENSE_INVX needs the dense-graph space (AZD_SPACE_DENSE)"
+                          : cfg->n < 4 || cfg->n > AZD_DENSE_INVX_MAX_N  ? "n: the extended invariant cost needs 4 <= n <= 32 (AZD_DENSE_INVX_MAX_N)"
+                          : cfg->layers > 1                              ? "layers: AZD_ENGINE_DENSE_INVX engines take no Layered wrapper (layers <= 1)"
+                          : cfg->max_slots > dense_edges(cfg->n)         ? "max_slots: AZD_ENGINE_DENSE_INVX needs max_slots <= E = n (n - 1) / 2"
+                          : cfg->path_kind != AZD_PATH_SET               ? "path_kind: AZD_ENGINE_DENSE_INVX engines keep ActionSet paths (AZD_PATH_SET)"
+                                                                         : nullptr;
+        if (bad) return refuse(bad);
+    } else if (cfg->flags & AZD_ENGINE_DENSE_INV_WIDE) { // the weighted-invariant cost's 64-row form: a second flag beside the first, never a cost of its own
         const char *bad = !(cfg->flags & AZD_ENGINE_DENSE_INV)
                               ? "flags: AZD_ENGINE_DENSE_INV_WIDE is valid only beside AZD_ENGINE_DENSE_INV (the weighted-invariant cost whose 64-row form it asks for)"
                           : dense_ah || dense_ah_wide
@@ -796,7 +811,8 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         // cost's type, as argmin_r_recs counts them for the Ramsey tiers -- one for every tier but the 64-row weighted-invariant
         // one, whose 64 rows, 32 slot words and ten invariants come to 872 bytes where the default cost's record has 856)
         static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseAhWideArgminRec) <= sizeof(azd::DenseArgminRec) &&
-                          sizeof(azd::DenseInvArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseInvWideArgminRec) <= 2 * sizeof(azd::DenseArgminRec),
+                          sizeof(azd::DenseInvArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseInvWideArgminRec) <= 2 * sizeof(azd::DenseArgminRec) &&
+                          sizeof(azd::DenseInvxArgminRec) <= sizeof(azd::DenseArgminRec),
                       "an AH or INV engine's argmin record lives in argmin_d's allocation");
         AZD_ST(e->alloc(&a.argmin_d, (tier->argmin_bytes + sizeof(azd::DenseArgminRec) - 1) / sizeof(azd::DenseArgminRec)));
         if (tier->id == TIER_DENSE) AZD_ST(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH and the weighted-invariant cost keep nothing per node)
@@ -909,6 +925,10 @@ int azd_engine_par_new_begin(azd_engine *e, const uint8_t *parents, const uint64
     if (!e || !parents || !permitted) return AZD_ERR_INVALID_ARGUMENT;
     if (tier_inv(e->tier) && !e->inv_recipe_set) {
         azd::g_last_error = "par_new: an AZD_ENGINE_DENSE_INV engine has no cost before azd_engine_set_dense_inv_recipe has given it its recipe";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (e->tier->id == TIER_DENSE_INVX && !e->inv_recipe_set) {
+        azd::g_last_error = "par_new: an AZD_ENGINE_DENSE_INVX engine has no cost before azd_engine_set_dense_invx_recipe has given it its recipe";
         return AZD_ERR_INVALID_ARGUMENT;
     }
     AZD_ENTER(e);

@@ -194,6 +194,17 @@ struct DenseInvWideArgminRec { // device copy of azd_dense_inv_wide_argmin (AZD_
     uint32_t node;
 };
 
+struct DenseInvxArgminRec { // device copy of azd_dense_invx_argmin (AZD_ENGINE_DENSE_INVX engines: n <= 32, E <= 496); in argmin_d's place too
+    uint64_t adj[32];
+    uint64_t permitted[8]; // modifiable slots (colex positions) still open
+    double inv[16];        // the sixteen invariants (c21_host.h: DenseInvxCost), 0.0 where not computed
+    int32_t dist_k;
+    uint32_t computed;
+    float cost, eval;
+    int32_t agent;
+    uint32_t node;
+};
+
 struct StatusRec { // small device block copied back after every host-visible call
     unsigned long long improved;   // k_argmin calls that improved the argmin
     unsigned long long expansions; // sum over agents and calls (metric numerator)

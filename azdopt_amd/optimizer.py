@@ -57,6 +57,21 @@ class DenseAhArgminData:
         self.agent, self.node = rec.agent, rec.node
 
 
+class DenseInvxArgminData:
+    """az-discrete-opt/src/log.rs:1-11 for the dense-graph space with the extended invariant cost: state = neighbourhoods + open
+    slots, cost = the sixteen invariants by name, dist_k, computed, cost"""
+
+    def __init__(self, rec, space):
+        from .space import InvariantCostX
+        slots = np.zeros(space.KEY_WORDS, np.uint64)
+        ow = (space.E + 63) // 64
+        slots[:ow] = rec.permitted[:ow]
+        self.state = dict(adj=np.array(rec.adj[:space.n], np.uint64), permitted=slots)
+        self.cost = InvariantCostX.record(rec)
+        self.eval = np.float32(rec.eval)
+        self.agent, self.node = rec.agent, rec.node
+
+
 class DenseInvArgminData:
     """az-discrete-opt/src/log.rs:1-11 for the dense-graph space with the weighted-invariant cost: state = neighbourhoods + open
     slots, cost = the ten invariants by name, dist_k, computed, cost"""
@@ -115,8 +130,8 @@ class NablaOptimizer:
         launch per phase.  ext_pool_step=True (Ramsey spaces with MAX_SLOTS > 0 only, a bf16 ActionModel): the searcher-only pool
         step with the model's batched GEMMs beside it (ENGINE_EXT_POOL_STEP); step_form() says whether it ran.  ext_pool_f32=True
         beside it (ENGINE_EXT_POOL_F32; alone the engine refuses it on c21 and the Ramsey spaces): that form also with an fp32
-        ActionModel.  On a DenseGraphSpace, whose pool step IS that form, ext_pool_f32=True stands alone (all five tiers: default
-        cost, cost="ah", ah_wide=True, cost=InvariantCost(...), inv_wide=True): where the engine's configured form is the pool step (256 agents or more, or pool_step=True)
+        ActionModel.  On a DenseGraphSpace, whose pool step IS that form, ext_pool_f32=True stands alone (all six tiers: default
+        cost, cost="ah", ah_wide=True, cost=InvariantCost(...), inv_wide=True, cost=InvariantCostX(...)): where the engine's configured form is the pool step (256 agents or more, or pool_step=True)
         an fp32 ActionModel is served by the gathered fp32 GEMMs instead of falling back to one launch per phase -- same
         predictions bit for bit; with persistent=False beside it the engine refuses it.  On an MI355X with a whole epoch per launch:
         AH N = 31 2.6 against 0.82 M expansions/s at 512 agents, 5.5 against 4.7 M at 4096; config E's shape (8192 agents,
@@ -145,6 +160,8 @@ class NablaOptimizer:
                 cfg.flags |= _lib.ENGINE_DENSE_INV
                 if getattr(space, "INV_WIDE", False):
                     cfg.flags |= _lib.ENGINE_DENSE_INV_WIDE
+            if getattr(space, "COST", "c21") == "invx":
+                cfg.flags |= _lib.ENGINE_DENSE_INVX
         if space.SPACE_ID == _lib.SPACE_RAMSEY:
             cfg.max_slots = getattr(space, "MAX_SLOTS", 0)
             if getattr(space, "U64", False):
@@ -161,6 +178,9 @@ class NablaOptimizer:
         if cfg.flags & _lib.ENGINE_DENSE_INV:  # the recipe is fixed before par_new computes the roots' evals with it
             r = space.INV.recipe()
             _lib.check(self._L.azd_engine_set_dense_inv_recipe(self._h, C.byref(r)), "set_dense_inv_recipe")
+        if cfg.flags & _lib.ENGINE_DENSE_INVX:  # (likewise)
+            r = space.INVX.recipe()
+            _lib.check(self._L.azd_engine_set_dense_invx_recipe(self._h, C.byref(r)), "set_dense_invx_recipe")
 
     def __del__(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -310,6 +330,10 @@ class NablaOptimizer:
                 rec = _lib.DenseInvArgmin()
                 _lib.check(self._L.azd_engine_dense_inv_argmin_data(self._h, C.byref(rec)), "dense_inv_argmin_data")
             return DenseInvArgminData(rec, self.space)
+        if self.space.SPACE_ID == _lib.SPACE_DENSE and getattr(self.space, "COST", "c21") == "invx":
+            rec = _lib.DenseInvxArgmin()
+            _lib.check(self._L.azd_engine_dense_invx_argmin_data(self._h, C.byref(rec)), "dense_invx_argmin_data")
+            return DenseInvxArgminData(rec, self.space)
         if self.space.SPACE_ID == _lib.SPACE_DENSE:
             rec = _lib.DenseArgmin()
             _lib.check(self._L.azd_engine_dense_argmin_data(self._h, C.byref(rec)), "dense_argmin_data")
@@ -421,6 +445,13 @@ class NablaOptimizer:
             c = _lib.DenseInvCost()
             _lib.check(self._L.azd_engine_dense_inv_agent_cost(self._h, agent, C.byref(c)), "dense_inv_agent_cost")
             return dict(parents=parents, permitted=permitted, path=path, state_pos=pos.value, **InvariantCost.record(c))
+        if self.space.SPACE_ID == _lib.SPACE_DENSE and getattr(self.space, "COST", "c21") == "invx":
+            from .space import InvariantCostX
+            _lib.check(self._L.azd_engine_agent_state(self._h, agent, _lib.ptr(parents), _lib.ptr(permitted), _lib.ptr(path),
+                                                      C.byref(pos), None, None), "agent_state")
+            c = _lib.DenseInvxCost()
+            _lib.check(self._L.azd_engine_dense_invx_agent_cost(self._h, agent, C.byref(c)), "dense_invx_agent_cost")
+            return dict(parents=parents, permitted=permitted, path=path, state_pos=pos.value, **InvariantCostX.record(c))
         _lib.check(self._L.azd_engine_agent_state(self._h, agent, _lib.ptr(parents), _lib.ptr(permitted), _lib.ptr(path),
                                                   C.byref(pos), C.byref(lam), C.byref(mu)), "agent_state")
         return dict(parents=parents, permitted=permitted, path=path, state_pos=pos.value, lambda1=lam.value, matching=mu.value)

@@ -248,6 +248,71 @@ class InvariantCost:
         return out
 
 
+class InvariantCostX:
+    """A recipe of the dense-graph space's extended invariant cost (AZD_ENGINE_DENSE_INVX; azd_dense_invx_recipe): sixteen
+    invariants of a connected graph -- InvariantCost's ten, then
+        lap_eig (eigenvalue of D - A at descending index lap_index; n - 2 is the algebraic connectivity), slap_eig (of D + A at
+        slap_index), randic, zagreb1, zagreb2, triangles
+    -- combined with weights and up to four pair terms `terms=[(coef, "a", "*" | "/", "b"), ...]`:
+    cost = (f32)(bias + sum of weight * invariant over the non-zero weights, in order, + sum of coef * (a * b or a / b), in order);
+    eval = eval_scale * (cost + eval_offset).  A divisor is one of the invariants that are positive on every connected graph
+    (DIVISORS).  An eigenvalue, randic, a Zagreb index or the triangle count is computed only when a non-zero weight or coefficient
+    asks for it.  With no such weight and no term it is InvariantCost's cost, bit for bit."""
+
+    NAMES = _lib.DENSE_INVX_NAMES
+    DIVISORS = _lib.DENSE_INVX_NAMES[:8] + ("randic", "zagreb1", "zagreb2")
+    OPS = {"*": _lib.DENSE_INVX_MUL, "/": _lib.DENSE_INVX_DIV}
+
+    def __init__(self, weights, terms=(), bias=0.0, adj_index=0, dist_index="ah", lap_index=0, slap_index=0, eval_offset=0.0, eval_scale=1.0):
+        terms = [(float(c), str(a), str(op), str(b)) for c, a, op, b in terms]
+        unknown = sorted((set(weights) | {x for _, a, _, b in terms for x in (a, b)}) - set(self.NAMES))
+        if unknown:
+            raise ValueError("unknown invariant(s) %s: the names are %s" % (", ".join(unknown), ", ".join(self.NAMES)))
+        if len(terms) > _lib.DENSE_INVX_MAX_TERMS:
+            raise ValueError("terms: at most %d pair terms" % _lib.DENSE_INVX_MAX_TERMS)
+        for _, _, op, b in terms:
+            if op not in self.OPS:
+                raise ValueError('terms: the operation is "*" or "/", not %r' % (op,))
+            if op == "/" and b not in self.DIVISORS:
+                raise ValueError("terms: %s cannot divide (it can be zero); the divisors are %s" % (b, ", ".join(self.DIVISORS)))
+        self.weights = {k: float(v) for k, v in weights.items()}
+        self.terms = terms
+        self.bias, self.adj_index, self.lap_index, self.slap_index = float(bias), int(adj_index), int(lap_index), int(slap_index)
+        self.dist_index = _lib.DENSE_INV_INDEX_AH if dist_index in ("ah", None) else int(dist_index)
+        self.eval_offset, self.eval_scale = np.float32(eval_offset), np.float32(eval_scale)
+
+    @classmethod
+    def from_invariant_cost(cls, cost):
+        """the recipe that gives an InvariantCost's cost, eval and trees bit for bit"""
+        return cls(cost.weights, bias=cost.bias, adj_index=cost.adj_index, dist_index=cost.dist_index, eval_offset=cost.eval_offset,
+                   eval_scale=cost.eval_scale)
+
+    @classmethod
+    def from_dict(cls, d):
+        """from a JSON object: {"weights": {...}, "terms": [[coef, "a", "*" | "/", "b"], ...], "bias": .., "adj_index": ..,
+        "dist_index": .. | "ah", "lap_index": .., "slap_index": .., "eval_offset": .., "eval_scale": ..}"""
+        keys = ("terms", "bias", "adj_index", "dist_index", "lap_index", "slap_index", "eval_offset", "eval_scale")
+        return cls(d.get("weights", {}), **{k: d[k] for k in keys if k in d})
+
+    def recipe(self):
+        r = _lib.DenseInvxRecipe()
+        for i, name in enumerate(self.NAMES):
+            r.weight[i] = self.weights.get(name, 0.0)
+        r.bias, r.adj_index, r.dist_index, r.lap_index, r.slap_index = self.bias, self.adj_index, self.dist_index, self.lap_index, self.slap_index
+        r.eval_offset, r.eval_scale = float(self.eval_offset), float(self.eval_scale)
+        for t, (coef, a, op, b) in enumerate(self.terms):
+            r.term[t].coef, r.term[t].a, r.term[t].b, r.term[t].op = coef, self.NAMES.index(a), self.NAMES.index(b), self.OPS[op]
+        r.n_terms = len(self.terms)
+        return r
+
+    @classmethod
+    def record(cls, rec):
+        """an azd_dense_invx_cost_t (or the cost part of an argmin record) as a dict: the invariants by name, dist_k, computed, cost"""
+        out = {name: rec.inv[i] for i, name in enumerate(cls.NAMES)}
+        out.update(dist_k=rec.dist_k, computed=rec.computed, cost=np.float32(rec.cost))
+        return out
+
+
 class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     """Connected graphs on N <= 64 vertices; an action adds an absent edge or deletes a present non-cut edge, every edge
     slot at most once (BASELINE configs[4], N = 50).  BUILD-DEFINED: the reference has the pieces
@@ -266,16 +331,23 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     combination of ten graph invariants whose weights are given here, at run time; NablaOptimizer.par_new hands the recipe to
     the engine.  InvariantCost.aouchiche_hansen(n) is the recipe that gives cost="ah"'s trees.  `inv_wide=True` (with an
     InvariantCost only): that cost's 64-row form, N <= 64 (AZD_ENGINE_DENSE_INV_WIDE beside the first flag; never chosen from N),
-    roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives."""
+    roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives.
+    `cost=InvariantCostX(...)`: the extended invariant cost (AZD_ENGINE_DENSE_INVX, N <= 32, a tier of its own with the
+    InvariantCost tier's limits): sixteen invariants -- Laplacian and signless-Laplacian eigenvalues, Randic and Zagreb indices and
+    the triangle count beside the ten -- and products or quotients of two of them.  InvariantCostX.from_invariant_cost(c) gives
+    cost=c's trees."""
 
     SPACE_ID = _lib.SPACE_DENSE
 
     def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False, inv_wide=False):
         self.INV = cost if isinstance(cost, InvariantCost) else None
+        self.INVX = cost if isinstance(cost, InvariantCostX) else None
         if self.INV is not None:
             cost = "inv"
+        elif self.INVX is not None:
+            cost = "invx"
         elif cost not in ("c21", "ah"):
-            raise ValueError('cost must be "c21", "ah" or an InvariantCost')
+            raise ValueError('cost must be "c21", "ah", an InvariantCost or an InvariantCostX')
         if ah_wide and cost != "ah":
             raise ValueError('ah_wide=True needs cost="ah" (it is the Aouchiche-Hansen cost\'s 64-row form)')
         if inv_wide and cost != "inv":
@@ -287,7 +359,7 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
         self.E = self.n * (self.n - 1) // 2
         # (an AZD_ENGINE_DENSE_AH engine refuses max_slots > E; a root cannot bring more than E slots anyway)
         # (... and an AZD_ENGINE_DENSE_AH_WIDE or AZD_ENGINE_DENSE_INV_WIDE engine max_slots > min(E, 640): its keys are 2, 4 or 10 words)
-        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide or inv_wide else min(int(max_slots), self.E) if cost in ("ah", "inv") else int(max_slots)
+        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide or inv_wide else min(int(max_slots), self.E) if cost in ("ah", "inv", "invx") else int(max_slots)
         L = _lib.lib()
         self.STATE_DIM = L.azd_dense_state_dim(self.n)
         self.ACTION_DIM = L.azd_dense_action_dim(self.n)
@@ -344,6 +416,18 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
         else:
             _lib.check(_lib.lib().azd_dense_inv_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_inv_cost")
         return dict(InvariantCost.record(out), eval=np.float32(out.eval))
+
+    def invx_cost(self, adj, cost=None):
+        """The extended invariant cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_invx_cost under this
+        space's recipe (or `cost`, another InvariantCostX), the same procedure as the device's, bit for bit.
+        -> dict(the sixteen invariants by name, dist_k, computed, cost, eval)"""
+        cost = self.INVX if cost is None else cost
+        if cost is None:
+            raise ValueError("invx_cost: the space has no InvariantCostX; pass one")
+        a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
+        out, r = _lib.DenseInvxCost(), cost.recipe()
+        _lib.check(_lib.lib().azd_dense_invx_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_invx_cost")
+        return dict(InvariantCostX.record(out), eval=np.float32(out.eval))
 
 
 class Layered:

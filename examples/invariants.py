@@ -2,16 +2,21 @@
 """examples/ah.py's loop with the objective taken from the command line: a search over connected graphs on N vertices for a graph
 that minimises a linear combination of graph invariants -- the shape of an AutoGraphiX conjecture, "a combination of invariants is
 bounded below by ..." -- on the MI355X engine's weighted-invariant cost (AZD_ENGINE_DENSE_INV, N <= 32; with --wide its 64-row
-form, AZD_ENGINE_DENSE_INV_WIDE, N <= 64, which is asked for by name and never chosen from N).
+form, AZD_ENGINE_DENSE_INV_WIDE, N <= 64, which is asked for by name and never chosen from N; with --extended the extended
+invariant cost, AZD_ENGINE_DENSE_INVX, N <= 32: sixteen invariants and products or quotients of two of them).
 
     python examples/invariants.py --recipe '{"weights": {"remoteness": 1, "proximity": -1}, "eval_offset": 2, "eval_scale": 0.02}'
-                                  [--n 31] [--wide] [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
+                                  [--n 31] [--wide | --extended] [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
 
 --recipe is a JSON object: "weights" (name -> weight over edges, max_degree, min_degree, diameter, radius, proximity, remoteness,
 avg_distance, adj_eig, dist_eig), and optionally "bias", "adj_index", "dist_index" (a descending index or "ah"), "eval_offset",
 "eval_scale" (the evaluator is trained on eval = eval_scale * (cost + eval_offset): choose them so that evals lie in (0, 1)).
 --recipe ah is the Aouchiche-Hansen cost as a recipe: the trees examples/ah.py grows, bit for bit.  A spectral invariant whose
 weight is zero is not computed, so a recipe over the integer invariants and the transmissions alone runs no eigen-solve.
+--extended: "weights" may also name lap_eig, slap_eig, randic, zagreb1, zagreb2, triangles; "lap_index" and "slap_index" are
+descending indices into the Laplacian and signless-Laplacian spectra (n - 2 is the algebraic connectivity); "terms" is a list of up
+to four [coef, "a", "*" or "/", "b"], e.g. [[1, "remoteness", "/", "radius"]] (a divisor is one of the first eight invariants, randic,
+zagreb1 or zagreb2).  Without the flag the driver is what it was: the new names are unknown to it.
 The loop is par_roll_out_episodes x episodes, par_update_model, par_reset_trees with the device root policy; every improvement of
 the argmin and every epoch print the argmin's invariants."""
 import argparse
@@ -33,6 +38,7 @@ def main():
     ap.add_argument("--recipe", required=True, help='a JSON object (see above), or "ah"')
     ap.add_argument("--n", type=int, default=31)
     ap.add_argument("--wide", action="store_true", help="the cost's 64-row form (N <= 64)")
+    ap.add_argument("--extended", action="store_true", help="the extended invariant cost: sixteen invariants, pair terms (N <= 32)")
     ap.add_argument("--epochs", type=int, default=250)
     ap.add_argument("--episodes", type=int, default=800)
     ap.add_argument("--batch", type=int, default=512)
@@ -42,7 +48,13 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
 
-    cost = az.InvariantCost.aouchiche_hansen(args.n) if args.recipe == "ah" else az.InvariantCost.from_dict(json.loads(args.recipe))
+    if args.extended and args.wide:
+        ap.error("--extended has no 64-row form: it cannot be combined with --wide")
+    cost = az.InvariantCost.aouchiche_hansen(args.n) if args.recipe == "ah" else None
+    if args.extended:
+        cost = az.InvariantCostX.from_invariant_cost(cost) if cost is not None else az.InvariantCostX.from_dict(json.loads(args.recipe))
+    elif cost is None:
+        cost = az.InvariantCost.from_dict(json.loads(args.recipe))
     space = az.DenseGraphSpace(args.n, P, max_slots=args.max_slots, cost=cost, inv_wide=args.wide)
     model = az.ActionModel(args.batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=1e-4, l2=1e-6, seed=args.seed,
                            dtype=args.dtype)
@@ -52,8 +64,8 @@ def main():
 
     def show(argmin, tag):
         c = argmin.cost
-        parts = ", ".join("%s: %s" % (name, c[name]) for i, name in enumerate(az.InvariantCost.NAMES) if (c["computed"] >> i) & 1)
-        print("%s\t%s\tInvariantCost { cost: %s, %s, dist_k: %d }" % (tag, argmin.eval, c["cost"], parts, c["dist_k"]))
+        parts = ", ".join("%s: %s" % (name, c[name]) for i, name in enumerate(cost.NAMES) if (c["computed"] >> i) & 1)
+        print("%s\t%s\t%s { cost: %s, %s, dist_k: %d }" % (tag, argmin.eval, type(cost).__name__, c["cost"], parts, c["dist_k"]))
 
     show(opt.argmin_data(), "argmin")
     for epoch in range(1, args.epochs + 1):

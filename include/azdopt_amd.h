@@ -332,6 +332,18 @@ typedef struct azd_engine_config {
  * the reverse).  Pool step: a searcher wave's LDS block is the AZD_ENGINE_DENSE_AH_WIDE tier's, so a searcher workgroup has the 6
  * wavefronts it has there (azd_debug_ext_pool_plan reports the plan for such a configuration too). */
 #define AZD_ENGINE_DENSE_INV_WIDE 2048u
+/* The dense-graph space with the extended invariant cost (azd_dense_invx_cost below): sixteen invariants -- the weighted-invariant
+ * cost's ten, one eigenvalue each of the Laplacian and the signless Laplacian, the Randic index, both Zagreb indices, the triangle
+ * count -- combined by a recipe of weights and up to four products or quotients of two invariants, given at RUN time by
+ * azd_engine_set_dense_invx_recipe.  A tier of its own beside AZD_ENGINE_DENSE_INV, in kernels of their own
+ * (dense_invx_kernels.hip); asked for by name, never inferred.  It has that tier's limits, step forms and pool-step wave counts:
+ * 4 <= n <= AZD_DENSE_INVX_MAX_N = 32, layers <= 1, max_slots <= E, ActionSet paths (refused with AZD_ERR_INVALID_ARGUMENT naming
+ * the argument, as is this flag beside AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV or
+ * AZD_ENGINE_DENSE_INV_WIDE, or on another space); AZD_ENGINE_EXT_POOL_F32 is accepted beside it.  Such an engine keeps the sixteen
+ * invariants, the distance index used and the `computed` mask per agent: azd_engine_dense_invx_agent_cost,
+ * azd_engine_dense_invx_argmin_data.  The INV, AH and default reads and the INV setter are AZD_ERR_UNSUPPORTED on it and name the
+ * right call, and the INVX calls on an AZD_ENGINE_DENSE_INV engine likewise. */
+#define AZD_ENGINE_DENSE_INVX 4096u
 /* Beside AZD_ENGINE_RAMSEY_U64 only (alone, on another space or on a 32-bit tier: AZD_ERR_INVALID_ARGUMENT naming both flags): the
  * 64-bit tier with forbidden cliques up to K8 -- clique sizes 2..AZD_RAMSEY_BIG_CLIQUE_MAX, the reference's count_cliques_inside
  * (bitset_graph/mod.rs:164-185) to depth 6 in kernels of their own; the 64-bit tier's kernels and every engine without the flag are
@@ -373,7 +385,7 @@ typedef struct azd_engine_config {
  * 512 agents 0.99 against 0.52 M expansions/s, r45 at 256 agents 1.03 against 0.31 M on the wide tier and 0.79 against 0.25 M on the
  * 64-bit tier.
  * AZD_SPACE_DENSE: the space's pool step is the searcher-only form and needs no flag of its own, so there this flag stands alone, on
- * all five tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
+ * all six tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
  * this flag beside AZD_ENGINE_NO_PERSISTENT_STEP is AZD_ERR_INVALID_ARGUMENT naming both.  It is a request to the configured pool
  * step, not a form: where the engine's form is not the pool step (fewer than 256 agents without AZD_ENGINE_POOL_STEP) nothing
  * changes and azd_engine_step_form gives the reason it gave.  With it an fp32 MLP is served by the same gathered fp32 GEMMs over the
@@ -857,6 +869,84 @@ typedef struct azd_dense_inv_wide_argmin {
 int azd_engine_dense_inv_wide_argmin_data(azd_engine *e, azd_dense_inv_wide_argmin *out);
 /* the cost record of agent `agent`'s current state as the engine keeps it (cost and eval recomputed from the kept invariants) */
 int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost_t *out);
+
+/* ---- Extended invariant cost (AZD_ENGINE_DENSE_INVX engines minimise it), BUILD-DEFINED (DESIGN.md "The extended invariant
+ * cost").  Sixteen invariants of a CONNECTED graph on 4 <= n <= 32 vertices -- index and name are ABI.  0 .. 9 are the
+ * weighted-invariant cost's, names and definitions unchanged; then
+ *   10 lap_eig    eigenvalue of L = D - A at descending index lap_index (n - 2: the algebraic connectivity)
+ *   11 slap_eig   eigenvalue of Q = D + A at descending index slap_index
+ *   12 randic     sum over edges uv of 1 / sqrt(d_u d_v)      (f64: per vertex u over its neighbours v < u ascending, one division
+ *                                                              and one square root per edge, summed with compensation (TwoSum), then
+ *                                                              the cost's balanced tree sum: within n 2^-52 of the exact sum of
+ *                                                              the terms on the tests' 560 graphs)
+ *   13 zagreb1    sum over vertices of d_u^2                  14 zagreb2    sum over edges uv of d_u d_v
+ *   15 triangles  (sum over edges uv of |N(u) & N(v)|) / 3
+ * combined by a recipe the caller gives at run time: the linear part as above over sixteen weights, then up to four PAIR TERMS
+ *   c = bias;  for i = 0 .. 15 in order, if weight[i] != 0:  c = c + weight[i] * I_i              (two IEEE f64 operations)
+ *   for t = 0 .. n_terms - 1 in order, if coef_t != 0:  v = I_a * I_b or I_a / I_b;  c = c + coef_t * v   (three)
+ *   cost = (float)c;  eval = eval_scale * (cost + eval_offset)
+ * The eight integer invariants 0 .. 7 are always computed.  Each of 8 .. 15 is computed only when its weight is not zero or a pair
+ * term with a coefficient that is not zero names it; otherwise it is reported as 0.0 and its bit of `computed` is clear.  The
+ * divisor of a DIV term must be an invariant that is positive on every connected graph with n >= 4 -- indices 0 .. 7, 12, 13, 14 --
+ * so the cost is always finite.  With weights 10 .. 15 zero and n_terms 0 the sequence of operations is the weighted-invariant
+ * cost's: inv[0 .. 9], dist_k, cost and eval are azd_dense_inv_cost's bit for bit. */
+#define AZD_DENSE_INVX_MAX_N 32
+#define AZD_DENSE_INVX_COUNT 16
+#define AZD_DENSE_INVX_MAX_TERMS 4
+#define AZD_DENSE_INVX_MUL 0
+#define AZD_DENSE_INVX_DIV 1
+#define AZD_DENSE_INVX_NAMES AZD_DENSE_INV_NAMES, "lap_eig", "slap_eig", "randic", "zagreb1", "zagreb2", "triangles"
+typedef struct azd_dense_invx_term {
+    double coef;
+    int a, b;          /* 0 .. 15 */
+    int op;            /* AZD_DENSE_INVX_MUL: I_a * I_b;  AZD_DENSE_INVX_DIV: I_a / I_b (b among 0 .. 7, 12, 13, 14) */
+} azd_dense_invx_term;
+typedef struct azd_dense_invx_recipe {
+    double weight[AZD_DENSE_INVX_COUNT];
+    double bias;
+    int adj_index;     /* 0 .. n - 1 */
+    int dist_index;    /* 0 .. n - 1, or AZD_DENSE_INV_INDEX_AH */
+    int lap_index;     /* 0 .. n - 1 */
+    int slap_index;    /* 0 .. n - 1 */
+    float eval_offset;
+    float eval_scale;  /* not zero */
+    azd_dense_invx_term term[AZD_DENSE_INVX_MAX_TERMS];
+    int n_terms;       /* 0 .. 4 */
+} azd_dense_invx_recipe;
+typedef struct azd_dense_invx_cost_t {
+    double inv[AZD_DENSE_INVX_COUNT];
+    int dist_k;        /* the distance index the recipe resolves to on this graph */
+    uint32_t computed; /* bit i: inv[i] was computed (0xFF always; bits 8 .. 15 by the weights and the pair terms) */
+    float cost;
+    float eval;
+} azd_dense_invx_cost_t;
+/* The cost on the host; needs no GPU.  The graph is checked like azd_dense_inv_cost's, the recipe like
+ * azd_engine_set_dense_invx_recipe's: AZD_ERR_INVALID_ARGUMENT naming the argument or field. */
+int azd_dense_invx_cost(const uint64_t *adj, int n, const azd_dense_invx_recipe *recipe, azd_dense_invx_cost_t *out);
+/* The device kernel in isolation, as azd_debug_probe_inv_cost: graphs and recipe are checked before the device is looked for. */
+int azd_debug_probe_invx_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
+                              azd_dense_invx_cost_t *out, float *ms);
+/* The recipe of an AZD_ENGINE_DENSE_INVX engine: set once, between azd_engine_create and the first par_new (par_new without it is
+ * refused and names this call; after par_new this call is AZD_ERR_INVALID_ARGUMENT).  AZD_ERR_INVALID_ARGUMENT naming the field:
+ * a weight, coefficient, the bias, eval_offset or eval_scale not finite; eval_scale 0; all weights and all coefficients zero;
+ * n_terms outside 0 .. 4; a term's a or b outside 0 .. 15, its op unknown, or a divisor outside 0 .. 7, 12, 13, 14; an index
+ * outside its range.  AZD_ERR_UNSUPPORTED on an engine of another tier. */
+int azd_engine_set_dense_invx_recipe(azd_engine *e, const azd_dense_invx_recipe *recipe);
+/* ArgminData of an AZD_ENGINE_DENSE_INVX engine: the graph, the slots still open, the cost record */
+typedef struct azd_dense_invx_argmin {
+    uint64_t adj[32];
+    uint64_t permitted[8]; /* modifiable slots (colex positions) still open; E <= 496 */
+    double inv[AZD_DENSE_INVX_COUNT];
+    int32_t dist_k;
+    uint32_t computed;
+    float cost;
+    float eval;
+    int32_t agent;
+    uint32_t node;
+} azd_dense_invx_argmin;
+int azd_engine_dense_invx_argmin_data(azd_engine *e, azd_dense_invx_argmin *out);
+/* the cost record of agent `agent`'s current state as the engine keeps it (cost and eval recomputed from the kept invariants) */
+int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_cost_t *out);
 /* Parity probe for the f64 primitives the AH cost depends on bit for bit.  in: 2*n doubles (pairs x, y); out: 3*n doubles per
  * pair: [0] x / y, [1] sqrt(|x|), [2] x - (x / y) * y (two roundings: a contracted form would differ). */
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n);

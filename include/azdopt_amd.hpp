@@ -285,6 +285,78 @@ private:
     bool wide_;
 };
 
+// A recipe of the extended invariant cost (azd_dense_invx_recipe): sixteen invariants -- InvariantCost's ten, then lap_eig, slap_eig,
+// randic, zagreb1, zagreb2, triangles (azdopt_amd.h has the definitions) -- combined with weights and up to four pair terms
+// coef * (a * b) or coef * (a / b).  cost = (float)(bias + sum of weight * invariant + sum of the terms); eval = scale * (cost + offset).
+class InvariantCostX {
+public:
+    InvariantCostX() : r_{} {
+        r_.dist_index = AZD_DENSE_INV_INDEX_AH;
+        r_.eval_scale = 1.0f;
+    }
+    // the recipe that gives an InvariantCost's cost, eval and trees, bit for bit
+    static InvariantCostX from_invariant_cost(const InvariantCost &c) {
+        InvariantCostX x;
+        const azd_dense_inv_recipe &r = c.recipe();
+        for (int i = 0; i < AZD_DENSE_INV_COUNT; ++i) x.r_.weight[i] = r.weight[i];
+        x.r_.bias = r.bias;
+        x.r_.adj_index = r.adj_index;
+        x.r_.dist_index = r.dist_index;
+        x.r_.eval_offset = r.eval_offset;
+        x.r_.eval_scale = r.eval_scale;
+        return x;
+    }
+    static int index_of(const std::string &name) {
+        static const char *const names[AZD_DENSE_INVX_COUNT] = {AZD_DENSE_INVX_NAMES};
+        for (int i = 0; i < AZD_DENSE_INVX_COUNT; ++i)
+            if (name == names[i]) return i;
+        throw Error(AZD_ERR_INVALID_ARGUMENT, "InvariantCostX: unknown invariant " + name);
+    }
+    InvariantCostX &weight(const std::string &name, double w) { r_.weight[index_of(name)] = w; return *this; }
+    // one more pair term: coef * (a * b) for op '*', coef * (a / b) for op '/' (the engine checks the divisor)
+    InvariantCostX &term(double coef, const std::string &a, char op, const std::string &b) {
+        if (r_.n_terms >= AZD_DENSE_INVX_MAX_TERMS || (op != '*' && op != '/')) throw Error(AZD_ERR_INVALID_ARGUMENT, "InvariantCostX: term");
+        azd_dense_invx_term &t = r_.term[r_.n_terms++];
+        t.coef = coef;
+        t.a = index_of(a);
+        t.b = index_of(b);
+        t.op = op == '/' ? AZD_DENSE_INVX_DIV : AZD_DENSE_INVX_MUL;
+        return *this;
+    }
+    InvariantCostX &bias(double b) { r_.bias = b; return *this; }
+    InvariantCostX &adj_index(int k) { r_.adj_index = k; return *this; }
+    InvariantCostX &dist_index(int k) { r_.dist_index = k; return *this; } // a descending index, or AZD_DENSE_INV_INDEX_AH (the default)
+    InvariantCostX &lap_index(int k) { r_.lap_index = k; return *this; }
+    InvariantCostX &slap_index(int k) { r_.slap_index = k; return *this; }
+    InvariantCostX &offset(float o) { r_.eval_offset = o; return *this; }
+    InvariantCostX &scale(float s) { r_.eval_scale = s; return *this; }
+    const azd_dense_invx_recipe &recipe() const { return r_; }
+
+private:
+    azd_dense_invx_recipe r_;
+};
+
+// The same space with the extended invariant cost as the objective (AZD_ENGINE_DENSE_INVX): n <= AZD_DENSE_INVX_MAX_N,
+// max_slots <= E; par_new hands the recipe to the engine.  argmin_data() gives a DenseInvxArgmin.
+class DenseGraphInvXSpace : public DenseGraphSpace {
+public:
+    DenseGraphInvXSpace(int n, double p, int max_slots, const InvariantCostX &cost) : DenseGraphSpace(n, p, max_slots), cost_(cost) {}
+    const InvariantCostX &invariant_cost() const { return cost_; }
+    void configure(azd_engine_config &cfg) const {
+        DenseGraphSpace::configure(cfg);
+        cfg.flags |= AZD_ENGINE_DENSE_INVX;
+    }
+    // the cost of one connected graph on the host (adj: n neighbourhood bitsets): the device's procedure, bit for bit
+    azd_dense_invx_cost_t cost(const uint64_t *adj) const {
+        azd_dense_invx_cost_t c;
+        check(azd_dense_invx_cost(adj, n(), &cost_.recipe(), &c), "azd_dense_invx_cost");
+        return c;
+    }
+
+private:
+    InvariantCostX cost_;
+};
+
 // ---------------------------------------------------------------- models (NablaModel, nabla/model/mod.rs:4-8)
 class NablaModel {
 public:
@@ -404,6 +476,15 @@ struct DenseInvArgmin {
     std::vector<uint64_t> adj;       // state: neighbourhood bitsets
     std::vector<uint64_t> permitted; // ... and the edge slots still modifiable
     azd_dense_inv_cost_t cost;       // the ten invariants (AZD_DENSE_INV_NAMES order), dist_k, computed, cost, eval
+    float eval;
+    int agent;
+    uint32_t node;
+};
+
+struct DenseInvxArgmin {
+    std::vector<uint64_t> adj;       // state: neighbourhood bitsets
+    std::vector<uint64_t> permitted; // ... and the edge slots still modifiable
+    azd_dense_invx_cost_t cost;      // the sixteen invariants (AZD_DENSE_INVX_NAMES order), dist_k, computed, cost, eval
     float eval;
     int agent;
     uint32_t node;
@@ -604,6 +685,9 @@ private:
     static void set_recipe(const DenseGraphInvSpace &sp, azd_engine *h) {
         check(azd_engine_set_dense_inv_recipe(h, &sp.invariant_cost().recipe()), "NablaOptimizer::par_new (recipe)");
     }
+    static void set_recipe(const DenseGraphInvXSpace &sp, azd_engine *h) {
+        check(azd_engine_set_dense_invx_recipe(h, &sp.invariant_cost().recipe()), "NablaOptimizer::par_new (recipe)");
+    }
     void host_predictions() { // the model call of optimizer/mod.rs:72 / :175-176 / :348 on the host side
         check(azd_engine_read_state_vecs(h_, sv_.data()), "read_state_vecs");
         host_->write_predictions(batch_, sv_.data(), pred_.data());
@@ -667,6 +751,22 @@ private:
         azd_dense_inv_argmin a;
         check(azd_engine_dense_inv_argmin_data(h_, &a), "argmin_data");
         return dense_inv_argmin_from(a, sp);
+    }
+    DenseInvxArgmin argmin_of(const DenseGraphInvXSpace &sp) {
+        azd_dense_invx_argmin a;
+        check(azd_engine_dense_invx_argmin_data(h_, &a), "argmin_data");
+        DenseInvxArgmin r;
+        r.adj.assign(a.adj, a.adj + sp.n());
+        r.permitted.assign(a.permitted, a.permitted + (sp.E() + 63) / 64);
+        std::memcpy(r.cost.inv, a.inv, sizeof(a.inv));
+        r.cost.dist_k = a.dist_k;
+        r.cost.computed = a.computed;
+        r.cost.cost = a.cost;
+        r.cost.eval = a.eval;
+        r.eval = a.eval;
+        r.agent = a.agent;
+        r.node = a.node;
+        return r;
     }
     template <class Rec>
     static DenseInvArgmin dense_inv_argmin_from(const Rec &a, const DenseGraphInvSpace &sp) {

@@ -1,0 +1,349 @@
+"""The dense-graph space with the extended invariant cost (AZD_ENGINE_DENSE_INVX; dense_invx_kernels.hip) on the GPU.
+  * the cost kernel alone (azd_debug_probe_invx_cost) against the host function azd_dense_invx_cost, records equal as bytes on the
+    whole graph set of tests/dense_ah_ref.py (560 connected graphs, n = 4 .. 32) under the five new recipes of
+    tests/dense_invx_ref.py and AH, one launch per n; against the Python reference at n = 31 under all nine; and against the INV
+    kernel (azd_debug_probe_inv_cost) under INV's four recipes at n = 4, 5, 20, 32;
+  * an engine under the converted BOTH recipe against an AZD_ENGINE_DENSE_INV engine on the same roots: the same trees, bit for bit;
+  * engines against the Python reference engine (PyDenseInvxEngine) through gpu_parity.run_lockstep with the comparison below:
+    trees, state vectors, the sixteen invariants (f64 by bits), mask, cost, counters, and the argmin re-evaluated through the host
+    function.  N = 8 after every call; N = 4, 5 (two Householder steps), 20, 32 (all 32 rows);
+  * the pool step against the reference at N = 8, and against the launch-per-phase form at 640 agents for key widths 2, 4, 10;
+    one fp32 model under AZD_ENGINE_EXT_POOL_F32; refusals and reads on a live engine; the example driver with --extended.
+Every run asserts on the REFERENCE's counters that it met expansions, terminals and transpositions (N <= 8: root exhaustions too).
+Run with -m gpu on an MI355X."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import dense_ah_ref as A
+import dense_inv_ref as I
+import dense_invx_ref as R
+from gpu_parity import C21_CTRS, TOL_REF, PyDenseRef, assert_same_run, assert_tree_equal, az, run_lockstep, same_array, same_counters  # noqa: F401
+from gpu_parity import f64_bits as bits
+
+pytestmark = pytest.mark.gpu
+
+TOL_SMALL = ([6, 3, 2], 1)
+c_recipe, c_inv_recipe = R.c_recipe, R.c_inv_recipe
+
+
+def cost_of(az, recipe):
+    return az.InvariantCostX(recipe.weights(), **recipe.kwargs())
+
+
+def assert_record_equals_reference(rec, ref, tag):
+    for i, name in enumerate(R.NAMES):
+        assert bits(rec.inv[i]) == bits(ref[name]), (tag, name, rec.inv[i], ref[name])
+    assert (rec.dist_k, rec.computed) == (ref["dist_k"], ref["computed"]), tag
+    assert np.float32(rec.cost).view(np.uint32) == ref["cost"].view(np.uint32), (tag, rec.cost, ref["cost"])
+    assert np.float32(rec.eval).view(np.uint32) == ref["eval"].view(np.uint32), (tag, rec.eval, ref["eval"])
+
+
+@pytest.mark.parametrize("name", R.NEW_RECIPES + ("AH",))
+def test_device_cost_equals_the_host_function_as_bytes(az, name):
+    from azdopt_amd import _lib
+    L = az.lib()
+    by_n = {}
+    for gname, n, adj in A.graph_set():
+        by_n.setdefault(n, []).append((gname, adj))
+    seen = 0
+    for n, graphs in sorted(by_n.items()):
+        rc = c_recipe(R.RECIPES[name](n))
+        a = np.array([adj for _, adj in graphs], dtype=np.uint64)
+        dev = (_lib.DenseInvxCost * len(graphs))()
+        _lib.check(L.azd_debug_probe_invx_cost(0, _lib.ptr(a), n, len(graphs), 2, C.byref(rc), dev, None), "probe_invx_cost")
+        for i, (gname, adj) in enumerate(graphs):
+            host = _lib.DenseInvxCost()
+            _lib.check(L.azd_dense_invx_cost(_lib.ptr(a[i]), n, C.byref(rc), C.byref(host)), "invx_cost")
+            assert bytes(dev[i]) == bytes(host), (name, gname, n, list(dev[i].inv), list(host.inv), dev[i].cost, host.cost)
+            seen += 1
+    assert seen == len(A.graph_set()) == 560
+
+
+def test_device_cost_equals_the_python_reference_at_n31(az):
+    """n = 31, G(31, 0.4) redrawn until connected (the example's roots): device == Python reference under every recipe"""
+    from azdopt_amd import _lib
+    rng = np.random.default_rng(31)
+    graphs = [A.gnp_connected(rng, 31, 0.4) for _ in range(24)]
+    a = np.array(graphs, dtype=np.uint64)
+    for name, mk in sorted(R.RECIPES.items()):
+        recipe = mk(31)
+        rc = c_recipe(recipe)
+        dev = (_lib.DenseInvxCost * len(graphs))()
+        _lib.check(az.lib().azd_debug_probe_invx_cost(0, _lib.ptr(a), 31, len(graphs), 1, C.byref(rc), dev, None), "probe_invx_cost")
+        for i, adj in enumerate(graphs):
+            assert_record_equals_reference(dev[i], R.invx_cost(adj, 31, recipe), (name, i))
+    assert len(R.RECIPES) == 9
+
+
+@pytest.mark.parametrize("n", [4, 5, 20, 32])
+def test_device_cost_equals_the_inv_kernel_under_the_inv_recipes(az, n):
+    """inv[0 .. 9], dist_k, computed, cost and eval of the INVX probe == azd_debug_probe_inv_cost's, bit for bit"""
+    from azdopt_amd import _lib
+    L = az.lib()
+    graphs = [adj for _, m, adj in A.graph_set() if m == n]
+    assert len(graphs) >= 8
+    a = np.array(graphs, dtype=np.uint64)
+    for name in R.INV_RECIPES:
+        rx, ri = c_recipe(R.RECIPES[name](n)), c_inv_recipe(I.RECIPES[name](n))
+        dx, di = (_lib.DenseInvxCost * len(graphs))(), (_lib.DenseInvCost * len(graphs))()
+        _lib.check(L.azd_debug_probe_invx_cost(0, _lib.ptr(a), n, len(graphs), 1, C.byref(rx), dx, None), "probe_invx_cost")
+        _lib.check(L.azd_debug_probe_inv_cost(0, _lib.ptr(a), n, len(graphs), 1, C.byref(ri), di, None), "probe_inv_cost")
+        for i in range(len(graphs)):
+            assert bytes(dx[i])[:80] + bytes(dx[i])[128:] == bytes(di[i]), (name, n, i, list(dx[i].inv), list(di[i].inv))
+            assert list(dx[i].inv)[10:] == [0.0] * 6
+
+
+# ---------------------------------------------------------------- the converted BOTH recipe against the INV tier
+def test_a_converted_both_recipe_engine_grows_the_inv_engines_trees(az):
+    """AZD_ENGINE_DENSE_INVX under InvariantCostX.from_invariant_cost(BOTH) against AZD_ENGINE_DENSE_INV under BOTH on the same
+    roots, with the device root policy over an epoch boundary: trees, state vectors, observations, counters, records and the
+    argmin are equal"""
+    n, B, p, kmin, kmax, tol, seed = 8, 16, 0.4, 2, 10, ([6, 3], 2), 5
+    both = I.recipe_both(n)
+    inv = az.InvariantCost(both.weights(), **both.kwargs())
+    spaces = (az.DenseGraphSpace(n, p, cost=az.InvariantCostX.from_invariant_cost(inv)), az.DenseGraphSpace(n, p, cost=inv))
+    roots = spaces[0].generate_roots(seed, B, kmin=kmin, kmax=kmax)
+    opts = [az.NablaOptimizer.par_new(sp, roots, az.HashStreamModel(sp.STATE_DIM, sp.ACTION_DIM, seed), B) for sp in spaces]
+
+    def same(tag):
+        o0, o1 = opts
+        same_counters(o0.counters(), o1.counters(), tag)
+        for i in range(B):
+            assert_tree_equal(o0.get_tree(i), o1.get_tree(i), f"{tag} agent {i}")
+            s0, s1 = o0.agent_state(i), o1.agent_state(i)
+            for k in ("parents", "permitted", "path", "state_pos", "dist_k", "computed"):
+                assert np.array_equal(s0[k], s1[k]), (tag, i, k)
+            assert all(bits(s0[k]) == bits(s1[k]) for k in I.NAMES) and s0["cost"].view(np.uint32) == s1["cost"].view(np.uint32), (tag, i)
+        same_array(o0.state_vecs(), o1.state_vecs(), f"{tag} state_vecs")
+        a0, a1 = o0.argmin_data(), o1.argmin_data()
+        assert a0.eval.view(np.uint32) == a1.eval.view(np.uint32) and (a0.agent, a0.node) == (a1.agent, a1.node), tag
+        assert np.array_equal(a0.state["adj"], a1.state["adj"]) and np.array_equal(a0.state["permitted"], a1.state["permitted"]), tag
+        assert all(bits(a0.cost[k]) == bits(a1.cost[k]) for k in I.NAMES), tag
+
+    same("par_new")
+    for epoch in range(2):
+        for s in range(0, 40, 8):
+            imp = [o.par_roll_out_episodes(tol, n_calls=8) for o in opts]
+            assert imp[0] == imp[1], (epoch, s, imp)
+            same(f"epoch {epoch} step {s + 8}")
+        obs = [o.observe(2) for o in opts]
+        for x, y, what in zip(obs[0], obs[1], ("rows", "observations", "weights")):
+            same_array(x, y, f"epoch {epoch} observe {what}")
+        for o in opts:
+            o.par_reset_trees_policy(seed, epoch, kmin, kmax)
+        same(f"epoch {epoch} reset")
+    c = opts[0].counters()
+    assert c["FAILED"] == 0 and c["EXPANSIONS"] > 0 and c["TRANSPOSITIONS"] > 0 and c["TERMINALS"] > 0
+
+
+# ---------------------------------------------------------------- engines against the Python reference
+def compare_invx(opt, ref, agents, tag):
+    """the extended invariant cost against PyDenseRef(PyDenseInvxEngine): the sixteen invariants bit for bit, mask, index, cost, the
+    counters the reference keeps, and the argmin's graph re-evaluated through the host function"""
+    same_array(opt.state_vecs(), ref.state_vecs(), f"{tag} state_vecs")
+    for i in agents:
+        assert_tree_equal(opt.get_tree(i), ref.tree(i), f"{tag} agent {i}")
+        sg, sp = opt.agent_state(i), ref.agent_state(i)
+        for k in sp:  # (the cost fields are absent while the reference's agent stands on its root)
+            if k in R.NAMES:
+                assert bits(sg[k]) == bits(sp[k]), (tag, i, k, sg[k], sp[k])
+            elif k == "cost":
+                assert np.float32(sg[k]).view(np.uint32) == np.float32(sp[k]).view(np.uint32), (tag, i, k)
+            else:
+                assert np.array_equal(sg[k], sp[k]), (tag, i, k, sg[k], sp[k])
+    cp = ref.counters()
+    same_counters(opt.counters(), cp, tag, names=cp)
+    ag, ap = opt.argmin_data(), ref.argmin()
+    assert ag.eval.view(np.uint32) == np.float32(ap["eval"]).view(np.uint32), tag
+    for k in R.NAMES:
+        assert bits(ag.cost[k]) == bits(ap[k]), (tag, k, ag.cost[k], ap[k])
+    assert (ag.cost["dist_k"], ag.cost["computed"]) == (ap["dist_k"], ap["computed"]) and ag.cost["cost"].view(np.uint32) == ap["cost"].view(np.uint32), tag
+    assert np.array_equal(ag.state["adj"], ap["adj"]) and np.array_equal(ag.state["permitted"], ap["permitted"]), tag
+    again = opt.space.invx_cost(ag.state["adj"])
+    assert again["cost"].view(np.uint32) == ag.cost["cost"].view(np.uint32) and again["eval"].view(np.uint32) == ag.eval.view(np.uint32), tag
+    assert all(bits(again[k]) == bits(ag.cost[k]) for k in R.NAMES), tag
+
+
+def run_invx_parity(az, orc, n, name, B, p, kmin, kmax, tol, steps, epochs, seed, check_every, exhaust=False, max_slots=128, pool=False):
+    recipe = R.RECIPES[name](n)
+    space = az.DenseGraphSpace(n, p, max_slots=max_slots, cost=cost_of(az, recipe))
+    model = az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed)
+    caps = {}
+    if pool:
+        model = model.serve_from_pool_evaluators()
+        caps = dict(pool_step=True)
+    roots = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
+    opt = az.NablaOptimizer.par_new(space, roots, model, B, **caps)
+    ref = PyDenseRef(R.PyDenseInvxEngine(n, B, recipe, p=p))
+    evals = []
+
+    def compare(o, r, agents, tag):
+        compare_invx(o, r, agents, tag)
+        evals.extend(float(c["eval"]) for c in r.e.costs if c is not None)
+
+    run_lockstep(opt, ref, roots, orc, compare, seed=seed, tol=tol, steps=steps, epochs=epochs, kmin=kmin, kmax=kmax, n_obs_tol=2,
+                 check_every=check_every, boundary="policy", last_boundary=epochs > 1, form="dense_pool" if pool else "dense_per_call",
+                 nan_payloads=True)
+    # on the reference alone: the run was not vacuous, and the recipe's offset and scale keep the evals inside (0, 1)
+    c = ref.counters()
+    assert c["EXPANSIONS"] > 0 and c["TERMINALS"] > 0 and c["TRANSPOSITIONS"] > 0, c
+    assert not exhaust or c["ROOT_EXHAUSTED"] > 0, c
+    assert evals and 0.0 < min(evals) and max(evals) < 1.0, (min(evals), max(evals))
+    return opt
+
+
+@pytest.mark.parametrize("name", ["LAP", "DEG", "RATIO", "ALL4"])
+def test_invx_parity_n8_every_call(az, orc, name):
+    run_invx_parity(az, orc, 8, name, 12, 0.4, 2, 10, ([6, 3], 2), steps=40, epochs=2, seed=5, check_every=1, exhaust=True)
+
+
+@pytest.mark.parametrize("n", [4, 5])
+def test_invx_parity_at_the_smallest_graphs(az, orc, n):
+    """n = 4 runs two Householder steps a pass, every root slot is modifiable (k up to E); all four spectra"""
+    run_invx_parity(az, orc, n, "ALL4", 12, 0.5, 1, n * (n - 1) // 2, TOL_SMALL, steps=12, epochs=2, seed=30 + n, check_every=1, exhaust=True)
+
+
+@pytest.mark.parametrize("name", ["LAP", "RATIO"])
+def test_invx_parity_n20_two_epochs_with_the_device_root_policy(az, orc, name):
+    run_invx_parity(az, orc, 20, name, 24, 0.2, 5, 60, ([50, 20, 10], 5), steps=60, epochs=2, seed=2, check_every=30)
+
+
+def test_invx_parity_n32_all_rows(az, orc):
+    """n = 32: every row of the triangle in all four passes, (1 << n) - 1 at the limit; the reference's tolerances"""
+    run_invx_parity(az, orc, 32, "ALL4", 8, 0.4, 5, 128, TOL_REF, steps=30, epochs=1, seed=1, check_every=15)
+
+
+def test_invx_pool_step_against_the_reference(az, orc):
+    run_invx_parity(az, orc, 8, "RATIO", 12, 0.4, 2, 10, ([6, 3], 2), steps=40, epochs=2, seed=7, check_every=1, exhaust=True, pool=True)
+
+
+@pytest.mark.parametrize("max_slots,kmin,kmax", [(128, 5, 128), (256, 129, 256), (465, 300, 465)])
+def test_invx_pool_step_equals_the_launch_per_phase_form_at_640_agents(az, max_slots, kmin, kmax):
+    """key widths 2, 4 and 10 (N = 31: E = 465) under the RATIO recipe: the pool step's searchers == one launch per phase -- trees,
+    counters, argmin, state vectors -- over an epoch boundary"""
+    n, B, seed, calls = 31, 640, 5, 40
+    space = az.DenseGraphSpace(n, 0.4, max_slots=max_slots, cost=cost_of(az, R.recipe_ratio(n)))
+    roots = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
+    runs = []
+    for pool in (True, False):
+        model = az.HashStreamModel(space.STATE_DIM, space.ACTION_DIM, seed)
+        if pool:
+            model = model.serve_from_pool_evaluators()
+        o = az.NablaOptimizer.par_new(space, roots, model, B, pool_step=pool, prediction_capacity=131072)
+        imp = o.par_roll_out_episodes(TOL_REF, n_calls=calls)
+        form = o.step_form()
+        if pool:
+            assert form == ("pool", ""), form
+            c = o.counters()
+            assert c["EVAL_ROWS"] == c["EXPANSIONS"] > 0
+        else:
+            assert form[0].startswith("per_call"), form
+        o.par_reset_trees_policy(seed, 0, kmin, kmax)
+        imp2 = o.par_roll_out_episodes(TOL_REF, n_calls=20)
+        runs.append((o, imp, imp2))
+    (o0, i0, j0), (o1, i1, j1) = runs
+    assert (i0, j0) == (i1, j1)
+    c0, c1 = o0.counters(), o1.counters()
+    for k in C21_CTRS:
+        assert c0[k] == c1[k], k
+    for i in range(0, B, 7):
+        assert_tree_equal(o0.get_tree(i), o1.get_tree(i), f"agent {i}")
+        s0, s1 = o0.agent_state(i), o1.agent_state(i)
+        assert all(np.array_equal(s0[k], s1[k]) for k in s0), i
+    a0, a1 = o0.argmin_data(), o1.argmin_data()
+    assert a0.eval == a1.eval and a0.agent == a1.agent and a0.node == a1.node and a0.cost == a1.cost
+    assert np.array_equal(o0.state_vecs(), o1.state_vecs())
+    assert o0.space.invx_cost(a0.state["adj"])["cost"] == a0.cost["cost"]
+
+
+def test_invx_with_an_fp32_model_on_the_pool_step_equals_the_launch_per_phase_form(az):
+    """AZD_ENGINE_EXT_POOL_F32 beside AZD_ENGINE_DENSE_INVX: the smallest case of tests/test_gpu_dense_ext_f32.py (n = 8, S = 85)"""
+    n, B, calls, seed, hidden = 8, 96, 20, 7, (64, 32)
+    space = az.DenseGraphSpace(n, 0.2, max_slots=28, cost=cost_of(az, R.recipe_all4(n)))
+    kmin, kmax = space.default_permitted_range()
+    roots = space.generate_roots(seed, B, kmin=kmin, kmax=kmax)
+    runs = []
+    for kw in (dict(pool_step=True, ext_pool_f32=True), dict(persistent=False)):
+        model = az.ActionModel(B, space.STATE_DIM, space.ACTION_DIM, hidden=hidden, seed=seed, dtype="f32")
+        o = az.NablaOptimizer.par_new(space, roots, model, B, **kw, **az.tree_capacities(calls + 12, kmax))
+        runs.append((o, o.par_roll_out_episodes(TOL_REF, n_calls=calls)))
+    (o0, i0), (o1, i1) = runs
+    assert o0.step_form() == ("pool", "") and o1.step_form()[0].startswith("per_call"), (o0.step_form(), o1.step_form())
+    assert i0 == i1
+    assert_same_run(o0, o1, B, "fp32 model")
+    c0 = o0.counters()
+    assert c0["EVAL_ROWS"] == c0["EXPANSIONS"] > 0 and c0["FAILED"] == 0
+
+
+def test_invx_refusals_and_reads_on_a_live_engine(az):
+    from azdopt_amd import _lib
+    L = az.lib()
+    n, B = 12, 4
+    recipe = R.recipe_ratio(n)
+    space = az.DenseGraphSpace(n, 0.3, cost=cost_of(az, recipe))
+    model = az.TrivialModel(space.STATE_DIM, space.ACTION_DIM)
+    adj, slots = space.generate_roots(0, B)
+    # par_new before the recipe: refused, and the text names the setter
+    # (NablaOptimizer's constructor sets the recipe: this engine is made by hand)
+    cfg = _lib.EngineConfig(_lib.SPACE_DENSE, n, B, 0, 0, 0, 0, 0, _lib.ENGINE_DENSE_INVX)
+    cfg.max_slots, cfg.dense_p = space.MAX_SLOTS, space.p
+    h = C.c_void_p()
+    _lib.check(L.azd_engine_create(C.byref(h), C.byref(cfg), model._h), "create")
+    a8, s64 = np.ascontiguousarray(adj, np.uint8), np.ascontiguousarray(slots, np.uint64)
+    assert L.azd_engine_par_new(h, _lib.ptr(a8), _lib.ptr(s64)) == 1
+    assert "azd_engine_set_dense_invx_recipe" in L.azd_last_error().decode()
+    rc = c_recipe(recipe)
+    # the INV setter on this tier: unsupported, naming the right call; a refused recipe names its field
+    assert L.azd_engine_set_dense_inv_recipe(h, C.byref(c_inv_recipe(I.recipe_both(n)))) == 8 and "azd_engine_set_dense_invx_recipe" in L.azd_last_error().decode()
+    bad = c_recipe(recipe)
+    bad.lap_index = n
+    assert L.azd_engine_set_dense_invx_recipe(h, C.byref(bad)) == 1 and "lap_index" in L.azd_last_error().decode()
+    assert L.azd_engine_set_dense_invx_recipe(h, C.byref(rc)) == 0
+    assert L.azd_engine_par_new(h, _lib.ptr(a8), _lib.ptr(s64)) == 0
+    assert L.azd_engine_set_dense_invx_recipe(h, C.byref(rc)) == 1 and "par_new" in L.azd_last_error().decode()  # fixed once par_new has run
+    L.azd_engine_destroy(h)
+    opt = az.NablaOptimizer.par_new(space, (adj, slots), model, B)
+    # the default, the AH and the INV reads on this tier: unsupported, naming the right call
+    for fn, rec in ((L.azd_engine_dense_argmin_data, _lib.DenseArgmin()), (L.azd_engine_dense_ah_argmin_data, _lib.DenseAhArgmin()),
+                    (L.azd_engine_dense_inv_argmin_data, _lib.DenseInvArgmin()), (L.azd_engine_dense_inv_wide_argmin_data, _lib.DenseInvWideArgmin())):
+        assert fn(opt._h, C.byref(rec)) == 8 and "azd_engine_dense_invx_argmin_data" in L.azd_last_error().decode()
+    assert L.azd_engine_dense_ah_agent_cost(opt._h, 0, C.byref(_lib.DenseAhCost())) == 8 and "azd_engine_dense_invx_agent_cost" in L.azd_last_error().decode()
+    assert L.azd_engine_dense_inv_agent_cost(opt._h, 0, C.byref(_lib.DenseInvCost())) == 8 and "azd_engine_dense_invx_agent_cost" in L.azd_last_error().decode()
+    lam = C.c_double()
+    assert L.azd_engine_agent_state(opt._h, 0, None, None, None, None, C.byref(lam), None) == 8
+    # the roots' records as the engine keeps them == the host function on the roots; the argmin re-evaluated
+    for i in range(B):
+        st, want = opt.agent_state(i), space.invx_cost(adj[i].view(np.uint64))
+        assert all(bits(st[k]) == bits(want[k]) for k in R.NAMES) and (st["dist_k"], st["computed"]) == (want["dist_k"], want["computed"])
+        assert st["cost"].view(np.uint32) == want["cost"].view(np.uint32)
+    a = opt.argmin_data()
+    assert space.invx_cost(a.state["adj"])["cost"] == a.cost["cost"] and a.cost["computed"] == 0xFF | 1 << 8
+    # the INVX reads and the setter on an INV engine (naming its calls), on an AH engine and on a default engine: unsupported
+    for cost in (az.InvariantCost({"edges": 1.0}), "ah", "c21"):
+        sp = az.DenseGraphSpace(n, 0.3, cost=cost)
+        o = az.NablaOptimizer.par_new(sp, (adj, slots), az.TrivialModel(sp.STATE_DIM, sp.ACTION_DIM), B)
+        inv = sp.COST == "inv"
+        assert L.azd_engine_dense_invx_argmin_data(o._h, C.byref(_lib.DenseInvxArgmin())) == 8
+        assert not inv or "azd_engine_dense_inv_argmin_data" in L.azd_last_error().decode()
+        assert L.azd_engine_dense_invx_agent_cost(o._h, 0, C.byref(_lib.DenseInvxCost())) == 8
+        assert not inv or "azd_engine_dense_inv_agent_cost" in L.azd_last_error().decode()
+        assert L.azd_engine_set_dense_invx_recipe(o._h, C.byref(rc)) == 8
+        assert not inv or "azd_engine_set_dense_inv_recipe" in L.azd_last_error().decode()
+
+
+def test_example_driver_runs_two_extended_epochs(tmp_path):
+    """examples/invariants.py --extended: exits 0 and prints the argmin's invariants per epoch, the new names and a pair term among them"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    recipe = ('{"weights": {"lap_eig": 1, "max_degree": -0.25, "randic": 0.125}, "terms": [[0.5, "remoteness", "/", "radius"]], "lap_index": 18, '
+              '"eval_offset": 20, "eval_scale": 0.0125}')
+    r = subprocess.run([sys.executable, os.path.join(root, "examples", "invariants.py"), "--extended", "--recipe", recipe, "--n", "20", "--epochs", "2",
+                        "--episodes", "20", "--batch", "32"], cwd=tmp_path, timeout=300, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.count("==== EPOCH") == 2
+    lines = [l for l in r.stdout.splitlines() if l.startswith("epoch ")]
+    assert len(lines) == 2 and all("lap_eig:" in l and "randic:" in l and "remoteness:" in l and "slap_eig" not in l and "adj_eig" not in l for l in lines), lines
