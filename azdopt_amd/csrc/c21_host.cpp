@@ -267,8 +267,8 @@ static void ah_bfs(const uint64_t *adj, int n, double *A, int *trans, int *ecc) 
     }
 }
 // Householder reduction of the symmetric matrix A (pitch DENSE_AH_STRIDE, reduced in place): step i clears column i below row i + 1.
-// deflate: a column whose tail is below it is left as it is, like one whose tail is zero (0.0: none -- the Aouchiche-Hansen cost and
-// the weighted-invariant cost up to 32 vertices; c21_host.h: DENSE_INV_DEFLATE)
+// deflate: a column whose tail is below it is left as it is, like one whose tail is zero (0.0: none -- the Aouchiche-Hansen cost,
+// which reduces distance matrices only; the invariant costs pass DENSE_INV_DEFLATE at every n: c21_host.h)
 static void ah_householder(double *A, int n, double *diag, double *sub, double deflate = 0.0) {
     constexpr int P = DENSE_AH_STRIDE;
     constexpr int MAX_N = DENSE_AH_WIDE_MAX_N;
@@ -415,16 +415,15 @@ void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, De
     I[7] = (double)sum_t / (double)(n * (n - 1));
     I[8] = I[9] = 0.0;
     double diag[MAX_N], sub[MAX_N];
-    const double deflate = n > DENSE_INV_MAX_N ? DENSE_INV_DEFLATE : 0.0;
     // the distance pass runs first, on the rows the BFS left; the adjacency pass refills the matrix from the bitsets
     if (need_dist) {
-        ah_householder(A, n, diag, sub, deflate);
+        ah_householder(A, n, diag, sub, DENSE_INV_DEFLATE);
         I[DENSE_INV_DIST_EIG] = ah_multisection(diag, sub, n, dist_k);
     }
     if (need_adj) {
         for (int u = 0; u < n; ++u)
             for (int v = 0; v < n; ++v) A[u * P + v] = (adj[u] >> v) & 1ull ? 1.0 : 0.0;
-        ah_householder(A, n, diag, sub, deflate);
+        ah_householder(A, n, diag, sub, DENSE_INV_DEFLATE);
         I[DENSE_INV_ADJ_EIG] = ah_multisection(diag, sub, n, r.adj_index);
     }
     double c = r.bias;
@@ -542,7 +541,7 @@ void dense_invx_cost_host(const uint64_t *adj, int n, const DenseInvxRecipe &r, 
     // one matrix, up to four passes: the distance pass on the rows the BFS left, then the adjacency, Laplacian and signless-Laplacian
     // refills from the bitsets and the degrees
     if (need_dist) {
-        ah_householder(A, n, diag, sub);
+        ah_householder(A, n, diag, sub, DENSE_INV_DEFLATE);
         I[DENSE_INV_DIST_EIG] = ah_multisection(diag, sub, n, dist_k);
     }
     for (int pass = 1; pass < 4; ++pass) {
@@ -551,7 +550,7 @@ void dense_invx_cost_host(const uint64_t *adj, int n, const DenseInvxRecipe &r, 
         const double off = pass == 2 ? -1.0 : 1.0;
         for (int u = 0; u < n; ++u)
             for (int v = 0; v < n; ++v) A[u * P + v] = pass > 1 && u == v ? (double)deg[u] : (adj[u] >> v) & 1ull ? off : 0.0;
-        ah_householder(A, n, diag, sub);
+        ah_householder(A, n, diag, sub, DENSE_INV_DEFLATE);
         I[which] = ah_multisection(diag, sub, n, pass == 1 ? r.adj_index : pass == 2 ? r.lap_index : r.slap_index);
     }
     double c = r.bias;

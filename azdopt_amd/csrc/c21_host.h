@@ -91,13 +91,16 @@ void dense_ah_cost_host(const uint64_t *adj, int n, DenseAhCost *out);
 // and eval are that cost's, bit for bit.
 constexpr int DENSE_INV_MAX_N = 32;
 constexpr int DENSE_INV_WIDE_MAX_N = 64; // AZD_ENGINE_DENSE_INV_WIDE engines, azd_dense_inv_cost_wide: the same procedure with 64 rows
-// Beyond 32 vertices only (n > DENSE_INV_MAX_N; at n <= 32 the procedure is the narrow tier's, bit for bit): a Householder step whose
-// column tail -- the sum of squares below the subdiagonal -- is below this is skipped like one whose tail is exactly zero.  A
-// rank-deficient matrix (the adjacency matrix of a double broom: rank 20 at n = 50) leaves a trailing block of rounding noise that
-// shrinks by about 2^-53 every other step; past step 35 its squares are subnormal, beta = 2 / (tail + v1 v1) overflows and the
-// reduction ends in NaN.  32 rows have too few steps to get there (smallest tail on the narrow graph set: 3e-224).  Both matrices
-// have integer entries, so ||M||_F >= 1: the entries dropped are below 2^-100 each, far inside the cost's own backward error
-// 64 n 2^-53 ||M||_F, and every tail that is reduced keeps beta <= 2^201.
+// At every n, in the invariant costs (INV at either row limit and INVX; the AH cost reduces distance matrices only, which do not
+// starve, and keeps its bits): a Householder step whose column tail -- the sum of squares below the subdiagonal -- is below this is
+// skipped like one whose tail is exactly zero.  A rank-deficient matrix (the adjacency matrix of a double broom: rank 20 at n = 50;
+// of a complete bipartite graph: rank 2) leaves a trailing block of rounding noise that shrinks by about 2^-53 every other step;
+// once its squares are subnormal, beta = 2 / (tail + v1 v1) overflows and the reduction ends in NaN, which the multisection turns
+// into a finite, wrong eigenvalue.  That takes some 36 steps on the brooms of 50 and 56 vertices that were met first, but 20 on
+// K(10,11) relabelled (n = 21) and on double_broom(23, 19, 2), the heavier end first: the narrow tiers starve from 19 vertices on
+// (DESIGN.md "The invariant cost up to 64 vertices" has the counts).  All four matrices have integer entries, so ||M||_F >= 1: the
+// entries dropped are below 2^-100 each, far inside the cost's own backward error 64 n 2^-53 ||M||_F, and every tail that is
+// reduced keeps beta <= 2^201.
 constexpr double DENSE_INV_DEFLATE = 0x1p-200;
 constexpr int DENSE_INV_COUNT = 10;
 constexpr int DENSE_INV_ADJ_EIG = 8, DENSE_INV_DIST_EIG = 9;

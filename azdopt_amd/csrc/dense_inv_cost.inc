@@ -24,9 +24,10 @@
 // The row limit ROWS is a template parameter of everything here that depends on it, as in dense_ah_cost.inc: 32 (DenseCostInv:
 // dense_inv_kernels.hip, AZD_ENGINE_DENSE_INV) or 64 (DenseCostInvWide: dense_inv_wide_kernels.hip, AZD_ENGINE_DENSE_INV_WIDE beside
 // the first flag: a triangle of 2080 doubles), and the engine's argmin record follows from it.  Order of operations, lane roles
-// and reductions do not depend on it: at n <= 32 the two compute the same bits.  Beyond 32 vertices, which only the 64-row form
-// reaches, a Householder step whose column tail is below DENSE_INV_DEFLATE is skipped like one whose tail is zero (c21_host.h: a
-// rank-deficient adjacency matrix otherwise runs the reduction into subnormal squares and NaN after some 36 steps).
+// and reductions do not depend on it: at n <= 32 the two compute the same bits.  At every n and either row limit a Householder step
+// whose column tail is below DENSE_INV_DEFLATE is skipped like one whose tail is zero (c21_host.h: a rank-deficient adjacency
+// matrix otherwise runs the reduction into subnormal squares and NaN -- after some 20 steps on K(10,11) or a double broom with
+// the heavier end first; from 19 vertices on).
 __device__ __forceinline__ uint32_t dense_inv_sum_u32(uint32_t v) {
 #pragma unroll
     for (int w = 1; w < 64; w <<= 1) v += (uint32_t)__shfl_xor((int)v, w, 64);
@@ -94,9 +95,9 @@ __device__ __forceinline__ void dense_inv_cost_wave(const uint64_t *adj, DenseAh
             const double tail = dense_tree_sum(lane > i + 1 ? x * x : 0.0);
             const double x1 = __shfl(x, i + 1, 64);
             if (lane == i) dg = w.A[row + i];
-            // (the column is tridiagonal already -- adjacency matrices: often -- or, beyond 32 vertices, is rounding noise of a matrix
-            // whose rank is used up: c21_host.h, DENSE_INV_DEFLATE.  At 32 rows the second condition is constant false)
-            if (tail == 0.0 || (ROWS > DENSE_INV_MAX_N && n > DENSE_INV_MAX_N && tail < DENSE_INV_DEFLATE)) {
+            // (the column is tridiagonal already -- adjacency matrices: often -- or is rounding noise of a matrix whose rank is used
+            // up: c21_host.h, DENSE_INV_DEFLATE.  At every n and either row limit)
+            if (tail == 0.0 || tail < DENSE_INV_DEFLATE) {
                 if (lane == i) sb = x1;
                 continue;
             }

@@ -99,7 +99,9 @@ __device__ __forceinline__ void dense_invx_cost_wave(const uint64_t *adj, DenseA
             const double tail = dense_tree_sum(lane > i + 1 ? x * x : 0.0);
             const double x1 = __shfl(x, i + 1, 64);
             if (lane == i) dg = w.A[row + i];
-            if (tail == 0.0) { // the column is tridiagonal already (adjacency and Laplacian matrices: often)
+            // (the column is tridiagonal already -- adjacency and Laplacian matrices: often -- or is rounding noise of a matrix whose
+            // rank is used up: c21_host.h, DENSE_INV_DEFLATE)
+            if (tail == 0.0 || tail < DENSE_INV_DEFLATE) {
                 if (lane == i) sb = x1;
                 continue;
             }

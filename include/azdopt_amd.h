@@ -822,11 +822,11 @@ typedef struct azd_dense_inv_cost_t {
  * symmetric, connected), the recipe like azd_engine_set_dense_inv_recipe's: AZD_ERR_INVALID_ARGUMENT naming the argument or field. */
 int azd_dense_inv_cost(const uint64_t *adj, int n, const azd_dense_inv_recipe *recipe, azd_dense_inv_cost_t *out);
 /* The same host function for 4 <= n <= AZD_DENSE_INV_WIDE_MAX_N: the same sequence of IEEE f64 operations, the same graph and
- * recipe checks (the indices against 0 .. n - 1); at n <= 32 the same bytes as azd_dense_inv_cost.  Beyond 32 vertices one
- * condition more, on the host and on the device alike: a Householder step whose column has less than 2^-200 below the subdiagonal
+ * recipe checks (the indices against 0 .. n - 1); at n <= 32 the same bytes as azd_dense_inv_cost.  In both, as in
+ * azd_dense_invx_cost and on the device, at every n: a Householder step whose column has less than 2^-200 below the subdiagonal
  * (sum of squares) is skipped like one that has nothing there -- the trailing block of a rank-deficient matrix (the adjacency
- * matrix of a double broom on 50 vertices) is rounding noise that otherwise shrinks into subnormal squares and ends in NaN.  The
- * entries dropped are below 2^-100, far inside the procedure's backward error. */
+ * matrix of a complete bipartite graph, of a double broom) is rounding noise that otherwise shrinks into subnormal squares and
+ * ends in NaN, from 19 vertices on.  The entries dropped are below 2^-100, far inside the procedure's backward error. */
 int azd_dense_inv_cost_wide(const uint64_t *adj, int n, const azd_dense_inv_recipe *recipe, azd_dense_inv_cost_t *out);
 /* The device kernel in isolation: the cost of `count` graphs on n vertices (adj[count][n]) under one recipe, one wavefront each,
  * repeated `reps` times; *ms = GPU time of the timed launch.  Graphs and recipe are checked before the device is looked for. */

@@ -71,8 +71,10 @@ def ah_index(diam, n):
     return q - 1 if q >= 1 else n - 1
 
 
-def tridiagonalise(dist, n):
-    """Householder reduction of the symmetric matrix to tridiagonal (diag, sub): step i annihilates column i below row i + 1."""
+def tridiagonalise(dist, n, deflate=0.0):
+    """Householder reduction of the symmetric matrix to tridiagonal (diag, sub): step i annihilates column i below row i + 1.
+    deflate: a column whose tail is below it is left as it is, like one whose tail is zero.  0.0 (none) for the AH cost, whose
+    bits tests/golden/ah_cost_vectors.json pins; the invariant costs pass dense_inv_ref.INV_DEFLATE at every n."""
     A = [[float(x) for x in row] for row in dist]
     diag, sub = [0.0] * n, [0.0] * n  # sub[i] couples i and i + 1; sub[n - 1] = 0
     for i in range(n - 2):
@@ -80,7 +82,7 @@ def tridiagonalise(dist, n):
         tail = tree_sum64([x[r] * x[r] if r > i + 1 else 0.0 for r in range(n)])
         x1 = x[i + 1]
         diag[i] = A[i][i]
-        if tail == 0.0:  # already tridiagonal in this column
+        if tail == 0.0 or tail < deflate:  # already tridiagonal in this column, or rounding noise of a matrix whose rank is used up
             sub[i] = x1
             continue
         sigma = tail + x1 * x1
@@ -144,6 +146,91 @@ def kth_eigenvalue(diag, sub, n, k):
         new_lo = xs[m - 1] if m > 0 else lo
         new_hi = xs[m] if m < 64 else hi
         lo, hi = new_lo, new_hi
+    return (lo + hi) * 0.5
+
+
+# ---------------------------------------------------------------- the two spectral stages over many matrices at once
+# tridiagonalise and kth_eigenvalue again, with the matrices of one size along the leading axis of numpy arrays: where the scalar
+# form has one Python float operation, these have one elementwise float64 numpy operation (IEEE, never fused), in the same order,
+# with the same fixed-order sums.  They exist because the scalar forms take tens of milliseconds a matrix and the hard case set
+# (tests/dense_spectral_cases.py) has thousands; test_dense_spectral_cases.py holds them to the scalar forms bit for bit.
+def _tree_sum64_many(v):
+    """tree_sum64 along the last axis (at most 64 slots)"""
+    pad = np.zeros(v.shape[:-1] + (64,))
+    pad[..., :v.shape[-1]] = v
+    while pad.shape[-1] > 1:
+        pad = pad[..., 0::2] + pad[..., 1::2]
+    return pad[..., 0]
+
+
+def tridiagonalise_many(mats, n, deflate=0.0):
+    """tridiagonalise(m, n, deflate) for every m of mats: (diag, sub), two float64 arrays [len(mats), n]"""
+    M = np.array(mats, dtype=np.float64).reshape(-1, n, n)
+    G = M.shape[0]
+    diag, sub = np.zeros((G, n)), np.zeros((G, n))
+    with np.errstate(all="ignore"):  # (a column that is skipped still goes through the arithmetic; its results are dropped)
+        for i in range(n - 2):
+            x = np.zeros((G, n))
+            x[:, i + 1:] = M[:, i + 1:, i]
+            sq = x * x
+            sq[:, :i + 2] = 0.0
+            tail = _tree_sum64_many(sq)
+            x1 = x[:, i + 1]
+            diag[:, i] = M[:, i, i]
+            skip = (tail == 0.0) | (tail < deflate)
+            sigma = tail + x1 * x1
+            s = np.sqrt(sigma)
+            alpha = np.where(x1 >= 0.0, -s, s)
+            v = x.copy()
+            v1 = x1 - alpha
+            v[:, i + 1] = v1
+            beta = 2.0 / (tail + v1 * v1)
+            acc = np.zeros((G, n))
+            for c in range(i + 1, n):
+                acc = acc + M[:, :, c] * v[:, c:c + 1]
+            p = beta[:, None] * acc
+            p[:, :i + 1] = 0.0
+            vp = _tree_sum64_many(v * p)
+            K = (0.5 * beta) * vp
+            q = p - K[:, None] * v
+            q[:, :i + 1] = 0.0
+            B = M[:, i + 1:, i + 1:]
+            new = B - (v[:, i + 1:, None] * q[:, None, i + 1:] + q[:, i + 1:, None] * v[:, None, i + 1:])
+            M[:, i + 1:, i + 1:] = np.where(skip[:, None, None], B, new)
+            sub[:, i] = np.where(skip, x1, alpha)
+    diag[:, n - 2] = M[:, n - 2, n - 2]
+    sub[:, n - 2] = M[:, n - 1, n - 2]
+    diag[:, n - 1] = M[:, n - 1, n - 1]
+    return diag, sub
+
+
+def kth_eigenvalues_many(diag, sub, n, ks):
+    """kth_eigenvalue(diag[g], sub[g], n, k) for every row g and every k of ks: a float64 array [rows, len(ks)]"""
+    diag, sub = np.asarray(diag, np.float64), np.asarray(sub, np.float64)
+    j = (n - 1 - np.asarray(ks, np.int64))[None, :, None]
+    sub2 = sub * sub
+    below = np.zeros_like(sub)
+    below[:, 1:] = np.abs(sub[:, :-1])
+    g = (np.abs(diag) + below) + np.abs(sub)
+    R = np.fmax.reduce(np.concatenate([np.zeros((len(diag), 1)), g], axis=1), axis=1)  # (`if g > R`: a NaN is passed over)
+    hi = np.repeat((R + 1.0)[:, None], len(ks), axis=1)
+    lo = -hi
+    lanes = np.arange(1, 65, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for _ in range(AH_ROUNDS):
+            w = hi - lo
+            xs = lo[:, :, None] + (w[:, :, None] * lanes) / 65.0
+            q = diag[:, 0, None, None] - xs
+            q = np.where(np.abs(q) < AH_TINY, -AH_TINY, q)
+            c = (q < 0.0).astype(np.int64)
+            for i in range(1, n):
+                q = (diag[:, i, None, None] - xs) - sub2[:, i - 1, None, None] / q
+                q = np.where(np.abs(q) < AH_TINY, -AH_TINY, q)
+                c += q < 0.0
+            m = (c <= j).sum(axis=2)
+            x_lo = np.take_along_axis(xs, np.maximum(m - 1, 0)[:, :, None], axis=2)[:, :, 0]
+            x_hi = np.take_along_axis(xs, np.minimum(m, 63)[:, :, None], axis=2)[:, :, 0]
+            lo, hi = np.where(m > 0, x_lo, lo), np.where(m < 64, x_hi, hi)
     return (lo + hi) * 0.5
 
 

@@ -8,6 +8,8 @@ tridiagonalise, kth_eigenvalue -- one IEEE f64 operation at a time:
     avg_distance = sum t / (n (n - 1))                                    integer sum, one f64 division
     adj_eig  = adjacency eigenvalue at descending index adj_index         Householder + multisection
     dist_eig = distance eigenvalue at descending index dist_index, or the AH rule (INDEX_AH)
+               (the reduction with INV_DEFLATE: a column whose tail is below 2^-200 is skipped like a zero one -- without it a
+               rank-deficient adjacency matrix ends in NaN from 19 vertices on; the AH cost itself keeps deflate = 0)
 
 and a recipe (weight[10], bias, adj_index, dist_index, eval_offset, eval_scale):
 
@@ -27,6 +29,7 @@ NAMES = ("edges", "max_degree", "min_degree", "diameter", "radius", "proximity",
 ADJ_EIG, DIST_EIG = 8, 9
 INDEX_AH = -1
 ALWAYS = 0xFF
+INV_DEFLATE = 2.0 ** -200  # a Householder column whose tail is below this is skipped (c21_host.h: DENSE_INV_DEFLATE)
 
 
 class Recipe:
@@ -84,11 +87,47 @@ def _stages(adj, n):
                       min_t=min(trans), max_t=max(trans), sum_t=sum(trans))
 
 
-@functools.lru_cache(maxsize=None)
+# The matrices a spectral pass reduces, by name: f(adj, n) -> rows.  dense_invx_ref adds "lap" and "slap".
+MATRICES = {"adj": adjacency_matrix, "dist": lambda adj, n: _stages(adj, n)[0]}
+_TRI, _EIG = {}, {}  # (adj, n, which) -> (diag, sub);  (adj, n, which, k) -> the eigenvalue
+
+
+def _tridiagonal(adj, n, which):
+    """(diag, sub) of the matrix `which` of the graph: it does not depend on the index wanted, so the indices share it.  The
+    reduction skips a column whose tail is below INV_DEFLATE, at every n (c21_host.h: DENSE_INV_DEFLATE)."""
+    key = (adj, n, which)
+    if key not in _TRI:
+        _TRI[key] = A.tridiagonalise(MATRICES[which](adj, n), n, INV_DEFLATE)
+    return _TRI[key]
+
+
 def _eig(adj, n, which, k):
-    m = _stages(adj, n)[0] if which == "dist" else adjacency_matrix(adj, n)
-    diag, sub = A.tridiagonalise(m, n)
-    return A.kth_eigenvalue(diag, sub, n, k)
+    key = (adj, n, which, k)
+    if key not in _EIG:
+        diag, sub = _tridiagonal(adj, n, which)
+        _EIG[key] = A.kth_eigenvalue(diag, sub, n, k)
+    return _EIG[key]
+
+
+def prime(entries, whiches, ks_of=lambda n: (0, 1, n // 2, n - 2, n - 1)):
+    """Fill the two caches for many graphs at once -- entries of (name, n, adj), the matrices `whiches`, the descending indices
+    ks_of(n) -- through dense_ah_ref's forms over many matrices: the same operations, the same bits (test_dense_spectral_cases.py),
+    some twenty times faster.  The hard case set has thousands of graphs; nothing else needs this."""
+    by_n = {}
+    for _, n, adj in entries:
+        by_n.setdefault(n, []).append(tuple(int(a) for a in adj))
+    for n, graphs in by_n.items():
+        ks = sorted(set(ks_of(n)))
+        for which in whiches:
+            todo = [g for g in graphs if any((g, n, which, k) not in _EIG for k in ks)]
+            if not todo:
+                continue
+            diag, sub = A.tridiagonalise_many([MATRICES[which](g, n) for g in todo], n, INV_DEFLATE)
+            eig = A.kth_eigenvalues_many(diag, sub, n, ks)
+            for i, g in enumerate(todo):
+                _TRI[(g, n, which)] = (diag[i].tolist(), sub[i].tolist())
+                for j, k in enumerate(ks):
+                    _EIG[(g, n, which, k)] = float(eig[i, j])
 
 
 def dist_index_of(recipe, diam, n):

@@ -147,11 +147,9 @@ def laplacian(adj, n, sign):
     return [[deg[u] if u == v else sign * ((adj[u] >> v) & 1) for v in range(n)] for u in range(n)]
 
 
-@functools.lru_cache(maxsize=None)
-def _eig(adj, n, which, k):
-    m = laplacian(adj, n, -1) if which == "lap" else laplacian(adj, n, 1)
-    diag, sub = A.tridiagonalise(m, n)
-    return A.kth_eigenvalue(diag, sub, n, k)
+# L and Q join the matrices dense_inv_ref reduces: one reduction (with INV_DEFLATE), one pair of caches, for all four
+I.MATRICES.update(lap=lambda adj, n: laplacian(adj, n, -1), slap=lambda adj, n: laplacian(adj, n, 1))
+_eig = I._eig
 
 
 @functools.lru_cache(maxsize=None)

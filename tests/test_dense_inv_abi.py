@@ -1,6 +1,7 @@
 """azd_dense_inv_cost, the host form of the weighted-invariant cost (c21_host.cpp), without a GPU: equal to the Python reference
 (tests/dense_inv_ref.py) bit for bit -- every field of the record compared as bytes -- on the whole graph set under the four test
-recipes and over a sweep of the spectral indices; skipped terms; azd_dense_ah_cost as one recipe; and every refusal that needs no
+recipes and over a sweep of the spectral indices, and on the hard case set of the spectral passes (tests/dense_spectral_cases.py)
+under an adjacency and a both-spectra recipe; skipped terms; azd_dense_ah_cost as one recipe; and every refusal that needs no
 device, with its status and the argument it names."""
 import ctypes as C
 import math
@@ -11,6 +12,7 @@ import pytest
 
 import dense_ah_ref as A
 import dense_inv_ref as R
+import dense_spectral_cases as S
 
 
 @pytest.fixture(scope="module")
@@ -67,6 +69,24 @@ def test_host_cost_equals_the_python_reference_as_bytes(lib):
             assert bytes(out) == reference_bytes(r), (name, n, rname, list(out.inv), r)
             seen += 1
     assert seen == 4 * 560
+
+
+def test_host_cost_equals_the_python_reference_on_the_hard_spectral_cases(lib):
+    """tests/dense_spectral_cases.py (rank-deficient adjacency matrices, every labelling; 186 of them end in NaN without the
+    deflation rule) under an adjacency recipe (index 0) and a both-spectra recipe (adjacency n - 1, distance 1): records as bytes,
+    every invariant finite"""
+    entries = S.graph_set()
+    R.prime(entries, ("adj", "dist"), lambda n: (0, 1, n - 1))
+    seen = 0
+    for name, n, adj in entries:
+        for rname in ("ADJ", "BOTH"):
+            recipe = R.RECIPES[rname](n)
+            st, out = host_cost(lib, adj, n, recipe)
+            assert st == 0, (name, rname, lib.azd_last_error())
+            assert all(math.isfinite(x) for x in out.inv), (name, rname, list(out.inv))
+            assert bytes(out) == reference_bytes(R.inv_cost(adj, n, recipe)), (name, rname, list(out.inv))
+            seen += 1
+    assert seen == 2 * 3700
 
 
 def test_index_sweep_on_every_tenth_graph(lib):

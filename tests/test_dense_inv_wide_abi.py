@@ -1,6 +1,6 @@
 """The weighted-invariant cost up to 64 vertices without a GPU: azd_dense_inv_cost_wide (c21_host.cpp) equal to the Python reference
 (tests/dense_inv_wide_ref.py) as bytes on the 88 graphs of graph_set_wide() under the four test recipes, to azd_dense_inv_cost as
-bytes on the n <= 32 set, and under the AH recipe to azd_dense_ah_cost_wide; both spectra against numpy.linalg.eigvalsh within the
+bytes on the n <= 32 set, both again on the hard case set of the spectral passes (tests/dense_spectral_cases.py), and under the AH recipe to azd_dense_ah_cost_wide; both spectra against numpy.linalg.eigvalsh within the
 project's backward-error tolerance; the argument checks of the new calls and of AZD_ENGINE_DENSE_INV_WIDE, made before any device
 is looked for; the pool plan; the Python and C++ hosts."""
 import ctypes as C
@@ -12,6 +12,7 @@ import pytest
 import dense_ah_ref as A
 import dense_inv_ref as R
 import dense_inv_wide_ref as W
+import dense_spectral_cases as S
 
 
 @pytest.fixture(scope="module")
@@ -82,6 +83,29 @@ def test_wide_host_cost_is_the_narrow_one_up_to_32_vertices(lib):
             assert sw == 0 == sn and bytes(w) == bytes(nr), (name, n, rname)
             seen += 1
     assert seen == 4 * 560
+
+
+def test_wide_host_cost_on_the_hard_spectral_cases(lib):
+    """tests/dense_spectral_cases.py under an adjacency recipe (index 0) and a both-spectra recipe (adjacency n - 1, distance 1):
+    beyond 32 vertices (n = 33, 40, 64: graphs other than the two brooms the deflation rule was made for) the wide host function
+    equals the Python reference as bytes; up to 32 vertices it equals the narrow host function as bytes; every invariant finite"""
+    import math
+    wide, narrow = S.graph_set_wide(), S.graph_set()
+    R.prime(wide, ("adj", "dist"), lambda n: (0, 1, n - 1))
+    seen = 0
+    for name, n, adj in wide + narrow:
+        for rname in ("ADJ", "BOTH"):
+            recipe = R.RECIPES[rname](n)
+            st, out = host_cost(lib, adj, n, recipe)
+            assert st == 0, (name, rname, why(lib))
+            assert all(math.isfinite(x) for x in out.inv), (name, rname, list(out.inv))
+            if n > 32:
+                assert bytes(out) == reference_bytes(W.inv_cost(adj, n, recipe)), (name, rname, list(out.inv))
+            else:
+                sn, nr = host_cost(lib, adj, n, recipe, wide=False)
+                assert sn == 0 and bytes(out) == bytes(nr), (name, rname, list(out.inv), list(nr.inv))
+            seen += 1
+    assert seen == 2 * (939 + 3700)
 
 
 def test_the_wide_ah_cost_is_the_ah_recipe(lib):

@@ -1,6 +1,6 @@
 """azd_dense_invx_cost, the host form of the extended invariant cost (c21_host.cpp), without a GPU: equal to the Python reference
 (tests/dense_invx_ref.py) bit for bit -- every field of the record compared as bytes -- on the whole graph set under the nine test
-recipes; equal to azd_dense_inv_cost (and, under the AH recipe, azd_dense_ah_cost) under the converted INV recipes; skipped terms;
+recipes, and on the hard case set of the spectral passes (tests/dense_spectral_cases.py) under four of them; equal to azd_dense_inv_cost (and, under the AH recipe, azd_dense_ah_cost) under the converted INV recipes; skipped terms;
 and every refusal that needs no device, with its status and the argument or field it names."""
 import ctypes as C
 import math
@@ -12,6 +12,7 @@ import pytest
 import dense_ah_ref as A
 import dense_inv_ref as I
 import dense_invx_ref as R
+import dense_spectral_cases as S
 
 
 @pytest.fixture(scope="module")
@@ -65,6 +66,24 @@ def test_host_cost_equals_the_python_reference_as_bytes(lib):
             assert bytes(out) == reference_bytes(r), (name, n, rname, list(out.inv), r)
             seen += 1
     assert seen == 9 * 560
+
+
+def test_host_cost_equals_the_python_reference_on_the_hard_spectral_cases(lib):
+    """tests/dense_spectral_cases.py (rank-deficient adjacency matrices, every labelling; 186 of them end in NaN without the
+    deflation rule) under an adjacency recipe, a both-spectra recipe, the Laplacian recipe (index n - 2) and the signless one
+    (index 0): records as bytes, every invariant finite"""
+    entries = S.graph_set()
+    I.prime(entries, ("adj", "dist", "lap", "slap"), lambda n: (0, 1, n - 2, n - 1))
+    seen = 0
+    for name, n, adj in entries:
+        for rname in ("ADJ", "BOTH", "LAP", "SLAP"):
+            recipe = R.RECIPES[rname](n)
+            st, out = host_cost(lib, adj, n, recipe)
+            assert st == 0, (name, rname, lib.azd_last_error())
+            assert all(math.isfinite(x) for x in out.inv), (name, rname, list(out.inv))
+            assert bytes(out) == reference_bytes(R.invx_cost(adj, n, recipe)), (name, rname, list(out.inv))
+            seen += 1
+    assert seen == 4 * 3700
 
 
 def test_the_converted_inv_recipes_give_the_inv_and_the_ah_host_functions(lib):

@@ -1,7 +1,9 @@
 """The dense-graph space with the weighted-invariant cost (AZD_ENGINE_DENSE_INV; dense_inv_kernels.hip) on the GPU.
   * the cost kernel alone (azd_debug_probe_inv_cost) against the host function azd_dense_inv_cost, records equal as bytes on the
     whole graph set of tests/dense_ah_ref.py (560 connected graphs, n = 4 .. 32) under the four recipes of tests/dense_inv_ref.py,
-    and against the Python reference at n = 31;
+    and against the Python reference at n = 31; on the hard case set of the spectral passes (tests/dense_spectral_cases.py: rank-deficient
+    adjacency matrices in every labelling) at n = 21, 23, 31, 32, one launch per n, every invariant finite; and an engine rooted at
+    double_broom(23, 19, 2), whose adjacency reduction ended in NaN before the deflation rule held at every n;
   * an engine with the AH recipe against an AZD_ENGINE_DENSE_AH engine on the same roots: the same trees, bit for bit;
   * engines against the Python reference engine (tests/dense_inv_ref.py: PyDenseInvEngine) through gpu_parity.run_lockstep with
     the comparison below: trees, state vectors, the ten invariants (f64 by bits), mask, cost, counters, and the argmin re-evaluated
@@ -20,6 +22,7 @@ import pytest
 
 import dense_ah_ref as A
 import dense_inv_ref as R
+import dense_spectral_cases as S
 from gpu_parity import C21_CTRS, TOL_REF, PyDenseRef, assert_same_run, assert_tree_equal, az, run_lockstep, same_array, same_counters  # noqa: F401
 from gpu_parity import f64_bits as bits
 
@@ -84,6 +87,55 @@ def test_device_cost_equals_the_python_reference_at_n31(az):
         _lib.check(az.lib().azd_debug_probe_inv_cost(0, _lib.ptr(a), 31, len(graphs), 1, C.byref(rc), dev, None), "probe_inv_cost")
         for i, adj in enumerate(graphs):
             assert_record_equals_reference(dev[i], R.inv_cost(adj, 31, recipe), (name, i))
+
+
+@pytest.mark.parametrize("name", ["ADJ", "BOTH"])
+@pytest.mark.parametrize("n", [21, 23, 31, 32])
+def test_device_cost_on_the_hard_spectral_cases(az, n, name):
+    """every graph of the set on n vertices in one launch, under the adjacency recipe (adj_index = 0) and the both-spectra recipe
+    (adj_index = n - 1, dist_index = 1): records equal to the host function's as bytes, every invariant finite, adj_eig within 64 n 2^-53 ||A||_F of LAPACK's"""
+    from azdopt_amd import _lib
+    L = az.lib()
+    graphs = S.by_size(S.graph_set())[n]
+    assert len(graphs) >= 3 * (7 * n - 21) and any(g[0] in S.PARENT_FAILS for g in graphs)
+    rc = c_recipe(R.RECIPES[name](n))
+    a = np.array([adj for _, _, adj in graphs], dtype=np.uint64)
+    dev = (_lib.DenseInvCost * len(graphs))()
+    _lib.check(L.azd_debug_probe_inv_cost(0, _lib.ptr(a), n, len(graphs), 1, C.byref(rc), dev, None), "probe_inv_cost")
+    for i, (gname, _, _) in enumerate(graphs):
+        host = _lib.DenseInvCost()
+        _lib.check(L.azd_dense_inv_cost(_lib.ptr(a[i]), n, C.byref(rc), C.byref(host)), "inv_cost")
+        assert all(np.isfinite(x) for x in dev[i].inv), (name, gname, list(dev[i].inv))
+        if dev[i].computed >> 8 & 1:  # adj_eig against LAPACK: a NaN in the tridiagonal form leaves a finite value far from it
+            m = np.array(R.adjacency_matrix(graphs[i][2], n), np.float64)
+            assert abs(dev[i].inv[8] - np.linalg.eigvalsh(m)[::-1][rc.adj_index]) <= 64.0 * n * 2.0 ** -53 * np.linalg.norm(m), (name, gname, dev[i].inv[8])
+        assert bytes(dev[i]) == bytes(host), (name, gname, list(dev[i].inv), list(host.inv), dev[i].cost, host.cost)
+
+
+def test_an_engine_rooted_at_the_heavy_end_first_brooms_reads_back_the_host_functions_adj_eig(az):
+    """AZD_ENGINE_DENSE_INV at n = 23 under {"adj_eig": 1}, rooted through par_new at double_broom(23, 19, 2) and double_broom(23, 20, 1)
+    (without the deflation rule: NaN in the tridiagonal form, a finite wrong adj_eig) and at two more graphs of the set: each agent's
+    record and the argmin read back the host function's adj_eig, which is LAPACK's within 64 n 2^-53 ||A||_F"""
+    n, B = 23, 4
+    by_name = {name: adj for name, _, adj in S.by_size(S.graph_set())[n]}
+    names = ("broom(19,2)-n23/id", "broom(20,1)-n23/id", "K[11,12]-n23/p1", "star-n23/p2")
+    assert set(names[:2]) <= set(S.PARENT_FAILS)
+    space = az.DenseGraphSpace(n, 0.3, cost=az.InvariantCost({"adj_eig": 1.0}, adj_index=0, eval_scale=1.0 / n))
+    adj, slots = space.generate_roots(0, B)
+    adj = np.array(adj, dtype=np.uint8).reshape(B, 8 * n)
+    for i, name in enumerate(names):
+        adj[i] = np.array(by_name[name], dtype=np.uint64).view(np.uint8)
+    opt = az.NablaOptimizer.par_new(space, (adj, slots), az.TrivialModel(space.STATE_DIM, space.ACTION_DIM), B)
+    for i, name in enumerate(names):
+        st, want = opt.agent_state(i), space.inv_cost(adj[i].view(np.uint64))
+        assert np.array_equal(st["parents"], adj[i]), name
+        assert bits(st["adj_eig"]) == bits(want["adj_eig"]) and st["computed"] == want["computed"] == 0xFF | 1 << 8, (name, st["adj_eig"], want["adj_eig"])
+        assert st["cost"].view(np.uint32) == want["cost"].view(np.uint32), name
+        m = np.array(R.adjacency_matrix(by_name[name], n), np.float64)
+        assert abs(st["adj_eig"] - np.linalg.eigvalsh(m)[-1]) <= 64.0 * n * 2.0 ** -53 * np.linalg.norm(m), (name, st["adj_eig"])
+    a = opt.argmin_data()
+    again = space.inv_cost(a.state["adj"])
+    assert bits(a.cost["adj_eig"]) == bits(again["adj_eig"]) and a.cost["cost"].view(np.uint32) == again["cost"].view(np.uint32)
 
 
 # ---------------------------------------------------------------- the AH recipe against the AH tier

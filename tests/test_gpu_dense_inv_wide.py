@@ -2,7 +2,8 @@
 the GPU.
   * the 64-row cost kernel alone (azd_debug_probe_inv_cost_wide) against the host function azd_dense_inv_cost_wide, records equal as
     bytes on the 88 graphs of tests/dense_ah_wide_ref.py (n = 33 .. 64) under the four recipes of tests/dense_inv_ref.py, one launch
-    per n; and against the 32-row kernel on every fifth graph of the n <= 32 set;
+    per n; against the 32-row kernel on every fifth graph of the n <= 32 set; and on the hard case set of the spectral passes
+    (tests/dense_spectral_cases.py) at n = 23, 32, 33, 64;
   * engines against the Python reference engine (tests/dense_inv_wide_ref.py: PyDenseInvWideEngine) through gpu_parity.run_lockstep,
     one launch per phase, compared after every call with test_gpu_dense_inv.py's comparison: n = 33 (the first row past 32) with
     the device root policy over two epochs under the INT and the ADJ recipe, n = 64 (every lane a row; the BFS mask and the bit
@@ -25,6 +26,7 @@ import pytest
 import dense_ah_ref as A
 import dense_inv_ref as R
 import dense_inv_wide_ref as W
+import dense_spectral_cases as S
 from gpu_parity import C21_CTRS, TOL_REF, PyDenseRef, assert_same_run, assert_tree_equal, az, run_lockstep, same_array, same_counters  # noqa: F401
 from gpu_parity import f64_bits as bits
 
@@ -85,6 +87,31 @@ def test_wide_kernel_equals_the_narrow_kernel_up_to_32_vertices(az):
                 assert bytes(wide[i]) == bytes(narrow[i]), (name, gname, n)
                 seen += 1
     assert seen == 4 * 112
+
+
+@pytest.mark.parametrize("name", ["ADJ", "BOTH"])
+@pytest.mark.parametrize("n", [23, 32, 33, 64])
+def test_wide_device_cost_on_the_hard_spectral_cases(az, n, name):
+    """every graph of tests/dense_spectral_cases.py on n vertices in one launch of the 64-row kernel (rank-deficient adjacency matrices
+    in every labelling; beyond 32 vertices graphs other than the two brooms the deflation rule was made for), under the adjacency
+    recipe (adj_index = 0) and the both-spectra recipe (adj_index = n - 1, dist_index = 1): records equal to the host function's as
+    bytes, every invariant finite"""
+    from azdopt_amd import _lib
+    L = az.lib()
+    graphs = S.by_size(S.graph_set() if n <= 32 else S.graph_set_wide())[n]
+    assert len(graphs) >= 200
+    rc = c_recipe(R.RECIPES[name](n))
+    a = np.array([adj for _, _, adj in graphs], dtype=np.uint64)
+    dev = (_lib.DenseInvCost * len(graphs))()
+    _lib.check(L.azd_debug_probe_inv_cost_wide(0, _lib.ptr(a), n, len(graphs), 1, C.byref(rc), dev, None), "probe_inv_cost_wide")
+    for i, (gname, _, _) in enumerate(graphs):
+        host = _lib.DenseInvCost()
+        _lib.check(L.azd_dense_inv_cost_wide(_lib.ptr(a[i]), n, C.byref(rc), C.byref(host)), "inv_cost_wide")
+        assert all(np.isfinite(x) for x in dev[i].inv), (name, gname, list(dev[i].inv))
+        if dev[i].computed >> 8 & 1:  # adj_eig against LAPACK: a NaN in the tridiagonal form leaves a finite value far from it
+            m = np.array(R.adjacency_matrix(graphs[i][2], n), np.float64)
+            assert abs(dev[i].inv[8] - np.linalg.eigvalsh(m)[::-1][rc.adj_index]) <= 64.0 * n * 2.0 ** -53 * np.linalg.norm(m), (name, gname, dev[i].inv[8])
+        assert bytes(dev[i]) == bytes(host), (name, gname, list(dev[i].inv), list(host.inv), dev[i].cost, host.cost)
 
 
 # ---------------------------------------------------------------- engines against the Python reference

@@ -22,6 +22,7 @@ import pytest
 import dense_ah_ref as A
 import dense_inv_ref as I
 import dense_invx_ref as R
+import dense_spectral_cases as S
 from gpu_parity import C21_CTRS, TOL_REF, PyDenseRef, assert_same_run, assert_tree_equal, az, run_lockstep, same_array, same_counters  # noqa: F401
 from gpu_parity import f64_bits as bits
 
@@ -78,6 +79,30 @@ def test_device_cost_equals_the_python_reference_at_n31(az):
         for i, adj in enumerate(graphs):
             assert_record_equals_reference(dev[i], R.invx_cost(adj, 31, recipe), (name, i))
     assert len(R.RECIPES) == 9
+
+
+@pytest.mark.parametrize("name", ["ADJ", "BOTH", "LAP", "SLAP"])
+@pytest.mark.parametrize("n", [21, 23, 31, 32])
+def test_device_cost_on_the_hard_spectral_cases(az, n, name):
+    """every graph of tests/dense_spectral_cases.py on n vertices in one launch (rank-deficient adjacency matrices in every labelling),
+    under the adjacency recipe (adj_index = 0), the both-spectra recipe (adj_index = n - 1, dist_index = 1), the Laplacian recipe
+    (lap_index = n - 2) and the signless one (slap_index = 0): records equal to the host function's as bytes, every invariant finite, adj_eig within 64 n 2^-53 ||A||_F of LAPACK's"""
+    from azdopt_amd import _lib
+    L = az.lib()
+    graphs = S.by_size(S.graph_set())[n]
+    assert len(graphs) >= 3 * (7 * n - 21) and any(g[0] in S.PARENT_FAILS for g in graphs)
+    rc = c_recipe(R.RECIPES[name](n))
+    a = np.array([adj for _, _, adj in graphs], dtype=np.uint64)
+    dev = (_lib.DenseInvxCost * len(graphs))()
+    _lib.check(L.azd_debug_probe_invx_cost(0, _lib.ptr(a), n, len(graphs), 1, C.byref(rc), dev, None), "probe_invx_cost")
+    for i, (gname, _, _) in enumerate(graphs):
+        host = _lib.DenseInvxCost()
+        _lib.check(L.azd_dense_invx_cost(_lib.ptr(a[i]), n, C.byref(rc), C.byref(host)), "invx_cost")
+        assert all(np.isfinite(x) for x in dev[i].inv), (name, gname, list(dev[i].inv))
+        if dev[i].computed >> 8 & 1:  # adj_eig against LAPACK: a NaN in the tridiagonal form leaves a finite value far from it
+            m = np.array(I.adjacency_matrix(graphs[i][2], n), np.float64)
+            assert abs(dev[i].inv[8] - np.linalg.eigvalsh(m)[::-1][rc.adj_index]) <= 64.0 * n * 2.0 ** -53 * np.linalg.norm(m), (name, gname, dev[i].inv[8])
+        assert bytes(dev[i]) == bytes(host), (name, gname, list(dev[i].inv), list(host.inv), dev[i].cost, host.cost)
 
 
 @pytest.mark.parametrize("n", [4, 5, 20, 32])
