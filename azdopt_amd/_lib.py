@@ -28,6 +28,7 @@ ENGINE_DENSE_AH_WIDE = 256  # AZD_ENGINE_DENSE_AH_WIDE: beside ENGINE_DENSE_AH o
 ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STEP (Ramsey), alone on SPACE_DENSE: that form with an fp32 model (gathered fp32 GEMMs)
 ENGINE_DENSE_INV = 1024  # AZD_ENGINE_DENSE_INV: the dense-graph space with the weighted-invariant cost (n <= 32; recipe set at run time)
 ENGINE_DENSE_INV_WIDE = 2048  # AZD_ENGINE_DENSE_INV_WIDE: beside ENGINE_DENSE_INV only: the weighted-invariant cost up to n = 64 (64-row kernels)
+ENGINE_DENSE_INVX_WIDE = 8192  # AZD_ENGINE_DENSE_INVX_WIDE: beside ENGINE_DENSE_INVX only: the extended invariant cost up to n = 64 (64-row kernels)
 ENGINE_DENSE_INVX = 4096  # AZD_ENGINE_DENSE_INVX: the dense-graph space with the extended invariant cost (n <= 32; sixteen invariants, pair terms)
 ENGINE_RAMSEY_BIG_CLIQUES = 512  # AZD_ENGINE_RAMSEY_BIG_CLIQUES: beside ENGINE_RAMSEY_U64 only: clique sizes up to 8 (kernels of their own)
 SPACE_C21 = 1
@@ -48,6 +49,7 @@ DENSE_INV_INDEX_AH = -1  # AZD_DENSE_INV_INDEX_AH: dist_index by the Aouchiche-H
 # AZD_DENSE_INV_NAMES: index and name are ABI
 DENSE_INV_NAMES = ("edges", "max_degree", "min_degree", "diameter", "radius", "proximity", "remoteness", "avg_distance", "adj_eig", "dist_eig")
 DENSE_INVX_MAX_N = 32   # AZD_DENSE_INVX_MAX_N: the extended invariant cost (azd_dense_invx_cost)
+DENSE_INVX_WIDE_MAX_N = 64  # AZD_DENSE_INVX_WIDE_MAX_N: its 64-row form (azd_dense_invx_cost_wide, ENGINE_DENSE_INVX_WIDE)
 DENSE_INVX_COUNT = 16   # AZD_DENSE_INVX_COUNT
 DENSE_INVX_MAX_TERMS = 4  # AZD_DENSE_INVX_MAX_TERMS: pair terms of a recipe
 DENSE_INVX_MUL, DENSE_INVX_DIV = 0, 1  # AZD_DENSE_INVX_MUL / _DIV: a pair term's op
@@ -143,6 +145,11 @@ class DenseInvxCost(C.Structure):  # azd_dense_invx_cost_t
 
 class DenseInvxArgmin(C.Structure):  # azd_dense_invx_argmin: ArgminData of a dense engine with the extended invariant cost
     _fields_ = [("adj", C.c_uint64 * 32), ("permitted", C.c_uint64 * 8), ("inv", C.c_double * 16), ("dist_k", C.c_int32),
+                ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
+
+
+class DenseInvxWideArgmin(C.Structure):  # azd_dense_invx_wide_argmin: the same of an engine with ENGINE_DENSE_INVX_WIDE (n <= 64, E <= 2016)
+    _fields_ = [("adj", C.c_uint64 * 64), ("permitted", C.c_uint64 * 32), ("inv", C.c_double * 16), ("dist_k", C.c_int32),
                 ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
 
 
@@ -290,6 +297,9 @@ def lib():
     sig("azd_engine_dense_inv_wide_argmin_data", C.c_int, vp, C.POINTER(DenseInvWideArgmin))
     sig("azd_dense_invx_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvxRecipe), C.POINTER(DenseInvxCost))
     sig("azd_debug_probe_invx_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DenseInvxRecipe), vp, f32p)
+    sig("azd_dense_invx_cost_wide", C.c_int, vp, C.c_int, C.POINTER(DenseInvxRecipe), C.POINTER(DenseInvxCost))
+    sig("azd_debug_probe_invx_cost_wide", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DenseInvxRecipe), vp, f32p)
+    sig("azd_engine_dense_invx_wide_argmin_data", C.c_int, vp, C.POINTER(DenseInvxWideArgmin))
     sig("azd_engine_set_dense_invx_recipe", C.c_int, vp, C.POINTER(DenseInvxRecipe))
     sig("azd_engine_dense_invx_argmin_data", C.c_int, vp, C.POINTER(DenseInvxArgmin))
     sig("azd_engine_dense_invx_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvxCost))

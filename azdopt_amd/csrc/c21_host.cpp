@@ -445,6 +445,9 @@ void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, De
 const char *dense_invx_check_graph(const uint64_t *adj, int n) {
     return ah_check_graph(adj, n, DENSE_INVX_MAX_N, "n: the extended invariant cost needs 4 <= n <= 32 (AZD_DENSE_INVX_MAX_N)");
 }
+const char *dense_invx_check_graph_wide(const uint64_t *adj, int n) {
+    return ah_check_graph(adj, n, DENSE_INVX_WIDE_MAX_N, "n: the wide extended invariant cost needs 4 <= n <= 64 (AZD_DENSE_INVX_WIDE_MAX_N)");
+}
 const char *dense_invx_check_recipe(const DenseInvxRecipe *r, int n) {
     if (!r) return "recipe: null";
     bool any = false;

@@ -125,8 +125,8 @@ const char *dense_inv_check_graph_wide(const uint64_t *adj, int n); // 4 <= n <=
 // n <= DENSE_INV_WIDE_MAX_N (one function behind azd_dense_inv_cost and azd_dense_inv_cost_wide: the limit is the callers' check)
 void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, DenseInvCost *out);
 
-// Extended invariant cost of a connected graph on 4 <= n <= DENSE_INVX_MAX_N vertices (BUILD-DEFINED; DESIGN.md "The extended
-// invariant cost"; AZD_ENGINE_DENSE_INVX): sixteen invariants -- index and name are ABI.  0 .. 9 are the weighted-invariant cost's;
+// Extended invariant cost of a connected graph on 4 <= n <= DENSE_INVX_MAX_N vertices, or DENSE_INVX_WIDE_MAX_N in the 64-row form
+// (BUILD-DEFINED; DESIGN.md "The extended invariant cost"; AZD_ENGINE_DENSE_INVX, AZD_ENGINE_DENSE_INVX_WIDE): sixteen invariants -- index and name are ABI.  0 .. 9 are the weighted-invariant cost's;
 //   10 lap_eig = eigenvalue of L = D - A at descending index lap_index   11 slap_eig = eigenvalue of Q = D + A at slap_index
 //   12 randic = sum_{uv in E} 1 / sqrt(d_u d_v): per vertex u, over its neighbours v < u ascending, x = 1.0 / sqrt((double)(d_u d_v)),
 //      (r, e) = TwoSum(r, x), c = c + e, one IEEE operation at a time (a compensated sum: the vertex's part r + c is right to an ulp;
@@ -139,6 +139,7 @@ void dense_inv_cost_host(const uint64_t *adj, int n, const DenseInvRecipe &r, De
 // (else 0.0, bit clear).  A divisor is one of DENSE_INVX_DIVISORS: positive on every connected graph with n >= 4, so the cost is
 // finite.  With weights 10 .. 15 zero and no term the sequence of operations is dense_inv_cost_host's.
 constexpr int DENSE_INVX_MAX_N = 32;
+constexpr int DENSE_INVX_WIDE_MAX_N = 64; // AZD_ENGINE_DENSE_INVX_WIDE engines, azd_dense_invx_cost_wide: the same procedure with 64 rows
 constexpr int DENSE_INVX_COUNT = 16;
 constexpr int DENSE_INVX_LAP_EIG = 10, DENSE_INVX_SLAP_EIG = 11, DENSE_INVX_RANDIC = 12, DENSE_INVX_ZAGREB1 = 13, DENSE_INVX_ZAGREB2 = 14,
               DENSE_INVX_TRIANGLES = 15;
@@ -175,6 +176,8 @@ constexpr uint32_t dense_invx_needed(const DenseInvxRecipe &r) {
 // nullptr when the recipe is acceptable for graphs on n vertices, else what is wrong with it (a field name leads the text)
 const char *dense_invx_check_recipe(const DenseInvxRecipe *r, int n);
 const char *dense_invx_check_graph(const uint64_t *adj, int n); // 4 <= n <= DENSE_INVX_MAX_N, in this cost's words
+const char *dense_invx_check_graph_wide(const uint64_t *adj, int n); // 4 <= n <= DENSE_INVX_WIDE_MAX_N
+// n <= DENSE_INVX_WIDE_MAX_N (one function behind azd_dense_invx_cost and azd_dense_invx_cost_wide: the limit is the callers' check)
 void dense_invx_cost_host(const uint64_t *adj, int n, const DenseInvxRecipe &r, DenseInvxCost *out);
 
 } // namespace azd

@@ -23,8 +23,10 @@
 // Each of the invariants 8 .. 15 is computed only when its weight is not zero or a pair term with a non-zero coefficient names it
 // (wave-uniform branches: the recipe is the same for all lanes): otherwise 0.0, and its bit of `computed` is clear.
 //
-// The row limit ROWS is a template parameter, as in dense_inv_cost.inc; only 32 is instantiated (DenseCostInvX:
-// dense_invx_kernels.hip, AZD_ENGINE_DENSE_INVX).
+// The row limit ROWS is a template parameter of everything here that depends on it, as in dense_inv_cost.inc: 32 (DenseCostInvX:
+// dense_invx_kernels.hip, AZD_ENGINE_DENSE_INVX) or 64 (DenseCostInvXWide: dense_invx_wide_kernels.hip, AZD_ENGINE_DENSE_INVX_WIDE
+// beside the first flag: a triangle of 2080 doubles serves the four passes), and the engine's argmin record follows from it.  Order
+// of operations, lane roles and reductions do not depend on it: at n <= 32 the two compute the same bits.
 __device__ __forceinline__ uint32_t dense_invx_sum_u32(uint32_t v) {
 #pragma unroll
     for (int w = 1; w < 64; w <<= 1) v += (uint32_t)__shfl_xor((int)v, w, 64);
@@ -35,11 +37,11 @@ __device__ __forceinline__ uint32_t dense_invx_sum_u32(uint32_t v) {
 template <int ROWS, class Hook>
 __device__ __forceinline__ void dense_invx_cost_wave(const uint64_t *adj, DenseAhLdsT<ROWS> &w, const int n, const DenseInvxRecipe *rc,
                                                      Hook &&hook, DenseInvxCost &out) {
-    static_assert(ROWS == DENSE_INVX_MAX_N, "only the 32-row form is built");
+    static_assert(ROWS == DENSE_INVX_MAX_N || ROWS == DENSE_INVX_WIDE_MAX_N, "the row limits that are built");
     const int lane = LANE;
     const int row = lane * (lane + 1) / 2; // this lane's row of the packed triangle (lanes < n only)
     const bool in = lane < n;
-    const uint64_t all = (1ull << n) - 1ull;
+    const uint64_t all = ROWS < 64 ? (1ull << n) - 1ull : ~0ull >> (64 - n); // (64 rows: n = 64 must not shift by 64; n >= 4)
     const uint32_t need = uni(dense_invx_needed(*rc));
     const bool need_dist = ((need >> DENSE_INV_DIST_EIG) & 1u) != 0u;
     const int dist_index = (int)uni((uint32_t)rc->dist_index);
@@ -250,8 +252,8 @@ __device__ __forceinline__ void dense_invx_cost_wave(const uint64_t *adj, DenseA
 }
 
 // ---------------------------------------------------------------- the extended invariant cost as a DenseSpace's cost policy (space_dense.inc)
-// A wave's block is the 32-row AH block (DenseAhSpaceLdsT<KW, 32>), so the pool step plans the INV tier's 10 / 9 / 7 waves at key
-// widths 2 / 4 / 10.  4 <= n <= 32, so E <= 496.
+// A wave's block is the AH block of the same row limit (DenseAhSpaceLdsT<KW, ROWS>), so at 32 rows the pool step plans the INV tier's
+// 10 / 9 / 7 waves at key widths 2 / 4 / 10, at 64 rows what the LDS holds, as the INV-wide tier.  4 <= n <= ROWS, so E <= 496 or 2016.
 // The recipe lies in device memory behind the per-agent cost arrays, as the INV tier's does.  An agent's record between launches:
 //   cur_lambda[i B + t] = I_i, i = 0 .. 15;  cur_lambda + 16 B: the engine's DenseInvxRecipe (azd_engine_set_dense_invx_recipe)
 //   cur_mu[t] = the distance index used, cur_mu[B + t] = the `computed` mask.  No per-node arena: node_mate is null.
@@ -261,7 +263,7 @@ __device__ __forceinline__ const DenseInvxRecipe *dense_invx_recipe(const Arenas
 }
 template <int ROWS>
 struct DenseCostInvXT {
-    using ArgminRec = DenseInvxArgminRec; // (what engine.hip sizes argmin_d for)
+    using ArgminRec = std::conditional_t<ROWS == DENSE_INVX_MAX_N, DenseInvxArgminRec, DenseInvxWideArgminRec>; // (what engine.hip sizes argmin_d for)
     template <int KW_>
     using Lds = DenseAhSpaceLdsT<KW_, ROWS>;
     template <int KW_>
@@ -324,12 +326,14 @@ struct DenseCostInvXT {
         }
     }
 };
-// A named struct, not an alias: the kernels' names carry it (k_rollout<DenseSpace<2, DenseCostInvX>>)
+// Named structs, not aliases: the kernels' names carry them (k_rollout<DenseSpace<2, DenseCostInvX>>)
 struct DenseCostInvX : DenseCostInvXT<DENSE_INVX_MAX_N> {};
+struct DenseCostInvXWide : DenseCostInvXT<DENSE_INVX_WIDE_MAX_N> {};
 
-// The cost outside any engine (space_ops.h: launch_probe_invx_cost): one wave per graph, `reps` repetitions (timing), the result
-// of the last one.  The host has checked the graphs and the recipe (engine_probes.hip): LDS is indexed by the bits of adj, and the
-// pair terms' indices pick among sixteen registers.
+// The cost outside any engine (space_ops.h: launch_probe_invx_cost, launch_probe_invx_cost_wide): one wave per graph, `reps`
+// repetitions (timing), the result of the last one.  Each unit launches the instantiation of its own row limit.  The host has
+// checked the graphs and the recipe (engine_probes.hip): LDS is indexed by the bits of adj, and the pair terms' indices pick among
+// sixteen registers.
 template <int ROWS>
 __global__ __launch_bounds__(64) void k_probe_invx_cost(const uint64_t *__restrict__ adj, const int n, const int count, const int reps,
                                                         const DenseInvxRecipe *__restrict__ recipe, DenseInvxCost *__restrict__ out) {

@@ -62,12 +62,12 @@ int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks) {
     return AZD_OK;
 }
 // The LDS plan of the searcher-only pool step for a configuration (AZD_ENGINE_EXT_POOL_STEP, or a dense-graph engine with
-// AZD_ENGINE_DENSE_AH_WIDE or AZD_ENGINE_DENSE_INV_WIDE, whose pool step is planned by what the LDS holds too): wavefronts per
+// AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV_WIDE or AZD_ENGINE_DENSE_INVX_WIDE, whose pool step is planned by what the LDS holds too): wavefronts per
 // searcher workgroup and bytes of LDS a workgroup takes, its static blocks included.  Arithmetic only: no device is touched.
 int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes) {
     if (!cfg || !waves || !lds_bytes) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ST(check_engine_config(cfg));
-    const bool ah_wide = (cfg->flags & (AZD_ENGINE_DENSE_AH_WIDE | AZD_ENGINE_DENSE_INV_WIDE)) != 0; // (the 64-row tiers)
+    const bool ah_wide = (cfg->flags & (AZD_ENGINE_DENSE_AH_WIDE | AZD_ENGINE_DENSE_INV_WIDE | AZD_ENGINE_DENSE_INVX_WIDE)) != 0; // (the 64-row tiers)
     // (a dense-graph configuration that sets AZD_ENGINE_EXT_POOL_F32 alone asks its pool step for the fp32 evaluator: the plan is
     // that step's, whatever the cost -- the searchers do not know which evaluator serves them)
     const bool dense_f32 = cfg->space_id == AZD_SPACE_DENSE && (cfg->flags & AZD_ENGINE_EXT_POOL_F32) != 0;
@@ -342,12 +342,12 @@ int azd_debug_probe_inv_cost_wide(int device, const uint64_t *adj, int n, int co
     return probe_inv_cost("azd_debug_probe_inv_cost_wide", true, device, adj, n, count, reps, recipe, out, ms);
 }
 // ------------------------------------------------------------------ extended invariant cost of the dense-graph space
-static_assert(AZD_DENSE_INVX_MAX_N == azd::DENSE_INVX_MAX_N && AZD_DENSE_INVX_COUNT == azd::DENSE_INVX_COUNT && AZD_DENSE_INVX_MAX_TERMS == azd::DENSE_INVX_MAX_TERMS &&
+static_assert(AZD_DENSE_INVX_MAX_N == azd::DENSE_INVX_MAX_N && AZD_DENSE_INVX_WIDE_MAX_N == azd::DENSE_INVX_WIDE_MAX_N && AZD_DENSE_INVX_COUNT == azd::DENSE_INVX_COUNT && AZD_DENSE_INVX_MAX_TERMS == azd::DENSE_INVX_MAX_TERMS &&
                   AZD_DENSE_INVX_MUL == azd::DENSE_INVX_MUL && AZD_DENSE_INVX_DIV == azd::DENSE_INVX_DIV,
               "AZD_DENSE_INVX_*");
 // graph `i` (or the only one) and the recipe, checked in this order; the text names `fn` and the argument
-static int invx_check(const char *fn, const uint64_t *adj, int n, int i, const azd_dense_invx_recipe *recipe) {
-    const char *why = azd::dense_invx_check_graph(adj, n);
+static int invx_check(const char *fn, bool wide, const uint64_t *adj, int n, int i, const azd_dense_invx_recipe *recipe) {
+    const char *why = wide ? azd::dense_invx_check_graph_wide(adj, n) : azd::dense_invx_check_graph(adj, n);
     if (!why) why = azd::dense_invx_check_recipe(reinterpret_cast<const azd::DenseInvxRecipe *>(recipe), n);
     else if (i >= 0) {
         azd::g_last_error = std::string(fn) + ": graph " + std::to_string(i) + ": " + why;
@@ -361,19 +361,29 @@ int azd_dense_invx_cost(const uint64_t *adj, int n, const azd_dense_invx_recipe 
         azd::g_last_error = "azd_dense_invx_cost: out: null";
         return AZD_ERR_INVALID_ARGUMENT;
     }
-    AZD_ST(invx_check("azd_dense_invx_cost", adj, n, -1, recipe));
+    AZD_ST(invx_check("azd_dense_invx_cost", false, adj, n, -1, recipe));
     azd::dense_invx_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvxRecipe *>(recipe), reinterpret_cast<azd::DenseInvxCost *>(out));
     return AZD_OK;
 }
-int azd_debug_probe_invx_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
-                              azd_dense_invx_cost_t *out, float *ms) {
-    const char *name = "azd_debug_probe_invx_cost";
+int azd_dense_invx_cost_wide(const uint64_t *adj, int n, const azd_dense_invx_recipe *recipe, azd_dense_invx_cost_t *out) {
+    if (!out) {
+        azd::g_last_error = "azd_dense_invx_cost_wide: out: null";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    AZD_ST(invx_check("azd_dense_invx_cost_wide", true, adj, n, -1, recipe));
+    azd::dense_invx_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvxRecipe *>(recipe), reinterpret_cast<azd::DenseInvxCost *>(out));
+    return AZD_OK;
+}
+// the two probes: the same host side around the 32-row and the 64-row kernel
+static int probe_invx_cost(const char *name, bool wide, int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
+                           azd_dense_invx_cost_t *out, float *ms) {
+    const auto launch = wide ? azd::launch_probe_invx_cost_wide : azd::launch_probe_invx_cost;
     if (!out || count <= 0 || reps <= 0) {
         azd::g_last_error = std::string(name) + ": out / count / reps";
         return AZD_ERR_INVALID_ARGUMENT;
     }
     for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
-        AZD_ST(invx_check(name, adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n, i, recipe));
+        AZD_ST(invx_check(name, wide, adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n, i, recipe));
     AZD_ST(azd::device_ok(device));
     AZD_HIP(hipSetDevice(device));
     azd::DevBuf<uint64_t> d_adj;
@@ -385,9 +395,9 @@ int azd_debug_probe_invx_cost(int device, const uint64_t *adj, int n, int count,
     AZD_ST(e1.create());
     AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
     AZD_HIP(hipMemcpy(d_recipe, recipe, sizeof(azd::DenseInvxRecipe), hipMemcpyHostToDevice));
-    azd::launch_probe_invx_cost(d_adj, n, count, 1, d_recipe, d_out, nullptr); // warm-up
+    launch(d_adj, n, count, 1, d_recipe, d_out, nullptr); // warm-up
     AZD_HIP(hipEventRecord(e0, nullptr));
-    azd::launch_probe_invx_cost(d_adj, n, count, reps, d_recipe, d_out, nullptr);
+    launch(d_adj, n, count, reps, d_recipe, d_out, nullptr);
     AZD_HIP(hipEventRecord(e1, nullptr));
     hipError_t he = hipDeviceSynchronize();
     float t = 0.f;
@@ -396,6 +406,14 @@ int azd_debug_probe_invx_cost(int device, const uint64_t *adj, int n, int count,
     if (he != hipSuccess) return azd::hip_fail(he, "probe_invx_cost");
     if (ms) *ms = t;
     return AZD_OK;
+}
+int azd_debug_probe_invx_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
+                              azd_dense_invx_cost_t *out, float *ms) {
+    return probe_invx_cost("azd_debug_probe_invx_cost", false, device, adj, n, count, reps, recipe, out, ms);
+}
+int azd_debug_probe_invx_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
+                                   azd_dense_invx_cost_t *out, float *ms) {
+    return probe_invx_cost("azd_debug_probe_invx_cost_wide", true, device, adj, n, count, reps, recipe, out, ms);
 }
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
     if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;

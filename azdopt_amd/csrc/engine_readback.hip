@@ -87,17 +87,20 @@ int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap,
 }
 // The dense argmin entries: `reads` is the tier whose record the entry copies out, `refusal` its text for an engine of another
 // tier -- said to an engine with the Aouchiche-Hansen cost (an engine without it is refused without a text), by the wide entry to all.
-// The two weighted-invariant tiers name each other's reader, as the two Aouchiche-Hansen tiers do.
+// The two weighted-invariant tiers name each other's reader, as the two Aouchiche-Hansen tiers do, and so do the two extended ones.
 static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes, const char *refusal) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (e->tier->id != reads) {
-        if (e->tier->id == TIER_DENSE_INVX)
+        if (e->tier->id == TIER_DENSE_INVX_WIDE)
+            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVX_WIDE engine's record is read with azd_engine_dense_invx_wide_argmin_data";
+        else if (e->tier->id == TIER_DENSE_INVX)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_argmin_data";
         else if (e->tier->id == TIER_DENSE_INV_WIDE)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INV_WIDE engine's record is read with azd_engine_dense_inv_wide_argmin_data";
         else if (e->tier->id == TIER_DENSE_INV)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_argmin_data";
-        else if (e->tier->ah || reads == TIER_DENSE_AH_WIDE || reads == TIER_DENSE_INV || reads == TIER_DENSE_INV_WIDE || reads == TIER_DENSE_INVX)
+        else if (e->tier->ah || reads == TIER_DENSE_AH_WIDE || reads == TIER_DENSE_INV || reads == TIER_DENSE_INV_WIDE || reads == TIER_DENSE_INVX ||
+                 reads == TIER_DENSE_INVX_WIDE)
             azd::g_last_error = refusal;
         return AZD_ERR_UNSUPPORTED;
     }
@@ -116,6 +119,9 @@ static_assert(sizeof(azd_dense_argmin) == sizeof(azd::DenseArgminRec) && sizeof(
                   offsetof(azd_dense_inv_wide_argmin, inv) == offsetof(azd::DenseInvWideArgminRec, inv) &&
                   sizeof(azd_dense_invx_argmin) == sizeof(azd::DenseInvxArgminRec) && offsetof(azd_dense_invx_argmin, node) == offsetof(azd::DenseInvxArgminRec, node) &&
                   offsetof(azd_dense_invx_argmin, inv) == offsetof(azd::DenseInvxArgminRec, inv) &&
+                  sizeof(azd_dense_invx_wide_argmin) == sizeof(azd::DenseInvxWideArgminRec) &&
+                  offsetof(azd_dense_invx_wide_argmin, node) == offsetof(azd::DenseInvxWideArgminRec, node) &&
+                  offsetof(azd_dense_invx_wide_argmin, inv) == offsetof(azd::DenseInvxWideArgminRec, inv) &&
                   sizeof(azd_dense_invx_recipe) == sizeof(azd::DenseInvxRecipe) && offsetof(azd_dense_invx_recipe, n_terms) == offsetof(azd::DenseInvxRecipe, n_terms) &&
                   offsetof(azd_dense_invx_recipe, term) == offsetof(azd::DenseInvxRecipe, term) && sizeof(azd_dense_invx_term) == sizeof(azd::DenseInvxTerm) &&
                   offsetof(azd_dense_invx_term, op) == offsetof(azd::DenseInvxTerm, op) &&
@@ -145,7 +151,7 @@ int azd_engine_dense_inv_wide_argmin_data(azd_engine *e, azd_dense_inv_wide_argm
 int azd_engine_set_dense_inv_recipe(azd_engine *e, const azd_dense_inv_recipe *recipe) {
     if (!e) return AZD_ERR_INVALID_ARGUMENT;
     if (!tier_inv(e->tier)) {
-        azd::g_last_error = e->tier->id == TIER_DENSE_INVX ? "azd_engine_set_dense_inv_recipe: an AZD_ENGINE_DENSE_INVX engine's recipe is set with azd_engine_set_dense_invx_recipe"
+        azd::g_last_error = tier_invx(e->tier) ? "azd_engine_set_dense_inv_recipe: an AZD_ENGINE_DENSE_INVX engine's recipe is set with azd_engine_set_dense_invx_recipe"
                                                            : "azd_engine_set_dense_inv_recipe: not an AZD_ENGINE_DENSE_INV engine";
         return AZD_ERR_UNSUPPORTED;
     }
@@ -167,7 +173,7 @@ int azd_engine_set_dense_inv_recipe(azd_engine *e, const azd_dense_inv_recipe *r
 int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
     if (!tier_inv(e->tier)) {
-        azd::g_last_error = e->tier->id == TIER_DENSE_INVX ? "azd_engine_dense_inv_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost"
+        azd::g_last_error = tier_invx(e->tier) ? "azd_engine_dense_inv_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost"
                                                            : "azd_engine_dense_inv_agent_cost: not an AZD_ENGINE_DENSE_INV engine";
         return AZD_ERR_UNSUPPORTED;
     }
@@ -189,14 +195,18 @@ int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost
     out->eval = r.eval_scale * (out->cost + r.eval_offset);
     return AZD_OK;
 }
-// The extended invariant cost's three entries, in the image of the weighted-invariant cost's: the recipe behind the sixteen per-agent
-// doubles of cur_lambda (dense_invx_cost.inc: dense_invx_recipe), the argmin record, an agent's record
+// The extended invariant cost's entries, in the image of the weighted-invariant cost's: the recipe behind the sixteen per-agent
+// doubles of cur_lambda (dense_invx_cost.inc: dense_invx_recipe; either row limit, the indices checked at the engine's n), the argmin
+// record of each row limit, an agent's record
 int azd_engine_dense_invx_argmin_data(azd_engine *e, azd_dense_invx_argmin *out) {
     return dense_argmin_read(e, out, TIER_DENSE_INVX, sizeof(*out), "azd_engine_dense_invx_argmin_data: not an AZD_ENGINE_DENSE_INVX engine");
 }
+int azd_engine_dense_invx_wide_argmin_data(azd_engine *e, azd_dense_invx_wide_argmin *out) {
+    return dense_argmin_read(e, out, TIER_DENSE_INVX_WIDE, sizeof(*out), "azd_engine_dense_invx_wide_argmin_data: not an AZD_ENGINE_DENSE_INVX_WIDE engine");
+}
 int azd_engine_set_dense_invx_recipe(azd_engine *e, const azd_dense_invx_recipe *recipe) {
     if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->tier->id != TIER_DENSE_INVX) {
+    if (!tier_invx(e->tier)) {
         azd::g_last_error = tier_inv(e->tier) ? "azd_engine_set_dense_invx_recipe: an AZD_ENGINE_DENSE_INV engine's recipe is set with azd_engine_set_dense_inv_recipe"
                                               : "azd_engine_set_dense_invx_recipe: not an AZD_ENGINE_DENSE_INVX engine";
         return AZD_ERR_UNSUPPORTED;
@@ -218,7 +228,7 @@ int azd_engine_set_dense_invx_recipe(azd_engine *e, const azd_dense_invx_recipe 
 }
 int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->tier->id != TIER_DENSE_INVX) {
+    if (!tier_invx(e->tier)) {
         azd::g_last_error = tier_inv(e->tier) ? "azd_engine_dense_invx_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost"
                                               : "azd_engine_dense_invx_agent_cost: not an AZD_ENGINE_DENSE_INVX engine";
         return AZD_ERR_UNSUPPORTED;
@@ -250,7 +260,7 @@ int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_co
 }
 int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->tier->id == TIER_DENSE_INVX) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost";
+    if (tier_invx(e->tier)) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost";
     if (tier_inv(e->tier)) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost";
     if (!e->tier->ah) return AZD_ERR_UNSUPPORTED;
     AZD_ENTER(e);
@@ -382,7 +392,7 @@ int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t 
     AZD_HIP(hipStreamSynchronize(e->stream));
     const azd::Arenas &a = e->a;
     if (a.space == azd::SPACE_DENSE) { // `parents` receives the neighbourhoods (8 n bytes); masks are kw_host words
-        if (e->tier->id == TIER_DENSE_INVX && (lambda_1 || matching_size)) {
+        if (tier_invx(e->tier) && (lambda_1 || matching_size)) {
             azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_INVX engine keeps neither (azd_engine_dense_invx_agent_cost)";
             return AZD_ERR_UNSUPPORTED;
         }

@@ -72,6 +72,7 @@ const SpaceOps &dense_ah_wide_ops();                            // ... with its 
 const SpaceOps &dense_inv_ops();                                // ... with the weighted-invariant cost (dense_inv_kernels.hip: AZD_ENGINE_DENSE_INV)
 const SpaceOps &dense_inv_wide_ops();                           // ... with its 64-row form (dense_inv_wide_kernels.hip: AZD_ENGINE_DENSE_INV_WIDE)
 const SpaceOps &dense_invx_ops();                               // ... with the extended invariant cost (dense_invx_kernels.hip: AZD_ENGINE_DENSE_INVX)
+const SpaceOps &dense_invx_wide_ops();                          // ... with its 64-row form (dense_invx_wide_kernels.hip: AZD_ENGINE_DENSE_INVX_WIDE)
 constexpr size_t POOL_SEARCH_STATIC_LDS = 16; // k_pool_search's static LDS (PoolIdle) beside the dynamic region the plans lay out
 
 // ---- the same for every space
@@ -107,6 +108,7 @@ void launch_probe_inv_cost_wide(const uint64_t *d_adj, int n, int count, int rep
 struct DenseInvxRecipe;
 struct DenseInvxCost;
 void launch_probe_invx_cost(const uint64_t *d_adj, int n, int count, int reps, const DenseInvxRecipe *d_recipe, DenseInvxCost *d_out, void *stream); // (dense_invx_kernels.hip)
+void launch_probe_invx_cost_wide(const uint64_t *d_adj, int n, int count, int reps, const DenseInvxRecipe *d_recipe, DenseInvxCost *d_out, void *stream); // n <= 64 (dense_invx_wide_kernels.hip)
 
 // ---- the evaluator's side of the searcher-only pool step and the recovery of an aborted launch (dense_kernels.hip; for every space that has the form)
 void launch_ext_take(const PoolArgs &pool, uint32_t *rows, uint32_t *home, uint32_t *n, unsigned long long *t0, void *stream);

@@ -335,11 +335,12 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     `cost=InvariantCostX(...)`: the extended invariant cost (AZD_ENGINE_DENSE_INVX, N <= 32, a tier of its own with the
     InvariantCost tier's limits): sixteen invariants -- Laplacian and signless-Laplacian eigenvalues, Randic and Zagreb indices and
     the triangle count beside the ten -- and products or quotients of two of them.  InvariantCostX.from_invariant_cost(c) gives
-    cost=c's trees."""
+    cost=c's trees.  `invx_wide=True` (with an InvariantCostX only): that cost's 64-row form, N <= 64 (AZD_ENGINE_DENSE_INVX_WIDE
+    beside the first flag; never chosen from N), roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives."""
 
     SPACE_ID = _lib.SPACE_DENSE
 
-    def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False, inv_wide=False):
+    def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False, inv_wide=False, invx_wide=False):
         self.INV = cost if isinstance(cost, InvariantCost) else None
         self.INVX = cost if isinstance(cost, InvariantCostX) else None
         if self.INV is not None:
@@ -352,14 +353,18 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
             raise ValueError('ah_wide=True needs cost="ah" (it is the Aouchiche-Hansen cost\'s 64-row form)')
         if inv_wide and cost != "inv":
             raise ValueError("inv_wide=True needs cost=InvariantCost(...) (it is the weighted-invariant cost's 64-row form)")
+        if invx_wide and cost != "invx":
+            raise ValueError("invx_wide=True needs cost=InvariantCostX(...) (it is the extended invariant cost's 64-row form)")
         self.COST = cost
         self.AH_WIDE = bool(ah_wide)
         self.INV_WIDE = bool(inv_wide)
+        self.INVX_WIDE = bool(invx_wide)
         self.n, self.p = int(n), float(p)
         self.E = self.n * (self.n - 1) // 2
         # (an AZD_ENGINE_DENSE_AH engine refuses max_slots > E; a root cannot bring more than E slots anyway)
-        # (... and an AZD_ENGINE_DENSE_AH_WIDE or AZD_ENGINE_DENSE_INV_WIDE engine max_slots > min(E, 640): its keys are 2, 4 or 10 words)
-        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide or inv_wide else min(int(max_slots), self.E) if cost in ("ah", "inv", "invx") else int(max_slots)
+        # (... and an AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV_WIDE or AZD_ENGINE_DENSE_INVX_WIDE engine max_slots > min(E, 640): its
+        # keys are 2, 4 or 10 words)
+        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide or inv_wide or invx_wide else min(int(max_slots), self.E) if cost in ("ah", "inv", "invx") else int(max_slots)
         L = _lib.lib()
         self.STATE_DIM = L.azd_dense_state_dim(self.n)
         self.ACTION_DIM = L.azd_dense_action_dim(self.n)
@@ -418,15 +423,19 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
         return dict(InvariantCost.record(out), eval=np.float32(out.eval))
 
     def invx_cost(self, adj, cost=None):
-        """The extended invariant cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_invx_cost under this
-        space's recipe (or `cost`, another InvariantCostX), the same procedure as the device's, bit for bit.
+        """The extended invariant cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_invx_cost
+        (azd_dense_invx_cost_wide for an invx_wide space) under this space's recipe (or `cost`, another InvariantCostX), the same
+        procedure as the device's, bit for bit.
         -> dict(the sixteen invariants by name, dist_k, computed, cost, eval)"""
         cost = self.INVX if cost is None else cost
         if cost is None:
             raise ValueError("invx_cost: the space has no InvariantCostX; pass one")
         a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
         out, r = _lib.DenseInvxCost(), cost.recipe()
-        _lib.check(_lib.lib().azd_dense_invx_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_invx_cost")
+        if getattr(self, "INVX_WIDE", False):
+            _lib.check(_lib.lib().azd_dense_invx_cost_wide(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_invx_cost_wide")
+        else:
+            _lib.check(_lib.lib().azd_dense_invx_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_invx_cost")
         return dict(InvariantCostX.record(out), eval=np.float32(out.eval))
 
 

@@ -3,10 +3,11 @@
 that minimises a linear combination of graph invariants -- the shape of an AutoGraphiX conjecture, "a combination of invariants is
 bounded below by ..." -- on the MI355X engine's weighted-invariant cost (AZD_ENGINE_DENSE_INV, N <= 32; with --wide its 64-row
 form, AZD_ENGINE_DENSE_INV_WIDE, N <= 64, which is asked for by name and never chosen from N; with --extended the extended
-invariant cost, AZD_ENGINE_DENSE_INVX, N <= 32: sixteen invariants and products or quotients of two of them).
+invariant cost, AZD_ENGINE_DENSE_INVX, N <= 32: sixteen invariants and products or quotients of two of them; with both flags that
+cost's 64-row form, AZD_ENGINE_DENSE_INVX_WIDE, N <= 64).
 
     python examples/invariants.py --recipe '{"weights": {"remoteness": 1, "proximity": -1}, "eval_offset": 2, "eval_scale": 0.02}'
-                                  [--n 31] [--wide | --extended] [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
+                                  [--n 31] [--wide] [--extended] [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
 
 --recipe is a JSON object: "weights" (name -> weight over edges, max_degree, min_degree, diameter, radius, proximity, remoteness,
 avg_distance, adj_eig, dist_eig), and optionally "bias", "adj_index", "dist_index" (a descending index or "ah"), "eval_offset",
@@ -38,7 +39,7 @@ def main():
     ap.add_argument("--recipe", required=True, help='a JSON object (see above), or "ah"')
     ap.add_argument("--n", type=int, default=31)
     ap.add_argument("--wide", action="store_true", help="the cost's 64-row form (N <= 64)")
-    ap.add_argument("--extended", action="store_true", help="the extended invariant cost: sixteen invariants, pair terms (N <= 32)")
+    ap.add_argument("--extended", action="store_true", help="the extended invariant cost: sixteen invariants, pair terms (N <= 32; N <= 64 with --wide)")
     ap.add_argument("--epochs", type=int, default=250)
     ap.add_argument("--episodes", type=int, default=800)
     ap.add_argument("--batch", type=int, default=512)
@@ -48,14 +49,13 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
 
-    if args.extended and args.wide:
-        ap.error("--extended has no 64-row form: it cannot be combined with --wide")
     cost = az.InvariantCost.aouchiche_hansen(args.n) if args.recipe == "ah" else None
     if args.extended:
         cost = az.InvariantCostX.from_invariant_cost(cost) if cost is not None else az.InvariantCostX.from_dict(json.loads(args.recipe))
     elif cost is None:
         cost = az.InvariantCost.from_dict(json.loads(args.recipe))
-    space = az.DenseGraphSpace(args.n, P, max_slots=args.max_slots, cost=cost, inv_wide=args.wide)
+    wide = dict(invx_wide=True) if args.wide and args.extended else dict(inv_wide=args.wide)
+    space = az.DenseGraphSpace(args.n, P, max_slots=args.max_slots, cost=cost, **wide)
     model = az.ActionModel(args.batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=1e-4, l2=1e-6, seed=args.seed,
                            dtype=args.dtype)
     kmin, kmax = space.default_permitted_range()

@@ -344,6 +344,20 @@ typedef struct azd_engine_config {
  * azd_engine_dense_invx_argmin_data.  The INV, AH and default reads and the INV setter are AZD_ERR_UNSUPPORTED on it and name the
  * right call, and the INVX calls on an AZD_ENGINE_DENSE_INV engine likewise. */
 #define AZD_ENGINE_DENSE_INVX 4096u
+/* Beside AZD_ENGINE_DENSE_INVX only (alone, beside any AZD_ENGINE_DENSE_AH* or AZD_ENGINE_DENSE_INV* flag, or on another space:
+ * AZD_ERR_INVALID_ARGUMENT naming the argument): the extended invariant cost up to 64 vertices, the dense-graph space's own limit
+ * -- the device procedure with 64 rows (one packed triangle of 2080 doubles serves the four spectral passes), in kernels of their
+ * own (dense_invx_wide_kernels.hip); the 32-row kernels and every engine without the flag are what they are without it.  Never
+ * chosen from the sizes.  Limits: 4 <= n <= AZD_DENSE_INVX_WIDE_MAX_N, layers <= 1, ActionSet paths, 1 <= max_slots <= min(E, 640)
+ * (key widths 2, 4 and 10; roots of more than 640 slots are out of scope); AZD_ENGINE_EXT_POOL_F32 is accepted beside it.  A wide
+ * engine on n <= 32 is accepted and gives the trees the narrow engine gives; under a weighted-invariant recipe it gives the trees
+ * of an AZD_ENGINE_DENSE_INV_WIDE engine.  azd_engine_set_dense_invx_recipe (indices checked against 0 .. n - 1 at the engine's n)
+ * and azd_engine_dense_invx_agent_cost serve both tiers.  Its argmin record is azd_dense_invx_wide_argmin, read with
+ * azd_engine_dense_invx_wide_argmin_data (azd_engine_dense_invx_argmin_data is AZD_ERR_UNSUPPORTED on it and names that call, and
+ * the reverse; the INV, AH and default reads likewise).  Pool step: a searcher wave's LDS block is the AZD_ENGINE_DENSE_AH_WIDE
+ * tier's, so a searcher workgroup has the 6 wavefronts it has there (azd_debug_ext_pool_plan reports the plan for such a
+ * configuration too). */
+#define AZD_ENGINE_DENSE_INVX_WIDE 8192u
 /* Beside AZD_ENGINE_RAMSEY_U64 only (alone, on another space or on a 32-bit tier: AZD_ERR_INVALID_ARGUMENT naming both flags): the
  * 64-bit tier with forbidden cliques up to K8 -- clique sizes 2..AZD_RAMSEY_BIG_CLIQUE_MAX, the reference's count_cliques_inside
  * (bitset_graph/mod.rs:164-185) to depth 6 in kernels of their own; the 64-bit tier's kernels and every engine without the flag are
@@ -385,7 +399,7 @@ typedef struct azd_engine_config {
  * 512 agents 0.99 against 0.52 M expansions/s, r45 at 256 agents 1.03 against 0.31 M on the wide tier and 0.79 against 0.25 M on the
  * 64-bit tier.
  * AZD_SPACE_DENSE: the space's pool step is the searcher-only form and needs no flag of its own, so there this flag stands alone, on
- * all six tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
+ * all seven tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX, AZD_ENGINE_DENSE_INVX_WIDE); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
  * this flag beside AZD_ENGINE_NO_PERSISTENT_STEP is AZD_ERR_INVALID_ARGUMENT naming both.  It is a request to the configured pool
  * step, not a form: where the engine's form is not the pool step (fewer than 256 agents without AZD_ENGINE_POOL_STEP) nothing
  * changes and azd_engine_step_form gives the reason it gave.  With it an fp32 MLP is served by the same gathered fp32 GEMMs over the
@@ -891,6 +905,8 @@ int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost
  * so the cost is always finite.  With weights 10 .. 15 zero and n_terms 0 the sequence of operations is the weighted-invariant
  * cost's: inv[0 .. 9], dist_k, cost and eval are azd_dense_inv_cost's bit for bit. */
 #define AZD_DENSE_INVX_MAX_N 32
+/* ... of the 64-row form, which has names of its own: azd_dense_invx_cost_wide, AZD_ENGINE_DENSE_INVX_WIDE */
+#define AZD_DENSE_INVX_WIDE_MAX_N 64
 #define AZD_DENSE_INVX_COUNT 16
 #define AZD_DENSE_INVX_MAX_TERMS 4
 #define AZD_DENSE_INVX_MUL 0
@@ -923,10 +939,16 @@ typedef struct azd_dense_invx_cost_t {
 /* The cost on the host; needs no GPU.  The graph is checked like azd_dense_inv_cost's, the recipe like
  * azd_engine_set_dense_invx_recipe's: AZD_ERR_INVALID_ARGUMENT naming the argument or field. */
 int azd_dense_invx_cost(const uint64_t *adj, int n, const azd_dense_invx_recipe *recipe, azd_dense_invx_cost_t *out);
+/* The same host function for 4 <= n <= AZD_DENSE_INVX_WIDE_MAX_N: the same sequence of IEEE f64 operations, the same graph and
+ * recipe checks (the indices against 0 .. n - 1); at n <= 32 the same bytes as azd_dense_invx_cost. */
+int azd_dense_invx_cost_wide(const uint64_t *adj, int n, const azd_dense_invx_recipe *recipe, azd_dense_invx_cost_t *out);
 /* The device kernel in isolation, as azd_debug_probe_inv_cost: graphs and recipe are checked before the device is looked for. */
 int azd_debug_probe_invx_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
                               azd_dense_invx_cost_t *out, float *ms);
-/* The recipe of an AZD_ENGINE_DENSE_INVX engine: set once, between azd_engine_create and the first par_new (par_new without it is
+/* ... and the 64-row kernel (AZD_ENGINE_DENSE_INVX_WIDE engines' cost), 4 <= n <= AZD_DENSE_INVX_WIDE_MAX_N; checked the same way */
+int azd_debug_probe_invx_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
+                                   azd_dense_invx_cost_t *out, float *ms);
+/* The recipe of an AZD_ENGINE_DENSE_INVX engine (with or without AZD_ENGINE_DENSE_INVX_WIDE): set once, between azd_engine_create and the first par_new (par_new without it is
  * refused and names this call; after par_new this call is AZD_ERR_INVALID_ARGUMENT).  AZD_ERR_INVALID_ARGUMENT naming the field:
  * a weight, coefficient, the bias, eval_offset or eval_scale not finite; eval_scale 0; all weights and all coefficients zero;
  * n_terms outside 0 .. 4; a term's a or b outside 0 .. 15, its op unknown, or a divisor outside 0 .. 7, 12, 13, 14; an index
@@ -945,6 +967,19 @@ typedef struct azd_dense_invx_argmin {
     uint32_t node;
 } azd_dense_invx_argmin;
 int azd_engine_dense_invx_argmin_data(azd_engine *e, azd_dense_invx_argmin *out);
+/* ArgminData of an engine with AZD_ENGINE_DENSE_INVX_WIDE beside AZD_ENGINE_DENSE_INVX (on any other engine: AZD_ERR_UNSUPPORTED) */
+typedef struct azd_dense_invx_wide_argmin {
+    uint64_t adj[64];
+    uint64_t permitted[32]; /* modifiable slots (colex positions) still open; E <= 2016 */
+    double inv[AZD_DENSE_INVX_COUNT];
+    int32_t dist_k;
+    uint32_t computed;
+    float cost;
+    float eval;
+    int32_t agent;
+    uint32_t node;
+} azd_dense_invx_wide_argmin;
+int azd_engine_dense_invx_wide_argmin_data(azd_engine *e, azd_dense_invx_wide_argmin *out);
 /* the cost record of agent `agent`'s current state as the engine keeps it (cost and eval recomputed from the kept invariants) */
 int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_cost_t *out);
 /* Parity probe for the f64 primitives the AH cost depends on bit for bit.  in: 2*n doubles (pairs x, y); out: 3*n doubles per

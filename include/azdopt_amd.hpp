@@ -338,23 +338,29 @@ private:
 
 // The same space with the extended invariant cost as the objective (AZD_ENGINE_DENSE_INVX): n <= AZD_DENSE_INVX_MAX_N,
 // max_slots <= E; par_new hands the recipe to the engine.  argmin_data() gives a DenseInvxArgmin.
+// wide = true: the cost's 64-row form (AZD_ENGINE_DENSE_INVX_WIDE beside the first flag; asked for by name, never chosen from n):
+// n <= AZD_DENSE_INVX_WIDE_MAX_N, max_slots <= min(E, 640); at n <= 32 it gives what the narrow form gives.
 class DenseGraphInvXSpace : public DenseGraphSpace {
 public:
-    DenseGraphInvXSpace(int n, double p, int max_slots, const InvariantCostX &cost) : DenseGraphSpace(n, p, max_slots), cost_(cost) {}
+    DenseGraphInvXSpace(int n, double p, int max_slots, const InvariantCostX &cost, bool wide = false)
+        : DenseGraphSpace(n, p, max_slots), cost_(cost), wide_(wide) {}
     const InvariantCostX &invariant_cost() const { return cost_; }
+    bool wide() const { return wide_; }
     void configure(azd_engine_config &cfg) const {
         DenseGraphSpace::configure(cfg);
-        cfg.flags |= AZD_ENGINE_DENSE_INVX;
+        cfg.flags |= AZD_ENGINE_DENSE_INVX | (wide_ ? AZD_ENGINE_DENSE_INVX_WIDE : 0u);
     }
     // the cost of one connected graph on the host (adj: n neighbourhood bitsets): the device's procedure, bit for bit
     azd_dense_invx_cost_t cost(const uint64_t *adj) const {
         azd_dense_invx_cost_t c;
-        check(azd_dense_invx_cost(adj, n(), &cost_.recipe(), &c), "azd_dense_invx_cost");
+        if (wide_) check(azd_dense_invx_cost_wide(adj, n(), &cost_.recipe(), &c), "azd_dense_invx_cost_wide");
+        else check(azd_dense_invx_cost(adj, n(), &cost_.recipe(), &c), "azd_dense_invx_cost");
         return c;
     }
 
 private:
     InvariantCostX cost_;
+    bool wide_;
 };
 
 // ---------------------------------------------------------------- models (NablaModel, nabla/model/mod.rs:4-8)
@@ -753,8 +759,17 @@ private:
         return dense_inv_argmin_from(a, sp);
     }
     DenseInvxArgmin argmin_of(const DenseGraphInvXSpace &sp) {
+        if (sp.wide()) { // (the 64-row form's record: 64 neighbourhoods, 32 words of open slots)
+            azd_dense_invx_wide_argmin a;
+            check(azd_engine_dense_invx_wide_argmin_data(h_, &a), "argmin_data");
+            return dense_invx_argmin_from(a, sp);
+        }
         azd_dense_invx_argmin a;
         check(azd_engine_dense_invx_argmin_data(h_, &a), "argmin_data");
+        return dense_invx_argmin_from(a, sp);
+    }
+    template <class Rec>
+    static DenseInvxArgmin dense_invx_argmin_from(const Rec &a, const DenseGraphInvXSpace &sp) {
         DenseInvxArgmin r;
         r.adj.assign(a.adj, a.adj + sp.n());
         r.permitted.assign(a.permitted, a.permitted + (sp.E() + 63) / 64);
