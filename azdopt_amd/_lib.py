@@ -29,6 +29,7 @@ ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STE
 ENGINE_DENSE_INV = 1024  # AZD_ENGINE_DENSE_INV: the dense-graph space with the weighted-invariant cost (n <= 32; recipe set at run time)
 ENGINE_DENSE_INV_WIDE = 2048  # AZD_ENGINE_DENSE_INV_WIDE: beside ENGINE_DENSE_INV only: the weighted-invariant cost up to n = 64 (64-row kernels)
 ENGINE_DENSE_INVX_WIDE = 8192  # AZD_ENGINE_DENSE_INVX_WIDE: beside ENGINE_DENSE_INVX only: the extended invariant cost up to n = 64 (64-row kernels)
+ENGINE_DENSE_INVS = 16384  # AZD_ENGINE_DENSE_INVS: the dense-graph space with the spectrum invariant cost (n <= 32; twenty-one invariants: energies, spread)
 ENGINE_DENSE_INVX = 4096  # AZD_ENGINE_DENSE_INVX: the dense-graph space with the extended invariant cost (n <= 32; sixteen invariants, pair terms)
 ENGINE_RAMSEY_BIG_CLIQUES = 512  # AZD_ENGINE_RAMSEY_BIG_CLIQUES: beside ENGINE_RAMSEY_U64 only: clique sizes up to 8 (kernels of their own)
 SPACE_C21 = 1
@@ -55,6 +56,11 @@ DENSE_INVX_MAX_TERMS = 4  # AZD_DENSE_INVX_MAX_TERMS: pair terms of a recipe
 DENSE_INVX_MUL, DENSE_INVX_DIV = 0, 1  # AZD_DENSE_INVX_MUL / _DIV: a pair term's op
 # AZD_DENSE_INVX_NAMES: index and name are ABI; the first ten are DENSE_INV_NAMES
 DENSE_INVX_NAMES = DENSE_INV_NAMES + ("lap_eig", "slap_eig", "randic", "zagreb1", "zagreb2", "triangles")
+DENSE_INVS_MAX_N = 32   # AZD_DENSE_INVS_MAX_N: the spectrum invariant cost (azd_dense_invs_cost)
+DENSE_INVS_COUNT = 21   # AZD_DENSE_INVS_COUNT
+DENSE_INVS_ROUNDS = 67  # AZD_DENSE_INVS_ROUNDS: bisection rounds of the whole-spectrum procedure
+# AZD_DENSE_INVS_NAMES: index and name are ABI; the first sixteen are DENSE_INVX_NAMES
+DENSE_INVS_NAMES = DENSE_INVX_NAMES + ("adj_energy", "dist_energy", "lap_energy", "slap_energy", "adj_spread")
 PATH_SET, PATH_SEQUENCE = 0, 1
 ROOT_RULE_THRESHOLD, ROOT_RULE_BEST = 0, 1  # AZD_ROOT_RULE_*
 ROOT_RULES = {"threshold": ROOT_RULE_THRESHOLD, "best": ROOT_RULE_BEST}
@@ -145,6 +151,20 @@ class DenseInvxCost(C.Structure):  # azd_dense_invx_cost_t
 
 class DenseInvxArgmin(C.Structure):  # azd_dense_invx_argmin: ArgminData of a dense engine with the extended invariant cost
     _fields_ = [("adj", C.c_uint64 * 32), ("permitted", C.c_uint64 * 8), ("inv", C.c_double * 16), ("dist_k", C.c_int32),
+                ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
+
+
+class DenseInvsRecipe(C.Structure):  # azd_dense_invs_recipe: twenty-one weights, bias, four spectral indices, the eval's offset and scale, pair terms
+    _fields_ = [("weight", C.c_double * 21), ("bias", C.c_double), ("adj_index", C.c_int), ("dist_index", C.c_int), ("lap_index", C.c_int),
+                ("slap_index", C.c_int), ("eval_offset", C.c_float), ("eval_scale", C.c_float), ("term", DenseInvxTerm * 4), ("n_terms", C.c_int)]
+
+
+class DenseInvsCost(C.Structure):  # azd_dense_invs_cost_t
+    _fields_ = [("inv", C.c_double * 21), ("dist_k", C.c_int), ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float)]
+
+
+class DenseInvsArgmin(C.Structure):  # azd_dense_invs_argmin: ArgminData of a dense engine with the spectrum invariant cost
+    _fields_ = [("adj", C.c_uint64 * 32), ("permitted", C.c_uint64 * 8), ("inv", C.c_double * 21), ("dist_k", C.c_int32),
                 ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
 
 
@@ -303,6 +323,12 @@ def lib():
     sig("azd_engine_set_dense_invx_recipe", C.c_int, vp, C.POINTER(DenseInvxRecipe))
     sig("azd_engine_dense_invx_argmin_data", C.c_int, vp, C.POINTER(DenseInvxArgmin))
     sig("azd_engine_dense_invx_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvxCost))
+    sig("azd_dense_invs_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvsRecipe), C.POINTER(DenseInvsCost))
+    sig("azd_dense_invs_spectrum", C.c_int, vp, C.c_int, C.c_int, vp)
+    sig("azd_debug_probe_invs_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DenseInvsRecipe), vp, f32p)
+    sig("azd_engine_set_dense_invs_recipe", C.c_int, vp, C.POINTER(DenseInvsRecipe))
+    sig("azd_engine_dense_invs_argmin_data", C.c_int, vp, C.POINTER(DenseInvsArgmin))
+    sig("azd_engine_dense_invs_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvsCost))
     sig("azd_engine_set_dense_inv_recipe", C.c_int, vp, C.POINTER(DenseInvRecipe))
     sig("azd_engine_dense_inv_argmin_data", C.c_int, vp, C.POINTER(DenseInvArgmin))
     sig("azd_engine_dense_inv_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvCost))

@@ -180,4 +180,54 @@ const char *dense_invx_check_graph_wide(const uint64_t *adj, int n); // 4 <= n <
 // n <= DENSE_INVX_WIDE_MAX_N (one function behind azd_dense_invx_cost and azd_dense_invx_cost_wide: the limit is the callers' check)
 void dense_invx_cost_host(const uint64_t *adj, int n, const DenseInvxRecipe &r, DenseInvxCost *out);
 
+// Spectrum invariant cost of a connected graph on 4 <= n <= DENSE_INVS_MAX_N vertices (BUILD-DEFINED; DESIGN.md "The spectrum
+// invariant cost"; AZD_ENGINE_DENSE_INVS): twenty-one invariants -- index and name are ABI.  0 .. 15 are the extended invariant cost's;
+//   16 adj_energy = sum_l |theta_l(A)|   17 dist_energy = sum_l |theta_l(D)|
+//   18 lap_energy = sum_l |theta_l(L) - s|   19 slap_energy = sum_l |theta_l(Q) - s|,  s = (double)(sum of degrees) / (double)n
+//   20 adj_spread = theta_{n-1}(A) - theta_0(A)
+// theta_0 <= .. <= theta_{n-1}: ALL eigenvalues of the tridiagonal form the matrix's one reduction leaves (the same Householder
+// steps, the same DENSE_INV_DEFLATE rule), each by a bisection of its own on the Sturm count: hi = R + 1, lo = -hi (R the
+// Gershgorin bound, as the multisection's), DENSE_INVS_ROUNDS rounds of x = (lo + hi) * 0.5, c = count(x), c <= l ? lo = x : hi = x,
+// then theta_l = (lo + hi) * 0.5.  The final bracket 2 (R + 1) 2^-67 is no wider than the multisection's 2 (R + 1) 65^-11.  An energy
+// is the balanced tree over 64 slots of |theta_l| or |theta_l - s| (slots >= n hold 0.0); every step one IEEE operation.
+// A matrix is reduced at most once per cost; after it the multisection runs only when the matrix's *_eig is needed, the bisections
+// only when its energy (or, for A, the spread) is.  Needed as in the extended cost: a non-zero weight, or a pair term with a
+// non-zero coefficient that names it; else 0.0 and the bit of `computed` clear.  All five are positive on every connected graph
+// with n >= 4 (A, D, L - sI and Q - sI are not zero and have trace zero), so all five may divide.  With weights 16 .. 20 zero and no
+// term naming 16 .. 20 the sequence of operations is dense_invx_cost_host's.
+constexpr int DENSE_INVS_MAX_N = 32;
+constexpr int DENSE_INVS_COUNT = 21;
+constexpr int DENSE_INVS_ADJ_ENERGY = 16, DENSE_INVS_DIST_ENERGY = 17, DENSE_INVS_LAP_ENERGY = 18, DENSE_INVS_SLAP_ENERGY = 19, DENSE_INVS_ADJ_SPREAD = 20;
+constexpr int DENSE_INVS_ROUNDS = 67; // bisection rounds of the whole-spectrum finisher: the same for every lane
+constexpr uint32_t DENSE_INVS_DIVISORS = DENSE_INVX_DIVISORS | 0x1Fu << DENSE_INVS_ADJ_ENERGY;
+struct DenseInvsRecipe {
+    double weight[DENSE_INVS_COUNT];
+    double bias;
+    int adj_index, dist_index, lap_index, slap_index;
+    float eval_offset, eval_scale;
+    DenseInvxTerm term[DENSE_INVX_MAX_TERMS];
+    int n_terms;
+};
+struct DenseInvsCost {
+    double inv[DENSE_INVS_COUNT];
+    int dist_k;
+    uint32_t computed;
+    float cost, eval;
+};
+// bits 8 .. 20 of `computed` under a checked recipe (constexpr: the device code calls it too)
+constexpr uint32_t dense_invs_needed(const DenseInvsRecipe &r) {
+    uint32_t m = 0;
+    for (int i = DENSE_INV_ADJ_EIG; i < DENSE_INVS_COUNT; ++i) m |= r.weight[i] != 0.0 ? 1u << i : 0u;
+    for (int t = 0; t < r.n_terms; ++t)
+        if (r.term[t].coef != 0.0) m |= (1u << r.term[t].a | 1u << r.term[t].b) & ~DENSE_INV_ALWAYS;
+    return m;
+}
+// the four matrices, as azd_dense_invs_spectrum names them
+constexpr int DENSE_INVS_MATRIX_ADJ = 0, DENSE_INVS_MATRIX_DIST = 1, DENSE_INVS_MATRIX_LAP = 2, DENSE_INVS_MATRIX_SLAP = 3;
+const char *dense_invs_check_recipe(const DenseInvsRecipe *r, int n);
+const char *dense_invs_check_graph(const uint64_t *adj, int n); // 4 <= n <= DENSE_INVS_MAX_N, in this cost's words
+void dense_invs_cost_host(const uint64_t *adj, int n, const DenseInvsRecipe &r, DenseInvsCost *out);
+// theta_0 .. theta_{n-1} of matrix `which` (DENSE_INVS_MATRIX_*), ascending: what the energies and the spread are summed from
+void dense_invs_spectrum_host(const uint64_t *adj, int n, int which, double *out);
+
 } // namespace azd

@@ -70,7 +70,7 @@ static const ExtPoolForm *ext_pool_form(bool dense_space) {
     return dense_space ? &dense : &ramsey;
 }
 
-// The twelve kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
+// The thirteen kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
 // parts: c21 has no searcher-only pool step; the 64-bit Ramsey tier's is joined to the three parts of its phase unit's table.
 static const TierDesc *tier_desc(Tier t) {
     static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops(), PoolSearchOps{}};
@@ -121,13 +121,18 @@ static const TierDesc *tier_desc(Tier t) {
         // AZD_ENGINE_DENSE_INVX_WIDE beside it: the same record per agent over the 64-row kernels (dense_invx_wide_kernels.hip)
         {TIER_DENSE_INVX_WIDE, SPACE_DENSE, &dense_invx_wide_ops(), xd, sizeof(DenseInvxWideArgminRec), 0, false, true, false, DENSE_INVX_COUNT, 2,
          (int)((sizeof(DenseInvxRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        // AZD_ENGINE_DENSE_INVS: the spectrum invariant cost (dense_invs_kernels.hip): twenty-one doubles and two ints per agent, the recipe behind the doubles
+        // (no searcher-only pool step on this tier yet: ext is null, so its engines run one launch per phase at every population)
+        {TIER_DENSE_INVS, SPACE_DENSE, &dense_invs_ops(), nullptr, sizeof(DenseInvsArgminRec), 0, false, true, false, DENSE_INVS_COUNT, 2,
+         (int)((sizeof(DenseInvsRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
     };
     return &tiers[t];
 }
 // the tier of a configuration that check_engine_config has accepted: the flags name it, never the sizes
 const TierDesc *engine_tier(const azd_engine_config *cfg) {
     if (cfg->space_id == AZD_SPACE_DENSE)
-        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_INVX_WIDE ? TIER_DENSE_INVX_WIDE
+        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_INVS      ? TIER_DENSE_INVS
+                         : cfg->flags & AZD_ENGINE_DENSE_INVX_WIDE ? TIER_DENSE_INVX_WIDE
                          : cfg->flags & AZD_ENGINE_DENSE_INVX    ? TIER_DENSE_INVX
                          : cfg->flags & AZD_ENGINE_DENSE_INV_WIDE ? TIER_DENSE_INV_WIDE
                          : cfg->flags & AZD_ENGINE_DENSE_INV     ? TIER_DENSE_INV
@@ -426,7 +431,19 @@ int check_engine_config(const azd_engine_config *cfg) {
                       "AZD_SPACE_RAMSEY with max_slots > 0, whose kernels for clique sizes up to 8 it asks for)");
     const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
     const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
-    if (cfg->flags & AZD_ENGINE_DENSE_INVX_WIDE) { // the extended invariant cost's 64-row form: a second flag beside the first, never a cost of its own
+    if (cfg->flags & AZD_ENGINE_DENSE_INVS) { // the spectrum invariant cost: a tier of its own, asked for by name; the INVX tier's limits
+        const char *bad = dense_ah || dense_ah_wide || (cfg->flags & (AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE | AZD_ENGINE_DENSE_INVX | AZD_ENGINE_DENSE_INVX_WIDE))
+                              ? "flags: AZD_ENGINE_DENSE_INVS is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
+                                "AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX or AZD_ENGINE_DENSE_INVX_WIDE (the Aouchiche-Hansen cost, the "
+                                "weighted-invariant cost and the extended invariant cost are among its recipes)"
+                          : !dense                                       ? "space_id: AZD_ENGINE_DENSE_INVS needs the dense-graph space (AZD_SPACE_DENSE)"
+                          : cfg->n < 4 || cfg->n > AZD_DENSE_INVS_MAX_N  ? "n: the spectrum invariant cost needs 4 <= n <= 32 (AZD_DENSE_INVS_MAX_N)"
+                          : cfg->layers > 1                              ? "layers: AZD_ENGINE_DENSE_INVS engines take no Layered wrapper (layers <= 1)"
+                          : cfg->max_slots > dense_edges(cfg->n)         ? "max_slots: AZD_ENGINE_DENSE_INVS needs max_slots <= E = n (n - 1) / 2"
+                          : cfg->path_kind != AZD_PATH_SET               ? "path_kind: AZD_ENGINE_DENSE_INVS engines keep ActionSet paths (AZD_PATH_SET)"
+                                                                         : nullptr;
+        if (bad) return refuse(bad);
+    } else if (cfg->flags & AZD_ENGINE_DENSE_INVX_WIDE) { // the extended invariant cost's 64-row form: a second flag beside the first, never a cost of its own
         const char *bad = !(cfg->flags & AZD_ENGINE_DENSE_INVX)
                               ? "flags: AZD_ENGINE_DENSE_INVX_WIDE is valid only beside AZD_ENGINE_DENSE_INVX (the extended invariant cost whose 64-row form it asks for)"
                           : dense_ah || dense_ah_wide || (cfg->flags & (AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE))
@@ -830,7 +847,8 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         // ones, whose 64 rows, 32 slot words and ten or sixteen invariants come to 872 and 920 bytes where the default cost's record has 856)
         static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseAhWideArgminRec) <= sizeof(azd::DenseArgminRec) &&
                           sizeof(azd::DenseInvArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseInvWideArgminRec) <= 2 * sizeof(azd::DenseArgminRec) &&
-                          sizeof(azd::DenseInvxArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseInvxWideArgminRec) <= 2 * sizeof(azd::DenseArgminRec),
+                          sizeof(azd::DenseInvxArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseInvxWideArgminRec) <= 2 * sizeof(azd::DenseArgminRec) &&
+                          sizeof(azd::DenseInvsArgminRec) <= sizeof(azd::DenseArgminRec),
                       "an AH or INV engine's argmin record lives in argmin_d's allocation");
         AZD_ST(e->alloc(&a.argmin_d, (tier->argmin_bytes + sizeof(azd::DenseArgminRec) - 1) / sizeof(azd::DenseArgminRec)));
         if (tier->id == TIER_DENSE) AZD_ST(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH and the weighted-invariant cost keep nothing per node)
@@ -943,6 +961,10 @@ int azd_engine_par_new_begin(azd_engine *e, const uint8_t *parents, const uint64
     if (!e || !parents || !permitted) return AZD_ERR_INVALID_ARGUMENT;
     if (tier_inv(e->tier) && !e->inv_recipe_set) {
         azd::g_last_error = "par_new: an AZD_ENGINE_DENSE_INV engine has no cost before azd_engine_set_dense_inv_recipe has given it its recipe";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (tier_invs(e->tier) && !e->inv_recipe_set) {
+        azd::g_last_error = "par_new: an AZD_ENGINE_DENSE_INVS engine has no cost before azd_engine_set_dense_invs_recipe has given it its recipe";
         return AZD_ERR_INVALID_ARGUMENT;
     }
     if (tier_invx(e->tier) && !e->inv_recipe_set) {

@@ -37,7 +37,7 @@ struct ExtPoolForm {
 
 // The kind of engine a configuration asks for, and what the host code goes by for it: chosen once (engine_tier, after
 // check_engine_config has accepted the configuration), never re-derived from how the arenas were filled.
-enum Tier { TIER_C21, TIER_RAMSEY, TIER_RAMSEY_WIDE, TIER_RAMSEY_U64, TIER_RAMSEY_U64_BIG, TIER_DENSE, TIER_DENSE_AH, TIER_DENSE_AH_WIDE, TIER_DENSE_INV, TIER_DENSE_INV_WIDE, TIER_DENSE_INVX, TIER_DENSE_INVX_WIDE, TIER_COUNT };
+enum Tier { TIER_C21, TIER_RAMSEY, TIER_RAMSEY_WIDE, TIER_RAMSEY_U64, TIER_RAMSEY_U64_BIG, TIER_DENSE, TIER_DENSE_AH, TIER_DENSE_AH_WIDE, TIER_DENSE_INV, TIER_DENSE_INV_WIDE, TIER_DENSE_INVX, TIER_DENSE_INVX_WIDE, TIER_DENSE_INVS, TIER_COUNT };
 struct TierDesc {
     Tier id;
     int space;                  // azd::SPACE_*
@@ -49,7 +49,7 @@ struct TierDesc {
     bool padded_keys;           // device keys are wider than kw_host, zero beyond it (the Ramsey tiers with max_slots > 0)
     bool cap_from_slots;        // a node holds max_slots edges' actions (else MAX_NODE_ACTIONS)
     bool ah;                    // Aouchiche-Hansen cost: cur_lambda and cur_mu hold two values per agent, there is no node_mate
-    int cost_f64, cost_i32;     // per-agent entries of cur_lambda / cur_mu (default cost 1 / 1, AH 2 / 2, weighted-invariant cost 10 / 2, extended invariant cost 16 / 2, at either row limit)
+    int cost_f64, cost_i32;     // per-agent entries of cur_lambda / cur_mu (default cost 1 / 1, AH 2 / 2, weighted-invariant cost 10 / 2, extended invariant cost 16 / 2, at either row limit, spectrum invariant cost 21 / 2)
     int cost_tail_f64;          // doubles behind cur_lambda's per-agent part: the weighted-invariant or the extended invariant cost's recipe (0: none)
     // Ramsey: what check_engine_config tests, and says
     int max_n, max_edges, max_actions, node_actions; // the most n, E, E*C and max_slots * (C - 1) (0: no bound of its own)
@@ -62,6 +62,8 @@ struct TierDesc {
 inline bool tier_inv(const TierDesc *t) { return t->id == TIER_DENSE_INV || t->id == TIER_DENSE_INV_WIDE; }
 // ... and the extended invariant cost at either row limit, likewise
 inline bool tier_invx(const TierDesc *t) { return t->id == TIER_DENSE_INVX || t->id == TIER_DENSE_INVX_WIDE; }
+// ... and the spectrum invariant cost, which has one row limit
+inline bool tier_invs(const TierDesc *t) { return t->id == TIER_DENSE_INVS; }
 
 // The evaluator groups' device memory (PoolArgs::grp_*): the two tables of the plan, and the per-slot exchange state, regrown as a
 // whole when the plan needs more of any of it.
@@ -95,10 +97,11 @@ struct azd_engine {
     azd_engine_config cfg;
     azd::Arenas a;
     const azd::SpaceOps *ops = nullptr; // the launchers and LDS plans of the engine's space and tier (space_ops.h)
-    const TierDesc *tier = nullptr;     // which of the twelve kinds of engine this is (engine_tier)
+    const TierDesc *tier = nullptr;     // which of the thirteen kinds of engine this is (engine_tier)
     bool inv_recipe_set = false;        // AZD_ENGINE_DENSE_INV: azd_engine_set_dense_inv_recipe has run (par_new refuses before it) ...
     azd::DenseInvRecipe inv_recipe{};   // ... the recipe as set (the device's copy lies behind cur_lambda's per-agent part)
     azd::DenseInvxRecipe invx_recipe{}; // ... (AZD_ENGINE_DENSE_INVX: azd_engine_set_dense_invx_recipe's, kept the same way under the same two flags)
+    azd::DenseInvsRecipe invs_recipe{}; // ... (AZD_ENGINE_DENSE_INVS: azd_engine_set_dense_invs_recipe's, likewise)
     bool inv_recipe_locked = false;     // ... and par_new has computed the roots' evals with it (the setter refuses from then on)
     azd_evaluator *ev = nullptr;
     azd::Stream stream;

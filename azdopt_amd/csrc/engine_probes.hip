@@ -80,6 +80,10 @@ int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *ld
     engine_shape(cfg, tier, &a);
     const azd::SpaceOps *ops = tier->ops;
     const ExtPoolForm *xf = tier->ext;
+    if (!xf) {
+        azd::g_last_error = "azd_debug_ext_pool_plan: the configuration's tier has no searcher-only pool step";
+        return AZD_ERR_UNSUPPORTED;
+    }
     const char *why = "";
     uint32_t dyn_stride = 0;
     size_t dyn_bytes = 0;
@@ -414,6 +418,74 @@ int azd_debug_probe_invx_cost(int device, const uint64_t *adj, int n, int count,
 int azd_debug_probe_invx_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
                                    azd_dense_invx_cost_t *out, float *ms) {
     return probe_invx_cost("azd_debug_probe_invx_cost_wide", true, device, adj, n, count, reps, recipe, out, ms);
+}
+// ------------------------------------------------------------------ spectrum invariant cost of the dense-graph space
+static_assert(AZD_DENSE_INVS_MAX_N == azd::DENSE_INVS_MAX_N && AZD_DENSE_INVS_COUNT == azd::DENSE_INVS_COUNT && AZD_DENSE_INVS_ROUNDS == azd::DENSE_INVS_ROUNDS &&
+                  AZD_DENSE_INVS_MATRIX_ADJ == azd::DENSE_INVS_MATRIX_ADJ && AZD_DENSE_INVS_MATRIX_DIST == azd::DENSE_INVS_MATRIX_DIST &&
+                  AZD_DENSE_INVS_MATRIX_LAP == azd::DENSE_INVS_MATRIX_LAP && AZD_DENSE_INVS_MATRIX_SLAP == azd::DENSE_INVS_MATRIX_SLAP,
+              "AZD_DENSE_INVS_*");
+// graph `i` (or the only one) and the recipe, checked in this order; the text names `fn` and the argument
+static int invs_check(const char *fn, const uint64_t *adj, int n, int i, const azd_dense_invs_recipe *recipe) {
+    const char *why = azd::dense_invs_check_graph(adj, n);
+    if (!why) why = azd::dense_invs_check_recipe(reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), n);
+    else if (i >= 0) {
+        azd::g_last_error = std::string(fn) + ": graph " + std::to_string(i) + ": " + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (why) azd::g_last_error = std::string(fn) + ": " + why;
+    return why ? AZD_ERR_INVALID_ARGUMENT : AZD_OK;
+}
+int azd_dense_invs_cost(const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out) {
+    if (!out) {
+        azd::g_last_error = "azd_dense_invs_cost: out: null";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    AZD_ST(invs_check("azd_dense_invs_cost", adj, n, -1, recipe));
+    azd::dense_invs_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), reinterpret_cast<azd::DenseInvsCost *>(out));
+    return AZD_OK;
+}
+int azd_dense_invs_spectrum(const uint64_t *adj, int n, int which, double *out) {
+    const char *why = !out ? "out: null" : azd::dense_invs_check_graph(adj, n);
+    if (!why && (which < AZD_DENSE_INVS_MATRIX_ADJ || which > AZD_DENSE_INVS_MATRIX_SLAP))
+        why = "which: must be one of AZD_DENSE_INVS_MATRIX_ADJ, _DIST, _LAP, _SLAP (0 .. 3)";
+    if (why) {
+        azd::g_last_error = std::string("azd_dense_invs_spectrum: ") + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    azd::dense_invs_spectrum_host(adj, n, which, out);
+    return AZD_OK;
+}
+int azd_debug_probe_invs_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invs_recipe *recipe,
+                              azd_dense_invs_cost_t *out, float *ms) {
+    const char *const name = "azd_debug_probe_invs_cost";
+    if (!out || count <= 0 || reps <= 0) {
+        azd::g_last_error = std::string(name) + ": out / count / reps";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
+        AZD_ST(invs_check(name, adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n, i, recipe));
+    AZD_ST(azd::device_ok(device));
+    AZD_HIP(hipSetDevice(device));
+    azd::DevBuf<uint64_t> d_adj;
+    azd::DevBuf<azd::DenseInvsCost> d_out;
+    azd::DevBuf<azd::DenseInvsRecipe> d_recipe;
+    azd::Event e0, e1;
+    AZD_ST(azd::alloc_set(d_adj, (size_t)count * n, d_out, (size_t)count, d_recipe, (size_t)1));
+    AZD_ST(e0.create());
+    AZD_ST(e1.create());
+    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
+    AZD_HIP(hipMemcpy(d_recipe, recipe, sizeof(azd::DenseInvsRecipe), hipMemcpyHostToDevice));
+    azd::launch_probe_invs_cost(d_adj, n, count, 1, d_recipe, d_out, nullptr); // warm-up
+    AZD_HIP(hipEventRecord(e0, nullptr));
+    azd::launch_probe_invs_cost(d_adj, n, count, reps, d_recipe, d_out, nullptr);
+    AZD_HIP(hipEventRecord(e1, nullptr));
+    hipError_t he = hipDeviceSynchronize();
+    float t = 0.f;
+    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
+    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseInvsCost), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return azd::hip_fail(he, "probe_invs_cost");
+    if (ms) *ms = t;
+    return AZD_OK;
 }
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
     if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;

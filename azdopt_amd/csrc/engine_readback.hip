@@ -91,7 +91,9 @@ int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap,
 static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes, const char *refusal) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (e->tier->id != reads) {
-        if (e->tier->id == TIER_DENSE_INVX_WIDE)
+        if (e->tier->id == TIER_DENSE_INVS)
+            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVS engine's record is read with azd_engine_dense_invs_argmin_data";
+        else if (e->tier->id == TIER_DENSE_INVX_WIDE)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVX_WIDE engine's record is read with azd_engine_dense_invx_wide_argmin_data";
         else if (e->tier->id == TIER_DENSE_INVX)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_argmin_data";
@@ -100,7 +102,7 @@ static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes,
         else if (e->tier->id == TIER_DENSE_INV)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_argmin_data";
         else if (e->tier->ah || reads == TIER_DENSE_AH_WIDE || reads == TIER_DENSE_INV || reads == TIER_DENSE_INV_WIDE || reads == TIER_DENSE_INVX ||
-                 reads == TIER_DENSE_INVX_WIDE)
+                 reads == TIER_DENSE_INVX_WIDE || reads == TIER_DENSE_INVS)
             azd::g_last_error = refusal;
         return AZD_ERR_UNSUPPORTED;
     }
@@ -126,6 +128,11 @@ static_assert(sizeof(azd_dense_argmin) == sizeof(azd::DenseArgminRec) && sizeof(
                   offsetof(azd_dense_invx_recipe, term) == offsetof(azd::DenseInvxRecipe, term) && sizeof(azd_dense_invx_term) == sizeof(azd::DenseInvxTerm) &&
                   offsetof(azd_dense_invx_term, op) == offsetof(azd::DenseInvxTerm, op) &&
                   sizeof(azd_dense_invx_cost_t) == sizeof(azd::DenseInvxCost) && offsetof(azd_dense_invx_cost_t, eval) == offsetof(azd::DenseInvxCost, eval) &&
+                  sizeof(azd_dense_invs_argmin) == sizeof(azd::DenseInvsArgminRec) && offsetof(azd_dense_invs_argmin, node) == offsetof(azd::DenseInvsArgminRec, node) &&
+                  offsetof(azd_dense_invs_argmin, inv) == offsetof(azd::DenseInvsArgminRec, inv) &&
+                  sizeof(azd_dense_invs_recipe) == sizeof(azd::DenseInvsRecipe) && offsetof(azd_dense_invs_recipe, n_terms) == offsetof(azd::DenseInvsRecipe, n_terms) &&
+                  offsetof(azd_dense_invs_recipe, term) == offsetof(azd::DenseInvsRecipe, term) &&
+                  sizeof(azd_dense_invs_cost_t) == sizeof(azd::DenseInvsCost) && offsetof(azd_dense_invs_cost_t, eval) == offsetof(azd::DenseInvsCost, eval) &&
                   sizeof(azd_dense_inv_recipe) == sizeof(azd::DenseInvRecipe) && offsetof(azd_dense_inv_recipe, eval_scale) == offsetof(azd::DenseInvRecipe, eval_scale) &&
                   sizeof(azd_dense_inv_cost_t) == sizeof(azd::DenseInvCost) && offsetof(azd_dense_inv_cost_t, eval) == offsetof(azd::DenseInvCost, eval),
               "ABI struct mismatch");
@@ -151,8 +158,9 @@ int azd_engine_dense_inv_wide_argmin_data(azd_engine *e, azd_dense_inv_wide_argm
 int azd_engine_set_dense_inv_recipe(azd_engine *e, const azd_dense_inv_recipe *recipe) {
     if (!e) return AZD_ERR_INVALID_ARGUMENT;
     if (!tier_inv(e->tier)) {
-        azd::g_last_error = tier_invx(e->tier) ? "azd_engine_set_dense_inv_recipe: an AZD_ENGINE_DENSE_INVX engine's recipe is set with azd_engine_set_dense_invx_recipe"
-                                                           : "azd_engine_set_dense_inv_recipe: not an AZD_ENGINE_DENSE_INV engine";
+        azd::g_last_error = tier_invs(e->tier)   ? "azd_engine_set_dense_inv_recipe: an AZD_ENGINE_DENSE_INVS engine's recipe is set with azd_engine_set_dense_invs_recipe"
+                            : tier_invx(e->tier) ? "azd_engine_set_dense_inv_recipe: an AZD_ENGINE_DENSE_INVX engine's recipe is set with azd_engine_set_dense_invx_recipe"
+                                                 : "azd_engine_set_dense_inv_recipe: not an AZD_ENGINE_DENSE_INV engine";
         return AZD_ERR_UNSUPPORTED;
     }
     if (e->inv_recipe_locked) {
@@ -173,8 +181,9 @@ int azd_engine_set_dense_inv_recipe(azd_engine *e, const azd_dense_inv_recipe *r
 int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
     if (!tier_inv(e->tier)) {
-        azd::g_last_error = tier_invx(e->tier) ? "azd_engine_dense_inv_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost"
-                                                           : "azd_engine_dense_inv_agent_cost: not an AZD_ENGINE_DENSE_INV engine";
+        azd::g_last_error = tier_invs(e->tier)   ? "azd_engine_dense_inv_agent_cost: an AZD_ENGINE_DENSE_INVS engine's record is read with azd_engine_dense_invs_agent_cost"
+                            : tier_invx(e->tier) ? "azd_engine_dense_inv_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost"
+                                                 : "azd_engine_dense_inv_agent_cost: not an AZD_ENGINE_DENSE_INV engine";
         return AZD_ERR_UNSUPPORTED;
     }
     AZD_ENTER(e);
@@ -207,8 +216,9 @@ int azd_engine_dense_invx_wide_argmin_data(azd_engine *e, azd_dense_invx_wide_ar
 int azd_engine_set_dense_invx_recipe(azd_engine *e, const azd_dense_invx_recipe *recipe) {
     if (!e) return AZD_ERR_INVALID_ARGUMENT;
     if (!tier_invx(e->tier)) {
-        azd::g_last_error = tier_inv(e->tier) ? "azd_engine_set_dense_invx_recipe: an AZD_ENGINE_DENSE_INV engine's recipe is set with azd_engine_set_dense_inv_recipe"
-                                              : "azd_engine_set_dense_invx_recipe: not an AZD_ENGINE_DENSE_INVX engine";
+        azd::g_last_error = tier_invs(e->tier)  ? "azd_engine_set_dense_invx_recipe: an AZD_ENGINE_DENSE_INVS engine's recipe is set with azd_engine_set_dense_invs_recipe"
+                            : tier_inv(e->tier) ? "azd_engine_set_dense_invx_recipe: an AZD_ENGINE_DENSE_INV engine's recipe is set with azd_engine_set_dense_inv_recipe"
+                                                : "azd_engine_set_dense_invx_recipe: not an AZD_ENGINE_DENSE_INVX engine";
         return AZD_ERR_UNSUPPORTED;
     }
     if (e->inv_recipe_locked) {
@@ -229,8 +239,9 @@ int azd_engine_set_dense_invx_recipe(azd_engine *e, const azd_dense_invx_recipe 
 int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
     if (!tier_invx(e->tier)) {
-        azd::g_last_error = tier_inv(e->tier) ? "azd_engine_dense_invx_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost"
-                                              : "azd_engine_dense_invx_agent_cost: not an AZD_ENGINE_DENSE_INVX engine";
+        azd::g_last_error = tier_invs(e->tier)  ? "azd_engine_dense_invx_agent_cost: an AZD_ENGINE_DENSE_INVS engine's record is read with azd_engine_dense_invs_agent_cost"
+                            : tier_inv(e->tier) ? "azd_engine_dense_invx_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost"
+                                                : "azd_engine_dense_invx_agent_cost: not an AZD_ENGINE_DENSE_INVX engine";
         return AZD_ERR_UNSUPPORTED;
     }
     AZD_ENTER(e);
@@ -258,8 +269,73 @@ int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_co
     out->eval = r.eval_scale * (out->cost + r.eval_offset);
     return AZD_OK;
 }
+// The spectrum invariant cost's entries, in the same image: the recipe behind the twenty-one per-agent doubles of cur_lambda
+// (dense_invs_cost.inc: dense_invs_recipe), the argmin record, an agent's record
+static const char *invs_other_tier(const azd_engine *e, const char *invx, const char *inv, const char *other) {
+    return tier_invx(e->tier) ? invx : tier_inv(e->tier) ? inv : other;
+}
+int azd_engine_dense_invs_argmin_data(azd_engine *e, azd_dense_invs_argmin *out) {
+    return dense_argmin_read(e, out, TIER_DENSE_INVS, sizeof(*out), "azd_engine_dense_invs_argmin_data: not an AZD_ENGINE_DENSE_INVS engine");
+}
+int azd_engine_set_dense_invs_recipe(azd_engine *e, const azd_dense_invs_recipe *recipe) {
+    if (!e) return AZD_ERR_INVALID_ARGUMENT;
+    if (!tier_invs(e->tier)) {
+        azd::g_last_error = invs_other_tier(e, "azd_engine_set_dense_invs_recipe: an AZD_ENGINE_DENSE_INVX engine's recipe is set with azd_engine_set_dense_invx_recipe",
+                                            "azd_engine_set_dense_invs_recipe: an AZD_ENGINE_DENSE_INV engine's recipe is set with azd_engine_set_dense_inv_recipe",
+                                            "azd_engine_set_dense_invs_recipe: not an AZD_ENGINE_DENSE_INVS engine");
+        return AZD_ERR_UNSUPPORTED;
+    }
+    if (e->inv_recipe_locked) {
+        azd::g_last_error = "azd_engine_set_dense_invs_recipe: par_new has run: the trees' evals were computed with the recipe in force, which stays";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    const azd::DenseInvsRecipe *r = reinterpret_cast<const azd::DenseInvsRecipe *>(recipe);
+    if (const char *why = azd::dense_invs_check_recipe(r, e->a.n)) {
+        azd::g_last_error = std::string("azd_engine_set_dense_invs_recipe: ") + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    AZD_HIP(hipSetDevice(e->cfg.device));
+    AZD_HIP(hipMemcpy(e->a.cur_lambda + (size_t)azd::DENSE_INVS_COUNT * e->a.B, r, sizeof(*r), hipMemcpyHostToDevice));
+    e->invs_recipe = *r;
+    e->inv_recipe_set = true;
+    return AZD_OK;
+}
+int azd_engine_dense_invs_agent_cost(azd_engine *e, int agent, azd_dense_invs_cost_t *out) {
+    if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
+    if (!tier_invs(e->tier)) {
+        azd::g_last_error = invs_other_tier(e, "azd_engine_dense_invs_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost",
+                                            "azd_engine_dense_invs_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost",
+                                            "azd_engine_dense_invs_agent_cost: not an AZD_ENGINE_DENSE_INVS engine");
+        return AZD_ERR_UNSUPPORTED;
+    }
+    AZD_ENTER(e);
+    AZD_HIP(hipStreamSynchronize(e->stream));
+    const azd::Arenas &a = e->a;
+    for (int i = 0; i < azd::DENSE_INVS_COUNT; ++i) AZD_HIP(hipMemcpy(&out->inv[i], a.cur_lambda + (size_t)i * a.B + agent, 8, hipMemcpyDeviceToHost));
+    AZD_HIP(hipMemcpy(&out->dist_k, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
+    AZD_HIP(hipMemcpy(&out->computed, a.cur_mu + a.B + agent, 4, hipMemcpyDeviceToHost));
+    // cost and eval from the kept invariants: the device's combination, operation for operation (this unit is built with -ffp-contract=off)
+    const azd::DenseInvsRecipe &r = e->invs_recipe;
+    double c = r.bias;
+    for (int i = 0; i < azd::DENSE_INVS_COUNT; ++i)
+        if (r.weight[i] != 0.0) {
+            const double term = r.weight[i] * out->inv[i];
+            c = c + term;
+        }
+    for (int t = 0; t < r.n_terms; ++t) {
+        const azd::DenseInvxTerm &p = r.term[t];
+        if (p.coef == 0.0) continue;
+        const double v = p.op == azd::DENSE_INVX_DIV ? out->inv[p.a] / out->inv[p.b] : out->inv[p.a] * out->inv[p.b];
+        const double term = p.coef * v;
+        c = c + term;
+    }
+    out->cost = (float)c;
+    out->eval = r.eval_scale * (out->cost + r.eval_offset);
+    return AZD_OK;
+}
 int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
+    if (tier_invs(e->tier)) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INVS engine's record is read with azd_engine_dense_invs_agent_cost";
     if (tier_invx(e->tier)) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost";
     if (tier_inv(e->tier)) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost";
     if (!e->tier->ah) return AZD_ERR_UNSUPPORTED;
@@ -392,6 +468,10 @@ int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t 
     AZD_HIP(hipStreamSynchronize(e->stream));
     const azd::Arenas &a = e->a;
     if (a.space == azd::SPACE_DENSE) { // `parents` receives the neighbourhoods (8 n bytes); masks are kw_host words
+        if (tier_invs(e->tier) && (lambda_1 || matching_size)) {
+            azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_INVS engine keeps neither (azd_engine_dense_invs_agent_cost)";
+            return AZD_ERR_UNSUPPORTED;
+        }
         if (tier_invx(e->tier) && (lambda_1 || matching_size)) {
             azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_INVX engine keeps neither (azd_engine_dense_invx_agent_cost)";
             return AZD_ERR_UNSUPPORTED;

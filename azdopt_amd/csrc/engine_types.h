@@ -215,6 +215,16 @@ struct DenseInvxWideArgminRec { // device copy of azd_dense_invx_wide_argmin (AZ
     int32_t agent;
     uint32_t node;
 };
+struct DenseInvsArgminRec { // device copy of azd_dense_invs_argmin (AZD_ENGINE_DENSE_INVS engines: n <= 32, E <= 496); in argmin_d's place too
+    uint64_t adj[32];
+    uint64_t permitted[8]; // modifiable slots (colex positions) still open
+    double inv[21];        // the twenty-one invariants (c21_host.h: DenseInvsCost), 0.0 where not computed
+    int32_t dist_k;
+    uint32_t computed;
+    float cost, eval;
+    int32_t agent;
+    uint32_t node;
+};
 static_assert(sizeof(DenseInvxWideArgminRec) == 920, "the largest dense argmin record: argmin_d is sized from the tier's argmin_bytes");
 
 struct StatusRec { // small device block copied back after every host-visible call

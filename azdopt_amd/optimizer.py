@@ -72,6 +72,21 @@ class DenseInvxArgminData:
         self.agent, self.node = rec.agent, rec.node
 
 
+class DenseInvsArgminData:
+    """az-discrete-opt/src/log.rs:1-11 for the dense-graph space with the spectrum invariant cost: state = neighbourhoods + open
+    slots, cost = the twenty-one invariants by name, dist_k, computed, cost"""
+
+    def __init__(self, rec, space):
+        from .space import InvariantCostS
+        slots = np.zeros(space.KEY_WORDS, np.uint64)
+        ow = (space.E + 63) // 64
+        slots[:ow] = rec.permitted[:ow]
+        self.state = dict(adj=np.array(rec.adj[:space.n], np.uint64), permitted=slots)
+        self.cost = InvariantCostS.record(rec)
+        self.eval = np.float32(rec.eval)
+        self.agent, self.node = rec.agent, rec.node
+
+
 class DenseInvArgminData:
     """az-discrete-opt/src/log.rs:1-11 for the dense-graph space with the weighted-invariant cost: state = neighbourhoods + open
     slots, cost = the ten invariants by name, dist_k, computed, cost"""
@@ -131,7 +146,7 @@ class NablaOptimizer:
         step with the model's batched GEMMs beside it (ENGINE_EXT_POOL_STEP); step_form() says whether it ran.  ext_pool_f32=True
         beside it (ENGINE_EXT_POOL_F32; alone the engine refuses it on c21 and the Ramsey spaces): that form also with an fp32
         ActionModel.  On a DenseGraphSpace, whose pool step IS that form, ext_pool_f32=True stands alone (all seven tiers: default
-        cost, cost="ah", ah_wide=True, cost=InvariantCost(...), inv_wide=True, cost=InvariantCostX(...), invx_wide=True): where the engine's configured form is the pool step (256 agents or more, or pool_step=True)
+        cost, cost="ah", ah_wide=True, cost=InvariantCost(...), inv_wide=True, cost=InvariantCostX(...), invx_wide=True, cost=InvariantCostS(...)): where the engine's configured form is the pool step (256 agents or more, or pool_step=True)
         an fp32 ActionModel is served by the gathered fp32 GEMMs instead of falling back to one launch per phase -- same
         predictions bit for bit; with persistent=False beside it the engine refuses it.  On an MI355X with a whole epoch per launch:
         AH N = 31 2.6 against 0.82 M expansions/s at 512 agents, 5.5 against 4.7 M at 4096; config E's shape (8192 agents,
@@ -164,6 +179,8 @@ class NablaOptimizer:
                 cfg.flags |= _lib.ENGINE_DENSE_INVX
                 if getattr(space, "INVX_WIDE", False):
                     cfg.flags |= _lib.ENGINE_DENSE_INVX_WIDE
+            if getattr(space, "COST", "c21") == "invs":
+                cfg.flags |= _lib.ENGINE_DENSE_INVS
         if space.SPACE_ID == _lib.SPACE_RAMSEY:
             cfg.max_slots = getattr(space, "MAX_SLOTS", 0)
             if getattr(space, "U64", False):
@@ -183,6 +200,9 @@ class NablaOptimizer:
         if cfg.flags & _lib.ENGINE_DENSE_INVX:  # (likewise)
             r = space.INVX.recipe()
             _lib.check(self._L.azd_engine_set_dense_invx_recipe(self._h, C.byref(r)), "set_dense_invx_recipe")
+        if cfg.flags & _lib.ENGINE_DENSE_INVS:  # (likewise)
+            r = space.INVS.recipe()
+            _lib.check(self._L.azd_engine_set_dense_invs_recipe(self._h, C.byref(r)), "set_dense_invs_recipe")
 
     def __del__(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -340,6 +360,10 @@ class NablaOptimizer:
                 rec = _lib.DenseInvxArgmin()
                 _lib.check(self._L.azd_engine_dense_invx_argmin_data(self._h, C.byref(rec)), "dense_invx_argmin_data")
             return DenseInvxArgminData(rec, self.space)
+        if self.space.SPACE_ID == _lib.SPACE_DENSE and getattr(self.space, "COST", "c21") == "invs":
+            rec = _lib.DenseInvsArgmin()
+            _lib.check(self._L.azd_engine_dense_invs_argmin_data(self._h, C.byref(rec)), "dense_invs_argmin_data")
+            return DenseInvsArgminData(rec, self.space)
         if self.space.SPACE_ID == _lib.SPACE_DENSE:
             rec = _lib.DenseArgmin()
             _lib.check(self._L.azd_engine_dense_argmin_data(self._h, C.byref(rec)), "dense_argmin_data")
@@ -458,6 +482,13 @@ class NablaOptimizer:
             c = _lib.DenseInvxCost()
             _lib.check(self._L.azd_engine_dense_invx_agent_cost(self._h, agent, C.byref(c)), "dense_invx_agent_cost")
             return dict(parents=parents, permitted=permitted, path=path, state_pos=pos.value, **InvariantCostX.record(c))
+        if self.space.SPACE_ID == _lib.SPACE_DENSE and getattr(self.space, "COST", "c21") == "invs":
+            from .space import InvariantCostS
+            _lib.check(self._L.azd_engine_agent_state(self._h, agent, _lib.ptr(parents), _lib.ptr(permitted), _lib.ptr(path),
+                                                      C.byref(pos), None, None), "agent_state")
+            c = _lib.DenseInvsCost()
+            _lib.check(self._L.azd_engine_dense_invs_agent_cost(self._h, agent, C.byref(c)), "dense_invs_agent_cost")
+            return dict(parents=parents, permitted=permitted, path=path, state_pos=pos.value, **InvariantCostS.record(c))
         _lib.check(self._L.azd_engine_agent_state(self._h, agent, _lib.ptr(parents), _lib.ptr(permitted), _lib.ptr(path),
                                                   C.byref(pos), C.byref(lam), C.byref(mu)), "agent_state")
         return dict(parents=parents, permitted=permitted, path=path, state_pos=pos.value, lambda1=lam.value, matching=mu.value)

@@ -313,6 +313,36 @@ class InvariantCostX:
         return out
 
 
+class InvariantCostS(InvariantCostX):
+    """A recipe of the dense-graph space's spectrum invariant cost (AZD_ENGINE_DENSE_INVS; azd_dense_invs_recipe): twenty-one
+    invariants of a connected graph -- InvariantCostX's sixteen, then functions of a matrix's WHOLE spectrum:
+        adj_energy (the graph energy, sum of |eigenvalue| of A), dist_energy (of the distance matrix), lap_energy and slap_energy
+        (sum of |eigenvalue - mean degree| of D - A and D + A), adj_spread (largest minus smallest eigenvalue of A)
+    -- combined by InvariantCostX's rule.  All five are positive on every connected graph and may divide.  A matrix is reduced once;
+    its one eigenvalue by index and its energy are each computed only when a non-zero weight or coefficient asks for it.  With none
+    of the five asked for it is InvariantCostX's cost, bit for bit."""
+
+    NAMES = _lib.DENSE_INVS_NAMES
+    DIVISORS = InvariantCostX.DIVISORS + _lib.DENSE_INVS_NAMES[16:]
+
+    @classmethod
+    def from_invariant_cost_x(cls, cost):
+        """the recipe that gives an InvariantCostX's cost, eval and trees bit for bit"""
+        return cls(cost.weights, terms=cost.terms, bias=cost.bias, adj_index=cost.adj_index, dist_index=cost.dist_index, lap_index=cost.lap_index,
+                   slap_index=cost.slap_index, eval_offset=cost.eval_offset, eval_scale=cost.eval_scale)
+
+    def recipe(self):
+        r = _lib.DenseInvsRecipe()
+        for i, name in enumerate(self.NAMES):
+            r.weight[i] = self.weights.get(name, 0.0)
+        r.bias, r.adj_index, r.dist_index, r.lap_index, r.slap_index = self.bias, self.adj_index, self.dist_index, self.lap_index, self.slap_index
+        r.eval_offset, r.eval_scale = float(self.eval_offset), float(self.eval_scale)
+        for t, (coef, a, op, b) in enumerate(self.terms):
+            r.term[t].coef, r.term[t].a, r.term[t].b, r.term[t].op = coef, self.NAMES.index(a), self.NAMES.index(b), self.OPS[op]
+        r.n_terms = len(self.terms)
+        return r
+
+
 class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     """Connected graphs on N <= 64 vertices; an action adds an absent edge or deletes a present non-cut edge, every edge
     slot at most once (BASELINE configs[4], N = 50).  BUILD-DEFINED: the reference has the pieces
@@ -336,19 +366,25 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     InvariantCost tier's limits): sixteen invariants -- Laplacian and signless-Laplacian eigenvalues, Randic and Zagreb indices and
     the triangle count beside the ten -- and products or quotients of two of them.  InvariantCostX.from_invariant_cost(c) gives
     cost=c's trees.  `invx_wide=True` (with an InvariantCostX only): that cost's 64-row form, N <= 64 (AZD_ENGINE_DENSE_INVX_WIDE
-    beside the first flag; never chosen from N), roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives."""
+    beside the first flag; never chosen from N), roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives.
+    `cost=InvariantCostS(...)`: the spectrum invariant cost (AZD_ENGINE_DENSE_INVS, N <= 32, a tier of its own with the
+    InvariantCostX tier's limits): the graph energy, the distance, Laplacian and signless-Laplacian energies and the adjacency spread
+    beside the sixteen.  InvariantCostS.from_invariant_cost_x(c) gives cost=c's trees.  It has no 64-row form."""
 
     SPACE_ID = _lib.SPACE_DENSE
 
     def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False, inv_wide=False, invx_wide=False):
         self.INV = cost if isinstance(cost, InvariantCost) else None
-        self.INVX = cost if isinstance(cost, InvariantCostX) else None
+        self.INVS = cost if isinstance(cost, InvariantCostS) else None
+        self.INVX = cost if isinstance(cost, InvariantCostX) and self.INVS is None else None
         if self.INV is not None:
             cost = "inv"
+        elif self.INVS is not None:
+            cost = "invs"
         elif self.INVX is not None:
             cost = "invx"
         elif cost not in ("c21", "ah"):
-            raise ValueError('cost must be "c21", "ah", an InvariantCost or an InvariantCostX')
+            raise ValueError('cost must be "c21", "ah", an InvariantCost, an InvariantCostX or an InvariantCostS')
         if ah_wide and cost != "ah":
             raise ValueError('ah_wide=True needs cost="ah" (it is the Aouchiche-Hansen cost\'s 64-row form)')
         if inv_wide and cost != "inv":
@@ -364,7 +400,7 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
         # (an AZD_ENGINE_DENSE_AH engine refuses max_slots > E; a root cannot bring more than E slots anyway)
         # (... and an AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV_WIDE or AZD_ENGINE_DENSE_INVX_WIDE engine max_slots > min(E, 640): its
         # keys are 2, 4 or 10 words)
-        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide or inv_wide or invx_wide else min(int(max_slots), self.E) if cost in ("ah", "inv", "invx") else int(max_slots)
+        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide or inv_wide or invx_wide else min(int(max_slots), self.E) if cost in ("ah", "inv", "invx", "invs") else int(max_slots)
         L = _lib.lib()
         self.STATE_DIM = L.azd_dense_state_dim(self.n)
         self.ACTION_DIM = L.azd_dense_action_dim(self.n)
@@ -437,6 +473,26 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
         else:
             _lib.check(_lib.lib().azd_dense_invx_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_invx_cost")
         return dict(InvariantCostX.record(out), eval=np.float32(out.eval))
+
+    def invs_cost(self, adj, cost=None):
+        """The spectrum invariant cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_invs_cost under this
+        space's recipe (or `cost`, another InvariantCostS), the same procedure as the device's, bit for bit.
+        -> dict(the twenty-one invariants by name, dist_k, computed, cost, eval)"""
+        cost = self.INVS if cost is None else cost
+        if cost is None:
+            raise ValueError("invs_cost: the space has no InvariantCostS; pass one")
+        a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
+        out, r = _lib.DenseInvsCost(), cost.recipe()
+        _lib.check(_lib.lib().azd_dense_invs_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_invs_cost")
+        return dict(InvariantCostS.record(out), eval=np.float32(out.eval))
+
+    def invs_spectrum(self, adj, which="adj"):
+        """All eigenvalues, ascending, of the graph's adjacency ("adj"), distance ("dist"), Laplacian ("lap") or signless-Laplacian
+        ("slap") matrix by the cost's whole-spectrum procedure on the host (azd_dense_invs_spectrum): what the energies sum."""
+        a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
+        out = np.zeros(self.n, np.float64)
+        _lib.check(_lib.lib().azd_dense_invs_spectrum(_lib.ptr(a), self.n, ("adj", "dist", "lap", "slap").index(which), _lib.ptr(out)), "azd_dense_invs_spectrum")
+        return out
 
 
 class Layered:

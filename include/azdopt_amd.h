@@ -358,6 +358,19 @@ typedef struct azd_engine_config {
  * tier's, so a searcher workgroup has the 6 wavefronts it has there (azd_debug_ext_pool_plan reports the plan for such a
  * configuration too). */
 #define AZD_ENGINE_DENSE_INVX_WIDE 8192u
+/* The dense-graph space with the spectrum invariant cost (azd_dense_invs_cost below): twenty-one invariants -- the extended
+ * invariant cost's sixteen, then the graph energy, the distance energy, the Laplacian and signless-Laplacian energies and the
+ * adjacency spread, each a function of a matrix's WHOLE spectrum -- combined by a recipe of weights and up to four products or
+ * quotients of two invariants, given at RUN time by azd_engine_set_dense_invs_recipe.  A tier of its own beside
+ * AZD_ENGINE_DENSE_INVX, in kernels of their own (dense_invs_kernels.hip); asked for by name, never inferred from a recipe.  It has
+ * that tier's limits: 4 <= n <= AZD_DENSE_INVS_MAX_N = 32, layers <= 1, max_slots <= E,
+ * ActionSet paths (refused with AZD_ERR_INVALID_ARGUMENT naming the argument, as is this flag beside any AZD_ENGINE_DENSE_AH*,
+ * AZD_ENGINE_DENSE_INV* or AZD_ENGINE_DENSE_INVX* flag, or on another space).  There is no 64-row form of it and, for now, no pool
+ * step: its engines run one launch per phase at every population; AZD_ENGINE_EXT_POOL_F32 is accepted beside it and changes
+ * nothing, and azd_debug_ext_pool_plan is AZD_ERR_UNSUPPORTED for such a configuration.  Such an engine keeps the twenty-one invariants, the distance index used and the `computed` mask per
+ * agent: azd_engine_dense_invs_agent_cost, azd_engine_dense_invs_argmin_data.  The INVX, INV, AH and default reads and the INV and
+ * INVX setters are AZD_ERR_UNSUPPORTED on it and name the right call, and the INVS calls on an engine of those tiers likewise. */
+#define AZD_ENGINE_DENSE_INVS 16384u
 /* Beside AZD_ENGINE_RAMSEY_U64 only (alone, on another space or on a 32-bit tier: AZD_ERR_INVALID_ARGUMENT naming both flags): the
  * 64-bit tier with forbidden cliques up to K8 -- clique sizes 2..AZD_RAMSEY_BIG_CLIQUE_MAX, the reference's count_cliques_inside
  * (bitset_graph/mod.rs:164-185) to depth 6 in kernels of their own; the 64-bit tier's kernels and every engine without the flag are
@@ -399,7 +412,7 @@ typedef struct azd_engine_config {
  * 512 agents 0.99 against 0.52 M expansions/s, r45 at 256 agents 1.03 against 0.31 M on the wide tier and 0.79 against 0.25 M on the
  * 64-bit tier.
  * AZD_SPACE_DENSE: the space's pool step is the searcher-only form and needs no flag of its own, so there this flag stands alone, on
- * all seven tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX, AZD_ENGINE_DENSE_INVX_WIDE); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
+ * all eight tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX, AZD_ENGINE_DENSE_INVX_WIDE; AZD_ENGINE_DENSE_INVS accepts the flag but has no pool step); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
  * this flag beside AZD_ENGINE_NO_PERSISTENT_STEP is AZD_ERR_INVALID_ARGUMENT naming both.  It is a request to the configured pool
  * step, not a form: where the engine's form is not the pool step (fewer than 256 agents without AZD_ENGINE_POOL_STEP) nothing
  * changes and azd_engine_step_form gives the reason it gave.  With it an fp32 MLP is served by the same gathered fp32 GEMMs over the
@@ -982,6 +995,84 @@ typedef struct azd_dense_invx_wide_argmin {
 int azd_engine_dense_invx_wide_argmin_data(azd_engine *e, azd_dense_invx_wide_argmin *out);
 /* the cost record of agent `agent`'s current state as the engine keeps it (cost and eval recomputed from the kept invariants) */
 int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_cost_t *out);
+
+/* ---- Spectrum invariant cost (AZD_ENGINE_DENSE_INVS engines minimise it), BUILD-DEFINED (DESIGN.md "The spectrum invariant
+ * cost").  Twenty-one invariants of a CONNECTED graph on 4 <= n <= 32 vertices -- index and name are ABI.  0 .. 15 are the extended
+ * invariant cost's, names and definitions unchanged; then, with theta_0 <= .. <= theta_{n-1} ALL eigenvalues of a matrix,
+ *   16 adj_energy   sum_l |theta_l(A)|         (the graph energy)
+ *   17 dist_energy  sum_l |theta_l(D)|         (D the distance matrix)
+ *   18 lap_energy   sum_l |theta_l(L) - s|     (L = Deg - A;  s = (double)(sum of degrees) / (double)n, the mean degree)
+ *   19 slap_energy  sum_l |theta_l(Q) - s|     (Q = Deg + A)
+ *   20 adj_spread   theta_{n-1}(A) - theta_0(A)
+ * Whole-spectrum procedure (one definition for device, host and the tests' reference; every f64 step one IEEE operation): on the
+ * tridiagonal form that the matrix's reduction leaves -- the same Householder steps and deflation rule as for the one eigenvalue
+ * by index -- with R the Gershgorin bound, eigenvalue l starts from hi = R + 1, lo = -hi and makes AZD_DENSE_INVS_ROUNDS = 67
+ * rounds of x = (lo + hi) * 0.5, c = the Sturm count at x, `c <= l ? lo = x : hi = x`; theta_l = (lo + hi) * 0.5.  The final
+ * bracket 2 (R + 1) 2^-67 is no wider than the one-eigenvalue multisection's 2 (R + 1) 65^-11.  An energy is the balanced tree
+ * sum over 64 slots (slots >= n hold 0.0).
+ * A matrix is reduced at most once per cost; then the multisection runs only when its *_eig is needed and the whole-spectrum
+ * procedure only when its energy (or, for A, the spread) is.  Needed, as in the extended cost: a weight that is not zero, or a pair
+ * term with a coefficient that is not zero that names it; otherwise the invariant is reported as 0.0 and its bit of `computed`
+ * (8 .. 20) is clear.  The combination rule is the extended cost's over twenty-one weights.  A DIV term's divisor is one of 0 .. 7,
+ * 12, 13, 14, 16 .. 20: all five new invariants are positive on every connected graph with n >= 4.  With weights 16 .. 20 zero and
+ * no term naming 16 .. 20 the sequence of operations is the extended invariant cost's: inv[0 .. 15], dist_k, computed, cost and
+ * eval are azd_dense_invx_cost's bit for bit. */
+#define AZD_DENSE_INVS_MAX_N 32
+#define AZD_DENSE_INVS_COUNT 21
+#define AZD_DENSE_INVS_ROUNDS 67
+#define AZD_DENSE_INVS_NAMES AZD_DENSE_INVX_NAMES, "adj_energy", "dist_energy", "lap_energy", "slap_energy", "adj_spread"
+/* the matrices azd_dense_invs_spectrum knows */
+#define AZD_DENSE_INVS_MATRIX_ADJ 0
+#define AZD_DENSE_INVS_MATRIX_DIST 1
+#define AZD_DENSE_INVS_MATRIX_LAP 2
+#define AZD_DENSE_INVS_MATRIX_SLAP 3
+typedef struct azd_dense_invs_recipe {
+    double weight[AZD_DENSE_INVS_COUNT];
+    double bias;
+    int adj_index;     /* 0 .. n - 1 */
+    int dist_index;    /* 0 .. n - 1, or AZD_DENSE_INV_INDEX_AH */
+    int lap_index;     /* 0 .. n - 1 */
+    int slap_index;    /* 0 .. n - 1 */
+    float eval_offset;
+    float eval_scale;  /* not zero */
+    azd_dense_invx_term term[AZD_DENSE_INVX_MAX_TERMS]; /* a, b in 0 .. 20; a divisor b among 0 .. 7, 12, 13, 14, 16 .. 20 */
+    int n_terms;       /* 0 .. 4 */
+} azd_dense_invs_recipe;
+typedef struct azd_dense_invs_cost_t {
+    double inv[AZD_DENSE_INVS_COUNT];
+    int dist_k;        /* the distance index the recipe resolves to on this graph */
+    uint32_t computed; /* bit i: inv[i] was computed (0xFF always; bits 8 .. 20 by the weights and the pair terms) */
+    float cost;
+    float eval;
+} azd_dense_invs_cost_t;
+/* The cost on the host; needs no GPU.  The graph is checked like azd_dense_invx_cost's, the recipe like
+ * azd_engine_set_dense_invs_recipe's: AZD_ERR_INVALID_ARGUMENT naming the argument or field. */
+int azd_dense_invs_cost(const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out);
+/* Host only: theta_0 <= .. <= theta_{n-1} of matrix `which` (AZD_DENSE_INVS_MATRIX_*) by the whole-spectrum procedure, n doubles
+ * -- what the energies and the spread are summed from, so that each eigenvalue can be checked.  The graph is checked as above. */
+int azd_dense_invs_spectrum(const uint64_t *adj, int n, int which, double *out);
+/* The device kernel in isolation, as azd_debug_probe_invx_cost: graphs and recipe are checked before the device is looked for. */
+int azd_debug_probe_invs_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invs_recipe *recipe,
+                              azd_dense_invs_cost_t *out, float *ms);
+/* The recipe of an AZD_ENGINE_DENSE_INVS engine: set once, between azd_engine_create and the first par_new (par_new without it is
+ * refused and names this call; after par_new this call is AZD_ERR_INVALID_ARGUMENT).  AZD_ERR_INVALID_ARGUMENT naming the field,
+ * as azd_engine_set_dense_invx_recipe, with a term's a or b in 0 .. 20.  AZD_ERR_UNSUPPORTED on an engine of another tier. */
+int azd_engine_set_dense_invs_recipe(azd_engine *e, const azd_dense_invs_recipe *recipe);
+/* ArgminData of an AZD_ENGINE_DENSE_INVS engine: the graph, the slots still open, the cost record */
+typedef struct azd_dense_invs_argmin {
+    uint64_t adj[32];
+    uint64_t permitted[8]; /* modifiable slots (colex positions) still open; E <= 496 */
+    double inv[AZD_DENSE_INVS_COUNT];
+    int32_t dist_k;
+    uint32_t computed;
+    float cost;
+    float eval;
+    int32_t agent;
+    uint32_t node;
+} azd_dense_invs_argmin;
+int azd_engine_dense_invs_argmin_data(azd_engine *e, azd_dense_invs_argmin *out);
+/* the cost record of agent `agent`'s current state as the engine keeps it (cost and eval recomputed from the kept invariants) */
+int azd_engine_dense_invs_agent_cost(azd_engine *e, int agent, azd_dense_invs_cost_t *out);
 /* Parity probe for the f64 primitives the AH cost depends on bit for bit.  in: 2*n doubles (pairs x, y); out: 3*n doubles per
  * pair: [0] x / y, [1] sqrt(|x|), [2] x - (x / y) * y (two roundings: a contracted form would differ). */
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n);

@@ -363,6 +363,87 @@ private:
     bool wide_;
 };
 
+// A recipe of the spectrum invariant cost (azd_dense_invs_recipe): twenty-one invariants -- InvariantCostX's sixteen, then adj_energy,
+// dist_energy, lap_energy, slap_energy, adj_spread (azdopt_amd.h has the definitions) -- combined by InvariantCostX's rule.
+class InvariantCostS {
+public:
+    InvariantCostS() : r_{} {
+        r_.dist_index = AZD_DENSE_INV_INDEX_AH;
+        r_.eval_scale = 1.0f;
+    }
+    // the recipe that gives an InvariantCostX's cost, eval and trees, bit for bit
+    static InvariantCostS from_invariant_cost_x(const InvariantCostX &c) {
+        InvariantCostS s;
+        const azd_dense_invx_recipe &r = c.recipe();
+        for (int i = 0; i < AZD_DENSE_INVX_COUNT; ++i) s.r_.weight[i] = r.weight[i];
+        s.r_.bias = r.bias;
+        s.r_.adj_index = r.adj_index;
+        s.r_.dist_index = r.dist_index;
+        s.r_.lap_index = r.lap_index;
+        s.r_.slap_index = r.slap_index;
+        s.r_.eval_offset = r.eval_offset;
+        s.r_.eval_scale = r.eval_scale;
+        for (int t = 0; t < r.n_terms; ++t) s.r_.term[t] = r.term[t];
+        s.r_.n_terms = r.n_terms;
+        return s;
+    }
+    static int index_of(const std::string &name) {
+        static const char *const names[AZD_DENSE_INVS_COUNT] = {AZD_DENSE_INVS_NAMES};
+        for (int i = 0; i < AZD_DENSE_INVS_COUNT; ++i)
+            if (name == names[i]) return i;
+        throw Error(AZD_ERR_INVALID_ARGUMENT, "InvariantCostS: unknown invariant " + name);
+    }
+    InvariantCostS &weight(const std::string &name, double w) { r_.weight[index_of(name)] = w; return *this; }
+    // one more pair term: coef * (a * b) for op '*', coef * (a / b) for op '/' (the engine checks the divisor)
+    InvariantCostS &term(double coef, const std::string &a, char op, const std::string &b) {
+        if (r_.n_terms >= AZD_DENSE_INVX_MAX_TERMS || (op != '*' && op != '/')) throw Error(AZD_ERR_INVALID_ARGUMENT, "InvariantCostS: term");
+        azd_dense_invx_term &t = r_.term[r_.n_terms++];
+        t.coef = coef;
+        t.a = index_of(a);
+        t.b = index_of(b);
+        t.op = op == '/' ? AZD_DENSE_INVX_DIV : AZD_DENSE_INVX_MUL;
+        return *this;
+    }
+    InvariantCostS &bias(double b) { r_.bias = b; return *this; }
+    InvariantCostS &adj_index(int k) { r_.adj_index = k; return *this; }
+    InvariantCostS &dist_index(int k) { r_.dist_index = k; return *this; } // a descending index, or AZD_DENSE_INV_INDEX_AH (the default)
+    InvariantCostS &lap_index(int k) { r_.lap_index = k; return *this; }
+    InvariantCostS &slap_index(int k) { r_.slap_index = k; return *this; }
+    InvariantCostS &offset(float o) { r_.eval_offset = o; return *this; }
+    InvariantCostS &scale(float s) { r_.eval_scale = s; return *this; }
+    const azd_dense_invs_recipe &recipe() const { return r_; }
+
+private:
+    azd_dense_invs_recipe r_;
+};
+
+// The same space with the spectrum invariant cost as the objective (AZD_ENGINE_DENSE_INVS): n <= AZD_DENSE_INVS_MAX_N,
+// max_slots <= E; par_new hands the recipe to the engine.  argmin_data() gives a DenseInvsArgmin.  There is no 64-row form.
+class DenseGraphInvSSpace : public DenseGraphSpace {
+public:
+    DenseGraphInvSSpace(int n, double p, int max_slots, const InvariantCostS &cost) : DenseGraphSpace(n, p, max_slots), cost_(cost) {}
+    const InvariantCostS &invariant_cost() const { return cost_; }
+    void configure(azd_engine_config &cfg) const {
+        DenseGraphSpace::configure(cfg);
+        cfg.flags |= AZD_ENGINE_DENSE_INVS;
+    }
+    // the cost of one connected graph on the host (adj: n neighbourhood bitsets): the device's procedure, bit for bit
+    azd_dense_invs_cost_t cost(const uint64_t *adj) const {
+        azd_dense_invs_cost_t c;
+        check(azd_dense_invs_cost(adj, n(), &cost_.recipe(), &c), "azd_dense_invs_cost");
+        return c;
+    }
+    // all eigenvalues, ascending, of matrix `which` (AZD_DENSE_INVS_MATRIX_*) by the cost's whole-spectrum procedure
+    std::vector<double> spectrum(const uint64_t *adj, int which) const {
+        std::vector<double> th((size_t)n());
+        check(azd_dense_invs_spectrum(adj, n(), which, th.data()), "azd_dense_invs_spectrum");
+        return th;
+    }
+
+private:
+    InvariantCostS cost_;
+};
+
 // ---------------------------------------------------------------- models (NablaModel, nabla/model/mod.rs:4-8)
 class NablaModel {
 public:
@@ -491,6 +572,15 @@ struct DenseInvxArgmin {
     std::vector<uint64_t> adj;       // state: neighbourhood bitsets
     std::vector<uint64_t> permitted; // ... and the edge slots still modifiable
     azd_dense_invx_cost_t cost;      // the sixteen invariants (AZD_DENSE_INVX_NAMES order), dist_k, computed, cost, eval
+    float eval;
+    int agent;
+    uint32_t node;
+};
+
+struct DenseInvsArgmin {
+    std::vector<uint64_t> adj;       // state: neighbourhood bitsets
+    std::vector<uint64_t> permitted; // ... and the edge slots still modifiable
+    azd_dense_invs_cost_t cost;      // the twenty-one invariants (AZD_DENSE_INVS_NAMES order), dist_k, computed, cost, eval
     float eval;
     int agent;
     uint32_t node;
@@ -694,6 +784,9 @@ private:
     static void set_recipe(const DenseGraphInvXSpace &sp, azd_engine *h) {
         check(azd_engine_set_dense_invx_recipe(h, &sp.invariant_cost().recipe()), "NablaOptimizer::par_new (recipe)");
     }
+    static void set_recipe(const DenseGraphInvSSpace &sp, azd_engine *h) {
+        check(azd_engine_set_dense_invs_recipe(h, &sp.invariant_cost().recipe()), "NablaOptimizer::par_new (recipe)");
+    }
     void host_predictions() { // the model call of optimizer/mod.rs:72 / :175-176 / :348 on the host side
         check(azd_engine_read_state_vecs(h_, sv_.data()), "read_state_vecs");
         host_->write_predictions(batch_, sv_.data(), pred_.data());
@@ -767,6 +860,22 @@ private:
         azd_dense_invx_argmin a;
         check(azd_engine_dense_invx_argmin_data(h_, &a), "argmin_data");
         return dense_invx_argmin_from(a, sp);
+    }
+    DenseInvsArgmin argmin_of(const DenseGraphInvSSpace &sp) {
+        azd_dense_invs_argmin a;
+        check(azd_engine_dense_invs_argmin_data(h_, &a), "argmin_data");
+        DenseInvsArgmin r;
+        r.adj.assign(a.adj, a.adj + sp.n());
+        r.permitted.assign(a.permitted, a.permitted + (sp.E() + 63) / 64);
+        std::memcpy(r.cost.inv, a.inv, sizeof(a.inv));
+        r.cost.dist_k = a.dist_k;
+        r.cost.computed = a.computed;
+        r.cost.cost = a.cost;
+        r.cost.eval = a.eval;
+        r.eval = a.eval;
+        r.agent = a.agent;
+        r.node = a.node;
+        return r;
     }
     template <class Rec>
     static DenseInvxArgmin dense_invx_argmin_from(const Rec &a, const DenseGraphInvXSpace &sp) {
