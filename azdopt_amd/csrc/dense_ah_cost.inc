@@ -1,5 +1,5 @@
 // dense_ah_cost.inc -- the Aouchiche-Hansen cost of a connected graph on the device, one wave per graph (included inside
-// namespace azd after tree_core.inc and space_dense.inc).
+// namespace azd after tree_core.inc, space_dense.inc and dense_spectral.inc, whose stages it is composed of).
 //
 // The objective is the reference's ConnectedBitsetGraph::ah_cost (graph-state/src/simple_graph/connected_bitset_graph/
 // mod.rs:156-198; the objective of examples/05-ah.rs), restated:
@@ -9,34 +9,15 @@
 // and, BUILD-DEFINED in the image of the dense space's squish, eval = slope (cost + 2) with slope = 1 / (2 n + 2).
 //
 // The eigenvalue procedure stands in for faer's (as the power iteration does for lambda_1): Householder reduction of the
-// distance matrix to tridiagonal form in LDS, then a Sturm-count multisection for the ONE eigenvalue wanted -- 64 lanes count at
-// 64 shifts, the bracket shrinks by 65 a round, DENSE_AH_ROUNDS rounds from the Gershgorin radius.  Every step is one IEEE f64
-// operation (-ffp-contract=off; f64 division and sqrt are correctly rounded on gfx950), every reduction an xor-butterfly = a
-// balanced binary tree: c21_host.cpp dense_ah_cost_host and tests/dense_ah_ref.py run the same sequence and agree bit for bit.
-//
-// Lanes: BFS -- lane u is source u.  Householder -- lane r owns row r of the working matrix.  Multisection -- lane l owns shift l;
-// the tridiagonal entries are LDS broadcasts.
-// The working matrix is kept as its LOWER TRIANGLE, packed (row r at r (r + 1) / 2: 4.1 KB a wave where the square is 8.3 KB --
-// sixteen waves' blocks of the pool step's searchers have to share a CU's 160 KB).  The host form keeps the square; the values are
-// the same to the bit, because the rank-two update A_rc - (v_r q_c + q_r v_c) is symmetric in (r, c) operation by operation
-// (products and the sum commute), so the square's two triangles never differ.
+// distance matrix to tridiagonal form in LDS, then a Sturm-count multisection for the ONE eigenvalue wanted -- DENSE_AH_ROUNDS
+// rounds from the Gershgorin radius (dense_spectral.inc).  c21_host.cpp dense_ah_cost_host and tests/dense_ah_ref.py run the same
+// sequence and agree bit for bit.  The reduction does not deflate: distance matrices of connected graphs are what it has always
+// reduced, to these bits.
 //
 // The row limit ROWS is a template parameter of everything here that depends on it: 32 (DenseCostAH: dense_ah_kernels.hip,
-// AZD_ENGINE_DENSE_AH) or 64 (DenseCostAhWide: dense_ah_wide_kernels.hip, AZD_ENGINE_DENSE_AH_WIDE: a triangle of 2080 doubles,
-// 16.6 KB a wave), and the engine's argmin record follows from it -- one library may instantiate both.  Order of operations, lane
-// roles and reductions do not depend on it: at n <= 32 the two compute the same bits.
-__device__ __forceinline__ int dense_ah_at(const int r, const int c) { return r >= c ? r * (r + 1) / 2 + c : c * (c + 1) / 2 + r; }
-template <int ROWS>
-struct DenseAhLdsT {
-    static_assert(ROWS == 32 || ROWS == 64, "the lanes of one wave own the rows");
-    static constexpr int TRI = ROWS * (ROWS + 1) / 2;
-    double A[TRI]; // distance matrix (lower triangle, packed), reduced in place
-    double v[ROWS], q[ROWS]; // Householder vector and its companion, by row
-    double diag[ROWS], sub2[ROWS]; // the tridiagonal form: diagonal, squared subdiagonal
-};
-using DenseAhLds = DenseAhLdsT<DENSE_AH_MAX_N>;
-using DenseAhWideLds = DenseAhLdsT<DENSE_AH_WIDE_MAX_N>;
-
+// AZD_ENGINE_DENSE_AH) or 64 (DenseCostAhWide: dense_ah_wide_kernels.hip, AZD_ENGINE_DENSE_AH_WIDE), and the engine's argmin
+// record follows from it -- one library may instantiate both.
+//
 // adj: the graph's neighbourhood bitsets in LDS (n <= ROWS words are read).  hook: called once, after the BFS (the pool
 // step's deferred post, as in dense_lambda1_wave).  Wave-uniform result in `out`.
 template <int ROWS, class Hook>
@@ -44,100 +25,15 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
     const int lane = LANE;
     const int row = lane * (lane + 1) / 2; // this lane's row of the packed triangle (lanes < n only)
     const bool in = lane < n;
-    const uint64_t all = ROWS < 64 ? (1ull << n) - 1ull : ~0ull >> (64 - n); // (64 rows: n = 64 must not shift by 64; n >= 4)
-    // ---- BFS from every vertex at once
-    int t = 0, d = 0;
-    if (in) {
-        w.A[row + lane] = 0.0;
-        uint64_t seen = 1ull << lane, frontier = seen;
-        for (;;) {
-            uint64_t next = 0;
-            for (uint64_t f = frontier; f; f &= f - 1ull) next |= adj[__ffsll((unsigned long long)f) - 1];
-            next &= ~seen & all;
-            if (!next) break;
-            ++d;
-            for (uint64_t m = next & ((1ull << lane) - 1ull); m; m &= m - 1ull) w.A[row + __ffsll((unsigned long long)m) - 1] = (double)d;
-            t += d * __popcll(next);
-            seen |= next;
-            frontier = next;
-        }
-    }
+    int t, d, deg;
+    dense_bfs_wave(adj, w, lane, row, in, dense_vertex_mask<ROWS>(n), true, t, d, deg);
     const int min_t = (int)wave_min_u32(in ? (uint32_t)t : 0xFFFFFFFFu);
     const int diam = (int)wave_max_u32(in ? (uint32_t)d : 0u);
     hook();
     const double prox = (double)min_t / (double)(n - 1);
-    const int q23 = (2 * diam) / 3, k = q23 >= 1 ? q23 - 1 : n - 1;
-    // ---- Householder reduction: step i clears column i below row i + 1; lane i keeps (diag_i, sub_i)
-    double dg = 0.0, sb = 0.0;
-#pragma unroll 1
-    for (int i = 0; i + 2 < n; ++i) {
-        LDS_SYNC();
-        const bool act = in && lane > i;
-        const double x = act ? w.A[row + i] : 0.0;
-        const double tail = dense_tree_sum(lane > i + 1 ? x * x : 0.0);
-        const double x1 = __shfl(x, i + 1, 64);
-        if (lane == i) dg = w.A[row + i];
-        if (tail == 0.0) { // the column is tridiagonal already
-            if (lane == i) sb = x1;
-            continue;
-        }
-        const double sigma = tail + x1 * x1;
-        const double s = sqrt(sigma);
-        const double alpha = x1 >= 0.0 ? -s : s;
-        const double v1 = x1 - alpha;
-        const double v = lane == i + 1 ? v1 : x;
-        const double beta = 2.0 / (tail + v1 * v1);
-        if (lane < ROWS) w.v[lane] = v;
-        LDS_SYNC();
-        double acc = 0.0;
-        if (act)
-            for (int c = i + 1; c < n; ++c) acc = acc + w.A[dense_ah_at(lane, c)] * w.v[c];
-        const double p = act ? beta * acc : 0.0;
-        const double vp = dense_tree_sum(v * p);
-        const double K = (0.5 * beta) * vp;
-        const double q = act ? p - K * v : 0.0;
-        if (lane < ROWS) w.q[lane] = q;
-        LDS_SYNC();
-        if (act)
-            for (int c = i + 1; c <= lane; ++c) w.A[row + c] = w.A[row + c] - (v * w.q[c] + q * w.v[c]);
-        if (lane == i) sb = alpha;
-    }
-    LDS_SYNC();
-    if (lane == n - 2) {
-        dg = w.A[row + lane];
-        sb = w.A[dense_ah_at(n - 1, n - 2)];
-    }
-    if (lane == n - 1) dg = w.A[row + lane];
-    // ---- multisection for the eigenvalue of ascending index j = n - 1 - k
-    const int j = n - 1 - k;
-    const double sb_below = __shfl(sb, lane > 0 ? lane - 1 : 0, 64);
-    const double g = (fabs(dg) + (lane > 0 ? fabs(sb_below) : 0.0)) + fabs(sb); // Gershgorin; >= 0: the bit patterns order like the numbers
-    const double R = __longlong_as_double((long long)wave_max_u64(in ? (uint64_t)__double_as_longlong(g) : 0ull));
-    if (lane < ROWS) {
-        w.diag[lane] = dg;
-        w.sub2[lane] = sb * sb;
-    }
-    LDS_SYNC();
-    double hi = R + 1.0, lo = -hi;
-#pragma unroll 1
-    for (int round = 0; round < DENSE_AH_ROUNDS; ++round) {
-        const double wd = hi - lo;
-        const double x = lo + (wd * (double)(lane + 1)) / 65.0;
-        double qq = w.diag[0] - x;
-        if (fabs(qq) < DENSE_AH_TINY) qq = -DENSE_AH_TINY;
-        int c = qq < 0.0 ? 1 : 0;
-        for (int i = 1; i < n; ++i) { // eigenvalues below x = negative pivots of T - x
-            const double r = w.sub2[i - 1] / qq;
-            qq = (w.diag[i] - x) - r;
-            if (fabs(qq) < DENSE_AH_TINY) qq = -DENSE_AH_TINY;
-            c += qq < 0.0 ? 1 : 0;
-        }
-        const int m = __popcll(__ballot(c <= j));
-        const double x_lo = __shfl(x, m > 0 ? m - 1 : 0, 64), x_hi = __shfl(x, m < 64 ? m : 63, 64);
-        lo = m > 0 ? x_lo : lo;
-        hi = m < 64 ? x_hi : hi;
-    }
-    const double eig = (lo + hi) * 0.5;
+    const int k = dense_ah_index(diam, n);
+    const double R = dense_tridiag_wave<ROWS, false>(w, n, lane, row, in);
+    const double eig = dense_multisection_wave(w, n, lane, n - 1 - k, R); // ascending index j = n - 1 - k
     out.proximity = prox;
     out.eigenvalue = eig;
     out.diameter = diam;
@@ -147,18 +43,7 @@ __device__ __forceinline__ void dense_ah_cost_wave(const uint64_t *adj, DenseAhL
 }
 
 // ---------------------------------------------------------------- the AH cost as a DenseSpace's cost policy (space_dense.inc)
-// A wave's block: DenseLds without the matching, with the cost's working set.  4 <= n <= ROWS, so E <= 496 or 2016.
-template <int KW_, int ROWS>
-struct DenseAhSpaceLdsT {
-    uint64_t adj[DENSE_MAX_N];
-    double x[32];                    // write_rows_direct's scratch (the present edges as a bitmap: 8 words at 32 rows, 32 at 64, read one past)
-    uint64_t slotmask[32];
-    uint16_t aid[64 * KW_];
-    unsigned long long ctr[NUM_COUNTERS];
-    uint16_t seq[4];
-    uint32_t stack[PATH_STACK];
-    DenseAhLdsT<ROWS> ah;
-};
+// A wave's block is DenseAhSpaceLdsT<KW, ROWS> (dense_spectral.inc).
 // An agent's record between launches lives in the arrays the default cost uses, twice as long (engine.hip allocates 2 B entries):
 // cur_lambda[t] = pi, cur_lambda[B + t] = eigenvalue, cur_mu[t] = D, cur_mu[B + t] = k.  No per-node arena: node_mate is null.
 template <int ROWS>

@@ -16,7 +16,7 @@ namespace azd {
 
 #include "tree_core.inc"
 #include "space_dense.inc"
-#include "dense_ah_cost.inc"
+#include "dense_spectral.inc"
 #include "dense_invx_cost.inc"
 
 #include "root_policy.inc"

@@ -1,6 +1,46 @@
 // engine_probes.hip -- the azd_debug_* entries (probes and test hooks) and the host entries of the Aouchiche-Hansen cost.
 #include "engine_impl.h"
 
+// ------------------------------------------------------------------ spectral costs of the dense-graph space: the probes' host side
+// One driver around every probe kernel (32 or 64 rows, with a recipe or without).  check(graph, i) refuses graph i, and the recipe
+// after it, with the entry's text; launch(d_adj, n, count, reps, d_recipe, d_out, stream) starts the tier's kernel (space_ops.h:
+// launch_probe_*_cost): once to warm up, then `reps` repetitions between two events.  recipe: null for a cost that takes none
+// (Recipe = char; nothing is allocated for it).
+template <class Cost, class Recipe, class Check, class Launch>
+static int probe_dense_cost(const char *name, const char *tag, int device, const uint64_t *adj, int n, int count, int reps, const Recipe *recipe,
+                            void *out, float *ms, Check check, Launch launch) {
+    if (!out || count <= 0 || reps <= 0) {
+        azd::g_last_error = std::string(name) + ": out / count / reps";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
+        AZD_ST(check(adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, i));
+    AZD_ST(azd::device_ok(device));
+    AZD_HIP(hipSetDevice(device));
+    azd::DevBuf<uint64_t> d_adj;
+    azd::DevBuf<Cost> d_out;
+    azd::DevBuf<Recipe> d_recipe;
+    azd::Event e0, e1;
+    AZD_ST(azd::alloc_set(d_adj, (size_t)count * n, d_out, (size_t)count, d_recipe, (size_t)(recipe ? 1 : 0)));
+    AZD_ST(e0.create());
+    AZD_ST(e1.create());
+    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
+    if (recipe) {
+        AZD_HIP(hipMemcpy(d_recipe, recipe, sizeof(Recipe), hipMemcpyHostToDevice));
+    }
+    launch(d_adj, n, count, 1, d_recipe, d_out, nullptr); // warm-up
+    AZD_HIP(hipEventRecord(e0, nullptr));
+    launch(d_adj, n, count, reps, d_recipe, d_out, nullptr);
+    AZD_HIP(hipEventRecord(e1, nullptr));
+    hipError_t he = hipDeviceSynchronize();
+    float t = 0.f;
+    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
+    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(Cost), hipMemcpyDeviceToHost);
+    if (he != hipSuccess) return azd::hip_fail(he, tag);
+    if (ms) *ms = t;
+    return AZD_OK;
+}
+
 extern "C" {
 
 int azd_debug_mlp_gradients(azd_evaluator *ev, int batch, const float *states, const float *observations, const float *action_weights,
@@ -231,39 +271,19 @@ int azd_dense_ah_cost_wide(const uint64_t *adj, int n, azd_dense_ah_cost_t *out)
     azd::dense_ah_cost_host(adj, n, reinterpret_cast<azd::DenseAhCost *>(out));
     return AZD_OK;
 }
-// the two probes: the same host side around the 32-row and the 64-row kernel
+// the two probes: the 32-row and the 64-row kernel
 static int probe_ah_cost(const char *name, bool wide, int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
-    if (!out || count <= 0 || reps <= 0) {
-        azd::g_last_error = std::string(name) + ": out / count / reps";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    const auto check = wide ? azd::dense_ah_check_graph_wide : azd::dense_ah_check_graph;
-    const auto launch = wide ? azd::launch_probe_ah_cost_wide : azd::launch_probe_ah_cost;
-    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
-        if (const char *why = check(adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n)) {
-            azd::g_last_error = std::string(name) + ": graph " + std::to_string(i) + ": " + why;
-            return AZD_ERR_INVALID_ARGUMENT;
-        }
-    AZD_ST(azd::device_ok(device));
-    AZD_HIP(hipSetDevice(device));
-    azd::DevBuf<uint64_t> d_adj;
-    azd::DevBuf<azd::DenseAhCost> d_out;
-    azd::Event e0, e1;
-    AZD_ST(azd::alloc_set(d_adj, (size_t)count * n, d_out, (size_t)count));
-    AZD_ST(e0.create());
-    AZD_ST(e1.create());
-    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
-    launch(d_adj, n, count, 1, d_out, nullptr); // warm-up
-    AZD_HIP(hipEventRecord(e0, nullptr));
-    launch(d_adj, n, count, reps, d_out, nullptr);
-    AZD_HIP(hipEventRecord(e1, nullptr));
-    hipError_t he = hipDeviceSynchronize();
-    float t = 0.f;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseAhCost), hipMemcpyDeviceToHost);
-    if (he != hipSuccess) return azd::hip_fail(he, "probe_ah_cost");
-    if (ms) *ms = t;
-    return AZD_OK;
+    const auto graph_check = wide ? azd::dense_ah_check_graph_wide : azd::dense_ah_check_graph;
+    const auto kernel = wide ? azd::launch_probe_ah_cost_wide : azd::launch_probe_ah_cost;
+    const auto check = [=](const uint64_t *g, int i) {
+        const char *why = graph_check(g, n);
+        if (why) azd::g_last_error = std::string(name) + ": graph " + std::to_string(i) + ": " + why;
+        return why ? AZD_ERR_INVALID_ARGUMENT : AZD_OK;
+    };
+    const auto launch = [=](const uint64_t *d_adj, int n_, int count_, int reps_, const char *, azd::DenseAhCost *d_out, void *stream) {
+        kernel(d_adj, n_, count_, reps_, d_out, stream);
+    };
+    return probe_dense_cost<azd::DenseAhCost, char>(name, "probe_ah_cost", device, adj, n, count, reps, (const char *)nullptr, out, ms, check, launch);
 }
 int azd_debug_probe_ah_cost(int device, const uint64_t *adj, int n, int count, int reps, azd_dense_ah_cost_t *out, float *ms) {
     return probe_ah_cost("azd_debug_probe_ah_cost", false, device, adj, n, count, reps, out, ms);
@@ -304,38 +324,12 @@ int azd_dense_inv_cost_wide(const uint64_t *adj, int n, const azd_dense_inv_reci
     azd::dense_inv_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvRecipe *>(recipe), reinterpret_cast<azd::DenseInvCost *>(out));
     return AZD_OK;
 }
-// the two probes: the same host side around the 32-row and the 64-row kernel
+// the two probes: the 32-row and the 64-row kernel
 static int probe_inv_cost(const char *name, bool wide, int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_inv_recipe *recipe,
                           azd_dense_inv_cost_t *out, float *ms) {
-    const auto launch = wide ? azd::launch_probe_inv_cost_wide : azd::launch_probe_inv_cost;
-    if (!out || count <= 0 || reps <= 0) {
-        azd::g_last_error = std::string(name) + ": out / count / reps";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
-        AZD_ST(inv_check(name, wide, adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n, i, recipe));
-    AZD_ST(azd::device_ok(device));
-    AZD_HIP(hipSetDevice(device));
-    azd::DevBuf<uint64_t> d_adj;
-    azd::DevBuf<azd::DenseInvCost> d_out;
-    azd::DevBuf<azd::DenseInvRecipe> d_recipe;
-    azd::Event e0, e1;
-    AZD_ST(azd::alloc_set(d_adj, (size_t)count * n, d_out, (size_t)count, d_recipe, (size_t)1));
-    AZD_ST(e0.create());
-    AZD_ST(e1.create());
-    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
-    AZD_HIP(hipMemcpy(d_recipe, recipe, sizeof(azd::DenseInvRecipe), hipMemcpyHostToDevice));
-    launch(d_adj, n, count, 1, d_recipe, d_out, nullptr); // warm-up
-    AZD_HIP(hipEventRecord(e0, nullptr));
-    launch(d_adj, n, count, reps, d_recipe, d_out, nullptr);
-    AZD_HIP(hipEventRecord(e1, nullptr));
-    hipError_t he = hipDeviceSynchronize();
-    float t = 0.f;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseInvCost), hipMemcpyDeviceToHost);
-    if (he != hipSuccess) return azd::hip_fail(he, "probe_inv_cost");
-    if (ms) *ms = t;
-    return AZD_OK;
+    const auto check = [=](const uint64_t *g, int i) { return inv_check(name, wide, g, n, i, recipe); };
+    return probe_dense_cost<azd::DenseInvCost>(name, "probe_inv_cost", device, adj, n, count, reps, reinterpret_cast<const azd::DenseInvRecipe *>(recipe), out, ms, check,
+                                               wide ? azd::launch_probe_inv_cost_wide : azd::launch_probe_inv_cost);
 }
 int azd_debug_probe_inv_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_inv_recipe *recipe,
                              azd_dense_inv_cost_t *out, float *ms) {
@@ -378,38 +372,12 @@ int azd_dense_invx_cost_wide(const uint64_t *adj, int n, const azd_dense_invx_re
     azd::dense_invx_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvxRecipe *>(recipe), reinterpret_cast<azd::DenseInvxCost *>(out));
     return AZD_OK;
 }
-// the two probes: the same host side around the 32-row and the 64-row kernel
+// the two probes: the 32-row and the 64-row kernel
 static int probe_invx_cost(const char *name, bool wide, int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
                            azd_dense_invx_cost_t *out, float *ms) {
-    const auto launch = wide ? azd::launch_probe_invx_cost_wide : azd::launch_probe_invx_cost;
-    if (!out || count <= 0 || reps <= 0) {
-        azd::g_last_error = std::string(name) + ": out / count / reps";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
-        AZD_ST(invx_check(name, wide, adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n, i, recipe));
-    AZD_ST(azd::device_ok(device));
-    AZD_HIP(hipSetDevice(device));
-    azd::DevBuf<uint64_t> d_adj;
-    azd::DevBuf<azd::DenseInvxCost> d_out;
-    azd::DevBuf<azd::DenseInvxRecipe> d_recipe;
-    azd::Event e0, e1;
-    AZD_ST(azd::alloc_set(d_adj, (size_t)count * n, d_out, (size_t)count, d_recipe, (size_t)1));
-    AZD_ST(e0.create());
-    AZD_ST(e1.create());
-    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
-    AZD_HIP(hipMemcpy(d_recipe, recipe, sizeof(azd::DenseInvxRecipe), hipMemcpyHostToDevice));
-    launch(d_adj, n, count, 1, d_recipe, d_out, nullptr); // warm-up
-    AZD_HIP(hipEventRecord(e0, nullptr));
-    launch(d_adj, n, count, reps, d_recipe, d_out, nullptr);
-    AZD_HIP(hipEventRecord(e1, nullptr));
-    hipError_t he = hipDeviceSynchronize();
-    float t = 0.f;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseInvxCost), hipMemcpyDeviceToHost);
-    if (he != hipSuccess) return azd::hip_fail(he, "probe_invx_cost");
-    if (ms) *ms = t;
-    return AZD_OK;
+    const auto check = [=](const uint64_t *g, int i) { return invx_check(name, wide, g, n, i, recipe); };
+    return probe_dense_cost<azd::DenseInvxCost>(name, "probe_invx_cost", device, adj, n, count, reps, reinterpret_cast<const azd::DenseInvxRecipe *>(recipe), out, ms,
+                                                check, wide ? azd::launch_probe_invx_cost_wide : azd::launch_probe_invx_cost);
 }
 int azd_debug_probe_invx_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
                               azd_dense_invx_cost_t *out, float *ms) {
@@ -458,34 +426,9 @@ int azd_dense_invs_spectrum(const uint64_t *adj, int n, int which, double *out) 
 int azd_debug_probe_invs_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invs_recipe *recipe,
                               azd_dense_invs_cost_t *out, float *ms) {
     const char *const name = "azd_debug_probe_invs_cost";
-    if (!out || count <= 0 || reps <= 0) {
-        azd::g_last_error = std::string(name) + ": out / count / reps";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    for (int i = 0; i < count; ++i) // (before the device check, like every limit: the kernel indexes LDS by the bits of adj)
-        AZD_ST(invs_check(name, adj ? adj + (size_t)i * (n > 0 ? n : 0) : nullptr, n, i, recipe));
-    AZD_ST(azd::device_ok(device));
-    AZD_HIP(hipSetDevice(device));
-    azd::DevBuf<uint64_t> d_adj;
-    azd::DevBuf<azd::DenseInvsCost> d_out;
-    azd::DevBuf<azd::DenseInvsRecipe> d_recipe;
-    azd::Event e0, e1;
-    AZD_ST(azd::alloc_set(d_adj, (size_t)count * n, d_out, (size_t)count, d_recipe, (size_t)1));
-    AZD_ST(e0.create());
-    AZD_ST(e1.create());
-    AZD_HIP(hipMemcpy(d_adj, adj, (size_t)count * n * 8, hipMemcpyHostToDevice));
-    AZD_HIP(hipMemcpy(d_recipe, recipe, sizeof(azd::DenseInvsRecipe), hipMemcpyHostToDevice));
-    azd::launch_probe_invs_cost(d_adj, n, count, 1, d_recipe, d_out, nullptr); // warm-up
-    AZD_HIP(hipEventRecord(e0, nullptr));
-    azd::launch_probe_invs_cost(d_adj, n, count, reps, d_recipe, d_out, nullptr);
-    AZD_HIP(hipEventRecord(e1, nullptr));
-    hipError_t he = hipDeviceSynchronize();
-    float t = 0.f;
-    if (he == hipSuccess) he = hipEventElapsedTime(&t, e0, e1);
-    if (he == hipSuccess) he = hipMemcpy(out, d_out, (size_t)count * sizeof(azd::DenseInvsCost), hipMemcpyDeviceToHost);
-    if (he != hipSuccess) return azd::hip_fail(he, "probe_invs_cost");
-    if (ms) *ms = t;
-    return AZD_OK;
+    const auto check = [=](const uint64_t *g, int i) { return invs_check(name, g, n, i, recipe); };
+    return probe_dense_cost<azd::DenseInvsCost>(name, "probe_invs_cost", device, adj, n, count, reps, reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), out, ms,
+                                                check, azd::launch_probe_invs_cost);
 }
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
     if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;
