@@ -29,6 +29,7 @@ ENGINE_EXT_POOL_F32 = 128  # AZD_ENGINE_EXT_POOL_F32: beside ENGINE_EXT_POOL_STE
 ENGINE_DENSE_INV = 1024  # AZD_ENGINE_DENSE_INV: the dense-graph space with the weighted-invariant cost (n <= 32; recipe set at run time)
 ENGINE_DENSE_INV_WIDE = 2048  # AZD_ENGINE_DENSE_INV_WIDE: beside ENGINE_DENSE_INV only: the weighted-invariant cost up to n = 64 (64-row kernels)
 ENGINE_DENSE_INVX_WIDE = 8192  # AZD_ENGINE_DENSE_INVX_WIDE: beside ENGINE_DENSE_INVX only: the extended invariant cost up to n = 64 (64-row kernels)
+ENGINE_DENSE_INVS_WIDE = 32768  # AZD_ENGINE_DENSE_INVS_WIDE: beside ENGINE_DENSE_INVS only: the spectrum invariant cost up to n = 64 (64-row kernels)
 ENGINE_DENSE_INVS = 16384  # AZD_ENGINE_DENSE_INVS: the dense-graph space with the spectrum invariant cost (n <= 32; twenty-one invariants: energies, spread)
 ENGINE_DENSE_INVX = 4096  # AZD_ENGINE_DENSE_INVX: the dense-graph space with the extended invariant cost (n <= 32; sixteen invariants, pair terms)
 ENGINE_RAMSEY_BIG_CLIQUES = 512  # AZD_ENGINE_RAMSEY_BIG_CLIQUES: beside ENGINE_RAMSEY_U64 only: clique sizes up to 8 (kernels of their own)
@@ -57,6 +58,7 @@ DENSE_INVX_MUL, DENSE_INVX_DIV = 0, 1  # AZD_DENSE_INVX_MUL / _DIV: a pair term'
 # AZD_DENSE_INVX_NAMES: index and name are ABI; the first ten are DENSE_INV_NAMES
 DENSE_INVX_NAMES = DENSE_INV_NAMES + ("lap_eig", "slap_eig", "randic", "zagreb1", "zagreb2", "triangles")
 DENSE_INVS_MAX_N = 32   # AZD_DENSE_INVS_MAX_N: the spectrum invariant cost (azd_dense_invs_cost)
+DENSE_INVS_WIDE_MAX_N = 64  # AZD_DENSE_INVS_WIDE_MAX_N: its 64-row form (azd_dense_invs_cost_wide, ENGINE_DENSE_INVS_WIDE)
 DENSE_INVS_COUNT = 21   # AZD_DENSE_INVS_COUNT
 DENSE_INVS_ROUNDS = 67  # AZD_DENSE_INVS_ROUNDS: bisection rounds of the whole-spectrum procedure
 # AZD_DENSE_INVS_NAMES: index and name are ABI; the first sixteen are DENSE_INVX_NAMES
@@ -165,6 +167,11 @@ class DenseInvsCost(C.Structure):  # azd_dense_invs_cost_t
 
 class DenseInvsArgmin(C.Structure):  # azd_dense_invs_argmin: ArgminData of a dense engine with the spectrum invariant cost
     _fields_ = [("adj", C.c_uint64 * 32), ("permitted", C.c_uint64 * 8), ("inv", C.c_double * 21), ("dist_k", C.c_int32),
+                ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
+
+
+class DenseInvsWideArgmin(C.Structure):  # azd_dense_invs_wide_argmin: the same of an engine with ENGINE_DENSE_INVS_WIDE (n <= 64, E <= 2016)
+    _fields_ = [("adj", C.c_uint64 * 64), ("permitted", C.c_uint64 * 32), ("inv", C.c_double * 21), ("dist_k", C.c_int32),
                 ("computed", C.c_uint32), ("cost", C.c_float), ("eval", C.c_float), ("agent", C.c_int32), ("node", C.c_uint32)]
 
 
@@ -326,6 +333,10 @@ def lib():
     sig("azd_dense_invs_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvsRecipe), C.POINTER(DenseInvsCost))
     sig("azd_dense_invs_spectrum", C.c_int, vp, C.c_int, C.c_int, vp)
     sig("azd_debug_probe_invs_cost", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DenseInvsRecipe), vp, f32p)
+    sig("azd_dense_invs_cost_wide", C.c_int, vp, C.c_int, C.POINTER(DenseInvsRecipe), C.POINTER(DenseInvsCost))
+    sig("azd_dense_invs_spectrum_wide", C.c_int, vp, C.c_int, C.c_int, vp)
+    sig("azd_debug_probe_invs_cost_wide", C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DenseInvsRecipe), vp, f32p)
+    sig("azd_engine_dense_invs_wide_argmin_data", C.c_int, vp, C.POINTER(DenseInvsWideArgmin))
     sig("azd_engine_set_dense_invs_recipe", C.c_int, vp, C.POINTER(DenseInvsRecipe))
     sig("azd_engine_dense_invs_argmin_data", C.c_int, vp, C.POINTER(DenseInvsArgmin))
     sig("azd_engine_dense_invs_agent_cost", C.c_int, vp, C.c_int, C.POINTER(DenseInvsCost))

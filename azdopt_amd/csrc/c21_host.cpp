@@ -582,6 +582,10 @@ void dense_invx_cost_host(const uint64_t *adj, int n, const DenseInvxRecipe &r, 
 const char *dense_invs_check_graph(const uint64_t *adj, int n) {
     return ah_check_graph(adj, n, DENSE_INVS_MAX_N, "n: the spectrum invariant cost needs 4 <= n <= 32 (AZD_DENSE_INVS_MAX_N)");
 }
+const char *dense_invs_check_graph_wide(const uint64_t *adj, int n) {
+    static_assert(DENSE_INVS_WIDE_MAX_N <= DENSE_AH_WIDE_MAX_N, "the host stages below are sized by DENSE_AH_WIDE_MAX_N");
+    return ah_check_graph(adj, n, DENSE_INVS_WIDE_MAX_N, "n: the wide spectrum invariant cost needs 4 <= n <= 64 (AZD_DENSE_INVS_WIDE_MAX_N)");
+}
 const char *dense_invs_check_recipe(const DenseInvsRecipe *r, int n) {
     if (!r) return "recipe: null";
     bool any = false;

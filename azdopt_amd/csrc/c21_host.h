@@ -180,8 +180,8 @@ const char *dense_invx_check_graph_wide(const uint64_t *adj, int n); // 4 <= n <
 // n <= DENSE_INVX_WIDE_MAX_N (one function behind azd_dense_invx_cost and azd_dense_invx_cost_wide: the limit is the callers' check)
 void dense_invx_cost_host(const uint64_t *adj, int n, const DenseInvxRecipe &r, DenseInvxCost *out);
 
-// Spectrum invariant cost of a connected graph on 4 <= n <= DENSE_INVS_MAX_N vertices (BUILD-DEFINED; DESIGN.md "The spectrum
-// invariant cost"; AZD_ENGINE_DENSE_INVS): twenty-one invariants -- index and name are ABI.  0 .. 15 are the extended invariant cost's;
+// Spectrum invariant cost of a connected graph on 4 <= n <= DENSE_INVS_MAX_N vertices, or DENSE_INVS_WIDE_MAX_N in the 64-row form
+// (BUILD-DEFINED; DESIGN.md "The spectrum invariant cost"; AZD_ENGINE_DENSE_INVS, AZD_ENGINE_DENSE_INVS_WIDE): twenty-one invariants -- index and name are ABI.  0 .. 15 are the extended invariant cost's;
 //   16 adj_energy = sum_l |theta_l(A)|   17 dist_energy = sum_l |theta_l(D)|
 //   18 lap_energy = sum_l |theta_l(L) - s|   19 slap_energy = sum_l |theta_l(Q) - s|,  s = (double)(sum of degrees) / (double)n
 //   20 adj_spread = theta_{n-1}(A) - theta_0(A)
@@ -196,6 +196,7 @@ void dense_invx_cost_host(const uint64_t *adj, int n, const DenseInvxRecipe &r, 
 // with n >= 4 (A, D, L - sI and Q - sI are not zero and have trace zero), so all five may divide.  With weights 16 .. 20 zero and no
 // term naming 16 .. 20 the sequence of operations is dense_invx_cost_host's.
 constexpr int DENSE_INVS_MAX_N = 32;
+constexpr int DENSE_INVS_WIDE_MAX_N = 64; // AZD_ENGINE_DENSE_INVS_WIDE engines, azd_dense_invs_cost_wide: the same procedure with 64 rows
 constexpr int DENSE_INVS_COUNT = 21;
 constexpr int DENSE_INVS_ADJ_ENERGY = 16, DENSE_INVS_DIST_ENERGY = 17, DENSE_INVS_LAP_ENERGY = 18, DENSE_INVS_SLAP_ENERGY = 19, DENSE_INVS_ADJ_SPREAD = 20;
 constexpr int DENSE_INVS_ROUNDS = 67; // bisection rounds of the whole-spectrum finisher: the same for every lane
@@ -226,6 +227,9 @@ constexpr uint32_t dense_invs_needed(const DenseInvsRecipe &r) {
 constexpr int DENSE_INVS_MATRIX_ADJ = 0, DENSE_INVS_MATRIX_DIST = 1, DENSE_INVS_MATRIX_LAP = 2, DENSE_INVS_MATRIX_SLAP = 3;
 const char *dense_invs_check_recipe(const DenseInvsRecipe *r, int n);
 const char *dense_invs_check_graph(const uint64_t *adj, int n); // 4 <= n <= DENSE_INVS_MAX_N, in this cost's words
+const char *dense_invs_check_graph_wide(const uint64_t *adj, int n); // 4 <= n <= DENSE_INVS_WIDE_MAX_N
+// n <= DENSE_INVS_WIDE_MAX_N (one function behind azd_dense_invs_cost and azd_dense_invs_cost_wide, and one behind the two
+// spectrum calls: the limit is the callers' check)
 void dense_invs_cost_host(const uint64_t *adj, int n, const DenseInvsRecipe &r, DenseInvsCost *out);
 // theta_0 .. theta_{n-1} of matrix `which` (DENSE_INVS_MATRIX_*), ascending: what the energies and the spread are summed from
 void dense_invs_spectrum_host(const uint64_t *adj, int n, int which, double *out);

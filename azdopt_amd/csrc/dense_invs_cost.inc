@@ -15,14 +15,19 @@
 // its one result is held across the next reduction.
 // A matrix is reduced at most once per cost: a pass runs when its *_eig, its energy or (adjacency) the spread is needed; after the
 // reduction the multisection runs only for the *_eig, the bisections only for the energy or the spread (wave-uniform branches).
-// The row limit is 32: the 64-row form of this cost is not built.
+// The row limit ROWS is a template parameter of everything here that depends on it, as in dense_invx_cost.inc: 32 (DenseCostInvS:
+// dense_invs_kernels.hip, AZD_ENGINE_DENSE_INVS) or 64 (DenseCostInvSWide: dense_invs_wide_kernels.hip, AZD_ENGINE_DENSE_INVS_WIDE
+// beside the first flag: a triangle of 2080 doubles serves the four passes), and the engine's argmin record follows from it.  At 64
+// rows and n = 64 every lane owns an eigenvalue of the whole-spectrum finisher, the spread's upper shuffle reads lane 63, and the
+// vertex mask is formed without a shift by 64 (dense_vertex_mask).  Order of operations, lane roles and reductions do not depend on
+// ROWS: at n <= 32 the two compute the same bits.
 //
-// adj: the graph's neighbourhood bitsets in LDS (n <= 32 words are read).  rc: the recipe in device memory, the same address in
+// adj: the graph's neighbourhood bitsets in LDS (n <= ROWS words are read).  rc: the recipe in device memory, the same address in
 // every lane.  hook: called once, after the BFS (the pool step's deferred post).  Wave-uniform result in `out`.
-template <class Hook>
-__device__ __forceinline__ void dense_invs_cost_wave(const uint64_t *adj, DenseAhLdsT<DENSE_INVS_MAX_N> &w, const int n, const DenseInvsRecipe *rc,
+template <int ROWS, class Hook>
+__device__ __forceinline__ void dense_invs_cost_wave(const uint64_t *adj, DenseAhLdsT<ROWS> &w, const int n, const DenseInvsRecipe *rc,
                                                      Hook &&hook, DenseInvsCost &out) {
-    constexpr int ROWS = DENSE_INVS_MAX_N;
+    static_assert(ROWS == DENSE_INVS_MAX_N || ROWS == DENSE_INVS_WIDE_MAX_N, "the row limits that are built");
     const int lane = LANE;
     const int row = lane * (lane + 1) / 2; // this lane's row of the packed triangle (lanes < n only)
     const bool in = lane < n;
@@ -113,25 +118,29 @@ __device__ __forceinline__ void dense_invs_cost_wave(const uint64_t *adj, DenseA
 }
 
 // ---------------------------------------------------------------- the spectrum invariant cost as a DenseSpace's cost policy
-// (dense_spectral.inc: DenseCostRecipeT -- a wave's block is the 32-row AH block, the recipe lies behind twenty-one doubles per
-// agent).  No pool searchers are built with this policy: dense_invs_kernels.hip.
+// (dense_spectral.inc: DenseCostRecipeT -- a wave's block is the AH block of the same row limit, the recipe lies behind twenty-one
+// doubles per agent).  No pool searchers are built with these policies: dense_invs_kernels.hip, dense_invs_wide_kernels.hip.
 struct DenseInvsCostFn {
     template <class W, class Hook>
     __device__ static __forceinline__ void run(const uint64_t *adj, W &w, const int n, const DenseInvsRecipe *rc, Hook &&hook, DenseInvsCost &out) {
         dense_invs_cost_wave(adj, w, n, rc, hook, out);
     }
 };
+// Named structs, not aliases: the kernels' names carry them (k_rollout<DenseSpace<2, DenseCostInvS>>)
 struct DenseCostInvS : DenseCostRecipeT<DenseInvsCost, DenseInvsRecipe, DENSE_INVS_COUNT, DENSE_INVS_MAX_N, DenseInvsArgminRec, DenseInvsCostFn> {};
+struct DenseCostInvSWide : DenseCostRecipeT<DenseInvsCost, DenseInvsRecipe, DENSE_INVS_COUNT, DENSE_INVS_WIDE_MAX_N, DenseInvsWideArgminRec, DenseInvsCostFn> {};
 
-// The cost outside any engine (space_ops.h: launch_probe_invs_cost): one wave per graph, `reps` repetitions (timing), the result of
-// the last one.  The host has checked the graphs and the recipe (engine_probes.hip): LDS is indexed by the bits of adj.
+// The cost outside any engine (space_ops.h: launch_probe_invs_cost, launch_probe_invs_cost_wide): one wave per graph, `reps`
+// repetitions (timing), the result of the last one.  Each unit launches the instantiation of its own row limit.  The host has
+// checked the graphs and the recipe (engine_probes.hip): LDS is indexed by the bits of adj.
+template <int ROWS>
 __global__ __launch_bounds__(64) void k_probe_invs_cost(const uint64_t *__restrict__ adj, const int n, const int count, const int reps,
                                                         const DenseInvsRecipe *__restrict__ recipe, DenseInvsCost *__restrict__ out) {
-    __shared__ uint64_t s_adj[DENSE_INVS_MAX_N];
-    __shared__ DenseAhLdsT<DENSE_INVS_MAX_N> w;
+    __shared__ uint64_t s_adj[ROWS];
+    __shared__ DenseAhLdsT<ROWS> w;
     const int g = blockIdx.x;
     if (g >= count) return;
-    if (LANE < DENSE_INVS_MAX_N) s_adj[LANE] = LANE < n ? adj[(size_t)g * n + LANE] : 0ull;
+    if (LANE < ROWS) s_adj[LANE] = LANE < n ? adj[(size_t)g * n + LANE] : 0ull;
     LDS_SYNC();
     DenseInvsCost c;
     for (int r = 0; r < reps; ++r) {

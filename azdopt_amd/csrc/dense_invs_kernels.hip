@@ -46,7 +46,7 @@ const SpaceOps &dense_invs_ops() {
 }
 
 void launch_probe_invs_cost(const uint64_t *d_adj, int n, int count, int reps, const DenseInvsRecipe *d_recipe, DenseInvsCost *d_out, void *stream) {
-    k_probe_invs_cost<<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, reps, d_recipe, d_out);
+    k_probe_invs_cost<DENSE_INVS_MAX_N><<<dim3(count), dim3(64), 0, (hipStream_t)stream>>>(d_adj, n, count, reps, d_recipe, d_out);
 }
 
 } // namespace azd

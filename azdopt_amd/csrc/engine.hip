@@ -70,7 +70,7 @@ static const ExtPoolForm *ext_pool_form(bool dense_space) {
     return dense_space ? &dense : &ramsey;
 }
 
-// The thirteen kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
+// The fourteen kinds of engine (engine_impl.h: TierDesc).  The tables of c21 and Ramsey (space_ops.h) are put together from their units'
 // parts: c21 has no searcher-only pool step; the 64-bit Ramsey tier's is joined to the three parts of its phase unit's table.
 static const TierDesc *tier_desc(Tier t) {
     static const SpaceOps c21 = {c21_phase_ops(), c21_async_ops(), c21_pool_ops(), PoolSearchOps{}};
@@ -125,13 +125,17 @@ static const TierDesc *tier_desc(Tier t) {
         // (no searcher-only pool step on this tier yet: ext is null, so its engines run one launch per phase at every population)
         {TIER_DENSE_INVS, SPACE_DENSE, &dense_invs_ops(), nullptr, sizeof(DenseInvsArgminRec), 0, false, true, false, DENSE_INVS_COUNT, 2,
          (int)((sizeof(DenseInvsRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+        // AZD_ENGINE_DENSE_INVS_WIDE beside it: the same record per agent over the 64-row kernels (dense_invs_wide_kernels.hip); no pool step either
+        {TIER_DENSE_INVS_WIDE, SPACE_DENSE, &dense_invs_wide_ops(), nullptr, sizeof(DenseInvsWideArgminRec), 0, false, true, false, DENSE_INVS_COUNT, 2,
+         (int)((sizeof(DenseInvsRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
     };
     return &tiers[t];
 }
 // the tier of a configuration that check_engine_config has accepted: the flags name it, never the sizes
 const TierDesc *engine_tier(const azd_engine_config *cfg) {
     if (cfg->space_id == AZD_SPACE_DENSE)
-        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_INVS      ? TIER_DENSE_INVS
+        return tier_desc(cfg->flags & AZD_ENGINE_DENSE_INVS_WIDE ? TIER_DENSE_INVS_WIDE
+                         : cfg->flags & AZD_ENGINE_DENSE_INVS    ? TIER_DENSE_INVS
                          : cfg->flags & AZD_ENGINE_DENSE_INVX_WIDE ? TIER_DENSE_INVX_WIDE
                          : cfg->flags & AZD_ENGINE_DENSE_INVX    ? TIER_DENSE_INVX
                          : cfg->flags & AZD_ENGINE_DENSE_INV_WIDE ? TIER_DENSE_INV_WIDE
@@ -431,7 +435,22 @@ int check_engine_config(const azd_engine_config *cfg) {
                       "AZD_SPACE_RAMSEY with max_slots > 0, whose kernels for clique sizes up to 8 it asks for)");
     const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
     const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
-    if (cfg->flags & AZD_ENGINE_DENSE_INVS) { // the spectrum invariant cost: a tier of its own, asked for by name; the INVX tier's limits
+    if (cfg->flags & AZD_ENGINE_DENSE_INVS_WIDE) { // the spectrum invariant cost's 64-row form: a second flag beside the first, never a cost of its own
+        const char *bad = !(cfg->flags & AZD_ENGINE_DENSE_INVS)
+                              ? "flags: AZD_ENGINE_DENSE_INVS_WIDE is valid only beside AZD_ENGINE_DENSE_INVS (the spectrum invariant cost whose 64-row form it asks for)"
+                          : dense_ah || dense_ah_wide || (cfg->flags & (AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE | AZD_ENGINE_DENSE_INVX | AZD_ENGINE_DENSE_INVX_WIDE))
+                              ? "flags: AZD_ENGINE_DENSE_INVS_WIDE belongs to a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
+                                "AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX or AZD_ENGINE_DENSE_INVX_WIDE (the Aouchiche-Hansen cost, the "
+                                "weighted-invariant cost and the extended invariant cost are among its recipes)"
+                          : !dense ? "space_id: AZD_ENGINE_DENSE_INVS_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
+                          : cfg->n < 4 || cfg->n > AZD_DENSE_INVS_WIDE_MAX_N ? "n: the wide spectrum invariant cost needs 4 <= n <= 64 (AZD_DENSE_INVS_WIDE_MAX_N)"
+                          : cfg->layers > 1 ? "layers: AZD_ENGINE_DENSE_INVS_WIDE engines take no Layered wrapper (layers <= 1)"
+                          : cfg->path_kind != AZD_PATH_SET ? "path_kind: AZD_ENGINE_DENSE_INVS_WIDE engines keep ActionSet paths (AZD_PATH_SET)"
+                          : cfg->max_slots < 1 || cfg->max_slots > std::min(dense_edges(cfg->n), 640)
+                              ? "max_slots: AZD_ENGINE_DENSE_INVS_WIDE needs 1 <= max_slots <= min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)"
+                              : nullptr;
+        if (bad) return refuse(bad);
+    } else if (cfg->flags & AZD_ENGINE_DENSE_INVS) { // the spectrum invariant cost: a tier of its own, asked for by name; the INVX tier's limits
         const char *bad = dense_ah || dense_ah_wide || (cfg->flags & (AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE | AZD_ENGINE_DENSE_INVX | AZD_ENGINE_DENSE_INVX_WIDE))
                               ? "flags: AZD_ENGINE_DENSE_INVS is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
                                 "AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX or AZD_ENGINE_DENSE_INVX_WIDE (the Aouchiche-Hansen cost, the "
@@ -844,11 +863,11 @@ int azd_engine_create(azd_engine **out, const azd_engine_config *cfg, azd_evalua
         AZD_ST(e->alloc(&e->d_stage_slots, B * (size_t)((a.E + 63) / 64)));
         // (a tier's kernels write its own record where argmin_d points, TierDesc::argmin_bytes of it: so many records of the default
         // cost's type, as argmin_r_recs counts them for the Ramsey tiers -- one for every tier but the 64-row invariant
-        // ones, whose 64 rows, 32 slot words and ten or sixteen invariants come to 872 and 920 bytes where the default cost's record has 856)
+        // ones, whose 64 rows, 32 slot words and ten, sixteen or twenty-one invariants come to 872, 920 and 960 bytes where the default cost's record has 856)
         static_assert(sizeof(azd::DenseAhArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseAhWideArgminRec) <= sizeof(azd::DenseArgminRec) &&
                           sizeof(azd::DenseInvArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseInvWideArgminRec) <= 2 * sizeof(azd::DenseArgminRec) &&
                           sizeof(azd::DenseInvxArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseInvxWideArgminRec) <= 2 * sizeof(azd::DenseArgminRec) &&
-                          sizeof(azd::DenseInvsArgminRec) <= sizeof(azd::DenseArgminRec),
+                          sizeof(azd::DenseInvsArgminRec) <= sizeof(azd::DenseArgminRec) && sizeof(azd::DenseInvsWideArgminRec) <= 2 * sizeof(azd::DenseArgminRec),
                       "an AH or INV engine's argmin record lives in argmin_d's allocation");
         AZD_ST(e->alloc(&a.argmin_d, (tier->argmin_bytes + sizeof(azd::DenseArgminRec) - 1) / sizeof(azd::DenseArgminRec)));
         if (tier->id == TIER_DENSE) AZD_ST(e->alloc(&a.node_mate, B * (size_t)a.node_cap * 64)); // (the AH and the weighted-invariant cost keep nothing per node)

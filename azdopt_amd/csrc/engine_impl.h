@@ -37,7 +37,7 @@ struct ExtPoolForm {
 
 // The kind of engine a configuration asks for, and what the host code goes by for it: chosen once (engine_tier, after
 // check_engine_config has accepted the configuration), never re-derived from how the arenas were filled.
-enum Tier { TIER_C21, TIER_RAMSEY, TIER_RAMSEY_WIDE, TIER_RAMSEY_U64, TIER_RAMSEY_U64_BIG, TIER_DENSE, TIER_DENSE_AH, TIER_DENSE_AH_WIDE, TIER_DENSE_INV, TIER_DENSE_INV_WIDE, TIER_DENSE_INVX, TIER_DENSE_INVX_WIDE, TIER_DENSE_INVS, TIER_COUNT };
+enum Tier { TIER_C21, TIER_RAMSEY, TIER_RAMSEY_WIDE, TIER_RAMSEY_U64, TIER_RAMSEY_U64_BIG, TIER_DENSE, TIER_DENSE_AH, TIER_DENSE_AH_WIDE, TIER_DENSE_INV, TIER_DENSE_INV_WIDE, TIER_DENSE_INVX, TIER_DENSE_INVX_WIDE, TIER_DENSE_INVS, TIER_DENSE_INVS_WIDE, TIER_COUNT };
 struct TierDesc {
     Tier id;
     int space;                  // azd::SPACE_*
@@ -63,7 +63,7 @@ inline bool tier_inv(const TierDesc *t) { return t->id == TIER_DENSE_INV || t->i
 // ... and the extended invariant cost at either row limit, likewise
 inline bool tier_invx(const TierDesc *t) { return t->id == TIER_DENSE_INVX || t->id == TIER_DENSE_INVX_WIDE; }
 // ... and the spectrum invariant cost, which has one row limit
-inline bool tier_invs(const TierDesc *t) { return t->id == TIER_DENSE_INVS; }
+inline bool tier_invs(const TierDesc *t) { return t->id == TIER_DENSE_INVS || t->id == TIER_DENSE_INVS_WIDE; }
 
 // The evaluator groups' device memory (PoolArgs::grp_*): the two tables of the plan, and the per-slot exchange state, regrown as a
 // whole when the plan needs more of any of it.
@@ -97,7 +97,7 @@ struct azd_engine {
     azd_engine_config cfg;
     azd::Arenas a;
     const azd::SpaceOps *ops = nullptr; // the launchers and LDS plans of the engine's space and tier (space_ops.h)
-    const TierDesc *tier = nullptr;     // which of the thirteen kinds of engine this is (engine_tier)
+    const TierDesc *tier = nullptr;     // which of the fourteen kinds of engine this is (engine_tier)
     bool inv_recipe_set = false;        // AZD_ENGINE_DENSE_INV: azd_engine_set_dense_inv_recipe has run (par_new refuses before it) ...
     azd::DenseInvRecipe inv_recipe{};   // ... the recipe as set (the device's copy lies behind cur_lambda's per-agent part)
     azd::DenseInvxRecipe invx_recipe{}; // ... (AZD_ENGINE_DENSE_INVX: azd_engine_set_dense_invx_recipe's, kept the same way under the same two flags)

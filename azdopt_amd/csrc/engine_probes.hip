@@ -107,7 +107,7 @@ int azd_debug_probe_xcc(int device, uint32_t *out, int n_blocks) {
 int azd_debug_ext_pool_plan(const azd_engine_config *cfg, int *waves, size_t *lds_bytes) {
     if (!cfg || !waves || !lds_bytes) return AZD_ERR_INVALID_ARGUMENT;
     AZD_ST(check_engine_config(cfg));
-    const bool ah_wide = (cfg->flags & (AZD_ENGINE_DENSE_AH_WIDE | AZD_ENGINE_DENSE_INV_WIDE | AZD_ENGINE_DENSE_INVX_WIDE)) != 0; // (the 64-row tiers)
+    const bool ah_wide = (cfg->flags & (AZD_ENGINE_DENSE_AH_WIDE | AZD_ENGINE_DENSE_INV_WIDE | AZD_ENGINE_DENSE_INVX_WIDE | AZD_ENGINE_DENSE_INVS_WIDE)) != 0; // (the 64-row tiers; the last has no such step and is told so below)
     // (a dense-graph configuration that sets AZD_ENGINE_EXT_POOL_F32 alone asks its pool step for the fp32 evaluator: the plan is
     // that step's, whatever the cost -- the searchers do not know which evaluator serves them)
     const bool dense_f32 = cfg->space_id == AZD_SPACE_DENSE && (cfg->flags & AZD_ENGINE_EXT_POOL_F32) != 0;
@@ -388,13 +388,13 @@ int azd_debug_probe_invx_cost_wide(int device, const uint64_t *adj, int n, int c
     return probe_invx_cost("azd_debug_probe_invx_cost_wide", true, device, adj, n, count, reps, recipe, out, ms);
 }
 // ------------------------------------------------------------------ spectrum invariant cost of the dense-graph space
-static_assert(AZD_DENSE_INVS_MAX_N == azd::DENSE_INVS_MAX_N && AZD_DENSE_INVS_COUNT == azd::DENSE_INVS_COUNT && AZD_DENSE_INVS_ROUNDS == azd::DENSE_INVS_ROUNDS &&
+static_assert(AZD_DENSE_INVS_MAX_N == azd::DENSE_INVS_MAX_N && AZD_DENSE_INVS_WIDE_MAX_N == azd::DENSE_INVS_WIDE_MAX_N && AZD_DENSE_INVS_COUNT == azd::DENSE_INVS_COUNT && AZD_DENSE_INVS_ROUNDS == azd::DENSE_INVS_ROUNDS &&
                   AZD_DENSE_INVS_MATRIX_ADJ == azd::DENSE_INVS_MATRIX_ADJ && AZD_DENSE_INVS_MATRIX_DIST == azd::DENSE_INVS_MATRIX_DIST &&
                   AZD_DENSE_INVS_MATRIX_LAP == azd::DENSE_INVS_MATRIX_LAP && AZD_DENSE_INVS_MATRIX_SLAP == azd::DENSE_INVS_MATRIX_SLAP,
               "AZD_DENSE_INVS_*");
 // graph `i` (or the only one) and the recipe, checked in this order; the text names `fn` and the argument
-static int invs_check(const char *fn, const uint64_t *adj, int n, int i, const azd_dense_invs_recipe *recipe) {
-    const char *why = azd::dense_invs_check_graph(adj, n);
+static int invs_check(const char *fn, bool wide, const uint64_t *adj, int n, int i, const azd_dense_invs_recipe *recipe) {
+    const char *why = wide ? azd::dense_invs_check_graph_wide(adj, n) : azd::dense_invs_check_graph(adj, n);
     if (!why) why = azd::dense_invs_check_recipe(reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), n);
     else if (i >= 0) {
         azd::g_last_error = std::string(fn) + ": graph " + std::to_string(i) + ": " + why;
@@ -403,32 +403,50 @@ static int invs_check(const char *fn, const uint64_t *adj, int n, int i, const a
     if (why) azd::g_last_error = std::string(fn) + ": " + why;
     return why ? AZD_ERR_INVALID_ARGUMENT : AZD_OK;
 }
-int azd_dense_invs_cost(const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out) {
+// the two host costs and the two spectrum calls: one host function each behind the 32-row and the 64-row check
+static int invs_cost(const char *fn, bool wide, const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out) {
     if (!out) {
-        azd::g_last_error = "azd_dense_invs_cost: out: null";
+        azd::g_last_error = std::string(fn) + ": out: null";
         return AZD_ERR_INVALID_ARGUMENT;
     }
-    AZD_ST(invs_check("azd_dense_invs_cost", adj, n, -1, recipe));
+    AZD_ST(invs_check(fn, wide, adj, n, -1, recipe));
     azd::dense_invs_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), reinterpret_cast<azd::DenseInvsCost *>(out));
     return AZD_OK;
 }
-int azd_dense_invs_spectrum(const uint64_t *adj, int n, int which, double *out) {
-    const char *why = !out ? "out: null" : azd::dense_invs_check_graph(adj, n);
+static int invs_spectrum(const char *fn, bool wide, const uint64_t *adj, int n, int which, double *out) {
+    const char *why = !out ? "out: null" : wide ? azd::dense_invs_check_graph_wide(adj, n) : azd::dense_invs_check_graph(adj, n);
     if (!why && (which < AZD_DENSE_INVS_MATRIX_ADJ || which > AZD_DENSE_INVS_MATRIX_SLAP))
         why = "which: must be one of AZD_DENSE_INVS_MATRIX_ADJ, _DIST, _LAP, _SLAP (0 .. 3)";
     if (why) {
-        azd::g_last_error = std::string("azd_dense_invs_spectrum: ") + why;
+        azd::g_last_error = std::string(fn) + ": " + why;
         return AZD_ERR_INVALID_ARGUMENT;
     }
     azd::dense_invs_spectrum_host(adj, n, which, out);
     return AZD_OK;
 }
+int azd_dense_invs_cost(const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out) {
+    return invs_cost("azd_dense_invs_cost", false, adj, n, recipe, out);
+}
+int azd_dense_invs_cost_wide(const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out) {
+    return invs_cost("azd_dense_invs_cost_wide", true, adj, n, recipe, out);
+}
+int azd_dense_invs_spectrum(const uint64_t *adj, int n, int which, double *out) { return invs_spectrum("azd_dense_invs_spectrum", false, adj, n, which, out); }
+int azd_dense_invs_spectrum_wide(const uint64_t *adj, int n, int which, double *out) {
+    return invs_spectrum("azd_dense_invs_spectrum_wide", true, adj, n, which, out);
+}
 int azd_debug_probe_invs_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invs_recipe *recipe,
                               azd_dense_invs_cost_t *out, float *ms) {
     const char *const name = "azd_debug_probe_invs_cost";
-    const auto check = [=](const uint64_t *g, int i) { return invs_check(name, g, n, i, recipe); };
+    const auto check = [=](const uint64_t *g, int i) { return invs_check(name, false, g, n, i, recipe); };
     return probe_dense_cost<azd::DenseInvsCost>(name, "probe_invs_cost", device, adj, n, count, reps, reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), out, ms,
                                                 check, azd::launch_probe_invs_cost);
+}
+int azd_debug_probe_invs_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invs_recipe *recipe,
+                                   azd_dense_invs_cost_t *out, float *ms) {
+    const char *const name = "azd_debug_probe_invs_cost_wide";
+    const auto check = [=](const uint64_t *g, int i) { return invs_check(name, true, g, n, i, recipe); };
+    return probe_dense_cost<azd::DenseInvsCost>(name, "probe_invs_cost_wide", device, adj, n, count, reps, reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), out, ms,
+                                                check, azd::launch_probe_invs_cost_wide);
 }
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
     if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;

@@ -87,11 +87,14 @@ int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap,
 }
 // The dense argmin entries: `reads` is the tier whose record the entry copies out, `refusal` its text for an engine of another
 // tier -- said to an engine with the Aouchiche-Hansen cost (an engine without it is refused without a text), by the wide entry to all.
-// The two weighted-invariant tiers name each other's reader, as the two Aouchiche-Hansen tiers do, and so do the two extended ones.
+// The two weighted-invariant tiers name each other's reader, as the two Aouchiche-Hansen tiers do, and so do the two extended ones
+// and the two spectrum ones.
 static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes, const char *refusal) {
     if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
     if (e->tier->id != reads) {
-        if (e->tier->id == TIER_DENSE_INVS)
+        if (e->tier->id == TIER_DENSE_INVS_WIDE)
+            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVS_WIDE engine's record is read with azd_engine_dense_invs_wide_argmin_data";
+        else if (e->tier->id == TIER_DENSE_INVS)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVS engine's record is read with azd_engine_dense_invs_argmin_data";
         else if (e->tier->id == TIER_DENSE_INVX_WIDE)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVX_WIDE engine's record is read with azd_engine_dense_invx_wide_argmin_data";
@@ -102,7 +105,7 @@ static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes,
         else if (e->tier->id == TIER_DENSE_INV)
             azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_argmin_data";
         else if (e->tier->ah || reads == TIER_DENSE_AH_WIDE || reads == TIER_DENSE_INV || reads == TIER_DENSE_INV_WIDE || reads == TIER_DENSE_INVX ||
-                 reads == TIER_DENSE_INVX_WIDE || reads == TIER_DENSE_INVS)
+                 reads == TIER_DENSE_INVX_WIDE || reads == TIER_DENSE_INVS || reads == TIER_DENSE_INVS_WIDE)
             azd::g_last_error = refusal;
         return AZD_ERR_UNSUPPORTED;
     }
@@ -130,6 +133,9 @@ static_assert(sizeof(azd_dense_argmin) == sizeof(azd::DenseArgminRec) && sizeof(
                   sizeof(azd_dense_invx_cost_t) == sizeof(azd::DenseInvxCost) && offsetof(azd_dense_invx_cost_t, eval) == offsetof(azd::DenseInvxCost, eval) &&
                   sizeof(azd_dense_invs_argmin) == sizeof(azd::DenseInvsArgminRec) && offsetof(azd_dense_invs_argmin, node) == offsetof(azd::DenseInvsArgminRec, node) &&
                   offsetof(azd_dense_invs_argmin, inv) == offsetof(azd::DenseInvsArgminRec, inv) &&
+                  sizeof(azd_dense_invs_wide_argmin) == sizeof(azd::DenseInvsWideArgminRec) &&
+                  offsetof(azd_dense_invs_wide_argmin, node) == offsetof(azd::DenseInvsWideArgminRec, node) &&
+                  offsetof(azd_dense_invs_wide_argmin, inv) == offsetof(azd::DenseInvsWideArgminRec, inv) &&
                   sizeof(azd_dense_invs_recipe) == sizeof(azd::DenseInvsRecipe) && offsetof(azd_dense_invs_recipe, n_terms) == offsetof(azd::DenseInvsRecipe, n_terms) &&
                   offsetof(azd_dense_invs_recipe, term) == offsetof(azd::DenseInvsRecipe, term) &&
                   sizeof(azd_dense_invs_cost_t) == sizeof(azd::DenseInvsCost) && offsetof(azd_dense_invs_cost_t, eval) == offsetof(azd::DenseInvsCost, eval) &&
@@ -270,12 +276,16 @@ int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_co
     return AZD_OK;
 }
 // The spectrum invariant cost's entries, in the same image: the recipe behind the twenty-one per-agent doubles of cur_lambda
-// (dense_invs_cost.inc: dense_invs_recipe), the argmin record, an agent's record
+// (dense_spectral.inc: DenseCostRecipeT::recipe; either row limit, the indices checked at the engine's n), the argmin record of each
+// row limit, an agent's record
 static const char *invs_other_tier(const azd_engine *e, const char *invx, const char *inv, const char *other) {
     return tier_invx(e->tier) ? invx : tier_inv(e->tier) ? inv : other;
 }
 int azd_engine_dense_invs_argmin_data(azd_engine *e, azd_dense_invs_argmin *out) {
     return dense_argmin_read(e, out, TIER_DENSE_INVS, sizeof(*out), "azd_engine_dense_invs_argmin_data: not an AZD_ENGINE_DENSE_INVS engine");
+}
+int azd_engine_dense_invs_wide_argmin_data(azd_engine *e, azd_dense_invs_wide_argmin *out) {
+    return dense_argmin_read(e, out, TIER_DENSE_INVS_WIDE, sizeof(*out), "azd_engine_dense_invs_wide_argmin_data: not an AZD_ENGINE_DENSE_INVS_WIDE engine");
 }
 int azd_engine_set_dense_invs_recipe(azd_engine *e, const azd_dense_invs_recipe *recipe) {
     if (!e) return AZD_ERR_INVALID_ARGUMENT;

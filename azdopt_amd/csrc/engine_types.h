@@ -225,7 +225,18 @@ struct DenseInvsArgminRec { // device copy of azd_dense_invs_argmin (AZD_ENGINE_
     int32_t agent;
     uint32_t node;
 };
-static_assert(sizeof(DenseInvxWideArgminRec) == 920, "the largest dense argmin record: argmin_d is sized from the tier's argmin_bytes");
+struct DenseInvsWideArgminRec { // device copy of azd_dense_invs_wide_argmin (AZD_ENGINE_DENSE_INVS_WIDE engines: n <= 64, E <= 2016); in argmin_d's place too
+    uint64_t adj[64];
+    uint64_t permitted[32]; // modifiable slots (colex positions) still open
+    double inv[21];
+    int32_t dist_k;
+    uint32_t computed;
+    float cost, eval;
+    int32_t agent;
+    uint32_t node;
+};
+static_assert(sizeof(DenseInvxWideArgminRec) == 920 && sizeof(DenseInvsWideArgminRec) == 960,
+              "the largest dense argmin records: argmin_d is sized from the tier's argmin_bytes");
 
 struct StatusRec { // small device block copied back after every host-visible call
     unsigned long long improved;   // k_argmin calls that improved the argmin

@@ -106,6 +106,7 @@ struct DenseInvCost;
 void launch_probe_inv_cost(const uint64_t *d_adj, int n, int count, int reps, const DenseInvRecipe *d_recipe, DenseInvCost *d_out, void *stream);
 void launch_probe_inv_cost_wide(const uint64_t *d_adj, int n, int count, int reps, const DenseInvRecipe *d_recipe, DenseInvCost *d_out, void *stream); // n <= 64 (dense_inv_wide_kernels.hip)
 const SpaceOps &dense_invs_ops();                               // ... with the spectrum invariant cost (dense_invs_kernels.hip: AZD_ENGINE_DENSE_INVS)
+const SpaceOps &dense_invs_wide_ops();                          // ... with its 64-row form (dense_invs_wide_kernels.hip: AZD_ENGINE_DENSE_INVS_WIDE)
 struct DenseInvxRecipe;
 struct DenseInvxCost;
 void launch_probe_invx_cost(const uint64_t *d_adj, int n, int count, int reps, const DenseInvxRecipe *d_recipe, DenseInvxCost *d_out, void *stream); // (dense_invx_kernels.hip)
@@ -113,6 +114,7 @@ void launch_probe_invx_cost_wide(const uint64_t *d_adj, int n, int count, int re
 struct DenseInvsRecipe;
 struct DenseInvsCost;
 void launch_probe_invs_cost(const uint64_t *d_adj, int n, int count, int reps, const DenseInvsRecipe *d_recipe, DenseInvsCost *d_out, void *stream); // n <= 32 (dense_invs_kernels.hip)
+void launch_probe_invs_cost_wide(const uint64_t *d_adj, int n, int count, int reps, const DenseInvsRecipe *d_recipe, DenseInvsCost *d_out, void *stream); // n <= 64 (dense_invs_wide_kernels.hip)
 
 // ---- the evaluator's side of the searcher-only pool step and the recovery of an aborted launch (dense_kernels.hip; for every space that has the form)
 void launch_ext_take(const PoolArgs &pool, uint32_t *rows, uint32_t *home, uint32_t *n, unsigned long long *t0, void *stream);

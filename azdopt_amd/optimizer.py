@@ -146,7 +146,7 @@ class NablaOptimizer:
         step with the model's batched GEMMs beside it (ENGINE_EXT_POOL_STEP); step_form() says whether it ran.  ext_pool_f32=True
         beside it (ENGINE_EXT_POOL_F32; alone the engine refuses it on c21 and the Ramsey spaces): that form also with an fp32
         ActionModel.  On a DenseGraphSpace, whose pool step IS that form, ext_pool_f32=True stands alone (all seven tiers: default
-        cost, cost="ah", ah_wide=True, cost=InvariantCost(...), inv_wide=True, cost=InvariantCostX(...), invx_wide=True, cost=InvariantCostS(...)): where the engine's configured form is the pool step (256 agents or more, or pool_step=True)
+        cost, cost="ah", ah_wide=True, cost=InvariantCost(...), inv_wide=True, cost=InvariantCostX(...), invx_wide=True; cost=InvariantCostS(...) and invs_wide=True accept it and have no pool step): where the engine's configured form is the pool step (256 agents or more, or pool_step=True)
         an fp32 ActionModel is served by the gathered fp32 GEMMs instead of falling back to one launch per phase -- same
         predictions bit for bit; with persistent=False beside it the engine refuses it.  On an MI355X with a whole epoch per launch:
         AH N = 31 2.6 against 0.82 M expansions/s at 512 agents, 5.5 against 4.7 M at 4096; config E's shape (8192 agents,
@@ -181,6 +181,8 @@ class NablaOptimizer:
                     cfg.flags |= _lib.ENGINE_DENSE_INVX_WIDE
             if getattr(space, "COST", "c21") == "invs":
                 cfg.flags |= _lib.ENGINE_DENSE_INVS
+                if getattr(space, "INVS_WIDE", False):
+                    cfg.flags |= _lib.ENGINE_DENSE_INVS_WIDE
         if space.SPACE_ID == _lib.SPACE_RAMSEY:
             cfg.max_slots = getattr(space, "MAX_SLOTS", 0)
             if getattr(space, "U64", False):
@@ -361,8 +363,12 @@ class NablaOptimizer:
                 _lib.check(self._L.azd_engine_dense_invx_argmin_data(self._h, C.byref(rec)), "dense_invx_argmin_data")
             return DenseInvxArgminData(rec, self.space)
         if self.space.SPACE_ID == _lib.SPACE_DENSE and getattr(self.space, "COST", "c21") == "invs":
-            rec = _lib.DenseInvsArgmin()
-            _lib.check(self._L.azd_engine_dense_invs_argmin_data(self._h, C.byref(rec)), "dense_invs_argmin_data")
+            if getattr(self.space, "INVS_WIDE", False):  # (the 64-row form's record: 64 neighbourhoods, 32 words of open slots)
+                rec = _lib.DenseInvsWideArgmin()
+                _lib.check(self._L.azd_engine_dense_invs_wide_argmin_data(self._h, C.byref(rec)), "dense_invs_wide_argmin_data")
+            else:
+                rec = _lib.DenseInvsArgmin()
+                _lib.check(self._L.azd_engine_dense_invs_argmin_data(self._h, C.byref(rec)), "dense_invs_argmin_data")
             return DenseInvsArgminData(rec, self.space)
         if self.space.SPACE_ID == _lib.SPACE_DENSE:
             rec = _lib.DenseArgmin()

@@ -369,11 +369,13 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
     beside the first flag; never chosen from N), roots of at most min(E, 640) slots; at N <= 32 it gives what the narrow form gives.
     `cost=InvariantCostS(...)`: the spectrum invariant cost (AZD_ENGINE_DENSE_INVS, N <= 32, a tier of its own with the
     InvariantCostX tier's limits): the graph energy, the distance, Laplacian and signless-Laplacian energies and the adjacency spread
-    beside the sixteen.  InvariantCostS.from_invariant_cost_x(c) gives cost=c's trees.  It has no 64-row form."""
+    beside the sixteen.  InvariantCostS.from_invariant_cost_x(c) gives cost=c's trees.  `invs_wide=True` (with an InvariantCostS
+    only): that cost's 64-row form, N <= 64 (AZD_ENGINE_DENSE_INVS_WIDE beside the first flag; never chosen from N), roots of at most
+    min(E, 640) slots; at N <= 32 it gives what the narrow form gives.  Neither form has a pool step."""
 
     SPACE_ID = _lib.SPACE_DENSE
 
-    def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False, inv_wide=False, invx_wide=False):
+    def __init__(self, n, p=0.2, max_slots=128, cost="c21", ah_wide=False, inv_wide=False, invx_wide=False, invs_wide=False):
         self.INV = cost if isinstance(cost, InvariantCost) else None
         self.INVS = cost if isinstance(cost, InvariantCostS) else None
         self.INVX = cost if isinstance(cost, InvariantCostX) and self.INVS is None else None
@@ -391,16 +393,19 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
             raise ValueError("inv_wide=True needs cost=InvariantCost(...) (it is the weighted-invariant cost's 64-row form)")
         if invx_wide and cost != "invx":
             raise ValueError("invx_wide=True needs cost=InvariantCostX(...) (it is the extended invariant cost's 64-row form)")
+        if invs_wide and cost != "invs":
+            raise ValueError("invs_wide=True needs cost=InvariantCostS(...) (it is the spectrum invariant cost's 64-row form)")
         self.COST = cost
         self.AH_WIDE = bool(ah_wide)
         self.INV_WIDE = bool(inv_wide)
         self.INVX_WIDE = bool(invx_wide)
+        self.INVS_WIDE = bool(invs_wide)
         self.n, self.p = int(n), float(p)
         self.E = self.n * (self.n - 1) // 2
         # (an AZD_ENGINE_DENSE_AH engine refuses max_slots > E; a root cannot bring more than E slots anyway)
-        # (... and an AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV_WIDE or AZD_ENGINE_DENSE_INVX_WIDE engine max_slots > min(E, 640): its
-        # keys are 2, 4 or 10 words)
-        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide or inv_wide or invx_wide else min(int(max_slots), self.E) if cost in ("ah", "inv", "invx", "invs") else int(max_slots)
+        # (... and an AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX_WIDE or AZD_ENGINE_DENSE_INVS_WIDE engine
+        # max_slots > min(E, 640): its keys are 2, 4 or 10 words)
+        self.MAX_SLOTS = min(int(max_slots), self.E, 640) if ah_wide or inv_wide or invx_wide or invs_wide else min(int(max_slots), self.E) if cost in ("ah", "inv", "invx", "invs") else int(max_slots)
         L = _lib.lib()
         self.STATE_DIM = L.azd_dense_state_dim(self.n)
         self.ACTION_DIM = L.azd_dense_action_dim(self.n)
@@ -475,23 +480,30 @@ class DenseGraphSpace(ActionsNeverRepeat, ActionOrderIndependent):
         return dict(InvariantCostX.record(out), eval=np.float32(out.eval))
 
     def invs_cost(self, adj, cost=None):
-        """The spectrum invariant cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_invs_cost under this
-        space's recipe (or `cost`, another InvariantCostS), the same procedure as the device's, bit for bit.
+        """The spectrum invariant cost of one connected graph (n neighbourhood bitsets) on the host: azd_dense_invs_cost
+        (azd_dense_invs_cost_wide for an invs_wide space) under this space's recipe (or `cost`, another InvariantCostS), the same
+        procedure as the device's, bit for bit.
         -> dict(the twenty-one invariants by name, dist_k, computed, cost, eval)"""
         cost = self.INVS if cost is None else cost
         if cost is None:
             raise ValueError("invs_cost: the space has no InvariantCostS; pass one")
         a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
         out, r = _lib.DenseInvsCost(), cost.recipe()
-        _lib.check(_lib.lib().azd_dense_invs_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_invs_cost")
+        if getattr(self, "INVS_WIDE", False):
+            _lib.check(_lib.lib().azd_dense_invs_cost_wide(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_invs_cost_wide")
+        else:
+            _lib.check(_lib.lib().azd_dense_invs_cost(_lib.ptr(a), self.n, C.byref(r), C.byref(out)), "azd_dense_invs_cost")
         return dict(InvariantCostS.record(out), eval=np.float32(out.eval))
 
     def invs_spectrum(self, adj, which="adj"):
         """All eigenvalues, ascending, of the graph's adjacency ("adj"), distance ("dist"), Laplacian ("lap") or signless-Laplacian
-        ("slap") matrix by the cost's whole-spectrum procedure on the host (azd_dense_invs_spectrum): what the energies sum."""
+        ("slap") matrix by the cost's whole-spectrum procedure on the host (azd_dense_invs_spectrum; azd_dense_invs_spectrum_wide for an
+        invs_wide space): what the energies sum."""
         a = np.ascontiguousarray(adj, np.uint64).reshape(self.n)
         out = np.zeros(self.n, np.float64)
-        _lib.check(_lib.lib().azd_dense_invs_spectrum(_lib.ptr(a), self.n, ("adj", "dist", "lap", "slap").index(which), _lib.ptr(out)), "azd_dense_invs_spectrum")
+        wide = getattr(self, "INVS_WIDE", False)
+        fn = _lib.lib().azd_dense_invs_spectrum_wide if wide else _lib.lib().azd_dense_invs_spectrum
+        _lib.check(fn(_lib.ptr(a), self.n, ("adj", "dist", "lap", "slap").index(which), _lib.ptr(out)), "azd_dense_invs_spectrum_wide" if wide else "azd_dense_invs_spectrum")
         return out
 
 

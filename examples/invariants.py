@@ -5,10 +5,11 @@ bounded below by ..." -- on the MI355X engine's weighted-invariant cost (AZD_ENG
 form, AZD_ENGINE_DENSE_INV_WIDE, N <= 64, which is asked for by name and never chosen from N; with --extended the extended
 invariant cost, AZD_ENGINE_DENSE_INVX, N <= 32: sixteen invariants and products or quotients of two of them; with both flags that
 cost's 64-row form, AZD_ENGINE_DENSE_INVX_WIDE, N <= 64; with --spectrum the spectrum invariant cost, AZD_ENGINE_DENSE_INVS, N <= 32:
-twenty-one invariants, the graph energies and the adjacency spread among them).
+twenty-one invariants, the graph energies and the adjacency spread among them; with --spectrum --wide that cost's 64-row form,
+AZD_ENGINE_DENSE_INVS_WIDE, N <= 64).
 
     python examples/invariants.py --recipe '{"weights": {"remoteness": 1, "proximity": -1}, "eval_offset": 2, "eval_scale": 0.02}'
-                                  [--n 31] [--wide] [--extended | --spectrum] [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
+                                  [--n 31] [--extended | --spectrum] [--wide] [--epochs 250] [--episodes 800] [--batch 512] [--dtype f32|bf16]
 
 --recipe is a JSON object: "weights" (name -> weight over edges, max_degree, min_degree, diameter, radius, proximity, remoteness,
 avg_distance, adj_eig, dist_eig), and optionally "bias", "adj_index", "dist_index" (a descending index or "ah"), "eval_offset",
@@ -21,7 +22,7 @@ to four [coef, "a", "*" or "/", "b"], e.g. [[1, "remoteness", "/", "radius"]] (a
 zagreb1 or zagreb2).  Without the flag the driver is what it was: the new names are unknown to it.
 --spectrum: everything --extended takes, and "weights" and "terms" may also name adj_energy (the graph energy), dist_energy,
 lap_energy, slap_energy and adj_spread, each a function of a matrix's whole spectrum, e.g.
-'{"weights": {"adj_energy": 1}, "eval_scale": 0.01}'; all five may divide.  There is no 64-row form: --wide is refused beside it.
+'{"weights": {"adj_energy": 1}, "eval_scale": 0.01}'; all five may divide.  With --wide beside it: N <= 64 (neither form has a pool step).
 The loop is par_roll_out_episodes x episodes, par_update_model, par_reset_trees with the device root policy; every improvement of
 the argmin and every epoch print the argmin's invariants."""
 import argparse
@@ -44,7 +45,7 @@ def main():
     ap.add_argument("--n", type=int, default=31)
     ap.add_argument("--wide", action="store_true", help="the cost's 64-row form (N <= 64)")
     ap.add_argument("--extended", action="store_true", help="the extended invariant cost: sixteen invariants, pair terms (N <= 32; N <= 64 with --wide)")
-    ap.add_argument("--spectrum", action="store_true", help="the spectrum invariant cost: twenty-one invariants, energies and spread (N <= 32)")
+    ap.add_argument("--spectrum", action="store_true", help="the spectrum invariant cost: twenty-one invariants, energies and spread (N <= 32; N <= 64 with --wide)")
     ap.add_argument("--epochs", type=int, default=250)
     ap.add_argument("--episodes", type=int, default=800)
     ap.add_argument("--batch", type=int, default=512)
@@ -54,8 +55,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
 
-    if args.spectrum and (args.wide or args.extended):
-        ap.error("--spectrum stands alone: the spectrum invariant cost takes --extended's recipes as they are and has no 64-row form")
+    if args.spectrum and args.extended:
+        ap.error("--spectrum and --extended exclude each other: the spectrum invariant cost takes --extended's recipes as they are")
     cost = az.InvariantCost.aouchiche_hansen(args.n) if args.recipe == "ah" else None
     if args.spectrum:
         cost = az.InvariantCostS.from_invariant_cost(cost) if cost is not None else az.InvariantCostS.from_dict(json.loads(args.recipe))
@@ -63,7 +64,7 @@ def main():
         cost = az.InvariantCostX.from_invariant_cost(cost) if cost is not None else az.InvariantCostX.from_dict(json.loads(args.recipe))
     elif cost is None:
         cost = az.InvariantCost.from_dict(json.loads(args.recipe))
-    wide = dict(invx_wide=True) if args.wide and args.extended else dict(inv_wide=args.wide and not args.spectrum)
+    wide = dict(invs_wide=True) if args.wide and args.spectrum else dict(invx_wide=True) if args.wide and args.extended else dict(inv_wide=args.wide)
     space = az.DenseGraphSpace(args.n, P, max_slots=args.max_slots, cost=cost, **wide)
     model = az.ActionModel(args.batch, space.STATE_DIM, space.ACTION_DIM, hidden=args.hidden, lr=1e-4, l2=1e-6, seed=args.seed,
                            dtype=args.dtype)

@@ -365,12 +365,26 @@ typedef struct azd_engine_config {
  * AZD_ENGINE_DENSE_INVX, in kernels of their own (dense_invs_kernels.hip); asked for by name, never inferred from a recipe.  It has
  * that tier's limits: 4 <= n <= AZD_DENSE_INVS_MAX_N = 32, layers <= 1, max_slots <= E,
  * ActionSet paths (refused with AZD_ERR_INVALID_ARGUMENT naming the argument, as is this flag beside any AZD_ENGINE_DENSE_AH*,
- * AZD_ENGINE_DENSE_INV* or AZD_ENGINE_DENSE_INVX* flag, or on another space).  There is no 64-row form of it and, for now, no pool
+ * AZD_ENGINE_DENSE_INV* or AZD_ENGINE_DENSE_INVX* flag, or on another space).  Its 64-row form is asked for by AZD_ENGINE_DENSE_INVS_WIDE beside it.  There is, for now, no pool
  * step: its engines run one launch per phase at every population; AZD_ENGINE_EXT_POOL_F32 is accepted beside it and changes
  * nothing, and azd_debug_ext_pool_plan is AZD_ERR_UNSUPPORTED for such a configuration.  Such an engine keeps the twenty-one invariants, the distance index used and the `computed` mask per
  * agent: azd_engine_dense_invs_agent_cost, azd_engine_dense_invs_argmin_data.  The INVX, INV, AH and default reads and the INV and
  * INVX setters are AZD_ERR_UNSUPPORTED on it and name the right call, and the INVS calls on an engine of those tiers likewise. */
 #define AZD_ENGINE_DENSE_INVS 16384u
+/* Beside AZD_ENGINE_DENSE_INVS only (alone, beside any AZD_ENGINE_DENSE_AH*, AZD_ENGINE_DENSE_INV* or AZD_ENGINE_DENSE_INVX* flag, or
+ * on another space: AZD_ERR_INVALID_ARGUMENT naming the argument): the spectrum invariant cost up to 64 vertices, the dense-graph
+ * space's own limit -- the device procedure with 64 rows (one packed triangle of 2080 doubles serves the four spectral passes; at
+ * n = 64 every lane of the wave owns an eigenvalue of the whole-spectrum finisher), in kernels of their own
+ * (dense_invs_wide_kernels.hip); the 32-row kernels and every engine without the flag are what they are without it.  Never chosen
+ * from the sizes.  Limits: 4 <= n <= AZD_DENSE_INVS_WIDE_MAX_N, layers <= 1, ActionSet paths, 1 <= max_slots <= min(E, 640) (key
+ * widths 2, 4 and 10; roots of more than 640 slots are out of scope).  A wide engine on n <= 32 is accepted and gives the trees the
+ * narrow engine gives; under an extended-invariant recipe it gives the trees of an AZD_ENGINE_DENSE_INVX_WIDE engine.
+ * azd_engine_set_dense_invs_recipe (indices checked against 0 .. n - 1 at the engine's n) and azd_engine_dense_invs_agent_cost
+ * serve both tiers.  Its argmin record is azd_dense_invs_wide_argmin, read with azd_engine_dense_invs_wide_argmin_data
+ * (azd_engine_dense_invs_argmin_data is AZD_ERR_UNSUPPORTED on it and names that call, and the reverse; the INVX, INV, AH and
+ * default reads likewise).  No pool step, as on the narrow tier: one launch per phase at every population,
+ * AZD_ENGINE_EXT_POOL_F32 is accepted and changes nothing, azd_debug_ext_pool_plan is AZD_ERR_UNSUPPORTED. */
+#define AZD_ENGINE_DENSE_INVS_WIDE 32768u
 /* Beside AZD_ENGINE_RAMSEY_U64 only (alone, on another space or on a 32-bit tier: AZD_ERR_INVALID_ARGUMENT naming both flags): the
  * 64-bit tier with forbidden cliques up to K8 -- clique sizes 2..AZD_RAMSEY_BIG_CLIQUE_MAX, the reference's count_cliques_inside
  * (bitset_graph/mod.rs:164-185) to depth 6 in kernels of their own; the 64-bit tier's kernels and every engine without the flag are
@@ -412,7 +426,7 @@ typedef struct azd_engine_config {
  * 512 agents 0.99 against 0.52 M expansions/s, r45 at 256 agents 1.03 against 0.31 M on the wide tier and 0.79 against 0.25 M on the
  * 64-bit tier.
  * AZD_SPACE_DENSE: the space's pool step is the searcher-only form and needs no flag of its own, so there this flag stands alone, on
- * all eight tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX, AZD_ENGINE_DENSE_INVX_WIDE; AZD_ENGINE_DENSE_INVS accepts the flag but has no pool step); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
+ * all eight tiers (default cost, AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX, AZD_ENGINE_DENSE_INVX_WIDE; AZD_ENGINE_DENSE_INVS, with or without AZD_ENGINE_DENSE_INVS_WIDE, accepts the flag but has no pool step); AZD_ENGINE_EXT_POOL_STEP stays refused there, and
  * this flag beside AZD_ENGINE_NO_PERSISTENT_STEP is AZD_ERR_INVALID_ARGUMENT naming both.  It is a request to the configured pool
  * step, not a form: where the engine's form is not the pool step (fewer than 256 agents without AZD_ENGINE_POOL_STEP) nothing
  * changes and azd_engine_step_form gives the reason it gave.  With it an fp32 MLP is served by the same gathered fp32 GEMMs over the
@@ -1018,6 +1032,8 @@ int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_co
  * no term naming 16 .. 20 the sequence of operations is the extended invariant cost's: inv[0 .. 15], dist_k, computed, cost and
  * eval are azd_dense_invx_cost's bit for bit. */
 #define AZD_DENSE_INVS_MAX_N 32
+/* ... of the 64-row form, which has names of its own: azd_dense_invs_cost_wide, AZD_ENGINE_DENSE_INVS_WIDE */
+#define AZD_DENSE_INVS_WIDE_MAX_N 64
 #define AZD_DENSE_INVS_COUNT 21
 #define AZD_DENSE_INVS_ROUNDS 67
 #define AZD_DENSE_INVS_NAMES AZD_DENSE_INVX_NAMES, "adj_energy", "dist_energy", "lap_energy", "slap_energy", "adj_spread"
@@ -1048,13 +1064,21 @@ typedef struct azd_dense_invs_cost_t {
 /* The cost on the host; needs no GPU.  The graph is checked like azd_dense_invx_cost's, the recipe like
  * azd_engine_set_dense_invs_recipe's: AZD_ERR_INVALID_ARGUMENT naming the argument or field. */
 int azd_dense_invs_cost(const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out);
+/* The same host function for 4 <= n <= AZD_DENSE_INVS_WIDE_MAX_N: the same sequence of IEEE f64 operations, the same graph and
+ * recipe checks (the indices against 0 .. n - 1); at n <= 32 the same bytes as azd_dense_invs_cost. */
+int azd_dense_invs_cost_wide(const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out);
 /* Host only: theta_0 <= .. <= theta_{n-1} of matrix `which` (AZD_DENSE_INVS_MATRIX_*) by the whole-spectrum procedure, n doubles
  * -- what the energies and the spread are summed from, so that each eigenvalue can be checked.  The graph is checked as above. */
 int azd_dense_invs_spectrum(const uint64_t *adj, int n, int which, double *out);
+/* ... for 4 <= n <= AZD_DENSE_INVS_WIDE_MAX_N; at n <= 32 the same bytes */
+int azd_dense_invs_spectrum_wide(const uint64_t *adj, int n, int which, double *out);
 /* The device kernel in isolation, as azd_debug_probe_invx_cost: graphs and recipe are checked before the device is looked for. */
 int azd_debug_probe_invs_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invs_recipe *recipe,
                               azd_dense_invs_cost_t *out, float *ms);
-/* The recipe of an AZD_ENGINE_DENSE_INVS engine: set once, between azd_engine_create and the first par_new (par_new without it is
+/* ... and the 64-row kernel (AZD_ENGINE_DENSE_INVS_WIDE engines' cost), 4 <= n <= AZD_DENSE_INVS_WIDE_MAX_N; checked the same way */
+int azd_debug_probe_invs_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invs_recipe *recipe,
+                                   azd_dense_invs_cost_t *out, float *ms);
+/* The recipe of an AZD_ENGINE_DENSE_INVS engine (with or without AZD_ENGINE_DENSE_INVS_WIDE): set once, between azd_engine_create and the first par_new (par_new without it is
  * refused and names this call; after par_new this call is AZD_ERR_INVALID_ARGUMENT).  AZD_ERR_INVALID_ARGUMENT naming the field,
  * as azd_engine_set_dense_invx_recipe, with a term's a or b in 0 .. 20.  AZD_ERR_UNSUPPORTED on an engine of another tier. */
 int azd_engine_set_dense_invs_recipe(azd_engine *e, const azd_dense_invs_recipe *recipe);
@@ -1071,6 +1095,19 @@ typedef struct azd_dense_invs_argmin {
     uint32_t node;
 } azd_dense_invs_argmin;
 int azd_engine_dense_invs_argmin_data(azd_engine *e, azd_dense_invs_argmin *out);
+/* ArgminData of an engine with AZD_ENGINE_DENSE_INVS_WIDE beside AZD_ENGINE_DENSE_INVS (on any other engine: AZD_ERR_UNSUPPORTED) */
+typedef struct azd_dense_invs_wide_argmin {
+    uint64_t adj[64];
+    uint64_t permitted[32]; /* modifiable slots (colex positions) still open; E <= 2016 */
+    double inv[AZD_DENSE_INVS_COUNT];
+    int32_t dist_k;
+    uint32_t computed;
+    float cost;
+    float eval;
+    int32_t agent;
+    uint32_t node;
+} azd_dense_invs_wide_argmin;
+int azd_engine_dense_invs_wide_argmin_data(azd_engine *e, azd_dense_invs_wide_argmin *out);
 /* the cost record of agent `agent`'s current state as the engine keeps it (cost and eval recomputed from the kept invariants) */
 int azd_engine_dense_invs_agent_cost(azd_engine *e, int agent, azd_dense_invs_cost_t *out);
 /* Parity probe for the f64 primitives the AH cost depends on bit for bit.  in: 2*n doubles (pairs x, y); out: 3*n doubles per

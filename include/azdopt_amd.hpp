@@ -418,30 +418,37 @@ private:
 };
 
 // The same space with the spectrum invariant cost as the objective (AZD_ENGINE_DENSE_INVS): n <= AZD_DENSE_INVS_MAX_N,
-// max_slots <= E; par_new hands the recipe to the engine.  argmin_data() gives a DenseInvsArgmin.  There is no 64-row form.
+// max_slots <= E; par_new hands the recipe to the engine.  argmin_data() gives a DenseInvsArgmin.
+// wide = true: the cost's 64-row form (AZD_ENGINE_DENSE_INVS_WIDE beside the first flag; asked for by name, never chosen from n):
+// n <= AZD_DENSE_INVS_WIDE_MAX_N, max_slots <= min(E, 640); at n <= 32 it gives what the narrow form gives.
 class DenseGraphInvSSpace : public DenseGraphSpace {
 public:
-    DenseGraphInvSSpace(int n, double p, int max_slots, const InvariantCostS &cost) : DenseGraphSpace(n, p, max_slots), cost_(cost) {}
+    DenseGraphInvSSpace(int n, double p, int max_slots, const InvariantCostS &cost, bool wide = false)
+        : DenseGraphSpace(n, p, max_slots), cost_(cost), wide_(wide) {}
     const InvariantCostS &invariant_cost() const { return cost_; }
+    bool wide() const { return wide_; }
     void configure(azd_engine_config &cfg) const {
         DenseGraphSpace::configure(cfg);
-        cfg.flags |= AZD_ENGINE_DENSE_INVS;
+        cfg.flags |= AZD_ENGINE_DENSE_INVS | (wide_ ? AZD_ENGINE_DENSE_INVS_WIDE : 0u);
     }
     // the cost of one connected graph on the host (adj: n neighbourhood bitsets): the device's procedure, bit for bit
     azd_dense_invs_cost_t cost(const uint64_t *adj) const {
         azd_dense_invs_cost_t c;
-        check(azd_dense_invs_cost(adj, n(), &cost_.recipe(), &c), "azd_dense_invs_cost");
+        if (wide_) check(azd_dense_invs_cost_wide(adj, n(), &cost_.recipe(), &c), "azd_dense_invs_cost_wide");
+        else check(azd_dense_invs_cost(adj, n(), &cost_.recipe(), &c), "azd_dense_invs_cost");
         return c;
     }
     // all eigenvalues, ascending, of matrix `which` (AZD_DENSE_INVS_MATRIX_*) by the cost's whole-spectrum procedure
     std::vector<double> spectrum(const uint64_t *adj, int which) const {
         std::vector<double> th((size_t)n());
-        check(azd_dense_invs_spectrum(adj, n(), which, th.data()), "azd_dense_invs_spectrum");
+        if (wide_) check(azd_dense_invs_spectrum_wide(adj, n(), which, th.data()), "azd_dense_invs_spectrum_wide");
+        else check(azd_dense_invs_spectrum(adj, n(), which, th.data()), "azd_dense_invs_spectrum");
         return th;
     }
 
 private:
     InvariantCostS cost_;
+    bool wide_;
 };
 
 // ---------------------------------------------------------------- models (NablaModel, nabla/model/mod.rs:4-8)
@@ -862,8 +869,17 @@ private:
         return dense_invx_argmin_from(a, sp);
     }
     DenseInvsArgmin argmin_of(const DenseGraphInvSSpace &sp) {
+        if (sp.wide()) { // (the 64-row form's record: 64 neighbourhoods, 32 words of open slots)
+            azd_dense_invs_wide_argmin a;
+            check(azd_engine_dense_invs_wide_argmin_data(h_, &a), "argmin_data");
+            return dense_invs_argmin_from(a, sp);
+        }
         azd_dense_invs_argmin a;
         check(azd_engine_dense_invs_argmin_data(h_, &a), "argmin_data");
+        return dense_invs_argmin_from(a, sp);
+    }
+    template <class Rec>
+    static DenseInvsArgmin dense_invs_argmin_from(const Rec &a, const DenseGraphInvSSpace &sp) {
         DenseInvsArgmin r;
         r.adj.assign(a.adj, a.adj + sp.n());
         r.permitted.assign(a.permitted, a.permitted + (sp.E() + 63) / 64);

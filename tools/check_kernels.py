@@ -19,7 +19,7 @@ import tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 SCRATCH_BUDGET = 512  # bytes per lane; the largest today is 504 (k_async<RamseyWideSpace<16>>; of the searcher-only
 # pool step, 464: k_pool_search<RamseyExtSpace<RamseyU64Space>, MODE, 8>)
-TREE_TUS = ("tree_kernels", "async_kernels", "pool_kernels", "ramsey_kernels", "ramsey_async_kernels", "ramsey_pool_kernels", "ramsey64_kernels", "dense_kernels", "dense_ah_kernels", "dense_ah_wide_kernels", "dense_inv_kernels", "dense_inv_wide_kernels", "dense_invx_kernels", "dense_invx_wide_kernels", "dense_invs_kernels",
+TREE_TUS = ("tree_kernels", "async_kernels", "pool_kernels", "ramsey_kernels", "ramsey_async_kernels", "ramsey_pool_kernels", "ramsey64_kernels", "dense_kernels", "dense_ah_kernels", "dense_ah_wide_kernels", "dense_inv_kernels", "dense_inv_wide_kernels", "dense_invx_kernels", "dense_invx_wide_kernels", "dense_invs_kernels", "dense_invs_wide_kernels",
             "ramsey_ext_kernels", "ramsey64_ext_kernels", "ramsey64_big_kernels", "ramsey64_big_ext_kernels")
 
 
