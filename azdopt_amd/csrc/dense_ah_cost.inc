@@ -10,7 +10,7 @@
 //
 // The eigenvalue procedure stands in for faer's (as the power iteration does for lambda_1): Householder reduction of the
 // distance matrix to tridiagonal form in LDS, then a Sturm-count multisection for the ONE eigenvalue wanted -- DENSE_AH_ROUNDS
-// rounds from the Gershgorin radius (dense_spectral.inc).  c21_host.cpp dense_ah_cost_host and tests/dense_ah_ref.py run the same
+// rounds from the Gershgorin radius (dense_spectral.inc).  dense_cost_host.cpp dense_ah_cost_host and tests/dense_ah_ref.py run the same
 // sequence and agree bit for bit.  The reduction does not deflate: distance matrices of connected graphs are what it has always
 // reduced, to these bits.
 //

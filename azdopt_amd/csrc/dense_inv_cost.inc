@@ -1,7 +1,7 @@
 // dense_inv_cost.inc -- the weighted-invariant cost of a connected graph on the device, one wave per graph (included inside
 // namespace azd after tree_core.inc, space_dense.inc and dense_spectral.inc, whose stages it is composed of).
 //
-// BUILD-DEFINED (c21_host.h: DenseInvRecipe; DESIGN.md "The invariant cost"): ten invariants in a fixed order --
+// BUILD-DEFINED (dense_cost_host.h: DenseInvRecipe; DESIGN.md "The invariant cost"): ten invariants in a fixed order --
 //   0 edges  1 max_degree  2 min_degree  3 diameter  4 radius  5 proximity  6 remoteness  7 avg_distance  8 adj_eig  9 dist_eig
 // -- combined with weights the caller gives at RUN time: c = bias, then c = c + weight[i] * I_i for every i whose weight is not
 // zero, in order; cost = (f32)c; eval = eval_scale * (cost + eval_offset).  One build serves a family of objectives of the

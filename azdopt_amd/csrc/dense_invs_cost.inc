@@ -1,7 +1,7 @@
 // dense_invs_cost.inc -- the spectrum invariant cost of a connected graph on the device, one wave per graph (included inside
 // namespace azd after tree_core.inc, space_dense.inc and dense_spectral.inc, whose stages it is composed of).
 //
-// BUILD-DEFINED (c21_host.h: DenseInvsRecipe; DESIGN.md "The spectrum invariant cost"): twenty-one invariants in a fixed order --
+// BUILD-DEFINED (dense_cost_host.h: DenseInvsRecipe; DESIGN.md "The spectrum invariant cost"): twenty-one invariants in a fixed order --
 //   0 .. 15 the extended invariant cost's (dense_invx_cost.inc)
 //   16 adj_energy  17 dist_energy  18 lap_energy  19 slap_energy  20 adj_spread
 // -- combined by a recipe the caller gives at RUN time, by the extended cost's rule over twenty-one weights and up to four pair

@@ -1,7 +1,7 @@
 // dense_invx_cost.inc -- the extended invariant cost of a connected graph on the device, one wave per graph (included inside
 // namespace azd after tree_core.inc, space_dense.inc and dense_spectral.inc, whose stages it is composed of).
 //
-// BUILD-DEFINED (c21_host.h: DenseInvxRecipe; DESIGN.md "The extended invariant cost"): sixteen invariants in a fixed order --
+// BUILD-DEFINED (dense_cost_host.h: DenseInvxRecipe; DESIGN.md "The extended invariant cost"): sixteen invariants in a fixed order --
 //   0 edges  1 max_degree  2 min_degree  3 diameter  4 radius  5 proximity  6 remoteness  7 avg_distance  8 adj_eig  9 dist_eig
 //   10 lap_eig  11 slap_eig  12 randic  13 zagreb1  14 zagreb2  15 triangles
 // -- combined by a recipe the caller gives at RUN time: c = bias, then c = c + weight[i] * I_i for every i whose weight is not zero,

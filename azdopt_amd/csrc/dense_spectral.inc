@@ -13,7 +13,7 @@
 //
 // ONE text of each: a numerical fix is made here once and reaches every tier.  What holds a tier's device code in place is not
 // the machine code it compiled to before but its bits: every device cost is pinned, as bytes, to its host function
-// (c21_host.cpp: ah_bfs, ah_householder, ah_sturm, ah_multisection share these stages the same way) by the GPU suite, and the
+// (dense_cost_host.cpp: ah_bfs, ah_householder, ah_sturm, ah_multisection share these stages the same way) by the GPU suite, and the
 // host functions to the Python references.  So every f64 step here is one IEEE operation (-ffp-contract=off; f64 division and
 // sqrt are correctly rounded on gfx950) in the order the host runs it, and every reduction an xor-butterfly = a balanced binary
 // tree.  Everything is __forceinline__ (tools/check_kernels.py: no device function out of line in a tree unit) and takes the
@@ -120,7 +120,7 @@ __device__ __forceinline__ void dense_refill_wave(const uint64_t *adj, DenseAhLd
 // ---- Householder reduction: step i clears column i below row i + 1; lane i keeps (diag_i, sub_i), which end in w.diag / w.sub2
 // (the subdiagonal squared).  Returns the Gershgorin radius of the tridiagonal form, wave-uniform.
 // A step whose column tail is zero is skipped: the column is tridiagonal already (adjacency and Laplacian matrices: often).  With
-// DEFLATE one whose tail is below DENSE_INV_DEFLATE is skipped too, at every n and either row limit (c21_host.h: the tail is
+// DEFLATE one whose tail is below DENSE_INV_DEFLATE is skipped too, at every n and either row limit (dense_cost_host.h: the tail is
 // rounding noise of a matrix whose rank is used up; a rank-deficient adjacency matrix otherwise runs the reduction into subnormal
 // squares and NaN -- after some 20 steps on K(10,11) or a double broom with the heavier end first; from 19 vertices on).  The
 // Aouchiche-Hansen cost reduces distance matrices alone and does not deflate.
@@ -241,7 +241,7 @@ __device__ __forceinline__ void dense_degree_sums_wave(const uint64_t *adj, cons
             const double s = sqrt((double)(deg * dv));
             const double term = 1.0 / s;
             // TwoSum (Knuth): t + e == r + term exactly.  Uncompensated, K_27's 351 equal terms round the same way 351 times
-            // and the sum leaves the n 2^-52 the invariant is held to (c21_host.h)
+            // and the sum leaves the n 2^-52 the invariant is held to (dense_cost_host.h)
             const double t = r + term;
             const double bp = t - r;
             const double ap = t - bp;

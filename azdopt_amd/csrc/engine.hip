@@ -111,23 +111,23 @@ static const TierDesc *tier_desc(Tier t) {
          nullptr, nullptr},
         // AZD_ENGINE_DENSE_INV: the weighted-invariant cost (dense_inv_kernels.hip): ten doubles and two ints per agent, the recipe behind the doubles
         {TIER_DENSE_INV, SPACE_DENSE, &dense_inv_ops(), xd, sizeof(DenseInvArgminRec), 0, false, true, false, DENSE_INV_COUNT, 2,
-         (int)((sizeof(DenseInvRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+         (int)((sizeof(DenseInvRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr, &dense_family(DENSE_FAMILY_INV), false},
         // AZD_ENGINE_DENSE_INV_WIDE beside it: the same record per agent over the 64-row kernels (dense_inv_wide_kernels.hip)
         {TIER_DENSE_INV_WIDE, SPACE_DENSE, &dense_inv_wide_ops(), xd, sizeof(DenseInvWideArgminRec), 0, false, true, false, DENSE_INV_COUNT, 2,
-         (int)((sizeof(DenseInvRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+         (int)((sizeof(DenseInvRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr, &dense_family(DENSE_FAMILY_INV), true},
         // AZD_ENGINE_DENSE_INVX: the extended invariant cost (dense_invx_kernels.hip): sixteen doubles and two ints per agent, the recipe behind the doubles
         {TIER_DENSE_INVX, SPACE_DENSE, &dense_invx_ops(), xd, sizeof(DenseInvxArgminRec), 0, false, true, false, DENSE_INVX_COUNT, 2,
-         (int)((sizeof(DenseInvxRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+         (int)((sizeof(DenseInvxRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr, &dense_family(DENSE_FAMILY_INVX), false},
         // AZD_ENGINE_DENSE_INVX_WIDE beside it: the same record per agent over the 64-row kernels (dense_invx_wide_kernels.hip)
         {TIER_DENSE_INVX_WIDE, SPACE_DENSE, &dense_invx_wide_ops(), xd, sizeof(DenseInvxWideArgminRec), 0, false, true, false, DENSE_INVX_COUNT, 2,
-         (int)((sizeof(DenseInvxRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+         (int)((sizeof(DenseInvxRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr, &dense_family(DENSE_FAMILY_INVX), true},
         // AZD_ENGINE_DENSE_INVS: the spectrum invariant cost (dense_invs_kernels.hip): twenty-one doubles and two ints per agent, the recipe behind the doubles
         // (no searcher-only pool step on this tier yet: ext is null, so its engines run one launch per phase at every population)
         {TIER_DENSE_INVS, SPACE_DENSE, &dense_invs_ops(), nullptr, sizeof(DenseInvsArgminRec), 0, false, true, false, DENSE_INVS_COUNT, 2,
-         (int)((sizeof(DenseInvsRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+         (int)((sizeof(DenseInvsRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr, &dense_family(DENSE_FAMILY_INVS), false},
         // AZD_ENGINE_DENSE_INVS_WIDE beside it: the same record per agent over the 64-row kernels (dense_invs_wide_kernels.hip); no pool step either
         {TIER_DENSE_INVS_WIDE, SPACE_DENSE, &dense_invs_wide_ops(), nullptr, sizeof(DenseInvsWideArgminRec), 0, false, true, false, DENSE_INVS_COUNT, 2,
-         (int)((sizeof(DenseInvsRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr},
+         (int)((sizeof(DenseInvsRecipe) + 7) / 8), 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, nullptr, &dense_family(DENSE_FAMILY_INVS), true},
     };
     return &tiers[t];
 }
@@ -426,6 +426,75 @@ static int check_ramsey_config(const azd_engine_config *cfg, const TierDesc &t) 
     if (cfg->layers > 1 || cfg->path_kind != AZD_PATH_SET) return refuse(t.e_paths);
     return AZD_OK;
 }
+// ... of a dense-graph configuration's cost flags: each cost is asked for by name, never chosen from the sizes, and a _WIDE flag is
+// a second flag beside its cost's, never a cost of its own.  One row per flag, in the order of precedence; the first flag set is checked.
+struct DenseCostFlag {
+    uint32_t flag, base, excludes; // base: the flag a _WIDE flag must stand beside (0: a cost's own flag); excludes: flags of other costs
+    const char *name;
+    int max_n;
+    bool cap_640, needs_slot; // max_slots <= min(E, 640), not E; max_slots >= 1
+    const char *e_base, *e_excludes, *e_n;
+};
+static int check_dense_cost_flags(const azd_engine_config *cfg) {
+    constexpr uint32_t AH = AZD_ENGINE_DENSE_AH | AZD_ENGINE_DENSE_AH_WIDE, INV = AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE,
+                       INVX = AZD_ENGINE_DENSE_INVX | AZD_ENGINE_DENSE_INVX_WIDE;
+    static const DenseCostFlag rows[] = {
+        {AZD_ENGINE_DENSE_INVS_WIDE, AZD_ENGINE_DENSE_INVS, AH | INV | INVX, "AZD_ENGINE_DENSE_INVS_WIDE", AZD_DENSE_INVS_WIDE_MAX_N, true, true,
+         "flags: AZD_ENGINE_DENSE_INVS_WIDE is valid only beside AZD_ENGINE_DENSE_INVS (the spectrum invariant cost whose 64-row form it asks for)",
+         "flags: AZD_ENGINE_DENSE_INVS_WIDE belongs to a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
+         "AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX or AZD_ENGINE_DENSE_INVX_WIDE (the Aouchiche-Hansen cost, the "
+         "weighted-invariant cost and the extended invariant cost are among its recipes)",
+         "n: the wide spectrum invariant cost needs 4 <= n <= 64 (AZD_DENSE_INVS_WIDE_MAX_N)"},
+        {AZD_ENGINE_DENSE_INVS, 0, AH | INV | INVX, "AZD_ENGINE_DENSE_INVS", AZD_DENSE_INVS_MAX_N, false, false, nullptr,
+         "flags: AZD_ENGINE_DENSE_INVS is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
+         "AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX or AZD_ENGINE_DENSE_INVX_WIDE (the Aouchiche-Hansen cost, the "
+         "weighted-invariant cost and the extended invariant cost are among its recipes)",
+         "n: the spectrum invariant cost needs 4 <= n <= 32 (AZD_DENSE_INVS_MAX_N)"},
+        {AZD_ENGINE_DENSE_INVX_WIDE, AZD_ENGINE_DENSE_INVX, AH | INV, "AZD_ENGINE_DENSE_INVX_WIDE", AZD_DENSE_INVX_WIDE_MAX_N, true, true,
+         "flags: AZD_ENGINE_DENSE_INVX_WIDE is valid only beside AZD_ENGINE_DENSE_INVX (the extended invariant cost whose 64-row form it asks for)",
+         "flags: AZD_ENGINE_DENSE_INVX_WIDE belongs to a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
+         "AZD_ENGINE_DENSE_INV or AZD_ENGINE_DENSE_INV_WIDE (the Aouchiche-Hansen cost and the weighted-invariant cost are among its recipes)",
+         "n: the wide extended invariant cost needs 4 <= n <= 64 (AZD_DENSE_INVX_WIDE_MAX_N)"},
+        {AZD_ENGINE_DENSE_INVX, 0, AH | INV, "AZD_ENGINE_DENSE_INVX", AZD_DENSE_INVX_MAX_N, false, false, nullptr,
+         "flags: AZD_ENGINE_DENSE_INVX is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
+         "AZD_ENGINE_DENSE_INV or AZD_ENGINE_DENSE_INV_WIDE (the Aouchiche-Hansen cost and the weighted-invariant cost are among its recipes)",
+         "n: the extended invariant cost needs 4 <= n <= 32 (AZD_DENSE_INVX_MAX_N)"},
+        {AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INV, AH, "AZD_ENGINE_DENSE_INV_WIDE", AZD_DENSE_INV_WIDE_MAX_N, true, true,
+         "flags: AZD_ENGINE_DENSE_INV_WIDE is valid only beside AZD_ENGINE_DENSE_INV (the weighted-invariant cost whose 64-row form it asks for)",
+         "flags: AZD_ENGINE_DENSE_INV_WIDE belongs to a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH or AZD_ENGINE_DENSE_AH_WIDE "
+         "(the Aouchiche-Hansen cost is one of its recipes)",
+         "n: the wide weighted-invariant cost needs 4 <= n <= 64 (AZD_DENSE_INV_WIDE_MAX_N)"},
+        {AZD_ENGINE_DENSE_INV, 0, AH, "AZD_ENGINE_DENSE_INV", AZD_DENSE_INV_MAX_N, false, false, nullptr,
+         "flags: AZD_ENGINE_DENSE_INV is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH or AZD_ENGINE_DENSE_AH_WIDE "
+         "(the Aouchiche-Hansen cost is one of its recipes)",
+         "n: the weighted-invariant cost needs 4 <= n <= 32 (AZD_DENSE_INV_MAX_N)"},
+        // (the one 64-row tier whose max_slots has no lower bound)
+        {AZD_ENGINE_DENSE_AH_WIDE, AZD_ENGINE_DENSE_AH, 0, "AZD_ENGINE_DENSE_AH_WIDE", AZD_DENSE_AH_WIDE_MAX_N, true, false,
+         "flags: AZD_ENGINE_DENSE_AH_WIDE is valid only beside AZD_ENGINE_DENSE_AH (the Aouchiche-Hansen cost whose 64-row form it asks for)", nullptr,
+         "n: the wide Aouchiche-Hansen cost needs 4 <= n <= 64 (AZD_DENSE_AH_WIDE_MAX_N)"},
+        {AZD_ENGINE_DENSE_AH, 0, 0, "AZD_ENGINE_DENSE_AH", AZD_DENSE_AH_MAX_N, false, false, nullptr, nullptr,
+         "n: the Aouchiche-Hansen cost needs 4 <= n <= 32 (AZD_DENSE_AH_MAX_N)"},
+    };
+    for (const DenseCostFlag &r : rows) {
+        if (!(cfg->flags & r.flag)) continue;
+        const std::string name = r.name;
+        if (r.base && !(cfg->flags & r.base)) return refuse(r.e_base);
+        if (cfg->flags & r.excludes) return refuse(r.e_excludes);
+        if (cfg->space_id != AZD_SPACE_DENSE) return refuse(("space_id: " + name + " needs the dense-graph space (AZD_SPACE_DENSE)").c_str());
+        if (cfg->n < 4 || cfg->n > r.max_n) return refuse(r.e_n);
+        if (cfg->layers > 1) return refuse(("layers: " + name + " engines take no Layered wrapper (layers <= 1)").c_str());
+        const bool bad_path = cfg->path_kind != AZD_PATH_SET;
+        const bool bad_slots = (r.needs_slot && cfg->max_slots < 1) || cfg->max_slots > (r.cap_640 ? std::min(dense_edges(cfg->n), 640) : dense_edges(cfg->n));
+        // (a cost's own flag says max_slots before path_kind, a _WIDE flag path_kind before max_slots)
+        if (bad_path && (r.base || !bad_slots)) return refuse(("path_kind: " + name + " engines keep ActionSet paths (AZD_PATH_SET)").c_str());
+        if (bad_slots)
+            return refuse(("max_slots: " + name + " needs " + (r.needs_slot ? "1 <= " : "") + "max_slots <= " +
+                           (r.cap_640 ? "min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)" : "E = n (n - 1) / 2"))
+                              .c_str());
+        return AZD_OK;
+    }
+    return AZD_OK;
+}
 int check_engine_config(const azd_engine_config *cfg) {
     const bool ramsey = cfg->space_id == AZD_SPACE_RAMSEY;
     const bool dense = cfg->space_id == AZD_SPACE_DENSE;
@@ -433,103 +502,7 @@ int check_engine_config(const azd_engine_config *cfg) {
     if ((cfg->flags & AZD_ENGINE_RAMSEY_BIG_CLIQUES) && (!ramsey || !(cfg->flags & AZD_ENGINE_RAMSEY_U64)))
         return refuse("flags: AZD_ENGINE_RAMSEY_BIG_CLIQUES is valid only beside AZD_ENGINE_RAMSEY_U64 (the 64-bit tier of the Ramsey space, "
                       "AZD_SPACE_RAMSEY with max_slots > 0, whose kernels for clique sizes up to 8 it asks for)");
-    const bool dense_ah = (cfg->flags & AZD_ENGINE_DENSE_AH) != 0; // the Aouchiche-Hansen cost: asked for by name, never chosen from the sizes
-    const bool dense_ah_wide = (cfg->flags & AZD_ENGINE_DENSE_AH_WIDE) != 0; // its 64-row form: a second flag beside the first, never a cost of its own
-    if (cfg->flags & AZD_ENGINE_DENSE_INVS_WIDE) { // the spectrum invariant cost's 64-row form: a second flag beside the first, never a cost of its own
-        const char *bad = !(cfg->flags & AZD_ENGINE_DENSE_INVS)
-                              ? "flags: AZD_ENGINE_DENSE_INVS_WIDE is valid only beside AZD_ENGINE_DENSE_INVS (the spectrum invariant cost whose 64-row form it asks for)"
-                          : dense_ah || dense_ah_wide || (cfg->flags & (AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE | AZD_ENGINE_DENSE_INVX | AZD_ENGINE_DENSE_INVX_WIDE))
-                              ? "flags: AZD_ENGINE_DENSE_INVS_WIDE belongs to a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
-                                "AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX or AZD_ENGINE_DENSE_INVX_WIDE (the Aouchiche-Hansen cost, the "
-                                "weighted-invariant cost and the extended invariant cost are among its recipes)"
-                          : !dense ? "space_id: AZD_ENGINE_DENSE_INVS_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_INVS_WIDE_MAX_N ? "n: the wide spectrum invariant cost needs 4 <= n <= 64 (AZD_DENSE_INVS_WIDE_MAX_N)"
-                          : cfg->layers > 1 ? "layers: AZD_ENGINE_DENSE_INVS_WIDE engines take no Layered wrapper (layers <= 1)"
-                          : cfg->path_kind != AZD_PATH_SET ? "path_kind: AZD_ENGINE_DENSE_INVS_WIDE engines keep ActionSet paths (AZD_PATH_SET)"
-                          : cfg->max_slots < 1 || cfg->max_slots > std::min(dense_edges(cfg->n), 640)
-                              ? "max_slots: AZD_ENGINE_DENSE_INVS_WIDE needs 1 <= max_slots <= min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)"
-                              : nullptr;
-        if (bad) return refuse(bad);
-    } else if (cfg->flags & AZD_ENGINE_DENSE_INVS) { // the spectrum invariant cost: a tier of its own, asked for by name; the INVX tier's limits
-        const char *bad = dense_ah || dense_ah_wide || (cfg->flags & (AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE | AZD_ENGINE_DENSE_INVX | AZD_ENGINE_DENSE_INVX_WIDE))
-                              ? "flags: AZD_ENGINE_DENSE_INVS is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
-                                "AZD_ENGINE_DENSE_INV, AZD_ENGINE_DENSE_INV_WIDE, AZD_ENGINE_DENSE_INVX or AZD_ENGINE_DENSE_INVX_WIDE (the Aouchiche-Hansen cost, the "
-                                "weighted-invariant cost and the extended invariant cost are among its recipes)"
-                          : !dense                                       ? "space_id: AZD_ENGINE_DENSE_INVS needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_INVS_MAX_N  ? "n: the spectrum invariant cost needs 4 <= n <= 32 (AZD_DENSE_INVS_MAX_N)"
-                          : cfg->layers > 1                              ? "layers: AZD_ENGINE_DENSE_INVS engines take no Layered wrapper (layers <= 1)"
-                          : cfg->max_slots > dense_edges(cfg->n)         ? "max_slots: AZD_ENGINE_DENSE_INVS needs max_slots <= E = n (n - 1) / 2"
-                          : cfg->path_kind != AZD_PATH_SET               ? "path_kind: AZD_ENGINE_DENSE_INVS engines keep ActionSet paths (AZD_PATH_SET)"
-                                                                         : nullptr;
-        if (bad) return refuse(bad);
-    } else if (cfg->flags & AZD_ENGINE_DENSE_INVX_WIDE) { // the extended invariant cost's 64-row form: a second flag beside the first, never a cost of its own
-        const char *bad = !(cfg->flags & AZD_ENGINE_DENSE_INVX)
-                              ? "flags: AZD_ENGINE_DENSE_INVX_WIDE is valid only beside AZD_ENGINE_DENSE_INVX (the extended invariant cost whose 64-row form it asks for)"
-                          : dense_ah || dense_ah_wide || (cfg->flags & (AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE))
-                              ? "flags: AZD_ENGINE_DENSE_INVX_WIDE belongs to a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
-                                "AZD_ENGINE_DENSE_INV or AZD_ENGINE_DENSE_INV_WIDE (the Aouchiche-Hansen cost and the weighted-invariant cost are among its recipes)"
-                          : !dense ? "space_id: AZD_ENGINE_DENSE_INVX_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_INVX_WIDE_MAX_N ? "n: the wide extended invariant cost needs 4 <= n <= 64 (AZD_DENSE_INVX_WIDE_MAX_N)"
-                          : cfg->layers > 1 ? "layers: AZD_ENGINE_DENSE_INVX_WIDE engines take no Layered wrapper (layers <= 1)"
-                          : cfg->path_kind != AZD_PATH_SET ? "path_kind: AZD_ENGINE_DENSE_INVX_WIDE engines keep ActionSet paths (AZD_PATH_SET)"
-                          : cfg->max_slots < 1 || cfg->max_slots > std::min(dense_edges(cfg->n), 640)
-                              ? "max_slots: AZD_ENGINE_DENSE_INVX_WIDE needs 1 <= max_slots <= min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)"
-                              : nullptr;
-        if (bad) return refuse(bad);
-    } else if (cfg->flags & AZD_ENGINE_DENSE_INVX) { // the extended invariant cost: a tier of its own, asked for by name; the INV tier's limits
-        const char *bad = dense_ah || dense_ah_wide || (cfg->flags & (AZD_ENGINE_DENSE_INV | AZD_ENGINE_DENSE_INV_WIDE))
-                              ? "flags: AZD_ENGINE_DENSE_INVX is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH, AZD_ENGINE_DENSE_AH_WIDE, "
-                                "AZD_ENGINE_DENSE_INV or AZD_ENGINE_DENSE_INV_WIDE (the Aouchiche-Hansen cost and the weighted-invariant cost are among its recipes)"
-                          : !dense                                       ? "space_id: AZD_ENGINE_DENSE_INVX needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_INVX_MAX_N  ? "n: the extended invariant cost needs 4 <= n <= 32 (AZD_DENSE_INVX_MAX_N)"
-                          : cfg->layers > 1                              ? "layers: AZD_ENGINE_DENSE_INVX engines take no Layered wrapper (layers <= 1)"
-                          : cfg->max_slots > dense_edges(cfg->n)         ? "max_slots: AZD_ENGINE_DENSE_INVX needs max_slots <= E = n (n - 1) / 2"
-                          : cfg->path_kind != AZD_PATH_SET               ? "path_kind: AZD_ENGINE_DENSE_INVX engines keep ActionSet paths (AZD_PATH_SET)"
-                                                                         : nullptr;
-        if (bad) return refuse(bad);
-    } else if (cfg->flags & AZD_ENGINE_DENSE_INV_WIDE) { // the weighted-invariant cost's 64-row form: a second flag beside the first, never a cost of its own
-        const char *bad = !(cfg->flags & AZD_ENGINE_DENSE_INV)
-                              ? "flags: AZD_ENGINE_DENSE_INV_WIDE is valid only beside AZD_ENGINE_DENSE_INV (the weighted-invariant cost whose 64-row form it asks for)"
-                          : dense_ah || dense_ah_wide
-                              ? "flags: AZD_ENGINE_DENSE_INV_WIDE belongs to a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH or AZD_ENGINE_DENSE_AH_WIDE "
-                                "(the Aouchiche-Hansen cost is one of its recipes)"
-                          : !dense ? "space_id: AZD_ENGINE_DENSE_INV_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_INV_WIDE_MAX_N ? "n: the wide weighted-invariant cost needs 4 <= n <= 64 (AZD_DENSE_INV_WIDE_MAX_N)"
-                          : cfg->layers > 1 ? "layers: AZD_ENGINE_DENSE_INV_WIDE engines take no Layered wrapper (layers <= 1)"
-                          : cfg->path_kind != AZD_PATH_SET ? "path_kind: AZD_ENGINE_DENSE_INV_WIDE engines keep ActionSet paths (AZD_PATH_SET)"
-                          : cfg->max_slots < 1 || cfg->max_slots > std::min(dense_edges(cfg->n), 640)
-                              ? "max_slots: AZD_ENGINE_DENSE_INV_WIDE needs 1 <= max_slots <= min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)"
-                              : nullptr;
-        if (bad) return refuse(bad);
-    } else if (cfg->flags & AZD_ENGINE_DENSE_INV) { // the weighted-invariant cost: a tier of its own, asked for by name; the AH tier's limits
-        const char *bad = dense_ah || dense_ah_wide ? "flags: AZD_ENGINE_DENSE_INV is a cost of its own: it cannot be combined with AZD_ENGINE_DENSE_AH or AZD_ENGINE_DENSE_AH_WIDE "
-                                                      "(the Aouchiche-Hansen cost is one of its recipes)"
-                          : !dense                                       ? "space_id: AZD_ENGINE_DENSE_INV needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_INV_MAX_N   ? "n: the weighted-invariant cost needs 4 <= n <= 32 (AZD_DENSE_INV_MAX_N)"
-                          : cfg->layers > 1                              ? "layers: AZD_ENGINE_DENSE_INV engines take no Layered wrapper (layers <= 1)"
-                          : cfg->max_slots > dense_edges(cfg->n)         ? "max_slots: AZD_ENGINE_DENSE_INV needs max_slots <= E = n (n - 1) / 2"
-                          : cfg->path_kind != AZD_PATH_SET               ? "path_kind: AZD_ENGINE_DENSE_INV engines keep ActionSet paths (AZD_PATH_SET)"
-                                                                         : nullptr;
-        if (bad) return refuse(bad);
-    } else if (dense_ah_wide) {
-        const char *bad = !dense_ah ? "flags: AZD_ENGINE_DENSE_AH_WIDE is valid only beside AZD_ENGINE_DENSE_AH (the Aouchiche-Hansen cost whose 64-row form it asks for)"
-                          : !dense  ? "space_id: AZD_ENGINE_DENSE_AH_WIDE needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_AH_WIDE_MAX_N ? "n: the wide Aouchiche-Hansen cost needs 4 <= n <= 64 (AZD_DENSE_AH_WIDE_MAX_N)"
-                          : cfg->layers > 1 ? "layers: AZD_ENGINE_DENSE_AH_WIDE engines take no Layered wrapper (layers <= 1)"
-                          : cfg->path_kind != AZD_PATH_SET ? "path_kind: AZD_ENGINE_DENSE_AH_WIDE engines keep ActionSet paths (AZD_PATH_SET)"
-                          : cfg->max_slots > std::min(dense_edges(cfg->n), 640)
-                              ? "max_slots: AZD_ENGINE_DENSE_AH_WIDE needs max_slots <= min(E, 640), E = n (n - 1) / 2 (key widths 2, 4 and 10)"
-                              : nullptr;
-        if (bad) return refuse(bad);
-    } else if (dense_ah) {
-        const char *bad = !dense                                                  ? "space_id: AZD_ENGINE_DENSE_AH needs the dense-graph space (AZD_SPACE_DENSE)"
-                          : cfg->n < 4 || cfg->n > AZD_DENSE_AH_MAX_N             ? "n: the Aouchiche-Hansen cost needs 4 <= n <= 32 (AZD_DENSE_AH_MAX_N)"
-                          : cfg->layers > 1                                       ? "layers: AZD_ENGINE_DENSE_AH engines take no Layered wrapper (layers <= 1)"
-                          : cfg->max_slots > dense_edges(cfg->n)                  ? "max_slots: AZD_ENGINE_DENSE_AH needs max_slots <= E = n (n - 1) / 2"
-                          : cfg->path_kind != AZD_PATH_SET                        ? "path_kind: AZD_ENGINE_DENSE_AH engines keep ActionSet paths (AZD_PATH_SET)"
-                                                                                  : nullptr;
-        if (bad) return refuse(bad);
-    }
+    AZD_ST(check_dense_cost_flags(cfg));
     if (dense) {
         if (cfg->n < 4 || cfg->n > AZD_DENSE_MAX_N || cfg->batch <= 0 || cfg->layers > 1 || cfg->max_slots < 0 || cfg->max_slots > AZD_DENSE_MAX_SLOTS ||
             !(cfg->dense_p >= 0.f && cfg->dense_p <= 1.f))
@@ -978,16 +951,9 @@ int azd_engine_destroy(azd_engine *e) {
 // optimizer/mod.rs:61-70
 int azd_engine_par_new_begin(azd_engine *e, const uint8_t *parents, const uint64_t *permitted) {
     if (!e || !parents || !permitted) return AZD_ERR_INVALID_ARGUMENT;
-    if (tier_inv(e->tier) && !e->inv_recipe_set) {
-        azd::g_last_error = "par_new: an AZD_ENGINE_DENSE_INV engine has no cost before azd_engine_set_dense_inv_recipe has given it its recipe";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (tier_invs(e->tier) && !e->inv_recipe_set) {
-        azd::g_last_error = "par_new: an AZD_ENGINE_DENSE_INVS engine has no cost before azd_engine_set_dense_invs_recipe has given it its recipe";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (tier_invx(e->tier) && !e->inv_recipe_set) {
-        azd::g_last_error = "par_new: an AZD_ENGINE_DENSE_INVX engine has no cost before azd_engine_set_dense_invx_recipe has given it its recipe";
+    if (e->tier->family && !e->inv_recipe_set) {
+        const azd::DenseFamilyDesc &f = *e->tier->family;
+        azd::g_last_error = std::string("par_new: an ") + f.flag[0] + " engine has no cost before " + f.setter + " has given it its recipe";
         return AZD_ERR_INVALID_ARGUMENT;
     }
     AZD_ENTER(e);

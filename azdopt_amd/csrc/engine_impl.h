@@ -56,14 +56,11 @@ struct TierDesc {
     int max_clique;             // the largest forbidden clique its kernels count
     bool clique_overflow_rule;  // sizes above 5: every colour must pass RamseyCounts::new's i32 bound, C(s,2) * C(n,s) <= 2^31 - 1
     const char *e_range, *e_slots, *e_node_actions, *e_paths;
+    // dense-graph space, the three recipe costs (dense_cost_host.h): which of them the tier runs, at which row limit.  The recipe, its
+    // setter and the per-agent record are the same at both limits.  null: the tier takes no recipe
+    const azd::DenseFamilyDesc *family;
+    bool wide;
 };
-
-// the weighted-invariant cost at either row limit: the recipe, its setter and the per-agent record are the same on both tiers
-inline bool tier_inv(const TierDesc *t) { return t->id == TIER_DENSE_INV || t->id == TIER_DENSE_INV_WIDE; }
-// ... and the extended invariant cost at either row limit, likewise
-inline bool tier_invx(const TierDesc *t) { return t->id == TIER_DENSE_INVX || t->id == TIER_DENSE_INVX_WIDE; }
-// ... and the spectrum invariant cost, which has one row limit
-inline bool tier_invs(const TierDesc *t) { return t->id == TIER_DENSE_INVS || t->id == TIER_DENSE_INVS_WIDE; }
 
 // The evaluator groups' device memory (PoolArgs::grp_*): the two tables of the plan, and the per-slot exchange state, regrown as a
 // whole when the plan needs more of any of it.
@@ -98,10 +95,8 @@ struct azd_engine {
     azd::Arenas a;
     const azd::SpaceOps *ops = nullptr; // the launchers and LDS plans of the engine's space and tier (space_ops.h)
     const TierDesc *tier = nullptr;     // which of the fourteen kinds of engine this is (engine_tier)
-    bool inv_recipe_set = false;        // AZD_ENGINE_DENSE_INV: azd_engine_set_dense_inv_recipe has run (par_new refuses before it) ...
-    azd::DenseInvRecipe inv_recipe{};   // ... the recipe as set (the device's copy lies behind cur_lambda's per-agent part)
-    azd::DenseInvxRecipe invx_recipe{}; // ... (AZD_ENGINE_DENSE_INVX: azd_engine_set_dense_invx_recipe's, kept the same way under the same two flags)
-    azd::DenseInvsRecipe invs_recipe{}; // ... (AZD_ENGINE_DENSE_INVS: azd_engine_set_dense_invs_recipe's, likewise)
+    bool inv_recipe_set = false;        // a recipe tier (TierDesc::family): the family's setter has run (par_new refuses before it) ...
+    azd::DenseInvsRecipe inv_recipe{};  // ... the recipe as set, widened (the device's copy, the caller's bytes, lies behind cur_lambda's per-agent part)
     bool inv_recipe_locked = false;     // ... and par_new has computed the roots' evals with it (the setter refuses from then on)
     azd_evaluator *ev = nullptr;
     azd::Stream stream;

@@ -40,6 +40,43 @@ static int probe_dense_cost(const char *name, const char *tag, int device, const
     if (ms) *ms = t;
     return AZD_OK;
 }
+// The three recipe costs (dense_cost_host.h: DenseFamily) behind one set of entries; the ABI's structs mirror the host's.
+// graph `i` (or the only one) and the recipe, checked in this order; the text names `fn` and the argument
+template <azd::DenseFamily F>
+static int recipe_check(const char *fn, bool wide, const uint64_t *adj, int n, int i, const typename azd::DenseFamilyOf<F>::Recipe *recipe) {
+    const azd::DenseFamilyDesc &f = azd::dense_family(F);
+    const char *why = azd::dense_check_graph(adj, n, f.max_n[wide], f.bad_n[wide]);
+    if (!why) why = azd::dense_check_recipe<F>(recipe, n);
+    else if (i >= 0) {
+        azd::g_last_error = std::string(fn) + ": graph " + std::to_string(i) + ": " + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (why) azd::g_last_error = std::string(fn) + ": " + why;
+    return why ? AZD_ERR_INVALID_ARGUMENT : AZD_OK;
+}
+// the host cost: one host function behind the 32-row and the 64-row check
+template <azd::DenseFamily F, class AbiRecipe, class AbiCost>
+static int recipe_cost(const char *fn, bool wide, const uint64_t *adj, int n, const AbiRecipe *recipe, AbiCost *out) {
+    using T = azd::DenseFamilyOf<F>;
+    static_assert(sizeof(AbiRecipe) == sizeof(typename T::Recipe) && sizeof(AbiCost) == sizeof(typename T::Cost), "ABI struct mismatch");
+    if (!out) {
+        azd::g_last_error = std::string(fn) + ": out: null";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    const auto *r = reinterpret_cast<const typename T::Recipe *>(recipe);
+    AZD_ST(recipe_check<F>(fn, wide, adj, n, -1, r));
+    T::cost_host(adj, n, *r, reinterpret_cast<typename T::Cost *>(out));
+    return AZD_OK;
+}
+// the probe: the 32-row or the 64-row kernel, as `launch` starts it
+template <azd::DenseFamily F, class AbiRecipe, class AbiCost, class Launch>
+static int probe_recipe_cost(const char *name, const char *tag, bool wide, int device, const uint64_t *adj, int n, int count, int reps, const AbiRecipe *recipe,
+                             AbiCost *out, float *ms, Launch launch) {
+    using T = azd::DenseFamilyOf<F>;
+    const auto *r = reinterpret_cast<const typename T::Recipe *>(recipe);
+    const auto check = [=](const uint64_t *g, int i) { return recipe_check<F>(name, wide, g, n, i, r); };
+    return probe_dense_cost<typename T::Cost>(name, tag, device, adj, n, count, reps, r, out, ms, check, launch);
+}
 
 extern "C" {
 
@@ -294,127 +331,50 @@ int azd_debug_probe_ah_cost_wide(int device, const uint64_t *adj, int n, int cou
 // ------------------------------------------------------------------ weighted-invariant cost of the dense-graph space
 static_assert(AZD_DENSE_INV_MAX_N == azd::DENSE_INV_MAX_N && AZD_DENSE_INV_WIDE_MAX_N == azd::DENSE_INV_WIDE_MAX_N && AZD_DENSE_INV_COUNT == azd::DENSE_INV_COUNT && AZD_DENSE_INV_INDEX_AH == azd::DENSE_INV_INDEX_AH,
               "AZD_DENSE_INV_*");
-// graph `i` (or the only one) and the recipe, checked in this order; the text names `fn` and the argument
-static int inv_check(const char *fn, bool wide, const uint64_t *adj, int n, int i, const azd_dense_inv_recipe *recipe) {
-    const char *why = wide ? azd::dense_inv_check_graph_wide(adj, n) : azd::dense_inv_check_graph(adj, n);
-    if (!why) why = azd::dense_inv_check_recipe(reinterpret_cast<const azd::DenseInvRecipe *>(recipe), n);
-    else if (i >= 0) {
-        azd::g_last_error = std::string(fn) + ": graph " + std::to_string(i) + ": " + why;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (!why) return AZD_OK;
-    azd::g_last_error = std::string(fn) + ": " + why;
-    return AZD_ERR_INVALID_ARGUMENT;
-}
 int azd_dense_inv_cost(const uint64_t *adj, int n, const azd_dense_inv_recipe *recipe, azd_dense_inv_cost_t *out) {
-    if (!out) {
-        azd::g_last_error = "azd_dense_inv_cost: out: null";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    AZD_ST(inv_check("azd_dense_inv_cost", false, adj, n, -1, recipe));
-    azd::dense_inv_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvRecipe *>(recipe), reinterpret_cast<azd::DenseInvCost *>(out));
-    return AZD_OK;
+    return recipe_cost<azd::DENSE_FAMILY_INV>("azd_dense_inv_cost", false, adj, n, recipe, out);
 }
 int azd_dense_inv_cost_wide(const uint64_t *adj, int n, const azd_dense_inv_recipe *recipe, azd_dense_inv_cost_t *out) {
-    if (!out) {
-        azd::g_last_error = "azd_dense_inv_cost_wide: out: null";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    AZD_ST(inv_check("azd_dense_inv_cost_wide", true, adj, n, -1, recipe));
-    azd::dense_inv_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvRecipe *>(recipe), reinterpret_cast<azd::DenseInvCost *>(out));
-    return AZD_OK;
-}
-// the two probes: the 32-row and the 64-row kernel
-static int probe_inv_cost(const char *name, bool wide, int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_inv_recipe *recipe,
-                          azd_dense_inv_cost_t *out, float *ms) {
-    const auto check = [=](const uint64_t *g, int i) { return inv_check(name, wide, g, n, i, recipe); };
-    return probe_dense_cost<azd::DenseInvCost>(name, "probe_inv_cost", device, adj, n, count, reps, reinterpret_cast<const azd::DenseInvRecipe *>(recipe), out, ms, check,
-                                               wide ? azd::launch_probe_inv_cost_wide : azd::launch_probe_inv_cost);
+    return recipe_cost<azd::DENSE_FAMILY_INV>("azd_dense_inv_cost_wide", true, adj, n, recipe, out);
 }
 int azd_debug_probe_inv_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_inv_recipe *recipe,
                              azd_dense_inv_cost_t *out, float *ms) {
-    return probe_inv_cost("azd_debug_probe_inv_cost", false, device, adj, n, count, reps, recipe, out, ms);
+    return probe_recipe_cost<azd::DENSE_FAMILY_INV>("azd_debug_probe_inv_cost", "probe_inv_cost", false, device, adj, n, count, reps, recipe, out, ms, azd::launch_probe_inv_cost);
 }
 int azd_debug_probe_inv_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_inv_recipe *recipe,
                                   azd_dense_inv_cost_t *out, float *ms) {
-    return probe_inv_cost("azd_debug_probe_inv_cost_wide", true, device, adj, n, count, reps, recipe, out, ms);
+    return probe_recipe_cost<azd::DENSE_FAMILY_INV>("azd_debug_probe_inv_cost_wide", "probe_inv_cost", true, device, adj, n, count, reps, recipe, out, ms,
+                                                    azd::launch_probe_inv_cost_wide);
 }
 // ------------------------------------------------------------------ extended invariant cost of the dense-graph space
 static_assert(AZD_DENSE_INVX_MAX_N == azd::DENSE_INVX_MAX_N && AZD_DENSE_INVX_WIDE_MAX_N == azd::DENSE_INVX_WIDE_MAX_N && AZD_DENSE_INVX_COUNT == azd::DENSE_INVX_COUNT && AZD_DENSE_INVX_MAX_TERMS == azd::DENSE_INVX_MAX_TERMS &&
                   AZD_DENSE_INVX_MUL == azd::DENSE_INVX_MUL && AZD_DENSE_INVX_DIV == azd::DENSE_INVX_DIV,
               "AZD_DENSE_INVX_*");
-// graph `i` (or the only one) and the recipe, checked in this order; the text names `fn` and the argument
-static int invx_check(const char *fn, bool wide, const uint64_t *adj, int n, int i, const azd_dense_invx_recipe *recipe) {
-    const char *why = wide ? azd::dense_invx_check_graph_wide(adj, n) : azd::dense_invx_check_graph(adj, n);
-    if (!why) why = azd::dense_invx_check_recipe(reinterpret_cast<const azd::DenseInvxRecipe *>(recipe), n);
-    else if (i >= 0) {
-        azd::g_last_error = std::string(fn) + ": graph " + std::to_string(i) + ": " + why;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (why) azd::g_last_error = std::string(fn) + ": " + why;
-    return why ? AZD_ERR_INVALID_ARGUMENT : AZD_OK;
-}
 int azd_dense_invx_cost(const uint64_t *adj, int n, const azd_dense_invx_recipe *recipe, azd_dense_invx_cost_t *out) {
-    if (!out) {
-        azd::g_last_error = "azd_dense_invx_cost: out: null";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    AZD_ST(invx_check("azd_dense_invx_cost", false, adj, n, -1, recipe));
-    azd::dense_invx_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvxRecipe *>(recipe), reinterpret_cast<azd::DenseInvxCost *>(out));
-    return AZD_OK;
+    return recipe_cost<azd::DENSE_FAMILY_INVX>("azd_dense_invx_cost", false, adj, n, recipe, out);
 }
 int azd_dense_invx_cost_wide(const uint64_t *adj, int n, const azd_dense_invx_recipe *recipe, azd_dense_invx_cost_t *out) {
-    if (!out) {
-        azd::g_last_error = "azd_dense_invx_cost_wide: out: null";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    AZD_ST(invx_check("azd_dense_invx_cost_wide", true, adj, n, -1, recipe));
-    azd::dense_invx_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvxRecipe *>(recipe), reinterpret_cast<azd::DenseInvxCost *>(out));
-    return AZD_OK;
-}
-// the two probes: the 32-row and the 64-row kernel
-static int probe_invx_cost(const char *name, bool wide, int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
-                           azd_dense_invx_cost_t *out, float *ms) {
-    const auto check = [=](const uint64_t *g, int i) { return invx_check(name, wide, g, n, i, recipe); };
-    return probe_dense_cost<azd::DenseInvxCost>(name, "probe_invx_cost", device, adj, n, count, reps, reinterpret_cast<const azd::DenseInvxRecipe *>(recipe), out, ms,
-                                                check, wide ? azd::launch_probe_invx_cost_wide : azd::launch_probe_invx_cost);
+    return recipe_cost<azd::DENSE_FAMILY_INVX>("azd_dense_invx_cost_wide", true, adj, n, recipe, out);
 }
 int azd_debug_probe_invx_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
                               azd_dense_invx_cost_t *out, float *ms) {
-    return probe_invx_cost("azd_debug_probe_invx_cost", false, device, adj, n, count, reps, recipe, out, ms);
+    return probe_recipe_cost<azd::DENSE_FAMILY_INVX>("azd_debug_probe_invx_cost", "probe_invx_cost", false, device, adj, n, count, reps, recipe, out, ms,
+                                                     azd::launch_probe_invx_cost);
 }
 int azd_debug_probe_invx_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invx_recipe *recipe,
                                    azd_dense_invx_cost_t *out, float *ms) {
-    return probe_invx_cost("azd_debug_probe_invx_cost_wide", true, device, adj, n, count, reps, recipe, out, ms);
+    return probe_recipe_cost<azd::DENSE_FAMILY_INVX>("azd_debug_probe_invx_cost_wide", "probe_invx_cost", true, device, adj, n, count, reps, recipe, out, ms,
+                                                     azd::launch_probe_invx_cost_wide);
 }
 // ------------------------------------------------------------------ spectrum invariant cost of the dense-graph space
 static_assert(AZD_DENSE_INVS_MAX_N == azd::DENSE_INVS_MAX_N && AZD_DENSE_INVS_WIDE_MAX_N == azd::DENSE_INVS_WIDE_MAX_N && AZD_DENSE_INVS_COUNT == azd::DENSE_INVS_COUNT && AZD_DENSE_INVS_ROUNDS == azd::DENSE_INVS_ROUNDS &&
                   AZD_DENSE_INVS_MATRIX_ADJ == azd::DENSE_INVS_MATRIX_ADJ && AZD_DENSE_INVS_MATRIX_DIST == azd::DENSE_INVS_MATRIX_DIST &&
                   AZD_DENSE_INVS_MATRIX_LAP == azd::DENSE_INVS_MATRIX_LAP && AZD_DENSE_INVS_MATRIX_SLAP == azd::DENSE_INVS_MATRIX_SLAP,
               "AZD_DENSE_INVS_*");
-// graph `i` (or the only one) and the recipe, checked in this order; the text names `fn` and the argument
-static int invs_check(const char *fn, bool wide, const uint64_t *adj, int n, int i, const azd_dense_invs_recipe *recipe) {
-    const char *why = wide ? azd::dense_invs_check_graph_wide(adj, n) : azd::dense_invs_check_graph(adj, n);
-    if (!why) why = azd::dense_invs_check_recipe(reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), n);
-    else if (i >= 0) {
-        azd::g_last_error = std::string(fn) + ": graph " + std::to_string(i) + ": " + why;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    if (why) azd::g_last_error = std::string(fn) + ": " + why;
-    return why ? AZD_ERR_INVALID_ARGUMENT : AZD_OK;
-}
-// the two host costs and the two spectrum calls: one host function each behind the 32-row and the 64-row check
-static int invs_cost(const char *fn, bool wide, const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out) {
-    if (!out) {
-        azd::g_last_error = std::string(fn) + ": out: null";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    AZD_ST(invs_check(fn, wide, adj, n, -1, recipe));
-    azd::dense_invs_cost_host(adj, n, *reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), reinterpret_cast<azd::DenseInvsCost *>(out));
-    return AZD_OK;
-}
+// the two spectrum calls: one host function behind the 32-row and the 64-row check
 static int invs_spectrum(const char *fn, bool wide, const uint64_t *adj, int n, int which, double *out) {
-    const char *why = !out ? "out: null" : wide ? azd::dense_invs_check_graph_wide(adj, n) : azd::dense_invs_check_graph(adj, n);
+    const azd::DenseFamilyDesc &f = azd::dense_family(azd::DENSE_FAMILY_INVS);
+    const char *why = !out ? "out: null" : azd::dense_check_graph(adj, n, f.max_n[wide], f.bad_n[wide]);
     if (!why && (which < AZD_DENSE_INVS_MATRIX_ADJ || which > AZD_DENSE_INVS_MATRIX_SLAP))
         why = "which: must be one of AZD_DENSE_INVS_MATRIX_ADJ, _DIST, _LAP, _SLAP (0 .. 3)";
     if (why) {
@@ -425,10 +385,10 @@ static int invs_spectrum(const char *fn, bool wide, const uint64_t *adj, int n, 
     return AZD_OK;
 }
 int azd_dense_invs_cost(const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out) {
-    return invs_cost("azd_dense_invs_cost", false, adj, n, recipe, out);
+    return recipe_cost<azd::DENSE_FAMILY_INVS>("azd_dense_invs_cost", false, adj, n, recipe, out);
 }
 int azd_dense_invs_cost_wide(const uint64_t *adj, int n, const azd_dense_invs_recipe *recipe, azd_dense_invs_cost_t *out) {
-    return invs_cost("azd_dense_invs_cost_wide", true, adj, n, recipe, out);
+    return recipe_cost<azd::DENSE_FAMILY_INVS>("azd_dense_invs_cost_wide", true, adj, n, recipe, out);
 }
 int azd_dense_invs_spectrum(const uint64_t *adj, int n, int which, double *out) { return invs_spectrum("azd_dense_invs_spectrum", false, adj, n, which, out); }
 int azd_dense_invs_spectrum_wide(const uint64_t *adj, int n, int which, double *out) {
@@ -436,17 +396,13 @@ int azd_dense_invs_spectrum_wide(const uint64_t *adj, int n, int which, double *
 }
 int azd_debug_probe_invs_cost(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invs_recipe *recipe,
                               azd_dense_invs_cost_t *out, float *ms) {
-    const char *const name = "azd_debug_probe_invs_cost";
-    const auto check = [=](const uint64_t *g, int i) { return invs_check(name, false, g, n, i, recipe); };
-    return probe_dense_cost<azd::DenseInvsCost>(name, "probe_invs_cost", device, adj, n, count, reps, reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), out, ms,
-                                                check, azd::launch_probe_invs_cost);
+    return probe_recipe_cost<azd::DENSE_FAMILY_INVS>("azd_debug_probe_invs_cost", "probe_invs_cost", false, device, adj, n, count, reps, recipe, out, ms,
+                                                     azd::launch_probe_invs_cost);
 }
 int azd_debug_probe_invs_cost_wide(int device, const uint64_t *adj, int n, int count, int reps, const azd_dense_invs_recipe *recipe,
                                    azd_dense_invs_cost_t *out, float *ms) {
-    const char *const name = "azd_debug_probe_invs_cost_wide";
-    const auto check = [=](const uint64_t *g, int i) { return invs_check(name, true, g, n, i, recipe); };
-    return probe_dense_cost<azd::DenseInvsCost>(name, "probe_invs_cost_wide", device, adj, n, count, reps, reinterpret_cast<const azd::DenseInvsRecipe *>(recipe), out, ms,
-                                                check, azd::launch_probe_invs_cost_wide);
+    return probe_recipe_cost<azd::DENSE_FAMILY_INVS>("azd_debug_probe_invs_cost_wide", "probe_invs_cost_wide", true, device, adj, n, count, reps, recipe, out, ms,
+                                                     azd::launch_probe_invs_cost_wide);
 }
 int azd_debug_probe_math_f64(int device, const double *in, double *out, int n) {
     if (!in || !out || n <= 0) return AZD_ERR_INVALID_ARGUMENT;

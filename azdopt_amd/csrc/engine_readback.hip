@@ -49,6 +49,74 @@ static int ramsey_argmin_typed(azd_engine *e, Abi *out, const char *too_many_edg
     return AZD_OK;
 }
 
+// What an entry says to the engine of a recipe tier (TierDesc::family) it does not serve: "<entry>: an <flag> engine's <thing> is
+// <done> with <with>", the flag and `with` the names of the engine's own family (dense_cost_host.h: DenseFamilyDesc)
+static std::string other_family(const char *entry, const char *flag, const char *thing_is_done, const char *with) {
+    return std::string(entry) + ": an " + flag + " engine's " + thing_is_done + " with " + with;
+}
+// The dense argmin entries: `reads` is the tier whose record the entry copies out, `refusal` its text for an engine of another
+// tier -- said to an engine with the Aouchiche-Hansen cost (an engine without it is refused without a text), by the wide entry and
+// the recipe tiers' to all.  The engine of a recipe tier is told its own tier's reader by every entry; the two Aouchiche-Hansen
+// tiers name each other's.
+static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes, const char *refusal) {
+    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
+    if (e->tier->id != reads) {
+        if (const azd::DenseFamilyDesc *f = e->tier->family)
+            azd::g_last_error = other_family("dense argmin read", f->flag[e->tier->wide], "record is read", f->argmin_reader[e->tier->wide]);
+        else if (e->tier->ah || (reads != TIER_DENSE && reads != TIER_DENSE_AH)) azd::g_last_error = refusal;
+        return AZD_ERR_UNSUPPORTED;
+    }
+    AZD_ENTER(e);
+    AZD_HIP(hipStreamSynchronize(e->stream));
+    AZD_HIP(hipMemcpy(out, e->a.argmin_d, bytes, hipMemcpyDeviceToHost));
+    return AZD_OK;
+}
+// The entries of the three recipe costs (dense_cost_host.h: DenseFamily), at either row limit: the indices are checked at the engine's n.
+// The recipe: checked, then copied -- the caller's bytes -- behind the per-agent doubles of cur_lambda, where the tier's kernels read it
+// (dense_spectral.inc: DenseCostRecipeT::recipe); the engine keeps it widened
+template <azd::DenseFamily F>
+static int set_recipe(azd_engine *e, const typename azd::DenseFamilyOf<F>::Recipe *r) {
+    if (!e) return AZD_ERR_INVALID_ARGUMENT;
+    const azd::DenseFamilyDesc &f = azd::dense_family(F), *const theirs = e->tier->family;
+    if (theirs != &f) {
+        azd::g_last_error = theirs ? other_family(f.setter, theirs->flag[0], "recipe is set", theirs->setter) : std::string(f.setter) + ": not an " + f.flag[0] + " engine";
+        return AZD_ERR_UNSUPPORTED;
+    }
+    if (e->inv_recipe_locked) {
+        azd::g_last_error = std::string(f.setter) + ": par_new has run: the trees' evals were computed with the recipe in force, which stays";
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    if (const char *why = azd::dense_check_recipe<F>(r, e->a.n)) {
+        azd::g_last_error = std::string(f.setter) + ": " + why;
+        return AZD_ERR_INVALID_ARGUMENT;
+    }
+    AZD_HIP(hipSetDevice(e->cfg.device));
+    AZD_HIP(hipMemcpy(e->a.cur_lambda + (size_t)f.count * e->a.B, r, sizeof(*r), hipMemcpyHostToDevice));
+    e->inv_recipe = azd::dense_widen_recipe(*r);
+    e->inv_recipe_set = true;
+    return AZD_OK;
+}
+// An agent's record: the kept invariants, and cost and eval from them by the device's combination, operation for operation
+// (dense_recipe_combine)
+template <azd::DenseFamily F>
+static int agent_cost(azd_engine *e, int agent, typename azd::DenseFamilyOf<F>::Cost *out) {
+    if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
+    const azd::DenseFamilyDesc &f = azd::dense_family(F), *const theirs = e->tier->family;
+    if (theirs != &f) {
+        azd::g_last_error =
+            theirs ? other_family(f.agent_cost, theirs->flag[0], "record is read", theirs->agent_cost) : std::string(f.agent_cost) + ": not an " + f.flag[0] + " engine";
+        return AZD_ERR_UNSUPPORTED;
+    }
+    AZD_ENTER(e);
+    AZD_HIP(hipStreamSynchronize(e->stream));
+    const azd::Arenas &a = e->a;
+    for (int i = 0; i < f.count; ++i) AZD_HIP(hipMemcpy(&out->inv[i], a.cur_lambda + (size_t)i * a.B + agent, 8, hipMemcpyDeviceToHost));
+    AZD_HIP(hipMemcpy(&out->dist_k, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
+    AZD_HIP(hipMemcpy(&out->computed, a.cur_mu + a.B + agent, 4, hipMemcpyDeviceToHost));
+    azd::dense_recipe_combine(e->inv_recipe, out->inv, f.count, &out->cost, &out->eval);
+    return AZD_OK;
+}
+
 extern "C" {
 
 static_assert(sizeof(azd_ramsey_argmin) == sizeof(azd::RamseyArgminRec) && sizeof(azd_ramsey_wide_argmin) == sizeof(azd::RamseyWideArgminRec),
@@ -83,35 +151,6 @@ int azd_engine_ramsey_argmin_any(azd_engine *e, uint8_t *colors, int colors_cap,
     if (eval) *eval = r.eval;
     if (agent) *agent = r.agent;
     if (node) *node = r.node;
-    return AZD_OK;
-}
-// The dense argmin entries: `reads` is the tier whose record the entry copies out, `refusal` its text for an engine of another
-// tier -- said to an engine with the Aouchiche-Hansen cost (an engine without it is refused without a text), by the wide entry to all.
-// The two weighted-invariant tiers name each other's reader, as the two Aouchiche-Hansen tiers do, and so do the two extended ones
-// and the two spectrum ones.
-static int dense_argmin_read(azd_engine *e, void *out, Tier reads, size_t bytes, const char *refusal) {
-    if (!e || !out || !e->initialised) return AZD_ERR_INVALID_ARGUMENT;
-    if (e->tier->id != reads) {
-        if (e->tier->id == TIER_DENSE_INVS_WIDE)
-            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVS_WIDE engine's record is read with azd_engine_dense_invs_wide_argmin_data";
-        else if (e->tier->id == TIER_DENSE_INVS)
-            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVS engine's record is read with azd_engine_dense_invs_argmin_data";
-        else if (e->tier->id == TIER_DENSE_INVX_WIDE)
-            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVX_WIDE engine's record is read with azd_engine_dense_invx_wide_argmin_data";
-        else if (e->tier->id == TIER_DENSE_INVX)
-            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_argmin_data";
-        else if (e->tier->id == TIER_DENSE_INV_WIDE)
-            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INV_WIDE engine's record is read with azd_engine_dense_inv_wide_argmin_data";
-        else if (e->tier->id == TIER_DENSE_INV)
-            azd::g_last_error = "dense argmin read: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_argmin_data";
-        else if (e->tier->ah || reads == TIER_DENSE_AH_WIDE || reads == TIER_DENSE_INV || reads == TIER_DENSE_INV_WIDE || reads == TIER_DENSE_INVX ||
-                 reads == TIER_DENSE_INVX_WIDE || reads == TIER_DENSE_INVS || reads == TIER_DENSE_INVS_WIDE)
-            azd::g_last_error = refusal;
-        return AZD_ERR_UNSUPPORTED;
-    }
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    AZD_HIP(hipMemcpy(out, e->a.argmin_d, bytes, hipMemcpyDeviceToHost));
     return AZD_OK;
 }
 static_assert(sizeof(azd_dense_argmin) == sizeof(azd::DenseArgminRec) && sizeof(azd_dense_ah_argmin) == sizeof(azd::DenseAhArgminRec) &&
@@ -159,60 +198,12 @@ int azd_engine_dense_inv_argmin_data(azd_engine *e, azd_dense_inv_argmin *out) {
 int azd_engine_dense_inv_wide_argmin_data(azd_engine *e, azd_dense_inv_wide_argmin *out) {
     return dense_argmin_read(e, out, TIER_DENSE_INV_WIDE, sizeof(*out), "azd_engine_dense_inv_wide_argmin_data: not an AZD_ENGINE_DENSE_INV_WIDE engine");
 }
-// The recipe of an AZD_ENGINE_DENSE_INV engine (either row limit: the indices are checked at the engine's n): checked, then copied
-// behind the per-agent doubles of cur_lambda, where the tier's kernels read it (dense_inv_cost.inc: dense_inv_recipe)
 int azd_engine_set_dense_inv_recipe(azd_engine *e, const azd_dense_inv_recipe *recipe) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (!tier_inv(e->tier)) {
-        azd::g_last_error = tier_invs(e->tier)   ? "azd_engine_set_dense_inv_recipe: an AZD_ENGINE_DENSE_INVS engine's recipe is set with azd_engine_set_dense_invs_recipe"
-                            : tier_invx(e->tier) ? "azd_engine_set_dense_inv_recipe: an AZD_ENGINE_DENSE_INVX engine's recipe is set with azd_engine_set_dense_invx_recipe"
-                                                 : "azd_engine_set_dense_inv_recipe: not an AZD_ENGINE_DENSE_INV engine";
-        return AZD_ERR_UNSUPPORTED;
-    }
-    if (e->inv_recipe_locked) {
-        azd::g_last_error = "azd_engine_set_dense_inv_recipe: par_new has run: the trees' evals were computed with the recipe in force, which stays";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    const azd::DenseInvRecipe *r = reinterpret_cast<const azd::DenseInvRecipe *>(recipe);
-    if (const char *why = azd::dense_inv_check_recipe(r, e->a.n)) {
-        azd::g_last_error = std::string("azd_engine_set_dense_inv_recipe: ") + why;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    AZD_HIP(hipSetDevice(e->cfg.device));
-    AZD_HIP(hipMemcpy(e->a.cur_lambda + (size_t)azd::DENSE_INV_COUNT * e->a.B, r, sizeof(*r), hipMemcpyHostToDevice));
-    e->inv_recipe = *r;
-    e->inv_recipe_set = true;
-    return AZD_OK;
+    return set_recipe<azd::DENSE_FAMILY_INV>(e, reinterpret_cast<const azd::DenseInvRecipe *>(recipe));
 }
 int azd_engine_dense_inv_agent_cost(azd_engine *e, int agent, azd_dense_inv_cost_t *out) {
-    if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (!tier_inv(e->tier)) {
-        azd::g_last_error = tier_invs(e->tier)   ? "azd_engine_dense_inv_agent_cost: an AZD_ENGINE_DENSE_INVS engine's record is read with azd_engine_dense_invs_agent_cost"
-                            : tier_invx(e->tier) ? "azd_engine_dense_inv_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost"
-                                                 : "azd_engine_dense_inv_agent_cost: not an AZD_ENGINE_DENSE_INV engine";
-        return AZD_ERR_UNSUPPORTED;
-    }
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    const azd::Arenas &a = e->a;
-    for (int i = 0; i < azd::DENSE_INV_COUNT; ++i) AZD_HIP(hipMemcpy(&out->inv[i], a.cur_lambda + (size_t)i * a.B + agent, 8, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&out->dist_k, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&out->computed, a.cur_mu + a.B + agent, 4, hipMemcpyDeviceToHost));
-    // cost and eval from the kept invariants: the device's combination, operation for operation (this unit is built with -ffp-contract=off)
-    const azd::DenseInvRecipe &r = e->inv_recipe;
-    double c = r.bias;
-    for (int i = 0; i < azd::DENSE_INV_COUNT; ++i)
-        if (r.weight[i] != 0.0) {
-            const double term = r.weight[i] * out->inv[i];
-            c = c + term;
-        }
-    out->cost = (float)c;
-    out->eval = r.eval_scale * (out->cost + r.eval_offset);
-    return AZD_OK;
+    return agent_cost<azd::DENSE_FAMILY_INV>(e, agent, reinterpret_cast<azd::DenseInvCost *>(out));
 }
-// The extended invariant cost's entries, in the image of the weighted-invariant cost's: the recipe behind the sixteen per-agent
-// doubles of cur_lambda (dense_invx_cost.inc: dense_invx_recipe; either row limit, the indices checked at the engine's n), the argmin
-// record of each row limit, an agent's record
 int azd_engine_dense_invx_argmin_data(azd_engine *e, azd_dense_invx_argmin *out) {
     return dense_argmin_read(e, out, TIER_DENSE_INVX, sizeof(*out), "azd_engine_dense_invx_argmin_data: not an AZD_ENGINE_DENSE_INVX engine");
 }
@@ -220,66 +211,10 @@ int azd_engine_dense_invx_wide_argmin_data(azd_engine *e, azd_dense_invx_wide_ar
     return dense_argmin_read(e, out, TIER_DENSE_INVX_WIDE, sizeof(*out), "azd_engine_dense_invx_wide_argmin_data: not an AZD_ENGINE_DENSE_INVX_WIDE engine");
 }
 int azd_engine_set_dense_invx_recipe(azd_engine *e, const azd_dense_invx_recipe *recipe) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (!tier_invx(e->tier)) {
-        azd::g_last_error = tier_invs(e->tier)  ? "azd_engine_set_dense_invx_recipe: an AZD_ENGINE_DENSE_INVS engine's recipe is set with azd_engine_set_dense_invs_recipe"
-                            : tier_inv(e->tier) ? "azd_engine_set_dense_invx_recipe: an AZD_ENGINE_DENSE_INV engine's recipe is set with azd_engine_set_dense_inv_recipe"
-                                                : "azd_engine_set_dense_invx_recipe: not an AZD_ENGINE_DENSE_INVX engine";
-        return AZD_ERR_UNSUPPORTED;
-    }
-    if (e->inv_recipe_locked) {
-        azd::g_last_error = "azd_engine_set_dense_invx_recipe: par_new has run: the trees' evals were computed with the recipe in force, which stays";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    const azd::DenseInvxRecipe *r = reinterpret_cast<const azd::DenseInvxRecipe *>(recipe);
-    if (const char *why = azd::dense_invx_check_recipe(r, e->a.n)) {
-        azd::g_last_error = std::string("azd_engine_set_dense_invx_recipe: ") + why;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    AZD_HIP(hipSetDevice(e->cfg.device));
-    AZD_HIP(hipMemcpy(e->a.cur_lambda + (size_t)azd::DENSE_INVX_COUNT * e->a.B, r, sizeof(*r), hipMemcpyHostToDevice));
-    e->invx_recipe = *r;
-    e->inv_recipe_set = true;
-    return AZD_OK;
+    return set_recipe<azd::DENSE_FAMILY_INVX>(e, reinterpret_cast<const azd::DenseInvxRecipe *>(recipe));
 }
 int azd_engine_dense_invx_agent_cost(azd_engine *e, int agent, azd_dense_invx_cost_t *out) {
-    if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (!tier_invx(e->tier)) {
-        azd::g_last_error = tier_invs(e->tier)  ? "azd_engine_dense_invx_agent_cost: an AZD_ENGINE_DENSE_INVS engine's record is read with azd_engine_dense_invs_agent_cost"
-                            : tier_inv(e->tier) ? "azd_engine_dense_invx_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost"
-                                                : "azd_engine_dense_invx_agent_cost: not an AZD_ENGINE_DENSE_INVX engine";
-        return AZD_ERR_UNSUPPORTED;
-    }
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    const azd::Arenas &a = e->a;
-    for (int i = 0; i < azd::DENSE_INVX_COUNT; ++i) AZD_HIP(hipMemcpy(&out->inv[i], a.cur_lambda + (size_t)i * a.B + agent, 8, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&out->dist_k, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&out->computed, a.cur_mu + a.B + agent, 4, hipMemcpyDeviceToHost));
-    // cost and eval from the kept invariants: the device's combination, operation for operation (this unit is built with -ffp-contract=off)
-    const azd::DenseInvxRecipe &r = e->invx_recipe;
-    double c = r.bias;
-    for (int i = 0; i < azd::DENSE_INVX_COUNT; ++i)
-        if (r.weight[i] != 0.0) {
-            const double term = r.weight[i] * out->inv[i];
-            c = c + term;
-        }
-    for (int t = 0; t < r.n_terms; ++t) {
-        const azd::DenseInvxTerm &p = r.term[t];
-        if (p.coef == 0.0) continue;
-        const double v = p.op == azd::DENSE_INVX_DIV ? out->inv[p.a] / out->inv[p.b] : out->inv[p.a] * out->inv[p.b];
-        const double term = p.coef * v;
-        c = c + term;
-    }
-    out->cost = (float)c;
-    out->eval = r.eval_scale * (out->cost + r.eval_offset);
-    return AZD_OK;
-}
-// The spectrum invariant cost's entries, in the same image: the recipe behind the twenty-one per-agent doubles of cur_lambda
-// (dense_spectral.inc: DenseCostRecipeT::recipe; either row limit, the indices checked at the engine's n), the argmin record of each
-// row limit, an agent's record
-static const char *invs_other_tier(const azd_engine *e, const char *invx, const char *inv, const char *other) {
-    return tier_invx(e->tier) ? invx : tier_inv(e->tier) ? inv : other;
+    return agent_cost<azd::DENSE_FAMILY_INVX>(e, agent, reinterpret_cast<azd::DenseInvxCost *>(out));
 }
 int azd_engine_dense_invs_argmin_data(azd_engine *e, azd_dense_invs_argmin *out) {
     return dense_argmin_read(e, out, TIER_DENSE_INVS, sizeof(*out), "azd_engine_dense_invs_argmin_data: not an AZD_ENGINE_DENSE_INVS engine");
@@ -288,66 +223,14 @@ int azd_engine_dense_invs_wide_argmin_data(azd_engine *e, azd_dense_invs_wide_ar
     return dense_argmin_read(e, out, TIER_DENSE_INVS_WIDE, sizeof(*out), "azd_engine_dense_invs_wide_argmin_data: not an AZD_ENGINE_DENSE_INVS_WIDE engine");
 }
 int azd_engine_set_dense_invs_recipe(azd_engine *e, const azd_dense_invs_recipe *recipe) {
-    if (!e) return AZD_ERR_INVALID_ARGUMENT;
-    if (!tier_invs(e->tier)) {
-        azd::g_last_error = invs_other_tier(e, "azd_engine_set_dense_invs_recipe: an AZD_ENGINE_DENSE_INVX engine's recipe is set with azd_engine_set_dense_invx_recipe",
-                                            "azd_engine_set_dense_invs_recipe: an AZD_ENGINE_DENSE_INV engine's recipe is set with azd_engine_set_dense_inv_recipe",
-                                            "azd_engine_set_dense_invs_recipe: not an AZD_ENGINE_DENSE_INVS engine");
-        return AZD_ERR_UNSUPPORTED;
-    }
-    if (e->inv_recipe_locked) {
-        azd::g_last_error = "azd_engine_set_dense_invs_recipe: par_new has run: the trees' evals were computed with the recipe in force, which stays";
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    const azd::DenseInvsRecipe *r = reinterpret_cast<const azd::DenseInvsRecipe *>(recipe);
-    if (const char *why = azd::dense_invs_check_recipe(r, e->a.n)) {
-        azd::g_last_error = std::string("azd_engine_set_dense_invs_recipe: ") + why;
-        return AZD_ERR_INVALID_ARGUMENT;
-    }
-    AZD_HIP(hipSetDevice(e->cfg.device));
-    AZD_HIP(hipMemcpy(e->a.cur_lambda + (size_t)azd::DENSE_INVS_COUNT * e->a.B, r, sizeof(*r), hipMemcpyHostToDevice));
-    e->invs_recipe = *r;
-    e->inv_recipe_set = true;
-    return AZD_OK;
+    return set_recipe<azd::DENSE_FAMILY_INVS>(e, reinterpret_cast<const azd::DenseInvsRecipe *>(recipe));
 }
 int azd_engine_dense_invs_agent_cost(azd_engine *e, int agent, azd_dense_invs_cost_t *out) {
-    if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (!tier_invs(e->tier)) {
-        azd::g_last_error = invs_other_tier(e, "azd_engine_dense_invs_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost",
-                                            "azd_engine_dense_invs_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost",
-                                            "azd_engine_dense_invs_agent_cost: not an AZD_ENGINE_DENSE_INVS engine");
-        return AZD_ERR_UNSUPPORTED;
-    }
-    AZD_ENTER(e);
-    AZD_HIP(hipStreamSynchronize(e->stream));
-    const azd::Arenas &a = e->a;
-    for (int i = 0; i < azd::DENSE_INVS_COUNT; ++i) AZD_HIP(hipMemcpy(&out->inv[i], a.cur_lambda + (size_t)i * a.B + agent, 8, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&out->dist_k, a.cur_mu + agent, 4, hipMemcpyDeviceToHost));
-    AZD_HIP(hipMemcpy(&out->computed, a.cur_mu + a.B + agent, 4, hipMemcpyDeviceToHost));
-    // cost and eval from the kept invariants: the device's combination, operation for operation (this unit is built with -ffp-contract=off)
-    const azd::DenseInvsRecipe &r = e->invs_recipe;
-    double c = r.bias;
-    for (int i = 0; i < azd::DENSE_INVS_COUNT; ++i)
-        if (r.weight[i] != 0.0) {
-            const double term = r.weight[i] * out->inv[i];
-            c = c + term;
-        }
-    for (int t = 0; t < r.n_terms; ++t) {
-        const azd::DenseInvxTerm &p = r.term[t];
-        if (p.coef == 0.0) continue;
-        const double v = p.op == azd::DENSE_INVX_DIV ? out->inv[p.a] / out->inv[p.b] : out->inv[p.a] * out->inv[p.b];
-        const double term = p.coef * v;
-        c = c + term;
-    }
-    out->cost = (float)c;
-    out->eval = r.eval_scale * (out->cost + r.eval_offset);
-    return AZD_OK;
+    return agent_cost<azd::DENSE_FAMILY_INVS>(e, agent, reinterpret_cast<azd::DenseInvsCost *>(out));
 }
 int azd_engine_dense_ah_agent_cost(azd_engine *e, int agent, azd_dense_ah_cost_t *out) {
     if (!e || !out || agent < 0 || agent >= e->a.B) return AZD_ERR_INVALID_ARGUMENT;
-    if (tier_invs(e->tier)) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INVS engine's record is read with azd_engine_dense_invs_agent_cost";
-    if (tier_invx(e->tier)) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INVX engine's record is read with azd_engine_dense_invx_agent_cost";
-    if (tier_inv(e->tier)) azd::g_last_error = "azd_engine_dense_ah_agent_cost: an AZD_ENGINE_DENSE_INV engine's record is read with azd_engine_dense_inv_agent_cost";
+    if (const azd::DenseFamilyDesc *f = e->tier->family) azd::g_last_error = other_family("azd_engine_dense_ah_agent_cost", f->flag[0], "record is read", f->agent_cost);
     if (!e->tier->ah) return AZD_ERR_UNSUPPORTED;
     AZD_ENTER(e);
     AZD_HIP(hipStreamSynchronize(e->stream));
@@ -478,16 +361,9 @@ int azd_engine_agent_state(azd_engine *e, int agent, uint8_t *parents, uint64_t 
     AZD_HIP(hipStreamSynchronize(e->stream));
     const azd::Arenas &a = e->a;
     if (a.space == azd::SPACE_DENSE) { // `parents` receives the neighbourhoods (8 n bytes); masks are kw_host words
-        if (tier_invs(e->tier) && (lambda_1 || matching_size)) {
-            azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_INVS engine keeps neither (azd_engine_dense_invs_agent_cost)";
-            return AZD_ERR_UNSUPPORTED;
-        }
-        if (tier_invx(e->tier) && (lambda_1 || matching_size)) {
-            azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_INVX engine keeps neither (azd_engine_dense_invx_agent_cost)";
-            return AZD_ERR_UNSUPPORTED;
-        }
-        if (tier_inv(e->tier) && (lambda_1 || matching_size)) {
-            azd::g_last_error = "azd_engine_agent_state: lambda_1 / matching_size: an AZD_ENGINE_DENSE_INV engine keeps neither (azd_engine_dense_inv_agent_cost)";
+        if (e->tier->family && (lambda_1 || matching_size)) {
+            const azd::DenseFamilyDesc &f = *e->tier->family;
+            azd::g_last_error = std::string("azd_engine_agent_state: lambda_1 / matching_size: an ") + f.flag[0] + " engine keeps neither (" + f.agent_cost + ")";
             return AZD_ERR_UNSUPPORTED;
         }
         if (e->tier->ah && (lambda_1 || matching_size)) {

@@ -175,7 +175,7 @@ struct DenseAhWideArgminRec { // device copy of azd_dense_ah_wide_argmin (AZD_EN
 struct DenseInvArgminRec { // device copy of azd_dense_inv_argmin (AZD_ENGINE_DENSE_INV engines: n <= 32, E <= 496); in argmin_d's place too
     uint64_t adj[32];
     uint64_t permitted[8]; // modifiable slots (colex positions) still open
-    double inv[10];        // the ten invariants (c21_host.h: DenseInvCost), 0.0 where not computed
+    double inv[10];        // the ten invariants (dense_cost_host.h: DenseInvCost), 0.0 where not computed
     int32_t dist_k;
     uint32_t computed;
     float cost, eval;
@@ -197,7 +197,7 @@ struct DenseInvWideArgminRec { // device copy of azd_dense_inv_wide_argmin (AZD_
 struct DenseInvxArgminRec { // device copy of azd_dense_invx_argmin (AZD_ENGINE_DENSE_INVX engines: n <= 32, E <= 496); in argmin_d's place too
     uint64_t adj[32];
     uint64_t permitted[8]; // modifiable slots (colex positions) still open
-    double inv[16];        // the sixteen invariants (c21_host.h: DenseInvxCost), 0.0 where not computed
+    double inv[16];        // the sixteen invariants (dense_cost_host.h: DenseInvxCost), 0.0 where not computed
     int32_t dist_k;
     uint32_t computed;
     float cost, eval;
@@ -218,7 +218,7 @@ struct DenseInvxWideArgminRec { // device copy of azd_dense_invx_wide_argmin (AZ
 struct DenseInvsArgminRec { // device copy of azd_dense_invs_argmin (AZD_ENGINE_DENSE_INVS engines: n <= 32, E <= 496); in argmin_d's place too
     uint64_t adj[32];
     uint64_t permitted[8]; // modifiable slots (colex positions) still open
-    double inv[21];        // the twenty-one invariants (c21_host.h: DenseInvsCost), 0.0 where not computed
+    double inv[21];        // the twenty-one invariants (dense_cost_host.h: DenseInvsCost), 0.0 where not computed
     int32_t dist_k;
     uint32_t computed;
     float cost, eval;

@@ -93,14 +93,14 @@ void launch_probe_math(const float *d_in, float *d_out, int n, void *stream); //
 // each: from nothing, then after each of n_toggles edge toggles with the matching repaired (outputs [count][n_toggles + 1])
 void launch_probe_dense_cost(const uint64_t *d_adj, int n, int count, const uint16_t *d_toggles, int n_toggles, double *d_lam, int *d_mu,
                              uint8_t *d_mate, int *d_hooks, void *stream);
-// dense_ah_kernels.hip: the Aouchiche-Hansen cost of `count` graphs on n vertices, one wave each (c21_host.h: DenseAhCost), and the
+// dense_ah_kernels.hip: the Aouchiche-Hansen cost of `count` graphs on n vertices, one wave each (dense_cost_host.h: DenseAhCost), and the
 // f64 division / sqrt parity probe (tests)
 struct DenseAhCost;
 void launch_probe_ah_cost(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream);
 void launch_probe_math_f64(const double *d_in, double *d_out, int n, void *stream);
 void launch_probe_ah_cost_wide(const uint64_t *d_adj, int n, int count, int reps, DenseAhCost *d_out, void *stream); // n <= 64 (dense_ah_wide_kernels.hip)
 // dense_inv_kernels.hip: the weighted-invariant cost of `count` graphs on n vertices under the recipe at d_recipe (device memory), one
-// wave each (c21_host.h: DenseInvRecipe, DenseInvCost)
+// wave each (dense_cost_host.h: DenseInvRecipe, DenseInvCost)
 struct DenseInvRecipe;
 struct DenseInvCost;
 void launch_probe_inv_cost(const uint64_t *d_adj, int n, int count, int reps, const DenseInvRecipe *d_recipe, DenseInvCost *d_out, void *stream);

@@ -14,7 +14,7 @@ BUILD-DEFINED, in the image of the dense space: eval = slope * (cost + 2.0f) wit
 The eigenvalue procedure stands in for faer: Householder reduction of the distance matrix to tridiagonal form, then a
 Sturm-count multisection (64 shifts per round, AH_ROUNDS rounds) for the one eigenvalue wanted.  It is written one IEEE f64
 operation at a time with every reduction in a fixed order (tree_sum64 = the xor-butterfly of a 64-lane wave), the same sequence
-as azd_dense_ah_cost (c21_host.cpp) and dense_ah_cost_wave (dense_ah_cost.inc): the three agree bit for bit.  Plain Python floats
+as azd_dense_ah_cost (dense_cost_host.cpp) and dense_ah_cost_wave (dense_ah_cost.inc): the three agree bit for bit.  Plain Python floats
 are IEEE binary64 and Python never contracts a * b + c.
 """
 import functools

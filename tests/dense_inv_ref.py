@@ -16,7 +16,7 @@ and a recipe (weight[10], bias, adj_index, dist_index, eval_offset, eval_scale):
     c = bias;  for i in 0 .. 9: if weight[i] != 0: c = c + weight[i] * I_i;  cost = f32(c);  eval = eval_scale * (cost + eval_offset)
 
 A spectral invariant whose weight is zero is not computed: 0.0, and its bit of `computed` is clear.  azd_dense_inv_cost
-(c21_host.cpp) and dense_inv_cost_wave (dense_inv_cost.inc) run the same sequence: the three agree bit for bit.
+(dense_cost_host.cpp) and dense_inv_cost_wave (dense_inv_cost.inc) run the same sequence: the three agree bit for bit.
 Also here: the four recipes the tests use, and PyDenseInvEngine, tests/dense_ah_ref.py's engine with this cost."""
 import functools
 
@@ -29,7 +29,7 @@ NAMES = ("edges", "max_degree", "min_degree", "diameter", "radius", "proximity",
 ADJ_EIG, DIST_EIG = 8, 9
 INDEX_AH = -1
 ALWAYS = 0xFF
-INV_DEFLATE = 2.0 ** -200  # a Householder column whose tail is below this is skipped (c21_host.h: DENSE_INV_DEFLATE)
+INV_DEFLATE = 2.0 ** -200  # a Householder column whose tail is below this is skipped (dense_cost_host.h: DENSE_INV_DEFLATE)
 
 
 class Recipe:
@@ -94,7 +94,7 @@ _TRI, _EIG = {}, {}  # (adj, n, which) -> (diag, sub);  (adj, n, which, k) -> th
 
 def _tridiagonal(adj, n, which):
     """(diag, sub) of the matrix `which` of the graph: it does not depend on the index wanted, so the indices share it.  The
-    reduction skips a column whose tail is below INV_DEFLATE, at every n (c21_host.h: DENSE_INV_DEFLATE)."""
+    reduction skips a column whose tail is below INV_DEFLATE, at every n (dense_cost_host.h: DENSE_INV_DEFLATE)."""
     key = (adj, n, which)
     if key not in _TRI:
         _TRI[key] = A.tridiagonalise(MATRICES[which](adj, n), n, INV_DEFLATE)

@@ -2,7 +2,7 @@
 infrastructure).  The image of tests/dense_ah_wide_ref.py: the stages of tests/dense_inv_ref.py (_stages, _tridiagonal, _eig,
 dist_index_of, the recipes) and of tests/dense_ah_ref.py (tridiagonalise, kth_eigenvalue) are generic in n; only
 dense_inv_ref.inv_cost's assert stops at 32.  inv_cost below is that function's sequence with the limit at 64, and nothing else
-differs: the Householder reduction skips a column whose tail is below 2^-200 (dense_inv_ref.INV_DEFLATE; c21_host.h:
+differs: the Householder reduction skips a column whose tail is below 2^-200 (dense_inv_ref.INV_DEFLATE; dense_cost_host.h:
 DENSE_INV_DEFLATE) at every n, in the narrow reference as here -- the condition was found on double brooms of 50 and 56 vertices
 and first held beyond 32 vertices only, until rank-deficient adjacency matrices on 21 vertices and more turned out to starve the
 same way.  The pure-Python reduction is slow at n = 64 and does not depend on the index wanted: dense_inv_ref caches it per

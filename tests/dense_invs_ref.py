@@ -16,7 +16,7 @@ from hi = R + 1.0, lo = -hi and makes ROUNDS = 67 rounds of
 then theta_l = (lo + hi) * 0.5.  An energy is dense_ah_ref.tree_sum64 over the n absolute values (64 slots, the rest 0.0).
 A matrix's *_eig comes from the multisection, its energy from the procedure above, each only when needed: a weight that is not zero
 or a term with a non-zero coefficient names it -- otherwise 0.0, and its bit (8 .. 20) of `computed` is clear.  The combination is
-dense_invx_ref's over twenty-one weights.  azd_dense_invs_cost (c21_host.cpp) and dense_invs_cost_wave (dense_invs_cost.inc) run the
+dense_invx_ref's over twenty-one weights.  azd_dense_invs_cost (dense_cost_host.cpp) and dense_invs_cost_wave (dense_invs_cost.inc) run the
 same sequence: the three agree bit for bit.  With weights 16 .. 20 zero and no term naming them the sequence is
 dense_invx_ref.invx_cost's.
 Also here: the five recipes the tests add and INVX's nine converted, their ctypes form, and PyDenseInvsEngine."""

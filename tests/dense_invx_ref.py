@@ -18,7 +18,7 @@ and a recipe (weight[16], bias, adj_index, dist_index, lap_index, slap_index, ev
     cost = f32(c);  eval = eval_scale * (cost + eval_offset)
 
 Invariants 0 .. 7 are always computed; each of 8 .. 15 only when its weight is not zero or a term with a non-zero coefficient names
-it -- otherwise 0.0, and its bit of `computed` is clear.  azd_dense_invx_cost (c21_host.cpp) and dense_invx_cost_wave
+it -- otherwise 0.0, and its bit of `computed` is clear.  azd_dense_invx_cost (dense_cost_host.cpp) and dense_invx_cost_wave
 (dense_invx_cost.inc) run the same sequence: the three agree bit for bit.  With weights 10 .. 15 zero and no term the sequence is
 dense_inv_ref.inv_cost's.
 Also here: the nine recipes the tests use, their ctypes forms, and PyDenseInvxEngine, tests/dense_ah_ref.py's engine with this cost."""

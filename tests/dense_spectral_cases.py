@@ -2,7 +2,7 @@
 device forms they are held to): connected graphs whose ADJACENCY matrix has few distinct eigenvalues -- double brooms with most
 vertices in the two bunches, complete multipartite graphs, the star, K_n -- each as generated and under two seeded relabellings.
 On such a matrix the Householder reduction uses the rank up after a few steps and goes on in rounding noise that shrinks by about
-2^-53 every other step; without the deflation rule (c21_host.h: DENSE_INV_DEFLATE) the squares reach the subnormals after some
+2^-53 every other step; without the deflation rule (dense_cost_host.h: DENSE_INV_DEFLATE) the squares reach the subnormals after some
 twenty steps and the tridiagonal form ends in NaN, which the multisection turns into a finite, wrong eigenvalue.  Which labelling
 a graph comes in decides: a double broom with the lighter bunch first passes, the same broom with the heavier bunch first fails.
 Shared by test_dense_spectral_cases.py (the references, CPU), the three test_dense_inv*_abi.py (host functions, CPU) and the

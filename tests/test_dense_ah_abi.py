@@ -1,4 +1,4 @@
-"""azd_dense_ah_cost, the host form of the Aouchiche-Hansen cost (c21_host.cpp), without a GPU: equal to the Python reference
+"""azd_dense_ah_cost, the host form of the Aouchiche-Hansen cost (dense_cost_host.cpp), without a GPU: equal to the Python reference
 (tests/dense_ah_ref.py) bit for bit on the whole graph set -- proximity and eigenvalue as f64 bit patterns, diameter and k as
 integers, cost and eval as f32 bit patterns -- and its argument checks."""
 import ctypes as C

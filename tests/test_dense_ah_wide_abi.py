@@ -1,4 +1,4 @@
-"""The Aouchiche-Hansen cost up to 64 vertices without a GPU: azd_dense_ah_cost_wide (c21_host.cpp) equal to the Python restatement
+"""The Aouchiche-Hansen cost up to 64 vertices without a GPU: azd_dense_ah_cost_wide (dense_cost_host.cpp) equal to the Python restatement
 (tests/dense_ah_wide_ref.py) bit for bit on the 88 graphs of graph_set_wide() -- proximity and eigenvalue as f64 bit patterns,
 diameter and k as integers, cost and eval as f32 bit patterns -- and to azd_dense_ah_cost on the n <= 32 set; the argument checks
 of the new calls and of AZD_ENGINE_DENSE_AH_WIDE, made before any device is looked for; the Python and C++ hosts."""

@@ -1,4 +1,4 @@
-"""azd_dense_inv_cost, the host form of the weighted-invariant cost (c21_host.cpp), without a GPU: equal to the Python reference
+"""azd_dense_inv_cost, the host form of the weighted-invariant cost (dense_cost_host.cpp), without a GPU: equal to the Python reference
 (tests/dense_inv_ref.py) bit for bit -- every field of the record compared as bytes -- on the whole graph set under the four test
 recipes and over a sweep of the spectral indices, and on the hard case set of the spectral passes (tests/dense_spectral_cases.py)
 under an adjacency and a both-spectra recipe; skipped terms; azd_dense_ah_cost as one recipe; and every refusal that needs no

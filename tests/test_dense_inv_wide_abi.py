@@ -1,4 +1,4 @@
-"""The weighted-invariant cost up to 64 vertices without a GPU: azd_dense_inv_cost_wide (c21_host.cpp) equal to the Python reference
+"""The weighted-invariant cost up to 64 vertices without a GPU: azd_dense_inv_cost_wide (dense_cost_host.cpp) equal to the Python reference
 (tests/dense_inv_wide_ref.py) as bytes on the 88 graphs of graph_set_wide() under the four test recipes, to azd_dense_inv_cost as
 bytes on the n <= 32 set, both again on the hard case set of the spectral passes (tests/dense_spectral_cases.py), and under the AH recipe to azd_dense_ah_cost_wide; both spectra against numpy.linalg.eigvalsh within the
 project's backward-error tolerance; the argument checks of the new calls and of AZD_ENGINE_DENSE_INV_WIDE, made before any device

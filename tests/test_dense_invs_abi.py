@@ -1,4 +1,4 @@
-"""azd_dense_invs_cost, the host form of the spectrum invariant cost (c21_host.cpp), without a GPU: equal to the Python reference
+"""azd_dense_invs_cost, the host form of the spectrum invariant cost (dense_cost_host.cpp), without a GPU: equal to the Python reference
 (tests/dense_invs_ref.py) bit for bit -- every field of the record compared as bytes -- on the whole graph set under the five new
 recipes, and on the hard case set of the spectral passes (tests/dense_spectral_cases.py) at n = 21, 23, 31, 32 under the heaviest;
 azd_dense_invs_spectrum equal to the reference's eigenvalues as bits; equal to azd_dense_invx_cost under the converted INVX

@@ -1,4 +1,4 @@
-"""azd_dense_invx_cost, the host form of the extended invariant cost (c21_host.cpp), without a GPU: equal to the Python reference
+"""azd_dense_invx_cost, the host form of the extended invariant cost (dense_cost_host.cpp), without a GPU: equal to the Python reference
 (tests/dense_invx_ref.py) bit for bit -- every field of the record compared as bytes -- on the whole graph set under the nine test
 recipes, and on the hard case set of the spectral passes (tests/dense_spectral_cases.py) under four of them; equal to azd_dense_inv_cost (and, under the AH recipe, azd_dense_ah_cost) under the converted INV recipes; skipped terms;
 and every refusal that needs no device, with its status and the argument or field it names."""

@@ -1,4 +1,4 @@
-"""The extended invariant cost up to 64 vertices without a GPU: azd_dense_invx_cost_wide (c21_host.cpp) equal to the Python reference
+"""The extended invariant cost up to 64 vertices without a GPU: azd_dense_invx_cost_wide (dense_cost_host.cpp) equal to the Python reference
 (tests/dense_invx_wide_ref.py) as bytes on the 88 graphs of graph_set_wide() under the five new recipes and BOTH, to
 azd_dense_invx_cost as bytes on every fifth graph of the n <= 32 set, and under the converted INV recipes to azd_dense_inv_cost_wide;
 the argument checks of the new calls and of AZD_ENGINE_DENSE_INVX_WIDE, made before any device is looked for; the pool plan; the

@@ -1,7 +1,9 @@
 """Every read-back entry of the C ABI on one engine of every tier, at the smallest shapes: which entry serves which tier, which
 refuses it with which status and text, and that the typed Ramsey records and the exported keys have the layout the header gives.
 The tiers: c21; Ramsey narrow, wide (max_slots > 0) and 64-bit (AZD_ENGINE_RAMSEY_U64); the dense-graph space with its default cost,
-with the Aouchiche-Hansen cost (AZD_ENGINE_DENSE_AH) and with that cost's 64-row form (AZD_ENGINE_DENSE_AH_WIDE)."""
+with the Aouchiche-Hansen cost (AZD_ENGINE_DENSE_AH) and with that cost's 64-row form (AZD_ENGINE_DENSE_AH_WIDE).  The six tiers
+of the dense-graph space that take a recipe (AZD_ENGINE_DENSE_INV, _INVX, _INVS, each with its _WIDE form) have a test of their
+own below: every setter, reader and argmin entry on an engine of every one of them, with the whole text of each refusal."""
 import ctypes as C
 
 import numpy as np
@@ -166,3 +168,98 @@ def test_typed_ramsey_entries_refuse_more_edges_than_their_record_holds(n, sizes
     st, _ = call(opt, entry)
     assert st == INVALID and opt._L.azd_last_error().decode() == text
     assert call(opt, "ramsey_argmin_any")[0] == OK
+
+
+# ---------------------------------------------------------------- the recipe tiers of the dense-graph space: every (entry, tier) pair
+FAMILIES = ("inv", "invx", "invs")
+RECIPE_TIERS = tuple((f, w) for f in FAMILIES for w in (False, True))  # (family, wide)
+DENSE_READERS = ("dense", "dense_ah", "dense_ah_wide") + tuple("dense_%s%s" % (f, "_wide" if w else "") for f, w in RECIPE_TIERS)
+
+
+def flag_of(stem):  # "dense_invx_wide" -> "AZD_ENGINE_DENSE_INVX_WIDE"
+    return "AZD_ENGINE_" + stem.upper()
+
+
+def recipe_engine(az, L, stem, n=4, B=1):
+    """an engine made by hand (NablaOptimizer's constructor would set the recipe): (handle, its evaluator, roots)"""
+    from azdopt_amd import _lib
+    flags = {"dense": 0, "dense_ah": _lib.ENGINE_DENSE_AH, "dense_inv": _lib.ENGINE_DENSE_INV, "dense_invx": _lib.ENGINE_DENSE_INVX, "dense_invs": _lib.ENGINE_DENSE_INVS}
+    wide = {"dense_inv_wide": _lib.ENGINE_DENSE_INV_WIDE, "dense_invx_wide": _lib.ENGINE_DENSE_INVX_WIDE, "dense_invs_wide": _lib.ENGINE_DENSE_INVS_WIDE}
+    fl = flags[stem[:-5]] | wide[stem] if stem in wide else flags[stem]
+    space = az.DenseGraphSpace(n, 0.5)
+    model = az.TrivialModel(space.STATE_DIM, space.ACTION_DIM)
+    cfg = _lib.EngineConfig(_lib.SPACE_DENSE, n, B, 0, 0, 0, 0, 0, fl)
+    cfg.max_slots, cfg.dense_p = space.E, space.p
+    h = C.c_void_p()
+    _lib.check(L.azd_engine_create(C.byref(h), C.byref(cfg), model._h), "create")
+    adj, slots = space.generate_roots(0, B, kmin=1, kmax=3)
+    return h, model, (np.ascontiguousarray(adj, np.uint8), np.ascontiguousarray(slots, np.uint64))
+
+
+def test_recipe_tiers_every_setter_reader_and_argmin_entry_says_its_text():
+    """n = 4, one agent.  The texts are the library's, whole: an entry of another cost names the engine's own flag and the entry that
+    serves it; an entry on an engine that takes no recipe says what engine it wants."""
+    import azdopt_amd as az
+    from azdopt_amd import _lib
+    if az.device_count() < 1:
+        pytest.fail("no gfx950 device: the GPU tests need the HIP path")
+    L = az.lib()
+    err = lambda: L.azd_last_error().decode()
+    n = 4
+    w = dict(edges=1.0)
+    recipes = dict(inv=az.InvariantCost(w, eval_scale=0.1).recipe(), invx=az.InvariantCostX(w, eval_scale=0.1).recipe(), invs=az.InvariantCostS(w, eval_scale=0.1).recipe())
+    costs = dict(inv=_lib.DenseInvCost, invx=_lib.DenseInvxCost, invs=_lib.DenseInvsCost)
+    argmins = dict(dense=_lib.DenseArgmin, dense_ah=_lib.DenseAhArgmin, dense_ah_wide=_lib.DenseAhWideArgmin, dense_inv=_lib.DenseInvArgmin,
+                   dense_inv_wide=_lib.DenseInvWideArgmin, dense_invx=_lib.DenseInvxArgmin, dense_invx_wide=_lib.DenseInvxWideArgmin,
+                   dense_invs=_lib.DenseInvsArgmin, dense_invs_wide=_lib.DenseInvsWideArgmin)
+    setter = lambda f: "azd_engine_set_dense_%s_recipe" % f
+    reader = lambda f: "azd_engine_dense_%s_agent_cost" % f
+    for stem in ("dense", "dense_ah") + DENSE_READERS[3:]:
+        h, model, (a8, s64) = recipe_engine(az, L, stem, n)
+        mine = next((f for f in FAMILIES if stem in ("dense_" + f, "dense_" + f + "_wide")), None)  # the engine's family; None: it takes no recipe
+        if mine:
+            assert L.azd_engine_par_new(h, _lib.ptr(a8), _lib.ptr(s64)) == INVALID
+            assert err() == "par_new: an %s engine has no cost before %s has given it its recipe" % (flag_of("dense_" + mine), setter(mine)), stem
+        for f in FAMILIES:
+            st = getattr(L, setter(f))(h, C.byref(recipes[f]))
+            if f == mine:
+                assert st == OK, (stem, f, err())
+            elif mine:
+                assert st == UNSUPPORTED and err() == "%s: an %s engine's recipe is set with %s" % (setter(f), flag_of("dense_" + mine), setter(mine)), (stem, f, err())
+            else:
+                assert st == UNSUPPORTED and err() == "%s: not an %s engine" % (setter(f), flag_of("dense_" + f)), (stem, f, err())
+        assert L.azd_engine_par_new(h, _lib.ptr(a8), _lib.ptr(s64)) == OK, (stem, err())
+        if mine:
+            assert getattr(L, setter(mine))(h, C.byref(recipes[mine])) == INVALID
+            assert err() == setter(mine) + ": par_new has run: the trees' evals were computed with the recipe in force, which stays", stem
+        for f in FAMILIES:
+            c = costs[f]()
+            st = getattr(L, reader(f))(h, 0, C.byref(c))
+            if f == mine:
+                assert st == OK and c.computed == 0xFF and c.cost == c.inv[0] > 0.0 and c.eval == np.float32(0.1) * np.float32(c.cost), (stem, c.cost, c.eval)
+            elif mine:
+                assert st == UNSUPPORTED and err() == "%s: an %s engine's record is read with %s" % (reader(f), flag_of("dense_" + mine), reader(mine)), (stem, f, err())
+            else:
+                assert st == UNSUPPORTED and err() == "%s: not an %s engine" % (reader(f), flag_of("dense_" + f)), (stem, f, err())
+        st = L.azd_engine_dense_ah_agent_cost(h, 0, C.byref(_lib.DenseAhCost()))
+        assert st == (OK if stem == "dense_ah" else UNSUPPORTED), stem
+        lam = C.c_double()
+        st = L.azd_engine_agent_state(h, 0, None, None, None, None, C.byref(lam), None)
+        if mine:
+            assert err() == "azd_engine_agent_state: lambda_1 / matching_size: an %s engine keeps neither (%s)" % (flag_of("dense_" + mine), reader(mine)), stem
+            assert st == UNSUPPORTED
+            assert L.azd_engine_dense_ah_agent_cost(h, 0, C.byref(_lib.DenseAhCost())) == UNSUPPORTED
+            assert err() == "azd_engine_dense_ah_agent_cost: an %s engine's record is read with %s" % (flag_of("dense_" + mine), reader(mine)), stem
+        for entry in DENSE_READERS:
+            st = getattr(L, "azd_engine_%s_argmin_data" % entry)(h, C.byref(argmins[entry]()))
+            if entry == stem:
+                assert st == OK, (stem, entry, err())
+                continue
+            assert st == UNSUPPORTED, (stem, entry)
+            if mine:
+                assert err() == "dense argmin read: an %s engine's record is read with azd_engine_%s_argmin_data" % (flag_of(stem), stem), (stem, entry, err())
+            elif entry == "dense":
+                assert err() == T_DENSE, stem  # (said to an AZD_ENGINE_DENSE_AH engine: the default engine has passed above)
+            elif entry != "dense_ah":  # (that entry refuses the default engine without a text)
+                assert err() == "azd_engine_%s_argmin_data: not an %s engine" % (entry, flag_of(entry)), (stem, entry, err())
+        L.azd_engine_destroy(h)
